@@ -19,6 +19,7 @@ a cohort, weak scaling), reported with that label.
   python bench.py --gpus 1 --steps 8 --warmup 2
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus 1 --steps 8 --warmup 2 --dump-outputs DIR   (the last timed step's outputs as .npy, dump_outputs())
 
 Steps are SUBMITTED to the pool (rsi_pool_submit) and waited for, gathered and turned into rows on a second host thread:
 `config.steps_in_flight` genomes are queued at once (2 for a whole genome on one GPU, as many as fill the pool's workers for
@@ -114,7 +115,11 @@ def main():
                     "share (2 for a whole genome, more for the few chromosomes of one rank among eight, at most 6); 1 = one genome at a time")
     ap.add_argument("--check-rows", choices=("auto", "off"), default="auto",
                     help="auto: a full-size configs[3] / configs[4] genome's rows must hash to what the reference wrote (tests/golden/genome_rows.json)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step handed its caller to DIR/<name>.npy (float64; see dump_outputs())")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # ---- `--gpus N` without a launcher: this process -- before torch is imported or a GPU touched -- starts the N ranks itself
     # (one process per GPU, torch.distributed.run on 127.0.0.1), relays rank 0's line and exits with the launcher's code.  A
@@ -234,6 +239,7 @@ def main():
     post_q = queue.Queue()
     post_err = []
     last_rows = [0]
+    last_outputs = [None]   # --dump-outputs: (this rank's results, the gathered summaries) of the latest timed step on rank 0
     if args.inflight <= 0:   # enough queued genomes that every worker has a chromosome of this rank's share
         args.inflight = max(2, min(6, (args.workers + max(1, len(mine)) - 1) // max(1, len(mine))))
     slots = threading.Semaphore(max(1, args.inflight))
@@ -284,6 +290,8 @@ def main():
         merged = rd.unpack_blocks(blocks)
         if len(merged) != (len(plans) if sharded else world * len(plans)):
             raise RuntimeError(f"gather returned {len(merged)} chromosomes of {len(plans)} x {1 if sharded else world}")
+        if timed and args.dump_outputs:
+            last_outputs[0] = (results, merged)
         rows = rd.format_rows(lib, merged, names if sharded else [names[c % len(plans)] for c in range(world * len(plans))])
         if timed:   # a step whose rows differ from another step's is a wrong step: every timed step is hashed
             h = hashlib.sha256()
@@ -329,6 +337,7 @@ def main():
     fence()                                   # joins the second thread: all K steps' rows exist
     elapsed = time.perf_counter() - t_start
     ncalls = last_rows[0]
+    headline_outputs = last_outputs[0]        # the K-th timed step's (later passes overwrite last_outputs)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=coll_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -507,6 +516,9 @@ def main():
         }
         if side:
             out.update(side)
+        if args.dump_outputs:
+            results, merged = headline_outputs
+            out["outputs_dumped"] = dump_outputs(args.dump_outputs, results, merged, [i + id_offset for i in mine])
         print(json.dumps(out), flush=True)
     drain()
     post_q.put(None)
@@ -519,6 +531,44 @@ def main():
                if ok is False]
         if bad:
             raise SystemExit(f"bench.py: rows differ from the reference's for: {', '.join(bad)}")
+
+
+DUMP_MAX_BYTES = 64 << 20
+# rsi_chrom_stats fields that say how a run went, not what it computed: left out of chrom_stats.npy
+DUMP_STATS_SKIPPED = ("t_device_ms", "t_kernels_ms", "scan_tiles", "scan_tiles_listed")
+
+
+def dump_outputs(path, results, merged, chrom_ids):
+    """--dump-outputs: what one timed step handed its caller on rank 0, as float64 DIR/<name>.npy (inputs are seeded, so two
+    builds given the same arguments can be compared file for file):
+      summary      [chromosomes of the genome, rsi_result_summary block]: the gathered blocks the rows are formatted from,
+                   in chromosome order
+      calls, calls_raw, segs, blocks
+                   [rows, 1 + 15]: chromosome id, then api.CALL_FIELDS, of each of this rank's chromosomes' lists
+      noncode      [rows, 3]: chromosome id, begin, end of the padded N regions
+      chrom_stats  [this rank's chromosomes, 1 + k]: chromosome id, then the rsi_chrom_stats fields not in DUMP_STATS_SKIPPED
+    An array over its share of DUMP_MAX_BYTES is cut to a fixed, seeded sample of its rows.  Returns {name: shape written}."""
+    import numpy as np
+    from rsicnv_amd import api
+    out = {"summary": np.stack([merged[c]["block"] for c in sorted(merged)])}
+    for which in api.WHICH:
+        rows = [[cid] + [c[f] for f in api.CALL_FIELDS] for cid, r in zip(chrom_ids, results) for c in r.calls(which)]
+        out[which] = np.array(rows, dtype=np.float64).reshape(-1, 1 + len(api.CALL_FIELDS))
+    out["noncode"] = np.array([[cid, b, e] for cid, r in zip(chrom_ids, results) for b, e in r.noncode.reshape(-1, 2)],
+                              dtype=np.float64).reshape(-1, 3)
+    fields = [f[0] for f in api.RsiChromStats._fields_ if f[0] not in DUMP_STATS_SKIPPED]
+    out["chrom_stats"] = np.array([[cid] + [r.stats[k] for k in fields] for cid, r in zip(chrom_ids, results)],
+                                  dtype=np.float64).reshape(-1, 1 + len(fields))
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_MAX_BYTES // len(out)
+    written = {}
+    for name, a in out.items():
+        if a.nbytes > share:
+            keep = share // (a.itemsize * a.shape[1])
+            a = a[np.sort(np.random.default_rng(0x5A3D1E).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+        written[name] = list(a.shape)
+    return written
 
 
 def side_measurements(lib, pool, dev, args):

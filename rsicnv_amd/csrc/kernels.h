@@ -160,6 +160,17 @@ struct BinAccum {
 // entries travel in `inl` with the kernel arguments (cbreak / cum may then be NULL).
 constexpr int kRegInline = 48;
 struct K4Regions { long long brk[kRegInline]; long long cum[kRegInline + 1]; };
+// The arguments of the K4 launchers below (pipeline.hip fills them once per launch site; each form reads its own).  src: the depth as
+// int32 (what K4 / K4w compact, what the byte forms recompute edge tiles from); src8: the byte forms' input, K2 / K2j's copy of the
+// raw depth (K4j, K4s) or the histogram pass' copy (K4', RAW K4s); rdc8 / rdc: the output as bytes / as int32; acc: K4 only;
+// gsum: K4, K4', K4j; rtab, escapes, pp: see K4j and K4s; vbase: K4 / K4w; raw: K4' on the raw depth (-NOGC).
+struct K4Args {
+  const int32_t* src; const uint8_t* src8; const uint64_t* gcbits; int64_t n; const double* table;
+  const int64_t* cbreak; const int64_t* cum; const K4Regions* inl; int nreg; int64_t ncompact; int32_t capval; int m;
+  uint8_t* rdc8; int32_t* rdc; int32_t* binmed; int64_t* binsum; uint32_t* res_hist; BinAccum* acc;
+  void* slabs; void* gsum; unsigned int* counters; const void* exp_src; void* exp_dst; size_t exp_bytes;
+  const unsigned int* rtab; const unsigned int* escapes; PhaseParams* pp; int vbase; int raw; hipStream_t stream;
+};
 size_t cap_compact_slab_bytes(int m, int32_t capval, int64_t ncompact, int vbase);
 int cap_compact_overwrites(int m, int32_t capval, int64_t ncompact, int vbase);
 // First value of the window the LDS histograms of the int32 kernels cover: 0 unless the distribution's centre (mean / median
@@ -167,41 +178,31 @@ int cap_compact_overwrites(int m, int32_t capval, int64_t ncompact, int vbase);
 // exactly.  K3 derives its window on the device (1024 values); K4's (kK4Window = 512 values) comes from the host.
 constexpr int kK4Window = 512;
 int hist_window_base(double center, int width);
-void launch_cap_compact_bin(const int32_t* src, int64_t n, const int64_t* cbreak, const int64_t* cum, const K4Regions& inl, int nreg,
-                            int64_t ncompact, int32_t capval, int m, int32_t* rdc, int32_t* binmed, int64_t* binsum,
-                            uint32_t* res_hist, BinAccum* acc, void* slabs, void* gsum, unsigned int* counters,
-                            const void* exp_src, void* exp_dst, size_t exp_bytes, int vbase /* hist_window_base(cap median), or 0 */,
-                            hipStream_t stream);
+void launch_cap_compact_bin(const K4Args& a);
 
 // K4w: the same for caps of 254 .. 32766 (deep coverage): int32 in, 16-bit tile and 16-bit window counters in LDS, int32 out.
 // res_hist must be zero before the launch (the window's sums and the stray values are added to it); vbase as for K4.
 int cap_compact16_applies(int m, int32_t capval, int64_t ncompact);
 size_t cap_compact16_slab_bytes(int m, int64_t ncompact);
-void launch_cap_compact_bin16(const int32_t* src, const int64_t* cbreak, const int64_t* cum, const K4Regions& inl, int nreg, int64_t ncompact,
-                              int32_t capval, int m, int32_t* rdc, int32_t* binmed, int64_t* binsum, uint32_t* res_hist, void* slabs,
-                              unsigned int* counters, const void* exp_src, void* exp_dst, size_t exp_bytes, int vbase, hipStream_t stream);
+void launch_cap_compact_bin16(const K4Args& a);
 
-// K4 fed from K3''s byte copy of the rescaled depth (rescaled8): the rescaled int32 array is never needed.  Applies when
-// cap_compact8_applies(): 1 <= capval < kByteSat (every capped value fits a byte, res_hist is overwritten) and m <= 104.
-// depth / gcbits / table (K2's [kGcLevels] level means + the mean of the positive depths): for the tiles at the chromosome's
-// ends and across removed regions, which recompute the rescale per element.
+// K4' fed from K3''s byte copy of the rescaled depth (src8): the rescaled int32 array is never needed.  Applies when
+// cap_compact8_applies(): 1 <= capval < kByteSat (every capped value fits a byte, res_hist is overwritten) and m <= 440.
+// src / gcbits / table: for the tiles at the chromosome's ends and across removed regions, which recompute the rescale per
+// element.  rdc8: ncompact + 64 bytes.
 int cap_compact8_applies(int m, int32_t capval);
 size_t cap_compact8_slab_bytes(int m, int32_t capval, int64_t ncompact);
-void launch_cap_compact_bin8(const uint8_t* rescaled8, const int32_t* depth, const uint64_t* gcbits, int64_t n, const double* table,
-                             const int64_t* cbreak, const int64_t* cum, const K4Regions& inl, int nreg, int64_t ncompact, int32_t capval,
-                             int m, uint8_t* rdc8 /* ncompact + 64 bytes: the capped, compacted depth as bytes */, int32_t* binmed, int64_t* binsum,
-                             uint32_t* res_hist, void* slabs, void* gsum,
-                             unsigned int* counters, const void* exp_src, void* exp_dst, size_t exp_bytes, hipStream_t stream, int raw = 0);
+// The byte forms' shape under a cap (K4', K4j, K4s, K4m): the value range of the LDS histogram (64, 128 or 256 values, covering
+// the cap) and the median phase's packing (SW7: four values to a register up to a cap of 127).
+struct ByteShape { int vr; bool sw7; bool operator==(const ByteShape& o) const { return vr == o.vr && sw7 == o.sw7; } };
+inline ByteShape byte_shape(int32_t capval) { int vr = 64; while (vr < 256 && vr <= capval) vr <<= 1; return {vr, capval <= 127}; }
+void launch_cap_compact_bin8(const K4Args& a);
 
 // K4j: K4' fed from the byte copy of the RAW depth (K2 / K2j's depth8), rescaling on the way with the GC table -- same outputs.
-void launch_rescale_compact_bin8(const uint8_t* depth8, const int32_t* depth, const uint64_t* gcbits, int64_t n, const double* table,
-                                 const int64_t* cbreak, const int64_t* cum, const K4Regions& inl, int nreg, int64_t ncompact, int32_t capval,
-                                 int m, uint8_t* rdc8, int32_t* binmed, int64_t* binsum, uint32_t* res_hist, void* slabs, void* gsum,
-                                 unsigned int* counters, const void* exp_src, void* exp_dst, size_t exp_bytes,
-                                 const unsigned int* rtab /* K2j's fixed-point ratios, or NULL: the float form with its exactness margin */,
-                                 PhaseParams* pp /* NULL, or: nreg / ncompact / capval are read from it on the device (cbreak / cum from device
-                                                    memory); the arguments of those names only shape the launch (capval: a guess, checked) */,
-                                 hipStream_t stream);
+// rtab: K2j's fixed-point ratios, or NULL: the float form with its exactness margin.  pp: NULL, or nreg / ncompact / capval are
+// read from it on the device (cbreak / cum from device memory); the arguments of those names only shape the launch (capval: a
+// guess, checked).
+void launch_rescale_compact_bin8(const K4Args& a);
 
 // K4 as two launches (kernels_k4s.hip): K4s -- rescale, cap, compaction, byte store, residue-class histogram, wave-autonomous at
 // eight waves per SIMD, fixed point in the loop, the chunks it cannot do that way (region cuts, chromosome ends, escape bytes, GC
@@ -212,12 +213,34 @@ void launch_rescale_compact_bin8(const uint8_t* depth8, const int32_t* depth, co
 int rescale_compact_split_applies(int m, int32_t capval, int64_t ncompact, int nreg);
 size_t rescale_compact_split_slab_bytes(int32_t capval, int64_t ncompact);
 size_t rescale_compact_split_rdc_bytes(int64_t ncompact);
-void launch_rescale_compact_stream(const uint8_t* depth8, const int32_t* depth, const uint64_t* gcbits, int64_t n, const double* table,
-                                   const int64_t* cbreak, const int64_t* cum, const K4Regions& inl, int nreg, int64_t ncompact, int32_t capval,
-                                   int m, uint8_t* rdc8, uint32_t* res_hist, void* slabs, unsigned int* counters, const void* exp_src, void* exp_dst,
-                                   size_t exp_bytes, const unsigned int* rtab, const unsigned int* escapes, PhaseParams* pp, hipStream_t stream);
-void launch_bin_median8(const uint8_t* rdc8, int64_t ncompact, int32_t capval, int m, int32_t* binmed, int64_t* binsum, const PhaseParams* pp,
-                        hipStream_t stream);
+void launch_rescale_compact_stream(const K4Args& a);
+void launch_bin_median8(const K4Args& a);
+
+// ---- which K4 form a chromosome takes ----
+// The per-base phase's A/B switches (RSI_HOT_<NAME>=0 turns each off, RSI_HOT_K1B_INSIDE=1 turns that one on), read once per run.
+struct PerBaseSwitches {
+  bool joint;        // K2j (RSI_HOT_JOINT); off: the three-pass chain K2, K3', K4'
+  bool spec;         // K4 queued behind K2j / the -NOGC histogram pass (RSI_HOT_SPEC)
+  bool k4j_fix;      // K2j's verified fixed-point ratios (RSI_HOT_K4J_FIX); off: K4j's float form
+  bool k4split;      // K4s + K4m where they apply (RSI_HOT_K4SPLIT); off: K4j
+  bool nogc_bytes;   // -NOGC on bytes (RSI_HOT_NOGC_BYTES); off: the int32 kernels
+  bool k4w;          // K4w for caps of 254 .. 32766 (RSI_HOT_K4W); off: the int32 K4
+  bool k1b_inside;   // K1b inside K2j's launch (RSI_HOT_K1B_INSIDE)
+};
+// stream: K4s + K4m; joint: K4j; bytes: K4'; wide16: K4w; int32: K4
+enum class K4Route { stream, joint, bytes, wide16, int32 };
+struct K4Plan {
+  K4Route route;
+  bool fixed;            // K4s / K4j rescale with K2j's verified fixed-point ratios (K4j without them: the float form)
+  bool raw;              // -NOGC: the bytes are the values (K4s in RAW mode, K4' with raw = 1)
+  bool bytes_fit;        // a cap under which every value fits a byte (cap_compact8_applies), whatever the route
+  ByteShape shape;       // byte_shape(capval)
+  const char* marks[2];  // the route's phase markers (rsi_hot_phase_times), NULL where none
+};
+// The route for what the host knows after the cap: capped = a cap applies; deep: the rescale went through the int32 kernel;
+// joint_ok: K2j ran to the end and its ratios verified.  The queued launch asks with its guessed cap, ncompact = n and nreg = 0.
+K4Plan k4_plan(bool gcadjust, bool capped, int32_t capval, int m, int64_t ncompact, int nreg, bool deep, bool joint_ok,
+               const PerBaseSwitches& sw);
 
 // ---- K5: NB variance-stabilising transform (negative_binomial_transfer, rsi.cpp:1155-1185) ----
 // raw[b] = (float)(2 sqrt(r) log(sqrt(q) + sqrt(1+q))), q = (sum+0.25)/(m2*r-0.5); *rawmin_bits =

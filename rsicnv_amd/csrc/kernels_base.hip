@@ -2827,8 +2827,7 @@ void launch_value_hist8(const uint8_t* depth8, const int32_t* depth, const uint6
 static void k4_geometry(int m, int32_t capval, int64_t ncompact, int vbase, int& TB, int& vr, int& grid) {
   TB = 64;   // bins per tile: as many as fit ~48 KB of values, 4..64, power of two
   while (TB > 4 && (size_t)TB * m * 4 > 48 * 1024) TB >>= 1;
-  vr = 64;   // LDS histogram range: covers the capped values when the cap is active, 64..256
-  while (vr < 256 && vr <= capval) vr <<= 1;
+  vr = byte_shape(capval).vr;   // LDS histogram range: covers the capped values when the cap is active, 64..256
   if (vbase > 0) vr = kK4Window;   // deep coverage: a window of 512 values around the median (64 KB of LDS, one workgroup per CU)
   const int64_t ntiles = (ncompact + (int64_t)TB * m - 1) / ((int64_t)TB * m);
   grid = (int)(ntiles < 256 * 3 ? (ntiles < 1 ? 1 : ntiles) : 256 * 3);
@@ -2847,8 +2846,7 @@ int cap_compact8_applies(int m, int32_t capval) { return capval >= 1 && capval <
 // above m = 104 through the int32 kernels (-m 201: 299 us of K3 + K4 per 60 Mb against 109).
 static int k48_bins_per_tile(int m) { return m <= 52 ? 128 : (m <= 104 ? 64 : (m <= 216 ? 32 : 16)); }
 static void k48_geometry(int m, int32_t capval, int64_t ncompact, int& vr, int& grid, int& maxc) {
-  vr = 64;
-  while (vr < 256 && vr <= capval) vr <<= 1;
+  vr = byte_shape(capval).vr;
   const int64_t tile = (int64_t)k48_bins_per_tile(m) * m;
   const int64_t ntiles = (ncompact + tile - 1) / tile;
   grid = (int)(ntiles < 256 * 4 ? (ntiles < 1 ? 1 : ntiles) : 256 * 4);   // 3, 5 or 6 per CU: 2-5 % slower
@@ -2859,47 +2857,38 @@ size_t cap_compact8_slab_bytes(int m, int32_t capval, int64_t ncompact) {
   k48_geometry(m, capval, ncompact, vr, grid, maxc);
   return (size_t)grid * vr * kResClasses * 4;
 }
-void launch_cap_compact_bin8(const uint8_t* depth8, const int32_t* depth, const uint64_t* gcbits, int64_t n, const double* table,
-                             const int64_t* cbreak, const int64_t* cum, const K4Regions& inl, int nreg, int64_t ncompact, int32_t capval,
-                             int m, uint8_t* rdc, int32_t* binmed, int64_t* binsum, uint32_t* res_hist, void* slabs, void* gsum,
-                             unsigned int* counters, const void* exp_src, void* exp_dst, size_t exp_bytes, hipStream_t stream, int raw) {
+void launch_cap_compact_bin8(const K4Args& a) {
   int vr, grid, maxc;
-  k48_geometry(m, capval, ncompact, vr, grid, maxc);
-  const int TB = k48_bins_per_tile(m);
+  k48_geometry(a.m, a.capval, a.ncompact, vr, grid, maxc);
+  const int TB = k48_bins_per_tile(a.m);
   const size_t lds = (size_t)maxc * kThreads * 16 + (size_t)vr * kResClasses * 4;
-  unsigned int* sl = static_cast<unsigned int*>(slabs);
-  unsigned int* gs = static_cast<unsigned int*>(gsum);
+  unsigned int* sl = static_cast<unsigned int*>(a.slabs);
+  unsigned int* gs = static_cast<unsigned int*>(a.gsum);
   const int pg = fold_per_group_add(grid);
-  const int ept = (m + 3) / 4;
-#define RSI_K48(MC, EP, SW) do { RSI_ALLOW_FULL_LDS((k_cap_compact_bin8<MC, EP, SW>));                                                  \
-    RSI_LAUNCH((k_cap_compact_bin8<MC, EP, SW>), dim3(grid), dim3(kThreads), lds, stream, depth8, depth, gcbits, n, n / 64 + 1, table, \
-                       cbreak, cum, nreg, ncompact, capval, m, TB, vr, rdc, binmed, binsum, res_hist, sl, gs, pg, counters,            \
-                       exp_src, exp_dst, (unsigned int)exp_bytes, inl, raw); } while (0)
-  const bool sw7 = capval <= 127;   // four values to a register in the median phase (k_cap_compact_bin8, SW7)
-  (void)ept;
+#define RSI_K48(MC, EP, SW) do { RSI_ALLOW_FULL_LDS((k_cap_compact_bin8<MC, EP, SW>));                                                        \
+    RSI_LAUNCH((k_cap_compact_bin8<MC, EP, SW>), dim3(grid), dim3(kThreads), lds, a.stream, a.src8, a.src, a.gcbits, a.n, a.n / 64 + 1, a.table, \
+                       a.cbreak, a.cum, a.nreg, a.ncompact, a.capval, a.m, TB, vr, a.rdc8, a.binmed, a.binsum, a.res_hist, sl, gs, pg,       \
+                       a.counters, a.exp_src, a.exp_dst, (unsigned int)a.exp_bytes, *a.inl, a.raw); } while (0)
+  const bool sw7 = byte_shape(a.capval).sw7;   // four values to a register in the median phase (k_cap_compact_bin8, SW7)
   if (sw7) { if (maxc == 1) RSI_K48(1, 1, true); else RSI_K48(2, 1, true); }
   else { if (maxc == 1) RSI_K48(1, 0, false); else RSI_K48(2, 0, false); }   // caps of 128 .. 253: two values to a register (EPT = 0)
 #undef RSI_K48
 }
 // K4j: the same from K2j's byte copy of the RAW depth, rescaling on the way (no K3' in front)
-void launch_rescale_compact_bin8(const uint8_t* depth8, const int32_t* depth, const uint64_t* gcbits, int64_t n, const double* table,
-                                 const int64_t* cbreak, const int64_t* cum, const K4Regions& inl, int nreg, int64_t ncompact, int32_t capval,
-                                 int m, uint8_t* rdc, int32_t* binmed, int64_t* binsum, uint32_t* res_hist, void* slabs, void* gsum,
-                                 unsigned int* counters, const void* exp_src, void* exp_dst, size_t exp_bytes, const unsigned int* rtab,
-                                 PhaseParams* pp, hipStream_t stream) {
+void launch_rescale_compact_bin8(const K4Args& a) {
   int vr, grid, maxc;
-  k48_geometry(m, capval, ncompact, vr, grid, maxc);   // pp != NULL: capval is the caller's guess (it fixes vr and SW7), ncompact an upper bound
-  const int TB = k48_bins_per_tile(m);
+  k48_geometry(a.m, a.capval, a.ncompact, vr, grid, maxc);   // pp != NULL: capval is the caller's guess (it fixes vr and SW7), ncompact an upper bound
+  const int TB = k48_bins_per_tile(a.m);
   const size_t lds = (size_t)maxc * kThreads * 16 + (size_t)vr * (vr <= 128 ? kK4jCols : kResClasses) * 4;
-  unsigned int* sl = static_cast<unsigned int*>(slabs);
-  unsigned int* gs = static_cast<unsigned int*>(gsum);
+  unsigned int* sl = static_cast<unsigned int*>(a.slabs);
+  unsigned int* gs = static_cast<unsigned int*>(a.gsum);
   const int pg = fold_per_group_add(grid);
-#define RSI_K48J(MC, EP, SW, FX) do { RSI_ALLOW_FULL_LDS((k_rescale_compact_bin8<MC, EP, SW, FX>));                                      \
-    RSI_LAUNCH((k_rescale_compact_bin8<MC, EP, SW, FX>), dim3(grid), dim3(kThreads), lds, stream, depth8, depth, gcbits, n, n / 64 + 1, table, \
-               cbreak, cum, nreg, ncompact, capval, m, TB, vr, rdc, binmed, binsum, res_hist, sl, gs, pg, counters,            \
-               exp_src, exp_dst, (unsigned int)exp_bytes, inl, rtab, pp); } while (0)
-  const bool sw7 = capval <= 127;   // four values to a register in the median phase (SW7)
-  const bool fix = rtab != nullptr;   // the caller hands the ratios over only when K2j verified them (pipeline.hip)
+#define RSI_K48J(MC, EP, SW, FX) do { RSI_ALLOW_FULL_LDS((k_rescale_compact_bin8<MC, EP, SW, FX>));                                               \
+    RSI_LAUNCH((k_rescale_compact_bin8<MC, EP, SW, FX>), dim3(grid), dim3(kThreads), lds, a.stream, a.src8, a.src, a.gcbits, a.n, a.n / 64 + 1, \
+               a.table, a.cbreak, a.cum, a.nreg, a.ncompact, a.capval, a.m, TB, vr, a.rdc8, a.binmed, a.binsum, a.res_hist, sl, gs, pg,        \
+               a.counters, a.exp_src, a.exp_dst, (unsigned int)a.exp_bytes, *a.inl, a.rtab, a.pp); } while (0)
+  const bool sw7 = byte_shape(a.capval).sw7;   // four values to a register in the median phase (SW7)
+  const bool fix = a.rtab != nullptr;   // the caller hands the ratios over only when K2j verified them (pipeline.hip)
   if (fix) {
     if (sw7) { if (maxc == 1) RSI_K48J(1, 1, true, true); else RSI_K48J(2, 1, true, true); }
     else { if (maxc == 1) RSI_K48J(1, 0, false, true); else RSI_K48J(2, 0, false, true); }
@@ -2930,17 +2919,16 @@ size_t cap_compact16_slab_bytes(int m, int64_t ncompact) {
   k416_geometry(m, ncompact, grid, maxc);
   return (size_t)grid * kK4Window * kResClasses * 4;
 }
-void launch_cap_compact_bin16(const int32_t* src, const int64_t* cbreak, const int64_t* cum, const K4Regions& inl, int nreg, int64_t ncompact,
-                              int32_t capval, int m, int32_t* rdc, int32_t* binmed, int64_t* binsum, uint32_t* res_hist, void* slabs,
-                              unsigned int* counters, const void* exp_src, void* exp_dst, size_t exp_bytes, int vbase, hipStream_t stream) {
+void launch_cap_compact_bin16(const K4Args& a) {
   int grid, maxc;
-  k416_geometry(m, ncompact, grid, maxc);
-  const int TB = k48_bins_per_tile(m);
+  k416_geometry(a.m, a.ncompact, grid, maxc);
+  const int TB = k48_bins_per_tile(a.m);
   const size_t lds = (size_t)maxc * kThreads * 32 + (size_t)kK4Window * kResClasses * 2;
   const int pg = fold_per_group_add(grid);
-#define RSI_K416(MC) do { RSI_ALLOW_FULL_LDS((k_cap_compact_bin16<MC>));                                                         \
-    RSI_LAUNCH((k_cap_compact_bin16<MC>), dim3(grid), dim3(kThreads), lds, stream, src, cbreak, cum, nreg, ncompact, capval, m, TB, vbase, \
-               rdc, binmed, binsum, res_hist, static_cast<unsigned int*>(slabs), pg, counters, exp_src, exp_dst, (unsigned int)exp_bytes, inl); } while (0)
+#define RSI_K416(MC) do { RSI_ALLOW_FULL_LDS((k_cap_compact_bin16<MC>));                                                                          \
+    RSI_LAUNCH((k_cap_compact_bin16<MC>), dim3(grid), dim3(kThreads), lds, a.stream, a.src, a.cbreak, a.cum, a.nreg, a.ncompact, a.capval, a.m, TB, \
+               a.vbase, a.rdc, a.binmed, a.binsum, a.res_hist, static_cast<unsigned int*>(a.slabs), pg, a.counters, a.exp_src, a.exp_dst,        \
+               (unsigned int)a.exp_bytes, *a.inl); } while (0)
   if (maxc == 1) RSI_K416(1); else RSI_K416(2);
 #undef RSI_K416
 }
@@ -2955,32 +2943,55 @@ int cap_compact_overwrites(int m, int32_t capval, int64_t ncompact, int vbase) {
   k4_geometry(m, capval, ncompact, vbase, TB, vr, grid);
   return vbase == 0 && capval < vr ? 1 : 0;
 }
-void launch_cap_compact_bin(const int32_t* src, int64_t n, const int64_t* cbreak, const int64_t* cum, const K4Regions& inl, int nreg,
-                            int64_t ncompact, int32_t capval, int m, int32_t* rdc, int32_t* binmed, int64_t* binsum,
-                            uint32_t* res_hist, BinAccum* acc, void* slabs, void* gsum, unsigned int* counters,
-                            const void* exp_src, void* exp_dst, size_t exp_bytes, int vbase, hipStream_t stream) {
+void launch_cap_compact_bin(const K4Args& a) {
   int TB, vr, grid;
-  k4_geometry(m, capval, ncompact, vbase, TB, vr, grid);
-  const size_t tile_pad = ((size_t)TB * m + 3) & ~(size_t)3;
+  k4_geometry(a.m, a.capval, a.ncompact, a.vbase, TB, vr, grid);
+  const size_t tile_pad = ((size_t)TB * a.m + 3) & ~(size_t)3;
   // deep coverage (a window that follows the depth): 16-bit LDS counters while a workgroup's share cannot make one wrap
-  const int pack16 = vbase > 0 && (ncompact + grid - 1) / grid < (int64_t)60000 * 31 ? 1 : 0;   // (margin: a class gets at most one value more per tile)
+  const int pack16 = a.vbase > 0 && (a.ncompact + grid - 1) / grid < (int64_t)60000 * 31 ? 1 : 0;   // (margin: a class gets at most one value more per tile)
   const size_t lds = tile_pad * 4 + (size_t)vr * kResClasses * (pack16 ? 2 : 4);
   const int quads = (int)(tile_pad / 4);
   const int maxv = (quads + kThreads - 1) / kThreads;          // 16-byte loads per thread and tile
-  const int parts = kThreads / TB, ept = (m + parts - 1) / parts;   // values per thread in the median phase
-  unsigned int* sl = static_cast<unsigned int*>(slabs);
-  unsigned int* gs = static_cast<unsigned int*>(gsum);
+  const int parts = kThreads / TB, ept = (a.m + parts - 1) / parts;   // values per thread in the median phase
+  unsigned int* sl = static_cast<unsigned int*>(a.slabs);
+  unsigned int* gs = static_cast<unsigned int*>(a.gsum);
   const int pg = fold_per_group(grid);
-  const int overwrite = vbase == 0 && capval < vr ? 1 : 0;
+  const int overwrite = a.vbase == 0 && a.capval < vr ? 1 : 0;
 #define RSI_K4(MV, EP) do { RSI_ALLOW_FULL_LDS((k_cap_compact_bin<MV, EP>));                                                            \
-    RSI_LAUNCH((k_cap_compact_bin<MV, EP>), dim3(grid), dim3(kThreads), lds, stream, src, n, cbreak, cum, nreg,                \
-                       ncompact, capval, m, TB, vr, vbase, rdc, binmed, binsum, res_hist, acc, sl, gs, pg, counters, overwrite,              \
-                       exp_src, exp_dst, (unsigned int)exp_bytes, inl, pack16); } while (0)
+    RSI_LAUNCH((k_cap_compact_bin<MV, EP>), dim3(grid), dim3(kThreads), lds, a.stream, a.src, a.n, a.cbreak, a.cum, a.nreg,          \
+                       a.ncompact, a.capval, a.m, TB, vr, a.vbase, a.rdc, a.binmed, a.binsum, a.res_hist, a.acc, sl, gs, pg, a.counters, \
+                       overwrite, a.exp_src, a.exp_dst, (unsigned int)a.exp_bytes, *a.inl, pack16); } while (0)
   if (maxv <= 4 && ept <= 13) RSI_K4(4, 13);          // m <= 52 (e.g. -m 51)
   else if (maxv <= 8 && ept <= 26) RSI_K4(8, 26);     // m <= 104 (e.g. the default -m 101)
   else if (ept <= 52) RSI_K4(13, 52);                 // m <= 191 with 4 threads per bin, or fewer bins per tile
   else RSI_K4(13, 0);
 #undef RSI_K4
+}
+
+// Byte forms where the cap keeps every value in a byte: under GC correction from K2 / K2j's copy of the raw depth (K4s + K4m with K2j's
+// verified ratios where they apply, else K4j; K4j's float form for a chromosome from the three-pass chain; RSI_HOT_JOINT=0: K4' from
+// K3''s rescaled bytes), under -NOGC from the histogram pass' copy (K4s in RAW mode, else K4' raw).  Otherwise the int32 kernels on
+// the rescaled or raw int32 array: K4w for caps of 254 .. 32766, K4 for the rest.
+K4Plan k4_plan(bool gcadjust, bool capped, int32_t capval, int m, int64_t ncompact, int nreg, bool deep, bool joint_ok,
+               const PerBaseSwitches& sw) {
+  K4Plan p{K4Route::int32, false, false, capped && cap_compact8_applies(m, capval) != 0, byte_shape(capval), {nullptr, nullptr}};
+  const bool split = sw.k4split && rescale_compact_split_applies(m, capval, ncompact, nreg);
+  if (gcadjust && p.bytes_fit && !deep) {
+    p.fixed = joint_ok && sw.k4j_fix;
+    if (!joint_ok && !sw.joint) p.route = K4Route::bytes;
+    else if (!p.fixed) { p.route = K4Route::joint; p.marks[0] = "k4j.float rescale"; }
+    else if (split) { p.route = K4Route::stream; p.marks[0] = "k4.split"; }
+    else p.route = K4Route::joint;
+  } else if (!gcadjust && p.bytes_fit && sw.nogc_bytes) {
+    p.raw = true;
+    p.marks[0] = "a5.nogc byte path";
+    if (split) { p.route = K4Route::stream; p.marks[1] = "k4.split"; }
+    else p.route = K4Route::bytes;
+  } else if (capped && sw.k4w && cap_compact16_applies(m, capval, ncompact)) {
+    p.route = K4Route::wide16;
+    p.marks[0] = "a5.k4w 16-bit tile";
+  }
+  return p;
 }
 
 }  // namespace rsik

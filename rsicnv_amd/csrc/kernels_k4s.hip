@@ -596,11 +596,6 @@ __global__ __launch_bounds__(kM4Threads, SW7 ? 8 : 6) void k_bin_median8(
   }
 }
 
-static int k4s_vr(int32_t capval) {
-  int vr = 64;
-  while (vr < 256 && vr <= capval) vr <<= 1;
-  return vr;
-}
 static int k4s_grid(int64_t ncompact) {
   const int64_t nsub = (ncompact + kS4Sub - 1) / kS4Sub;
   int64_t g = (nsub + kS4Waves - 1) / kS4Waves;
@@ -626,40 +621,39 @@ int rescale_compact_split_applies(int m, int32_t capval, int64_t ncompact, int n
   return (nsub + stride - 1) / stride <= kS4MaxTrips ? 1 : 0;
 }
 size_t rescale_compact_split_slab_bytes(int32_t capval, int64_t ncompact) {
-  return (size_t)k4s_grid(ncompact) * k4s_vr(capval) * (kResClasses / 2) * 4;   // packed: two classes per word
+  return (size_t)k4s_grid(ncompact) * byte_shape(capval).vr * (kResClasses / 2) * 4;   // packed: two classes per word
 }
 size_t rescale_compact_split_rdc_bytes(int64_t ncompact) { return (size_t)(((ncompact + kS4Sub - 1) / kS4Sub + 1) * kS4Sub + 64); }
 
-void launch_rescale_compact_stream(const uint8_t* depth8, const int32_t* depth, const uint64_t* gcbits, int64_t n, const double* table,
-                                   const int64_t* cbreak, const int64_t* cum, const K4Regions& inl, int nreg, int64_t ncompact, int32_t capval,
-                                   int m, uint8_t* rdc, uint32_t* res_hist, void* slabs, unsigned int* counters, const void* exp_src, void* exp_dst,
-                                   size_t exp_bytes, const unsigned int* rtab, const unsigned int* escapes, PhaseParams* pp, hipStream_t stream) {
-  const int vr = k4s_vr(capval);   // pp != NULL: capval is the caller's guess (it fixes vr and SW7), ncompact an upper bound
-  const int grid = k4s_grid(ncompact);
+void launch_rescale_compact_stream(const K4Args& a) {
+  const ByteShape sh = byte_shape(a.capval);   // pp != NULL: capval is the caller's guess (it fixes vr and SW7), ncompact an upper bound
+  const int vr = sh.vr;
+  const int grid = k4s_grid(a.ncompact);
   const size_t lds = (size_t)vr * (vr <= 128 ? kS4Cols : kResClasses) * 4;
-  unsigned int* sl = static_cast<unsigned int*>(slabs);
+  unsigned int* sl = static_cast<unsigned int*>(a.slabs);
   const int pg = fold_per_group_add(grid);
-  const bool sw7 = capval <= 127;
-#define RSI_K4S(C64, RW) do { RSI_ALLOW_FULL_LDS((k_rescale_compact_stream<C64, RW>));                                                                   \
-    RSI_LAUNCH((k_rescale_compact_stream<C64, RW>), dim3(grid), dim3(kS4Threads), lds, stream, depth8, depth, gcbits, n, n / 64 + 1, table, cbreak, cum, \
-               nreg, ncompact, capval, m, vr, sw7 ? 1 : 0, rdc, res_hist, sl, pg, counters, exp_src, exp_dst, (unsigned int)exp_bytes, inl, rtab, escapes, pp); } while (0)
-  const bool rawmode = rtab == nullptr;   // the bytes are final values (the caller has no ratios to hand over: -NOGC, the three-pass chain)
+#define RSI_K4S(C64, RW) do { RSI_ALLOW_FULL_LDS((k_rescale_compact_stream<C64, RW>));                                                                  \
+    RSI_LAUNCH((k_rescale_compact_stream<C64, RW>), dim3(grid), dim3(kS4Threads), lds, a.stream, a.src8, a.src, a.gcbits, a.n, a.n / 64 + 1, a.table, \
+               a.cbreak, a.cum, a.nreg, a.ncompact, a.capval, a.m, vr, sh.sw7 ? 1 : 0, a.rdc8, a.res_hist, sl, pg, a.counters, a.exp_src, a.exp_dst, \
+               (unsigned int)a.exp_bytes, *a.inl, a.rtab, a.escapes, a.pp); } while (0)
+  const bool rawmode = a.rtab == nullptr;   // the bytes are final values (the caller has no ratios to hand over: -NOGC, the three-pass chain)
   if (vr <= 128) { if (rawmode) RSI_K4S(true, true); else RSI_K4S(true, false); }
   else { if (rawmode) RSI_K4S(false, true); else RSI_K4S(false, false); }
 #undef RSI_K4S
 }
 
 // the bins' medians and sums from the bytes the launch above leaves: PARTS lanes per bin, seven dwords each
-void launch_bin_median8(const uint8_t* rdc, int64_t ncompact, int32_t capval, int m, int32_t* binmed, int64_t* binsum, const PhaseParams* pp,
-                        hipStream_t stream) {
-  const int vr = k4s_vr(capval);
-  const bool sw7 = capval <= 127;
+void launch_bin_median8(const K4Args& a) {
+  const ByteShape sh = byte_shape(a.capval);
+  const int vr = sh.vr;
+  const bool sw7 = sh.sw7;
+  const int m = a.m;
   const int parts = m <= 52 ? 2 : (m <= 104 ? 4 : (m <= 216 ? 8 : 16));
-  const int64_t nb = ncompact / m;
+  const int64_t nb = a.ncompact / m;
   const int64_t ntrips = (nb + 64 / parts - 1) / (64 / parts);
   int64_t mg = (ntrips + kM4Threads / 64 - 1) / (kM4Threads / 64);
   mg = mg < 1 ? 1 : (mg > kM4Grid ? kM4Grid : mg);
-#define RSI_K4M(SW, PT) RSI_LAUNCH((k_bin_median8<SW, PT>), dim3((unsigned)mg), dim3(kM4Threads), 0, stream, rdc, ncompact, capval, m, vr, binmed, binsum, pp)
+#define RSI_K4M(SW, PT) RSI_LAUNCH((k_bin_median8<SW, PT>), dim3((unsigned)mg), dim3(kM4Threads), 0, a.stream, a.rdc8, a.ncompact, a.capval, m, vr, a.binmed, a.binsum, a.pp)
   if (sw7) { if (parts == 2) RSI_K4M(true, 2); else if (parts == 4) RSI_K4M(true, 4); else if (parts == 8) RSI_K4M(true, 8); else RSI_K4M(true, 16); }
   else { if (parts == 2) RSI_K4M(false, 2); else if (parts == 4) RSI_K4M(false, 4); else if (parts == 8) RSI_K4M(false, 8); else RSI_K4M(false, 16); }
 #undef RSI_K4M

@@ -292,8 +292,7 @@ class DeviceTester : public rsih::NeighbourTester {
     // full ones take their CUs.  RSI_HOT_CAND_SPLIT=0 / 1 overrides.
     // several workgroups per test when the chip has room for them: a stand-alone context, or a pool run over a few
     // chromosomes only (a rank's share of a sharded genome); one workgroup per test when a dozen chromosomes share the chip
-    const char* split_env = getenv("RSI_HOT_CAND_SPLIT");
-    const bool split = split_env ? atoi(split_env) != 0 : true;
+    const bool split = env_int("RSI_HOT_CAND_SPLIT", 1) != 0;
     size_t first = 0;
     while (first < n) {
       std::vector<CandJob> jobs;
@@ -369,7 +368,7 @@ class DeviceTester : public rsih::NeighbourTester {
       if (slot) memcpy(outs.data(), d_outs, ob);
       gs.release();
       ph.stop();
-      static const bool cand_dbg = getenv("RSI_HOT_CAND_DBG") && atoi(getenv("RSI_HOT_CAND_DBG")) != 0;   // every test's plan and what the device found, on stderr
+      static const bool cand_dbg = env_int("RSI_HOT_CAND_DBG", 0) != 0;   // every test's plan and what the device found, on stderr
       for (size_t k = 0; k < jobs.size(); ++k) {
         const CandOut& O = outs[k];
         if (cand_dbg)
@@ -878,11 +877,40 @@ int materialize_rdc(rsi_ctx* ctx) {
   return RSI_OK;
 }
 
+// K4 in the form the plan names, from the phase's arguments: the route picks the byte copy, the ratios and the mode.  Kernel
+// timers: "cap_compact_bin" around the (streaming) launch, "bin_median" around K4m.
+static void issue_k4(rsi_ctx* ctx, const K4Plan& plan, K4Args a) {
+  a.src8 = (plan.route == K4Route::bytes || plan.raw ? ctx->rescaled8 : ctx->depth8).as<uint8_t>();
+  if (!plan.fixed) a.rtab = a.escapes = nullptr;
+  a.raw = plan.raw;
+  // RAW K4s: the bytes are the values (no ratios, no escapes: the histogram pass saturates them at 254, above any cap of this path)
+  if (plan.route == K4Route::stream && plan.raw) a.table = nullptr;
+  {
+    Timer t(ctx, "cap_compact_bin", true);
+    switch (plan.route) {
+      case K4Route::stream: launch_rescale_compact_stream(a); break;
+      case K4Route::joint: launch_rescale_compact_bin8(a); break;
+      case K4Route::bytes: launch_cap_compact_bin8(a); break;
+      case K4Route::wide16: launch_cap_compact_bin16(a); break;
+      case K4Route::int32: launch_cap_compact_bin(a); break;
+    }
+  }
+  if (plan.route == K4Route::stream) { Timer t(ctx, "bin_median", true); launch_bin_median8(a); }
+}
+
 // A1-A9: GC mask and N runs, GC table and rescale, cap, compaction, bins, chromosome statistics (K1-K4).  The kernels are
 // HBM-bound: workers of a pool take turns through this phase (GpuGate, held until the function returns).
 int per_base_phase(rsi_ctx* ctx, const rsi_params& P, const int32_t* d_depth, const uint8_t* d_fasta, int64_t n, rsi_result* res,
                    PerBase& pb) {
   std::vector<Region>& noncode = pb.noncode;
+  PerBaseSwitches sw;   // read per run: a process may change them between runs
+  sw.joint = !env_off("RSI_HOT_JOINT");
+  sw.spec = !env_off("RSI_HOT_SPEC");
+  sw.k4j_fix = !env_off("RSI_HOT_K4J_FIX");
+  sw.k4split = !env_off("RSI_HOT_K4SPLIT");
+  sw.nogc_bytes = !env_off("RSI_HOT_NOGC_BYTES");
+  sw.k4w = !env_off("RSI_HOT_K4W");
+  sw.k1b_inside = env_on("RSI_HOT_K1B_INSIDE");
   // The per-base kernels are HBM-bound: workers of a pool take turns through this phase (GpuGate).
   struct StreamTurn {
     GpuGate* g = nullptr;
@@ -920,10 +948,9 @@ int per_base_phase(rsi_ctx* ctx, const rsi_params& P, const int32_t* d_depth, co
   // Two per-base passes behind K1 instead of three: K2j counts (GC count, depth byte) pairs, its last workgroup derives the GC
   // table, the rescaled-value histogram and the cap median from them, K4j rescales on its way to the bins.  RSI_HOT_JOINT=0:
   // the three-pass chain (K2, K3', K4'), which is also where a chromosome goes whose joint counters wrapped.
-  const char* joint_env = getenv("RSI_HOT_JOINT");
-  const bool joint = P.gcadjust && want_cap && !(joint_env && atoi(joint_env) == 0);
+  const bool joint = P.gcadjust && want_cap && sw.joint;
   // -NOGC with a cap: the histogram pass leaves the depth as bytes and (round 5) the cap on the device, so that K4s / K4m can be queued behind it
-  const bool nogc_bytes = !P.gcadjust && want_cap && !(getenv("RSI_HOT_NOGC_BYTES") && atoi(getenv("RSI_HOT_NOGC_BYTES")) == 0);
+  const bool nogc_bytes = !P.gcadjust && want_cap && sw.nogc_bytes;
   // one buffer: the folded pair counters (cleared by K1) | the workgroups' escape lists | the levels' fixed-point ratios for K4j
   const size_t joint_list_off = (gc_joint_totals_bytes() + 255) & ~size_t(255), joint_lut_off = joint_list_off + ((gc_joint_esc_list_bytes() + 255) & ~size_t(255));
   if (joint) HIPCHK(ctx->joint_tot.ensure(joint_lut_off + (size_t)kGcLevels * 4 + 64));
@@ -948,7 +975,7 @@ int per_base_phase(rsi_ctx* ctx, const rsi_params& P, const int32_t* d_depth, co
   int64_t* d_cum = d_cbreak + 4100;
   // K1b: the N runs' boundaries and the removed regions -- inside K2j's launch where there is one (RSI_HOT_K1B_INSIDE=1; measured: 0.7 % on the pooled step, 13 us of a lone
   // chromosome -- and 10 us MORE for K2j itself, the kernel the roofline is quoted on: off by default)
-  const bool k1b_inside = joint && getenv("RSI_HOT_K1B_INSIDE") && atoi(getenv("RSI_HOT_K1B_INSIDE")) == 1;
+  const bool k1b_inside = joint && sw.k1b_inside;
   const NRuns k1b_args{ctx->nbits.as<uint64_t>(), d_ntrans, d_ncount, (uint32_t)kMaxTransitions, std::max(50, P.m / 4), d_cbreak, d_cum};
   if (!k1b_inside) { Timer t(ctx, "n_transitions"); launch_n_transitions(ctx->nbits.as<uint64_t>(), nwords, d_ntrans, d_ncount, kMaxTransitions, n, std::max(50, P.m / 4), (joint || nogc_bytes) ? d_pp : nullptr, d_cbreak, d_cum, d_done + 4 * kDoneStride + 8, st); }
   constexpr uint32_t kEagerRuns = 1024;
@@ -964,6 +991,8 @@ int per_base_phase(rsi_ctx* ctx, const rsi_params& P, const int32_t* d_depth, co
   GcAccum* d_acc = reinterpret_cast<GcAccum*>(small + kOffGcAcc);
   double* d_table = reinterpret_cast<double*>(small + kOffTable);
   ValueMedian* d_vm = reinterpret_cast<ValueMedian*>(small + kOffValMedian);
+  BinAccum* d_bacc = reinterpret_cast<BinAccum*>(ctx->hist_res.p);
+  uint32_t* d_res = reinterpret_cast<uint32_t*>(static_cast<char*>(ctx->hist_res.p) + kResHead);
   GcAccum acc;
   ValueHistAux aux;
   ValueMedian vm;
@@ -980,62 +1009,41 @@ int per_base_phase(rsi_ctx* ctx, const rsi_params& P, const int32_t* d_depth, co
                          d_pp, (double)P.cap, st, k1b_inside ? &k1b_args : nullptr);
     return RSI_OK;
   };
-  // K4j right behind K2j, no host in between (one wait per per-base phase instead of two): regions, length and cap reach it
+  // K4's arguments from the buffers as they are when it is issued (ensure() may move them); the caller sets regions, length, cap, export
+  auto k4_args = [&](const K4Regions& regs, int nreg, int64_t ncomp, int32_t cv, void* exp_dst, size_t exp_bytes) {
+    K4Args a{};
+    a.src = d_src; a.gcbits = ctx->gcbits.as<uint64_t>(); a.n = n; a.table = d_table;
+    a.cbreak = d_cbreak; a.cum = d_cum; a.inl = &regs; a.nreg = nreg; a.ncompact = ncomp; a.capval = cv; a.m = P.m;
+    a.rdc8 = ctx->rdc8.as<uint8_t>(); a.rdc = ctx->rdc.as<int32_t>(); a.binmed = ctx->binmed.as<int32_t>(); a.binsum = ctx->binsum.as<int64_t>();
+    a.res_hist = d_res; a.acc = d_bacc; a.slabs = ctx->slabs.p; a.gsum = ctx->gsum.p; a.counters = d_done + 2 * kDoneStride;
+    a.exp_src = ctx->hist_res.p; a.exp_dst = exp_dst; a.exp_bytes = exp_bytes;
+    a.rtab = joint ? reinterpret_cast<const unsigned int*>(ctx->joint_tot.as<uint8_t>() + joint_lut_off) : nullptr;
+    a.escapes = &d_acc->escapes;
+    a.stream = st;
+    return a;
+  };
+  // K4 right behind K2j, no host in between (one wait per per-base phase instead of two): regions, length and cap reach it
   // through device memory (K1b's and K2j's last workgroups); what the launch itself must know -- the value range of its LDS
   // histogram, the median phase's packing -- comes from the cap of this context's previous chromosome under the same flags.
   // The kernel declines when the real cap does not fit that configuration; the host checks everything again below and
-  // launches the ordinary way whenever anything differs.  RSI_HOT_SPEC=0 switches it off.
-  const char* spec_env = getenv("RSI_HOT_SPEC");
-  const bool k4j_fix_off = getenv("RSI_HOT_K4J_FIX") && atoi(getenv("RSI_HOT_K4J_FIX")) == 0;   // the queued K4j always takes K2j's ratios
-  // K4 as three launches (kernels_k4s.hip: streaming half at eight waves per SIMD, the odd chunks exactly, the bin medians without
-  // LDS) wherever K2j's verified ratios exist; RSI_HOT_K4SPLIT=0: K4j, the one-kernel form
-  const bool k4_split = !(getenv("RSI_HOT_K4SPLIT") && atoi(getenv("RSI_HOT_K4SPLIT")) == 0);
-  const bool spec_ok = !(spec_env && atoi(spec_env) == 0) && ctx->spec_capval >= 1 && ctx->spec_m == P.m && ctx->spec_cap == (double)P.cap &&
-                       ctx->spec_gc == (P.gcadjust != 0) && cap_compact8_applies(P.m, ctx->spec_capval);
-  const bool spec_nogc = nogc_bytes && spec_ok && k4_split && rescale_compact_split_applies(P.m, ctx->spec_capval, n, 0);   // (the split form only)
-  const bool spec = (joint && spec_ok && !k4j_fix_off) || spec_nogc;
+  // launches the ordinary way whenever anything differs.  It is the route k4_plan gives the guessed cap over the whole
+  // chromosome when that is K4s + K4m (with K2j's ratios, or RAW under -NOGC) or K4j with K2j's ratios.  RSI_HOT_SPEC=0
+  // switches it off.
+  const K4Plan spec_plan = k4_plan(P.gcadjust, want_cap, ctx->spec_capval, P.m, n, 0, false, joint, sw);
+  const bool spec = sw.spec && ctx->spec_capval >= 1 && ctx->spec_m == P.m && ctx->spec_cap == (double)P.cap && ctx->spec_gc == (P.gcadjust != 0) &&
+                    (spec_plan.route == K4Route::stream || (spec_plan.route == K4Route::joint && spec_plan.fixed));
   constexpr uint32_t kSpecMagic = 0x5bec5bec;
   uint32_t* spec_slot = nullptr;
-  size_t spec_bytes = 0;
-  auto issue_k4j_spec = [&]() -> int {
-    const int32_t guess = ctx->spec_capval;
-    int vr = 64;
-    while (vr < 256 && vr <= guess) vr <<= 1;
-    spec_bytes = kResHead + (size_t)vr * kResClasses * 4;
+  K4Regions none;
+  memset(&none, 0, sizeof(none));
+  auto issue_spec = [&]() {
+    const size_t spec_bytes = kResHead + (size_t)spec_plan.shape.vr * kResClasses * 4;
     spec_slot = static_cast<uint32_t*>(mb_alloc(ctx, spec_bytes));
-    if (!spec_slot) return RSI_OK;   // no room in the mailbox: the ordinary way
-    spec_slot[3] = kSpecMagic;       // BinAccum::pad: the kernel's export overwrites it with zero; still there = the kernel declined
-    HIPCHK(ctx->slabs.ensure(std::max(gc_joint_slab_bytes(n), std::max(cap_compact8_slab_bytes(P.m, guess, n), rescale_compact_split_slab_bytes(guess, n)))));
-    HIPCHK(ctx->rdc8.ensure(rescale_compact_split_rdc_bytes(n)));
-    HIPCHK(ctx->binmed.ensure((size_t)(n / P.m + 1) * 4));
-    HIPCHK(ctx->binsum.ensure((size_t)(n / P.m + 1) * 8));
-    K4Regions none;
-    memset(&none, 0, sizeof(none));
-    Timer t(ctx, "cap_compact_bin", true);
-    if (spec_nogc) {   // -NOGC: the bytes are the values (no ratios, no escapes: the histogram pass saturates them at 254, above any cap of this path)
-      launch_rescale_compact_stream(ctx->rescaled8.as<uint8_t>(), d_depth, ctx->gcbits.as<uint64_t>(), n, nullptr, d_cbreak, d_cum, none, 0, n, guess, P.m,
-                                    ctx->rdc8.as<uint8_t>(), reinterpret_cast<uint32_t*>(static_cast<char*>(ctx->hist_res.p) + kResHead), ctx->slabs.p,
-                                    d_done + 2 * kDoneStride, ctx->hist_res.p, spec_slot, spec_bytes, nullptr, nullptr, d_pp, st);
-      t.~Timer();
-      new (&t) Timer(ctx, "bin_median", true);
-      launch_bin_median8(ctx->rdc8.as<uint8_t>(), n, guess, P.m, ctx->binmed.as<int32_t>(), ctx->binsum.as<int64_t>(), d_pp, st);
-      return RSI_OK;
-    }
-    if (k4_split && rescale_compact_split_applies(P.m, guess, n, 0)) {
-      launch_rescale_compact_stream(ctx->depth8.as<uint8_t>(), d_depth, ctx->gcbits.as<uint64_t>(), n, d_table, d_cbreak, d_cum, none, 0, n, guess, P.m,
-                                    ctx->rdc8.as<uint8_t>(), reinterpret_cast<uint32_t*>(static_cast<char*>(ctx->hist_res.p) + kResHead), ctx->slabs.p,
-                                    d_done + 2 * kDoneStride, ctx->hist_res.p, spec_slot, spec_bytes,
-                                    reinterpret_cast<const unsigned int*>(ctx->joint_tot.as<uint8_t>() + joint_lut_off), &d_acc->escapes, d_pp, st);
-      t.~Timer();   // (closes the streaming half's bracket: the medians have their own)
-      new (&t) Timer(ctx, "bin_median", true);
-      launch_bin_median8(ctx->rdc8.as<uint8_t>(), n, guess, P.m, ctx->binmed.as<int32_t>(), ctx->binsum.as<int64_t>(), d_pp, st);
-      return RSI_OK;
-    }
-    launch_rescale_compact_bin8(ctx->depth8.as<uint8_t>(), d_depth, ctx->gcbits.as<uint64_t>(), n, d_table, d_cbreak, d_cum, none, 0, n, guess, P.m,
-                                ctx->rdc8.as<uint8_t>(), ctx->binmed.as<int32_t>(), ctx->binsum.as<int64_t>(),
-                                reinterpret_cast<uint32_t*>(static_cast<char*>(ctx->hist_res.p) + kResHead), ctx->slabs.p, ctx->gsum.p, d_done + 2 * kDoneStride,
-                                ctx->hist_res.p, spec_slot, spec_bytes, reinterpret_cast<const unsigned int*>(ctx->joint_tot.as<uint8_t>() + joint_lut_off), d_pp, st);
-    return RSI_OK;
+    if (!spec_slot) return;       // no room in the mailbox: the ordinary way
+    spec_slot[3] = kSpecMagic;    // BinAccum::pad: the kernel's export overwrites it with zero; still there = the kernel declined
+    K4Args a = k4_args(none, 0, n, ctx->spec_capval, spec_slot, spec_bytes);
+    a.pp = d_pp;
+    issue_k4(ctx, spec_plan, a);
   };
   auto issue_gc_chain = [&](int packed) -> int {
     if (P.gcadjust) {
@@ -1066,10 +1074,15 @@ int per_base_phase(rsi_ctx* ctx, const rsi_params& P, const int32_t* d_depth, co
   };
   // the slab buffer serves K2 and K3 one after the other: size it for both before anything is in flight
   if (P.gcadjust) HIPCHK(ctx->slabs.ensure(std::max(std::max(gc_hist_slab_bytes(n), joint ? gc_joint_slab_bytes(n) : 0), std::max(gc_rescale_slab_bytes(n), value_hist8_slab_bytes(n)))));
-  if (spec) HIPCHK(ctx->slabs.ensure(std::max(gc_joint_slab_bytes(n), std::max(cap_compact8_slab_bytes(P.m, ctx->spec_capval, n), rescale_compact_split_slab_bytes(ctx->spec_capval, n)))));   // before anything is in flight
+  if (spec) {   // the queued launch's buffers, before anything is in flight
+    HIPCHK(ctx->slabs.ensure(std::max(gc_joint_slab_bytes(n), std::max(cap_compact8_slab_bytes(P.m, ctx->spec_capval, n), rescale_compact_split_slab_bytes(ctx->spec_capval, n)))));
+    HIPCHK(ctx->rdc8.ensure(rescale_compact_split_rdc_bytes(n)));
+    HIPCHK(ctx->binmed.ensure((size_t)(n / P.m + 1) * 4));
+    HIPCHK(ctx->binsum.ensure((size_t)(n / P.m + 1) * 8));
+  }
   int rc = joint ? issue_joint() : issue_gc_chain(1);
   if (rc != RSI_OK) return rc;
-  if (spec && (rc = issue_k4j_spec()) != RSI_OK) return rc;
+  if (spec) issue_spec();
   ph_a1b.stop();
   { Phase ph_a1c(ctx, "a1c.wait K1-K3"); HIPCHK(CTX_SYNC()); }
   unpack_head();
@@ -1219,24 +1232,21 @@ int per_base_phase(rsi_ctx* ctx, const rsi_params& P, const int32_t* d_depth, co
   HIPCHK(ctx->binmed.ensure((size_t)nb * 4));
   HIPCHK(ctx->binsum.ensure((size_t)nb * 8));
   const size_t res_vals = want_cap && capval < kHistValues - 1 ? (size_t)std::max(capval, 0) + 1 : (size_t)kHistValues;
-  BinAccum* d_bacc = reinterpret_cast<BinAccum*>(ctx->hist_res.p);
-  uint32_t* d_res = reinterpret_cast<uint32_t*>(static_cast<char*>(ctx->hist_res.p) + kResHead);
   // K4's last workgroup folds the per-workgroup histograms and writes [BinAccum | histogram] into the mailbox.  With the
   // cap below the kernel's LDS value range the fold overwrites res_hist (nothing to clear); otherwise (no cap, or a cap
   // of 256 and more) stray values reach res_hist through global atomics and it is cleared first.
   size_t exp_bytes = kResHead + res_vals * kResClasses * 4;
-  // the K4j that was queued behind K2j: accepted when it ran (its export replaced the marker) under exactly the regions, length
-  // and cap the host has just derived itself, with nothing about the chromosome that the ordinary path treats differently
+  const K4Plan plan = k4_plan(P.gcadjust, want_cap, capval, P.m, ncompact, (int)noncode.size(), deep, joint_ok, sw);
+  // the K4 that was queued behind K2j: accepted when it ran (its export replaced the marker) under exactly the regions, length
+  // and cap the host has just derived itself, in the shape of the real cap, with nothing about the chromosome that the ordinary
+  // path treats differently
   PhaseParams hpp;
   memcpy(&hpp, head + kOffPhase, sizeof(hpp));
   bool spec_done = false;
   if (spec_slot) {
-    int vr_g = 64, vr_c = 64;
-    while (vr_g < 256 && vr_g <= ctx->spec_capval) vr_g <<= 1;
-    while (vr_c < 256 && vr_c <= capval) vr_c <<= 1;
     const bool ran = spec_slot[3] != kSpecMagic;
-    spec_done = ran && (P.gcadjust ? (joint_ok && !deep && !jinfo.esc_pending) : spec_nogc) && hpp.regions_ok == 1 && hpp.capval == capval && hpp.nreg == (int32_t)noncode.size() &&
-                hpp.ncompact == ncompact && cap_compact8_applies(P.m, capval) && vr_g == vr_c && (ctx->spec_capval <= 127) == (capval <= 127) &&
+    spec_done = ran && (!P.gcadjust || (joint_ok && !deep && !jinfo.esc_pending)) && hpp.regions_ok == 1 && hpp.capval == capval &&
+                hpp.nreg == (int32_t)noncode.size() && hpp.ncompact == ncompact && plan.bytes_fit && plan.shape == spec_plan.shape &&
                 (int)noncode.size() <= kMaxRegions;
     if (ran && !spec_done) HIPCHK(hipMemsetAsync(ctx->hist_res.p, 0, kResHead + (size_t)256 * kResClasses * 4, st));   // it added its histogram to the rows: clean again
     ctx->phases.push_back({spec_done ? "spec.k4j accepted" : "spec.k4j rejected", 1.0});
@@ -1245,93 +1255,38 @@ int per_base_phase(rsi_ctx* ctx, const rsi_params& P, const int32_t* d_depth, co
   if (spec_done) {
     ctx->rdc_is_bytes = true;   // all done by the queued launch
     if (!P.gcadjust) ctx->phases.push_back({"a5.nogc byte path", 1.0});
-  } else if (P.gcadjust && want_cap && !deep && cap_compact8_applies(P.m, capval)) {
-    // K4': from the byte copy of the raw depth, rescaling on the way -- the rescaled int32 array is never written or read
-    HIPCHK(ctx->slabs.ensure(cap_compact8_slab_bytes(P.m, capval, ncompact)));
-    HIPCHK(ctx->rdc8.ensure((size_t)ncompact + 64));
-    ctx->rdc_is_bytes = true;
-    // K2j's verified fixed-point ratios when it ran to the end; the float form with its exactness margin for a chromosome that
-    // went through K2 + K3' (wrapped pair counters) -- RSI_HOT_K4J_FIX=0 selects that form for any chromosome
-    const bool k4j_fix = joint_ok && !k4j_fix_off;
-    const bool k4j = joint_ok || !(joint_env && atoi(joint_env) == 0);
-    if (k4j && !k4j_fix) ctx->phases.push_back({"k4j.float rescale", 1.0});
-    const bool split = k4j && k4j_fix && k4_split && rescale_compact_split_applies(P.m, capval, ncompact, (int)noncode.size());
-    if (split) {
-      HIPCHK(ctx->slabs.ensure(rescale_compact_split_slab_bytes(capval, ncompact)));
-      HIPCHK(ctx->rdc8.ensure(rescale_compact_split_rdc_bytes(ncompact)));
-      ctx->phases.push_back({"k4.split", 1.0});
-    }
-    Timer t(ctx, "cap_compact_bin", true);
-    if (split) {   // K4s, K4m
-      launch_rescale_compact_stream(ctx->depth8.as<uint8_t>(), d_depth, ctx->gcbits.as<uint64_t>(), n, d_table, d_cbreak, d_cum, inl, (int)noncode.size(),
-                                    ncompact, capval, P.m, ctx->rdc8.as<uint8_t>(), d_res, ctx->slabs.p, d_done + 2 * kDoneStride, ctx->hist_res.p, exp_slot,
-                                    exp_slot ? exp_bytes : 0, reinterpret_cast<const unsigned int*>(ctx->joint_tot.as<uint8_t>() + joint_lut_off),
-                                    &d_acc->escapes, nullptr, st);
-      t.~Timer();   // (closes the streaming half's bracket: the medians have their own)
-      new (&t) Timer(ctx, "bin_median", true);
-      launch_bin_median8(ctx->rdc8.as<uint8_t>(), ncompact, capval, P.m, ctx->binmed.as<int32_t>(), ctx->binsum.as<int64_t>(), nullptr, st);
-    }
-    else if (k4j)   // K4j: from the byte copy of the RAW depth (K2 and K2j both leave it), rescaling on the way
-      launch_rescale_compact_bin8(ctx->depth8.as<uint8_t>(), d_depth, ctx->gcbits.as<uint64_t>(), n, d_table, d_cbreak, d_cum, inl, (int)noncode.size(),
-                                  ncompact, capval, P.m, ctx->rdc8.as<uint8_t>(), ctx->binmed.as<int32_t>(), ctx->binsum.as<int64_t>(), d_res, ctx->slabs.p,
-                                  ctx->gsum.p, d_done + 2 * kDoneStride, ctx->hist_res.p, exp_slot, exp_slot ? exp_bytes : 0,
-                                  k4j_fix ? reinterpret_cast<const unsigned int*>(ctx->joint_tot.as<uint8_t>() + joint_lut_off) : nullptr, nullptr, st);
-    else   // RSI_HOT_JOINT=0: round 2's chain to the end (K4' from K3''s rescaled bytes), kept for A/B runs
-    launch_cap_compact_bin8(ctx->rescaled8.as<uint8_t>(), d_depth, ctx->gcbits.as<uint64_t>(), n, d_table, d_cbreak, d_cum, inl, (int)noncode.size(),
-                            ncompact, capval, P.m, ctx->rdc8.as<uint8_t>(), ctx->binmed.as<int32_t>(), ctx->binsum.as<int64_t>(), d_res, ctx->slabs.p,
-                            ctx->gsum.p, d_done + 2 * kDoneStride, ctx->hist_res.p, exp_slot, exp_slot ? exp_bytes : 0, st);
-  } else if (!P.gcadjust && want_cap && cap_compact8_applies(P.m, capval) && !(getenv("RSI_HOT_NOGC_BYTES") && atoi(getenv("RSI_HOT_NOGC_BYTES")) == 0)) {
-    // -NOGC with a cap below 254: K4' from the byte copy the histogram pass left (raw depth: no rescale anywhere)
-    HIPCHK(ctx->slabs.ensure(cap_compact8_slab_bytes(P.m, capval, ncompact)));
-    HIPCHK(ctx->rdc8.ensure((size_t)ncompact + 64));
-    ctx->rdc_is_bytes = true;
-    ctx->phases.push_back({"a5.nogc byte path", 1.0});
-    const bool split = k4_split && rescale_compact_split_applies(P.m, capval, ncompact, (int)noncode.size());
-    if (split) {
-      HIPCHK(ctx->slabs.ensure(rescale_compact_split_slab_bytes(capval, ncompact)));
-      HIPCHK(ctx->rdc8.ensure(rescale_compact_split_rdc_bytes(ncompact)));
-      ctx->phases.push_back({"k4.split", 1.0});
-    }
-    Timer t(ctx, "cap_compact_bin", true);
-    if (split) {   // K4s without ratios (the bytes are the values), K4m
-      launch_rescale_compact_stream(ctx->rescaled8.as<uint8_t>(), d_depth, ctx->gcbits.as<uint64_t>(), n, nullptr, d_cbreak, d_cum, inl, (int)noncode.size(),
-                                    ncompact, capval, P.m, ctx->rdc8.as<uint8_t>(), d_res, ctx->slabs.p, d_done + 2 * kDoneStride, ctx->hist_res.p, exp_slot,
-                                    exp_slot ? exp_bytes : 0, nullptr, nullptr, nullptr, st);
-      t.~Timer();
-      new (&t) Timer(ctx, "bin_median", true);
-      launch_bin_median8(ctx->rdc8.as<uint8_t>(), ncompact, capval, P.m, ctx->binmed.as<int32_t>(), ctx->binsum.as<int64_t>(), nullptr, st);
-    } else
-    launch_cap_compact_bin8(ctx->rescaled8.as<uint8_t>(), d_depth, ctx->gcbits.as<uint64_t>(), n, d_table, d_cbreak, d_cum, inl, (int)noncode.size(),
-                            ncompact, capval, P.m, ctx->rdc8.as<uint8_t>(), ctx->binmed.as<int32_t>(), ctx->binsum.as<int64_t>(), d_res, ctx->slabs.p,
-                            ctx->gsum.p, d_done + 2 * kDoneStride, ctx->hist_res.p, exp_slot, exp_slot ? exp_bytes : 0, st, 1);
   } else {
-    if (P.gcadjust) {   // no cap, a cap of 255 and more, or a wide bin: K4 from the rescaled int32 array, built first
-      int rcm = materialize_rd_gc(ctx);
-      if (rcm != RSI_OK) return rcm;
-      d_src = ctx->rd_gc.as<int32_t>();
+    int vbase = 0;
+    if (plan.route == K4Route::wide16 || plan.route == K4Route::int32) {
+      if (P.gcadjust) {   // no cap, a cap of 255 and more, deep coverage or a wide bin: K4 from the rescaled int32 array, built first
+        const int rcm = materialize_rd_gc(ctx);
+        if (rcm != RSI_OK) return rcm;
+        d_src = ctx->rd_gc.as<int32_t>();
+      }
+      vbase = want_cap ? hist_window_base(S.cap_median, kK4Window) : (P.gcadjust ? hist_window_base(S.gc_rdmean, kK4Window) : 0);
+      // K4w (16-bit tile and window counters) adds to res_hist; K4 overwrites it when every value is below its LDS range
+      if (plan.route == K4Route::wide16 || !cap_compact_overwrites(P.m, capval, ncompact, vbase)) HIPCHK(hipMemsetAsync(d_res, 0, res_vals * kResClasses * 4, st));
+      HIPCHK(ctx->slabs.ensure(plan.route == K4Route::wide16 ? cap_compact16_slab_bytes(P.m, ncompact) : cap_compact_slab_bytes(P.m, capval, ncompact, vbase)));
+    } else {   // the byte forms: the rescaled int32 array is never written or read
+      HIPCHK(ctx->slabs.ensure(cap_compact8_slab_bytes(P.m, capval, ncompact)));
+      HIPCHK(ctx->rdc8.ensure((size_t)ncompact + 64));
+      if (plan.route == K4Route::stream) {
+        HIPCHK(ctx->slabs.ensure(rescale_compact_split_slab_bytes(capval, ncompact)));
+        HIPCHK(ctx->rdc8.ensure(rescale_compact_split_rdc_bytes(ncompact)));
+      }
+      ctx->rdc_is_bytes = true;
     }
-    const int vbase = want_cap ? hist_window_base(S.cap_median, kK4Window) : (P.gcadjust ? hist_window_base(S.gc_rdmean, kK4Window) : 0);
-    const char* w16_env = getenv("RSI_HOT_K4W");
-    if (want_cap && cap_compact16_applies(P.m, capval, ncompact) && !(w16_env && atoi(w16_env) == 0)) {
-      // K4w: a cap of 254 .. 32766 (deep coverage, or a generous cap): 16-bit tile and window counters.  RSI_HOT_K4W=0: the int32 kernel
-      HIPCHK(hipMemsetAsync(d_res, 0, res_vals * kResClasses * 4, st));
-      HIPCHK(ctx->slabs.ensure(cap_compact16_slab_bytes(P.m, ncompact)));
-      ctx->phases.push_back({"a5.k4w 16-bit tile", 1.0});
-      Timer t(ctx, "cap_compact_bin", true);
-      launch_cap_compact_bin16(d_src, d_cbreak, d_cum, inl, (int)noncode.size(), ncompact, capval, P.m, ctx->rdc.as<int32_t>(), ctx->binmed.as<int32_t>(), ctx->binsum.as<int64_t>(), d_res, ctx->slabs.p, d_done + 2 * kDoneStride, ctx->hist_res.p, exp_slot, exp_slot ? exp_bytes : 0, vbase, st);
-    } else {
-      const bool overwrite = cap_compact_overwrites(P.m, capval, ncompact, vbase) != 0;
-      if (!overwrite) HIPCHK(hipMemsetAsync(d_res, 0, res_vals * kResClasses * 4, st));
-      HIPCHK(ctx->slabs.ensure(cap_compact_slab_bytes(P.m, capval, ncompact, vbase)));
-      Timer t(ctx, "cap_compact_bin", true);
-      launch_cap_compact_bin(d_src, n, d_cbreak, d_cum, inl, (int)noncode.size(), ncompact, capval, P.m, ctx->rdc.as<int32_t>(), ctx->binmed.as<int32_t>(), ctx->binsum.as<int64_t>(), d_res, d_bacc, ctx->slabs.p, ctx->gsum.p, d_done + 2 * kDoneStride, ctx->hist_res.p, exp_slot, exp_slot ? exp_bytes : 0, vbase, st);
-    }
+    for (const char* mark : plan.marks)
+      if (mark) ctx->phases.push_back({mark, 1.0});
+    K4Args a = k4_args(inl, (int)noncode.size(), ncompact, capval, exp_slot, exp_slot ? exp_bytes : 0);
+    a.vbase = vbase;
+    issue_k4(ctx, plan, a);
   }
   BinAccum bacc;
   std::vector<uint32_t> hres_all(kResHead / 4 + res_vals * kResClasses);
   if (!exp_slot) HIPCHK(copy_d2h(ctx, hres_all.data(), ctx->hist_res.p, hres_all.size() * 4));
   if (!spec_done) HIPCHK(CTX_SYNC());
-  if ((joint_ok || nogc_bytes) && want_cap && cap_compact8_applies(P.m, capval)) { ctx->spec_capval = capval; ctx->spec_m = P.m; ctx->spec_cap = (double)P.cap; ctx->spec_gc = P.gcadjust != 0; }
+  if ((joint_ok || nogc_bytes) && plan.bytes_fit) { ctx->spec_capval = capval; ctx->spec_m = P.m; ctx->spec_cap = (double)P.cap; ctx->spec_gc = P.gcadjust != 0; }
   if (exp_slot) memcpy(hres_all.data(), exp_slot, exp_bytes);
   memcpy(&bacc, hres_all.data(), sizeof(bacc));
   const uint32_t* hres = hres_all.data() + kResHead / 4;
@@ -1501,10 +1456,9 @@ int bin_level_stages(rsi_ctx* ctx, const rsi_params& P, int64_t n, rsi_result* r
       {   // areblockscnv, rsi.cpp:1847: on the bin medians; a scan with many segments sends its first round to the device as one batch
         Phase ph(ctx, "a15.blocks");
         HIPCHK(join_copy(ctx));   // the host copy of the bin medians
-        const char* bb_env = getenv("RSI_HOT_BLOCK_BATCH");   // 0: every block test on the host
         DeviceTester block_tester(ctx, DepthRef{ctx->binmed.p, 4}, nb, RDmedian);
         rsih::CallProfile bprof;
-        in.block_tester = (bb_env && atoi(bb_env) == 0) ? nullptr : &block_tester;
+        in.block_tester = env_off("RSI_HOT_BLOCK_BATCH") ? nullptr : &block_tester;   // 0: every block test on the host
         in.prof = &bprof;
         rsih::test_block_segments(in, so.status2, segs);
         in.block_tester = nullptr;
@@ -1539,8 +1493,7 @@ int bin_level_stages(rsi_ctx* ctx, const rsi_params& P, int64_t n, rsi_result* r
     in.prof = &prof;
     const DepthRef depth_ref = ctx->rdc_is_bytes ? DepthRef{ctx->rdc8.p, 1} : DepthRef{ctx->rdc.p, 4};
     DeviceTester tester(ctx, depth_ref, ncompact, RDmedian);
-    const char* host_env = getenv("RSI_HOT_HOST_CANDIDATES");   // debugging switch: candidate stages on the host
-    const bool host_tests = host_env && atoi(host_env) != 0;
+    const bool host_tests = env_int("RSI_HOT_HOST_CANDIDATES", 0) != 0;   // debugging switch: candidate stages on the host
     in.tester = host_tests ? nullptr : &tester;
     { Phase ph(ctx, "a16-19.calls"); rsih::call_from_segments(in, tested, pager, blocks, raw, kept); }
     if (tester.failed) return RSI_ERR_HIP;
@@ -1698,8 +1651,7 @@ int rsi_hot_run(rsi_ctx* ctx, const rsi_params* p, const int32_t* depth, const u
   // again (1 + 4 bytes per base of HBM traffic, 0.1 ms per 100 Mb): 2 bytes per base over the link instead of 5.  One thread
   // narrows slower than the link copies, so this is for a pool whose workers each bring a chromosome of their own (the link
   // is what sixteen of them share); a lone call copies the array as it is.  RSI_HOT_H2D_NARROW=0 / 1 forces either.
-  const char* narrow_v = getenv("RSI_HOT_H2D_NARROW");
-  const int narrow_env = narrow_v ? atoi(narrow_v) : -1;
+  const int narrow_env = env_int("RSI_HOT_H2D_NARROW", -1);
   const bool narrow = n >= (1 << 18) && (narrow_env >= 0 ? narrow_env != 0 : (ctx->gate != nullptr && !ctx->gate->lonely()));
   bool narrowed = false;
   if (narrow) {

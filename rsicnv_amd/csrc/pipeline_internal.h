@@ -48,9 +48,15 @@ inline void set_global_error(const std::string& m) { std::lock_guard<std::mutex>
 inline thread_local double tl_grow = 1.0;
 inline thread_local double tl_grow_ms = 0.0;   // time this thread spent re-allocating during the current run
 
+// The RSI_HOT_* switches: an integer, `unset` when the variable is not set.  env_off: "=0" turns a default path off; env_on: "=1"
+// turns an alternative on.
+inline int env_int(const char* name, int unset) { const char* v = getenv(name); return v ? atoi(v) : unset; }
+inline bool env_off(const char* name) { return env_int(name, 1) == 0; }
+inline bool env_on(const char* name) { return env_int(name, 0) == 1; }
+
 // RSI_HOT_POISON=1 (debugging): every new device and pinned allocation is filled with 0xA5 instead of whatever the driver
 // hands out (zero pages in a fresh process, another context's leftovers in a long one)
-inline bool poison_allocations() { static const bool on = getenv("RSI_HOT_POISON") && atoi(getenv("RSI_HOT_POISON")) != 0; return on; }
+inline bool poison_allocations() { static const bool on = env_int("RSI_HOT_POISON", 0) != 0; return on; }
 
 struct DevBuf {   // grow-only device allocation
   void* p = nullptr;
@@ -213,7 +219,7 @@ constexpr double kStreamWaitDeadlineMs = 60000.0;
 // the same with none, and a pool of 24 workers on a 16-core box went from 14 to 25 ms with them).  A lone chromosome's waits
 // are short and nobody else wants the core: spin.  RSI_HOT_SPIN overrides the count.
 inline hipError_t event_wait(hipEvent_t ev, bool busy_pool = false) {   // an event that has been recorded
-  static const int spin_env = [] { const char* v = getenv("RSI_HOT_SPIN"); return v ? atoi(v) : -1; }();
+  static const int spin_env = env_int("RSI_HOT_SPIN", -1);
   const int spins = spin_env >= 0 ? spin_env : (busy_pool ? 50 : 2000);
   hipError_t e = hipSuccess;
   for (int spin = 0; spin < spins; ++spin) {

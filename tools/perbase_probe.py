@@ -1,4 +1,4 @@
-"""Per-base kernels alone on the chip under debug switches (RSI_HOT_K2J_DBG, RSI_HOT_K4J_DBG: ablations that break the
+"""Per-base kernels alone on the chip under a debug switch (RSI_HOT_K2J_DBG: ablations that break the
 results -- a failing run is expected there; the kernel times are still read).  usage: perbase_probe.py "ENV=VAL,..." ..."""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -115,6 +115,43 @@ int rsi_hot_load_depth_text(rsi_ctx* ctx, const char* path, int64_t n, rsi_text_
 int rsi_hot_run_text(rsi_ctx* ctx, const rsi_params* p, const char* depth_path, const uint8_t* fasta, int64_t n,
                      rsi_result** out, rsi_text_stats* stats);
 
+/* ---- Whole-genome depth text: "RNAME pos depth" lines, every chromosome in one file --------------------
+ * (samtools depth -a, or mpileup | cut -f1,2,4).  A streaming reader that parses the file on the device and hands over each
+ * chromosome's depth, resident in HBM, as soon as its last line has been parsed.  Lines: empty ones and those whose first
+ * byte is '#' are skipped; the name is the first token (leading blanks skipped, up to the next blank); what follows it is
+ * read by rsi_hot_load_depth_text's rules.  Each chromosome X gives exactly what rsi_hot_load_depth_text gives on its slice
+ * (its lines without the name), counts and fallback included -- the fallback per chromosome.  Names: looked up in
+ * names[] as read_fasta does (names[i] == X or "chr" + X, the first match); names containing "MT" or '.' are skipped
+ * silently (the BAM walk's filter); other names not in names[] are handed over with slot = -1 and no depth.  Chromosomes
+ * come in order of first appearance; a name that comes back after another one is an error (the lines of a chromosome
+ * must be contiguous).  At most max_resident depth buffers exist: the reader needs one free for each new chromosome, so
+ * a caller that holds max_resident - 1 of them releases one before asking for the next.  chunk_bytes: bytes of text per
+ * transfer (0: 64 MB).  Every wait has the library's 60 s deadline. */
+typedef struct rsi_genome_text rsi_genome_text;
+typedef struct rsi_genome_chrom {
+  int32_t slot;            /* depth buffer, -1: the name is not in names[] (no depth) */
+  int32_t pad;
+  int64_t n;               /* chromosome length (lengths[i]) */
+  const void* d_depth;     /* int32[n] in HBM; valid until rsi_genome_text_release(slot) */
+  rsi_text_stats stats;    /* bytes: the chromosome's byte range in the file; lines / stored / beyond / fallback as for its slice */
+  char name[256];          /* the name as in the file */
+} rsi_genome_chrom;
+rsi_genome_text* rsi_genome_text_open(int device, const char* path, int nref, const char* const* names, const int64_t* lengths,
+                                      int max_resident, size_t chunk_bytes, int* status);
+/* 1: one chromosome complete (*out); 0: end of the file; < 0: error (rsi_genome_text_last_error) */
+int rsi_genome_text_next(rsi_genome_text* g, rsi_genome_chrom* out);
+void rsi_genome_text_release(rsi_genome_text* g, int slot);   /* its device buffer may be reused */
+/* a handed-over chromosome's depth into host memory (tests); returns the element count, < 0 on error */
+int64_t rsi_genome_text_copy_depth(rsi_genome_text* g, int slot, int32_t* out, int64_t cap);
+/* summed HIP-event time of the boundary and the parse launches so far */
+int rsi_genome_text_kernel_ms(const rsi_genome_text* g, double* bound_ms, double* parse_ms);
+void rsi_genome_text_close(rsi_genome_text* g);
+const char* rsi_genome_text_last_error(const rsi_genome_text* g);
+/* One chromosome whose depth is already in HBM (e.g. a genome reader's buffer, not modified) and whose fasta[n] is in
+ * host memory: the sequence goes to the context's own device buffer, then rsi_hot_run_device. */
+int rsi_hot_run_depth_device(rsi_ctx* ctx, const rsi_params* p, const void* d_depth, const uint8_t* fasta, int64_t n,
+                             rsi_result** out);
+
 /* ---- BAM pileup -> per-base depth, GPU-assisted -------------------------------------
  * Replaces the read loop of load_data_from_bam (loaddata.cpp:277-333): reads of chromosome `chrom`
  * (all of them, as bam_iter_query(ref, 0, 0x7fffffff) yields) that pass pos != 0, mapq >= minq, not

@@ -49,6 +49,8 @@ int rsi_synth_generate_device(const rsi_synth_spec* spec, void* d_fasta, void* d
  * comment line first), the chromosome as a FASTA file of 60-base lines with its .fai index next to it.  0 or < 0. */
 int rsi_synth_write_depth_text(const char* path, const int32_t* depth, int64_t n);
 int rsi_synth_write_fasta(const char* path, const char* chrom, const uint8_t* fasta, int64_t n);
+/* "RNAME<TAB>pos<TAB>depth" lines of one chromosome appended to `path` (whole-genome depth text).  0 or < 0. */
+int rsi_synth_append_genome_text(const char* path, const char* chrom, const int32_t* depth, int64_t n);
 
 #ifdef __cplusplus
 }

@@ -28,7 +28,9 @@ EXPORTS = ["rsi_default_params", "rsi_hot_create", "rsi_hot_destroy", "rsi_hot_l
            "rsi_hot_run_device", "rsi_hot_load_depth_text", "rsi_hot_run_text", "rsi_hot_load_depth_bam", "rsi_hot_run_bam", "rsi_bam_references", "rsi_result_annotate_bam", "rsi_result_summary", "rsi_summary_format_row", "rsi_summary_format_rows", "rsi_result_pairs", "rsi_result_ncalls", "rsi_result_calls", "rsi_result_stats", "rsi_result_noncode",
            "rsi_result_format_row", "rsi_result_free", "rsi_hot_fetch_i32", "rsi_hot_fetch_f32", "rsi_hot_fetch_i64",
            "rsi_hot_kernel_times", "rsi_hot_phase_times", "rsi_hot_set_timing", "rsi_pool_create", "rsi_pool_destroy", "rsi_pool_workers", "rsi_pool_worker",
-           "rsi_pool_set_timing", "rsi_pool_set_timing_kernel", "rsi_hot_set_timing_kernel", "rsi_pool_set_schedule", "rsi_pool_last_error", "rsi_pool_run", "rsi_pool_run_host", "rsi_pool_submit", "rsi_pool_wait", "rsi_plot_expand", "rsi_plot_write_files", "rsi_result_log_line", "rsi_hot_debug_level_sums", "rsi_hot_debug_scan", "rsi_synth_generate_host", "rsi_synth_generate_device", "rsi_synth_write_depth_text", "rsi_synth_write_fasta"]
+           "rsi_pool_set_timing", "rsi_pool_set_timing_kernel", "rsi_hot_set_timing_kernel", "rsi_pool_set_schedule", "rsi_pool_last_error", "rsi_pool_run", "rsi_pool_run_host", "rsi_pool_submit", "rsi_pool_wait", "rsi_plot_expand", "rsi_plot_write_files", "rsi_result_log_line", "rsi_hot_debug_level_sums", "rsi_hot_debug_scan", "rsi_synth_generate_host", "rsi_synth_generate_device", "rsi_synth_write_depth_text", "rsi_synth_write_fasta", "rsi_synth_append_genome_text",
+           "rsi_genome_text_open", "rsi_genome_text_next", "rsi_genome_text_release", "rsi_genome_text_copy_depth",
+           "rsi_genome_text_kernel_ms", "rsi_genome_text_close", "rsi_genome_text_last_error", "rsi_hot_run_depth_device"]
 
 
 class RsiParams(C.Structure):
@@ -62,6 +64,11 @@ SUMMARY_HEAD, SUMMARY_CALL = 8, 8   # rsi_hot.h: RSI_SUMMARY_HEAD, RSI_SUMMARY_C
 class RsiTextStats(C.Structure):
     _fields_ = [("bytes", C.c_int64), ("lines", C.c_int64), ("stored", C.c_int64), ("beyond", C.c_int64),
                 ("fallback", C.c_int32), ("pad", C.c_int32), ("t_total_ms", C.c_double), ("t_parse_kernel_ms", C.c_double)]
+
+
+class RsiGenomeChrom(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("pad", C.c_int32), ("n", C.c_int64), ("d_depth", C.c_void_p), ("stats", RsiTextStats),
+                ("name", C.c_char * 256)]
 
 
 class RsiBamStats(C.Structure):
@@ -156,6 +163,18 @@ def load_library():
     L.rsi_pool_submit.argtypes = L.rsi_pool_run.argtypes
     L.rsi_pool_submit.restype = C.c_uint64
     L.rsi_pool_wait.argtypes = [C.c_void_p, C.c_uint64]
+    L.rsi_hot_run_depth_device.argtypes = [C.c_void_p, C.POINTER(RsiParams), C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]
+    L.rsi_genome_text_open.argtypes = [C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_int, C.c_size_t,
+                                       C.POINTER(C.c_int)]
+    L.rsi_genome_text_open.restype = C.c_void_p
+    L.rsi_genome_text_next.argtypes = [C.c_void_p, C.POINTER(RsiGenomeChrom)]
+    L.rsi_genome_text_release.argtypes = [C.c_void_p, C.c_int]
+    L.rsi_genome_text_copy_depth.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]
+    L.rsi_genome_text_copy_depth.restype = C.c_int64
+    L.rsi_genome_text_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.rsi_genome_text_close.argtypes = [C.c_void_p]
+    L.rsi_genome_text_last_error.argtypes = [C.c_void_p]
+    L.rsi_genome_text_last_error.restype = C.c_char_p
     _lib = L
     return L
 
@@ -466,3 +485,134 @@ class RsiPool:
     def phase_table(self):
         t = self.times
         return {t.phase_name[i].decode(): t.phase_ms[i] for i in range(t.nphases)}
+
+
+class GenomeText:
+    """Streaming reader of a whole-genome depth file, "RNAME pos depth" lines (rsi_genome_text_*): iterating yields
+    (name, d_depth_ptr, n, stats) per chromosome in the file's order, its depth resident in HBM.  names / lengths: the
+    reference's sequences (the .fai's), looked up as read_fasta does; a name that is not among them comes with d_depth_ptr
+    None; names with "MT" or "." are skipped.  stats carries the slice counts and the depth buffer's "slot".
+
+    auto_release=True: a chromosome's buffer is given back when the next one is asked for (read it inside the loop, e.g.
+    with depth()).  auto_release=False: the caller gives it back with release(slot); at most max_resident buffers exist, and
+    the reader needs one for each new chromosome."""
+
+    def __init__(self, path, names, lengths, chunk_bytes=0, device=0, max_resident=2, auto_release=True):
+        self.lib = load_library()
+        enc = [n.encode() for n in names]
+        self._names = (C.c_char_p * max(len(enc), 1))(*enc)
+        self._lens = (C.c_int64 * max(len(enc), 1))(*[int(x) for x in lengths])
+        st = C.c_int(0)
+        self.g = self.lib.rsi_genome_text_open(int(device), os.fsencode(path), len(enc), self._names, self._lens, int(max_resident),
+                                               int(chunk_bytes), C.byref(st))
+        if not self.g:
+            raise RsiError(st.value, self.lib.rsi_hot_last_error(None).decode())
+        self.auto_release = auto_release
+        self._last = None
+
+    def close(self):
+        if getattr(self, "g", None):
+            self.lib.rsi_genome_text_close(self.g)
+            self.g = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def release(self, slot):
+        if slot is not None and slot >= 0:
+            self.lib.rsi_genome_text_release(self.g, int(slot))
+
+    def next(self):
+        """(name, d_depth_ptr or None, n, stats), or None at the end of the file; raises on errors (RsiError)."""
+        if self.auto_release and self._last is not None:
+            self.release(self._last)
+            self._last = None
+        c = RsiGenomeChrom()
+        rc = self.lib.rsi_genome_text_next(self.g, C.byref(c))
+        if rc == 0:
+            return None
+        if rc < 0:
+            raise RsiError(rc, self.lib.rsi_genome_text_last_error(self.g).decode())
+        stats = {f[0]: getattr(c.stats, f[0]) for f in RsiTextStats._fields_ if f[0] != "pad"}
+        stats["slot"] = c.slot
+        if c.slot >= 0:
+            self._last = c.slot
+        return c.name.decode(), (c.d_depth if c.slot >= 0 else None), c.n, stats
+
+    def __iter__(self):
+        while True:
+            item = self.next()
+            if item is None:
+                return
+            yield item
+
+    def depth(self, slot):
+        """A handed-over chromosome's depth as a host int32 array."""
+        n = self.lib.rsi_genome_text_copy_depth(self.g, int(slot), None, 0)
+        if n < 0:
+            raise RsiError(int(n), self.lib.rsi_genome_text_last_error(self.g).decode())
+        out = np.zeros(n, dtype=np.int32)
+        k = self.lib.rsi_genome_text_copy_depth(self.g, int(slot), out.ctypes.data, n)
+        if k < 0:
+            raise RsiError(int(k), self.lib.rsi_genome_text_last_error(self.g).decode())
+        return out
+
+    def kernel_ms(self):
+        """(boundary pass, parse pass): summed HIP-event milliseconds so far."""
+        b, p = C.c_double(0), C.c_double(0)
+        self.lib.rsi_genome_text_kernel_ms(self.g, C.byref(b), C.byref(p))
+        return b.value, p.value
+
+
+def run_genome_text(path, names, lengths, fasta, params=None, pool=None, device=0, workers=4, chunk_bytes=0):
+    """Every chromosome of a whole-genome depth file through an RsiPool, each submitted as soon as its depth is parsed:
+    {name: Result} in the file's order (names not among `names` are left out).  fasta: {name: uint8 array} or a callable
+    name -> uint8 array (the chromosome's sequence, length n)."""
+    import torch
+    params = params if params is not None else make_params()
+    own = pool is None
+    pool = pool or RsiPool(device, workers)
+    get = fasta if callable(fasta) else fasta.__getitem__
+    inflight = []   # (name, handle, slot, the device sequence: kept alive until the run is through)
+    out = {}
+    g = GenomeText(path, names, lengths, chunk_bytes=chunk_bytes, device=device, max_resident=workers + 1, auto_release=False)
+
+    def collect():
+        name, h, slot, _ = inflight.pop(0)
+        out[name] = pool.wait(h)[0]
+        g.release(slot)
+
+    try:
+        for name, d_depth, n, st in g:
+            if d_depth is None:
+                continue
+            while len(inflight) >= workers:
+                collect()
+            seq = np.ascontiguousarray(get(name), dtype=np.uint8)
+            if seq.size != n:
+                g.release(st["slot"])
+                raise ValueError(f"{name}: sequence of {seq.size} bases, the reference index says {n}")
+            d_fa = torch.from_numpy(seq).to(f"cuda:{device}")
+            torch.cuda.synchronize(device)
+            inflight.append((name, pool.submit(params, [(d_depth, d_fa.data_ptr(), n)]), st["slot"], d_fa))
+        while inflight:
+            collect()
+    finally:
+        for name, h, slot, _ in inflight:   # an error above: the queued runs still have to be waited for
+            try:
+                pool.wait(h)
+            except RsiError:
+                pass
+        g.close()
+        if own:
+            pool.close()
+    return out

@@ -1,8 +1,10 @@
 // cli.cpp -- `rsicnv rsi ...`: the reference's command line (rsi.cpp:1949-2068, 2069-2217) in
 // front of librsi_hot.so.  Same flags and defaults, same output file (header lines, columns,
-// number formatting).  Inputs: a depth file (-d RDFILE -c RNAME, parsed on the device) or a BAM
-// file (-b BAMFILE [-c RNAME], piled up on the device, calls annotated with RP / Q0 from its read
-// pairs); plot, stat and pin are outside the accelerated path and say so.
+// number formatting).  Inputs: a depth file (-d RDFILE -c RNAME, parsed on the device), a whole-genome
+// depth file (-d GENOME.depth without -c: "RNAME pos depth" lines, every chromosome in one pass, each run
+// as soon as its lines are parsed) or a BAM file (-b BAMFILE [-c RNAME], piled up on the device, calls
+// annotated with RP / Q0 from its read pairs); plot, stat and pin are outside the accelerated path
+//  and say so.
 #include <fcntl.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -20,6 +22,9 @@
 #include <mutex>
 #include <thread>
 #include <algorithm>
+#include <condition_variable>
+#include <deque>
+#include <iterator>
 
 #include "../../include/rsi_hot.h"
 #include "hostmath.h"
@@ -31,13 +36,14 @@ struct Options {
   rsi_params P;
   int minq = 0, min_baseQ = 13, device = 0;
   int gpus = 0;      // -gpus N: chromosomes spread over N devices, several in flight per device (0: one context, one at a time)
-  int workers = 4;   // -workers W: chromosomes in flight per device with -gpus
+  int workers = 4;   // -workers W: chromosomes in flight per device with -gpus, and on -gpu for a whole-genome depth file
   bool saverd = false, plot = true, plotfiles = false;
 };
 
 int usage() {
   std::cerr << "Usage:\n\n1. detect CNV\n\n"
             << "   rsicnv rsi <options> [-b BAMFILE | -d RDFILE -c RNAME ] -f REFFILE \n"
+            << "   rsicnv rsi <options> -d GENOME.depth -f REFFILE      (every chromosome of a whole-genome depth file)\n"
             << "\nOptions:\n"
             << "   -m   INT  bin size, default=101\n"
             << "   -q   INT  minimum mapping quality, default=0\n"
@@ -52,10 +58,13 @@ int usage() {
             << "   -gpu INT  HIP device to run on, default=0\n"
             << "   -gpus INT spread the chromosomes of a BAM over INT devices (longest first), several in flight per\n"
             << "             device (-workers INT, default=4); rows are written in BAM header order all the same\n"
+            << "   -workers INT chromosomes in flight (with -gpus; and on -gpu for a whole-genome depth file), default=4\n"
             << "\nNote:\n"
             << "   This build runs the read-depth hot path on an MI355X; input is a read depth file\n"
-            << "   (samtools mpileup BAM | cut -f2,4) with -c RNAME, or a coordinate-sorted BAM file (all\n"
-            << "   chromosomes with reads, or the one named with -c), plus the indexed reference.\n"
+            << "   (samtools mpileup BAM | cut -f2,4) with -c RNAME, a whole-genome depth file without -c\n"
+            << "   (samtools depth -a BAM, or samtools mpileup BAM | cut -f1,2,4: RNAME POS DEPTH, each\n"
+            << "   chromosome's lines together; rows follow the file's order), or a coordinate-sorted BAM file\n"
+            << "   (all chromosomes with reads, or the one named with -c), plus the indexed reference.\n"
             << "   -s saves the BAM's depth to OUT.RNAME_rd.\n"
             << std::endl;
   return 0;
@@ -156,7 +165,10 @@ struct ChromOutput {
   bool fatal = false;              // the single-chromosome modes stop here (the reference exits)
 };
 
-// One chromosome on one context: FASTA, depth (text or BAM, on the device), the hot path, RP / Q0, the rows.
+void report_chromosome(rsi_ctx* ctx, const Options& o, const std::string& chr, rsi_result* res, const rsi_text_stats* ts,
+                       const rsi_bam_stats* bs, double t_fasta, double t_path, std::ostringstream& info, ChromOutput& co);
+
+// One chromosome on one context, first half: FASTA, depth (text or BAM, on the device), the hot path; then report_chromosome.
 void process_chromosome(rsi_ctx* ctx, const Options& o, const std::string& chr, bool many, ChromOutput& co) {
   const bool from_bam = !o.bamfile.empty();
   std::ostringstream info;
@@ -188,13 +200,21 @@ void process_chromosome(rsi_ctx* ctx, const Options& o, const std::string& chr, 
     rsi_result_free(res);
     return;
   }
+  report_chromosome(ctx, o, chr, res, from_bam ? nullptr : &ts, from_bam ? &bs : nullptr, t1 - t0, t2 - t1, info, co);
+}
+
+// Second half, shared by every input: a chromosome's result (run on ctx, which still holds it) -> its log block, RP / Q0
+// (BAM input), its rows, its plots.  Frees res.
+void report_chromosome(rsi_ctx* ctx, const Options& o, const std::string& chr, rsi_result* res, const rsi_text_stats* ts,
+                       const rsi_bam_stats* bs, double t_fasta, double t_path, std::ostringstream& info, ChromOutput& co) {
+  const bool from_bam = bs != nullptr;
   co.populated = true;
   if (from_bam && o.saverd) {   // -s: write_rd_to_file, loaddata.cpp:340-344, 464-470
     const std::string dump = o.outfile + "." + chr + "_rd";
-    std::vector<int32_t> rd((size_t)bs.n);
-    rsi_hot_fetch_i32(ctx, "depth_in", rd.data(), bs.n);
+    std::vector<int32_t> rd((size_t)bs->n);
+    rsi_hot_fetch_i32(ctx, "depth_in", rd.data(), bs->n);
     FILE* f = fopen(dump.c_str(), "w");
-    if (f) { for (int64_t i = 0; i < bs.n; ++i) fprintf(f, "%lld\t%d\n", (long long)i + 1, rd[(size_t)i]); fclose(f); }
+    if (f) { for (int64_t i = 0; i < bs->n; ++i) fprintf(f, "%lld\t%d\n", (long long)i + 1, rd[(size_t)i]); fclose(f); }
     info << "RD of " << chr << " is saved to " << dump << "\n";
   }
   const rsi_chrom_stats* S = rsi_result_stats(res);
@@ -217,14 +237,14 @@ void process_chromosome(rsi_ctx* ctx, const Options& o, const std::string& chr, 
        << "second pass\n\tmedian of transformations : " << S->tmedian2 << "\n\tsigma : " << S->tsigma2 << "\n\tlamda : " << S->tlamda2 << "\n"
        << "Selected " << rsi_result_ncalls(res, 3) << " segments for testing\n"
        << "Found " << rsi_result_ncalls(res, 1) << " CNVs before sd_filters, " << rsi_result_ncalls(res, 0) << " written\n"
-       << "timing: fasta " << (t1 - t0) << " s, ";
+       << "timing: fasta " << t_fasta << " s, ";
   if (from_bam)
-    info << "BAM pileup " << bs.t_total_ms * 1e-3 << " s (" << bs.bytes_compressed << " bytes compressed, " << bs.records << " reads read, " << bs.used
-         << " counted, inflate " << bs.t_inflate_ms * 1e-3 << " s" << (bs.indexed ? ", index used" : ", no index: scanned from the top") << ")";
+    info << "BAM pileup " << bs->t_total_ms * 1e-3 << " s (" << bs->bytes_compressed << " bytes compressed, " << bs->records << " reads read, " << bs->used
+         << " counted, inflate " << bs->t_inflate_ms * 1e-3 << " s" << (bs->indexed ? ", index used" : ", no index: scanned from the top") << ")";
   else
-    info << "depth text " << ts.t_total_ms * 1e-3 << " s (" << ts.bytes << " bytes, " << ts.lines << " lines"
-         << (ts.fallback ? ", host parser: positions not increasing" : "") << ")";
-  info << ", whole device path " << (t2 - t1) << " s (" << S->t_device_ms << " ms on resident inputs)\n";
+    info << "depth text " << ts->t_total_ms * 1e-3 << " s (" << ts->bytes << " bytes, " << ts->lines << " lines"
+         << (ts->fallback ? ", host parser: positions not increasing" : "") << ")";
+  info << ", whole device path " << t_path << " s (" << S->t_device_ms << " ms on resident inputs)\n";
   if (from_bam) {   // if ( fp_in ) cnv_stat(fp_in, bamidx, cnvlist), rsi.cpp:2210
     if (rsi_result_annotate_bam(res, o.bamfile.c_str(), chr.c_str()) != RSI_OK) info << "RP / Q0 annotation failed: " << rsi_hot_last_error(nullptr) << "\n";
   }
@@ -285,6 +305,146 @@ void process_chromosome(rsi_ctx* ctx, const Options& o, const std::string& chr, 
   rsi_result_free(res);
 }
 
+// Columns of the first data line of a depth file (-1: none): a whole-genome file has three, RNAME POS DEPTH.
+int first_line_columns(const std::string& path) {
+  std::ifstream f(path.c_str());
+  std::string line, tok;
+  while (std::getline(f, line)) {
+    if (line.empty() || line[0] == '#') continue;
+    std::istringstream iss(line);
+    int k = 0;
+    while (iss >> tok) ++k;
+    if (k) return k;
+  }
+  return -1;
+}
+
+// The .fai's names and lengths, in its order (read_fasta's index, readref.cpp:10-86)
+bool read_fai(const std::string& fasta, std::vector<std::string>& names, std::vector<int64_t>& lens) {
+  std::ifstream fai((fasta + ".fai").c_str());
+  if (!fai) { std::cerr << "[read_fasta] Index file " << fasta << ".fai not found\n"; return false; }
+  std::string line, name;
+  while (std::getline(fai, line)) {
+    std::istringstream iss(line);
+    long len = 0;
+    if (iss >> name >> len) { names.push_back(name); lens.push_back(len); }
+  }
+  return true;
+}
+
+// -d GENOME.depth without -c: the main thread drives the genome reader (ingest.hip) and reads each finished chromosome's FASTA;
+// `workers` threads, each on a context of one pool on -gpu, run the chromosomes whose depth is already in HBM and format them
+// (report_chromosome, on the context that ran them: the plots fetch from it).  At most workers + 1 depth buffers exist: before
+// asking for the next chromosome the main thread waits until one of the `workers` it may hold has come back.  Returns the
+// outputs in the file's order of first appearance; false (message in `err`) when the file cannot be read through.
+bool run_genome(const Options& o, std::vector<std::string>& chroms, std::vector<ChromOutput>& outs, std::string& err, std::string& summary) {
+  std::vector<std::string> names;
+  std::vector<int64_t> lens;
+  if (!read_fai(o.reffile, names, lens)) { err = "no reference index"; return false; }
+  std::vector<const char*> cnames;
+  for (const std::string& nm : names) cnames.push_back(nm.c_str());
+  const int nwork = std::max(1, std::min(o.workers, 32));
+  int st = 0;
+  rsi_pool* pool = rsi_pool_create(o.device, nwork, &st);
+  if (!pool) { err = rsi_hot_last_error(nullptr); return false; }
+  rsi_genome_text* g = rsi_genome_text_open(o.device, o.rdfile.c_str(), (int)cnames.size(), cnames.data(), lens.data(), nwork + 1, 0, &st);
+  if (!g) { err = rsi_hot_last_error(nullptr); rsi_pool_destroy(pool); return false; }
+  const double t0 = now_s();
+
+  struct Job { size_t idx; rsi_genome_chrom c; std::string fasta; double t_fasta; };
+  std::deque<Job> jobs;
+  std::deque<ChromOutput> done_outs;   // stable references while the main thread appends
+  std::vector<int> returned;           // depth buffers whose chromosome has been run
+  std::mutex mu;
+  std::condition_variable cv_job, cv_back;
+  bool closing = false;
+  std::vector<std::thread> threads;
+  for (int w = 0; w < nwork; ++w)
+    threads.emplace_back([&, w]() {
+      rsi_ctx* ctx = rsi_pool_worker(pool, w);
+      for (;;) {
+        Job j;
+        {
+          std::unique_lock<std::mutex> lk(mu);
+          cv_job.wait(lk, [&] { return closing || !jobs.empty(); });
+          if (jobs.empty()) return;
+          j = std::move(jobs.front());
+          jobs.pop_front();
+        }
+        ChromOutput co;
+        std::ostringstream info;
+        const std::string chr = j.c.name;
+        info << "#processing " << chr << "\n";
+        rsi_result* res = nullptr;
+        const double t1 = now_s();
+        const int rc = rsi_hot_run_depth_device(ctx, &o.P, j.c.d_depth, reinterpret_cast<const uint8_t*>(j.fasta.data()), j.c.n, &res);
+        if (rc != RSI_OK) {   // as the BAM walk: a chromosome that has data and fails stops the run (rsi.cpp exits)
+          info << rsi_hot_last_error(ctx) << "\n";
+          co.log = info.str();
+          co.fatal = true;
+        } else {
+          report_chromosome(ctx, o, chr, res, &j.c.stats, nullptr, j.t_fasta, now_s() - t1, info, co);
+        }
+        std::lock_guard<std::mutex> lk(mu);
+        done_outs[j.idx] = std::move(co);
+        returned.push_back(j.c.slot);
+        cv_back.notify_one();
+      }
+    });
+  int held = 0;
+  bool ok = true;
+  for (;;) {
+    {   // hand the run chromosomes' buffers back; hold at most nwork
+      std::unique_lock<std::mutex> lk(mu);
+      for (;;) {
+        for (int slot : returned) { rsi_genome_text_release(g, slot); --held; }
+        returned.clear();
+        if (held < nwork) break;
+        cv_back.wait(lk, [&] { return !returned.empty(); });
+      }
+    }
+    rsi_genome_chrom c;
+    const int rc = rsi_genome_text_next(g, &c);
+    if (rc == 0) break;
+    if (rc < 0) { err = rsi_genome_text_last_error(g); ok = false; break; }
+    const std::string chr = c.name;
+    size_t idx;
+    { std::lock_guard<std::mutex> lk(mu); idx = done_outs.size(); done_outs.emplace_back(); }
+    chroms.push_back(chr);
+    if (c.slot < 0) {
+      std::lock_guard<std::mutex> lk(mu);
+      done_outs[idx].log = chr + " not found in fai index, skipped\n";
+      continue;
+    }
+    const double tf = now_s();
+    std::string fasta;
+    if (!read_fasta(o.reffile, chr, fasta)) {   // not fatal for a run over many chromosomes (process_chromosome with `many`)
+      rsi_genome_text_release(g, c.slot);
+      std::lock_guard<std::mutex> lk(mu);
+      done_outs[idx].log = "#processing " + chr + "\n";
+      continue;
+    }
+    Job j{idx, c, std::move(fasta), now_s() - tf};
+    std::lock_guard<std::mutex> lk(mu);
+    jobs.push_back(std::move(j));
+    ++held;
+    cv_job.notify_one();
+  }
+  { std::lock_guard<std::mutex> lk(mu); closing = true; }
+  cv_job.notify_all();
+  for (auto& t : threads) t.join();
+  double bound_ms = 0, parse_ms = 0;
+  rsi_genome_text_kernel_ms(g, &bound_ms, &parse_ms);
+  std::ostringstream sm;
+  sm << "timing: whole-genome depth text " << (now_s() - t0) << " s, " << chroms.size() << " chromosomes, boundary kernels " << bound_ms
+     << " ms, parse kernels " << parse_ms << " ms\n";
+  summary = sm.str();
+  rsi_genome_text_close(g);
+  rsi_pool_destroy(pool);
+  outs.assign(std::make_move_iterator(done_outs.begin()), std::make_move_iterator(done_outs.end()));
+  return ok;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -298,6 +458,13 @@ int main(int argc, char** argv) {
     return 0;
   }
   const bool from_bam = !o.bamfile.empty();
+  // -d without -c (-c defaults to 1-22XY): a whole-genome depth file, RNAME POS DEPTH
+  const bool genome = !from_bam && !o.rdfile.empty() && o.chr == "1-22XY";
+  if (genome) {
+    const int cols = first_line_columns(o.rdfile);
+    if (cols >= 0 && cols < 3) { std::cerr << "readdepth file and chromosome must be specified together" << std::endl; return usage(); }
+    if (o.gpus > 1) { std::cerr << "-gpus: a whole-genome depth file runs on one device (-gpu INT picks it)" << std::endl; return 1; }
+  }
   std::ofstream log((o.outfile + ".log").c_str());
   std::ostringstream hdr;
   hdr << "#command:   "; for (int i = 0; i < argc; ++i) hdr << argv[i] << " ";
@@ -338,7 +505,7 @@ int main(int argc, char** argv) {
     if (!co.populated) return;
     std::ofstream out(o.outfile.c_str(), wrote_header ? std::ios::app : std::ios::trunc);
     if (!wrote_header) {
-      if (!o.rdfile.empty()) out << "#input " << o.rdfile << " " << chr << std::endl;
+      if (!o.rdfile.empty()) out << "#input " << o.rdfile << (genome ? "" : " " + chr) << std::endl;
       if (from_bam) out << "#input " << o.bamfile << std::endl;
       if (o.P.gcadjust) out << "#GC adjusted\n";
       out << kHeader << std::endl;
@@ -348,6 +515,25 @@ int main(int argc, char** argv) {
     out.close();
     std::cerr << "output written to " << o.outfile << std::endl; log << "output written to " << o.outfile << std::endl;
   };
+
+  if (genome) {
+    std::vector<std::string> chroms;
+    std::vector<ChromOutput> outs;
+    std::string err, summary;
+    const bool ok = run_genome(o, chroms, outs, err, summary);
+    if (!ok) {   // nothing is written under OUT: the rows of a file that cannot be read through are not an answer
+      for (const ChromOutput& co : outs) { std::cerr << co.log; log << co.log; }
+      std::cerr << "rsicnv: " << err << std::endl; log << "rsicnv: " << err << std::endl;
+      remove(o.outfile.c_str());
+      return 1;
+    }
+    for (size_t i = 0; i < chroms.size(); ++i) {
+      emit(chroms[i], outs[i]);
+      if (outs[i].fatal) break;
+    }
+    std::cerr << summary; log << summary;
+    return 0;
+  }
 
   if (o.gpus <= 0 || !many) {   // the reference's own shape: one chromosome after the other on one context
     int st = 0;

@@ -3,6 +3,8 @@
 // The file bytes go through pinned double buffers; parsing, per-read work and the difference-array scan are kernels
 // (kernels_io.hip); BGZF inflation and the record walk stay on host threads (bam_host.cpp).
 #include "pipeline_internal.h"
+#include <memory>
+#include <unordered_set>
 
 using namespace rsik;
 using namespace rsip;
@@ -12,8 +14,9 @@ using rsih::Region;
 namespace {
 
 // The sequential parse loop (the reference's rules in the reference's order), used when the device
-// cannot prove that positions are strictly increasing.
-void parse_depth_text_host(const char* p, size_t sz, int64_t size, std::vector<int32_t>& rd, rsi_text_stats* st) {
+// cannot prove that positions are strictly increasing.  named: "RNAME pos depth" lines of one chromosome (the genome
+// reader's fallback): the name token and the blanks around it go first, lines without one are skipped.
+void parse_depth_text_host(const char* p, size_t sz, int64_t size, std::vector<int32_t>& rd, rsi_text_stats* st, bool named = false) {
   const char* end = p + sz;
   auto blank = [](char c) { return c == ' ' || c == '\t' || c == '\r' || c == '\v' || c == '\f'; };
   auto parse_int = [&](const char*& q, const char* e, long long& v) {
@@ -32,8 +35,15 @@ void parse_depth_text_host(const char* p, size_t sz, int64_t size, std::vector<i
     if (!eol) eol = end;
     if (eol > q && *q != '#') {
       const char* c = q;
+      bool data = true;
+      if (named) {
+        while (c < eol && blank(*c)) ++c;
+        const char* name = c;
+        while (c < eol && !blank(*c)) ++c;
+        data = c > name;
+      }
       long long pos = 0, d = 0;
-      if (parse_int(c, eol, pos)) {
+      if (data && parse_int(c, eol, pos)) {
         parse_int(c, eol, d);
         if (pos >= 1) {
           ++st->lines;
@@ -179,6 +189,16 @@ int rsi_hot_run_text(rsi_ctx* ctx, const rsi_params* p, const char* depth_path, 
   return rsi_hot_run_device(ctx, p, ctx->in_depth.p, ctx->in_fasta.p, n, out);
 }
 
+int rsi_hot_run_depth_device(rsi_ctx* ctx, const rsi_params* p, const void* d_depth, const uint8_t* fasta, int64_t n, rsi_result** out) {
+  if (!ctx || !p || !d_depth || !fasta || !out) return fail(ctx, RSI_ERR_BAD_ARG, "null argument");
+  if (n <= 0) return fail(ctx, RSI_ERR_BAD_ARG, "empty chromosome");
+  if (!ctx_enter(ctx)) return RSI_ERR_HIP;
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(ctx->in_fasta.ensure((size_t)n + 64));
+  HIPCHK(hipMemcpyAsync(ctx->in_fasta.p, fasta, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(CTX_SYNC());
+  return rsi_hot_run_device(ctx, p, d_depth, ctx->in_fasta.p, n, out);
+}
 
 int rsi_hot_load_depth_bam(rsi_ctx* ctx, const char* bam_path, const char* chrom, int minq, int min_baseq, rsi_bam_stats* stats) {
   rsi_bam_stats local;
@@ -410,6 +430,405 @@ int rsi_hot_run_bam(rsi_ctx* ctx, const rsi_params* p, const char* bam_path, con
   HIPCHK(hipMemcpyAsync(ctx->in_fasta.p, fasta, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return rsi_hot_run_device(ctx, p, ctx->in_depth.p, ctx->in_fasta.p, n, out);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// Whole-genome depth text ("RNAME pos depth", every chromosome in one file): a streaming reader that hands over each
+// chromosome's depth, resident in HBM, once its last line has been parsed, so that the caller can run it while the next one
+// is being parsed.  Per chunk of the file: one transfer, the boundary pass (kernels_io.hip, k_text_name_bounds), ONE small
+// read-back (the chunk's name changes and the counts of the chromosomes closed in the chunk before), then parse launches
+// over the chunk's segments -- each new name resolved to a depth buffer by the host in between.  Every chromosome's lines
+// give what its slice (its lines without the name) gives through rsi_hot_load_depth_text: same rules, same order proof
+// (per chromosome), same fallback to the sequential loop (over that chromosome's bytes only).
+struct rsi_genome_text {
+  struct Chrom { std::string name; int slot = -1; int64_t n = 0, start = 0, end = 0; double t0 = 0; bool report = true; };
+  struct Pending { hipEvent_t a, b; bool parse; };
+  int device = 0;
+  hipStream_t stream = nullptr;
+  hipEvent_t sync_ev = nullptr;
+  int fd = -1;
+  std::string path, err;
+  int64_t file_size = 0, consumed = 0;   // consumed: file offset behind the last chunk cut
+  std::vector<std::string> ref_names;
+  std::vector<int64_t> ref_len;
+  int max_resident = 1;
+  size_t chunk = 0;
+  unsigned bound_cap = 0, seg_cap = 0;
+  char* pin[2] = {nullptr, nullptr};
+  DevBuf text_dev[2], dread, dsegs, dwg;
+  PinBuf hread, hsegs;
+  size_t slots_bytes = 0;                // dread / hread: GenomeSlotStats[max_resident], then the count, then NameBound[bound_cap]
+  std::unique_ptr<DevBuf[]> slot_buf;
+  std::vector<int> slot_state;           // 0 free, 1 the reader's, 2 handed to the caller
+  std::vector<Chrom> awaiting;           // closed, their counts not read back yet (first-appearance order)
+  std::vector<rsi_genome_chrom> ready;   // complete, in order; handed out from the front
+  size_t ready_head = 0;
+  Chrom open;
+  bool open_valid = false;
+  std::unordered_set<std::string> seen;  // every name met so far (contiguity)
+  std::vector<int64_t> slot_n;           // length of the chromosome in each depth buffer
+  std::vector<char> carry;               // unfinished last line of the chunk read last
+  int cur = 0;
+  size_t len[2] = {0, 0};
+  int64_t foff[2] = {0, 0};
+  bool active = false, prefetched = false, done = false, failed = false;
+  std::vector<NameBound> bounds;
+  std::vector<std::string> bnames;
+  size_t cursor = 0, seg_used = 0;
+  long long range_start = 0;
+  std::vector<Pending> timed;
+  std::vector<hipEvent_t> ev_free;
+  double ms_bound = 0, ms_parse = 0;
+
+  ~rsi_genome_text() {
+    if (stream && sync_ev) (void)stream_wait(stream, sync_ev);   // nothing may still write the buffers freed below (deadline as every wait)
+    for (auto& t : timed) { ev_free.push_back(t.a); ev_free.push_back(t.b); }
+    for (hipEvent_t e : ev_free) (void)hipEventDestroy(e);
+    for (int b = 0; b < 2; ++b) if (pin[b]) (void)hipHostFree(pin[b]);
+    if (sync_ev) (void)hipEventDestroy(sync_ev);
+    if (stream) (void)hipStreamDestroy(stream);
+    if (fd >= 0) close(fd);
+  }
+  int fail_(int code, const std::string& m) { err = m; failed = true; set_global_error(m); return code; }
+  int hip_(hipError_t e, const char* what) { return e == hipSuccess ? RSI_OK : fail_(RSI_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
+  GenomeSlotStats* h_slots() { return hread.as<GenomeSlotStats>(); }
+  unsigned* h_count() { return reinterpret_cast<unsigned*>(hread.as<char>() + slots_bytes); }
+  NameBound* h_bounds() { return reinterpret_cast<NameBound*>(hread.as<char>() + slots_bytes + 16); }
+  unsigned* d_count() { return reinterpret_cast<unsigned*>(dread.as<char>() + slots_bytes); }
+  NameBound* d_bounds() { return reinterpret_cast<NameBound*>(dread.as<char>() + slots_bytes + 16); }
+
+  hipEvent_t event() {
+    if (!ev_free.empty()) { hipEvent_t e = ev_free.back(); ev_free.pop_back(); return e; }
+    hipEvent_t e = nullptr;
+    return hipEventCreate(&e) == hipSuccess ? e : nullptr;
+  }
+  // every wait: the project's deadline (stream_wait) and the launch errors of the chain in front of it
+  int wait() {
+    hipError_t e = stream_wait(stream, sync_ev);
+    const hipError_t launch = take_launch_error();
+    if (e == hipSuccess) e = launch;
+    if (e == hipErrorLaunchTimeOut) return fail_(RSI_ERR_HIP, "genome text: a wait gave up after 60 s with kernels still queued");
+    if (e != hipSuccess) return hip_(e, "genome text");
+    for (const Pending& t : timed) {
+      float ms = 0;
+      if (hipEventElapsedTime(&ms, t.a, t.b) == hipSuccess) (t.parse ? ms_parse : ms_bound) += ms;
+      ev_free.push_back(t.a); ev_free.push_back(t.b);
+    }
+    timed.clear();
+    seg_used = 0;   // the segment tables' transfers are through
+    return RSI_OK;
+  }
+
+  int find_ref(const std::string& x) const {   // read_fasta's rule (readref.cpp): name == X || name == "chr" + X
+    for (size_t i = 0; i < ref_names.size(); ++i) if (ref_names[i] == x || ref_names[i] == "chr" + x) return (int)i;
+    return -1;
+  }
+
+  // Next chunk of the file into pin[b]: the carried line first, cut behind the last line end.  len[b] == 0: end of file.
+  int fill(int b) {
+    char* buf = pin[b];
+    size_t have = carry.size();
+    if (have) memcpy(buf, carry.data(), have);
+    bool eof = false;
+    while (have < chunk) {
+      const ssize_t got = read(fd, buf + have, chunk - have);
+      if (got < 0) return fail_(RSI_ERR_INTERNAL, "read error on " + path);
+      if (got == 0) { eof = true; break; }
+      have += (size_t)got;
+    }
+    size_t l = have;
+    if (!eof) {
+      while (l > 0 && buf[l - 1] != '\n') --l;
+      if (l == 0) return fail_(RSI_ERR_UNSUPPORTED, "a line of the depth file is longer than the chunk (" + std::to_string(chunk) + " bytes)");
+    }
+    carry.assign(buf + l, buf + have);
+    len[b] = l; foff[b] = consumed; consumed += (int64_t)l;
+    return RSI_OK;
+  }
+
+  // counts of the closed chromosomes are in hread: hand them over (in order), the unsorted ones through the sequential loop
+  int finalize_awaiting() {
+    for (Chrom& c : awaiting) {
+      rsi_genome_chrom o;
+      memset(&o, 0, sizeof(o));
+      o.slot = c.slot; o.n = c.n;
+      snprintf(o.name, sizeof(o.name), "%s", c.name.c_str());
+      o.stats.bytes = c.end - c.start;
+      if (c.slot >= 0) {
+        const GenomeSlotStats& S = h_slots()[c.slot];
+        o.d_depth = slot_buf[(size_t)c.slot].p;
+        o.stats.lines = (int64_t)S.lines; o.stats.stored = (int64_t)S.stored; o.stats.beyond = (int64_t)S.beyond;
+        if (S.unsorted) {   // order-dependent rules in play: this chromosome's bytes through the sequential loop
+          o.stats.fallback = 1; o.stats.lines = o.stats.stored = o.stats.beyond = 0;
+          std::vector<char> text((size_t)(c.end - c.start));
+          size_t have = 0;
+          while (have < text.size()) {
+            const ssize_t got = pread(fd, text.data() + have, text.size() - have, (off_t)(c.start + (int64_t)have));
+            if (got <= 0) return fail_(RSI_ERR_INTERNAL, "read error on " + path);
+            have += (size_t)got;
+          }
+          std::vector<int32_t> rd((size_t)c.n, 0);
+          parse_depth_text_host(text.data(), have, c.n, rd, &o.stats, true);
+          if (int rc = hip_(hipMemcpyAsync(slot_buf[(size_t)c.slot].p, rd.data(), (size_t)c.n * 4, hipMemcpyHostToDevice, stream), "hipMemcpyAsync")) return rc;
+          if (int rc = wait()) return rc;
+        }
+      }
+      o.stats.t_total_ms = now_ms() - c.t0;
+      ready.push_back(o);
+    }
+    awaiting.clear();
+    return RSI_OK;
+  }
+  int sync_counts() {   // read the depth buffers' counts back (only when no chunk read-back is coming to carry them)
+    if (int rc = hip_(hipMemcpyAsync(hread.p, dread.p, slots_bytes, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync")) return rc;
+    if (int rc = wait()) return rc;
+    return finalize_awaiting();
+  }
+
+  void close_open(int64_t end_off) {
+    if (!open_valid) return;
+    open.end = end_off;
+    if (open.report) awaiting.push_back(open);
+    open_valid = false;
+  }
+
+  // The boundary pass over the chunk in pin[b] and its one read-back.  Too many name changes for the list: the chunk is cut
+  // shorter (at a line end) and the rest goes in front of the next one.
+  int start_chunk(int b) {
+    if (int rc = hip_(hipMemcpyAsync(text_dev[b].p, pin[b], len[b], hipMemcpyHostToDevice, stream), "hipMemcpyAsync")) return rc;
+    const size_t first = std::min<size_t>(bound_cap, 4096);
+    for (;;) {
+      if (int rc = hip_(hipMemsetAsync(d_count(), 0, 16, stream), "hipMemsetAsync")) return rc;
+      hipEvent_t a = event(), e = event();
+      if (a) (void)hipEventRecord(a, stream);
+      launch_text_name_bounds(text_dev[b].p, (long long)len[b], d_bounds(), d_count(), bound_cap, stream);
+      if (a && e) { (void)hipEventRecord(e, stream); timed.push_back({a, e, false}); }
+      if (int rc = hip_(hipMemcpyAsync(hread.p, dread.p, slots_bytes + 16 + first * sizeof(NameBound), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync")) return rc;
+      if (int rc = wait()) return rc;
+      if (*h_count() <= bound_cap) break;
+      size_t l = len[b] / 2;
+      while (l > 0 && pin[b][l - 1] != '\n') --l;
+      if (l == 0) return fail_(RSI_ERR_INTERNAL, "genome text: no line end in the first half of a chunk");
+      carry.insert(carry.begin(), pin[b] + l, pin[b] + len[b]);
+      consumed -= (int64_t)(len[b] - l);
+      len[b] = l;
+    }
+    const unsigned k = *h_count();
+    if (k > first) {
+      if (int rc = hip_(hipMemcpyAsync(h_bounds() + first, d_bounds() + first, (k - first) * sizeof(NameBound), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync")) return rc;
+      if (int rc = wait()) return rc;
+    }
+    if (int rc = finalize_awaiting()) return rc;
+    bounds.assign(h_bounds(), h_bounds() + k);
+    std::sort(bounds.begin(), bounds.end(), [](const NameBound& x, const NameBound& y) { return x.line < y.line; });
+    bnames.clear();
+    for (const NameBound& nb : bounds) {
+      if (nb.len >= (int)sizeof(rsi_genome_chrom::name)) return fail_(RSI_ERR_UNSUPPORTED, "genome text: a chromosome name is longer than 255 bytes");
+      bnames.emplace_back(pin[b] + nb.name, (size_t)nb.len);
+    }
+    cursor = 0; range_start = 0;
+    return RSI_OK;
+  }
+
+  // Parse launches over the chunk from range_start on.  1: the chunk is through; 2: stopped at a new chromosome for want of a
+  // free depth buffer (range_start / cursor point at it); < 0: error.
+  int issue(int b) {
+    const char* d_text = static_cast<const char*>(text_dev[b].p);
+    for (;;) {
+      const long long begin = range_start;
+      long long end = (long long)len[b];
+      GenomeSeg* segs = hsegs.as<GenomeSeg>() + seg_used;
+      int nseg = 0;
+      auto seg_of_open = [&](long long start) {
+        const bool buf = open_valid && open.slot >= 0;
+        return GenomeSeg{start, buf ? open.n : 0, buf ? slot_buf[(size_t)open.slot].as<int32_t>() : nullptr, buf ? open.slot : -1, 0};
+      };
+      segs[nseg++] = seg_of_open(begin);
+      bool stalled = false;
+      while (cursor < bounds.size()) {
+        const NameBound& B = bounds[cursor];
+        const std::string& name = bnames[cursor];
+        if (open_valid && name == open.name) { ++cursor; continue; }   // the chunk's first data line, continuing the chromosome
+        if (seen.count(name))
+          return fail_(RSI_ERR_BAD_ARG, "genome text: the lines of chromosome " + name + " are not contiguous: it comes back at byte " +
+                                              std::to_string(foff[b] + B.line) + " after other chromosomes");
+        const bool filtered = name.find("MT") != std::string::npos || name.find('.') != std::string::npos;   // the BAM walk's filter
+        const int ref = filtered ? -1 : find_ref(name);
+        int slot = -1;
+        if (ref >= 0) {
+          for (int s = 0; s < max_resident; ++s) if (slot_state[(size_t)s] == 0) { slot = s; break; }
+          if (slot < 0) {   // the open chromosome is complete at B: parse up to there, hand it over, resume here once a buffer is free
+            close_open(foff[b] + B.line);
+            end = B.line; stalled = true;
+            break;
+          }
+        }
+        if (nseg == kMaxGenomeSegs) { end = B.line; break; }
+        close_open(foff[b] + B.line);
+        open = Chrom();
+        open.name = name; open.start = foff[b] + B.line; open.t0 = now_ms(); open.report = !filtered;
+        open_valid = true;
+        seen.insert(name);
+        if (ref >= 0) {
+          const int64_t n = ref_len[(size_t)ref];
+          if (n <= 0 || n >= (1ll << 31) - 4096) return fail_(RSI_ERR_BAD_ARG, "chromosome length must be in (0, 2^31): " + name);
+          DevBuf& d = slot_buf[(size_t)slot];
+          if (int rc = hip_(d.ensure((size_t)(n + 4) * 4), "hipMalloc")) return rc;
+          if (int rc = hip_(hipMemsetAsync(d.p, 0, (size_t)(n + 4) * 4, stream), "hipMemsetAsync")) return rc;
+          if (int rc = hip_(hipMemsetAsync(dread.as<GenomeSlotStats>() + slot, 0, sizeof(GenomeSlotStats), stream), "hipMemsetAsync")) return rc;
+          slot_state[(size_t)slot] = 1;
+          open.slot = slot; open.n = n; slot_n[(size_t)slot] = n;
+        }
+        if (segs[nseg - 1].start == B.line) segs[nseg - 1] = seg_of_open(B.line);
+        else segs[nseg++] = seg_of_open(B.line);
+        ++cursor;
+      }
+      if (end > begin) {
+        GenomeSeg* d_segs = dsegs.as<GenomeSeg>() + seg_used;
+        if (int rc = hip_(hipMemcpyAsync(d_segs, segs, (size_t)nseg * sizeof(GenomeSeg), hipMemcpyHostToDevice, stream), "hipMemcpyAsync")) return rc;
+        seg_used += (size_t)nseg;
+        hipEvent_t a = event(), e = event();
+        if (a) (void)hipEventRecord(a, stream);
+        launch_parse_genome_text(d_text, begin, end, d_segs, nseg, dread.as<GenomeSlotStats>(), dwg.as<long long>(), stream);
+        if (a && e) { (void)hipEventRecord(e, stream); timed.push_back({a, e, true}); }
+      }
+      range_start = end;
+      if (stalled) return 2;
+      if (cursor == bounds.size() && end == (long long)len[b]) return 1;
+    }
+  }
+
+  // one step: a chunk started, parsed as far as the depth buffers allow, the next one read from the file meanwhile
+  int advance() {
+    if (!active) {
+      if (!prefetched) if (int rc = fill(cur)) return rc;
+      prefetched = false;
+      if (len[cur] == 0) {   // end of the file
+        close_open(file_size);
+        if (int rc = sync_counts()) return rc;
+        done = true;
+        return RSI_OK;
+      }
+      if (int rc = start_chunk(cur)) return rc;
+      active = true;
+    }
+    const int r = issue(cur);
+    if (r < 0) return r;
+    if (r == 1) {   // while the device parses this chunk, the next one comes off the disk
+      active = false;
+      if (int rc = fill(cur ^ 1)) return rc;
+      prefetched = true;
+      cur ^= 1;
+      return RSI_OK;
+    }
+    if (!awaiting.empty()) return sync_counts();   // stalled: hand over what is complete, so that the caller can release
+    return fail_(RSI_ERR_BAD_ARG, "genome text: every depth buffer (max_resident = " + std::to_string(max_resident) +
+                                      ") is held by the caller: release one before asking for the next chromosome");
+  }
+};
+
+extern "C" {
+
+rsi_genome_text* rsi_genome_text_open(int device, const char* path, int nref, const char* const* names, const int64_t* lengths,
+                                      int max_resident, size_t chunk_bytes, int* status) {
+  int st_local = 0;
+  int* st = status ? status : &st_local;
+  *st = RSI_OK;
+  try {
+    if (!path || nref < 0 || (nref > 0 && (!names || !lengths)) || max_resident < 1) { set_global_error("rsi_genome_text_open: bad argument"); *st = RSI_ERR_BAD_ARG; return nullptr; }
+    if (chunk_bytes != 0 && (chunk_bytes < 64 || chunk_bytes > (size_t(1) << 30))) { set_global_error("rsi_genome_text_open: chunk_bytes must be 0 or in [64, 2^30]"); *st = RSI_ERR_BAD_ARG; return nullptr; }
+    std::unique_ptr<rsi_genome_text> g(new rsi_genome_text());
+    auto bad = [&](int code) { *st = code; return nullptr; };
+    g->device = device; g->path = path; g->max_resident = max_resident;
+    g->chunk = chunk_bytes ? chunk_bytes : kTextChunk;
+    for (int i = 0; i < nref; ++i) { g->ref_names.emplace_back(names[i] ? names[i] : ""); g->ref_len.push_back(lengths[i]); }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_global_error("no HIP device: rsicnv_amd has no CPU fallback"); return bad(RSI_ERR_NO_DEVICE); }
+    if (device < 0 || device >= ndev) { set_global_error("rsi_genome_text_open: no such device"); return bad(RSI_ERR_BAD_ARG); }
+    if (hipSetDevice(device) != hipSuccess) { set_global_error("hipSetDevice failed"); return bad(RSI_ERR_HIP); }
+    drain_stale_errors();
+    g->fd = open(path, O_RDONLY);
+    if (g->fd < 0) { set_global_error(std::string("Cannot open file ") + path); return bad(RSI_ERR_BAD_ARG); }
+    struct stat sb;
+    if (fstat(g->fd, &sb) != 0) { set_global_error(std::string("Cannot stat file ") + path); return bad(RSI_ERR_BAD_ARG); }
+    g->file_size = (int64_t)sb.st_size;
+    if (hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess ||
+        hipEventCreateWithFlags(&g->sync_ev, hipEventDisableTiming) != hipSuccess) { set_global_error("genome text: stream / event creation failed"); return bad(RSI_ERR_HIP); }
+    // name changes per chunk: every 64 bytes of text at most before the chunk is cut shorter (start_chunk)
+    g->bound_cap = (unsigned)std::max<size_t>(1024, g->chunk / 64);
+    g->seg_cap = 2 * g->bound_cap + 2 * kMaxGenomeSegs;
+    g->slots_bytes = ((size_t)max_resident * sizeof(GenomeSlotStats) + 255) & ~size_t(255);
+    const size_t read_bytes = g->slots_bytes + 16 + (size_t)g->bound_cap * sizeof(NameBound);
+    for (int b = 0; b < 2; ++b)
+      if (hipHostMalloc(reinterpret_cast<void**>(&g->pin[b]), g->chunk, hipHostMallocDefault) != hipSuccess) { g->pin[b] = nullptr; set_global_error("out of pinned host memory for the text staging"); return bad(RSI_ERR_INTERNAL); }
+    if (g->text_dev[0].ensure(g->chunk) != hipSuccess || g->text_dev[1].ensure(g->chunk) != hipSuccess || g->dread.ensure(read_bytes) != hipSuccess ||
+        g->dsegs.ensure((size_t)g->seg_cap * sizeof(GenomeSeg)) != hipSuccess ||
+        g->dwg.ensure((size_t)genome_parse_workgroups((long long)g->chunk) * 4 * sizeof(long long)) != hipSuccess ||
+        g->hread.ensure(read_bytes) != hipSuccess || g->hsegs.ensure((size_t)g->seg_cap * sizeof(GenomeSeg)) != hipSuccess) {
+      set_global_error("genome text: out of device or pinned memory for the staging buffers");
+      return bad(RSI_ERR_HIP);
+    }
+    g->slot_buf.reset(new DevBuf[(size_t)max_resident]);
+    g->slot_state.assign((size_t)max_resident, 0);
+    g->slot_n.assign((size_t)max_resident, 0);
+    return g.release();
+  } catch (const std::exception& e) {
+    set_global_error(std::string("rsi_genome_text_open: ") + e.what());
+    *st = RSI_ERR_INTERNAL;
+    return nullptr;
+  }
+}
+
+int rsi_genome_text_next(rsi_genome_text* g, rsi_genome_chrom* out) {
+  if (!g || !out) return RSI_ERR_BAD_ARG;
+  if (g->failed) return RSI_ERR_BAD_ARG;
+  try {
+    if (hipSetDevice(g->device) != hipSuccess) return g->fail_(RSI_ERR_HIP, "hipSetDevice failed");
+    while (g->ready_head == g->ready.size() && !g->done) {
+      g->ready.erase(g->ready.begin(), g->ready.begin() + (ptrdiff_t)g->ready_head);
+      g->ready_head = 0;
+      if (int rc = g->advance()) return rc;
+    }
+    if (g->ready_head == g->ready.size()) return 0;
+    *out = g->ready[g->ready_head++];
+    if (out->slot >= 0) g->slot_state[(size_t)out->slot] = 2;
+    return 1;
+  } catch (const std::exception& e) {
+    return g->fail_(RSI_ERR_INTERNAL, std::string("rsi_genome_text_next: ") + e.what());
+  }
+}
+
+void rsi_genome_text_release(rsi_genome_text* g, int slot) {
+  if (g && slot >= 0 && slot < g->max_resident && g->slot_state[(size_t)slot] == 2) g->slot_state[(size_t)slot] = 0;
+}
+
+int64_t rsi_genome_text_copy_depth(rsi_genome_text* g, int slot, int32_t* out, int64_t cap) {
+  if (!g || slot < 0 || slot >= g->max_resident || g->slot_state[(size_t)slot] != 2) return RSI_ERR_BAD_ARG;
+  if (g->failed) return RSI_ERR_BAD_ARG;
+  const int64_t n = g->slot_n[(size_t)slot];
+  if (!out) return n;
+  const int64_t k = std::min(n, cap);
+  if (hipSetDevice(g->device) != hipSuccess) return g->fail_(RSI_ERR_HIP, "hipSetDevice failed");
+  if (int rc = g->hip_(hipMemcpyAsync(out, g->slot_buf[(size_t)slot].p, (size_t)k * 4, hipMemcpyDeviceToHost, g->stream), "hipMemcpyAsync")) return rc;
+  if (int rc = g->wait()) return rc;
+  return k;
+}
+
+int rsi_genome_text_kernel_ms(const rsi_genome_text* g, double* bound_ms, double* parse_ms) {
+  if (!g) return RSI_ERR_BAD_ARG;
+  if (bound_ms) *bound_ms = g->ms_bound;
+  if (parse_ms) *parse_ms = g->ms_parse;
+  return RSI_OK;
+}
+
+const char* rsi_genome_text_last_error(const rsi_genome_text* g) { return g ? g->err.c_str() : "null reader"; }
+
+void rsi_genome_text_close(rsi_genome_text* g) {
+  if (!g) return;
+  (void)hipSetDevice(g->device);
+  delete g;
 }
 
 }  // extern "C"

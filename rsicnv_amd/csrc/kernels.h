@@ -455,6 +455,25 @@ int text_parse_workgroups(long long nbytes);
 void launch_parse_depth_text(const void* text, long long nbytes, long long size, int32_t* depth, long long* wg_first,
                              long long* wg_max, TextParseStats* stats, hipStream_t stream);
 
+// ---- named lines: "RNAME pos depth", every chromosome of a genome in one file (kernels_io.hip) ----
+// Boundary pass: every data line (not empty, first byte not '#', a name token after the leading blanks) whose name differs
+// from the previous data line's within [0, nbytes) -- the chunk's first data line always -- is one entry, in no particular
+// order: {line start, name start, name length}.  count (zeroed by the caller) receives how many there were, also beyond cap.
+struct NameBound { long long line; int32_t name, len; };
+void launch_text_name_bounds(const void* text, long long nbytes, NameBound* bounds, unsigned int* count, unsigned int cap,
+                             hipStream_t stream);
+// Parse pass over [begin, end) of a chunk: the segments' starts ascend, segs[0].start <= begin, nseg <= kMaxGenomeSegs.  Every
+// line belongs to the last segment that starts at or before it; a segment without a depth buffer (slot < 0) is skipped.  The
+// rest of a line behind its name is read like a "pos depth" line; counts and the order proof go to slots[slot].
+struct GenomeSeg { long long start, n; int32_t* depth; int32_t slot, pad; };
+struct GenomeSlotStats { unsigned long long lines, stored, beyond; unsigned int unsorted, pad; long long last_pos; /* 0: none yet */ };
+constexpr int kMaxGenomeSegs = 512;
+int genome_parse_workgroups(long long nbytes);
+// wg: 4 * genome_parse_workgroups(end - begin) words of scratch (per workgroup: first segment, first position, last segment,
+// last position) that the order fold reads.
+void launch_parse_genome_text(const void* text, long long begin, long long end, const GenomeSeg* segs, int nseg,
+                              GenomeSlotStats* slots, long long* wg, hipStream_t stream);
+
 // ---- BAM pileup -> depth (kernels_io.hip; load_data_from_bam, loaddata.cpp:277-333 + resolve_cigar_pos, samfunctions.cpp:38-100) ----
 struct BamDepthStats { unsigned long long used, runs, malformed; };   // malformed: records whose fields overrun their block_size (skipped)
 // One thread per record: data = inflated BAM bytes, rec_off[i] = offset of record i's block_size field.  diff: int32[n + 1], zeroed

@@ -100,7 +100,203 @@ __global__ __launch_bounds__(kThreads) void k_parse_depth_text(const unsigned ch
   }
 }
 
+// ---- named lines (whole-genome files): "RNAME pos depth" ----
+// A data line is a line that is not empty, does not start with '#' and has a name token: leading blanks, then the bytes up to
+// the next blank.  What follows the name is read exactly like a "pos depth" line above, so that every chromosome's lines give
+// what its slice (the same lines without the name) gives through k_parse_depth_text.
+
+// The line that starts at s: its end e (a '\n' or `lim`) and its name token [ns, ne); ns == ne when it is no data line.
+__device__ inline void line_name(const unsigned char* __restrict__ t, long long s, long long lim, long long& e, long long& ns, long long& ne) {
+  e = s;
+  while (e < lim && t[e] != '\n') ++e;
+  ns = ne = s;
+  if (e == s || t[s] == '#') return;
+  long long q = s;
+  while (q < e && is_blank(t[q])) ++q;
+  ns = q;
+  while (q < e && !is_blank(t[q])) ++q;
+  ne = q;
+}
+
+__device__ inline bool same_name(const unsigned char* __restrict__ t, long long a, long long alen, long long b, long long blen) {
+  if (alen != blen) return false;
+  for (long long k = 0; k < alen; ++k) if (t[a + k] != t[b + k]) return false;
+  return true;
+}
+
+// Boundary pass: one entry per data line whose name is not the previous data line's.  A thread compares the first data line
+// of its span with the data line before it (walking back over comment and empty lines: each such stretch is walked by one
+// thread only), the others with the thread's own previous one.
+__global__ __launch_bounds__(kThreads) void k_text_name_bounds(const unsigned char* __restrict__ text, long long nbytes,
+                                                               NameBound* __restrict__ bounds, unsigned int* __restrict__ count,
+                                                               unsigned int cap) {
+  const long long b0 = ((long long)blockIdx.x * kThreads + threadIdx.x) * kSpan;
+  if (b0 >= nbytes) return;
+  const long long b1 = b0 + kSpan < nbytes ? b0 + kSpan : nbytes;
+  long long pns = -1, pne = -1;   // name of the previous data line, once known
+  for (long long s = b0; s < b1; ++s) {
+    if (s != 0 && text[s - 1] != '\n') continue;
+    long long e, ns, ne;
+    line_name(text, s, nbytes, e, ns, ne);
+    if (ns == ne) continue;
+    if (pns < 0) {   // first data line of the span: find the data line in front of it
+      long long p = s;
+      while (p > 0) {
+        long long ls = p - 1;                              // text[p - 1] is the '\n' that ends the line before
+        while (ls > 0 && text[ls - 1] != '\n') --ls;
+        long long e2, ns2, ne2;
+        line_name(text, ls, p - 1, e2, ns2, ne2);
+        if (ns2 != ne2) { pns = ns2; pne = ne2; break; }
+        p = ls;
+      }
+    }
+    if (pns < 0 || !same_name(text, pns, pne - pns, ns, ne - ns)) {
+      const unsigned int k = atomicAdd(count, 1u);
+      if (k < cap) bounds[k] = NameBound{s, (int32_t)ns, (int32_t)(ne - ns)};
+    }
+    pns = ns; pne = ne;
+  }
+}
+
+// Parse pass.  The order proof of k_parse_depth_text, per chromosome: within a thread, within a workgroup (thread 0 over the
+// threads' first and last counted lines), then k_genome_order_fold across the workgroups and against the chromosome's last
+// position in the chunks before.  Counts go out with one set of atomics per workgroup when the workgroup's lines end in one
+// segment (the common case: a chromosome is millions of lines), per thread otherwise.
+__global__ __launch_bounds__(kThreads) void k_parse_genome_text(const unsigned char* __restrict__ text, long long begin, long long end,
+                                                                const GenomeSeg* __restrict__ segs, int nseg,
+                                                                GenomeSlotStats* __restrict__ slots, long long* __restrict__ wg) {
+  __shared__ long long s_start[kMaxGenomeSegs];
+  __shared__ int s_segA[kThreads], s_segB[kThreads];
+  __shared__ long long s_firstA[kThreads], s_lastB[kThreads];
+  __shared__ int s_lo, s_hi;
+  for (int i = threadIdx.x; i < nseg; i += kThreads) s_start[i] = segs[i].start;
+  if (threadIdx.x == 0) { s_lo = 0x7fffffff; s_hi = -1; }
+  __syncthreads();
+  const long long b0 = begin + ((long long)blockIdx.x * kThreads + threadIdx.x) * kSpan;
+  int segA = -1, segB = -1;            // segments of the thread's first / last counted line
+  long long firstA = -1, lastB = -1;   // their positions
+  int cseg = -1;                       // segment the counters below belong to
+  unsigned lines = 0, stored = 0, beyond = 0;
+  bool bad = false;
+  auto flush = [&]() {
+    if (cseg >= 0 && (lines | bad)) {
+      GenomeSlotStats* S = &slots[segs[cseg].slot];
+      if (lines) atomicAdd(&S->lines, (unsigned long long)lines);
+      if (stored) atomicAdd(&S->stored, (unsigned long long)stored);
+      if (beyond) atomicAdd(&S->beyond, (unsigned long long)beyond);
+      if (bad) atomicOr(&S->unsorted, 1u);
+    }
+    lines = stored = beyond = 0; bad = false;
+  };
+  if (b0 < end) {
+    const long long b1 = b0 + kSpan < end ? b0 + kSpan : end;
+    int g = -1;
+    for (long long s = b0; s < b1; ++s) {
+      if (s != 0 && text[s - 1] != '\n') continue;
+      long long e, ns, ne;
+      line_name(text, s, end, e, ns, ne);
+      if (ns == ne) continue;
+      if (g < 0) {   // last segment starting at or before s
+        int lo = 0, hi = nseg - 1;
+        while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (s_start[mid] <= s) lo = mid; else hi = mid - 1; }
+        g = lo;
+      }
+      while (g + 1 < nseg && s_start[g + 1] <= s) ++g;
+      const GenomeSeg& G = segs[g];
+      if (G.slot < 0) continue;
+      long long q = ne, pos = 0, d = 0;
+      if (!parse_int(text, q, e, pos)) continue;
+      parse_int(text, q, e, d);
+      if (pos < 1) continue;
+      if (g != cseg) { flush(); cseg = g; }
+      ++lines;
+      if (segB == g && pos <= lastB) bad = true;
+      if (segA < 0) { segA = g; firstA = pos; }
+      segB = g; lastB = pos;
+      if (pos >= G.n) { ++beyond; continue; }
+      G.depth[pos - 1] = (int32_t)d;
+      ++stored;
+    }
+  }
+  s_segA[threadIdx.x] = segA; s_segB[threadIdx.x] = segB;
+  s_firstA[threadIdx.x] = firstA; s_lastB[threadIdx.x] = lastB;
+  if (cseg >= 0 && (lines | bad)) { atomicMin(&s_lo, cseg); atomicMax(&s_hi, cseg); }
+  __syncthreads();
+  if (threadIdx.x == 0) {   // the threads in order: a counted line must lie beyond the previous one of its segment
+    int run_seg = -1, wseg = -1;
+    long long run_last = -1, wfirst = -1;
+    for (int t = 0; t < kThreads; ++t) {
+      if (s_segA[t] < 0) continue;
+      if (wseg < 0) { wseg = s_segA[t]; wfirst = s_firstA[t]; }
+      if (s_segA[t] == run_seg && s_firstA[t] <= run_last) atomicOr(&slots[segs[run_seg].slot].unsorted, 1u);
+      run_seg = s_segB[t]; run_last = s_lastB[t];
+    }
+    long long* r = wg + 4 * (long long)blockIdx.x;
+    r[0] = wseg; r[1] = wfirst; r[2] = run_seg; r[3] = run_last;
+  }
+  if (s_lo == s_hi) {   // every thread's remaining counts are one segment's: one set of atomics for the workgroup
+    const bool mine = cseg == s_lo && (lines | bad);
+    unsigned l = mine ? lines : 0, st = mine ? stored : 0, bd = mine ? beyond : 0, bb = mine && bad ? 1u : 0u;
+    for (int d = 32; d >= 1; d >>= 1) { l += __shfl_xor(l, d); st += __shfl_xor(st, d); bd += __shfl_xor(bd, d); bb |= __shfl_xor(bb, d); }
+    __shared__ unsigned s_tot[kThreads / 64][4];
+    if ((threadIdx.x & 63) == 0) { s_tot[threadIdx.x >> 6][0] = l; s_tot[threadIdx.x >> 6][1] = st; s_tot[threadIdx.x >> 6][2] = bd; s_tot[threadIdx.x >> 6][3] = bb; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      unsigned long long t0 = 0, t1 = 0, t2 = 0; unsigned t3 = 0;
+      for (int w = 0; w < kThreads / 64; ++w) { t0 += s_tot[w][0]; t1 += s_tot[w][1]; t2 += s_tot[w][2]; t3 |= s_tot[w][3]; }
+      GenomeSlotStats* S = &slots[segs[s_lo].slot];
+      if (t0) atomicAdd(&S->lines, t0);
+      if (t1) atomicAdd(&S->stored, t1);
+      if (t2) atomicAdd(&S->beyond, t2);
+      if (t3) atomicOr(&S->unsorted, 1u);
+    }
+  } else {
+    flush();
+  }
+}
+
+// Across the workgroups of one parse launch: a workgroup's first counted line against the last one of the nearest workgroup
+// before it that counted any (same segment only); the launch's first counted line against its chromosome's last position so
+// far; the launch's last counted line becomes its chromosome's last position.  One workgroup.
+__global__ __launch_bounds__(kThreads) void k_genome_order_fold(const long long* __restrict__ wg, int nwg, const GenomeSeg* __restrict__ segs,
+                                                                GenomeSlotStats* __restrict__ slots) {
+  __shared__ int s_first, s_last;
+  if (threadIdx.x == 0) { s_first = 0x7fffffff; s_last = -1; }
+  __syncthreads();
+  for (int w = threadIdx.x; w < nwg; w += kThreads) {
+    if (wg[4 * (long long)w] < 0) continue;
+    atomicMin(&s_first, w); atomicMax(&s_last, w);
+    int p = w - 1;
+    while (p >= 0 && wg[4 * (long long)p] < 0) --p;
+    if (p >= 0 && wg[4 * (long long)p + 2] == wg[4 * (long long)w] && wg[4 * (long long)w + 1] <= wg[4 * (long long)p + 3])
+      atomicOr(&slots[segs[wg[4 * (long long)w]].slot].unsorted, 1u);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && s_last >= 0) {
+    GenomeSlotStats* F = &slots[segs[wg[4 * (long long)s_first]].slot];
+    if (F->last_pos > 0 && wg[4 * (long long)s_first + 1] <= F->last_pos) F->unsorted = 1u;
+    slots[segs[wg[4 * (long long)s_last + 2]].slot].last_pos = wg[4 * (long long)s_last + 3];
+  }
+}
+
 }  // namespace
+
+int genome_parse_workgroups(long long nbytes) { return (int)((nbytes + kTile - 1) / kTile); }
+
+void launch_text_name_bounds(const void* text, long long nbytes, NameBound* bounds, unsigned int* count, unsigned int cap, hipStream_t stream) {
+  const int grid = (int)((nbytes + kTile - 1) / kTile);
+  if (grid <= 0) return;
+  RSI_LAUNCH(k_text_name_bounds, dim3(grid), dim3(kThreads), 0, stream, static_cast<const unsigned char*>(text), nbytes, bounds, count, cap);
+}
+
+void launch_parse_genome_text(const void* text, long long begin, long long end, const GenomeSeg* segs, int nseg, GenomeSlotStats* slots,
+                              long long* wg, hipStream_t stream) {
+  const int grid = genome_parse_workgroups(end - begin);
+  if (grid <= 0 || nseg <= 0) return;
+  RSI_LAUNCH(k_parse_genome_text, dim3(grid), dim3(kThreads), 0, stream, static_cast<const unsigned char*>(text), begin, end, segs, nseg,
+             slots, wg);
+  RSI_LAUNCH(k_genome_order_fold, dim3(1), dim3(kThreads), 0, stream, wg, grid, segs, slots);
+}
 
 int text_parse_workgroups(long long nbytes) { return (int)((nbytes + kTile - 1) / kTile); }
 

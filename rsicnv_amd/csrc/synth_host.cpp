@@ -153,6 +153,33 @@ extern "C" int rsi_synth_write_depth_text(const char* path, const int32_t* depth
   return fclose(f) == 0 ? 0 : -3;
 }
 
+// "RNAME<TAB>pos<TAB>depth" lines of one chromosome, appended to `path` (a whole-genome depth file, as samtools depth -a writes it)
+extern "C" int rsi_synth_append_genome_text(const char* path, const char* chrom, const int32_t* depth, int64_t n) {
+  if (!path || !chrom || !depth || n <= 0) return -1;
+  FILE* f = fopen(path, "ab");
+  if (!f) return -2;
+  const size_t kBuf = size_t(16) << 20;
+  const size_t lc = strlen(chrom);
+  if (lc == 0 || lc > 255) { fclose(f); return -1; }
+  std::vector<char> buf(kBuf + 320);
+  size_t used = 0;
+  auto put_int = [&](long long v) {
+    char tmp[24];
+    int k = 0;
+    unsigned long long u = v < 0 ? (unsigned long long)(-v) : (unsigned long long)v;
+    do { tmp[k++] = (char)('0' + u % 10); u /= 10; } while (u);
+    if (v < 0) buf[used++] = '-';
+    while (k) buf[used++] = tmp[--k];
+  };
+  for (int64_t i = 0; i < n; ++i) {
+    memcpy(buf.data() + used, chrom, lc); used += lc; buf[used++] = '\t';
+    put_int(i + 1); buf[used++] = '\t'; put_int(depth[i]); buf[used++] = '\n';
+    if (used >= kBuf) { if (fwrite(buf.data(), 1, used, f) != used) { fclose(f); return -3; } used = 0; }
+  }
+  if (used && fwrite(buf.data(), 1, used, f) != used) { fclose(f); return -3; }
+  return fclose(f) == 0 ? 0 : -3;
+}
+
 extern "C" int rsi_synth_write_fasta(const char* path, const char* chrom, const uint8_t* fasta, int64_t n) {
   if (!path || !chrom || !fasta || n <= 0) return -1;
   FILE* f = fopen(path, "wb");

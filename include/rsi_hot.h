@@ -115,6 +115,31 @@ int rsi_hot_load_depth_text(rsi_ctx* ctx, const char* path, int64_t n, rsi_text_
 int rsi_hot_run_text(rsi_ctx* ctx, const rsi_params* p, const char* depth_path, const uint8_t* fasta, int64_t n,
                      rsi_result** out, rsi_text_stats* stats);
 
+/* ---- Compressed depth files ------------------------------------------------------------------------------------
+ * Both text readers (rsi_hot_load_depth_text / _run_text and rsi_genome_text_*) take plain text, BGZF (bgzip's output;
+ * inflated on the device, CRC32 and ISIZE checked there) or ordinary gzip (single- or multi-member; inflated on the host
+ * with zlib).  The format comes from the first bytes: 1f 8b 08 with FEXTRA holding a "BC" subfield of length 2 is BGZF, any
+ * other 1f 8b start gzip, anything else text.  Depth, counts and rows are those of the text; rsi_text_stats.bytes and the
+ * genome reader's byte ranges count text bytes.  A bad member (CRC32 / ISIZE mismatch, invalid deflate data, a member past
+ * the end of the file, a non-BGZF member inside a BGZF file) is RSI_ERR_BAD_ARG naming its compressed offset. */
+typedef struct rsi_inflate_stats {
+  int32_t format;              /* 0 text, 1 BGZF, 2 gzip */
+  int32_t eof_block;           /* BGZF: 1 when the file ends with the empty EOF member */
+  int32_t input_error;         /* 1: the load failed on the compressed data itself (bad member, truncated file) */
+  int32_t pad;
+  int64_t compressed_bytes;    /* bytes of the file read */
+  int64_t text_bytes;          /* bytes of text they gave */
+  int64_t blocks;              /* BGZF members inflated on the device */
+  double t_inflate_kernel_ms;  /* summed HIP-event time of the inflate launches (BGZF) */
+  double t_host_inflate_ms;    /* wall time in zlib on the host (gzip) */
+} rsi_inflate_stats;
+/* The format and the inflate figures of the context's last rsi_hot_load_depth_text / rsi_hot_run_text / rsi_hot_inflate_bgzf. */
+int rsi_hot_last_inflate_stats(const rsi_ctx* ctx, rsi_inflate_stats* out);
+/* comp[0, comp_len): whole BGZF members, inflated on the device into out[0, out_cap).  Returns the text length (>= 0), or
+ * an error code (out_cap too small: RSI_ERR_BAD_ARG).  For tests and tools. */
+int64_t rsi_hot_inflate_bgzf(rsi_ctx* ctx, const uint8_t* comp, int64_t comp_len, uint8_t* out, int64_t out_cap,
+                             rsi_inflate_stats* stats);
+
 /* ---- Whole-genome depth text: "RNAME pos depth" lines, every chromosome in one file --------------------
  * (samtools depth -a, or mpileup | cut -f1,2,4).  A streaming reader that parses the file on the device and hands over each
  * chromosome's depth, resident in HBM, as soon as its last line has been parsed.  Lines: empty ones and those whose first
@@ -147,6 +172,8 @@ int64_t rsi_genome_text_copy_depth(rsi_genome_text* g, int slot, int32_t* out, i
 int rsi_genome_text_kernel_ms(const rsi_genome_text* g, double* bound_ms, double* parse_ms);
 void rsi_genome_text_close(rsi_genome_text* g);
 const char* rsi_genome_text_last_error(const rsi_genome_text* g);
+/* the file's format and the inflate figures so far (rsi_inflate_stats) */
+int rsi_genome_text_inflate_stats(const rsi_genome_text* g, rsi_inflate_stats* out);
 /* One chromosome whose depth is already in HBM (e.g. a genome reader's buffer, not modified) and whose fasta[n] is in
  * host memory: the sequence goes to the context's own device buffer, then rsi_hot_run_device. */
 int rsi_hot_run_depth_device(rsi_ctx* ctx, const rsi_params* p, const void* d_depth, const uint8_t* fasta, int64_t n,

@@ -51,6 +51,9 @@ int rsi_synth_write_depth_text(const char* path, const int32_t* depth, int64_t n
 int rsi_synth_write_fasta(const char* path, const char* chrom, const uint8_t* fasta, int64_t n);
 /* "RNAME<TAB>pos<TAB>depth" lines of one chromosome appended to `path` (whole-genome depth text).  0 or < 0. */
 int rsi_synth_append_genome_text(const char* path, const char* chrom, const int32_t* depth, int64_t n);
+/* The same lines as BGZF (bgzip's layout: 65280 text bytes per member, zlib level 6, then the empty EOF member; members of
+ * earlier calls stay in front), compressed on up to 16 host threads.  0 or < 0. */
+int rsi_synth_append_genome_bgzf(const char* path, const char* chrom, const int32_t* depth, int64_t n);
 
 #ifdef __cplusplus
 }

@@ -30,7 +30,9 @@ EXPORTS = ["rsi_default_params", "rsi_hot_create", "rsi_hot_destroy", "rsi_hot_l
            "rsi_hot_kernel_times", "rsi_hot_phase_times", "rsi_hot_set_timing", "rsi_pool_create", "rsi_pool_destroy", "rsi_pool_workers", "rsi_pool_worker",
            "rsi_pool_set_timing", "rsi_pool_set_timing_kernel", "rsi_hot_set_timing_kernel", "rsi_pool_set_schedule", "rsi_pool_last_error", "rsi_pool_run", "rsi_pool_run_host", "rsi_pool_submit", "rsi_pool_wait", "rsi_plot_expand", "rsi_plot_write_files", "rsi_result_log_line", "rsi_hot_debug_level_sums", "rsi_hot_debug_scan", "rsi_synth_generate_host", "rsi_synth_generate_device", "rsi_synth_write_depth_text", "rsi_synth_write_fasta", "rsi_synth_append_genome_text",
            "rsi_genome_text_open", "rsi_genome_text_next", "rsi_genome_text_release", "rsi_genome_text_copy_depth",
-           "rsi_genome_text_kernel_ms", "rsi_genome_text_close", "rsi_genome_text_last_error", "rsi_hot_run_depth_device"]
+           "rsi_genome_text_kernel_ms", "rsi_genome_text_close", "rsi_genome_text_last_error", "rsi_hot_run_depth_device",
+           "rsi_hot_last_inflate_stats", "rsi_hot_inflate_bgzf", "rsi_genome_text_inflate_stats",
+           "rsi_synth_append_genome_bgzf"]
 
 
 class RsiParams(C.Structure):
@@ -64,6 +66,20 @@ SUMMARY_HEAD, SUMMARY_CALL = 8, 8   # rsi_hot.h: RSI_SUMMARY_HEAD, RSI_SUMMARY_C
 class RsiTextStats(C.Structure):
     _fields_ = [("bytes", C.c_int64), ("lines", C.c_int64), ("stored", C.c_int64), ("beyond", C.c_int64),
                 ("fallback", C.c_int32), ("pad", C.c_int32), ("t_total_ms", C.c_double), ("t_parse_kernel_ms", C.c_double)]
+
+
+class RsiInflateStats(C.Structure):
+    _fields_ = [("format", C.c_int32), ("eof_block", C.c_int32), ("input_error", C.c_int32), ("pad", C.c_int32), ("compressed_bytes", C.c_int64), ("text_bytes", C.c_int64),
+                ("blocks", C.c_int64), ("t_inflate_kernel_ms", C.c_double), ("t_host_inflate_ms", C.c_double)]
+
+
+INFLATE_FORMATS = {0: "text", 1: "bgzf", 2: "gzip"}
+
+
+def _inflate_dict(st):
+    d = {f[0]: getattr(st, f[0]) for f in RsiInflateStats._fields_ if f[0] != "pad"}
+    d["format"] = INFLATE_FORMATS.get(st.format, str(st.format))
+    return d
 
 
 class RsiGenomeChrom(C.Structure):
@@ -175,6 +191,10 @@ def load_library():
     L.rsi_genome_text_close.argtypes = [C.c_void_p]
     L.rsi_genome_text_last_error.argtypes = [C.c_void_p]
     L.rsi_genome_text_last_error.restype = C.c_char_p
+    L.rsi_genome_text_inflate_stats.argtypes = [C.c_void_p, C.POINTER(RsiInflateStats)]
+    L.rsi_hot_last_inflate_stats.argtypes = [C.c_void_p, C.POINTER(RsiInflateStats)]
+    L.rsi_hot_inflate_bgzf.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(RsiInflateStats)]
+    L.rsi_hot_inflate_bgzf.restype = C.c_int64
     _lib = L
     return L
 
@@ -339,6 +359,45 @@ class RsiHot:
         st = RsiTextStats()
         self._check(self.lib.rsi_hot_load_depth_text(self.ctx, os.fsencode(path), int(n), C.byref(st)))
         return {f[0]: getattr(st, f[0]) for f in RsiTextStats._fields_ if f[0] != "pad"}
+
+    def inflate_bgzf(self, data):
+        """BGZF bytes (whole members) -> their text, inflated on the device (rsi_hot_inflate_bgzf; CRC32 and ISIZE checked
+        there).  Raises RsiError on a bad member."""
+        data = bytes(data)
+        st = RsiInflateStats()
+        src = np.frombuffer(data, dtype=np.uint8) if data else np.zeros(1, dtype=np.uint8)
+        size = self._bgzf_text_size(data)
+        out = np.zeros(max(size, 1), dtype=np.uint8)
+        k = self.lib.rsi_hot_inflate_bgzf(self.ctx, src.ctypes.data, len(data), out.ctypes.data, size, C.byref(st))
+        self._check(int(k) if k < 0 else 0)
+        return out[:k].tobytes()
+
+    @staticmethod
+    def _bgzf_text_size(data):
+        """Sum of the members' ISIZE (the footers), walking BSIZE; a malformed walk returns what it has (the device call
+        reports the error)."""
+        p, total = 0, 0
+        while p + 18 <= len(data):
+            xlen = data[p + 10] | (data[p + 11] << 8)
+            bsize = None
+            k = p + 12
+            while k + 4 <= p + 12 + xlen and k + 4 <= len(data):
+                slen = data[k + 2] | (data[k + 3] << 8)
+                if data[k] == 66 and data[k + 1] == 67 and slen == 2 and k + 6 <= len(data):
+                    bsize = (data[k + 4] | (data[k + 5] << 8)) + 1
+                k += 4 + slen
+            if bsize is None or p + bsize > len(data):
+                break
+            total += int.from_bytes(data[p + bsize - 4:p + bsize], "little")
+            p += bsize
+        return total
+
+    def inflate_stats(self):
+        """Format and inflate figures of the last load_depth_text / run_text / inflate_bgzf: format ("text", "bgzf",
+        "gzip"), compressed_bytes, text_bytes, blocks, t_inflate_kernel_ms (device), t_host_inflate_ms (zlib)."""
+        st = RsiInflateStats()
+        self._check(self.lib.rsi_hot_last_inflate_stats(self.ctx, C.byref(st)))
+        return _inflate_dict(st)
 
     def run_text(self, params, path, fasta):
         """Depth from a text file (parsed on the device), fasta: uint8[n] host array."""
@@ -565,6 +624,12 @@ class GenomeText:
         if k < 0:
             raise RsiError(int(k), self.lib.rsi_genome_text_last_error(self.g).decode())
         return out
+
+    def inflate_stats(self):
+        """The file's format and the inflate figures so far (see RsiHot.inflate_stats)."""
+        st = RsiInflateStats()
+        self.lib.rsi_genome_text_inflate_stats(self.g, C.byref(st))
+        return _inflate_dict(st)
 
     def kernel_ms(self):
         """(boundary pass, parse pass): summed HIP-event milliseconds so far."""

@@ -25,6 +25,7 @@
 #include <condition_variable>
 #include <deque>
 #include <iterator>
+#include <zlib.h>
 
 #include "../../include/rsi_hot.h"
 #include "hostmath.h"
@@ -66,6 +67,8 @@ int usage() {
             << "   chromosome's lines together; rows follow the file's order), or a coordinate-sorted BAM file\n"
             << "   (all chromosomes with reads, or the one named with -c), plus the indexed reference.\n"
             << "   -s saves the BAM's depth to OUT.RNAME_rd.\n"
+            << "   A depth file may be BGZF (bgzip; inflated on the GPU) or gzip (inflated on the host): the format is\n"
+            << "   read from the file's first bytes (1f 8b 08 with a BC extra subfield: BGZF; other 1f 8b: gzip; else text).\n"
             << std::endl;
   return 0;
 }
@@ -163,7 +166,18 @@ struct ChromOutput {
   std::vector<std::string> rows;   // output rows (cnv_format1), without the header
   bool populated = false;          // the chromosome was processed (has reads / could be read): it counts for the header
   bool fatal = false;              // the single-chromosome modes stop here (the reference exits)
+  bool bad_input = false;          // the compressed depth file is broken: exit 1, no output file
 };
+
+// One log line for a compressed depth file (none for plain text, whose logs stay as they were)
+std::string inflate_line(const rsi_inflate_stats& s) {
+  if (s.format == 0) return "";
+  std::ostringstream o;
+  o << "#depth file: " << (s.format == 1 ? "BGZF" : "gzip") << ", " << s.compressed_bytes << " compressed bytes, " << s.text_bytes
+    << " text bytes, inflate " << (s.format == 1 ? s.t_inflate_kernel_ms : s.t_host_inflate_ms) << " ms ("
+    << (s.format == 1 ? "device" : "host") << ")" << (s.format == 1 && !s.eof_block ? ", no BGZF EOF block at the end" : "") << "\n";
+  return o.str();
+}
 
 void report_chromosome(rsi_ctx* ctx, const Options& o, const std::string& chr, rsi_result* res, const rsi_text_stats* ts,
                        const rsi_bam_stats* bs, double t_fasta, double t_path, std::ostringstream& info, ChromOutput& co);
@@ -190,10 +204,16 @@ void process_chromosome(rsi_ctx* ctx, const Options& o, const std::string& chr, 
   if (rc != RSI_OK) {   // the reference prints its message and exits with status 0
     info << rsi_hot_last_error(ctx) << "\n";
     co.log = info.str();
+    rsi_inflate_stats is;
+    if (!from_bam && rsi_hot_last_inflate_stats(ctx, &is) == RSI_OK && is.input_error) co.bad_input = true;
     co.fatal = !(many && from_bam && bs.on_chrom == 0);   // a reference without reads is simply not "populated" (rsi.cpp:2125)
     return;
   }
   const double t2 = now_s();
+  if (!from_bam) {
+    rsi_inflate_stats is;
+    if (rsi_hot_last_inflate_stats(ctx, &is) == RSI_OK) info << inflate_line(is);
+  }
   if (from_bam && many && bs.on_chrom == 0) {   // not "populated": the reference does not process it (rsi.cpp:2125)
     info << "no reads on " << chr << "\n";
     co.log = info.str();
@@ -306,10 +326,15 @@ void report_chromosome(rsi_ctx* ctx, const Options& o, const std::string& chr, r
 }
 
 // Columns of the first data line of a depth file (-1: none): a whole-genome file has three, RNAME POS DEPTH.
-int first_line_columns(const std::string& path) {
-  std::ifstream f(path.c_str());
+int first_line_columns(const std::string& path) {   // through gzip / BGZF compression (zlib reads plain text as it is)
+  gzFile f = gzopen(path.c_str(), "rb");
+  if (!f) return -1;
+  struct Close { gzFile f; ~Close() { gzclose(f); } } closer{f};
   std::string line, tok;
-  while (std::getline(f, line)) {
+  std::vector<char> buf(1 << 16);
+  while (gzgets(f, buf.data(), (int)buf.size())) {
+    line = buf.data();
+    while (!line.empty() && line.back() == '\n') line.pop_back();
     if (line.empty() || line[0] == '#') continue;
     std::istringstream iss(line);
     int k = 0;
@@ -438,6 +463,8 @@ bool run_genome(const Options& o, std::vector<std::string>& chroms, std::vector<
   std::ostringstream sm;
   sm << "timing: whole-genome depth text " << (now_s() - t0) << " s, " << chroms.size() << " chromosomes, boundary kernels " << bound_ms
      << " ms, parse kernels " << parse_ms << " ms\n";
+  rsi_inflate_stats is;
+  if (rsi_genome_text_inflate_stats(g, &is) == RSI_OK) sm << inflate_line(is);
   summary = sm.str();
   rsi_genome_text_close(g);
   rsi_pool_destroy(pool);
@@ -542,6 +569,12 @@ int main(int argc, char** argv) {
     for (const std::string& chr : todo) {
       ChromOutput co;
       process_chromosome(ctx, o, chr, many, co);
+      if (co.bad_input) {   // as the genome mode: a depth file that cannot be read through gives no output
+        std::cerr << co.log; log << co.log;
+        remove(o.outfile.c_str());
+        rsi_hot_destroy(ctx);
+        return 1;
+      }
       emit(chr, co);
       if (co.fatal) break;
     }

@@ -3,8 +3,10 @@
 // The file bytes go through pinned double buffers; parsing, per-read work and the difference-array scan are kernels
 // (kernels_io.hip); BGZF inflation and the record walk stay on host threads (bam_host.cpp).
 #include "pipeline_internal.h"
+#include "inflate_core.h"
 #include <memory>
 #include <unordered_set>
+#include <zlib.h>
 
 using namespace rsik;
 using namespace rsip;
@@ -58,6 +60,210 @@ void parse_depth_text_host(const char* p, size_t sz, int64_t size, std::vector<i
 }
 
 constexpr size_t kTextChunk = size_t(64) << 20;   // bytes of text per transfer + kernel
+constexpr size_t kBgzfMinChunk = size_t(128) << 10; // BGZF input: a chunk holds whole members, at least this much text
+constexpr size_t kMemberMax = 65536;               // BGZF: BSIZE and ISIZE
+
+// Text bytes [skip, skip + len) of the gzip stream that starts at file offset foff (any member start of a gzip or BGZF
+// file), inflated on the host: the sequential fallback parser's input for compressed files.
+int host_text_range(const std::string& path, int64_t foff, int64_t skip, int64_t len, std::vector<char>& out, std::string& err) {
+  const int fd = open(path.c_str(), O_RDONLY);
+  if (fd < 0 || lseek(fd, (off_t)foff, SEEK_SET) != (off_t)foff) { if (fd >= 0) close(fd); err = "Cannot open file " + path; return RSI_ERR_BAD_ARG; }
+  gzFile g = gzdopen(fd, "rb");
+  if (!g) { close(fd); err = "zlib: cannot read " + path; return RSI_ERR_INTERNAL; }
+  gzbuffer(g, 1 << 20);
+  out.assign((size_t)len, 0);
+  int rc = RSI_OK;
+  if (skip > 0 && gzseek(g, (z_off_t)skip, SEEK_SET) != (z_off_t)skip) rc = RSI_ERR_BAD_ARG;
+  size_t have = 0;
+  while (rc == RSI_OK && have < out.size()) {
+    const int got = gzread(g, out.data() + have, (unsigned)std::min<size_t>(out.size() - have, size_t(1) << 30));
+    if (got <= 0) { rc = RSI_ERR_BAD_ARG; break; }
+    have += (size_t)got;
+  }
+  if (rc != RSI_OK) { int e = 0; const char* m = gzerror(g, &e); err = std::string("gzip: ") + (e ? m : "unexpected end of the text") + " in " + path; }
+  gzclose(g);
+  return rc;
+}
+
+// Where the text readers get their bytes from.  Text and gzip: read_text() in the place of read() (zlib on
+// the host for gzip).  BGZF: launch() walks the member headers on the host, uploads the compressed payloads and the member
+// table, and inflates them on the device straight into the reader's text buffer, behind the bytes carried over from the
+// chunk before; the text exists only in HBM.  check() reads the launch's status word (read back with the caller's next
+// wait): the first bad member, the last line end.
+struct DepthSource {
+  int fd = -1;                     // the reader's
+  std::string path, err;
+  int format = 0;                  // 0 text, 1 BGZF, 2 gzip
+  gzFile gz = nullptr;
+  rsi_inflate_stats st{};
+  // BGZF
+  std::vector<uint8_t> cbuf;       // compressed bytes read from the file; cbuf[cpos..] not taken yet
+  size_t cpos = 0;
+  int64_t cbuf_off = 0;            // file offset of cbuf[0]
+  bool file_eof = false, exhausted = false;
+  std::vector<std::pair<int64_t, int64_t>> index;   // (text offset, file offset) of every member: the fallback's entry points
+  PinBuf cpin[2], tpin[2], wpin;
+  DevBuf cdev[2], tdev[2], wdev;
+  std::vector<int64_t> foffs[2];   // file offsets of the members of each launch (messages)
+  bool launched[2] = {false, false};
+  hipEvent_t ev[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+
+  ~DepthSource() {
+    if (gz) gzclose(gz);
+    for (int b = 0; b < 2; ++b) for (int k = 0; k < 2; ++k) if (ev[b][k]) (void)hipEventDestroy(ev[b][k]);
+  }
+  int fail_(int code, const std::string& m) { err = m; return code; }
+  int bad_data(const std::string& m) { st.input_error = 1; return fail_(RSI_ERR_BAD_ARG, m); }   // the compressed data is broken
+
+  int open_(int fd_, const std::string& p, int64_t file_size) {
+    fd = fd_; path = p;
+    uint8_t head[512];
+    const ssize_t n = pread(fd, head, sizeof(head), 0);
+    format = rsinf::detect_format(head, n > 0 ? (size_t)n : 0);
+    st.format = format;
+    if (format == 0) { st.compressed_bytes = st.text_bytes = file_size; return RSI_OK; }
+    if (format == 2) {
+      st.compressed_bytes = file_size;
+      const int d = dup(fd);
+      gz = d >= 0 ? gzdopen(d, "rb") : nullptr;
+      if (!gz) { if (d >= 0) close(d); return fail_(RSI_ERR_INTERNAL, "zlib: cannot read " + path); }
+      gzbuffer(gz, 1 << 20);
+    }
+    return RSI_OK;
+  }
+
+  // text / gzip: like read(); < 0 on an error (err)
+  ssize_t read_text(char* buf, size_t n) {
+    if (format == 0) {
+      const ssize_t got = read(fd, buf, n);
+      if (got < 0) err = "read error on " + path;
+      return got;
+    }
+    const double t = now_ms();
+    const int got = gzread(gz, buf, (unsigned)std::min<size_t>(n, size_t(1) << 30));
+    st.t_host_inflate_ms += now_ms() - t;
+    int e = Z_OK;
+    const char* m = got <= 0 ? gzerror(gz, &e) : nullptr;
+    if (got < 0 || (got == 0 && e != Z_OK)) {   // a file cut inside a member ends with 0 and Z_BUF_ERROR, not with -1
+      bad_data(std::string("gzip: ") + m + " near compressed offset " + std::to_string((long long)gzoffset(gz)) + " of " + path);
+      return -1;
+    }
+    st.text_bytes += got;
+    return got;
+  }
+
+  // at least `need` untaken compressed bytes in cbuf, unless the file ends first
+  bool have_bytes(size_t need) {
+    if (cbuf.size() - cpos >= need) return true;
+    if (cpos) { cbuf.erase(cbuf.begin(), cbuf.begin() + (ptrdiff_t)cpos); cbuf_off += (int64_t)cpos; cpos = 0; }
+    while (cbuf.size() < need && !file_eof) {
+      const size_t old = cbuf.size(), want = std::max(need - old, size_t(4) << 20);
+      cbuf.resize(old + want);
+      const ssize_t got = read(fd, cbuf.data() + old, want);
+      cbuf.resize(old + (got > 0 ? (size_t)got : 0));
+      if (got < 0) { err = "read error on " + path; return false; }
+      if (got == 0) file_eof = true;
+    }
+    return cbuf.size() - cpos >= need;
+  }
+
+  // BGZF: the next members into d_text[carry, ...) -- at most max_text bytes of text in the buffer in all, one member at least.
+  // carry_nl: offset of the last line end in the carried bytes (-1: none).  text_off: text offset of d_text[carry].  Queues
+  // the uploads, the inflate launch and its status read-back on s.  *added: text bytes added (0 with exhausted: the end).
+  int launch(int b, void* d_text, size_t carry, int carry_nl, size_t max_text, int64_t text_off, hipStream_t s, size_t& added) {
+    added = 0;
+    launched[b] = false;
+    foffs[b].clear();
+    std::vector<InflateBlock> tab;
+    const size_t ccap = max_text + 4 * kMemberMax;
+    if (cpin[b].ensure(ccap) != hipSuccess || cdev[b].ensure(ccap) != hipSuccess || wpin.ensure(32) != hipSuccess || wdev.ensure(32) != hipSuccess)
+      return fail_(RSI_ERR_HIP, "BGZF: out of pinned or device memory for the compressed staging");
+    uint8_t* cp = cpin[b].as<uint8_t>();
+    size_t comp = 0;
+    while (!exhausted) {
+      if (!have_bytes(18)) {
+        if (!err.empty()) return RSI_ERR_INTERNAL;
+        if (cbuf.size() == cpos) { exhausted = true; break; }
+        return bad_data("BGZF: a member runs past the end of the file at compressed offset " + std::to_string(cbuf_off + (int64_t)cpos));
+      }
+      const int64_t at = cbuf_off + (int64_t)cpos;
+      rsinf::Member m;
+      int r = rsinf::bgzf_member(cbuf.data() + cpos, cbuf.size() - cpos, m);
+      if (r < 0) {   // a long extra field
+        const size_t xlen = (size_t)cbuf[cpos + 10] | ((size_t)cbuf[cpos + 11] << 8);
+        if (have_bytes(12 + xlen)) r = rsinf::bgzf_member(cbuf.data() + cpos, cbuf.size() - cpos, m);
+      }
+      if (r <= 0) return bad_data("BGZF: not a BGZF member at compressed offset " + std::to_string(at) + " (the file changes format part-way)");
+      if (!have_bytes(m.bsize)) {
+        if (!err.empty()) return RSI_ERR_INTERNAL;
+        return bad_data("BGZF: the member at compressed offset " + std::to_string(at) + " runs past the end of the file");
+      }
+      rsinf::bgzf_member(cbuf.data() + cpos, cbuf.size() - cpos, m);   // the footer is in now
+      if (m.isize > kMemberMax) return bad_data("BGZF: ISIZE above 65536 in the member at compressed offset " + std::to_string(at));
+      if (!tab.empty() && (carry + added + m.isize > max_text || comp + m.clen > ccap)) break;
+      memcpy(cp + comp, cbuf.data() + cpos + m.hdr, m.clen);
+      tab.push_back(InflateBlock{(long long)comp, (long long)(carry + added), m.clen, m.isize, m.crc, 0});
+      index.emplace_back(text_off + (int64_t)added, at);
+      foffs[b].push_back(at);
+      comp += m.clen; added += m.isize; cpos += m.bsize;
+      st.compressed_bytes += m.bsize; st.text_bytes += m.isize; ++st.blocks;
+      st.eof_block = m.isize == 0;
+    }
+    if (tab.empty()) return RSI_OK;
+    const size_t tb = tab.size() * sizeof(InflateBlock);
+    if (tpin[b].ensure(tb) != hipSuccess || tdev[b].ensure(tb) != hipSuccess) return fail_(RSI_ERR_HIP, "BGZF: out of memory for the member table");
+    memcpy(tpin[b].p, tab.data(), tb);
+    char* w = wdev.as<char>() + 16 * b;
+    hipError_t e = hipMemcpyAsync(cdev[b].p, cp, comp, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(tdev[b].p, tpin[b].p, tb, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemsetAsync(w, 0xff, 8, s);
+    if (e == hipSuccess) e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(w + 8), carry_nl, 1, s);
+    if (e != hipSuccess) return fail_(RSI_ERR_HIP, std::string("BGZF: ") + hipGetErrorString(e));
+    for (int k = 0; k < 2; ++k) if (!ev[b][k]) (void)hipEventCreate(&ev[b][k]);
+    if (ev[b][0]) (void)hipEventRecord(ev[b][0], s);
+    launch_inflate_bgzf(cdev[b].p, tdev[b].as<InflateBlock>(), (int)tab.size(), d_text, reinterpret_cast<int*>(w + 8),
+                        reinterpret_cast<unsigned long long*>(w), s);
+    if (ev[b][1]) (void)hipEventRecord(ev[b][1], s);
+    e = hipMemcpyAsync(wpin.as<char>() + 16 * b, w, 16, hipMemcpyDeviceToHost, s);
+    if (e != hipSuccess) return fail_(RSI_ERR_HIP, std::string("BGZF: ") + hipGetErrorString(e));
+    launched[b] = true;
+    return RSI_OK;
+  }
+
+  // after a wait behind launch(b): the first bad member's error, else *last_nl (unchanged when nothing was launched)
+  int check(int b, int* last_nl) {
+    if (!launched[b]) return RSI_OK;
+    launched[b] = false;
+    float ms = 0;
+    if (ev[b][0] && ev[b][1] && hipEventElapsedTime(&ms, ev[b][0], ev[b][1]) == hipSuccess) st.t_inflate_kernel_ms += ms;
+    const char* w = wpin.as<char>() + 16 * b;
+    unsigned long long status;
+    memcpy(&status, w, 8);
+    if (status != ~0ull) {
+      const size_t k = (size_t)(status >> 8);
+      const int64_t at = k < foffs[b].size() ? foffs[b][k] : -1;
+      return bad_data("BGZF: the member at compressed offset " + std::to_string(at) + " of " + path + " is bad: " +
+                                        rsinf::err_name((int)(status & 0xff)));
+    }
+    memcpy(last_nl, w + 8, 4);
+    return RSI_OK;
+  }
+
+  // the fallback parser's text: [start, end) of the whole text, inflated on the host from the nearest member (BGZF) or
+  // from the start (gzip)
+  int host_range(int64_t start, int64_t end, std::vector<char>& out) {
+    int64_t foff = 0, toff = 0;
+    if (format == 1) {
+      auto it = std::upper_bound(index.begin(), index.end(), std::make_pair(start, INT64_MAX));
+      if (it != index.begin()) { --it; toff = it->first; foff = it->second; }
+    }
+    const double t = now_ms();
+    const int rc = host_text_range(path, foff, start - toff, end - start, out, err);
+    st.t_host_inflate_ms += now_ms() - t;
+    if (rc == RSI_ERR_BAD_ARG) st.input_error = 1;
+    return rc;
+  }
+};
 
 }  // namespace
 
@@ -68,6 +274,7 @@ int rsi_hot_load_depth_text(rsi_ctx* ctx, const char* path, int64_t n, rsi_text_
   rsi_text_stats* st = stats ? stats : &local;
   memset(st, 0, sizeof(*st));
   if (!ctx || !path) return fail(ctx, RSI_ERR_BAD_ARG, "null argument");
+  ctx->last_inflate = rsi_inflate_stats{};
   if (n <= 0 || n >= (1ll << 31) - 4096) return fail(ctx, RSI_ERR_BAD_ARG, "chromosome length must be in (0, 2^31)");
   const double t0 = now_ms();
   HIPCHK(hipSetDevice(ctx->device));
@@ -76,6 +283,9 @@ int rsi_hot_load_depth_text(rsi_ctx* ctx, const char* path, int64_t n, rsi_text_
   struct FdGuard { int fd; ~FdGuard() { close(fd); } } guard{fd};
   struct stat sb;
   if (fstat(fd, &sb) != 0) return fail(ctx, RSI_ERR_BAD_ARG, std::string("Cannot stat file ") + path);
+  DepthSource src;
+  struct StatsOut { rsi_ctx* c; const DepthSource& s; ~StatsOut() { c->last_inflate = s.st; } } stats_out{ctx, src};   // every return
+  if (int rc = src.open_(fd, path, (int64_t)sb.st_size)) return fail(ctx, rc, src.err);
   st->bytes = (int64_t)sb.st_size;
   if (!ctx_enter(ctx)) return RSI_ERR_HIP;
   mailbox_reset(ctx);
@@ -122,12 +332,50 @@ int rsi_hot_load_depth_text(rsi_ctx* ctx, const char* path, int64_t n, rsi_text_
   };
   int cur = 0;
   bool used[2] = {false, false};
+  if (src.format == 1) {
+    // BGZF: the members are inflated on the device into text_dev[cur], behind the unfinished line of the chunk before
+    // (moved there device to device); the inflate reports the last line end, read back with the one wait per chunk
+    size_t carry_b = 0, cut = 0;
+    int64_t text_off = 0;
+    for (;;) {
+      const int other = cur ^ 1;
+      if (carry_b) HIPCHK(hipMemcpyAsync(ctx->text_dev[cur].p, static_cast<char*>(ctx->text_dev[other].p) + cut, carry_b, hipMemcpyDeviceToDevice, ctx->stream));
+      size_t added = 0;
+      if (int rc = src.launch(cur, ctx->text_dev[cur].p, carry_b, -1, kTextChunk, text_off + (int64_t)carry_b, ctx->stream, added)) return fail(ctx, rc, src.err);
+      const size_t total = carry_b + added;
+      if (total == 0) break;
+      HIPCHK(CTX_SYNC());
+      if (used[other]) { check_chunk(other); used[other] = false; }
+      int last_nl = -1;
+      if (int rc = src.check(cur, &last_nl)) return fail(ctx, rc, src.err);
+      size_t len = total;
+      if (!src.exhausted) {
+        if (last_nl < 0) return fail(ctx, RSI_ERR_UNSUPPORTED, "a line of the depth file is longer than the chunk");
+        len = (size_t)last_nl + 1;
+      }
+      if (total - len >= kTextChunk / 2) return fail(ctx, RSI_ERR_UNSUPPORTED, "a line of the depth file is longer than half the chunk");
+      const int nwg = text_parse_workgroups((long long)len);
+      long long* d_first = reinterpret_cast<long long*>(wgbase + (size_t)cur * max_wg * 16);
+      long long* d_max = d_first + nwg;
+      { Timer t(ctx, "parse_depth_text"); launch_parse_depth_text(ctx->text_dev[cur].p, (long long)len, (long long)n, ctx->in_depth.as<int32_t>(), d_first, d_max, d_stats, ctx->stream); }
+      HIPCHK(hipMemcpyAsync(wg_host[cur].data(), d_first, (size_t)nwg * 16, hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHK(hipEventRecord(done[cur], ctx->stream));
+      inflight_wgs[cur] = nwg;
+      used[cur] = true;
+      text_off += (int64_t)len;
+      cut = len; carry_b = total - len;
+      if (carry_b == 0 && src.exhausted) break;
+      cur = other;
+    }
+    eof = true;
+    st->bytes = src.st.text_bytes;
+  }
   while (!eof) {
     char* buf = ctx->text_pin[cur];   // free: its previous chunk was waited for before `carry` was parked in it
     size_t have = carry;
     while (have < kTextChunk) {
-      const ssize_t got = read(fd, buf + have, kTextChunk - have);
-      if (got < 0) return fail(ctx, RSI_ERR_INTERNAL, std::string("read error on ") + path);
+      const ssize_t got = src.read_text(buf + have, kTextChunk - have);
+      if (got < 0) return fail(ctx, src.format == 2 ? RSI_ERR_BAD_ARG : RSI_ERR_INTERNAL, src.err);
       if (got == 0) { eof = true; break; }
       have += (size_t)got;
     }
@@ -156,6 +404,7 @@ int rsi_hot_load_depth_text(rsi_ctx* ctx, const char* path, int64_t n, rsi_text_
     cur = other;
   }
   for (int b = 0; b < 2; ++b) if (used[b] && inflight_wgs[b]) { HIPCHK(hipEventSynchronize(done[b])); check_chunk(b); }
+  if (src.format == 2) st->bytes = src.st.text_bytes;
   TextParseStats hs;
   HIPCHK(hipMemcpyAsync(&hs, d_stats, sizeof(hs), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -164,10 +413,16 @@ int rsi_hot_load_depth_text(rsi_ctx* ctx, const char* path, int64_t n, rsi_text_
     // order-dependent rules in play: redo the file with the sequential loop
     st->fallback = 1; st->lines = st->stored = st->beyond = 0;
     std::vector<int32_t> rd((size_t)n, 0);
-    std::vector<char> all((size_t)st->bytes);
-    if (lseek(fd, 0, SEEK_SET) != 0) return fail(ctx, RSI_ERR_INTERNAL, "seek error");
+    std::vector<char> all;
     size_t have = 0;
-    while (have < all.size()) { const ssize_t got = read(fd, all.data() + have, all.size() - have); if (got <= 0) break; have += (size_t)got; }
+    if (src.format != 0) {   // compressed: the text once more, inflated on the host from the start
+      if (int rc = src.host_range(0, st->bytes, all)) return fail(ctx, rc, src.err);
+      have = all.size();
+    } else {
+      all.resize((size_t)st->bytes);
+      if (lseek(fd, 0, SEEK_SET) != 0) return fail(ctx, RSI_ERR_INTERNAL, "seek error");
+      while (have < all.size()) { const ssize_t got = read(fd, all.data() + have, all.size() - have); if (got <= 0) break; have += (size_t)got; }
+    }
     parse_depth_text_host(all.data(), have, n, rd, st);
     HIPCHK(hipMemcpyAsync(ctx->in_depth.p, rd.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -175,6 +430,77 @@ int rsi_hot_load_depth_text(rsi_ctx* ctx, const char* path, int64_t n, rsi_text_
   st->t_total_ms = now_ms() - t0;
   if (ctx->timing) { double tot = 0; for (const KernelTime& k : ctx->ktimes) { float ms = 0; (void)hipEventElapsedTime(&ms, k.a, k.b); tot += ms; } st->t_parse_kernel_ms = tot; }
   return RSI_OK;
+}
+
+int rsi_hot_last_inflate_stats(const rsi_ctx* ctx, rsi_inflate_stats* out) {
+  if (!ctx || !out) return RSI_ERR_BAD_ARG;
+  *out = ctx->last_inflate;
+  return RSI_OK;
+}
+
+int64_t rsi_hot_inflate_bgzf(rsi_ctx* ctx, const uint8_t* comp, int64_t comp_len, uint8_t* out, int64_t out_cap, rsi_inflate_stats* stats) {
+  if (!ctx || comp_len < 0 || out_cap < 0 || (!comp && comp_len) || (!out && out_cap)) return fail(ctx, RSI_ERR_BAD_ARG, "null argument");
+  rsi_inflate_stats st{};
+  st.format = 1; st.compressed_bytes = comp_len;
+  std::vector<InflateBlock> tab;
+  std::vector<int64_t> starts;   // member offsets (messages)
+  int64_t text = 0;
+  for (int64_t p = 0; p < comp_len;) {   // the member headers, on the host
+    rsinf::Member m;
+    const int r = rsinf::bgzf_member(comp + p, (size_t)(comp_len - p), m);
+    if (r == 0) return fail(ctx, RSI_ERR_BAD_ARG, "BGZF: not a BGZF member at compressed offset " + std::to_string(p));
+    if (r < 0 || (int64_t)m.bsize > comp_len - p) return fail(ctx, RSI_ERR_BAD_ARG, "BGZF: the member at compressed offset " + std::to_string(p) + " runs past the end of the data");
+    if (m.isize > kMemberMax) return fail(ctx, RSI_ERR_BAD_ARG, "BGZF: ISIZE above 65536 in the member at compressed offset " + std::to_string(p));
+    tab.push_back(InflateBlock{(long long)(p + m.hdr), (long long)text, m.clen, m.isize, m.crc, 0});
+    starts.push_back(p);
+    text += m.isize; p += m.bsize;
+    st.eof_block = m.isize == 0;
+  }
+  st.blocks = (int64_t)tab.size(); st.text_bytes = text;
+  if (text > out_cap) return fail(ctx, RSI_ERR_BAD_ARG, "rsi_hot_inflate_bgzf: out_cap is smaller than the text (" + std::to_string(text) + " bytes)");
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!ctx_enter(ctx)) return RSI_ERR_HIP;
+  constexpr int64_t kBatch = int64_t(256) << 20;   // text bytes per launch
+  DevBuf dcomp, dtext, dtab, dword;
+  HIPCHK(dword.ensure(16));
+  unsigned long long status = 0;
+  hipEvent_t ea = nullptr, eb = nullptr;
+  if (hipEventCreate(&ea) != hipSuccess || hipEventCreate(&eb) != hipSuccess) return fail(ctx, RSI_ERR_HIP, "hipEventCreate failed");
+  struct EvGuard { hipEvent_t a, b; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } evguard{ea, eb};
+  for (size_t i = 0; i < tab.size();) {
+    size_t j = i;
+    const int64_t t0 = tab[i].out, cbase = tab[i].coff;
+    while (j < tab.size() && (j == i || tab[j].out + tab[j].isize - t0 <= kBatch)) ++j;
+    const int64_t t1 = tab[j - 1].out + tab[j - 1].isize, c1 = tab[j - 1].coff + tab[j - 1].clen;
+    std::vector<InflateBlock> part(tab.begin() + (ptrdiff_t)i, tab.begin() + (ptrdiff_t)j);
+    for (InflateBlock& B : part) { B.coff -= cbase; B.out -= t0; }
+    HIPCHK(dcomp.ensure((size_t)(c1 - cbase) + 16));
+    HIPCHK(dtext.ensure((size_t)(t1 - t0) + 16));
+    HIPCHK(dtab.ensure(part.size() * sizeof(InflateBlock)));
+    HIPCHK(hipMemcpyAsync(dcomp.p, comp + cbase, (size_t)(c1 - cbase), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(dtab.p, part.data(), part.size() * sizeof(InflateBlock), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemsetAsync(dword.p, 0xff, 8, ctx->stream));
+    HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(dword.as<char>() + 8), -1, 1, ctx->stream));
+    HIPCHK(hipEventRecord(ea, ctx->stream));
+    launch_inflate_bgzf(dcomp.p, dtab.as<InflateBlock>(), (int)part.size(), dtext.p, reinterpret_cast<int*>(dword.as<char>() + 8),
+                        dword.as<unsigned long long>(), ctx->stream);
+    HIPCHK(hipEventRecord(eb, ctx->stream));
+    HIPCHK(hipMemcpyAsync(&status, dword.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (t1 > t0) HIPCHK(hipMemcpyAsync(out + t0, dtext.p, (size_t)(t1 - t0), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(CTX_SYNC());
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, ea, eb) == hipSuccess) st.t_inflate_kernel_ms += ms;
+    if (status != ~0ull) {
+      const size_t k = i + (size_t)(status >> 8);
+      const int64_t at = k < starts.size() ? starts[k] : -1;
+      ctx->last_inflate = st;
+      return fail(ctx, RSI_ERR_BAD_ARG, "BGZF: the member at compressed offset " + std::to_string(at) + " is bad: " + rsinf::err_name((int)(status & 0xff)));
+    }
+    i = j;
+  }
+  ctx->last_inflate = st;
+  if (stats) *stats = st;
+  return text;
 }
 
 int rsi_hot_run_text(rsi_ctx* ctx, const rsi_params* p, const char* depth_path, const uint8_t* fasta, int64_t n, rsi_result** out,
@@ -481,9 +807,19 @@ struct rsi_genome_text {
   std::vector<Pending> timed;
   std::vector<hipEvent_t> ev_free;
   double ms_bound = 0, ms_parse = 0;
+  DepthSource src;                       // the file's format; BGZF: the members inflated on the device into text_dev[b]
+  size_t dcarry = 0, dcut = 0;           // BGZF: the text behind the cut, text_dev[b][dcut, dcut + dcarry) of the chunk started last
+  int dcarry_nl = -1;                    // ... the offset of its last line end in it (-1: none, the usual unfinished line)
+  DevBuf dnames;                         // BGZF: the boundary entries' names (launch_gather_names) and their pinned copy
+  PinBuf hnames;
+  hipStream_t istream = nullptr;         // BGZF: the next chunk's uploads and inflate run here, beside the parse of this one
+  hipEvent_t iev = nullptr;              // ... recorded behind them; the boundary pass of that chunk waits for it
 
   ~rsi_genome_text() {
     if (stream && sync_ev) (void)stream_wait(stream, sync_ev);   // nothing may still write the buffers freed below (deadline as every wait)
+    if (istream && iev) (void)stream_wait(istream, iev);
+    if (iev) (void)hipEventDestroy(iev);
+    if (istream) (void)hipStreamDestroy(istream);
     for (auto& t : timed) { ev_free.push_back(t.a); ev_free.push_back(t.b); }
     for (hipEvent_t e : ev_free) (void)hipEventDestroy(e);
     for (int b = 0; b < 2; ++b) if (pin[b]) (void)hipHostFree(pin[b]);
@@ -526,15 +862,30 @@ struct rsi_genome_text {
     return -1;
   }
 
+  // BGZF: the carried line device to device, then the next members inflated behind it, on istream: text_dev[b]'s chunk
+  // before was parsed before the last wait, so the inflate overlaps the parse launches of the chunk in text_dev[b ^ 1]
+  // (which it only reads, for the carry).  len[b]: the text in text_dev[b], cut at its last line end by start_chunk, once
+  // the inflate's report is back.
+  int fill_bgzf(int b) {
+    if (dcarry) if (int rc = hip_(hipMemcpyAsync(text_dev[b].p, static_cast<char*>(text_dev[b ^ 1].p) + dcut, dcarry, hipMemcpyDeviceToDevice, istream), "hipMemcpyAsync")) return rc;
+    size_t added = 0;
+    if (int rc = src.launch(b, text_dev[b].p, dcarry, dcarry_nl, chunk, consumed + (int64_t)dcarry, istream, added)) return fail_(rc, src.err);
+    if (int rc = hip_(hipEventRecord(iev, istream), "hipEventRecord")) return rc;
+    len[b] = dcarry + added; foff[b] = consumed;
+    dcarry = dcut = 0;
+    return RSI_OK;
+  }
+
   // Next chunk of the file into pin[b]: the carried line first, cut behind the last line end.  len[b] == 0: end of file.
   int fill(int b) {
+    if (src.format == 1) return fill_bgzf(b);
     char* buf = pin[b];
     size_t have = carry.size();
     if (have) memcpy(buf, carry.data(), have);
     bool eof = false;
     while (have < chunk) {
-      const ssize_t got = read(fd, buf + have, chunk - have);
-      if (got < 0) return fail_(RSI_ERR_INTERNAL, "read error on " + path);
+      const ssize_t got = src.read_text(buf + have, chunk - have);
+      if (got < 0) return fail_(src.format == 2 ? RSI_ERR_BAD_ARG : RSI_ERR_INTERNAL, src.err);
       if (got == 0) { eof = true; break; }
       have += (size_t)got;
     }
@@ -562,8 +913,12 @@ struct rsi_genome_text {
         o.stats.lines = (int64_t)S.lines; o.stats.stored = (int64_t)S.stored; o.stats.beyond = (int64_t)S.beyond;
         if (S.unsorted) {   // order-dependent rules in play: this chromosome's bytes through the sequential loop
           o.stats.fallback = 1; o.stats.lines = o.stats.stored = o.stats.beyond = 0;
-          std::vector<char> text((size_t)(c.end - c.start));
+          std::vector<char> text;
           size_t have = 0;
+          if (src.format != 0) {   // compressed: the range inflated once more on the host
+            if (int rc = src.host_range(c.start, c.end, text)) return fail_(rc, src.err);
+            have = text.size();
+          } else text.resize((size_t)(c.end - c.start));
           while (have < text.size()) {
             const ssize_t got = pread(fd, text.data() + have, text.size() - have, (off_t)(c.start + (int64_t)have));
             if (got <= 0) return fail_(RSI_ERR_INTERNAL, "read error on " + path);
@@ -597,6 +952,7 @@ struct rsi_genome_text {
   // The boundary pass over the chunk in pin[b] and its one read-back.  Too many name changes for the list: the chunk is cut
   // shorter (at a line end) and the rest goes in front of the next one.
   int start_chunk(int b) {
+    if (src.format == 1) return start_chunk_bgzf(b);
     if (int rc = hip_(hipMemcpyAsync(text_dev[b].p, pin[b], len[b], hipMemcpyHostToDevice, stream), "hipMemcpyAsync")) return rc;
     const size_t first = std::min<size_t>(bound_cap, 4096);
     for (;;) {
@@ -628,6 +984,78 @@ struct rsi_genome_text {
       if (nb.len >= (int)sizeof(rsi_genome_chrom::name)) return fail_(RSI_ERR_UNSUPPORTED, "genome text: a chromosome name is longer than 255 bytes");
       bnames.emplace_back(pin[b] + nb.name, (size_t)nb.len);
     }
+    cursor = 0; range_start = 0;
+    return RSI_OK;
+  }
+
+  // BGZF: the boundary pass over all the chunk's text (the unfinished last line too) and the one read-back, which also brings
+  // the inflate's report: a bad member, the last line end.  The chunk is cut there and the entries behind the cut dropped;
+  // the rest goes device to device in front of the next chunk (fill_bgzf).  The names come back from the device
+  // (launch_gather_names, 4096 at a time).  More name changes than the list holds: the chunk is cut shorter at a listed
+  // line start (in its second half where one is listed) and the pass repeats, as the text path does on the host.
+  int start_chunk_bgzf(int b) {
+    if (int rc = hip_(hipStreamWaitEvent(stream, iev, 0), "hipStreamWaitEvent")) return rc;   // the chunk's inflate (fill_bgzf)
+    const size_t first = std::min<size_t>(bound_cap, 4096);
+    const size_t total = len[b];
+    size_t cut = total;
+    int last_nl = -1;
+    for (bool once = true;; once = false) {
+      if (int rc = hip_(hipMemsetAsync(d_count(), 0, 16, stream), "hipMemsetAsync")) return rc;
+      hipEvent_t a = event(), e = event();
+      if (a) (void)hipEventRecord(a, stream);
+      launch_text_name_bounds(text_dev[b].p, (long long)cut, d_bounds(), d_count(), bound_cap, stream);
+      if (a && e) { (void)hipEventRecord(e, stream); timed.push_back({a, e, false}); }
+      if (int rc = hip_(hipMemcpyAsync(hread.p, dread.p, slots_bytes + 16 + first * sizeof(NameBound), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync")) return rc;
+      if (int rc = wait()) return rc;
+      if (once) {
+        if (int rc = src.check(b, &last_nl)) return fail_(rc, src.err);
+        if (!src.exhausted) {
+          if (last_nl < 0) return fail_(RSI_ERR_UNSUPPORTED, "a line of the depth file is longer than the chunk (" + std::to_string(chunk) + " bytes)");
+          cut = (size_t)last_nl + 1;
+        }
+      }
+      if (*h_count() <= bound_cap) break;
+      long long hi = -1, lo = 0;   // the first listed line start in the second half; the last one in the first half
+      for (size_t i = 0; i < first; ++i) {
+        const long long l = h_bounds()[i].line;
+        if (l <= 0 || l >= (long long)cut) continue;
+        if (2 * l >= (long long)cut) hi = hi < 0 ? l : std::min(hi, l);
+        else lo = std::max(lo, l);
+      }
+      const long long c = hi > 0 ? hi : lo;
+      if (c <= 0) return fail_(RSI_ERR_INTERNAL, "genome text: no line start listed to cut a chunk at");
+      cut = (size_t)c;
+    }
+    if (total - cut >= chunk) return fail_(RSI_ERR_UNSUPPORTED, "a line of the depth file is longer than the chunk (" + std::to_string(chunk) + " bytes)");
+    const unsigned k = *h_count();
+    if (k > first) {
+      if (int rc = hip_(hipMemcpyAsync(h_bounds() + first, d_bounds() + first, (k - first) * sizeof(NameBound), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync")) return rc;
+      if (int rc = wait()) return rc;
+    }
+    if (int rc = finalize_awaiting()) return rc;
+    constexpr unsigned kWin = 4096;
+    if (int rc = hip_(dnames.ensure((size_t)kWin * 256), "hipMalloc")) return rc;
+    if (int rc = hip_(hnames.ensure((size_t)kWin * 256), "hipHostMalloc")) return rc;
+    std::vector<std::pair<NameBound, std::string>> named;
+    for (unsigned w0 = 0; w0 < k; w0 += kWin) {
+      const unsigned w1 = std::min(k, w0 + kWin);
+      launch_gather_names(text_dev[b].p, d_bounds(), w0, w1, dnames.as<char>(), stream);
+      if (int rc = hip_(hipMemcpyAsync(hnames.p, dnames.p, (size_t)(w1 - w0) * 256, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync")) return rc;
+      if (int rc = wait()) return rc;
+      for (unsigned i = w0; i < w1; ++i) {
+        const NameBound& nb = h_bounds()[i];
+        if (nb.line >= (long long)cut) continue;   // the unfinished line: parsed with the next chunk
+        if (nb.len >= (int)sizeof(rsi_genome_chrom::name)) return fail_(RSI_ERR_UNSUPPORTED, "genome text: a chromosome name is longer than 255 bytes");
+        named.emplace_back(nb, std::string(hnames.as<char>() + (size_t)(i - w0) * 256, (size_t)nb.len));
+      }
+    }
+    std::sort(named.begin(), named.end(), [](const std::pair<NameBound, std::string>& x, const std::pair<NameBound, std::string>& y) { return x.first.line < y.first.line; });
+    bounds.clear(); bnames.clear();
+    for (auto& x : named) { bounds.push_back(x.first); bnames.push_back(std::move(x.second)); }
+    len[b] = cut;
+    dcut = cut; dcarry = total - cut;
+    dcarry_nl = last_nl >= (int)cut ? last_nl - (int)cut : -1;
+    consumed += (int64_t)cut;
     cursor = 0; range_start = 0;
     return RSI_OK;
   }
@@ -706,7 +1134,7 @@ struct rsi_genome_text {
       if (!prefetched) if (int rc = fill(cur)) return rc;
       prefetched = false;
       if (len[cur] == 0) {   // end of the file
-        close_open(file_size);
+        close_open(consumed);
         if (int rc = sync_counts()) return rc;
         done = true;
         return RSI_OK;
@@ -754,6 +1182,12 @@ rsi_genome_text* rsi_genome_text_open(int device, const char* path, int nref, co
     struct stat sb;
     if (fstat(g->fd, &sb) != 0) { set_global_error(std::string("Cannot stat file ") + path); return bad(RSI_ERR_BAD_ARG); }
     g->file_size = (int64_t)sb.st_size;
+    if (g->src.open_(g->fd, g->path, g->file_size)) { set_global_error(g->src.err); return bad(RSI_ERR_INTERNAL); }
+    if (g->src.format == 1) {
+      g->chunk = std::max(g->chunk, kBgzfMinChunk);   // whole members per chunk
+      if (hipStreamCreateWithFlags(&g->istream, hipStreamNonBlocking) != hipSuccess ||
+          hipEventCreateWithFlags(&g->iev, hipEventDisableTiming) != hipSuccess) { set_global_error("genome text: stream / event creation failed"); return bad(RSI_ERR_HIP); }
+    }
     if (hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&g->sync_ev, hipEventDisableTiming) != hipSuccess) { set_global_error("genome text: stream / event creation failed"); return bad(RSI_ERR_HIP); }
     // name changes per chunk: every 64 bytes of text at most before the chunk is cut shorter (start_chunk)
@@ -763,9 +1197,11 @@ rsi_genome_text* rsi_genome_text_open(int device, const char* path, int nref, co
     const size_t read_bytes = g->slots_bytes + 16 + (size_t)g->bound_cap * sizeof(NameBound);
     for (int b = 0; b < 2; ++b)
       if (hipHostMalloc(reinterpret_cast<void**>(&g->pin[b]), g->chunk, hipHostMallocDefault) != hipSuccess) { g->pin[b] = nullptr; set_global_error("out of pinned host memory for the text staging"); return bad(RSI_ERR_INTERNAL); }
-    if (g->text_dev[0].ensure(g->chunk) != hipSuccess || g->text_dev[1].ensure(g->chunk) != hipSuccess || g->dread.ensure(read_bytes) != hipSuccess ||
+    // BGZF: a chunk may run one member past `chunk` (the text carried in front of it is shorter than `chunk`)
+    const size_t text_cap = g->chunk + (g->src.format == 1 ? kMemberMax : 0);
+    if (g->text_dev[0].ensure(text_cap) != hipSuccess || g->text_dev[1].ensure(text_cap) != hipSuccess || g->dread.ensure(read_bytes) != hipSuccess ||
         g->dsegs.ensure((size_t)g->seg_cap * sizeof(GenomeSeg)) != hipSuccess ||
-        g->dwg.ensure((size_t)genome_parse_workgroups((long long)g->chunk) * 4 * sizeof(long long)) != hipSuccess ||
+        g->dwg.ensure((size_t)genome_parse_workgroups((long long)text_cap) * 4 * sizeof(long long)) != hipSuccess ||
         g->hread.ensure(read_bytes) != hipSuccess || g->hsegs.ensure((size_t)g->seg_cap * sizeof(GenomeSeg)) != hipSuccess) {
       set_global_error("genome text: out of device or pinned memory for the staging buffers");
       return bad(RSI_ERR_HIP);
@@ -824,6 +1260,12 @@ int rsi_genome_text_kernel_ms(const rsi_genome_text* g, double* bound_ms, double
 }
 
 const char* rsi_genome_text_last_error(const rsi_genome_text* g) { return g ? g->err.c_str() : "null reader"; }
+
+int rsi_genome_text_inflate_stats(const rsi_genome_text* g, rsi_inflate_stats* out) {
+  if (!g || !out) return RSI_ERR_BAD_ARG;
+  *out = g->src.st;
+  return RSI_OK;
+}
 
 void rsi_genome_text_close(rsi_genome_text* g) {
   if (!g) return;

@@ -474,6 +474,16 @@ int genome_parse_workgroups(long long nbytes);
 void launch_parse_genome_text(const void* text, long long begin, long long end, const GenomeSeg* segs, int nseg,
                               GenomeSlotStats* slots, long long* wg, hipStream_t stream);
 
+// ---- BGZF members inflated on the device (kernels_inflate.hip, inflate_core.h) ----
+// One member per entry: its deflate payload at comp[coff, coff + clen), its ISIZE bytes to text[out, out + isize) once ISIZE
+// and the CRC32 are verified.  isize <= 65536.  last_nl: atomicMax of the offset of the last '\n' written (the caller sets its
+// start value); status: atomicMin of (member index << 8 | rsinf::Err) over the bad members (the caller sets it to ~0).
+struct InflateBlock { long long coff, out; uint32_t clen, isize, crc, pad; };
+void launch_inflate_bgzf(const void* comp, const InflateBlock* blocks, int nblocks, void* text, int* last_nl,
+                         unsigned long long* status, hipStream_t stream);
+// Name bytes of the boundary pass's entries bounds[k0, k1) into out[(i - k0) * 256 ...] (at most 255 bytes each).
+void launch_gather_names(const void* text, const NameBound* bounds, unsigned k0, unsigned k1, char* out, hipStream_t stream);
+
 // ---- BAM pileup -> depth (kernels_io.hip; load_data_from_bam, loaddata.cpp:277-333 + resolve_cigar_pos, samfunctions.cpp:38-100) ----
 struct BamDepthStats { unsigned long long used, runs, malformed; };   // malformed: records whose fields overrun their block_size (skipped)
 // One thread per record: data = inflated BAM bytes, rec_off[i] = offset of record i's block_size field.  diff: int32[n + 1], zeroed

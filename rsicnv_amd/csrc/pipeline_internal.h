@@ -151,6 +151,7 @@ struct rsi_ctx {
   DevBuf text_dev[2], text_wg;               // depth text ingestion: two chunks of file bytes in HBM, per-workgroup order records
   char* text_pin[2] = {nullptr, nullptr};    // pinned staging for the file bytes
   size_t text_pin_cap = 0;
+  rsi_inflate_stats last_inflate{};          // format and inflate figures of the last text load (rsi_hot_last_inflate_stats)
   int64_t n_in = 0;                          // length of the depth currently in in_depth
   DevBuf gcbits, nbits, rd_gc, rdc, binmed, binsum, tnb, tmed, first_del;
   DevBuf depth8, rescaled8;   // byte copies: the raw depth (K2 writes it, K3' streams it), the rescaled depth (K3' -> K4')

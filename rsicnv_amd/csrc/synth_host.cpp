@@ -2,11 +2,13 @@
 // (include/rsi_synth.h).  Compiled with -ffp-contract=off so that the tables are the same
 // whatever CPU runs this.
 #include <string.h>
+#include <algorithm>
 #include <thread>
 #include <string>
 #include <stdio.h>
 #include <string.h>
 #include <vector>
+#include <zlib.h>
 #include "synth_tables.h"
 
 namespace {
@@ -153,14 +155,14 @@ extern "C" int rsi_synth_write_depth_text(const char* path, const int32_t* depth
   return fclose(f) == 0 ? 0 : -3;
 }
 
-// "RNAME<TAB>pos<TAB>depth" lines of one chromosome, appended to `path` (a whole-genome depth file, as samtools depth -a writes it)
-extern "C" int rsi_synth_append_genome_text(const char* path, const char* chrom, const int32_t* depth, int64_t n) {
-  if (!path || !chrom || !depth || n <= 0) return -1;
-  FILE* f = fopen(path, "ab");
-  if (!f) return -2;
+namespace {
+
+// "RNAME<TAB>pos<TAB>depth" lines of one chromosome, about 16 MB at a time to sink(bytes, len) (false: stop, -3)
+template <class Sink>
+int genome_lines(const char* chrom, const int32_t* depth, int64_t n, Sink sink) {
   const size_t kBuf = size_t(16) << 20;
   const size_t lc = strlen(chrom);
-  if (lc == 0 || lc > 255) { fclose(f); return -1; }
+  if (lc == 0 || lc > 255) return -1;
   std::vector<char> buf(kBuf + 320);
   size_t used = 0;
   auto put_int = [&](long long v) {
@@ -174,10 +176,77 @@ extern "C" int rsi_synth_append_genome_text(const char* path, const char* chrom,
   for (int64_t i = 0; i < n; ++i) {
     memcpy(buf.data() + used, chrom, lc); used += lc; buf[used++] = '\t';
     put_int(i + 1); buf[used++] = '\t'; put_int(depth[i]); buf[used++] = '\n';
-    if (used >= kBuf) { if (fwrite(buf.data(), 1, used, f) != used) { fclose(f); return -3; } used = 0; }
+    if (used >= kBuf) { if (!sink(buf.data(), used)) return -3; used = 0; }
   }
-  if (used && fwrite(buf.data(), 1, used, f) != used) { fclose(f); return -3; }
+  if (used && !sink(buf.data(), used)) return -3;
+  return 0;
+}
+
+// One BGZF member holding text[0, len), len <= 65280: level 6, or stored when that does not fit 64 KiB
+std::string bgzf_member(const char* text, size_t len) {
+  std::string out(65536, '\0');
+  for (int level : {6, 0}) {
+    z_stream z;
+    memset(&z, 0, sizeof(z));
+    if (deflateInit2(&z, level, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) return std::string();
+    z.next_in = reinterpret_cast<Bytef*>(const_cast<char*>(text)); z.avail_in = (uInt)len;
+    z.next_out = reinterpret_cast<Bytef*>(&out[18]); z.avail_out = 65536 - 18 - 8;
+    const int rc = deflate(&z, Z_FINISH);
+    const size_t clen = z.total_out;
+    deflateEnd(&z);
+    if (rc != Z_STREAM_END) continue;
+    const size_t bsize = 18 + clen + 8;
+    static const unsigned char head[16] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0};
+    memcpy(&out[0], head, 16);
+    out[16] = (char)((bsize - 1) & 0xff); out[17] = (char)((bsize - 1) >> 8);
+    const uint32_t crc = (uint32_t)crc32(0L, reinterpret_cast<const Bytef*>(text), (uInt)len), isz = (uint32_t)len;
+    for (int k = 0; k < 4; ++k) { out[18 + clen + k] = (char)(crc >> (8 * k)); out[22 + clen + k] = (char)(isz >> (8 * k)); }
+    out.resize(bsize);
+    return out;
+  }
+  return std::string();
+}
+
+}  // namespace
+
+// "RNAME<TAB>pos<TAB>depth" lines of one chromosome, appended to `path` (a whole-genome depth file, as samtools depth -a writes it)
+extern "C" int rsi_synth_append_genome_text(const char* path, const char* chrom, const int32_t* depth, int64_t n) {
+  if (!path || !chrom || !depth || n <= 0) return -1;
+  FILE* f = fopen(path, "ab");
+  if (!f) return -2;
+  const int rc = genome_lines(chrom, depth, n, [&](const char* p, size_t k) { return fwrite(p, 1, k, f) == k; });
+  if (rc != 0) { fclose(f); return rc; }
   return fclose(f) == 0 ? 0 : -3;
+}
+
+extern "C" int rsi_synth_append_genome_bgzf(const char* path, const char* chrom, const int32_t* depth, int64_t n) {
+  if (!path || !chrom || !depth || n <= 0) return -1;
+  FILE* f = fopen(path, "ab");
+  if (!f) return -2;
+  constexpr size_t kMember = 65280;
+  const unsigned nthreads = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+  std::string pending;   // text not yet in a member
+  bool ok = true;
+  auto flush = [&](bool all) {   // the whole members of `pending` (all: the last part too) compressed on the threads, written in order
+    const size_t nm = all ? (pending.size() + kMember - 1) / kMember : pending.size() / kMember;
+    std::vector<std::string> mem(nm);
+    std::vector<std::thread> th;
+    const unsigned nt = (unsigned)std::min<size_t>(nthreads, nm);
+    for (unsigned t = 0; t < nt; ++t)
+      th.emplace_back([&, t]() {
+        for (size_t k = t; k < nm; k += nt) mem[k] = bgzf_member(pending.data() + k * kMember, std::min(kMember, pending.size() - k * kMember));
+      });
+    for (auto& x : th) x.join();
+    for (const std::string& m : mem) ok = ok && !m.empty() && fwrite(m.data(), 1, m.size(), f) == m.size();
+    pending.erase(0, std::min(pending.size(), nm * kMember));
+    return ok;
+  };
+  int rc = genome_lines(chrom, depth, n, [&](const char* p, size_t k) { pending.append(p, k); return flush(false); });
+  if (rc == 0 && !flush(true)) rc = -3;
+  static const unsigned char kEof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  if (rc == 0 && fwrite(kEof, 1, sizeof(kEof), f) != sizeof(kEof)) rc = -3;
+  if (fclose(f) != 0 && rc == 0) rc = -3;
+  return rc;
 }
 
 extern "C" int rsi_synth_write_fasta(const char* path, const char* chrom, const uint8_t* fasta, int64_t n) {

@@ -7,8 +7,11 @@ the whole genome, the largest prefix of chromosomes (in file order) that fits is
 rows_match: the process's rows equal those of every chromosome run on its own through the library (depth from the arrays,
 last base 0 as the text path leaves it, App. A Q7), concatenated in file order.
 
-usage: genome_text_e2e.py [--dir SCRATCH] [--out JSON] [--config 4] [--workers 4] [--max-gb G]"""
-import argparse, json, os, re, shutil, subprocess, sys, tempfile, time
+--compress bgzf writes the file as BGZF (rsi_synth_append_genome_bgzf: bgzip's layout, level 6, 16 host threads; the
+process inflates it on the device), --compress gzip as ordinary gzip (one member per chromosome; inflated on the host).
+
+usage: genome_text_e2e.py [--dir SCRATCH] [--out JSON] [--config 4] [--workers 4] [--max-gb G] [--compress none|bgzf|gzip]"""
+import argparse, json, os, re, shutil, subprocess, sys, tempfile, time, zlib
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import ctypes as C
 import numpy as np
@@ -22,17 +25,20 @@ ap.add_argument("--out", default=None, help="also write the record to this JSON 
 ap.add_argument("--config", type=int, default=4)
 ap.add_argument("--workers", type=int, default=4)
 ap.add_argument("--max-gb", type=float, default=0.0, help="cap on the bytes of files (0: what the scratch directory has free, minus 4 GB)")
+ap.add_argument("--compress", choices=["none", "bgzf", "gzip"], default="none")
 args = ap.parse_args()
 
 lib = api.load_library()
 lib.rsi_synth_append_genome_text.argtypes = [C.c_char_p, C.c_char_p, C.c_void_p, C.c_int64]
+lib.rsi_synth_append_genome_bgzf.argtypes = [C.c_char_p, C.c_char_p, C.c_void_p, C.c_int64]
+bytes_per_base = {"none": 19.5, "bgzf": 5.5, "gzip": 5.5 + 17.5 / 24}[args.compress]   # file + FASTA, margin (gzip: one chromosome's text at a time)
 os.makedirs(args.dir, exist_ok=True)
 free = shutil.disk_usage(args.dir).free
 budget = (args.max_gb * (1 << 30)) if args.max_gb > 0 else max(0, free - 4 * (1 << 30))
 plans = [synth.config_plan(args.config, chrom=c) for c in range(24)]
 chosen, need = [], 0
 for c in range(24):                 # file order: chr1 .. chr24, the prefix that fits
-    b = int(plans[c]["n"] * 19.5)   # ~17 bytes of text per base + 1 of FASTA, with margin
+    b = int(plans[c]["n"] * bytes_per_base)   # ~17 bytes of text per base (or ~4 compressed) + 1 of FASTA, with margin
     if need + b > budget:
         break
     chosen.append(c); need += b
@@ -63,7 +69,20 @@ with open(fa, "wb") as ff:
         fasta = d_fa[:p["n"]].cpu().numpy(); depth = d_rd[:p["n"]].cpu().numpy()
         del d_fa, d_rd
         depth[p["n"] - 1] = 0
-        if lib.rsi_synth_append_genome_text(genome.encode(), name.encode(), depth.ctypes.data, depth.size) != 0:
+        if args.compress == "bgzf":
+            if lib.rsi_synth_append_genome_bgzf(genome.encode(), name.encode(), depth.ctypes.data, depth.size) != 0:
+                raise RuntimeError("rsi_synth_append_genome_bgzf failed")
+        elif args.compress == "gzip":
+            part = genome + ".part"
+            if lib.rsi_synth_append_genome_text(part.encode(), name.encode(), depth.ctypes.data, depth.size) != 0:
+                raise RuntimeError("rsi_synth_append_genome_text failed")
+            z = zlib.compressobj(6, zlib.DEFLATED, 31)
+            with open(part, "rb") as fi, open(genome, "ab") as fo:
+                for blk in iter(lambda: fi.read(16 << 20), b""):
+                    fo.write(z.compress(blk))
+                fo.write(z.flush())
+            os.remove(part)
+        elif lib.rsi_synth_append_genome_text(genome.encode(), name.encode(), depth.ctypes.data, depth.size) != 0:
             raise RuntimeError("rsi_synth_append_genome_text failed")
         head = f">{name}\n".encode()
         ff.write(head); off += len(head)
@@ -81,8 +100,8 @@ pool.close()
 torch.cuda.empty_cache()
 t_files = time.time() - t0
 bases = sum(plans[c]["n"] for c in chosen)
-text_bytes = os.path.getsize(genome)
-print(f"[genome_text_e2e] {len(chosen)} of 24 chromosomes, {bases / 1e9:.3f} Gb, {text_bytes / 1e9:.1f} GB of text written in {t_files:.0f} s", flush=True)
+file_bytes = os.path.getsize(genome)
+print(f"[genome_text_e2e] {len(chosen)} of 24 chromosomes, {bases / 1e9:.3f} Gb, {file_bytes / 1e9:.1f} GB of {args.compress} depth file written in {t_files:.0f} s", flush=True)
 
 
 def run_once(tag):
@@ -94,15 +113,22 @@ def run_once(tag):
     if r.returncode != 0:
         raise RuntimeError(r.stderr[-2000:])
     m = re.search(r"timing: whole-genome depth text ([0-9.e+-]+) s, (\d+) chromosomes, boundary kernels ([0-9.e+-]+) ms, parse kernels ([0-9.e+-]+) ms", r.stderr)
-    return out, wall, m
+    z = re.search(r"#depth file: (\w+), (\d+) compressed bytes, (\d+) text bytes, inflate ([0-9.e+-]+) ms", r.stderr)
+    return out, wall, m, z
 
 
 run_once("warm")                    # page cache, the device's first allocations
-out, wall, m = run_once("timed")
+out, wall, m, z = run_once("timed")
+text_bytes = int(z.group(3)) if z else file_bytes
+# depth-file bytes over PCIe: the text (plain text; gzip, inflated on the host), or the members' deflate payloads (BGZF)
+pcie_bytes = int(z.group(2)) if (z and args.compress == "bgzf") else text_bytes
 rows = [l for l in open(out).read().splitlines() if not l.startswith("#")]
 rec = {"config": f"configs[{args.config - 1}]: {flags}", "chromosomes_run": len(chosen), "chromosomes_of_genome": 24, "bases": bases,
-       "whole_genome": len(chosen) == 24, "depth_text_bytes": text_bytes, "scratch_free_bytes_at_start": free,
-       "page_cache_may_hold_file": text_bytes < os.sysconf("SC_PAGE_SIZE") * os.sysconf("SC_PHYS_PAGES") * 0.8,
+       "whole_genome": len(chosen) == 24, "compress": args.compress, "depth_text_bytes": text_bytes, "depth_file_bytes": file_bytes,
+       "pcie_depth_bytes": pcie_bytes, "inflate_ms": float(z.group(4)) if z else None,
+       "inflate_where": {"none": None, "bgzf": "device (summed kernel time)", "gzip": "host zlib (wall time)"}[args.compress],
+       "scratch_free_bytes_at_start": free,
+       "page_cache_may_hold_file": file_bytes < os.sysconf("SC_PAGE_SIZE") * os.sysconf("SC_PHYS_PAGES") * 0.8,
        "files_written_in_s": round(t_files, 1), "workers": args.workers,
        "one_process": {"s": round(wall, 3), "bases_per_s": round(bases / wall, 1), "text_bytes_per_s": round(text_bytes / wall, 1)},
        "reader_s": float(m.group(1)) if m else None, "boundary_kernels_ms": float(m.group(3)) if m else None,

@@ -174,6 +174,24 @@ void rsi_genome_text_close(rsi_genome_text* g);
 const char* rsi_genome_text_last_error(const rsi_genome_text* g);
 /* the file's format and the inflate figures so far (rsi_inflate_stats) */
 int rsi_genome_text_inflate_stats(const rsi_genome_text* g, rsi_inflate_stats* out);
+/* Cohort files, "RNAME pos d1 d2 ... dK" (samtools depth -a s1.bam ... sK.bam): the same reader, calling each selected depth
+ * column as a sample of its own.  cols: ncols 1-based depth columns, distinct, ncols in [1, 64]; sample j is column cols[j].
+ * Sample j of a line is what `iss >> pos >> d1 >> ... >> dc` leaves in dc for c = cols[j]: 0 once an extraction has failed
+ * or the line has fewer columns.  For every sample the depth and the counts are those rsi_genome_text_open gives on the file
+ * whose lines carry that column alone; the counts (and the fallback, for all samples together) depend on the positions
+ * only, so one rsi_genome_chrom serves every sample, and its d_depth is sample 0.  A depth buffer holds all samples of its
+ * chromosome and is allocated at the size of the longest of lengths[]: when fewer than two such buffers fit in the device's
+ * free memory the call fails with RSI_ERR_UNSUPPORTED, and with fewer than max_resident it uses as many as fit
+ * (rsi_genome_text_max_resident). */
+rsi_genome_text* rsi_genome_text_open_samples(int device, const char* path, int nref, const char* const* names,
+                                              const int64_t* lengths, const int32_t* cols, int ncols, int max_resident,
+                                              size_t chunk_bytes, int* status);
+int rsi_genome_text_samples(const rsi_genome_text* g);        /* ncols (1 for rsi_genome_text_open) */
+int rsi_genome_text_max_resident(const rsi_genome_text* g);   /* the depth buffers the reader uses */
+/* sample j (< ncols) of a handed-over chromosome: int32[n] in HBM, 16-byte aligned; valid until rsi_genome_text_release(slot) */
+const void* rsi_genome_text_sample_depth(const rsi_genome_text* g, int slot, int j);
+/* sample j of a handed-over chromosome into host memory; returns the element count, < 0 on error */
+int64_t rsi_genome_text_copy_sample_depth(rsi_genome_text* g, int slot, int j, int32_t* out, int64_t cap);
 /* One chromosome whose depth is already in HBM (e.g. a genome reader's buffer, not modified) and whose fasta[n] is in
  * host memory: the sequence goes to the context's own device buffer, then rsi_hot_run_device. */
 int rsi_hot_run_depth_device(rsi_ctx* ctx, const rsi_params* p, const void* d_depth, const uint8_t* fasta, int64_t n,

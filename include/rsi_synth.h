@@ -54,6 +54,9 @@ int rsi_synth_append_genome_text(const char* path, const char* chrom, const int3
 /* The same lines as BGZF (bgzip's layout: 65280 text bytes per member, zlib level 6, then the empty EOF member; members of
  * earlier calls stay in front), compressed on up to 16 host threads.  0 or < 0. */
 int rsi_synth_append_genome_bgzf(const char* path, const char* chrom, const int32_t* depth, int64_t n);
+/* A cohort file's lines, "RNAME<TAB>pos<TAB>d1<TAB>...<TAB>dk" (samtools depth -a s1.bam ... sk.bam): depths[s * n + i] is
+ * sample s + 1 at position i + 1, k in [1, 4096]; appended as text (bgzf == 0) or as BGZF members as above.  0 or < 0. */
+int rsi_synth_append_genome_samples(const char* path, const char* chrom, const int32_t* depths, int k, int64_t n, int bgzf);
 
 #ifdef __cplusplus
 }

@@ -32,7 +32,8 @@ EXPORTS = ["rsi_default_params", "rsi_hot_create", "rsi_hot_destroy", "rsi_hot_l
            "rsi_genome_text_open", "rsi_genome_text_next", "rsi_genome_text_release", "rsi_genome_text_copy_depth",
            "rsi_genome_text_kernel_ms", "rsi_genome_text_close", "rsi_genome_text_last_error", "rsi_hot_run_depth_device",
            "rsi_hot_last_inflate_stats", "rsi_hot_inflate_bgzf", "rsi_genome_text_inflate_stats",
-           "rsi_synth_append_genome_bgzf"]
+           "rsi_synth_append_genome_bgzf", "rsi_genome_text_open_samples", "rsi_genome_text_samples", "rsi_genome_text_max_resident",
+           "rsi_genome_text_sample_depth", "rsi_genome_text_copy_sample_depth", "rsi_synth_append_genome_samples"]
 
 
 class RsiParams(C.Structure):
@@ -192,6 +193,16 @@ def load_library():
     L.rsi_genome_text_last_error.argtypes = [C.c_void_p]
     L.rsi_genome_text_last_error.restype = C.c_char_p
     L.rsi_genome_text_inflate_stats.argtypes = [C.c_void_p, C.POINTER(RsiInflateStats)]
+    L.rsi_genome_text_open_samples.argtypes = [C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64),
+                                               C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_int)]
+    L.rsi_genome_text_open_samples.restype = C.c_void_p
+    L.rsi_genome_text_samples.argtypes = [C.c_void_p]
+    L.rsi_genome_text_max_resident.argtypes = [C.c_void_p]
+    L.rsi_genome_text_sample_depth.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.rsi_genome_text_sample_depth.restype = C.c_void_p
+    L.rsi_genome_text_copy_sample_depth.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64]
+    L.rsi_genome_text_copy_sample_depth.restype = C.c_int64
+    L.rsi_synth_append_genome_samples.argtypes = [C.c_char_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int64, C.c_int]
     L.rsi_hot_last_inflate_stats.argtypes = [C.c_void_p, C.POINTER(RsiInflateStats)]
     L.rsi_hot_inflate_bgzf.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(RsiInflateStats)]
     L.rsi_hot_inflate_bgzf.restype = C.c_int64
@@ -554,18 +565,29 @@ class GenomeText:
 
     auto_release=True: a chromosome's buffer is given back when the next one is asked for (read it inside the loop, e.g.
     with depth()).  auto_release=False: the caller gives it back with release(slot); at most max_resident buffers exist, and
-    the reader needs one for each new chromosome."""
+    the reader needs one for each new chromosome.
 
-    def __init__(self, path, names, lengths, chunk_bytes=0, device=0, max_resident=2, auto_release=True):
+    samples=[k1, k2, ...]: a cohort file, "RNAME pos d1 ... dK" (rsi_genome_text_open_samples): sample j is depth column
+    samples[j] (1-based); the stats are every sample's, d_depth_ptr is sample 0's, and sample_ptr() / sample_depth() give
+    sample j.  The reader may use fewer than max_resident buffers when device memory holds fewer (self.max_resident)."""
+
+    def __init__(self, path, names, lengths, chunk_bytes=0, device=0, max_resident=2, auto_release=True, samples=None):
         self.lib = load_library()
         enc = [n.encode() for n in names]
         self._names = (C.c_char_p * max(len(enc), 1))(*enc)
         self._lens = (C.c_int64 * max(len(enc), 1))(*[int(x) for x in lengths])
         st = C.c_int(0)
-        self.g = self.lib.rsi_genome_text_open(int(device), os.fsencode(path), len(enc), self._names, self._lens, int(max_resident),
-                                               int(chunk_bytes), C.byref(st))
+        if samples is None:
+            self.g = self.lib.rsi_genome_text_open(int(device), os.fsencode(path), len(enc), self._names, self._lens, int(max_resident),
+                                                   int(chunk_bytes), C.byref(st))
+        else:
+            cols = (C.c_int32 * max(len(samples), 1))(*[int(k) for k in samples])
+            self.g = self.lib.rsi_genome_text_open_samples(int(device), os.fsencode(path), len(enc), self._names, self._lens, cols,
+                                                           len(samples), int(max_resident), int(chunk_bytes), C.byref(st))
         if not self.g:
             raise RsiError(st.value, self.lib.rsi_hot_last_error(None).decode())
+        self.samples = list(samples) if samples is not None else [1]
+        self.max_resident = self.lib.rsi_genome_text_max_resident(self.g)
         self.auto_release = auto_release
         self._last = None
 
@@ -625,6 +647,24 @@ class GenomeText:
             raise RsiError(int(k), self.lib.rsi_genome_text_last_error(self.g).decode())
         return out
 
+    def sample_ptr(self, slot, j):
+        """Sample j's depth of a handed-over chromosome: its device pointer (int32[n] in HBM)."""
+        p = self.lib.rsi_genome_text_sample_depth(self.g, int(slot), int(j))
+        if not p:
+            raise RsiError(-2, f"no sample {j} in depth buffer {slot}")
+        return p
+
+    def sample_depth(self, slot, j):
+        """Sample j's depth of a handed-over chromosome as a host int32 array."""
+        n = self.lib.rsi_genome_text_copy_sample_depth(self.g, int(slot), int(j), None, 0)
+        if n < 0:
+            raise RsiError(int(n), self.lib.rsi_genome_text_last_error(self.g).decode())
+        out = np.zeros(n, dtype=np.int32)
+        k = self.lib.rsi_genome_text_copy_sample_depth(self.g, int(slot), int(j), out.ctypes.data, n)
+        if k < 0:
+            raise RsiError(int(k), self.lib.rsi_genome_text_last_error(self.g).decode())
+        return out
+
     def inflate_stats(self):
         """The file's format and the inflate figures so far (see RsiHot.inflate_stats)."""
         st = RsiInflateStats()
@@ -638,29 +678,33 @@ class GenomeText:
         return b.value, p.value
 
 
-def run_genome_text(path, names, lengths, fasta, params=None, pool=None, device=0, workers=4, chunk_bytes=0):
+def run_genome_text(path, names, lengths, fasta, params=None, pool=None, device=0, workers=4, chunk_bytes=0, samples=None):
     """Every chromosome of a whole-genome depth file through an RsiPool, each submitted as soon as its depth is parsed:
     {name: Result} in the file's order (names not among `names` are left out).  fasta: {name: uint8 array} or a callable
-    name -> uint8 array (the chromosome's sequence, length n)."""
+    name -> uint8 array (the chromosome's sequence, length n).  samples=[k1, k2, ...] (a cohort file, see GenomeText): one
+    such dict per sample, in the order of `samples`; all samples of a chromosome go to the pool as one batch."""
     import torch
     params = params if params is not None else make_params()
     own = pool is None
     pool = pool or RsiPool(device, workers)
     get = fasta if callable(fasta) else fasta.__getitem__
     inflight = []   # (name, handle, slot, the device sequence: kept alive until the run is through)
-    out = {}
-    g = GenomeText(path, names, lengths, chunk_bytes=chunk_bytes, device=device, max_resident=workers + 1, auto_release=False)
+    out = [{} for _ in (samples or [1])]
+    g = GenomeText(path, names, lengths, chunk_bytes=chunk_bytes, device=device, max_resident=workers + 1, auto_release=False,
+                   samples=samples)
+    held = max(1, min(workers, g.max_resident - 1))
 
     def collect():
         name, h, slot, _ = inflight.pop(0)
-        out[name] = pool.wait(h)[0]
+        for j, r in enumerate(pool.wait(h)):
+            out[j][name] = r
         g.release(slot)
 
     try:
         for name, d_depth, n, st in g:
             if d_depth is None:
                 continue
-            while len(inflight) >= workers:
+            while len(inflight) >= held:
                 collect()
             seq = np.ascontiguousarray(get(name), dtype=np.uint8)
             if seq.size != n:
@@ -668,7 +712,8 @@ def run_genome_text(path, names, lengths, fasta, params=None, pool=None, device=
                 raise ValueError(f"{name}: sequence of {seq.size} bases, the reference index says {n}")
             d_fa = torch.from_numpy(seq).to(f"cuda:{device}")
             torch.cuda.synchronize(device)
-            inflight.append((name, pool.submit(params, [(d_depth, d_fa.data_ptr(), n)]), st["slot"], d_fa))
+            batch = [(d_depth if samples is None else g.sample_ptr(st["slot"], j), d_fa.data_ptr(), n) for j in range(len(out))]
+            inflight.append((name, pool.submit(params, batch), st["slot"], d_fa))
         while inflight:
             collect()
     finally:
@@ -680,4 +725,4 @@ def run_genome_text(path, names, lengths, fasta, params=None, pool=None, device=
         g.close()
         if own:
             pool.close()
-    return out
+    return out if samples is not None else out[0]

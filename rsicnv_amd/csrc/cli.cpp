@@ -4,7 +4,8 @@
 // depth file (-d GENOME.depth without -c: "RNAME pos depth" lines, every chromosome in one pass, each run
 // as soon as its lines are parsed) or a BAM file (-b BAMFILE [-c RNAME], piled up on the device, calls
 // annotated with RP / Q0 from its read pairs); plot, stat and pin are outside the accelerated path
-//  and say so.
+//  and say so.  A whole-genome file with several depth columns (a cohort, RNAME POS D1 ... DK) is
+// called sample by sample with -samples all|LIST: one OUT.k per selected column k.
 #include <fcntl.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -25,6 +26,8 @@
 #include <condition_variable>
 #include <deque>
 #include <iterator>
+#include <memory>
+#include <set>
 #include <zlib.h>
 
 #include "../../include/rsi_hot.h"
@@ -39,6 +42,8 @@ struct Options {
   int gpus = 0;      // -gpus N: chromosomes spread over N devices, several in flight per device (0: one context, one at a time)
   int workers = 4;   // -workers W: chromosomes in flight per device with -gpus, and on -gpu for a whole-genome depth file
   bool saverd = false, plot = true, plotfiles = false;
+  std::string samples;   // -samples all|k1,k2,...: the depth columns of a cohort file to call (without: the first one, as always)
+  bool samples_given = false, chr_given = false;
 };
 
 int usage() {
@@ -60,6 +65,7 @@ int usage() {
             << "   -gpus INT spread the chromosomes of a BAM over INT devices (longest first), several in flight per\n"
             << "             device (-workers INT, default=4); rows are written in BAM header order all the same\n"
             << "   -workers INT chromosomes in flight (with -gpus; and on -gpu for a whole-genome depth file), default=4\n"
+            << "   -samples all|k1,k2,... call depth columns k of RNAME POS D1 ... DK (1-based, at most 64) as samples: OUT.k each\n"
             << "\nNote:\n"
             << "   This build runs the read-depth hot path on an MI355X; input is a read depth file\n"
             << "   (samtools mpileup BAM | cut -f2,4) with -c RNAME, a whole-genome depth file without -c\n"
@@ -95,7 +101,7 @@ void parse(int argc, char** argv, Options& o) {
     else if (s == "-f") { o.reffile = need(i); ++i; }
     else if (s == "-v") { need(i); ++i; }
     else if (s == "-o") { o.outfile = need(i); ++i; }
-    else if (s == "-c") { o.chr = need(i); ++i; }
+    else if (s == "-c") { o.chr = need(i); o.chr_given = true; ++i; }
     else if (s == "-s") o.saverd = true;
     else if (s == "-m") { o.P.m = atoi(need(i).c_str()); ++i; }
     else if (s == "-q") { o.minq = atoi(need(i).c_str()); ++i; }
@@ -119,6 +125,7 @@ void parse(int argc, char** argv, Options& o) {
     else if (s == "-gpu") { o.device = atoi(need(i).c_str()); ++i; }
     else if (s == "-gpus") { o.gpus = atoi(need(i).c_str()); ++i; }
     else if (s == "-workers") { o.workers = atoi(need(i).c_str()); ++i; }
+    else if (s == "-samples") { o.samples = need(i); o.samples_given = true; ++i; }
     else { std::cerr << "unknown option " << s << std::endl; exit(usage()); }
   }
   if (o.rdfile.empty() && o.bamfile.empty()) { std::cerr << "need input file " << std::endl; exit(usage()); }
@@ -325,9 +332,10 @@ void report_chromosome(rsi_ctx* ctx, const Options& o, const std::string& chr, r
   rsi_result_free(res);
 }
 
-// Columns of the first data line of a depth file (-1: none): a whole-genome file has three, RNAME POS DEPTH.
-int first_line_columns(const std::string& path) {   // through gzip / BGZF compression (zlib reads plain text as it is)
-  gzFile f = gzopen(path.c_str(), "rb");
+// Columns of the first data line of a depth file (-1: none): a whole-genome file has three, RNAME POS DEPTH, a cohort file
+// RNAME POS D1 ... DK.  header: the tokens of the last "#CHROM ..." line in front of it (samtools depth -H), if any.
+int first_line_columns(const std::string& path, std::vector<std::string>* header = nullptr) {   // through gzip / BGZF compression
+  gzFile f = gzopen(path.c_str(), "rb");                                                        // (zlib reads plain text as it is)
   if (!f) return -1;
   struct Close { gzFile f; ~Close() { gzclose(f); } } closer{f};
   std::string line, tok;
@@ -335,6 +343,11 @@ int first_line_columns(const std::string& path) {   // through gzip / BGZF compr
   while (gzgets(f, buf.data(), (int)buf.size())) {
     line = buf.data();
     while (!line.empty() && line.back() == '\n') line.pop_back();
+    if (header && line.compare(0, 6, "#CHROM") == 0) {
+      std::istringstream iss(line);
+      header->clear();
+      while (iss >> tok) header->push_back(tok);
+    }
     if (line.empty() || line[0] == '#') continue;
     std::istringstream iss(line);
     int k = 0;
@@ -360,9 +373,12 @@ bool read_fai(const std::string& fasta, std::vector<std::string>& names, std::ve
 // -d GENOME.depth without -c: the main thread drives the genome reader (ingest.hip) and reads each finished chromosome's FASTA;
 // `workers` threads, each on a context of one pool on -gpu, run the chromosomes whose depth is already in HBM and format them
 // (report_chromosome, on the context that ran them: the plots fetch from it).  At most workers + 1 depth buffers exist: before
-// asking for the next chromosome the main thread waits until one of the `workers` it may hold has come back.  Returns the
-// outputs in the file's order of first appearance; false (message in `err`) when the file cannot be read through.
-bool run_genome(const Options& o, std::vector<std::string>& chroms, std::vector<ChromOutput>& outs, std::string& err, std::string& summary) {
+// asking for the next chromosome the main thread waits until one of the `workers` it may hold has come back.  cols (-samples):
+// the cohort file's depth columns; a job is one (chromosome, sample), and a depth buffer goes back once all its samples have
+// run.  Returns the outputs in the file's order of first appearance, outs[i][j] for sample j (one sample without cols); false
+// (message in `err`) when the file cannot be read through.
+bool run_genome(const Options& o, const std::vector<int32_t>& cols, std::vector<std::string>& chroms, std::vector<std::vector<ChromOutput>>& outs,
+                std::string& err, std::string& summary) {
   std::vector<std::string> names;
   std::vector<int64_t> lens;
   if (!read_fai(o.reffile, names, lens)) { err = "no reference index"; return false; }
@@ -372,14 +388,22 @@ bool run_genome(const Options& o, std::vector<std::string>& chroms, std::vector<
   int st = 0;
   rsi_pool* pool = rsi_pool_create(o.device, nwork, &st);
   if (!pool) { err = rsi_hot_last_error(nullptr); return false; }
-  rsi_genome_text* g = rsi_genome_text_open(o.device, o.rdfile.c_str(), (int)cnames.size(), cnames.data(), lens.data(), nwork + 1, 0, &st);
+  rsi_genome_text* g = cols.empty()
+      ? rsi_genome_text_open(o.device, o.rdfile.c_str(), (int)cnames.size(), cnames.data(), lens.data(), nwork + 1, 0, &st)
+      : rsi_genome_text_open_samples(o.device, o.rdfile.c_str(), (int)cnames.size(), cnames.data(), lens.data(), cols.data(), (int)cols.size(),
+                                     nwork + 1, 0, &st);
   if (!g) { err = rsi_hot_last_error(nullptr); rsi_pool_destroy(pool); return false; }
   const double t0 = now_s();
+  const int nsamp = std::max<int>(1, (int)cols.size());
+  const int max_held = rsi_genome_text_max_resident(g) - 1;   // the reader needs one free depth buffer for each new chromosome
+  std::vector<Options> so(nsamp, o);   // sample k's plots go under <plotfolder>/k
+  for (int j = 0; j < (int)cols.size(); ++j) so[j].plotfolder = o.plotfolder + "/" + std::to_string(cols[j]);
 
-  struct Job { size_t idx; rsi_genome_chrom c; std::string fasta; double t_fasta; };
+  struct Job { size_t idx; int j; rsi_genome_chrom c; const void* d_depth; std::shared_ptr<const std::string> fasta; double t_fasta; };
   std::deque<Job> jobs;
-  std::deque<ChromOutput> done_outs;   // stable references while the main thread appends
-  std::vector<int> returned;           // depth buffers whose chromosome has been run
+  std::deque<std::vector<ChromOutput>> done_outs;   // stable references while the main thread appends
+  std::vector<int> pending(rsi_genome_text_max_resident(g), 0);   // samples of each held depth buffer not run yet
+  std::vector<int> returned;           // depth buffers whose chromosome has been run (all its samples)
   std::mutex mu;
   std::condition_variable cv_job, cv_back;
   bool closing = false;
@@ -402,29 +426,31 @@ bool run_genome(const Options& o, std::vector<std::string>& chroms, std::vector<
         info << "#processing " << chr << "\n";
         rsi_result* res = nullptr;
         const double t1 = now_s();
-        const int rc = rsi_hot_run_depth_device(ctx, &o.P, j.c.d_depth, reinterpret_cast<const uint8_t*>(j.fasta.data()), j.c.n, &res);
-        if (rc != RSI_OK) {   // as the BAM walk: a chromosome that has data and fails stops the run (rsi.cpp exits)
+        const int rc = rsi_hot_run_depth_device(ctx, &o.P, j.d_depth, reinterpret_cast<const uint8_t*>(j.fasta->data()), j.c.n, &res);
+        if (rc != RSI_OK) {   // as the BAM walk: a chromosome that has data and fails stops the run (rsi.cpp exits) -- of its sample
           info << rsi_hot_last_error(ctx) << "\n";
           co.log = info.str();
           co.fatal = true;
         } else {
-          report_chromosome(ctx, o, chr, res, &j.c.stats, nullptr, j.t_fasta, now_s() - t1, info, co);
+          report_chromosome(ctx, so[(size_t)j.j], chr, res, &j.c.stats, nullptr, j.t_fasta, now_s() - t1, info, co);
         }
         std::lock_guard<std::mutex> lk(mu);
-        done_outs[j.idx] = std::move(co);
-        returned.push_back(j.c.slot);
-        cv_back.notify_one();
+        done_outs[j.idx][(size_t)j.j] = std::move(co);
+        if (--pending[(size_t)j.c.slot] == 0) {
+          returned.push_back(j.c.slot);
+          cv_back.notify_one();
+        }
       }
     });
   int held = 0;
   bool ok = true;
   for (;;) {
-    {   // hand the run chromosomes' buffers back; hold at most nwork
+    {   // hand the run chromosomes' buffers back; hold at most max_held (nwork when memory allows)
       std::unique_lock<std::mutex> lk(mu);
       for (;;) {
         for (int slot : returned) { rsi_genome_text_release(g, slot); --held; }
         returned.clear();
-        if (held < nwork) break;
+        if (held < max_held) break;
         cv_back.wait(lk, [&] { return !returned.empty(); });
       }
     }
@@ -434,26 +460,28 @@ bool run_genome(const Options& o, std::vector<std::string>& chroms, std::vector<
     if (rc < 0) { err = rsi_genome_text_last_error(g); ok = false; break; }
     const std::string chr = c.name;
     size_t idx;
-    { std::lock_guard<std::mutex> lk(mu); idx = done_outs.size(); done_outs.emplace_back(); }
+    { std::lock_guard<std::mutex> lk(mu); idx = done_outs.size(); done_outs.emplace_back((size_t)nsamp); }
     chroms.push_back(chr);
     if (c.slot < 0) {
       std::lock_guard<std::mutex> lk(mu);
-      done_outs[idx].log = chr + " not found in fai index, skipped\n";
+      for (ChromOutput& co : done_outs[idx]) co.log = chr + " not found in fai index, skipped\n";
       continue;
     }
     const double tf = now_s();
-    std::string fasta;
-    if (!read_fasta(o.reffile, chr, fasta)) {   // not fatal for a run over many chromosomes (process_chromosome with `many`)
+    auto fasta = std::make_shared<std::string>();
+    if (!read_fasta(o.reffile, chr, *fasta)) {   // not fatal for a run over many chromosomes (process_chromosome with `many`)
       rsi_genome_text_release(g, c.slot);
       std::lock_guard<std::mutex> lk(mu);
-      done_outs[idx].log = "#processing " + chr + "\n";
+      for (ChromOutput& co : done_outs[idx]) co.log = "#processing " + chr + "\n";
       continue;
     }
-    Job j{idx, c, std::move(fasta), now_s() - tf};
+    const double t_fasta = now_s() - tf;
     std::lock_guard<std::mutex> lk(mu);
-    jobs.push_back(std::move(j));
+    pending[(size_t)c.slot] = nsamp;
+    for (int j = 0; j < nsamp; ++j)
+      jobs.push_back(Job{idx, j, c, cols.empty() ? c.d_depth : rsi_genome_text_sample_depth(g, c.slot, j), fasta, t_fasta});
     ++held;
-    cv_job.notify_one();
+    cv_job.notify_all();
   }
   { std::lock_guard<std::mutex> lk(mu); closing = true; }
   cv_job.notify_all();
@@ -472,6 +500,44 @@ bool run_genome(const Options& o, std::vector<std::string>& chroms, std::vector<
   return ok;
 }
 
+// -samples all|k1,k2,...: the depth columns to call, checked against the file's K (its first data line's columns minus RNAME
+// POS) before anything touches the device.  false: `err` says why.
+bool select_samples(const Options& o, std::vector<int32_t>& cols, std::vector<std::string>& names, std::string& err) {
+  if (o.chr_given) { err = "-samples: a cohort file is read as a whole genome, without -c"; return false; }
+  if (!o.bamfile.empty() || o.rdfile.empty()) { err = "-samples: the samples are the depth columns of a whole-genome depth file (-d), not a BAM file"; return false; }
+  if (o.gpus > 1) { err = "-gpus: a whole-genome depth file runs on one device (-gpu INT picks it)"; return false; }
+  std::vector<std::string> header;
+  const int ncol = first_line_columns(o.rdfile, &header);
+  if (ncol < 0) { err = "-samples: no data line in " + o.rdfile; return false; }
+  if (ncol < 3) { err = "-samples: " + o.rdfile + " has no RNAME POS DEPTH lines (readdepth file and chromosome must be specified together)"; return false; }
+  const int K = ncol - 2;
+  if (o.samples == "all") {
+    if (K > 64) { err = "-samples all: the file has " + std::to_string(K) + " depth columns, more than 64 samples: select at most 64 with a list"; return false; }
+    for (int k = 1; k <= K; ++k) cols.push_back(k);
+  } else {
+    std::stringstream ss(o.samples);
+    std::string tok;
+    std::set<int> seen;
+    while (std::getline(ss, tok, ',')) {
+      char* end = nullptr;
+      const long k = tok.empty() ? 0 : strtol(tok.c_str(), &end, 10);
+      if (tok.empty() || *end != '\0' || k < 1 || k > K) {
+        err = "-samples: \"" + tok + "\" is not a depth column of " + o.rdfile + " (1.." + std::to_string(K) + ")";
+        return false;
+      }
+      if (!seen.insert((int)k).second) { err = "-samples: column " + tok + " is selected twice"; return false; }
+      cols.push_back((int32_t)k);
+    }
+    if (cols.empty() || o.samples.back() == ',') { err = "-samples: expected all or a list k1,k2,... of depth columns"; return false; }
+    if (cols.size() > 64) { err = "-samples: " + std::to_string(cols.size()) + " columns selected, at most 64"; return false; }
+  }
+  if ((int)header.size() == ncol)   // "#CHROM POS name1 ... nameK"
+    for (int32_t k : cols) names.push_back(header[(size_t)k + 1]);
+  else
+    names.assign(cols.size(), "");
+  return true;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -485,6 +551,12 @@ int main(int argc, char** argv) {
     return 0;
   }
   const bool from_bam = !o.bamfile.empty();
+  std::vector<int32_t> cols;            // -samples: the cohort file's depth columns, and the header's names for them
+  std::vector<std::string> sample_names;
+  if (o.samples_given) {
+    std::string err;
+    if (!select_samples(o, cols, sample_names, err)) { std::cerr << "rsicnv: " << err << std::endl; return 1; }
+  }
   // -d without -c (-c defaults to 1-22XY): a whole-genome depth file, RNAME POS DEPTH
   const bool genome = !from_bam && !o.rdfile.empty() && o.chr == "1-22XY";
   if (genome) {
@@ -543,20 +615,66 @@ int main(int argc, char** argv) {
     std::cerr << "output written to " << o.outfile << std::endl; log << "output written to " << o.outfile << std::endl;
   };
 
+  if (genome && !cols.empty()) {   // a cohort file: OUT.k and OUT.k.log per selected column k, OUT.log for the whole run
+    auto out_k = [&](size_t j) { return o.outfile + "." + std::to_string(cols[j]); };
+    for (size_t j = 0; j < cols.size(); ++j) {
+      std::ostringstream l;
+      l << "#sample " << cols[j] << (sample_names[j].empty() ? "" : ": " + sample_names[j]) << "\n";
+      std::cerr << l.str(); log << l.str();
+    }
+    std::vector<std::string> chroms;
+    std::vector<std::vector<ChromOutput>> outs;
+    std::string err, summary;
+    const bool ok = run_genome(o, cols, chroms, outs, err, summary);
+    if (!ok) {   // no sample's output: the rows of a file that cannot be read through are not an answer
+      std::cerr << "rsicnv: " << err << std::endl; log << "rsicnv: " << err << std::endl;
+      for (size_t j = 0; j < cols.size(); ++j) { remove(out_k(j).c_str()); remove((out_k(j) + ".log").c_str()); }
+      return 1;
+    }
+    // each sample as its own genome run would write it: header, then its chromosomes until the first fatal one
+    for (size_t j = 0; j < cols.size(); ++j) {
+      const std::string path = out_k(j);
+      std::ofstream slog((path + ".log").c_str());
+      std::string h = hdr.str();
+      h.replace(h.find("#output:    " + o.outfile + "\n"), 12 + o.outfile.size() + 1, "#output:    " + path + "\n");
+      slog << h << "#sample " << cols[j] << (sample_names[j].empty() ? "" : ": " + sample_names[j]) << "\n";
+      bool header_done = false;
+      for (size_t i = 0; i < chroms.size(); ++i) {
+        const ChromOutput& co = outs[i][j];
+        std::cerr << co.log; slog << co.log;
+        if (co.populated) {
+          std::ofstream out(path.c_str(), header_done ? std::ios::app : std::ios::trunc);
+          if (!header_done) {
+            out << "#input " << o.rdfile << " sample " << cols[j] << (sample_names[j].empty() ? "" : " " + sample_names[j]) << std::endl;
+            if (o.P.gcadjust) out << "#GC adjusted\n";
+            out << kHeader << std::endl;
+            header_done = true;
+          }
+          for (const std::string& r : co.rows) out << r << std::endl;
+          out.close();
+          std::cerr << "output written to " << path << std::endl; slog << "output written to " << path << std::endl;
+        }
+        if (co.fatal) break;
+      }
+    }
+    std::cerr << summary; log << summary;
+    return 0;
+  }
+
   if (genome) {
     std::vector<std::string> chroms;
-    std::vector<ChromOutput> outs;
+    std::vector<std::vector<ChromOutput>> outs;
     std::string err, summary;
-    const bool ok = run_genome(o, chroms, outs, err, summary);
+    const bool ok = run_genome(o, cols, chroms, outs, err, summary);
     if (!ok) {   // nothing is written under OUT: the rows of a file that cannot be read through are not an answer
-      for (const ChromOutput& co : outs) { std::cerr << co.log; log << co.log; }
+      for (const auto& co : outs) { std::cerr << co[0].log; log << co[0].log; }
       std::cerr << "rsicnv: " << err << std::endl; log << "rsicnv: " << err << std::endl;
       remove(o.outfile.c_str());
       return 1;
     }
     for (size_t i = 0; i < chroms.size(); ++i) {
-      emit(chroms[i], outs[i]);
-      if (outs[i].fatal) break;
+      emit(chroms[i], outs[i][0]);
+      if (outs[i][0].fatal) break;
     }
     std::cerr << summary; log << summary;
     return 0;

@@ -17,8 +17,11 @@ namespace {
 
 // The sequential parse loop (the reference's rules in the reference's order), used when the device
 // cannot prove that positions are strictly increasing.  named: "RNAME pos depth" lines of one chromosome (the genome
-// reader's fallback): the name token and the blanks around it go first, lines without one are skipped.
-void parse_depth_text_host(const char* p, size_t sz, int64_t size, std::vector<int32_t>& rd, rsi_text_stats* st, bool named = false) {
+// reader's fallback): the name token and the blanks around it go first, lines without one are skipped.  cols (named cohort
+// lines, "RNAME pos d1 ... dK"): the 1-based depth columns to keep; sample j's array is rd[j * stride, ...), and a column is
+// what `iss >> pos >> d1 >> ... >> dc` leaves in dc (0 once an extraction has failed).
+void parse_depth_text_host(const char* p, size_t sz, int64_t size, std::vector<int32_t>& rd, rsi_text_stats* st, bool named = false,
+                           const std::vector<int32_t>* cols = nullptr, int64_t stride = 0) {
   const char* end = p + sz;
   auto blank = [](char c) { return c == ' ' || c == '\t' || c == '\r' || c == '\v' || c == '\f'; };
   auto parse_int = [&](const char*& q, const char* e, long long& v) {
@@ -31,6 +34,7 @@ void parse_depth_text_host(const char* p, size_t sz, int64_t size, std::vector<i
     v = neg ? -x : x;
     return true;
   };
+  std::vector<long long> vals(cols ? (size_t)*std::max_element(cols->begin(), cols->end()) : 0);
   const char* q = p;
   while (q < end) {
     const char* eol = (const char*)memchr(q, '\n', (size_t)(end - q));
@@ -46,11 +50,18 @@ void parse_depth_text_host(const char* p, size_t sz, int64_t size, std::vector<i
       }
       long long pos = 0, d = 0;
       if (data && parse_int(c, eol, pos)) {
+        const char* after_pos = c;
         parse_int(c, eol, d);
         if (pos >= 1) {
           ++st->lines;
           if (pos >= size) { ++st->beyond; break; }       // loaddata.cpp:514
-          rd[(size_t)pos - 1] = (int32_t)d;
+          if (cols) {
+            bool ok = true;
+            for (long long& v : vals) { v = 0; if (ok) ok = parse_int(after_pos, eol, v); }
+            for (size_t j = 0; j < cols->size(); ++j) rd[(size_t)j * (size_t)stride + (size_t)pos - 1] = (int32_t)vals[(size_t)(*cols)[j] - 1];
+          } else {
+            rd[(size_t)pos - 1] = (int32_t)d;
+          }
           ++st->stored;
         }
       }
@@ -814,6 +825,15 @@ struct rsi_genome_text {
   PinBuf hnames;
   hipStream_t istream = nullptr;         // BGZF: the next chunk's uploads and inflate run here, beside the parse of this one
   hipEvent_t iev = nullptr;              // ... recorded behind them; the boundary pass of that chunk waits for it
+  // cohort files (rsi_genome_text_open_samples): the selected depth columns, in the caller's order (sample j = cols[j]); a depth
+  // buffer holds every sample of its chromosome, sample j at j * genome_sample_stride(n), and is allocated once at its full size
+  bool samples = false;
+  std::vector<int32_t> cols{1};
+  GenomeSampleCols scols{};              // the kernel's view: ascending columns and their samples
+  size_t sample_slot_bytes = 0;          // ncols * stride(longest .fai length) * 4
+
+  int ncols() const { return (int)cols.size(); }
+  int64_t sample_stride(int slot) const { return samples ? genome_sample_stride(slot_n[(size_t)slot]) : 0; }
 
   ~rsi_genome_text() {
     if (stream && sync_ev) (void)stream_wait(stream, sync_ev);   // nothing may still write the buffers freed below (deadline as every wait)
@@ -924,9 +944,10 @@ struct rsi_genome_text {
             if (got <= 0) return fail_(RSI_ERR_INTERNAL, "read error on " + path);
             have += (size_t)got;
           }
-          std::vector<int32_t> rd((size_t)c.n, 0);
-          parse_depth_text_host(text.data(), have, c.n, rd, &o.stats, true);
-          if (int rc = hip_(hipMemcpyAsync(slot_buf[(size_t)c.slot].p, rd.data(), (size_t)c.n * 4, hipMemcpyHostToDevice, stream), "hipMemcpyAsync")) return rc;
+          const int64_t stride = samples ? genome_sample_stride(c.n) : c.n;
+          std::vector<int32_t> rd((size_t)(samples ? ncols() * stride : c.n), 0);
+          parse_depth_text_host(text.data(), have, c.n, rd, &o.stats, true, samples ? &cols : nullptr, stride);
+          if (int rc = hip_(hipMemcpyAsync(slot_buf[(size_t)c.slot].p, rd.data(), rd.size() * 4, hipMemcpyHostToDevice, stream), "hipMemcpyAsync")) return rc;
           if (int rc = wait()) return rc;
         }
       }
@@ -1103,8 +1124,9 @@ struct rsi_genome_text {
           const int64_t n = ref_len[(size_t)ref];
           if (n <= 0 || n >= (1ll << 31) - 4096) return fail_(RSI_ERR_BAD_ARG, "chromosome length must be in (0, 2^31): " + name);
           DevBuf& d = slot_buf[(size_t)slot];
-          if (int rc = hip_(d.ensure((size_t)(n + 4) * 4), "hipMalloc")) return rc;
-          if (int rc = hip_(hipMemsetAsync(d.p, 0, (size_t)(n + 4) * 4, stream), "hipMemsetAsync")) return rc;
+          const size_t bytes = samples ? (size_t)ncols() * (size_t)genome_sample_stride(n) * 4 : (size_t)(n + 4) * 4;
+          if (int rc = hip_(d.ensure(samples ? sample_slot_bytes : bytes), "hipMalloc")) return rc;
+          if (int rc = hip_(hipMemsetAsync(d.p, 0, bytes, stream), "hipMemsetAsync")) return rc;
           if (int rc = hip_(hipMemsetAsync(dread.as<GenomeSlotStats>() + slot, 0, sizeof(GenomeSlotStats), stream), "hipMemsetAsync")) return rc;
           slot_state[(size_t)slot] = 1;
           open.slot = slot; open.n = n; slot_n[(size_t)slot] = n;
@@ -1119,7 +1141,8 @@ struct rsi_genome_text {
         seg_used += (size_t)nseg;
         hipEvent_t a = event(), e = event();
         if (a) (void)hipEventRecord(a, stream);
-        launch_parse_genome_text(d_text, begin, end, d_segs, nseg, dread.as<GenomeSlotStats>(), dwg.as<long long>(), stream);
+        if (samples) launch_parse_genome_samples(d_text, begin, end, d_segs, nseg, scols, dread.as<GenomeSlotStats>(), dwg.as<long long>(), stream);
+        else launch_parse_genome_text(d_text, begin, end, d_segs, nseg, dread.as<GenomeSlotStats>(), dwg.as<long long>(), stream);
         if (a && e) { (void)hipEventRecord(e, stream); timed.push_back({a, e, true}); }
       }
       range_start = end;
@@ -1157,26 +1180,61 @@ struct rsi_genome_text {
   }
 };
 
-extern "C" {
+namespace {
 
-rsi_genome_text* rsi_genome_text_open(int device, const char* path, int nref, const char* const* names, const int64_t* lengths,
-                                      int max_resident, size_t chunk_bytes, int* status) {
+// rsi_genome_text_open (cols == nullptr) and rsi_genome_text_open_samples
+rsi_genome_text* genome_text_open(const char* fn, int device, const char* path, int nref, const char* const* names, const int64_t* lengths,
+                                  const int32_t* cols, int ncols, int max_resident, size_t chunk_bytes, int* status) {
   int st_local = 0;
   int* st = status ? status : &st_local;
   *st = RSI_OK;
   try {
-    if (!path || nref < 0 || (nref > 0 && (!names || !lengths)) || max_resident < 1) { set_global_error("rsi_genome_text_open: bad argument"); *st = RSI_ERR_BAD_ARG; return nullptr; }
-    if (chunk_bytes != 0 && (chunk_bytes < 64 || chunk_bytes > (size_t(1) << 30))) { set_global_error("rsi_genome_text_open: chunk_bytes must be 0 or in [64, 2^30]"); *st = RSI_ERR_BAD_ARG; return nullptr; }
+    if (!path || nref < 0 || (nref > 0 && (!names || !lengths)) || max_resident < 1) { set_global_error(std::string(fn) + ": bad argument"); *st = RSI_ERR_BAD_ARG; return nullptr; }
+    if (chunk_bytes != 0 && (chunk_bytes < 64 || chunk_bytes > (size_t(1) << 30))) { set_global_error(std::string(fn) + ": chunk_bytes must be 0 or in [64, 2^30]"); *st = RSI_ERR_BAD_ARG; return nullptr; }
     std::unique_ptr<rsi_genome_text> g(new rsi_genome_text());
     auto bad = [&](int code) { *st = code; return nullptr; };
+    if (cols) {   // 1-based, distinct, 1..64 of them
+      if (ncols < 1 || ncols > kMaxGenomeSamples) { set_global_error(std::string(fn) + ": ncols must be in [1, 64]"); return bad(RSI_ERR_BAD_ARG); }
+      std::vector<std::pair<int32_t, int32_t>> order;
+      for (int j = 0; j < ncols; ++j) order.emplace_back(cols[j], j);
+      std::sort(order.begin(), order.end());
+      for (int i = 0; i < ncols; ++i)
+        if (order[(size_t)i].first < 1 || (i && order[(size_t)i].first == order[(size_t)i - 1].first)) {
+          set_global_error(std::string(fn) + ": the depth columns must be distinct and 1-based");
+          return bad(RSI_ERR_BAD_ARG);
+        }
+      g->samples = true;
+      g->cols.assign(cols, cols + ncols);
+      g->scols.n = ncols;
+      for (int i = 0; i < ncols; ++i) { g->scols.col[i] = order[(size_t)i].first; g->scols.j[i] = order[(size_t)i].second; }
+    }
     g->device = device; g->path = path; g->max_resident = max_resident;
     g->chunk = chunk_bytes ? chunk_bytes : kTextChunk;
     for (int i = 0; i < nref; ++i) { g->ref_names.emplace_back(names[i] ? names[i] : ""); g->ref_len.push_back(lengths[i]); }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_global_error("no HIP device: rsicnv_amd has no CPU fallback"); return bad(RSI_ERR_NO_DEVICE); }
-    if (device < 0 || device >= ndev) { set_global_error("rsi_genome_text_open: no such device"); return bad(RSI_ERR_BAD_ARG); }
+    if (device < 0 || device >= ndev) { set_global_error(std::string(fn) + ": no such device"); return bad(RSI_ERR_BAD_ARG); }
     if (hipSetDevice(device) != hipSuccess) { set_global_error("hipSetDevice failed"); return bad(RSI_ERR_HIP); }
     drain_stale_errors();
+    if (g->samples) {   // every depth buffer is allocated at the longest sequence's size: at least two must fit
+      int64_t longest = 1;
+      for (int64_t n : g->ref_len) if (n > 0 && n < (1ll << 31) - 4096) longest = std::max(longest, n);
+      const size_t bytes = (size_t)ncols * (size_t)genome_sample_stride(longest) * 4;
+      g->sample_slot_bytes = bytes;
+      const size_t alloc = bytes + bytes / 8 + 256;   // what DevBuf::ensure asks for
+      size_t free_b = 0, total_b = 0;
+      if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { set_global_error("hipMemGetInfo failed"); return bad(RSI_ERR_HIP); }
+      const size_t usable = free_b - free_b / 8;      // an eighth stays for the contexts that run the chromosomes
+      const size_t fit = usable / alloc;
+      if (fit < 2) {
+        set_global_error(std::string(fn) + ": " + std::to_string(ncols) + " samples of the longest sequence (" + std::to_string(longest) +
+                         " bases) need " + std::to_string(alloc) + " bytes of device memory per depth buffer and two buffers at least (" +
+                         std::to_string(2 * alloc) + " bytes), but only " + std::to_string(usable) + " of " + std::to_string(free_b) +
+                         " free bytes are usable: select fewer samples");
+        return bad(RSI_ERR_UNSUPPORTED);
+      }
+      g->max_resident = (int)std::min<size_t>((size_t)max_resident, fit);
+    }
     g->fd = open(path, O_RDONLY);
     if (g->fd < 0) { set_global_error(std::string("Cannot open file ") + path); return bad(RSI_ERR_BAD_ARG); }
     struct stat sb;
@@ -1206,15 +1264,56 @@ rsi_genome_text* rsi_genome_text_open(int device, const char* path, int nref, co
       set_global_error("genome text: out of device or pinned memory for the staging buffers");
       return bad(RSI_ERR_HIP);
     }
-    g->slot_buf.reset(new DevBuf[(size_t)max_resident]);
-    g->slot_state.assign((size_t)max_resident, 0);
-    g->slot_n.assign((size_t)max_resident, 0);
+    g->slot_buf.reset(new DevBuf[(size_t)g->max_resident]);
+    g->slot_state.assign((size_t)g->max_resident, 0);
+    g->slot_n.assign((size_t)g->max_resident, 0);
     return g.release();
   } catch (const std::exception& e) {
-    set_global_error(std::string("rsi_genome_text_open: ") + e.what());
+    set_global_error(std::string(fn) + ": " + e.what());
     *st = RSI_ERR_INTERNAL;
     return nullptr;
   }
+}
+
+}  // namespace
+
+extern "C" {
+
+rsi_genome_text* rsi_genome_text_open(int device, const char* path, int nref, const char* const* names, const int64_t* lengths,
+                                      int max_resident, size_t chunk_bytes, int* status) {
+  return genome_text_open("rsi_genome_text_open", device, path, nref, names, lengths, nullptr, 0, max_resident, chunk_bytes, status);
+}
+
+rsi_genome_text* rsi_genome_text_open_samples(int device, const char* path, int nref, const char* const* names, const int64_t* lengths,
+                                              const int32_t* cols, int ncols, int max_resident, size_t chunk_bytes, int* status) {
+  if (!cols) {
+    set_global_error("rsi_genome_text_open_samples: no columns");
+    if (status) *status = RSI_ERR_BAD_ARG;
+    return nullptr;
+  }
+  return genome_text_open("rsi_genome_text_open_samples", device, path, nref, names, lengths, cols, ncols, max_resident, chunk_bytes, status);
+}
+
+int rsi_genome_text_samples(const rsi_genome_text* g) { return g ? g->ncols() : RSI_ERR_BAD_ARG; }
+
+int rsi_genome_text_max_resident(const rsi_genome_text* g) { return g ? g->max_resident : RSI_ERR_BAD_ARG; }
+
+const void* rsi_genome_text_sample_depth(const rsi_genome_text* g, int slot, int j) {
+  if (!g || slot < 0 || slot >= g->max_resident || g->slot_state[(size_t)slot] != 2 || j < 0 || j >= g->ncols()) return nullptr;
+  return static_cast<const int32_t*>(g->slot_buf[(size_t)slot].p) + (size_t)j * (size_t)g->sample_stride(slot);
+}
+
+int64_t rsi_genome_text_copy_sample_depth(rsi_genome_text* g, int slot, int j, int32_t* out, int64_t cap) {
+  if (!g || slot < 0 || slot >= g->max_resident || g->slot_state[(size_t)slot] != 2 || j < 0 || j >= g->ncols()) return RSI_ERR_BAD_ARG;
+  if (g->failed) return RSI_ERR_BAD_ARG;
+  const int64_t n = g->slot_n[(size_t)slot];
+  if (!out) return n;
+  const int64_t k = std::min(n, cap);
+  if (hipSetDevice(g->device) != hipSuccess) return g->fail_(RSI_ERR_HIP, "hipSetDevice failed");
+  const int32_t* src = static_cast<const int32_t*>(g->slot_buf[(size_t)slot].p) + (size_t)j * (size_t)g->sample_stride(slot);
+  if (int rc = g->hip_(hipMemcpyAsync(out, src, (size_t)k * 4, hipMemcpyDeviceToHost, g->stream), "hipMemcpyAsync")) return rc;
+  if (int rc = g->wait()) return rc;
+  return k;
 }
 
 int rsi_genome_text_next(rsi_genome_text* g, rsi_genome_chrom* out) {
@@ -1241,15 +1340,7 @@ void rsi_genome_text_release(rsi_genome_text* g, int slot) {
 }
 
 int64_t rsi_genome_text_copy_depth(rsi_genome_text* g, int slot, int32_t* out, int64_t cap) {
-  if (!g || slot < 0 || slot >= g->max_resident || g->slot_state[(size_t)slot] != 2) return RSI_ERR_BAD_ARG;
-  if (g->failed) return RSI_ERR_BAD_ARG;
-  const int64_t n = g->slot_n[(size_t)slot];
-  if (!out) return n;
-  const int64_t k = std::min(n, cap);
-  if (hipSetDevice(g->device) != hipSuccess) return g->fail_(RSI_ERR_HIP, "hipSetDevice failed");
-  if (int rc = g->hip_(hipMemcpyAsync(out, g->slot_buf[(size_t)slot].p, (size_t)k * 4, hipMemcpyDeviceToHost, g->stream), "hipMemcpyAsync")) return rc;
-  if (int rc = g->wait()) return rc;
-  return k;
+  return rsi_genome_text_copy_sample_depth(g, slot, 0, out, cap);
 }
 
 int rsi_genome_text_kernel_ms(const rsi_genome_text* g, double* bound_ms, double* parse_ms) {

@@ -473,6 +473,17 @@ int genome_parse_workgroups(long long nbytes);
 // last position) that the order fold reads.
 void launch_parse_genome_text(const void* text, long long begin, long long end, const GenomeSeg* segs, int nseg,
                               GenomeSlotStats* slots, long long* wg, hipStream_t stream);
+// Cohort files, "RNAME pos d1 d2 ... dK": the same pass, storing the selected depth columns.  Sample j of a segment lives at
+// depth + j * genome_sample_stride(n) (16-byte aligned starts); a line's column c is what `iss >> pos >> d1 >> ... >> dc`
+// leaves in dc (0 once an extraction has failed).  cols: the selected 1-based columns in ascending order, j[i] the sample
+// that column col[i] goes to.
+constexpr int kMaxGenomeSamples = 64;
+struct GenomeSampleCols { int32_t col[kMaxGenomeSamples], j[kMaxGenomeSamples]; int32_t n, pad; };
+__host__ __device__ inline long long genome_sample_stride(long long n) { return (n + 4 + 3) & ~3ll; }
+int genome_sample_parse_workgroups(long long nbytes);
+// wg: 4 * genome_sample_parse_workgroups(end - begin) words, as above
+void launch_parse_genome_samples(const void* text, long long begin, long long end, const GenomeSeg* segs, int nseg,
+                                 const GenomeSampleCols& cols, GenomeSlotStats* slots, long long* wg, hipStream_t stream);
 
 // ---- BGZF members inflated on the device (kernels_inflate.hip, inflate_core.h) ----
 // One member per entry: its deflate payload at comp[coff, coff + clen), its ISIZE bytes to text[out, out + isize) once ISIZE

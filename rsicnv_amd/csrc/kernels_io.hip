@@ -279,9 +279,130 @@ __global__ __launch_bounds__(kThreads) void k_genome_order_fold(const long long*
   }
 }
 
+// Cohort files: k_parse_genome_text's line walk, segment lookup, order proof and counter atomics; per counted
+// line below the chromosome's end, the depth tokens are read in order up to the largest selected column and every selected
+// one is stored to its sample's array.  A line is 15-20 bytes plus 3-4 per sample, so a thread takes kSampleSpan bytes of
+// text instead of kSpan: with 32-byte spans most threads of a wave would find no line start while a few walk a whole line.
+constexpr int kSampleSpan = 128;
+constexpr int kSampleTile = kThreads * kSampleSpan;   // 32 KB of text per workgroup
+
+__global__ __launch_bounds__(kThreads) void k_parse_genome_samples(const unsigned char* __restrict__ text, long long begin, long long end,
+                                                                   const GenomeSeg* __restrict__ segs, int nseg, GenomeSampleCols cols,
+                                                                   GenomeSlotStats* __restrict__ slots, long long* __restrict__ wg) {
+  __shared__ long long s_start[kMaxGenomeSegs];
+  __shared__ int s_segA[kThreads], s_segB[kThreads];
+  __shared__ long long s_firstA[kThreads], s_lastB[kThreads];
+  __shared__ int s_col[kMaxGenomeSamples], s_j[kMaxGenomeSamples];
+  __shared__ int s_lo, s_hi;
+  for (int i = threadIdx.x; i < nseg; i += kThreads) s_start[i] = segs[i].start;
+  if (threadIdx.x < kMaxGenomeSamples) { s_col[threadIdx.x] = cols.col[threadIdx.x]; s_j[threadIdx.x] = cols.j[threadIdx.x]; }
+  if (threadIdx.x == 0) { s_lo = 0x7fffffff; s_hi = -1; }
+  __syncthreads();
+  const int ncol = cols.n;
+  const long long b0 = begin + ((long long)blockIdx.x * kThreads + threadIdx.x) * kSampleSpan;
+  int segA = -1, segB = -1;            // segments of the thread's first / last counted line
+  long long firstA = -1, lastB = -1;   // their positions
+  int cseg = -1;                       // segment the counters below belong to
+  unsigned lines = 0, stored = 0, beyond = 0;
+  bool bad = false;
+  auto flush = [&]() {
+    if (cseg >= 0 && (lines | bad)) {
+      GenomeSlotStats* S = &slots[segs[cseg].slot];
+      if (lines) atomicAdd(&S->lines, (unsigned long long)lines);
+      if (stored) atomicAdd(&S->stored, (unsigned long long)stored);
+      if (beyond) atomicAdd(&S->beyond, (unsigned long long)beyond);
+      if (bad) atomicOr(&S->unsorted, 1u);
+    }
+    lines = stored = beyond = 0; bad = false;
+  };
+  if (b0 < end) {
+    const long long b1 = b0 + kSampleSpan < end ? b0 + kSampleSpan : end;
+    int g = -1;
+    for (long long s = b0; s < b1; ++s) {
+      if (s != 0 && text[s - 1] != '\n') continue;
+      long long e, ns, ne;
+      line_name(text, s, end, e, ns, ne);
+      if (ns == ne) continue;
+      if (g < 0) {   // last segment starting at or before s
+        int lo = 0, hi = nseg - 1;
+        while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (s_start[mid] <= s) lo = mid; else hi = mid - 1; }
+        g = lo;
+      }
+      while (g + 1 < nseg && s_start[g + 1] <= s) ++g;
+      const GenomeSeg& G = segs[g];
+      if (G.slot < 0) continue;
+      long long q = ne, pos = 0;
+      if (!parse_int(text, q, e, pos)) continue;
+      if (pos < 1) continue;
+      if (g != cseg) { flush(); cseg = g; }
+      ++lines;
+      if (segB == g && pos <= lastB) bad = true;
+      if (segA < 0) { segA = g; firstA = pos; }
+      segB = g; lastB = pos;
+      if (pos >= G.n) { ++beyond; continue; }
+      int32_t* out = G.depth + (pos - 1);
+      const long long stride = genome_sample_stride(G.n);
+      long long v = 0;
+      bool ok = true;
+      int c = 1;                       // the next depth column to extract
+      for (int i = 0; i < ncol; ++i) {
+        const int want = s_col[i];
+        while (ok && c <= want) { ok = parse_int(text, q, e, v); ++c; }
+        out[(long long)s_j[i] * stride] = ok ? (int32_t)v : 0;
+      }
+      ++stored;
+    }
+  }
+  s_segA[threadIdx.x] = segA; s_segB[threadIdx.x] = segB;
+  s_firstA[threadIdx.x] = firstA; s_lastB[threadIdx.x] = lastB;
+  if (cseg >= 0 && (lines | bad)) { atomicMin(&s_lo, cseg); atomicMax(&s_hi, cseg); }
+  __syncthreads();
+  if (threadIdx.x == 0) {   // the threads in order: a counted line must lie beyond the previous one of its segment
+    int run_seg = -1, wseg = -1;
+    long long run_last = -1, wfirst = -1;
+    for (int t = 0; t < kThreads; ++t) {
+      if (s_segA[t] < 0) continue;
+      if (wseg < 0) { wseg = s_segA[t]; wfirst = s_firstA[t]; }
+      if (s_segA[t] == run_seg && s_firstA[t] <= run_last) atomicOr(&slots[segs[run_seg].slot].unsorted, 1u);
+      run_seg = s_segB[t]; run_last = s_lastB[t];
+    }
+    long long* r = wg + 4 * (long long)blockIdx.x;
+    r[0] = wseg; r[1] = wfirst; r[2] = run_seg; r[3] = run_last;
+  }
+  if (s_lo == s_hi) {   // every thread's remaining counts are one segment's: one set of atomics for the workgroup
+    const bool mine = cseg == s_lo && (lines | bad);
+    unsigned l = mine ? lines : 0, st = mine ? stored : 0, bd = mine ? beyond : 0, bb = mine && bad ? 1u : 0u;
+    for (int d = 32; d >= 1; d >>= 1) { l += __shfl_xor(l, d); st += __shfl_xor(st, d); bd += __shfl_xor(bd, d); bb |= __shfl_xor(bb, d); }
+    __shared__ unsigned s_tot[kThreads / 64][4];
+    if ((threadIdx.x & 63) == 0) { s_tot[threadIdx.x >> 6][0] = l; s_tot[threadIdx.x >> 6][1] = st; s_tot[threadIdx.x >> 6][2] = bd; s_tot[threadIdx.x >> 6][3] = bb; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      unsigned long long t0 = 0, t1 = 0, t2 = 0; unsigned t3 = 0;
+      for (int w = 0; w < kThreads / 64; ++w) { t0 += s_tot[w][0]; t1 += s_tot[w][1]; t2 += s_tot[w][2]; t3 |= s_tot[w][3]; }
+      GenomeSlotStats* S = &slots[segs[s_lo].slot];
+      if (t0) atomicAdd(&S->lines, t0);
+      if (t1) atomicAdd(&S->stored, t1);
+      if (t2) atomicAdd(&S->beyond, t2);
+      if (t3) atomicOr(&S->unsorted, 1u);
+    }
+  } else {
+    flush();
+  }
+}
+
 }  // namespace
 
 int genome_parse_workgroups(long long nbytes) { return (int)((nbytes + kTile - 1) / kTile); }
+int genome_sample_parse_workgroups(long long nbytes) { return (int)((nbytes + kSampleTile - 1) / kSampleTile); }
+
+void launch_parse_genome_samples(const void* text, long long begin, long long end, const GenomeSeg* segs, int nseg,
+                                 const GenomeSampleCols& cols, GenomeSlotStats* slots, long long* wg, hipStream_t stream) {
+  const int grid = genome_sample_parse_workgroups(end - begin);
+  if (grid <= 0 || nseg <= 0 || cols.n <= 0) return;
+  RSI_LAUNCH(k_parse_genome_samples, dim3(grid), dim3(kThreads), 0, stream, static_cast<const unsigned char*>(text), begin, end, segs,
+             nseg, cols, slots, wg);
+  RSI_LAUNCH(k_genome_order_fold, dim3(1), dim3(kThreads), 0, stream, wg, grid, segs, slots);
+}
 
 void launch_text_name_bounds(const void* text, long long nbytes, NameBound* bounds, unsigned int* count, unsigned int cap, hipStream_t stream) {
   const int grid = (int)((nbytes + kTile - 1) / kTile);

@@ -157,13 +157,14 @@ extern "C" int rsi_synth_write_depth_text(const char* path, const int32_t* depth
 
 namespace {
 
-// "RNAME<TAB>pos<TAB>depth" lines of one chromosome, about 16 MB at a time to sink(bytes, len) (false: stop, -3)
+// "RNAME<TAB>pos<TAB>depth" lines of one chromosome (k depth columns: depth[s * n + i] is sample s at position i + 1), about
+// 16 MB at a time to sink(bytes, len) (false: stop, -3)
 template <class Sink>
-int genome_lines(const char* chrom, const int32_t* depth, int64_t n, Sink sink) {
+int genome_lines(const char* chrom, const int32_t* depth, int k, int64_t n, Sink sink) {
   const size_t kBuf = size_t(16) << 20;
   const size_t lc = strlen(chrom);
-  if (lc == 0 || lc > 255) return -1;
-  std::vector<char> buf(kBuf + 320);
+  if (lc == 0 || lc > 255 || k < 1 || k > 4096) return -1;
+  std::vector<char> buf(kBuf + 320 + 12 * (size_t)k);
   size_t used = 0;
   auto put_int = [&](long long v) {
     char tmp[24];
@@ -175,7 +176,9 @@ int genome_lines(const char* chrom, const int32_t* depth, int64_t n, Sink sink) 
   };
   for (int64_t i = 0; i < n; ++i) {
     memcpy(buf.data() + used, chrom, lc); used += lc; buf[used++] = '\t';
-    put_int(i + 1); buf[used++] = '\t'; put_int(depth[i]); buf[used++] = '\n';
+    put_int(i + 1);
+    for (int s = 0; s < k; ++s) { buf[used++] = '\t'; put_int(depth[(size_t)s * (size_t)n + (size_t)i]); }
+    buf[used++] = '\n';
     if (used >= kBuf) { if (!sink(buf.data(), used)) return -3; used = 0; }
   }
   if (used && !sink(buf.data(), used)) return -3;
@@ -214,12 +217,14 @@ extern "C" int rsi_synth_append_genome_text(const char* path, const char* chrom,
   if (!path || !chrom || !depth || n <= 0) return -1;
   FILE* f = fopen(path, "ab");
   if (!f) return -2;
-  const int rc = genome_lines(chrom, depth, n, [&](const char* p, size_t k) { return fwrite(p, 1, k, f) == k; });
+  const int rc = genome_lines(chrom, depth, 1, n, [&](const char* p, size_t k) { return fwrite(p, 1, k, f) == k; });
   if (rc != 0) { fclose(f); return rc; }
   return fclose(f) == 0 ? 0 : -3;
 }
 
-extern "C" int rsi_synth_append_genome_bgzf(const char* path, const char* chrom, const int32_t* depth, int64_t n) {
+namespace {
+
+int append_genome_bgzf(const char* path, const char* chrom, const int32_t* depth, int k, int64_t n) {
   if (!path || !chrom || !depth || n <= 0) return -1;
   FILE* f = fopen(path, "ab");
   if (!f) return -2;
@@ -241,12 +246,29 @@ extern "C" int rsi_synth_append_genome_bgzf(const char* path, const char* chrom,
     pending.erase(0, std::min(pending.size(), nm * kMember));
     return ok;
   };
-  int rc = genome_lines(chrom, depth, n, [&](const char* p, size_t k) { pending.append(p, k); return flush(false); });
+  int rc = genome_lines(chrom, depth, k, n, [&](const char* p, size_t len) { pending.append(p, len); return flush(false); });
   if (rc == 0 && !flush(true)) rc = -3;
   static const unsigned char kEof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   if (rc == 0 && fwrite(kEof, 1, sizeof(kEof), f) != sizeof(kEof)) rc = -3;
   if (fclose(f) != 0 && rc == 0) rc = -3;
   return rc;
+}
+
+}  // namespace
+
+extern "C" int rsi_synth_append_genome_bgzf(const char* path, const char* chrom, const int32_t* depth, int64_t n) {
+  return append_genome_bgzf(path, chrom, depth, 1, n);
+}
+
+// "RNAME<TAB>pos<TAB>d1<TAB>...<TAB>dk" lines (samtools depth -a s1.bam ... sk.bam), as text or as BGZF
+extern "C" int rsi_synth_append_genome_samples(const char* path, const char* chrom, const int32_t* depths, int k, int64_t n, int bgzf) {
+  if (bgzf) return append_genome_bgzf(path, chrom, depths, k, n);
+  if (!path || !chrom || !depths || n <= 0) return -1;
+  FILE* f = fopen(path, "ab");
+  if (!f) return -2;
+  const int rc = genome_lines(chrom, depths, k, n, [&](const char* p, size_t len) { return fwrite(p, 1, len, f) == len; });
+  if (rc != 0) { fclose(f); return rc; }
+  return fclose(f) == 0 ? 0 : -3;
 }
 
 extern "C" int rsi_synth_write_fasta(const char* path, const char* chrom, const uint8_t* fasta, int64_t n) {

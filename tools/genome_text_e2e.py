@@ -10,7 +10,14 @@ last base 0 as the text path leaves it, App. A Q7), concatenated in file order.
 --compress bgzf writes the file as BGZF (rsi_synth_append_genome_bgzf: bgzip's layout, level 6, 16 host threads; the
 process inflates it on the device), --compress gzip as ordinary gzip (one member per chromosome; inflated on the host).
 
-usage: genome_text_e2e.py [--dir SCRATCH] [--out JSON] [--config 4] [--workers 4] [--max-gb G] [--compress none|bgzf|gzip]"""
+--samples K writes a cohort file instead, "RNAME pos d1 ... dK" (rsi_synth_append_genome_samples; sample s's depth is the
+config's chromosome with the seed and mean shifted, the FASTA is sample 1's), and runs it once through `-samples all`
+(warm-up run, then the timed one).  Then, one at a time to bound the disk, each derived single-sample file (the same lines
+with column k alone) is written, run the same way and deleted; the rows of OUT.k must equal that run's.  The record
+(default profiles/e2e_genome_samples.json) holds the cohort run's wall time against the sum of the K single-sample runs'.
+
+usage: genome_text_e2e.py [--dir SCRATCH] [--out JSON] [--config 4] [--workers 4] [--max-gb G] [--compress none|bgzf|gzip]
+                          [--samples K]"""
 import argparse, json, os, re, shutil, subprocess, sys, tempfile, time, zlib
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import ctypes as C
@@ -26,12 +33,19 @@ ap.add_argument("--config", type=int, default=4)
 ap.add_argument("--workers", type=int, default=4)
 ap.add_argument("--max-gb", type=float, default=0.0, help="cap on the bytes of files (0: what the scratch directory has free, minus 4 GB)")
 ap.add_argument("--compress", choices=["none", "bgzf", "gzip"], default="none")
+ap.add_argument("--samples", type=int, default=0, help="K > 0: a K-column cohort file through -samples all, against its K derived files")
 args = ap.parse_args()
+if args.samples > 0 and args.out is None:
+    args.out = os.path.join(ROOT, "profiles", "e2e_genome_samples.json")
 
 lib = api.load_library()
 lib.rsi_synth_append_genome_text.argtypes = [C.c_char_p, C.c_char_p, C.c_void_p, C.c_int64]
 lib.rsi_synth_append_genome_bgzf.argtypes = [C.c_char_p, C.c_char_p, C.c_void_p, C.c_int64]
+lib.rsi_synth_append_genome_samples.argtypes = [C.c_char_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int64, C.c_int]
 bytes_per_base = {"none": 19.5, "bgzf": 5.5, "gzip": 5.5 + 17.5 / 24}[args.compress]   # file + FASTA, margin (gzip: one chromosome's text at a time)
+if args.samples > 0:   # the cohort file (~4 more text bytes per sample) and one derived file at a time
+    bytes_per_base = {"none": 19.5 + 4.5 * (args.samples - 1) + 18.5, "bgzf": 5.5 + 1.5 * (args.samples - 1) + 4.5,
+                      "gzip": 5.5 + 1.5 * (args.samples - 1) + 4.5 + (17.5 + 4.5 * args.samples) / 24}[args.compress]
 os.makedirs(args.dir, exist_ok=True)
 free = shutil.disk_usage(args.dir).free
 budget = (args.max_gb * (1 << 30)) if args.max_gb > 0 else max(0, free - 4 * (1 << 30))
@@ -50,6 +64,138 @@ flag_args = ["-m", str(flags["m"])] + (["-MED"] if flags.get("trans", 0) == 1 el
 params = api.make_params(**flags)
 
 genome, fa = os.path.join(args.dir, "genome.depth"), os.path.join(args.dir, "ref.fa")
+
+
+def append_lines(path, name, depths):
+    """depths: K x n int32 (K = 1: a three-column file) appended to `path` in the --compress form."""
+    depths = np.ascontiguousarray(depths, dtype=np.int32)
+    k, n = depths.shape
+    if args.compress == "gzip":
+        part = path + ".part"
+        if lib.rsi_synth_append_genome_samples(part.encode(), name.encode(), depths.ctypes.data, k, n, 0) != 0:
+            raise RuntimeError("rsi_synth_append_genome_samples failed")
+        z = zlib.compressobj(6, zlib.DEFLATED, 31)
+        with open(part, "rb") as fi, open(path, "ab") as fo:
+            for blk in iter(lambda: fi.read(16 << 20), b""):
+                fo.write(z.compress(blk))
+            fo.write(z.flush())
+        os.remove(part)
+    elif lib.rsi_synth_append_genome_samples(path.encode(), name.encode(), depths.ctypes.data, k, n, int(args.compress == "bgzf")) != 0:
+        raise RuntimeError("rsi_synth_append_genome_samples failed")
+
+
+def sample_depth(c, s, d_fa=None):
+    """Sample s (0-based) of chromosome c on the device: the config's plan, seed and mean shifted for s > 0; the last base 0."""
+    p = dict(plans[c])
+    if s:
+        p.update(seed=p["seed"] + 0x1000 * s, mean=p["mean"] * (1.0 + 0.15 * s))
+    d_rd = torch.empty(p["n"] + 16, dtype=torch.int32, device="cuda")
+    scratch = d_fa if d_fa is not None else torch.empty(p["n"] + 64, dtype=torch.uint8, device="cuda")
+    synth.generate_device(lib, p, scratch.data_ptr(), d_rd.data_ptr())
+    d_rd[p["n"] - 1] = 0        # the text path never sets the last base (App. A Q7)
+    torch.cuda.synchronize()
+    return d_rd
+
+
+def run_cli(depth_file, out, extra):
+    t = time.perf_counter()
+    r = subprocess.run([exe, "rsi", "-f", fa, "-d", depth_file, "-o", out, "-np", "-workers", str(args.workers)] + flag_args + extra,
+                       capture_output=True, text=True, timeout=3600)
+    wall = time.perf_counter() - t
+    if r.returncode != 0:
+        raise RuntimeError(r.stderr[-2000:])
+    m = re.search(r"timing: whole-genome depth text ([0-9.e+-]+) s, (\d+) chromosomes, boundary kernels ([0-9.e+-]+) ms, parse kernels ([0-9.e+-]+) ms", r.stderr)
+    return wall, m
+
+
+def rows_of(path):
+    return [l for l in open(path).read().splitlines() if not l.startswith("#")]
+
+
+if args.samples > 0:
+    K = args.samples
+    for p in (genome, fa):
+        if os.path.exists(p):
+            os.remove(p)
+    torch.cuda.set_device(0)
+    t0 = time.time()
+    fai, off = [], 0
+    with open(fa, "wb") as ff:
+        for c in chosen:
+            name = f"chr{c + 1}"
+            d_fa = torch.empty(plans[c]["n"] + 64, dtype=torch.uint8, device="cuda")
+            depths = np.stack([sample_depth(c, s, d_fa if s == 0 else None)[:plans[c]["n"]].cpu().numpy() for s in range(K)])
+            fasta = d_fa[:plans[c]["n"]].cpu().numpy()
+            del d_fa
+            append_lines(genome, name, depths)
+            head = f">{name}\n".encode()
+            ff.write(head); off += len(head)
+            full = (fasta.size // 60) * 60
+            body = np.concatenate([fasta[:full].reshape(-1, 60), np.full((full // 60, 1), 10, np.uint8)], axis=1).tobytes()
+            if fasta.size > full:
+                body += fasta[full:].tobytes() + b"\n"
+            ff.write(body)
+            fai.append(f"{name}\t{fasta.size}\t{off}\t60\t61")
+            off += len(body)
+            del fasta, depths
+    with open(fa + ".fai", "w") as f:
+        f.write("\n".join(fai) + "\n")
+    torch.cuda.empty_cache()
+    t_files = time.time() - t0
+    bases = sum(plans[c]["n"] for c in chosen)
+    cohort_bytes = os.path.getsize(genome)
+    print(f"[genome_text_e2e] cohort of {K}: {len(chosen)} of 24 chromosomes, {bases / 1e9:.3f} Gb, {cohort_bytes / 1e9:.1f} GB "
+          f"{args.compress} file written in {t_files:.0f} s", flush=True)
+    out = os.path.join(args.dir, "cohort.txt")
+    run_cli(genome, out, ["-samples", "all"])                # page cache, the device's first allocations
+    wall, m = run_cli(genome, out, ["-samples", "all"])
+    cohort_rows = {k: rows_of(f"{out}.{k}") for k in range(1, K + 1)}
+    cohort_text = int(re.search(r"(\d+) text bytes", open(out + ".log").read()).group(1)) if args.compress != "none" else cohort_bytes
+    singles, rows_equal = [], {}
+    os.remove(genome)
+    for k in range(1, K + 1):   # derived file k: the same lines with column k alone, written from the same depths
+        one = os.path.join(args.dir, f"derived_{k}.depth")
+        for c in chosen:
+            append_lines(one, f"chr{c + 1}", sample_depth(c, k - 1)[:plans[c]["n"]].cpu().numpy()[None, :])
+        torch.cuda.empty_cache()
+        o1 = os.path.join(args.dir, f"one_{k}.txt")
+        run_cli(one, o1, [])
+        w1, m1 = run_cli(one, o1, [])
+        size = os.path.getsize(one)
+        os.remove(one)
+        rows_equal[k] = rows_of(o1) == cohort_rows[k]
+        singles.append({"sample": k, "s": round(w1, 3), "file_bytes": size, "reader_s": float(m1.group(1)) if m1 else None,
+                        "parse_kernels_ms": float(m1.group(4)) if m1 else None, "calls": len(rows_of(o1))})
+        print(f"[genome_text_e2e] derived file {k}: {w1:.2f} s, rows equal: {rows_equal[k]}", flush=True)
+    sum_single = sum(x["s"] for x in singles)
+    parse_ms = float(m.group(4)) if m else None
+    single_parse = [x["parse_kernels_ms"] for x in singles if x["parse_kernels_ms"]]
+    rec = {"what": f"tools/genome_text_e2e.py --samples {K} --compress {args.compress}: one {K}-column cohort file through "
+                   f"`rsicnv rsi -d COHORT -samples all`, against the {K} derived single-sample files run one after the other in the same session",
+           "config": f"configs[{args.config - 1}]: {flags}", "chromosomes_run": len(chosen), "chromosomes_of_genome": 24, "bases": bases,
+           "whole_genome": len(chosen) == 24, "genome_used": f"chr1..chr{len(chosen)} of the 3 Gb synthetic genome, {bases / 1e9:.3f} Gb "
+                                                           f"(--max-gb {args.max_gb}: the files must fit)",
+           "samples": K, "compress": args.compress, "workers": args.workers, "cohort_file_bytes": cohort_bytes, "cohort_text_bytes": cohort_text,
+           "files_written_in_s": round(t_files, 1),
+           "cohort": {"s": round(wall, 3), "reader_s": float(m.group(1)) if m else None,
+                      "boundary_kernels_ms": float(m.group(3)) if m else None, "parse_kernels_ms": parse_ms,
+                      "parse_kernel_text_bytes_per_s": round(cohort_text / (parse_ms * 1e-3), 1) if parse_ms else "not measured",
+                      "sample_bases_per_s": round(K * bases / wall, 1)},
+           "single_sample_runs": singles, "sum_single_s": round(sum_single, 3),
+           "single_parse_kernel_text_bytes_per_s": round(sum(x["file_bytes"] for x in singles) / (sum(single_parse) * 1e-3), 1)
+           if len(single_parse) == K and args.compress == "none" else "not measured",
+           "cohort_over_sum": round(wall / sum_single, 3), "bar_met": wall < sum_single,
+           "rows_equal": all(rows_equal.values()), "rows_equal_per_sample": rows_equal,
+           "calls_per_sample": {k: len(v) for k, v in cohort_rows.items()},
+           "compare": "profiles/e2e_genome_bgzf.json: one text run of the whole genome, 3.3e8 bases/s",
+           "note": "wall times of whole processes (start, FASTA reads, one pass over the depth file, detection, output); each the "
+                   "second of two runs of the same file (the file in the page cache as far as it holds it)"}
+    with open(args.out, "w") as f:
+        json.dump(rec, f, indent=1)
+    print(json.dumps(rec), flush=True)
+    shutil.rmtree(args.dir, ignore_errors=True)
+    sys.exit(0)
+
 for p in (genome, fa):
     if os.path.exists(p):
         os.remove(p)

@@ -99,7 +99,8 @@ int rsi_hot_run(rsi_ctx* ctx, const rsi_params* p, const int32_t* depth, const u
                 rsi_result** out);
 
 /* ---- Depth text ingestion on the device --------------------------------------------
- * Replaces the parse loop of load_data_from_text (loaddata.cpp:496-517): "pos depth" lines; empty lines
+ * Replaces the parse loop of load_data_from_text (loaddata.cpp:496-517): "pos depth" lines read as
+ * libstdc++'s `iss >> pos >> d` reads them (an int outside its range is clamped and fails); empty lines
  * and '#' lines skipped; pos < 1 skipped; reading stops at the first pos >= n (the last base is never
  * set); RD[pos-1] = depth; positions that never appear stay 0.  The file is streamed to HBM in pinned
  * chunks and parsed by a kernel; files whose positions are not strictly increasing (where the order-
@@ -176,8 +177,8 @@ const char* rsi_genome_text_last_error(const rsi_genome_text* g);
 int rsi_genome_text_inflate_stats(const rsi_genome_text* g, rsi_inflate_stats* out);
 /* Cohort files, "RNAME pos d1 d2 ... dK" (samtools depth -a s1.bam ... sK.bam): the same reader, calling each selected depth
  * column as a sample of its own.  cols: ncols 1-based depth columns, distinct, ncols in [1, 64]; sample j is column cols[j].
- * Sample j of a line is what `iss >> pos >> d1 >> ... >> dc` leaves in dc for c = cols[j]: 0 once an extraction has failed
- * or the line has fewer columns.  For every sample the depth and the counts are those rsi_genome_text_open gives on the file
+ * Sample j of a line is what `iss >> pos >> d1 >> ... >> dc` leaves in dc for c = cols[j]: the clamped bound when dc itself
+ * overflows, 0 once an earlier extraction has failed (an overflow included) or the line has fewer columns.  For every sample the depth and the counts are those rsi_genome_text_open gives on the file
  * whose lines carry that column alone; the counts (and the fallback, for all samples together) depend on the positions
  * only, so one rsi_genome_chrom serves every sample, and its d_depth is sample 0.  A depth buffer holds all samples of its
  * chromosome and is allocated at the size of the longest of lengths[]: when fewer than two such buffers fit in the device's
@@ -193,7 +194,8 @@ const void* rsi_genome_text_sample_depth(const rsi_genome_text* g, int slot, int
 /* sample j of a handed-over chromosome into host memory; returns the element count, < 0 on error */
 int64_t rsi_genome_text_copy_sample_depth(rsi_genome_text* g, int slot, int j, int32_t* out, int64_t cap);
 /* bedGraph files, "RNAME start end d" (mosdepth per-base.bed.gz, bedtools genomecov -bg / -bga): the same reader and handle.
- * A line stands for the lines "RNAME p d", p = start + 1 .. end (0-based, half-open; none when end <= start), and every
+ * A line stands for the lines "RNAME p d", p = start + 1 .. end (0-based, half-open; start and end read as long long, none
+ * when either fails, an overflow included, or end <= start), and every
  * chromosome's depth, counts, hand-over order and errors are those rsi_genome_text_open gives on that expanded file; only
  * stats.bytes is the chromosome's byte range in the bedGraph text.  "track" and "browser" lines are skipped.  Parse time goes
  * to rsi_genome_text_kernel_ms's parse_ms. */

@@ -161,6 +161,8 @@ class Ref:
         L = self.lib = C.CDLL(REF_SO)
         L.ref_load.argtypes = [C.POINTER(Params), C.POINTER(C.c_int32), C.c_char_p, C.c_int32, C.c_char_p, C.c_char_p]
         L.ref_get_rd.argtypes = [C.POINTER(C.c_int32), C.c_int32]
+        if self.has_load_text():   # a libref.so built from an older ref_driver.cpp lacks it; everything else still works
+            L.ref_load_text.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_int32), C.c_int32]
         L.ref_get_noncode.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32]
         L.ref_get_chrom_scalars.argtypes = [C.POINTER(C.c_double)]
         L.ref_get_bins.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int32]
@@ -186,6 +188,23 @@ class Ref:
         self._keep = (d, f)
         return self.lib.ref_load(C.byref(params), dp, f.ctypes.data_as(C.c_char_p), d.size, chrom.encode(),
                                  (log or "").encode())
+
+    def has_load_text(self):
+        """True when this libref.so has ref_load_text (built from today's oracle/ref_driver.cpp)."""
+        return hasattr(self.lib, "ref_load_text")
+
+    def load_text(self, path, fasta_path, chrom="chrS", cap=None):
+        """The reference's load_data_from_text on a depth file (GC adjustment and cap off): RD as int32.  The reference
+        exits the process when the FASTA's .fai is missing, so that is checked here first."""
+        if not self.has_load_text():
+            raise RuntimeError(f"{REF_SO} predates ref_load_text: rebuild it with `make -f oracle/Makefile.ref`")
+        if not os.path.exists(str(fasta_path) + ".fai"):
+            raise FileNotFoundError(f"{fasta_path}.fai")
+        cap = int(cap if cap is not None else 1 << 28)
+        out = np.zeros(cap, dtype=np.int32)
+        n = self.lib.ref_load_text(str(path).encode(), str(fasta_path).encode(), chrom.encode(),
+                                   out.ctypes.data_as(C.POINTER(C.c_int32)), cap)
+        return out[:n].copy() if n <= cap else self.rd()
 
     def stage_gc(self):
         return self.lib.ref_stage_gc()

@@ -200,6 +200,32 @@ int ref_stage_concat(void) {   // rsi.cpp:2200-2203
   quiet_end();
   return S.RD.size();
 }
+// The reference's own text loader on a depth file: the globals set as ref_load sets them, GC adjustment and cap off,
+// then the unmodified load_data_from_text (loaddata.cpp:473-531; fasta_path needs its .fai).  RD is copied to out (at most
+// cap values) and kept as the session's RD.  Returns RD's size.  The loader's summary lines go to /dev/null.
+int ref_load_text(const char* path, const char* fasta_path, const char* chrom, int32_t* out, int32_t cap) {
+  ref_params p;
+  ref_default_params(&p);
+  p.gcadjust = 0; p.cap = 0.0;
+  ref_load(&p, nullptr, "", 0, chrom, nullptr);
+  rsi::reffile = fasta_path;
+  rsi::rdfile = path;
+  quiet_begin();
+  fflush(stdout); cout.flush();
+  const int saved_stdout = dup(1);
+  const int nul = open("/dev/null", O_WRONLY);
+  dup2(nul, 1);
+  close(nul);
+  load_data_from_text(path, S.RD);
+  cout.flush(); fflush(stdout);
+  dup2(saved_stdout, 1);
+  close(saved_stdout);
+  quiet_end();
+  const int n = S.RD.size() < cap ? S.RD.size() : cap;
+  for (int i = 0; i < n; ++i) out[i] = S.RD[i];
+  return S.RD.size();
+}
+
 int ref_rd_size(void) { return S.RD.size(); }
 int ref_get_rd(int32_t* out, int32_t cap) {
   int n = S.RD.size() < cap ? S.RD.size() : cap;

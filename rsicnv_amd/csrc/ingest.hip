@@ -4,6 +4,7 @@
 // (kernels_io.hip); BGZF inflation and the record walk stay on host threads (bam_host.cpp).
 #include "pipeline_internal.h"
 #include "inflate_core.h"
+#include "text_rules.h"
 #include <memory>
 #include <unordered_set>
 #include <zlib.h>
@@ -21,20 +22,17 @@ namespace {
 // lines, "RNAME pos d1 ... dK"): the 1-based depth columns to keep; sample j's array is rd[j * stride, ...), and a column is
 // what `iss >> pos >> d1 >> ... >> dc` leaves in dc (0 once an extraction has failed).  bed (named bedGraph lines, "RNAME start
 // end d"): each line is read as the lines "RNAME p d", p = start + 1 .. end, in order; "track" and "browser"
-// lines are skipped.
+// lines are skipped.  Every extraction is text_rules.h's, the device kernels' own.
 void parse_depth_text_host(const char* p, size_t sz, int64_t size, std::vector<int32_t>& rd, rsi_text_stats* st, bool named = false,
                            const std::vector<int32_t>* cols = nullptr, int64_t stride = 0, bool bed = false) {
   const char* end = p + sz;
-  auto blank = [](char c) { return c == ' ' || c == '\t' || c == '\r' || c == '\v' || c == '\f'; };
-  auto parse_int = [&](const char*& q, const char* e, long long& v) {
-    while (q < e && blank(*q)) ++q;
-    bool neg = false;
-    if (q < e && (*q == '-' || *q == '+')) { neg = *q == '-'; ++q; }
-    if (q >= e || *q < '0' || *q > '9') { v = 0; return false; }
-    long long x = 0;
-    while (q < e && *q >= '0' && *q <= '9') { x = x * 10 + (*q - '0'); ++q; }
-    v = neg ? -x : x;
-    return true;
+  auto blank = [](char c) { return rsitxt::is_blank((unsigned char)c); };
+  // `iss >> v` on [q, e) into an int (i32) or a long long (bedGraph start and end)
+  auto parse_int = [](const char*& q, const char* e, long long& v, bool i64 = false) {
+    long long k = 0;
+    const bool ok = i64 ? rsitxt::extract_i64(q, k, (long long)(e - q), v) : rsitxt::extract_i32(q, k, (long long)(e - q), v);
+    q += k;
+    return ok;
   };
   std::vector<long long> vals(cols ? (size_t)*std::max_element(cols->begin(), cols->end()) : 0);
   const char* q = p;
@@ -56,7 +54,7 @@ void parse_depth_text_host(const char* p, size_t sz, int64_t size, std::vector<i
         if ((nl == 5 && memcmp(name, "track", 5) == 0) || (nl == 7 && memcmp(name, "browser", 7) == 0)) data = false;
       }
       long long start = 0, stop = 0, d = 0;
-      if (bed && data && parse_int(c, eol, start) && parse_int(c, eol, stop)) {
+      if (bed && data && parse_int(c, eol, start, true) && parse_int(c, eol, stop, true)) {
         parse_int(c, eol, d);
         const long long a = std::max(start, 0ll), b = stop;
         if (b > a) {   // positions a + 1 .. b; the first one >= size ends the file (loaddata.cpp:514)
@@ -69,15 +67,16 @@ void parse_depth_text_host(const char* p, size_t sz, int64_t size, std::vector<i
         }
       }
       long long pos = 0;
-      if (!bed && data && parse_int(c, eol, pos)) {
+      if (!bed && data) {   // a failed pos is 0 or clamped (INT_MIN: skipped, INT_MAX: the end) and leaves d at 0
+        const bool ok = parse_int(c, eol, pos);
         const char* after_pos = c;
-        parse_int(c, eol, d);
+        if (ok) parse_int(c, eol, d);
         if (pos >= 1) {
           ++st->lines;
           if (pos >= size) { ++st->beyond; break; }       // loaddata.cpp:514
           if (cols) {
-            bool ok = true;
-            for (long long& v : vals) { v = 0; if (ok) ok = parse_int(after_pos, eol, v); }
+            bool good = true;
+            for (long long& v : vals) { v = 0; if (good) good = parse_int(after_pos, eol, v); }
             for (size_t j = 0; j < cols->size(); ++j) rd[(size_t)j * (size_t)stride + (size_t)pos - 1] = (int32_t)vals[(size_t)(*cols)[j] - 1];
           } else {
             rd[(size_t)pos - 1] = (int32_t)d;

@@ -3,14 +3,17 @@
 // about 65 % of its wall time on the -d path.  Here the file's bytes are streamed to HBM in pinned
 // chunks and parsed by one kernel at memory speed.
 //
-// Reference semantics kept: empty lines and lines starting with '#' are skipped; `iss >> pos >> d`
-// (leading blanks, optional sign, digits; a failed extraction leaves 0); pos < 1 skipped; reading
+// Reference semantics kept: empty lines and lines starting with '#' are skipped; `iss >> pos >> d` with libstdc++'s
+// extraction (text_rules.h: leading blanks, optional sign, digits; no digit gives 0, a value outside int the clamped
+// bound, and either failure leaves d at 0; an overflowing pos is therefore INT_MIN, skipped, or INT_MAX, beyond the
+// end); pos < 1 skipped; reading
 // STOPS at the first pos >= size (the last base is never set, App. A Q7); RD[pos-1] = d, later lines
 // overwrite earlier ones.  The last two rules are order-dependent, so the kernel also proves that
 // positions are strictly increasing through the file (true for any samtools-depth style file): then
 // "stop at the first pos >= size" equals "ignore every pos >= size" and no position is written twice.
 // When the proof fails the caller falls back to the sequential host parser (same semantics, slower).
 #include "kernels.h"
+#include "text_rules.h"
 
 namespace rsik {
 
@@ -20,19 +23,9 @@ constexpr int kThreads = 256;
 constexpr int kSpan = 32;                      // bytes of text per thread: the lines that START in them are the thread's
 constexpr int kTile = kThreads * kSpan;        // 8 KB of text per workgroup
 
-__device__ inline bool is_blank(unsigned char c) { return c == ' ' || c == '\t' || c == '\r' || c == '\v' || c == '\f'; }
-
-// `iss >> v` on [q, e): leading blanks, optional sign, digits.  false (v = 0) when no digit follows.
-__device__ inline bool parse_int(const unsigned char* __restrict__ t, long long& q, long long e, long long& v) {
-  while (q < e && is_blank(t[q])) ++q;
-  bool neg = false;
-  if (q < e && (t[q] == '-' || t[q] == '+')) { neg = t[q] == '-'; ++q; }
-  if (q >= e || t[q] < '0' || t[q] > '9') { v = 0; return false; }
-  long long x = 0;
-  while (q < e && t[q] >= '0' && t[q] <= '9') { x = x * 10 + (t[q] - '0'); ++q; }
-  v = neg ? -x : x;
-  return true;
-}
+using rsitxt::is_blank;
+using rsitxt::extract_i32;   // `iss >> v` into an int: pos, d and the cohort columns
+using rsitxt::extract_i64;   // into a long long: bedGraph start and end
 
 __global__ __launch_bounds__(kThreads) void k_parse_depth_text(const unsigned char* __restrict__ text, long long nbytes,
                                                               long long size, int32_t* __restrict__ depth,
@@ -53,8 +46,7 @@ __global__ __launch_bounds__(kThreads) void k_parse_depth_text(const unsigned ch
       while (e < nbytes && text[e] != '\n') ++e;              // lines are short; they may run past the span
       if (e == s || text[s] == '#') continue;
       long long q = s, pos = 0, d = 0;
-      if (!parse_int(text, q, e, pos)) continue;              // extraction failed: pos = 0, skipped below anyway
-      parse_int(text, q, e, d);
+      if (extract_i32(text, q, e, pos)) extract_i32(text, q, e, d);   // a failed pos (0 or clamped) leaves d at 0
       if (pos < 1) continue;
       ++lines;
       if (last >= 0 && pos <= last) sorted = false;
@@ -131,7 +123,7 @@ __device__ inline void data_line(const unsigned char* __restrict__ t, long long 
   line_name(t, s, lim, e, ns, ne);
   if (!kBed || ns == ne) return;
   long long q = ne, a = 0, b = 0;
-  if (is_word(t, ns, ne, "track", 5) || is_word(t, ns, ne, "browser", 7) || !parse_int(t, q, e, a) || !parse_int(t, q, e, b) || b <= a) ne = ns;
+  if (is_word(t, ns, ne, "track", 5) || is_word(t, ns, ne, "browser", 7) || !extract_i64(t, q, e, a) || !extract_i64(t, q, e, b) || b <= a) ne = ns;
 }
 
 __device__ inline bool same_name(const unsigned char* __restrict__ t, long long a, long long alen, long long b, long long blen) {
@@ -223,8 +215,7 @@ __global__ __launch_bounds__(kThreads) void k_parse_genome_text(const unsigned c
       const GenomeSeg& G = segs[g];
       if (G.slot < 0) continue;
       long long q = ne, pos = 0, d = 0;
-      if (!parse_int(text, q, e, pos)) continue;
-      parse_int(text, q, e, d);
+      if (extract_i32(text, q, e, pos)) extract_i32(text, q, e, d);
       if (pos < 1) continue;
       if (g != cseg) { flush(); cseg = g; }
       ++lines;
@@ -350,7 +341,7 @@ __global__ __launch_bounds__(kThreads) void k_parse_genome_samples(const unsigne
       const GenomeSeg& G = segs[g];
       if (G.slot < 0) continue;
       long long q = ne, pos = 0;
-      if (!parse_int(text, q, e, pos)) continue;
+      bool ok = extract_i32(text, q, e, pos);
       if (pos < 1) continue;
       if (g != cseg) { flush(); cseg = g; }
       ++lines;
@@ -360,13 +351,14 @@ __global__ __launch_bounds__(kThreads) void k_parse_genome_samples(const unsigne
       if (pos >= G.n) { ++beyond; continue; }
       int32_t* out = G.depth + (pos - 1);
       const long long stride = genome_sample_stride(G.n);
+      // Column c is what its own extraction gives (the clamped bound included) while every extraction before it succeeded,
+      // 0 after a failed one.  (pos < n here, so pos did not overflow and ok holds.)
       long long v = 0;
-      bool ok = true;
       int c = 1;                       // the next depth column to extract
       for (int i = 0; i < ncol; ++i) {
         const int want = s_col[i];
-        while (ok && c <= want) { ok = parse_int(text, q, e, v); ++c; }
-        out[(long long)s_j[i] * stride] = ok ? (int32_t)v : 0;
+        while (c <= want) { v = 0; if (ok) ok = extract_i32(text, q, e, v); ++c; }
+        out[(long long)s_j[i] * stride] = (int32_t)v;
       }
       ++stored;
     }
@@ -463,8 +455,8 @@ __global__ __launch_bounds__(kThreads) void k_parse_genome_bedgraph(const unsign
       const GenomeSeg& G = segs[g];
       if (G.slot < 0) continue;
       long long q = ne, start = 0, stop = 0, d = 0;
-      if (!parse_int(text, q, e, start) || !parse_int(text, q, e, stop)) continue;
-      parse_int(text, q, e, d);
+      if (!extract_i64(text, q, e, start) || !extract_i64(text, q, e, stop)) continue;   // overflow included: no line
+      extract_i32(text, q, e, d);
       const long long a = start > 0 ? start : 0, b = stop;
       if (b <= a) continue;            // no position >= 1
       if (g != cseg) { flush(); cseg = g; }

@@ -13,37 +13,15 @@ import pytest
 
 import bgzf_util as bz
 from conftest import make_case
-from test_cohort_depth import parse_int
+from text_rules import expand_line
 from test_genome_text import EXE, write_fasta
 
-BLANK = " \t\r\v\f"
 STATS = ("lines", "stored", "beyond", "fallback")
 
 
 # ---------------------------------------------------------------------------------------------------------------------
 # the rule, restated: the expanded per-base file
 # ---------------------------------------------------------------------------------------------------------------------
-
-def expand_line(line):
-    """One bedGraph text line (no '\\n') -> the per-base lines it stands for."""
-    if not line or line[0] == "#":
-        return []
-    q = 0
-    while q < len(line) and line[q] in BLANK:
-        q += 1
-    s = q
-    while q < len(line) and line[q] not in BLANK:
-        q += 1
-    name = line[s:q]
-    if not name or name in ("track", "browser"):
-        return []
-    ok1, start, q = parse_int(line, q)
-    ok2, end, q = parse_int(line, q) if ok1 else (False, 0, q)
-    if not (ok1 and ok2) or end <= start:
-        return []
-    _, d, _ = parse_int(line, q)
-    return [f"{name}\t{p}\t{d}" for p in range(start + 1, end + 1)]
-
 
 def expand(text):
     out = []

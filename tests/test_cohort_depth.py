@@ -10,10 +10,10 @@ import numpy as np
 import pytest
 
 import bgzf_util as bz
+import text_rules as tr
 from conftest import make_case
 from test_genome_text import EXE, render, slice_text, write_fasta
 
-BLANK = " \t\r\v\f"
 STATS = ("lines", "stored", "beyond", "fallback")
 
 
@@ -21,34 +21,13 @@ STATS = ("lines", "stored", "beyond", "fallback")
 # the line rule, restated: derived files
 # ---------------------------------------------------------------------------------------------------------------------
 
-def parse_int(t, q):
-    """`iss >> v` on t[q:]: (ok, v, q after it) -- parse_int in kernels_io.hip."""
-    e = len(t)
-    while q < e and t[q] in BLANK:
-        q += 1
-    neg = False
-    if q < e and t[q] in "+-":
-        neg = t[q] == "-"
-        q += 1
-    if q >= e or not ("0" <= t[q] <= "9"):
-        return False, 0, q
-    x = 0
-    while q < e and "0" <= t[q] <= "9":
-        x = x * 10 + ord(t[q]) - 48
-        q += 1
-    return True, (-x if neg else x), q
-
-
 def derive(rest, k):
-    """A cohort line's part behind the name -> derived file k's: the position as it is, then dk."""
-    ok, pos, q = parse_int(rest, 0)
+    """A cohort line's part behind the name -> derived file k's: the position as it is, then dk (tests/text_rules.py: what
+    `iss >> pos >> d1 >> ... >> dk` leaves in dk)."""
+    ok, pos, q = tr.extract(rest, 0)
     if not ok:
-        return rest                                         # no position: skipped in either file
-    v, good, p = 0, True, q
-    for _ in range(k):
-        if good:
-            good, v, p = parse_int(rest, p)
-    return f"{rest[:q]}\t{v if good else 0}"
+        return rest                                         # no position (or an overflowing one): the same in either file
+    return f"{rest[:q]}\t{tr.columns(rest, k)[1][k - 1]}"
 
 
 def derived_lines(lines, k):

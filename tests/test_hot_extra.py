@@ -309,27 +309,9 @@ def test_host_candidate_path_still_agrees(hot, hotlib, oracle_cls, monkeypatch):
 
 
 def _reference_text_semantics(lines, n):
-    """load_data_from_text's loop (loaddata.cpp:496-517) in Python, for small inputs."""
-    rd = np.zeros(n, dtype=np.int32)
-    for ln in lines:
-        if len(ln) < 1 or ln[0] == "#":
-            continue
-        toks = ln.split()
-        def as_int(t):
-            import re
-            m = re.match(r"[+-]?\d+", t)
-            return int(m.group(0)) if m else None
-        pos = as_int(toks[0]) if toks else None
-        if pos is None:
-            continue                      # failed extraction leaves 0: skipped by pos < 1
-        d = as_int(toks[1]) if len(toks) > 1 else None
-        d = 0 if d is None else d
-        if pos < 1:
-            continue
-        if pos >= n:
-            break
-        rd[pos - 1] = d
-    return rd
+    """load_data_from_text's loop (loaddata.cpp:496-517) on these lines: tests/text_rules.py's restatement."""
+    import text_rules as tr
+    return tr.load_text("\n".join(lines), n)[0]
 
 
 def test_depth_text_parsed_on_device(hot, tmp_path):

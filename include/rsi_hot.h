@@ -293,6 +293,21 @@ int rsi_hot_debug_level_sums(rsi_ctx* ctx, const float* T, const int32_t* status
  * detection pass listed, trimming walks that left the array, inexact-threshold flags, 0. */
 int rsi_hot_debug_scan(rsi_ctx* ctx, const float* T, const int32_t* medint, int64_t nb, double RDmedian, double tmedian, double tlamda,
                        int Lmax, int32_t* status, int32_t* info);
+/* Test hook: the 0.01-grid median and MAD (partition_stat_tp, wufunctions.cpp:364-424) of the HOST array x[nb], restricted to
+ * mask[i] == 0 when mask != NULL, through the forms the scan's thresholds take:
+ *   mode 0: the device chain of a (median, MAD) pair, the MAD centred on the chain's own median;
+ *   mode 1: the device chain of the MAD alone, around `center`;
+ *   mode 2: the host-driven form (a min/max launch, a histogram launch, the walk on the host) for the median, then the MAD.
+ * Where the chain reports a range too wide for its buckets, or a degenerate median, the pipeline's own fall-backs follow.
+ * out[4] = median, its count, MAD, its count (modes 1 and 3: out[0] = center, out[1] = 0).  info[8] = the raw flags and bucket
+ * count of the chain's median record, the same of its MAD record (-1 and 0 for a record no chain wrote), 1 / 0 for 16-bit /
+ * 32-bit counters in the chain's histogram launch (-1: no chain ran), the number of host-driven medians, 0, 0.
+ * A non-finite selected value fails with RSI_ERR_UNSUPPORTED.  Overwrites the bin arrays the rsi_hot_fetch_* calls read. */
+int rsi_hot_debug_grid_median(rsi_ctx* ctx, const float* x, const int32_t* mask, int64_t nb, int mode, double center, double* out,
+                              int32_t* info);
+/* Mode 3 of the same hook, -MED's form: the int32 bin medians x[nb] become floats in the kernel that also plans the MAD's grid
+ * around `center`, then the MAD's chain. */
+int rsi_hot_debug_grid_mad_i32(rsi_ctx* ctx, const int32_t* x, int64_t nb, double center, double* out, int32_t* info);
 
 /* Timing hooks for bench.py: per-kernel HIP-event times (ms) of the last run, by kernel name.
  * names/ms receive up to cap entries; returns the number of timed launches. */

@@ -28,7 +28,7 @@ EXPORTS = ["rsi_default_params", "rsi_hot_create", "rsi_hot_destroy", "rsi_hot_l
            "rsi_hot_run_device", "rsi_hot_load_depth_text", "rsi_hot_run_text", "rsi_hot_load_depth_bam", "rsi_hot_run_bam", "rsi_bam_references", "rsi_result_annotate_bam", "rsi_result_summary", "rsi_summary_format_row", "rsi_summary_format_rows", "rsi_result_pairs", "rsi_result_ncalls", "rsi_result_calls", "rsi_result_stats", "rsi_result_noncode",
            "rsi_result_format_row", "rsi_result_free", "rsi_hot_fetch_i32", "rsi_hot_fetch_f32", "rsi_hot_fetch_i64",
            "rsi_hot_kernel_times", "rsi_hot_phase_times", "rsi_hot_set_timing", "rsi_pool_create", "rsi_pool_destroy", "rsi_pool_workers", "rsi_pool_worker",
-           "rsi_pool_set_timing", "rsi_pool_set_timing_kernel", "rsi_hot_set_timing_kernel", "rsi_pool_set_schedule", "rsi_pool_last_error", "rsi_pool_run", "rsi_pool_run_host", "rsi_pool_submit", "rsi_pool_wait", "rsi_plot_expand", "rsi_plot_write_files", "rsi_result_log_line", "rsi_hot_debug_level_sums", "rsi_hot_debug_scan", "rsi_synth_generate_host", "rsi_synth_generate_device", "rsi_synth_write_depth_text", "rsi_synth_write_fasta", "rsi_synth_append_genome_text",
+           "rsi_pool_set_timing", "rsi_pool_set_timing_kernel", "rsi_hot_set_timing_kernel", "rsi_pool_set_schedule", "rsi_pool_last_error", "rsi_pool_run", "rsi_pool_run_host", "rsi_pool_submit", "rsi_pool_wait", "rsi_plot_expand", "rsi_plot_write_files", "rsi_result_log_line", "rsi_hot_debug_level_sums", "rsi_hot_debug_scan", "rsi_hot_debug_grid_median", "rsi_hot_debug_grid_mad_i32", "rsi_synth_generate_host", "rsi_synth_generate_device", "rsi_synth_write_depth_text", "rsi_synth_write_fasta", "rsi_synth_append_genome_text",
            "rsi_genome_text_open", "rsi_genome_text_next", "rsi_genome_text_release", "rsi_genome_text_copy_depth",
            "rsi_genome_text_kernel_ms", "rsi_genome_text_close", "rsi_genome_text_last_error", "rsi_hot_run_depth_device",
            "rsi_hot_last_inflate_stats", "rsi_hot_inflate_bgzf", "rsi_genome_text_inflate_stats",
@@ -357,6 +357,29 @@ class RsiHot:
         self._check(self.lib.rsi_hot_debug_scan(self.ctx, t.ctypes.data, mi.ctypes.data, t.size, float(RDmedian), float(tmedian), float(tlamda),
                                                 int(Lmax), st.ctypes.data, info.ctypes.data))
         return st, info
+
+    GRID_MODES = {"pair": 0, "mad": 1, "host": 2}
+
+    def debug_grid_median(self, x, mask=None, mode="pair", center=0.0):
+        """0.01-grid median and MAD of a host array on the device (test hook, include/rsi_hot.h): (out, info).
+        x: float32 values, or int32 bin medians for mode "med" (-MED's MAD around `center`); mask: int32, 0 = selected.
+        out = (median, count, MAD, count); info = flags and buckets of the median record, the same of the MAD record,
+        16-bit counters (1 / 0, -1: no chain), host-driven medians, 0, 0."""
+        out = np.zeros(4, dtype=np.float64)
+        info = np.zeros(8, dtype=np.int32)
+        if mode == "med":
+            assert mask is None
+            xi = np.ascontiguousarray(x, dtype=np.int32)
+            self.lib.rsi_hot_debug_grid_mad_i32.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p]
+            self._check(self.lib.rsi_hot_debug_grid_mad_i32(self.ctx, xi.ctypes.data, xi.size, float(center), out.ctypes.data, info.ctypes.data))
+            return out, info
+        xf = np.ascontiguousarray(x, dtype=np.float32)
+        mk = None if mask is None else np.ascontiguousarray(mask, dtype=np.int32)
+        assert mk is None or mk.size == xf.size
+        self.lib.rsi_hot_debug_grid_median.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_void_p, C.c_void_p]
+        self._check(self.lib.rsi_hot_debug_grid_median(self.ctx, xf.ctypes.data, None if mk is None else mk.ctypes.data, xf.size,
+                                                       self.GRID_MODES[mode], float(center), out.ctypes.data, info.ctypes.data))
+        return out, info
 
     def run(self, params, depth, fasta):
         """depth: int32[n] raw per-base depth, fasta: uint8[n] sequence bytes (host arrays)."""

@@ -283,6 +283,8 @@ void launch_minmax_plan(const float* x, const int32_t* mask, int64_t nb, int use
 // second link: histogram on the planned grid, median into *out; then the export, and `fill` for the kernels behind it
 void launch_hist_walk(const float* x, const int32_t* mask, int64_t nb, int use_abs, double center, const double* d_center,
                       const GridChain& c, GridMedian* out, const GridExport* ex, const FillList* fill, hipStream_t stream);
+// whether launch_hist_walk counts nb values with 16-bit LDS counters (else 32-bit)
+bool hist_walk_pack16(int64_t nb);
 
 // ---- K7: RSI scan (rsistatus, rsi.cpp:1191-1259; runmeantp wufunctions.cpp:573-647) ----
 struct ScanParams {

@@ -1286,13 +1286,22 @@ void launch_minmax_plan(const float* x, const int32_t* mask, int64_t nb, int use
   RSI_LAUNCH(k_minmax_plan, dim3(bounded_grid(nb, kThreads * 16, 256)), dim3(kThreads), 0, stream, x, mask, nb, use_abs, center, d_center, c.mm,
                      c.counters, c.cap, c.hist, out);
 }
+static int hist_walk_grid(int64_t nb) { const int g = grid_for(nb, kThreads * kHistRun * 2); return g > 256 ? 256 : g; }
+// 16-bit LDS counters while a workgroup's share of the bins cannot make one wrap.  The share is not nb / grid: the grid-stride
+// loop hands every workgroup kThreads runs of kHistRun values out of each grid * kThreads runs, and the first workgroup takes
+// the head of the last, partial stride as well (the former bound, nb / grid + kHistRun < 65536, let it count 65536 values
+// from nb = 16 254 976 on: a bucket that held them all wrapped to 0).
+bool hist_walk_pack16(int64_t nb) {
+  const int64_t run = (int64_t)kThreads * kHistRun, stride = (int64_t)hist_walk_grid(nb) * run;
+  const int64_t tail = nb % stride;
+  const int64_t most = nb / stride * run + (tail < run ? tail : run);   // values the first workgroup counts
+  return most < 65536;
+}
 void launch_hist_walk(const float* x, const int32_t* mask, int64_t nb, int use_abs, double center, const double* d_center,
                       const GridChain& c, GridMedian* out, const GridExport* ex, const FillList* fill, hipStream_t stream) {
   const uint32_t bins = kLdsBins;
-  int grid = grid_for(nb, kThreads * kHistRun * 2);
-  if (grid > 256) grid = 256;
-  // 16-bit LDS counters while a workgroup's share of the bins cannot make one wrap
-  const bool pack16 = (nb + grid - 1) / grid + kHistRun < 65536;
+  const int grid = hist_walk_grid(nb);
+  const bool pack16 = hist_walk_pack16(nb);
   const size_t lds = pack16 ? (size_t)bins * 2 : (size_t)bins * 4;
   ExportPair e{};
   if (ex) for (int k = 0; k < 2; ++k) { e.src[k] = ex->src[k]; e.dst[k] = ex->dst[k]; e.bytes[k] = (unsigned int)ex->bytes[k]; }

@@ -1561,6 +1561,43 @@ int run_device_impl(rsi_ctx* ctx, const rsi_params* Pp, const int32_t* d_depth, 
   return RSI_OK;
 }
 
+// Test hooks: the 0.01-grid median and MAD of host arrays through grid_pair_issue / grid_result / grid_median (include/rsi_hot.h).
+// The chains' shared state -- the min/max record, the arrival counters, the bucket array -- is sized as a run sizes it and
+// cleared only when the call allocates it: otherwise it is what the previous call or run left, so that a chain which does not
+// restore it shows in the call after it.
+int grid_debug_enter(rsi_ctx* ctx, int64_t nb, double* out, int32_t* info) {
+  if (!ctx || !out || !info || nb <= 0 || nb >= (1ll << 31) - 4096) return fail(ctx, RSI_ERR_BAD_ARG, "bad argument");
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!ctx_enter(ctx)) return RSI_ERR_HIP;
+  mailbox_reset(ctx);
+  const bool fresh = ctx->small.p == nullptr;
+  HIPCHK(ctx->small.ensure(kSmallBytes));
+  if (fresh) HIPCHK(hipMemsetAsync(ctx->small.p, 0, kHeaderBytes, ctx->stream));
+  HIPCHK(ctx->hist_f.ensure((size_t)kGridCap * 4));
+  for (int k = 0; k < 4; ++k) out[k] = 0.0;
+  for (int k = 0; k < 8; ++k) info[k] = 0;
+  info[0] = info[2] = info[4] = -1;
+  return RSI_OK;
+}
+void grid_debug_record(const GridMedian& g, int32_t* info) { info[0] = (int32_t)g.flags; info[1] = (int32_t)g.np; }
+// the MAD of a chain issued without its median (modes 1 and 3), the way run_scan takes the -MED MAD
+int grid_debug_mad(rsi_ctx* ctx, const float* d_x, const int32_t* d_mask, int64_t nb, double center, bool planned, double* out,
+                   int32_t* info) {
+  ChainOut* co = nullptr;
+  int rc;
+  if ((rc = grid_pair_issue(ctx, d_x, d_mask, nb, false, center, planned, -1, &co)) != RSI_OK) return rc;
+  HIPCHK(CTX_SYNC());
+  const GridMedian g = co->g[1];
+  grid_debug_record(g, info + 2);
+  info[4] = hist_walk_pack16(nb) ? 1 : 0;
+  double mad = 0;
+  uint64_t cnt = 0;
+  if (g.flags & kGridTooWide) { ++info[5]; rc = grid_median(ctx, d_x, d_mask, nb, 1, center, &mad, &cnt); }
+  else rc = grid_result(ctx, g, Selection{d_x, d_mask, nb, 1, center}, &mad, &cnt);
+  if (rc != RSI_OK) return rc;
+  out[0] = center; out[1] = 0; out[2] = mad; out[3] = (double)cnt;
+  return RSI_OK;
+}
 }  // namespace
 
 // ------------------------------------------------------------------------------------------
@@ -1836,6 +1873,64 @@ int rsi_hot_debug_scan(rsi_ctx* ctx, const float* T, const int32_t* medint, int6
   HIPCHK(CTX_SYNC());
   if (info) { info[0] = (int32_t)wslot[8]; info[1] = (int32_t)wslot[0]; info[2] = (int32_t)wslot[1]; info[3] = 0; }
   return RSI_OK;
+}
+
+int rsi_hot_debug_grid_median(rsi_ctx* ctx, const float* x, const int32_t* mask, int64_t nb, int mode, double center, double* out,
+                              int32_t* info) {
+  int rc;
+  if (!x || mode < 0 || mode > 2) return fail(ctx, RSI_ERR_BAD_ARG, "bad argument");
+  if ((rc = grid_debug_enter(ctx, nb, out, info)) != RSI_OK) return rc;
+  HIPCHK(ctx->tnb.ensure((size_t)nb * 4));
+  HIPCHK(hipMemcpyAsync(ctx->tnb.p, x, (size_t)nb * 4, hipMemcpyHostToDevice, ctx->stream));
+  ctx->have_nb = false;   // tnb holds the caller's array now
+  const int32_t* d_mask = nullptr;
+  if (mask) {
+    HIPCHK(ctx->status1f.ensure((size_t)nb * 4));
+    HIPCHK(hipMemcpyAsync(ctx->status1f.p, mask, (size_t)nb * 4, hipMemcpyHostToDevice, ctx->stream));
+    d_mask = ctx->status1f.as<int32_t>();
+  }
+  const float* d_x = ctx->tnb.as<float>();
+  if (mode == 1) return grid_debug_mad(ctx, d_x, d_mask, nb, center, false, out, info);
+  double med = 0, mad = 0;
+  uint64_t c0 = 0, c1 = 0;
+  if (mode == 2) {
+    info[5] = 2;
+    if ((rc = grid_median(ctx, d_x, d_mask, nb, 0, 0.0, &med, &c0)) != RSI_OK) return rc;
+    if ((rc = grid_median(ctx, d_x, d_mask, nb, 1, med, &mad, &c1)) != RSI_OK) return rc;
+  } else {   // the pair as run_scan takes it: the host-driven form when either record is too wide, the MAD again around a mean
+    ChainOut* co = nullptr;
+    if ((rc = grid_pair_issue(ctx, d_x, d_mask, nb, true, 0.0, false, -1, &co)) != RSI_OK) return rc;
+    HIPCHK(CTX_SYNC());
+    const GridMedian g0 = co->g[0], g1 = co->g[1];
+    grid_debug_record(g0, info);
+    grid_debug_record(g1, info + 2);
+    info[4] = hist_walk_pack16(nb) ? 1 : 0;
+    if ((g0.flags | g1.flags) & kGridTooWide) {
+      info[5] = 2;
+      if ((rc = grid_median(ctx, d_x, d_mask, nb, 0, 0.0, &med, &c0)) != RSI_OK) return rc;
+      if ((rc = grid_median(ctx, d_x, d_mask, nb, 1, med, &mad, &c1)) != RSI_OK) return rc;
+    } else {
+      if ((rc = grid_result(ctx, g0, Selection{d_x, d_mask, nb, 0, 0.0}, &med, &c0)) != RSI_OK) return rc;
+      if (g0.flags & kGridDegenerate) { info[5] = 1; rc = grid_median(ctx, d_x, d_mask, nb, 1, med, &mad, &c1); }
+      else rc = grid_result(ctx, g1, Selection{d_x, d_mask, nb, 1, med}, &mad, &c1);
+      if (rc != RSI_OK) return rc;
+    }
+  }
+  out[0] = med; out[1] = (double)c0; out[2] = mad; out[3] = (double)c1;
+  return RSI_OK;
+}
+
+int rsi_hot_debug_grid_mad_i32(rsi_ctx* ctx, const int32_t* x, int64_t nb, double center, double* out, int32_t* info) {
+  int rc;
+  if (!x) return fail(ctx, RSI_ERR_BAD_ARG, "bad argument");
+  if ((rc = grid_debug_enter(ctx, nb, out, info)) != RSI_OK) return rc;
+  HIPCHK(ctx->binmed.ensure((size_t)nb * 4));
+  HIPCHK(ctx->tmed.ensure((size_t)nb * 4));
+  HIPCHK(hipMemcpyAsync(ctx->binmed.p, x, (size_t)nb * 4, hipMemcpyHostToDevice, ctx->stream));
+  ctx->have_med = false;   // tmed holds the caller's values now
+  GridMedian* d_g = reinterpret_cast<GridMedian*>(ctx->small.as<uint8_t>() + kOffGrid);
+  { Timer t(ctx, "i32_to_f32"); launch_i32_to_f32_minmax(ctx->binmed.as<int32_t>(), ctx->tmed.as<float>(), nb, center, grid_chain(ctx), d_g + 1, ctx->stream); }
+  return grid_debug_mad(ctx, ctx->tmed.as<float>(), nullptr, nb, center, true, out, info);
 }
 
 int rsi_hot_phase_times(const rsi_ctx* ctx, const char** names, double* ms, int cap) {

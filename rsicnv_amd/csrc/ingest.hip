@@ -93,44 +93,62 @@ constexpr size_t kTextChunk = size_t(64) << 20;   // bytes of text per transfer 
 constexpr size_t kBgzfMinChunk = size_t(128) << 10; // BGZF input: a chunk holds whole members, at least this much text
 constexpr size_t kMemberMax = 65536;               // BGZF: BSIZE and ISIZE
 
-// Text bytes [skip, skip + len) of the gzip stream that starts at file offset foff (any member start of a gzip or BGZF
-// file), inflated on the host: the sequential fallback parser's input for compressed files.
-int host_text_range(const std::string& path, int64_t foff, int64_t skip, int64_t len, std::vector<char>& out, std::string& err) {
-  const int fd = open(path.c_str(), O_RDONLY);
-  if (fd < 0 || lseek(fd, (off_t)foff, SEEK_SET) != (off_t)foff) { if (fd >= 0) close(fd); err = "Cannot open file " + path; return RSI_ERR_BAD_ARG; }
-  gzFile g = gzdopen(fd, "rb");
-  if (!g) { close(fd); err = "zlib: cannot read " + path; return RSI_ERR_INTERNAL; }
-  gzbuffer(g, 1 << 20);
-  out.assign((size_t)len, 0);
-  int rc = RSI_OK;
-  if (skip > 0 && gzseek(g, (z_off_t)skip, SEEK_SET) != (z_off_t)skip) rc = RSI_ERR_BAD_ARG;
-  size_t have = 0;
-  while (rc == RSI_OK && have < out.size()) {
-    const int got = gzread(g, out.data() + have, (unsigned)std::min<size_t>(out.size() - have, size_t(1) << 30));
-    if (got <= 0) { rc = RSI_ERR_BAD_ARG; break; }
-    have += (size_t)got;
-  }
-  if (rc != RSI_OK) { int e = 0; const char* m = gzerror(g, &e); err = std::string("gzip: ") + (e ? m : "unexpected end of the text") + " in " + path; }
-  gzclose(g);
-  return rc;
+// The BGZF member at compressed offset `at`, with `avail` bytes of the input at p: "" and m filled when it is a whole,
+// well-formed member, else the error to report
+std::string bgzf_member_error(const uint8_t* p, size_t avail, int64_t at, rsinf::Member& m) {
+  const int r = rsinf::bgzf_member(p, avail, m);
+  const std::string where = " at compressed offset " + std::to_string((long long)at);
+  if (r == 0) return "BGZF: not a BGZF member" + where;
+  if (r < 0 || m.bsize > avail) return "BGZF: the member" + where + " runs past the end of the input";
+  if (m.isize > kMemberMax) return "BGZF: ISIZE above 65536 in the member" + where;
+  return std::string();
 }
 
-// Where the text readers get their bytes from.  Text and gzip: read_text() in the place of read() (zlib on
-// the host for gzip).  BGZF: launch() walks the member headers on the host, uploads the compressed payloads and the member
-// table, and inflates them on the device straight into the reader's text buffer, behind the bytes carried over from the
-// chunk before; the text exists only in HBM.  check() reads the launch's status word (read back with the caller's next
-// wait): the first bad member, the last line end.
+// The context's two chunk buffers, pinned and in HBM: the staging of the text and BAM loaders, kept from load to load
+int ctx_staging(rsi_ctx* ctx) {
+  if (ctx->text_pin_cap < kTextChunk) {
+    for (int b = 0; b < 2; ++b) {
+      if (ctx->text_pin[b]) (void)hipHostFree(ctx->text_pin[b]);
+      ctx->text_pin[b] = nullptr;
+      if (hipHostMalloc(reinterpret_cast<void**>(&ctx->text_pin[b]), kTextChunk, hipHostMallocDefault) != hipSuccess)
+        return fail(ctx, RSI_ERR_INTERNAL, "out of pinned host memory for the staging buffers");
+    }
+    ctx->text_pin_cap = kTextChunk;
+  }
+  HIPCHK(ctx->text_dev[0].ensure(kTextChunk));
+  HIPCHK(ctx->text_dev[1].ensure(kTextChunk));
+  return RSI_OK;
+}
+
+// The chunk source of both text readers.  It owns the file and turns its text -- plain, gzip or BGZF -- into
+// line-aligned chunks in two buffers that the reader lends (pin[b] on the host, dev[b] in HBM) and fills in turn.  fill(b)
+// puts the tail of the chunk before (its bytes behind the cut) in front of the new text.  Text and gzip: read() or zlib's
+// gzread() into pin[b], cut at the last line end at once.  BGZF: the host walks the member headers, uploads the compressed
+// payloads and a member table, and one launch inflates them into dev[b] behind the tail (moved there device to device), so
+// the text exists only in HBM; cut(b) takes the last line end from the launch's status word once the caller has waited
+// behind it.  A reader may keep less of a chunk (give_back).  foff[b] is chunk b's text offset; host_range() gives the
+// sequential fallback any text range once more.
 struct DepthSource {
-  int fd = -1;                     // the reader's
+  int fd = -1;
   std::string path, err;
+  int64_t file_size = 0;
   int format = 0;                  // 0 text, 1 BGZF, 2 gzip
   gzFile gz = nullptr;
   rsi_inflate_stats st{};
+  char* pin[2] = {nullptr, nullptr};   // the reader's buffers (borrow)
+  void* dev[2] = {nullptr, nullptr};
+  size_t cap = 0;                  // text bytes per chunk
+  size_t carry_max = 0;            // a cut leaves fewer bytes than this behind it
+  size_t total[2] = {0, 0};        // bytes in buffer b; the chunk is [0, len[b]) of them, the rest its tail
+  size_t len[2] = {0, 0};
+  int64_t foff[2] = {0, 0};        // text offset of buffer b's first byte
+  int last_nl[2] = {-1, -1};       // BGZF: the last line end in buffer b (-1: none, or not read back yet)
+  bool exhausted = false;          // no text left in the file
   // BGZF
   std::vector<uint8_t> cbuf;       // compressed bytes read from the file; cbuf[cpos..] not taken yet
   size_t cpos = 0;
   int64_t cbuf_off = 0;            // file offset of cbuf[0]
-  bool file_eof = false, exhausted = false;
+  bool file_eof = false;
   std::vector<std::pair<int64_t, int64_t>> index;   // (text offset, file offset) of every member: the fallback's entry points
   PinBuf cpin[2], tpin[2], wpin;
   DevBuf cdev[2], tdev[2], wdev;
@@ -140,13 +158,20 @@ struct DepthSource {
 
   ~DepthSource() {
     if (gz) gzclose(gz);
+    if (fd >= 0) close(fd);
     for (int b = 0; b < 2; ++b) for (int k = 0; k < 2; ++k) if (ev[b][k]) (void)hipEventDestroy(ev[b][k]);
   }
   int fail_(int code, const std::string& m) { err = m; return code; }
   int bad_data(const std::string& m) { st.input_error = 1; return fail_(RSI_ERR_BAD_ARG, m); }   // the compressed data is broken
+  int too_long(size_t n) { return fail_(RSI_ERR_UNSUPPORTED, "a line of the depth file is longer than " + std::to_string(n) + " bytes"); }
 
-  int open_(int fd_, const std::string& p, int64_t file_size) {
-    fd = fd_; path = p;
+  int open_(const std::string& p) {
+    path = p;
+    fd = open(path.c_str(), O_RDONLY);
+    if (fd < 0) return fail_(RSI_ERR_BAD_ARG, "Cannot open file " + path);
+    struct stat sb;
+    if (fstat(fd, &sb) != 0) return fail_(RSI_ERR_BAD_ARG, "Cannot stat file " + path);
+    file_size = (int64_t)sb.st_size;
     uint8_t head[512];
     const ssize_t n = pread(fd, head, sizeof(head), 0);
     format = rsinf::detect_format(head, n > 0 ? (size_t)n : 0);
@@ -160,6 +185,69 @@ struct DepthSource {
       gzbuffer(gz, 1 << 20);
     }
     return RSI_OK;
+  }
+
+  void borrow(char* pin0, char* pin1, void* dev0, void* dev1, size_t chunk) {
+    pin[0] = pin0; pin[1] = pin1; dev[0] = dev0; dev[1] = dev1;
+    cap = carry_max = chunk;
+  }
+
+  // The next chunk into buffer b, the other one holding the chunk before: that chunk's tail, then new text.  len[b] == 0:
+  // the end of the file.  BGZF queues its copies and the inflate on s; len[b] is the whole buffer until cut(b).
+  int fill(int b, hipStream_t s) {
+    const int p = b ^ 1;
+    const size_t tail = total[p] - len[p];
+    foff[b] = foff[p] + (int64_t)len[p];
+    last_nl[b] = -1;
+    if (format == 1) {
+      if (tail) {
+        const hipError_t e = hipMemcpyAsync(dev[b], static_cast<char*>(dev[p]) + len[p], tail, hipMemcpyDeviceToDevice, s);
+        if (e != hipSuccess) return fail_(RSI_ERR_HIP, std::string("BGZF: ") + hipGetErrorString(e));
+      }
+      size_t added = 0;
+      const int rc = launch(b, tail, last_nl[p] >= (int)len[p] ? last_nl[p] - (int)len[p] : -1, s, added);
+      total[b] = len[b] = tail + added;
+      return rc;
+    }
+    if (tail) memcpy(pin[b], pin[p] + len[p], tail);
+    size_t have = tail;
+    while (have < cap && !exhausted) {
+      const ssize_t got = read_text(pin[b] + have, cap - have);
+      if (got < 0) return format == 2 ? RSI_ERR_BAD_ARG : RSI_ERR_INTERNAL;
+      exhausted = got == 0;
+      have += (size_t)got;
+    }
+    total[b] = len[b] = have;
+    if (exhausted) return RSI_OK;
+    len[b] = line_cut(b, have);
+    return len[b] ? RSI_OK : too_long(cap);
+  }
+
+  // After the caller's wait behind fill(b): BGZF's chunk is cut behind the last line end the inflate reported.  Text and
+  // gzip were cut in fill().
+  int cut(int b) {
+    if (format != 1) return RSI_OK;
+    if (int rc = check(b, &last_nl[b])) return rc;
+    if (exhausted) return RSI_OK;
+    if (last_nl[b] < 0) return too_long(cap);
+    return give_back(b, (size_t)last_nl[b] + 1);
+  }
+
+  // the reader keeps [0, k) of chunk b; the rest goes in front of the next chunk
+  int give_back(int b, size_t k) {
+    len[b] = k;
+    return total[b] - k >= carry_max ? too_long(carry_max) : RSI_OK;
+  }
+
+  // text and gzip: the end of the last whole line in the first n bytes of pin[b] (0: none)
+  size_t line_cut(int b, size_t n) const {
+    while (n > 0 && pin[b][n - 1] != '\n') --n;
+    return n;
+  }
+
+  // chunk b's text to dev[b] on s (BGZF: there already)
+  hipError_t upload(int b, hipStream_t s) {
+    return format == 1 ? hipSuccess : hipMemcpyAsync(dev[b], pin[b], len[b], hipMemcpyHostToDevice, s);
   }
 
   // text / gzip: like read(); < 0 on an error (err)
@@ -197,43 +285,34 @@ struct DepthSource {
     return cbuf.size() - cpos >= need;
   }
 
-  // BGZF: the next members into d_text[carry, ...) -- at most max_text bytes of text in the buffer in all, one member at least.
-  // carry_nl: offset of the last line end in the carried bytes (-1: none).  text_off: text offset of d_text[carry].  Queues
-  // the uploads, the inflate launch and its status read-back on s.  *added: text bytes added (0 with exhausted: the end).
-  int launch(int b, void* d_text, size_t carry, int carry_nl, size_t max_text, int64_t text_off, hipStream_t s, size_t& added) {
+  // BGZF: the next members into dev[b] behind its `tail` bytes -- at most cap bytes of text in the buffer in all, one member
+  // at least.  tail_nl: offset of the last line end in the tail (-1: none).  Queues the uploads, the inflate launch and its
+  // status read-back on s.  added: text bytes added (0 with exhausted: the end).
+  int launch(int b, size_t tail, int tail_nl, hipStream_t s, size_t& added) {
     added = 0;
     launched[b] = false;
     foffs[b].clear();
     std::vector<InflateBlock> tab;
-    const size_t ccap = max_text + 4 * kMemberMax;
+    const size_t ccap = cap + 4 * kMemberMax;
     if (cpin[b].ensure(ccap) != hipSuccess || cdev[b].ensure(ccap) != hipSuccess || wpin.ensure(32) != hipSuccess || wdev.ensure(32) != hipSuccess)
       return fail_(RSI_ERR_HIP, "BGZF: out of pinned or device memory for the compressed staging");
     uint8_t* cp = cpin[b].as<uint8_t>();
     size_t comp = 0;
     while (!exhausted) {
-      if (!have_bytes(18)) {
-        if (!err.empty()) return RSI_ERR_INTERNAL;
-        if (cbuf.size() == cpos) { exhausted = true; break; }
-        return bad_data("BGZF: a member runs past the end of the file at compressed offset " + std::to_string(cbuf_off + (int64_t)cpos));
-      }
-      const int64_t at = cbuf_off + (int64_t)cpos;
+      // the member's fixed header, its extra field (BSIZE), then all of it, as far as the file has them
+      have_bytes(18);
+      if (cbuf.size() - cpos >= 12) have_bytes(12 + ((size_t)cbuf[cpos + 10] | ((size_t)cbuf[cpos + 11] << 8)));
       rsinf::Member m;
-      int r = rsinf::bgzf_member(cbuf.data() + cpos, cbuf.size() - cpos, m);
-      if (r < 0) {   // a long extra field
-        const size_t xlen = (size_t)cbuf[cpos + 10] | ((size_t)cbuf[cpos + 11] << 8);
-        if (have_bytes(12 + xlen)) r = rsinf::bgzf_member(cbuf.data() + cpos, cbuf.size() - cpos, m);
-      }
-      if (r <= 0) return bad_data("BGZF: not a BGZF member at compressed offset " + std::to_string(at) + " (the file changes format part-way)");
-      if (!have_bytes(m.bsize)) {
-        if (!err.empty()) return RSI_ERR_INTERNAL;
-        return bad_data("BGZF: the member at compressed offset " + std::to_string(at) + " runs past the end of the file");
-      }
-      rsinf::bgzf_member(cbuf.data() + cpos, cbuf.size() - cpos, m);   // the footer is in now
-      if (m.isize > kMemberMax) return bad_data("BGZF: ISIZE above 65536 in the member at compressed offset " + std::to_string(at));
-      if (!tab.empty() && (carry + added + m.isize > max_text || comp + m.clen > ccap)) break;
+      if (rsinf::bgzf_member(cbuf.data() + cpos, cbuf.size() - cpos, m) > 0) have_bytes(m.bsize);
+      if (!err.empty()) return RSI_ERR_INTERNAL;
+      if (cbuf.size() == cpos) { exhausted = true; break; }
+      const int64_t at = cbuf_off + (int64_t)cpos;
+      const std::string bad = bgzf_member_error(cbuf.data() + cpos, cbuf.size() - cpos, at, m);
+      if (!bad.empty()) return bad_data(bad);
+      if (!tab.empty() && (tail + added + m.isize > cap || comp + m.clen > ccap)) break;
       memcpy(cp + comp, cbuf.data() + cpos + m.hdr, m.clen);
-      tab.push_back(InflateBlock{(long long)comp, (long long)(carry + added), m.clen, m.isize, m.crc, 0});
-      index.emplace_back(text_off + (int64_t)added, at);
+      tab.push_back(InflateBlock{(long long)comp, (long long)(tail + added), m.clen, m.isize, m.crc, 0});
+      index.emplace_back(foff[b] + (int64_t)(tail + added), at);
       foffs[b].push_back(at);
       comp += m.clen; added += m.isize; cpos += m.bsize;
       st.compressed_bytes += m.bsize; st.text_bytes += m.isize; ++st.blocks;
@@ -247,11 +326,11 @@ struct DepthSource {
     hipError_t e = hipMemcpyAsync(cdev[b].p, cp, comp, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(tdev[b].p, tpin[b].p, tb, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemsetAsync(w, 0xff, 8, s);
-    if (e == hipSuccess) e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(w + 8), carry_nl, 1, s);
+    if (e == hipSuccess) e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(w + 8), tail_nl, 1, s);
     if (e != hipSuccess) return fail_(RSI_ERR_HIP, std::string("BGZF: ") + hipGetErrorString(e));
     for (int k = 0; k < 2; ++k) if (!ev[b][k]) (void)hipEventCreate(&ev[b][k]);
     if (ev[b][0]) (void)hipEventRecord(ev[b][0], s);
-    launch_inflate_bgzf(cdev[b].p, tdev[b].as<InflateBlock>(), (int)tab.size(), d_text, reinterpret_cast<int*>(w + 8),
+    launch_inflate_bgzf(cdev[b].p, tdev[b].as<InflateBlock>(), (int)tab.size(), dev[b], reinterpret_cast<int*>(w + 8),
                         reinterpret_cast<unsigned long long*>(w), s);
     if (ev[b][1]) (void)hipEventRecord(ev[b][1], s);
     e = hipMemcpyAsync(wpin.as<char>() + 16 * b, w, 16, hipMemcpyDeviceToHost, s);
@@ -279,19 +358,42 @@ struct DepthSource {
     return RSI_OK;
   }
 
-  // the fallback parser's text: [start, end) of the whole text, inflated on the host from the nearest member (BGZF) or
-  // from the start (gzip)
+  // The fallback parser's text: [start, end) of the whole text once more, on the host.  Text: pread().  BGZF and gzip:
+  // inflated from the member that holds `start` (BGZF) or from the start of the file (gzip), through a descriptor of its
+  // own (fd's offset belongs to the chunks).  A short read is an error.
   int host_range(int64_t start, int64_t end, std::vector<char>& out) {
-    int64_t foff = 0, toff = 0;
+    out.assign((size_t)(end - start), 0);
+    if (format == 0) {
+      for (size_t have = 0; have < out.size();) {
+        const ssize_t got = pread(fd, out.data() + have, out.size() - have, (off_t)(start + (int64_t)have));
+        if (got <= 0) return fail_(RSI_ERR_INTERNAL, "read error on " + path);
+        have += (size_t)got;
+      }
+      return RSI_OK;
+    }
+    int64_t coff = 0, skip = start;
     if (format == 1) {
       auto it = std::upper_bound(index.begin(), index.end(), std::make_pair(start, INT64_MAX));
-      if (it != index.begin()) { --it; toff = it->first; foff = it->second; }
+      if (it != index.begin()) { --it; skip = start - it->first; coff = it->second; }
     }
     const double t = now_ms();
-    const int rc = host_text_range(path, foff, start - toff, end - start, out, err);
+    const int hfd = open(path.c_str(), O_RDONLY);
+    if (hfd < 0 || lseek(hfd, (off_t)coff, SEEK_SET) != (off_t)coff) { if (hfd >= 0) close(hfd); return bad_data("Cannot open file " + path); }
+    gzFile g = gzdopen(hfd, "rb");
+    if (!g) { close(hfd); return fail_(RSI_ERR_INTERNAL, "zlib: cannot read " + path); }
+    gzbuffer(g, 1 << 20);
+    bool ok = skip == 0 || gzseek(g, (z_off_t)skip, SEEK_SET) == (z_off_t)skip;
+    for (size_t have = 0; ok && have < out.size();) {
+      const int got = gzread(g, out.data() + have, (unsigned)std::min<size_t>(out.size() - have, size_t(1) << 30));
+      ok = got > 0;
+      if (ok) have += (size_t)got;
+    }
+    int e = 0;
+    const char* m = ok ? nullptr : gzerror(g, &e);
+    const std::string msg = ok ? std::string() : std::string("gzip: ") + (e ? m : "unexpected end of the text") + " in " + path;
+    gzclose(g);
     st.t_host_inflate_ms += now_ms() - t;
-    if (rc == RSI_ERR_BAD_ARG) st.input_error = 1;
-    return rc;
+    return ok ? RSI_OK : bad_data(msg);
   }
 };
 
@@ -308,32 +410,19 @@ int rsi_hot_load_depth_text(rsi_ctx* ctx, const char* path, int64_t n, rsi_text_
   if (n <= 0 || n >= (1ll << 31) - 4096) return fail(ctx, RSI_ERR_BAD_ARG, "chromosome length must be in (0, 2^31)");
   const double t0 = now_ms();
   HIPCHK(hipSetDevice(ctx->device));
-  const int fd = open(path, O_RDONLY);
-  if (fd < 0) return fail(ctx, RSI_ERR_BAD_ARG, std::string("Cannot open file ") + path);
-  struct FdGuard { int fd; ~FdGuard() { close(fd); } } guard{fd};
-  struct stat sb;
-  if (fstat(fd, &sb) != 0) return fail(ctx, RSI_ERR_BAD_ARG, std::string("Cannot stat file ") + path);
   DepthSource src;
   struct StatsOut { rsi_ctx* c; const DepthSource& s; ~StatsOut() { c->last_inflate = s.st; } } stats_out{ctx, src};   // every return
-  if (int rc = src.open_(fd, path, (int64_t)sb.st_size)) return fail(ctx, rc, src.err);
-  st->bytes = (int64_t)sb.st_size;
+  if (int rc = src.open_(path)) return fail(ctx, rc, src.err);
+  st->bytes = src.file_size;
   if (!ctx_enter(ctx)) return RSI_ERR_HIP;
   mailbox_reset(ctx);
   HIPCHK(ctx->in_depth.ensure((size_t)(n + 4) * 4));
   HIPCHK(hipMemsetAsync(ctx->in_depth.p, 0, (size_t)n * 4, ctx->stream));
   ctx->n_in = n;
-  if (ctx->text_pin_cap < kTextChunk) {
-    for (int b = 0; b < 2; ++b) {
-      if (ctx->text_pin[b]) (void)hipHostFree(ctx->text_pin[b]);
-      ctx->text_pin[b] = nullptr;
-      if (hipHostMalloc(reinterpret_cast<void**>(&ctx->text_pin[b]), kTextChunk, hipHostMallocDefault) != hipSuccess)
-        return fail(ctx, RSI_ERR_INTERNAL, "out of pinned host memory for the text staging");
-    }
-    ctx->text_pin_cap = kTextChunk;
-  }
+  if (int rc = ctx_staging(ctx)) return rc;
+  src.borrow(ctx->text_pin[0], ctx->text_pin[1], ctx->text_dev[0].p, ctx->text_dev[1].p, kTextChunk);
+  if (src.format == 1) src.carry_max = kTextChunk / 2;   // no room past the chunk in text_dev: the tail and a member fit in it
   const int max_wg = text_parse_workgroups((long long)kTextChunk);
-  HIPCHK(ctx->text_dev[0].ensure(kTextChunk));
-  HIPCHK(ctx->text_dev[1].ensure(kTextChunk));
   HIPCHK(ctx->text_wg.ensure((size_t)max_wg * 16 * 2 + 256));   // (first, max) per workgroup, two chunks in flight, + stats
   uint8_t* wgbase = ctx->text_wg.as<uint8_t>();
   TextParseStats* d_stats = reinterpret_cast<TextParseStats*>(wgbase + (size_t)max_wg * 32);
@@ -341,16 +430,18 @@ int rsi_hot_load_depth_text(rsi_ctx* ctx, const char* path, int64_t n, rsi_text_
   std::vector<long long> wg_host[2];
   wg_host[0].resize((size_t)max_wg * 2); wg_host[1].resize((size_t)max_wg * 2);
 
-  // Double buffering: while the device parses chunk k the host reads chunk k+1 from the file.  A chunk ends on
-  // a line end; the partial last line is carried to the front of the next chunk.
-  size_t carry = 0;            // bytes of an unfinished line already at the front of the buffer being filled
-  bool eof = false, unsorted = false;
+  // Double buffering: while the device parses chunk k the source fills the other buffer with chunk k+1 (text and gzip:
+  // read on the host once chunk k-1 there is through; BGZF: inflated on the device behind chunk k's parse).
+  bool unsorted = false;
   long long run_max = -1;      // largest position seen in the chunks checked so far
   int inflight_wgs[2] = {0, 0};
+  bool used[2] = {false, false};
   hipEvent_t done[2] = {nullptr, nullptr};
   for (int b = 0; b < 2; ++b) if (hipEventCreateWithFlags(&done[b], hipEventDisableTiming) != hipSuccess) return fail(ctx, RSI_ERR_HIP, "hipEventCreate failed");
   struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int b = 0; b < 2; ++b) if (e[b]) (void)hipEventDestroy(e[b]); } } evguard{done};
-  auto check_chunk = [&](int b) {   // cross-workgroup order of a finished chunk
+  auto retire = [&](int b) {   // a parsed chunk: its buffer is free again, and the cross-workgroup order is checked
+    if (!used[b]) return hipSuccess;
+    const hipError_t e = hipEventSynchronize(done[b]);
     const long long* f = wg_host[b].data();
     const long long* m = f + inflight_wgs[b];
     for (int w = 0; w < inflight_wgs[b]; ++w) {
@@ -358,83 +449,30 @@ int rsi_hot_load_depth_text(rsi_ctx* ctx, const char* path, int64_t n, rsi_text_
       if (run_max >= 0 && f[w] <= run_max) unsorted = true;
       run_max = m[w] > run_max ? m[w] : run_max;
     }
-    inflight_wgs[b] = 0;
+    used[b] = false;
+    return e;
   };
-  int cur = 0;
-  bool used[2] = {false, false};
-  if (src.format == 1) {
-    // BGZF: the members are inflated on the device into text_dev[cur], behind the unfinished line of the chunk before
-    // (moved there device to device); the inflate reports the last line end, read back with the one wait per chunk
-    size_t carry_b = 0, cut = 0;
-    int64_t text_off = 0;
-    for (;;) {
-      const int other = cur ^ 1;
-      if (carry_b) HIPCHK(hipMemcpyAsync(ctx->text_dev[cur].p, static_cast<char*>(ctx->text_dev[other].p) + cut, carry_b, hipMemcpyDeviceToDevice, ctx->stream));
-      size_t added = 0;
-      if (int rc = src.launch(cur, ctx->text_dev[cur].p, carry_b, -1, kTextChunk, text_off + (int64_t)carry_b, ctx->stream, added)) return fail(ctx, rc, src.err);
-      const size_t total = carry_b + added;
-      if (total == 0) break;
+  for (int cur = 0;; cur ^= 1) {
+    HIPCHK(retire(cur));
+    if (int rc = src.fill(cur, ctx->stream)) return fail(ctx, rc, src.err);
+    if (src.len[cur] == 0) break;
+    if (src.format == 1) {   // the inflate's report comes back with the one wait per chunk, which also ends the chunk before
       HIPCHK(CTX_SYNC());
-      if (used[other]) { check_chunk(other); used[other] = false; }
-      int last_nl = -1;
-      if (int rc = src.check(cur, &last_nl)) return fail(ctx, rc, src.err);
-      size_t len = total;
-      if (!src.exhausted) {
-        if (last_nl < 0) return fail(ctx, RSI_ERR_UNSUPPORTED, "a line of the depth file is longer than the chunk");
-        len = (size_t)last_nl + 1;
-      }
-      if (total - len >= kTextChunk / 2) return fail(ctx, RSI_ERR_UNSUPPORTED, "a line of the depth file is longer than half the chunk");
-      const int nwg = text_parse_workgroups((long long)len);
-      long long* d_first = reinterpret_cast<long long*>(wgbase + (size_t)cur * max_wg * 16);
-      long long* d_max = d_first + nwg;
-      { Timer t(ctx, "parse_depth_text"); launch_parse_depth_text(ctx->text_dev[cur].p, (long long)len, (long long)n, ctx->in_depth.as<int32_t>(), d_first, d_max, d_stats, ctx->stream); }
-      HIPCHK(hipMemcpyAsync(wg_host[cur].data(), d_first, (size_t)nwg * 16, hipMemcpyDeviceToHost, ctx->stream));
-      HIPCHK(hipEventRecord(done[cur], ctx->stream));
-      inflight_wgs[cur] = nwg;
-      used[cur] = true;
-      text_off += (int64_t)len;
-      cut = len; carry_b = total - len;
-      if (carry_b == 0 && src.exhausted) break;
-      cur = other;
+      HIPCHK(retire(cur ^ 1));
+      if (int rc = src.cut(cur)) return fail(ctx, rc, src.err);
     }
-    eof = true;
-    st->bytes = src.st.text_bytes;
+    const int nwg = text_parse_workgroups((long long)src.len[cur]);
+    long long* d_first = reinterpret_cast<long long*>(wgbase + (size_t)cur * max_wg * 16);
+    long long* d_max = d_first + nwg;
+    HIPCHK(src.upload(cur, ctx->stream));
+    { Timer t(ctx, "parse_depth_text"); launch_parse_depth_text(ctx->text_dev[cur].p, (long long)src.len[cur], (long long)n, ctx->in_depth.as<int32_t>(), d_first, d_max, d_stats, ctx->stream); }
+    HIPCHK(hipMemcpyAsync(wg_host[cur].data(), d_first, (size_t)nwg * 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipEventRecord(done[cur], ctx->stream));
+    inflight_wgs[cur] = nwg;
+    used[cur] = true;
   }
-  while (!eof) {
-    char* buf = ctx->text_pin[cur];   // free: its previous chunk was waited for before `carry` was parked in it
-    size_t have = carry;
-    while (have < kTextChunk) {
-      const ssize_t got = src.read_text(buf + have, kTextChunk - have);
-      if (got < 0) return fail(ctx, src.format == 2 ? RSI_ERR_BAD_ARG : RSI_ERR_INTERNAL, src.err);
-      if (got == 0) { eof = true; break; }
-      have += (size_t)got;
-    }
-    size_t len = have;
-    if (!eof) {   // cut at the last line end
-      while (len > 0 && buf[len - 1] != '\n') --len;
-      if (len == 0) return fail(ctx, RSI_ERR_UNSUPPORTED, "a line of the depth file is longer than 64 MB");
-    }
-    if (len > 0) {
-      const int nwg = text_parse_workgroups((long long)len);
-      long long* d_first = reinterpret_cast<long long*>(wgbase + (size_t)cur * max_wg * 16);
-      long long* d_max = d_first + nwg;
-      HIPCHK(hipMemcpyAsync(ctx->text_dev[cur].p, buf, len, hipMemcpyHostToDevice, ctx->stream));
-      { Timer t(ctx, "parse_depth_text"); launch_parse_depth_text(ctx->text_dev[cur].p, (long long)len, (long long)n, ctx->in_depth.as<int32_t>(), d_first, d_max, d_stats, ctx->stream); }
-      HIPCHK(hipMemcpyAsync(wg_host[cur].data(), d_first, (size_t)nwg * 16, hipMemcpyDeviceToHost, ctx->stream));
-      HIPCHK(hipEventRecord(done[cur], ctx->stream));
-      inflight_wgs[cur] = nwg;
-      used[cur] = true;
-    }
-    // the other buffer's chunk (the older one) has to be through before the unfinished line is parked in it
-    // and the next read fills it; the chunk just launched keeps the device busy meanwhile
-    const int other = cur ^ 1;
-    if (used[other]) { HIPCHK(hipEventSynchronize(done[other])); check_chunk(other); used[other] = false; }
-    carry = have - len;
-    if (carry) memcpy(ctx->text_pin[other], buf + len, carry);
-    cur = other;
-  }
-  for (int b = 0; b < 2; ++b) if (used[b] && inflight_wgs[b]) { HIPCHK(hipEventSynchronize(done[b])); check_chunk(b); }
-  if (src.format == 2) st->bytes = src.st.text_bytes;
+  for (int b = 0; b < 2; ++b) HIPCHK(retire(b));
+  if (src.format != 0) st->bytes = src.st.text_bytes;
   TextParseStats hs;
   HIPCHK(hipMemcpyAsync(&hs, d_stats, sizeof(hs), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -444,16 +482,8 @@ int rsi_hot_load_depth_text(rsi_ctx* ctx, const char* path, int64_t n, rsi_text_
     st->fallback = 1; st->lines = st->stored = st->beyond = 0;
     std::vector<int32_t> rd((size_t)n, 0);
     std::vector<char> all;
-    size_t have = 0;
-    if (src.format != 0) {   // compressed: the text once more, inflated on the host from the start
-      if (int rc = src.host_range(0, st->bytes, all)) return fail(ctx, rc, src.err);
-      have = all.size();
-    } else {
-      all.resize((size_t)st->bytes);
-      if (lseek(fd, 0, SEEK_SET) != 0) return fail(ctx, RSI_ERR_INTERNAL, "seek error");
-      while (have < all.size()) { const ssize_t got = read(fd, all.data() + have, all.size() - have); if (got <= 0) break; have += (size_t)got; }
-    }
-    parse_depth_text_host(all.data(), have, n, rd, st);
+    if (int rc = src.host_range(0, st->bytes, all)) return fail(ctx, rc, src.err);
+    parse_depth_text_host(all.data(), all.size(), n, rd, st);
     HIPCHK(hipMemcpyAsync(ctx->in_depth.p, rd.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
   }
@@ -477,10 +507,8 @@ int64_t rsi_hot_inflate_bgzf(rsi_ctx* ctx, const uint8_t* comp, int64_t comp_len
   int64_t text = 0;
   for (int64_t p = 0; p < comp_len;) {   // the member headers, on the host
     rsinf::Member m;
-    const int r = rsinf::bgzf_member(comp + p, (size_t)(comp_len - p), m);
-    if (r == 0) return fail(ctx, RSI_ERR_BAD_ARG, "BGZF: not a BGZF member at compressed offset " + std::to_string(p));
-    if (r < 0 || (int64_t)m.bsize > comp_len - p) return fail(ctx, RSI_ERR_BAD_ARG, "BGZF: the member at compressed offset " + std::to_string(p) + " runs past the end of the data");
-    if (m.isize > kMemberMax) return fail(ctx, RSI_ERR_BAD_ARG, "BGZF: ISIZE above 65536 in the member at compressed offset " + std::to_string(p));
+    const std::string bad = bgzf_member_error(comp + p, (size_t)(comp_len - p), p, m);
+    if (!bad.empty()) return fail(ctx, RSI_ERR_BAD_ARG, bad);
     tab.push_back(InflateBlock{(long long)(p + m.hdr), (long long)text, m.clen, m.isize, m.crc, 0});
     starts.push_back(p);
     text += m.isize; p += m.bsize;
@@ -585,17 +613,7 @@ int rsi_hot_load_depth_bam(rsi_ctx* ctx, const char* bam_path, const char* chrom
   int32_t* d_diff = ctx->in_depth.as<int32_t>();     // difference array first, scanned in place into the depth
   HIPCHK(hipMemsetAsync(d_diff, 0, (size_t)(n + 1) * 4, ctx->stream));
   ctx->n_in = n;
-  if (ctx->text_pin_cap < kTextChunk) {
-    for (int b = 0; b < 2; ++b) {
-      if (ctx->text_pin[b]) (void)hipHostFree(ctx->text_pin[b]);
-      ctx->text_pin[b] = nullptr;
-      if (hipHostMalloc(reinterpret_cast<void**>(&ctx->text_pin[b]), kTextChunk, hipHostMallocDefault) != hipSuccess)
-        return fail(ctx, RSI_ERR_INTERNAL, "out of pinned host memory for the BAM staging");
-    }
-    ctx->text_pin_cap = kTextChunk;
-  }
-  HIPCHK(ctx->text_dev[0].ensure(kTextChunk));
-  HIPCHK(ctx->text_dev[1].ensure(kTextChunk));
+  if (int rc = ctx_staging(ctx)) return rc;
   constexpr size_t kMaxRec = kTextChunk / 36 + 16;   // a record is at least 36 bytes
   const size_t stats_off = 2 * kMaxRec * 4, scan_off = stats_off + 256;
   HIPCHK(ctx->text_wg.ensure(scan_off + (size_t)scan_tiles(n) * 4 + 64));
@@ -804,9 +822,7 @@ struct rsi_genome_text {
   int device = 0;
   hipStream_t stream = nullptr;
   hipEvent_t sync_ev = nullptr;
-  int fd = -1;
-  std::string path, err;
-  int64_t file_size = 0, consumed = 0;   // consumed: file offset behind the last chunk cut
+  std::string err;
   std::vector<std::string> ref_names;
   std::vector<int64_t> ref_len;
   int max_resident = 1;
@@ -825,10 +841,7 @@ struct rsi_genome_text {
   bool open_valid = false;
   std::unordered_set<std::string> seen;  // every name met so far (contiguity)
   std::vector<int64_t> slot_n;           // length of the chromosome in each depth buffer
-  std::vector<char> carry;               // unfinished last line of the chunk read last
   int cur = 0;
-  size_t len[2] = {0, 0};
-  int64_t foff[2] = {0, 0};
   bool active = false, prefetched = false, done = false, failed = false;
   std::vector<NameBound> bounds;
   std::vector<std::string> bnames;
@@ -837,9 +850,7 @@ struct rsi_genome_text {
   std::vector<Pending> timed;
   std::vector<hipEvent_t> ev_free;
   double ms_bound = 0, ms_parse = 0;
-  DepthSource src;                       // the file's format; BGZF: the members inflated on the device into text_dev[b]
-  size_t dcarry = 0, dcut = 0;           // BGZF: the text behind the cut, text_dev[b][dcut, dcut + dcarry) of the chunk started last
-  int dcarry_nl = -1;                    // ... the offset of its last line end in it (-1: none, the usual unfinished line)
+  DepthSource src;                       // the file, its chunks in pin[b] / text_dev[b], their cuts and offsets
   DevBuf dnames;                         // BGZF: the boundary entries' names (launch_gather_names) and their pinned copy
   PinBuf hnames;
   hipStream_t istream = nullptr;         // BGZF: the next chunk's uploads and inflate run here, beside the parse of this one
@@ -868,7 +879,6 @@ struct rsi_genome_text {
     for (int b = 0; b < 2; ++b) if (pin[b]) (void)hipHostFree(pin[b]);
     if (sync_ev) (void)hipEventDestroy(sync_ev);
     if (stream) (void)hipStreamDestroy(stream);
-    if (fd >= 0) close(fd);
   }
   int fail_(int code, const std::string& m) { err = m; failed = true; set_global_error(m); return code; }
   int hip_(hipError_t e, const char* what) { return e == hipSuccess ? RSI_OK : fail_(RSI_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
@@ -905,41 +915,13 @@ struct rsi_genome_text {
     return -1;
   }
 
-  // BGZF: the carried line device to device, then the next members inflated behind it, on istream: text_dev[b]'s chunk
-  // before was parsed before the last wait, so the inflate overlaps the parse launches of the chunk in text_dev[b ^ 1]
-  // (which it only reads, for the carry).  len[b]: the text in text_dev[b], cut at its last line end by start_chunk, once
-  // the inflate's report is back.
-  int fill_bgzf(int b) {
-    if (dcarry) if (int rc = hip_(hipMemcpyAsync(text_dev[b].p, static_cast<char*>(text_dev[b ^ 1].p) + dcut, dcarry, hipMemcpyDeviceToDevice, istream), "hipMemcpyAsync")) return rc;
-    size_t added = 0;
-    if (int rc = src.launch(b, text_dev[b].p, dcarry, dcarry_nl, chunk, consumed + (int64_t)dcarry, istream, added)) return fail_(rc, src.err);
-    if (int rc = hip_(hipEventRecord(iev, istream), "hipEventRecord")) return rc;
-    len[b] = dcarry + added; foff[b] = consumed;
-    dcarry = dcut = 0;
-    return RSI_OK;
-  }
-
-  // Next chunk of the file into pin[b]: the carried line first, cut behind the last line end.  len[b] == 0: end of file.
+  // The next chunk into buffer b.  BGZF: the tail of the chunk before moves device to device and the next members are
+  // inflated behind it, on istream: text_dev[b]'s chunk before was parsed before the last wait, so the inflate overlaps the
+  // parse launches of the chunk in text_dev[b ^ 1] (which it only reads, for the tail).  start_chunk cuts it once the
+  // inflate's report is back.
   int fill(int b) {
-    if (src.format == 1) return fill_bgzf(b);
-    char* buf = pin[b];
-    size_t have = carry.size();
-    if (have) memcpy(buf, carry.data(), have);
-    bool eof = false;
-    while (have < chunk) {
-      const ssize_t got = src.read_text(buf + have, chunk - have);
-      if (got < 0) return fail_(src.format == 2 ? RSI_ERR_BAD_ARG : RSI_ERR_INTERNAL, src.err);
-      if (got == 0) { eof = true; break; }
-      have += (size_t)got;
-    }
-    size_t l = have;
-    if (!eof) {
-      while (l > 0 && buf[l - 1] != '\n') --l;
-      if (l == 0) return fail_(RSI_ERR_UNSUPPORTED, "a line of the depth file is longer than the chunk (" + std::to_string(chunk) + " bytes)");
-    }
-    carry.assign(buf + l, buf + have);
-    len[b] = l; foff[b] = consumed; consumed += (int64_t)l;
-    return RSI_OK;
+    if (int rc = src.fill(b, istream)) return fail_(rc, src.err);
+    return src.format == 1 ? hip_(hipEventRecord(iev, istream), "hipEventRecord") : RSI_OK;
   }
 
   // counts of the closed chromosomes are in hread: hand them over (in order), the unsorted ones through the sequential loop
@@ -957,19 +939,10 @@ struct rsi_genome_text {
         if (S.unsorted) {   // order-dependent rules in play: this chromosome's bytes through the sequential loop
           o.stats.fallback = 1; o.stats.lines = o.stats.stored = o.stats.beyond = 0;
           std::vector<char> text;
-          size_t have = 0;
-          if (src.format != 0) {   // compressed: the range inflated once more on the host
-            if (int rc = src.host_range(c.start, c.end, text)) return fail_(rc, src.err);
-            have = text.size();
-          } else text.resize((size_t)(c.end - c.start));
-          while (have < text.size()) {
-            const ssize_t got = pread(fd, text.data() + have, text.size() - have, (off_t)(c.start + (int64_t)have));
-            if (got <= 0) return fail_(RSI_ERR_INTERNAL, "read error on " + path);
-            have += (size_t)got;
-          }
+          if (int rc = src.host_range(c.start, c.end, text)) return fail_(rc, src.err);
           const int64_t stride = samples ? genome_sample_stride(c.n) : c.n;
           std::vector<int32_t> rd((size_t)(samples ? ncols() * stride : c.n), 0);
-          parse_depth_text_host(text.data(), have, c.n, rd, &o.stats, true, samples ? &cols : nullptr, stride, bed);
+          parse_depth_text_host(text.data(), text.size(), c.n, rd, &o.stats, true, samples ? &cols : nullptr, stride, bed);
           if (int rc = hip_(hipMemcpyAsync(slot_buf[(size_t)c.slot].p, rd.data(), rd.size() * 4, hipMemcpyHostToDevice, stream), "hipMemcpyAsync")) return rc;
           if (int rc = wait()) return rc;
         }
@@ -993,84 +966,42 @@ struct rsi_genome_text {
     open_valid = false;
   }
 
-  // The boundary pass over the chunk in pin[b] and its one read-back.  Too many name changes for the list: the chunk is cut
-  // shorter (at a line end) and the rest goes in front of the next one.
+  // The boundary pass over the chunk in buffer b and its one read-back.  BGZF: the pass runs over all the inflated text, the
+  // unfinished last line too, and the read-back also brings the inflate's report; the source cuts the chunk there and the
+  // entries behind the cut are dropped.  More name changes than the list holds: the chunk is cut shorter at a line end, the
+  // rest given back to the source for the next chunk, and the pass repeats.  The names come from the pinned text, or for
+  // BGZF back from the device (launch_gather_names, 4096 at a time).
   int start_chunk(int b) {
-    if (src.format == 1) return start_chunk_bgzf(b);
-    if (int rc = hip_(hipMemcpyAsync(text_dev[b].p, pin[b], len[b], hipMemcpyHostToDevice, stream), "hipMemcpyAsync")) return rc;
+    const bool in_hbm = src.format == 1;   // BGZF: the text exists only in text_dev[b]
+    if (in_hbm) { if (int rc = hip_(hipStreamWaitEvent(stream, iev, 0), "hipStreamWaitEvent")) return rc; }   // the chunk's inflate (fill)
+    else if (int rc = hip_(src.upload(b, stream), "hipMemcpyAsync")) return rc;
     const size_t first = std::min<size_t>(bound_cap, 4096);
-    for (;;) {
-      if (int rc = hip_(hipMemsetAsync(d_count(), 0, 16, stream), "hipMemsetAsync")) return rc;
-      hipEvent_t a = event(), e = event();
-      if (a) (void)hipEventRecord(a, stream);
-      launch_text_name_bounds(text_dev[b].p, (long long)len[b], d_bounds(), d_count(), bound_cap, stream, bed);
-      if (a && e) { (void)hipEventRecord(e, stream); timed.push_back({a, e, false}); }
-      if (int rc = hip_(hipMemcpyAsync(hread.p, dread.p, slots_bytes + 16 + first * sizeof(NameBound), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync")) return rc;
-      if (int rc = wait()) return rc;
-      if (*h_count() <= bound_cap) break;
-      size_t l = len[b] / 2;
-      while (l > 0 && pin[b][l - 1] != '\n') --l;
-      if (l == 0) return fail_(RSI_ERR_INTERNAL, "genome text: no line end in the first half of a chunk");
-      carry.insert(carry.begin(), pin[b] + l, pin[b] + len[b]);
-      consumed -= (int64_t)(len[b] - l);
-      len[b] = l;
-    }
-    const unsigned k = *h_count();
-    if (k > first) {
-      if (int rc = hip_(hipMemcpyAsync(h_bounds() + first, d_bounds() + first, (k - first) * sizeof(NameBound), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync")) return rc;
-      if (int rc = wait()) return rc;
-    }
-    if (int rc = finalize_awaiting()) return rc;
-    bounds.assign(h_bounds(), h_bounds() + k);
-    std::sort(bounds.begin(), bounds.end(), [](const NameBound& x, const NameBound& y) { return x.line < y.line; });
-    bnames.clear();
-    for (const NameBound& nb : bounds) {
-      if (nb.len >= (int)sizeof(rsi_genome_chrom::name)) return fail_(RSI_ERR_UNSUPPORTED, "genome text: a chromosome name is longer than 255 bytes");
-      bnames.emplace_back(pin[b] + nb.name, (size_t)nb.len);
-    }
-    cursor = 0; range_start = 0;
-    return RSI_OK;
-  }
-
-  // BGZF: the boundary pass over all the chunk's text (the unfinished last line too) and the one read-back, which also brings
-  // the inflate's report: a bad member, the last line end.  The chunk is cut there and the entries behind the cut dropped;
-  // the rest goes device to device in front of the next chunk (fill_bgzf).  The names come back from the device
-  // (launch_gather_names, 4096 at a time).  More name changes than the list holds: the chunk is cut shorter at a listed
-  // line start (in its second half where one is listed) and the pass repeats, as the text path does on the host.
-  int start_chunk_bgzf(int b) {
-    if (int rc = hip_(hipStreamWaitEvent(stream, iev, 0), "hipStreamWaitEvent")) return rc;   // the chunk's inflate (fill_bgzf)
-    const size_t first = std::min<size_t>(bound_cap, 4096);
-    const size_t total = len[b];
-    size_t cut = total;
-    int last_nl = -1;
     for (bool once = true;; once = false) {
       if (int rc = hip_(hipMemsetAsync(d_count(), 0, 16, stream), "hipMemsetAsync")) return rc;
       hipEvent_t a = event(), e = event();
       if (a) (void)hipEventRecord(a, stream);
-      launch_text_name_bounds(text_dev[b].p, (long long)cut, d_bounds(), d_count(), bound_cap, stream, bed);
+      launch_text_name_bounds(text_dev[b].p, (long long)src.len[b], d_bounds(), d_count(), bound_cap, stream, bed);
       if (a && e) { (void)hipEventRecord(e, stream); timed.push_back({a, e, false}); }
       if (int rc = hip_(hipMemcpyAsync(hread.p, dread.p, slots_bytes + 16 + first * sizeof(NameBound), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync")) return rc;
       if (int rc = wait()) return rc;
-      if (once) {
-        if (int rc = src.check(b, &last_nl)) return fail_(rc, src.err);
-        if (!src.exhausted) {
-          if (last_nl < 0) return fail_(RSI_ERR_UNSUPPORTED, "a line of the depth file is longer than the chunk (" + std::to_string(chunk) + " bytes)");
-          cut = (size_t)last_nl + 1;
-        }
-      }
+      if (once) if (int rc = src.cut(b)) return fail_(rc, src.err);
       if (*h_count() <= bound_cap) break;
-      long long hi = -1, lo = 0;   // the first listed line start in the second half; the last one in the first half
-      for (size_t i = 0; i < first; ++i) {
-        const long long l = h_bounds()[i].line;
-        if (l <= 0 || l >= (long long)cut) continue;
-        if (2 * l >= (long long)cut) hi = hi < 0 ? l : std::min(hi, l);
-        else lo = std::max(lo, l);
+      const long long len = (long long)src.len[b];
+      long long c = 0;
+      if (!in_hbm) c = (long long)src.line_cut(b, (size_t)len / 2);   // the last line end in the first half
+      else {   // the first listed line start in the second half, else the last one in the first half
+        long long hi = -1;
+        for (size_t i = 0; i < first; ++i) {
+          const long long l = h_bounds()[i].line;
+          if (l <= 0 || l >= len) continue;
+          if (2 * l >= len) hi = hi < 0 ? l : std::min(hi, l);
+          else c = std::max(c, l);
+        }
+        if (hi > 0) c = hi;
       }
-      const long long c = hi > 0 ? hi : lo;
-      if (c <= 0) return fail_(RSI_ERR_INTERNAL, "genome text: no line start listed to cut a chunk at");
-      cut = (size_t)c;
+      if (c <= 0) return fail_(RSI_ERR_INTERNAL, "genome text: no line end to cut a chunk shorter at");
+      if (int rc = src.give_back(b, (size_t)c)) return fail_(rc, src.err);
     }
-    if (total - cut >= chunk) return fail_(RSI_ERR_UNSUPPORTED, "a line of the depth file is longer than the chunk (" + std::to_string(chunk) + " bytes)");
     const unsigned k = *h_count();
     if (k > first) {
       if (int rc = hip_(hipMemcpyAsync(h_bounds() + first, d_bounds() + first, (k - first) * sizeof(NameBound), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync")) return rc;
@@ -1078,28 +1009,29 @@ struct rsi_genome_text {
     }
     if (int rc = finalize_awaiting()) return rc;
     constexpr unsigned kWin = 4096;
-    if (int rc = hip_(dnames.ensure((size_t)kWin * 256), "hipMalloc")) return rc;
-    if (int rc = hip_(hnames.ensure((size_t)kWin * 256), "hipHostMalloc")) return rc;
+    if (in_hbm) {
+      if (int rc = hip_(dnames.ensure((size_t)kWin * 256), "hipMalloc")) return rc;
+      if (int rc = hip_(hnames.ensure((size_t)kWin * 256), "hipHostMalloc")) return rc;
+    }
     std::vector<std::pair<NameBound, std::string>> named;
     for (unsigned w0 = 0; w0 < k; w0 += kWin) {
       const unsigned w1 = std::min(k, w0 + kWin);
-      launch_gather_names(text_dev[b].p, d_bounds(), w0, w1, dnames.as<char>(), stream);
-      if (int rc = hip_(hipMemcpyAsync(hnames.p, dnames.p, (size_t)(w1 - w0) * 256, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync")) return rc;
-      if (int rc = wait()) return rc;
+      if (in_hbm) {
+        launch_gather_names(text_dev[b].p, d_bounds(), w0, w1, dnames.as<char>(), stream);
+        if (int rc = hip_(hipMemcpyAsync(hnames.p, dnames.p, (size_t)(w1 - w0) * 256, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync")) return rc;
+        if (int rc = wait()) return rc;
+      }
       for (unsigned i = w0; i < w1; ++i) {
         const NameBound& nb = h_bounds()[i];
-        if (nb.line >= (long long)cut) continue;   // the unfinished line: parsed with the next chunk
+        if (nb.line >= (long long)src.len[b]) continue;   // BGZF: behind the cut, parsed with the next chunk
         if (nb.len >= (int)sizeof(rsi_genome_chrom::name)) return fail_(RSI_ERR_UNSUPPORTED, "genome text: a chromosome name is longer than 255 bytes");
-        named.emplace_back(nb, std::string(hnames.as<char>() + (size_t)(i - w0) * 256, (size_t)nb.len));
+        const char* name = in_hbm ? hnames.as<char>() + (size_t)(i - w0) * 256 : src.pin[b] + nb.name;
+        named.emplace_back(nb, std::string(name, (size_t)nb.len));
       }
     }
     std::sort(named.begin(), named.end(), [](const std::pair<NameBound, std::string>& x, const std::pair<NameBound, std::string>& y) { return x.first.line < y.first.line; });
     bounds.clear(); bnames.clear();
     for (auto& x : named) { bounds.push_back(x.first); bnames.push_back(std::move(x.second)); }
-    len[b] = cut;
-    dcut = cut; dcarry = total - cut;
-    dcarry_nl = last_nl >= (int)cut ? last_nl - (int)cut : -1;
-    consumed += (int64_t)cut;
     cursor = 0; range_start = 0;
     return RSI_OK;
   }
@@ -1110,7 +1042,7 @@ struct rsi_genome_text {
     const char* d_text = static_cast<const char*>(text_dev[b].p);
     for (;;) {
       const long long begin = range_start;
-      long long end = (long long)len[b];
+      long long end = (long long)src.len[b];
       GenomeSeg* segs = hsegs.as<GenomeSeg>() + seg_used;
       int nseg = 0;
       auto seg_of_open = [&](long long start) {
@@ -1125,22 +1057,22 @@ struct rsi_genome_text {
         if (open_valid && name == open.name) { ++cursor; continue; }   // the chunk's first data line, continuing the chromosome
         if (seen.count(name))
           return fail_(RSI_ERR_BAD_ARG, "genome text: the lines of chromosome " + name + " are not contiguous: it comes back at byte " +
-                                              std::to_string(foff[b] + B.line) + " after other chromosomes");
+                                              std::to_string(src.foff[b] + B.line) + " after other chromosomes");
         const bool filtered = name.find("MT") != std::string::npos || name.find('.') != std::string::npos;   // the BAM walk's filter
         const int ref = filtered ? -1 : find_ref(name);
         int slot = -1;
         if (ref >= 0) {
           for (int s = 0; s < max_resident; ++s) if (slot_state[(size_t)s] == 0) { slot = s; break; }
           if (slot < 0) {   // the open chromosome is complete at B: parse up to there, hand it over, resume here once a buffer is free
-            close_open(foff[b] + B.line);
+            close_open(src.foff[b] + B.line);
             end = B.line; stalled = true;
             break;
           }
         }
         if (nseg == kMaxGenomeSegs) { end = B.line; break; }
-        close_open(foff[b] + B.line);
+        close_open(src.foff[b] + B.line);
         open = Chrom();
-        open.name = name; open.start = foff[b] + B.line; open.t0 = now_ms(); open.report = !filtered;
+        open.name = name; open.start = src.foff[b] + B.line; open.t0 = now_ms(); open.report = !filtered;
         open_valid = true;
         seen.insert(name);
         if (ref >= 0) {
@@ -1174,7 +1106,7 @@ struct rsi_genome_text {
       }
       range_start = end;
       if (stalled) return 2;
-      if (cursor == bounds.size() && end == (long long)len[b]) return 1;
+      if (cursor == bounds.size() && end == (long long)src.len[b]) return 1;
     }
   }
 
@@ -1183,8 +1115,8 @@ struct rsi_genome_text {
     if (!active) {
       if (!prefetched) if (int rc = fill(cur)) return rc;
       prefetched = false;
-      if (len[cur] == 0) {   // end of the file
-        close_open(consumed);
+      if (src.len[cur] == 0) {   // end of the file
+        close_open(src.foff[cur]);
         if (int rc = sync_counts()) return rc;
         done = true;
         return RSI_OK;
@@ -1235,7 +1167,7 @@ rsi_genome_text* genome_text_open(const char* fn, int device, const char* path, 
       g->scols.n = ncols;
       for (int i = 0; i < ncols; ++i) { g->scols.col[i] = order[(size_t)i].first; g->scols.j[i] = order[(size_t)i].second; }
     }
-    g->device = device; g->path = path; g->max_resident = max_resident; g->bed = bed;
+    g->device = device; g->max_resident = max_resident; g->bed = bed;
     g->chunk = chunk_bytes ? chunk_bytes : kTextChunk;
     for (int i = 0; i < nref; ++i) { g->ref_names.emplace_back(names[i] ? names[i] : ""); g->ref_len.push_back(lengths[i]); }
     int ndev = 0;
@@ -1262,12 +1194,7 @@ rsi_genome_text* genome_text_open(const char* fn, int device, const char* path, 
       }
       g->max_resident = (int)std::min<size_t>((size_t)max_resident, fit);
     }
-    g->fd = open(path, O_RDONLY);
-    if (g->fd < 0) { set_global_error(std::string("Cannot open file ") + path); return bad(RSI_ERR_BAD_ARG); }
-    struct stat sb;
-    if (fstat(g->fd, &sb) != 0) { set_global_error(std::string("Cannot stat file ") + path); return bad(RSI_ERR_BAD_ARG); }
-    g->file_size = (int64_t)sb.st_size;
-    if (g->src.open_(g->fd, g->path, g->file_size)) { set_global_error(g->src.err); return bad(RSI_ERR_INTERNAL); }
+    if (int rc = g->src.open_(path)) { set_global_error(g->src.err); return bad(rc); }
     if (g->src.format == 1) {
       g->chunk = std::max(g->chunk, kBgzfMinChunk);   // whole members per chunk
       if (hipStreamCreateWithFlags(&g->istream, hipStreamNonBlocking) != hipSuccess ||
@@ -1291,6 +1218,7 @@ rsi_genome_text* genome_text_open(const char* fn, int device, const char* path, 
       set_global_error("genome text: out of device or pinned memory for the staging buffers");
       return bad(RSI_ERR_HIP);
     }
+    g->src.borrow(g->pin[0], g->pin[1], g->text_dev[0].p, g->text_dev[1].p, g->chunk);
     if (g->bed) {   // the run list: room for every piece a sorted chunk can give (bedgraph_run_cap)
       long long sum_len = 0;
       for (int64_t n : g->ref_len) if (n > 0 && n < (1ll << 31) - 4096) sum_len += n;

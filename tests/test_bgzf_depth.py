@@ -309,6 +309,25 @@ def test_single_chromosome_reader_over_many_chunks(hot, tmp_path):
         assert np.array_equal(hot.fetch("depth_in"), d0), form
         assert tuple(st[k] for k in STATS) == tuple(st0[k] for k in STATS), (form, st, st0)
         q.unlink()
+    # The order broken exactly at each format's first chunk cut: the first line of chunk 2 repeats the last position of
+    # chunk 1, which only the host's check across chunks sees.  The cut is the last line end in the first 64 MiB of text;
+    # for BGZF, in the whole members (bz.bgzf's 65280 text bytes each) that fit in 64 MiB.
+    chunk = 64 << 20
+    for form, limit, pack in (("text", chunk, None), ("gzip", chunk, bz.gzip_members), ("bgzf", chunk // 65280 * 65280, bz.bgzf)):
+        cut = text.rindex(b"\n", 0, limit) + 1
+        end = text.index(b"\n", cut)
+        pos, x = (int(v) for v in text[cut:end].split(b"\t"))
+        line = f"{pos - 1}\t{x}".encode()
+        assert len(line) == end - cut
+        q = tmp_path / f"cut_{form}"
+        bad = text[:cut] + line + text[end:]
+        q.write_bytes(pack(bad, level=1) if pack else bad)
+        st = hot.load_depth_text(str(q), n)
+        exp = d0.copy()
+        exp[pos - 2], exp[pos - 1] = x, 0   # what the sequential loop stores: the repeat overwrites, pos stays unset
+        assert st["fallback"] == 1, (form, st)
+        assert np.array_equal(hot.fetch("depth_in"), exp), form
+        q.unlink()
 
 
 @pytest.mark.gpu

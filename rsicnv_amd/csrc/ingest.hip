@@ -1096,12 +1096,10 @@ struct rsi_genome_text {
         seg_used += (size_t)nseg;
         hipEvent_t a = event(), e = event();
         if (a) (void)hipEventRecord(a, stream);
-        if (bed) {
-          if (int rc = hip_(hipMemsetAsync(druns.p, 0, sizeof(unsigned long long), stream), "hipMemsetAsync")) return rc;
-          launch_parse_genome_bedgraph(d_text, begin, end, d_segs, nseg, dread.as<GenomeSlotStats>(), dwg.as<long long>(),
-                                       reinterpret_cast<BedRun*>(druns.as<char>() + 256), druns.as<unsigned long long>(), run_cap, stream);
-        } else if (samples) launch_parse_genome_samples(d_text, begin, end, d_segs, nseg, scols, dread.as<GenomeSlotStats>(), dwg.as<long long>(), stream);
-        else launch_parse_genome_text(d_text, begin, end, d_segs, nseg, dread.as<GenomeSlotStats>(), dwg.as<long long>(), stream);
+        if (bed) if (int rc = hip_(hipMemsetAsync(druns.p, 0, sizeof(unsigned long long), stream), "hipMemsetAsync")) return rc;
+        launch_parse_genome(bed ? GenomeFormat::kBedgraph : samples ? GenomeFormat::kSamples : GenomeFormat::kText, d_text, begin, end, d_segs,
+                            nseg, dread.as<GenomeSlotStats>(), dwg.as<long long>(), &scols,
+                            bed ? reinterpret_cast<BedRun*>(druns.as<char>() + 256) : nullptr, druns.as<unsigned long long>(), run_cap, stream);
         if (a && e) { (void)hipEventRecord(e, stream); timed.push_back({a, e, true}); }
       }
       range_start = end;
@@ -1213,7 +1211,7 @@ rsi_genome_text* genome_text_open(const char* fn, int device, const char* path, 
     const size_t text_cap = g->chunk + (g->src.format == 1 ? kMemberMax : 0);
     if (g->text_dev[0].ensure(text_cap) != hipSuccess || g->text_dev[1].ensure(text_cap) != hipSuccess || g->dread.ensure(read_bytes) != hipSuccess ||
         g->dsegs.ensure((size_t)g->seg_cap * sizeof(GenomeSeg)) != hipSuccess ||
-        g->dwg.ensure((size_t)genome_parse_workgroups((long long)text_cap) * 4 * sizeof(long long)) != hipSuccess ||
+        g->dwg.ensure((size_t)genome_parse_workgroups(GenomeFormat::kText, (long long)text_cap) * 4 * sizeof(long long)) != hipSuccess ||
         g->hread.ensure(read_bytes) != hipSuccess || g->hsegs.ensure((size_t)g->seg_cap * sizeof(GenomeSeg)) != hipSuccess) {
       set_global_error("genome text: out of device or pinned memory for the staging buffers");
       return bad(RSI_ERR_HIP);

@@ -471,11 +471,6 @@ void launch_text_name_bounds(const void* text, long long nbytes, NameBound* boun
 struct GenomeSeg { long long start, n; int32_t* depth; int32_t slot, pad; };
 struct GenomeSlotStats { unsigned long long lines, stored, beyond; unsigned int unsorted, pad; long long last_pos; /* 0: none yet */ };
 constexpr int kMaxGenomeSegs = 512;
-int genome_parse_workgroups(long long nbytes);
-// wg: 4 * genome_parse_workgroups(end - begin) words of scratch (per workgroup: first segment, first position, last segment,
-// last position) that the order fold reads.
-void launch_parse_genome_text(const void* text, long long begin, long long end, const GenomeSeg* segs, int nseg,
-                              GenomeSlotStats* slots, long long* wg, hipStream_t stream);
 // Cohort files, "RNAME pos d1 d2 ... dK": the same pass, storing the selected depth columns.  Sample j of a segment lives at
 // depth + j * genome_sample_stride(n) (16-byte aligned starts); a line's column c is what `iss >> pos >> d1 >> ... >> dc`
 // leaves in dc (0 once an extraction has failed).  cols: the selected 1-based columns in ascending order, j[i] the sample
@@ -483,20 +478,24 @@ void launch_parse_genome_text(const void* text, long long begin, long long end, 
 constexpr int kMaxGenomeSamples = 64;
 struct GenomeSampleCols { int32_t col[kMaxGenomeSamples], j[kMaxGenomeSamples]; int32_t n, pad; };
 __host__ __device__ inline long long genome_sample_stride(long long n) { return (n + 4 + 3) & ~3ll; }
-int genome_sample_parse_workgroups(long long nbytes);
-// wg: 4 * genome_sample_parse_workgroups(end - begin) words, as above
-void launch_parse_genome_samples(const void* text, long long begin, long long end, const GenomeSeg* segs, int nseg,
-                                 const GenomeSampleCols& cols, GenomeSlotStats* slots, long long* wg, hipStream_t stream);
 // bedGraph files, "RNAME start end d" (DESIGN.md 6d): the same pass over intervals.  A line stands for the lines "RNAME p d",
-// p = start + 1 .. end; depth, counts and order proof are what launch_parse_genome_text gives on those lines.  Runs longer than
+// p = start + 1 .. end; depth, counts and order proof are what the text format gives on those lines.  Runs longer than
 // the parsing thread writes go to `runs` in pieces of at most kBedPiece bases, written by a fill kernel behind the parse;
 // *nruns (8 bytes) must be zeroed before each launch.  run_cap: bedgraph_run_cap(chunk bytes, the sum of the chromosomes'
 // lengths), enough for any sorted text; a chromosome whose pieces do not fit is marked unsorted (the host loop rebuilds it).
 struct BedRun { int32_t* dst; uint32_t len; int32_t d; };
 constexpr long long kBedPiece = 1ll << 20;
 unsigned long long bedgraph_run_cap(long long text_bytes, long long sum_len);
-void launch_parse_genome_bedgraph(const void* text, long long begin, long long end, const GenomeSeg* segs, int nseg, GenomeSlotStats* slots,
-                                  long long* wg, BedRun* runs, unsigned long long* nruns, unsigned int run_cap, hipStream_t stream);
+// What a line behind its name holds: "pos d", "pos d1 ... dK" or "start end d".
+enum class GenomeFormat { kText, kSamples, kBedgraph };
+// Workgroups of the parse over nbytes of text; the most for kText and kBedgraph (the smaller tile).
+int genome_parse_workgroups(GenomeFormat format, long long nbytes);
+// The parse of `format`, the order fold behind it and, for kBedgraph, the fill.  wg: 4 * genome_parse_workgroups(format, end -
+// begin) words of scratch (per workgroup: first segment, first position, last segment, last position) that the order fold
+// reads.  cols is read for kSamples only; runs, nruns and run_cap for kBedgraph only.
+void launch_parse_genome(GenomeFormat format, const void* text, long long begin, long long end, const GenomeSeg* segs, int nseg,
+                         GenomeSlotStats* slots, long long* wg, const GenomeSampleCols* cols, BedRun* runs, unsigned long long* nruns,
+                         unsigned int run_cap, hipStream_t stream);
 
 // ---- BGZF members inflated on the device (kernels_inflate.hip, inflate_core.h) ----
 // One member per entry: its deflate payload at comp[coff, coff + clen), its ISIZE bytes to text[out, out + isize) once ISIZE

@@ -168,102 +168,6 @@ __global__ __launch_bounds__(kThreads) void k_text_name_bounds(const unsigned ch
   }
 }
 
-// Parse pass.  The order proof of k_parse_depth_text, per chromosome: within a thread, within a workgroup (thread 0 over the
-// threads' first and last counted lines), then k_genome_order_fold across the workgroups and against the chromosome's last
-// position in the chunks before.  Counts go out with one set of atomics per workgroup when the workgroup's lines end in one
-// segment (the common case: a chromosome is millions of lines), per thread otherwise.
-__global__ __launch_bounds__(kThreads) void k_parse_genome_text(const unsigned char* __restrict__ text, long long begin, long long end,
-                                                                const GenomeSeg* __restrict__ segs, int nseg,
-                                                                GenomeSlotStats* __restrict__ slots, long long* __restrict__ wg) {
-  __shared__ long long s_start[kMaxGenomeSegs];
-  __shared__ int s_segA[kThreads], s_segB[kThreads];
-  __shared__ long long s_firstA[kThreads], s_lastB[kThreads];
-  __shared__ int s_lo, s_hi;
-  for (int i = threadIdx.x; i < nseg; i += kThreads) s_start[i] = segs[i].start;
-  if (threadIdx.x == 0) { s_lo = 0x7fffffff; s_hi = -1; }
-  __syncthreads();
-  const long long b0 = begin + ((long long)blockIdx.x * kThreads + threadIdx.x) * kSpan;
-  int segA = -1, segB = -1;            // segments of the thread's first / last counted line
-  long long firstA = -1, lastB = -1;   // their positions
-  int cseg = -1;                       // segment the counters below belong to
-  unsigned lines = 0, stored = 0, beyond = 0;
-  bool bad = false;
-  auto flush = [&]() {
-    if (cseg >= 0 && (lines | bad)) {
-      GenomeSlotStats* S = &slots[segs[cseg].slot];
-      if (lines) atomicAdd(&S->lines, (unsigned long long)lines);
-      if (stored) atomicAdd(&S->stored, (unsigned long long)stored);
-      if (beyond) atomicAdd(&S->beyond, (unsigned long long)beyond);
-      if (bad) atomicOr(&S->unsorted, 1u);
-    }
-    lines = stored = beyond = 0; bad = false;
-  };
-  if (b0 < end) {
-    const long long b1 = b0 + kSpan < end ? b0 + kSpan : end;
-    int g = -1;
-    for (long long s = b0; s < b1; ++s) {
-      if (s != 0 && text[s - 1] != '\n') continue;
-      long long e, ns, ne;
-      line_name(text, s, end, e, ns, ne);
-      if (ns == ne) continue;
-      if (g < 0) {   // last segment starting at or before s
-        int lo = 0, hi = nseg - 1;
-        while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (s_start[mid] <= s) lo = mid; else hi = mid - 1; }
-        g = lo;
-      }
-      while (g + 1 < nseg && s_start[g + 1] <= s) ++g;
-      const GenomeSeg& G = segs[g];
-      if (G.slot < 0) continue;
-      long long q = ne, pos = 0, d = 0;
-      if (extract_i32(text, q, e, pos)) extract_i32(text, q, e, d);
-      if (pos < 1) continue;
-      if (g != cseg) { flush(); cseg = g; }
-      ++lines;
-      if (segB == g && pos <= lastB) bad = true;
-      if (segA < 0) { segA = g; firstA = pos; }
-      segB = g; lastB = pos;
-      if (pos >= G.n) { ++beyond; continue; }
-      G.depth[pos - 1] = (int32_t)d;
-      ++stored;
-    }
-  }
-  s_segA[threadIdx.x] = segA; s_segB[threadIdx.x] = segB;
-  s_firstA[threadIdx.x] = firstA; s_lastB[threadIdx.x] = lastB;
-  if (cseg >= 0 && (lines | bad)) { atomicMin(&s_lo, cseg); atomicMax(&s_hi, cseg); }
-  __syncthreads();
-  if (threadIdx.x == 0) {   // the threads in order: a counted line must lie beyond the previous one of its segment
-    int run_seg = -1, wseg = -1;
-    long long run_last = -1, wfirst = -1;
-    for (int t = 0; t < kThreads; ++t) {
-      if (s_segA[t] < 0) continue;
-      if (wseg < 0) { wseg = s_segA[t]; wfirst = s_firstA[t]; }
-      if (s_segA[t] == run_seg && s_firstA[t] <= run_last) atomicOr(&slots[segs[run_seg].slot].unsorted, 1u);
-      run_seg = s_segB[t]; run_last = s_lastB[t];
-    }
-    long long* r = wg + 4 * (long long)blockIdx.x;
-    r[0] = wseg; r[1] = wfirst; r[2] = run_seg; r[3] = run_last;
-  }
-  if (s_lo == s_hi) {   // every thread's remaining counts are one segment's: one set of atomics for the workgroup
-    const bool mine = cseg == s_lo && (lines | bad);
-    unsigned l = mine ? lines : 0, st = mine ? stored : 0, bd = mine ? beyond : 0, bb = mine && bad ? 1u : 0u;
-    for (int d = 32; d >= 1; d >>= 1) { l += __shfl_xor(l, d); st += __shfl_xor(st, d); bd += __shfl_xor(bd, d); bb |= __shfl_xor(bb, d); }
-    __shared__ unsigned s_tot[kThreads / 64][4];
-    if ((threadIdx.x & 63) == 0) { s_tot[threadIdx.x >> 6][0] = l; s_tot[threadIdx.x >> 6][1] = st; s_tot[threadIdx.x >> 6][2] = bd; s_tot[threadIdx.x >> 6][3] = bb; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      unsigned long long t0 = 0, t1 = 0, t2 = 0; unsigned t3 = 0;
-      for (int w = 0; w < kThreads / 64; ++w) { t0 += s_tot[w][0]; t1 += s_tot[w][1]; t2 += s_tot[w][2]; t3 |= s_tot[w][3]; }
-      GenomeSlotStats* S = &slots[segs[s_lo].slot];
-      if (t0) atomicAdd(&S->lines, t0);
-      if (t1) atomicAdd(&S->stored, t1);
-      if (t2) atomicAdd(&S->beyond, t2);
-      if (t3) atomicOr(&S->unsorted, 1u);
-    }
-  } else {
-    flush();
-  }
-}
-
 // Across the workgroups of one parse launch: a workgroup's first counted line against the last one of the nearest workgroup
 // before it that counted any (same segment only); the launch's first counted line against its chromosome's last position so
 // far; the launch's last counted line becomes its chromosome's last position.  One workgroup.
@@ -288,34 +192,166 @@ __global__ __launch_bounds__(kThreads) void k_genome_order_fold(const long long*
   }
 }
 
-// Cohort files: k_parse_genome_text's line walk, segment lookup, order proof and counter atomics; per counted
-// line below the chromosome's end, the depth tokens are read in order up to the largest selected column and every selected
-// one is stored to its sample's array.  A line is 15-20 bytes plus 3-4 per sample, so a thread takes kSampleSpan bytes of
-// text instead of kSpan: with 32-byte spans most threads of a wave would find no line start while a few walk a whole line.
-constexpr int kSampleSpan = 128;
-constexpr int kSampleTile = kThreads * kSampleSpan;   // 32 KB of text per workgroup
+// ---- parse pass: one skeleton, k_parse_genome<Format>, and per format what one data line means ----
+// A Format gives kSpan (bytes of text per thread: the lines that START in them are the thread's), Count (the type of the
+// per-thread and per-workgroup counters), Args (its own kernel arguments, by value), Shared (its LDS, filled by stage() before
+// the first barrier), header() (name tokens that name no chromosome; tested before the segment lookup) and the line rule:
+//   counted(): is the line's tail [ne, e) a counted line?  Then L holds its first and last position (the order record; it
+//              counts last - first + 1 positions) and what store() needs of the line.
+//   store():   the writes; it returns how many of the counted positions are stored, the others lie beyond the chromosome's end.
+// Between the two the skeleton moves the counters to the line's segment and extends the order record.
 
-__global__ __launch_bounds__(kThreads) void k_parse_genome_samples(const unsigned char* __restrict__ text, long long begin, long long end,
-                                                                   const GenomeSeg* __restrict__ segs, int nseg, GenomeSampleCols cols,
-                                                                   GenomeSlotStats* __restrict__ slots, long long* __restrict__ wg) {
+// "NAME pos d", read like k_parse_depth_text's "pos d".
+struct TextLines {
+  static constexpr int kSpan = rsik::kSpan;
+  using Count = unsigned;
+  struct Args {};
+  struct Shared {};
+  struct Line { long long first, last, d; };
+  static __device__ void stage(const Args&, Shared&) {}
+  static __device__ bool header(const unsigned char*, long long, long long) { return false; }
+  static __device__ __forceinline__ bool counted(const unsigned char* __restrict__ t, long long ne, long long e, Line& L) {
+    long long q = ne, pos = 0;
+    L.d = 0;
+    if (extract_i32(t, q, e, pos)) extract_i32(t, q, e, L.d);
+    L.first = L.last = pos;
+    return pos >= 1;
+  }
+  static __device__ __forceinline__ Count store(const unsigned char* __restrict__, long long, const GenomeSeg& G, const Line& L, const Args&,
+                                                const Shared&, bool&) {
+    if (L.first >= G.n) return 0;
+    G.depth[L.first - 1] = (int32_t)L.d;
+    return 1;
+  }
+};
+
+// Cohort files, "NAME pos d1 ... dK": per counted line below the chromosome's end, the depth tokens are read in
+// order up to the largest selected column and every selected one is stored to its sample's array.  A line is 15-20 bytes plus
+// 3-4 per sample, so a thread takes 128 bytes of text: with 32-byte spans most threads of a wave would find no line start
+// while a few walk a whole line.
+struct SampleLines {
+  static constexpr int kSpan = 128;
+  using Count = unsigned;
+  using Args = GenomeSampleCols;
+  struct Shared { int col[kMaxGenomeSamples], j[kMaxGenomeSamples]; };
+  struct Line { long long first, last, q; bool ok; };
+  static __device__ void stage(const Args& cols, Shared& sh) {
+    if (threadIdx.x < kMaxGenomeSamples) { sh.col[threadIdx.x] = cols.col[threadIdx.x]; sh.j[threadIdx.x] = cols.j[threadIdx.x]; }
+  }
+  static __device__ bool header(const unsigned char*, long long, long long) { return false; }
+  static __device__ __forceinline__ bool counted(const unsigned char* __restrict__ t, long long ne, long long e, Line& L) {
+    long long pos = 0;
+    L.q = ne;
+    L.ok = extract_i32(t, L.q, e, pos);
+    L.first = L.last = pos;
+    return pos >= 1;
+  }
+  static __device__ __forceinline__ Count store(const unsigned char* __restrict__ t, long long e, const GenomeSeg& G, const Line& L,
+                                                const Args& cols, const Shared& sh, bool&) {
+    if (L.first >= G.n) return 0;
+    int32_t* out = G.depth + (L.first - 1);
+    const long long stride = genome_sample_stride(G.n);
+    // Column c is what its own extraction gives (the clamped bound included) while every extraction before it succeeded,
+    // 0 after a failed one.  (pos < n here, so pos did not overflow and ok holds.)
+    long long q = L.q, v = 0;
+    bool ok = L.ok;
+    int col = 1;                     // the next depth column to extract
+    for (int i = 0; i < cols.n; ++i) {
+      const int want = sh.col[i];
+      while (col <= want) { v = 0; if (ok) ok = extract_i32(t, q, e, v); ++col; }
+      out[(long long)sh.j[i] * stride] = (int32_t)v;
+    }
+    return 1;
+  }
+};
+
+// bedGraph files: a line "NAME start end d" stands for "NAME p d", p = start + 1 .. end; with a = max(start, 0)
+// and b = end its counted positions are a + 1 .. b: lines += b - a, those >= n are beyond, the others are stored at indices
+// [a, min(b, n - 1)).  The proof is the text one with first = a + 1 and last = b per line.  One line may stand for 2^31
+// positions, so the counters are 64-bit.
+// Writes: a run of at most kBedInline bases is written by the thread that parsed it, a longer one goes to the run list in
+// pieces of at most kBedPiece bases that k_bedgraph_fill writes, one workgroup per piece.  d == 0 writes nothing: the buffer
+// was cleared when the chromosome opened and, once the order proof holds, no base is written twice (a chromosome whose proof
+// fails, or whose pieces do not fit the list, is rebuilt on the host from a cleared buffer).
+constexpr int kBedInline = 128;
+
+struct BedLines {
+  static constexpr int kSpan = rsik::kSpan;
+  using Count = unsigned long long;
+  struct Args { BedRun* __restrict__ runs; unsigned long long* __restrict__ nruns; unsigned int run_cap; };
+  struct Shared {};
+  struct Line { long long first, last, d; };
+  static __device__ void stage(const Args&, Shared&) {}
+  static __device__ bool header(const unsigned char* __restrict__ t, long long ns, long long ne) {
+    return is_word(t, ns, ne, "track", 5) || is_word(t, ns, ne, "browser", 7);
+  }
+  static __device__ __forceinline__ bool counted(const unsigned char* __restrict__ t, long long ne, long long e, Line& L) {
+    long long q = ne, start = 0, stop = 0;
+    if (!extract_i64(t, q, e, start) || !extract_i64(t, q, e, stop)) return false;   // overflow included: no line
+    L.d = 0;
+    extract_i32(t, q, e, L.d);
+    const long long a = start > 0 ? start : 0;
+    L.first = a + 1; L.last = stop;
+    return stop > a;                   // else no position >= 1
+  }
+  static __device__ __forceinline__ Count store(const unsigned char* __restrict__, long long, const GenomeSeg& G, const Line& L, const Args& A,
+                                                const Shared&, bool& bad) {
+    const long long a = L.first - 1, b = L.last;
+    const long long edge = G.n - 1;  // positions >= n: beyond; the last base is never set
+    const long long hi = b < edge ? b : edge;
+    if (hi <= a) return 0;
+    const Count stored = (Count)(hi - a);
+    if (L.d == 0) return stored;
+    const int32_t v = (int32_t)L.d;
+    if (hi - a <= kBedInline) {
+      for (long long i = a; i < hi; ++i) G.depth[i] = v;
+      return stored;
+    }
+    const long long np = (hi - a + kBedPiece - 1) / kBedPiece;   // <= 2^31 / kBedPiece
+    const unsigned long long k = atomicAdd(A.nruns, (unsigned long long)np);
+    if (k + (unsigned long long)np > A.run_cap) {
+      // No room: the chromosome goes to the host loop.  The entries of [k, k + np) below run_cap are this thread's alone
+      // (the reservations are disjoint) and k_bedgraph_fill reads every entry below min(*nruns, run_cap), so each of them
+      // gets an empty piece: the fill never sees an entry nobody wrote in this launch.
+      bad = true;
+      for (unsigned long long r = k; r < A.run_cap && r < k + (unsigned long long)np; ++r) A.runs[r] = BedRun{nullptr, 0u, 0};
+      return stored;
+    }
+    for (long long j = 0; j < np; ++j) {
+      const long long p0 = a + j * kBedPiece, len = hi - p0 < kBedPiece ? hi - p0 : kBedPiece;
+      A.runs[k + (unsigned long long)j] = BedRun{G.depth + p0, (uint32_t)len, v};
+    }
+    return stored;
+  }
+};
+
+// The skeleton.  The order proof of k_parse_depth_text, per chromosome: within a thread, within a workgroup (thread 0 over the
+// threads' first and last counted lines), then k_genome_order_fold across the workgroups and against the chromosome's last
+// position in the chunks before.  Counts go out with one set of atomics per workgroup when the workgroup's lines end in one
+// segment (the common case: a chromosome is millions of lines), per thread otherwise.
+template <class F>
+__global__ __launch_bounds__(kThreads) void k_parse_genome(const unsigned char* __restrict__ text, long long begin, long long end,
+                                                           const GenomeSeg* __restrict__ segs, int nseg,
+                                                           GenomeSlotStats* __restrict__ slots, long long* __restrict__ wg,
+                                                           typename F::Args args) {
+  using Count = typename F::Count;
   __shared__ long long s_start[kMaxGenomeSegs];
   __shared__ int s_segA[kThreads], s_segB[kThreads];
   __shared__ long long s_firstA[kThreads], s_lastB[kThreads];
-  __shared__ int s_col[kMaxGenomeSamples], s_j[kMaxGenomeSamples];
+  __shared__ typename F::Shared s_fmt;
   __shared__ int s_lo, s_hi;
   for (int i = threadIdx.x; i < nseg; i += kThreads) s_start[i] = segs[i].start;
-  if (threadIdx.x < kMaxGenomeSamples) { s_col[threadIdx.x] = cols.col[threadIdx.x]; s_j[threadIdx.x] = cols.j[threadIdx.x]; }
+  F::stage(args, s_fmt);
   if (threadIdx.x == 0) { s_lo = 0x7fffffff; s_hi = -1; }
   __syncthreads();
-  const int ncol = cols.n;
-  const long long b0 = begin + ((long long)blockIdx.x * kThreads + threadIdx.x) * kSampleSpan;
+  const long long b0 = begin + ((long long)blockIdx.x * kThreads + threadIdx.x) * F::kSpan;
   int segA = -1, segB = -1;            // segments of the thread's first / last counted line
-  long long firstA = -1, lastB = -1;   // their positions
+  long long firstA = -1, lastB = -1;   // the first position of the one, the last of the other
   int cseg = -1;                       // segment the counters below belong to
-  unsigned lines = 0, stored = 0, beyond = 0;
+  Count lines = 0, stored = 0, beyond = 0;
   bool bad = false;
   auto flush = [&]() {
-    if (cseg >= 0 && (lines | bad)) {
+    if (cseg >= 0 && (lines || bad)) {
       GenomeSlotStats* S = &slots[segs[cseg].slot];
       if (lines) atomicAdd(&S->lines, (unsigned long long)lines);
       if (stored) atomicAdd(&S->stored, (unsigned long long)stored);
@@ -325,13 +361,13 @@ __global__ __launch_bounds__(kThreads) void k_parse_genome_samples(const unsigne
     lines = stored = beyond = 0; bad = false;
   };
   if (b0 < end) {
-    const long long b1 = b0 + kSampleSpan < end ? b0 + kSampleSpan : end;
+    const long long b1 = b0 + F::kSpan < end ? b0 + F::kSpan : end;
     int g = -1;
     for (long long s = b0; s < b1; ++s) {
       if (s != 0 && text[s - 1] != '\n') continue;
       long long e, ns, ne;
       line_name(text, s, end, e, ns, ne);
-      if (ns == ne) continue;
+      if (ns == ne || F::header(text, ns, ne)) continue;
       if (g < 0) {   // last segment starting at or before s
         int lo = 0, hi = nseg - 1;
         while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (s_start[mid] <= s) lo = mid; else hi = mid - 1; }
@@ -340,155 +376,16 @@ __global__ __launch_bounds__(kThreads) void k_parse_genome_samples(const unsigne
       while (g + 1 < nseg && s_start[g + 1] <= s) ++g;
       const GenomeSeg& G = segs[g];
       if (G.slot < 0) continue;
-      long long q = ne, pos = 0;
-      bool ok = extract_i32(text, q, e, pos);
-      if (pos < 1) continue;
+      typename F::Line L;
+      if (!F::counted(text, ne, e, L)) continue;
       if (g != cseg) { flush(); cseg = g; }
-      ++lines;
-      if (segB == g && pos <= lastB) bad = true;
-      if (segA < 0) { segA = g; firstA = pos; }
-      segB = g; lastB = pos;
-      if (pos >= G.n) { ++beyond; continue; }
-      int32_t* out = G.depth + (pos - 1);
-      const long long stride = genome_sample_stride(G.n);
-      // Column c is what its own extraction gives (the clamped bound included) while every extraction before it succeeded,
-      // 0 after a failed one.  (pos < n here, so pos did not overflow and ok holds.)
-      long long v = 0;
-      int c = 1;                       // the next depth column to extract
-      for (int i = 0; i < ncol; ++i) {
-        const int want = s_col[i];
-        while (c <= want) { v = 0; if (ok) ok = extract_i32(text, q, e, v); ++c; }
-        out[(long long)s_j[i] * stride] = (int32_t)v;
-      }
-      ++stored;
-    }
-  }
-  s_segA[threadIdx.x] = segA; s_segB[threadIdx.x] = segB;
-  s_firstA[threadIdx.x] = firstA; s_lastB[threadIdx.x] = lastB;
-  if (cseg >= 0 && (lines | bad)) { atomicMin(&s_lo, cseg); atomicMax(&s_hi, cseg); }
-  __syncthreads();
-  if (threadIdx.x == 0) {   // the threads in order: a counted line must lie beyond the previous one of its segment
-    int run_seg = -1, wseg = -1;
-    long long run_last = -1, wfirst = -1;
-    for (int t = 0; t < kThreads; ++t) {
-      if (s_segA[t] < 0) continue;
-      if (wseg < 0) { wseg = s_segA[t]; wfirst = s_firstA[t]; }
-      if (s_segA[t] == run_seg && s_firstA[t] <= run_last) atomicOr(&slots[segs[run_seg].slot].unsorted, 1u);
-      run_seg = s_segB[t]; run_last = s_lastB[t];
-    }
-    long long* r = wg + 4 * (long long)blockIdx.x;
-    r[0] = wseg; r[1] = wfirst; r[2] = run_seg; r[3] = run_last;
-  }
-  if (s_lo == s_hi) {   // every thread's remaining counts are one segment's: one set of atomics for the workgroup
-    const bool mine = cseg == s_lo && (lines | bad);
-    unsigned l = mine ? lines : 0, st = mine ? stored : 0, bd = mine ? beyond : 0, bb = mine && bad ? 1u : 0u;
-    for (int d = 32; d >= 1; d >>= 1) { l += __shfl_xor(l, d); st += __shfl_xor(st, d); bd += __shfl_xor(bd, d); bb |= __shfl_xor(bb, d); }
-    __shared__ unsigned s_tot[kThreads / 64][4];
-    if ((threadIdx.x & 63) == 0) { s_tot[threadIdx.x >> 6][0] = l; s_tot[threadIdx.x >> 6][1] = st; s_tot[threadIdx.x >> 6][2] = bd; s_tot[threadIdx.x >> 6][3] = bb; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      unsigned long long t0 = 0, t1 = 0, t2 = 0; unsigned t3 = 0;
-      for (int w = 0; w < kThreads / 64; ++w) { t0 += s_tot[w][0]; t1 += s_tot[w][1]; t2 += s_tot[w][2]; t3 |= s_tot[w][3]; }
-      GenomeSlotStats* S = &slots[segs[s_lo].slot];
-      if (t0) atomicAdd(&S->lines, t0);
-      if (t1) atomicAdd(&S->stored, t1);
-      if (t2) atomicAdd(&S->beyond, t2);
-      if (t3) atomicOr(&S->unsorted, 1u);
-    }
-  } else {
-    flush();
-  }
-}
-
-// bedGraph files: k_parse_genome_text's line walk, segment lookup and order proof, over intervals.  A line
-// "NAME start end d" stands for "NAME p d", p = start + 1 .. end; with a = max(start, 0) and b = end its counted positions are
-// a + 1 .. b: lines += b - a, those >= n are beyond, the others are stored at indices [a, min(b, n - 1)).  The proof is the
-// text one with first = a + 1 and last = b per line.  One line may stand for 2^31 positions, so the counters are 64-bit.
-// Writes: a run of at most kBedInline bases is written by the thread that parsed it, a longer one goes to the run list in
-// pieces of at most kBedPiece bases that k_bedgraph_fill writes, one workgroup per piece.  d == 0 writes nothing: the buffer
-// was cleared when the chromosome opened and, once the order proof holds, no base is written twice (a chromosome whose proof
-// fails, or whose pieces do not fit the list, is rebuilt on the host from a cleared buffer).
-constexpr int kBedInline = 128;
-
-__global__ __launch_bounds__(kThreads) void k_parse_genome_bedgraph(const unsigned char* __restrict__ text, long long begin, long long end,
-                                                                    const GenomeSeg* __restrict__ segs, int nseg,
-                                                                    GenomeSlotStats* __restrict__ slots, long long* __restrict__ wg,
-                                                                    BedRun* __restrict__ runs, unsigned long long* __restrict__ nruns,
-                                                                    unsigned int run_cap) {
-  __shared__ long long s_start[kMaxGenomeSegs];
-  __shared__ int s_segA[kThreads], s_segB[kThreads];
-  __shared__ long long s_firstA[kThreads], s_lastB[kThreads];
-  __shared__ int s_lo, s_hi;
-  for (int i = threadIdx.x; i < nseg; i += kThreads) s_start[i] = segs[i].start;
-  if (threadIdx.x == 0) { s_lo = 0x7fffffff; s_hi = -1; }
-  __syncthreads();
-  const long long b0 = begin + ((long long)blockIdx.x * kThreads + threadIdx.x) * kSpan;
-  int segA = -1, segB = -1;            // segments of the thread's first / last counted line
-  long long firstA = -1, lastB = -1;   // the first position of the one, the last of the other
-  int cseg = -1;                       // segment the counters below belong to
-  unsigned long long lines = 0, stored = 0, beyond = 0;
-  bool bad = false;
-  auto flush = [&]() {
-    if (cseg >= 0 && (lines || bad)) {
-      GenomeSlotStats* S = &slots[segs[cseg].slot];
-      if (lines) atomicAdd(&S->lines, lines);
-      if (stored) atomicAdd(&S->stored, stored);
-      if (beyond) atomicAdd(&S->beyond, beyond);
-      if (bad) atomicOr(&S->unsorted, 1u);
-    }
-    lines = stored = beyond = 0; bad = false;
-  };
-  if (b0 < end) {
-    const long long b1 = b0 + kSpan < end ? b0 + kSpan : end;
-    int g = -1;
-    for (long long s = b0; s < b1; ++s) {
-      if (s != 0 && text[s - 1] != '\n') continue;
-      long long e, ns, ne;
-      line_name(text, s, end, e, ns, ne);
-      if (ns == ne || is_word(text, ns, ne, "track", 5) || is_word(text, ns, ne, "browser", 7)) continue;
-      if (g < 0) {   // last segment starting at or before s
-        int lo = 0, hi = nseg - 1;
-        while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (s_start[mid] <= s) lo = mid; else hi = mid - 1; }
-        g = lo;
-      }
-      while (g + 1 < nseg && s_start[g + 1] <= s) ++g;
-      const GenomeSeg& G = segs[g];
-      if (G.slot < 0) continue;
-      long long q = ne, start = 0, stop = 0, d = 0;
-      if (!extract_i64(text, q, e, start) || !extract_i64(text, q, e, stop)) continue;   // overflow included: no line
-      extract_i32(text, q, e, d);
-      const long long a = start > 0 ? start : 0, b = stop;
-      if (b <= a) continue;            // no position >= 1
-      if (g != cseg) { flush(); cseg = g; }
-      lines += (unsigned long long)(b - a);
-      if (segB == g && a + 1 <= lastB) bad = true;
-      if (segA < 0) { segA = g; firstA = a + 1; }
-      segB = g; lastB = b;
-      const long long edge = G.n - 1;  // positions >= n: beyond; the last base is never set
-      if (b > (a > edge ? a : edge)) beyond += (unsigned long long)(b - (a > edge ? a : edge));
-      const long long hi = b < edge ? b : edge;
-      if (hi <= a) continue;
-      stored += (unsigned long long)(hi - a);
-      if (d == 0) continue;
-      const int32_t v = (int32_t)d;
-      if (hi - a <= kBedInline) {
-        for (long long i = a; i < hi; ++i) G.depth[i] = v;
-        continue;
-      }
-      const long long np = (hi - a + kBedPiece - 1) / kBedPiece;   // <= 2^31 / kBedPiece
-      const unsigned long long k = atomicAdd(nruns, (unsigned long long)np);
-      if (k + (unsigned long long)np > run_cap) {
-        // No room: the chromosome goes to the host loop.  The entries of [k, k + np) below run_cap are this thread's alone
-        // (the reservations are disjoint) and k_bedgraph_fill reads every entry below min(*nruns, run_cap), so each of them
-        // gets an empty piece: the fill never sees an entry nobody wrote in this launch.
-        bad = true;
-        for (unsigned long long r = k; r < run_cap && r < k + (unsigned long long)np; ++r) runs[r] = BedRun{nullptr, 0u, 0};
-        continue;
-      }
-      for (long long j = 0; j < np; ++j) {
-        const long long p0 = a + j * kBedPiece, len = hi - p0 < kBedPiece ? hi - p0 : kBedPiece;
-        runs[k + (unsigned long long)j] = BedRun{G.depth + p0, (uint32_t)len, v};
-      }
+      const Count n = (Count)(L.last - L.first + 1);
+      lines += n;
+      if (segB == g && L.first <= lastB) bad = true;
+      if (segA < 0) { segA = g; firstA = L.first; }
+      segB = g; lastB = L.last;
+      const Count st = F::store(text, e, G, L, args, s_fmt, bad);
+      stored += st; beyond += n - st;
     }
   }
   s_segA[threadIdx.x] = segA; s_segB[threadIdx.x] = segB;
@@ -509,10 +406,10 @@ __global__ __launch_bounds__(kThreads) void k_parse_genome_bedgraph(const unsign
   }
   if (s_lo == s_hi) {   // every thread's remaining counts are one segment's: one set of atomics for the workgroup
     const bool mine = cseg == s_lo && (lines || bad);
-    unsigned long long l = mine ? lines : 0, st = mine ? stored : 0, bd = mine ? beyond : 0;
+    Count l = mine ? lines : 0, st = mine ? stored : 0, bd = mine ? beyond : 0;
     unsigned bb = mine && bad ? 1u : 0u;
     for (int d = 32; d >= 1; d >>= 1) { l += __shfl_xor(l, d); st += __shfl_xor(st, d); bd += __shfl_xor(bd, d); bb |= __shfl_xor(bb, d); }
-    __shared__ unsigned long long s_tot[kThreads / 64][3];
+    __shared__ Count s_tot[kThreads / 64][3];
     __shared__ unsigned s_bad[kThreads / 64];
     if ((threadIdx.x & 63) == 0) { s_tot[threadIdx.x >> 6][0] = l; s_tot[threadIdx.x >> 6][1] = st; s_tot[threadIdx.x >> 6][2] = bd; s_bad[threadIdx.x >> 6] = bb; }
     __syncthreads();
@@ -557,30 +454,29 @@ __global__ __launch_bounds__(kThreads) void k_bedgraph_fill(const BedRun* __rest
 
 }  // namespace
 
-int genome_parse_workgroups(long long nbytes) { return (int)((nbytes + kTile - 1) / kTile); }
-int genome_sample_parse_workgroups(long long nbytes) { return (int)((nbytes + kSampleTile - 1) / kSampleTile); }
-
-void launch_parse_genome_samples(const void* text, long long begin, long long end, const GenomeSeg* segs, int nseg,
-                                 const GenomeSampleCols& cols, GenomeSlotStats* slots, long long* wg, hipStream_t stream) {
-  const int grid = genome_sample_parse_workgroups(end - begin);
-  if (grid <= 0 || nseg <= 0 || cols.n <= 0) return;
-  RSI_LAUNCH(k_parse_genome_samples, dim3(grid), dim3(kThreads), 0, stream, static_cast<const unsigned char*>(text), begin, end, segs,
-             nseg, cols, slots, wg);
-  RSI_LAUNCH(k_genome_order_fold, dim3(1), dim3(kThreads), 0, stream, wg, grid, segs, slots);
+int genome_parse_workgroups(GenomeFormat format, long long nbytes) {
+  const long long tile = (long long)kThreads * (format == GenomeFormat::kSamples ? SampleLines::kSpan : kSpan);
+  return (int)((nbytes + tile - 1) / tile);
 }
 
 unsigned long long bedgraph_run_cap(long long text_bytes, long long sum_len) {
   return (unsigned long long)(text_bytes / 8 + 2 + sum_len / kBedPiece);
 }
 
-void launch_parse_genome_bedgraph(const void* text, long long begin, long long end, const GenomeSeg* segs, int nseg, GenomeSlotStats* slots,
-                                  long long* wg, BedRun* runs, unsigned long long* nruns, unsigned int run_cap, hipStream_t stream) {
-  const int grid = genome_parse_workgroups(end - begin);
-  if (grid <= 0 || nseg <= 0) return;
-  RSI_LAUNCH(k_parse_genome_bedgraph, dim3(grid), dim3(kThreads), 0, stream, static_cast<const unsigned char*>(text), begin, end, segs,
-             nseg, slots, wg, runs, nruns, run_cap);
+void launch_parse_genome(GenomeFormat format, const void* text, long long begin, long long end, const GenomeSeg* segs, int nseg,
+                         GenomeSlotStats* slots, long long* wg, const GenomeSampleCols* cols, BedRun* runs, unsigned long long* nruns,
+                         unsigned int run_cap, hipStream_t stream) {
+  const int grid = genome_parse_workgroups(format, end - begin);
+  if (grid <= 0 || nseg <= 0 || (format == GenomeFormat::kSamples && cols->n <= 0)) return;
+  const unsigned char* t = static_cast<const unsigned char*>(text);
+  const BedLines::Args bed{runs, nruns, run_cap};
+  switch (format) {
+    case GenomeFormat::kText: RSI_LAUNCH(k_parse_genome<TextLines>, dim3(grid), dim3(kThreads), 0, stream, t, begin, end, segs, nseg, slots, wg, TextLines::Args()); break;
+    case GenomeFormat::kSamples: RSI_LAUNCH(k_parse_genome<SampleLines>, dim3(grid), dim3(kThreads), 0, stream, t, begin, end, segs, nseg, slots, wg, *cols); break;
+    case GenomeFormat::kBedgraph: RSI_LAUNCH(k_parse_genome<BedLines>, dim3(grid), dim3(kThreads), 0, stream, t, begin, end, segs, nseg, slots, wg, bed); break;
+  }
   RSI_LAUNCH(k_genome_order_fold, dim3(1), dim3(kThreads), 0, stream, wg, grid, segs, slots);
-  RSI_LAUNCH(k_bedgraph_fill, dim3(kBedFillGrid), dim3(kThreads), 0, stream, runs, nruns, run_cap);
+  if (format == GenomeFormat::kBedgraph) RSI_LAUNCH(k_bedgraph_fill, dim3(kBedFillGrid), dim3(kThreads), 0, stream, runs, nruns, run_cap);
 }
 
 void launch_text_name_bounds(const void* text, long long nbytes, NameBound* bounds, unsigned int* count, unsigned int cap, hipStream_t stream,
@@ -589,15 +485,6 @@ void launch_text_name_bounds(const void* text, long long nbytes, NameBound* boun
   if (grid <= 0) return;
   if (bedgraph) RSI_LAUNCH(k_text_name_bounds<true>, dim3(grid), dim3(kThreads), 0, stream, static_cast<const unsigned char*>(text), nbytes, bounds, count, cap);
   else RSI_LAUNCH(k_text_name_bounds<false>, dim3(grid), dim3(kThreads), 0, stream, static_cast<const unsigned char*>(text), nbytes, bounds, count, cap);
-}
-
-void launch_parse_genome_text(const void* text, long long begin, long long end, const GenomeSeg* segs, int nseg, GenomeSlotStats* slots,
-                              long long* wg, hipStream_t stream) {
-  const int grid = genome_parse_workgroups(end - begin);
-  if (grid <= 0 || nseg <= 0) return;
-  RSI_LAUNCH(k_parse_genome_text, dim3(grid), dim3(kThreads), 0, stream, static_cast<const unsigned char*>(text), begin, end, segs, nseg,
-             slots, wg);
-  RSI_LAUNCH(k_genome_order_fold, dim3(1), dim3(kThreads), 0, stream, wg, grid, segs, slots);
 }
 
 int text_parse_workgroups(long long nbytes) { return (int)((nbytes + kTile - 1) / kTile); }

@@ -269,6 +269,48 @@ def test_bedgraph_equals_expanded_file(case_files, form, chunk):
 
 
 @pytest.mark.gpu
+@pytest.mark.timeout(300)
+def test_bedgraph_hundreds_of_tiny_contigs(tmp_path):
+    """600 contigs of 100-600 bases, more than one parse launch's segment table holds (kMaxGenomeSegs = 512): a workgroup's
+    8 KB of text covers some twenty contigs and a thread's 32 bytes cross from one into the next, so the counts leave per
+    thread and the default chunk takes two parse launches.  Runs of 1-40 bases, in every fifth contig one of 129-400 (the
+    run list beside the inline writes), every third contig with the quirks of quirk_lines."""
+    rng = np.random.default_rng(0xB1D)
+    lines, names, lens = ["track type=bedGraph name=tiny"], [], []
+    for i in range(600):
+        n = int(rng.integers(100, 601))
+        while i % 5 == 0 and n < 420:                            # room for the long run in front of quirk_lines' n - 11
+            n = int(rng.integers(100, 601))
+        quirks = i % 3 == 0
+        d = np.zeros(n - 11 if quirks else n, dtype=np.int32)
+        p = 0
+        while p < d.size:
+            ln = int(rng.integers(1, 41))
+            d[p:p + ln] = int(rng.integers(0, 90))
+            p += ln
+        if i % 5 == 0:
+            ln = int(rng.integers(129, 401))
+            a = int(rng.integers(1, d.size - ln))
+            d[a:a + ln] = 200 + i % 50                           # no neighbour has this depth: one run of ln bases
+            assert (a, a + ln, 200 + i % 50) in runs_of(d, 0, d.size)
+        name = f"ctg{i:04d}"
+        names.append(name); lens.append(n)
+        lines += quirk_lines(name, d, 0xB1D + i) if quirks else [f"{name}\t{a}\t{b}\t{v}" for a, b, v in runs_of(d, 0, d.size)]
+        if i % 17 == 0:
+            lines.append("")
+    text = "\n".join(lines) + "\n"
+    assert len(text) < 1_000_000
+    (tmp_path / "tiny.bed").write_text(text)
+    (tmp_path / "tiny.depth").write_text(expand(text))
+    ref = genome_of(tmp_path / "tiny.depth", names, lens)
+    assert list(ref) == names
+    for kw in ({}, dict(chunk_bytes=4097, max_resident=2)):
+        got = genome_of(tmp_path / "tiny.bed", names, lens, bedgraph=True, **kw)
+        check_equal(got, ref, kw)
+        assert list(got) == names and all(got[nm][1]["fallback"] == 0 for nm in names), kw
+
+
+@pytest.mark.gpu
 @pytest.mark.timeout(900)
 def test_bedgraph_long_runs(tmp_path):
     """A 201 Mb chromosome that is one zero run but for a few long runs that start and end off 16-byte boundaries (and runs

@@ -261,6 +261,31 @@ int rsi_hot_run_bam(rsi_ctx* ctx, const rsi_params* p, const char* bam_path, con
 int rsi_hot_run_device(rsi_ctx* ctx, const rsi_params* p, const void* d_depth, const void* d_fasta, int64_t n,
                        rsi_result** out);
 
+/* ---- Excluded regions: a mask applied on the device ---------------------------------------------------------------------
+ * An excluded base behaves exactly like an N of the reference sequence: it is not GC, its run is padded by max(50, m/4) and
+ * merged with its neighbours (get_noseq_regions, loaddata.cpp:243-273), removed before binning and re-inserted when the calls
+ * are mapped back -- a run with mask M on sequence F gives what a run without a mask gives on F with M's bases replaced by
+ * 'N'.  The sequence itself is not touched (it is const host memory, or the caller's HBM): a kernel behind the classification
+ * edits the two bit planes everything else reads.  The mask's runs count like the sequence's own: more than 128 padded regions
+ * take the general compaction kernel, more than 512 runs leave region building to the host, more than 4096 padded regions
+ * are RSI_ERR_UNSUPPORTED.
+ * rsi_hot_set_exclude: `count` intervals, 0-based half-open [start[i], end[i]), in any order, overlapping or not; end <= start is
+ * ignored, a negative start counts as 0; the library sorts and merges them and clips them to the run's n.  The mask arms the
+ * NEXT run on this context only -- rsi_hot_run, _run_text, _run_bam, _run_device or _run_depth_device -- which consumes it whether
+ * it succeeds or fails (a context serves one chromosome after another: a mask that stayed would land on the wrong one).
+ * count == 0 disarms (the arrays may then be NULL); count < 0, or count > 0 with a NULL array, is RSI_ERR_BAD_ARG.  The pool's
+ * entry points (rsi_pool_run / _run_host / _submit) take no mask; arming a pool worker's context while pool runs are queued is
+ * the caller's error. */
+int rsi_hot_set_exclude(rsi_ctx* ctx, const int64_t* start, const int64_t* end, int count);
+/* The intervals a BED file holds for `chrom` (length n), normalised: sorted, merged (touching ones too), end clipped to n.  Host
+ * only.  Returns their number -- also when cap is too small or the arrays are NULL, as rsi_bam_references does -- and writes the
+ * first min(number, cap).  Fields are separated by tabs or blanks, the first three count; empty lines, '#' lines and "track" /
+ * "browser" lines are skipped; the file is read through zlib (plain text or gzip).  A name matches `chrom` when they are equal or
+ * differ by a leading "chr" in either direction.  Every other line must be well formed whichever sequence it names: fewer than
+ * three fields, a coordinate that is not a non-negative integer, or end <= start is RSI_ERR_BAD_ARG, with the line number in
+ * rsi_hot_last_error(NULL). */
+int rsi_exclude_read_bed(const char* path, const char* chrom, int64_t n, int64_t* start, int64_t* end, int cap);
+
 /* Results.  which: 0 = calls after sd_filters (what write_cnv_to_file prints),
  *                  1 = detectcnv output before sd_filters,
  *                  2 = bin-space segments after the scan (rsicnvnbn / rsicnvmed output),
@@ -308,6 +333,12 @@ int rsi_hot_debug_grid_median(rsi_ctx* ctx, const float* x, const int32_t* mask,
 /* Mode 3 of the same hook, -MED's form: the int32 bin medians x[nb] become floats in the kernel that also plans the MAD's grid
  * around `center`, then the MAD's chain. */
 int rsi_hot_debug_grid_mad_i32(rsi_ctx* ctx, const int32_t* x, int64_t nb, double center, double* out, int32_t* info);
+
+/* Test hook: the classification alone, at any length: fasta[n] is uploaded and classified (K1), the intervals -- taken as
+ * rsi_hot_set_exclude takes them -- are applied by the mask kernel when count > 0, and the two planes come back: n/64 + 1 words
+ * each, bit j of word w for base 64 w + j, zero beyond n.  Neither arms nor consumes the context's mask. */
+int rsi_hot_debug_classify(rsi_ctx* ctx, const uint8_t* fasta, int64_t n, const int64_t* start, const int64_t* end, int count,
+                           uint64_t* gcbits, uint64_t* nbits);
 
 /* Timing hooks for bench.py: per-kernel HIP-event times (ms) of the last run, by kernel name.
  * names/ms receive up to cap entries; returns the number of timed launches. */

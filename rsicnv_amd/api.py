@@ -34,7 +34,8 @@ EXPORTS = ["rsi_default_params", "rsi_hot_create", "rsi_hot_destroy", "rsi_hot_l
            "rsi_hot_last_inflate_stats", "rsi_hot_inflate_bgzf", "rsi_genome_text_inflate_stats",
            "rsi_synth_append_genome_bgzf", "rsi_genome_text_open_samples", "rsi_genome_text_samples", "rsi_genome_text_max_resident",
            "rsi_genome_text_sample_depth", "rsi_genome_text_copy_sample_depth", "rsi_synth_append_genome_samples",
-           "rsi_genome_bedgraph_open", "rsi_synth_append_genome_bedgraph"]
+           "rsi_genome_bedgraph_open", "rsi_synth_append_genome_bedgraph",
+           "rsi_hot_set_exclude", "rsi_exclude_read_bed", "rsi_hot_debug_classify"]
 
 
 class RsiParams(C.Structure):
@@ -210,6 +211,9 @@ def load_library():
     L.rsi_hot_last_inflate_stats.argtypes = [C.c_void_p, C.POINTER(RsiInflateStats)]
     L.rsi_hot_inflate_bgzf.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(RsiInflateStats)]
     L.rsi_hot_inflate_bgzf.restype = C.c_int64
+    L.rsi_hot_set_exclude.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    L.rsi_exclude_read_bed.argtypes = [C.c_char_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int]
+    L.rsi_hot_debug_classify.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -221,6 +225,28 @@ def make_params(m=101, gcadjust=1, trans=0, merge=1, maxchkbp=100000, debug=0, c
     if m % 2 != 1:
         m += 1
     return RsiParams(m, gcadjust, trans, merge, maxchkbp, debug, cap, epsilon, threshold, chklen, minmlen, buffer, p)
+
+
+def _interval_arrays(exclude):
+    """An (k, 2) array or a list of (start, end) pairs -> two contiguous int64 arrays."""
+    iv = np.asarray(exclude, dtype=np.int64).reshape(-1, 2)
+    return np.ascontiguousarray(iv[:, 0]), np.ascontiguousarray(iv[:, 1])
+
+
+def read_exclude_bed(path, chrom, n):
+    """The intervals a BED file (plain or gzip) holds for `chrom` of length n, sorted, merged and clipped to n: an (k, 2) int64
+    array of 0-based half-open (start, end) pairs (rsi_exclude_read_bed; host only).  A malformed line raises RsiError."""
+    lib = load_library()
+    k = lib.rsi_exclude_read_bed(os.fsencode(path), chrom.encode(), int(n), None, None, 0)
+    if k < 0:
+        raise RsiError(k, lib.rsi_hot_last_error(None).decode())
+    s = np.zeros(max(k, 1), dtype=np.int64)
+    e = np.zeros(max(k, 1), dtype=np.int64)
+    k2 = lib.rsi_exclude_read_bed(os.fsencode(path), chrom.encode(), int(n), s.ctypes.data, e.ctypes.data, k)
+    if k2 < 0:
+        raise RsiError(k2, lib.rsi_hot_last_error(None).decode())
+    k = min(k, k2)
+    return np.stack([s[:k], e[:k]], axis=1)
 
 
 class RsiError(RuntimeError):
@@ -381,13 +407,39 @@ class RsiHot:
                                                        self.GRID_MODES[mode], float(center), out.ctypes.data, info.ctypes.data))
         return out, info
 
-    def run(self, params, depth, fasta):
-        """depth: int32[n] raw per-base depth, fasta: uint8[n] sequence bytes (host arrays)."""
+    def set_exclude(self, exclude):
+        """Arm the NEXT run on this context with excluded intervals: an (k, 2) integer array or a list of (start, end) pairs,
+        0-based half-open, any order; their bases are treated as N (rsi_hot_set_exclude).  None or an empty list disarms."""
+        if exclude is None or len(exclude) == 0:
+            self._check(self.lib.rsi_hot_set_exclude(self.ctx, None, None, 0))
+            return
+        s, e = _interval_arrays(exclude)
+        self._check(self.lib.rsi_hot_set_exclude(self.ctx, s.ctypes.data, e.ctypes.data, s.size))
+
+    def debug_classify(self, fasta, exclude=None):
+        """The GC and N bit planes of a host sequence after the classification kernel and, with `exclude`, the mask kernel (test
+        hook): (gcbits, nbits), uint64[n // 64 + 1] each, bit j of word w for base 64 w + j."""
+        f = np.ascontiguousarray(fasta, dtype=np.uint8)
+        gc = np.zeros(f.size // 64 + 1, dtype=np.uint64)
+        nb = np.zeros(f.size // 64 + 1, dtype=np.uint64)
+        if exclude is None or len(exclude) == 0:
+            rc = self.lib.rsi_hot_debug_classify(self.ctx, f.ctypes.data, f.size, None, None, 0, gc.ctypes.data, nb.ctypes.data)
+        else:
+            s, e = _interval_arrays(exclude)
+            rc = self.lib.rsi_hot_debug_classify(self.ctx, f.ctypes.data, f.size, s.ctypes.data, e.ctypes.data, s.size, gc.ctypes.data, nb.ctypes.data)
+        self._check(rc)
+        return gc, nb
+
+    def run(self, params, depth, fasta, exclude=None):
+        """depth: int32[n] raw per-base depth, fasta: uint8[n] sequence bytes (host arrays); exclude: intervals treated as N
+        in this run (set_exclude)."""
         d = np.ascontiguousarray(depth, dtype=np.int32)
         f = np.ascontiguousarray(fasta, dtype=np.uint8)
         if d.shape != f.shape or d.ndim != 1:
             raise ValueError("depth and fasta must be 1-D arrays of the same length")
         out = C.c_void_p()
+        if exclude is not None:
+            self.set_exclude(exclude)
         self._check(self.lib.rsi_hot_run(self.ctx, C.byref(params), d.ctypes.data, f.ctypes.data, d.size, C.byref(out)))
         return Result(self.lib, out)
 
@@ -437,9 +489,11 @@ class RsiHot:
         self._check(self.lib.rsi_hot_last_inflate_stats(self.ctx, C.byref(st)))
         return _inflate_dict(st)
 
-    def run_text(self, params, path, fasta):
-        """Depth from a text file (parsed on the device), fasta: uint8[n] host array."""
+    def run_text(self, params, path, fasta, exclude=None):
+        """Depth from a text file (parsed on the device), fasta: uint8[n] host array; exclude: as for run."""
         f = np.ascontiguousarray(fasta, dtype=np.uint8)
+        if exclude is not None:
+            self.set_exclude(exclude)
         out = C.c_void_p()
         st = RsiTextStats()
         self._check(self.lib.rsi_hot_run_text(self.ctx, C.byref(params), os.fsencode(path), f.ctypes.data, f.size, C.byref(out), C.byref(st)))
@@ -453,8 +507,10 @@ class RsiHot:
         self._check(self.lib.rsi_hot_load_depth_bam(self.ctx, os.fsencode(bam), chrom.encode(), int(minq), int(min_baseq), C.byref(st)))
         return {f[0]: getattr(st, f[0]) for f in RsiBamStats._fields_}
 
-    def run_bam(self, params, bam, chrom, fasta, minq=0, min_baseq=13):
+    def run_bam(self, params, bam, chrom, fasta, minq=0, min_baseq=13, exclude=None):
         f = np.ascontiguousarray(fasta, dtype=np.uint8)
+        if exclude is not None:
+            self.set_exclude(exclude)
         out = C.c_void_p()
         st = RsiBamStats()
         self._check(self.lib.rsi_hot_run_bam(self.ctx, C.byref(params), os.fsencode(bam), chrom.encode(), int(minq), int(min_baseq),
@@ -463,9 +519,11 @@ class RsiHot:
         res.bam_stats = {f_[0]: getattr(st, f_[0]) for f_ in RsiBamStats._fields_}
         return res
 
-    def run_device(self, params, d_depth_ptr, d_fasta_ptr, n):
-        """Inputs already in HBM (raw device pointers, 16-byte aligned)."""
+    def run_device(self, params, d_depth_ptr, d_fasta_ptr, n, exclude=None):
+        """Inputs already in HBM (raw device pointers, 16-byte aligned); exclude: as for run."""
         out = C.c_void_p()
+        if exclude is not None:
+            self.set_exclude(exclude)
         self._check(self.lib.rsi_hot_run_device(self.ctx, C.byref(params), C.c_void_p(d_depth_ptr), C.c_void_p(d_fasta_ptr),
                                                 n, C.byref(out)))
         return Result(self.lib, out)

@@ -46,6 +46,7 @@ struct Options {
   std::string samples;   // -samples all|k1,k2,...: the depth columns of a cohort file to call (without: the first one, as always)
   bool samples_given = false, chr_given = false;
   std::string dformat;   // -dformat depth|bedgraph: the -d file's format (without: from its name, is_bedgraph_name)
+  std::string excludefile;   // -x FILE: BED file of regions left out of calling, treated as N of the reference
 };
 
 int usage() {
@@ -69,6 +70,7 @@ int usage() {
             << "   -workers INT chromosomes in flight (with -gpus; and on -gpu for a whole-genome depth file), default=4\n"
             << "   -samples all|k1,k2,... call depth columns k of RNAME POS D1 ... DK (1-based, at most 64) as samples: OUT.k each\n"
             << "   -dformat depth|bedgraph  read -d as per-base lines or as bedGraph (default: from the file name, see below)\n"
+            << "   -x   FILE exclude the regions of a BED file (plain or gzip) from calling, see below\n"
             << "\nNote:\n"
             << "   This build runs the read-depth hot path on an MI355X; input is a read depth file\n"
             << "   (samtools mpileup BAM | cut -f2,4) with -c RNAME, a whole-genome depth file without -c\n"
@@ -83,6 +85,13 @@ int usage() {
             << "   per-base.bed.gz, bedtools genomecov -bg / -bga; track and browser lines skipped), read as the per-base\n"
             << "   lines RNAME POS DEPTH, POS = START+1 .. END, that it stands for.  Without -c every chromosome is called;\n"
             << "   -c RNAME calls that chromosome's lines alone.\n"
+            << "   -x FILE: the bases of the BED file's intervals (CHROM START END, 0-based half-open, tabs or blanks, any order,\n"
+            << "   overlaps allowed; #, track, browser and empty lines skipped; any other malformed line is an error) are\n"
+            << "   treated as N of the reference: not GC, padded by max(50, m/4) and merged like N runs, removed before binning.\n"
+            << "   Names match with or without a leading chr; names of no processed chromosome are ignored.  Works with every\n"
+            << "   input (-d with -c, whole-genome -d, -samples, bedGraph, -b, -gpus).  A mask adds to the chromosome's N regions,\n"
+            << "   so their limits apply: above 128 merged regions the general compaction kernel runs instead of the streaming\n"
+            << "   one, above 512 runs the regions are built on the host, above 4096 merged regions the chromosome is refused.\n"
             << std::endl;
   return 0;
 }
@@ -135,6 +144,7 @@ void parse(int argc, char** argv, Options& o) {
     else if (s == "-workers") { o.workers = atoi(need(i).c_str()); ++i; }
     else if (s == "-samples") { o.samples = need(i); o.samples_given = true; ++i; }
     else if (s == "-dformat") { o.dformat = need(i); ++i; }
+    else if (s == "-x") { o.excludefile = need(i); ++i; }
     else { std::cerr << "unknown option " << s << std::endl; exit(usage()); }
   }
   if (o.rdfile.empty() && o.bamfile.empty()) { std::cerr << "need input file " << std::endl; exit(usage()); }
@@ -198,6 +208,23 @@ std::string inflate_line(const rsi_inflate_stats& s) {
 void report_chromosome(rsi_ctx* ctx, const Options& o, const std::string& chr, rsi_result* res, const rsi_text_stats* ts,
                        const rsi_bam_stats* bs, double t_fasta, double t_path, std::ostringstream& info, ChromOutput& co);
 
+// -x FILE: the BED file's intervals on `chr` (n bases) arm the context for the run that follows (the mask is spent by that run);
+// one log line.  false: the file could not be read (the message is in the log line).
+bool arm_exclude(rsi_ctx* ctx, const Options& o, const std::string& chr, int64_t n, std::ostringstream& info) {
+  if (o.excludefile.empty()) return true;
+  int k = rsi_exclude_read_bed(o.excludefile.c_str(), chr.c_str(), n, nullptr, nullptr, 0);
+  std::vector<int64_t> s((size_t)std::max(k, 1)), e((size_t)std::max(k, 1));
+  if (k > 0) k = std::min(k, rsi_exclude_read_bed(o.excludefile.c_str(), chr.c_str(), n, s.data(), e.data(), k));
+  if (k < 0 || rsi_hot_set_exclude(ctx, s.data(), e.data(), k) != RSI_OK) {
+    info << "#exclude: " << (k < 0 ? rsi_hot_last_error(nullptr) : rsi_hot_last_error(ctx)) << "\n";
+    return false;
+  }
+  int64_t bases = 0;
+  for (int i = 0; i < k; ++i) bases += e[(size_t)i] - s[(size_t)i];
+  info << "#exclude: " << o.excludefile << ", " << k << " intervals, " << bases << " bases on " << chr << "\n";
+  return true;
+}
+
 // One chromosome on one context, first half: FASTA, depth (text or BAM, on the device), the hot path; then report_chromosome.
 void process_chromosome(rsi_ctx* ctx, const Options& o, const std::string& chr, bool many, ChromOutput& co) {
   const bool from_bam = !o.bamfile.empty();
@@ -207,6 +234,7 @@ void process_chromosome(rsi_ctx* ctx, const Options& o, const std::string& chr, 
   std::string fasta;
   if (!read_fasta(o.reffile, chr, fasta)) { co.log = info.str(); co.fatal = !many; return; }
   const double t1 = now_s();
+  if (!arm_exclude(ctx, o, chr, (int64_t)fasta.size(), info)) { co.log = info.str(); co.fatal = true; return; }
 
   rsi_result* res = nullptr;
   rsi_text_stats ts;
@@ -454,9 +482,10 @@ bool run_genome(const Options& o, const std::vector<int32_t>& cols, std::vector<
         info << "#processing " << chr << "\n";
         rsi_result* res = nullptr;
         const double t1 = now_s();
-        const int rc = rsi_hot_run_depth_device(ctx, &o.P, j.d_depth, reinterpret_cast<const uint8_t*>(j.fasta->data()), j.c.n, &res);
+        const bool armed = arm_exclude(ctx, o, chr, j.c.n, info);   // (false: it has logged why)
+        const int rc = !armed ? RSI_ERR_BAD_ARG : rsi_hot_run_depth_device(ctx, &o.P, j.d_depth, reinterpret_cast<const uint8_t*>(j.fasta->data()), j.c.n, &res);
         if (rc != RSI_OK) {   // as the BAM walk: a chromosome that has data and fails stops the run (rsi.cpp exits) -- of its sample
-          info << rsi_hot_last_error(ctx) << "\n";
+          if (armed) info << rsi_hot_last_error(ctx) << "\n";
           co.log = info.str();
           co.fatal = true;
         } else {
@@ -602,6 +631,11 @@ int main(int argc, char** argv) {
       // a file without lines for RNAME is found by the one pass of the reader (run_genome: exit 1, no output); a host pass
       // in front of it would read the text once more, up to RNAME's first line or through the whole file
     }
+  }
+  // -x: a BED file with a bad line is refused as a whole, whichever chromosome the line names, before any output exists
+  if (!o.excludefile.empty() && rsi_exclude_read_bed(o.excludefile.c_str(), "", 0, nullptr, nullptr, 0) < 0) {
+    std::cerr << "rsicnv: -x: " << rsi_hot_last_error(nullptr) << std::endl;
+    return 1;
   }
   std::vector<int32_t> cols;            // -samples: the cohort file's depth columns, and the header's names for them
   std::vector<std::string> sample_names;

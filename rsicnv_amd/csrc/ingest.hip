@@ -563,6 +563,7 @@ int64_t rsi_hot_inflate_bgzf(rsi_ctx* ctx, const uint8_t* comp, int64_t comp_len
 
 int rsi_hot_run_text(rsi_ctx* ctx, const rsi_params* p, const char* depth_path, const uint8_t* fasta, int64_t n, rsi_result** out,
                      rsi_text_stats* stats) {
+  ExcludeOneShot one_shot(ctx);
   if (!ctx || !p || !depth_path || !fasta || !out) return fail(ctx, RSI_ERR_BAD_ARG, "null argument");
   ctx->ktimes.clear(); ctx->event_next = 0;
   int rc = rsi_hot_load_depth_text(ctx, depth_path, n, stats);
@@ -574,6 +575,7 @@ int rsi_hot_run_text(rsi_ctx* ctx, const rsi_params* p, const char* depth_path, 
 }
 
 int rsi_hot_run_depth_device(rsi_ctx* ctx, const rsi_params* p, const void* d_depth, const uint8_t* fasta, int64_t n, rsi_result** out) {
+  ExcludeOneShot one_shot(ctx);
   if (!ctx || !p || !d_depth || !fasta || !out) return fail(ctx, RSI_ERR_BAD_ARG, "null argument");
   if (n <= 0) return fail(ctx, RSI_ERR_BAD_ARG, "empty chromosome");
   if (!ctx_enter(ctx)) return RSI_ERR_HIP;
@@ -791,8 +793,70 @@ int rsi_bam_references(const char* bam_path, char* names, int names_cap, int64_t
   return (int)refs.size();
 }
 
+// Exclusion masks as BED files (include/rsi_hot.h): host only.  Every line that is not blank, a comment or a track / browser
+// line must be a good BED line, whichever sequence it names: a typo in a mask file is reported, never skipped.
+int rsi_exclude_read_bed(const char* path, const char* chrom, int64_t n, int64_t* start, int64_t* end, int cap) {
+  if (!path || !chrom || n < 0) { set_global_error("rsi_exclude_read_bed: bad argument"); return RSI_ERR_BAD_ARG; }
+  gzFile gz = gzopen(path, "rb");
+  if (!gz) { set_global_error(std::string("cannot open the exclusion BED file ") + path); return RSI_ERR_BAD_ARG; }
+  const std::string want(chrom);
+  auto same_name = [&](const std::string& x) {   // read_fasta's rule, in either direction
+    return x == want || "chr" + x == want || x == "chr" + want;
+  };
+  auto coord = [](const std::string& t, long long* v) {   // a whole token of digits that fits a long long
+    if (t.empty() || t.size() > 19) return false;
+    for (char c : t) if (c < '0' || c > '9') return false;
+    errno = 0;
+    *v = strtoll(t.c_str(), nullptr, 10);
+    return errno == 0;
+  };
+  std::vector<std::pair<int64_t, int64_t>> iv;
+  std::string line, bad;
+  std::vector<char> buf(1 << 16);
+  long long lineno = 0;
+  bool more = true;
+  while (more && bad.empty()) {
+    line.clear();
+    bool got = false;
+    for (;;) {   // one line, however long
+      if (!gzgets(gz, buf.data(), (int)buf.size())) { more = false; break; }
+      got = true;
+      line += buf.data();
+      if (!line.empty() && line.back() == '\n') break;
+    }
+    if (!got) break;
+    ++lineno;
+    while (!line.empty() && (line.back() == '\n' || line.back() == '\r')) line.pop_back();
+    std::string tok[3];
+    int nt = 0;
+    for (size_t i = 0; i < line.size() && nt < 3;) {
+      while (i < line.size() && (line[i] == ' ' || line[i] == '\t')) ++i;
+      const size_t b = i;
+      while (i < line.size() && line[i] != ' ' && line[i] != '\t') ++i;
+      if (i > b) tok[nt++] = line.substr(b, i - b);
+    }
+    if (nt == 0 || tok[0][0] == '#' || tok[0] == "track" || tok[0] == "browser") continue;
+    long long a = 0, b = 0;
+    const std::string where = std::string(path) + ": line " + std::to_string(lineno) + ": ";
+    if (nt < 3) bad = where + "fewer than three fields";
+    else if (!coord(tok[1], &a) || !coord(tok[2], &b)) bad = where + "start and end must be non-negative integers";
+    else if (b <= a) bad = where + "end <= start";
+    else if (same_name(tok[0])) iv.push_back({(int64_t)a, (int64_t)b});
+  }
+  int zerr = 0;
+  const char* zmsg = gzerror(gz, &zerr);
+  if (bad.empty() && zerr != Z_OK && zerr != Z_STREAM_END) bad = std::string(path) + ": " + (zmsg ? zmsg : "read error");
+  gzclose(gz);
+  if (!bad.empty()) { set_global_error(bad); return RSI_ERR_BAD_ARG; }
+  normalize_intervals(iv, n);
+  if (iv.size() > (size_t)0x7fffffff) { set_global_error(std::string(path) + ": too many intervals"); return RSI_ERR_UNSUPPORTED; }
+  if (start && end) for (size_t i = 0; i < iv.size() && (int64_t)i < (int64_t)cap; ++i) { start[i] = iv[i].first; end[i] = iv[i].second; }
+  return (int)iv.size();
+}
+
 int rsi_hot_run_bam(rsi_ctx* ctx, const rsi_params* p, const char* bam_path, const char* chrom, int minq, int min_baseq,
                     const uint8_t* fasta, int64_t n, rsi_result** out, rsi_bam_stats* stats) {
+  ExcludeOneShot one_shot(ctx);
   if (!ctx || !p || !bam_path || !chrom || !fasta || !out) return fail(ctx, RSI_ERR_BAD_ARG, "null argument");
   rsi_bam_stats local;
   rsi_bam_stats* st = stats ? stats : &local;

@@ -34,6 +34,11 @@ constexpr int kTileBases = 4096;      // bases per workgroup tile in the streami
 void launch_fasta_classify(const uint8_t* fasta, int64_t n, uint64_t* gcbits, uint64_t* nbits, int64_t nwords,
                            const FillList& fill, hipStream_t stream);
 void launch_fill(const FillList& fill, hipStream_t stream);   // the same clearing as a launch of its own (rare paths)
+// ---- K1x: excluded intervals -> N in both planes (nbits |= bit, gcbits &= ~bit), behind K1 and before anything reads them ----
+// starts / ends: `count` intervals [s, e) in device memory, sorted, disjoint and not touching, all inside [0, n);
+// first_start = starts[0], last_end = ends[count - 1] (host copies: the grid covers the mask's span only).  count <= 0: no launch.
+void launch_exclude_mask(const int64_t* starts, const int64_t* ends, int count, int64_t first_start, int64_t last_end,
+                         uint64_t* gcbits, uint64_t* nbits, hipStream_t stream);
 // Scratch for the in-kernel folds of the per-workgroup slabs (device_util.h, fold_slabs): group sums of the widest slab.
 // counters: kFoldGroups + 1 arrival counters per kernel, zero before the launch (every launch leaves them zero).
 size_t fold_scratch_bytes();

@@ -60,6 +60,54 @@ __global__ __launch_bounds__(kThreads) void k_fasta_classify(const uint8_t* __re
   }
 }
 
+// K1x exclude_mask: the caller's excluded intervals become N in the two planes K1 wrote (nbits |= bit, gcbits &= ~bit), so that
+// everything behind K1 treats them as it treats the sequence's own N runs.  The intervals are [s, e), sorted, disjoint, not
+// touching, inside [0, n).  A workgroup owns a tile of kExTileWords words of the mask's span and serves the intervals that
+// reach into it: a long interval is spread over the workgroups of all its tiles, a tile without an interval costs its two
+// searches.  Each thread takes intervals of the tile: the interval's first and last word, where the tile holds them, by 64-bit
+// atomics (a neighbouring interval may end or begin in the same word), a short interior by plain stores; a long interior goes
+// onto the workgroup's list and is stored by all of its threads.  No state, no counter: launching it twice gives the same planes.
+constexpr int kExTileWords = 1024;   // 65 536 bases: 8 KB of each plane
+constexpr int kExShort = 8;          // interior words one thread stores itself
+constexpr int kExList = kExTileWords / (kExShort + 1) + 2;   // interiors longer than kExShort words that fit one tile
+__global__ __launch_bounds__(kThreads) void k_exclude_mask(const int64_t* __restrict__ starts, const int64_t* __restrict__ ends, int count,
+                                                           int64_t tile0, uint64_t* __restrict__ gcbits, uint64_t* __restrict__ nbits) {
+  __shared__ int64_t s_a[kExList], s_b[kExList];
+  __shared__ int s_n;
+  if (threadIdx.x == 0) s_n = 0;
+  __syncthreads();
+  const int64_t tw0 = (tile0 + blockIdx.x) * kExTileWords, tw1 = tw0 + kExTileWords;
+  // the tile's intervals [lo, hi): the first that ends behind the tile's first base, up to the first that starts at or behind its end
+  int lo = 0, hi = count;
+  for (int b = count; lo < b;) { const int mid = (lo + b) >> 1; if (ends[mid] > tw0 * 64) b = mid; else lo = mid + 1; }
+  for (int a = lo; a < hi;) { const int mid = (a + hi) >> 1; if (starts[mid] >= tw1 * 64) hi = mid; else a = mid + 1; }
+  for (int i = lo + (int)threadIdx.x; i < hi; i += kThreads) {
+    const int64_t s = starts[i], e = ends[i];
+    const int64_t w0 = s >> 6, w1 = (e - 1) >> 6;
+    const uint64_t first = ~0ull << (s & 63), last = ~0ull >> (63 - ((e - 1) & 63));
+    if (w0 == w1) {   // (inside the tile: the interval overlaps it)
+      atomicOr(reinterpret_cast<unsigned long long*>(&nbits[w0]), (unsigned long long)(first & last));
+      atomicAnd(reinterpret_cast<unsigned long long*>(&gcbits[w0]), (unsigned long long)~(first & last));
+      continue;
+    }
+    if (w0 >= tw0) {
+      atomicOr(reinterpret_cast<unsigned long long*>(&nbits[w0]), (unsigned long long)first);
+      atomicAnd(reinterpret_cast<unsigned long long*>(&gcbits[w0]), (unsigned long long)~first);
+    }
+    if (w1 < tw1) {
+      atomicOr(reinterpret_cast<unsigned long long*>(&nbits[w1]), (unsigned long long)last);
+      atomicAnd(reinterpret_cast<unsigned long long*>(&gcbits[w1]), (unsigned long long)~last);
+    }
+    const int64_t a = w0 + 1 > tw0 ? w0 + 1 : tw0, b = w1 < tw1 ? w1 : tw1;   // the interior words in this tile
+    if (b - a > kExShort) { const int k = atomicAdd(&s_n, 1); s_a[k] = a; s_b[k] = b; }
+    else for (int64_t w = a; w < b; ++w) { nbits[w] = ~0ull; gcbits[w] = 0; }
+  }
+  __syncthreads();
+  const int nlist = s_n;
+  for (int k = 0; k < nlist; ++k)
+    for (int64_t w = s_a[k] + threadIdx.x; w < s_b[k]; w += kThreads) { nbits[w] = ~0ull; gcbits[w] = 0; }
+}
+
 // K1b n_transitions: run starts and (exclusive) ends of the N mask.  With `pp` the launch's last workgroup also turns the list
 // into what K4j needs -- the padded, merged regions of get_noseq_regions (loaddata.cpp:243-273) as compacted break points
 // and removed lengths (cbreak / cum) -- so that K4j can be queued behind K2j without the host in between; the host builds
@@ -2712,6 +2760,12 @@ void launch_fasta_classify(const uint8_t* fasta, int64_t n, uint64_t* gcbits, ui
                            const FillList& fill, hipStream_t stream) {
   RSI_LAUNCH(k_fasta_classify, dim3(grid_for(nwords * 4, kThreads)), dim3(kThreads), 0, stream, fasta, n, gcbits,
                      nbits, nwords, fill);
+}
+void launch_exclude_mask(const int64_t* starts, const int64_t* ends, int count, int64_t first_start, int64_t last_end,
+                         uint64_t* gcbits, uint64_t* nbits, hipStream_t stream) {
+  if (count <= 0) return;
+  const int64_t tile0 = (first_start >> 6) / kExTileWords, tile1 = ((last_end - 1) >> 6) / kExTileWords;   // the mask's span in tiles
+  RSI_LAUNCH(k_exclude_mask, dim3((unsigned)(tile1 - tile0 + 1)), dim3(kThreads), 0, stream, starts, ends, count, tile0, gcbits, nbits);
 }
 __global__ __launch_bounds__(kThreads) void k_fill(FillList fill) { fill_ranges(fill); }
 void launch_fill(const FillList& fill, hipStream_t stream) {

@@ -898,6 +898,23 @@ static void issue_k4(rsi_ctx* ctx, const K4Plan& plan, K4Args a) {
   if (plan.route == K4Route::stream) { Timer t(ctx, "bin_median", true); launch_bin_median8(a); }
 }
 
+// K1x behind K1 on the context's stream: `iv` (normalised, rsi_hot_set_exclude) clipped to [0, n), uploaded into the context's
+// interval buffer, then the kernel that turns those bases into N in both planes.  An empty mask launches nothing.
+int issue_exclude_mask(rsi_ctx* ctx, std::vector<std::pair<int64_t, int64_t>> iv, int64_t n) {
+  normalize_intervals(iv, n);
+  if (iv.empty()) return RSI_OK;
+  if (iv.size() > (size_t)0x7fffffff) return fail(ctx, RSI_ERR_UNSUPPORTED, "more than 2^31 excluded intervals");
+  const size_t k = iv.size();
+  ctx->excl_host.resize(2 * k);
+  for (size_t i = 0; i < k; ++i) { ctx->excl_host[i] = iv[i].first; ctx->excl_host[k + i] = iv[i].second; }
+  HIPCHK(ctx->excl_dev.ensure(2 * k * 8));
+  HIPCHK(copy_h2d(ctx, ctx->excl_dev.p, ctx->excl_host.data(), 2 * k * 8));
+  Timer t(ctx, "exclude_mask", true);
+  launch_exclude_mask(ctx->excl_dev.as<int64_t>(), ctx->excl_dev.as<int64_t>() + k, (int)k, iv.front().first, iv.back().second,
+                      ctx->gcbits.as<uint64_t>(), ctx->nbits.as<uint64_t>(), ctx->stream);
+  return RSI_OK;
+}
+
 // A1-A9: GC mask and N runs, GC table and rescale, cap, compaction, bins, chromosome statistics (K1-K4).  The kernels are
 // HBM-bound: workers of a pool take turns through this phase (GpuGate, held until the function returns).
 int per_base_phase(rsi_ctx* ctx, const rsi_params& P, const int32_t* d_depth, const uint8_t* d_fasta, int64_t n, rsi_result* res,
@@ -969,6 +986,8 @@ int per_base_phase(rsi_ctx* ctx, const rsi_params& P, const int32_t* d_depth, co
     Timer t(ctx, "fasta_classify", true);
     launch_fasta_classify(d_fasta, n, ctx->gcbits.as<uint64_t>(), ctx->nbits.as<uint64_t>(), nwords, fl, st);
   }
+  // the caller's excluded intervals become N before anything reads the planes (one-shot: rsi_hot_set_exclude)
+  if (!ctx->excl_armed.empty()) { const int rcx = issue_exclude_mask(ctx, std::move(ctx->excl_armed), n); ctx->excl_armed.clear(); if (rcx != RSI_OK) return rcx; }
   uint64_t* d_ntrans = reinterpret_cast<uint64_t*>(small + kOffNtrans);
   PhaseParams* d_pp = reinterpret_cast<PhaseParams*>(small + kOffPhase);
   int64_t* d_cbreak = reinterpret_cast<int64_t*>(small + kOffBreaks);
@@ -1666,7 +1685,50 @@ const char* rsi_hot_last_error(const rsi_ctx* ctx) {
 void rsi_hot_set_timing(rsi_ctx* ctx, int on) { if (ctx) ctx->timing = on < 0 ? 0 : on > 3 ? 1 : on; }
 void rsi_hot_set_timing_kernel(rsi_ctx* ctx, const char* name) { if (ctx) ctx->timing_kernel = (name && name[0]) ? name : "cap_compact_bin"; }
 
+int rsi_hot_set_exclude(rsi_ctx* ctx, const int64_t* start, const int64_t* end, int count) {
+  if (!ctx) return fail(ctx, RSI_ERR_BAD_ARG, "null context");
+  if (count < 0) return fail(ctx, RSI_ERR_BAD_ARG, "negative interval count");
+  if (count > 0 && (!start || !end)) return fail(ctx, RSI_ERR_BAD_ARG, "intervals announced, but an array is NULL");
+  ctx->excl_armed.clear();   // count == 0: disarmed
+  for (int i = 0; i < count; ++i) ctx->excl_armed.push_back({start[i], end[i]});
+  normalize_intervals(ctx->excl_armed, -1);
+  return RSI_OK;
+}
+
+// Test hook: K1 and, with intervals, the mask kernel on a host sequence of any length; the two planes come back.
+int rsi_hot_debug_classify(rsi_ctx* ctx, const uint8_t* fasta, int64_t n, const int64_t* start, const int64_t* end, int count,
+                           uint64_t* gcbits, uint64_t* nbits) {
+  if (!ctx || !fasta || !gcbits || !nbits || n <= 0 || n >= (1ll << 31) - 4096 || count < 0 || (count > 0 && (!start || !end)))
+    return fail(ctx, RSI_ERR_BAD_ARG, "bad argument");
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!ctx_enter(ctx)) return RSI_ERR_HIP;
+  mailbox_reset(ctx);
+  ctx->ktimes.clear();
+  ctx->event_next = 0;
+  const int64_t nwords = n / 64 + 1;
+  HIPCHK(ctx->in_fasta.ensure((size_t)n + 64));
+  HIPCHK(ctx->gcbits.ensure((size_t)nwords * 8));
+  HIPCHK(ctx->nbits.ensure((size_t)nwords * 8));
+  HIPCHK(copy_h2d(ctx, ctx->in_fasta.p, fasta, (size_t)n));
+  {
+    FillList fl{};
+    Timer t(ctx, "fasta_classify", true);
+    launch_fasta_classify(ctx->in_fasta.as<uint8_t>(), n, ctx->gcbits.as<uint64_t>(), ctx->nbits.as<uint64_t>(), nwords, fl, ctx->stream);
+  }
+  if (count > 0) {
+    std::vector<std::pair<int64_t, int64_t>> iv;
+    for (int i = 0; i < count; ++i) iv.push_back({start[i], end[i]});
+    const int rc = issue_exclude_mask(ctx, std::move(iv), n);
+    if (rc != RSI_OK) return rc;
+  }
+  HIPCHK(hipMemcpyAsync(gcbits, ctx->gcbits.p, (size_t)nwords * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(nbits, ctx->nbits.p, (size_t)nwords * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(CTX_SYNC());
+  return RSI_OK;
+}
+
 int rsi_hot_run_device(rsi_ctx* ctx, const rsi_params* p, const void* d_depth, const void* d_fasta, int64_t n, rsi_result** out) {
+  ExcludeOneShot one_shot(ctx);
   if (!ctx || !p || !d_depth || !d_fasta || !out) return fail(ctx, RSI_ERR_BAD_ARG, "null argument");
   rsi_result* res = new rsi_result();
   int rc = run_device_impl(ctx, p, static_cast<const int32_t*>(d_depth), static_cast<const uint8_t*>(d_fasta), n, res);
@@ -1677,6 +1739,7 @@ int rsi_hot_run_device(rsi_ctx* ctx, const rsi_params* p, const void* d_depth, c
 
 
 int rsi_hot_run(rsi_ctx* ctx, const rsi_params* p, const int32_t* depth, const uint8_t* fasta, int64_t n, rsi_result** out) {
+  ExcludeOneShot one_shot(ctx);
   if (!ctx || !p || !depth || !fasta || !out) return fail(ctx, RSI_ERR_BAD_ARG, "null argument");
   if (n <= 0) return fail(ctx, RSI_ERR_BAD_ARG, "empty chromosome");
   HIPCHK(hipSetDevice(ctx->device));

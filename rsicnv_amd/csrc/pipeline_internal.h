@@ -192,6 +192,11 @@ struct rsi_ctx {
   std::atomic<int64_t> reserve_n{0};   // largest chromosome the pool has seen: workspace growth is sized for it (written at submission, read when a chromosome starts)
   bool poisoned = false;      // a wait hit its deadline with work still queued (ctx_sync): no further runs
   bool gate_shared = false;   // RSI_HOT_ISOLATE_STREAMING=1: bin-level kernels wait while a per-base phase runs (clean kernel timings, ~20 % less throughput)
+  // Excluded intervals (rsi_hot_set_exclude): [s, e) pairs, sorted and merged, armed for the NEXT run only -- every run entry
+  // point disarms on its way out (ExcludeOneShot), whether the run got as far as the mask kernel or not.
+  std::vector<std::pair<int64_t, int64_t>> excl_armed;
+  std::vector<int64_t> excl_host;   // the run's intervals clipped to its n, starts then ends: the upload's source
+  DevBuf excl_dev;                  // the same in HBM, grow-only
 };
 
 namespace rsip {
@@ -331,6 +336,25 @@ inline int fail(rsi_ctx* ctx, int code, const std::string& msg) {
   set_global_error(msg);
   return code;
 }
+
+// Intervals [s, e) -> sorted, start clamped to 0, end clipped to n (n < 0: not clipped), empty ones dropped, overlapping and
+// touching ones merged: the form k_exclude_mask takes.
+inline void normalize_intervals(std::vector<std::pair<int64_t, int64_t>>& v, int64_t n) {
+  std::vector<std::pair<int64_t, int64_t>> in;
+  in.swap(v);
+  for (auto& r : in) { if (r.first < 0) r.first = 0; if (n >= 0 && r.second > n) r.second = n; }
+  std::sort(in.begin(), in.end());
+  for (const auto& r : in) {
+    if (r.second <= r.first) continue;
+    if (!v.empty() && r.first <= v.back().second) v.back().second = std::max(v.back().second, r.second);
+    else v.push_back(r);
+  }
+}
+struct ExcludeOneShot {   // first statement of a run entry point: the armed mask does not outlive the call
+  rsi_ctx* ctx;
+  explicit ExcludeOneShot(rsi_ctx* c) : ctx(c) {}
+  ~ExcludeOneShot() { if (ctx) ctx->excl_armed.clear(); }
+};
 
 // offsets into the `small` buffer (accumulators and little lists), all 256-byte aligned
 constexpr size_t kOffGcAcc = 0;                                   // GcAccum

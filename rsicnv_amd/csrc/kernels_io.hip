@@ -543,7 +543,10 @@ __global__ __launch_bounds__(256) void k_bam_depth(const unsigned char* __restri
       if (anchor >= 0) {
         used = 1;
         long long ref_end = (long long)pos0 + 1;     // 1-based position of op `anchor` (samfunctions.cpp:85-92)
-        int q = 0;
+        // The query position is 64 bits wide because it goes on growing behind the read's end: an op adds less than 2^28
+        // and there are fewer than 2^16 ops, so q stays below 2^44 and never wraps, whatever a crafted CIGAR says (as an
+        // int it could turn negative and pass the `q + t >= l_seq` cut below).  qual[] is read at 0 <= q + t < l_seq only.
+        long long q = 0;
         for (int k = 0; k < n_cig; ++k) {
           const uint32_t c = ld_u32(cig + 4 * k);
           const int op = (int)(c & 0xf), len = (int)(c >> 4);

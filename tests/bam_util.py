@@ -12,9 +12,17 @@ CIGAR_OPS = "MIDNSHP=X"
 FLAG_SECONDARY, FLAG_DUP, FLAG_REVERSE, FLAG_UNMAP = 0x100, 0x400, 0x10, 0x4
 
 
+BGZF_MAX_PAYLOAD = 0xff00                               # what htslib puts into one block at the most
+
+
 def _bgzf_block(data):
+    if len(data) > BGZF_MAX_PAYLOAD:
+        raise ValueError(f"{len(data)} bytes do not fit one BGZF block")
     comp = zlib.compressobj(6, zlib.DEFLATED, -15)
     body = comp.compress(data) + comp.flush()
+    if len(body) + 25 > 0xffff:                         # incompressible: stored, which always fits the 16-bit BSIZE
+        comp = zlib.compressobj(0, zlib.DEFLATED, -15)
+        body = comp.compress(data) + comp.flush()
     bsize = len(body) + 25
     head = struct.pack("<BBBBIBBHBBHH", 0x1f, 0x8b, 8, 4, 0, 0, 0xff, 6, ord("B"), ord("C"), 2, bsize)
     return head + body + struct.pack("<II", zlib.crc32(data) & 0xffffffff, len(data))
@@ -31,9 +39,10 @@ def reg2bin(beg, end):
 
 
 def encode_read(tid, pos0, mapq, flag, cigar, seq_len, qual, name=b"r", mtid=-1, mpos=-1, tlen=0):
-    """cigar: list of (op_char, length); qual: bytes of length seq_len; pos0: 0-based leftmost position."""
-    ref_len = sum(l for op, l in cigar if op in "MDN=X")
-    cig = b"".join(struct.pack("<I", (l << 4) | CIGAR_OPS.index(op)) for op, l in cigar)
+    """cigar: list of (op, length), op a character of CIGAR_OPS or the op code itself (the way to write the codes 9-15
+    that have no character); qual: bytes of length seq_len; pos0: 0-based leftmost position."""
+    ref_len = sum(l for op, l in cigar if op in ("M", "D", "N", "=", "X", 0, 2, 3, 7, 8))
+    cig = b"".join(struct.pack("<I", (l << 4) | (op if isinstance(op, int) else CIGAR_OPS.index(op))) for op, l in cigar)
     seq = bytes([0x11] * ((seq_len + 1) // 2))          # all 'A'
     nm = name + b"\0"
     core = struct.pack("<iiBBHHHiiii", tid, pos0, len(nm), mapq, reg2bin(pos0, pos0 + max(ref_len, 1)), len(cigar), flag, seq_len, mtid, mpos, tlen)
@@ -44,7 +53,10 @@ def encode_read(tid, pos0, mapq, flag, cigar, seq_len, qual, name=b"r", mtid=-1,
 def write_bam(path, refs, records, block=60000, straddle=False):
     """refs: list of (name, length); records: encoded reads in coordinate order.  straddle: cut the BGZF blocks at
     fixed sizes wherever that falls (records, even their length fields, then span blocks -- legal, and what a reader
-    has to survive), instead of flushing before a record that would not fit (what samtools / htslib write)."""
+    has to survive), instead of flushing before a record that would not fit (what samtools / htslib write: only a record
+    that is itself larger than a block is split there, over as many blocks as it takes)."""
+    if not 0 < block <= BGZF_MAX_PAYLOAD:
+        raise ValueError("block must be in (0, 0xff00]")
     text = "@HD\tVN:1.0\tSO:coordinate\n" + "".join(f"@SQ\tSN:{n}\tLN:{l}\n" for n, l in refs)
     hdr = b"BAM\1" + struct.pack("<i", len(text)) + text.encode() + struct.pack("<i", len(refs))
     for n, l in refs:
@@ -61,7 +73,7 @@ def write_bam(path, refs, records, block=60000, straddle=False):
             if len(buf) + len(r) > block and buf:       # records may also straddle blocks: every 7th flush splits one
                 f.write(_bgzf_block(buf)); buf = b""
             buf += r
-            if len(buf) > block:
+            while len(buf) > block:
                 f.write(_bgzf_block(buf[:block])); buf = buf[block:]
         if buf:
             f.write(_bgzf_block(buf))
@@ -137,6 +149,73 @@ def depth_rules(records_raw, tid, n, minq=0, min_baseq=13):
     return rd
 
 
+def read_runs(rec, tid, n, minq=0, min_baseq=13):
+    """One record under the same rules as depth_rules, as the stretches of counted bases rather than the bases:
+    None for a read that is filtered or has no anchor, else the list of (first, past-the-last) reference positions of
+    every maximal stretch of counted bases inside one M or '=' op.  Where the reference has no defined behaviour the
+    library's contract applies: an op walks no further than the read's last base (a CIGAR longer than the read, l_seq = 0),
+    and the op codes 9-15 neither count nor move either position."""
+    body = rec[4:]
+    rtid, pos0, l_nm, mapq, _bin, n_cig, flag, l_seq, _a, _b, _c = struct.unpack_from("<iiBBHHHiiii", body, 0)
+    if rtid != tid or pos0 <= 0 or mapq < minq or (flag & FLAG_SECONDARY) or (flag & FLAG_DUP):
+        return None
+    off = 32 + l_nm
+    ops = [(c & 0xf, c >> 4) for c in struct.unpack_from(f"<{n_cig}I", body, off)]
+    qual = body[off + 4 * n_cig + (l_seq + 1) // 2: off + 4 * n_cig + (l_seq + 1) // 2 + l_seq]
+    if not any(op in (0, 2, 7, 8) for op, _ in ops):
+        return None
+    runs, q, ref, anchored = [], 0, pos0, False
+    for op, l in ops:
+        anchored = anchored or op in (0, 2, 7, 8)
+        if op in (0, 7):
+            open_at = None
+            for i in range(l):
+                if ref + i >= n or q + i >= l_seq:
+                    break
+                if qual[q + i] >= min_baseq:
+                    if open_at is None: open_at = ref + i
+                    last = ref + i
+                elif open_at is not None:
+                    runs.append((open_at, last + 1)); open_at = None
+            if open_at is not None:
+                runs.append((open_at, last + 1))
+        if op in (0, 1, 4, 7, 8): q += l
+        if anchored and op in (0, 2, 3, 4): ref += l
+    return runs
+
+
+def depth_rules_counts(records_raw, tid, n, minq=0, min_baseq=13):
+    """depth_rules once more, written run by run (read_runs), with the counts the library reports next to the depth:
+    `used`, the reads that pass the filters and have an anchor, and `runs`, the stretches they add.  Records with the
+    same bytes share one walk, so a pile of identical reads costs one."""
+    rd = np.zeros(n, dtype=np.int32)
+    used = nruns = 0
+    seen = {}
+    for rec in records_raw:
+        if rec not in seen:
+            seen[rec] = read_runs(rec, tid, n, minq, min_baseq)
+        runs = seen[rec]
+        if runs is None:
+            continue
+        used += 1
+        nruns += len(runs)
+        for a, b in runs:
+            rd[a:b] += 1
+    return rd, {"used": used, "runs": nruns}
+
+
+def walk_counts(records_raw, tid):
+    """What a reader that starts at the first record and stops at the first one beyond `tid` (a later reference or an
+    unplaced read) has seen: `records`, that one included, and `on_chrom`, the records of `tid` among them."""
+    records = on_chrom = 0
+    for rec in records_raw:
+        rtid = struct.unpack_from("<i", rec, 4)[0]
+        records += 1
+        if rtid == tid: on_chrom += 1
+        elif rtid > tid or rtid < 0: break
+    return {"records": records, "on_chrom": on_chrom}
+
+
 def reference_depth_dump(ref_bin, libref, bam, fasta_path, chrom, workdir, extra=()):
     """Index the BAM with the reference's own samtools and run the reference with -s: returns its per-base depth."""
     import ctypes
@@ -153,7 +232,7 @@ def reference_depth_dump(ref_bin, libref, bam, fasta_path, chrom, workdir, extra
     dump = out + "." + chrom + "_rd"
     if not os.path.exists(dump):
         raise RuntimeError("the reference did not write its depth dump: " + r.stderr.decode()[-400:])
-    a = np.loadtxt(dump, dtype=np.int64)
+    a = np.loadtxt(dump, dtype=np.int64, ndmin=2)           # ndmin: a reference of one base gives one line
     return a[:, 1].astype(np.int32), (out if r.returncode == 0 and os.path.exists(out) else None)
 
 

@@ -340,6 +340,17 @@ int rsi_hot_debug_grid_mad_i32(rsi_ctx* ctx, const int32_t* x, int64_t nb, doubl
 int rsi_hot_debug_classify(rsi_ctx* ctx, const uint8_t* fasta, int64_t n, const int64_t* start, const int64_t* end, int count,
                            uint64_t* gcbits, uint64_t* nbits);
 
+/* Test hook: the per-base phase alone -- K1 / K1b, K2j or its fallbacks, the cap, then the K4 route the plan picks -- on a host
+ * chromosome uploaded as rsi_hot_run uploads it, with the intervals (count > 0: as rsi_hot_set_exclude takes them) applied, and
+ * nothing behind it: chromosomes of a few bins or without spread, which the scan refuses, still show their per-base result.
+ * Afterwards "rd_gc", "rd_concat", "binmedint", "binsum" and "noncode" (int32 (start, end) pairs) are fetchable and the phase /
+ * kernel names are those of the phase, followed by "k4.form ..." entries whose VALUE is what the K4 launcher chose inside its
+ * route: "vr" (LDS histogram range), "sw7" (0 / 1), "parts" (K4m's lanes per bin), "tile bins", "int32 template" (100 MV + EP).
+ * out: n, n_noncode, gc_rdmean, byte_escapes, cap_median, n_compact, nbins, RDmedian, RDsd; the rest zero.  On an error out holds
+ * what the phase had derived before it. */
+int rsi_hot_debug_per_base(rsi_ctx* ctx, const rsi_params* p, const int32_t* depth, const uint8_t* fasta, int64_t n, const int64_t* start,
+                           const int64_t* end, int count, rsi_chrom_stats* out);
+
 /* Timing hooks for bench.py: per-kernel HIP-event times (ms) of the last run, by kernel name.
  * names/ms receive up to cap entries; returns the number of timed launches. */
 int rsi_hot_kernel_times(const rsi_ctx* ctx, const char** names, float* ms, int cap);

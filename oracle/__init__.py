@@ -76,6 +76,8 @@ class Oracle:
         L.orc_destroy.argtypes = [C.c_void_p]
         L.orc_run.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.c_int32, C.c_int32]
         L.orc_run.restype = C.c_int
+        L.orc_run_per_base.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.c_int32]
+        L.orc_run_per_base.restype = C.c_int
         for nm, ct in (("orc_get_i32", C.c_int32), ("orc_get_f32", C.c_float), ("orc_get_f64", C.c_double)):
             f = getattr(L, nm)
             f.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(ct), C.c_int64]
@@ -102,6 +104,13 @@ class Oracle:
         f, fp = _u8(fasta)
         assert d.shape == f.shape
         return self.lib.orc_run(self.h, C.byref(params), dp, fp, d.size, 1 if snapshots else 0)
+
+    def run_per_base(self, params, depth, fasta):
+        """The per-base stages alone: rd_gc, rd_cap, rd_concat, noncode, binmedint and the "chrom" scalars; returns the bins."""
+        d, dp = _i32(depth)
+        f, fp = _u8(fasta)
+        assert d.shape == f.shape
+        return self.lib.orc_run_per_base(self.h, C.byref(params), dp, fp, d.size)
 
     def _get(self, fn, ct, dt, name):
         n = fn(self.h, name.encode(), None, 0)

@@ -259,13 +259,18 @@ struct Oracle {
   static double nb_formula(double sum, double m2, double r) {
     return 2.0 * sqrt(r) * log(sqrt((sum + 0.25) / (m2 * r - 0.5)) + sqrt(1.0 + (sum + 0.25) / (m2 * r - 0.5)));
   }
-  void bins() {
+  void bin_medians() {
     const int m = P.m, np = (int)rd.size(), nb = np / m;
-    binmed.assign(nb, -1.0f); binmedint.assign(nb, 0); binnb.assign(nb, -1.0f);
+    binmed.assign(nb, -1.0f); binmedint.assign(nb, 0);
     for (int b = 0; b < nb; ++b) {
       binmed[b] = (float)exact_median(&rd[(size_t)b * m], m);
       binmedint[b] = (int)(binmed[b] + 0.5);
     }
+  }
+  void bins() {
+    const int m = P.m, np = (int)rd.size(), nb = np / m;
+    bin_medians();
+    binnb.assign(nb, -1.0f);
     RDmedian = pmedian(rd.data(), rd.size());   // rsi.cpp:1821
     // MAD over 31 interleaved subsamples
     double med = pmedian(rd.data(), rd.size());
@@ -853,6 +858,20 @@ int orc_run(void* h, const orc_params* p, const int32_t* depth, const uint8_t* f
   O.stage_s[0] = t1 - t0; O.stage_s[1] = t2 - t1; O.stage_s[2] = t3 - t2; O.stage_s[3] = t4 - t3; O.stage_s[4] = t5 - t4;
   if (O.short_neighbourhoods) return -3;   // the reference aborts on this input (a candidate longer than its neighbourhood)
   return (int)O.calls.size();
+}
+
+// The per-base stages alone (GC adjustment, cap, compaction, bin medians) with their snapshots: chromosomes of a few bins or
+// without spread, on which the stages behind have nothing to work with.  Returns the number of bins.
+int orc_run_per_base(void* h, const orc_params* p, const int32_t* depth, const uint8_t* fasta, int32_t n) {
+  orc::Oracle& O = *(orc::Oracle*)h;
+  O.load(conv(p), depth, fasta, n);
+  O.gc_correct();
+  O.snap_i["rd_gc"] = O.rd;
+  O.cap();
+  O.snap_i["rd_cap"] = O.rd;
+  O.concat();
+  O.bin_medians();
+  return (int)O.binmedint.size();
 }
 
 static const std::vector<int>* ivec(orc::Oracle& O, const char* name) {

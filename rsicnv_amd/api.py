@@ -35,7 +35,7 @@ EXPORTS = ["rsi_default_params", "rsi_hot_create", "rsi_hot_destroy", "rsi_hot_l
            "rsi_synth_append_genome_bgzf", "rsi_genome_text_open_samples", "rsi_genome_text_samples", "rsi_genome_text_max_resident",
            "rsi_genome_text_sample_depth", "rsi_genome_text_copy_sample_depth", "rsi_synth_append_genome_samples",
            "rsi_genome_bedgraph_open", "rsi_synth_append_genome_bedgraph",
-           "rsi_hot_set_exclude", "rsi_exclude_read_bed", "rsi_hot_debug_classify"]
+           "rsi_hot_set_exclude", "rsi_exclude_read_bed", "rsi_hot_debug_classify", "rsi_hot_debug_per_base"]
 
 
 class RsiParams(C.Structure):
@@ -214,6 +214,8 @@ def load_library():
     L.rsi_hot_set_exclude.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.rsi_exclude_read_bed.argtypes = [C.c_char_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int]
     L.rsi_hot_debug_classify.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.rsi_hot_debug_per_base.argtypes = [C.c_void_p, C.POINTER(RsiParams), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
+                                         C.POINTER(RsiChromStats)]
     _lib = L
     return L
 
@@ -429,6 +431,25 @@ class RsiHot:
             rc = self.lib.rsi_hot_debug_classify(self.ctx, f.ctypes.data, f.size, s.ctypes.data, e.ctypes.data, s.size, gc.ctypes.data, nb.ctypes.data)
         self._check(rc)
         return gc, nb
+
+    def debug_per_base(self, params, depth, fasta, exclude=None):
+        """The per-base phase alone on host arrays (test hook, rsi_hot_debug_per_base): the statistics it fills, as a dict.
+        Afterwards fetch("rd_gc" / "rd_concat" / "binmedint" / "binsum" / "noncode"), phase_times() and kernel_times() are those
+        of the phase; phase_times() ends with the "k4.form ..." entries."""
+        d = np.ascontiguousarray(depth, dtype=np.int32)
+        f = np.ascontiguousarray(fasta, dtype=np.uint8)
+        if d.shape != f.shape or d.ndim != 1:
+            raise ValueError("depth and fasta must be 1-D arrays of the same length")
+        st = RsiChromStats()
+        if exclude is None or len(exclude) == 0:
+            rc = self.lib.rsi_hot_debug_per_base(self.ctx, C.byref(params), d.ctypes.data, f.ctypes.data, d.size, None, None, 0, C.byref(st))
+        else:
+            s, e = _interval_arrays(exclude)
+            rc = self.lib.rsi_hot_debug_per_base(self.ctx, C.byref(params), d.ctypes.data, f.ctypes.data, d.size, s.ctypes.data, e.ctypes.data,
+                                                 s.size, C.byref(st))
+        self.last_stats = {k[0]: getattr(st, k[0]) for k in RsiChromStats._fields_}
+        self._check(rc)
+        return self.last_stats
 
     def run(self, params, depth, fasta, exclude=None):
         """depth: int32[n] raw per-base depth, fasta: uint8[n] sequence bytes (host arrays); exclude: intervals treated as N

@@ -169,12 +169,17 @@ struct K4Regions { long long brk[kRegInline]; long long cum[kRegInline + 1]; };
 // int32 (what K4 / K4w compact, what the byte forms recompute edge tiles from); src8: the byte forms' input, K2 / K2j's copy of the
 // raw depth (K4j, K4s) or the histogram pass' copy (K4', RAW K4s); rdc8 / rdc: the output as bytes / as int32; acc: K4 only;
 // gsum: K4, K4', K4j; rtab, escapes, pp: see K4j and K4s; vbase: K4 / K4w; raw: K4' on the raw depth (-NOGC).
+// What a K4 launcher chose inside its route, reported by the launcher itself where K4Args::form is set (test hook
+// rsi_hot_debug_per_base; -1 / 0: the route has no such choice): the LDS histogram's value range, the median phase's packing,
+// K4m's lanes per bin, the tile's bins (K4', K4j, K4w, K4), the int32 K4's template <MV, EP> as 100 MV + EP.
+struct K4Form { int vr = 0, sw7 = -1, parts = 0, tile_bins = 0, tmpl = -1; };
 struct K4Args {
   const int32_t* src; const uint8_t* src8; const uint64_t* gcbits; int64_t n; const double* table;
   const int64_t* cbreak; const int64_t* cum; const K4Regions* inl; int nreg; int64_t ncompact; int32_t capval; int m;
   uint8_t* rdc8; int32_t* rdc; int32_t* binmed; int64_t* binsum; uint32_t* res_hist; BinAccum* acc;
   void* slabs; void* gsum; unsigned int* counters; const void* exp_src; void* exp_dst; size_t exp_bytes;
   const unsigned int* rtab; const unsigned int* escapes; PhaseParams* pp; int vbase; int raw; hipStream_t stream;
+  K4Form* form;   // NULL, or where the launcher notes its choice
 };
 size_t cap_compact_slab_bytes(int m, int32_t capval, int64_t ncompact, int vbase);
 int cap_compact_overwrites(int m, int32_t capval, int64_t ncompact, int vbase);

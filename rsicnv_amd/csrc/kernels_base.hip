@@ -2924,6 +2924,7 @@ void launch_cap_compact_bin8(const K4Args& a) {
                        a.cbreak, a.cum, a.nreg, a.ncompact, a.capval, a.m, TB, vr, a.rdc8, a.binmed, a.binsum, a.res_hist, sl, gs, pg,       \
                        a.counters, a.exp_src, a.exp_dst, (unsigned int)a.exp_bytes, *a.inl, a.raw); } while (0)
   const bool sw7 = byte_shape(a.capval).sw7;   // four values to a register in the median phase (k_cap_compact_bin8, SW7)
+  if (a.form) { a.form->vr = vr; a.form->sw7 = sw7; a.form->tile_bins = TB; }
   if (sw7) { if (maxc == 1) RSI_K48(1, 1, true); else RSI_K48(2, 1, true); }
   else { if (maxc == 1) RSI_K48(1, 0, false); else RSI_K48(2, 0, false); }   // caps of 128 .. 253: two values to a register (EPT = 0)
 #undef RSI_K48
@@ -2942,6 +2943,7 @@ void launch_rescale_compact_bin8(const K4Args& a) {
                a.table, a.cbreak, a.cum, a.nreg, a.ncompact, a.capval, a.m, TB, vr, a.rdc8, a.binmed, a.binsum, a.res_hist, sl, gs, pg,        \
                a.counters, a.exp_src, a.exp_dst, (unsigned int)a.exp_bytes, *a.inl, a.rtab, a.pp); } while (0)
   const bool sw7 = byte_shape(a.capval).sw7;   // four values to a register in the median phase (SW7)
+  if (a.form) { a.form->vr = vr; a.form->sw7 = sw7; a.form->tile_bins = TB; }
   const bool fix = a.rtab != nullptr;   // the caller hands the ratios over only when K2j verified them (pipeline.hip)
   if (fix) {
     if (sw7) { if (maxc == 1) RSI_K48J(1, 1, true, true); else RSI_K48J(2, 1, true, true); }
@@ -2983,6 +2985,7 @@ void launch_cap_compact_bin16(const K4Args& a) {
     RSI_LAUNCH((k_cap_compact_bin16<MC>), dim3(grid), dim3(kThreads), lds, a.stream, a.src, a.cbreak, a.cum, a.nreg, a.ncompact, a.capval, a.m, TB, \
                a.vbase, a.rdc, a.binmed, a.binsum, a.res_hist, static_cast<unsigned int*>(a.slabs), pg, a.counters, a.exp_src, a.exp_dst,        \
                (unsigned int)a.exp_bytes, *a.inl); } while (0)
+  if (a.form) { a.form->vr = kK4Window; a.form->tile_bins = TB; }
   if (maxc == 1) RSI_K416(1); else RSI_K416(2);
 #undef RSI_K416
 }
@@ -3015,10 +3018,12 @@ void launch_cap_compact_bin(const K4Args& a) {
     RSI_LAUNCH((k_cap_compact_bin<MV, EP>), dim3(grid), dim3(kThreads), lds, a.stream, a.src, a.n, a.cbreak, a.cum, a.nreg,          \
                        a.ncompact, a.capval, a.m, TB, vr, a.vbase, a.rdc, a.binmed, a.binsum, a.res_hist, a.acc, sl, gs, pg, a.counters, \
                        overwrite, a.exp_src, a.exp_dst, (unsigned int)a.exp_bytes, *a.inl, pack16); } while (0)
-  if (maxv <= 4 && ept <= 13) RSI_K4(4, 13);          // m <= 52 (e.g. -m 51)
-  else if (maxv <= 8 && ept <= 26) RSI_K4(8, 26);     // m <= 104 (e.g. the default -m 101)
-  else if (ept <= 52) RSI_K4(13, 52);                 // m <= 191 with 4 threads per bin, or fewer bins per tile
-  else RSI_K4(13, 0);
+#define RSI_K4_AS(MV, EP) do { if (a.form) { a.form->vr = vr; a.form->tile_bins = TB; a.form->tmpl = 100 * MV + EP; } RSI_K4(MV, EP); } while (0)
+  if (maxv <= 4 && ept <= 13) RSI_K4_AS(4, 13);          // m <= 52 (e.g. -m 51)
+  else if (maxv <= 8 && ept <= 26) RSI_K4_AS(8, 26);     // m <= 104 (e.g. the default -m 101)
+  else if (ept <= 52) RSI_K4_AS(13, 52);                 // m <= 191 with 4 threads per bin, or fewer bins per tile
+  else RSI_K4_AS(13, 0);
+#undef RSI_K4_AS
 #undef RSI_K4
 }
 

@@ -636,6 +636,7 @@ void launch_rescale_compact_stream(const K4Args& a) {
     RSI_LAUNCH((k_rescale_compact_stream<C64, RW>), dim3(grid), dim3(kS4Threads), lds, a.stream, a.src8, a.src, a.gcbits, a.n, a.n / 64 + 1, a.table, \
                a.cbreak, a.cum, a.nreg, a.ncompact, a.capval, a.m, vr, sh.sw7 ? 1 : 0, a.rdc8, a.res_hist, sl, pg, a.counters, a.exp_src, a.exp_dst, \
                (unsigned int)a.exp_bytes, *a.inl, a.rtab, a.escapes, a.pp); } while (0)
+  if (a.form) { a.form->vr = vr; a.form->sw7 = sh.sw7; }
   const bool rawmode = a.rtab == nullptr;   // the bytes are final values (the caller has no ratios to hand over: -NOGC, the three-pass chain)
   if (vr <= 128) { if (rawmode) RSI_K4S(true, true); else RSI_K4S(true, false); }
   else { if (rawmode) RSI_K4S(false, true); else RSI_K4S(false, false); }
@@ -649,6 +650,7 @@ void launch_bin_median8(const K4Args& a) {
   const bool sw7 = sh.sw7;
   const int m = a.m;
   const int parts = m <= 52 ? 2 : (m <= 104 ? 4 : (m <= 216 ? 8 : 16));
+  if (a.form) { a.form->vr = vr; a.form->sw7 = sw7; a.form->parts = parts; }
   const int64_t nb = a.ncompact / m;
   const int64_t ntrips = (nb + 64 / parts - 1) / (64 / parts);
   int64_t mg = (ntrips + kM4Threads / 64 - 1) / (kM4Threads / 64);

@@ -883,6 +883,8 @@ static void issue_k4(rsi_ctx* ctx, const K4Plan& plan, K4Args a) {
   a.src8 = (plan.route == K4Route::bytes || plan.raw ? ctx->rescaled8 : ctx->depth8).as<uint8_t>();
   if (!plan.fixed) a.rtab = a.escapes = nullptr;
   a.raw = plan.raw;
+  ctx->k4_form = K4Form{};
+  a.form = &ctx->k4_form;
   // RAW K4s: the bytes are the values (no ratios, no escapes: the histogram pass saturates them at 254, above any cap of this path)
   if (plan.route == K4Route::stream && plan.raw) a.table = nullptr;
   {
@@ -1190,6 +1192,7 @@ int per_base_phase(rsi_ctx* ctx, const rsi_params& P, const int32_t* d_depth, co
   S.n_noncode = (int)noncode.size();
   res->noncode.clear();
   for (const Region& r : noncode) { res->noncode.push_back(r.start); res->noncode.push_back(r.end); }
+  ctx->noncode_pairs = res->noncode;
   ph_a1.stop();
 
   Phase ph_cap(ctx, "a4.checks+cap");
@@ -1272,8 +1275,9 @@ int per_base_phase(rsi_ctx* ctx, const rsi_params& P, const int32_t* d_depth, co
   }
   uint32_t* exp_slot = spec_done ? spec_slot : (exp_bytes <= kMailboxMaxCopy ? static_cast<uint32_t*>(mb_alloc(ctx, exp_bytes)) : nullptr);
   if (spec_done) {
-    ctx->rdc_is_bytes = true;   // all done by the queued launch
-    if (!P.gcadjust) ctx->phases.push_back({"a5.nogc byte path", 1.0});
+    ctx->rdc_is_bytes = true;   // all done by the queued launch, whose route's markers stand for the run
+    for (const char* mark : spec_plan.marks)
+      if (mark) ctx->phases.push_back({mark, 1.0});
   } else {
     int vbase = 0;
     if (plan.route == K4Route::wide16 || plan.route == K4Route::int32) {
@@ -1537,10 +1541,8 @@ int bin_level_stages(rsi_ctx* ctx, const rsi_params& P, int64_t n, rsi_result* r
   return RSI_OK;
 }
 
-int run_device_impl(rsi_ctx* ctx, const rsi_params* Pp, const int32_t* d_depth, const uint8_t* d_fasta, int64_t n,
-                    rsi_result* res) {
-  const rsi_params& P = *Pp;
-  const double t_begin = now_ms();
+// What every run checks and resets before its first launch (rsi_hot_run_device, rsi_hot_debug_per_base).
+int run_enter(rsi_ctx* ctx, const rsi_params& P, const int32_t* d_depth, const uint8_t* d_fasta, int64_t n) {
   if (n <= 0 || n >= (1ll << 31) - 4096) return fail(ctx, RSI_ERR_BAD_ARG, "chromosome length must be in (0, 2^31)");
   if (P.m < 1 || (P.m % 2) != 1) return fail(ctx, RSI_ERR_BAD_ARG, "m must be odd (the reference forces it, rsi.cpp:2061-2064)");
   if (P.m > 3000) return fail(ctx, RSI_ERR_UNSUPPORTED, "bin size above 3000 is not supported by the bin kernel");
@@ -1555,8 +1557,17 @@ int run_device_impl(rsi_ctx* ctx, const rsi_params* Pp, const int32_t* d_depth, 
   tl_grow_ms = 0.0;
   if (!ctx_enter(ctx)) return RSI_ERR_HIP;
   mailbox_reset(ctx);
+  return RSI_OK;
+}
+
+int run_device_impl(rsi_ctx* ctx, const rsi_params* Pp, const int32_t* d_depth, const uint8_t* d_fasta, int64_t n,
+                    rsi_result* res) {
+  const rsi_params& P = *Pp;
+  const double t_begin = now_ms();
+  int rc = run_enter(ctx, P, d_depth, d_fasta, n);
+  if (rc != RSI_OK) return rc;
   PerBase pb;
-  int rc = per_base_phase(ctx, P, d_depth, d_fasta, n, res, pb);
+  rc = per_base_phase(ctx, P, d_depth, d_fasta, n, res, pb);
   if (rc != RSI_OK) return rc;
   rsi_chrom_stats& S = res->stats;
   std::vector<Candidate> blocks, raw, kept, segs_all;
@@ -1738,10 +1749,8 @@ int rsi_hot_run_device(rsi_ctx* ctx, const rsi_params* p, const void* d_depth, c
 }
 
 
-int rsi_hot_run(rsi_ctx* ctx, const rsi_params* p, const int32_t* depth, const uint8_t* fasta, int64_t n, rsi_result** out) {
-  ExcludeOneShot one_shot(ctx);
-  if (!ctx || !p || !depth || !fasta || !out) return fail(ctx, RSI_ERR_BAD_ARG, "null argument");
-  if (n <= 0) return fail(ctx, RSI_ERR_BAD_ARG, "empty chromosome");
+// A host chromosome into the context's input buffers (rsi_hot_run, rsi_hot_debug_per_base).
+static int upload_inputs(rsi_ctx* ctx, const int32_t* depth, const uint8_t* fasta, int64_t n) {
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(ctx->in_depth.ensure((size_t)(n + 4) * 4));
   HIPCHK(ctx->in_fasta.ensure((size_t)n + 64));
@@ -1792,7 +1801,44 @@ int rsi_hot_run(rsi_ctx* ctx, const rsi_params* p, const int32_t* depth, const u
   if (!narrowed) HIPCHK(copy_h2d(ctx, ctx->in_depth.p, depth, (size_t)n * 4));
   HIPCHK(copy_h2d(ctx, ctx->in_fasta.p, fasta, (size_t)n));
   HIPCHK(CTX_SYNC());
+  return RSI_OK;
+}
+
+int rsi_hot_run(rsi_ctx* ctx, const rsi_params* p, const int32_t* depth, const uint8_t* fasta, int64_t n, rsi_result** out) {
+  ExcludeOneShot one_shot(ctx);
+  if (!ctx || !p || !depth || !fasta || !out) return fail(ctx, RSI_ERR_BAD_ARG, "null argument");
+  if (n <= 0) return fail(ctx, RSI_ERR_BAD_ARG, "empty chromosome");
+  const int rcu = upload_inputs(ctx, depth, fasta, n);
+  if (rcu != RSI_OK) return rcu;
   return rsi_hot_run_device(ctx, p, ctx->in_depth.p, ctx->in_fasta.p, n, out);
+}
+
+// Test hook: the per-base phase alone (include/rsi_hot.h).  The production per_base_phase on the uploaded chromosome, nothing behind it.
+int rsi_hot_debug_per_base(rsi_ctx* ctx, const rsi_params* p, const int32_t* depth, const uint8_t* fasta, int64_t n, const int64_t* start,
+                           const int64_t* end, int count, rsi_chrom_stats* out) {
+  ExcludeOneShot one_shot(ctx);
+  if (!ctx || !p || !depth || !fasta || !out || count < 0 || (count > 0 && (!start || !end))) return fail(ctx, RSI_ERR_BAD_ARG, "bad argument");
+  if (n <= 0) return fail(ctx, RSI_ERR_BAD_ARG, "empty chromosome");
+  memset(out, 0, sizeof(*out));
+  int rc = rsi_hot_set_exclude(ctx, start, end, count);
+  if (rc != RSI_OK) return rc;
+  if ((rc = upload_inputs(ctx, depth, fasta, n)) != RSI_OK) return rc;
+  const int32_t* d_depth = ctx->in_depth.as<int32_t>();
+  if ((rc = run_enter(ctx, *p, d_depth, ctx->in_fasta.as<uint8_t>(), n)) != RSI_OK) return rc;
+  ctx->k4_form = K4Form{};
+  rsi_result res;
+  PerBase pb;
+  rc = per_base_phase(ctx, *p, d_depth, ctx->in_fasta.as<uint8_t>(), n, &res, pb);
+  *out = res.stats;   // on an error: what the phase had derived before it
+  if (rc != RSI_OK) return rc;
+  // the form the K4 launch that counts took inside its route, as its launcher noted it
+  const K4Form& f = ctx->k4_form;
+  ctx->phases.push_back({"k4.form vr", (double)f.vr});
+  if (f.sw7 >= 0) ctx->phases.push_back({"k4.form sw7", (double)f.sw7});
+  if (f.parts > 0) ctx->phases.push_back({"k4.form parts", (double)f.parts});
+  if (f.tile_bins > 0) ctx->phases.push_back({"k4.form tile bins", (double)f.tile_bins});
+  if (f.tmpl >= 0) ctx->phases.push_back({"k4.form int32 template", (double)f.tmpl});
+  return RSI_OK;
 }
 
 int rsi_result_ncalls(const rsi_result* r, int which) { return (r && which >= 0 && which < 4) ? (int)r->lists[which].size() : 0; }
@@ -1819,6 +1865,11 @@ int64_t rsi_hot_fetch_i32(rsi_ctx* ctx, const char* name, int32_t* out, int64_t 
   else if (s == "rd_concat") {
     if (out) { HIPCHK(hipSetDevice(ctx->device)); const int rcm = materialize_rdc(ctx); if (rcm != RSI_OK) return rcm; }
     src = ctx->rdc.p ? ctx->rdc.p : static_cast<const void*>(ctx); cnt = ctx->ncompact;
+  }
+  else if (s == "noncode") {   // host data: the last run's removed regions as (start, end) pairs
+    const int64_t k = (int64_t)ctx->noncode_pairs.size();
+    if (out) memcpy(out, ctx->noncode_pairs.data(), (size_t)std::min(k, cap) * 4);
+    return k;
   }
   else if (s == "depth_in" && ctx->in_depth.p) { src = ctx->in_depth.p; cnt = ctx->n_in; }
   else if (s == "binmedint") { src = ctx->binmed.p; cnt = ctx->nb; }

@@ -176,6 +176,8 @@ struct rsi_ctx {
   bool rd_gc_valid = false;                  // rd_gc holds the rescaled depth of the last run (else rsi_hot_fetch builds it on demand)
   const int32_t* last_depth = nullptr;       // device input of the last run (borrowed; needed to build rd_gc on demand)
   int last_scan_med = 0;
+  std::vector<int32_t> noncode_pairs;        // the last run's removed regions, (start, end) pairs (rsi_hot_fetch_i32 "noncode")
+  rsik::K4Form k4_form;                      // what the last K4 launch chose inside its route (rsi_hot_debug_per_base reports it)
   // wall-clock per pipeline phase of the last run (host view, includes waits), for bench.py
   std::vector<std::pair<const char*, double>> phases;
   // when the context belongs to a pool: arbitration of the GPU between workers

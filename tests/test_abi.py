@@ -22,6 +22,7 @@ def test_every_declared_symbol_is_exported(hotlib):
     missing = [n for n in names if not hasattr(hotlib, n)]
     assert not missing, f"librsi_hot.so lacks: {missing}"
     assert set(api.EXPORTS) <= set(names)
+    assert "rsi_hot_debug_per_base" in names and "rsi_hot_debug_per_base" in api.EXPORTS
 
 
 def test_struct_layouts_match_header(hotlib):

@@ -1,5 +1,6 @@
 """Small and odd chromosomes through the library and the oracle (the oracle in a child process: where the reference would exit or
-abort, the restatement may too).  Prints one line per case; anything but `same` / `both refuse` deserves a look."""
+abort, the restatement may too).  Prints one line per case; anything but `same` / `both refuse` deserves a look.
+The per-base arrays of such chromosomes are tested, not printed: tests/test_per_base_edges.py (cases: tests/per_base_cases.py)."""
 import json, os, subprocess, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -286,6 +286,31 @@ int rsi_hot_set_exclude(rsi_ctx* ctx, const int64_t* start, const int64_t* end, 
  * rsi_hot_last_error(NULL). */
 int rsi_exclude_read_bed(const char* path, const char* chrom, int64_t n, int64_t* start, int64_t* end, int cap);
 
+/* ---- Depth tracks: bedGraph written from the device --------------------------------------------------------------------------
+ * An int32[n] array in HBM as the text of `bedtools genomecov -bga`: one line "NAME<TAB>start<TAB>end<TAB>value" per maximal run of
+ * equal values, start 0-based, end exclusive, zeros included, value as %d (negative values too), coordinates as %lld.  Runs are
+ * found, measured and formatted by kernels; only finished text crosses PCIe, slice by slice through two pinned buffers, so
+ * that the workspace does not grow with n.  A bedGraph reader (rsi_genome_bedgraph_open, -d track.bedgraph) takes
+ * the file back.  An empty name, one longer than 255 bytes or one with a tab or a newline is RSI_ERR_BAD_ARG; n == 0 writes
+ * nothing and is RSI_OK; a write() that fails is RSI_ERR_INTERNAL with errno's text in rsi_hot_last_error.  Every wait has the
+ * library's 60 s deadline. */
+typedef struct rsi_track_stats { int64_t n, lines, bytes, slices; double t_total_ms, t_kernel_ms, t_write_ms; } rsi_track_stats;
+/* The last run's depth of this context as bedGraph, appended to (append != 0) or replacing `path`.
+ * which: 0 = the raw input depth of the run, 1 = the GC-adjusted depth ("rd_gc", before the cap; RSI_ERR_BAD_ARG after a -NOGC run).
+ * The raw depth is what the run read: the context's own buffer after rsi_hot_run / _run_text / _run_bam, the CALLER's buffer
+ * after rsi_hot_run_device / _run_depth_device -- borrowed, so both forms are valid only while the caller still holds that
+ * buffer unchanged (a genome reader's slot: before rsi_genome_text_release; the context's own buffer: before the next
+ * rsi_hot_load_depth_*).  RSI_ERR_BAD_ARG when the context has run nothing, or rsi_hot_debug_track has taken its buffer since. */
+int rsi_hot_write_track(rsi_ctx* ctx, int which, const char* chrom, const char* path, int append, rsi_track_stats* stats);
+/* Any int32[n] in HBM (not modified), e.g. a genome reader's buffer. */
+int rsi_hot_write_track_device(rsi_ctx* ctx, const void* d_values, int64_t n, const char* chrom, const char* path, int append,
+                               rsi_track_stats* stats);
+/* Test hook: host values[n] uploaded (into the context's input depth buffer), formatted with coordinates offset by pos0, text
+ * into out[cap]; slice_bases > 0 forces that slice length (0: the default).  Returns the text length (also when out == NULL or
+ * cap is too small, writing nothing then), < 0 on error. */
+int64_t rsi_hot_debug_track(rsi_ctx* ctx, const int32_t* values, int64_t n, const char* chrom, int64_t pos0, int64_t slice_bases,
+                            char* out, int64_t cap, rsi_track_stats* stats);
+
 /* Results.  which: 0 = calls after sd_filters (what write_cnv_to_file prints),
  *                  1 = detectcnv output before sd_filters,
  *                  2 = bin-space segments after the scan (rsicnvnbn / rsicnvmed output),

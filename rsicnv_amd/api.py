@@ -35,7 +35,8 @@ EXPORTS = ["rsi_default_params", "rsi_hot_create", "rsi_hot_destroy", "rsi_hot_l
            "rsi_synth_append_genome_bgzf", "rsi_genome_text_open_samples", "rsi_genome_text_samples", "rsi_genome_text_max_resident",
            "rsi_genome_text_sample_depth", "rsi_genome_text_copy_sample_depth", "rsi_synth_append_genome_samples",
            "rsi_genome_bedgraph_open", "rsi_synth_append_genome_bedgraph",
-           "rsi_hot_set_exclude", "rsi_exclude_read_bed", "rsi_hot_debug_classify", "rsi_hot_debug_per_base"]
+           "rsi_hot_set_exclude", "rsi_exclude_read_bed", "rsi_hot_debug_classify", "rsi_hot_debug_per_base",
+           "rsi_hot_write_track", "rsi_hot_write_track_device", "rsi_hot_debug_track"]
 
 
 class RsiParams(C.Structure):
@@ -74,6 +75,11 @@ class RsiTextStats(C.Structure):
 class RsiInflateStats(C.Structure):
     _fields_ = [("format", C.c_int32), ("eof_block", C.c_int32), ("input_error", C.c_int32), ("pad", C.c_int32), ("compressed_bytes", C.c_int64), ("text_bytes", C.c_int64),
                 ("blocks", C.c_int64), ("t_inflate_kernel_ms", C.c_double), ("t_host_inflate_ms", C.c_double)]
+
+
+class RsiTrackStats(C.Structure):
+    _fields_ = [("n", C.c_int64), ("lines", C.c_int64), ("bytes", C.c_int64), ("slices", C.c_int64),
+                ("t_total_ms", C.c_double), ("t_kernel_ms", C.c_double), ("t_write_ms", C.c_double)]
 
 
 INFLATE_FORMATS = {0: "text", 1: "bgzf", 2: "gzip"}
@@ -216,6 +222,11 @@ def load_library():
     L.rsi_hot_debug_classify.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     L.rsi_hot_debug_per_base.argtypes = [C.c_void_p, C.POINTER(RsiParams), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
                                          C.POINTER(RsiChromStats)]
+    L.rsi_hot_write_track.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(RsiTrackStats)]
+    L.rsi_hot_write_track_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(RsiTrackStats)]
+    L.rsi_hot_debug_track.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_char_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+                                      C.POINTER(RsiTrackStats)]
+    L.rsi_hot_debug_track.restype = C.c_int64
     _lib = L
     return L
 
@@ -560,6 +571,48 @@ class RsiHot:
                     raise RsiError(int(k), self.lib.rsi_hot_last_error(self.ctx).decode())
                 return out
         raise KeyError(name)
+
+    TRACK_DEPTHS = {"raw": 0, "gc": 1}
+
+    @staticmethod
+    def _name_bytes(chrom):
+        return chrom if isinstance(chrom, bytes) else chrom.encode()
+
+    def write_track(self, which, chrom, path, append=False):
+        """The last run's depth as bedGraph lines of `chrom` (rsi_hot_write_track), replacing `path` or appended to it.
+        which: 0 / "raw" = the depth the run read, 1 / "gc" = the GC-adjusted depth (fetch("rd_gc"); RsiError after a
+        -NOGC run).  Returns the statistics (RsiTrackStats) as a dict."""
+        st = RsiTrackStats()
+        w = self.TRACK_DEPTHS.get(which, which)
+        self._check(self.lib.rsi_hot_write_track(self.ctx, int(w), self._name_bytes(chrom), os.fsencode(path), int(bool(append)), C.byref(st)))
+        return {f[0]: getattr(st, f[0]) for f in RsiTrackStats._fields_}
+
+    def write_track_device(self, d_values_ptr, n, chrom, path, append=False):
+        """Any int32[n] in HBM (a raw device pointer) as bedGraph lines of `chrom` (rsi_hot_write_track_device)."""
+        st = RsiTrackStats()
+        self._check(self.lib.rsi_hot_write_track_device(self.ctx, C.c_void_p(d_values_ptr), int(n), self._name_bytes(chrom), os.fsencode(path),
+                                                        int(bool(append)), C.byref(st)))
+        return {f[0]: getattr(st, f[0]) for f in RsiTrackStats._fields_}
+
+    def debug_track(self, values, chrom, pos0=0, slice_bases=0):
+        """The bedGraph text of a host int32 array through the device's track writer (test hook, rsi_hot_debug_track):
+        (bytes, stats).  pos0: added to every coordinate; slice_bases > 0: the slice length to work in."""
+        v = np.ascontiguousarray(values, dtype=np.int32)
+        name = self._name_bytes(chrom)
+        # room for every line at its longest; the call says when that was not enough
+        lines = (int(np.count_nonzero(v[1:] != v[:-1])) + 1) if v.size else 0
+        cap = lines * (len(name) + 4 + 2 * 20 + 11)
+        st = RsiTrackStats()
+        for _ in range(2):
+            out = np.zeros(max(cap, 1), dtype=np.uint8)
+            k = self.lib.rsi_hot_debug_track(self.ctx, v.ctypes.data if v.size else None, v.size, name, int(pos0), int(slice_bases),
+                                             out.ctypes.data, cap, C.byref(st))
+            if k < 0:
+                self._check(int(k))
+            if k <= cap:
+                break
+            cap = int(k)
+        return out[:k].tobytes(), {f[0]: getattr(st, f[0]) for f in RsiTrackStats._fields_}
 
     def phase_times(self):
         names = (C.c_char_p * 64)()

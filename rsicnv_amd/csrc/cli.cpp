@@ -7,6 +7,8 @@
 //  and say so.  A whole-genome file with several depth columns (a cohort, RNAME POS D1 ... DK) is
 // called sample by sample with -samples all|LIST: one OUT.k per selected column k.  A bedGraph depth file (RNAME START END
 // DEPTH: mosdepth, bedtools genomecov -bg / -bga) runs as the per-base file it stands for, whole or one chromosome (-c).
+// -track FILE saves the depth every chromosome was called from (raw, or GC-adjusted with -trackdepth gc) as one bedGraph file,
+// written by the device (rsi_hot_write_track) chromosome by chromosome into part files that are joined in row order at the end.
 #include <fcntl.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -33,6 +35,7 @@
 
 #include "../../include/rsi_hot.h"
 #include "hostmath.h"
+#include "track_host.h"
 
 namespace {
 
@@ -47,6 +50,8 @@ struct Options {
   bool samples_given = false, chr_given = false;
   std::string dformat;   // -dformat depth|bedgraph: the -d file's format (without: from its name, is_bedgraph_name)
   std::string excludefile;   // -x FILE: BED file of regions left out of calling, treated as N of the reference
+  std::string trackfile;     // -track FILE: the depth of every called chromosome as bedGraph (with -samples: FILE.k per column k)
+  std::string trackdepth = "raw";   // -trackdepth raw|gc: the depth as read, or after the GC adjustment
 };
 
 int usage() {
@@ -71,6 +76,8 @@ int usage() {
             << "   -samples all|k1,k2,... call depth columns k of RNAME POS D1 ... DK (1-based, at most 64) as samples: OUT.k each\n"
             << "   -dformat depth|bedgraph  read -d as per-base lines or as bedGraph (default: from the file name, see below)\n"
             << "   -x   FILE exclude the regions of a BED file (plain or gzip) from calling, see below\n"
+            << "   -track FILE  save the depth of every called chromosome as bedGraph (bedtools genomecov -bga), see below\n"
+            << "   -trackdepth raw|gc  the depth -track saves: as read (default), or GC-adjusted (what the calls are made from)\n"
             << "\nNote:\n"
             << "   This build runs the read-depth hot path on an MI355X; input is a read depth file\n"
             << "   (samtools mpileup BAM | cut -f2,4) with -c RNAME, a whole-genome depth file without -c\n"
@@ -92,6 +99,11 @@ int usage() {
             << "   input (-d with -c, whole-genome -d, -samples, bedGraph, -b, -gpus).  A mask adds to the chromosome's N regions,\n"
             << "   so their limits apply: above 128 merged regions the general compaction kernel runs instead of the streaming\n"
             << "   one, above 512 runs the regions are built on the host, above 4096 merged regions the chromosome is refused.\n"
+            << "   -track FILE: one line RNAME START END DEPTH per run of equal depth (0-based half-open, zero runs included), the\n"
+            << "   chromosomes in the order of the output rows; run-length encoded and formatted on the GPU.  Genome browsers and\n"
+            << "   bedtools read it, and so does -d FILE (name it .bedgraph, or -dformat bedgraph).  Works with every input but -gpus\n"
+            << "   above 1; with -samples it writes FILE.k per column k.  The depth of bases excluded with -x is saved unchanged.\n"
+            << "   -trackdepth gc saves the depth after the GC adjustment, before the cap (not with -NOGC).\n"
             << std::endl;
   return 0;
 }
@@ -145,6 +157,8 @@ void parse(int argc, char** argv, Options& o) {
     else if (s == "-samples") { o.samples = need(i); o.samples_given = true; ++i; }
     else if (s == "-dformat") { o.dformat = need(i); ++i; }
     else if (s == "-x") { o.excludefile = need(i); ++i; }
+    else if (s == "-track") { o.trackfile = need(i); ++i; }
+    else if (s == "-trackdepth") { o.trackdepth = need(i); ++i; }
     else { std::cerr << "unknown option " << s << std::endl; exit(usage()); }
   }
   if (o.rdfile.empty() && o.bamfile.empty()) { std::cerr << "need input file " << std::endl; exit(usage()); }
@@ -193,6 +207,8 @@ struct ChromOutput {
   bool populated = false;          // the chromosome was processed (has reads / could be read): it counts for the header
   bool fatal = false;              // the single-chromosome modes stop here (the reference exits)
   bool bad_input = false;          // the compressed depth file is broken: exit 1, no output file
+  size_t track_index = 0;          // -track: the chromosome's place in the order of the rows (set by the caller: names its part file)
+  bool track_failed = false;       // -track: its part could not be written (the reason is in the log): no track file
 };
 
 // One log line for a compressed depth file (none for plain text, whose logs stay as they were)
@@ -280,6 +296,17 @@ void report_chromosome(rsi_ctx* ctx, const Options& o, const std::string& chr, r
     FILE* f = fopen(dump.c_str(), "w");
     if (f) { for (int64_t i = 0; i < bs->n; ++i) fprintf(f, "%lld\t%d\n", (long long)i + 1, rd[(size_t)i]); fclose(f); }
     info << "RD of " << chr << " is saved to " << dump << "\n";
+  }
+  if (!o.trackfile.empty()) {   // -track: this chromosome's lines into its part file, from the depth the context still holds
+    rsi_track_stats tk;
+    const std::string part = rsitrack::part_path(o.trackfile, co.track_index);
+    if (rsi_hot_write_track(ctx, o.trackdepth == "gc" ? 1 : 0, chr.c_str(), part.c_str(), 0, &tk) != RSI_OK) {
+      info << "track: " << chr << ": " << rsi_hot_last_error(ctx) << "\n";
+      co.track_failed = true;
+    } else {
+      info << "track: " << chr << " " << tk.lines << " lines, " << tk.bytes << " bytes, " << tk.t_total_ms * 1e-3 << " s (kernels "
+           << tk.t_kernel_ms * 1e-3 << " s, write " << tk.t_write_ms * 1e-3 << " s)\n";
+    }
   }
   const rsi_chrom_stats* S = rsi_result_stats(res);
   info << "#Noseq regions excluded\n";
@@ -453,7 +480,10 @@ bool run_genome(const Options& o, const std::vector<int32_t>& cols, std::vector<
   const int nsamp = std::max<int>(1, (int)cols.size());
   const int max_held = rsi_genome_text_max_resident(g) - 1;   // the reader needs one free depth buffer for each new chromosome
   std::vector<Options> so(nsamp, o);   // sample k's plots go under <plotfolder>/k
-  for (int j = 0; j < (int)cols.size(); ++j) so[j].plotfolder = o.plotfolder + "/" + std::to_string(cols[j]);
+  for (int j = 0; j < (int)cols.size(); ++j) {
+    so[j].plotfolder = o.plotfolder + "/" + std::to_string(cols[j]);
+    if (!o.trackfile.empty()) so[j].trackfile = o.trackfile + "." + std::to_string(cols[j]);   // as -o: FILE.k
+  }
 
   struct Job { size_t idx; int j; rsi_genome_chrom c; const void* d_depth; std::shared_ptr<const std::string> fasta; double t_fasta; };
   std::deque<Job> jobs;
@@ -477,6 +507,7 @@ bool run_genome(const Options& o, const std::vector<int32_t>& cols, std::vector<
           jobs.pop_front();
         }
         ChromOutput co;
+        co.track_index = j.idx;
         std::ostringstream info;
         const std::string chr = j.c.name;
         info << "#processing " << chr << "\n";
@@ -489,7 +520,17 @@ bool run_genome(const Options& o, const std::vector<int32_t>& cols, std::vector<
           co.log = info.str();
           co.fatal = true;
         } else {
-          report_chromosome(ctx, so[(size_t)j.j], chr, res, &j.c.stats, nullptr, j.t_fasta, now_s() - t1, info, co);
+          // -track reads the reader's depth buffer through the context (rsi_hot_write_track: borrowed): the slot goes back only
+          // below, once every sample's report is through -- checked, since a buffer released early would be another chromosome's
+          bool slot_held;
+          { std::lock_guard<std::mutex> lk(mu); slot_held = pending[(size_t)j.c.slot] > 0; }
+          Options oj = so[(size_t)j.j];
+          if (!slot_held && !oj.trackfile.empty()) {
+            info << "track: " << chr << ": the depth buffer has been released\n";
+            co.track_failed = true;
+            oj.trackfile.clear();
+          }
+          report_chromosome(ctx, oj, chr, res, &j.c.stats, nullptr, j.t_fasta, now_s() - t1, info, co);
         }
         std::lock_guard<std::mutex> lk(mu);
         done_outs[j.idx][(size_t)j.j] = std::move(co);
@@ -598,6 +639,23 @@ bool select_samples(const Options& o, std::vector<int32_t>& cols, std::vector<st
   return true;
 }
 
+// -track, after the run: the parts of the chromosomes whose rows were written (`order`, in row order) become FILE; every part
+// 0 .. count - 1 is deleted whatever happened.  failed: a chromosome's part could not be written -- then there is no FILE.
+bool finish_track(const std::string& file, const std::vector<size_t>& order, size_t count, bool failed, std::ostream& log) {
+  if (file.empty()) return true;
+  std::string err;
+  if (failed) {
+    rsitrack::remove_parts(file, count);
+    remove(file.c_str());
+    err = "a chromosome's track could not be written (see above)";
+  } else if (rsitrack::join_parts(file, order, count, err)) {
+    std::cerr << "track written to " << file << std::endl; log << "track written to " << file << std::endl;
+    return true;
+  }
+  std::cerr << "rsicnv: -track: " << err << std::endl; log << "rsicnv: -track: " << err << std::endl;
+  return false;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -631,6 +689,16 @@ int main(int argc, char** argv) {
       // a file without lines for RNAME is found by the one pass of the reader (run_genome: exit 1, no output); a host pass
       // in front of it would read the text once more, up to RNAME's first line or through the whole file
     }
+  }
+  // -track: refused where it cannot work, before any output or device work
+  if (o.trackdepth != "raw" && o.trackdepth != "gc") {
+    std::cerr << "rsicnv: -trackdepth " << o.trackdepth << ": expected raw or gc" << std::endl;
+    return 1;
+  }
+  if (!o.trackfile.empty()) {
+    if (o.gpus > 1) { std::cerr << "rsicnv: -track: not with -gpus above 1 (the track is written by one device: -gpu INT picks it)" << std::endl; return 1; }
+    if (o.trackdepth == "gc" && !o.P.gcadjust) { std::cerr << "rsicnv: -trackdepth gc: -NOGC leaves no GC-adjusted depth to save" << std::endl; return 1; }
+    if (o.trackfile == o.outfile || o.trackfile == o.rdfile || o.trackfile == o.bamfile) { std::cerr << "rsicnv: -track: the track file is an input or the output file" << std::endl; return 1; }
   }
   // -x: a BED file with a bad line is refused as a whole, whichever chromosome the line names, before any output exists
   if (!o.excludefile.empty() && rsi_exclude_read_bed(o.excludefile.c_str(), "", 0, nullptr, nullptr, 0) < 0) {
@@ -715,8 +783,10 @@ int main(int argc, char** argv) {
     if (!ok) {   // no sample's output: the rows of a file that cannot be read through are not an answer
       std::cerr << "rsicnv: " << err << std::endl; log << "rsicnv: " << err << std::endl;
       for (size_t j = 0; j < cols.size(); ++j) { remove(out_k(j).c_str()); remove((out_k(j) + ".log").c_str()); }
+      if (!o.trackfile.empty()) for (size_t j = 0; j < cols.size(); ++j) rsitrack::remove_parts(o.trackfile + "." + std::to_string(cols[j]), chroms.size());
       return 1;
     }
+    bool tracks_ok = true;
     // each sample as its own genome run would write it: header, then its chromosomes until the first fatal one
     for (size_t j = 0; j < cols.size(); ++j) {
       const std::string path = out_k(j);
@@ -724,10 +794,13 @@ int main(int argc, char** argv) {
       std::string h = hdr.str();
       h.replace(h.find("#output:    " + o.outfile + "\n"), 12 + o.outfile.size() + 1, "#output:    " + path + "\n");
       slog << h << "#sample " << cols[j] << (sample_names[j].empty() ? "" : ": " + sample_names[j]) << "\n";
-      bool header_done = false;
+      bool header_done = false, track_failed = false;
+      std::vector<size_t> track_order;
       for (size_t i = 0; i < chroms.size(); ++i) {
         const ChromOutput& co = outs[i][j];
         std::cerr << co.log; slog << co.log;
+        track_failed = track_failed || co.track_failed;
+        if (co.populated) track_order.push_back(i);
         if (co.populated) {
           std::ofstream out(path.c_str(), header_done ? std::ios::app : std::ios::trunc);
           if (!header_done) {
@@ -742,9 +815,10 @@ int main(int argc, char** argv) {
         }
         if (co.fatal) break;
       }
+      if (!o.trackfile.empty() && !finish_track(o.trackfile + "." + std::to_string(cols[j]), track_order, chroms.size(), track_failed, slog)) tracks_ok = false;
     }
     std::cerr << summary; log << summary;
-    return 0;
+    return tracks_ok ? 0 : 1;
   }
 
   if (genome) {
@@ -756,34 +830,46 @@ int main(int argc, char** argv) {
       for (const auto& co : outs) { std::cerr << co[0].log; log << co[0].log; }
       std::cerr << "rsicnv: " << err << std::endl; log << "rsicnv: " << err << std::endl;
       remove(o.outfile.c_str());
+      rsitrack::remove_parts(o.trackfile, chroms.size());
       return 1;
     }
+    std::vector<size_t> track_order;
+    bool track_failed = false;
     for (size_t i = 0; i < chroms.size(); ++i) {
       emit(chroms[i], outs[i][0]);
+      track_failed = track_failed || outs[i][0].track_failed;
+      if (outs[i][0].populated) track_order.push_back(i);
       if (outs[i][0].fatal) break;
     }
     std::cerr << summary; log << summary;
-    return 0;
+    return finish_track(o.trackfile, track_order, chroms.size(), track_failed, log) ? 0 : 1;
   }
 
   if (o.gpus <= 0 || !many) {   // the reference's own shape: one chromosome after the other on one context
     int st = 0;
     rsi_ctx* ctx = rsi_hot_create(o.device, &st);
     if (!ctx) { std::cerr << "rsicnv: " << rsi_hot_last_error(nullptr) << std::endl; return 1; }
-    for (const std::string& chr : todo) {
+    std::vector<size_t> track_order;
+    bool track_failed = false;
+    for (size_t i = 0; i < todo.size(); ++i) {
+      const std::string& chr = todo[i];
       ChromOutput co;
+      co.track_index = i;
       process_chromosome(ctx, o, chr, many, co);
       if (co.bad_input) {   // as the genome mode: a depth file that cannot be read through gives no output
         std::cerr << co.log; log << co.log;
         remove(o.outfile.c_str());
+        rsitrack::remove_parts(o.trackfile, todo.size());
         rsi_hot_destroy(ctx);
         return 1;
       }
       emit(chr, co);
+      track_failed = track_failed || co.track_failed;
+      if (co.populated) track_order.push_back(i);
       if (co.fatal) break;
     }
     rsi_hot_destroy(ctx);
-    return 0;
+    return finish_track(o.trackfile, track_order, todo.size(), track_failed, log) ? 0 : 1;
   }
 
   // ---- -gpus N: the iterations of the loop are independent.  Chromosomes go to devices longest first
@@ -825,6 +911,7 @@ int main(int argc, char** argv) {
     }
   }
   std::vector<ChromOutput> outs(todo.size());
+  for (size_t i = 0; i < todo.size(); ++i) outs[i].track_index = i;
   std::vector<std::thread> threads;
   std::vector<std::atomic<int>> next(pools.size());
   for (auto& a : next) a = 0;
@@ -840,7 +927,13 @@ int main(int argc, char** argv) {
         }
       });
   for (auto& t : threads) t.join();
-  for (size_t i = 0; i < todo.size(); ++i) emit(todo[i], outs[i]);
+  std::vector<size_t> track_order;
+  bool track_failed = false;
+  for (size_t i = 0; i < todo.size(); ++i) {
+    emit(todo[i], outs[i]);
+    track_failed = track_failed || outs[i].track_failed;
+    if (outs[i].populated) track_order.push_back(i);
+  }
   for (rsi_pool* pl : pools) rsi_pool_destroy(pl);
-  return 0;
+  return finish_track(o.trackfile, track_order, todo.size(), track_failed, log) ? 0 : 1;   // (-track: one device only, -gpus 1)
 }

@@ -526,4 +526,33 @@ void launch_bam_depth(const void* data, const uint32_t* rec_off, int nrec, int t
 int scan_tiles(long long n);
 void launch_inclusive_scan_i32(int32_t* x, long long n, int32_t* tile_scratch, hipStream_t stream);
 
+// ---- depth track: an int32 array as bedGraph text, run-length encoded and formatted on the device (kernels_track.hip) ----
+// One line "NAME \t pos0+start \t pos0+end \t value \n" per maximal run of equal values of v[0, n), worked through in slices
+// [b, e) of bases.  A run start is i == 0 or v[i] != v[i - 1] -- read from the whole array, so slicing moves no start.  A line is
+// written by the slice that sees its END: the start of the last run seen so far stays open in TrackState::carry and becomes the
+// first entry of the next slice's start list; the last slice (e == n) closes it with n.  Per slice: launch_track_starts, then
+// launch_track_line_bytes, then -- once the host has read the state's nlines / nbytes and checked them against its buffers --
+// launch_track_format.
+struct TrackState {
+  long long carry;     // start of the open run (index into v), -1 before the first slice
+  long long nstarts;   // entries of starts[] for this slice, the carried one included (the closing n not)
+  long long nlines;    // lines this slice writes
+  long long nbytes;    // their bytes
+};
+struct TrackName { char s[256]; int len; };   // the chromosome name, at most 255 bytes, travels with the kernel arguments
+constexpr int kTrackTile = 256;               // bases (passes 1-3) or lines (passes 4-5) per workgroup
+__host__ __device__ inline int track_tiles(long long count) { return (int)((count + kTrackTile - 1) / kTrackTile); }
+// Passes 1-3: run starts of [b, e) flagged and counted per tile, the tile counts scanned (one workgroup), the starts
+// scattered to starts[] behind the carried one.  tiles: track_tiles(e - b) + 1 words; starts: e - b + 2 entries; e - b > 0.
+void launch_track_starts(const int32_t* v, long long b, long long e, long long n, unsigned int* tiles, long long* starts, TrackState* st,
+                         hipStream_t stream);
+// Pass 4: every line's byte length from digit counts, summed per tile of lines and scanned (one workgroup): st->nbytes, and
+// st->carry for the next slice.  max_lines: e - b + 1 (the grid; workgroups beyond st->nlines leave at once); ltiles:
+// track_tiles(max_lines) + 1 words.
+void launch_track_line_bytes(const int32_t* v, const long long* starts, TrackState* st, long long pos0, int name_len, long long max_lines,
+                             unsigned int* ltiles, hipStream_t stream);
+// Pass 5: line j of nlines at its byte offset in text[0, cap); a line that would pass cap is not written.
+void launch_track_format(const int32_t* v, const long long* starts, const unsigned int* ltiles, long long nlines, long long pos0,
+                         const TrackName& name, char* text, long long cap, hipStream_t stream);
+
 }  // namespace rsik

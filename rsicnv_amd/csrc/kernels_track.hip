@@ -1,0 +1,195 @@
+// kernels_track.hip -- an int32 array in HBM as bedGraph text (bedtools genomecov -bga: one line per maximal run of equal
+// values, zeros included), run-length encoded and formatted on the device so that only finished text crosses PCIe.  The mirror
+// image of the bedGraph reader's expansion (kernels_io.hip); the passes and the slice rule: DESIGN.md 6f.
+// All of it is integer work: digits come from comparisons and divisions by ten, nothing is printed through printf.
+#include "kernels.h"
+
+namespace rsik {
+namespace {
+
+static_assert(kTrackTile == 256, "the kernels below are written for four waves of 64 lanes");
+
+// Exclusive prefix of v over the workgroup's 256 threads; *total: the workgroup's sum (in every thread).  s_w: four words of LDS.
+__device__ inline unsigned int wg_exscan_u32(unsigned int v, unsigned int* s_w, unsigned int* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const unsigned int incl = (unsigned int)wave_incl_scan((int)v);
+  __syncthreads();   // the previous call's readers are through with s_w
+  if (lane == 63) s_w[wave] = incl;
+  __syncthreads();
+  unsigned int base = 0, tot = 0;
+  for (int w = 0; w < kTrackTile / 64; ++w) { const unsigned int s = s_w[w]; if (w < wave) base += s; tot += s; }
+  *total = tot;
+  return base + incl - v;
+}
+
+__device__ inline bool run_start(const int32_t* __restrict__ v, long long i) { return i == 0 || v[i] != v[i - 1]; }
+
+// ---- pass 1: run starts per tile of 256 bases ----
+__global__ __launch_bounds__(kTrackTile) void k_track_count(const int32_t* __restrict__ v, long long b, long long e,
+                                                            unsigned int* __restrict__ tiles) {
+  __shared__ unsigned int s_w[kTrackTile / 64];
+  const long long i = b + (long long)blockIdx.x * kTrackTile + threadIdx.x;
+  const unsigned int flag = i < e && run_start(v, i) ? 1u : 0u;
+  unsigned int total;
+  (void)wg_exscan_u32(flag, s_w, &total);
+  if (threadIdx.x == 0) tiles[blockIdx.x] = total;
+}
+
+// Exclusive scan of t[0, nt) in place by one workgroup, the first entry becoming `base`; returns base + the sum (every thread).
+__device__ inline unsigned long long scan_tile_words(unsigned int* __restrict__ t, int nt, unsigned int base, unsigned int* s_w) {
+  unsigned long long run = base;
+  for (int t0 = 0; t0 < nt; t0 += kTrackTile) {
+    const int k = t0 + (int)threadIdx.x;
+    const unsigned int x = k < nt ? t[k] : 0u;
+    unsigned int total;
+    const unsigned int ex = wg_exscan_u32(x, s_w, &total);
+    if (k < nt) t[k] = (unsigned int)run + ex;
+    run += total;
+  }
+  return run;
+}
+
+// ---- pass 2: the tile counts become offsets into starts[]; the carried start in front, the closing n behind the last slice's ----
+__global__ __launch_bounds__(kTrackTile) void k_track_scan_starts(unsigned int* __restrict__ tiles, int ntiles, long long* __restrict__ starts,
+                                                                  TrackState* __restrict__ st, long long e, long long n) {
+  __shared__ unsigned int s_w[kTrackTile / 64];
+  const long long carry = st->carry;
+  const unsigned long long m = scan_tile_words(tiles, ntiles, carry >= 0 ? 1u : 0u, s_w);
+  if (threadIdx.x == 0) {
+    if (carry >= 0) starts[0] = carry;
+    const bool last = e == n;
+    if (last) starts[m] = n;
+    st->nstarts = (long long)m;
+    st->nlines = last ? (long long)m : (m > 0 ? (long long)m - 1 : 0);   // the last start stays open until a later slice ends its run
+  }
+}
+
+// ---- pass 3: the starts of [b, e) into starts[], in order ----
+__global__ __launch_bounds__(kTrackTile) void k_track_scatter(const int32_t* __restrict__ v, long long b, long long e,
+                                                              const unsigned int* __restrict__ tiles, long long* __restrict__ starts) {
+  __shared__ unsigned int s_w[kTrackTile / 64];
+  const long long i = b + (long long)blockIdx.x * kTrackTile + threadIdx.x;
+  const unsigned int flag = i < e && run_start(v, i) ? 1u : 0u;
+  unsigned int total;
+  const unsigned int rank = wg_exscan_u32(flag, s_w, &total);
+  if (flag) starts[(unsigned long long)tiles[blockIdx.x] + rank] = i;
+}
+
+// ---- decimal digits without division where a count is enough ----
+__device__ inline int dec_len_u32(unsigned int x) {
+  return x < 10u ? 1 : x < 100u ? 2 : x < 1000u ? 3 : x < 10000u ? 4 : x < 100000u ? 5 : x < 1000000u ? 6 : x < 10000000u ? 7
+       : x < 100000000u ? 8 : x < 1000000000u ? 9 : 10;
+}
+__device__ inline int dec_len_u64(unsigned long long x) {
+  if (x <= 0xffffffffull) return dec_len_u32((unsigned int)x);
+  int d = 10;
+  unsigned long long p = 10000000000ull;   // 10^10: the smallest number of 11 digits
+  while (x >= p) { ++d; if (d == 20) break; p *= 10ull; }   // 10^19 is the last power of ten below 2^64
+  return d;
+}
+__device__ inline int dec_len_i64(long long x) { return x < 0 ? 1 + dec_len_u64(0ull - (unsigned long long)x) : dec_len_u64((unsigned long long)x); }
+__device__ inline int dec_len_i32(int x) { return x < 0 ? 1 + dec_len_u32(0u - (unsigned int)x) : dec_len_u32((unsigned int)x); }   // INT32_MIN: 11
+// x as `len` = its digit count characters at p, last digit first; the 64-bit divisions end once the rest fits 32 bits
+__device__ inline void put_dec(char* __restrict__ p, int len, unsigned long long x) {
+  while (x > 0xffffffffull) { p[--len] = (char)('0' + (int)(x % 10ull)); x /= 10ull; }
+  unsigned int y = (unsigned int)x;
+  do { p[--len] = (char)('0' + (int)(y % 10u)); y /= 10u; } while (len > 0);
+}
+__device__ inline char* put_i64(char* __restrict__ p, long long x, int len) {
+  if (x < 0) { p[0] = '-'; put_dec(p + 1, len - 1, 0ull - (unsigned long long)x); }
+  else put_dec(p, len, (unsigned long long)x);
+  return p + len;
+}
+
+// Where the lines come from.  The length, scan and format passes see (start, end, value) triples only: another source of
+// triples (a per-bin signal, say) takes the same passes with a struct of its own.
+struct RunLines {
+  const int32_t* __restrict__ v;
+  const long long* __restrict__ starts;
+  __device__ void get(long long j, long long& s, long long& e, int& val) const { s = starts[j]; e = starts[j + 1]; val = v[s]; }
+};
+struct LineShape { long long s, e; int val, ls, le, lv; };
+template <class Lines>
+__device__ inline int line_shape(const Lines& src, long long j, long long pos0, int name_len, LineShape& L) {
+  src.get(j, L.s, L.e, L.val);
+  L.s += pos0; L.e += pos0;
+  L.ls = dec_len_i64(L.s); L.le = dec_len_i64(L.e); L.lv = dec_len_i32(L.val);
+  return name_len + 4 + L.ls + L.le + L.lv;   // three tabs and the newline
+}
+
+// ---- pass 4: bytes per tile of 256 lines ----
+template <class Lines>
+__global__ __launch_bounds__(kTrackTile) void k_track_line_bytes(Lines src, const TrackState* __restrict__ st, long long pos0, int name_len,
+                                                                 unsigned int* __restrict__ ltiles) {
+  __shared__ unsigned int s_w[kTrackTile / 64];
+  const long long nlines = st->nlines;
+  if ((long long)blockIdx.x * kTrackTile >= nlines) return;   // the grid covers the most lines a slice can have
+  const long long j = (long long)blockIdx.x * kTrackTile + threadIdx.x;
+  LineShape L;
+  const unsigned int len = j < nlines ? (unsigned int)line_shape(src, j, pos0, name_len, L) : 0u;
+  unsigned int total;
+  (void)wg_exscan_u32(len, s_w, &total);
+  if (threadIdx.x == 0) ltiles[blockIdx.x] = total;
+}
+
+// ... scanned: every tile's byte offset, the slice's bytes, and the run left open for the next slice
+__global__ __launch_bounds__(kTrackTile) void k_track_scan_lines(unsigned int* __restrict__ ltiles, const long long* __restrict__ starts,
+                                                                 TrackState* __restrict__ st) {
+  __shared__ unsigned int s_w[kTrackTile / 64];
+  const unsigned long long bytes = scan_tile_words(ltiles, track_tiles(st->nlines), 0u, s_w);
+  if (threadIdx.x == 0) {
+    st->nbytes = (long long)bytes;
+    if (st->nstarts > 0) st->carry = starts[st->nstarts - 1];
+  }
+}
+
+// ---- pass 5: one thread per line ----
+template <class Lines>
+__global__ __launch_bounds__(kTrackTile) void k_track_format(Lines src, const unsigned int* __restrict__ ltiles, long long nlines, long long pos0,
+                                                             const TrackName name, char* __restrict__ text, long long cap) {
+  __shared__ unsigned int s_w[kTrackTile / 64];
+  const long long j = (long long)blockIdx.x * kTrackTile + threadIdx.x;
+  LineShape L;
+  const unsigned int len = j < nlines ? (unsigned int)line_shape(src, j, pos0, name.len, L) : 0u;
+  unsigned int total;
+  const unsigned long long off = (unsigned long long)ltiles[blockIdx.x] + wg_exscan_u32(len, s_w, &total);
+  if (len == 0u || (long long)(off + len) > cap) return;
+  char* p = text + off;
+  for (int k = 0; k < name.len; ++k) p[k] = name.s[k];
+  p += name.len;
+  *p++ = '\t';
+  p = put_i64(p, L.s, L.ls);
+  *p++ = '\t';
+  p = put_i64(p, L.e, L.le);
+  *p++ = '\t';
+  p = put_i64(p, (long long)L.val, L.lv);
+  *p = '\n';
+}
+
+}  // namespace
+
+void launch_track_starts(const int32_t* v, long long b, long long e, long long n, unsigned int* tiles, long long* starts, TrackState* st,
+                         hipStream_t stream) {
+  const int ntiles = track_tiles(e - b);
+  if (ntiles <= 0) return;
+  RSI_LAUNCH(k_track_count, dim3(ntiles), dim3(kTrackTile), 0, stream, v, b, e, tiles);
+  RSI_LAUNCH(k_track_scan_starts, dim3(1), dim3(kTrackTile), 0, stream, tiles, ntiles, starts, st, e, n);
+  RSI_LAUNCH(k_track_scatter, dim3(ntiles), dim3(kTrackTile), 0, stream, v, b, e, tiles, starts);
+}
+
+void launch_track_line_bytes(const int32_t* v, const long long* starts, TrackState* st, long long pos0, int name_len, long long max_lines,
+                             unsigned int* ltiles, hipStream_t stream) {
+  const int ntiles = track_tiles(max_lines);
+  if (ntiles <= 0) return;
+  RSI_LAUNCH(k_track_line_bytes<RunLines>, dim3(ntiles), dim3(kTrackTile), 0, stream, RunLines{v, starts}, st, pos0, name_len, ltiles);
+  RSI_LAUNCH(k_track_scan_lines, dim3(1), dim3(kTrackTile), 0, stream, ltiles, starts, st);
+}
+
+void launch_track_format(const int32_t* v, const long long* starts, const unsigned int* ltiles, long long nlines, long long pos0,
+                         const TrackName& name, char* text, long long cap, hipStream_t stream) {
+  const int ntiles = track_tiles(nlines);
+  if (ntiles <= 0) return;
+  RSI_LAUNCH(k_track_format<RunLines>, dim3(ntiles), dim3(kTrackTile), 0, stream, RunLines{v, starts}, ltiles, nlines, pos0, name, text, cap);
+}
+
+}  // namespace rsik

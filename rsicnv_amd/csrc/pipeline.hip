@@ -1630,6 +1630,8 @@ int grid_debug_mad(rsi_ctx* ctx, const float* d_x, const int32_t* d_mask, int64_
 }
 }  // namespace
 
+namespace rsip { int ensure_rd_gc(rsi_ctx* ctx) { return materialize_rd_gc(ctx); } }
+
 // ------------------------------------------------------------------------------------------
 extern "C" {
 
@@ -1680,6 +1682,7 @@ void rsi_hot_destroy(rsi_ctx* ctx) {
   if (ctx->mirror) (void)hipHostFree(ctx->mirror);
   if (ctx->mailbox) (void)hipHostFree(ctx->mailbox);
   for (int b = 0; b < 2; ++b) if (ctx->text_pin[b]) (void)hipHostFree(ctx->text_pin[b]);
+  track_free(ctx);
   if (ctx->sync_ev) (void)hipEventDestroy(ctx->sync_ev);
   if (ctx->copy_ev) (void)hipEventDestroy(ctx->copy_ev);   // (copy_stream is the device's shared one: never destroyed)
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);

@@ -199,6 +199,15 @@ struct rsi_ctx {
   std::vector<std::pair<int64_t, int64_t>> excl_armed;
   std::vector<int64_t> excl_host;   // the run's intervals clipped to its n, starts then ends: the upload's source
   DevBuf excl_dev;                  // the same in HBM, grow-only
+  // Depth-track writer (track.hip): its workspace, allocated at the first call and for what the call's slices need -- never more
+  // than track_host.h's bounds, whatever the chromosome -- and its events (timing around the kernel groups, one behind each
+  // pinned buffer's copy).  Freed by rsi_hot_destroy.
+  struct TrackWs {
+    void* dev = nullptr; size_t dev_bytes = 0;           // text, starts, tiles, line tiles, state
+    char* pin[2] = {nullptr, nullptr}; size_t pin_bytes = 0;   // two text buffers: one is written to the file while the other fills
+    void* pin_state = nullptr;                           // two TrackState: the device's, read back per slice; the initial one
+    hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  } track;
 };
 
 namespace rsip {
@@ -352,6 +361,10 @@ inline void normalize_intervals(std::vector<std::pair<int64_t, int64_t>>& v, int
     else v.push_back(r);
   }
 }
+// The GC-rescaled depth of the last run in ctx->rd_gc (pipeline.hip: built on demand); RSI_ERR_BAD_ARG after a -NOGC run.
+int ensure_rd_gc(rsi_ctx* ctx);
+void track_free(rsi_ctx* ctx);   // track.hip: the track writer's workspace and events
+
 struct ExcludeOneShot {   // first statement of a run entry point: the armed mask does not outlive the call
   rsi_ctx* ctx;
   explicit ExcludeOneShot(rsi_ctx* c) : ctx(c) {}

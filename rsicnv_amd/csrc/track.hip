@@ -1,0 +1,225 @@
+// track.hip -- depth tracks as bedGraph (include/rsi_hot.h: rsi_hot_write_track, _write_track_device, rsi_hot_debug_track).  The
+// host drives kernels_track.hip slice by slice: the passes that find and measure a slice's lines, one wait for their two numbers,
+// the format pass and the copy of exactly those bytes into one of two pinned buffers; while that runs, the slice before goes
+// out through write().  Slice rule, bounds and numbers: DESIGN.md 6f.
+#include "pipeline_internal.h"
+#include "track_host.h"
+
+using namespace rsik;
+using namespace rsip;
+
+namespace rsip {
+
+void track_free(rsi_ctx* ctx) {
+  rsi_ctx::TrackWs& w = ctx->track;
+  if (w.dev) (void)hipFree(w.dev);
+  for (char*& p : w.pin) { if (p) (void)hipHostFree(p); p = nullptr; }
+  if (w.pin_state) (void)hipHostFree(w.pin_state);
+  for (hipEvent_t& e : w.ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+  w.dev = w.pin_state = nullptr; w.dev_bytes = w.pin_bytes = 0;
+}
+
+}  // namespace rsip
+
+namespace {
+
+// Where a slice's text goes: a file, or (the test hook) host memory.
+struct TrackSink {
+  int fd = -1;
+  std::string* text = nullptr;
+  bool put(const char* p, size_t len) {
+    if (text) { text->append(p, len); return true; }
+    return rsitrack::write_all(fd, p, len);
+  }
+};
+
+enum { kEvP0, kEvP1, kEvF0, kEvF1 = kEvF0 + 2, kEvCopy = kEvF1 + 2 };   // events: the measuring passes; per pinned buffer: format begin / end, copy done
+
+struct TrackLayout { size_t text, starts, tiles, ltiles, state, bytes; };
+TrackLayout track_layout(const rsitrack::Plan& p) {
+  auto up = [](size_t x) { return (x + 255) & ~size_t(255); };
+  TrackLayout L;
+  L.text = 0;
+  L.starts = up((size_t)p.text_cap);
+  L.tiles = L.starts + up((size_t)(p.slice + 2) * 8);
+  L.ltiles = L.tiles + up((size_t)(track_tiles(p.slice) + 1) * 4);
+  L.state = L.ltiles + up((size_t)(track_tiles(p.slice + 1) + 1) * 4);
+  L.bytes = L.state + up(sizeof(TrackState));
+  return L;
+}
+
+int track_ensure(rsi_ctx* ctx, const rsitrack::Plan& p, const TrackLayout& L) {
+  rsi_ctx::TrackWs& w = ctx->track;
+  for (hipEvent_t& e : w.ev) if (!e) HIPCHK(hipEventCreate(&e));
+  if (!w.pin_state) HIPCHK(hipHostMalloc(&w.pin_state, 2 * sizeof(TrackState), hipHostMallocDefault));
+  if (L.bytes > w.dev_bytes) {
+    if (w.dev) (void)hipFree(w.dev);
+    w.dev = nullptr; w.dev_bytes = 0;
+    HIPCHK(hipMalloc(&w.dev, L.bytes));
+    w.dev_bytes = L.bytes;
+  }
+  if ((size_t)p.text_cap > w.pin_bytes) {
+    for (char*& b : w.pin) { if (b) (void)hipHostFree(b); b = nullptr; }
+    w.pin_bytes = 0;
+    for (char*& b : w.pin) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&b), (size_t)p.text_cap, hipHostMallocDefault));
+    w.pin_bytes = (size_t)p.text_cap;
+  }
+  return RSI_OK;
+}
+
+// d_v[0, n) as bedGraph lines of `chrom` into the sink.
+int track_run(rsi_ctx* ctx, const int32_t* d_v, int64_t n, const char* chrom, int64_t pos0, int64_t slice_bases, TrackSink& sink,
+              rsi_track_stats* stats) {
+  const double t_begin = now_ms();
+  rsi_track_stats S;
+  memset(&S, 0, sizeof(S));
+  if (stats) *stats = S;
+  const int name_len = rsitrack::name_length(chrom);
+  if (name_len < 0) return fail(ctx, RSI_ERR_BAD_ARG, "track: the name must have 1 to 255 bytes and no tab or newline");
+  rsitrack::Plan plan;
+  if (!rsitrack::plan(name_len, pos0, n, slice_bases, plan)) return fail(ctx, RSI_ERR_BAD_ARG, "track: bad length or coordinate offset");
+  S.n = n;
+  if (n == 0) { if (stats) *stats = S; return RSI_OK; }
+  if (!d_v) return fail(ctx, RSI_ERR_BAD_ARG, "track: no values");
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!ctx_enter(ctx)) return RSI_ERR_HIP;
+  const TrackLayout L = track_layout(plan);
+  int rc = track_ensure(ctx, plan, L);
+  if (rc != RSI_OK) return rc;
+  rsi_ctx::TrackWs& w = ctx->track;
+  char* d_text = static_cast<char*>(w.dev) + L.text;
+  long long* d_starts = reinterpret_cast<long long*>(static_cast<char*>(w.dev) + L.starts);
+  unsigned int* d_tiles = reinterpret_cast<unsigned int*>(static_cast<char*>(w.dev) + L.tiles);
+  unsigned int* d_ltiles = reinterpret_cast<unsigned int*>(static_cast<char*>(w.dev) + L.ltiles);
+  TrackState* d_st = reinterpret_cast<TrackState*>(static_cast<char*>(w.dev) + L.state);
+  TrackState* h_st = static_cast<TrackState*>(w.pin_state);
+  TrackName name;
+  memset(&name, 0, sizeof(name));
+  memcpy(name.s, chrom, (size_t)name_len);
+  name.len = name_len;
+  hipStream_t st = ctx->stream;
+
+  // Whatever goes wrong below, nothing of this call is still queued when it returns: the copies land in the context's buffers.
+  auto leave = [&](int code, const std::string& msg) { (void)ctx_sync(ctx); return fail(ctx, code, msg); };
+  auto hip_failed = [&](hipError_t e, const char* what) { return leave(RSI_ERR_HIP, std::string("track: ") + what + ": " + hipGetErrorString(e)); };
+  auto elapsed = [&](int a, int b) { float ms = 0.f; return hipEventElapsedTime(&ms, w.ev[a], w.ev[b]) == hipSuccess ? (double)ms : 0.0; };
+
+  h_st[1] = TrackState{-1, 0, 0, 0};
+  hipError_t e = hipMemcpyAsync(d_st, &h_st[1], sizeof(TrackState), hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) return hip_failed(e, "hipMemcpyAsync");
+  int pending = -1, next_buf = 0;   // the pinned buffer whose slice is formatted and on its way, not yet in the sink
+  int64_t pending_bytes = 0;
+  auto flush = [&]() -> int {       // the pending slice: wait for its copy, note its format time, hand it to the sink
+    if (pending < 0) return RSI_OK;
+    const hipError_t ew = event_wait(w.ev[kEvCopy + pending]);
+    if (ew == hipErrorLaunchTimeOut) ctx->poisoned = true;
+    if (ew != hipSuccess) return fail(ctx, RSI_ERR_HIP, std::string("track: waiting for a slice's text: ") + hipGetErrorString(ew));
+    S.t_kernel_ms += elapsed(kEvF0 + pending, kEvF1 + pending);
+    const double t0 = now_ms();
+    const bool ok = sink.put(w.pin[pending], (size_t)pending_bytes);
+    const int err = errno;
+    S.t_write_ms += now_ms() - t0;
+    pending = -1;
+    if (!ok) return fail(ctx, RSI_ERR_INTERNAL, std::string("track: write failed: ") + strerror(err));
+    return RSI_OK;
+  };
+  for (int64_t b = 0; b < n; b += plan.slice) {
+    const int64_t end = std::min(n, b + plan.slice);
+    (void)hipEventRecord(w.ev[kEvP0], st);
+    launch_track_starts(d_v, b, end, n, d_tiles, d_starts, d_st, st);
+    launch_track_line_bytes(d_v, d_starts, d_st, pos0, name_len, end - b + 1, d_ltiles, st);
+    (void)hipEventRecord(w.ev[kEvP1], st);
+    e = hipMemcpyAsync(&h_st[0], d_st, sizeof(TrackState), hipMemcpyDeviceToHost, st);
+    if (e != hipSuccess) return hip_failed(e, "hipMemcpyAsync");
+    e = ctx_sync(ctx);   // (the slice before has been formatted and copied by now too: same stream)
+    if (e != hipSuccess) return fail(ctx, RSI_ERR_HIP, std::string("track: waiting for a slice's line count: ") + hipGetErrorString(e));
+    S.t_kernel_ms += elapsed(kEvP0, kEvP1);
+    const int64_t nlines = h_st[0].nlines, nbytes = h_st[0].nbytes;
+    // the format pass writes nbytes of text for nlines lines: both must be what this slice's buffers were sized for
+    if (nlines < 0 || nlines > end - b + 1 || nbytes < 0 || nbytes > plan.text_cap || nbytes > nlines * plan.max_line)
+      return leave(RSI_ERR_INTERNAL, "track: a slice's line or byte count is out of range");
+    ++S.slices;
+    S.lines += nlines;
+    S.bytes += nbytes;
+    int fresh = -1;
+    if (nlines > 0) {
+      fresh = next_buf;
+      next_buf ^= 1;   // (at most one slice is pending, in the other buffer)
+      (void)hipEventRecord(w.ev[kEvF0 + fresh], st);
+      launch_track_format(d_v, d_starts, d_ltiles, nlines, pos0, name, d_text, plan.text_cap, st);
+      (void)hipEventRecord(w.ev[kEvF1 + fresh], st);
+      e = hipMemcpyAsync(w.pin[fresh], d_text, (size_t)nbytes, hipMemcpyDeviceToHost, st);
+      if (e == hipSuccess) e = hipEventRecord(w.ev[kEvCopy + fresh], st);
+      if (e != hipSuccess) return hip_failed(e, "hipMemcpyAsync");
+    }
+    if ((rc = flush()) != RSI_OK) { (void)ctx_sync(ctx); return rc; }   // the slice before, while this one is formatted and copied
+    if (fresh >= 0) { pending = fresh; pending_bytes = nbytes; }
+  }
+  if ((rc = flush()) != RSI_OK) { (void)ctx_sync(ctx); return rc; }
+  e = ctx_sync(ctx);   // collects a launch error of the last format pass
+  if (e != hipSuccess) return fail(ctx, RSI_ERR_HIP, std::string("track: ") + hipGetErrorString(e));
+  S.t_total_ms = now_ms() - t_begin;
+  if (stats) *stats = S;
+  return RSI_OK;
+}
+
+int track_to_file(rsi_ctx* ctx, const int32_t* d_v, int64_t n, const char* chrom, const char* path, int append, rsi_track_stats* stats) {
+  if (!path || !path[0]) return fail(ctx, RSI_ERR_BAD_ARG, "track: no path");
+  if (rsitrack::name_length(chrom) < 0) return fail(ctx, RSI_ERR_BAD_ARG, "track: the name must have 1 to 255 bytes and no tab or newline");
+  TrackSink sink;
+  sink.fd = ::open(path, O_WRONLY | O_CREAT | (append ? O_APPEND : O_TRUNC), 0644);
+  if (sink.fd < 0) return fail(ctx, RSI_ERR_INTERNAL, std::string("track: cannot open ") + path + ": " + strerror(errno));
+  int rc = track_run(ctx, d_v, n, chrom, 0, 0, sink, stats);
+  if (::close(sink.fd) != 0 && rc == RSI_OK) rc = fail(ctx, RSI_ERR_INTERNAL, std::string("track: write failed: ") + strerror(errno));
+  return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rsi_hot_write_track(rsi_ctx* ctx, int which, const char* chrom, const char* path, int append, rsi_track_stats* stats) {
+  if (!ctx) return fail(ctx, RSI_ERR_BAD_ARG, "null context");
+  if (which != 0 && which != 1) return fail(ctx, RSI_ERR_BAD_ARG, "track: which must be 0 (raw depth) or 1 (GC-adjusted depth)");
+  if (!ctx->last_depth || ctx->n <= 0) return fail(ctx, RSI_ERR_BAD_ARG, "track: this context has run no chromosome");
+  const int32_t* d_v = ctx->last_depth;
+  if (which == 1) {
+    HIPCHK(hipSetDevice(ctx->device));
+    if (!ctx_enter(ctx)) return RSI_ERR_HIP;
+    const int rc = ensure_rd_gc(ctx);   // RSI_ERR_BAD_ARG after a -NOGC run
+    if (rc != RSI_OK) return rc;
+    d_v = ctx->rd_gc.as<int32_t>();
+  }
+  return track_to_file(ctx, d_v, ctx->n, chrom, path, append, stats);
+}
+
+int rsi_hot_write_track_device(rsi_ctx* ctx, const void* d_values, int64_t n, const char* chrom, const char* path, int append,
+                               rsi_track_stats* stats) {
+  if (!ctx) return fail(ctx, RSI_ERR_BAD_ARG, "null context");
+  if (n < 0 || (n > 0 && !d_values)) return fail(ctx, RSI_ERR_BAD_ARG, "track: bad array");
+  return track_to_file(ctx, static_cast<const int32_t*>(d_values), n, chrom, path, append, stats);
+}
+
+int64_t rsi_hot_debug_track(rsi_ctx* ctx, const int32_t* values, int64_t n, const char* chrom, int64_t pos0, int64_t slice_bases, char* out,
+                            int64_t cap, rsi_track_stats* stats) {
+  if (!ctx) return fail(ctx, RSI_ERR_BAD_ARG, "null context");
+  if (n < 0 || (n > 0 && !values) || slice_bases < 0) return fail(ctx, RSI_ERR_BAD_ARG, "track: bad argument");
+  if (n > 0) {
+    HIPCHK(hipSetDevice(ctx->device));
+    if (!ctx_enter(ctx)) return RSI_ERR_HIP;
+    if (ctx->last_depth == ctx->in_depth.p) ctx->last_depth = nullptr;   // the last run's depth is about to be overwritten
+    HIPCHK(ctx->in_depth.ensure((size_t)(n + 4) * 4));
+    ctx->n_in = n;
+    HIPCHK(hipMemcpyAsync(ctx->in_depth.p, values, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(CTX_SYNC());   // the caller's array is pageable: free again once this returns
+  }
+  std::string text;
+  TrackSink sink;
+  sink.text = &text;
+  const int rc = track_run(ctx, ctx->in_depth.as<int32_t>(), n, chrom, pos0, slice_bases, sink, stats);
+  if (rc != RSI_OK) return rc;
+  if (out && (int64_t)text.size() <= cap) memcpy(out, text.data(), text.size());
+  return (int64_t)text.size();
+}
+
+}  // extern "C"

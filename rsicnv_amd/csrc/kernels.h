@@ -418,7 +418,7 @@ struct CandJob {            // one isitcnvwrap test, prepared on the host from t
   int32_t budget;           // maxchkbp*10: thinning threshold
   int32_t cut;              // bit 0 / 1: the left / right chain was cut short by the host (the kernel reports when it runs out)
   double right_cap;         // 2*chklen*d (the right side appends while used < right_cap)
-  int64_t iscratch_off;     // int32 scratch: (top+1) + capacity + min(capacity, budget), each rounded up to a multiple of 4; offset a multiple of 4
+  int64_t iscratch_off;     // value scratch, in int32 units (a multiple of 4): the pieces of cand_scratch_bytes
   int64_t lscratch_off;     // int64 scratch: capacity + 1 rounded up to a multiple of 4; offset even
 };
 struct CandOut {
@@ -438,9 +438,19 @@ void launch_range_sums(DepthRef rdc, const void* ranges /* int2 lo,hi inclusive 
 void launch_sharpen_edges(DepthRef rdc, int64_t ncompact, EdgeJob* jobs, int njobs, void* ws, int ws_jobs, hipStream_t stream);
 size_t sharpen_workspace_bytes(int njobs);
 size_t sharpen_workspace_zero_bytes(int njobs);
+// How the candidate kernels store the values they gather: one byte each where the depth is bytes (value_bytes = 1), else
+// int32 (value_bytes = 4; also allowed for byte depth: RSI_HOT_CAND_BYTES=0).  The value scratch of one test, every piece
+// on a 16-byte boundary: top + 1 values (left part), capacity floats (the window means; the one-workgroup form keeps the
+// neighbourhood's values there first), min(capacity, budget) values (thinned copy) and, for the split form, capacity
+// values more (the right walk's own slots).
+inline size_t cand_scratch_bytes(int top, int capacity, int budget, int value_bytes, bool split) {
+  auto up16 = [](size_t x) { return (x + 15) & ~size_t(15); };
+  const size_t vb = (size_t)value_bytes;
+  return up16((size_t)(top + 1 > 0 ? top + 1 : 0) * vb) + up16((size_t)capacity * 4) +
+         up16((size_t)(capacity < budget ? capacity : budget) * vb) + (split ? up16((size_t)capacity * vb) : 0);
+}
 // The same test spread over several workgroups (four launches: the two walks side by side; chunked prefix + the candidate's
-// statistics; chunked window means; chunked histogram with a last-workgroup fold).  iscratch carries a fourth piece per job
-// (the right walk's own `capacity` slots, after the three of the single-workgroup form); mid: njobs CandMid records, `done`
+// statistics; chunked window means; chunked histogram with a last-workgroup fold).  mid: njobs CandMid records, `done`
 // zero before the first launch (each launch leaves it zero); ghist: njobs x kCandHistBins counters, zero likewise.
 constexpr int kCandChunks = 16;
 struct CandMid {
@@ -454,9 +464,9 @@ struct CandMid {
 };
 void launch_candidate_test_split(DepthRef rdc, int64_t ncompact, const CandJob* jobs, int njobs, const void* chains,
                                  int32_t* iscratch, long long* lscratch, double RDmedian, CandMid* mid, uint32_t* ghist,
-                                 CandOut* outs, hipStream_t stream);
+                                 CandOut* outs, int value_bytes, hipStream_t stream);
 void launch_candidate_test(DepthRef rdc, int64_t ncompact, const CandJob* jobs, int njobs, const void* chains,
-                           int32_t* iscratch, long long* lscratch, double RDmedian, CandOut* outs, hipStream_t stream);
+                           int32_t* iscratch, long long* lscratch, double RDmedian, CandOut* outs, int value_bytes, hipStream_t stream);
 
 // ---- depth text ingestion (kernels_io.hip; load_data_from_text's parse loop, loaddata.cpp:496-517) ----
 struct TextParseStats { unsigned long long lines, stored, beyond; unsigned int unsorted, pad; };

@@ -217,8 +217,10 @@ __global__ __launch_bounds__(kThreads) void k_sharpen_edges(const TD* __restrict
 
 // ------------------------------------------------------------------------------------------
 // Neighbourhood test.  See CandJob in kernels.h for what the host prepares.
-constexpr int kWalkPer = 16;                          // consecutive positions per thread and trip: ONE 16-byte load of the byte array
-constexpr int kWalkBlock = kWalkPer * kTestThreads;   // positions examined per trip of a walk
+// The gathered values are stored as TS: bytes where the compacted depth is bytes, int32 where it is int32 -- or where
+// RSI_HOT_CAND_BYTES=0 asks for the wide form of byte depth (pipeline.hip).  The values, their order and everything the
+// walk decides are the same in both; the width only sets what the scratch arrays hold and how far a trip of the walk reaches.
+constexpr int kWalkLds = kCandHistBins * 4;   // the walks stage a trip's taken values in the histogram's LDS
 
 // s_scan doubles as scratch of hist_ranks; the rest is the walk's per-trip exchange, double-buffered by trip parity
 struct WalkShared { int s_scan[kMaxWaves]; int cnt[2][kMaxWaves]; int trg[2][kMaxWaves]; int kept[2]; int lastt[2]; };
@@ -252,24 +254,100 @@ __device__ inline void walk_load16(const int32_t* __restrict__ A, int64_t N, lon
   }
 }
 
+// What one thread holds of a trip: kPer consecutive positions in walk order.
+// int32 storage: sixteen values as ints (16 384 positions per trip: the 64 KB stage holds that many ints).
+// byte storage: sixty-four values packed in sixteen registers (65 536 positions per trip, the same 64 KB as bytes); unpacked
+// they would be 2 x 64 registers with the trip loaded ahead.  The registers keep memory order; get() turns it for the walk to the left.
+// swz: a thread's values have consecutive ranks, so the lanes of a wave write the stage kPer slots apart; the rank's
+// bits that tell the lanes apart are XORed into the bits that choose the LDS bank.  A bijection on every aligned block.
+template <typename TS> struct WalkTrip;
+template <> struct WalkTrip<int32_t> {
+  static constexpr int kPer = 16;
+  typedef unsigned int Mask;
+  int v[16];
+  template <typename TD>
+  __device__ inline void load(const TD* __restrict__ A, int64_t N, long long first, int dir) { walk_load16(A, N, first, dir, v); }
+  __device__ inline int get(int j, int) const { return v[j]; }
+  __device__ inline void pin(int, int) {}
+  __device__ inline Mask extreme(int hi_lim, int lo_lim, int) const {   // bit j: value j is extreme
+    Mask m = 0;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) if (v[j] > hi_lim || v[j] < lo_lim) m |= (Mask)1 << j;
+    return m;
+  }
+  __device__ static inline int swz(int r) { return r ^ ((r >> 4) & 15); }
+};
+template <> struct WalkTrip<uint8_t> {
+  static constexpr int kPer = 64;
+  typedef unsigned long long Mask;
+  uint32_t w[16];   // the 64 bytes in memory order: value j of the walk is byte j (dir > 0) or 63 - j (dir < 0)
+  // four 16-byte loads, requested together, where the 64 positions lie inside the array
+  __device__ inline void load(const uint8_t* __restrict__ A, int64_t N, long long first, int dir) {
+    const long long lo = dir > 0 ? first : first - 63;
+    if (lo >= 0 && lo + 63 <= N - 1) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const WalkBytes16 b = *reinterpret_cast<const WalkBytes16*>(A + lo + 16 * q);
+        w[4 * q] = b.w[0]; w[4 * q + 1] = b.w[1]; w[4 * q + 2] = b.w[2]; w[4 * q + 3] = b.w[3];
+      }
+    } else {   // clamped single loads at the chromosome's ends, a register at a time
+#pragma unroll
+      for (int k = 0; k < 16; ++k) {
+        uint32_t x = 0;
+#pragma unroll
+        for (int i = 4 * k; i < 4 * k + 4; ++i) { long long p = lo + i; p = p < 0 ? 0 : (p > N - 1 ? N - 1 : p); x |= (uint32_t)A[p] << (8 * (i & 3)); }
+        w[k] = x;
+      }
+    }
+  }
+  __device__ inline int get(int j, int dir) const { const int i = dir > 0 ? j : 63 - j; return (int)((w[i >> 2] >> (8 * (i & 3))) & 0xffu); }
+  // Called in front of the use of value j in an unrolled loop: keeps the unpacking of a register behind the work on the one
+  // before it.  Left alone the compiler unpacks all sixty-four values first, and a workgroup of 1024 has 128 registers a thread.
+  __device__ inline void pin(int j, int dir) { if ((j & 3) == 0) asm volatile("" : "+v"(w[(dir > 0 ? j : 63 - j) >> 2]) : : "memory"); }
+  // bit j: value j is extreme.  Gathered in memory order, a register's four bits at a time behind a pin (sixty-four
+  // one-bit terms would otherwise each get a register of their own), and mirrored for the walk to the left.
+  __device__ inline Mask extreme(int hi_lim, int lo_lim, int dir) const {
+    uint32_t half[2] = {0u, 0u};
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      uint32_t nib = 0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { const int x = (int)((w[k] >> (8 * i)) & 0xffu); if (x > hi_lim || x < lo_lim) nib |= 1u << i; }
+      half[k >> 3] |= nib << (4 * (k & 7));
+      asm volatile("" : "+v"(half[k >> 3]));
+    }
+    const Mask m = (Mask)half[0] | ((Mask)half[1] << 32);
+    return dir > 0 ? m : (Mask)__brevll(m);
+  }
+  __device__ static inline int swz(int r) { return r ^ (((r >> 7) & 15) << 2); }
+};
+
 // One side of the reference gather (rsi.cpp:206-257).  dir = -1: left of the candidate, values land
 // in dst[fill], dst[fill-1], ...; dir = +1: right, values land in dst[used], dst[used+1], ...
 // Returns the number of values stored; *reach = last position examined.
-// A trip examines kWalkBlock positions in walk order (sixteen consecutive ones per thread): which are
+// A trip examines kBlock positions in walk order (kPer consecutive ones per thread): which are
 // taken (not extreme, not inside the neighbour the walk is about to meet), and where the walk first
 // steps into that neighbour (the trigger, rsi.cpp:222-228 / 246-252: everything after it is dropped
 // and the walk jumps).  One barrier per trip: the waves exchange their taken-counts and triggers; a
 // second one only when there is a trigger, a third when the slots run out.
-template <typename TD>
-__device__ inline int gather_side(const TD* __restrict__ A, int64_t N, int dir, int pos, int room /* slots left */,
-                                  int32_t* __restrict__ dst, int first_slot, const int2* __restrict__ chain, int nchain,
+template <int dir, typename TD, typename TS>
+__device__ inline int gather_side(const TD* __restrict__ A, int64_t N, int pos, int room /* slots left */,
+                                  TS* __restrict__ dst, int first_slot, const int2* __restrict__ chain, int nchain,
                                   int kind, double too_high, double too_low, WalkShared& W, int* reach, int* chain_used,
-                                  int* __restrict__ stage /* LDS, kWalkBlock ints: a trip's taken values in rank order */) {
+                                  TS* __restrict__ stage /* LDS, kBlock values: a trip's taken values in rank order */) {
+  typedef WalkTrip<TS> Trip;
+  typedef typename Trip::Mask Mask;
+  constexpr int kPer = Trip::kPer;
+  constexpr int kBlock = kPer * kTestThreads;   // positions examined per trip
+  static_assert((size_t)kBlock * sizeof(TS) <= (size_t)kWalkLds, "a trip's values fit the stage");
   constexpr int kNone = 0x7fffffff;
-  // A thread's sixteen values have consecutive ranks, so a store of value j by the 64 lanes of a wave would touch 64 cache
-  // lines 64 bytes apart -- the walk spent most of its time in those stores.  The values go to LDS first (the rank's low
-  // four bits XORed with the lane's, which spreads a wave over the banks) and leave as consecutive dwords per wave.
-  auto swz = [](int r) { return r ^ ((r >> 4) & 15); };
+  auto bits_below = [](long long n) -> Mask {   // bits 0 .. n-1 of a thread's kPer positions
+    const Mask all = kPer == 64 ? ~(Mask)0 : (Mask)((1ull << (kPer & 63)) - 1);
+    return n <= 0 ? (Mask)0 : (n >= kPer ? all : (Mask)(((Mask)1 << n) - 1));
+  };
+  // A thread's values have consecutive ranks, so a store of value j by the 64 lanes of a wave would touch 64 cache
+  // lines -- the walk spent most of its time in those stores.  The values go to LDS first (swizzled, see WalkTrip)
+  // and leave as consecutive values per wave.
   int stored = 0, ci = 0, trip = 0;
   int last = pos;
   const int lane = lane_id(), wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
@@ -281,9 +359,9 @@ __device__ inline int gather_side(const TD* __restrict__ A, int64_t N, int dir, 
   const int lo_lim = kind == 1 && too_low == too_low ? (too_low < -2147483647.0 ? (int)0x80000000 : (int)tl) : (int)0x80000000;   // extreme: v < lo_lim
   // the values of a trip are loaded one trip ahead (the walk continues straight on unless it meets a
   // neighbour, which is rare)
-  auto load16 = [&](int from, int* out) { walk_load16(A, N, (long long)from + (long long)dir * (1 + kWalkPer * (int)threadIdx.x), dir, out); };
-  int vnext[kWalkPer];
-  load16(pos, vnext);
+  Trip vnext;
+  auto load_trip = [&](int from) { vnext.load(A, N, (long long)from + (long long)dir * (1 + kPer * (int)threadIdx.x), dir); };
+  load_trip(pos);
   // the neighbour the walk may meet next: read when it changes, not per trip (the list may sit in mapped host memory)
   int2 cur = ci < nchain ? chain[ci] : make_int2(1, 0);   // empty interval when the chain is used up
   while (room > 0 && (dir < 0 ? pos > 2 : (int64_t)pos < N - 2)) {
@@ -291,23 +369,21 @@ __device__ inline int gather_side(const TD* __restrict__ A, int64_t N, int dir, 
     ++trip;
     // positions of this trip in walk order: p_t = pos + dir*(1+t)
     const int avail = dir < 0 ? pos - 2 : (int)(N - 2 - pos);     // how many positions the walk may still visit
-    const int cnt = avail < kWalkBlock ? avail : kWalkBlock;
-    int v[kWalkPer]; unsigned accm = 0; int nacc = 0; int trig = kNone;
-#pragma unroll
-    for (int j = 0; j < kWalkPer; ++j) v[j] = vnext[j];
-    load16(pos + dir * cnt, vnext);                                // next trip, if the walk goes straight on
-    const int t0 = kWalkPer * (int)threadIdx.x;
-#pragma unroll
-    for (int j = 0; j < kWalkPer; ++j) {
-      const int t = t0 + j;
-      if (t < cnt) {
-        const int p = pos + dir * (1 + t);
-        const bool ext = v[j] > hi_lim || v[j] < lo_lim;
-        const bool inside = p >= cur.x && p <= cur.y;
-        if (!ext && inside && t < trig) trig = t;
-        if (!ext && !inside) { accm |= 1u << j; ++nacc; }
-      }
-    }
+    const int cnt = avail < kBlock ? avail : kBlock;
+    Trip v = vnext;
+    load_trip(pos + dir * cnt);                                    // next trip, if the walk goes straight on
+    const int t0 = kPer * (int)threadIdx.x;
+    // one bit per position of this thread: which exist (t < cnt) and which lie inside the neighbour follow from the
+    // coordinates alone, which are extreme from the values
+    const Mask valid = bits_below(cnt - t0);
+    const long long in_lo = dir > 0 ? (long long)cur.x - pos - 1 : (long long)pos - 1 - cur.y;   // inside <=> in_lo <= t <= in_hi
+    const long long in_hi = dir > 0 ? (long long)cur.y - pos - 1 : (long long)pos - 1 - cur.x;
+    const Mask inside = bits_below(in_hi - t0 + 1) & ~bits_below(in_lo - t0);
+    const Mask extm = v.extreme(hi_lim, lo_lim, dir);
+    const Mask accm = valid & ~extm & ~inside;                     // taken unless a trigger in front of them drops them
+    const Mask hits = valid & ~extm & inside;                      // the first of these in the block is the trigger
+    const int nacc = __popcll((unsigned long long)accm);
+    const int trig = hits ? t0 + __ffsll((unsigned long long)hits) - 1 : kNone;
     int incl = wave_incl_scan(nacc), wtrig = trig;
     for (int d = 32; d >= 1; d >>= 1) { const int o = __shfl_xor(wtrig, d); wtrig = o < wtrig ? o : wtrig; }
     if (lane == 63) W.cnt[par][wave] = incl;
@@ -318,29 +394,27 @@ __device__ inline int gather_side(const TD* __restrict__ A, int64_t N, int dir, 
     int rank = base + incl - nacc;             // rank of this thread's first taken value if nothing were dropped
     int total = all;
     if (tstar != kNone) {                       // values taken before the trigger = the trigger position's rank
-      if ((int)threadIdx.x == tstar / kWalkPer) {
-        int k = rank;
-#pragma unroll
-        for (int j = 0; j < kWalkPer; ++j) if (((accm >> j) & 1u) && t0 + j < tstar) ++k;
-        W.kept[par] = k;
+      if ((int)threadIdx.x == tstar / kPer) {
+        W.kept[par] = rank + __popcll((unsigned long long)(accm & bits_below(tstar - t0)));
       }
       __syncthreads();
       total = W.kept[par];
     }
     const bool fills = total >= room;
+    const Mask keep = tstar != kNone ? accm & bits_below((long long)tstar - t0) : accm;
 #pragma unroll
-    for (int j = 0; j < kWalkPer; ++j) {
-      const int t = t0 + j;
-      if (((accm >> j) & 1u) && t < tstar) {
-        if (rank < room) stage[swz(rank)] = v[j];
-        if (fills && rank == room - 1) W.lastt[par] = t;      // the value that fills the last slot
+    for (int j = 0; j < kPer; ++j) {
+      v.pin(j, dir);
+      if ((keep >> j) & 1u) {
+        if (rank < room) stage[Trip::swz(rank)] = (TS)v.get(j, dir);
+        if (fills && rank == room - 1) W.lastt[par] = t0 + j;   // the value that fills the last slot
         ++rank;
       }
     }
     __syncthreads();
     {
       const int ncopy = total < room ? total : room;
-      for (int e = threadIdx.x; e < ncopy; e += blockDim.x) dst[first_slot + dir * (stored + e)] = stage[swz(e)];
+      for (int e = threadIdx.x; e < ncopy; e += blockDim.x) dst[first_slot + dir * (stored + e)] = stage[Trip::swz(e)];
     }   // the next trip writes `stage` only behind its own exchange barrier, which every thread reaches after this loop
     if (fills) {   // the walk stops right after the value that filled the last slot
       last = pos + dir * (1 + W.lastt[par]);
@@ -353,7 +427,7 @@ __device__ inline int gather_side(const TD* __restrict__ A, int64_t N, int dir, 
       pos = dir < 0 ? cur.x - 1 : cur.y + 1;
       ++ci;
       cur = ci < nchain ? chain[ci] : make_int2(1, 0);
-      load16(pos, vnext);      // the prefetch was for the straight continuation
+      load_trip(pos);          // the prefetch was for the straight continuation
     } else {
       pos += dir * cnt;
       last = pos;
@@ -388,7 +462,30 @@ __device__ inline void hist_ranks(const unsigned int* hist, unsigned nbk, size_t
   __syncthreads();
 }
 
-template <typename TD>
+// The scratch of one test (the host sizes it the same way, DeviceTester::test): the gathered values -- left part, thinned
+// copy, the split form's right part -- in `vb` bytes each (1 or 4: the storage type of the launch), the window means as
+// floats in `ref` (which the one-workgroup form fills with the neighbourhood's values first), the prefixes in P.  Every
+// piece starts on a 16-byte boundary.
+struct CandBufs { unsigned char *left, *thin, *right; int32_t* ref; long long* P; };
+__device__ inline CandBufs cand_buffers(const CandJob& J, int32_t* iscratch, long long* lscratch, int vb) {
+  auto up16 = [](size_t x) { return (x + 15) & ~size_t(15); };
+  CandBufs b;
+  unsigned char* p = reinterpret_cast<unsigned char*>(iscratch + J.iscratch_off);
+  b.left = p; p += up16((size_t)(J.top + 1 > 0 ? J.top + 1 : 0) * vb);
+  b.ref = reinterpret_cast<int32_t*>(p); p += up16((size_t)J.capacity * 4);
+  b.thin = p; p += up16((size_t)(J.capacity < J.budget ? J.capacity : J.budget) * vb);
+  b.right = p;
+  b.P = lscratch + J.lscratch_off;
+  return b;
+}
+// four consecutive stored values from a 4-aligned index of a piece
+__device__ inline int4 cand_load4(const int32_t* p) { return *reinterpret_cast<const int4*>(p); }
+__device__ inline int4 cand_load4(const uint8_t* p) {
+  const uint32_t u = *reinterpret_cast<const uint32_t*>(p);
+  return make_int4((int)(u & 0xffu), (int)((u >> 8) & 0xffu), (int)((u >> 16) & 0xffu), (int)(u >> 24));
+}
+
+template <typename TD, typename TS>
 __global__ __launch_bounds__(kTestThreads) void k_candidate_test(const TD* __restrict__ A, int64_t N,
                                                              const CandJob* __restrict__ jobs, const int2* __restrict__ chains,
                                                              int32_t* __restrict__ iscratch, long long* __restrict__ lscratch,
@@ -404,23 +501,23 @@ __global__ __launch_bounds__(kTestThreads) void k_candidate_test(const TD* __res
   const CandJob J = jobs[blockIdx.x];
   CandOut O;
   O.flags = 0;
-  // every piece starts on a 16-byte boundary (the host sizes the scratch the same way, cand_scratch_ints)
-  int32_t* left = iscratch + J.iscratch_off;                          // J.top + 1 slots
-  int32_t* ref = left + (((J.top + 1 > 0 ? J.top + 1 : 0) + 3) & ~3);  // J.capacity slots
-  int32_t* thin = ref + ((J.capacity + 3) & ~3);                      // min(capacity, budget) slots
-  long long* P = lscratch + J.lscratch_off;               // capacity + 1
+  const CandBufs B = cand_buffers(J, iscratch, lscratch, (int)sizeof(TS));
+  TS* left = reinterpret_cast<TS*>(B.left);     // J.top + 1 slots
+  TS* ref = reinterpret_cast<TS*>(B.ref);       // J.capacity slots (sized for the float means that replace the values)
+  TS* thin = reinterpret_cast<TS*>(B.thin);     // min(capacity, budget) slots
+  long long* P = B.P;                           // capacity + 1
   const double too_high = RDmedian * 3.0, too_low = RDmedian * 0.15;
 
   // ---- gather: left side into left[top..], then ref = left part ++ right part ----
   int lreach = J.start, rreach = J.end;
   int lcnt = 0, lused = 0, rused = 0;
   if (J.top >= 0)
-    lcnt = gather_side(A, N, -1, J.start - J.margin, J.top + 1, left, J.top, chains + J.left_off, J.nleft, J.kind, too_high, too_low, W, &lreach, &lused, reinterpret_cast<int*>(s_hist));
+    lcnt = gather_side<-1>(A, N, J.start - J.margin, J.top + 1, left, J.top, chains + J.left_off, J.nleft, J.kind, too_high, too_low, W, &lreach, &lused, reinterpret_cast<TS*>(s_hist));
   __syncthreads();
   // the reference closes the gap when the left side ran out of sequence, otherwise used = top + 1 (rsi.cpp:231-236)
   const int used0 = lcnt < J.top + 1 ? lcnt : J.top + 1;
   for (int j0 = threadIdx.x; j0 < used0; j0 += 8 * kTestThreads) {   // eight independent loads per round
-    int x[8];
+    TS x[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) { const int j = j0 + k * kTestThreads; x[k] = left[J.top + 1 - used0 + (j < used0 ? j : j0)]; }
 #pragma unroll
@@ -433,14 +530,14 @@ __global__ __launch_bounds__(kTestThreads) void k_candidate_test(const TD* __res
     if (lim - used0 < room) room = lim - used0;
     if (room < 0) room = 0;
   }
-  const int rcnt = gather_side(A, N, +1, J.end + J.margin, room, ref, used0, chains + J.right_off, J.nright, J.kind, too_high, too_low, W, &rreach, &rused, reinterpret_cast<int*>(s_hist));
+  const int rcnt = gather_side<+1>(A, N, J.end + J.margin, room, ref, used0, chains + J.right_off, J.nright, J.kind, too_high, too_low, W, &rreach, &rused, reinterpret_cast<TS*>(s_hist));
   __syncthreads();
   // a chain the host cut short was consumed to its end: the walk may have missed a neighbour
   if (((J.cut & 1) && lused >= J.nleft) || ((J.cut & 2) && rused >= J.nright)) O.flags |= 8;
   int nref = used0 + rcnt;
   int nbody = J.end - J.start + 1;
   // ---- thinning to about `budget` points (rsi.cpp:264-282) ----
-  const int32_t* R = ref;
+  const TS* R = ref;
   int body_len = nbody;       // source length of the body
   bool thin_body = false;
   int nbody_eff = nbody;
@@ -449,7 +546,7 @@ __global__ __launch_bounds__(kTestThreads) void k_candidate_test(const TD* __res
     const int tref = (int)((double)nref / (double)total * (double)J.budget);
     const int tbody = (int)((double)nbody / (double)total * (double)J.budget);
     for (int q0 = threadIdx.x; q0 < tref; q0 += 8 * kTestThreads) {   // eight independent loads per round
-      int x[8];
+      TS x[8];
 #pragma unroll
       for (int k = 0; k < 8; ++k) { const int q = q0 + k * kTestThreads; x[k] = ref[(int)((double)(q < tref ? q : q0) / (double)tref * (double)nref)]; }
 #pragma unroll
@@ -506,7 +603,7 @@ __global__ __launch_bounds__(kTestThreads) void k_candidate_test(const TD* __res
     }
   }
   // ---- running mean of width `width` over the neighbourhood (rsi.cpp:113-124): exact prefix, float means ----
-  {   // rounds of four tiles (4096 values each, four consecutive values per thread and tile, one 16-byte load each): the
+  {   // rounds of four tiles (4096 values each, four consecutive values per thread and tile, one load each): the
       // four wave scans of a round share ONE barrier, the exchange buffer alternates with the round's parity
     constexpr int kTile = 4 * kTestThreads, kRound = 4 * kTile;
     long long carry = 0;
@@ -515,8 +612,8 @@ __global__ __launch_bounds__(kTestThreads) void k_candidate_test(const TD* __res
     auto load_tile = [&](int t0) {
       const int e = t0 + 4 * (int)threadIdx.x;
       int4 v = make_int4(0, 0, 0, 0);
-      if (e + 3 < nref) v = *reinterpret_cast<const int4*>(R + e);
-      else { if (e < nref) v.x = R[e]; if (e + 1 < nref) v.y = R[e + 1]; if (e + 2 < nref) v.z = R[e + 2]; }
+      if (e + 3 < nref) v = cand_load4(R + e);
+      else { if (e < nref) v.x = (int)R[e]; if (e + 1 < nref) v.y = (int)R[e + 1]; if (e + 2 < nref) v.z = (int)R[e + 2]; }
       return v;
     };
     int4 nx0 = load_tile(0), nx1 = load_tile(kTile), nx2 = load_tile(2 * kTile), nx3 = load_tile(3 * kTile);
@@ -559,7 +656,7 @@ __global__ __launch_bounds__(kTestThreads) void k_candidate_test(const TD* __res
   }
   const double dw = (double)width;
   // the means are kept (as floats, over the neighbourhood values, which are not needed any more) for the histogram pass
-  float* Wm = reinterpret_cast<float*>(ref);
+  float* Wm = reinterpret_cast<float*>(B.ref);
   {
     float flo = 3.0e38f, fhi = -3.0e38f; double m1 = 0, m2 = 0;
     for (int i = threadIdx.x; i < nwin; i += 4 * kTestThreads) {
@@ -652,61 +749,53 @@ __device__ inline CandGeom cand_geometry(const CandJob& J, const CandMid& M) {
   g.nwin = g.nref - g.width;
   return g;
 }
-struct CandBufs { int32_t *left, *ref, *thin, *right; long long* P; };
-__device__ inline CandBufs cand_buffers(const CandJob& J, int32_t* iscratch, long long* lscratch) {
-  CandBufs b;
-  b.left = iscratch + J.iscratch_off;
-  b.ref = b.left + (((J.top + 1 > 0 ? J.top + 1 : 0) + 3) & ~3);
-  b.thin = b.ref + ((J.capacity + 3) & ~3);
-  const int nthin = J.capacity < J.budget ? J.capacity : J.budget;
-  b.right = b.thin + ((nthin + 3) & ~3);
-  b.P = lscratch + J.lscratch_off;
-  return b;
-}
 // element i of the (possibly thinned) neighbourhood
-__device__ inline int cand_value(const CandJob& J, const CandGeom& g, const CandBufs& b, int i) {
+template <typename TS>
+__device__ inline int cand_value(const CandJob& J, const CandGeom& g, const TS* __restrict__ left, const TS* __restrict__ right, int i) {
   const int j = g.thin ? (int)((double)i / (double)g.nref * (double)g.nref_raw) : i;
-  return j < g.used0 ? b.left[J.top + 1 - g.used0 + j] : b.right[j - g.used0];
+  return (int)(j < g.used0 ? left[J.top + 1 - g.used0 + j] : right[j - g.used0]);
 }
 __device__ inline int cand_chunk_len(int n) { return (((n + kCandChunks - 1) / kCandChunks) + 3) & ~3; }
 constexpr int kCandP32MaxChunk = 16000000;   // 255 x this many bytes still fit 32 bits: chunk-local prefixes of byte depth are kept as uint32
 
 // launch 1: grid (2, njobs) -- the left and the right walk of every test side by side
-template <typename TD>
+template <typename TD, typename TS>
 __global__ __launch_bounds__(kTestThreads) void k_cand_gather(const TD* __restrict__ A, int64_t N, const CandJob* __restrict__ jobs,
                                                           const int2* __restrict__ chains, int32_t* __restrict__ iscratch,
                                                           long long* __restrict__ lscratch, double RDmedian, CandMid* __restrict__ mid) {
   __shared__ WalkShared W;
-  extern __shared__ int s_stage[];   // kWalkBlock ints: a trip's taken values on their way to coalesced stores
+  extern __shared__ int s_stage_raw[];   // kWalkLds bytes: a trip's taken values on their way to coalesced stores
+  TS* const s_stage = reinterpret_cast<TS*>(s_stage_raw);
   const CandJob J = jobs[blockIdx.y];
-  const CandBufs b = cand_buffers(J, iscratch, lscratch);
+  const CandBufs b = cand_buffers(J, iscratch, lscratch, (int)sizeof(TS));
   const double too_high = RDmedian * 3.0, too_low = RDmedian * 0.15;
   CandMid& M = mid[blockIdx.y];
   if (blockIdx.x == 0) {
     int lreach = J.start, lused = 0, lcnt = 0;
     if (J.top >= 0)
-      lcnt = gather_side(A, N, -1, J.start - J.margin, J.top + 1, b.left, J.top, chains + J.left_off, J.nleft, J.kind, too_high, too_low, W, &lreach, &lused, s_stage);
+      lcnt = gather_side<-1>(A, N, J.start - J.margin, J.top + 1, reinterpret_cast<TS*>(b.left), J.top, chains + J.left_off, J.nleft, J.kind, too_high, too_low, W, &lreach, &lused, s_stage);
     if (threadIdx.x == 0) { M.lcnt = lcnt; M.lreach = lreach; M.lused = lused; }
   } else {
     // The right walk does not know yet how many slots the left one leaves.  Where the host vouches that the left walk fills
     // all of its top + 1 slots (J.cut bit 2: more than twice as many positions to the left, known neighbours taken off, as
     // slots -- it would take every other base to be extreme for that to fail, and k_cand_hist checks: flag 16 sends the test
     // to the host path) the right walk takes what is left, about half the capacity; else as many as it could ever get.  The
-    // right walk is the launch's critical path: a trip of 16 384 positions at a time, twice as many trips as needed before.
+    // right walk is the launch's critical path: a trip of 16 384 positions at a time (65 536 with byte storage), twice as many
+    // trips as needed before.
     int room = J.capacity;
     const int lim = (int)ceil(J.right_cap);
     if (lim < room) room = lim;
     if ((J.cut & 4) && J.top >= 0) room -= J.top + 1;
     if (room < 0) room = 0;
     int rreach = J.end, rused = 0;
-    const int rcnt = gather_side(A, N, +1, J.end + J.margin, room, b.right, 0, chains + J.right_off, J.nright, J.kind, too_high, too_low, W, &rreach, &rused, s_stage);
+    const int rcnt = gather_side<+1>(A, N, J.end + J.margin, room, reinterpret_cast<TS*>(b.right), 0, chains + J.right_off, J.nright, J.kind, too_high, too_low, W, &rreach, &rused, s_stage);
     if (threadIdx.x == 0) { M.rcnt_max = rcnt; M.rreach = rreach; M.rused = rused; }
   }
 }
 
 // launch 2: grid (kCandChunks + 1, njobs) -- chunk-local exact prefix of the neighbourhood (+ chunk totals); the last
 // workgroup of a job computes the candidate's own statistics meanwhile
-template <typename TD>
+template <typename TD, typename TS>
 __global__ __launch_bounds__(kTestThreads) void k_cand_prefix(const TD* __restrict__ A, const CandJob* __restrict__ jobs,
                                                           int32_t* __restrict__ iscratch, long long* __restrict__ lscratch,
                                                           CandMid* __restrict__ mid) {
@@ -718,7 +807,9 @@ __global__ __launch_bounds__(kTestThreads) void k_cand_prefix(const TD* __restri
   const CandJob J = jobs[blockIdx.y];
   CandMid& M = mid[blockIdx.y];
   const CandGeom g = cand_geometry(J, M);
-  const CandBufs b = cand_buffers(J, iscratch, lscratch);
+  const CandBufs b = cand_buffers(J, iscratch, lscratch, (int)sizeof(TS));
+  const TS* const left = reinterpret_cast<const TS*>(b.left);
+  const TS* const right = reinterpret_cast<const TS*>(b.right);
   if (g.nwin <= 0 || g.width <= 0) return;
   if (blockIdx.x < kCandChunks) {
     const int Lc = cand_chunk_len(g.nref);
@@ -737,14 +828,20 @@ __global__ __launch_bounds__(kTestThreads) void k_cand_prefix(const TD* __restri
       const int e = t0 + kPer * (int)threadIdx.x;
       int v[kPer];
       if (!g.thin && e + kPer <= ce && (e + kPer <= g.used0 || e >= g.used0)) {
-        // sixteen consecutive values from one side of the neighbourhood: four 16-byte loads (a 4-byte load per value makes the
-        // 64 lanes of every load touch 64 cache lines, sixteen times over)
-        const int32_t* src = e < g.used0 ? b.left + (J.top + 1 - g.used0 + e) : b.right + (e - g.used0);
+        // sixteen consecutive values from one side of the neighbourhood: ONE 16-byte load of stored bytes, four of stored ints
+        // (a load per value makes the 64 lanes of every load touch 64 cache lines, sixteen times over)
+        const TS* src = e < g.used0 ? left + (J.top + 1 - g.used0 + e) : right + (e - g.used0);
+        if constexpr (sizeof(TS) == 1) {
+          const WalkBytes16 w16 = *reinterpret_cast<const WalkBytes16*>(src);
 #pragma unroll
-        for (int q = 0; q < 4; ++q) { const WalkInts4 w4 = *reinterpret_cast<const WalkInts4*>(src + 4 * q); v[4 * q] = w4.x; v[4 * q + 1] = w4.y; v[4 * q + 2] = w4.z; v[4 * q + 3] = w4.w; }
+          for (int k = 0; k < kPer; ++k) v[k] = (int)((w16.w[k >> 2] >> (8 * (k & 3))) & 0xffu);
+        } else {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) { const WalkInts4 w4 = *reinterpret_cast<const WalkInts4*>(src + 4 * q); v[4 * q] = w4.x; v[4 * q + 1] = w4.y; v[4 * q + 2] = w4.z; v[4 * q + 3] = w4.w; }
+        }
       } else {
 #pragma unroll
-        for (int k = 0; k < kPer; ++k) v[k] = e + k < ce ? cand_value(J, g, b, e + k) : 0;
+        for (int k = 0; k < kPer; ++k) v[k] = e + k < ce ? cand_value(J, g, left, right, e + k) : 0;
       }
       long long run = 0;
 #pragma unroll
@@ -861,14 +958,15 @@ __global__ __launch_bounds__(kTestThreads) void k_cand_prefix(const TD* __restri
 // launch 3: grid (kCandChunks, njobs) -- float window means of a chunk of windows, their extremes and moments
 __global__ __launch_bounds__(kTestThreads) void k_cand_means(const CandJob* __restrict__ jobs, int32_t* __restrict__ iscratch,
                                                          long long* __restrict__ lscratch, CandMid* __restrict__ mid,
-                                                         int p32 /* the chunk-local prefixes are 32-bit (byte depth, k_cand_prefix) */) {
+                                                         int p32 /* the chunk-local prefixes are 32-bit (byte depth, k_cand_prefix) */,
+                                                         int vb /* bytes per stored neighbourhood value: where `ref` lies */) {
   __shared__ long long s_off[kCandChunks];
   __shared__ double s_d[kMaxWaves];
   __shared__ float s_f[kMaxWaves];
   const CandJob J = jobs[blockIdx.y];
   CandMid& M = mid[blockIdx.y];
   const CandGeom g = cand_geometry(J, M);
-  const CandBufs b = cand_buffers(J, iscratch, lscratch);
+  const CandBufs b = cand_buffers(J, iscratch, lscratch, vb);
   if (g.nwin <= 0 || g.width <= 0) return;
   if (threadIdx.x == 0) { long long o = 0; for (int c = 0; c < kCandChunks; ++c) { s_off[c] = o; o += M.totals[c]; } }
   __syncthreads();
@@ -898,7 +996,8 @@ __global__ __launch_bounds__(kTestThreads) void k_cand_means(const CandJob* __re
 // writes the result.  ghist and the ticket are left zero.
 __global__ __launch_bounds__(kTestThreads) void k_cand_hist(const CandJob* __restrict__ jobs, int32_t* __restrict__ iscratch,
                                                         long long* __restrict__ lscratch, CandMid* __restrict__ mid,
-                                                        uint32_t* __restrict__ ghist_all, CandOut* __restrict__ outs) {
+                                                        uint32_t* __restrict__ ghist_all, CandOut* __restrict__ outs,
+                                                        int vb /* bytes per stored neighbourhood value: where `ref` lies */) {
   extern __shared__ unsigned int s_hist[];   // kCandHistBins counters
   __shared__ int s_scan[kMaxWaves];
   __shared__ int s_q[3];
@@ -906,7 +1005,7 @@ __global__ __launch_bounds__(kTestThreads) void k_cand_hist(const CandJob* __res
   const CandJob J = jobs[blockIdx.y];
   CandMid& M = mid[blockIdx.y];
   const CandGeom g = cand_geometry(J, M);
-  const CandBufs b = cand_buffers(J, iscratch, lscratch);
+  const CandBufs b = cand_buffers(J, iscratch, lscratch, vb);
   uint32_t* ghist = ghist_all + (size_t)blockIdx.y * kCandHistBins;
   CandOut O;
   O.flags = M.body_flags;
@@ -1004,38 +1103,53 @@ void launch_sharpen_edges(DepthRef d, int64_t ncompact, EdgeJob* jobs, int njobs
     RSI_LAUNCH(k_sharpen_edges<int32_t>, dim3(2 * kEdgeChunks, njobs), dim3(kThreads), 0, stream, rdc, ncompact, jobs, ws_jobs, ws),
     RSI_LAUNCH(k_sharpen_edges<uint8_t>, dim3(2 * kEdgeChunks, njobs), dim3(kThreads), 0, stream, rdc, ncompact, jobs, ws_jobs, ws));
 }
+namespace {
+template <typename TD, typename TS>
+void cand_launch_split(const TD* rdc, int depth_bytes, int64_t ncompact, const CandJob* jobs, int njobs, const int2* ch, int32_t* iscratch,
+                       long long* lscratch, double RDmedian, CandMid* mid, uint32_t* ghist, CandOut* outs, hipStream_t stream) {
+  const size_t lds = (size_t)kCandHistBins * 4;
+  RSI_ALLOW_FULL_LDS((k_cand_gather<TD, TS>));
+  RSI_ALLOW_FULL_LDS((k_cand_prefix<TD, TS>));
+  RSI_ALLOW_FULL_LDS(k_cand_hist);
+  const int vb = (int)sizeof(TS);
+  RSI_LAUNCH((k_cand_gather<TD, TS>), dim3(2, njobs), dim3(kTestThreads), lds, stream, rdc, ncompact, jobs, ch, iscratch, lscratch, RDmedian, mid);
+  RSI_LAUNCH((k_cand_prefix<TD, TS>), dim3(kCandChunks + 1, njobs), dim3(kTestThreads), lds, stream, rdc, jobs, iscratch, lscratch, mid);
+  RSI_LAUNCH(k_cand_means, dim3(kCandChunks, njobs), dim3(kTestThreads), 0, stream, jobs, iscratch, lscratch, mid, depth_bytes == 1 ? 1 : 0, vb);
+  RSI_LAUNCH(k_cand_hist, dim3(kCandChunks, njobs), dim3(kTestThreads), lds, stream, jobs, iscratch, lscratch, mid, ghist, outs, vb);
+}
+template <typename TD, typename TS>
+void cand_launch_one_wg(const TD* rdc, int64_t ncompact, const CandJob* jobs, int njobs, const int2* ch, int32_t* iscratch,
+                        long long* lscratch, double RDmedian, CandOut* outs, hipStream_t stream) {
+  const size_t lds = (size_t)kCandHistBins * 4;
+  RSI_ALLOW_FULL_LDS((k_candidate_test<TD, TS>));
+  RSI_LAUNCH((k_candidate_test<TD, TS>), dim3(njobs), dim3(kTestThreads), lds, stream, rdc, ncompact, jobs, ch, iscratch, lscratch, RDmedian, outs);
+}
+}  // namespace
+// value_bytes: how the gathered values are stored, 1 (byte depth only) or 4; the caller sizes iscratch accordingly
 void launch_candidate_test_split(DepthRef d, int64_t ncompact, const CandJob* jobs, int njobs, const void* chains,
                                  int32_t* iscratch, long long* lscratch, double RDmedian, CandMid* mid, uint32_t* ghist,
-                                 CandOut* outs, hipStream_t stream) {
+                                 CandOut* outs, int value_bytes, hipStream_t stream) {
   if (njobs <= 0) return;
-  const size_t lds = (size_t)kCandHistBins * 4;
-  static_assert(kCandHistBins * 4 >= (unsigned)kWalkBlock * 4, "the walks stage a trip in the histogram's LDS");
-  RSI_ALLOW_FULL_LDS(k_cand_gather<int32_t>);
-  RSI_ALLOW_FULL_LDS(k_cand_gather<uint8_t>);
-  RSI_ALLOW_FULL_LDS(k_cand_prefix<int32_t>);
-  RSI_ALLOW_FULL_LDS(k_cand_prefix<uint8_t>);
-  RSI_ALLOW_FULL_LDS(k_cand_hist);
   const int2* ch = static_cast<const int2*>(chains);
-  RSI_DEPTH_DISPATCH(d,
-    RSI_LAUNCH(k_cand_gather<int32_t>, dim3(2, njobs), dim3(kTestThreads), lds, stream, rdc, ncompact, jobs, ch, iscratch, lscratch, RDmedian, mid),
-    RSI_LAUNCH(k_cand_gather<uint8_t>, dim3(2, njobs), dim3(kTestThreads), lds, stream, rdc, ncompact, jobs, ch, iscratch, lscratch, RDmedian, mid));
-  RSI_DEPTH_DISPATCH(d,
-    RSI_LAUNCH(k_cand_prefix<int32_t>, dim3(kCandChunks + 1, njobs), dim3(kTestThreads), lds, stream, rdc, jobs, iscratch, lscratch, mid),
-    RSI_LAUNCH(k_cand_prefix<uint8_t>, dim3(kCandChunks + 1, njobs), dim3(kTestThreads), lds, stream, rdc, jobs, iscratch, lscratch, mid));
-  RSI_LAUNCH(k_cand_means, dim3(kCandChunks, njobs), dim3(kTestThreads), 0, stream, jobs, iscratch, lscratch, mid, d.bytes == 1 ? 1 : 0);
-  RSI_LAUNCH(k_cand_hist, dim3(kCandChunks, njobs), dim3(kTestThreads), lds, stream, jobs, iscratch, lscratch, mid, ghist, outs);
+  if (d.bytes == 1 && value_bytes == 1)
+    cand_launch_split<uint8_t, uint8_t>(static_cast<const uint8_t*>(d.p), d.bytes, ncompact, jobs, njobs, ch, iscratch, lscratch, RDmedian, mid, ghist, outs, stream);
+  else if (d.bytes == 1)
+    cand_launch_split<uint8_t, int32_t>(static_cast<const uint8_t*>(d.p), d.bytes, ncompact, jobs, njobs, ch, iscratch, lscratch, RDmedian, mid, ghist, outs, stream);
+  else
+    cand_launch_split<int32_t, int32_t>(static_cast<const int32_t*>(d.p), d.bytes, ncompact, jobs, njobs, ch, iscratch, lscratch, RDmedian, mid, ghist, outs, stream);
 }
 size_t sharpen_workspace_bytes(int njobs) { return sharpen_zero_bytes(njobs) + (size_t)njobs * 2 * kEdgeChunks * (8 + 8 + 4); }
 size_t sharpen_workspace_zero_bytes(int njobs) { return sharpen_zero_bytes(njobs); }
 void launch_candidate_test(DepthRef d, int64_t ncompact, const CandJob* jobs, int njobs, const void* chains,
-                           int32_t* iscratch, long long* lscratch, double RDmedian, CandOut* outs, hipStream_t stream) {
+                           int32_t* iscratch, long long* lscratch, double RDmedian, CandOut* outs, int value_bytes, hipStream_t stream) {
   if (njobs <= 0) return;
-  const size_t lds = (size_t)kCandHistBins * 4;
-  RSI_ALLOW_FULL_LDS(k_candidate_test<int32_t>);
-  RSI_ALLOW_FULL_LDS(k_candidate_test<uint8_t>);
-  RSI_DEPTH_DISPATCH(d,
-    RSI_LAUNCH(k_candidate_test<int32_t>, dim3(njobs), dim3(kTestThreads), lds, stream, rdc, ncompact, jobs, static_cast<const int2*>(chains), iscratch, lscratch, RDmedian, outs),
-    RSI_LAUNCH(k_candidate_test<uint8_t>, dim3(njobs), dim3(kTestThreads), lds, stream, rdc, ncompact, jobs, static_cast<const int2*>(chains), iscratch, lscratch, RDmedian, outs));
+  const int2* ch = static_cast<const int2*>(chains);
+  if (d.bytes == 1 && value_bytes == 1)
+    cand_launch_one_wg<uint8_t, uint8_t>(static_cast<const uint8_t*>(d.p), ncompact, jobs, njobs, ch, iscratch, lscratch, RDmedian, outs, stream);
+  else if (d.bytes == 1)
+    cand_launch_one_wg<uint8_t, int32_t>(static_cast<const uint8_t*>(d.p), ncompact, jobs, njobs, ch, iscratch, lscratch, RDmedian, outs, stream);
+  else
+    cand_launch_one_wg<int32_t, int32_t>(static_cast<const int32_t*>(d.p), ncompact, jobs, njobs, ch, iscratch, lscratch, RDmedian, outs, stream);
 }
 #undef RSI_DEPTH_DISPATCH
 

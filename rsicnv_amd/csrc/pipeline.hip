@@ -293,19 +293,21 @@ class DeviceTester : public rsih::NeighbourTester {
     // several workgroups per test when the chip has room for them: a stand-alone context, or a pool run over a few
     // chromosomes only (a rank's share of a sharded genome); one workgroup per test when a dozen chromosomes share the chip
     const bool split = env_int("RSI_HOT_CAND_SPLIT", 1) != 0;
+    // byte depth: the gathered values are stored as bytes and a trip of the walk covers 65 536 positions; RSI_HOT_CAND_BYTES=0
+    // keeps them as int32, with trips of 16 384 (the form int32 depth always takes)
+    const int value_bytes = d_rdc.bytes == 1 && env_int("RSI_HOT_CAND_BYTES", 1) != 0 ? 1 : 4;
     size_t first = 0;
     while (first < n) {
       std::vector<CandJob> jobs;
       std::vector<int32_t> chains;   // (start, end) pairs
-      size_t iwords = 0, lwords = 0, last = first;
+      size_t ibytes = 0, lwords = 0, last = first;
       for (; last < n; ++last) {
         const rsih::TestPlan& T = plans[last];
         if (T.capacity <= 0 || T.end < T.start || T.start < 0 || T.end >= N) break;   // left to the host path (ok stays 0)
         auto up4 = [](size_t x) { return (x + 3) & ~(size_t)3; };   // the kernel wants every piece on a 16-byte boundary
-        const size_t iw = up4((size_t)std::max(T.top + 1, 0)) + up4((size_t)T.capacity) + up4((size_t)std::min(T.capacity, T.budget)) +
-                          (split ? up4((size_t)T.capacity) : 0);   // the split form's right walk has its own slots
+        const size_t ib = cand_scratch_bytes(T.top, T.capacity, T.budget, value_bytes, split);
         const size_t lw = up4((size_t)T.capacity + 1);
-        if (!jobs.empty() && (iwords + iw) * 4 + (lwords + lw) * 8 > kCandScratchBytes) break;
+        if (!jobs.empty() && ibytes + ib + (lwords + lw) * 8 > kCandScratchBytes) break;
         CandJob J{};
         J.start = T.start; J.end = T.end; J.kind = T.kind; J.margin = T.margin; J.capacity = T.capacity; J.top = T.top;
         J.nleft = (int)T.left_chain.size(); J.nright = (int)T.right_chain.size();
@@ -314,8 +316,8 @@ class DeviceTester : public rsih::NeighbourTester {
         J.right_off = (int)(chains.size() / 2);
         for (const auto& iv : T.right_chain) { chains.push_back(iv.first); chains.push_back(iv.second); }
         J.budget = T.budget; J.cut = T.cut; J.right_cap = T.right_cap;
-        J.iscratch_off = (int64_t)iwords; J.lscratch_off = (int64_t)lwords;
-        iwords += iw; lwords += lw;
+        J.iscratch_off = (int64_t)(ibytes / 4); J.lscratch_off = (int64_t)lwords;
+        ibytes += ib; lwords += lw;
         jobs.push_back(J);
       }
       if (jobs.empty()) { ++first; continue; }   // plans[first] was declined
@@ -324,7 +326,7 @@ class DeviceTester : public rsih::NeighbourTester {
       {
         Phase ph(ctx, "cand.ensure");
         if (!ok(ctx->cand_jobs.ensure(jobs.size() * sizeof(CandJob))) || !ok(ctx->cand_chains.ensure(chains.size() * 4)) ||
-            !ok(ctx->cand_outs.ensure(outs.size() * sizeof(CandOut))) || !ok(ctx->cand_i32.ensure(iwords * 4)) ||
+            !ok(ctx->cand_outs.ensure(outs.size() * sizeof(CandOut))) || !ok(ctx->cand_i32.ensure(ibytes)) ||
             !ok(ctx->cand_i64.ensure(lwords * 8)))
           return false;
         if (split) {   // per-job records and folded histograms of the split form: zero when (re)allocated, left zero by every launch
@@ -354,14 +356,16 @@ class DeviceTester : public rsih::NeighbourTester {
         if (!ok(copy_h2d(ctx, ctx->cand_chains.p, chains.data(), chains.size() * 4))) return false;
       }
       {
-        Timer t(ctx, split ? "candidate_test" : "candidate_test_one_wg");
+        // byte depth through the int32 storage (RSI_HOT_CAND_BYTES=0) runs under names of its own, so that a test can tell which ran
+        const bool wide = d_rdc.bytes == 1 && value_bytes == 4;
+        Timer t(ctx, split ? (wide ? "candidate_test_i32" : "candidate_test") : (wide ? "candidate_test_one_wg_i32" : "candidate_test_one_wg"));
         if (split)
           launch_candidate_test_split(d_rdc, N, d_jobs, (int)jobs.size(), d_chains, ctx->cand_i32.as<int32_t>(),
                                       ctx->cand_i64.as<long long>(), median, ctx->cand_mid.as<CandMid>(), ctx->cand_hist.as<uint32_t>(),
-                                      d_outs, ctx->stream);
+                                      d_outs, value_bytes, ctx->stream);
         else
           launch_candidate_test(d_rdc, N, d_jobs, (int)jobs.size(), d_chains, ctx->cand_i32.as<int32_t>(),
-                                ctx->cand_i64.as<long long>(), median, d_outs, ctx->stream);
+                                ctx->cand_i64.as<long long>(), median, d_outs, value_bytes, ctx->stream);
       }
       if (!slot && !ok(copy_d2h(ctx, outs.data(), ctx->cand_outs.p, outs.size() * sizeof(CandOut)))) return false;
       if (!wait()) return false;

@@ -1756,13 +1756,7 @@ __global__ __launch_bounds__(kThreads, (MAXV <= 8 ? 3 : 1)) void k_cap_compact_b
   unsigned int* s_hist = reinterpret_cast<unsigned int*>(smem + (size_t)tile_pad * 4);   // [vr][32]
   __shared__ int64_t s_break[kRegLds], s_cum[kRegLds + 1];
   for (int e = threadIdx.x; e < (pack16 ? vr * kResClasses / 2 : vr * kResClasses); e += kThreads) s_hist[e] = 0;
-  if (nreg <= kRegInline) {   // the short list travels with the kernel arguments: no upload in front of the launch
-    for (int e = threadIdx.x; e < nreg; e += kThreads) s_break[e] = inl.brk[e];
-    for (int e = threadIdx.x; e <= nreg; e += kThreads) s_cum[e] = inl.cum[e];
-  } else {
-    for (int e = threadIdx.x; e < kRegLds && e < nreg; e += kThreads) s_break[e] = cbreak[e];
-    for (int e = threadIdx.x; e <= kRegLds && e <= nreg; e += kThreads) s_cum[e] = cum[e];
-  }
+  stage_regions(s_break, s_cum, nreg, inl, cbreak, cum, true, kThreads);
   __syncthreads();
   const RegionTable R{cbreak, cum, nreg, s_break, s_cum};
 
@@ -1773,15 +1767,8 @@ __global__ __launch_bounds__(kThreads, (MAXV <= 8 ? 3 : 1)) void k_cap_compact_b
   const int kth = (m + 1) / 2;              // rank of the median, m odd (rsi.cpp:2061)
   const bool sw16 = capval >= 0 && capval < 32767 && (int64_t)m * capval < (int64_t)1 << 31;   // every value of the tile fits a 16-bit field with a spare bit
 
-  // tile geometry: k = regions cut out at or before P0; a tile is `plain` when no region cuts it
-  int k = 0;
-  auto geometry = [&](int64_t tile, int64_t& P0, int64_t& P1, bool& plain, int64_t& soff) {
-    P0 = tile * tile_elems;
-    P1 = (P0 + tile_elems < ncompact) ? P0 + tile_elems : ncompact;
-    while (k < nreg && R.brk(k) <= P0) ++k;   // tiles are visited in increasing order
-    plain = (k >= nreg) || (R.brk(k) >= P1);
-    soff = P0 + R.shift(k);
-  };
+  int k = 0;   // regions cut out at or before P0 (tile_geometry)
+  auto geometry = [&](int64_t tile, int64_t& P0, int64_t& P1, bool& plain, int64_t& soff) { tile_geometry(R, nreg, k, tile, tile_elems, ncompact, P0, P1, plain, soff); };
   // Destination-aligned quads: thread idx owns compacted elements 4*idx .. 4*idx+3 of the tile and
   // loads them with one 16-byte load from src + soff + 4*idx, which is only dword-aligned in the
   // source (global_load_dwordx4 needs no more on gfx950).  Whole quads only; the partial quad at
@@ -1840,7 +1827,9 @@ __global__ __launch_bounds__(kThreads, (MAXV <= 8 ? 3 : 1)) void k_cap_compact_b
         }
       }
     } else {
-      // ---- generic: contiguous source segments between removed regions ----
+      // ---- generic: contiguous source segments between removed regions.  for_each_tile_element (per_base_device.h) written
+      // out: through the helper the same instructions leave the hoisting pass in another order, and this kernel's <13, 0>,
+      // <13, 52> and <8, 26> forms, which fill the register file, then get other register and spill counts ----
       int kk = k;
       int64_t seg = P0;
       while (seg < P1) {
@@ -1874,11 +1863,8 @@ __global__ __launch_bounds__(kThreads, (MAXV <= 8 ? 3 : 1)) void k_cap_compact_b
     int lo = 0x7fffffff, hi = (int)0x80000000;
     long long ssum = 0;
     if (EPT > 0 && sw16) {
-      // Values below 2^15 (a cap is in force and lies below): two to a register as 16-bit fields, bit 15 of each as the guard --
-      // #{x > t} of two values is one subtraction and one popcount, as in the byte kernels' median phase; slots past the bin
-      // hold 0xffff, above every t.  The median lies next to the bin's mean: 64 values around it bracket it on all but a
-      // handful of bins (the two counts that prove it, then six bisection steps); a wave with a bin outside its bracket
-      // bisects [0, cap].  32-bit sums: m * cap stays below 2^31.  (The int32 form below cost 40 of this kernel's 80 vector
+      // Values below 2^15 (a cap is in force and lies below): two to a register as 16-bit fields, slots past the bin 0xffff, and
+      // the bracketed counting median of per_base_device.h (median16).  (The int32 form below cost 40 of this kernel's 80 vector
       // instructions per base at 300x: up to ten data-dependent steps of 26 compares over min .. max of the bin.)
       constexpr int kPairs = (EPT + 1) / 2;
       uint32_t pk[EPT > 0 ? kPairs : 1];
@@ -1892,32 +1878,8 @@ __global__ __launch_bounds__(kThreads, (MAXV <= 8 ? 3 : 1)) void k_cap_compact_b
         pk[i] = a | (c << 16) | 0x80008000u;
       }
       s32 = (uint32_t)parts_sum((int)s32, parts);
-      auto count_le = [&](int t) {   // #{x <= t} of the bin, t = -1 .. 32766
-        const uint32_t sub = (uint32_t)(t + 1) * 0x00010001u;
-        int gt = 0;
-#pragma unroll
-        for (int i = 0; i < kPairs; ++i) gt += __popc((pk[i] - sub) & 0x80008000u);
-        return 2 * kPairs * parts - parts_sum(gt, parts);
-      };
-      int blo = 0, bhi = capval, steps = 15;
-      {
-        const int est = (int)((float)s32 / (float)m);
-        int lo0 = est - 31;
-        lo0 = lo0 < 0 ? 0 : lo0;
-        int hi0 = lo0 + 63;
-        hi0 = hi0 > capval ? capval : hi0;
-        lo0 = lo0 > hi0 ? hi0 : lo0;
-        const bool below = count_le(lo0 - 1) < kth;
-        const bool above = hi0 >= capval || count_le(hi0) >= kth;
-        if (__all((below && above) || !active)) { blo = lo0; bhi = hi0; steps = 6; }
-      }
-#pragma unroll 1
-      for (int it = 0; it < steps; ++it) {
-        const int mid = (blo + bhi) >> 1;
-        const int le = count_le(mid);
-        if (blo < bhi) { if (le >= kth) bhi = mid; else blo = mid + 1; }
-      }
-      lo = blo; ssum = (long long)s32;
+      lo = median16(pk, s32, m, kth, capval, active, parts);
+      ssum = (long long)s32;
     } else if (EPT > 0) {
       // the thread's share of the bin in registers; slots past the bin hold INT_MAX (never <= mid)
       int r[EPT > 0 ? EPT : 1];
@@ -2017,13 +1979,7 @@ __global__ __launch_bounds__(kThreads, 4) void k_cap_compact_bin8(
   __shared__ int64_t s_break[kRegLds], s_cum[kRegLds + 1];
   for (int e = threadIdx.x; e < vr * kResClasses; e += kThreads) s_hist[e] = 0;
   for (int e = threadIdx.x; e < kGcLevels; e += kThreads) s_table[e] = table[e];
-  if (nreg <= kRegInline) {
-    for (int e = threadIdx.x; e < nreg; e += kThreads) s_break[e] = inl.brk[e];
-    for (int e = threadIdx.x; e <= nreg; e += kThreads) s_cum[e] = inl.cum[e];
-  } else {
-    for (int e = threadIdx.x; e < kRegLds && e < nreg; e += kThreads) s_break[e] = cbreak[e];
-    for (int e = threadIdx.x; e <= kRegLds && e <= nreg; e += kThreads) s_cum[e] = cum[e];
-  }
+  stage_regions(s_break, s_cum, nreg, inl, cbreak, cum, true, kThreads);
   const double rdmean = table[kGcLevels];
   __syncthreads();
   const RegionTable R{cbreak, cum, nreg, s_break, s_cum};
@@ -2035,36 +1991,18 @@ __global__ __launch_bounds__(kThreads, 4) void k_cap_compact_bin8(
   const int64_t ntiles = (ncompact + tile_elems - 1) / tile_elems;
   const int parts = kThreads / TB;          // threads cooperating on one bin
   const int kth = (m + 1) / 2;              // rank of the median, m odd (rsi.cpp:2061)
-  // the 20-slice write-back's tail (App. A Q2/Q3): cells n-201 .. n-201+r-1 carry the rescaled depth of the last r bases,
-  // computed with the fresh edge window [n-201, n-1]; the last r bases keep their raw depth
-  const int64_t S20 = n / 20, r20 = n - 20 * S20;
-  const int64_t zone = n - 201;             // no fast-path tile may reach this base (also covers the clamped windows, i >= n-101)
-
-  auto rescale = [&](int d, uint32_t g) { return (int)((double)d * rdmean / s_table[g] + 0.5); };   // gccontent.cpp:89, truncation
-  auto slow_value = [&](int64_t i) -> int {   // the value K3 + its tail fixup would have left at source index i
-    if (raw) return depth[i];
-    if (r20 >= 2 && i >= n - 201 && i < n - 201 + r20) return rescale(depth[20 * S20 + (i - (n - 201))], (uint32_t)gc_count201(gcbits, n - 201));
-    if (i >= 20 * S20) return depth[i];
-    int64_t lo = i - 100;
-    if (lo < 0) lo = 0;
-    if (lo > n - 202) lo = n - 202;
-    return rescale(depth[i], (uint32_t)gc_count201(gcbits, lo));
-  };
+  const SlowSource slow{depth, gcbits, n, n / 20, n - 20 * (n / 20), s_table, rdmean};   // the per-element path's values (slow_value)
+  const int64_t zone = n - 201;             // no fast-path tile may reach this base: the 20-slice tail (App. A Q2/Q3), the clamped windows (i >= n-101)
 
   int k = 0;
   auto geometry = [&](int64_t tile, int64_t& P0, int64_t& P1, bool& fast, int64_t& soff) {
-    P0 = tile * tile_elems;
-    P1 = (P0 + tile_elems < ncompact) ? P0 + tile_elems : ncompact;
-    while (k < nreg && R.brk(k) <= P0) ++k;   // tiles are visited in increasing order
-    const bool plain = (k >= nreg) || (R.brk(k) >= P1);
-    soff = P0 + R.shift(k);
+    bool plain;
+    tile_geometry(R, nreg, k, tile, tile_elems, ncompact, P0, P1, plain, soff);
     // fast: a whole tile, contiguous in the source, every base with an unclamped window, before the tail zone and before
     // the last partial stride of the 31 MAD residue classes
     fast = plain && P1 - P0 == tile_elems && P1 <= lim31 && soff >= 101 && soff + tile_elems <= zone;
   };
-  // Chunks are aligned in the COMPACTED array (16 values = 64 aligned bytes of rdc, 16 aligned bytes of the LDS tile); in the
-  // source they start at any byte, which a 16-byte load of the byte copy does not mind.
-  uint4 regs[MAXC];
+  uint4 regs[MAXC];   // chunk kc of the tile: sixteen bytes at any byte address of the source
   auto request = [&](int64_t soff) {   // branch-free: chunks beyond the tile re-read chunk 0 (ignored later)
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) {
@@ -2105,27 +2043,14 @@ __global__ __launch_bounds__(kThreads, 4) void k_cap_compact_bin8(
       }
     } else {
       // ---- per-element path: contiguous source segments between removed regions, values from the int32 array ----
-      int kk = k;
-      int64_t seg = P0;
-      while (seg < P1) {
-        const int64_t nxt = (kk < nreg && R.brk(kk) < P1) ? R.brk(kk) : P1;
-        const int64_t len = nxt - seg;
-        if (len > 0) {
-          const int64_t so = seg + R.shift(kk);
-          const int dst = (int)(seg - P0);
-          for (int64_t e = threadIdx.x; e < len; e += kThreads) {
-            int x = slow_value(so + e);
-            if (x > capval) x = capval;
-            if (x < 0) x = 0;   // negative depth is refused by the caller (K2's flag); keep the byte store in range
-            s_val[dst + e] = (unsigned char)x;
-            rdc8[seg + e] = (unsigned char)x;
-            const int64_t p = seg + e;
-            atomicAdd(&s_hist[x * kResClasses + (p < lim31 ? (int)((uint32_t)p % 31u) : 31)], 1u);
-          }
-        }
-        seg = nxt;
-        if (kk < nreg && R.brk(kk) == nxt) ++kk;
-      }
+      for_each_tile_element(R, k, nreg, P0, P1, kThreads, [&](int64_t i, int64_t p, int64_t e) {
+        int x = slow_value(slow, i, raw);
+        if (x > capval) x = capval;
+        if (x < 0) x = 0;   // negative depth is refused by the caller (K2's flag); keep the byte store in range
+        s_val[e] = (unsigned char)x;
+        rdc8[p] = (unsigned char)x;
+        atomicAdd(&s_hist[x * kResClasses + (p < lim31 ? (int)((uint32_t)p % 31u) : 31)], 1u);
+      });
     }
     __syncthreads();
     // ---- request the next tile now: its loads fly during the median phase ----
@@ -2135,80 +2060,12 @@ __global__ __launch_bounds__(kThreads, 4) void k_cap_compact_bin8(
     const int b_local = threadIdx.x / parts, part = threadIdx.x % parts;
     const int64_t b = cur_tile * TB + b_local;
     const bool active = b < nb;
-    if (SW7) {
-      // Values below 128 (the cap is): four to a register, straight from the LDS bytes.  A bin is the bytes [B, B + m) of the
-      // tile; its (up to 27) dwords go round robin to the bin's four threads, bytes outside the bin masked -- to 0 for the
-      // sum (v_sad_u8 adds four bytes in one instruction), to 0xff for the counts.  #{x > mid} of four values is one
-      // subtraction and one popcount: with the top bit of every byte set, (x | 0x80) - (mid + 1) keeps that bit exactly
-      // where x > mid, and no byte borrows from its neighbour.  Bisection from [0, cap]: the same seven steps for every bin.
-      const int B = b_local * m;
-      const int d0 = B >> 2, d1 = (B + m - 1) >> 2;
-      const uint32_t* w = reinterpret_cast<const uint32_t*>(s_val);
-      uint32_t xo[7];
-      uint32_t ssum = 0;
-#pragma unroll
-      for (int i = 0; i < 7; ++i) {
-        const int d = d0 + part + parts * i;
-        const uint32_t v = w[d <= d1 ? d : d1];
-        const int lo_cut = B - 4 * d, hi_cut = 4 * d + 4 - (B + m);          // bytes of the dword before / after the bin
-        uint32_t keep = 0xffffffffu;
-        keep = lo_cut > 0 ? keep << (8 * lo_cut) : keep;
-        keep = hi_cut > 0 ? keep & (0xffffffffu >> (8 * hi_cut)) : keep;
-        keep = (d <= d1 && active) ? keep : 0u;
-        ssum = __builtin_amdgcn_sad_u8(v & keep, 0u, ssum);
-        xo[i] = (v | ~keep) | 0x80808080u;
-      }
-      ssum = (uint32_t)parts_sum((int)ssum, parts);
-      int lo = 0, hi = capval;
-#pragma unroll 1
-      for (int it = 0; it < 7; ++it) {
-        const int mid = (lo + hi) >> 1;
-        const uint32_t sub = (uint32_t)(mid + 1) * 0x01010101u;
-        int gt = 0;
-#pragma unroll
-        for (int i = 0; i < 7; ++i) gt += __popc((xo[i] - sub) & 0x80808080u);
-        gt = parts_sum(gt, parts);
-        // masked bytes (0xff) always count as "> mid" (mid <= 126): 28 dword slots x 4 bytes - m of them per bin
-        const int le = 4 * 7 * parts - gt;
-        if (lo < hi) { if (le >= kth) hi = mid; else lo = mid + 1; }
-      }
-      if (active && part == 0) { binmed[b] = lo; binsum[b] = (int64_t)ssum; }
-    } else if (EPT == 0) {
-      // Caps of 128 .. 253 (a byte has no spare bit): the same scheme on 16-bit fields, two values to a register -- bytes 0
-      // and 2 of a dword in one, bytes 1 and 3 in another, bit 15 of every field as the guard.  #{x > mid} of four values is
-      // two subtractions and two popcounts; eight bisection steps from [0, cap].
-      const int B = b_local * m;
-      const int d0 = B >> 2, d1 = (B + m - 1) >> 2;
-      const uint32_t* w = reinterpret_cast<const uint32_t*>(s_val);
-      uint32_t xa[7], xc[7];
-      uint32_t ssum = 0;
-#pragma unroll
-      for (int i = 0; i < 7; ++i) {
-        const int d = d0 + part + parts * i;
-        const uint32_t v = w[d <= d1 ? d : d1];
-        const int lo_cut = B - 4 * d, hi_cut = 4 * d + 4 - (B + m);          // bytes of the dword before / after the bin
-        uint32_t keep = 0xffffffffu;
-        keep = lo_cut > 0 ? keep << (8 * lo_cut) : keep;
-        keep = hi_cut > 0 ? keep & (0xffffffffu >> (8 * hi_cut)) : keep;
-        keep = (d <= d1 && active) ? keep : 0u;
-        ssum = __builtin_amdgcn_sad_u8(v & keep, 0u, ssum);
-        const uint32_t xb = v | ~keep;                                       // bytes outside the bin: 0xff, above every mid
-        xa[i] = (xb & 0x00ff00ffu) | 0x80008000u;
-        xc[i] = ((xb >> 8) & 0x00ff00ffu) | 0x80008000u;
-      }
-      ssum = (uint32_t)parts_sum((int)ssum, parts);
-      int lo = 0, hi = capval;
-#pragma unroll 1
-      for (int it = 0; it < 8; ++it) {
-        const int mid = (lo + hi) >> 1;
-        const uint32_t sub = (uint32_t)(mid + 1) * 0x00010001u;
-        int gt = 0;
-#pragma unroll
-        for (int i = 0; i < 7; ++i) gt += __popc((xa[i] - sub) & 0x80008000u) + __popc((xc[i] - sub) & 0x80008000u);
-        gt = parts_sum(gt, parts);
-        const int le = 4 * 7 * parts - gt;   // masked bytes (0xff) always count as "> mid" (mid <= 252)
-        if (lo < hi) { if (le >= kth) hi = mid; else lo = mid + 1; }
-      }
+    if (SW7 || EPT == 0) {
+      // the packed byte median of per_base_device.h, straight from the LDS bytes; bisection from [0, cap]: the same seven (eight,
+      // caps of 128 .. 253) steps for every bin
+      BinBytes<SW7> X;
+      const uint32_t ssum = load_bin_bytes<SW7>(s_val, b_local * m, m, part, parts, active, X);
+      const int lo = X.template median<false>(ssum, 0.0f, kth, capval, active, parts);
       if (active && part == 0) { binmed[b] = lo; binsum[b] = (int64_t)ssum; }
     }
   }
@@ -2246,13 +2103,7 @@ __global__ __launch_bounds__(kThreads, 3) void k_cap_compact_bin16(
   constexpr int vr = kK4Window;
   for (int e = threadIdx.x; e < vr * kResClasses / 2; e += kThreads) s_hist[e] = 0;
   if (threadIdx.x < 2 * kResClasses) s_extra[threadIdx.x] = 0u;
-  if (nreg <= kRegInline) {
-    for (int e = threadIdx.x; e < nreg; e += kThreads) s_break[e] = inl.brk[e];
-    for (int e = threadIdx.x; e <= nreg; e += kThreads) s_cum[e] = inl.cum[e];
-  } else {
-    for (int e = threadIdx.x; e < kRegLds && e < nreg; e += kThreads) s_break[e] = cbreak[e];
-    for (int e = threadIdx.x; e <= kRegLds && e <= nreg; e += kThreads) s_cum[e] = cum[e];
-  }
+  stage_regions(s_break, s_cum, nreg, inl, cbreak, cum, true, kThreads);
   __syncthreads();
   const RegionTable R{cbreak, cum, nreg, s_break, s_cum};
   const int64_t lim31 = (ncompact / 31) * 31;
@@ -2272,11 +2123,8 @@ __global__ __launch_bounds__(kThreads, 3) void k_cap_compact_bin16(
   };
   int k = 0;
   auto geometry = [&](int64_t tile, int64_t& P0, int64_t& P1, bool& fast, int64_t& soff) {
-    P0 = tile * tile_elems;
-    P1 = (P0 + tile_elems < ncompact) ? P0 + tile_elems : ncompact;
-    while (k < nreg && R.brk(k) <= P0) ++k;   // tiles are visited in increasing order
-    const bool plain = (k >= nreg) || (R.brk(k) >= P1);
-    soff = P0 + R.shift(k);
+    bool plain;
+    tile_geometry(R, nreg, k, tile, tile_elems, ncompact, P0, P1, plain, soff);
     fast = plain && P1 - P0 == tile_elems && P1 <= lim31;   // a whole tile, contiguous in the source, before the last partial stride of the 31 classes
   };
   int4 regs[MAXC][4];
@@ -2324,26 +2172,13 @@ __global__ __launch_bounds__(kThreads, 3) void k_cap_compact_bin16(
       }
     } else {
       // ---- per-element path: contiguous source segments between removed regions; the chromosome's last, partial tile ----
-      int kk = k;
-      int64_t seg = P0;
-      while (seg < P1) {
-        const int64_t nxt = (kk < nreg && R.brk(kk) < P1) ? R.brk(kk) : P1;
-        const int64_t len = nxt - seg;
-        if (len > 0) {
-          const int64_t so = seg + R.shift(kk);
-          const int dst = (int)(seg - P0);
-          for (int64_t e = threadIdx.x; e < len; e += kThreads) {
-            int x = src[so + e];
-            if (x > capval) x = capval;
-            s_val[dst + e] = (uint16_t)x;
-            rdc[seg + e] = x;
-            const int64_t p = seg + e;
-            count_value(x, p < lim31 ? (int)((uint32_t)p % 31u) : 31);
-          }
-        }
-        seg = nxt;
-        if (kk < nreg && R.brk(kk) == nxt) ++kk;
-      }
+      for_each_tile_element(R, k, nreg, P0, P1, kThreads, [&](int64_t i, int64_t p, int64_t e) {
+        int x = src[i];
+        if (x > capval) x = capval;
+        s_val[e] = (uint16_t)x;
+        rdc[p] = x;
+        count_value(x, p < lim31 ? (int)((uint32_t)p % 31u) : 31);
+      });
     }
     __syncthreads();
     // ---- request the next tile now: its loads fly during the median phase ----
@@ -2371,33 +2206,7 @@ __global__ __launch_bounds__(kThreads, 3) void k_cap_compact_bin16(
       xo[i] = (val | ~keep) | 0x80008000u;                 // halves outside the bin: 0xffff, above every t
     }
     ssum = (uint32_t)parts_sum((int)ssum, parts);
-    auto count_le = [&](int t) {   // #{x <= t} of the bin, t = -1 .. 32766
-      const uint32_t sub = (uint32_t)(t + 1) * 0x00010001u;
-      int gt = 0;
-#pragma unroll
-      for (int i = 0; i < kW16; ++i) gt += __popc((xo[i] - sub) & 0x80008000u);
-      return 2 * kW16 * parts - parts_sum(gt, parts);
-    };
-    // 64 values around the bin's mean bracket its median on all but a handful of bins: the two counts that prove it, then six
-    // bisection steps; a wave with a bin outside its bracket bisects [0, cap] (the result is the same either way)
-    int lo = 0, hi = capval, steps = 15;
-    {
-      const int est = (int)((float)ssum / (float)m);
-      int lo0 = est - 31;
-      lo0 = lo0 < 0 ? 0 : lo0;
-      int hi0 = lo0 + 63;
-      hi0 = hi0 > capval ? capval : hi0;
-      lo0 = lo0 > hi0 ? hi0 : lo0;
-      const bool below = count_le(lo0 - 1) < kth;
-      const bool above = hi0 >= capval || count_le(hi0) >= kth;
-      if (__all((below && above) || !active)) { lo = lo0; hi = hi0; steps = 6; }
-    }
-#pragma unroll 1
-    for (int it = 0; it < steps; ++it) {
-      const int mid = (lo + hi) >> 1;
-      const int le = count_le(mid);
-      if (lo < hi) { if (le >= kth) hi = mid; else lo = mid + 1; }
-    }
+    const int lo = median16(xo, ssum, m, kth, capval, active, parts);   // bracketed around the bin's mean (per_base_device.h)
     if (active && part == 0) { binmed[b] = lo; binsum[b] = (int64_t)ssum; }
   }
   __syncthreads();
@@ -2455,13 +2264,7 @@ __global__ __launch_bounds__(kThreads, 4) void k_rescale_compact_bin8(
   for (int e = threadIdx.x; e < vr * cols; e += kThreads) s_hist[e] = 0;
   for (int e = threadIdx.x; e < kGcLevels; e += kThreads) { const double t = table[e]; s_table[e] = t; s_ratio[e] = (float)(table[kGcLevels] / t); }
   if (FIX) for (int e = threadIdx.x; e < kGcLevels; e += kThreads) s_rt[e] = rtab[e];
-  if (nreg <= kRegInline && !pp) {
-    for (int e = threadIdx.x; e < nreg; e += kThreads) s_break[e] = inl.brk[e];
-    for (int e = threadIdx.x; e <= nreg; e += kThreads) s_cum[e] = inl.cum[e];
-  } else {
-    for (int e = threadIdx.x; e < kRegLds && e < nreg; e += kThreads) s_break[e] = cbreak[e];
-    for (int e = threadIdx.x; e <= kRegLds && e <= nreg; e += kThreads) s_cum[e] = cum[e];
-  }
+  stage_regions(s_break, s_cum, nreg, inl, cbreak, cum, !pp, kThreads);
   const double rdmean = table[kGcLevels];
   __syncthreads();
   const RegionTable R{cbreak, cum, nreg, s_break, s_cum};
@@ -2474,35 +2277,18 @@ __global__ __launch_bounds__(kThreads, 4) void k_rescale_compact_bin8(
   const int parts = kThreads / TB;          // threads cooperating on one bin
   const int kth = (m + 1) / 2;              // rank of the median, m odd (rsi.cpp:2061)
   const float inv_m = 1.0f / (float)m;      // for the median phase's first guess only (any guess gives the same median)
-  // the 20-slice write-back's tail (App. A Q2/Q3): cells n-201 .. n-201+r-1 carry the rescaled depth of the last r bases,
-  // computed with the fresh edge window [n-201, n-1]; the last r bases keep their raw depth
-  const int64_t S20 = n / 20, r20 = n - 20 * S20;
-  const int64_t zone = n - 201;             // no fast-path tile may reach this base (also covers the clamped windows, i >= n-101)
-
-  auto rescale = [&](int d, uint32_t g) { return (int)((double)d * rdmean / s_table[g] + 0.5); };   // gccontent.cpp:89, truncation
-  auto slow_value = [&](int64_t i) -> int {   // the value K3 + its tail fixup would have left at source index i
-    if (r20 >= 2 && i >= n - 201 && i < n - 201 + r20) return rescale(depth[20 * S20 + (i - (n - 201))], (uint32_t)gc_count201(gcbits, n - 201));
-    if (i >= 20 * S20) return depth[i];
-    int64_t lo = i - 100;
-    if (lo < 0) lo = 0;
-    if (lo > n - 202) lo = n - 202;
-    return rescale(depth[i], (uint32_t)gc_count201(gcbits, lo));
-  };
+  const SlowSource slow{depth, gcbits, n, n / 20, n - 20 * (n / 20), s_table, rdmean};   // the per-element path's values (slow_value), the exact rescale
+  const int64_t zone = n - 201;             // no fast-path tile may reach this base: the 20-slice tail (App. A Q2/Q3), the clamped windows (i >= n-101)
 
   int k = 0;
   auto geometry = [&](int64_t tile, int64_t& P0, int64_t& P1, bool& fast, int64_t& soff) {
-    P0 = tile * tile_elems;
-    P1 = (P0 + tile_elems < ncompact) ? P0 + tile_elems : ncompact;
-    while (k < nreg && R.brk(k) <= P0) ++k;   // tiles are visited in increasing order
-    const bool plain = (k >= nreg) || (R.brk(k) >= P1);
-    soff = P0 + R.shift(k);
+    bool plain;
+    tile_geometry(R, nreg, k, tile, tile_elems, ncompact, P0, P1, plain, soff);
     // fast: a whole tile, contiguous in the source, every base with an unclamped window, before the tail zone and before
     // the last partial stride of the 31 MAD residue classes
     fast = plain && P1 - P0 == tile_elems && P1 <= lim31 && soff >= 101 && soff + tile_elems <= zone;
   };
-  // Chunks are aligned in the COMPACTED array (16 values = 64 aligned bytes of rdc, 16 aligned bytes of the LDS tile); in the
-  // source they start at any byte, which a 16-byte load of the byte copy does not mind.
-  uint4 regs[MAXC];
+  uint4 regs[MAXC];   // chunks aligned in the compacted array, as in K4'
   uint64_t gwreg = 0;          // thread t < kK4GcWords: word t of the tile's staged GC words, committed to s_gw when the tile's turn comes
   int64_t gw0 = 0, gw0_next = 0;   // index of the first staged word of the tile being consumed / requested
   auto request = [&](int64_t soff) {   // branch-free: chunks beyond the tile re-read chunk 0 (ignored later)
@@ -2565,7 +2351,7 @@ __global__ __launch_bounds__(kThreads, 4) void k_rescale_compact_bin8(
 #pragma unroll
           for (int j = 0; j < 16; ++j) {
             const int x = esc ? depth[p + j] : (int)((w4[j >> 2] >> (8 * (j & 3))) & 0xffu);
-            v[j] = rescale(x, cnt);
+            v[j] = slow.rescale(x, cnt);
             v[j] = v[j] < 0 ? 0 : v[j];   // an escaped depth is any int32 (negative ones are refused by the caller, K2j's flag)
             cnt = cnt - ((leave >> j) & 1u) + ((enter >> j) & 1u);
           }
@@ -2593,27 +2379,14 @@ __global__ __launch_bounds__(kThreads, 4) void k_rescale_compact_bin8(
       }
     } else {
       // ---- per-element path: contiguous source segments between removed regions, values from the int32 array ----
-      int kk = k;
-      int64_t seg = P0;
-      while (seg < P1) {
-        const int64_t nxt = (kk < nreg && R.brk(kk) < P1) ? R.brk(kk) : P1;
-        const int64_t len = nxt - seg;
-        if (len > 0) {
-          const int64_t so = seg + R.shift(kk);
-          const int dst = (int)(seg - P0);
-          for (int64_t e = threadIdx.x; e < len; e += kThreads) {
-            int x = slow_value(so + e);
-            if (x > capval) x = capval;
-            if (x < 0) x = 0;   // negative depth is refused by the caller (K2's flag); keep the byte store in range
-            s_val[dst + e] = (unsigned char)x;
-            rdc8[seg + e] = (unsigned char)x;
-            const int64_t p = seg + e;
-            atomicAdd(&s_hist[x * cols + (p < lim31 ? (int)((uint32_t)p % 31u) : cols - 1)], 1u);
-          }
-        }
-        seg = nxt;
-        if (kk < nreg && R.brk(kk) == nxt) ++kk;
-      }
+      for_each_tile_element(R, k, nreg, P0, P1, kThreads, [&](int64_t i, int64_t p, int64_t e) {
+        int x = slow_value(slow, i, false);
+        if (x > capval) x = capval;
+        if (x < 0) x = 0;   // negative depth is refused by the caller (K2's flag); keep the byte store in range
+        s_val[e] = (unsigned char)x;
+        rdc8[p] = (unsigned char)x;
+        atomicAdd(&s_hist[x * cols + (p < lim31 ? (int)((uint32_t)p % 31u) : cols - 1)], 1u);
+      });
     }
     __syncthreads();
     // ---- request the next tile now: its loads fly during the median phase ----
@@ -2623,110 +2396,11 @@ __global__ __launch_bounds__(kThreads, 4) void k_rescale_compact_bin8(
     const int b_local = threadIdx.x / parts, part = threadIdx.x % parts;
     const int64_t b = cur_tile * TB + b_local;
     const bool active = b < nb;
-    if (SW7) {
-      // Values below 128 (the cap is): four to a register, straight from the LDS bytes.  A bin is the bytes [B, B + m) of the
-      // tile; its (up to 27) dwords go round robin to the bin's four threads, bytes outside the bin masked -- to 0 for the
-      // sum (v_sad_u8 adds four bytes in one instruction), to 0xff for the counts.  #{x > mid} of four values is one
-      // subtraction and one popcount: with the top bit of every byte set, (x | 0x80) - (mid + 1) keeps that bit exactly
-      // where x > mid, and no byte borrows from its neighbour.  Bisection from [0, cap]: the same seven steps for every bin.
-      const int B = b_local * m;
-      const int d0 = B >> 2, d1 = (B + m - 1) >> 2;
-      const uint32_t* w = reinterpret_cast<const uint32_t*>(s_val);
-      uint32_t xo[7];
-      uint32_t ssum = 0;
-#pragma unroll
-      for (int i = 0; i < 7; ++i) {
-        const int d = d0 + part + parts * i;
-        const uint32_t v = w[d <= d1 ? d : d1];
-        const int lo_cut = B - 4 * d, hi_cut = 4 * d + 4 - (B + m);          // bytes of the dword before / after the bin
-        uint32_t keep = 0xffffffffu;
-        keep = lo_cut > 0 ? keep << (8 * lo_cut) : keep;
-        keep = hi_cut > 0 ? keep & (0xffffffffu >> (8 * hi_cut)) : keep;
-        keep = (d <= d1 && active) ? keep : 0u;
-        ssum = __builtin_amdgcn_sad_u8(v & keep, 0u, ssum);
-        xo[i] = (v | ~keep) | 0x80808080u;
-      }
-      ssum = (uint32_t)parts_sum((int)ssum, parts);
-      // #{x <= t} of the bin, t = -1 .. 126 (masked bytes, 0xff, always count as "> t": 28 dword slots x 4 bytes - m of them per bin)
-      auto count_le = [&](int t) {
-        const uint32_t sub = (uint32_t)(t + 1) * 0x01010101u;
-        int gt = 0;
-#pragma unroll
-        for (int i = 0; i < 7; ++i) gt += __popc((xo[i] - sub) & 0x80808080u);
-        return 4 * 7 * parts - parts_sum(gt, parts);
-      };
-      // The median of a bin lies next to its mean: eight values around sum / m bracket it on all but a handful of bins (event
-      // edges), and three bisection steps inside the bracket plus the two counts that prove it replace seven steps from
-      // [0, cap].  A wave with a bin outside its bracket takes the seven steps (the result is the same either way).
-      int lo = 0, hi = capval, steps = 7;
-      {
-        const int est = (int)((float)ssum * inv_m);
-        int lo0 = est - 3;
-        lo0 = lo0 < 0 ? 0 : lo0;
-        int hi0 = lo0 + 7;
-        hi0 = hi0 > capval ? capval : hi0;
-        lo0 = lo0 > hi0 ? hi0 : lo0;
-        const bool below = count_le(lo0 - 1) < kth;                                   // the median is not below the bracket
-        const bool above = hi0 >= capval || count_le(hi0 > 126 ? 126 : hi0) >= kth;   // ... nor above it (every value is <= cap)
-        if (__all((below && above) || !active)) { lo = lo0; hi = hi0; steps = 3; }
-      }
-#pragma unroll 1
-      for (int it = 0; it < steps; ++it) {
-        const int mid = (lo + hi) >> 1;
-        const int le = count_le(mid);
-        if (lo < hi) { if (le >= kth) hi = mid; else lo = mid + 1; }
-      }
-      if (active && part == 0) { binmed[b] = lo; binsum[b] = (int64_t)ssum; }
-    } else if (EPT == 0) {
-      // Caps of 128 .. 253 (a byte has no spare bit): the same scheme on 16-bit fields, two values to a register -- bytes 0
-      // and 2 of a dword in one, bytes 1 and 3 in another, bit 15 of every field as the guard.  #{x > mid} of four values is
-      // two subtractions and two popcounts; eight bisection steps from [0, cap].
-      const int B = b_local * m;
-      const int d0 = B >> 2, d1 = (B + m - 1) >> 2;
-      const uint32_t* w = reinterpret_cast<const uint32_t*>(s_val);
-      uint32_t xa[7], xc[7];
-      uint32_t ssum = 0;
-#pragma unroll
-      for (int i = 0; i < 7; ++i) {
-        const int d = d0 + part + parts * i;
-        const uint32_t v = w[d <= d1 ? d : d1];
-        const int lo_cut = B - 4 * d, hi_cut = 4 * d + 4 - (B + m);          // bytes of the dword before / after the bin
-        uint32_t keep = 0xffffffffu;
-        keep = lo_cut > 0 ? keep << (8 * lo_cut) : keep;
-        keep = hi_cut > 0 ? keep & (0xffffffffu >> (8 * hi_cut)) : keep;
-        keep = (d <= d1 && active) ? keep : 0u;
-        ssum = __builtin_amdgcn_sad_u8(v & keep, 0u, ssum);
-        const uint32_t xb = v | ~keep;                                       // bytes outside the bin: 0xff, above every mid
-        xa[i] = (xb & 0x00ff00ffu) | 0x80008000u;
-        xc[i] = ((xb >> 8) & 0x00ff00ffu) | 0x80008000u;
-      }
-      ssum = (uint32_t)parts_sum((int)ssum, parts);
-      auto count_le = [&](int t) {   // #{x <= t}, t = -1 .. 252; masked bytes (0xff) always count as "> t"
-        const uint32_t sub = (uint32_t)(t + 1) * 0x00010001u;
-        int gt = 0;
-#pragma unroll
-        for (int i = 0; i < 7; ++i) gt += __popc((xa[i] - sub) & 0x80008000u) + __popc((xc[i] - sub) & 0x80008000u);
-        return 4 * 7 * parts - parts_sum(gt, parts);
-      };
-      // bracket of sixteen values around the bin's mean (deeper coverage: wider bins of values), four steps inside it
-      int lo = 0, hi = capval, steps = 8;
-      {
-        const int est = (int)((float)ssum * inv_m);
-        int lo0 = est - 7;
-        lo0 = lo0 < 0 ? 0 : lo0;
-        int hi0 = lo0 + 15;
-        hi0 = hi0 > capval ? capval : hi0;
-        lo0 = lo0 > hi0 ? hi0 : lo0;
-        const bool below = count_le(lo0 - 1) < kth;
-        const bool above = hi0 >= capval || count_le(hi0 > 252 ? 252 : hi0) >= kth;
-        if (__all((below && above) || !active)) { lo = lo0; hi = hi0; steps = 4; }
-      }
-#pragma unroll 1
-      for (int it = 0; it < steps; ++it) {
-        const int mid = (lo + hi) >> 1;
-        const int le = count_le(mid);
-        if (lo < hi) { if (le >= kth) hi = mid; else lo = mid + 1; }
-      }
+    if (SW7 || EPT == 0) {
+      // the packed byte median of per_base_device.h, straight from the LDS bytes, bracketed around the bin's mean
+      BinBytes<SW7> X;
+      const uint32_t ssum = load_bin_bytes<SW7>(s_val, b_local * m, m, part, parts, active, X);
+      const int lo = X.template median<true>(ssum, inv_m, kth, capval, active, parts);
       if (active && part == 0) { binmed[b] = lo; binsum[b] = (int64_t)ssum; }
     }
   }

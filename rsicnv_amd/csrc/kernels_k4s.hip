@@ -172,13 +172,7 @@ __global__ __launch_bounds__(kS4Threads, 6) void k_rescale_compact_stream(
   for (int e = threadIdx.x; e < vr * cols; e += kS4Threads) s_hist[e] = 0;
   if (!RAW) for (int e = threadIdx.x; e < kGcLevels; e += kS4Threads) L.rt[e] = rtab[e];
   if (threadIdx.x < 8) L.badbits[threadIdx.x] = 0u;
-  if (nreg <= kRegInline && !pp) {
-    for (int e = threadIdx.x; e < nreg; e += kS4Threads) L.brk[e] = inl.brk[e];
-    for (int e = threadIdx.x; e <= nreg; e += kS4Threads) L.cum[e] = inl.cum[e];
-  } else {
-    for (int e = threadIdx.x; e < kRegLds && e < nreg; e += kS4Threads) L.brk[e] = cbreak[e];
-    for (int e = threadIdx.x; e <= kRegLds && e <= nreg; e += kS4Threads) L.cum[e] = cum[e];
-  }
+  stage_regions(L.brk, L.cum, nreg, inl, cbreak, cum, !pp, kS4Threads);
   __syncthreads();
   if (!RAW) for (int e = threadIdx.x; e < kGcLevels; e += kS4Threads) {
     const unsigned int r = L.rt[e];
@@ -473,11 +467,7 @@ __global__ __launch_bounds__(kS4Threads, 6) void k_rescale_compact_stream(
 // K4m: per bin the exact median (order statistic kth = (m + 1) / 2, m odd: rsi.cpp:2061, 1363-1379) and the sum
 // (rsi.cpp:1147-1153) of the capped, compacted bytes.  A bin is the bytes [b m, b m + m) of rdc8; its (up to 7 * PARTS) dwords
 // go round robin to the bin's PARTS lanes, bytes outside the bin masked -- to 0 for the sum (v_sad_u8 adds four bytes in one
-// instruction), to 0xff for the counts.  SW7 (cap <= 127): #{x > t} of four values is one subtraction and one popcount -- with
-// the top bit of every byte set, (x | 0x80) - (t + 1) keeps that bit exactly where x > t, and no byte borrows from its
-// neighbour; caps of 128 .. 253: the same on 16-bit fields, two values to a register.  The median of a bin lies next to its
-// mean: a bracket of eight (sixteen) values around sum / m holds it on all but a handful of bins (event edges); two counts
-// prove the bracket, three (four) bisection steps finish inside it, a wave with a bin outside its bracket bisects [0, cap].
+// instruction), to 0xff for the counts: the packed byte median of per_base_device.h (BinBytes), bracketed around the bin's mean.
 // The dwords of the NEXT trip are requested before the current trip's bisection: a wave always has seven loads in flight.
 template <bool SW7, int PARTS>
 __global__ __launch_bounds__(kM4Threads, SW7 ? 8 : 6) void k_bin_median8(
@@ -525,7 +515,7 @@ __global__ __launch_bounds__(kM4Threads, SW7 ? 8 : 6) void k_bin_median8(
     const int end = (int)(x + (uint32_t)m);   // first byte behind the bin, counted from dword q
     const int d0 = (int)(x >> 2) + part;
     uint32_t ssum = 0;
-    uint32_t xa[7], xc[SW7 ? 1 : 7];
+    BinBytes<SW7> X;
 #pragma unroll
     for (int i = 0; i < 7; ++i) {
       uint32_t xb = v[i];
@@ -540,43 +530,10 @@ __global__ __launch_bounds__(kM4Threads, SW7 ? 8 : 6) void k_bin_median8(
         ssum = __builtin_amdgcn_sad_u8(xb & keep, 0u, ssum);
         xb |= ~keep;                                                          // bytes outside the bin: 0xff, above every threshold
       }
-      if (SW7) xa[i] = xb | 0x80808080u;
-      else { xa[i] = (xb & 0x00ff00ffu) | 0x80008000u; xc[i] = ((xb >> 8) & 0x00ff00ffu) | 0x80008000u; }
+      X.set(i, xb);
     }
     ssum = (uint32_t)parts_sum((int)ssum, PARTS);
-    // #{x <= t} of the bin (masked bytes always count as "> t": 28 byte slots per lane, minus the bin's m, over the bin's lanes)
-    auto count_le = [&](int t) {
-      int gt = 0;
-      if (SW7) {
-        const uint32_t sub = (uint32_t)(t + 1) * 0x01010101u;
-#pragma unroll
-        for (int i = 0; i < 7; ++i) gt += __popc((xa[i] - sub) & 0x80808080u);
-      } else {
-        const uint32_t sub = (uint32_t)(t + 1) * 0x00010001u;
-#pragma unroll
-        for (int i = 0; i < 7; ++i) gt += __popc((xa[i] - sub) & 0x80008000u) + __popc((xc[i] - sub) & 0x80008000u);
-      }
-      return 4 * 7 * PARTS - parts_sum(gt, PARTS);
-    };
-    constexpr int kHalf = SW7 ? 3 : 7, kTop = SW7 ? 126 : 252;
-    int lo = 0, hi = capval, steps = SW7 ? 7 : 8;
-    {
-      const int est = (int)((float)ssum * inv_m);
-      int lo0 = est - kHalf;
-      lo0 = lo0 < 0 ? 0 : lo0;
-      int hi0 = lo0 + 2 * kHalf + 1;
-      hi0 = hi0 > capval ? capval : hi0;
-      lo0 = lo0 > hi0 ? hi0 : lo0;
-      const bool below = count_le(lo0 - 1) < kth;                                     // the median is not below the bracket
-      const bool above = hi0 >= capval || count_le(hi0 > kTop ? kTop : hi0) >= kth;   // ... nor above it (every value is <= cap)
-      if (__all((below && above) || !active)) { lo = lo0; hi = hi0; steps = SW7 ? 3 : 4; }
-    }
-#pragma unroll 1
-    for (int it = 0; it < steps; ++it) {
-      const int mid = (lo + hi) >> 1;
-      const int le = count_le(mid);
-      if (lo < hi) { if (le >= kth) hi = mid; else lo = mid + 1; }
-    }
+    const int lo = X.template median<true>(ssum, inv_m, kth, capval, active, PARTS);
     if (active && part == 0) { binmed[b] = lo; binsum[b] = (int64_t)ssum; }
   };
 

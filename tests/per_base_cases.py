@@ -109,9 +109,9 @@ def _even_runs(k, first, step, length=3):
     return [(first + i * step, length) for i in range(k)]
 
 
-def _spec(cid, n, m, mu, cap, gc=1, runs=(), capval=None, error=None, exclude=None, cap_exact=True, **kw):
+def _spec(cid, n, m, mu, cap, gc=1, runs=(), capval=None, error=None, exclude=None, cap_exact=True, seed=None, **kw):
     return dict(id=cid, n=n, m=m, mu=mu, cap=cap, gc=gc, runs=list(runs), capval=capval, error=error, exclude=exclude,
-                cap_exact=cap_exact and error is None, kw=kw)
+                cap_exact=cap_exact and error is None, seed=seed, kw=kw)
 
 
 def _capflag(target, med):
@@ -161,6 +161,11 @@ def _specs():
     for k in (48, 49, 128, 129):
         for gc in (1, 0):
             S.append(_spec(f"reg{k}_{'gc' if gc else 'nogc'}", 400 * k + 6000, 101, 30, 4.0, gc, runs=_even_runs(k, 3000, 400), capval=120))
+    # the same lists through the region staging and the segment walk of K4w (a cap of 300) and of the int32 K4 (no cap); seeds of their
+    # own, so that the cases behind them keep theirs
+    for j, k in enumerate((49, 129)):
+        S.append(_spec(f"reg{k}_k4w", 400 * k + 6000, 101, 30, _capflag(300, 30), 1, runs=_even_runs(k, 3000, 400), capval=300, seed=0x9E2B00 + 2 * j))
+        S.append(_spec(f"reg{k}_int32", 400 * k + 6000, 101, 30, -1.0, 1, runs=_even_runs(k, 3000, 400), capval=None, seed=0x9E2B01 + 2 * j))
     S.append(_spec("reg49_exclude", 400 * 49 + 6000, 101, 30, 4.0, 1, capval=120,
                    exclude=[(3000 + 400 * i, 3003 + 400 * i) for i in range(49)]))
     # ---- n' around 8 m (m = 439: 3512) and around one K4s sub-tile of 2048 (m = 51) ----
@@ -201,11 +206,15 @@ def _specs():
             step = 2 * p + 203
             S.append(_spec(f"seq_m{m}_reg49{g}", 49 * step + 8 * m + 5000, m, 60, 2.0, gc, runs=_even_runs(49, 2000, step), capval=120, cap_exact=False))
             S.append(_spec(f"seq_m{m}_reg129{g}", 129 * step + 8 * m + 5000, m, 60, 2.0, gc, runs=_even_runs(129, 2000, step), capval=120, cap_exact=False))
+    k = 0       # a case without a seed of its own: numbered among those, in list order
+    for sp in S:
+        if sp["seed"] is None:
+            sp["seed"], k = 0x9E1B00 + k, k + 1
     return S
 
 
-def _case(sp, k):
-    fasta, depth = _build(0x9E1B00 + k, sp["n"], sp["mu"], sp["runs"], **{"spikes": sp["kw"].get("spikes", ()), "stretch": sp["kw"].get("stretch"),
+def _case(sp):
+    fasta, depth = _build(sp["seed"], sp["n"], sp["mu"], sp["runs"], **{"spikes": sp["kw"].get("spikes", ()), "stretch": sp["kw"].get("stretch"),
                                                                         "noise": sp["kw"].get("noise")})
     flags = dict(m=sp["m"], cap=sp["cap"], gcadjust=sp["gc"])
     runs = sp["runs"] if sp["exclude"] is None else [(s, e - s) for s, e in sp["exclude"]]
@@ -230,8 +239,7 @@ def get_case(cid):
     """The case of that id (built once per process; the arrays are shared: leave them unchanged)."""
     ids = case_ids()
     if cid not in _CACHE:
-        k = ids.index(cid)
-        _CACHE[cid] = _case(_CACHE["specs"][k], k)
+        _CACHE[cid] = _case(_CACHE["specs"][ids.index(cid)])
     return _CACHE[cid]
 
 

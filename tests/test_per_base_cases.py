@@ -159,6 +159,9 @@ def test_every_boundary_has_a_case_on_each_side(oracle_runs):
     for k in (0, 48, 49, 128, 129):
         for gc in (1, 0):
             have(lambda c, m, n, nc, nr, f, ex: nr == k and f["gcadjust"] == gc, f"{k} regions, gcadjust {gc}")
+    for k in (49, 129):                     # the LDS-mirrored and the HBM list through K4w's and the int32 K4's staging and walk
+        for route in ("wide16", "int32"):
+            have(lambda c, m, n, nc, nr, f, ex: nr == k and landing(c, m, nr, True)[0] == route, f"{k} regions, {route}")
     assert _landed(oracle_runs, lambda c, m, n, nc, nr, f, ex: nc - 8 * m == -1 and ex["error"] == "RSI_ERR_TOO_SMALL")
     for d in (0, 1):
         have(lambda c, m, n, nc, nr, f, ex: nc - 8 * m == d, f"n' = 8 m + {d}")

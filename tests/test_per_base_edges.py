@@ -8,8 +8,8 @@ tests/test_fallback_paths.py), and the route AND the form inside it as the run i
 RSI_HOT_K4SPLIT=0, RSI_HOT_JOINT=0 and RSI_HOT_K4W=0; (c) the K4 queued behind K2j / the -NOGC histogram pass across shape edges, short
 chromosomes and long region lists, with the accepted / rejected marker derived from the rule in pipeline.hip.
 
-Wall time on an MI355X: not measured yet -- no GPU run of this file has taken place (262 runs of 4 ... 66 kb through the per-base
-phase; the estimate of about a minute is an estimate)."""
+Wall time on an MI355X: 2.5 s for the file's 268 tests (pytest's own figure; 4 s with the interpreter's start), 4 ... 66 kb per run
+through the per-base phase; the slowest is the first, which loads the library (1.5 s)."""
 import os
 
 import numpy as np

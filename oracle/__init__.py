@@ -190,6 +190,10 @@ class Ref:
         L.ref_pnorm.argtypes = [C.c_double]
         L.ref_pnorm.restype = C.c_double
         L.ref_runmean_f32.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32, C.c_int32]
+        if hasattr(L, "ref_rsistatus"):   # a libref.so built from an older ref_driver.cpp lacks it
+            L.ref_rsistatus.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_int32), C.c_int32, C.c_double, C.c_double, C.c_double,
+                                        C.c_int32, C.POINTER(C.c_int32)]
+            L.ref_rsistatus.restype = None
 
     def load(self, params, depth, fasta, chrom="chrS", log=None):
         d, dp = _i32(depth)
@@ -312,4 +316,17 @@ class Ref:
         y = np.ascontiguousarray(y, dtype=np.float32)
         out = np.zeros_like(y)
         self.lib.ref_runmean_f32(y.ctypes.data_as(C.POINTER(C.c_float)), out.ctypes.data_as(C.POINTER(C.c_float)), y.size, band)
+        return out
+
+    def rsistatus(self, T, medint, RDmedian, tmedian, tlamda, Lmax):
+        """One scan pass (the reference's rsistatus, rsi.cpp:1191-1259) over the caller's bins: the status array.  The
+        reference's trimming walks are unbounded; the caller keeps them inside the arrays."""
+        if not hasattr(self.lib, "ref_rsistatus"):
+            raise RuntimeError(f"{REF_SO} predates ref_rsistatus: rebuild it with `make -f oracle/Makefile.ref`")
+        t = np.ascontiguousarray(T, dtype=np.float32)
+        mi, mp = _i32(medint)
+        assert t.shape == mi.shape and t.ndim == 1
+        out = np.zeros(t.size, dtype=np.int32)
+        self.lib.ref_rsistatus(t.ctypes.data_as(C.POINTER(C.c_float)), mp, t.size, float(RDmedian), float(tmedian), float(tlamda),
+                               int(Lmax), out.ctypes.data_as(C.POINTER(C.c_int32)))
         return out

@@ -435,6 +435,23 @@ int ref_plot_icnv(const ref_params* p, const int32_t* rd, int32_t n, const ref_c
   return 0;
 }
 
+// One scan pass on the caller's arrays: the reference's rsistatus (rsi.cpp:1191-1259) with the caller's thresholds.  Its median
+// limits come from the global rsi::RDmedian, set for the call and restored.  The reference's four trimming walks have no bound:
+// the caller keeps them inside [0, nb) (tests/scan_cases.py checks every case before it comes here).
+void ref_rsistatus(const float* T, const int32_t* medint, int32_t nb, double RDmedian, double tmedian, double tlamda, int32_t Lmax,
+                   int32_t* status) {
+  Array<float> t(nb, T);
+  Array<int> mi(nb, 0), st(nb, 0);
+  for (int i = 0; i < nb; ++i) mi[i] = medint[i];
+  const double keep = rsi::RDmedian;
+  rsi::RDmedian = RDmedian;
+  quiet_begin();
+  rsistatus(t, mi, tmedian, tlamda, Lmax, st);
+  quiet_end();
+  rsi::RDmedian = keep;
+  for (int i = 0; i < nb; ++i) status[i] = st[i];
+}
+
 // Direct probes of the numeric utilities (used to pin the oracle's restatements).
 double ref_median_i32(const int32_t* x, int64_t n) { return _median(const_cast<int*>(x), (size_t)n); }
 double ref_median_f32(const float* x, int64_t n) { return _median(const_cast<float*>(x), (size_t)n); }

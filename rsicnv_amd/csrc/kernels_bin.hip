@@ -666,9 +666,54 @@ __device__ inline void scan_sweep(const SL& S, const ScanTile& t, const double* 
 // double prefixes -- and one in the subtraction), so against thresholds widened by 4 * 2^-24 * max|P| of the workgroup's own
 // stretch and rounded outwards, "no float hit" implies "no exact hit".  It lists the tiles where a float test fires; k_rsi_scan
 // then runs the exact sweep on those tiles only, its lengths split over several workgroups.  A listed tile without a real hit
-// costs time, never correctness; a chromosome-end tile ignores the cut-off of its lanes' lengths here (a superset again).
+// costs time, never correctness; at a chromosome end the lanes stop at the lengths the reference visits for their bins, as in the sweep.
 // One workgroup = kDetTiles tiles of kScanTile bins (one per wave; lane l looks at bins l, l + 64, l + 128, l + 192 of its
 // tile: four independent chains per lane), staged with one halo for all of them.
+// ---- the exact-sum precondition ------------------------------------------------------------------------
+// The exact sweep takes a window sum as the difference of two double prefixes of its staged stretch, where the reference slides
+// sum = sum - y[first-1] + y[last] along the chromosome.  The two agree when no prefix of the stretch is ever rounded.  Every float
+// is a multiple of the last bit of the smallest non-zero |v| staged, 2^-23 of that value's power of two p (for a subnormal, of
+// 2^-126), and so is every partial sum; a multiple of 2^-23 p below 2^30 p has at most 53 bits.  So
+//     sum |v| over the stretch  <  2^30 p(smallest non-zero |v|)
+// is sufficient, whatever the signs, and it is what is tested: a range for the single values is not enough (2^-10 next to a
+// prefix of 2^32 needs 65 bits).  The sum of the |v| is itself exact below that bound, and at or above it wherever the true sum
+// is (2^30 p is a double, rounding is monotone, every term is >= 0), so the test never reads a rounded sum wrongly.
+// What is counted: the bins a workgroup owns that are too small for its stretch (2^30 p(|v|) <= sum |v|, v != 0, or not finite);
+// a stretch whose too-small bins all lie in its halo counts once.  One workgroup of k_scan_detect owns kDetBins bins, one of
+// k_rsi_scan kScanTile; the stretch of the latter lies inside the former's, so a clean detection pass covers the sweep behind it.
+struct ScanExact { double asum; uint32_t amin; };   // sum of |v|; bits of the smallest non-zero |v| (none: 0xffffffff)
+__device__ inline void scan_exact_add(ScanExact& x, float v) {
+  const float av = fabsf(v);
+  const uint32_t b = __float_as_uint(av);
+  x.asum += (double)av;
+  x.amin = (b != 0u && b < x.amin) ? b : x.amin;
+}
+__device__ inline double scan_exact_bound(uint32_t abits) {   // 2^30 times the power of two of a non-zero |v| (infinite for Inf / NaN)
+  const uint32_t ex = (abits >> 23) & 0xffu;
+  return 1073741824.0 * (double)__uint_as_float((ex ? ex : 1u) << 23);
+}
+__device__ inline bool scan_exact_small(float v, double asum) {   // is this bin too small for a stretch with this sum of |v| ?
+  const uint32_t b = __float_as_uint(fabsf(v));
+  return b != 0u && !(asum < scan_exact_bound(b));
+}
+// Wave totals into s_asum / s_amin [kThreads / 64]; after the workgroup's next barrier scan_exact_total() gives every thread the
+// same stretch totals (summed in one order).
+__device__ inline void scan_exact_commit(ScanExact x, double* s_asum, uint32_t* s_amin) {
+  // DPP moves, no trips through the LDS crossbar; all 64 lanes are active.  The minimum as the maximum of the complements (zeros
+  // shifted in are the identity of both).  Any association of the sum of the |v| serves (see above).
+  const double asum = wave_lane63(wave_incl_scan(x.asum));
+  const uint32_t amin = ~(uint32_t)wave_lane63((int)wave_incl_max(~x.amin));
+  if (lane_id() == 0) { s_asum[threadIdx.x >> 6] = asum; s_amin[threadIdx.x >> 6] = amin; }
+}
+__device__ inline ScanExact scan_exact_total(const double* s_asum, const uint32_t* s_amin) {
+  ScanExact t = {0.0, 0xffffffffu};
+  for (int w = 0; w < kThreads / 64; ++w) { t.asum += s_asum[w]; t.amin = s_amin[w] < t.amin ? s_amin[w] : t.amin; }
+  return t;
+}
+__device__ inline bool scan_exact_flagged(const ScanExact& t) {
+  return !(t.asum < (t.amin == 0xffffffffu ? INFINITY : scan_exact_bound(t.amin)));   // NaN: flagged
+}
+
 constexpr int kScanPartsMax = 8;                   // shares of a listed tile's lengths (k_rsi_scan)
 constexpr int kDetTiles = 4;                       // tiles per workgroup = waves per workgroup
 constexpr int kDetBins = kDetTiles * kScanTile;    // 1024
@@ -689,25 +734,29 @@ __global__ __launch_bounds__(kThreads) void k_scan_detect(const float* __restric
   float2* TH = reinterpret_cast<float2*>(sm);                           // per L: (DEL, DUP) float thresholds of this workgroup
   float* Pf = reinterpret_cast<float*>(TH + (Lmax + 1 + kScanPad));     // count + 1 prefixes
   __shared__ double s_tot[kThreads];
-  __shared__ unsigned int s_pmax;
+  __shared__ double s_asum[kThreads / 64];
+  __shared__ uint32_t s_amin[kThreads / 64];
+  __shared__ unsigned int s_pmax, s_owned;
   const int64_t first = (int64_t)blockIdx.x * kDetBins;
   const int64_t lo = first - halo;
-  if (threadIdx.x == 0) s_pmax = 0u;
+  if (threadIdx.x == 0) { s_pmax = 0u; s_owned = 0u; }
   // ---- exact double prefix of the staged stretch (serial chunk per thread + scan of the chunk totals), rounded to float ----
   const int chunk = (count + kThreads - 1) / kThreads;
   const int c0 = threadIdx.x * chunk;
   double run = 0.0;
   unsigned int inexact = 0;
+  ScanExact ex = {0.0, 0xffffffffu};   // the exact-sum precondition of the exact sweep, over this stretch (see ScanExact)
   for (int e = c0; e < c0 + chunk && e < count; ++e) {
     const int64_t i = lo + e;
     const float v = (i >= 0 && i < nb) ? T[i] : 0.0f;
-    // exact-sum precondition of the exact sweep: 0, or 2^-10 <= |v| < 2^20; counted once, by the owning workgroup
-    const float av = fabsf(v);
-    if (!(av == 0.0f || (av >= 0.0009765625f && av < 1048576.0f)) && e >= halo && e < halo + kDetBins) inexact++;
+    scan_exact_add(ex, v);
     run += (double)v;
   }
   s_tot[threadIdx.x] = run;
+  scan_exact_commit(ex, s_asum, s_amin);
   __syncthreads();
+  ex = scan_exact_total(s_asum, s_amin);
+  const bool flagged = scan_exact_flagged(ex);   // workgroup-uniform, and false on every chromosome that is not built for it
   if (threadIdx.x < 64) {   // wave 0 turns the 256 totals into exclusive offsets
     double carry = 0.0;
     for (int k = 0; k < kThreads / 64; ++k) {
@@ -726,6 +775,7 @@ __global__ __launch_bounds__(kThreads) void k_scan_detect(const float* __restric
     for (int e = c0; e < c0 + chunk && e < count; ++e) {
       const int64_t i = lo + e;
       const float v = (i >= 0 && i < nb) ? T[i] : 0.0f;   // a second read (L1 / L2) instead of 8 bytes of LDS per staged bin
+      if (flagged && e >= halo && e < halo + kDetBins && scan_exact_small(v, ex.asum)) inexact++;   // counted once, by the owning workgroup
       acc += (double)v;
       const float pf = (float)acc;
       Pf[e + 1] = pf;
@@ -737,9 +787,12 @@ __global__ __launch_bounds__(kThreads) void k_scan_detect(const float* __restric
     for (int d = 32; d >= 1; d >>= 1) { const unsigned int o = (unsigned int)__shfl_xor((int)ab, d); ab = o > ab ? o : ab; }
     if (lane_id() == 0) atomicMax(&s_pmax, ab);
   }
-  for (int d = 32; d >= 1; d >>= 1) inexact += __shfl_xor(inexact, d);
-  if (lane_id() == 0 && inexact) atomicAdd(&counters[1], inexact);
+  if (flagged) {   // (rare) the owned bins that are too small, or one for a stretch whose too-small bins are all in the halo
+    for (int d = 32; d >= 1; d >>= 1) inexact += __shfl_xor(inexact, d);
+    if (lane_id() == 0 && inexact) atomicAdd(&s_owned, inexact);
+  }
   __syncthreads();
+  if (flagged && threadIdx.x == 0) atomicAdd(&counters[1], s_owned ? s_owned : 1u);
   {
     const double pmax = (double)__uint_as_float(s_pmax);
     const double margin = pmax * (4.0 / 16777216.0);
@@ -763,31 +816,49 @@ __global__ __launch_bounds__(kThreads) void k_scan_detect(const float* __restric
 #pragma unroll
   for (int b = 0; b < 4; ++b) f_lo[b] = Pf[rel0 + 64 * b];
   unsigned long long cand = 0;
-  for (int L0 = 1; L0 <= Lmax && cand == 0; L0 += kScanPad) {
-    float2 th[kScanPad];
-    int off[kScanPad];   // wave-uniform: staged offset of the prefix value that is new at this length
+  // EDGE: a workgroup whose stretch reaches a chromosome end cuts every lane off at the lengths the reference visits for its bin
+  // (i in [L/2 + 1, nb - L/2 - 2], rsi.cpp:1204), as the exact sweep does: the zeros staged beyond the ends look like deletions
+  // to the windows that reach them, and used to list the last tile of every chromosome (nb is rarely a multiple of 256) and the
+  // only tile of a chromosome without a hit.
+  auto sweep = [&](auto edge_tag) {
+    constexpr bool EDGE = decltype(edge_tag)::value;
+    int lend[4] = {0, 0, 0, 0};
+    if (EDGE) {
 #pragma unroll
-    for (int u = 0; u < kScanPad; ++u) {
-      int L = L0 + u;
-      L = L > Lmax ? Lmax : L;                              // past Lmax the thresholds are unreachable; just stay in range
-      const int h = L >> 1;
-      off[u] = (u & 1) ? -h : h + 1;                        // L0 is odd: odd u <=> even L <=> the window grew on the left
-      th[u] = TH[L0 + u];                                   // the same address in every lane: a broadcast read
-    }
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      float pf[kScanPad];
-#pragma unroll
-      for (int u = 0; u < kScanPad; ++u) pf[u] = Pf[rel0 + 64 * b + off[u]];
-#pragma unroll
-      for (int u = 0; u < kScanPad; ++u) {
-        if (u & 1) f_lo[b] = pf[u]; else f_hi[b] = pf[u];
-        const float fs = f_hi[b] - f_lo[b];
-        // wave masks straight from the compares, OR-ed with scalar instructions: no per-lane flag, no branches
-        cand |= __builtin_amdgcn_ballot_w64(fs <= th[u].x) | __builtin_amdgcn_ballot_w64(fs >= th[u].y);
+      for (int b = 0; b < 4; ++b) {
+        const int64_t i = tile * kScanTile + lane + 64 * b;
+        const int64_t hmax = (i - 1) < (nb - i - 2) ? (i - 1) : (nb - i - 2);
+        lend[b] = (i < nb && hmax >= 0) ? (int)(hmax < Lmax ? 2 * hmax + 1 : Lmax) : 0;
       }
     }
-  }
+    for (int L0 = 1; L0 <= Lmax && cand == 0; L0 += kScanPad) {
+      float2 th[kScanPad];
+      int off[kScanPad];   // wave-uniform: staged offset of the prefix value that is new at this length
+#pragma unroll
+      for (int u = 0; u < kScanPad; ++u) {
+        int L = L0 + u;
+        L = L > Lmax ? Lmax : L;                              // past Lmax the thresholds are unreachable; just stay in range
+        const int h = L >> 1;
+        off[u] = (u & 1) ? -h : h + 1;                        // L0 is odd: odd u <=> even L <=> the window grew on the left
+        th[u] = TH[L0 + u];                                   // the same address in every lane: a broadcast read
+      }
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        float pf[kScanPad];
+#pragma unroll
+        for (int u = 0; u < kScanPad; ++u) pf[u] = Pf[rel0 + 64 * b + off[u]];
+#pragma unroll
+        for (int u = 0; u < kScanPad; ++u) {
+          if (u & 1) f_lo[b] = pf[u]; else f_hi[b] = pf[u];
+          const float fs = f_hi[b] - f_lo[b];
+          // wave masks straight from the compares, OR-ed with scalar instructions: no per-lane flag, no branches
+          if (EDGE) cand |= __builtin_amdgcn_ballot_w64((fs <= th[u].x || fs >= th[u].y) && L0 + u <= lend[b]);
+          else cand |= __builtin_amdgcn_ballot_w64(fs <= th[u].x) | __builtin_amdgcn_ballot_w64(fs >= th[u].y);
+        }
+      }
+    }
+  };
+  if (lo <= 0 || lo + count >= nb) sweep(std::true_type{}); else sweep(std::false_type{});
   if (cand != 0 && lane == 0) tiles[atomicAdd(&counters[8], 1u)] = (uint32_t)tile;
 }
 
@@ -823,7 +894,9 @@ __global__ __launch_bounds__(kThreads) void k_rsi_scan(const float* __restrict__
   double* const gtile = GTILE ? reinterpret_cast<double*>(gws + (size_t)blockIdx.x * gbytes) : nullptr;
   if (GTILE) scan_lds_carve(S, gtile, count, kcap); else scan_lds_carve(S, sm, count, kcap);
   __shared__ int s_c[4][kThreads];
-  __shared__ unsigned int s_task;
+  __shared__ double s_asum[kThreads / 64];
+  __shared__ uint32_t s_amin[kThreads / 64];
+  __shared__ unsigned int s_task, s_owned;
   // integer forms of the median limits: x > lim_del <=> x > fl_del ; x < lim_dup <=> x < ce_dup
   const int fl_del = (int)floor(sp.lim_del), ce_dup = (int)ceil(sp.lim_dup);
   const double tmed = sp.tmedian;
@@ -853,15 +926,15 @@ __global__ __launch_bounds__(kThreads) void k_rsi_scan(const float* __restrict__
     const int c0 = threadIdx.x * chunk;
     double run = 0.0;
     int rc[4] = {0, 0, 0, 0};
-    unsigned int inexact = 0;
+    // exact-sum precondition (see ScanExact): tested by the detection pass when there is one -- its stretch contains this one --
+    // else here, by the tile's first part
+    const bool test_exact = !tiles && part == 0;
+    ScanExact ex = {0.0, 0xffffffffu};
     for (int e = c0; e < c0 + chunk && e < count; ++e) {
       const bool in = e >= vlo && e < vhi;
       const float v = in ? T[lo + e] : 0.0f;
       const int mi = in ? medint[lo + e] : 0;
-      // exact-sum precondition: 0, or 2^-10 <= |v| < 2^20; counted once per bin: by the detection pass
-      // when there is one, else by the owning tile's first part
-      const float av = fabsf(v);
-      if (!tiles && part == 0 && !(av == 0.0f || (av >= 0.0009765625f && av < 1048576.0f)) && e >= halo && e < halo + kScanTile) inexact++;
+      if (test_exact) scan_exact_add(ex, v);
       S.M[e] = mi;
       run += (double)v;
       rc[kCL] += (in && mi <= fl_del);
@@ -875,8 +948,18 @@ __global__ __launch_bounds__(kThreads) void k_rsi_scan(const float* __restrict__
     S.tot[threadIdx.x] = run;
 #pragma unroll
     for (int q = 0; q < 4; ++q) s_c[q][threadIdx.x] = rc[q];
-    if (threadIdx.x == 0) { S.P[0] = 0.0; for (int q = 0; q < 4; ++q) S.C(q, 0) = 0; }
+    if (threadIdx.x == 0) { S.P[0] = 0.0; for (int q = 0; q < 4; ++q) S.C(q, 0) = 0; s_owned = 0u; }
+    if (test_exact) scan_exact_commit(ex, s_asum, s_amin);
     tile_sync();
+    if (test_exact) ex = scan_exact_total(s_asum, s_amin);
+    const bool flagged = test_exact && scan_exact_flagged(ex);   // workgroup-uniform
+    if (flagged) {   // (rare) count the owned bins that are too small for this stretch
+      unsigned int small = 0;
+      for (int e = c0; e < c0 + chunk && e < count; ++e)
+        if (e >= vlo && e < vhi && e >= halo && e < halo + kScanTile && scan_exact_small(T[lo + e], ex.asum)) small++;
+      for (int d = 32; d >= 1; d >>= 1) small += __shfl_xor(small, d);
+      if (lane_id() == 0 && small) atomicAdd(&s_owned, small);
+    }
     if (threadIdx.x < 64) {   // wave 0 turns the 256 totals into exclusive offsets
       double carry = 0.0;
       int car[4] = {0, 0, 0, 0};
@@ -913,8 +996,7 @@ __global__ __launch_bounds__(kThreads) void k_rsi_scan(const float* __restrict__
         S.PF[e] = (IX)bits;
       }
     }
-    for (int d = 32; d >= 1; d >>= 1) inexact += __shfl_xor(inexact, d);
-    if (lane_id() == 0 && inexact) atomicAdd(&counters[1], inexact);
+    if (flagged && threadIdx.x == 0) atomicAdd(&counters[1], s_owned ? s_owned : 1u);   // the LDS atomics landed before the barrier above
     tile_sync();
 
     // ---- every (bin, L) of the tile within this task's lengths.  Going from L-1 to L the window gains one bin -- on the left for

@@ -542,6 +542,7 @@ def test_median_depth_beyond_65535(hot, hotlib, oracle_cls, flags):
     assert np.array_equal(hot.fetch("binmedint"), O.i32("binmedint"))
     nbs = O.f64("nb")
     assert st["nb_mad"] == nbs[1] and st["nb_r"] == nbs[2]
+    assert st["inexact_sums"] == 0      # every transformed bin is large: the sum of a staged stretch stays far below 2^30 times the smallest one's power of two
     pre = "med" if flags.get("trans", 0) == 1 else "nb"
     for mine, theirs in (("status1", f"{pre}_status1"), ("status1f", f"{pre}_status1f"), ("status2", f"{pre}_status2")):
         assert np.array_equal(hot.fetch(mine), O.i32(theirs)), mine

@@ -89,6 +89,18 @@ typedef struct rsi_result rsi_result;
 /* Reference defaults (rsi.cpp:34-98). */
 void rsi_default_params(rsi_params* p);
 
+/* The process-wide setting the library depends on, applied to the environment: call it BEFORE the process's first HIP call
+ * (the HIP runtime reads GPU_MAX_HW_QUEUES once, when it initialises; later the call changes the environment and nothing else).
+ * It makes no HIP call itself.  A pool runs one stream per worker and wants each on a hardware queue of its own, so:
+ *   GPU_MAX_HW_QUEUES missing, not a number, or below 32   -> set to 32;   32 or more -> left as it is (nothing above 32 is
+ *   ever written);
+ *   RSI_HOT_HW_QUEUES=keep   -> the environment is left exactly as found;
+ *   RSI_HOT_HW_QUEUES=N      -> N clamped to 4 .. 32 is written, whatever was there (anything else in that variable is ignored).
+ * A number is one to nine decimal digits and nothing else.  Returns the number GPU_MAX_HW_QUEUES holds afterwards, or 0 when
+ * it holds none (possible under `keep` only: the runtime then uses its default of 4).  Not thread-safe
+ * against other writers of the environment, like setenv itself. */
+int rsi_hot_process_setup(void);
+
 /* Context on HIP device `device`.  Returns NULL on failure; *status receives the reason. */
 rsi_ctx* rsi_hot_create(int device, int* status);
 void rsi_hot_destroy(rsi_ctx* ctx);
@@ -411,6 +423,11 @@ typedef struct rsi_batch_times {   /* accumulated over rsi_pool_run calls; zero 
 rsi_pool* rsi_pool_create(int device, int nworkers, int* status);
 void rsi_pool_destroy(rsi_pool* pool);
 int rsi_pool_workers(const rsi_pool* pool);
+/* The hardware queues the process had asked for when the pool was made: GPU_MAX_HW_QUEUES as rsi_pool_create found it, 4 (the
+ * runtime's default) when it held no number.  A pool with more workers than that minus two (the copy stream's and the host
+ * framework's own) shares queues between workers -- the regime of "22 workers: 14-17 ms" -- and rsi_pool_create says so on
+ * stderr, once per process, naming GPU_MAX_HW_QUEUES and rsi_hot_process_setup. */
+int rsi_pool_hw_queues(const rsi_pool* pool);
 rsi_ctx* rsi_pool_worker(rsi_pool* pool, int w);
 void rsi_pool_set_timing(rsi_pool* pool, int on);
 void rsi_pool_set_timing_kernel(rsi_pool* pool, const char* name);   /* rsi_hot_set_timing_kernel on every worker */

@@ -12,8 +12,34 @@ import numpy as np
 # A pool drives one HIP stream per worker.  The ROCm runtime multiplexes streams onto
 # GPU_MAX_HW_QUEUES hardware queues (default 4); with a dozen streams that puts unrelated chromosomes
 # in line behind each other's kernels (measured: ~10 % of the genome rate).  The variable is read when
-# the HIP runtime initialises, so it has to be in the environment before the first HIP call.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")
+# the HIP runtime initialises, so it has to be in the environment before the first HIP call: importing
+# this module is that moment for a Python program (librsi_hot.so is loaded later, and need not exist
+# for the import).  A lower value that is already there does NOT win -- boxes that start every command
+# with GPU_MAX_HW_QUEUES=4 kept a pool of twenty on four queues for three rounds; RSI_HOT_HW_QUEUES
+# is how a caller has its way.
+POOL_HW_QUEUES, MIN_HW_QUEUES = 32, 4
+
+
+def _queue_count(s):
+    """One to nine decimal digits and nothing else -> the number; anything else -> -1 (parse_queue_count, process_setup.cpp)."""
+    return int(s) if s is not None and 1 <= len(s) <= 9 and all(c in "0123456789" for c in s) else -1
+
+
+def _process_setup(env=os.environ):
+    """rsi_hot_process_setup (include/rsi_hot.h) restated: the same policy on `env`, returning what GPU_MAX_HW_QUEUES holds
+    afterwards (0: no number).  GPU_MAX_HW_QUEUES below 32, missing or not a number -> 32; 32 or more -> left alone;
+    RSI_HOT_HW_QUEUES=keep -> nothing changes; RSI_HOT_HW_QUEUES=N -> N clamped to 4 .. 32 is written."""
+    user = env.get("RSI_HOT_HW_QUEUES")
+    if user != "keep":
+        want = _queue_count(user)
+        if want >= 0:
+            env["GPU_MAX_HW_QUEUES"] = str(min(POOL_HW_QUEUES, max(MIN_HW_QUEUES, want)))
+        elif _queue_count(env.get("GPU_MAX_HW_QUEUES")) < POOL_HW_QUEUES:
+            env["GPU_MAX_HW_QUEUES"] = str(POOL_HW_QUEUES)
+    return max(0, _queue_count(env.get("GPU_MAX_HW_QUEUES")))
+
+
+HW_QUEUES = _process_setup()
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RSI_HOT_LIB: another build of the same ABI (A/B measurements of library versions, tools/ab_bench.py)
@@ -27,7 +53,7 @@ STATUS_NAMES = {0: "RSI_OK", -1: "RSI_ERR_NO_DEVICE", -2: "RSI_ERR_BAD_ARG", -3:
 EXPORTS = ["rsi_default_params", "rsi_hot_create", "rsi_hot_destroy", "rsi_hot_last_error", "rsi_hot_run",
            "rsi_hot_run_device", "rsi_hot_load_depth_text", "rsi_hot_run_text", "rsi_hot_load_depth_bam", "rsi_hot_run_bam", "rsi_bam_references", "rsi_result_annotate_bam", "rsi_result_summary", "rsi_summary_format_row", "rsi_summary_format_rows", "rsi_result_pairs", "rsi_result_ncalls", "rsi_result_calls", "rsi_result_stats", "rsi_result_noncode",
            "rsi_result_format_row", "rsi_result_free", "rsi_hot_fetch_i32", "rsi_hot_fetch_f32", "rsi_hot_fetch_i64",
-           "rsi_hot_kernel_times", "rsi_hot_phase_times", "rsi_hot_set_timing", "rsi_pool_create", "rsi_pool_destroy", "rsi_pool_workers", "rsi_pool_worker",
+           "rsi_hot_kernel_times", "rsi_hot_phase_times", "rsi_hot_set_timing", "rsi_hot_process_setup", "rsi_pool_create", "rsi_pool_destroy", "rsi_pool_workers", "rsi_pool_hw_queues", "rsi_pool_worker",
            "rsi_pool_set_timing", "rsi_pool_set_timing_kernel", "rsi_hot_set_timing_kernel", "rsi_pool_set_schedule", "rsi_pool_last_error", "rsi_pool_run", "rsi_pool_run_host", "rsi_pool_submit", "rsi_pool_wait", "rsi_plot_expand", "rsi_plot_write_files", "rsi_result_log_line", "rsi_hot_debug_level_sums", "rsi_hot_debug_scan", "rsi_hot_debug_grid_median", "rsi_hot_debug_grid_mad_i32", "rsi_synth_generate_host", "rsi_synth_generate_device", "rsi_synth_write_depth_text", "rsi_synth_write_fasta", "rsi_synth_append_genome_text",
            "rsi_genome_text_open", "rsi_genome_text_next", "rsi_genome_text_release", "rsi_genome_text_copy_depth",
            "rsi_genome_text_kernel_ms", "rsi_genome_text_close", "rsi_genome_text_last_error", "rsi_hot_run_depth_device",
@@ -173,6 +199,8 @@ def load_library():
     L.rsi_pool_create.restype = C.c_void_p
     L.rsi_pool_destroy.argtypes = [C.c_void_p]
     L.rsi_pool_workers.argtypes = [C.c_void_p]
+    L.rsi_pool_hw_queues.argtypes = [C.c_void_p]
+    L.rsi_hot_process_setup.argtypes = []
     L.rsi_pool_worker.argtypes = [C.c_void_p, C.c_int]
     L.rsi_pool_worker.restype = C.c_void_p
     L.rsi_pool_set_timing.argtypes = [C.c_void_p, C.c_int]
@@ -649,6 +677,12 @@ class RsiPool:
             self.close()
         except Exception:
             pass
+
+    @property
+    def hw_queues(self):
+        """The hardware queues the process had asked for when the pool was made (rsi_pool_hw_queues): with more workers than
+        this minus two, workers share queues and the library has said so on stderr."""
+        return self.lib.rsi_pool_hw_queues(self.pool)
 
     def set_timing(self, on=True):
         self.lib.rsi_pool_set_timing(self.pool, int(on))

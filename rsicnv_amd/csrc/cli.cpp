@@ -660,8 +660,9 @@ bool finish_track(const std::string& file, const std::vector<size_t>& order, siz
 
 int main(int argc, char** argv) {
   // one hardware queue per stream of a pool (the runtime's default of 4 puts unrelated chromosomes in line behind each other);
-  // read when the HIP runtime initialises, so it has to be set before the first HIP call; the caller's own setting wins
-  setenv("GPU_MAX_HW_QUEUES", "32", 0);
+  // read when the HIP runtime initialises, so it has to be decided before the first HIP call.  A lower value found in the
+  // environment is raised to 32; RSI_HOT_HW_QUEUES=keep or =N is the caller's say (rsi_hot_process_setup, rsi_hot.h)
+  rsi_hot_process_setup();
   Options o;
   parse(argc, argv, o);
   if (o.function != "rsi") {

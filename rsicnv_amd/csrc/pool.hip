@@ -5,6 +5,7 @@
 #include "pipeline_internal.h"
 #include "run_queue.h"
 #include "retire.h"
+#include "process_setup.h"
 #include <memory>
 #include <thread>
 
@@ -41,6 +42,7 @@ struct PoolRun : rsip::RunBase {   // nitems = chromosomes
 
 struct rsi_pool {
   int device = 0;
+  int hw_queues = 0;   // GPU_MAX_HW_QUEUES when the pool was made (process_setup.h), the runtime's default if it held no number
   std::vector<rsi_ctx*> workers;
   GpuGate gate;
   std::string err;
@@ -143,6 +145,15 @@ rsi_pool* rsi_pool_create(int device, int nworkers, int* status) {
     c->gate_shared = iso && iso[0] == '1';   // default off: bin-level kernels of other chromosomes overlap the per-base phase
     pool->workers.push_back(c);
   }
+  // One stream per worker: with fewer hardware queues than streams the runtime puts unrelated chromosomes in line behind each
+  // other's kernels (INTEGRATION.md has the curve).  Said once per process, not per pool.
+  const int asked = rsip::env_hw_queues();
+  pool->hw_queues = asked > 0 ? asked : rsip::kRuntimeHwQueues;
+  static std::atomic<bool> warned{false};
+  if (nworkers > pool->hw_queues - rsip::kQueuesNotWorkers && !warned.exchange(true))
+    fprintf(stderr, "rsi_pool_create: %d workers share %d hardware queues (GPU_MAX_HW_QUEUES=%s): chromosomes wait behind each other's kernels; "
+                    "call rsi_hot_process_setup() before the process's first HIP call\n", nworkers, pool->hw_queues,
+            getenv("GPU_MAX_HW_QUEUES") ? getenv("GPU_MAX_HW_QUEUES") : "unset");
   pool->retire.reset(pool->workers.size());
   for (size_t w = 1; w < pool->workers.size(); ++w) pool->threads.emplace_back([pool, w] { pool->worker_loop(w); });
   if (status) *status = RSI_OK;
@@ -158,6 +169,7 @@ void rsi_pool_destroy(rsi_pool* pool) {
 }
 
 int rsi_pool_workers(const rsi_pool* pool) { return pool ? (int)pool->workers.size() : 0; }
+int rsi_pool_hw_queues(const rsi_pool* pool) { return pool ? pool->hw_queues : 0; }
 rsi_ctx* rsi_pool_worker(rsi_pool* pool, int w) { return (pool && w >= 0 && w < (int)pool->workers.size()) ? pool->workers[(size_t)w] : nullptr; }
 void rsi_pool_set_timing(rsi_pool* pool, int on) { if (pool) for (rsi_ctx* c : pool->workers) rsi_hot_set_timing(c, on); }
 void rsi_pool_set_timing_kernel(rsi_pool* pool, const char* name) { if (pool) for (rsi_ctx* c : pool->workers) rsi_hot_set_timing_kernel(c, name); }

@@ -3,6 +3,7 @@ sw="$1"; reps="${2:-2}"
 for r in $(seq 1 $reps); do
   for mode in off on; do
     if [ $mode = on ]; then export "$sw"; else unset "${sw%%=*}"; fi
+    echo "$mode $sw hardware queues asked for: $(python tools/hw_queues.py)"
     timeout -k 10 200 python bench.py --no-cpu-baseline --steps 10 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])

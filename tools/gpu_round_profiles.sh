@@ -5,6 +5,7 @@ cd $GRAFT_REPO_ROOT
 TAG=$1
 OUT=$GRAFT_REPO_ROOT/gpurun_out/round_$TAG
 mkdir -p $OUT
+echo "hardware queues asked for: $(python tools/hw_queues.py)" | tee $OUT/hw_queues.txt
 timeout -k 10 500 python bench.py > $OUT/bench.json 2> $OUT/bench.err
 echo "bench done"
 bash tools/gpu_trace.sh ${TAG}_pool > $OUT/trace_pool.log 2>&1

@@ -159,6 +159,7 @@ struct Oracle {
   struct Scan {
     double tmedian1 = 0, tsigma1 = 0, tlamda1 = 0, tmedian2 = 0, tsigma2 = 0, tlamda2 = 0, target = 0;
     int Lmax = 0, cal_max = 0;
+    double absmed1 = 0;   // the first pass' median absolute deviation, before the division by 0.6745
     std::vector<int> st1, st1f, st2;
     std::vector<Cnv> segs;
     int trim_escapes = 0;
@@ -434,12 +435,13 @@ struct Oracle {
     const std::vector<float>& T = use_med ? binmed : binnb;
     const int nb = (int)T.size();
     std::vector<float> tmp(nb);
-    double tmedian, tsigma, tlamda, target, dev;
+    double tmedian, tsigma, tlamda, target, dev, absmed;
     int Lmax = LmaxBase, cal_max;
     if (!use_med) {
       tmedian = pmedian(T.data(), T.size());
       for (int i = 0; i < nb; ++i) tmp[i] = (float)fabs(T[i] - tmedian);
-      tsigma = pmedian(tmp.data(), tmp.size()) / 0.6745;
+      absmed = pmedian(tmp.data(), tmp.size());
+      tsigma = absmed / 0.6745;
       tlamda = factor * tsigma;
       target = (T[2] - T[0]) * sqrt(2.5);
       tlamda = std::max(tlamda, target);
@@ -450,7 +452,8 @@ struct Oracle {
     } else {
       tmedian = RDmedian;
       for (int i = 0; i < nb; ++i) tmp[i] = (float)fabs(T[i] - tmedian);
-      tsigma = pmedian(tmp.data(), tmp.size()) / 0.6745;
+      absmed = pmedian(tmp.data(), tmp.size());
+      tsigma = absmed / 0.6745;
       tlamda = factor * tsigma;
       target = tmedian * sqrt(2.0);
       tlamda = std::max(tlamda, target);
@@ -461,6 +464,7 @@ struct Oracle {
     }
     if (Lmax < cal_max) Lmax = cal_max;
     R.tmedian1 = tmedian; R.tsigma1 = tsigma; R.tlamda1 = tlamda; R.target = target; R.Lmax = Lmax; R.cal_max = cal_max;
+    R.absmed1 = absmed;
     R.trim_escapes = 0;
     rsistatus(T, tmedian, tlamda, Lmax, R.st1, R.trim_escapes);
     R.st1f = R.st1;
@@ -918,7 +922,7 @@ int64_t orc_get_f64(void* h, const char* name, double* out, int64_t cap) {
   else if (s == "scan_nb" || s == "scan_med") {
     const orc::Oracle::Scan& R = s == "scan_nb" ? O.scan_nb : O.scan_med;
     v = {R.tmedian1, R.tsigma1, R.tlamda1, R.tmedian2, R.tsigma2, R.tlamda2, R.target, (double)R.Lmax, (double)R.cal_max,
-         (double)R.trim_escapes};
+         (double)R.trim_escapes, R.absmed1};
   } else if (s == "stage_s") v.assign(O.stage_s, O.stage_s + 5);
   else return -1;
   for (int64_t i = 0; i < (int64_t)v.size() && i < cap; ++i) out[i] = v[i];

@@ -335,6 +335,8 @@ size_t scan_tile_workspace_bytes(int Lmax);   // 0: the exact sweep's tile fits 
 // host_copy (mapped host memory).
 constexpr int kMaxLevels = 10416;   // >= kMaxScanL + 1 + kScanPad, a multiple of 4
 inline int scan_level_stride(int Lmax) { return (Lmax + 1 + kScanPad + 3) & ~3; }   // hist_dup sits this many words behind hist_del
+// the words of that record the host reads (pipeline_steps.h: ScanRecord); [8] is the scan's own (tiles listed, launch_rsi_scan)
+constexpr int kScanRecEscapes = 0, kScanRecInexact = 1, kScanRecStop = 2 /* ldel, ldup */, kScanRecTiles = 8, kScanRecLevels = 16;
 constexpr size_t kScanWorkBytes = 64 + 2 * (size_t)kMaxLevels * 4;
 void launch_level_stop(const uint32_t* first_del, const uint32_t* first_dup, int64_t nb, int32_t Lmax, uint32_t* work, void* both,
                        unsigned int* counter, void* host_copy, size_t host_bytes, hipStream_t stream);

@@ -6,6 +6,7 @@
 // device-built histograms and runs the candidate list logic (host_calls.cpp).
 #include <new>
 #include "pipeline_internal.h"
+#include "pipeline_steps.h"   // the host decisions between the kernels, as pure functions (tested on the CPU: tests/sanitize)
 
 using namespace rsik;
 using namespace rsip;
@@ -13,8 +14,6 @@ using rsih::Candidate;
 using rsih::Region;
 
 namespace {
-
-struct ScanPassOut { uint32_t escapes, inexact, ldel, ldup; };   // what one rsistatus pass leaves in `small`
 
 struct ScanOut {
   double tmedian1 = 0, tsigma1 = 0, tlamda1 = 0, tmedian2 = 0, tsigma2 = 0, tlamda2 = 0;
@@ -70,8 +69,7 @@ int grid_median(rsi_ctx* ctx, const float* d_x, const int32_t* d_mask, int64_t n
   HIPCHK(CTX_SYNC());
   if (mm.min_inv == 0u) { *count = 0; *med = 0; return RSI_OK; }
   if (mm.nonfinite) return fail(ctx, RSI_ERR_UNSUPPORTED, "non-finite value in the transformed bins");
-  auto unkey = [](uint32_t k) { uint32_t b = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k; float f; memcpy(&f, &b, 4); return f; };
-  const double ymin = unkey(~mm.min_inv), ymax = unkey(mm.max_bits);
+  const double ymin = rsih::unkey_f32(~mm.min_inv), ymax = rsih::unkey_f32(mm.max_bits);
   if ((ymax - ymin) < 0.01) return selection_mean(ctx, d_x, d_mask, nb, use_abs, center, med, count);
   const size_t np = (size_t)((ymax - ymin) / 0.01 + 2);
   if (np > (64u << 20)) return fail(ctx, RSI_ERR_UNSUPPORTED, "transformed bin range too wide for the 0.01 grid");
@@ -164,33 +162,6 @@ void scan_thresholds(double tmedian, double tlamda, int Lmax, std::vector<double
   }
 }
 
-// Collect (pos << 1 | is_end) boundary entries from the device into sorted [start, end] pairs.
-int fetch_pairs(rsi_ctx* ctx, const uint64_t* d_list, const uint32_t* d_count, uint32_t cap, std::vector<Region>& out,
-                bool end_exclusive) {
-  // the count and the first entries travel together (one round trip for all but the longest lists)
-  constexpr uint32_t kEager = 1024;
-  uint32_t cnt = 0;
-  std::vector<uint64_t> raw(kEager);
-  HIPCHK(copy_d2h(ctx, &cnt, d_count, 4));
-  HIPCHK(copy_d2h(ctx, raw.data(), d_list, (size_t)std::min(cap, kEager) * 8));
-  HIPCHK(CTX_SYNC());
-  out.clear();
-  if (cnt == 0) return RSI_OK;
-  if (cnt > cap) return fail(ctx, RSI_ERR_UNSUPPORTED, "boundary list overflow");
-  raw.resize(cnt);
-  if (cnt > kEager) {
-    HIPCHK(copy_d2h(ctx, raw.data() + kEager, d_list + kEager, (size_t)(cnt - kEager) * 8));
-    HIPCHK(CTX_SYNC());
-  }
-  std::vector<int64_t> s, e;
-  for (uint64_t v : raw) ((v & 1) ? e : s).push_back((int64_t)(v >> 1));
-  if (s.size() != e.size()) return fail(ctx, RSI_ERR_INTERNAL, "unbalanced run boundaries");
-  std::sort(s.begin(), s.end());
-  std::sort(e.begin(), e.end());
-  for (size_t i = 0; i < s.size(); ++i) out.push_back({(int)s[i], (int)(e[i] - (end_exclusive ? 1 : 0))});
-  return RSI_OK;
-}
-
 // Marked runs in the reference's sense (last run not emitted, Q11) from what k_resolve_runs left in the mailbox
 // ([count, 0][first kEagerBounds boundary entries]) and, for longer lists, in the device list.
 constexpr uint32_t kEagerBounds = 1024;
@@ -205,12 +176,7 @@ int runs_from_export(rsi_ctx* ctx, const uint32_t* slot, const uint64_t* d_list,
     HIPCHK(copy_d2h(ctx, raw.data() + kEagerBounds, d_list + kEagerBounds, (size_t)(cnt - kEagerBounds) * 8));
     HIPCHK(CTX_SYNC());
   }
-  std::vector<int64_t> s, e;
-  for (uint64_t v : raw) ((v & 1) ? e : s).push_back((int64_t)(v >> 1));
-  if (s.size() != e.size()) return fail(ctx, RSI_ERR_INTERNAL, "unbalanced run boundaries");
-  std::sort(s.begin(), s.end());
-  std::sort(e.begin(), e.end());
-  for (size_t i = 0; i < s.size(); ++i) runs.push_back({(int)s[i], (int)e[i]});
+  if (!rsih::boundary_pairs(raw.data(), raw.size(), false, runs)) return fail(ctx, RSI_ERR_INTERNAL, "unbalanced run boundaries");
   runs.pop_back();
   return RSI_OK;
 }
@@ -447,7 +413,7 @@ class DeviceTester : public rsih::NeighbourTester {
 // One rsistatus pass on the device (rsi.cpp:1191-1259) -> d_status (and d_copy).  Three launches and no round trip: the scan
 // (thresholds in the kernel arguments), the stop levels of the two sweeps, the status values with the run boundaries.  The
 // first-L arrays, the work block and the boundary counter were cleared by the last launch of the quantile chain in front.
-// What the host wants from the pass lands in the pinned mailbox: *work_slot = [ScanPassOut | per-L counts], *runs_slot =
+// What the host wants from the pass lands in the pinned mailbox: *work_slot = the pass's record (rsih::ScanRecord), *runs_slot =
 // [count | first boundaries].
 // A scan longer than kMaxL (a computed length, rsi.cpp:1286-1289, beyond 10 400 bins: a large -threshold, a very noisy chromosome)
 // takes the same launches with its work block in a buffer of its own (the resident one is sized for kMaxL), cleared here, and
@@ -507,10 +473,10 @@ int scan_pass(rsi_ctx* ctx, int pass, const float* d_T, const int32_t* d_medint,
 int run_scan(rsi_ctx* ctx, const rsi_params& P, bool use_med, const float* d_T, int64_t nb, double RDmedian,
              double factor, int LmaxBase, ChainOut* first, double nb_med_raw, double nb_del_raw, double nb_dup_raw, ScanOut& out) {
   const int32_t* d_medint = ctx->binmed.as<int32_t>();
-  double tmedian, tsigma, tlamda, target, dev, absmed;
+  double tmedian, absmed;
   uint64_t cnt;
-  int rc, cal_max;
-  float t0 = 0, t2 = 0;
+  int rc;
+  rsih::NbScaled lv{0, 0};
   {
     Phase ph(ctx, "scan.quantiles");
     HIPCHK(CTX_SYNC());
@@ -533,42 +499,16 @@ int run_scan(rsi_ctx* ctx, const rsi_params& P, bool use_med, const float* d_T, 
       if (rc != RSI_OK) return rc;
     }
     if (!use_med) {   // the scaled reference levels (bins 0 and 2), as k_nb_scale_mm derived them from the raw minimum
-      const uint32_t key = ~first->rawmin_inv;
-      float tminf;
-      { const uint32_t b = (key & 0x80000000u) ? (key & 0x7fffffffu) : ~key; memcpy(&tminf, &b, 4); }
-      const double tmin = tminf;
-      const double med_nbt = nb_med_raw - tmin;
-      t0 = (float)((nb_del_raw - tmin) / med_nbt * RDmedian);
-      t2 = (float)(med_nbt / med_nbt * RDmedian);
+      lv = rsih::nb_scaled_levels(rsih::unkey_f32(~first->rawmin_inv), nb_med_raw, nb_del_raw, RDmedian);
       (void)nb_dup_raw;
     }
   }
-  tsigma = absmed / 0.6745;
-  tlamda = factor * tsigma;
-  if (!use_med) {
-    target = (t2 - t0) * sqrt(2.5);                 // float difference, as RDtrans[2]-RDtrans[0]
-    tlamda = std::max(tlamda, target);
-    const double dnb = fabsf(t2 - t0) + 0.0001;
-    const double q = tlamda * 2 / dnb;
-    cal_max = (int)(q * q);
-    dev = tsigma * 3.0;
-  } else {
-    target = tmedian * sqrt(2.0);
-    tlamda = std::max(tlamda, target);
-    if (P.threshold > 0) tlamda = tmedian * P.threshold;
-    const double q = tlamda * 4 / (tmedian + 0.001);
-    cal_max = (int)(q * q);
-    dev = tmedian * 0.6;
-  }
-  int Lmax = LmaxBase;
-  if (Lmax < cal_max) Lmax = cal_max;
-  out.tmedian1 = tmedian; out.tsigma1 = tsigma; out.tlamda1 = tlamda; out.Lmax = Lmax;   // the reference's Lmax, as its log prints it
-  // More lengths than bins: the reference's sweeps run L = 1, 2, ... and the PROGRAM exits at L = nb + 1 (runmean refuses a
-  // span beyond the array, wufunctions.cpp:589-596) -- unless the 20 % rule (rsi.cpp:1226, 1256) has ended the sweep before,
-  // which on a chromosome with so few bins per length it usually has.  So the scan runs up to nb lengths, and a sweep that
-  // gets there without having stopped is what the reference exits on.
-  const bool clipped = Lmax > nb;
-  if (clipped) Lmax = (int)nb;
+  const rsih::ScanSetup su = rsih::scan_first_pass(use_med, tmedian, absmed, factor, LmaxBase, lv.t0, lv.t2, P.threshold, nb);
+  double tsigma = su.tsigma, tlamda = su.tlamda;
+  const double target = su.target, dev = su.dev;
+  const int Lmax = su.Lmax;
+  const bool clipped = su.clipped;   // more lengths than bins: the scan runs up to nb of them (pipeline_steps.h)
+  out.tmedian1 = tmedian; out.tsigma1 = tsigma; out.tlamda1 = tlamda; out.Lmax = su.Lmax_ref;   // the reference's Lmax, as its log prints it
   // Up to kMaxL (the reference's own ceiling without a larger computed length is 10000, at -m 1) everything the scan needs is
   // resident; beyond, the scan takes its long form (scan_pass; kernels_bin.hip: device-memory tiles, 32-bit staged indices past
   // 32 000, per-L counts in device memory past 20 000) and filterstatus' level sums run on the host.  kHardMaxL bounds the
@@ -576,14 +516,16 @@ int run_scan(rsi_ctx* ctx, const rsi_params& P, bool use_med, const float* d_T, 
   if (Lmax > kHardMaxL) return fail(ctx, RSI_ERR_UNSUPPORTED, "scan length Lmax beyond 4194304 bins");
   const bool long_scan = Lmax > kMaxL;
   std::vector<uint32_t> spill1, spill2;
-  auto sweeps_stopped = [&](const uint32_t* w) -> bool {   // both sweeps of a pass ended by the 20 % rule (w: the pass's work block)
+  // what a pass's record tells the run: the reference's exit (a sweep reached every bin), the counters, the per-L log of sweeps 2 * pass, 2 * pass + 1
+  auto take_record = [&](const uint32_t* w, int pass) -> int {
+    const rsih::ScanRecord rec{w, Lmax};
+    if (clipped && !rec.sweeps_stopped(nb)) return fail(ctx, RSI_ERR_TOO_SMALL, "fewer bins than the scan length, and a sweep reached them all (the reference exits in runmean)");
+    out.escapes += rec.escapes(); out.inexact = rec.inexact(); out.tiles_listed += rec.tiles_listed();
     for (int k = 0; k < 2; ++k) {
-      const uint32_t* cnt = w + 16 + (size_t)k * scan_level_stride(Lmax);
-      uint64_t cum = 0;
-      for (uint32_t L = 0; L <= w[2 + k] && L <= (uint32_t)Lmax; ++L) cum += cnt[L];
-      if (!((double)(int)cum / (double)(int)nb > 0.2)) return false;
+      out.level_log[2 * pass + k].assign(rec.level_counts(k), rec.level_counts(k) + Lmax + 1);
+      out.stop_levels[2 * pass + k] = rec.stop_level(k);
     }
-    return true;
+    return RSI_OK;
   };
 
   int32_t* d_st1 = ctx->status1.as<int32_t>();
@@ -607,11 +549,7 @@ int run_scan(rsi_ctx* ctx, const rsi_params& P, bool use_med, const float* d_T, 
                       reinterpret_cast<unsigned int*>(ctx->small.as<uint8_t>() + kOffDone) + kDoneBinSlot + 4, fs_slot, ctx->stream);
   }
   { Phase phc(ctx, "fs.wait"); HIPCHK(CTX_SYNC()); }
-  if (clipped && !sweeps_stopped(wslot)) return fail(ctx, RSI_ERR_TOO_SMALL, "fewer bins than the scan length, and a sweep reached them all (the reference exits in runmean)");
-  out.escapes += wslot[0]; out.inexact = wslot[1]; out.tiles_listed += wslot[8];
-  out.level_log[0].assign(wslot + 16, wslot + 16 + Lmax + 1);
-  out.level_log[1].assign(wslot + 16 + scan_level_stride(Lmax), wslot + 16 + scan_level_stride(Lmax) + Lmax + 1);
-  out.stop_levels[0] = wslot[2]; out.stop_levels[1] = wslot[3];
+  if ((rc = take_record(wslot, 0)) != RSI_OK) return rc;
   {
     Phase phs(ctx, "fs.sums");
     // status values lie in [-Lmax, Lmax].  The level range the reference works on is [min status, max status]: taken from
@@ -629,41 +567,15 @@ int run_scan(rsi_ctx* ctx, const rsi_params& P, bool use_med, const float* d_T, 
       HIPCHK(hipMemcpyAsync(ctx->h_T.p, d_T, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
       HIPCHK(hipMemcpyAsync(ctx->h_status.p, d_st1, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
       HIPCHK(CTX_SYNC());
-      const int* st = ctx->h_status.as<int>();
-      const float* tv = ctx->h_T.as<float>();
-      std::fill(wsum.begin(), wsum.end(), 0.0f);
-      std::fill(wcnt.begin(), wcnt.end(), 0);
-      float s0 = 0.0f;
-      int n0 = 0;
-      for (int64_t i = 0; i < nb; ++i) {
-        const int sv = st[i];
-        if (sv == 0) { s0 += tv[i]; ++n0; }
-        else { wsum[(size_t)(sv + Lmax)] += tv[i]; ++wcnt[(size_t)(sv + Lmax)]; }
-      }
-      wsum[(size_t)Lmax] = s0; wcnt[(size_t)Lmax] = n0;
+      rsih::level_sums_host(ctx->h_T.as<float>(), ctx->h_status.as<int>(), nb, Lmax, wsum, wcnt);
     }
-    int lo = 0, hi = 0;
-    { int a = 0, b = 2 * Lmax; while (a < b && wcnt[a] == 0) ++a; while (b > a && wcnt[b] == 0) --b; lo = a - Lmax; hi = b - Lmax; }
-    const int nl = hi - lo + 1;
-    std::vector<float> lsum(wsum.begin() + (lo + Lmax), wsum.begin() + (hi + Lmax + 1));
-    std::vector<int> lcnt(wcnt.begin() + (lo + Lmax), wcnt.begin() + (hi + Lmax + 1));
-    for (int l = 0; l < nl; ++l) if (lcnt[l] != 0) lsum[l] /= (double)lcnt[l];
+    rsih::LevelChoice lc = rsih::choose_levels(wsum, wcnt, Lmax, dev);
     phs.stop();
     Phase phr(ctx, "fs.runs");
-    if (lo <= 0 && -lo < nl) {
-      const float m0 = lsum[-lo];
-      int leveldel = lo, leveladd = hi;
-      for (int l = 0; l < nl; ++l) if (lsum[l] < m0 - dev) { leveldel = l + lo; break; }
-      for (int l = nl - 1; l >= 0; --l) if (lsum[l] > m0 + dev) { leveladd = l + lo; break; }
-      {   // the table the reference writes to its log: level, bins, mean; then the two chosen levels (rsi.cpp:991-997)
-        char line[128];
-        out.fs_lines.clear();
-        for (int l = 0; l < nl; ++l) if (lcnt[l] != 0) { snprintf(line, sizeof(line), "%d\t%d\t%g", l + lo, lcnt[l], (double)lsum[l]); out.fs_lines.push_back(line); }
-        snprintf(line, sizeof(line), "%d\t%g", leveldel, (double)lsum[leveldel - lo]); out.fs_lines.push_back(line);
-        snprintf(line, sizeof(line), "%d\t%g", leveladd, (double)lsum[leveladd - lo]); out.fs_lines.push_back(line);
-        if (leveldel > 0 || leveladd < 0 || leveldel > leveladd) out.fs_lines.push_back("warning level error, status not filtered");
-      }
-      if (!(leveldel > 0 || leveladd < 0 || leveldel > leveladd)) {
+    if (lc.has_level0) {
+      const float m0 = lc.m0;
+      out.fs_lines = std::move(lc.lines);   // filterstatus' level table as the reference logs it (rsi.cpp:991-997)
+      if (lc.trim) {
         std::vector<Region> runs;
         GateShared gs(ctx);
         if ((rc = runs_from_export(ctx, rslot, ctx->runs.as<uint64_t>(), runs)) != RSI_OK) return rc;
@@ -693,9 +605,8 @@ int run_scan(rsi_ctx* ctx, const rsi_params& P, bool use_med, const float* d_T, 
       tmedian = tmed2;
       if ((rc = (wide2 || (g2[1].flags & (kGridTooWide)) || (g2[0].flags & kGridDegenerate)) ? grid_median(ctx, d_T, d_st1f, nb, 1, tmedian, &absmed, &cnt)
                                                         : grid_result(ctx, g2[1], Selection{d_T, d_st1f, nb, 1, tmedian}, &absmed, &cnt)) != RSI_OK) return rc;
-      tsigma = absmed / 0.6745;
-      tlamda = factor * tsigma;
-      tlamda = std::max(tlamda, target);
+      const rsih::Lamda l2 = rsih::lamda_from_mad(absmed, factor, target);
+      tsigma = l2.tsigma; tlamda = l2.tlamda;
     }
   }
   out.tmedian2 = tmedian; out.tsigma2 = tsigma; out.tlamda2 = tlamda;
@@ -708,15 +619,11 @@ int run_scan(rsi_ctx* ctx, const rsi_params& P, bool use_med, const float* d_T, 
   HIPCHK(CTX_SYNC());
   std::vector<Region> runs;
   if ((rc = runs_from_export(ctx, rslot, ctx->runs.as<uint64_t>(), runs)) != RSI_OK) return rc;
-  if (clipped && !sweeps_stopped(wslot)) return fail(ctx, RSI_ERR_TOO_SMALL, "fewer bins than the scan length, and a sweep reached them all (the reference exits in runmean)");
-  out.escapes += wslot[0]; out.inexact = wslot[1]; out.tiles_listed += wslot[8];
-  out.level_log[2].assign(wslot + 16, wslot + 16 + Lmax + 1);
-  out.level_log[3].assign(wslot + 16 + scan_level_stride(Lmax), wslot + 16 + scan_level_stride(Lmax) + Lmax + 1);
-  out.stop_levels[2] = wslot[2]; out.stop_levels[3] = wslot[3];
+  if ((rc = take_record(wslot, 1)) != RSI_OK) return rc;
   out.status2 = rsih::IntSpan();
   out.segs.clear();
   if (runs.empty()) return RSI_OK;
-  std::vector<int64_t> poff(runs.size() + 1, 0);
+  std::vector<int64_t> poff;
   std::vector<SegItem> items;
   // About 256 (L, offset) pairs per thread of a workgroup in a pool that shares the chip (a long, thin kernel there costs the
   // other chromosomes next to nothing).  A chromosome that has the chip to itself (a stand-alone context, a pool run over a
@@ -729,18 +636,7 @@ int run_scan(rsi_ctx* ctx, const rsi_params& P, bool use_med, const float* d_T, 
     const int64_t room = std::max<int64_t>(8, (int64_t)kItemsInline - 2 * (int64_t)runs.size());   // every run's last item is a partial one
     pairs_per_item = std::min<int64_t>(pairs_per_item, std::max<int64_t>(1 << 13, total / room + 1));
   }
-  const int64_t kPairsPerItem = pairs_per_item;
-  for (size_t r = 0; r < runs.size(); ++r) {
-    const int len = runs[r].end - runs[r].start + 1;
-    poff[r + 1] = poff[r] + len + 1;
-    int L = 1;
-    while (L <= len) {   // chunks of lengths with about kPairsPerItem (L, offset) pairs
-      int64_t pairs = 0; int Le = L;
-      while (Le <= len && pairs < kPairsPerItem) { pairs += len - Le + 1; ++Le; }
-      items.push_back({(int32_t)r, (int32_t)len, (int32_t)L, (int32_t)Le});
-      L = Le;
-    }
-  }
+  rsih::segment_items(runs, pairs_per_item, poff, items);
   HIPCHK(ctx->scratch.ensure((size_t)poff.back() * 8 + (runs.size() + 1) * 8));
   double* d_scratch = ctx->scratch.as<double>();
   // short lists ride in the kernel arguments and the per-item results land in the pinned mailbox: two launches, no copy
@@ -795,22 +691,7 @@ int run_scan(rsi_ctx* ctx, const rsi_params& P, bool use_med, const float* d_T, 
     HIPCHK(copy_d2h(ctx, best.data(), ctx->best.p, items.size() * sizeof(BestSeg)));
     HIPCHK(CTX_SYNC());
   }
-  std::vector<BestSeg> per_run(runs.size(), BestSeg{-1.0, 0, 0});
-  for (size_t i = 0; i < items.size(); ++i) {   // items of a run are in increasing L: strict > keeps the earliest
-    BestSeg& b = per_run[(size_t)items[i].run];
-    if (best[i].score > b.score) b = best[i];
-  }
-  for (size_t r = 0; r < runs.size(); ++r) {
-    Candidate c;
-    const int len = runs[r].end - runs[r].start + 1;
-    double sc = per_run[r].score;
-    if (sc > 0) { c.start = runs[r].start + per_run[r].start; c.end = c.start + per_run[r].len - 1; }
-    else { c.start = runs[r].start; c.end = runs[r].start + len - 1; sc = 0; }
-    const rsih::Quantiles q = rsih::grid_quantiles(out.status2.at(c.start), (size_t)(c.end - c.start + 1));
-    if (q.med > 0) { c.type = rsih::kDup; c.score = sc; } else { c.type = rsih::kDel; c.score = -sc; }
-    if (fabs(c.score) < tlamda * 0.5) continue;   // rsi.cpp:1343-1346
-    out.segs.push_back(c);
-  }
+  rsih::segments_from_best(runs, items, best.data(), out.status2, tlamda, out.segs);
   return RSI_OK;
 }
 
@@ -839,17 +720,6 @@ constexpr size_t kResHead = 256;     // BinAccum sits in a header of the residue
 // The device's integer statistics are walks over directly indexed histograms of 65 536 values (kHistValues).  A chromosome
 // whose median depth lies above that (or, without a cap, any value) used to be refused; now the array itself comes to the host
 // -- 4 bytes per base over PCIe, a selection instead of a histogram walk: seconds for a large chromosome, and exact.
-// value at which the cumulated count first reaches `rank` (partition_stat_tp's walk with dy = 1, wufunctions.cpp:398-420, as
-// hist_quantiles_int restates it): the rank-th smallest, the minimum for rank 0 or when all values are equal
-static double rank_value_i32(std::vector<int32_t>& v, uint64_t rank) {
-  if (v.empty()) return 0.0;
-  const auto mm = std::minmax_element(v.begin(), v.end());
-  const int32_t lo = *mm.first, hi = *mm.second;
-  if ((double)hi - (double)lo < 1.0 || rank == 0) return (double)lo;
-  const size_t k = (size_t)std::min<uint64_t>(rank, v.size()) - 1;
-  std::nth_element(v.begin(), v.begin() + k, v.end());
-  return (double)v[k];
-}
 // the device array d_src[0 .. n) on the host
 static int fetch_i32(rsi_ctx* ctx, const int32_t* d_src, int64_t n, std::vector<int32_t>& out) {
   out.resize((size_t)n);
@@ -1111,40 +981,46 @@ int per_base_phase(rsi_ctx* ctx, const rsi_params& P, const int32_t* d_depth, co
   ph_a1b.stop();
   { Phase ph_a1c(ctx, "a1c.wait K1-K3"); HIPCHK(CTX_SYNC()); }
   unpack_head();
+  // One rung of the redo ladder: clear what `fl` lists (nothing listed: no launch), issue, wait, read the header again.
+  auto redo = [&](const char* name, const FillList& fl, auto&& issue) -> int {
+    Phase ph(ctx, name);
+    if (fl.n) launch_fill(fl, st);
+    const int rcr = issue();
+    if (rcr != RSI_OK) return rcr;
+    HIPCHK(CTX_SYNC());
+    unpack_head();
+    return RSI_OK;
+  };
+  static_assert(sizeof(ValueHistAux) == 16, "ValueHistAux is cleared as one 16-byte unit");
+  auto clean_value_hist = [&](FillList& fl) {
+    fill_add(fl, ctx->hist_val.p, (size_t)kHistValues * 4, 0u);
+    fill_add(fl, d_aux, 16, 0u);
+  };
   bool joint_ok = joint;
   if (joint && (acc.negatives & 4u)) {
     // a workgroup's 16-bit pair counters wrapped (a sequence without GC variation under a constant depth): the three-pass
     // chain from clean accumulators
-    Phase ph_w(ctx, "a2-3.joint wrapped: three-pass chain");
-    joint_ok = false;
     FillList fl{};
     fill_add(fl, small + kOffGcAcc, 4096, 0u);
-    fill_add(fl, ctx->hist_val.p, (size_t)kHistValues * 4, 0u);
-    fill_add(fl, d_aux, 16, 0u);
+    clean_value_hist(fl);
     fill_add(fl, d_vm, 32, 0u);
-    launch_fill(fl, st);
-    if ((rc = issue_gc_chain(1)) != RSI_OK) return rc;
-    HIPCHK(CTX_SYNC());
-    unpack_head();
+    if ((rc = redo("a2-3.joint wrapped: three-pass chain", fl, [&] { return issue_gc_chain(1); })) != RSI_OK) return rc;
+    joint_ok = false;
   }
   if (joint_ok && !(acc.negatives & 1u) && jinfo.esc_pending && (uint64_t)acc.escapes <= (uint64_t)byte_escape_limit(n)) {
     // depths of 255 and more are not in K2j's pair counters, and there were too many for its last workgroup to add them from the
     // workgroups' lists: their rescaled values enter the histogram now, then the median walk
-    Phase ph_e(ctx, "a2-3.escapes");
-    { Timer t(ctx, "escape_hist", true); launch_escape_hist(ctx->depth8.as<uint8_t>(), d_depth, ctx->gcbits.as<uint64_t>(), n, d_table, ctx->hist_val.as<uint32_t>(), d_aux, d_done + kDoneStride, d_vm, small, head, head_bytes, st); }
-    HIPCHK(CTX_SYNC());
-    unpack_head();
+    rc = redo("a2-3.escapes", FillList{}, [&] {
+      Timer t(ctx, "escape_hist", true);
+      launch_escape_hist(ctx->depth8.as<uint8_t>(), d_depth, ctx->gcbits.as<uint64_t>(), n, d_table, ctx->hist_val.as<uint32_t>(), d_aux, d_done + kDoneStride, d_vm, small, head, head_bytes, st);
+      return RSI_OK;
+    });
+    if (rc != RSI_OK) return rc;
   }
   if (P.gcadjust && !joint_ok && (acc.negatives & 2u)) {
-    Phase ph_w(ctx, "a2-3.gc wide redo");
     FillList fl{};
-    fill_add(fl, ctx->hist_val.p, (size_t)kHistValues * 4, 0u);
-    fill_add(fl, d_aux, 16, 0u);
-    static_assert(sizeof(ValueHistAux) == 16, "ValueHistAux is cleared as one 16-byte unit");
-    launch_fill(fl, st);
-    if ((rc = issue_gc_chain(0)) != RSI_OK) return rc;
-    HIPCHK(CTX_SYNC());
-    unpack_head();
+    clean_value_hist(fl);
+    if ((rc = redo("a2-3.gc wide redo", fl, [&] { return issue_gc_chain(0); })) != RSI_OK) return rc;
   }
 
   // Deep coverage: more than an eighth of the bases did not fit K2's byte copy, and K3' only handed the header over.  The
@@ -1152,19 +1028,17 @@ int per_base_phase(rsi_ctx* ctx, const rsi_params& P, const int32_t* d_depth, co
   // depth, kernels.h: hist_window_base), which also leaves the rescaled int32 array for K4.
   bool deep = false;
   if (P.gcadjust && (uint64_t)acc.escapes > (uint64_t)byte_escape_limit(n)) {
-    Phase ph_d(ctx, "a2-3.deep coverage");
+    FillList fl{};
+    if (joint_ok) clean_value_hist(fl);   // K2j's last workgroup has counted the byte-sized depths already: the int32 kernel starts from a clean histogram
+    rc = redo("a2-3.deep coverage", fl, [&]() -> int {
+      HIPCHK(ctx->rd_gc.ensure((size_t)(n + 4) * 4));
+      HIPCHK(ctx->slabs.ensure(gc_rescale_slab_bytes(n)));
+      Timer t(ctx, "gc_rescale", true);
+      launch_gc_rescale(d_depth, ctx->gcbits.as<uint64_t>(), n, d_table, 1, ctx->rd_gc.as<int32_t>(), ctx->hist_val.as<uint32_t>(), d_aux, ctx->slabs.p, ctx->gsum.p, d_done + kDoneStride, d_vm, small, head, head_bytes, st);
+      return RSI_OK;
+    });
+    if (rc != RSI_OK) return rc;
     deep = true;
-    if (joint_ok) {   // K2j's last workgroup has counted the byte-sized depths already: the int32 kernel starts from a clean histogram
-      FillList fl{};
-      fill_add(fl, ctx->hist_val.p, (size_t)kHistValues * 4, 0u);
-      fill_add(fl, d_aux, 16, 0u);
-      launch_fill(fl, st);
-    }
-    HIPCHK(ctx->rd_gc.ensure((size_t)(n + 4) * 4));
-    HIPCHK(ctx->slabs.ensure(gc_rescale_slab_bytes(n)));
-    { Timer t(ctx, "gc_rescale", true); launch_gc_rescale(d_depth, ctx->gcbits.as<uint64_t>(), n, d_table, 1, ctx->rd_gc.as<int32_t>(), ctx->hist_val.as<uint32_t>(), d_aux, ctx->slabs.p, ctx->gsum.p, d_done + kDoneStride, d_vm, small, head, head_bytes, st); }
-    HIPCHK(CTX_SYNC());
-    unpack_head();
     ctx->rd_gc_valid = true;
   }
 
@@ -1177,21 +1051,9 @@ int per_base_phase(rsi_ctx* ctx, const rsi_params& P, const int32_t* d_depth, co
       HIPCHK(copy_d2h(ctx, trans_raw.data() + kEagerRuns, d_ntrans + kEagerRuns, (size_t)(n_trans - kEagerRuns) * 8));
       HIPCHK(CTX_SYNC());
     }
-    std::vector<int64_t> rs, re;
-    for (uint32_t i = 0; i < n_trans; ++i) { const uint64_t v = trans_raw[i]; ((v & 1) ? re : rs).push_back((int64_t)(v >> 1)); }
-    if (rs.size() != re.size()) return fail(ctx, RSI_ERR_INTERNAL, "unbalanced run boundaries");
-    std::sort(rs.begin(), rs.end());
-    std::sort(re.begin(), re.end());
-    for (size_t i = 0; i < rs.size(); ++i) nruns.push_back({(int)rs[i], (int)(re[i] - 1)});
+    if (!rsih::boundary_pairs(trans_raw.data(), n_trans, true, nruns)) return fail(ctx, RSI_ERR_INTERNAL, "unbalanced run boundaries");
   }
-  {
-    const int dx = std::max(50, P.m / 4);
-    for (const Region& r : nruns) {
-      Region g{std::max(0, r.start - dx), (int)std::min<int64_t>(n - 1, (int64_t)r.end + dx)};
-      if (!noncode.empty() && g.start <= noncode.back().end + 1) noncode.back().end = std::max(noncode.back().end, g.end);
-      else noncode.push_back(g);
-    }
-  }
+  noncode = rsih::noncode_regions(nruns, n, std::max(50, P.m / 4));
   if ((int)noncode.size() > kMaxRegions) return fail(ctx, RSI_ERR_UNSUPPORTED, "more than 4096 N regions");
   S.n_noncode = (int)noncode.size();
   res->noncode.clear();
@@ -1213,10 +1075,8 @@ int per_base_phase(rsi_ctx* ctx, const rsi_params& P, const int32_t* d_depth, co
   if (want_cap) {
     if (aux.negatives) return fail(ctx, RSI_ERR_UNSUPPORTED, "negative depth values");
     if (vm.inrange + aux.big != (uint64_t)n) return fail(ctx, RSI_ERR_INTERNAL, "value histogram does not add up to n");
-    rsih::Quantiles q;   // hist_quantiles_int's result for the median (hostmath.h), from the device's walk
-    q.med = (double)vm.lo;
-    if (vm.lo <= vm.hi && (double)vm.hi - (double)vm.lo >= 1.0 && vm.med >= 0) q.med = (double)vm.med;
-    if ((uint64_t)n / 2 > vm.inrange) {
+    rsih::CapMedian q = rsih::cap_median(vm, n);
+    if (q.beyond) {
       // the median lies above the histogram's 65 536 values (loaddata.cpp:233 takes it from the whole rescaled array): from the
       // array itself -- the rescaled int32 array the deep-coverage pass left, or the raw depth under -NOGC
       Phase ph_m(ctx, "a4.median on the host (depth > 65535)");
@@ -1224,21 +1084,17 @@ int per_base_phase(rsi_ctx* ctx, const rsi_params& P, const int32_t* d_depth, co
       std::vector<int32_t> all;
       const int rcf = fetch_i32(ctx, P.gcadjust ? ctx->rd_gc.as<int32_t>() : d_depth, n, all);
       if (rcf != RSI_OK) return rcf;
-      q.med = rank_value_i32(all, (uint64_t)n / 2);
+      q.med = rsih::rank_value_i32(all, (uint64_t)n / 2);
     }
     S.cap_median = q.med;
-    capval = (int32_t)(q.med * P.cap);   // RD[i] = RDmedian*cap, truncated (loaddata.cpp:238)
+    capval = rsih::cap_value(q.med, P.cap);
   }
 
   ph_cap.stop();
   Phase ph_bins(ctx, "a5-9.compact+bins+stats");
   // ---- A5-A9: cap + compaction + bins + statistics (K4) ----
-  std::vector<int64_t> cbreak(noncode.size()), cum(noncode.size() + 1, 0);
-  for (size_t k = 0; k < noncode.size(); ++k) {
-    cbreak[k] = (int64_t)noncode[k].start - cum[k];
-    cum[k + 1] = cum[k] + (noncode[k].end - noncode[k].start + 1);
-  }
-  const int64_t ncompact = n - cum.back();
+  const rsih::CompactTable ct = rsih::compact_table(noncode, n);
+  const int64_t ncompact = ct.ncompact;
   const int64_t nb = ncompact / P.m;
   S.n_compact = ncompact; S.nbins = nb;
   ctx->ncompact = ncompact; ctx->nb = nb;
@@ -1246,12 +1102,12 @@ int per_base_phase(rsi_ctx* ctx, const rsi_params& P, const int32_t* d_depth, co
   K4Regions inl;
   memset(&inl, 0, sizeof(inl));
   if ((int)noncode.size() <= kRegInline) {   // the usual case: the list rides with the kernel arguments
-    for (size_t k = 0; k < cbreak.size(); ++k) inl.brk[k] = cbreak[k];
-    for (size_t k = 0; k < cum.size(); ++k) inl.cum[k] = cum[k];
+    for (size_t k = 0; k < ct.cbreak.size(); ++k) inl.brk[k] = ct.cbreak[k];
+    for (size_t k = 0; k < ct.cum.size(); ++k) inl.cum[k] = ct.cum[k];
   } else {   // cbreak[4100] | cum: one upload
-    std::vector<int64_t> both((size_t)4100 + cum.size(), 0);
-    std::copy(cbreak.begin(), cbreak.end(), both.begin());
-    std::copy(cum.begin(), cum.end(), both.begin() + 4100);
+    std::vector<int64_t> both((size_t)4100 + ct.cum.size(), 0);
+    std::copy(ct.cbreak.begin(), ct.cbreak.end(), both.begin());
+    std::copy(ct.cum.begin(), ct.cum.end(), both.begin() + 4100);
     HIPCHK(copy_h2d(ctx, d_cbreak, both.data(), both.size() * 8));
   }
   HIPCHK(ctx->rdc.ensure((size_t)(ncompact + 4) * 4));
@@ -1326,33 +1182,19 @@ int per_base_phase(rsi_ctx* ctx, const rsi_params& P, const int32_t* d_depth, co
     std::vector<int32_t> rd;
     const int rcf = fetch_i32(ctx, ctx->rdc.as<int32_t>(), ncompact, rd);
     if (rcf != RSI_OK) return rcf;
-    S.RDsd = sqrt(rsih::variance_pop(rd.data(), (size_t)ncompact));   // the reference's own loop: double sums in index order (wufunctions.cpp:766-809)
-    const uint64_t sublen = (uint64_t)(ncompact / 31);
-    std::vector<int32_t> sub((size_t)sublen);
-    std::vector<int32_t> sorted = rd;
-    const double RDmed = rank_value_i32(sorted, (uint64_t)ncompact / 2);
-    for (int j = 0; j < 31 && sublen > 0; ++j) {
-      for (uint64_t k = 0; k < sublen; ++k) sub[(size_t)k] = (int)fabs((float)rd[(size_t)(j + 31 * k)] - RDmed);   // rsi.cpp:1134
-      pb.mads[j] = rank_value_i32(sub, sublen / 2);
-    }
+    rsih::ChromStats cs;
+    rsih::array_chrom_stats(rd, cs, pb.mads);
+    const double RDmed = cs.median;
+    S.RDsd = cs.sd;
     S.RDmedian = RDmed;
     pb.host_stats = true;
     pb.ncompact = ncompact; pb.nb = nb; pb.res_vals = 0; pb.RDmedian = RDmed;
     return RSI_OK;
   }
-  // chromosome median / SD (rsi.cpp:2202-2203)
-  std::vector<uint64_t> hall(res_vals, 0);
-  for (size_t v = 0; v < res_vals; ++v) for (int c = 0; c < kResClasses; ++c) hall[v] += hres[v * kResClasses + c];
-  rsih::Quantiles qall;
-  if (!int_quantiles(hall, (uint64_t)ncompact, qall)) return fail(ctx, RSI_ERR_INTERNAL, "empty depth histogram");
-  const double RDmedian = qall.med;
-  {   // variance(RD,...,-1), wufunctions.cpp:766-809: exact integer sums, one rounding each
-    unsigned __int128 s1 = 0, s2 = 0;
-    for (size_t v = 0; v < res_vals; ++v) { s1 += (unsigned __int128)v * hall[v]; s2 += (unsigned __int128)v * v * hall[v]; }
-    const double d1 = (double)s1, d2 = (double)s2;
-    const double mean = d1 / double((int)ncompact);
-    S.RDsd = sqrt(d2 / double((int)ncompact) - mean * mean);
-  }
+  rsih::ChromStats cs;   // chromosome median / SD (rsi.cpp:2202-2203)
+  if (!rsih::hist_chrom_stats(hres, res_vals, ncompact, cs)) return fail(ctx, RSI_ERR_INTERNAL, "empty depth histogram");
+  const double RDmedian = cs.median;
+  S.RDsd = cs.sd;
   S.RDmedian = RDmedian;
   pb.ncompact = ncompact; pb.nb = nb; pb.res_vals = res_vals; pb.RDmedian = RDmedian;
   pb.hres_all = std::move(hres_all);
@@ -1380,19 +1222,8 @@ int bin_level_stages(rsi_ctx* ctx, const rsi_params& P, int64_t n, rsi_result* r
     double mads[31];
     const uint64_t sublen = (uint64_t)(ncompact / 31);
     if (sublen == 0) return fail(ctx, RSI_ERR_TOO_SMALL, "fewer than 31 bases");
-    for (int j = 0; j < 31; ++j) {
-      if (pb.host_stats) { mads[j] = pb.mads[j]; continue; }
-      std::vector<uint64_t> hd(res_vals + 1, 0);
-      for (size_t v = 0; v < res_vals; ++v) {
-        const uint32_t c = hres[v * kResClasses + j];
-        if (!c) continue;
-        const int a = (int)fabs((float)(int)v - RDmedian);    // RDtmp[k]=abs((float)RD[i]-RDmedian), rsi.cpp:1134
-        hd[(size_t)a] += c;
-      }
-      rsih::Quantiles qd;
-      if (!int_quantiles(hd, sublen, qd)) return fail(ctx, RSI_ERR_INTERNAL, "empty MAD histogram");
-      mads[j] = qd.med;
-    }
+    if (pb.host_stats) std::copy(pb.mads, pb.mads + 31, mads);
+    else if (!rsih::hist_subsample_mads(hres, res_vals, RDmedian, sublen, mads)) return fail(ctx, RSI_ERR_INTERNAL, "empty MAD histogram");
     const double mad = rsih::grid_quantiles(mads, (size_t)31).med;
     const double r = RDmedian / mad;
     S.nb_mad = mad; S.nb_r = r;
@@ -1416,11 +1247,8 @@ int bin_level_stages(rsi_ctx* ctx, const rsi_params& P, int64_t n, rsi_result* r
     uint32_t* d_rawmin = reinterpret_cast<uint32_t*>(small + kOffRawMin);
     GridMedian* d_g = reinterpret_cast<GridMedian*>(small + kOffGrid);
     { Timer t(ctx, "nb_raw"); launch_nb_raw(ctx->binsum.as<int64_t>(), nb, P.m, ncompact, r, ctx->tnb.as<float>(), d_rawmin, st); }
-    auto nbf = [&](double sum) {
-      const double mm = (double)P.m;
-      return 2.0 * sqrt(r) * log(sqrt((sum + 0.25) / (mm * r - 0.5)) + sqrt(1.0 + (sum + 0.25) / (mm * r - 0.5)));
-    };
-    const double med_raw = nbf(RDmedian * P.m), del_raw = nbf(RDmedian / 2.0 * (double)P.m), dup_raw = nbf(RDmedian * 1.5 * (double)P.m);
+    const rsih::NbLevels lev = rsih::nb_reference_levels(RDmedian, P.m, r);
+    const double med_raw = lev.med_raw, del_raw = lev.del_raw, dup_raw = lev.dup_raw;
     { Timer t(ctx, "nb_scale"); launch_nb_scale_minmax(ctx->tnb.as<float>(), nb, d_rawmin, med_raw, del_raw, dup_raw, RDmedian, grid_chain(ctx), d_g, st); }
     bool nb_planned = true;   // d_g[0] holds the grid of the NB values' median, its buckets are clear
     ctx->have_nb = true;
@@ -1464,12 +1292,7 @@ int bin_level_stages(rsi_ctx* ctx, const rsi_params& P, int64_t n, rsi_result* r
       }
       rc2 = run_scan(ctx, P, use_med, d_T, nb, RDmedian, factor, LmaxBase, first, med_raw, del_raw, dup_raw, so);
       if (rc2 != RSI_OK) return rc2;
-      {
-        const uint32_t key = ~first->rawmin_inv;
-        float tminf;
-        { const uint32_t bb = (key & 0x80000000u) ? (key & 0x7fffffffu) : ~key; memcpy(&tminf, &bb, 4); }
-        S.nb_tmin = tminf;
-      }
+      S.nb_tmin = rsih::unkey_f32(~first->rawmin_inv);
       ctx->last_scan_med = use_med;
       S.tmedian1 = so.tmedian1; S.tsigma1 = so.tsigma1; S.tlamda1 = so.tlamda1;
       S.tmedian2 = so.tmedian2; S.tsigma2 = so.tsigma2; S.tlamda2 = so.tlamda2;
@@ -1992,7 +1815,8 @@ int rsi_hot_debug_scan(rsi_ctx* ctx, const float* T, const int32_t* medint, int6
   if (rc != RSI_OK) return rc;
   HIPCHK(hipMemcpyAsync(status, ctx->status1.p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(CTX_SYNC());
-  if (info) { info[0] = (int32_t)wslot[8]; info[1] = (int32_t)wslot[0]; info[2] = (int32_t)wslot[1]; info[3] = 0; }
+  const rsih::ScanRecord rec{wslot, Lmax};
+  if (info) { info[0] = (int32_t)rec.tiles_listed(); info[1] = (int32_t)rec.escapes(); info[2] = (int32_t)rec.inexact(); info[3] = 0; }
   return RSI_OK;
 }
 

@@ -391,7 +391,7 @@ constexpr size_t kOffNtrans = kHeaderBytes;                       // uint64[kMax
 constexpr size_t kOffTable = kOffNtrans + (size_t)kMaxTransitions * 8;   // double[202]
 constexpr size_t kOffGrid = kOffTable + 1792;                     // GridMedian[2]: the two links of a median -> MAD chain
 constexpr size_t kOffScanPass = kOffGrid + 1024;                  // 2 x ScanPassWork (one per rsistatus pass)
-constexpr size_t kScanPassBytes = kScanWorkBytes;                 // ScanPassOut, level histograms of the two sweeps (kernels.h)
+constexpr size_t kScanPassBytes = kScanWorkBytes;                 // the pass record (kScanRec*), level histograms of the two sweeps (kernels.h)
 constexpr size_t kOffBreaks = kOffScanPass + 2 * kScanPassBytes + 128;   // int64 cbreak[4100], cum[4097]
 constexpr size_t kSmallBytes = kOffBreaks + 2 * 4100 * 8;
 constexpr int kMaxRegions = 4096;

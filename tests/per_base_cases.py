@@ -243,6 +243,17 @@ def get_case(cid):
     return _CACHE[cid]
 
 
+def gc_wide_case():
+    """(fasta, depth, flags) for the rung of the per-base phase's redo ladder that no case above takes: the smallest GC-adjusted
+    chromosome (n4040_gc) with one depth of exactly 2^21, where the packed accumulators of the three-pass chain's K2 overflow and the
+    chain is issued again in its two-atomic form (RSI_HOT_JOINT=0: "a2-3.gc wide redo", gc_hist_wide), and one of 2^21 - 1 next to
+    the threshold.  Not one of the golden cases: it is compared with the oracle's per-base stages."""
+    _, fasta, depth, flags, _, _ = get_case("n4040_gc")
+    depth = depth.copy()
+    depth[1000], depth[3000] = 1 << 21, (1 << 21) - 1
+    return fasta, depth, flags
+
+
 def checker_inputs(case):
     """What the CPU checkers (oracle, reference) read for the case: excluded bases painted 'N' (they know no mask)."""
     _, fasta, depth, _, exclude, _ = case

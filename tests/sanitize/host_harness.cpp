@@ -4,6 +4,9 @@
 //   * host_calls.cpp's candidate stages (block tests, sharpening, neighbourhood tests, merge, final filters) on their
 //     host path -- the depth in host memory, no device tester -- from the oracle's bin arrays and segments, and compares
 //     blocks / raw calls / final calls with the oracle's,
+//   * pipeline_steps.h's host decisions between the pipeline's kernels (regions and compaction table, chromosome statistics, NB
+//     levels, scan parameters, filterstatus' level choice, segments) from the oracle's arrays of the same chromosomes against the
+//     oracle's results, and on hand-made edge inputs,
 //   * bam_host.cpp's BGZF / BAM / BAI reader and the read-pair annotation on a BAM given on the command line, then on
 //     truncated and bit-flipped copies of it (errors are fine, memory errors are not).
 // Exit status 0 = everything agreed and the sanitizers stayed quiet.
@@ -21,6 +24,7 @@
 #include "../../rsicnv_amd/csrc/bam_host.h"
 #include "../../rsicnv_amd/csrc/host_calls.h"
 #include "../../rsicnv_amd/csrc/hostmath.h"
+#include "../../rsicnv_amd/csrc/pipeline_steps.h"
 
 extern "C" {   // oracle/rsi_oracle.cpp
 struct orc_params { int32_t m, gcadjust, trans, merge, maxchkbp, debug; double cap, epsilon, threshold, chklen, minmlen, buffer, p; };
@@ -30,6 +34,7 @@ void orc_destroy(void* h);
 void orc_default_params(orc_params* p);
 int orc_run(void* h, const orc_params* p, const int32_t* depth, const uint8_t* fasta, int32_t n, int32_t keep_snapshots);
 int64_t orc_get_i32(void* h, const char* name, int32_t* out, int64_t cap);
+int64_t orc_get_f32(void* h, const char* name, float* out, int64_t cap);
 int64_t orc_get_f64(void* h, const char* name, double* out, int64_t cap);
 int orc_get_calls(void* h, const char* which, orc_call* out, int32_t cap);
 double orc_median_i32(const int32_t* x, int64_t n);
@@ -44,6 +49,12 @@ static std::vector<int32_t> geti(void* h, const char* name) {
   const int64_t k = orc_get_i32(h, name, nullptr, 0);
   std::vector<int32_t> v((size_t)(k > 0 ? k : 0));
   if (k > 0) orc_get_i32(h, name, v.data(), k);
+  return v;
+}
+static std::vector<float> getf(void* h, const char* name) {
+  const int64_t k = orc_get_f32(h, name, nullptr, 0);
+  std::vector<float> v((size_t)(k > 0 ? k : 0));
+  if (k > 0) orc_get_f32(h, name, v.data(), k);
   return v;
 }
 static std::vector<orc_call> getc(void* h, const char* which) {
@@ -83,6 +94,8 @@ static bool same_calls(const std::vector<rsih::Candidate>& a, const std::vector<
   }
   return true;
 }
+
+static void pipeline_step_checks(void* O, const orc_params& P, const std::vector<uint8_t>& fasta, uint64_t seed);   // below
 
 static void candidate_stage_case(uint64_t seed, int n, int model, const orc_params& P, int deep_bimodal = 0) {
   // a chromosome with N runs at the ends, one gap and a few events (layout as tests/conftest.py's plans)
@@ -133,7 +146,264 @@ static void candidate_stage_case(uint64_t seed, int n, int model, const orc_para
   same_calls(kept, getc(O, "calls"), "calls");
   CHECK(!raw.empty(), "the case should call something (seed %llu)", (unsigned long long)seed);
   if (deep_bimodal) CHECK(raw.size() > 100, "the bimodal case should be crowded (%zu raw calls)", raw.size());
+  pipeline_step_checks(O, P, fasta, seed);
   orc_destroy(O);
+}
+
+// ---- the pipeline's host decisions (pipeline_steps.h) -------------------------------------------------------------------------------
+// Run boundaries (pos << 1 | is_end) of a status array as k_resolve_runs emits them (a run: adjacent marked bins of one sign),
+// shuffled: the device appends them unordered.  Then the runs in the reference's sense (the last one is not emitted, Q11).
+static std::vector<rsih::Region> marked_runs(const std::vector<int32_t>& st, std::mt19937_64& rng) {
+  std::vector<uint64_t> ent;
+  const int64_t nb = (int64_t)st.size();
+  for (int64_t i = 0; i < nb; ++i) {
+    const int s = st[(size_t)i];
+    if (s == 0) continue;
+    const int p = i > 0 ? st[(size_t)i - 1] : 0, q = i + 1 < nb ? st[(size_t)i + 1] : 0;
+    if (p == 0 || ((p > 0) != (s > 0))) ent.push_back((uint64_t)i << 1);
+    if (q == 0 || ((q > 0) != (s > 0))) ent.push_back(((uint64_t)i << 1) | 1);
+  }
+  std::shuffle(ent.begin(), ent.end(), rng);
+  std::vector<rsih::Region> runs;
+  CHECK(rsih::boundary_pairs(ent.data(), ent.size(), false, runs), "run boundaries of a status array are balanced");
+  if (!runs.empty()) runs.pop_back();
+  return runs;
+}
+
+static void pipeline_step_checks(void* O, const orc_params& P, const std::vector<uint8_t>& fasta, uint64_t seed) {
+  const int n = (int)fasta.size();
+  const bool med = P.trans == 1;
+  const char* pre = med ? "med" : "nb";
+  auto name = [&](const char* what) { return std::string(pre) + what; };
+  std::mt19937_64 rng(seed);
+  const std::vector<int32_t> rdc = geti(O, "rd_concat"), noncode = geti(O, "noncode");
+  double chrom[4], nbv[6], sc[11];
+  orc_get_f64(O, "chrom", chrom, 4);
+  orc_get_f64(O, "nb", nbv, 6);                                   // median, MAD, r, raw minimum, factor, LmaxBase
+  CHECK(orc_get_f64(O, med ? "scan_med" : "scan_nb", sc, 11) == 11, "the oracle's scan record has 11 entries");   // ..., [6] target, [7] Lmax, [8] cal_max, [10] absmed
+
+  // regions and compaction table: the N runs of the FASTA by a plain loop
+  std::vector<uint64_t> ent;
+  for (int i = 0; i < n; ++i) {
+    if (fasta[(size_t)i] != 'N') continue;
+    if (i == 0 || fasta[(size_t)i - 1] != 'N') ent.push_back((uint64_t)i << 1);
+    if (i == n - 1 || fasta[(size_t)i + 1] != 'N') ent.push_back(((uint64_t)(i + 1) << 1) | 1);   // exclusive end
+  }
+  std::shuffle(ent.begin(), ent.end(), rng);
+  std::vector<rsih::Region> nruns;
+  CHECK(rsih::boundary_pairs(ent.data(), ent.size(), true, nruns), "N-run boundaries are balanced");
+  const std::vector<rsih::Region> regs = rsih::noncode_regions(nruns, n, std::max(50, P.m / 4));
+  bool same = regs.size() * 2 == noncode.size();
+  for (size_t k = 0; same && k < regs.size(); ++k) same = regs[k].start == noncode[2 * k] && regs[k].end == noncode[2 * k + 1];
+  CHECK(same, "noncode_regions: %zu regions, oracle %zu, or a pair differs", regs.size(), noncode.size() / 2);
+  const rsih::CompactTable ct = rsih::compact_table(regs, n);
+  CHECK(ct.ncompact == (int64_t)rdc.size(), "compact_table: n' %lld, oracle %zu", (long long)ct.ncompact, rdc.size());
+
+  // chromosome statistics from the residue-class histogram ([value][32], kernels.h: class = index mod 31 below 31 * (n' / 31),
+  // class 31 for the tail) and from the array itself
+  const int64_t nc = (int64_t)rdc.size(), body = 31 * (nc / 31);
+  const size_t res_vals = (size_t)*std::max_element(rdc.begin(), rdc.end()) + 1;
+  std::vector<uint32_t> hres(res_vals * rsik::kResClasses, 0);
+  for (int64_t i = 0; i < nc; ++i) ++hres[(size_t)rdc[(size_t)i] * rsik::kResClasses + (size_t)(i < body ? i % 31 : 31)];
+  auto sd_close = [&](double sd) { return fabs(sd - chrom[1]) <= 1e-12 * fabs(chrom[1]); };
+  rsih::ChromStats hs, as;
+  double hmads[31] = {0}, amads[31] = {0};
+  CHECK(rsih::hist_chrom_stats(hres.data(), res_vals, nc, hs) && hs.median == chrom[0], "histogram median %g, oracle %g", hs.median, chrom[0]);
+  CHECK(sd_close(hs.sd), "histogram SD %.17g, oracle %.17g", hs.sd, chrom[1]);
+  CHECK(rsih::hist_subsample_mads(hres.data(), res_vals, chrom[0], (uint64_t)(nc / 31), hmads) && rsih::grid_quantiles(hmads, (size_t)31).med == nbv[1],
+        "histogram MAD, oracle %g", nbv[1]);
+  rsih::array_chrom_stats(rdc, as, amads);
+  CHECK(as.median == chrom[0] && sd_close(as.sd) && rsih::grid_quantiles(amads, (size_t)31).med == nbv[1],
+        "array statistics: median %g SD %.17g, oracle %g %.17g MAD %g", as.median, as.sd, chrom[0], chrom[1], nbv[1]);
+  for (int j = 0; j < 31; ++j) CHECK(hmads[j] == amads[j], "subsample %d: MAD %g from the histogram, %g from the array", j, hmads[j], amads[j]);
+
+  // NB reference levels: bins 0 and 2 of the transformed array carry the scaled DEL and median levels (App. A Q9)
+  const std::vector<float> binnb = getf(O, "binnb");
+  const rsih::NbLevels lev = rsih::nb_reference_levels(nbv[0], P.m, nbv[2]);
+  const rsih::NbScaled lv = rsih::nb_scaled_levels(nbv[3], lev.med_raw, lev.del_raw, nbv[0]);
+  CHECK(lv.t0 == binnb[0] && lv.t2 == binnb[2], "NB levels %.9g %.9g, oracle %.9g %.9g", lv.t0, lv.t2, binnb[0], binnb[2]);
+
+  // scan parameters
+  const std::vector<float> T = med ? getf(O, "binmed") : binnb;
+  const int64_t nb = (int64_t)T.size();
+  const rsih::ScanSetup su = rsih::scan_first_pass(med, sc[0], sc[10], nbv[4], (int)nbv[5], T[0], T[2], P.threshold, nb);
+  CHECK(su.tsigma == sc[1] && su.tlamda == sc[2] && su.target == sc[6] && su.cal_max == (int)sc[8] && su.Lmax_ref == (int)sc[7],
+        "scan parameters: tsigma %.17g tlamda %.17g target %.17g cal_max %d Lmax %d, oracle %.17g %.17g %.17g %d %d", su.tsigma, su.tlamda,
+        su.target, su.cal_max, su.Lmax_ref, sc[1], sc[2], sc[6], (int)sc[8], (int)sc[7]);
+  CHECK(!su.clipped && su.Lmax == su.Lmax_ref, "a synthetic chromosome has more bins than scan lengths");
+
+  // filterstatus: the host loop and the level choice against rsi.cpp:948-1002 restated over the same arrays
+  const std::vector<int32_t> st1 = geti(O, name("_status1").c_str()), st1f = geti(O, name("_status1f").c_str());
+  const int Lmax = su.Lmax;
+  std::vector<float> wsum((size_t)(2 * Lmax + 1), 1.0f);
+  std::vector<int> wcnt((size_t)(2 * Lmax + 1), 1);
+  rsih::level_sums_host(T.data(), st1.data(), nb, Lmax, wsum, wcnt);
+  const rsih::LevelChoice lc = rsih::choose_levels(wsum, wcnt, Lmax, su.dev);
+  int minl = st1[0], maxl = st1[0];
+  for (int32_t v : st1) { minl = std::min(minl, v); maxl = std::max(maxl, v); }
+  const int nl = maxl - minl + 1;
+  std::vector<float> lsum((size_t)nl, 0.0f);
+  std::vector<int> lcnt((size_t)nl, 0);
+  for (int64_t i = 0; i < nb; ++i) { lsum[(size_t)(st1[(size_t)i] - minl)] += T[(size_t)i]; ++lcnt[(size_t)(st1[(size_t)i] - minl)]; }   // float accumulators
+  for (int l = 0; l < nl; ++l) if (lcnt[(size_t)l] != 0) lsum[(size_t)l] /= (double)lcnt[(size_t)l];
+  const bool level0 = !(-minl < 0 || -minl >= nl);
+  CHECK(lc.lo == minl && lc.hi == maxl && lc.has_level0 == level0, "level range [%d, %d], restated [%d, %d]", lc.lo, lc.hi, minl, maxl);
+  std::vector<int32_t> trimmed = st1;
+  if (level0 && lc.has_level0) {
+    const float m0 = lsum[(size_t)-minl];
+    int leveldel = minl, leveladd = maxl;
+    for (int l = 0; l < nl; ++l) if (lsum[(size_t)l] < m0 - su.dev) { leveldel = l + minl; break; }
+    for (int l = nl - 1; l >= 0; --l) if (lsum[(size_t)l] > m0 + su.dev) { leveladd = l + minl; break; }
+    const bool trim = !(leveldel > 0 || leveladd < 0 || leveldel > leveladd);
+    CHECK(lc.m0 == m0 && lc.leveldel == leveldel && lc.leveladd == leveladd && lc.trim == trim,
+          "level choice m0 %.9g del %d add %d trim %d, restated %.9g %d %d %d", lc.m0, lc.leveldel, lc.leveladd, (int)lc.trim, m0, leveldel, leveladd, (int)trim);
+    size_t populated = 0;
+    for (int c : lcnt) populated += c != 0;
+    CHECK(lc.lines.size() == populated + 2 + (trim ? 0 : 1), "level table: %zu lines for %zu populated levels", lc.lines.size(), populated);
+    if (lc.trim) {   // k_trim_runs' rule (rsi.cpp:1023-1044) in plain C++, over the runs as the pipeline gets them
+      const double delthr = (double)lc.m0 - su.dev, addthr = (double)lc.m0 + su.dev;
+      for (const rsih::Region& r : marked_runs(st1, rng)) {
+        int i1 = r.start, i2 = r.end;
+        auto within = [&](int i) { return (T[(size_t)i] > delthr && trimmed[(size_t)i] < 0) || (T[(size_t)i] < addthr && trimmed[(size_t)i] > 0); };
+        while (within(i1)) { trimmed[(size_t)i1] = 0; ++i1; if (i1 >= i2) break; }
+        while (within(i2)) { trimmed[(size_t)i2] = 0; --i2; if (i2 <= i1) break; }
+      }
+    }
+  }
+  CHECK(trimmed == st1f, "status after the level choice and the trim differs from the oracle's %s_status1f", pre);
+
+  // segments: runs of the second pass' status, the item plan, a plain best subsegment per item (the kernel's visiting order:
+  // larger score, then smaller L, then smaller offset), one candidate per run
+  const std::vector<int32_t> st2 = geti(O, name("_status2").c_str());
+  const std::vector<rsih::Region> runs = marked_runs(st2, rng);
+  const double tmedian2 = sc[3], tlamda2 = sc[5];
+  std::vector<int64_t> poff;
+  std::vector<rsik::SegItem> items;
+  rsih::segment_items(runs, (int64_t)1 << 13, poff, items);
+  CHECK(poff.size() == runs.size() + 1 && (runs.empty() || !items.empty()), "item plan: offsets and items");
+  std::vector<rsik::BestSeg> best(items.size(), rsik::BestSeg{0.0, 0, 0});
+  std::vector<double> prefix;
+  for (size_t i = 0; i < items.size(); ++i) {
+    const rsik::SegItem& it = items[i];
+    const rsih::Region& r = runs[(size_t)it.run];
+    CHECK(it.len == r.end - r.start + 1 && it.Lbeg >= 1 && it.Lbeg < it.Lend && it.Lend <= it.len + 1 &&
+          (i == 0 || items[i - 1].run != it.run ? it.Lbeg == 1 : it.Lbeg == items[i - 1].Lend), "item %zu does not continue its run's lengths", i);
+    if (it.Lbeg == 1) {
+      prefix.assign((size_t)it.len + 1, 0.0);
+      for (int e = 0; e < it.len; ++e) prefix[(size_t)e + 1] = prefix[(size_t)e] + (double)T[(size_t)(r.start + e)];
+    }
+    for (int L = it.Lbeg; L < it.Lend; ++L)
+      for (int off = 0; off + L <= it.len; ++off) {
+        const double score = fabs((prefix[(size_t)(off + L)] - prefix[(size_t)off]) / (double)L - tmedian2) * sqrt((double)L);
+        if (score > best[i].score) best[i] = rsik::BestSeg{score, off, L};
+      }
+  }
+  for (size_t r = 0; r < runs.size(); ++r) {
+    bool closed = false;
+    for (const rsik::SegItem& it : items) closed = closed || (it.run == (int32_t)r && it.Lend == it.len + 1);
+    CHECK(closed, "run %zu: no item reaches its full length", r);
+  }
+  const std::vector<int> s2(st2.begin(), st2.end());
+  std::vector<rsih::Candidate> segs;
+  rsih::segments_from_best(runs, items, best.data(), rsih::IntSpan(s2), tlamda2, segs);
+  const std::vector<orc_call> segs_o = getc(O, name("").insert(0, "segs_").c_str());
+  if (same_calls(segs, segs_o, "segments"))
+    for (size_t i = 0; i < segs.size(); ++i)
+      CHECK(fabs(segs[i].score - segs_o[i].score) <= 1e-9 * fabs(segs_o[i].score), "segment %zu: score %.17g, oracle %.17g", i, segs[i].score, segs_o[i].score);
+  printf("pipeline steps (%s): %zu regions, n' %lld, Lmax %d, level choice %d..%d trim %d, %zu runs in %zu items -> %zu segments\n", pre, regs.size(),
+         (long long)ct.ncompact, su.Lmax, lc.leveldel, lc.leveladd, (int)lc.trim, runs.size(), items.size(), segs.size());
+}
+
+// kernels_bin.hip's encoder of the order-preserving key, restated
+static uint32_t f32_key(float f) { uint32_t b; memcpy(&b, &f, 4); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
+
+// Hand-made inputs for what a synthetic chromosome does not reach.
+static void pipeline_step_edges() {
+  using rsih::Region;
+  {   // boundary lists
+    std::vector<Region> out = {{1, 2}};
+    CHECK(rsih::boundary_pairs(nullptr, 0, true, out) && out.empty(), "empty boundary list");
+    const uint64_t one[2] = {(9u << 1) | 1, 5u << 1};
+    CHECK(rsih::boundary_pairs(one, 2, true, out) && out.size() == 1 && out[0].start == 5 && out[0].end == 8, "one run, exclusive end");
+    CHECK(rsih::boundary_pairs(one, 2, false, out) && out.size() == 1 && out[0].start == 5 && out[0].end == 9, "one run, inclusive end");
+    const uint64_t odd[3] = {5u << 1, (9u << 1) | 1, 20u << 1};
+    CHECK(!rsih::boundary_pairs(odd, 3, true, out), "unbalanced boundary list");
+  }
+  {   // region merge: padded by 50, [100, 110] ends at 160
+    auto regions = [](std::vector<Region> runs) { return rsih::noncode_regions(runs, 1000, 50); };
+    std::vector<Region> r = regions({{100, 110}, {211, 220}});   // 211 - 50 == 160 + 1: touch
+    CHECK(r.size() == 1 && r[0].start == 50 && r[0].end == 270, "padded regions that touch merge");
+    r = regions({{100, 110}, {212, 220}});                       // one base between them
+    CHECK(r.size() == 2 && r[0].end == 160 && r[1].start == 162, "padded regions one base apart stay two");
+    r = regions({{0, 3}, {990, 999}});
+    CHECK(r.size() == 2 && r[0].start == 0 && r[0].end == 53 && r[1].start == 940 && r[1].end == 999, "runs at base 0 and up to n - 1 are clamped");
+    const rsih::CompactTable t = rsih::compact_table(r, 1000);
+    CHECK(t.ncompact == 1000 - 54 - 60 && t.cbreak[0] == 0 && t.cbreak[1] == 940 - 54 && t.cum.back() == 114, "compaction table of two regions");
+    const rsih::CompactTable none = rsih::compact_table({}, 1000);
+    CHECK(none.ncompact == 1000 && none.cbreak.empty() && none.cum.size() == 1 && none.cum[0] == 0, "compaction table without regions");
+    CHECK(rsih::compact_table(regions({{0, 999}}), 1000).ncompact == 0, "a chromosome of N only compacts to nothing");
+  }
+  {   // cap
+    rsik::ValueMedian vm{1000, 3, 90, 30, 0};
+    CHECK(rsih::cap_median(vm, 1000).med == 30.0 && !rsih::cap_median(vm, 1000).beyond, "cap median from the device's walk");
+    vm.hi = 3;
+    CHECK(rsih::cap_median(vm, 1000).med == 3.0, "one value only: the minimum");
+    vm.inrange = 499;
+    CHECK(rsih::cap_median(vm, 1000).beyond && !rsih::cap_median(vm, 999).beyond, "the median lies beyond the histogram");
+    CHECK(rsih::cap_value(30.0, 4.0) == 120 && rsih::cap_value(30.0, 63.5 / 30) == 63, "cap value, truncated");
+  }
+  {   // order key
+    std::mt19937_64 rng(11);
+    std::vector<float> xs = {0.0f, -0.0f, 1.4e-45f, -1.4e-45f, 1.1e-38f, -1.1e-38f, 3.402823466e38f, -3.402823466e38f, 1.0f, -1.0f};
+    for (int k = 0; k < 1000; ++k) { uint32_t b = (uint32_t)rng(); if ((b & 0x7f800000u) == 0x7f800000u) b &= ~0x00800000u; float f; memcpy(&f, &b, 4); xs.push_back(f); }
+    for (float x : xs) {
+      const float y = rsih::unkey_f32(f32_key(x));
+      CHECK(memcmp(&x, &y, 4) == 0, "order key does not give %.9g back", x);
+    }
+    for (size_t i = 0; i + 1 < xs.size(); ++i) if (xs[i] < xs[i + 1]) CHECK(f32_key(xs[i]) < f32_key(xs[i + 1]), "order key does not keep the order of %.9g and %.9g", xs[i], xs[i + 1]);
+  }
+  {   // level choice
+    std::vector<float> wsum(7, 0.0f);
+    std::vector<int> wcnt(7, 0);
+    wsum[3] = 50.0f; wcnt[3] = 10;   // Lmax 3: only level 0
+    rsih::LevelChoice c = rsih::choose_levels(wsum, wcnt, 3, 3.0);
+    CHECK(c.has_level0 && c.lo == 0 && c.hi == 0 && c.m0 == 5.0f && c.leveldel == 0 && c.leveladd == 0 && c.trim && c.lines.size() == 3 &&
+          c.lines[0] == "0\t10\t5" && c.lines[1] == "0\t5", "only level 0 populated");
+    wsum[3] = 100.0f; wsum[4] = 8.0f; wcnt[4] = 4;   // level +1 lies BELOW level 0: the DEL level comes out positive
+    c = rsih::choose_levels(wsum, wcnt, 3, 3.0);
+    CHECK(c.has_level0 && c.leveldel == 1 && !c.trim && c.lines.back() == "warning level error, status not filtered", "level error");
+    wsum[3] = 0.0f; wcnt[3] = 0;   // no unmarked bin
+    CHECK(!rsih::choose_levels(wsum, wcnt, 3, 3.0).has_level0, "no level 0");
+  }
+  {   // scan parameters
+    rsih::ScanSetup s = rsih::scan_first_pass(false, 20.0, 0.6745, 5.0, 99, 10.0f, 20.0f, -1.0, 1000);
+    CHECK(s.tsigma == 1.0 && s.target == 10.0 * sqrt(2.5) && s.tlamda == s.target && s.cal_max == 9 && s.Lmax_ref == 99 && s.Lmax == 99 && !s.clipped && s.dev == 3.0,
+          "cal_max below LmaxBase: tlamda %.17g cal_max %d Lmax %d", s.tlamda, s.cal_max, s.Lmax);
+    s = rsih::scan_first_pass(false, 20.0, 0.6745, 5.0, 99, 10.0f, 20.0f, -1.0, 50);
+    CHECK(s.clipped && s.Lmax == 50 && s.Lmax_ref == 99, "more lengths than bins");
+    s = rsih::scan_first_pass(true, 30.0, 2.0, 6.6, 20, 0.0f, 0.0f, 0.5, 1000);
+    CHECK(s.tlamda == 30.0 * 0.5 && s.target == 30.0 * sqrt(2.0) && s.tsigma == 2.0 / 0.6745 && s.cal_max == 3 && s.Lmax == 20 && s.dev == 30.0 * 0.6, "-threshold in the median branch");
+    s = rsih::scan_first_pass(true, 30.0, 2.0, 6.6, 20, 0.0f, 0.0f, -1.0, 1000);
+    const rsih::Lamda l = rsih::lamda_from_mad(2.0, 6.6, 30.0 * sqrt(2.0));
+    CHECK(s.tlamda == l.tlamda && s.tsigma == l.tsigma && l.tlamda == 30.0 * sqrt(2.0), "the second pass' update is the first pass' rule");
+  }
+  {   // scan record: 100 bins, the 20 % rule by one bin
+    const int Lmax = 4, stride = rsik::scan_level_stride(Lmax);
+    std::vector<uint32_t> w((size_t)(rsik::kScanRecLevels + 2 * stride), 0u);
+    w[rsik::kScanRecEscapes] = 7; w[rsik::kScanRecInexact] = 1; w[rsik::kScanRecStop] = 2; w[rsik::kScanRecStop + 1] = 3; w[rsik::kScanRecTiles] = 5;
+    uint32_t* del = w.data() + rsik::kScanRecLevels;
+    uint32_t* dup = del + stride;
+    del[1] = 10; del[2] = 11; del[3] = 50;   // [3] lies behind the stop level
+    dup[1] = 7; dup[2] = 7; dup[3] = 7;
+    const rsih::ScanRecord rec{w.data(), Lmax};
+    CHECK(rec.escapes() == 7 && rec.inexact() == 1 && rec.stop_level(0) == 2 && rec.stop_level(1) == 3 && rec.tiles_listed() == 5 &&
+          rec.level_counts(0) == del && rec.level_counts(1) == dup, "scan record fields");
+    CHECK(rec.sweeps_stopped(100), "21 of 100 bins marked in both sweeps");
+    del[2] = 10;
+    CHECK(!rec.sweeps_stopped(100), "20 of 100 bins is not more than 20 %%");
+    del[2] = 11; dup[3] = 6;
+    CHECK(!rec.sweeps_stopped(100), "the DUP sweep one bin short");
+  }
 }
 
 static void bam_checks(const char* path) {
@@ -228,6 +498,7 @@ int main(int argc, char** argv) {
   quantile_checks();
   span_checks();
   narrow_checks();
+  pipeline_step_edges();
   orc_params P;
   orc_default_params(&P);
   candidate_stage_case(0x5A11, 400007, 0, P);

@@ -1,7 +1,8 @@
 """CPU: the cases of tests/per_base_cases.py are what golden/per_base_edges.npz was made from, the oracle reproduces the reference's
 answers on every one of them (nothing else pins oracle/rsi_oracle.cpp at chromosomes of 4040 bases, eight bins or a cap of 63), and
 every case lands on the route, form and residue it was built for -- recomputed here from the ORACLE's cap median, n' and regions
-with the kernels' thresholds restated as constants, so that a changed seed which moves a case off its edge fails here."""
+with the kernels' thresholds restated as constants, so that a changed seed which moves a case off its edge fails here.
+GPU (the one test marked so): per_base_cases.gc_wide_case(), the redo rung a depth of 2^21 takes, against the oracle."""
 import numpy as np
 import pytest
 
@@ -212,3 +213,35 @@ def test_escape_values_sit_at_the_cut_and_on_the_last_base(cid):
     (a, b), = pc.merged_regions(depth.size, [(8000, 100)], flags["m"])
     assert sorted(depth[a - 3:a]) == [254, 255, 256] == sorted(depth[b + 1:b + 4]) == sorted(depth[-3:])
     assert (fasta[a - 3:a] != ord("N")).all() and depth[-1] == 255
+
+
+@pytest.mark.gpu
+def test_gc_wide_redo_against_the_oracle(oracle_cls):
+    """GPU: a depth of 2^21 under RSI_HOT_JOINT=0 sends the three-pass chain round again with the two-atomic K2 (pipeline.hip, per_base_phase:
+    "a2-3.gc wide redo"); per-base arrays, bin medians and the chromosome's scalars as the oracle's per-base stages give them (RDsd: rel
+    1e-12, the bar of tests/test_per_base_edges.py and tests/test_fallback_paths.py for the same number)."""
+    import os
+    import oracle
+    from rsicnv_amd import api
+    fasta, depth, flags = pc.gc_wide_case()
+    assert depth.size == K_MIN_N and (depth == 1 << 21).sum() == 1 and (depth == (1 << 21) - 1).sum() == 1 and depth.max() == 1 << 21
+    O = oracle_cls()
+    O.run_per_base(oracle.make_params(**flags), depth, fasta)
+    ch = O.f64("chrom")
+    hot = api.RsiHot(0)
+    hot.set_timing(1)
+    os.environ["RSI_HOT_JOINT"] = "0"
+    try:
+        st = hot.debug_per_base(api.make_params(**flags), depth, fasta)
+        phases, kernels = dict(hot.phase_times()), [k for k, _ in hot.kernel_times()]
+        got = {name: hot.fetch(name) for name in ("rd_gc", "rd_concat", "binmedint")}
+    finally:
+        del os.environ["RSI_HOT_JOINT"]
+        hot.close()
+    print(f"phases {sorted(phases)} kernels {kernels} RDmedian {st['RDmedian']} RDsd {st['RDsd']!r} / {ch[1]!r} cap median {st['cap_median']} rdmean {st['gc_rdmean']!r}")
+    assert "a2-3.gc wide redo" in phases and "gc_hist_wide" in kernels and "gc_joint_hist" not in kernels, (phases, kernels)
+    for name in ("rd_gc", "rd_concat", "binmedint"):
+        assert np.array_equal(got[name], O.i32(name)), name
+    assert (st["RDmedian"], st["cap_median"], st["gc_rdmean"]) == (ch[0], ch[2], ch[3])
+    assert st["RDsd"] == pytest.approx(ch[1], rel=1e-12)
+    assert st["byte_escapes"] == 2

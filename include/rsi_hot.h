@@ -323,6 +323,25 @@ int rsi_hot_write_track_device(rsi_ctx* ctx, const void* d_values, int64_t n, co
 int64_t rsi_hot_debug_track(rsi_ctx* ctx, const int32_t* values, int64_t n, const char* chrom, int64_t pos0, int64_t slice_bases,
                             char* out, int64_t cap, rsi_track_stats* stats);
 
+/* ---- Per-bin tracks: the signal the caller worked on, one value per bin ----------------------------------------
+ * After a run the context holds nb bins of m compacted bases, their exact medians, the removed regions and the chromosome's
+ * median.  Bin b covers the compacted positions [b m, (b + 1) m), mapped back to the reference through the removed regions; it
+ * is written as one line "NAME<TAB>start<TAB>end<TAB>value" (0-based half-open, %lld) per maximal stretch of consecutive reference
+ * positions: cut where a removed region lies strictly inside it, never covering a removed base.  Lines come in increasing
+ * order and do not overlap; equal neighbours are not merged; the ncompact mod m bases behind the last bin get no line.
+ * which: 0 = the bin's median as %d; 1 = the median over the chromosome's median with three decimals, rounded half up in
+ * integers: q = (4000 v + M2) / (2 M2) with M2 = twice the chromosome's median, written as q / 1000 "." q % 1000.
+ * stats.n is the number of bins.  RSI_ERR_BAD_ARG: a context that has run nothing or whose last run failed (or whose bins a
+ * test hook has overwritten since), a bad name (as above), which outside 0 and 1, a chromosome median of 0 with which = 1. */
+int rsi_hot_write_bin_track(rsi_ctx* ctx, int which, const char* chrom, const char* path, int append, rsi_track_stats* stats);
+/* Test hook: host values[nb] and regions (npairs inclusive pairs, sorted, apart by at least one kept base) of a chromosome of n
+ * bases, bins of m compacted bases, median2 = twice the chromosome's median; slice_bins > 0 forces that slice length.  The
+ * values go into the context's bin-median buffer.  RSI_ERR_BAD_ARG also for regions that are unsorted, touching or outside
+ * [0, n), and for nb m above the kept bases.  Returns the text length as rsi_hot_debug_track does. */
+int64_t rsi_hot_debug_bin_track(rsi_ctx* ctx, const int32_t* values, int64_t nb, int m, int64_t n, const int32_t* pairs, int npairs,
+                                int64_t median2, int which, const char* chrom, int64_t slice_bins, char* out, int64_t cap,
+                                rsi_track_stats* stats);
+
 /* Results.  which: 0 = calls after sd_filters (what write_cnv_to_file prints),
  *                  1 = detectcnv output before sd_filters,
  *                  2 = bin-space segments after the scan (rsicnvnbn / rsicnvmed output),

@@ -62,7 +62,8 @@ EXPORTS = ["rsi_default_params", "rsi_hot_create", "rsi_hot_destroy", "rsi_hot_l
            "rsi_genome_text_sample_depth", "rsi_genome_text_copy_sample_depth", "rsi_synth_append_genome_samples",
            "rsi_genome_bedgraph_open", "rsi_synth_append_genome_bedgraph",
            "rsi_hot_set_exclude", "rsi_exclude_read_bed", "rsi_hot_debug_classify", "rsi_hot_debug_per_base",
-           "rsi_hot_write_track", "rsi_hot_write_track_device", "rsi_hot_debug_track"]
+           "rsi_hot_write_track", "rsi_hot_write_track_device", "rsi_hot_debug_track",
+           "rsi_hot_write_bin_track", "rsi_hot_debug_bin_track"]
 
 
 class RsiParams(C.Structure):
@@ -255,6 +256,10 @@ def load_library():
     L.rsi_hot_debug_track.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_char_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
                                       C.POINTER(RsiTrackStats)]
     L.rsi_hot_debug_track.restype = C.c_int64
+    L.rsi_hot_write_bin_track.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(RsiTrackStats)]
+    L.rsi_hot_debug_bin_track.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_int,
+                                          C.c_char_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(RsiTrackStats)]
+    L.rsi_hot_debug_bin_track.restype = C.c_int64
     _lib = L
     return L
 
@@ -640,6 +645,36 @@ class RsiHot:
             if k <= cap:
                 break
             cap = int(k)
+        return out[:k].tobytes(), {f[0]: getattr(st, f[0]) for f in RsiTrackStats._fields_}
+
+    BIN_TRACK_VALUES = {"median": 0, "ratio": 1}
+
+    def write_bin_track(self, which, chrom, path, append=False):
+        """The last run's bins as bedGraph lines of `chrom` (rsi_hot_write_bin_track), replacing `path` or appended to it.
+        which: 0 / "median" = every bin's median, 1 / "ratio" = the median over the chromosome's median, three decimals.
+        Returns the statistics (RsiTrackStats, n = the number of bins) as a dict."""
+        st = RsiTrackStats()
+        w = self.BIN_TRACK_VALUES.get(which, which)
+        self._check(self.lib.rsi_hot_write_bin_track(self.ctx, int(w), self._name_bytes(chrom), os.fsencode(path), int(bool(append)), C.byref(st)))
+        return {f[0]: getattr(st, f[0]) for f in RsiTrackStats._fields_}
+
+    def debug_bin_track(self, values, m, n, pairs, median2, which, name, slice_bins=0):
+        """The bin track of host values[nb] (bins of m compacted bases of a chromosome of n bases whose removed regions are the
+        inclusive (start, end) `pairs`) through the device's writer (test hook, rsi_hot_debug_bin_track): (bytes, stats)."""
+        v = np.ascontiguousarray(values, dtype=np.int32)
+        pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1)
+        nm = self._name_bytes(name)
+        w = self.BIN_TRACK_VALUES.get(which, which)
+        cap = (v.size + pr.size // 2) * (len(nm) + 4 + 2 * 20 + 18)   # room for every piece at its longest
+        st = RsiTrackStats()
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        k = self.lib.rsi_hot_debug_bin_track(self.ctx, v.ctypes.data if v.size else None, v.size, int(m), int(n),
+                                             pr.ctypes.data if pr.size else None, pr.size // 2, int(median2), int(w), nm, int(slice_bins),
+                                             out.ctypes.data, cap, C.byref(st))
+        if k < 0:
+            self._check(int(k))
+        if k > cap:
+            raise RsiError(-6, "bin track: more text than its pieces can take")
         return out[:k].tobytes(), {f[0]: getattr(st, f[0]) for f in RsiTrackStats._fields_}
 
     def phase_times(self):

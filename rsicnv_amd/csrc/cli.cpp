@@ -9,6 +9,8 @@
 // DEPTH: mosdepth, bedtools genomecov -bg / -bga) runs as the per-base file it stands for, whole or one chromosome (-c).
 // -track FILE saves the depth every chromosome was called from (raw, or GC-adjusted with -trackdepth gc) as one bedGraph file,
 // written by the device (rsi_hot_write_track) chromosome by chromosome into part files that are joined in row order at the end.
+// -bintrack FILE saves the signal the calls are made from, one value per bin (its median, or with -bintrackvalue ratio its ratio
+// to the chromosome's median), the same way (rsi_hot_write_bin_track).
 #include <fcntl.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -52,6 +54,8 @@ struct Options {
   std::string excludefile;   // -x FILE: BED file of regions left out of calling, treated as N of the reference
   std::string trackfile;     // -track FILE: the depth of every called chromosome as bedGraph (with -samples: FILE.k per column k)
   std::string trackdepth = "raw";   // -trackdepth raw|gc: the depth as read, or after the GC adjustment
+  std::string bintrackfile;  // -bintrack FILE: one value per bin of every called chromosome as bedGraph (with -samples: FILE.k per column k)
+  std::string bintrackvalue = "ratio";   // -bintrackvalue ratio|median: the bin's median over the chromosome's, or the median itself
 };
 
 int usage() {
@@ -78,6 +82,8 @@ int usage() {
             << "   -x   FILE exclude the regions of a BED file (plain or gzip) from calling, see below\n"
             << "   -track FILE  save the depth of every called chromosome as bedGraph (bedtools genomecov -bga), see below\n"
             << "   -trackdepth raw|gc  the depth -track saves: as read (default), or GC-adjusted (what the calls are made from)\n"
+            << "   -bintrack FILE  save one value per bin of every called chromosome as bedGraph, see below\n"
+            << "   -bintrackvalue ratio|median  the value -bintrack saves: the bin's median over the chromosome's (default), or the median\n"
             << "\nNote:\n"
             << "   This build runs the read-depth hot path on an MI355X; input is a read depth file\n"
             << "   (samtools mpileup BAM | cut -f2,4) with -c RNAME, a whole-genome depth file without -c\n"
@@ -104,6 +110,12 @@ int usage() {
             << "   bedtools read it, and so does -d FILE (name it .bedgraph, or -dformat bedgraph).  Works with every input but -gpus\n"
             << "   above 1; with -samples it writes FILE.k per column k.  The depth of bases excluded with -x is saved unchanged.\n"
             << "   -trackdepth gc saves the depth after the GC adjustment, before the cap (not with -NOGC).\n"
+            << "   -bintrack FILE: one line RNAME START END VALUE per bin of -m kept bases (0-based half-open), the signal the calls\n"
+            << "   are made from: the bin's median over the chromosome's median with three decimals (a DUP is a plateau at 1.5), or\n"
+            << "   with -bintrackvalue median the bin's median itself.  A bin is cut where N or -x regions lie inside it, so no line\n"
+            << "   covers a removed base; the bases behind the last whole bin get no line.  Chromosomes in the order of the output\n"
+            << "   rows; formatted on the GPU.  Works with every input but -gpus above 1, and beside -track; with -samples it writes\n"
+            << "   FILE.k per column k.\n"
             << std::endl;
   return 0;
 }
@@ -159,6 +171,8 @@ void parse(int argc, char** argv, Options& o) {
     else if (s == "-x") { o.excludefile = need(i); ++i; }
     else if (s == "-track") { o.trackfile = need(i); ++i; }
     else if (s == "-trackdepth") { o.trackdepth = need(i); ++i; }
+    else if (s == "-bintrack") { o.bintrackfile = need(i); ++i; }
+    else if (s == "-bintrackvalue") { o.bintrackvalue = need(i); ++i; }
     else { std::cerr << "unknown option " << s << std::endl; exit(usage()); }
   }
   if (o.rdfile.empty() && o.bamfile.empty()) { std::cerr << "need input file " << std::endl; exit(usage()); }
@@ -207,8 +221,9 @@ struct ChromOutput {
   bool populated = false;          // the chromosome was processed (has reads / could be read): it counts for the header
   bool fatal = false;              // the single-chromosome modes stop here (the reference exits)
   bool bad_input = false;          // the compressed depth file is broken: exit 1, no output file
-  size_t track_index = 0;          // -track: the chromosome's place in the order of the rows (set by the caller: names its part file)
+  size_t track_index = 0;          // -track, -bintrack: the chromosome's place in the order of the rows (set by the caller: names its part files)
   bool track_failed = false;       // -track: its part could not be written (the reason is in the log): no track file
+  bool bintrack_failed = false;    // -bintrack: likewise
 };
 
 // One log line for a compressed depth file (none for plain text, whose logs stay as they were)
@@ -305,6 +320,17 @@ void report_chromosome(rsi_ctx* ctx, const Options& o, const std::string& chr, r
       co.track_failed = true;
     } else {
       info << "track: " << chr << " " << tk.lines << " lines, " << tk.bytes << " bytes, " << tk.t_total_ms * 1e-3 << " s (kernels "
+           << tk.t_kernel_ms * 1e-3 << " s, write " << tk.t_write_ms * 1e-3 << " s)\n";
+    }
+  }
+  if (!o.bintrackfile.empty()) {   // -bintrack: this chromosome's bins into their part file, while the context still holds the run
+    rsi_track_stats tk;
+    const std::string part = rsitrack::part_path(o.bintrackfile, co.track_index);
+    if (rsi_hot_write_bin_track(ctx, o.bintrackvalue == "median" ? 0 : 1, chr.c_str(), part.c_str(), 0, &tk) != RSI_OK) {
+      info << "bintrack: " << chr << ": " << rsi_hot_last_error(ctx) << "\n";
+      co.bintrack_failed = true;
+    } else {
+      info << "bintrack: " << chr << " " << tk.lines << " lines, " << tk.bytes << " bytes, " << tk.t_total_ms * 1e-3 << " s (kernels "
            << tk.t_kernel_ms * 1e-3 << " s, write " << tk.t_write_ms * 1e-3 << " s)\n";
     }
   }
@@ -483,6 +509,7 @@ bool run_genome(const Options& o, const std::vector<int32_t>& cols, std::vector<
   for (int j = 0; j < (int)cols.size(); ++j) {
     so[j].plotfolder = o.plotfolder + "/" + std::to_string(cols[j]);
     if (!o.trackfile.empty()) so[j].trackfile = o.trackfile + "." + std::to_string(cols[j]);   // as -o: FILE.k
+    if (!o.bintrackfile.empty()) so[j].bintrackfile = o.bintrackfile + "." + std::to_string(cols[j]);
   }
 
   struct Job { size_t idx; int j; rsi_genome_chrom c; const void* d_depth; std::shared_ptr<const std::string> fasta; double t_fasta; };
@@ -639,21 +666,30 @@ bool select_samples(const Options& o, std::vector<int32_t>& cols, std::vector<st
   return true;
 }
 
-// -track, after the run: the parts of the chromosomes whose rows were written (`order`, in row order) become FILE; every part
-// 0 .. count - 1 is deleted whatever happened.  failed: a chromosome's part could not be written -- then there is no FILE.
-bool finish_track(const std::string& file, const std::vector<size_t>& order, size_t count, bool failed, std::ostream& log) {
+// -track and -bintrack (`what`: "track" / "bin track", `flag`: the option), after the run: the parts of the chromosomes whose rows
+// were written (`order`, in row order) become FILE; every part 0 .. count - 1 is deleted whatever happened.  failed: a
+// chromosome's part could not be written -- then there is no FILE.
+bool finish_track(const std::string& file, const std::vector<size_t>& order, size_t count, bool failed, std::ostream& log,
+                  const char* what = "track", const char* flag = "-track") {
   if (file.empty()) return true;
   std::string err;
   if (failed) {
     rsitrack::remove_parts(file, count);
     remove(file.c_str());
-    err = "a chromosome's track could not be written (see above)";
+    err = std::string("a chromosome's ") + what + " could not be written (see above)";
   } else if (rsitrack::join_parts(file, order, count, err)) {
-    std::cerr << "track written to " << file << std::endl; log << "track written to " << file << std::endl;
+    std::cerr << what << " written to " << file << std::endl; log << what << " written to " << file << std::endl;
     return true;
   }
-  std::cerr << "rsicnv: -track: " << err << std::endl; log << "rsicnv: -track: " << err << std::endl;
+  std::cerr << "rsicnv: " << flag << ": " << err << std::endl; log << "rsicnv: " << flag << ": " << err << std::endl;
   return false;
+}
+// both kinds of track of one output: every part is dealt with, whichever fails
+bool finish_tracks(const Options& o, const std::string& suffix, const std::vector<size_t>& order, size_t count, bool track_failed,
+                   bool bintrack_failed, std::ostream& log) {
+  const bool a = finish_track(o.trackfile.empty() ? "" : o.trackfile + suffix, order, count, track_failed, log);
+  const bool b = finish_track(o.bintrackfile.empty() ? "" : o.bintrackfile + suffix, order, count, bintrack_failed, log, "bin track", "-bintrack");
+  return a && b;
 }
 
 }  // namespace
@@ -700,6 +736,17 @@ int main(int argc, char** argv) {
     if (o.gpus > 1) { std::cerr << "rsicnv: -track: not with -gpus above 1 (the track is written by one device: -gpu INT picks it)" << std::endl; return 1; }
     if (o.trackdepth == "gc" && !o.P.gcadjust) { std::cerr << "rsicnv: -trackdepth gc: -NOGC leaves no GC-adjusted depth to save" << std::endl; return 1; }
     if (o.trackfile == o.outfile || o.trackfile == o.rdfile || o.trackfile == o.bamfile) { std::cerr << "rsicnv: -track: the track file is an input or the output file" << std::endl; return 1; }
+  }
+  if (o.bintrackvalue != "ratio" && o.bintrackvalue != "median") {
+    std::cerr << "rsicnv: -bintrackvalue " << o.bintrackvalue << ": expected ratio or median" << std::endl;
+    return 1;
+  }
+  if (!o.bintrackfile.empty()) {
+    if (o.gpus > 1) { std::cerr << "rsicnv: -bintrack: not with -gpus above 1 (the track is written by one device: -gpu INT picks it)" << std::endl; return 1; }
+    if (o.bintrackfile == o.outfile || o.bintrackfile == o.rdfile || o.bintrackfile == o.bamfile || o.bintrackfile == o.trackfile) {
+      std::cerr << "rsicnv: -bintrack: the bin track file is an input, the output file or -track's file" << std::endl;
+      return 1;
+    }
   }
   // -x: a BED file with a bad line is refused as a whole, whichever chromosome the line names, before any output exists
   if (!o.excludefile.empty() && rsi_exclude_read_bed(o.excludefile.c_str(), "", 0, nullptr, nullptr, 0) < 0) {
@@ -785,6 +832,7 @@ int main(int argc, char** argv) {
       std::cerr << "rsicnv: " << err << std::endl; log << "rsicnv: " << err << std::endl;
       for (size_t j = 0; j < cols.size(); ++j) { remove(out_k(j).c_str()); remove((out_k(j) + ".log").c_str()); }
       if (!o.trackfile.empty()) for (size_t j = 0; j < cols.size(); ++j) rsitrack::remove_parts(o.trackfile + "." + std::to_string(cols[j]), chroms.size());
+      if (!o.bintrackfile.empty()) for (size_t j = 0; j < cols.size(); ++j) rsitrack::remove_parts(o.bintrackfile + "." + std::to_string(cols[j]), chroms.size());
       return 1;
     }
     bool tracks_ok = true;
@@ -795,12 +843,13 @@ int main(int argc, char** argv) {
       std::string h = hdr.str();
       h.replace(h.find("#output:    " + o.outfile + "\n"), 12 + o.outfile.size() + 1, "#output:    " + path + "\n");
       slog << h << "#sample " << cols[j] << (sample_names[j].empty() ? "" : ": " + sample_names[j]) << "\n";
-      bool header_done = false, track_failed = false;
+      bool header_done = false, track_failed = false, bintrack_failed = false;
       std::vector<size_t> track_order;
       for (size_t i = 0; i < chroms.size(); ++i) {
         const ChromOutput& co = outs[i][j];
         std::cerr << co.log; slog << co.log;
         track_failed = track_failed || co.track_failed;
+        bintrack_failed = bintrack_failed || co.bintrack_failed;
         if (co.populated) track_order.push_back(i);
         if (co.populated) {
           std::ofstream out(path.c_str(), header_done ? std::ios::app : std::ios::trunc);
@@ -816,7 +865,7 @@ int main(int argc, char** argv) {
         }
         if (co.fatal) break;
       }
-      if (!o.trackfile.empty() && !finish_track(o.trackfile + "." + std::to_string(cols[j]), track_order, chroms.size(), track_failed, slog)) tracks_ok = false;
+      if (!finish_tracks(o, "." + std::to_string(cols[j]), track_order, chroms.size(), track_failed, bintrack_failed, slog)) tracks_ok = false;
     }
     std::cerr << summary; log << summary;
     return tracks_ok ? 0 : 1;
@@ -832,18 +881,20 @@ int main(int argc, char** argv) {
       std::cerr << "rsicnv: " << err << std::endl; log << "rsicnv: " << err << std::endl;
       remove(o.outfile.c_str());
       rsitrack::remove_parts(o.trackfile, chroms.size());
+      rsitrack::remove_parts(o.bintrackfile, chroms.size());
       return 1;
     }
     std::vector<size_t> track_order;
-    bool track_failed = false;
+    bool track_failed = false, bintrack_failed = false;
     for (size_t i = 0; i < chroms.size(); ++i) {
       emit(chroms[i], outs[i][0]);
       track_failed = track_failed || outs[i][0].track_failed;
+      bintrack_failed = bintrack_failed || outs[i][0].bintrack_failed;
       if (outs[i][0].populated) track_order.push_back(i);
       if (outs[i][0].fatal) break;
     }
     std::cerr << summary; log << summary;
-    return finish_track(o.trackfile, track_order, chroms.size(), track_failed, log) ? 0 : 1;
+    return finish_tracks(o, "", track_order, chroms.size(), track_failed, bintrack_failed, log) ? 0 : 1;
   }
 
   if (o.gpus <= 0 || !many) {   // the reference's own shape: one chromosome after the other on one context
@@ -851,7 +902,7 @@ int main(int argc, char** argv) {
     rsi_ctx* ctx = rsi_hot_create(o.device, &st);
     if (!ctx) { std::cerr << "rsicnv: " << rsi_hot_last_error(nullptr) << std::endl; return 1; }
     std::vector<size_t> track_order;
-    bool track_failed = false;
+    bool track_failed = false, bintrack_failed = false;
     for (size_t i = 0; i < todo.size(); ++i) {
       const std::string& chr = todo[i];
       ChromOutput co;
@@ -861,16 +912,18 @@ int main(int argc, char** argv) {
         std::cerr << co.log; log << co.log;
         remove(o.outfile.c_str());
         rsitrack::remove_parts(o.trackfile, todo.size());
+        rsitrack::remove_parts(o.bintrackfile, todo.size());
         rsi_hot_destroy(ctx);
         return 1;
       }
       emit(chr, co);
       track_failed = track_failed || co.track_failed;
+      bintrack_failed = bintrack_failed || co.bintrack_failed;
       if (co.populated) track_order.push_back(i);
       if (co.fatal) break;
     }
     rsi_hot_destroy(ctx);
-    return finish_track(o.trackfile, track_order, todo.size(), track_failed, log) ? 0 : 1;
+    return finish_tracks(o, "", track_order, todo.size(), track_failed, bintrack_failed, log) ? 0 : 1;
   }
 
   // ---- -gpus N: the iterations of the loop are independent.  Chromosomes go to devices longest first
@@ -929,12 +982,13 @@ int main(int argc, char** argv) {
       });
   for (auto& t : threads) t.join();
   std::vector<size_t> track_order;
-  bool track_failed = false;
+  bool track_failed = false, bintrack_failed = false;
   for (size_t i = 0; i < todo.size(); ++i) {
     emit(todo[i], outs[i]);
     track_failed = track_failed || outs[i].track_failed;
+    bintrack_failed = bintrack_failed || outs[i].bintrack_failed;
     if (outs[i].populated) track_order.push_back(i);
   }
   for (rsi_pool* pl : pools) rsi_pool_destroy(pl);
-  return finish_track(o.trackfile, track_order, todo.size(), track_failed, log) ? 0 : 1;   // (-track: one device only, -gpus 1)
+  return finish_tracks(o, "", track_order, todo.size(), track_failed, bintrack_failed, log) ? 0 : 1;   // (-track, -bintrack: one device only, -gpus 1)
 }

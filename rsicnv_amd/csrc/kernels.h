@@ -567,4 +567,27 @@ void launch_track_line_bytes(const int32_t* v, const long long* starts, TrackSta
 void launch_track_format(const int32_t* v, const long long* starts, const unsigned int* ltiles, long long nlines, long long pos0,
                          const TrackName& name, char* text, long long cap, hipStream_t stream);
 
+// ---- per-bin track: one value per bin as bedGraph text, a line per piece of a bin (kernels_track.hip) ----
+// Bin b holds the compacted positions [b m, (b + 1) m), mapped back through the removed-region table (cbreak[nreg], cum[nreg + 1],
+// in HBM); it is cut where a removed region lies strictly inside it.  Slices are ranges of bins [b0, b1); a piece belongs to the
+// slice of its bin, so no state passes from slice to slice.  pieces: one 8-byte word per piece, (bin - b0) << 16 | region index.
+struct BinTrackSource {
+  const int32_t* v;                 // value of every bin of the chromosome
+  const unsigned long long* pieces;
+  const long long* cbreak; const long long* cum;
+  int nreg, m;
+  long long b0;                     // the slice's first bin
+  int which;                        // 0: the value as %d; 1: value / (median2 / 2) with three decimals, rounded half up
+  long long median2;                // > 0 when which == 1
+};
+// Passes 1-3: pieces counted per tile of bins, the tile counts scanned, the pieces scattered (none at or beyond cap); st->nlines.
+// tiles: track_tiles(b1 - b0) + 1 words; b1 - b0 > 0.
+void launch_bintrack_pieces(const long long* cbreak, const long long* cum, int nreg, int m, long long b0, long long b1, unsigned int* tiles,
+                            unsigned long long* pieces, long long cap, TrackState* st, hipStream_t stream);
+// Passes 4 and 5 of the depth track on the pieces: max_lines bounds the grid as there; ltiles: track_tiles(max_lines) + 1 words.
+void launch_bintrack_line_bytes(const BinTrackSource& src, TrackState* st, int name_len, long long max_lines, unsigned int* ltiles,
+                                hipStream_t stream);
+void launch_bintrack_format(const BinTrackSource& src, const unsigned int* ltiles, long long nlines, const TrackName& name, char* text,
+                            long long cap, hipStream_t stream);
+
 }  // namespace rsik

@@ -108,25 +108,49 @@ struct RunLines {
   const long long* __restrict__ starts;
   __device__ void get(long long j, long long& s, long long& e, int& val) const { s = starts[j]; e = starts[j + 1]; val = v[s]; }
 };
-struct LineShape { long long s, e; int val, ls, le, lv; };
-template <class Lines>
-__device__ inline int line_shape(const Lines& src, long long j, long long pos0, int name_len, LineShape& L) {
+struct LineShape { long long s, e; int val, ls, le, lv; unsigned long long q; };
+
+// How a line's value is written, chosen at compile time: its length for line_shape, its digits for the format pass.
+struct DecValue {   // %d
+  __device__ int len(int val, unsigned long long& q) const { q = 0; return dec_len_i32(val); }
+  __device__ char* put(char* __restrict__ p, int val, unsigned long long, int lv) const { return put_i64(p, (long long)val, lv); }
+};
+// val over half of m2, three decimals, rounded half up: q = (4000 val + m2) / (2 m2) thousandths, in integers (val >= 0, m2 > 0)
+struct RatioValue {
+  long long m2;
+  __device__ int len(int val, unsigned long long& q) const {
+    q = val < 0 ? 0ull : (4000ull * (unsigned long long)val + (unsigned long long)m2) / (2ull * (unsigned long long)m2);
+    return dec_len_u64(q / 1000ull) + 4;   // the point and three places
+  }
+  __device__ char* put(char* __restrict__ p, int, unsigned long long q, int lv) const {
+    put_dec(p, lv - 4, q / 1000ull);
+    unsigned int f = (unsigned int)(q % 1000ull);
+    p[lv - 4] = '.';
+    p[lv - 1] = (char)('0' + (int)(f % 10u)); f /= 10u;
+    p[lv - 2] = (char)('0' + (int)(f % 10u)); f /= 10u;
+    p[lv - 3] = (char)('0' + (int)f);
+    return p + lv;
+  }
+};
+
+template <class Lines, class Value>
+__device__ inline int line_shape(const Lines& src, const Value& fmt, long long j, long long pos0, int name_len, LineShape& L) {
   src.get(j, L.s, L.e, L.val);
   L.s += pos0; L.e += pos0;
-  L.ls = dec_len_i64(L.s); L.le = dec_len_i64(L.e); L.lv = dec_len_i32(L.val);
+  L.ls = dec_len_i64(L.s); L.le = dec_len_i64(L.e); L.lv = fmt.len(L.val, L.q);
   return name_len + 4 + L.ls + L.le + L.lv;   // three tabs and the newline
 }
 
 // ---- pass 4: bytes per tile of 256 lines ----
-template <class Lines>
-__global__ __launch_bounds__(kTrackTile) void k_track_line_bytes(Lines src, const TrackState* __restrict__ st, long long pos0, int name_len,
+template <class Lines, class Value>
+__global__ __launch_bounds__(kTrackTile) void k_track_line_bytes(Lines src, Value fmt, const TrackState* __restrict__ st, long long pos0, int name_len,
                                                                  unsigned int* __restrict__ ltiles) {
   __shared__ unsigned int s_w[kTrackTile / 64];
   const long long nlines = st->nlines;
   if ((long long)blockIdx.x * kTrackTile >= nlines) return;   // the grid covers the most lines a slice can have
   const long long j = (long long)blockIdx.x * kTrackTile + threadIdx.x;
   LineShape L;
-  const unsigned int len = j < nlines ? (unsigned int)line_shape(src, j, pos0, name_len, L) : 0u;
+  const unsigned int len = j < nlines ? (unsigned int)line_shape(src, fmt, j, pos0, name_len, L) : 0u;
   unsigned int total;
   (void)wg_exscan_u32(len, s_w, &total);
   if (threadIdx.x == 0) ltiles[blockIdx.x] = total;
@@ -144,13 +168,13 @@ __global__ __launch_bounds__(kTrackTile) void k_track_scan_lines(unsigned int* _
 }
 
 // ---- pass 5: one thread per line ----
-template <class Lines>
-__global__ __launch_bounds__(kTrackTile) void k_track_format(Lines src, const unsigned int* __restrict__ ltiles, long long nlines, long long pos0,
+template <class Lines, class Value>
+__global__ __launch_bounds__(kTrackTile) void k_track_format(Lines src, Value fmt, const unsigned int* __restrict__ ltiles, long long nlines, long long pos0,
                                                              const TrackName name, char* __restrict__ text, long long cap) {
   __shared__ unsigned int s_w[kTrackTile / 64];
   const long long j = (long long)blockIdx.x * kTrackTile + threadIdx.x;
   LineShape L;
-  const unsigned int len = j < nlines ? (unsigned int)line_shape(src, j, pos0, name.len, L) : 0u;
+  const unsigned int len = j < nlines ? (unsigned int)line_shape(src, fmt, j, pos0, name.len, L) : 0u;
   unsigned int total;
   const unsigned long long off = (unsigned long long)ltiles[blockIdx.x] + wg_exscan_u32(len, s_w, &total);
   if (len == 0u || (long long)(off + len) > cap) return;
@@ -162,9 +186,88 @@ __global__ __launch_bounds__(kTrackTile) void k_track_format(Lines src, const un
   *p++ = '\t';
   p = put_i64(p, L.e, L.le);
   *p++ = '\t';
-  p = put_i64(p, (long long)L.val, L.lv);
+  p = fmt.put(p, L.val, L.q, L.lv);
   *p = '\n';
 }
+
+// ---- per-bin lines: one line per piece of a bin, a piece being a maximal stretch of consecutive reference positions ----
+// Bin b covers the compacted positions [b m, (b + 1) m); a compacted position p lies at p + cum[k], k = #{cbreak <= p}
+// (rsih::compact_table).  A bin is cut at every break strictly inside it, so it has 1 + #{b m < cbreak < (b + 1) m} pieces; a
+// break at b m belongs to the gap in front.  The table comes from HBM, at most 4096 entries: twelve steps per search.
+struct BinTable { const long long* __restrict__ cbreak; const long long* __restrict__ cum; int nreg; int m; };
+__device__ inline int breaks_le(const BinTable& t, long long p) {   // #{cbreak <= p}
+  int lo = 0, hi = t.nreg;
+  while (lo < hi) { const int mid = (lo + hi) >> 1; if (t.cbreak[mid] <= p) lo = mid + 1; else hi = mid; }
+  return lo;
+}
+__device__ inline int breaks_lt(const BinTable& t, long long p) {   // #{cbreak < p}
+  int lo = 0, hi = t.nreg;
+  while (lo < hi) { const int mid = (lo + hi) >> 1; if (t.cbreak[mid] < p) lo = mid + 1; else hi = mid; }
+  return lo;
+}
+// pieces of bin b and the region index of its first one (= the breaks at or in front of its first position)
+__device__ inline unsigned int bin_pieces(const BinTable& t, long long b, int& k0) {
+  const long long lo = b * t.m;
+  k0 = breaks_le(t, lo);
+  return 1u + (unsigned int)(breaks_lt(t, lo + t.m) - k0);
+}
+
+// A piece is stored as (bin - b0) << 16 | region index: eight bytes where the triple takes twenty, and the accessor needs no
+// search to get the triple back -- the piece of bin b with k breaks in front runs from max(b m, cbreak[k - 1]) to
+// min((b + 1) m, cbreak[k]) in compacted positions, shifted by cum[k].
+constexpr int kPieceRegionBits = 16;
+static_assert((1 << kPieceRegionBits) > 4096, "a region index fits the low bits of a piece");
+
+// pass 1: pieces per tile of 256 bins
+__global__ __launch_bounds__(kTrackTile) void k_bintrack_count(BinTable t, long long b0, long long b1, unsigned int* __restrict__ tiles) {
+  __shared__ unsigned int s_w[kTrackTile / 64];
+  const long long b = b0 + (long long)blockIdx.x * kTrackTile + threadIdx.x;
+  int k0;
+  const unsigned int cnt = b < b1 ? bin_pieces(t, b, k0) : 0u;
+  unsigned int total;
+  (void)wg_exscan_u32(cnt, s_w, &total);
+  if (threadIdx.x == 0) tiles[blockIdx.x] = total;
+}
+
+// pass 2: the tile counts become offsets into pieces[]; nothing is carried from slice to slice
+__global__ __launch_bounds__(kTrackTile) void k_bintrack_scan(unsigned int* __restrict__ tiles, int ntiles, TrackState* __restrict__ st) {
+  __shared__ unsigned int s_w[kTrackTile / 64];
+  const unsigned long long total = scan_tile_words(tiles, ntiles, 0u, s_w);
+  if (threadIdx.x == 0) { st->carry = -1; st->nstarts = 0; st->nlines = (long long)total; st->nbytes = 0; }
+}
+
+// pass 3: every bin writes its pieces, in order, at its offset; the loop is as long as the breaks inside the bin (at most the table)
+__global__ __launch_bounds__(kTrackTile) void k_bintrack_scatter(BinTable t, long long b0, long long b1, const unsigned int* __restrict__ tiles,
+                                                                 unsigned long long* __restrict__ pieces, long long cap) {
+  __shared__ unsigned int s_w[kTrackTile / 64];
+  const long long b = b0 + (long long)blockIdx.x * kTrackTile + threadIdx.x;
+  int k0 = 0;
+  const unsigned int cnt = b < b1 ? bin_pieces(t, b, k0) : 0u;
+  unsigned int total;
+  const unsigned long long off = (unsigned long long)tiles[blockIdx.x] + wg_exscan_u32(cnt, s_w, &total);
+  const unsigned long long word = (unsigned long long)(b - b0) << kPieceRegionBits;
+  for (unsigned int i = 0; i < cnt; ++i)
+    if ((long long)(off + i) < cap) pieces[off + i] = word | (unsigned int)(k0 + (int)i);
+}
+
+struct BinLines {
+  const int32_t* __restrict__ v;   // the bins' values, v[0] = bin 0 of the chromosome
+  const unsigned long long* __restrict__ pieces;
+  BinTable t;
+  long long b0;
+  __device__ void get(long long j, long long& s, long long& e, int& val) const {
+    const unsigned long long w = pieces[j];
+    const int k = (int)(w & ((1u << kPieceRegionBits) - 1u));
+    const long long b = b0 + (long long)(w >> kPieceRegionBits);
+    const long long lo = b * t.m, hi = lo + t.m;
+    s = lo; e = hi;
+    if (k > 0) { const long long c = t.cbreak[k - 1]; if (c > s) s = c; }
+    if (k < t.nreg) { const long long c = t.cbreak[k]; if (c < e) e = c; }
+    const long long shift = t.cum[k];
+    s += shift; e += shift;
+    val = v[b];
+  }
+};
 
 }  // namespace
 
@@ -181,7 +284,7 @@ void launch_track_line_bytes(const int32_t* v, const long long* starts, TrackSta
                              unsigned int* ltiles, hipStream_t stream) {
   const int ntiles = track_tiles(max_lines);
   if (ntiles <= 0) return;
-  RSI_LAUNCH(k_track_line_bytes<RunLines>, dim3(ntiles), dim3(kTrackTile), 0, stream, RunLines{v, starts}, st, pos0, name_len, ltiles);
+  RSI_LAUNCH((k_track_line_bytes<RunLines, DecValue>), dim3(ntiles), dim3(kTrackTile), 0, stream, RunLines{v, starts}, DecValue{}, st, pos0, name_len, ltiles);
   RSI_LAUNCH(k_track_scan_lines, dim3(1), dim3(kTrackTile), 0, stream, ltiles, starts, st);
 }
 
@@ -189,7 +292,40 @@ void launch_track_format(const int32_t* v, const long long* starts, const unsign
                          const TrackName& name, char* text, long long cap, hipStream_t stream) {
   const int ntiles = track_tiles(nlines);
   if (ntiles <= 0) return;
-  RSI_LAUNCH(k_track_format<RunLines>, dim3(ntiles), dim3(kTrackTile), 0, stream, RunLines{v, starts}, ltiles, nlines, pos0, name, text, cap);
+  RSI_LAUNCH((k_track_format<RunLines, DecValue>), dim3(ntiles), dim3(kTrackTile), 0, stream, RunLines{v, starts}, DecValue{}, ltiles, nlines, pos0, name, text, cap);
+}
+
+void launch_bintrack_pieces(const long long* cbreak, const long long* cum, int nreg, int m, long long b0, long long b1, unsigned int* tiles,
+                            unsigned long long* pieces, long long cap, TrackState* st, hipStream_t stream) {
+  const int ntiles = track_tiles(b1 - b0);
+  if (ntiles <= 0) return;
+  const BinTable t{cbreak, cum, nreg, m};
+  RSI_LAUNCH(k_bintrack_count, dim3(ntiles), dim3(kTrackTile), 0, stream, t, b0, b1, tiles);
+  RSI_LAUNCH(k_bintrack_scan, dim3(1), dim3(kTrackTile), 0, stream, tiles, ntiles, st);
+  RSI_LAUNCH(k_bintrack_scatter, dim3(ntiles), dim3(kTrackTile), 0, stream, t, b0, b1, tiles, pieces, cap);
+}
+
+void launch_bintrack_line_bytes(const BinTrackSource& src, TrackState* st, int name_len, long long max_lines, unsigned int* ltiles,
+                                hipStream_t stream) {
+  const int ntiles = track_tiles(max_lines);
+  if (ntiles <= 0) return;
+  const BinLines lines{src.v, src.pieces, BinTable{src.cbreak, src.cum, src.nreg, src.m}, src.b0};
+  if (src.which == 1)
+    RSI_LAUNCH((k_track_line_bytes<BinLines, RatioValue>), dim3(ntiles), dim3(kTrackTile), 0, stream, lines, RatioValue{src.median2}, st, 0ll, name_len, ltiles);
+  else
+    RSI_LAUNCH((k_track_line_bytes<BinLines, DecValue>), dim3(ntiles), dim3(kTrackTile), 0, stream, lines, DecValue{}, st, 0ll, name_len, ltiles);
+  RSI_LAUNCH(k_track_scan_lines, dim3(1), dim3(kTrackTile), 0, stream, ltiles, static_cast<const long long*>(nullptr), st);
+}
+
+void launch_bintrack_format(const BinTrackSource& src, const unsigned int* ltiles, long long nlines, const TrackName& name, char* text,
+                            long long cap, hipStream_t stream) {
+  const int ntiles = track_tiles(nlines);
+  if (ntiles <= 0) return;
+  const BinLines lines{src.v, src.pieces, BinTable{src.cbreak, src.cum, src.nreg, src.m}, src.b0};
+  if (src.which == 1)
+    RSI_LAUNCH((k_track_format<BinLines, RatioValue>), dim3(ntiles), dim3(kTrackTile), 0, stream, lines, RatioValue{src.median2}, ltiles, nlines, 0ll, name, text, cap);
+  else
+    RSI_LAUNCH((k_track_format<BinLines, DecValue>), dim3(ntiles), dim3(kTrackTile), 0, stream, lines, DecValue{}, ltiles, nlines, 0ll, name, text, cap);
 }
 
 }  // namespace rsik

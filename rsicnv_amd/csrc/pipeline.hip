@@ -816,7 +816,7 @@ int per_base_phase(rsi_ctx* ctx, const rsi_params& P, const int32_t* d_depth, co
     hbm_turn.g = ctx->gate;
   }
   Phase ph_a1(ctx, "a1.classify+nruns");
-  ctx->n = n; ctx->ncompact = 0; ctx->nb = 0; ctx->have_gc = ctx->have_nb = ctx->have_med = false;
+  ctx->n = n; ctx->ncompact = 0; ctx->nb = 0; ctx->run_m = 0; ctx->run_rdmedian = 0.0; ctx->have_gc = ctx->have_nb = ctx->have_med = false;
   ctx->rd_gc_valid = false; ctx->last_depth = d_depth; ctx->rdc_is_bytes = false; ctx->rdc_valid = false;
   rsi_chrom_stats& S = res->stats;
   memset(&S, 0, sizeof(S));
@@ -1370,6 +1370,7 @@ int bin_level_stages(rsi_ctx* ctx, const rsi_params& P, int64_t n, rsi_result* r
 
 // What every run checks and resets before its first launch (rsi_hot_run_device, rsi_hot_debug_per_base).
 int run_enter(rsi_ctx* ctx, const rsi_params& P, const int32_t* d_depth, const uint8_t* d_fasta, int64_t n) {
+  ctx->run_m = 0; ctx->run_rdmedian = 0.0;   // whatever becomes of this run, the one before is no longer the last
   if (n <= 0 || n >= (1ll << 31) - 4096) return fail(ctx, RSI_ERR_BAD_ARG, "chromosome length must be in (0, 2^31)");
   if (P.m < 1 || (P.m % 2) != 1) return fail(ctx, RSI_ERR_BAD_ARG, "m must be odd (the reference forces it, rsi.cpp:2061-2064)");
   if (P.m > 3000) return fail(ctx, RSI_ERR_UNSUPPORTED, "bin size above 3000 is not supported by the bin kernel");
@@ -1415,6 +1416,7 @@ int run_device_impl(rsi_ctx* ctx, const rsi_params* Pp, const int32_t* d_depth, 
     for (const KernelTime& k : ctx->ktimes) { float ms = 0; (void)hipEventElapsedTime(&ms, k.a, k.b); tot += ms; }
     S.t_kernels_ms = tot;
   }
+  ctx->run_m = P.m; ctx->run_rdmedian = S.RDmedian;   // the run is whole: rsi_hot_write_bin_track may read its bins
   return RSI_OK;
 }
 
@@ -1787,7 +1789,7 @@ int rsi_hot_debug_scan(rsi_ctx* ctx, const float* T, const int32_t* medint, int6
   HIPCHK(hipSetDevice(ctx->device));
   if (!ctx_enter(ctx)) return RSI_ERR_HIP;
   mailbox_reset(ctx);
-  ctx->nb = nb;
+  ctx->nb = nb; ctx->run_m = 0;
   HIPCHK(ctx->small.ensure(kSmallBytes));
   HIPCHK(ctx->tnb.ensure((size_t)nb * 4));
   HIPCHK(ctx->binmed.ensure((size_t)nb * 4));
@@ -1869,6 +1871,7 @@ int rsi_hot_debug_grid_mad_i32(rsi_ctx* ctx, const int32_t* x, int64_t nb, doubl
   int rc;
   if (!x) return fail(ctx, RSI_ERR_BAD_ARG, "bad argument");
   if ((rc = grid_debug_enter(ctx, nb, out, info)) != RSI_OK) return rc;
+  ctx->run_m = 0;   // binmed is no longer the last run's
   HIPCHK(ctx->binmed.ensure((size_t)nb * 4));
   HIPCHK(ctx->tmed.ensure((size_t)nb * 4));
   HIPCHK(hipMemcpyAsync(ctx->binmed.p, x, (size_t)nb * 4, hipMemcpyHostToDevice, ctx->stream));

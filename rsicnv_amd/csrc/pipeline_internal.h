@@ -170,6 +170,7 @@ struct rsi_ctx {
   int sharpen_ws_jobs = 0;    // jobs it is laid out for
   // host mirrors kept for rsi_hot_fetch_* (what the last run left on the device)
   int64_t n = 0, ncompact = 0, nb = 0;
+  int run_m = 0; double run_rdmedian = 0.0;   // bin size and chromosome median of the last successful run (0: none, or binmed is no longer its)
   bool have_gc = false, have_nb = false, have_med = false;
   DevBuf rdc8;                               // the capped, compacted depth as bytes (what K4' writes; the candidate kernels read it in place)
   bool rdc_is_bytes = false, rdc_valid = false;   // rdc8 is the last run's array / the int32 rdc holds it too (materialize_rdc)
@@ -203,7 +204,7 @@ struct rsi_ctx {
   // than track_host.h's bounds, whatever the chromosome -- and its events (timing around the kernel groups, one behind each
   // pinned buffer's copy).  Freed by rsi_hot_destroy.
   struct TrackWs {
-    void* dev = nullptr; size_t dev_bytes = 0;           // text, starts, tiles, line tiles, state
+    void* dev = nullptr; size_t dev_bytes = 0;           // text, starts or pieces, tiles, line tiles, state, the bin track's region table
     char* pin[2] = {nullptr, nullptr}; size_t pin_bytes = 0;   // two text buffers: one is written to the file while the other fills
     void* pin_state = nullptr;                           // two TrackState: the device's, read back per slice; the initial one
     hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};

@@ -1,7 +1,8 @@
-// track.hip -- depth tracks as bedGraph (include/rsi_hot.h: rsi_hot_write_track, _write_track_device, rsi_hot_debug_track).  The
+// track.hip -- depth tracks and per-bin tracks as bedGraph (include/rsi_hot.h: rsi_hot_write_track, _write_track_device,
+// rsi_hot_debug_track; rsi_hot_write_bin_track, rsi_hot_debug_bin_track).  The
 // host drives kernels_track.hip slice by slice: the passes that find and measure a slice's lines, one wait for their two numbers,
 // the format pass and the copy of exactly those bytes into one of two pinned buffers; while that runs, the slice before goes
-// out through write().  Slice rule, bounds and numbers: DESIGN.md 6f.
+// out through write().  Slice rules, bounds and numbers: DESIGN.md 6f and 6g.
 #include "pipeline_internal.h"
 #include "track_host.h"
 
@@ -35,20 +36,24 @@ struct TrackSink {
 
 enum { kEvP0, kEvP1, kEvF0, kEvF1 = kEvF0 + 2, kEvCopy = kEvF1 + 2 };   // events: the measuring passes; per pinned buffer: format begin / end, copy done
 
-struct TrackLayout { size_t text, starts, tiles, ltiles, state, bytes; };
-TrackLayout track_layout(const rsitrack::Plan& p) {
-  auto up = [](size_t x) { return (x + 255) & ~size_t(255); };
+struct TrackLayout { size_t text, starts, tiles, ltiles, state, table, bytes; };
+size_t up256(size_t x) { return (x + 255) & ~size_t(255); }
+// text_cap bytes of text, `entries` 8-byte starts or pieces, tile words for `items` (passes 1-3) and `lines` (passes 4-5),
+// the state, and table_words 8-byte words of a region table
+TrackLayout track_layout(int64_t text_cap, int64_t entries, int64_t items, int64_t lines, size_t table_words) {
   TrackLayout L;
   L.text = 0;
-  L.starts = up((size_t)p.text_cap);
-  L.tiles = L.starts + up((size_t)(p.slice + 2) * 8);
-  L.ltiles = L.tiles + up((size_t)(track_tiles(p.slice) + 1) * 4);
-  L.state = L.ltiles + up((size_t)(track_tiles(p.slice + 1) + 1) * 4);
-  L.bytes = L.state + up(sizeof(TrackState));
+  L.starts = up256((size_t)text_cap);
+  L.tiles = L.starts + up256((size_t)entries * 8);
+  L.ltiles = L.tiles + up256((size_t)(track_tiles(items) + 1) * 4);
+  L.state = L.ltiles + up256((size_t)(track_tiles(lines) + 1) * 4);
+  L.table = L.state + up256(sizeof(TrackState));
+  L.bytes = L.table + up256(table_words * 8);
   return L;
 }
+TrackLayout track_layout(const rsitrack::Plan& p) { return track_layout(p.text_cap, p.slice + 2, p.slice, p.slice + 1, 0); }
 
-int track_ensure(rsi_ctx* ctx, const rsitrack::Plan& p, const TrackLayout& L) {
+int track_ensure(rsi_ctx* ctx, int64_t text_cap, const TrackLayout& L) {
   rsi_ctx::TrackWs& w = ctx->track;
   for (hipEvent_t& e : w.ev) if (!e) HIPCHK(hipEventCreate(&e));
   if (!w.pin_state) HIPCHK(hipHostMalloc(&w.pin_state, 2 * sizeof(TrackState), hipHostMallocDefault));
@@ -58,12 +63,80 @@ int track_ensure(rsi_ctx* ctx, const rsitrack::Plan& p, const TrackLayout& L) {
     HIPCHK(hipMalloc(&w.dev, L.bytes));
     w.dev_bytes = L.bytes;
   }
-  if ((size_t)p.text_cap > w.pin_bytes) {
+  if ((size_t)text_cap > w.pin_bytes) {
     for (char*& b : w.pin) { if (b) (void)hipHostFree(b); b = nullptr; }
     w.pin_bytes = 0;
-    for (char*& b : w.pin) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&b), (size_t)p.text_cap, hipHostMallocDefault));
-    w.pin_bytes = (size_t)p.text_cap;
+    for (char*& b : w.pin) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&b), (size_t)text_cap, hipHostMallocDefault));
+    w.pin_bytes = (size_t)text_cap;
   }
+  return RSI_OK;
+}
+
+// The slices of one call, whatever their lines come from: per slice [b, end) of `count` items, measure(b, end) queues the passes
+// that find and measure its lines; one wait for the state's two numbers, checked against max_lines(b, end), text_cap and
+// max_line; format(b, nlines) queues the format pass, the text is copied into one of the two pinned buffers, and the slice
+// before goes to the sink meanwhile.  Nothing of the call is still queued when this returns.
+template <class Measure, class MaxLines, class Format>
+int track_slices(rsi_ctx* ctx, int64_t count, int64_t slice, int64_t text_cap, int64_t max_line, TrackState* d_st, const char* d_text,
+                 TrackSink& sink, rsi_track_stats& S, Measure measure, MaxLines max_lines, Format format) {
+  rsi_ctx::TrackWs& w = ctx->track;
+  TrackState* h_st = static_cast<TrackState*>(w.pin_state);
+  hipStream_t st = ctx->stream;
+  int rc = RSI_OK;
+  auto leave = [&](int code, const std::string& msg) { (void)ctx_sync(ctx); return fail(ctx, code, msg); };
+  auto hip_failed = [&](hipError_t e, const char* what) { return leave(RSI_ERR_HIP, std::string("track: ") + what + ": " + hipGetErrorString(e)); };
+  auto elapsed = [&](int a, int b) { float ms = 0.f; return hipEventElapsedTime(&ms, w.ev[a], w.ev[b]) == hipSuccess ? (double)ms : 0.0; };
+  hipError_t e = hipSuccess;
+  int pending = -1, next_buf = 0;   // the pinned buffer whose slice is formatted and on its way, not yet in the sink
+  int64_t pending_bytes = 0;
+  auto flush = [&]() -> int {       // the pending slice: wait for its copy, note its format time, hand it to the sink
+    if (pending < 0) return RSI_OK;
+    const hipError_t ew = event_wait(w.ev[kEvCopy + pending]);
+    if (ew == hipErrorLaunchTimeOut) ctx->poisoned = true;
+    if (ew != hipSuccess) return fail(ctx, RSI_ERR_HIP, std::string("track: waiting for a slice's text: ") + hipGetErrorString(ew));
+    S.t_kernel_ms += elapsed(kEvF0 + pending, kEvF1 + pending);
+    const double t0 = now_ms();
+    const bool ok = sink.put(w.pin[pending], (size_t)pending_bytes);
+    const int err = errno;
+    S.t_write_ms += now_ms() - t0;
+    pending = -1;
+    if (!ok) return fail(ctx, RSI_ERR_INTERNAL, std::string("track: write failed: ") + strerror(err));
+    return RSI_OK;
+  };
+  for (int64_t b = 0; b < count; b += slice) {
+    const int64_t end = std::min(count, b + slice);
+    (void)hipEventRecord(w.ev[kEvP0], st);
+    measure(b, end);
+    (void)hipEventRecord(w.ev[kEvP1], st);
+    e = hipMemcpyAsync(&h_st[0], d_st, sizeof(TrackState), hipMemcpyDeviceToHost, st);
+    if (e != hipSuccess) return hip_failed(e, "hipMemcpyAsync");
+    e = ctx_sync(ctx);   // (the slice before has been formatted and copied by now too: same stream)
+    if (e != hipSuccess) return fail(ctx, RSI_ERR_HIP, std::string("track: waiting for a slice's line count: ") + hipGetErrorString(e));
+    S.t_kernel_ms += elapsed(kEvP0, kEvP1);
+    const int64_t nlines = h_st[0].nlines, nbytes = h_st[0].nbytes;
+    // the format pass writes nbytes of text for nlines lines: both must be what this slice's buffers were sized for
+    if (nlines < 0 || nlines > max_lines(b, end) || nbytes < 0 || nbytes > text_cap || nbytes > nlines * max_line)
+      return leave(RSI_ERR_INTERNAL, "track: a slice's line or byte count is out of range");
+    ++S.slices;
+    S.lines += nlines;
+    S.bytes += nbytes;
+    int fresh = -1;
+    if (nlines > 0) {
+      fresh = next_buf;
+      next_buf ^= 1;   // (at most one slice is pending, in the other buffer)
+      (void)hipEventRecord(w.ev[kEvF0 + fresh], st);
+      format(b, nlines);
+      (void)hipEventRecord(w.ev[kEvF1 + fresh], st);
+      e = hipMemcpyAsync(w.pin[fresh], d_text, (size_t)nbytes, hipMemcpyDeviceToHost, st);
+      if (e == hipSuccess) e = hipEventRecord(w.ev[kEvCopy + fresh], st);
+      if (e != hipSuccess) return hip_failed(e, "hipMemcpyAsync");
+    }
+    if ((rc = flush()) != RSI_OK) { (void)ctx_sync(ctx); return rc; }   // the slice before, while this one is formatted and copied
+    if (fresh >= 0) { pending = fresh; pending_bytes = nbytes; }
+  }
+  if ((rc = flush()) != RSI_OK) { (void)ctx_sync(ctx); return rc; }
+  e = ctx_sync(ctx);   // collects a launch error of the last format pass
+  if (e != hipSuccess) return fail(ctx, RSI_ERR_HIP, std::string("track: ") + hipGetErrorString(e));
   return RSI_OK;
 }
 
@@ -84,7 +157,7 @@ int track_run(rsi_ctx* ctx, const int32_t* d_v, int64_t n, const char* chrom, in
   HIPCHK(hipSetDevice(ctx->device));
   if (!ctx_enter(ctx)) return RSI_ERR_HIP;
   const TrackLayout L = track_layout(plan);
-  int rc = track_ensure(ctx, plan, L);
+  int rc = track_ensure(ctx, plan.text_cap, L);
   if (rc != RSI_OK) return rc;
   rsi_ctx::TrackWs& w = ctx->track;
   char* d_text = static_cast<char*>(w.dev) + L.text;
@@ -99,65 +172,17 @@ int track_run(rsi_ctx* ctx, const int32_t* d_v, int64_t n, const char* chrom, in
   name.len = name_len;
   hipStream_t st = ctx->stream;
 
-  // Whatever goes wrong below, nothing of this call is still queued when it returns: the copies land in the context's buffers.
-  auto leave = [&](int code, const std::string& msg) { (void)ctx_sync(ctx); return fail(ctx, code, msg); };
-  auto hip_failed = [&](hipError_t e, const char* what) { return leave(RSI_ERR_HIP, std::string("track: ") + what + ": " + hipGetErrorString(e)); };
-  auto elapsed = [&](int a, int b) { float ms = 0.f; return hipEventElapsedTime(&ms, w.ev[a], w.ev[b]) == hipSuccess ? (double)ms : 0.0; };
-
   h_st[1] = TrackState{-1, 0, 0, 0};
-  hipError_t e = hipMemcpyAsync(d_st, &h_st[1], sizeof(TrackState), hipMemcpyHostToDevice, st);
-  if (e != hipSuccess) return hip_failed(e, "hipMemcpyAsync");
-  int pending = -1, next_buf = 0;   // the pinned buffer whose slice is formatted and on its way, not yet in the sink
-  int64_t pending_bytes = 0;
-  auto flush = [&]() -> int {       // the pending slice: wait for its copy, note its format time, hand it to the sink
-    if (pending < 0) return RSI_OK;
-    const hipError_t ew = event_wait(w.ev[kEvCopy + pending]);
-    if (ew == hipErrorLaunchTimeOut) ctx->poisoned = true;
-    if (ew != hipSuccess) return fail(ctx, RSI_ERR_HIP, std::string("track: waiting for a slice's text: ") + hipGetErrorString(ew));
-    S.t_kernel_ms += elapsed(kEvF0 + pending, kEvF1 + pending);
-    const double t0 = now_ms();
-    const bool ok = sink.put(w.pin[pending], (size_t)pending_bytes);
-    const int err = errno;
-    S.t_write_ms += now_ms() - t0;
-    pending = -1;
-    if (!ok) return fail(ctx, RSI_ERR_INTERNAL, std::string("track: write failed: ") + strerror(err));
-    return RSI_OK;
-  };
-  for (int64_t b = 0; b < n; b += plan.slice) {
-    const int64_t end = std::min(n, b + plan.slice);
-    (void)hipEventRecord(w.ev[kEvP0], st);
-    launch_track_starts(d_v, b, end, n, d_tiles, d_starts, d_st, st);
-    launch_track_line_bytes(d_v, d_starts, d_st, pos0, name_len, end - b + 1, d_ltiles, st);
-    (void)hipEventRecord(w.ev[kEvP1], st);
-    e = hipMemcpyAsync(&h_st[0], d_st, sizeof(TrackState), hipMemcpyDeviceToHost, st);
-    if (e != hipSuccess) return hip_failed(e, "hipMemcpyAsync");
-    e = ctx_sync(ctx);   // (the slice before has been formatted and copied by now too: same stream)
-    if (e != hipSuccess) return fail(ctx, RSI_ERR_HIP, std::string("track: waiting for a slice's line count: ") + hipGetErrorString(e));
-    S.t_kernel_ms += elapsed(kEvP0, kEvP1);
-    const int64_t nlines = h_st[0].nlines, nbytes = h_st[0].nbytes;
-    // the format pass writes nbytes of text for nlines lines: both must be what this slice's buffers were sized for
-    if (nlines < 0 || nlines > end - b + 1 || nbytes < 0 || nbytes > plan.text_cap || nbytes > nlines * plan.max_line)
-      return leave(RSI_ERR_INTERNAL, "track: a slice's line or byte count is out of range");
-    ++S.slices;
-    S.lines += nlines;
-    S.bytes += nbytes;
-    int fresh = -1;
-    if (nlines > 0) {
-      fresh = next_buf;
-      next_buf ^= 1;   // (at most one slice is pending, in the other buffer)
-      (void)hipEventRecord(w.ev[kEvF0 + fresh], st);
-      launch_track_format(d_v, d_starts, d_ltiles, nlines, pos0, name, d_text, plan.text_cap, st);
-      (void)hipEventRecord(w.ev[kEvF1 + fresh], st);
-      e = hipMemcpyAsync(w.pin[fresh], d_text, (size_t)nbytes, hipMemcpyDeviceToHost, st);
-      if (e == hipSuccess) e = hipEventRecord(w.ev[kEvCopy + fresh], st);
-      if (e != hipSuccess) return hip_failed(e, "hipMemcpyAsync");
-    }
-    if ((rc = flush()) != RSI_OK) { (void)ctx_sync(ctx); return rc; }   // the slice before, while this one is formatted and copied
-    if (fresh >= 0) { pending = fresh; pending_bytes = nbytes; }
-  }
-  if ((rc = flush()) != RSI_OK) { (void)ctx_sync(ctx); return rc; }
-  e = ctx_sync(ctx);   // collects a launch error of the last format pass
-  if (e != hipSuccess) return fail(ctx, RSI_ERR_HIP, std::string("track: ") + hipGetErrorString(e));
+  const hipError_t e = hipMemcpyAsync(d_st, &h_st[1], sizeof(TrackState), hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) { (void)ctx_sync(ctx); return fail(ctx, RSI_ERR_HIP, std::string("track: hipMemcpyAsync: ") + hipGetErrorString(e)); }
+  rc = track_slices(ctx, n, plan.slice, plan.text_cap, plan.max_line, d_st, d_text, sink, S,
+      [&](int64_t b, int64_t end) {
+        launch_track_starts(d_v, b, end, n, d_tiles, d_starts, d_st, st);
+        launch_track_line_bytes(d_v, d_starts, d_st, pos0, name_len, end - b + 1, d_ltiles, st);
+      },
+      [](int64_t b, int64_t end) { return end - b + 1; },
+      [&](int64_t, int64_t nlines) { launch_track_format(d_v, d_starts, d_ltiles, nlines, pos0, name, d_text, plan.text_cap, st); });
+  if (rc != RSI_OK) return rc;
   S.t_total_ms = now_ms() - t_begin;
   if (stats) *stats = S;
   return RSI_OK;
@@ -172,6 +197,66 @@ int track_to_file(rsi_ctx* ctx, const int32_t* d_v, int64_t n, const char* chrom
   int rc = track_run(ctx, d_v, n, chrom, 0, 0, sink, stats);
   if (::close(sink.fd) != 0 && rc == RSI_OK) rc = fail(ctx, RSI_ERR_INTERNAL, std::string("track: write failed: ") + strerror(errno));
   return rc;
+}
+
+// values d_v[nb] of bins of m compacted bases as bedGraph lines of `chrom`, a line per piece of a bin, into the sink.  The table is
+// rsitrack::bin_table's for a chromosome of n bases; which / median2: the value format (kernels.h, BinTrackSource).
+int bin_track_run(rsi_ctx* ctx, const int32_t* d_v, int64_t nb, int m, int64_t n, const std::vector<int64_t>& cbreak,
+                  const std::vector<int64_t>& cum, int64_t median2, int which, const char* chrom, int64_t slice_bins, TrackSink& sink,
+                  rsi_track_stats* stats) {
+  static_assert(rsitrack::kMaxBinRegions == kMaxRegions, "the bin track takes every chromosome the pipeline takes");
+  const double t_begin = now_ms();
+  rsi_track_stats S;
+  memset(&S, 0, sizeof(S));
+  if (stats) *stats = S;
+  const int name_len = rsitrack::name_length(chrom);
+  if (name_len < 0) return fail(ctx, RSI_ERR_BAD_ARG, "bin track: the name must have 1 to 255 bytes and no tab or newline");
+  if (which != 0 && which != 1) return fail(ctx, RSI_ERR_BAD_ARG, "bin track: which must be 0 (bin median) or 1 (ratio to the chromosome's median)");
+  if (which == 1 && median2 <= 0) return fail(ctx, RSI_ERR_BAD_ARG, "bin track: the chromosome's median is 0: no ratio");
+  const int nreg = (int)cbreak.size();
+  rsitrack::BinPlan plan;
+  if (m < 1 || !rsitrack::bin_plan(name_len, n, nb, nreg, which, slice_bins, plan)) return fail(ctx, RSI_ERR_BAD_ARG, "bin track: bad bin count, bin size or region count");
+  if (nb > (n - cum.back()) / m) return fail(ctx, RSI_ERR_BAD_ARG, "bin track: more bins than the kept bases hold");
+  S.n = nb;
+  if (nb == 0) { if (stats) *stats = S; return RSI_OK; }
+  if (!d_v) return fail(ctx, RSI_ERR_BAD_ARG, "bin track: no values");
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!ctx_enter(ctx)) return RSI_ERR_HIP;
+  const TrackLayout L = track_layout(plan.text_cap, plan.max_pieces, plan.slice, plan.max_pieces, (size_t)2 * nreg + 1);
+  int rc = track_ensure(ctx, plan.text_cap, L);
+  if (rc != RSI_OK) return rc;
+  rsi_ctx::TrackWs& w = ctx->track;
+  char* d_text = static_cast<char*>(w.dev) + L.text;
+  unsigned long long* d_pieces = reinterpret_cast<unsigned long long*>(static_cast<char*>(w.dev) + L.starts);
+  unsigned int* d_tiles = reinterpret_cast<unsigned int*>(static_cast<char*>(w.dev) + L.tiles);
+  unsigned int* d_ltiles = reinterpret_cast<unsigned int*>(static_cast<char*>(w.dev) + L.ltiles);
+  TrackState* d_st = reinterpret_cast<TrackState*>(static_cast<char*>(w.dev) + L.state);
+  long long* d_cbreak = reinterpret_cast<long long*>(static_cast<char*>(w.dev) + L.table);
+  long long* d_cum = d_cbreak + nreg;
+  TrackName name;
+  memset(&name, 0, sizeof(name));
+  memcpy(name.s, chrom, (size_t)name_len);
+  name.len = name_len;
+  hipStream_t st = ctx->stream;
+
+  // the region table, once per call: cbreak[nreg] | cum[nreg + 1] (`table` outlives every wait of track_slices)
+  std::vector<int64_t> table(cbreak);
+  table.insert(table.end(), cum.begin(), cum.end());
+  const hipError_t e = hipMemcpyAsync(d_cbreak, table.data(), table.size() * 8, hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) { (void)ctx_sync(ctx); return fail(ctx, RSI_ERR_HIP, std::string("bin track: hipMemcpyAsync: ") + hipGetErrorString(e)); }
+  BinTrackSource src{d_v, d_pieces, d_cbreak, d_cum, nreg, m, 0, which, median2};
+  rc = track_slices(ctx, nb, plan.slice, plan.text_cap, plan.max_line, d_st, d_text, sink, S,
+      [&](int64_t b, int64_t end) {
+        src.b0 = b;
+        launch_bintrack_pieces(d_cbreak, d_cum, nreg, m, b, end, d_tiles, d_pieces, plan.max_pieces, d_st, st);
+        launch_bintrack_line_bytes(src, d_st, name_len, end - b + nreg, d_ltiles, st);
+      },
+      [&](int64_t b, int64_t end) { return end - b + nreg; },
+      [&](int64_t b, int64_t nlines) { src.b0 = b; launch_bintrack_format(src, d_ltiles, nlines, name, d_text, plan.text_cap, st); });
+  if (rc != RSI_OK) return rc;
+  S.t_total_ms = now_ms() - t_begin;
+  if (stats) *stats = S;
+  return RSI_OK;
 }
 
 }  // namespace
@@ -217,6 +302,56 @@ int64_t rsi_hot_debug_track(rsi_ctx* ctx, const int32_t* values, int64_t n, cons
   TrackSink sink;
   sink.text = &text;
   const int rc = track_run(ctx, ctx->in_depth.as<int32_t>(), n, chrom, pos0, slice_bases, sink, stats);
+  if (rc != RSI_OK) return rc;
+  if (out && (int64_t)text.size() <= cap) memcpy(out, text.data(), text.size());
+  return (int64_t)text.size();
+}
+
+int rsi_hot_write_bin_track(rsi_ctx* ctx, int which, const char* chrom, const char* path, int append, rsi_track_stats* stats) {
+  if (!ctx) return fail(ctx, RSI_ERR_BAD_ARG, "null context");
+  if (which != 0 && which != 1) return fail(ctx, RSI_ERR_BAD_ARG, "bin track: which must be 0 (bin median) or 1 (ratio to the chromosome's median)");
+  if (ctx->run_m <= 0) return fail(ctx, RSI_ERR_BAD_ARG, "bin track: this context holds no successful run");
+  if (!path || !path[0]) return fail(ctx, RSI_ERR_BAD_ARG, "bin track: no path");
+  if (rsitrack::name_length(chrom) < 0) return fail(ctx, RSI_ERR_BAD_ARG, "bin track: the name must have 1 to 255 bytes and no tab or newline");
+  int64_t median2 = 0, ncompact = 0;
+  if (!rsitrack::twice_median(ctx->run_rdmedian, median2)) return fail(ctx, RSI_ERR_INTERNAL, "bin track: the chromosome's median is no multiple of 0.5");
+  if (which == 1 && median2 == 0) return fail(ctx, RSI_ERR_BAD_ARG, "bin track: the chromosome's median is 0: no ratio");
+  std::vector<int64_t> cbreak, cum;
+  if (!rsitrack::bin_table(ctx->noncode_pairs.data(), (int)(ctx->noncode_pairs.size() / 2), ctx->n, cbreak, cum, ncompact) || ncompact != ctx->ncompact)
+    return fail(ctx, RSI_ERR_INTERNAL, "bin track: the run's removed regions do not give its compacted length");
+  TrackSink sink;
+  sink.fd = ::open(path, O_WRONLY | O_CREAT | (append ? O_APPEND : O_TRUNC), 0644);
+  if (sink.fd < 0) return fail(ctx, RSI_ERR_INTERNAL, std::string("bin track: cannot open ") + path + ": " + strerror(errno));
+  int rc = bin_track_run(ctx, ctx->binmed.as<int32_t>(), ctx->nb, ctx->run_m, ctx->n, cbreak, cum, median2, which, chrom, 0, sink, stats);
+  if (::close(sink.fd) != 0 && rc == RSI_OK) rc = fail(ctx, RSI_ERR_INTERNAL, std::string("bin track: write failed: ") + strerror(errno));
+  return rc;
+}
+
+int64_t rsi_hot_debug_bin_track(rsi_ctx* ctx, const int32_t* values, int64_t nb, int m, int64_t n, const int32_t* pairs, int npairs,
+                                int64_t median2, int which, const char* chrom, int64_t slice_bins, char* out, int64_t cap,
+                                rsi_track_stats* stats) {
+  if (!ctx) return fail(ctx, RSI_ERR_BAD_ARG, "null context");
+  if (nb < 0 || nb >= (1ll << 31) || (nb > 0 && !values) || m < 1 || n < 0 || slice_bins < 0 || median2 < 0 || median2 > (1ll << 33))
+    return fail(ctx, RSI_ERR_BAD_ARG, "bin track: bad argument");
+  if (npairs < 0 || npairs > kMaxRegions) return fail(ctx, RSI_ERR_BAD_ARG, "bin track: more than 4096 regions");
+  std::vector<int64_t> cbreak, cum;
+  int64_t ncompact = 0;
+  if (!rsitrack::bin_table(pairs, npairs, n, cbreak, cum, ncompact))
+    return fail(ctx, RSI_ERR_BAD_ARG, "bin track: regions must be sorted, inside [0, n) and apart by at least one kept base");
+  if (nb > 0) {
+    HIPCHK(hipSetDevice(ctx->device));
+    if (!ctx_enter(ctx)) return RSI_ERR_HIP;
+    ctx->run_m = 0;   // the last run's bin medians are about to be overwritten
+    ctx->nb = 0;
+    HIPCHK(ctx->binmed.ensure((size_t)nb * 4));
+    HIPCHK(hipMemcpyAsync(ctx->binmed.p, values, (size_t)nb * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(CTX_SYNC());   // the caller's array is pageable: free again once this returns
+    ctx->nb = nb;
+  }
+  std::string text;
+  TrackSink sink;
+  sink.text = &text;
+  const int rc = bin_track_run(ctx, ctx->binmed.as<int32_t>(), nb, m, n, cbreak, cum, median2, which, chrom, slice_bins, sink, stats);
   if (rc != RSI_OK) return rc;
   if (out && (int64_t)text.size() <= cap) memcpy(out, text.data(), text.size());
   return (int64_t)text.size();

@@ -1,4 +1,4 @@
-// track_host.h -- the host side of the depth-track writer that needs no device: name validation, the slice plan, write()
+// track_host.h -- the host side of the depth-track and bin-track writers that needs no device: name validation, the slice plans, write()
 // until everything is out, and the command line's part files.  Plain C++ (librsi_hot.so and cli.cpp include it; tests/sanitize_track
 // builds it alone under ASan + UBSan).
 #pragma once
@@ -54,6 +54,61 @@ inline bool plan(int name_len, int64_t pos0, int64_t n, int64_t slice_bases, Pla
   s = std::max<int64_t>(1, std::min(s, n));
   p.slice = s;
   p.text_cap = (s + 1) * p.max_line;
+  return true;
+}
+
+// ---- the per-bin track: slices are ranges of bins ----
+constexpr int kMaxBinRegions = 4096;   // removed regions of a chromosome (the pipeline's kMaxRegions)
+constexpr int kMedianBytes = 11;       // a value as long as INT32_MIN
+constexpr int kRatioBytes = 18;        // the largest q / 1000 with its point and three places
+static_assert(kTextBytes / (kMaxName + 4 + 2 * 20 + kRatioBytes) > kMaxBinRegions + 1, "one bin and every region's cut fit the text buffer");
+static_assert(kSliceBases > kMaxBinRegions, "one bin and every region's cut fit the pieces");
+
+struct BinPlan {
+  int64_t slice;       // bins per slice
+  int64_t max_line;    // bytes of the longest line this call can write
+  int64_t max_pieces;  // lines a slice can have: slice + nreg (every break cuts at most one bin)
+  int64_t text_cap;    // max_pieces * max_line <= kTextBytes
+};
+// Bins of a chromosome of n bases with nreg removed regions; which: 0 = median, 1 = ratio.  false: n < 0, nb < 0, nreg outside
+// [0, kMaxBinRegions] or which outside 0 and 1.  slice_bins > 0 asks for that slice length (tests); the bounds hold all the same:
+// max_pieces <= kSliceBases + 1 (the depth track's starts workspace) and text_cap <= kTextBytes, with at least one bin a slice.
+inline bool bin_plan(int name_len, int64_t n, int64_t nb, int nreg, int which, int64_t slice_bins, BinPlan& p) {
+  if (n < 0 || nb < 0 || nreg < 0 || nreg > kMaxBinRegions || (which != 0 && which != 1)) return false;
+  p.max_line = (int64_t)name_len + 4 + 2 * dec_len(n) + (which == 1 ? kRatioBytes : kMedianBytes);   // coordinates run from 0 to n
+  int64_t s = slice_bins > 0 ? std::min(slice_bins, kSliceBases) : kSliceBases;
+  s = std::min(s, kSliceBases + 1 - nreg);
+  s = std::min(s, kTextBytes / p.max_line - nreg);
+  s = std::max<int64_t>(1, std::min(s, nb));
+  p.slice = s;
+  p.max_pieces = s + nreg;
+  p.text_cap = p.max_pieces * p.max_line;
+  return true;
+}
+
+// npairs inclusive [start, end] pairs -> cbreak[k]: compacted index at which region k is cut out; cum[k]: bases removed in front
+// of region k (cum[npairs]: in all) -- rsih::compact_table's table.  false: a region outside [0, n), empty, out of order, or
+// touching the one before (at least one kept base lies between two regions).
+inline bool bin_table(const int32_t* pairs, int npairs, int64_t n, std::vector<int64_t>& cbreak, std::vector<int64_t>& cum, int64_t& ncompact) {
+  if (npairs < 0 || n < 0 || (npairs > 0 && !pairs)) return false;
+  cbreak.assign((size_t)npairs, 0);
+  cum.assign((size_t)npairs + 1, 0);
+  for (int k = 0; k < npairs; ++k) {
+    const int64_t a = pairs[2 * k], b = pairs[2 * k + 1];
+    if (a < 0 || b < a || b >= n) return false;
+    if (k > 0 && a <= (int64_t)pairs[2 * k - 1] + 1) return false;
+    cbreak[(size_t)k] = a - cum[(size_t)k];
+    cum[(size_t)k + 1] = cum[(size_t)k] + (b - a + 1);
+  }
+  ncompact = n - cum.back();
+  return true;
+}
+
+// Twice a chromosome's median as an integer (the median of integers is a multiple of 0.5); false: it is not one, or out of range
+inline bool twice_median(double median, int64_t& m2) {
+  const double d = 2.0 * median;
+  if (!(d >= 0.0) || d > 8589934592.0 || d != (double)(int64_t)d) return false;
+  m2 = (int64_t)d;
   return true;
 }
 

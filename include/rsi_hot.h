@@ -342,6 +342,34 @@ int64_t rsi_hot_debug_bin_track(rsi_ctx* ctx, const int32_t* values, int64_t nb,
                                 int64_t median2, int which, const char* chrom, int64_t slice_bins, char* out, int64_t cap,
                                 rsi_track_stats* stats);
 
+/* ---- BGZF tracks: the writers' text deflated on the device ------------------------------------------------------
+ * With the format set to RSI_TRACK_BGZF, rsi_hot_write_track, _write_track_device, rsi_hot_write_bin_track and the two test hooks
+ * (rsi_hot_debug_track, rsi_hot_debug_bin_track: their out[] then holds the BGZF bytes, their return value is that length) write
+ * what `bgzip` makes of the text: a sequence of BGZF members, each holding at most 65280 bytes of text (members are cut per
+ * slice, so a slice's last member may be short), deflated with dynamic Huffman codes or, where that would not be shorter,
+ * stored.  The bytes depend on the text alone.  Only the compressed bytes cross PCIe.  rsi_track_stats goes on counting text
+ * (bytes, lines); the compressed side is in rsi_deflate_stats.  The writers write members only: a file is complete once
+ * rsi_bgzf_write_eof has appended the end-of-file block -- once, after the last chromosome appended to it.  Every reader of
+ * this library (-d FILE.bedgraph.gz, rsi_genome_bedgraph_open) takes the file back, inflating it on the device. */
+enum { RSI_TRACK_TEXT = 0, RSI_TRACK_BGZF = 1 };
+/* The format of this context's track calls from now on (RSI_TRACK_TEXT when never called); any other value is RSI_ERR_BAD_ARG. */
+int rsi_hot_set_track_format(rsi_ctx* ctx, int format);
+typedef struct rsi_deflate_stats {
+  int64_t members;          /* BGZF members written */
+  int64_t stored_members;   /* those that are one stored block (text that does not compress) */
+  int64_t text_bytes;       /* bytes of text they hold */
+  int64_t file_bytes;       /* their bytes in the file (no end-of-file block) */
+  double t_kernel_ms;       /* summed HIP-event time of the deflate and pack launches */
+} rsi_deflate_stats;
+/* The figures of the context's last track call or rsi_hot_debug_deflate (all zero after a plain-text one). */
+int rsi_hot_last_deflate_stats(const rsi_ctx* ctx, rsi_deflate_stats* out);
+/* Appends the 28-byte BGZF end-of-file block to `path` (created when missing).  RSI_ERR_INTERNAL when that fails. */
+int rsi_bgzf_write_eof(const char* path);
+/* Test hook for the two kernels alone: text[len] (any bytes) uploaded, cut into members of 65280 bytes, deflated and packed;
+ * the BGZF bytes (no end-of-file block) into out[cap].  Returns their length (also when out == NULL or cap is too small,
+ * writing nothing then; 0 for len == 0), < 0 on error. */
+int64_t rsi_hot_debug_deflate(rsi_ctx* ctx, const uint8_t* text, int64_t len, uint8_t* out, int64_t cap, rsi_deflate_stats* stats);
+
 /* Results.  which: 0 = calls after sd_filters (what write_cnv_to_file prints),
  *                  1 = detectcnv output before sd_filters,
  *                  2 = bin-space segments after the scan (rsicnvnbn / rsicnvmed output),

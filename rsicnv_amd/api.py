@@ -4,6 +4,7 @@ per-chromosome hot path (rsi.cpp:2189-2212).
 The library is the product: there is no Python or CPU fallback.  `load_library()` raises if the
 shared object is missing, and `RsiHot()` raises if no HIP device can be opened.
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -63,7 +64,8 @@ EXPORTS = ["rsi_default_params", "rsi_hot_create", "rsi_hot_destroy", "rsi_hot_l
            "rsi_genome_bedgraph_open", "rsi_synth_append_genome_bedgraph",
            "rsi_hot_set_exclude", "rsi_exclude_read_bed", "rsi_hot_debug_classify", "rsi_hot_debug_per_base",
            "rsi_hot_write_track", "rsi_hot_write_track_device", "rsi_hot_debug_track",
-           "rsi_hot_write_bin_track", "rsi_hot_debug_bin_track"]
+           "rsi_hot_write_bin_track", "rsi_hot_debug_bin_track",
+           "rsi_hot_set_track_format", "rsi_hot_last_deflate_stats", "rsi_bgzf_write_eof", "rsi_hot_debug_deflate"]
 
 
 class RsiParams(C.Structure):
@@ -109,7 +111,13 @@ class RsiTrackStats(C.Structure):
                 ("t_total_ms", C.c_double), ("t_kernel_ms", C.c_double), ("t_write_ms", C.c_double)]
 
 
+class RsiDeflateStats(C.Structure):
+    _fields_ = [("members", C.c_int64), ("stored_members", C.c_int64), ("text_bytes", C.c_int64), ("file_bytes", C.c_int64),
+                ("t_kernel_ms", C.c_double)]
+
+
 INFLATE_FORMATS = {0: "text", 1: "bgzf", 2: "gzip"}
+TRACK_FORMATS = {"text": 0, "bgzf": 1}
 
 
 def _inflate_dict(st):
@@ -260,6 +268,11 @@ def load_library():
     L.rsi_hot_debug_bin_track.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_int,
                                           C.c_char_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(RsiTrackStats)]
     L.rsi_hot_debug_bin_track.restype = C.c_int64
+    L.rsi_hot_set_track_format.argtypes = [C.c_void_p, C.c_int]
+    L.rsi_hot_last_deflate_stats.argtypes = [C.c_void_p, C.POINTER(RsiDeflateStats)]
+    L.rsi_bgzf_write_eof.argtypes = [C.c_char_p]
+    L.rsi_hot_debug_deflate.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(RsiDeflateStats)]
+    L.rsi_hot_debug_deflate.restype = C.c_int64
     _lib = L
     return L
 
@@ -293,6 +306,15 @@ def read_exclude_bed(path, chrom, n):
         raise RsiError(k2, lib.rsi_hot_last_error(None).decode())
     k = min(k, k2)
     return np.stack([s[:k], e[:k]], axis=1)
+
+
+def bgzf_write_eof(path):
+    """Ends a BGZF track: appends the 28-byte end-of-file block to `path` (rsi_bgzf_write_eof; host only) -- once, after the
+    last chromosome appended to it."""
+    lib = load_library()
+    k = lib.rsi_bgzf_write_eof(os.fsencode(path))
+    if k < 0:
+        raise RsiError(k, lib.rsi_hot_last_error(None).decode())
 
 
 class RsiError(RuntimeError):
@@ -611,30 +633,79 @@ class RsiHot:
     def _name_bytes(chrom):
         return chrom if isinstance(chrom, bytes) else chrom.encode()
 
-    def write_track(self, which, chrom, path, append=False):
+    def set_track_format(self, format):
+        """The format of this context's track calls from now on (rsi_hot_set_track_format): "text" / 0 or "bgzf" / 1."""
+        f = TRACK_FORMATS.get(format, format)
+        if isinstance(f, str):
+            raise ValueError("track format: 'text' or 'bgzf'")
+        self._check(self.lib.rsi_hot_set_track_format(self.ctx, int(f)))
+        self._track_format = int(f)
+
+    @contextlib.contextmanager
+    def _track_format_for(self, format):
+        """format=None: the context's setting; else that format for one call, the setting as it was afterwards."""
+        before = getattr(self, "_track_format", 0)
+        if format is not None:
+            self.set_track_format(format)
+        try:
+            yield
+        finally:
+            if format is not None:
+                self.set_track_format(before)
+
+    def deflate_stats(self):
+        """The compressed side of the last track call or debug_deflate (rsi_hot_last_deflate_stats): members, stored_members,
+        text_bytes, file_bytes (no end-of-file block), t_kernel_ms of the deflate and pack launches; zeros after a text call."""
+        st = RsiDeflateStats()
+        self._check(self.lib.rsi_hot_last_deflate_stats(self.ctx, C.byref(st)))
+        return {f[0]: getattr(st, f[0]) for f in RsiDeflateStats._fields_}
+
+    def debug_deflate(self, text):
+        """`text` (any bytes) as BGZF members of 65280 text bytes through the deflate and pack kernels alone (test hook,
+        rsi_hot_debug_deflate): (bytes, stats).  No end-of-file block."""
+        t = np.frombuffer(bytes(text), dtype=np.uint8)
+        cap = t.size + 31 * (t.size // 65280 + 1)
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        st = RsiDeflateStats()
+        k = self.lib.rsi_hot_debug_deflate(self.ctx, t.ctypes.data if t.size else None, t.size, out.ctypes.data, cap, C.byref(st))
+        if k < 0:
+            self._check(int(k))
+        if k > cap:
+            raise RsiError(-6, "deflate: more bytes than stored members take")
+        return out[:k].tobytes(), {f[0]: getattr(st, f[0]) for f in RsiDeflateStats._fields_}
+
+    def write_track(self, which, chrom, path, append=False, format=None):
         """The last run's depth as bedGraph lines of `chrom` (rsi_hot_write_track), replacing `path` or appended to it.
         which: 0 / "raw" = the depth the run read, 1 / "gc" = the GC-adjusted depth (fetch("rd_gc"); RsiError after a
-        -NOGC run).  Returns the statistics (RsiTrackStats) as a dict."""
+        -NOGC run).  format: "text" or "bgzf" for this call (None: the context's setting, set_track_format); a BGZF file is
+        complete once bgzf_write_eof(path) has ended it.  Returns the statistics (RsiTrackStats) as a dict."""
         st = RsiTrackStats()
         w = self.TRACK_DEPTHS.get(which, which)
-        self._check(self.lib.rsi_hot_write_track(self.ctx, int(w), self._name_bytes(chrom), os.fsencode(path), int(bool(append)), C.byref(st)))
+        with self._track_format_for(format):
+            self._check(self.lib.rsi_hot_write_track(self.ctx, int(w), self._name_bytes(chrom), os.fsencode(path), int(bool(append)), C.byref(st)))
         return {f[0]: getattr(st, f[0]) for f in RsiTrackStats._fields_}
 
-    def write_track_device(self, d_values_ptr, n, chrom, path, append=False):
+    def write_track_device(self, d_values_ptr, n, chrom, path, append=False, format=None):
         """Any int32[n] in HBM (a raw device pointer) as bedGraph lines of `chrom` (rsi_hot_write_track_device)."""
         st = RsiTrackStats()
-        self._check(self.lib.rsi_hot_write_track_device(self.ctx, C.c_void_p(d_values_ptr), int(n), self._name_bytes(chrom), os.fsencode(path),
-                                                        int(bool(append)), C.byref(st)))
+        with self._track_format_for(format):
+            self._check(self.lib.rsi_hot_write_track_device(self.ctx, C.c_void_p(d_values_ptr), int(n), self._name_bytes(chrom), os.fsencode(path),
+                                                            int(bool(append)), C.byref(st)))
         return {f[0]: getattr(st, f[0]) for f in RsiTrackStats._fields_}
 
-    def debug_track(self, values, chrom, pos0=0, slice_bases=0):
+    def debug_track(self, values, chrom, pos0=0, slice_bases=0, format=None):
         """The bedGraph text of a host int32 array through the device's track writer (test hook, rsi_hot_debug_track):
-        (bytes, stats).  pos0: added to every coordinate; slice_bases > 0: the slice length to work in."""
+        (bytes, stats).  pos0: added to every coordinate; slice_bases > 0: the slice length to work in.  With the format
+        "bgzf" the bytes are the BGZF members of that text."""
+        with self._track_format_for(format):
+            return self._debug_track(values, chrom, pos0, slice_bases)
+
+    def _debug_track(self, values, chrom, pos0, slice_bases):
         v = np.ascontiguousarray(values, dtype=np.int32)
         name = self._name_bytes(chrom)
         # room for every line at its longest; the call says when that was not enough
         lines = (int(np.count_nonzero(v[1:] != v[:-1])) + 1) if v.size else 0
-        cap = lines * (len(name) + 4 + 2 * 20 + 11)
+        cap = lines * (len(name) + 4 + 2 * 20 + 11) + 64   # (a member's frame around a short text)
         st = RsiTrackStats()
         for _ in range(2):
             out = np.zeros(max(cap, 1), dtype=np.uint8)
@@ -649,23 +720,28 @@ class RsiHot:
 
     BIN_TRACK_VALUES = {"median": 0, "ratio": 1}
 
-    def write_bin_track(self, which, chrom, path, append=False):
+    def write_bin_track(self, which, chrom, path, append=False, format=None):
         """The last run's bins as bedGraph lines of `chrom` (rsi_hot_write_bin_track), replacing `path` or appended to it.
         which: 0 / "median" = every bin's median, 1 / "ratio" = the median over the chromosome's median, three decimals.
         Returns the statistics (RsiTrackStats, n = the number of bins) as a dict."""
         st = RsiTrackStats()
         w = self.BIN_TRACK_VALUES.get(which, which)
-        self._check(self.lib.rsi_hot_write_bin_track(self.ctx, int(w), self._name_bytes(chrom), os.fsencode(path), int(bool(append)), C.byref(st)))
+        with self._track_format_for(format):
+            self._check(self.lib.rsi_hot_write_bin_track(self.ctx, int(w), self._name_bytes(chrom), os.fsencode(path), int(bool(append)), C.byref(st)))
         return {f[0]: getattr(st, f[0]) for f in RsiTrackStats._fields_}
 
-    def debug_bin_track(self, values, m, n, pairs, median2, which, name, slice_bins=0):
+    def debug_bin_track(self, values, m, n, pairs, median2, which, name, slice_bins=0, format=None):
         """The bin track of host values[nb] (bins of m compacted bases of a chromosome of n bases whose removed regions are the
         inclusive (start, end) `pairs`) through the device's writer (test hook, rsi_hot_debug_bin_track): (bytes, stats)."""
+        with self._track_format_for(format):
+            return self._debug_bin_track(values, m, n, pairs, median2, which, name, slice_bins)
+
+    def _debug_bin_track(self, values, m, n, pairs, median2, which, name, slice_bins):
         v = np.ascontiguousarray(values, dtype=np.int32)
         pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1)
         nm = self._name_bytes(name)
         w = self.BIN_TRACK_VALUES.get(which, which)
-        cap = (v.size + pr.size // 2) * (len(nm) + 4 + 2 * 20 + 18)   # room for every piece at its longest
+        cap = (v.size + pr.size // 2) * (len(nm) + 4 + 2 * 20 + 18) + 64   # room for every piece at its longest (and a member's frame)
         st = RsiTrackStats()
         out = np.zeros(max(cap, 1), dtype=np.uint8)
         k = self.lib.rsi_hot_debug_bin_track(self.ctx, v.ctypes.data if v.size else None, v.size, int(m), int(n),

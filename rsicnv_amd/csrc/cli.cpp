@@ -56,6 +56,8 @@ struct Options {
   std::string trackdepth = "raw";   // -trackdepth raw|gc: the depth as read, or after the GC adjustment
   std::string bintrackfile;  // -bintrack FILE: one value per bin of every called chromosome as bedGraph (with -samples: FILE.k per column k)
   std::string bintrackvalue = "ratio";   // -bintrackvalue ratio|median: the bin's median over the chromosome's, or the median itself
+  std::string trackformat;   // -trackformat text|bgzf: both tracks as text or as BGZF, whatever their names (empty: by the name)
+  bool track_bgzf = false, bintrack_bgzf = false;   // what the rule gives -track's and -bintrack's FILE (main sets them)
 };
 
 int usage() {
@@ -84,6 +86,7 @@ int usage() {
             << "   -trackdepth raw|gc  the depth -track saves: as read (default), or GC-adjusted (what the calls are made from)\n"
             << "   -bintrack FILE  save one value per bin of every called chromosome as bedGraph, see below\n"
             << "   -bintrackvalue ratio|median  the value -bintrack saves: the bin's median over the chromosome's (default), or the median\n"
+            << "   -trackformat text|bgzf  -track and -bintrack as plain text or as BGZF (default: BGZF when FILE ends in .gz or .bgz)\n"
             << "\nNote:\n"
             << "   This build runs the read-depth hot path on an MI355X; input is a read depth file\n"
             << "   (samtools mpileup BAM | cut -f2,4) with -c RNAME, a whole-genome depth file without -c\n"
@@ -116,6 +119,10 @@ int usage() {
             << "   covers a removed base; the bases behind the last whole bin get no line.  Chromosomes in the order of the output\n"
             << "   rows; formatted on the GPU.  Works with every input but -gpus above 1, and beside -track; with -samples it writes\n"
             << "   FILE.k per column k.\n"
+            << "   A track whose FILE ends in .gz or .bgz (in any case; with -samples the FILE given, not FILE.k) is written as BGZF,\n"
+            << "   what bgzip makes of the text: the text is deflated on the GPU in members of 65280 bytes and the file ends with the\n"
+            << "   end-of-file block, so tabix, IGV and bedtools take it and -d FILE.bedgraph.gz reads it back.  -trackformat text or\n"
+            << "   bgzf decides for both tracks whatever their names.\n"
             << std::endl;
   return 0;
 }
@@ -173,6 +180,7 @@ void parse(int argc, char** argv, Options& o) {
     else if (s == "-trackdepth") { o.trackdepth = need(i); ++i; }
     else if (s == "-bintrack") { o.bintrackfile = need(i); ++i; }
     else if (s == "-bintrackvalue") { o.bintrackvalue = need(i); ++i; }
+    else if (s == "-trackformat") { o.trackformat = need(i); ++i; }
     else { std::cerr << "unknown option " << s << std::endl; exit(usage()); }
   }
   if (o.rdfile.empty() && o.bamfile.empty()) { std::cerr << "need input file " << std::endl; exit(usage()); }
@@ -315,7 +323,8 @@ void report_chromosome(rsi_ctx* ctx, const Options& o, const std::string& chr, r
   if (!o.trackfile.empty()) {   // -track: this chromosome's lines into its part file, from the depth the context still holds
     rsi_track_stats tk;
     const std::string part = rsitrack::part_path(o.trackfile, co.track_index);
-    if (rsi_hot_write_track(ctx, o.trackdepth == "gc" ? 1 : 0, chr.c_str(), part.c_str(), 0, &tk) != RSI_OK) {
+    if (rsi_hot_set_track_format(ctx, o.track_bgzf ? RSI_TRACK_BGZF : RSI_TRACK_TEXT) != RSI_OK ||
+        rsi_hot_write_track(ctx, o.trackdepth == "gc" ? 1 : 0, chr.c_str(), part.c_str(), 0, &tk) != RSI_OK) {
       info << "track: " << chr << ": " << rsi_hot_last_error(ctx) << "\n";
       co.track_failed = true;
     } else {
@@ -326,7 +335,8 @@ void report_chromosome(rsi_ctx* ctx, const Options& o, const std::string& chr, r
   if (!o.bintrackfile.empty()) {   // -bintrack: this chromosome's bins into their part file, while the context still holds the run
     rsi_track_stats tk;
     const std::string part = rsitrack::part_path(o.bintrackfile, co.track_index);
-    if (rsi_hot_write_bin_track(ctx, o.bintrackvalue == "median" ? 0 : 1, chr.c_str(), part.c_str(), 0, &tk) != RSI_OK) {
+    if (rsi_hot_set_track_format(ctx, o.bintrack_bgzf ? RSI_TRACK_BGZF : RSI_TRACK_TEXT) != RSI_OK ||
+        rsi_hot_write_bin_track(ctx, o.bintrackvalue == "median" ? 0 : 1, chr.c_str(), part.c_str(), 0, &tk) != RSI_OK) {
       info << "bintrack: " << chr << ": " << rsi_hot_last_error(ctx) << "\n";
       co.bintrack_failed = true;
     } else {
@@ -455,6 +465,14 @@ bool is_bedgraph_name(const std::string& path) {
   if (ends(".gz")) n.resize(n.size() - 3);
   else if (ends(".bgz")) n.resize(n.size() - 4);
   return ends(".bed") || ends(".bedgraph") || ends(".bg");
+}
+
+// A track is BGZF by name: it ends in .gz or .bgz (case-insensitive), the suffixes is_bedgraph_name looks behind
+bool gz_name(const std::string& path) {
+  std::string n = path.substr(path.find_last_of('/') == std::string::npos ? 0 : path.find_last_of('/') + 1);
+  std::transform(n.begin(), n.end(), n.begin(), [](unsigned char c) { return (char)std::tolower(c); });
+  auto ends = [&](const char* x) { const size_t k = strlen(x); return n.size() > k && n.compare(n.size() - k, k, x) == 0; };
+  return ends(".gz") || ends(".bgz");
 }
 
 // The .fai's names and lengths, in its order (read_fasta's index, readref.cpp:10-86)
@@ -668,8 +686,8 @@ bool select_samples(const Options& o, std::vector<int32_t>& cols, std::vector<st
 
 // -track and -bintrack (`what`: "track" / "bin track", `flag`: the option), after the run: the parts of the chromosomes whose rows
 // were written (`order`, in row order) become FILE; every part 0 .. count - 1 is deleted whatever happened.  failed: a
-// chromosome's part could not be written -- then there is no FILE.
-bool finish_track(const std::string& file, const std::vector<size_t>& order, size_t count, bool failed, std::ostream& log,
+// chromosome's part could not be written -- then there is no FILE.  bgzf: the parts are BGZF members; the end-of-file block ends FILE.
+bool finish_track(const std::string& file, const std::vector<size_t>& order, size_t count, bool failed, bool bgzf, std::ostream& log,
                   const char* what = "track", const char* flag = "-track") {
   if (file.empty()) return true;
   std::string err;
@@ -677,7 +695,7 @@ bool finish_track(const std::string& file, const std::vector<size_t>& order, siz
     rsitrack::remove_parts(file, count);
     remove(file.c_str());
     err = std::string("a chromosome's ") + what + " could not be written (see above)";
-  } else if (rsitrack::join_parts(file, order, count, err)) {
+  } else if (rsitrack::join_parts(file, order, count, err, bgzf)) {
     std::cerr << what << " written to " << file << std::endl; log << what << " written to " << file << std::endl;
     return true;
   }
@@ -687,8 +705,8 @@ bool finish_track(const std::string& file, const std::vector<size_t>& order, siz
 // both kinds of track of one output: every part is dealt with, whichever fails
 bool finish_tracks(const Options& o, const std::string& suffix, const std::vector<size_t>& order, size_t count, bool track_failed,
                    bool bintrack_failed, std::ostream& log) {
-  const bool a = finish_track(o.trackfile.empty() ? "" : o.trackfile + suffix, order, count, track_failed, log);
-  const bool b = finish_track(o.bintrackfile.empty() ? "" : o.bintrackfile + suffix, order, count, bintrack_failed, log, "bin track", "-bintrack");
+  const bool a = finish_track(o.trackfile.empty() ? "" : o.trackfile + suffix, order, count, track_failed, o.track_bgzf, log);
+  const bool b = finish_track(o.bintrackfile.empty() ? "" : o.bintrackfile + suffix, order, count, bintrack_failed, o.bintrack_bgzf, log, "bin track", "-bintrack");
   return a && b;
 }
 
@@ -732,6 +750,13 @@ int main(int argc, char** argv) {
     std::cerr << "rsicnv: -trackdepth " << o.trackdepth << ": expected raw or gc" << std::endl;
     return 1;
   }
+  if (!o.trackformat.empty() && o.trackformat != "text" && o.trackformat != "bgzf") {
+    std::cerr << "rsicnv: -trackformat " << o.trackformat << ": expected text or bgzf" << std::endl;
+    return 1;
+  }
+  // BGZF by the name as -d takes it (.gz / .bgz, in any case) -- the FILE given, before -samples adds .k -- unless -trackformat says
+  o.track_bgzf = o.trackformat.empty() ? gz_name(o.trackfile) : o.trackformat == "bgzf";
+  o.bintrack_bgzf = o.trackformat.empty() ? gz_name(o.bintrackfile) : o.trackformat == "bgzf";
   if (!o.trackfile.empty()) {
     if (o.gpus > 1) { std::cerr << "rsicnv: -track: not with -gpus above 1 (the track is written by one device: -gpu INT picks it)" << std::endl; return 1; }
     if (o.trackdepth == "gc" && !o.P.gcadjust) { std::cerr << "rsicnv: -trackdepth gc: -NOGC leaves no GC-adjusted depth to save" << std::endl; return 1; }

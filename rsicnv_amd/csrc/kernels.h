@@ -550,6 +550,8 @@ struct TrackState {
   long long nstarts;   // entries of starts[] for this slice, the carried one included (the closing n not)
   long long nlines;    // lines this slice writes
   long long nbytes;    // their bytes
+  long long packed;    // BGZF: bytes of the last slice's packed members (k_bgzf_pack; read with the next slice's numbers)
+  long long stored;    // BGZF: how many of them are one stored block
 };
 struct TrackName { char s[256]; int len; };   // the chromosome name, at most 255 bytes, travels with the kernel arguments
 constexpr int kTrackTile = 256;               // bases (passes 1-3) or lines (passes 4-5) per workgroup
@@ -589,5 +591,17 @@ void launch_bintrack_line_bytes(const BinTrackSource& src, TrackState* st, int n
                                 hipStream_t stream);
 void launch_bintrack_format(const BinTrackSource& src, const unsigned int* ltiles, long long nlines, const TrackName& name, char* text,
                             long long cap, hipStream_t stream);
+
+
+// ---- BGZF tracks: a slice's text deflated member by member (kernels_deflate.hip, deflate_core.h) ----
+constexpr unsigned int kDeflateMemberText = 65280;   // text bytes of a member (the last of a slice may hold fewer)
+constexpr unsigned int kDeflateSlotBytes = 65536;    // where a member is left: header, payload, footer from the slot's start
+inline int deflate_members(long long nbytes) { return nbytes <= 0 ? 0 : (int)((nbytes + kDeflateMemberText - 1) / kDeflateMemberText); }
+// text[0, nbytes) (256-byte aligned) -> member k, a whole BGZF member of text[k * 65280 ...], at slots[k * 65536 ...]; sizes[k]: its
+// bytes, bit 31 set when it is one stored block.  The bytes are a function of the text alone.
+void launch_deflate_bgzf(const void* text, long long nbytes, void* slots, unsigned int* sizes, hipStream_t stream);
+// The members back to back in packed[0, cap); st->packed: their bytes (nothing is copied past cap; the sum says so), st->stored.
+void launch_bgzf_pack(const void* slots, const unsigned int* sizes, int nmembers, void* packed, long long cap, TrackState* st,
+                      hipStream_t stream);
 
 }  // namespace rsik

@@ -204,11 +204,13 @@ struct rsi_ctx {
   // than track_host.h's bounds, whatever the chromosome -- and its events (timing around the kernel groups, one behind each
   // pinned buffer's copy).  Freed by rsi_hot_destroy.
   struct TrackWs {
-    void* dev = nullptr; size_t dev_bytes = 0;           // text, starts or pieces, tiles, line tiles, state, the bin track's region table
+    void* dev = nullptr; size_t dev_bytes = 0;           // text, starts or pieces, tiles, line tiles, state, the bin track's region table; BGZF: sizes, slots, packed members
     char* pin[2] = {nullptr, nullptr}; size_t pin_bytes = 0;   // two text buffers: one is written to the file while the other fills
     void* pin_state = nullptr;                           // two TrackState: the device's, read back per slice; the initial one
-    hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t ev[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   } track;
+  int track_format = RSI_TRACK_TEXT;         // rsi_hot_set_track_format
+  rsi_deflate_stats last_deflate{};          // of the last track call (rsi_hot_last_deflate_stats)
 };
 
 namespace rsip {

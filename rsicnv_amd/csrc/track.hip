@@ -1,8 +1,10 @@
 // track.hip -- depth tracks and per-bin tracks as bedGraph (include/rsi_hot.h: rsi_hot_write_track, _write_track_device,
-// rsi_hot_debug_track; rsi_hot_write_bin_track, rsi_hot_debug_bin_track).  The
+// rsi_hot_debug_track; rsi_hot_write_bin_track, rsi_hot_debug_bin_track), as text or as BGZF (rsi_hot_set_track_format).  The
 // host drives kernels_track.hip slice by slice: the passes that find and measure a slice's lines, one wait for their two numbers,
 // the format pass and the copy of exactly those bytes into one of two pinned buffers; while that runs, the slice before goes
-// out through write().  Slice rules, bounds and numbers: DESIGN.md 6f and 6g.
+// out through write().  A BGZF slice is deflated and packed behind its format pass (kernels_deflate.hip) and only the packed
+// members are copied, one slice later: their length comes with the next slice's two numbers.  Slice rules, bounds and numbers:
+// DESIGN.md 6f, 6g and 6h.
 #include "pipeline_internal.h"
 #include "track_host.h"
 
@@ -34,13 +36,20 @@ struct TrackSink {
   }
 };
 
-enum { kEvP0, kEvP1, kEvF0, kEvF1 = kEvF0 + 2, kEvCopy = kEvF1 + 2 };   // events: the measuring passes; per pinned buffer: format begin / end, copy done
+// events: the measuring passes; per pinned buffer: format begin / end, copy done, deflate and pack done
+enum { kEvP0, kEvP1, kEvF0, kEvF1 = kEvF0 + 2, kEvCopy = kEvF1 + 2, kEvD1 = kEvCopy + 2, kEvCount = kEvD1 + 2 };
+static_assert(kEvCount == sizeof(rsi_ctx::TrackWs::ev) / sizeof(hipEvent_t), "one event per use");
 
-struct TrackLayout { size_t text, starts, tiles, ltiles, state, table, bytes; };
+struct TrackLayout {
+  size_t text, starts, tiles, ltiles, state, table, bytes;
+  size_t sizes = 0, slots = 0, packed = 0;   // BGZF only: a size word and a slot per member of a slice, the members packed
+  int64_t packed_cap = 0;
+  size_t pin_bytes = 0;                      // what a slice sends to the host at most
+};
 size_t up256(size_t x) { return (x + 255) & ~size_t(255); }
 // text_cap bytes of text, `entries` 8-byte starts or pieces, tile words for `items` (passes 1-3) and `lines` (passes 4-5),
-// the state, and table_words 8-byte words of a region table
-TrackLayout track_layout(int64_t text_cap, int64_t entries, int64_t items, int64_t lines, size_t table_words) {
+// the state, and table_words 8-byte words of a region table; bgzf: what the members of text_cap bytes of text need on top
+TrackLayout track_layout(int64_t text_cap, int64_t entries, int64_t items, int64_t lines, size_t table_words, bool bgzf) {
   TrackLayout L;
   L.text = 0;
   L.starts = up256((size_t)text_cap);
@@ -49,11 +58,38 @@ TrackLayout track_layout(int64_t text_cap, int64_t entries, int64_t items, int64
   L.state = L.ltiles + up256((size_t)(track_tiles(lines) + 1) * 4);
   L.table = L.state + up256(sizeof(TrackState));
   L.bytes = L.table + up256(table_words * 8);
+  L.pin_bytes = (size_t)text_cap;
+  if (bgzf) {
+    const int64_t members = rsitrack::members_of(text_cap);
+    L.sizes = L.bytes;
+    L.slots = L.sizes + up256((size_t)members * 4);
+    L.packed = L.slots + (size_t)members * rsitrack::kMemberSlot;
+    L.packed_cap = text_cap + members * rsitrack::kMemberOverhead;
+    L.bytes = L.packed + up256((size_t)L.packed_cap);
+    L.pin_bytes = (size_t)L.packed_cap;
+  }
   return L;
 }
-TrackLayout track_layout(const rsitrack::Plan& p) { return track_layout(p.text_cap, p.slice + 2, p.slice, p.slice + 1, 0); }
+TrackLayout track_layout(const rsitrack::Plan& p, bool bgzf) { return track_layout(p.text_cap, p.slice + 2, p.slice, p.slice + 1, 0, bgzf); }
+static_assert(rsitrack::kMemberText == kDeflateMemberText && rsitrack::kMemberSlot == kDeflateSlotBytes, "the host plans the kernels' members");
 
-int track_ensure(rsi_ctx* ctx, int64_t text_cap, const TrackLayout& L) {
+// The compressed side of a call: where the members go on the device, and the figures (null / zero for a plain-text call)
+struct TrackBgzf {
+  unsigned int* sizes = nullptr;
+  char* slots = nullptr;
+  char* packed = nullptr;
+  int64_t packed_cap = 0;
+  rsi_deflate_stats D{};
+  bool on() const { return packed != nullptr; }
+  void place(void* dev, const TrackLayout& L) {
+    sizes = reinterpret_cast<unsigned int*>(static_cast<char*>(dev) + L.sizes);
+    slots = static_cast<char*>(dev) + L.slots;
+    packed = static_cast<char*>(dev) + L.packed;
+    packed_cap = L.packed_cap;
+  }
+};
+
+int track_ensure(rsi_ctx* ctx, const TrackLayout& L) {
   rsi_ctx::TrackWs& w = ctx->track;
   for (hipEvent_t& e : w.ev) if (!e) HIPCHK(hipEventCreate(&e));
   if (!w.pin_state) HIPCHK(hipHostMalloc(&w.pin_state, 2 * sizeof(TrackState), hipHostMallocDefault));
@@ -63,11 +99,11 @@ int track_ensure(rsi_ctx* ctx, int64_t text_cap, const TrackLayout& L) {
     HIPCHK(hipMalloc(&w.dev, L.bytes));
     w.dev_bytes = L.bytes;
   }
-  if ((size_t)text_cap > w.pin_bytes) {
+  if (L.pin_bytes > w.pin_bytes) {
     for (char*& b : w.pin) { if (b) (void)hipHostFree(b); b = nullptr; }
     w.pin_bytes = 0;
-    for (char*& b : w.pin) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&b), (size_t)text_cap, hipHostMallocDefault));
-    w.pin_bytes = (size_t)text_cap;
+    for (char*& b : w.pin) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&b), L.pin_bytes, hipHostMallocDefault));
+    w.pin_bytes = L.pin_bytes;
   }
   return RSI_OK;
 }
@@ -75,10 +111,13 @@ int track_ensure(rsi_ctx* ctx, int64_t text_cap, const TrackLayout& L) {
 // The slices of one call, whatever their lines come from: per slice [b, end) of `count` items, measure(b, end) queues the passes
 // that find and measure its lines; one wait for the state's two numbers, checked against max_lines(b, end), text_cap and
 // max_line; format(b, nlines) queues the format pass, the text is copied into one of the two pinned buffers, and the slice
-// before goes to the sink meanwhile.  Nothing of the call is still queued when this returns.
+// before goes to the sink meanwhile.  With z.on() the format pass is followed by the deflate and pack passes, and what is copied
+// are the packed members: their length is read together with the NEXT slice's state (the same stream: the pack is done by then),
+// so the copy is issued one slice later and a slice still costs one wait; the last slice's length takes one wait of its own,
+// once a call.  Nothing of the call is still queued when this returns.
 template <class Measure, class MaxLines, class Format>
 int track_slices(rsi_ctx* ctx, int64_t count, int64_t slice, int64_t text_cap, int64_t max_line, TrackState* d_st, const char* d_text,
-                 TrackSink& sink, rsi_track_stats& S, Measure measure, MaxLines max_lines, Format format) {
+                 TrackSink& sink, rsi_track_stats& S, TrackBgzf& z, Measure measure, MaxLines max_lines, Format format) {
   rsi_ctx::TrackWs& w = ctx->track;
   TrackState* h_st = static_cast<TrackState*>(w.pin_state);
   hipStream_t st = ctx->stream;
@@ -95,12 +134,31 @@ int track_slices(rsi_ctx* ctx, int64_t count, int64_t slice, int64_t text_cap, i
     if (ew == hipErrorLaunchTimeOut) ctx->poisoned = true;
     if (ew != hipSuccess) return fail(ctx, RSI_ERR_HIP, std::string("track: waiting for a slice's text: ") + hipGetErrorString(ew));
     S.t_kernel_ms += elapsed(kEvF0 + pending, kEvF1 + pending);
+    if (z.on()) z.D.t_kernel_ms += elapsed(kEvF1 + pending, kEvD1 + pending);
     const double t0 = now_ms();
     const bool ok = sink.put(w.pin[pending], (size_t)pending_bytes);
     const int err = errno;
     S.t_write_ms += now_ms() - t0;
     pending = -1;
     if (!ok) return fail(ctx, RSI_ERR_INTERNAL, std::string("track: write failed: ") + strerror(err));
+    return RSI_OK;
+  };
+  // BGZF: the slice whose members lie packed on the device, their length not yet known to the host
+  int packed_buf = -1;
+  int64_t packed_text = 0;
+  auto copy_packed = [&]() -> int {   // h_st[0] holds the state read behind that slice's pack: copy its members, make it the pending slice
+    const int64_t members = rsitrack::members_of(packed_text), bytes = h_st[0].packed, stored = h_st[0].stored;
+    if (bytes <= 0 || bytes > packed_text + members * rsitrack::kMemberOverhead || bytes > z.packed_cap || stored < 0 || stored > members)
+      return leave(RSI_ERR_INTERNAL, "track: a slice's compressed size is out of range");
+    z.D.members += members;
+    z.D.stored_members += stored;
+    z.D.text_bytes += packed_text;
+    z.D.file_bytes += bytes;
+    e = hipMemcpyAsync(w.pin[packed_buf], z.packed, (size_t)bytes, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipEventRecord(w.ev[kEvCopy + packed_buf], st);
+    if (e != hipSuccess) return hip_failed(e, "hipMemcpyAsync");
+    pending = packed_buf; pending_bytes = bytes;
+    packed_buf = -1;
     return RSI_OK;
   };
   for (int64_t b = 0; b < count; b += slice) {
@@ -120,6 +178,7 @@ int track_slices(rsi_ctx* ctx, int64_t count, int64_t slice, int64_t text_cap, i
     ++S.slices;
     S.lines += nlines;
     S.bytes += nbytes;
+    if (packed_buf >= 0 && (rc = copy_packed()) != RSI_OK) return rc;   // the slice before: out of the packed buffer before this one's pack
     int fresh = -1;
     if (nlines > 0) {
       fresh = next_buf;
@@ -127,12 +186,26 @@ int track_slices(rsi_ctx* ctx, int64_t count, int64_t slice, int64_t text_cap, i
       (void)hipEventRecord(w.ev[kEvF0 + fresh], st);
       format(b, nlines);
       (void)hipEventRecord(w.ev[kEvF1 + fresh], st);
-      e = hipMemcpyAsync(w.pin[fresh], d_text, (size_t)nbytes, hipMemcpyDeviceToHost, st);
-      if (e == hipSuccess) e = hipEventRecord(w.ev[kEvCopy + fresh], st);
-      if (e != hipSuccess) return hip_failed(e, "hipMemcpyAsync");
+      if (z.on()) {
+        launch_deflate_bgzf(d_text, nbytes, z.slots, z.sizes, st);
+        launch_bgzf_pack(z.slots, z.sizes, deflate_members(nbytes), z.packed, z.packed_cap, d_st, st);
+        (void)hipEventRecord(w.ev[kEvD1 + fresh], st);
+      } else {
+        e = hipMemcpyAsync(w.pin[fresh], d_text, (size_t)nbytes, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipEventRecord(w.ev[kEvCopy + fresh], st);
+        if (e != hipSuccess) return hip_failed(e, "hipMemcpyAsync");
+      }
     }
     if ((rc = flush()) != RSI_OK) { (void)ctx_sync(ctx); return rc; }   // the slice before, while this one is formatted and copied
-    if (fresh >= 0) { pending = fresh; pending_bytes = nbytes; }
+    if (fresh >= 0 && z.on()) { packed_buf = fresh; packed_text = nbytes; }
+    else if (fresh >= 0) { pending = fresh; pending_bytes = nbytes; }
+  }
+  if (packed_buf >= 0) {   // the last slice's members: their length has no next slice to travel with
+    e = hipMemcpyAsync(&h_st[0], d_st, sizeof(TrackState), hipMemcpyDeviceToHost, st);
+    if (e != hipSuccess) return hip_failed(e, "hipMemcpyAsync");
+    e = ctx_sync(ctx);
+    if (e != hipSuccess) return fail(ctx, RSI_ERR_HIP, std::string("track: waiting for a slice's compressed size: ") + hipGetErrorString(e));
+    if ((rc = copy_packed()) != RSI_OK) return rc;
   }
   if ((rc = flush()) != RSI_OK) { (void)ctx_sync(ctx); return rc; }
   e = ctx_sync(ctx);   // collects a launch error of the last format pass
@@ -147,6 +220,8 @@ int track_run(rsi_ctx* ctx, const int32_t* d_v, int64_t n, const char* chrom, in
   rsi_track_stats S;
   memset(&S, 0, sizeof(S));
   if (stats) *stats = S;
+  ctx->last_deflate = rsi_deflate_stats{};
+  const bool bgzf = ctx->track_format == RSI_TRACK_BGZF;
   const int name_len = rsitrack::name_length(chrom);
   if (name_len < 0) return fail(ctx, RSI_ERR_BAD_ARG, "track: the name must have 1 to 255 bytes and no tab or newline");
   rsitrack::Plan plan;
@@ -156,10 +231,12 @@ int track_run(rsi_ctx* ctx, const int32_t* d_v, int64_t n, const char* chrom, in
   if (!d_v) return fail(ctx, RSI_ERR_BAD_ARG, "track: no values");
   HIPCHK(hipSetDevice(ctx->device));
   if (!ctx_enter(ctx)) return RSI_ERR_HIP;
-  const TrackLayout L = track_layout(plan);
-  int rc = track_ensure(ctx, plan.text_cap, L);
+  const TrackLayout L = track_layout(plan, bgzf);
+  int rc = track_ensure(ctx, L);
   if (rc != RSI_OK) return rc;
   rsi_ctx::TrackWs& w = ctx->track;
+  TrackBgzf z;
+  if (bgzf) z.place(w.dev, L);
   char* d_text = static_cast<char*>(w.dev) + L.text;
   long long* d_starts = reinterpret_cast<long long*>(static_cast<char*>(w.dev) + L.starts);
   unsigned int* d_tiles = reinterpret_cast<unsigned int*>(static_cast<char*>(w.dev) + L.tiles);
@@ -172,10 +249,10 @@ int track_run(rsi_ctx* ctx, const int32_t* d_v, int64_t n, const char* chrom, in
   name.len = name_len;
   hipStream_t st = ctx->stream;
 
-  h_st[1] = TrackState{-1, 0, 0, 0};
+  h_st[1] = TrackState{-1, 0, 0, 0, 0, 0};
   const hipError_t e = hipMemcpyAsync(d_st, &h_st[1], sizeof(TrackState), hipMemcpyHostToDevice, st);
   if (e != hipSuccess) { (void)ctx_sync(ctx); return fail(ctx, RSI_ERR_HIP, std::string("track: hipMemcpyAsync: ") + hipGetErrorString(e)); }
-  rc = track_slices(ctx, n, plan.slice, plan.text_cap, plan.max_line, d_st, d_text, sink, S,
+  rc = track_slices(ctx, n, plan.slice, plan.text_cap, plan.max_line, d_st, d_text, sink, S, z,
       [&](int64_t b, int64_t end) {
         launch_track_starts(d_v, b, end, n, d_tiles, d_starts, d_st, st);
         launch_track_line_bytes(d_v, d_starts, d_st, pos0, name_len, end - b + 1, d_ltiles, st);
@@ -185,6 +262,7 @@ int track_run(rsi_ctx* ctx, const int32_t* d_v, int64_t n, const char* chrom, in
   if (rc != RSI_OK) return rc;
   S.t_total_ms = now_ms() - t_begin;
   if (stats) *stats = S;
+  ctx->last_deflate = z.D;
   return RSI_OK;
 }
 
@@ -209,6 +287,8 @@ int bin_track_run(rsi_ctx* ctx, const int32_t* d_v, int64_t nb, int m, int64_t n
   rsi_track_stats S;
   memset(&S, 0, sizeof(S));
   if (stats) *stats = S;
+  ctx->last_deflate = rsi_deflate_stats{};
+  const bool bgzf = ctx->track_format == RSI_TRACK_BGZF;
   const int name_len = rsitrack::name_length(chrom);
   if (name_len < 0) return fail(ctx, RSI_ERR_BAD_ARG, "bin track: the name must have 1 to 255 bytes and no tab or newline");
   if (which != 0 && which != 1) return fail(ctx, RSI_ERR_BAD_ARG, "bin track: which must be 0 (bin median) or 1 (ratio to the chromosome's median)");
@@ -222,10 +302,12 @@ int bin_track_run(rsi_ctx* ctx, const int32_t* d_v, int64_t nb, int m, int64_t n
   if (!d_v) return fail(ctx, RSI_ERR_BAD_ARG, "bin track: no values");
   HIPCHK(hipSetDevice(ctx->device));
   if (!ctx_enter(ctx)) return RSI_ERR_HIP;
-  const TrackLayout L = track_layout(plan.text_cap, plan.max_pieces, plan.slice, plan.max_pieces, (size_t)2 * nreg + 1);
-  int rc = track_ensure(ctx, plan.text_cap, L);
+  const TrackLayout L = track_layout(plan.text_cap, plan.max_pieces, plan.slice, plan.max_pieces, (size_t)2 * nreg + 1, bgzf);
+  int rc = track_ensure(ctx, L);
   if (rc != RSI_OK) return rc;
   rsi_ctx::TrackWs& w = ctx->track;
+  TrackBgzf z;
+  if (bgzf) z.place(w.dev, L);
   char* d_text = static_cast<char*>(w.dev) + L.text;
   unsigned long long* d_pieces = reinterpret_cast<unsigned long long*>(static_cast<char*>(w.dev) + L.starts);
   unsigned int* d_tiles = reinterpret_cast<unsigned int*>(static_cast<char*>(w.dev) + L.tiles);
@@ -245,7 +327,7 @@ int bin_track_run(rsi_ctx* ctx, const int32_t* d_v, int64_t nb, int m, int64_t n
   const hipError_t e = hipMemcpyAsync(d_cbreak, table.data(), table.size() * 8, hipMemcpyHostToDevice, st);
   if (e != hipSuccess) { (void)ctx_sync(ctx); return fail(ctx, RSI_ERR_HIP, std::string("bin track: hipMemcpyAsync: ") + hipGetErrorString(e)); }
   BinTrackSource src{d_v, d_pieces, d_cbreak, d_cum, nreg, m, 0, which, median2};
-  rc = track_slices(ctx, nb, plan.slice, plan.text_cap, plan.max_line, d_st, d_text, sink, S,
+  rc = track_slices(ctx, nb, plan.slice, plan.text_cap, plan.max_line, d_st, d_text, sink, S, z,
       [&](int64_t b, int64_t end) {
         src.b0 = b;
         launch_bintrack_pieces(d_cbreak, d_cum, nreg, m, b, end, d_tiles, d_pieces, plan.max_pieces, d_st, st);
@@ -256,6 +338,7 @@ int bin_track_run(rsi_ctx* ctx, const int32_t* d_v, int64_t nb, int m, int64_t n
   if (rc != RSI_OK) return rc;
   S.t_total_ms = now_ms() - t_begin;
   if (stats) *stats = S;
+  ctx->last_deflate = z.D;
   return RSI_OK;
 }
 
@@ -355,6 +438,76 @@ int64_t rsi_hot_debug_bin_track(rsi_ctx* ctx, const int32_t* values, int64_t nb,
   if (rc != RSI_OK) return rc;
   if (out && (int64_t)text.size() <= cap) memcpy(out, text.data(), text.size());
   return (int64_t)text.size();
+}
+
+int rsi_hot_set_track_format(rsi_ctx* ctx, int format) {
+  if (!ctx) return fail(ctx, RSI_ERR_BAD_ARG, "null context");
+  if (format != RSI_TRACK_TEXT && format != RSI_TRACK_BGZF) return fail(ctx, RSI_ERR_BAD_ARG, "track: the format must be RSI_TRACK_TEXT (0) or RSI_TRACK_BGZF (1)");
+  ctx->track_format = format;
+  return RSI_OK;
+}
+
+int rsi_hot_last_deflate_stats(const rsi_ctx* ctx, rsi_deflate_stats* out) {
+  if (!ctx || !out) return RSI_ERR_BAD_ARG;
+  *out = ctx->last_deflate;
+  return RSI_OK;
+}
+
+int rsi_bgzf_write_eof(const char* path) {
+  if (!path || !path[0]) return fail(nullptr, RSI_ERR_BAD_ARG, "bgzf: no path");
+  if (!rsitrack::append_bgzf_eof(path)) return fail(nullptr, RSI_ERR_INTERNAL, std::string("bgzf: cannot write ") + path + ": " + strerror(errno));
+  return RSI_OK;
+}
+
+int64_t rsi_hot_debug_deflate(rsi_ctx* ctx, const uint8_t* text, int64_t len, uint8_t* out, int64_t cap, rsi_deflate_stats* stats) {
+  if (!ctx) return fail(ctx, RSI_ERR_BAD_ARG, "null context");
+  rsi_deflate_stats D{};
+  if (stats) *stats = D;
+  ctx->last_deflate = D;
+  if (len < 0 || (len > 0 && !text)) return fail(ctx, RSI_ERR_BAD_ARG, "deflate: bad argument");
+  if (len == 0) return 0;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!ctx_enter(ctx)) return RSI_ERR_HIP;
+  // the track workspace of a slice of text, filled from the caller's bytes instead of a format pass; whole members but the last
+  const int64_t chunk = std::min(len, rsitrack::kTextBytes / rsitrack::kMemberText * rsitrack::kMemberText);
+  const TrackLayout L = track_layout(chunk, 0, 0, 0, 0, true);
+  const int rc = track_ensure(ctx, L);
+  if (rc != RSI_OK) return rc;
+  rsi_ctx::TrackWs& w = ctx->track;
+  TrackBgzf z;
+  z.place(w.dev, L);
+  char* d_text = static_cast<char*>(w.dev) + L.text;
+  TrackState* d_st = reinterpret_cast<TrackState*>(static_cast<char*>(w.dev) + L.state);
+  TrackState* h_st = static_cast<TrackState*>(w.pin_state);
+  hipStream_t st = ctx->stream;
+  std::string file;
+  for (int64_t off = 0; off < len; off += chunk) {
+    const int64_t nbytes = std::min(chunk, len - off);
+    const int64_t members = rsitrack::members_of(nbytes);
+    HIPCHK(hipMemcpyAsync(d_text, text + off, (size_t)nbytes, hipMemcpyHostToDevice, st));
+    (void)hipEventRecord(w.ev[kEvF1], st);
+    launch_deflate_bgzf(d_text, nbytes, z.slots, z.sizes, st);
+    launch_bgzf_pack(z.slots, z.sizes, deflate_members(nbytes), z.packed, z.packed_cap, d_st, st);
+    (void)hipEventRecord(w.ev[kEvD1], st);
+    HIPCHK(hipMemcpyAsync(&h_st[0], d_st, sizeof(TrackState), hipMemcpyDeviceToHost, st));
+    HIPCHK(CTX_SYNC());
+    const int64_t bytes = h_st[0].packed, stored = h_st[0].stored;
+    if (bytes <= 0 || bytes > nbytes + members * rsitrack::kMemberOverhead || stored < 0 || stored > members)
+      return fail(ctx, RSI_ERR_INTERNAL, "deflate: a compressed size is out of range");
+    HIPCHK(hipMemcpyAsync(w.pin[0], z.packed, (size_t)bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(CTX_SYNC());
+    file.append(w.pin[0], (size_t)bytes);
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, w.ev[kEvF1], w.ev[kEvD1]) == hipSuccess) D.t_kernel_ms += ms;
+    D.members += members;
+    D.stored_members += stored;
+    D.text_bytes += nbytes;
+    D.file_bytes += bytes;
+  }
+  if (stats) *stats = D;
+  ctx->last_deflate = D;
+  if (out && (int64_t)file.size() <= cap) memcpy(out, file.data(), file.size());
+  return (int64_t)file.size();
 }
 
 }  // extern "C"

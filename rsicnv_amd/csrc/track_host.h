@@ -17,10 +17,19 @@ namespace rsitrack {
 // Bounds of one slice, whatever the chromosome's length: at most kSliceBases bases, and few enough of them
 // that even one line per base, each as long as a line of this call can be, fits kTextBytes.  Per context the writer holds
 // kTextBytes + 8 (kSliceBases + 2) + 8 (kSliceBases / 256 + 2) + 32 bytes of HBM (text, run starts, two tile arrays, state) and
-// 2 kTextBytes + 64 of pinned host memory -- at most; a short array takes what its one slice needs.
+// 2 kTextBytes + 64 of pinned host memory -- at most; a short array takes what its one slice needs.  A BGZF track
+// adds, for its kMaxMembers = 515 members of kMemberText text bytes a slice: a slot of kMemberSlot bytes and a 4-byte size each,
+// and the packed members, at most kTextBytes + 31 kMaxMembers bytes -- 64.3 MiB of HBM more, and 31 kMaxMembers bytes more in
+// each pinned buffer.  The plain-text track allocates none of it.
 constexpr int64_t kSliceBases = int64_t(512) << 10;
 constexpr int64_t kTextBytes = int64_t(32) << 20;
 constexpr int kMaxName = 255;
+constexpr int64_t kMemberText = 65280;     // text bytes of one BGZF member (bgzip's)
+constexpr int64_t kMemberSlot = 65536;     // where the device leaves one: 18 + (kMemberText + 5) + 8 at most
+constexpr int64_t kMemberOverhead = 31;    // header, a stored block's 5 bytes, footer
+constexpr int64_t kMaxMembers = (kTextBytes + kMemberText - 1) / kMemberText;
+static_assert(kMaxMembers == 515, "a slice's members: what k_bgzf_pack scans");
+inline int64_t members_of(int64_t text_bytes) { return (text_bytes + kMemberText - 1) / kMemberText; }
 
 // The name's length, or -1: empty, longer than kMaxName, or with a tab or a newline in it (either would break the line)
 inline int name_length(const char* name) {
@@ -131,9 +140,27 @@ inline void remove_parts(const std::string& path, size_t count) {
   for (size_t i = 0; i < count; ++i) (void)::unlink(part_path(path, i).c_str());
 }
 
+// The BGZF end-of-file block: the empty member that bgzip ends every file with, byte for byte
+constexpr size_t kBgzfEofBytes = 28;
+inline const char* bgzf_eof() {
+  static const unsigned char e[kBgzfEofBytes] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  return reinterpret_cast<const char*>(e);
+}
+// Appends the end-of-file block to PATH (created if missing).  false: errno says why.
+inline bool append_bgzf_eof(const char* path) {
+  const int fd = ::open(path, O_WRONLY | O_CREAT | O_APPEND, 0644);
+  if (fd < 0) return false;
+  const bool ok = write_all(fd, bgzf_eof(), kBgzfEofBytes);
+  const int err = errno;
+  if (::close(fd) != 0 && ok) return false;
+  errno = err;
+  return ok;
+}
+
 // PATH = the parts `order` names, one after the other (a part that does not exist is a chromosome that wrote none: skipped).
 // Every part 0 .. count - 1 is gone afterwards, whatever happened; on a failure PATH is removed too and err says why.
-inline bool join_parts(const std::string& path, const std::vector<size_t>& order, size_t count, std::string& err) {
+// bgzf: the parts are whole BGZF members (concatenation keeps the file valid) and one end-of-file block follows the last.
+inline bool join_parts(const std::string& path, const std::vector<size_t>& order, size_t count, std::string& err, bool bgzf = false) {
   bool ok = true;
   const int out = ::open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
   if (out < 0) { err = "cannot write " + path + ": " + strerror(errno); ok = false; }
@@ -155,6 +182,7 @@ inline bool join_parts(const std::string& path, const std::vector<size_t>& order
     }
     ::close(in);
   }
+  if (ok && bgzf && !write_all(out, bgzf_eof(), kBgzfEofBytes)) { err = "cannot write " + path + ": " + strerror(errno); ok = false; }
   if (out >= 0 && ::close(out) != 0 && ok) { err = "cannot write " + path + ": " + strerror(errno); ok = false; }
   remove_parts(path, count);
   if (!ok) (void)::unlink(path.c_str());

@@ -2,9 +2,10 @@
 """Times the bin-track writer (rsi_hot_write_bin_track: one value per bin as bedGraph, pieces found and formatted on the GPU)
 after a run of synth.config_plan(3) -- 250 Mb, resident in HBM, default flags -- against the host loop it replaces: the bin
 medians and regions fetched, one fprintf per line (tools/bin_track_probe_fprintf.c).  Medians of --repeat calls after a
-warm-up call.  Prints one JSON line.
+warm-up call.  Prints one JSON line.  --format bgzf: the device writer deflates its text on the GPU; its entries
+then also hold the file's bytes, members, stored members and the two kernels' time.
 
-  python tools/bin_track_probe.py [--repeat 7] [--scale 1.0] [--dir DIR] [--value ratio|median]"""
+  python tools/bin_track_probe.py [--repeat 7] [--scale 1.0] [--dir DIR] [--value ratio|median] [--format text|bgzf]"""
 import argparse
 import json
 import os
@@ -26,6 +27,7 @@ def main():
     ap.add_argument("--scale", type=float, default=1.0, help="shrinks the chromosome (a quick look)")
     ap.add_argument("--value", default="ratio", choices=["ratio", "median"])
     ap.add_argument("--dir", default=None, help="where the files go (default: a temporary directory)")
+    ap.add_argument("--format", default="text", choices=["text", "bgzf"], help="bgzf: the device writer's calls deflate on the GPU (DESIGN.md 6h)")
     a = ap.parse_args()
     import torch
     from rsicnv_amd import api, synth
@@ -54,14 +56,19 @@ def main():
                 if target == "file" and os.path.exists(path):
                     os.unlink(path)         # (replacing a file costs its truncation: not the writer's)
                 t0 = time.perf_counter()
-                st = hot.write_bin_track(a.value, "chrProbe", path)
+                st = hot.write_bin_track(a.value, "chrProbe", path, format=a.format)
                 st["wall_s"] = time.perf_counter() - t0
+                st["deflate"] = hot.deflate_stats()
                 runs.append(st)
             warm = runs[1:]
             out[target] = {"lines": warm[0]["lines"], "bytes": warm[0]["bytes"], "slices": warm[0]["slices"],
                            "first_call_s": round(runs[0]["wall_s"], 6), "wall_s": med([s["wall_s"] for s in warm]),
                            "kernel_s": med([s["t_kernel_ms"] * 1e-3 for s in warm]), "write_s": med([s["t_write_ms"] * 1e-3 for s in warm]),
                            "inside_call_s": med([s["t_total_ms"] * 1e-3 for s in warm])}
+            if a.format == "bgzf":
+                ds = warm[0]["deflate"]
+                out[target].update(file_bytes=ds["file_bytes"], members=ds["members"], stored_members=ds["stored_members"],
+                                   deflate_kernel_s=med([s["deflate"]["t_kernel_ms"] * 1e-3 for s in warm]))
         # the host loop: fetch the arrays (timed: the loop needs them on the host), then one fprintf per line
         t_fetch = []
         for _ in range(a.repeat):

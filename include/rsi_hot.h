@@ -213,6 +213,20 @@ int64_t rsi_genome_text_copy_sample_depth(rsi_genome_text* g, int slot, int j, i
  * to rsi_genome_text_kernel_ms's parse_ms. */
 rsi_genome_text* rsi_genome_bedgraph_open(int device, const char* path, int nref, const char* const* names, const int64_t* lengths,
                                           int max_resident, size_t chunk_bytes, int* status);
+/* The same for a BGZF file with a tabix index beside it (index_path: a .tbi, as rsi_track_index_write_tbi or tabix write it, or a
+ * .csi, as mosdepth writes it): only the members between the smallest chunk begin and the largest chunk end the index holds for
+ * names[] (each matched with or without a leading "chr") are read and inflated, the first one's text from the begin's in-member
+ * offset on.  Depth, counts, names, hand-over order and errors are those of rsi_genome_bedgraph_open with the same names (the
+ * sequences outside names[] that the whole-file reader names and passes over are met only as far as they lie inside the range); only
+ * rsi_inflate_stats' blocks, compressed_bytes and text_bytes count the members of that range alone.  An index that does not fit
+ * the file is RSI_ERR_BAD_ARG naming it: a begin that is no member header or lies behind a byte other than a line end, a first
+ * line of another sequence, a line of names[] directly behind the range's end inside its last member; so is a file that is not
+ * BGZF or an index that cannot be parsed.  No name in the index: the reader hands over nothing, as for a file without their lines. */
+rsi_genome_text* rsi_genome_bedgraph_open_indexed(int device, const char* path, const char* index_path, int nref, const char* const* names,
+                                                  const int64_t* lengths, int max_resident, size_t chunk_bytes, int* status);
+/* The compressed byte range [begin, stop) an indexed reader takes from its file (both 0: no name in the index); RSI_ERR_BAD_ARG for
+ * a reader opened without an index. */
+int rsi_genome_text_index_range(const rsi_genome_text* g, int64_t* begin, int64_t* stop);
 /* One chromosome whose depth is already in HBM (e.g. a genome reader's buffer, not modified) and whose fasta[n] is in
  * host memory: the sequence goes to the context's own device buffer, then rsi_hot_run_device. */
 int rsi_hot_run_depth_device(rsi_ctx* ctx, const rsi_params* p, const void* d_depth, const uint8_t* fasta, int64_t n,
@@ -369,6 +383,34 @@ int rsi_bgzf_write_eof(const char* path);
  * the BGZF bytes (no end-of-file block) into out[cap].  Returns their length (also when out == NULL or cap is too small,
  * writing nothing then; 0 for len == 0), < 0 on error. */
 int64_t rsi_hot_debug_deflate(rsi_ctx* ctx, const uint8_t* text, int64_t len, uint8_t* out, int64_t cap, rsi_deflate_stats* stats);
+
+/* ---- The tabix index of a BGZF track, built from the device -----------------------------------------------------
+ * An rsi_track_index collects, chromosome by chromosome in the order of the calls, what a .tbi file holds: per bin (tabix's
+ * reg2bin over 0-based half-open lines) the chunks of the file with that bin's lines, as BGZF virtual offsets (compressed offset
+ * of a member << 16 | offset in its text), and per 16 384-base window the offset of the first line that reaches into it.  While
+ * one is set on a context, every BGZF rsi_hot_write_track, rsi_hot_write_track_device and rsi_hot_write_bin_track (and the two
+ * test hooks, whose file starts at offset 0) adds its chromosome: each slice's records come from one more launch behind its
+ * deflate and pack launches and cross PCIe with the slice, at no wait of their own.  Offsets are absolute in the file the call
+ * wrote: with `append`, the file's size before the call is added.  A call of the name the index ends with goes on with that
+ * chromosome.  A line that ends beyond 2^29 is RSI_ERR_UNSUPPORTED (the format's limit; checked before anything is written), a
+ * text-format call with an index set RSI_ERR_BAD_ARG.  A chromosome that wrote no line is not listed.  A track call that fails
+ * after its first slice leaves the slices it had written in the index: the index is then of no use (a retry of the same name would
+ * go on with the partial chromosome); free it and begin a new one, as the command line does. */
+typedef struct rsi_track_index rsi_track_index;
+rsi_track_index* rsi_track_index_create(void);
+void rsi_track_index_free(rsi_track_index* ix);
+/* ix == NULL turns indexing off (the default).  The index must outlive its use by the context; the context does not own it. */
+int rsi_hot_set_track_index(rsi_ctx* ctx, rsi_track_index* ix);
+/* src's chromosomes behind dst's, their compressed offsets moved by `shift` bytes (a part file appended at that offset).  A first
+ * chromosome of src with the name dst ends with goes on with that chromosome (two parts of one chromosome), as a later call would. */
+int rsi_track_index_append(rsi_track_index* dst, const rsi_track_index* src, int64_t shift);
+/* PATH as a .tbi: the index for a BED-like file (columns 1, 2, 3; 0-based; '#' comments), BGZF-compressed on the host, without
+ * the optional pseudo-bin and unplaced count.  RSI_ERR_INTERNAL when the file cannot be written. */
+int rsi_track_index_write_tbi(rsi_track_index* ix, const char* path);
+/* What it holds: chromosomes, chunks and linear-index windows (any pointer may be NULL). */
+int rsi_track_index_counts(const rsi_track_index* ix, int64_t* nref, int64_t* nchunks, int64_t* nwindows);
+/* Test hook: the .tbi stream before compression into out[cap]; returns its length (also when it does not fit: nothing written). */
+int64_t rsi_track_index_debug_tbi(const rsi_track_index* ix, uint8_t* out, int64_t cap);
 
 /* Results.  which: 0 = calls after sd_filters (what write_cnv_to_file prints),
  *                  1 = detectcnv output before sd_filters,

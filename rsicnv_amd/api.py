@@ -61,11 +61,13 @@ EXPORTS = ["rsi_default_params", "rsi_hot_create", "rsi_hot_destroy", "rsi_hot_l
            "rsi_hot_last_inflate_stats", "rsi_hot_inflate_bgzf", "rsi_genome_text_inflate_stats",
            "rsi_synth_append_genome_bgzf", "rsi_genome_text_open_samples", "rsi_genome_text_samples", "rsi_genome_text_max_resident",
            "rsi_genome_text_sample_depth", "rsi_genome_text_copy_sample_depth", "rsi_synth_append_genome_samples",
-           "rsi_genome_bedgraph_open", "rsi_synth_append_genome_bedgraph",
+           "rsi_genome_bedgraph_open", "rsi_synth_append_genome_bedgraph", "rsi_genome_bedgraph_open_indexed", "rsi_genome_text_index_range",
            "rsi_hot_set_exclude", "rsi_exclude_read_bed", "rsi_hot_debug_classify", "rsi_hot_debug_per_base",
            "rsi_hot_write_track", "rsi_hot_write_track_device", "rsi_hot_debug_track",
            "rsi_hot_write_bin_track", "rsi_hot_debug_bin_track",
-           "rsi_hot_set_track_format", "rsi_hot_last_deflate_stats", "rsi_bgzf_write_eof", "rsi_hot_debug_deflate"]
+           "rsi_hot_set_track_format", "rsi_hot_last_deflate_stats", "rsi_bgzf_write_eof", "rsi_hot_debug_deflate",
+           "rsi_track_index_create", "rsi_track_index_free", "rsi_hot_set_track_index", "rsi_track_index_append",
+           "rsi_track_index_write_tbi", "rsi_track_index_counts", "rsi_track_index_debug_tbi"]
 
 
 class RsiParams(C.Structure):
@@ -250,6 +252,10 @@ def load_library():
     L.rsi_synth_append_genome_samples.argtypes = [C.c_char_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int64, C.c_int]
     L.rsi_genome_bedgraph_open.argtypes = L.rsi_genome_text_open.argtypes
     L.rsi_genome_bedgraph_open.restype = C.c_void_p
+    L.rsi_genome_bedgraph_open_indexed.argtypes = [C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_int,
+                                                   C.c_size_t, C.POINTER(C.c_int)]
+    L.rsi_genome_bedgraph_open_indexed.restype = C.c_void_p
+    L.rsi_genome_text_index_range.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.rsi_synth_append_genome_bedgraph.argtypes = [C.c_char_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_int]
     L.rsi_hot_last_inflate_stats.argtypes = [C.c_void_p, C.POINTER(RsiInflateStats)]
     L.rsi_hot_inflate_bgzf.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(RsiInflateStats)]
@@ -271,6 +277,16 @@ def load_library():
     L.rsi_hot_set_track_format.argtypes = [C.c_void_p, C.c_int]
     L.rsi_hot_last_deflate_stats.argtypes = [C.c_void_p, C.POINTER(RsiDeflateStats)]
     L.rsi_bgzf_write_eof.argtypes = [C.c_char_p]
+    L.rsi_track_index_create.argtypes = []
+    L.rsi_track_index_create.restype = C.c_void_p
+    L.rsi_track_index_free.argtypes = [C.c_void_p]
+    L.rsi_track_index_free.restype = None
+    L.rsi_hot_set_track_index.argtypes = [C.c_void_p, C.c_void_p]
+    L.rsi_track_index_append.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    L.rsi_track_index_write_tbi.argtypes = [C.c_void_p, C.c_char_p]
+    L.rsi_track_index_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.rsi_track_index_debug_tbi.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    L.rsi_track_index_debug_tbi.restype = C.c_int64
     L.rsi_hot_debug_deflate.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(RsiDeflateStats)]
     L.rsi_hot_debug_deflate.restype = C.c_int64
     _lib = L
@@ -321,6 +337,50 @@ class RsiError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"{STATUS_NAMES.get(code, code)}: {msg}")
         self.code = code
+
+
+class TrackIndex:
+    """The tabix index of BGZF tracks (rsi_track_index; host memory only): set on a context with RsiHot.set_track_index, filled by
+    that context's BGZF track calls chromosome by chromosome, written as FILE.tbi."""
+
+    def __init__(self):
+        self.lib = load_library()
+        self.handle = self.lib.rsi_track_index_create()
+        if not self.handle:
+            raise MemoryError("rsi_track_index_create")
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.rsi_track_index_free(self.handle)
+            self.handle = None
+
+    __del__ = close
+
+    def _check(self, k):
+        if k < 0:
+            raise RsiError(k, self.lib.rsi_hot_last_error(None).decode())
+
+    def append(self, src, shift):
+        """src's chromosomes behind this index's, their compressed offsets moved by `shift` bytes (rsi_track_index_append)."""
+        self._check(self.lib.rsi_track_index_append(self.handle, src.handle, int(shift)))
+
+    def write_tbi(self, path):
+        self._check(self.lib.rsi_track_index_write_tbi(self.handle, os.fsencode(path)))
+
+    def counts(self):
+        """{"nref", "chunks", "windows"} (rsi_track_index_counts)."""
+        r, c, w = C.c_int64(), C.c_int64(), C.c_int64()
+        self._check(self.lib.rsi_track_index_counts(self.handle, C.byref(r), C.byref(c), C.byref(w)))
+        return {"nref": r.value, "chunks": c.value, "windows": w.value}
+
+    def tbi_bytes(self):
+        """The .tbi stream before compression (test hook, rsi_track_index_debug_tbi)."""
+        k = self.lib.rsi_track_index_debug_tbi(self.handle, None, 0)
+        self._check(int(k))
+        out = np.zeros(max(k, 1), dtype=np.uint8)
+        k2 = self.lib.rsi_track_index_debug_tbi(self.handle, out.ctypes.data, k)
+        self._check(int(k2))
+        return out[:k].tobytes()
 
 
 class Result:
@@ -653,6 +713,12 @@ class RsiHot:
             if format is not None:
                 self.set_track_format(before)
 
+    def set_track_index(self, index):
+        """Every BGZF track call of this context from now on adds its chromosome to `index` (a TrackIndex; None: no indexing,
+        the default) -- rsi_hot_set_track_index.  The debug_track / debug_bin_track hooks do too, for a file that starts at 0."""
+        self._check(self.lib.rsi_hot_set_track_index(self.ctx, index.handle if index is not None else None))
+        self._track_index = index   # kept alive while the context points at it
+
     def deflate_stats(self):
         """The compressed side of the last track call or debug_deflate (rsi_hot_last_deflate_stats): members, stored_members,
         text_bytes, file_bytes (no end-of-file block), t_kernel_ms of the deflate and pack launches; zeros after a text call."""
@@ -876,9 +942,12 @@ class GenomeText:
     sample j.  The reader may use fewer than max_resident buffers when device memory holds fewer (self.max_resident).
 
     bedgraph=True: a bedGraph file, "RNAME start end d" (rsi_genome_bedgraph_open): each line is read as the lines
-    "RNAME p d", p = start + 1 .. end; the stats are those of that expanded file, bytes aside."""
+    "RNAME p d", p = start + 1 .. end; the stats are those of that expanded file, bytes aside.  index=PATH (with bedgraph=True,
+    a BGZF file): the .tbi or .csi beside it; only the members that hold the lines of `names` are read
+    (rsi_genome_bedgraph_open_indexed), index_range() says which."""
 
-    def __init__(self, path, names, lengths, chunk_bytes=0, device=0, max_resident=2, auto_release=True, samples=None, bedgraph=False):
+    def __init__(self, path, names, lengths, chunk_bytes=0, device=0, max_resident=2, auto_release=True, samples=None, bedgraph=False,
+                 index=None):
         self.lib = load_library()
         enc = [n.encode() for n in names]
         self._names = (C.c_char_p * max(len(enc), 1))(*enc)
@@ -886,7 +955,12 @@ class GenomeText:
         st = C.c_int(0)
         if bedgraph and samples is not None:
             raise ValueError("a bedGraph file has one depth column")
-        if samples is None:
+        if index is not None and not bedgraph:
+            raise ValueError("an index serves a bedGraph file")
+        if index is not None:
+            self.g = self.lib.rsi_genome_bedgraph_open_indexed(int(device), os.fsencode(path), os.fsencode(index), len(enc), self._names, self._lens,
+                                                               int(max_resident), int(chunk_bytes), C.byref(st))
+        elif samples is None:
             opener = self.lib.rsi_genome_bedgraph_open if bedgraph else self.lib.rsi_genome_text_open
             self.g = opener(int(device), os.fsencode(path), len(enc), self._names, self._lens, int(max_resident), int(chunk_bytes), C.byref(st))
         else:
@@ -973,6 +1047,14 @@ class GenomeText:
         if k < 0:
             raise RsiError(int(k), self.lib.rsi_genome_text_last_error(self.g).decode())
         return out
+
+    def index_range(self):
+        """(begin, stop): the compressed bytes an indexed reader takes from its file (rsi_genome_text_index_range)."""
+        b, e = C.c_int64(), C.c_int64()
+        k = self.lib.rsi_genome_text_index_range(self.g, C.byref(b), C.byref(e))
+        if k < 0:
+            raise RsiError(k, "the reader was opened without an index")
+        return b.value, e.value
 
     def inflate_stats(self):
         """The file's format and the inflate figures so far (see RsiHot.inflate_stats)."""

@@ -58,6 +58,9 @@ struct Options {
   std::string bintrackvalue = "ratio";   // -bintrackvalue ratio|median: the bin's median over the chromosome's, or the median itself
   std::string trackformat;   // -trackformat text|bgzf: both tracks as text or as BGZF, whatever their names (empty: by the name)
   bool track_bgzf = false, bintrack_bgzf = false;   // what the rule gives -track's and -bintrack's FILE (main sets them)
+  std::string dindex;        // -dindex PATH|none: the .tbi / .csi of a BGZF bedGraph -d FILE for -c RNAME (empty: FILE.tbi, else FILE.csi, when there)
+  std::string dindex_path;   // what that gives (main sets it); empty: the whole file is read
+  bool trackindex = false;   // -trackindex: FILE.tbi beside every track that is BGZF, built from the device's records
 };
 
 int usage() {
@@ -87,6 +90,8 @@ int usage() {
             << "   -bintrack FILE  save one value per bin of every called chromosome as bedGraph, see below\n"
             << "   -bintrackvalue ratio|median  the value -bintrack saves: the bin's median over the chromosome's (default), or the median\n"
             << "   -trackformat text|bgzf  -track and -bintrack as plain text or as BGZF (default: BGZF when FILE ends in .gz or .bgz)\n"
+            << "   -trackindex  write the tabix index FILE.tbi beside every BGZF track, see below\n"
+            << "   -dindex PATH|none  the tabix / CSI index of a BGZF bedGraph -d FILE, used with -c RNAME (default: FILE.tbi, else FILE.csi)\n"
             << "\nNote:\n"
             << "   This build runs the read-depth hot path on an MI355X; input is a read depth file\n"
             << "   (samtools mpileup BAM | cut -f2,4) with -c RNAME, a whole-genome depth file without -c\n"
@@ -123,6 +128,12 @@ int usage() {
             << "   what bgzip makes of the text: the text is deflated on the GPU in members of 65280 bytes and the file ends with the\n"
             << "   end-of-file block, so tabix, IGV and bedtools take it and -d FILE.bedgraph.gz reads it back.  -trackformat text or\n"
             << "   bgzf decides for both tracks whatever their names.\n"
+            << "   -d FILE.bed.gz -c RNAME with FILE.tbi or FILE.csi beside a BGZF FILE (tabix's, mosdepth's or -trackindex's; -dindex PATH\n"
+            << "   names another, -dindex none reads without) inflates RNAME's members alone instead of the whole file.  An index that\n"
+            << "   does not fit the file is an error, never wrong depth; one older than the file gets a warning.\n"
+            << "   -trackindex writes FILE.tbi beside every BGZF track (with -samples: FILE.k.tbi): the index tabix -p bed would make,\n"
+            << "   collected on the GPU while the track is written, so that IGV and tabix FILE chr7:1-2000000 take the file as it\n"
+            << "   is.  Chromosomes longer than 2^29 bases are beyond that format; a plain-text track has no index.\n"
             << std::endl;
   return 0;
 }
@@ -181,6 +192,8 @@ void parse(int argc, char** argv, Options& o) {
     else if (s == "-bintrack") { o.bintrackfile = need(i); ++i; }
     else if (s == "-bintrackvalue") { o.bintrackvalue = need(i); ++i; }
     else if (s == "-trackformat") { o.trackformat = need(i); ++i; }
+    else if (s == "-trackindex") o.trackindex = true;
+    else if (s == "-dindex") { o.dindex = need(i); ++i; }
     else { std::cerr << "unknown option " << s << std::endl; exit(usage()); }
   }
   if (o.rdfile.empty() && o.bamfile.empty()) { std::cerr << "need input file " << std::endl; exit(usage()); }
@@ -232,7 +245,16 @@ struct ChromOutput {
   size_t track_index = 0;          // -track, -bintrack: the chromosome's place in the order of the rows (set by the caller: names its part files)
   bool track_failed = false;       // -track: its part could not be written (the reason is in the log): no track file
   bool bintrack_failed = false;    // -bintrack: likewise
+  std::shared_ptr<rsi_track_index> track_ix, bintrack_ix;   // -trackindex: the index of this chromosome's part (offsets from the part's start)
 };
+
+std::shared_ptr<rsi_track_index> new_track_index() { return std::shared_ptr<rsi_track_index>(rsi_track_index_create(), rsi_track_index_free); }
+// ", index: C chunks, W windows" for the log's track lines
+std::string index_counts(const rsi_track_index* ix) {
+  int64_t refs = 0, chunks = 0, windows = 0;
+  if (!ix || rsi_track_index_counts(ix, &refs, &chunks, &windows) != RSI_OK) return "";
+  return ", index: " + std::to_string(chunks) + " chunks, " + std::to_string(windows) + " windows";
+}
 
 // One log line for a compressed depth file (none for plain text, whose logs stay as they were)
 std::string inflate_line(const rsi_inflate_stats& s) {
@@ -323,26 +345,32 @@ void report_chromosome(rsi_ctx* ctx, const Options& o, const std::string& chr, r
   if (!o.trackfile.empty()) {   // -track: this chromosome's lines into its part file, from the depth the context still holds
     rsi_track_stats tk;
     const std::string part = rsitrack::part_path(o.trackfile, co.track_index);
+    if (o.trackindex && o.track_bgzf) co.track_ix = new_track_index();
     if (rsi_hot_set_track_format(ctx, o.track_bgzf ? RSI_TRACK_BGZF : RSI_TRACK_TEXT) != RSI_OK ||
+        rsi_hot_set_track_index(ctx, co.track_ix.get()) != RSI_OK ||
         rsi_hot_write_track(ctx, o.trackdepth == "gc" ? 1 : 0, chr.c_str(), part.c_str(), 0, &tk) != RSI_OK) {
       info << "track: " << chr << ": " << rsi_hot_last_error(ctx) << "\n";
       co.track_failed = true;
     } else {
       info << "track: " << chr << " " << tk.lines << " lines, " << tk.bytes << " bytes, " << tk.t_total_ms * 1e-3 << " s (kernels "
-           << tk.t_kernel_ms * 1e-3 << " s, write " << tk.t_write_ms * 1e-3 << " s)\n";
+           << tk.t_kernel_ms * 1e-3 << " s, write " << tk.t_write_ms * 1e-3 << " s)" << index_counts(co.track_ix.get()) << "\n";
     }
+    (void)rsi_hot_set_track_index(ctx, nullptr);
   }
   if (!o.bintrackfile.empty()) {   // -bintrack: this chromosome's bins into their part file, while the context still holds the run
     rsi_track_stats tk;
     const std::string part = rsitrack::part_path(o.bintrackfile, co.track_index);
+    if (o.trackindex && o.bintrack_bgzf) co.bintrack_ix = new_track_index();
     if (rsi_hot_set_track_format(ctx, o.bintrack_bgzf ? RSI_TRACK_BGZF : RSI_TRACK_TEXT) != RSI_OK ||
+        rsi_hot_set_track_index(ctx, co.bintrack_ix.get()) != RSI_OK ||
         rsi_hot_write_bin_track(ctx, o.bintrackvalue == "median" ? 0 : 1, chr.c_str(), part.c_str(), 0, &tk) != RSI_OK) {
       info << "bintrack: " << chr << ": " << rsi_hot_last_error(ctx) << "\n";
       co.bintrack_failed = true;
     } else {
       info << "bintrack: " << chr << " " << tk.lines << " lines, " << tk.bytes << " bytes, " << tk.t_total_ms * 1e-3 << " s (kernels "
-           << tk.t_kernel_ms * 1e-3 << " s, write " << tk.t_write_ms * 1e-3 << " s)\n";
+           << tk.t_kernel_ms * 1e-3 << " s, write " << tk.t_write_ms * 1e-3 << " s)" << index_counts(co.bintrack_ix.get()) << "\n";
     }
+    (void)rsi_hot_set_track_index(ctx, nullptr);
   }
   const rsi_chrom_stats* S = rsi_result_stats(res);
   info << "#Noseq regions excluded\n";
@@ -514,7 +542,9 @@ bool run_genome(const Options& o, const std::vector<int32_t>& cols, std::vector<
   int st = 0;
   rsi_pool* pool = rsi_pool_create(o.device, nwork, &st);
   if (!pool) { err = rsi_hot_last_error(nullptr); return false; }
-  rsi_genome_text* g = bed ? rsi_genome_bedgraph_open(o.device, o.rdfile.c_str(), (int)cnames.size(), cnames.data(), lens.data(), nwork + 1, 0, &st)
+  const bool indexed = bed && only && !o.dindex_path.empty();
+  rsi_genome_text* g = indexed ? rsi_genome_bedgraph_open_indexed(o.device, o.rdfile.c_str(), o.dindex_path.c_str(), (int)cnames.size(), cnames.data(), lens.data(), nwork + 1, 0, &st)
+      : bed ? rsi_genome_bedgraph_open(o.device, o.rdfile.c_str(), (int)cnames.size(), cnames.data(), lens.data(), nwork + 1, 0, &st)
       : cols.empty()
       ? rsi_genome_text_open(o.device, o.rdfile.c_str(), (int)cnames.size(), cnames.data(), lens.data(), nwork + 1, 0, &st)
       : rsi_genome_text_open_samples(o.device, o.rdfile.c_str(), (int)cnames.size(), cnames.data(), lens.data(), cols.data(), (int)cols.size(),
@@ -635,6 +665,14 @@ bool run_genome(const Options& o, const std::vector<int32_t>& cols, std::vector<
   std::ostringstream sm;
   if (only && ok && chroms.empty()) { ok = false; err = "no lines for " + *only + " in " + o.rdfile; }
   if (bed) sm << "#depth file: bedGraph (RNAME START END DEPTH), read as the per-base lines it stands for\n";
+  if (indexed) {
+    int64_t from = 0, stop = 0;
+    (void)rsi_genome_text_index_range(g, &from, &stop);
+    struct stat si, sd;
+    if (stat(o.dindex_path.c_str(), &si) == 0 && stat(o.rdfile.c_str(), &sd) == 0 && si.st_mtime < sd.st_mtime)
+      sm << "#depth index: warning: " << o.dindex_path << " is older than " << o.rdfile << "\n";
+    sm << "#depth index: " << o.dindex_path << ", members at compressed offsets " << from << "-" << stop << " of the file\n";
+  }
   sm << "timing: whole-genome depth text " << (now_s() - t0) << " s, " << chroms.size() << " chromosomes, boundary kernels " << bound_ms
      << " ms, parse kernels " << parse_ms << " ms\n";
   rsi_inflate_stats is;
@@ -687,26 +725,55 @@ bool select_samples(const Options& o, std::vector<int32_t>& cols, std::vector<st
 // -track and -bintrack (`what`: "track" / "bin track", `flag`: the option), after the run: the parts of the chromosomes whose rows
 // were written (`order`, in row order) become FILE; every part 0 .. count - 1 is deleted whatever happened.  failed: a
 // chromosome's part could not be written -- then there is no FILE.  bgzf: the parts are BGZF members; the end-of-file block ends FILE.
+// index (-trackindex, a BGZF track): per entry of `order` its part's index; they are appended in row order, each moved by its
+// part's offset in FILE, and written as FILE.tbi behind the end-of-file block.  A track that failed leaves no index.
 bool finish_track(const std::string& file, const std::vector<size_t>& order, size_t count, bool failed, bool bgzf, std::ostream& log,
-                  const char* what = "track", const char* flag = "-track") {
+                  const std::vector<std::shared_ptr<rsi_track_index>>* index, const char* what = "track", const char* flag = "-track") {
   if (file.empty()) return true;
   std::string err;
+  std::vector<int64_t> offsets;
+  if (index) remove((file + ".tbi").c_str());
   if (failed) {
     rsitrack::remove_parts(file, count);
     remove(file.c_str());
     err = std::string("a chromosome's ") + what + " could not be written (see above)";
-  } else if (rsitrack::join_parts(file, order, count, err, bgzf)) {
+  } else if (rsitrack::join_parts(file, order, count, err, bgzf, &offsets)) {
     std::cerr << what << " written to " << file << std::endl; log << what << " written to " << file << std::endl;
-    return true;
+    if (!index) return true;
+    const std::shared_ptr<rsi_track_index> all = new_track_index();
+    bool ok = all != nullptr;
+    for (size_t k = 0; ok && k < order.size(); ++k)
+      if (offsets[k] >= 0 && (*index)[k]) ok = rsi_track_index_append(all.get(), (*index)[k].get(), offsets[k]) == RSI_OK;
+    ok = ok && rsi_track_index_write_tbi(all.get(), (file + ".tbi").c_str()) == RSI_OK;
+    if (ok) {
+      std::cerr << what << " index written to " << file << ".tbi" << std::endl; log << what << " index written to " << file << ".tbi" << std::endl;
+      return true;
+    }
+    err = std::string("the index: ") + rsi_hot_last_error(nullptr);
   }
   std::cerr << "rsicnv: " << flag << ": " << err << std::endl; log << "rsicnv: " << flag << ": " << err << std::endl;
   return false;
 }
 // both kinds of track of one output: every part is dealt with, whichever fails
-bool finish_tracks(const Options& o, const std::string& suffix, const std::vector<size_t>& order, size_t count, bool track_failed,
-                   bool bintrack_failed, std::ostream& log) {
-  const bool a = finish_track(o.trackfile.empty() ? "" : o.trackfile + suffix, order, count, track_failed, o.track_bgzf, log);
-  const bool b = finish_track(o.bintrackfile.empty() ? "" : o.bintrackfile + suffix, order, count, bintrack_failed, o.bintrack_bgzf, log, "bin track", "-bintrack");
+// What the chromosomes of one output leave for its tracks: whose rows were written, in row order, whether a part failed, the parts' indexes
+struct TrackParts {
+  std::vector<size_t> order;
+  bool track_failed = false, bintrack_failed = false;
+  std::vector<std::shared_ptr<rsi_track_index>> track_ix, bintrack_ix;   // per entry of `order`
+  void add(size_t i, const ChromOutput& co) {
+    track_failed = track_failed || co.track_failed;
+    bintrack_failed = bintrack_failed || co.bintrack_failed;
+    if (!co.populated) return;
+    order.push_back(i);
+    track_ix.push_back(co.track_ix);
+    bintrack_ix.push_back(co.bintrack_ix);
+  }
+};
+bool finish_tracks(const Options& o, const std::string& suffix, const TrackParts& p, size_t count, std::ostream& log) {
+  const bool a = finish_track(o.trackfile.empty() ? "" : o.trackfile + suffix, p.order, count, p.track_failed, o.track_bgzf, log,
+                              o.trackindex && o.track_bgzf ? &p.track_ix : nullptr);
+  const bool b = finish_track(o.bintrackfile.empty() ? "" : o.bintrackfile + suffix, p.order, count, p.bintrack_failed, o.bintrack_bgzf, log,
+                              o.trackindex && o.bintrack_bgzf ? &p.bintrack_ix : nullptr, "bin track", "-bintrack");
   return a && b;
 }
 
@@ -741,9 +808,22 @@ int main(int argc, char** argv) {
       size_t k = 0;
       while (k < fnames.size() && fnames[k] != o.chr && fnames[k] != "chr" + o.chr) ++k;
       if (k == fnames.size()) { std::cerr << "rsicnv: " << o.chr << " not found in fai index" << std::endl; return 1; }
+      // -dindex: the index that says where RNAME's members are; without one the whole file is inflated
+      if (o.dindex != "none") {
+        unsigned char head[4] = {0, 0, 0, 0};
+        FILE* f = fopen(o.rdfile.c_str(), "rb");
+        const bool bgzf = f && fread(head, 1, 4, f) == 4 && head[0] == 0x1f && head[1] == 0x8b && head[2] == 8 && (head[3] & 4);
+        if (f) fclose(f);
+        if (!o.dindex.empty()) o.dindex_path = o.dindex;   // named: used, or refused by the reader when it cannot be
+        else if (bgzf) for (const char* ext : {".tbi", ".csi"}) if (o.dindex_path.empty() && access((o.rdfile + ext).c_str(), R_OK) == 0) o.dindex_path = o.rdfile + ext;
+      }
       // a file without lines for RNAME is found by the one pass of the reader (run_genome: exit 1, no output); a host pass
       // in front of it would read the text once more, up to RNAME's first line or through the whole file
     }
+  }
+  if (!o.dindex.empty() && o.dindex != "none" && !bed_one) {
+    std::cerr << "rsicnv: -dindex: an index serves -d FILE -c RNAME with a bedGraph FILE in BGZF only" << std::endl;
+    return 1;
   }
   // -track: refused where it cannot work, before any output or device work
   if (o.trackdepth != "raw" && o.trackdepth != "gc") {
@@ -757,6 +837,23 @@ int main(int argc, char** argv) {
   // BGZF by the name as -d takes it (.gz / .bgz, in any case) -- the FILE given, before -samples adds .k -- unless -trackformat says
   o.track_bgzf = o.trackformat.empty() ? gz_name(o.trackfile) : o.trackformat == "bgzf";
   o.bintrack_bgzf = o.trackformat.empty() ? gz_name(o.bintrackfile) : o.trackformat == "bgzf";
+  if (o.trackindex && !((!o.trackfile.empty() && o.track_bgzf) || (!o.bintrackfile.empty() && o.bintrack_bgzf))) {
+    std::cerr << "rsicnv: -trackindex: no BGZF track to index (a plain-text track has none: name FILE .gz or .bgz, or give -trackformat bgzf)" << std::endl;
+    return 1;
+  }
+  if (o.trackindex) {   // the format ends at 2^29: a longer sequence among those this run can write (the .fai's, or -c's alone) is refused here
+    const bool one_named = !o.chr.empty() && o.chr != "1-22XY";   // -c RNAME was given: that sequence alone can be written
+    std::ifstream fai((o.reffile + ".fai").c_str());
+    std::string line, name;
+    while (std::getline(fai, line)) {
+      std::istringstream iss(line);
+      long long len = 0;
+      if ((iss >> name >> len) && len > (1ll << 29) && (!one_named || name == o.chr || name == "chr" + o.chr || "chr" + name == o.chr)) {
+        std::cerr << "rsicnv: -trackindex: " << name << " has " << len << " bases, more than 2^29 = 536870912, the limit of a tabix index" << std::endl;
+        return 1;
+      }
+    }
+  }
   if (!o.trackfile.empty()) {
     if (o.gpus > 1) { std::cerr << "rsicnv: -track: not with -gpus above 1 (the track is written by one device: -gpu INT picks it)" << std::endl; return 1; }
     if (o.trackdepth == "gc" && !o.P.gcadjust) { std::cerr << "rsicnv: -trackdepth gc: -NOGC leaves no GC-adjusted depth to save" << std::endl; return 1; }
@@ -868,14 +965,12 @@ int main(int argc, char** argv) {
       std::string h = hdr.str();
       h.replace(h.find("#output:    " + o.outfile + "\n"), 12 + o.outfile.size() + 1, "#output:    " + path + "\n");
       slog << h << "#sample " << cols[j] << (sample_names[j].empty() ? "" : ": " + sample_names[j]) << "\n";
-      bool header_done = false, track_failed = false, bintrack_failed = false;
-      std::vector<size_t> track_order;
+      bool header_done = false;
+      TrackParts parts;
       for (size_t i = 0; i < chroms.size(); ++i) {
         const ChromOutput& co = outs[i][j];
         std::cerr << co.log; slog << co.log;
-        track_failed = track_failed || co.track_failed;
-        bintrack_failed = bintrack_failed || co.bintrack_failed;
-        if (co.populated) track_order.push_back(i);
+        parts.add(i, co);
         if (co.populated) {
           std::ofstream out(path.c_str(), header_done ? std::ios::app : std::ios::trunc);
           if (!header_done) {
@@ -890,7 +985,7 @@ int main(int argc, char** argv) {
         }
         if (co.fatal) break;
       }
-      if (!finish_tracks(o, "." + std::to_string(cols[j]), track_order, chroms.size(), track_failed, bintrack_failed, slog)) tracks_ok = false;
+      if (!finish_tracks(o, "." + std::to_string(cols[j]), parts, chroms.size(), slog)) tracks_ok = false;
     }
     std::cerr << summary; log << summary;
     return tracks_ok ? 0 : 1;
@@ -909,25 +1004,21 @@ int main(int argc, char** argv) {
       rsitrack::remove_parts(o.bintrackfile, chroms.size());
       return 1;
     }
-    std::vector<size_t> track_order;
-    bool track_failed = false, bintrack_failed = false;
+    TrackParts parts;
     for (size_t i = 0; i < chroms.size(); ++i) {
       emit(chroms[i], outs[i][0]);
-      track_failed = track_failed || outs[i][0].track_failed;
-      bintrack_failed = bintrack_failed || outs[i][0].bintrack_failed;
-      if (outs[i][0].populated) track_order.push_back(i);
+      parts.add(i, outs[i][0]);
       if (outs[i][0].fatal) break;
     }
     std::cerr << summary; log << summary;
-    return finish_tracks(o, "", track_order, chroms.size(), track_failed, bintrack_failed, log) ? 0 : 1;
+    return finish_tracks(o, "", parts, chroms.size(), log) ? 0 : 1;
   }
 
   if (o.gpus <= 0 || !many) {   // the reference's own shape: one chromosome after the other on one context
     int st = 0;
     rsi_ctx* ctx = rsi_hot_create(o.device, &st);
     if (!ctx) { std::cerr << "rsicnv: " << rsi_hot_last_error(nullptr) << std::endl; return 1; }
-    std::vector<size_t> track_order;
-    bool track_failed = false, bintrack_failed = false;
+    TrackParts parts;
     for (size_t i = 0; i < todo.size(); ++i) {
       const std::string& chr = todo[i];
       ChromOutput co;
@@ -942,13 +1033,11 @@ int main(int argc, char** argv) {
         return 1;
       }
       emit(chr, co);
-      track_failed = track_failed || co.track_failed;
-      bintrack_failed = bintrack_failed || co.bintrack_failed;
-      if (co.populated) track_order.push_back(i);
+      parts.add(i, co);
       if (co.fatal) break;
     }
     rsi_hot_destroy(ctx);
-    return finish_tracks(o, "", track_order, todo.size(), track_failed, bintrack_failed, log) ? 0 : 1;
+    return finish_tracks(o, "", parts, todo.size(), log) ? 0 : 1;
   }
 
   // ---- -gpus N: the iterations of the loop are independent.  Chromosomes go to devices longest first
@@ -1006,14 +1095,11 @@ int main(int argc, char** argv) {
         }
       });
   for (auto& t : threads) t.join();
-  std::vector<size_t> track_order;
-  bool track_failed = false, bintrack_failed = false;
+  TrackParts parts;
   for (size_t i = 0; i < todo.size(); ++i) {
     emit(todo[i], outs[i]);
-    track_failed = track_failed || outs[i].track_failed;
-    bintrack_failed = bintrack_failed || outs[i].bintrack_failed;
-    if (outs[i].populated) track_order.push_back(i);
+    parts.add(i, outs[i]);
   }
   for (rsi_pool* pl : pools) rsi_pool_destroy(pl);
-  return finish_tracks(o, "", track_order, todo.size(), track_failed, bintrack_failed, log) ? 0 : 1;   // (-track, -bintrack: one device only, -gpus 1)
+  return finish_tracks(o, "", parts, todo.size(), log) ? 0 : 1;   // (-track, -bintrack: one device only, -gpus 1)
 }

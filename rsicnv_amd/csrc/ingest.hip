@@ -5,6 +5,7 @@
 #include "pipeline_internal.h"
 #include "inflate_core.h"
 #include "text_rules.h"
+#include "track_index_host.h"
 #include <memory>
 #include <unordered_set>
 #include <zlib.h>
@@ -155,6 +156,13 @@ struct DepthSource {
   std::vector<int64_t> foffs[2];   // file offsets of the members of each launch (messages)
   bool launched[2] = {false, false};
   hipEvent_t ev[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+  // BGZF read by index (open_range): the members [range_begin, range_stop) of the file alone.  The first one is inflated on the
+  // host when the range is opened, for the index checks; its text from the begin's in-member offset on goes in front of the
+  // first chunk like a tail.
+  bool ranged = false, first_pending = false, file_has_eof = false;
+  int64_t range_begin = 0, range_stop = 0;
+  size_t range_drop = 0;           // text of the range's last member behind the range's end: foreign lines, the last one cut short
+  std::vector<char> first_text;
 
   ~DepthSource() {
     if (gz) gzclose(gz);
@@ -200,13 +208,23 @@ struct DepthSource {
     foff[b] = foff[p] + (int64_t)len[p];
     last_nl[b] = -1;
     if (format == 1) {
+      size_t lead = tail;
+      int lead_nl = last_nl[p] >= (int)len[p] ? last_nl[p] - (int)len[p] : -1;
       if (tail) {
         const hipError_t e = hipMemcpyAsync(dev[b], static_cast<char*>(dev[p]) + len[p], tail, hipMemcpyDeviceToDevice, s);
         if (e != hipSuccess) return fail_(RSI_ERR_HIP, std::string("BGZF: ") + hipGetErrorString(e));
+      } else if (first_pending) {   // the range's first member, inflated by open_range: through pin[b], which a BGZF chunk does not use
+        first_pending = false;
+        lead = first_text.size();
+        memcpy(pin[b], first_text.data(), lead);
+        for (lead_nl = (int)lead - 1; lead_nl >= 0 && pin[b][lead_nl] != '\n';) --lead_nl;
+        const hipError_t e = hipMemcpyAsync(dev[b], pin[b], lead, hipMemcpyHostToDevice, s);
+        if (e != hipSuccess) return fail_(RSI_ERR_HIP, std::string("BGZF: ") + hipGetErrorString(e));
       }
       size_t added = 0;
-      const int rc = launch(b, tail, last_nl[p] >= (int)len[p] ? last_nl[p] - (int)len[p] : -1, s, added);
-      total[b] = len[b] = tail + added;
+      const int rc = launch(b, lead, lead_nl, s, added);
+      total[b] = len[b] = lead + added;
+      if (ranged && exhausted && added >= range_drop) { total[b] = len[b] = lead + added - range_drop; range_drop = 0; }   // (the launch that took the last member)
       return rc;
     }
     if (tail) memcpy(pin[b], pin[p] + len[p], tail);
@@ -288,6 +306,7 @@ struct DepthSource {
   // BGZF: the next members into dev[b] behind its `tail` bytes -- at most cap bytes of text in the buffer in all, one member
   // at least.  tail_nl: offset of the last line end in the tail (-1: none).  Queues the uploads, the inflate launch and its
   // status read-back on s.  added: text bytes added (0 with exhausted: the end).
+  void st_range_end() { st.eof_block = file_has_eof; }   // (the file's end-of-file block is not read: it is there or not all the same)
   int launch(int b, size_t tail, int tail_nl, hipStream_t s, size_t& added) {
     added = 0;
     launched[b] = false;
@@ -299,6 +318,7 @@ struct DepthSource {
     uint8_t* cp = cpin[b].as<uint8_t>();
     size_t comp = 0;
     while (!exhausted) {
+      if (ranged && cbuf_off + (int64_t)cpos >= range_stop) { exhausted = true; st_range_end(); break; }   // the range's end is the text's
       // the member's fixed header, its extra field (BSIZE), then all of it, as far as the file has them
       have_bytes(18);
       if (cbuf.size() - cpos >= 12) have_bytes(12 + ((size_t)cbuf[cpos + 10] | ((size_t)cbuf[cpos + 11] << 8)));
@@ -317,6 +337,7 @@ struct DepthSource {
       comp += m.clen; added += m.isize; cpos += m.bsize;
       st.compressed_bytes += m.bsize; st.text_bytes += m.isize; ++st.blocks;
       st.eof_block = m.isize == 0;
+      if (ranged && cbuf_off + (int64_t)cpos >= range_stop) { exhausted = true; st_range_end(); break; }   // the range's last member: the text ends with this chunk
     }
     if (tab.empty()) return RSI_OK;
     const size_t tb = tab.size() * sizeof(InflateBlock);
@@ -355,6 +376,97 @@ struct DepthSource {
                                         rsinf::err_name((int)(status & 0xff)));
     }
     memcpy(last_nl, w + 8, 4);
+    return RSI_OK;
+  }
+
+  // The member at compressed offset `at`, inflated on the host (zlib) with its CRC32 and ISIZE checked: "" or what is wrong with it
+  std::string host_member(int64_t at, rsinf::Member& m, std::vector<char>& text) {
+    std::vector<uint8_t> raw(kMemberMax);
+    const ssize_t got = at >= 0 && at < file_size ? pread(fd, raw.data(), raw.size(), (off_t)at) : 0;
+    const std::string bad = bgzf_member_error(raw.data(), got > 0 ? (size_t)got : 0, at, m);
+    if (!bad.empty()) return bad;
+    text.assign(m.isize, 0);
+    z_stream z;
+    memset(&z, 0, sizeof(z));
+    if (inflateInit2(&z, -15) != Z_OK) return "zlib: inflateInit2 failed";
+    z.next_in = raw.data() + m.hdr; z.avail_in = m.clen;
+    Bytef spare = 0;
+    z.next_out = m.isize ? reinterpret_cast<Bytef*>(text.data()) : &spare; z.avail_out = m.isize;
+    const int zr = inflate(&z, Z_FINISH);
+    const bool whole = zr == Z_STREAM_END && z.avail_out == 0 && z.avail_in == 0;
+    inflateEnd(&z);
+    if (!whole || (uint32_t)crc32(crc32(0L, Z_NULL, 0), reinterpret_cast<const Bytef*>(text.data()), m.isize) != m.crc)
+      return "BGZF: the member at compressed offset " + std::to_string((long long)at) + " is bad";
+    return std::string();
+  }
+
+  // The sequence name that begins text[at ...], as far as the member holds it (whole: a delimiter ends it inside the member)
+  static std::string name_at(const std::vector<char>& text, size_t at, bool& whole) {
+    size_t k = at;
+    while (k < text.size() && text[k] != '\t' && text[k] != ' ' && text[k] != '\n') ++k;
+    whole = k < text.size();
+    return std::string(text.data() + at, k - at);
+  }
+  static bool names_it(const std::vector<std::string>& names, const std::string& got, bool whole) {
+    for (const std::string& n : names)
+      for (const std::string& form : {n, "chr" + n, n.compare(0, 3, "chr") == 0 ? n.substr(3) : n})
+        if (whole ? form == got : form.compare(0, got.size(), got) == 0) return true;
+    return false;
+  }
+
+  // After open_(): the file is read from the smallest chunk begin to the largest chunk end that the index (.tbi or .csi) holds
+  // for `names`, and nothing else of it.  An index that does not fit the file -- a begin that is no member header or lies
+  // behind a byte other than a line end, a first line of another sequence, a line of the sequences directly behind the end --
+  // is RSI_ERR_BAD_ARG naming the index: never quiet wrong depth.  No line for any name: the range is empty.
+  int open_range(const std::string& index_path, const std::vector<std::string>& names) {
+    if (format != 1) return fail_(RSI_ERR_BAD_ARG, "index " + index_path + ": " + path + " is not BGZF, an index cannot be used with it");
+    rsitbx::FileIndex ix;
+    std::string why;
+    if (!rsitbx::read_index(index_path, ix, why)) return fail_(RSI_ERR_BAD_ARG, why);
+    uint64_t beg = rsitbx::kNoOffset, end = 0;
+    for (const std::string& n : names) {
+      uint64_t b = 0, e = 0;
+      if (rsitbx::locate(ix, n, b, e)) { beg = std::min(beg, b); end = std::max(end, e); }
+    }
+    uint8_t tail28[rsitrack::kBgzfEofBytes];
+    file_has_eof = file_size >= (int64_t)sizeof(tail28) && pread(fd, tail28, sizeof(tail28), (off_t)(file_size - (int64_t)sizeof(tail28))) == (ssize_t)sizeof(tail28) &&
+                   memcmp(tail28, rsitrack::bgzf_eof(), sizeof(tail28)) == 0;
+    ranged = true;
+    if (end <= beg) { range_begin = range_stop = 0; return RSI_OK; }   // nothing to read: the reader finds no sequence
+    auto misfit = [&](const std::string& what) { return fail_(RSI_ERR_BAD_ARG, "index " + index_path + " does not fit " + path + ": " + what); };
+    const int64_t cb = (int64_t)(beg >> 16), ce = (int64_t)(end >> 16);
+    const size_t ub = (size_t)(beg & 0xffff), ue = (size_t)(end & 0xffff);
+    rsinf::Member mb, me;
+    std::vector<char> tb, te;
+    std::string bad = host_member(cb, mb, tb);
+    if (!bad.empty()) return misfit("its range begins where no sound member does (" + bad + ")");
+    if (ub >= tb.size()) return misfit("its range begins behind the text of the member at compressed offset " + std::to_string((long long)cb));
+    if (ub > 0 && tb[ub - 1] != '\n') return misfit("its range begins inside a line (compressed offset " + std::to_string((long long)cb) + ", text offset " + std::to_string(ub) + ")");
+    bool whole = false;
+    const std::string first = name_at(tb, ub, whole);
+    if (!names_it(names, first, whole)) return misfit("the first line of its range names " + first);
+    range_begin = cb;
+    range_stop = ce;
+    if (ue > 0) {   // the range ends inside the member at ce: read to that member's end, and look at what follows the range in it
+      if (ce == cb) { me = mb; te = tb; }
+      else if (!(bad = host_member(ce, me, te)).empty()) return misfit("its range ends where no sound member is (" + bad + ")");
+      if (ue > te.size()) return misfit("its range ends behind the text of the member at compressed offset " + std::to_string((long long)ce));
+      if (ue < te.size()) {
+        const std::string next = name_at(te, ue, whole);
+        if (names_it(names, next, whole)) return misfit("a line of " + next + " follows the end of its range");
+      }
+      range_stop = ce + (int64_t)me.bsize;
+      range_drop = te.size() - ue;   // what follows the range in its last member is foreign by construction: not handed on
+    }
+    if (range_stop <= cb || range_stop > file_size) return misfit("its range ends in front of its begin, or behind the file");
+    // the first member is taken: its text from ub on leads the first chunk; the chunks go on with the member behind it
+    first_text.assign(tb.begin() + (ptrdiff_t)ub, ce == cb && ue > 0 ? tb.begin() + (ptrdiff_t)ue : tb.end());
+    if (ce == cb) range_drop = 0;
+    first_pending = true;
+    index.emplace_back(-(int64_t)ub, cb);
+    st.compressed_bytes += mb.bsize; st.text_bytes += mb.isize; ++st.blocks;
+    cbuf_off = cb + (int64_t)mb.bsize;
+    if (lseek(fd, (off_t)cbuf_off, SEEK_SET) != (off_t)cbuf_off) return fail_(RSI_ERR_INTERNAL, "cannot seek in " + path);
     return RSI_OK;
   }
 
@@ -1205,7 +1317,8 @@ namespace {
 
 // rsi_genome_text_open (cols == nullptr), rsi_genome_text_open_samples and rsi_genome_bedgraph_open (bed)
 rsi_genome_text* genome_text_open(const char* fn, int device, const char* path, int nref, const char* const* names, const int64_t* lengths,
-                                  const int32_t* cols, int ncols, int max_resident, size_t chunk_bytes, int* status, bool bed = false) {
+                                  const int32_t* cols, int ncols, int max_resident, size_t chunk_bytes, int* status, bool bed = false,
+                                  const char* index_path = nullptr) {
   int st_local = 0;
   int* st = status ? status : &st_local;
   *st = RSI_OK;
@@ -1257,6 +1370,7 @@ rsi_genome_text* genome_text_open(const char* fn, int device, const char* path, 
       g->max_resident = (int)std::min<size_t>((size_t)max_resident, fit);
     }
     if (int rc = g->src.open_(path)) { set_global_error(g->src.err); return bad(rc); }
+    if (index_path) if (int rc = g->src.open_range(index_path, g->ref_names)) { set_global_error(g->src.err); return bad(rc); }
     if (g->src.format == 1) {
       g->chunk = std::max(g->chunk, kBgzfMinChunk);   // whole members per chunk
       if (hipStreamCreateWithFlags(&g->istream, hipStreamNonBlocking) != hipSuccess ||
@@ -1325,6 +1439,23 @@ rsi_genome_text* rsi_genome_text_open_samples(int device, const char* path, int 
 rsi_genome_text* rsi_genome_bedgraph_open(int device, const char* path, int nref, const char* const* names, const int64_t* lengths,
                                           int max_resident, size_t chunk_bytes, int* status) {
   return genome_text_open("rsi_genome_bedgraph_open", device, path, nref, names, lengths, nullptr, 0, max_resident, chunk_bytes, status, true);
+}
+
+rsi_genome_text* rsi_genome_bedgraph_open_indexed(int device, const char* path, const char* index_path, int nref, const char* const* names,
+                                                  const int64_t* lengths, int max_resident, size_t chunk_bytes, int* status) {
+  if (!index_path || !index_path[0]) {
+    set_global_error("rsi_genome_bedgraph_open_indexed: no index");
+    if (status) *status = RSI_ERR_BAD_ARG;
+    return nullptr;
+  }
+  return genome_text_open("rsi_genome_bedgraph_open_indexed", device, path, nref, names, lengths, nullptr, 0, max_resident, chunk_bytes, status, true, index_path);
+}
+
+int rsi_genome_text_index_range(const rsi_genome_text* g, int64_t* begin, int64_t* stop) {
+  if (!g || !g->src.ranged) return RSI_ERR_BAD_ARG;
+  if (begin) *begin = g->src.range_begin;
+  if (stop) *stop = g->src.range_stop;
+  return RSI_OK;
 }
 
 int rsi_genome_text_samples(const rsi_genome_text* g) { return g ? g->ncols() : RSI_ERR_BAD_ARG; }

@@ -604,4 +604,31 @@ void launch_deflate_bgzf(const void* text, long long nbytes, void* slots, unsign
 void launch_bgzf_pack(const void* slots, const unsigned int* sizes, int nmembers, void* packed, long long cap, TrackState* st,
                       hipStream_t stream);
 
+// ---- the tabix index of a BGZF track: a slice's chunk starts and window starts (kernels_track.hip) ----
+// Run behind a slice's deflate and pack launches.  Line j of the slice (0-based half-open [s, e), e' = e - 1) lies at text offset t
+// (the ltiles prefix plus the scan of the line lengths, as in the format pass); its virtual offset, relative to the slice's first
+// packed byte, is (sum of sizes[0, t / 65280)) << 16 | t % 65280.  Two record lists, each gathered workgroup by workgroup behind an
+// atomic counter (in line order inside a workgroup; the host sorts by voff, which is unique per line):
+//   chunk starts  {voff, a = reg2bin(s, e)}:       j == 0 or the bin differs from line j - 1's
+//   window starts {voff, a = w_first, b = w_last}: j == 0 (w_first = s >> 14: the host knows how far the slices before reached) or
+//                                                  e'_j >> 14 > e'_(j-1) >> 14, w_first = max(s_j >> 14, (e'_(j-1) >> 14) + 1)
+// with w_last = e'_j >> 14.  A count above its capacity says that records are missing: nothing is written past a capacity.
+struct TrackIndexRec { unsigned long long voff; unsigned int a, b; };
+struct TrackIndexHead { unsigned int nchunk, nwin, bad, pad; };   // bad: more members than the kernel's LDS table holds
+constexpr int kTrackIndexMembers = 515;                            // members of a slice at most (track_host.h: kMaxMembers)
+// One allocation per slice: the head, chunk_cap chunk records, win_cap window records
+struct TrackIndexOut { TrackIndexHead* head; TrackIndexRec* chunks; unsigned int chunk_cap; TrackIndexRec* wins; unsigned int win_cap; };
+inline size_t track_index_bytes(unsigned int chunk_cap, unsigned int win_cap) {
+  return sizeof(TrackIndexHead) + ((size_t)chunk_cap + win_cap) * sizeof(TrackIndexRec);
+}
+inline TrackIndexOut track_index_out(void* base, unsigned int chunk_cap, unsigned int win_cap) {
+  TrackIndexRec* r = reinterpret_cast<TrackIndexRec*>(static_cast<char*>(base) + sizeof(TrackIndexHead));
+  return TrackIndexOut{static_cast<TrackIndexHead*>(base), r, chunk_cap, r + chunk_cap, win_cap};
+}
+// out.head zeroed by the caller on the same stream; nlines > 0; pos0 >= 0
+void launch_track_index(const int32_t* v, const long long* starts, const unsigned int* ltiles, long long nlines, long long pos0, int name_len,
+                        const unsigned int* sizes, int nmembers, const TrackIndexOut& out, hipStream_t stream);
+void launch_bintrack_index(const BinTrackSource& src, const unsigned int* ltiles, long long nlines, int name_len, const unsigned int* sizes,
+                           int nmembers, const TrackIndexOut& out, hipStream_t stream);
+
 }  // namespace rsik

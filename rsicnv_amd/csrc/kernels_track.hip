@@ -269,7 +269,99 @@ struct BinLines {
   }
 };
 
+// ---- the index pass: one thread per line, as the format pass (kernels.h states the records) ----
+// tabix's reg2bin of [s, e1], e1 the line's last base: the first level at which both fall into one bin
+__device__ inline unsigned int reg2bin(long long s, long long e1) {
+  if (s >> 14 == e1 >> 14) return 4681u + (unsigned int)(s >> 14);
+  if (s >> 17 == e1 >> 17) return 585u + (unsigned int)(s >> 17);
+  if (s >> 20 == e1 >> 20) return 73u + (unsigned int)(s >> 20);
+  if (s >> 23 == e1 >> 23) return 9u + (unsigned int)(s >> 23);
+  if (s >> 26 == e1 >> 26) return 1u + (unsigned int)(s >> 26);
+  return 0u;
+}
+
+template <class Lines, class Value>
+__global__ __launch_bounds__(kTrackTile) void k_track_index(Lines src, Value fmt, const unsigned int* __restrict__ ltiles, long long nlines, long long pos0,
+                                                            int name_len, const unsigned int* __restrict__ sizes, int nmembers, TrackIndexOut out) {
+  __shared__ unsigned int s_w[kTrackTile / 64];
+  __shared__ unsigned int s_front[kTrackIndexMembers + 1];   // compressed bytes in front of every member of the slice
+  __shared__ unsigned int s_base[2];
+  if (nmembers > kTrackIndexMembers) {   // (the host plans at most that many: never)
+    if (blockIdx.x == 0 && threadIdx.x == 0) out.head->bad = 1u;
+    return;
+  }
+  for (int k = threadIdx.x; k < nmembers; k += kTrackTile) s_front[k] = sizes[k] & 0x7fffffffu;   // bit 31: a stored member
+  __syncthreads();
+  (void)scan_tile_words(s_front, nmembers, 0u, s_w);
+  __syncthreads();
+
+  const long long j = (long long)blockIdx.x * kTrackTile + threadIdx.x;
+  const bool live = j < nlines;
+  LineShape L;
+  const unsigned int len = live ? (unsigned int)line_shape(src, fmt, j, pos0, name_len, L) : 0u;
+  unsigned int total;
+  const unsigned long long off = (unsigned long long)ltiles[blockIdx.x] + wg_exscan_u32(len, s_w, &total);
+  unsigned int cflag = 0u, wflag = 0u, bin = 0u, w_first = 0u, w_last = 0u;
+  unsigned long long voff = 0ull;
+  if (live) {
+    const long long e1 = L.e - 1;
+    bin = reg2bin(L.s, e1);
+    w_first = (unsigned int)(L.s >> 14);
+    w_last = (unsigned int)(e1 >> 14);
+    cflag = wflag = 1u;
+    if (j > 0) {
+      long long ps, pe; int pv;
+      src.get(j - 1, ps, pe, pv);
+      const long long p1 = pe + pos0 - 1;
+      cflag = reg2bin(ps + pos0, p1) != bin ? 1u : 0u;
+      wflag = (e1 >> 14) > (p1 >> 14) ? 1u : 0u;
+      const unsigned int reached = (unsigned int)(p1 >> 14) + 1u;
+      if (reached > w_first) w_first = reached;
+    }
+    const unsigned int member = (unsigned int)(off / kDeflateMemberText);
+    const unsigned int front = member < (unsigned int)nmembers ? s_front[member] : 0u;
+    voff = (unsigned long long)front << 16 | (off - (unsigned long long)member * kDeflateMemberText);
+  }
+  unsigned int ctot, wtot;
+  const unsigned int crank = wg_exscan_u32(cflag, s_w, &ctot);
+  const unsigned int wrank = wg_exscan_u32(wflag, s_w, &wtot);
+  if (threadIdx.x == 0) {
+    s_base[0] = ctot ? atomicAdd(&out.head->nchunk, ctot) : 0u;
+    s_base[1] = wtot ? atomicAdd(&out.head->nwin, wtot) : 0u;
+  }
+  __syncthreads();
+  if (cflag) {
+    const unsigned int k = s_base[0] + crank;
+    if (k < out.chunk_cap) out.chunks[k] = TrackIndexRec{voff, bin, 0u};
+  }
+  if (wflag) {
+    const unsigned int k = s_base[1] + wrank;
+    if (k < out.win_cap) out.wins[k] = TrackIndexRec{voff, w_first, w_last};
+  }
+}
+
 }  // namespace
+
+void launch_track_index(const int32_t* v, const long long* starts, const unsigned int* ltiles, long long nlines, long long pos0, int name_len,
+                        const unsigned int* sizes, int nmembers, const TrackIndexOut& out, hipStream_t stream) {
+  const int ntiles = track_tiles(nlines);
+  if (ntiles <= 0) return;
+  RSI_LAUNCH((k_track_index<RunLines, DecValue>), dim3(ntiles), dim3(kTrackTile), 0, stream, RunLines{v, starts}, DecValue{}, ltiles, nlines, pos0, name_len,
+             sizes, nmembers, out);
+}
+
+void launch_bintrack_index(const BinTrackSource& src, const unsigned int* ltiles, long long nlines, int name_len, const unsigned int* sizes,
+                           int nmembers, const TrackIndexOut& out, hipStream_t stream) {
+  const int ntiles = track_tiles(nlines);
+  if (ntiles <= 0) return;
+  const BinLines lines{src.v, src.pieces, BinTable{src.cbreak, src.cum, src.nreg, src.m}, src.b0};
+  if (src.which == 1)
+    RSI_LAUNCH((k_track_index<BinLines, RatioValue>), dim3(ntiles), dim3(kTrackTile), 0, stream, lines, RatioValue{src.median2}, ltiles, nlines, 0ll, name_len,
+               sizes, nmembers, out);
+  else
+    RSI_LAUNCH((k_track_index<BinLines, DecValue>), dim3(ntiles), dim3(kTrackTile), 0, stream, lines, DecValue{}, ltiles, nlines, 0ll, name_len,
+               sizes, nmembers, out);
+}
 
 void launch_track_starts(const int32_t* v, long long b, long long e, long long n, unsigned int* tiles, long long* starts, TrackState* st,
                          hipStream_t stream) {

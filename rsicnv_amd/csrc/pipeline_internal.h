@@ -207,10 +207,12 @@ struct rsi_ctx {
     void* dev = nullptr; size_t dev_bytes = 0;           // text, starts or pieces, tiles, line tiles, state, the bin track's region table; BGZF: sizes, slots, packed members
     char* pin[2] = {nullptr, nullptr}; size_t pin_bytes = 0;   // two text buffers: one is written to the file while the other fills
     void* pin_state = nullptr;                           // two TrackState: the device's, read back per slice; the initial one
-    hipEvent_t ev[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t ev[12] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    void* idx_dev = nullptr; char* idx_pin = nullptr; size_t idx_bytes = 0;   // an indexed BGZF track: a slice's index records, in HBM and pinned
   } track;
   int track_format = RSI_TRACK_TEXT;         // rsi_hot_set_track_format
   rsi_deflate_stats last_deflate{};          // of the last track call (rsi_hot_last_deflate_stats)
+  rsi_track_index* track_index = nullptr;    // rsi_hot_set_track_index: the caller's, filled by every BGZF track call while set
 };
 
 namespace rsip {

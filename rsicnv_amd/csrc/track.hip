@@ -7,6 +7,9 @@
 // DESIGN.md 6f, 6g and 6h.
 #include "pipeline_internal.h"
 #include "track_host.h"
+#include "track_index_host.h"
+#include <sys/stat.h>
+#include <new>
 
 using namespace rsik;
 using namespace rsip;
@@ -19,6 +22,9 @@ void track_free(rsi_ctx* ctx) {
   for (char*& p : w.pin) { if (p) (void)hipHostFree(p); p = nullptr; }
   if (w.pin_state) (void)hipHostFree(w.pin_state);
   for (hipEvent_t& e : w.ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+  if (w.idx_dev) (void)hipFree(w.idx_dev);
+  if (w.idx_pin) (void)hipHostFree(w.idx_pin);
+  w.idx_dev = nullptr; w.idx_pin = nullptr; w.idx_bytes = 0;
   w.dev = w.pin_state = nullptr; w.dev_bytes = w.pin_bytes = 0;
 }
 
@@ -30,14 +36,15 @@ namespace {
 struct TrackSink {
   int fd = -1;
   std::string* text = nullptr;
+  int64_t base = 0;   // bytes the file held before this call (what an index adds to its offsets)
   bool put(const char* p, size_t len) {
     if (text) { text->append(p, len); return true; }
     return rsitrack::write_all(fd, p, len);
   }
 };
 
-// events: the measuring passes; per pinned buffer: format begin / end, copy done, deflate and pack done
-enum { kEvP0, kEvP1, kEvF0, kEvF1 = kEvF0 + 2, kEvCopy = kEvF1 + 2, kEvD1 = kEvCopy + 2, kEvCount = kEvD1 + 2 };
+// events: the measuring passes; per pinned buffer: format begin / end, copy done, deflate and pack done, index pass done
+enum { kEvP0, kEvP1, kEvF0, kEvF1 = kEvF0 + 2, kEvCopy = kEvF1 + 2, kEvD1 = kEvCopy + 2, kEvX1 = kEvD1 + 2, kEvCount = kEvX1 + 2 };
 static_assert(kEvCount == sizeof(rsi_ctx::TrackWs::ev) / sizeof(hipEvent_t), "one event per use");
 
 struct TrackLayout {
@@ -108,16 +115,48 @@ int track_ensure(rsi_ctx* ctx, const TrackLayout& L) {
   return RSI_OK;
 }
 
+// The index side of a call (null / off without rsi_hot_set_track_index): the builder, the call's name and file offset, and where a
+// slice's records go on the device and in pinned memory.  A slice's records are laid out for its own capacities, so that one
+// copy of exactly track_index_bytes() brings them over.
+struct TrackIndexer {
+  rsi_track_index* ix = nullptr;
+  std::string name;
+  int64_t base = 0;                   // the file's size before this call
+  unsigned int chunk_cap = 0, win_cap = 0;   // of the slice whose records lie in pinned memory (or are on their way there)
+  bool on() const { return ix != nullptr; }
+};
+int track_index_ensure(rsi_ctx* ctx, size_t bytes) {
+  rsi_ctx::TrackWs& w = ctx->track;
+  if (bytes <= w.idx_bytes) return RSI_OK;
+  if (w.idx_dev) (void)hipFree(w.idx_dev);
+  if (w.idx_pin) (void)hipHostFree(w.idx_pin);
+  w.idx_dev = nullptr; w.idx_pin = nullptr; w.idx_bytes = 0;
+  HIPCHK(hipMalloc(&w.idx_dev, bytes));
+  HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&w.idx_pin), bytes, hipHostMallocDefault));
+  w.idx_bytes = bytes;
+  return RSI_OK;
+}
+// What every indexed call checks before it writes anything
+int track_index_admit(rsi_ctx* ctx, bool bgzf, int64_t last_end) {
+  if (!bgzf) return fail(ctx, RSI_ERR_BAD_ARG, "track: an index is set (rsi_hot_set_track_index) and the format is text: only a BGZF track is indexed");
+  if (last_end > rsitbx::kMaxEnd) return fail(ctx, RSI_ERR_UNSUPPORTED, "track: a line would end beyond 2^29 = 536870912, the limit of a tabix index");
+  return RSI_OK;
+}
+
 // The slices of one call, whatever their lines come from: per slice [b, end) of `count` items, measure(b, end) queues the passes
 // that find and measure its lines; one wait for the state's two numbers, checked against max_lines(b, end), text_cap and
 // max_line; format(b, nlines) queues the format pass, the text is copied into one of the two pinned buffers, and the slice
 // before goes to the sink meanwhile.  With z.on() the format pass is followed by the deflate and pack passes, and what is copied
 // are the packed members: their length is read together with the NEXT slice's state (the same stream: the pack is done by then),
 // so the copy is issued one slice later and a slice still costs one wait; the last slice's length takes one wait of its own,
-// once a call.  Nothing of the call is still queued when this returns.
-template <class Measure, class MaxLines, class Format>
+// once a call.  With X.on() (a BGZF call) windows(b, end) bounds the 16 384-base windows the slice's lines span and
+// index(b, nlines, nbytes, out) queues the index pass behind the pack; its records are copied at once, for the slice's capacities,
+// and read where the slice's compressed size is read: behind a wait the slice has anyway.  Nothing of the call is still queued
+// when this returns.
+template <class Measure, class MaxLines, class Format, class Windows, class Index>
 int track_slices(rsi_ctx* ctx, int64_t count, int64_t slice, int64_t text_cap, int64_t max_line, TrackState* d_st, const char* d_text,
-                 TrackSink& sink, rsi_track_stats& S, TrackBgzf& z, Measure measure, MaxLines max_lines, Format format) {
+                 TrackSink& sink, rsi_track_stats& S, TrackBgzf& z, TrackIndexer& X, Measure measure, MaxLines max_lines, Format format,
+                 Windows windows, Index index) {
   rsi_ctx::TrackWs& w = ctx->track;
   TrackState* h_st = static_cast<TrackState*>(w.pin_state);
   hipStream_t st = ctx->stream;
@@ -135,6 +174,7 @@ int track_slices(rsi_ctx* ctx, int64_t count, int64_t slice, int64_t text_cap, i
     if (ew != hipSuccess) return fail(ctx, RSI_ERR_HIP, std::string("track: waiting for a slice's text: ") + hipGetErrorString(ew));
     S.t_kernel_ms += elapsed(kEvF0 + pending, kEvF1 + pending);
     if (z.on()) z.D.t_kernel_ms += elapsed(kEvF1 + pending, kEvD1 + pending);
+    if (X.on()) S.t_kernel_ms += elapsed(kEvD1 + pending, kEvX1 + pending);
     const double t0 = now_ms();
     const bool ok = sink.put(w.pin[pending], (size_t)pending_bytes);
     const int err = errno;
@@ -150,6 +190,15 @@ int track_slices(rsi_ctx* ctx, int64_t count, int64_t slice, int64_t text_cap, i
     const int64_t members = rsitrack::members_of(packed_text), bytes = h_st[0].packed, stored = h_st[0].stored;
     if (bytes <= 0 || bytes > packed_text + members * rsitrack::kMemberOverhead || bytes > z.packed_cap || stored < 0 || stored > members)
       return leave(RSI_ERR_INTERNAL, "track: a slice's compressed size is out of range");
+    if (X.on()) {   // the slice's records: copied behind its index pass, in front of the wait that brought `bytes`
+      const TrackIndexOut r = track_index_out(w.idx_pin, X.chunk_cap, X.win_cap);
+      if (r.head->bad || r.head->nchunk > r.chunk_cap || r.head->nwin > r.win_cap)
+        return leave(RSI_ERR_INTERNAL, "track: a slice's index records are out of range");
+      static_assert(sizeof(rsitbx::Rec) == sizeof(TrackIndexRec), "the builder reads the device's records");
+      const int k = X.ix->add_slice(X.name, X.base + z.D.file_bytes, bytes, reinterpret_cast<const rsitbx::Rec*>(r.chunks), r.head->nchunk,
+                                    reinterpret_cast<const rsitbx::Rec*>(r.wins), r.head->nwin);
+      if (k != rsitbx::kOk) return leave(k == rsitbx::kUnsupported ? RSI_ERR_UNSUPPORTED : RSI_ERR_INTERNAL, X.ix->err);
+    }
     z.D.members += members;
     z.D.stored_members += stored;
     z.D.text_bytes += packed_text;
@@ -190,6 +239,18 @@ int track_slices(rsi_ctx* ctx, int64_t count, int64_t slice, int64_t text_cap, i
         launch_deflate_bgzf(d_text, nbytes, z.slots, z.sizes, st);
         launch_bgzf_pack(z.slots, z.sizes, deflate_members(nbytes), z.packed, z.packed_cap, d_st, st);
         (void)hipEventRecord(w.ev[kEvD1 + fresh], st);
+        if (X.on()) {
+          const int64_t span = windows(b, end);
+          X.chunk_cap = rsitbx::chunk_capacity(span); X.win_cap = rsitbx::window_capacity(span);
+          const size_t xbytes = track_index_bytes(X.chunk_cap, X.win_cap);
+          if (xbytes > w.idx_bytes) return leave(RSI_ERR_INTERNAL, "track: a slice's index records do not fit their buffer");
+          e = hipMemsetAsync(w.idx_dev, 0, sizeof(TrackIndexHead), st);
+          if (e != hipSuccess) return hip_failed(e, "hipMemsetAsync");
+          index(b, nlines, nbytes, track_index_out(w.idx_dev, X.chunk_cap, X.win_cap));
+          (void)hipEventRecord(w.ev[kEvX1 + fresh], st);
+          e = hipMemcpyAsync(w.idx_pin, w.idx_dev, xbytes, hipMemcpyDeviceToHost, st);
+          if (e != hipSuccess) return hip_failed(e, "hipMemcpyAsync");
+        }
       } else {
         e = hipMemcpyAsync(w.pin[fresh], d_text, (size_t)nbytes, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipEventRecord(w.ev[kEvCopy + fresh], st);
@@ -227,6 +288,13 @@ int track_run(rsi_ctx* ctx, const int32_t* d_v, int64_t n, const char* chrom, in
   rsitrack::Plan plan;
   if (!rsitrack::plan(name_len, pos0, n, slice_bases, plan)) return fail(ctx, RSI_ERR_BAD_ARG, "track: bad length or coordinate offset");
   S.n = n;
+  TrackIndexer X;
+  if (ctx->track_index) {
+    const int rc = track_index_admit(ctx, bgzf, pos0 + n);
+    if (rc != RSI_OK) return rc;
+    if (pos0 < 0) return fail(ctx, RSI_ERR_BAD_ARG, "track: an indexed track has no negative coordinates");
+    X.ix = ctx->track_index; X.name.assign(chrom, (size_t)name_len); X.base = sink.base;
+  }
   if (n == 0) { if (stats) *stats = S; return RSI_OK; }
   if (!d_v) return fail(ctx, RSI_ERR_BAD_ARG, "track: no values");
   HIPCHK(hipSetDevice(ctx->device));
@@ -234,6 +302,8 @@ int track_run(rsi_ctx* ctx, const int32_t* d_v, int64_t n, const char* chrom, in
   const TrackLayout L = track_layout(plan, bgzf);
   int rc = track_ensure(ctx, L);
   if (rc != RSI_OK) return rc;
+  // a slice's lines end inside it: they span the windows of its plan.slice bases, one more where it does not start on a boundary
+  if (X.on() && (rc = track_index_ensure(ctx, track_index_bytes(rsitbx::chunk_capacity(plan.slice / 16384 + 2), rsitbx::window_capacity(plan.slice / 16384 + 2)))) != RSI_OK) return rc;
   rsi_ctx::TrackWs& w = ctx->track;
   TrackBgzf z;
   if (bgzf) z.place(w.dev, L);
@@ -252,18 +322,31 @@ int track_run(rsi_ctx* ctx, const int32_t* d_v, int64_t n, const char* chrom, in
   h_st[1] = TrackState{-1, 0, 0, 0, 0, 0};
   const hipError_t e = hipMemcpyAsync(d_st, &h_st[1], sizeof(TrackState), hipMemcpyHostToDevice, st);
   if (e != hipSuccess) { (void)ctx_sync(ctx); return fail(ctx, RSI_ERR_HIP, std::string("track: hipMemcpyAsync: ") + hipGetErrorString(e)); }
-  rc = track_slices(ctx, n, plan.slice, plan.text_cap, plan.max_line, d_st, d_text, sink, S, z,
+  rc = track_slices(ctx, n, plan.slice, plan.text_cap, plan.max_line, d_st, d_text, sink, S, z, X,
       [&](int64_t b, int64_t end) {
         launch_track_starts(d_v, b, end, n, d_tiles, d_starts, d_st, st);
         launch_track_line_bytes(d_v, d_starts, d_st, pos0, name_len, end - b + 1, d_ltiles, st);
       },
       [](int64_t b, int64_t end) { return end - b + 1; },
-      [&](int64_t, int64_t nlines) { launch_track_format(d_v, d_starts, d_ltiles, nlines, pos0, name, d_text, plan.text_cap, st); });
+      [&](int64_t, int64_t nlines) { launch_track_format(d_v, d_starts, d_ltiles, nlines, pos0, name, d_text, plan.text_cap, st); },
+      // the lines a slice writes end in (b, end]: their last bases, which decide both record kinds, lie in [pos0 + b, pos0 + end)
+      [&](int64_t b, int64_t end) { return rsitbx::windows_spanned(pos0 + b, pos0 + end); },
+      [&](int64_t, int64_t nlines, int64_t nbytes, const TrackIndexOut& out) {
+        launch_track_index(d_v, d_starts, d_ltiles, nlines, pos0, name_len, z.sizes, deflate_members(nbytes), out, st);
+      });
   if (rc != RSI_OK) return rc;
   S.t_total_ms = now_ms() - t_begin;
   if (stats) *stats = S;
   ctx->last_deflate = z.D;
   return RSI_OK;
+}
+
+// the size of the sink's file as it was opened (appended to, or truncated): sink.base
+bool sink_base(TrackSink& sink) {
+  struct stat sb;
+  if (::fstat(sink.fd, &sb) != 0) return false;
+  sink.base = (int64_t)sb.st_size;
+  return true;
 }
 
 int track_to_file(rsi_ctx* ctx, const int32_t* d_v, int64_t n, const char* chrom, const char* path, int append, rsi_track_stats* stats) {
@@ -272,6 +355,7 @@ int track_to_file(rsi_ctx* ctx, const int32_t* d_v, int64_t n, const char* chrom
   TrackSink sink;
   sink.fd = ::open(path, O_WRONLY | O_CREAT | (append ? O_APPEND : O_TRUNC), 0644);
   if (sink.fd < 0) return fail(ctx, RSI_ERR_INTERNAL, std::string("track: cannot open ") + path + ": " + strerror(errno));
+  if (!sink_base(sink)) { const int err = errno; (void)::close(sink.fd); return fail(ctx, RSI_ERR_INTERNAL, std::string("track: cannot size ") + path + ": " + strerror(err)); }
   int rc = track_run(ctx, d_v, n, chrom, 0, 0, sink, stats);
   if (::close(sink.fd) != 0 && rc == RSI_OK) rc = fail(ctx, RSI_ERR_INTERNAL, std::string("track: write failed: ") + strerror(errno));
   return rc;
@@ -298,6 +382,16 @@ int bin_track_run(rsi_ctx* ctx, const int32_t* d_v, int64_t nb, int m, int64_t n
   if (m < 1 || !rsitrack::bin_plan(name_len, n, nb, nreg, which, slice_bins, plan)) return fail(ctx, RSI_ERR_BAD_ARG, "bin track: bad bin count, bin size or region count");
   if (nb > (n - cum.back()) / m) return fail(ctx, RSI_ERR_BAD_ARG, "bin track: more bins than the kept bases hold");
   S.n = nb;
+  TrackIndexer X;
+  if (ctx->track_index) {
+    const int rc = track_index_admit(ctx, bgzf, n);
+    if (rc != RSI_OK) return rc;
+    X.ix = ctx->track_index; X.name.assign(chrom, (size_t)name_len); X.base = sink.base;
+  }
+  // where the compacted position p lies on the chromosome (rsih::compact_table's rule, as the kernels')
+  auto genomic = [&](int64_t p) { return p + cum[(size_t)(std::upper_bound(cbreak.begin(), cbreak.end(), p) - cbreak.begin())]; };
+  // bins [b, end) hold slice_bins m kept bases and the removed regions between them: from the first one's base to the last one's
+  auto bin_windows = [&](int64_t b, int64_t end) { return rsitbx::windows_spanned(genomic(b * m), genomic(end * m - 1) + 1); };
   if (nb == 0) { if (stats) *stats = S; return RSI_OK; }
   if (!d_v) return fail(ctx, RSI_ERR_BAD_ARG, "bin track: no values");
   HIPCHK(hipSetDevice(ctx->device));
@@ -305,6 +399,11 @@ int bin_track_run(rsi_ctx* ctx, const int32_t* d_v, int64_t nb, int m, int64_t n
   const TrackLayout L = track_layout(plan.text_cap, plan.max_pieces, plan.slice, plan.max_pieces, (size_t)2 * nreg + 1, bgzf);
   int rc = track_ensure(ctx, L);
   if (rc != RSI_OK) return rc;
+  if (X.on()) {
+    int64_t span = 0;
+    for (int64_t b = 0; b < nb; b += plan.slice) span = std::max(span, bin_windows(b, std::min(nb, b + plan.slice)));
+    if ((rc = track_index_ensure(ctx, track_index_bytes(rsitbx::chunk_capacity(span), rsitbx::window_capacity(span)))) != RSI_OK) return rc;
+  }
   rsi_ctx::TrackWs& w = ctx->track;
   TrackBgzf z;
   if (bgzf) z.place(w.dev, L);
@@ -327,14 +426,19 @@ int bin_track_run(rsi_ctx* ctx, const int32_t* d_v, int64_t nb, int m, int64_t n
   const hipError_t e = hipMemcpyAsync(d_cbreak, table.data(), table.size() * 8, hipMemcpyHostToDevice, st);
   if (e != hipSuccess) { (void)ctx_sync(ctx); return fail(ctx, RSI_ERR_HIP, std::string("bin track: hipMemcpyAsync: ") + hipGetErrorString(e)); }
   BinTrackSource src{d_v, d_pieces, d_cbreak, d_cum, nreg, m, 0, which, median2};
-  rc = track_slices(ctx, nb, plan.slice, plan.text_cap, plan.max_line, d_st, d_text, sink, S, z,
+  rc = track_slices(ctx, nb, plan.slice, plan.text_cap, plan.max_line, d_st, d_text, sink, S, z, X,
       [&](int64_t b, int64_t end) {
         src.b0 = b;
         launch_bintrack_pieces(d_cbreak, d_cum, nreg, m, b, end, d_tiles, d_pieces, plan.max_pieces, d_st, st);
         launch_bintrack_line_bytes(src, d_st, name_len, end - b + nreg, d_ltiles, st);
       },
       [&](int64_t b, int64_t end) { return end - b + nreg; },
-      [&](int64_t b, int64_t nlines) { src.b0 = b; launch_bintrack_format(src, d_ltiles, nlines, name, d_text, plan.text_cap, st); });
+      [&](int64_t b, int64_t nlines) { src.b0 = b; launch_bintrack_format(src, d_ltiles, nlines, name, d_text, plan.text_cap, st); },
+      bin_windows,
+      [&](int64_t b, int64_t nlines, int64_t nbytes, const TrackIndexOut& out) {
+        src.b0 = b;
+        launch_bintrack_index(src, d_ltiles, nlines, name_len, z.sizes, deflate_members(nbytes), out, st);
+      });
   if (rc != RSI_OK) return rc;
   S.t_total_ms = now_ms() - t_begin;
   if (stats) *stats = S;
@@ -405,6 +509,7 @@ int rsi_hot_write_bin_track(rsi_ctx* ctx, int which, const char* chrom, const ch
   TrackSink sink;
   sink.fd = ::open(path, O_WRONLY | O_CREAT | (append ? O_APPEND : O_TRUNC), 0644);
   if (sink.fd < 0) return fail(ctx, RSI_ERR_INTERNAL, std::string("bin track: cannot open ") + path + ": " + strerror(errno));
+  if (!sink_base(sink)) { const int err = errno; (void)::close(sink.fd); return fail(ctx, RSI_ERR_INTERNAL, std::string("bin track: cannot size ") + path + ": " + strerror(err)); }
   int rc = bin_track_run(ctx, ctx->binmed.as<int32_t>(), ctx->nb, ctx->run_m, ctx->n, cbreak, cum, median2, which, chrom, 0, sink, stats);
   if (::close(sink.fd) != 0 && rc == RSI_OK) rc = fail(ctx, RSI_ERR_INTERNAL, std::string("bin track: write failed: ") + strerror(errno));
   return rc;
@@ -445,6 +550,44 @@ int rsi_hot_set_track_format(rsi_ctx* ctx, int format) {
   if (format != RSI_TRACK_TEXT && format != RSI_TRACK_BGZF) return fail(ctx, RSI_ERR_BAD_ARG, "track: the format must be RSI_TRACK_TEXT (0) or RSI_TRACK_BGZF (1)");
   ctx->track_format = format;
   return RSI_OK;
+}
+
+int rsi_hot_set_track_index(rsi_ctx* ctx, rsi_track_index* ix) {
+  if (!ctx) return fail(ctx, RSI_ERR_BAD_ARG, "null context");
+  ctx->track_index = ix;
+  return RSI_OK;
+}
+
+rsi_track_index* rsi_track_index_create(void) { return new (std::nothrow) rsi_track_index(); }
+void rsi_track_index_free(rsi_track_index* ix) { delete ix; }
+
+int rsi_track_index_append(rsi_track_index* dst, const rsi_track_index* src, int64_t shift) {
+  if (!dst || !src || dst == src) return fail(nullptr, RSI_ERR_BAD_ARG, "track index: two different indexes are needed");
+  if (dst->append(*src, shift) != rsitbx::kOk) return fail(nullptr, RSI_ERR_BAD_ARG, dst->err);
+  return RSI_OK;
+}
+
+int rsi_track_index_write_tbi(rsi_track_index* ix, const char* path) {
+  if (!ix || !path || !path[0]) return fail(nullptr, RSI_ERR_BAD_ARG, "track index: no index or no path");
+  if (!ix->write_tbi(path)) return fail(nullptr, RSI_ERR_INTERNAL, ix->err);
+  return RSI_OK;
+}
+
+int rsi_track_index_counts(const rsi_track_index* ix, int64_t* nref, int64_t* nchunks, int64_t* nwindows) {
+  if (!ix) return fail(nullptr, RSI_ERR_BAD_ARG, "track index: no index");
+  int64_t r, c, w;
+  ix->counts(r, c, w);
+  if (nref) *nref = r;
+  if (nchunks) *nchunks = c;
+  if (nwindows) *nwindows = w;
+  return RSI_OK;
+}
+
+int64_t rsi_track_index_debug_tbi(const rsi_track_index* ix, uint8_t* out, int64_t cap) {
+  if (!ix) return fail(nullptr, RSI_ERR_BAD_ARG, "track index: no index");
+  const std::string raw = ix->tbi();
+  if (out && (int64_t)raw.size() <= cap) memcpy(out, raw.data(), raw.size());
+  return (int64_t)raw.size();
 }
 
 int rsi_hot_last_deflate_stats(const rsi_ctx* ctx, rsi_deflate_stats* out) {

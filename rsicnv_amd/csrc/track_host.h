@@ -160,8 +160,12 @@ inline bool append_bgzf_eof(const char* path) {
 // PATH = the parts `order` names, one after the other (a part that does not exist is a chromosome that wrote none: skipped).
 // Every part 0 .. count - 1 is gone afterwards, whatever happened; on a failure PATH is removed too and err says why.
 // bgzf: the parts are whole BGZF members (concatenation keeps the file valid) and one end-of-file block follows the last.
-inline bool join_parts(const std::string& path, const std::vector<size_t>& order, size_t count, std::string& err, bool bgzf = false) {
+// offsets (optional): per entry of `order`, where its part begins in PATH, or -1 for a part that does not exist.
+inline bool join_parts(const std::string& path, const std::vector<size_t>& order, size_t count, std::string& err, bool bgzf = false,
+                       std::vector<int64_t>* offsets = nullptr) {
   bool ok = true;
+  int64_t written = 0;
+  if (offsets) offsets->assign(order.size(), -1);
   const int out = ::open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
   if (out < 0) { err = "cannot write " + path + ": " + strerror(errno); ok = false; }
   std::vector<char> buf(size_t(1) << 20);
@@ -173,12 +177,14 @@ inline bool join_parts(const std::string& path, const std::vector<size_t>& order
       err = "cannot read " + part + ": " + strerror(errno); ok = false;
       break;
     }
+    if (offsets) (*offsets)[k] = written;
     for (;;) {
       const ssize_t got = ::read(in, buf.data(), buf.size());
       if (got < 0 && errno == EINTR) continue;
       if (got < 0) { err = "cannot read " + part + ": " + strerror(errno); ok = false; break; }
       if (got == 0) break;
       if (!write_all(out, buf.data(), (size_t)got)) { err = "cannot write " + path + ": " + strerror(errno); ok = false; break; }
+      written += (int64_t)got;
     }
     ::close(in);
   }

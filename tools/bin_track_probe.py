@@ -5,7 +5,11 @@ medians and regions fetched, one fprintf per line (tools/bin_track_probe_fprintf
 warm-up call.  Prints one JSON line.  --format bgzf: the device writer deflates its text on the GPU; its entries
 then also hold the file's bytes, members, stored members and the two kernels' time.
 
-  python tools/bin_track_probe.py [--repeat 7] [--scale 1.0] [--dir DIR] [--value ratio|median] [--format text|bgzf]"""
+--index (with --format bgzf): the tabix index built from the device -- the depth track of the same run
+(rsi_hot_write_track) and the bin track, each written --repeat times without and with an index set, alternating; the JSON's
+"index" holds the medians of t_total_ms and t_kernel_ms of both, and what the index holds.
+
+  python tools/bin_track_probe.py [--repeat 7] [--scale 1.0] [--dir DIR] [--value ratio|median] [--format text|bgzf] [--index]"""
 import argparse
 import json
 import os
@@ -21,6 +25,41 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def index_runs(api, hot, a, tmp):
+    """The depth track and the bin track of the run the context holds, as BGZF, without and with an index set: alternating calls,
+    medians of the writer's own figures."""
+    med = lambda xs: round(statistics.median(xs), 3)
+    res = {}
+    writers = {"track": lambda path: hot.write_track(0, "chrProbe", path, format="bgzf"),
+               "bintrack": lambda path: hot.write_bin_track(a.value, "chrProbe", path, format="bgzf")}
+    for what, write in writers.items():
+        path = os.path.join(tmp, f"index_{what}.bedgraph.gz")
+        runs = {"plain": [], "indexed": []}
+        ix = api.TrackIndex()
+        for k in range(a.repeat + 1):       # the first pair warms up
+            for mode in ("plain", "indexed"):
+                if os.path.exists(path):
+                    os.unlink(path)
+                if mode == "indexed":
+                    ix.close()
+                    ix = api.TrackIndex()
+                hot.set_track_index(ix if mode == "indexed" else None)
+                st = write(path)
+                hot.set_track_index(None)
+                if k:
+                    runs[mode].append(st)
+        res[what] = {mode: {"t_total_ms": med([s["t_total_ms"] for s in rs]), "t_kernel_ms": med([s["t_kernel_ms"] for s in rs]),
+                            "all_t_total_ms": [round(s["t_total_ms"], 3) for s in rs]} for mode, rs in runs.items()}
+        res[what].update(lines=runs["plain"][0]["lines"], slices=runs["plain"][0]["slices"], **{"index_" + k: v for k, v in ix.counts().items()})
+        t0 = time.perf_counter()
+        api.bgzf_write_eof(path)
+        ix.write_tbi(path + ".tbi")
+        res[what]["write_tbi_s"] = round(time.perf_counter() - t0, 4)
+        res[what]["tbi_bytes"] = os.path.getsize(path + ".tbi")
+        ix.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeat", type=int, default=7)
@@ -28,7 +67,10 @@ def main():
     ap.add_argument("--value", default="ratio", choices=["ratio", "median"])
     ap.add_argument("--dir", default=None, help="where the files go (default: a temporary directory)")
     ap.add_argument("--format", default="text", choices=["text", "bgzf"], help="bgzf: the device writer's calls deflate on the GPU (DESIGN.md 6h)")
+    ap.add_argument("--index", action="store_true", help="with --format bgzf: time the tracks without and with the tabix index (DESIGN.md 6i)")
     a = ap.parse_args()
+    if a.index and a.format != "bgzf":
+        ap.error("--index needs --format bgzf: a plain-text track has no index")
     import torch
     from rsicnv_amd import api, synth
 
@@ -69,6 +111,8 @@ def main():
                 ds = warm[0]["deflate"]
                 out[target].update(file_bytes=ds["file_bytes"], members=ds["members"], stored_members=ds["stored_members"],
                                    deflate_kernel_s=med([s["deflate"]["t_kernel_ms"] * 1e-3 for s in warm]))
+        if a.index:
+            out["index"] = index_runs(api, hot, a, tmp)
         # the host loop: fetch the arrays (timed: the loop needs them on the host), then one fprintf per line
         t_fetch = []
         for _ in range(a.repeat):

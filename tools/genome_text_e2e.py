@@ -22,8 +22,14 @@ per-base file in the same call, and records both: wall time, text bytes per base
 per second.  The synthetic depth is i.i.d. per base, so its runs are about one base long and the bedGraph text is LARGER
 than the per-base one; compare bytes parsed per second, not only wall time (real mosdepth files are smaller per base).
 
+--index-read K times `-d FILE.bed.gz -c RNAME` by index and nothing else: the first K chromosomes of the config,
+shrunk by --index-scale, are written as one BGZF bedGraph by the project's own track writer with its .tbi
+(rsi_hot_write_track_device, rsi_track_index_write_tbi), and the LAST one is read `--index-repeat` times with the index and
+with -dindex none, alternating after a warm-up pair.  The record holds the medians of the wall time and of the log's inflate
+figures, and says whether the rows agree.
+
 usage: genome_text_e2e.py [--dir SCRATCH] [--out JSON] [--config 4] [--workers 4] [--max-gb G] [--compress none|bgzf|gzip]
-                          [--samples K] [--format depth|bedgraph]"""
+                          [--samples K] [--format depth|bedgraph] [--index-read K [--index-scale S] [--index-repeat R]]"""
 import argparse, json, os, re, shutil, subprocess, sys, tempfile, time, zlib
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import ctypes as C
@@ -42,11 +48,95 @@ ap.add_argument("--compress", choices=["none", "bgzf", "gzip"], default="none")
 ap.add_argument("--samples", type=int, default=0, help="K > 0: a K-column cohort file through -samples all, against its K derived files")
 ap.add_argument("--format", choices=["depth", "bedgraph"], default="depth",
                 help="bedgraph: also a bedGraph file of the same depth, run beside the per-base one")
+ap.add_argument("--index-read", type=int, default=0, help="K > 0: only time -c on the last of K chromosomes of a BGZF bedGraph, with and without its index")
+ap.add_argument("--index-scale", type=float, default=0.05, help="--index-read: shrinks the chromosomes")
+ap.add_argument("--index-repeat", type=int, default=3)
 args = ap.parse_args()
 if args.format == "bedgraph" and (args.samples > 0 or args.compress == "gzip"):
     raise SystemExit("genome_text_e2e: --format bedgraph takes --compress none or bgzf, without --samples")
 if args.samples > 0 and args.out is None:
     args.out = os.path.join(ROOT, "profiles", "e2e_genome_samples.json")
+
+
+
+def index_read():
+    """-c on the last chromosome of a K-chromosome BGZF bedGraph the track writer wrote and indexed: by index, and without."""
+    import statistics
+    K = args.index_read
+    os.makedirs(args.dir, exist_ok=True)
+    lib = api.load_library()
+    exe = os.path.join(ROOT, "rsicnv_amd", "bin", "rsicnv")
+    bed, fa = os.path.join(args.dir, "indexed.bed.gz"), os.path.join(args.dir, "indexed_ref.fa")
+    for f in (bed, bed + ".tbi"):
+        if os.path.exists(f):
+            os.unlink(f)
+    hot = api.RsiHot(0)
+    hot.set_track_format("bgzf")
+    ix = api.TrackIndex()
+    hot.set_track_index(ix)
+    bases, t0 = 0, time.perf_counter()
+    for c in range(K):
+        plan = synth.config_plan(args.config, chrom=c, scale=args.index_scale)
+        n = plan["n"]
+        d_fa = torch.empty(n + 64, dtype=torch.uint8, device="cuda")
+        d_rd = torch.empty(n + 16, dtype=torch.int32, device="cuda")
+        synth.generate_device(lib, plan, d_fa.data_ptr(), d_rd.data_ptr())
+        torch.cuda.synchronize()
+        hot.write_track_device(d_rd.data_ptr(), n, f"chr{c + 1}", bed, append=True)
+        bases += n
+        if c == K - 1:                                  # the FASTA of the chromosome that is read, 60 columns a line, and its .fai
+            seq = d_fa[:n].cpu().numpy()
+            head = f">chr{K}\n".encode()
+            with open(fa, "wb") as f:
+                f.write(head)
+                full = n // 60 * 60
+                body = np.concatenate([seq[:full].reshape(-1, 60), np.full((full // 60, 1), 10, dtype=np.uint8)], axis=1).tobytes()
+                f.write(body + (seq[full:].tobytes() + b"\n" if full < n else b""))
+            with open(fa + ".fai", "w") as f:
+                f.write(f"chr{K}\t{n}\t{len(head)}\t60\t61\n")
+            last_n = n
+    hot.set_track_index(None)
+    hot.close()
+    api.bgzf_write_eof(bed)
+    ix.write_tbi(bed + ".tbi")
+    t_files = time.perf_counter() - t0
+    flags = synth.config_flags(args.config)
+    flag_args = ["-m", str(flags["m"])] + (["-MED"] if flags.get("trans", 0) == 1 else []) + (["-cap", str(flags["cap"])] if "cap" in flags else [])
+    runs = {"indexed": [], "whole": []}
+    rows = {}
+    for k in range(args.index_repeat + 1):              # the first pair warms up (page cache, first allocations)
+        for mode in ("whole", "indexed"):
+            out = os.path.join(args.dir, f"indexed_{mode}.txt")
+            t = time.perf_counter()
+            r = subprocess.run([exe, "rsi", "-f", fa, "-d", bed, "-c", f"chr{K}", "-o", out, "-np", "-workers", str(args.workers)] + flag_args +
+                               (["-dindex", "none"] if mode == "whole" else []), capture_output=True, text=True, timeout=1800)
+            wall = time.perf_counter() - t
+            if r.returncode != 0:
+                raise RuntimeError(r.stderr[-2000:])
+            z = re.search(r"#depth file: (\w+), (\d+) compressed bytes, (\d+) text bytes, inflate ([0-9.e+-]+) ms", r.stderr)
+            rows[mode] = [l for l in open(out).read().splitlines() if not l.startswith("#")]
+            if k:
+                runs[mode].append({"s": wall, "compressed_bytes": int(z.group(2)), "text_bytes": int(z.group(3)), "inflate_ms": float(z.group(4))})
+    med = lambda xs: round(statistics.median(xs), 4)
+    rec = {"what": f"tools/genome_text_e2e.py --index-read {K} --index-scale {args.index_scale}: rsicnv rsi -d indexed.bed.gz -c chr{K} with "
+                   "indexed.bed.gz.tbi beside the file, and with -dindex none; medians of alternating runs after a warm-up pair",
+           "chromosomes": K, "bases": bases, "bases_of_the_chromosome_read": last_n, "file_bytes": os.path.getsize(bed),
+           "tbi_bytes": os.path.getsize(bed + ".tbi"), "files_written_in_s": round(t_files, 1), "index": ix.counts(), "rows_match": rows["indexed"] == rows["whole"],
+           "calls": len(rows["whole"])}
+    for mode, rs in runs.items():
+        rec[mode] = {"s": med([x["s"] for x in rs]), "all_s": [round(x["s"], 4) for x in rs], "compressed_bytes": rs[0]["compressed_bytes"],
+                     "text_bytes": rs[0]["text_bytes"], "inflate_ms": med([x["inflate_ms"] for x in rs])}
+    ix.close()
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(rec, f, indent=1)
+    print(json.dumps(rec), flush=True)
+    shutil.rmtree(args.dir, ignore_errors=True)
+
+
+if args.index_read > 0:
+    index_read()
+    raise SystemExit(0)
 
 lib = api.load_library()
 lib.rsi_synth_append_genome_text.argtypes = [C.c_char_p, C.c_char_p, C.c_void_p, C.c_int64]

@@ -10,7 +10,10 @@ start and end at a few percent of the positions), which is what makes a bedGraph
 
 --format bgzf: the track deflated on the GPU.  The JSON then also holds the file's bytes, members, stored members
 and the two kernels' time ("bgzf"), the plain-text call on the same array and disk beside it ("track"), and what zlib makes of
-the same 65280-byte members at level 1 and 6 -- of the first --zlib-members members, read back from the file."""
+the same 65280-byte members at level 1 and 6 -- of the first --zlib-members members, read back from the file.
+
+--index (with --format bgzf): the same BGZF call without and with a tabix index set, alternating, --repeat times
+each after a warm-up pair; "index" holds the medians of t_total_ms and t_kernel_ms and what the index holds."""
 import argparse
 import json
 import os
@@ -74,6 +77,30 @@ def bgzf_runs(api, hot, d_depth, a, path, text_best):
     return r
 
 
+def index_runs(api, hot, d_depth, a, path):
+    import statistics
+    med = lambda xs: round(statistics.median(xs), 3)
+    runs = {"plain": [], "indexed": []}
+    ix = api.TrackIndex()
+    for k in range(a.repeat + 1):       # the first pair warms up
+        for mode in ("plain", "indexed"):
+            if os.path.exists(path):
+                os.unlink(path)
+            if mode == "indexed":
+                ix.close()
+                ix = api.TrackIndex()
+            hot.set_track_index(ix if mode == "indexed" else None)
+            st = hot.write_track_device(d_depth.data_ptr(), a.n, "chrProbe", path, format="bgzf")
+            hot.set_track_index(None)
+            if k:
+                runs[mode].append(st)
+    res = {mode: {"t_total_ms": med([s["t_total_ms"] for s in rs]), "t_kernel_ms": med([s["t_kernel_ms"] for s in rs]),
+                  "all_t_total_ms": [round(s["t_total_ms"], 3) for s in rs]} for mode, rs in runs.items()}
+    res.update({"index_" + k: v for k, v in ix.counts().items()})
+    ix.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=60_000_000)
@@ -84,7 +111,10 @@ def main():
     ap.add_argument("--no-baseline", action="store_true")
     ap.add_argument("--format", default="text", choices=["text", "bgzf"])
     ap.add_argument("--zlib-members", type=int, default=256, help="members of the BGZF file that zlib compresses for comparison")
+    ap.add_argument("--index", action="store_true", help="with --format bgzf: time the call without and with the tabix index (DESIGN.md 6i)")
     a = ap.parse_args()
+    if a.index and a.format != "bgzf":
+        ap.error("--index needs --format bgzf: a plain-text track has no index")
     import torch
     from rsicnv_amd import api
 
@@ -116,6 +146,8 @@ def main():
         os.unlink(track)
         if a.format == "bgzf":
             out["bgzf"] = bgzf_runs(api, hot, d_depth, a, os.path.join(tmp, "probe.bedgraph.gz"), best)
+        if a.index:
+            out["index"] = index_runs(api, hot, d_depth, a, os.path.join(tmp, "probe_index.bedgraph.gz"))
         if not a.no_baseline:
             exe, raw, dump = os.path.join(tmp, "fprintf_loop"), os.path.join(tmp, "depth.i32"), os.path.join(tmp, "probe_rd")
             subprocess.run(["cc", "-O2", "-o", exe, os.path.join(ROOT, "tools", "track_probe_fprintf.c")], check=True)

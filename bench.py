@@ -20,6 +20,14 @@ a cohort, weak scaling), reported with that label.
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
   python bench.py --gpus 1 --steps 8 --warmup 2 --dump-outputs DIR   (the last timed step's outputs as .npy, dump_outputs())
+  python bench.py --gpus 1 --steps 8 --warmup 2 --full               (everything beside the headline figure as well, see below)
+
+A plain run does what the headline figure needs and no more: it generates the genome, warms up, picks the dominant per-base
+kernel (one pass: the timed steps carry HIP events around that kernel, so the pick is part of how they run), times the steps,
+writes --dump-outputs and prints the line.  Every measurement or check that takes runs of its own -- one genome at a time, the
+isolated and all-launch kernel passes, the rows against the reference's, the side measurements, the CPU baseline -- waits for
+`--full`; in a plain run's line their fields are null or absent (marked [--full] below) and `full` is false.  The timed steps
+and `value` / `ms_per_step` are the same with and without it.
 
 Steps are SUBMITTED to the pool (rsi_pool_submit) and waited for, gathered and turned into rows on a second host thread:
 `config.steps_in_flight` genomes are queued at once (2 for a whole genome on one GPU, as many as fill the pool's workers for
@@ -28,7 +36,7 @@ chromosomes of genome k + 1 run beside the last ones of genome k.  Every step's 
 region; the timer is read after the last step's rows exist (barrier + synchronize on both sides, max over ranks).
 
 Rank 0 prints ONE JSON line.  In it:
-  roofline      the dominant per-base kernel -- the one an untimed pass with HIP events around every
+  roofline      `isolated`, `streaming_kernels` and `scan` are [--full].  The dominant per-base kernel -- the one an untimed pass with HIP events around every
                 per-base launch MEASURES as the longest -- then timed inside the timed steps (events
                 around that kernel only, on the library's own streams): algorithmic bytes (SURVEY 8d's
                 row of the kernel) over that time; `isolated` = the same launches with the chip to
@@ -40,10 +48,13 @@ Rank 0 prints ONE JSON line.  In it:
                 the step time: the fraction BASELINE.md defines for the path; `scan` = window
                 evaluations per second of the RSI scan kernel (2 sweeps x Lmax x bins x 2 passes).
   steps_identical  every timed step's rows hashed: true when all steps produced the same bytes.
-  cpu_baseline  the compiled reference (oracle/_ref, kind "reference") or the CPU restatement
+  rows_match_reference  [--full] every timed step's hash equals the hash of the reference's rows for the same genome
+                (tests/golden/genome_rows.json); a mismatch is a non-zero exit.
+  one_genome_at_a_time, kernel_ms_all_launches_extra_pass  [--full] extra untimed passes after the timed steps.
+  cpu_baseline  [--full] the compiled reference (oracle/_ref, kind "reference") or the CPU restatement
                 (kind "port") on one 60 Mb chromosome of the same model, one core; `all_cores` =
                 one such process per host core at once.
-  t_device_h2d  rsi_hot_run from pinned host buffers (H2D of the inputs included) for configs[1]
+  t_device_h2d  [--full] rsi_hot_run from pinned host buffers (H2D of the inputs included) for configs[1]
                 and configs[2]; t_e2e = the command line on a 60 Mb depth text file (parse included).
 """
 import argparse
@@ -106,15 +117,19 @@ def main():
                     help="N > 1: one genome sharded by chromosome over the ranks (strong scaling, the north_star mode) or one genome per rank (weak)")
     ap.add_argument("--scale", type=float, default=1.0, help="shrink chromosome lengths (debug only; invalidates the metric)")
     ap.add_argument("--cpu-sample-mb", type=float, default=60.0, help="size of the CPU-baseline sample chromosome")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-single", action="store_true", help="skip the side measurements (single chromosomes, host-buffer runs, command line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-single", action="store_true", help="with --full: skip the side measurements (single chromosomes, host-buffer runs, command line)")
     ap.add_argument("--workers", type=int, default=0, help="host threads / HIP streams per GPU (chromosomes in flight); 0 = min(20 on one GPU / 16 per rank of several, max(4, 2 x the "
                     "host cores this rank may use)): sixteen on a box with eight cores and more per rank, fewer where eight ranks share sixteen cores")
     ap.add_argument("--inflight", type=int, default=0, help="steps (genomes) queued in the pool at once (rsi_pool_submit): the next genome's first "
                     "chromosomes run beside the last ones of the current genome.  0 = as many as keep the pool's workers busy with this rank's "
                     "share (2 for a whole genome, more for the few chromosomes of one rank among eight, at most 6); 1 = one genome at a time")
     ap.add_argument("--check-rows", choices=("auto", "off"), default="auto",
-                    help="auto: a full-size configs[3] / configs[4] genome's rows must hash to what the reference wrote (tests/golden/genome_rows.json)")
+                    help="with --full.  auto: a full-size configs[3] / configs[4] genome's rows must hash to what the reference wrote (tests/golden/genome_rows.json)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beside the headline figure: one genome at a time, the isolated and "
+                         "all-launch kernel passes, the rows against the reference's, the side measurements and the CPU baseline "
+                         "(--no-single / --no-cpu-baseline leave the last two out again).  Without it none of these run")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step handed its caller to DIR/<name>.npy (float64; see dump_outputs())")
     args = ap.parse_args()
@@ -311,7 +326,8 @@ def main():
     for _ in range(args.warmup):
         step()
     # ---- which per-base kernel is the dominant one?  Measured, not assumed: one untimed pass with HIP events around every
-    # per-base launch (timing mode 2); the timed steps then bracket that kernel only (event records are not free). ----
+    # per-base launch (timing mode 2); the timed steps then bracket that kernel only (event records are not free).  A plain
+    # run keeps this pass: it decides which launches carry events inside the timed steps. ----
     fence()                # the warm-up genomes are done before the timing mode changes under the workers
     pool.reset_times()
     pool.set_timing(2)
@@ -348,7 +364,7 @@ def main():
 
     # ---- beside the headline: the same genome ONE AT A TIME (a step is submitted when the previous step's rows exist) ----
     one_at_a_time = None
-    if args.inflight > 1:
+    if args.full and args.inflight > 1:
         saved_slots = slots
         slots = threading.Semaphore(1)
         k1 = max(3, min(args.steps, 10))
@@ -407,60 +423,63 @@ def main():
                     "dominant_pick_ms": {k: round(insitu_all[k][0], 3) for k in sorted(streaming_names, key=lambda k: -insitu_all[k][0])},
                     "whole_path": {"algorithmic_bytes_per_base": whole_bpb, "achieved": round(whole, 1), "frac": round(whole / HBM_PEAK_GBS, 4),
                                    "note": "SURVEY 8d's whole-path algorithmic bytes x the bases one GPU processed per step / step time"}}
-        # The same kernel with the per-base phases run alone on the chip (rsi_pool_set_schedule isolate=1):
-        # one extra, untimed genome pass; `value` above does not include it.
+        if args.full:
+            # The same kernel with the per-base phases run alone on the chip (rsi_pool_set_schedule isolate=1):
+            # one extra, untimed genome pass; `value` above does not include it.
+            fence()
+            pool.set_schedule(isolate=True)
+            pool.set_timing(2)
+            timed_tables = (pool.times, )
+            pool.reset_times()
+            step(timed=True)
+            fence()
+            iso = pool.kernel_table()
+            del step_hashes[args.steps:]
+            pool.set_schedule(isolate=False)
+            pool.set_timing(3)
+            if dom in iso:
+                ims, icnt, ibases, ibyts, iach = kernel_roofline(iso, dom)
+                roofline["isolated"] = {"achieved": round(iach, 1), "frac": round(iach / HBM_PEAK_GBS, 4), "avg_launch_ms": round(ims / icnt, 4),
+                                        "launches": int(icnt), "note": "same launches with the chip to themselves (untimed extra pass)"}
+            # every per-base kernel, three fractions each: against SURVEY's algorithmic bytes, against the bytes the kernel
+            # really moves (PMC), against the chip's vector-instruction issue rate (PMC) -- in situ (the untimed pass that picked
+            # the dominant kernel) and isolated
+            roofline["streaming_kernels"] = {
+                k: {"algorithmic_bytes_per_base": ALGO_BYTES_PER_BASE[k],
+                    "actual_bytes_per_base": None if pmc_traffic_per_base(k) is None else round(pmc_traffic_per_base(k), 3),
+                    "valu_insts_per_base_x64": None if pmc_valu_per_base(k) is None else round(64 * pmc_valu_per_base(k), 2),
+                    "in_situ": three_fractions(insitu_all, k), "isolated": three_fractions(iso, k) if k in iso else None}
+                for k in sorted(streaming_names, key=lambda k: -insitu_all[k][0])}
+            pool.times = timed_tables[0]
+    kernel_ms_all = None
+    if args.full:
+        # every launch of one more untimed pass (normal schedule), for the per-kernel picture of the whole path
         fence()
-        pool.set_schedule(isolate=True)
-        pool.set_timing(2)
-        timed_tables = (pool.times, )
+        timed_table = pool.times
         pool.reset_times()
+        pool.set_timing(1)
         step(timed=True)
         fence()
-        iso = pool.kernel_table()
         del step_hashes[args.steps:]
-        pool.set_schedule(isolate=False)
+        all_table = pool.kernel_table()
+        kernel_ms_all = {k: round(v[0], 3) for k, v in sorted(all_table.items(), key=lambda kv: -kv[1][0])}
+        if roofline is not None and "rsi_scan" in all_table and all_table["rsi_scan"][0] > 0:
+            sms = all_table["rsi_scan"][0]
+            roofline["scan"] = {"kernel": "rsi_scan", "bound": "lds/alu", "window_evaluations_per_step": int(scan_evals[0]),
+                                "kernel_ms_per_step_in_situ": round(sms, 3),
+                                "evaluations_per_s": round(scan_evals[0] / (sms * 1e-3), 1),
+                                "note": "2 sweeps x Lmax x bins x 2 passes per chromosome over the kernel's HIP-event time (all launches of one untimed pass)"}
         pool.set_timing(3)
-        if dom in iso:
-            ims, icnt, ibases, ibyts, iach = kernel_roofline(iso, dom)
-            roofline["isolated"] = {"achieved": round(iach, 1), "frac": round(iach / HBM_PEAK_GBS, 4), "avg_launch_ms": round(ims / icnt, 4),
-                                    "launches": int(icnt), "note": "same launches with the chip to themselves (untimed extra pass)"}
-        # every per-base kernel, three fractions each: against SURVEY's algorithmic bytes, against the bytes the kernel
-        # really moves (PMC), against the chip's vector-instruction issue rate (PMC) -- in situ (the untimed pass that picked
-        # the dominant kernel) and isolated
-        roofline["streaming_kernels"] = {
-            k: {"algorithmic_bytes_per_base": ALGO_BYTES_PER_BASE[k],
-                "actual_bytes_per_base": None if pmc_traffic_per_base(k) is None else round(pmc_traffic_per_base(k), 3),
-                "valu_insts_per_base_x64": None if pmc_valu_per_base(k) is None else round(64 * pmc_valu_per_base(k), 2),
-                "in_situ": three_fractions(insitu_all, k), "isolated": three_fractions(iso, k) if k in iso else None}
-            for k in sorted(streaming_names, key=lambda k: -insitu_all[k][0])}
-        pool.times = timed_tables[0]
-    # every launch of one more untimed pass (normal schedule), for the per-kernel picture of the whole path
-    fence()
-    timed_table = pool.times
-    pool.reset_times()
-    pool.set_timing(1)
-    step(timed=True)
-    fence()
-    del step_hashes[args.steps:]
-    all_table = pool.kernel_table()
-    kernel_ms_all = {k: round(v[0], 3) for k, v in sorted(all_table.items(), key=lambda kv: -kv[1][0])}
-    if roofline is not None and "rsi_scan" in all_table and all_table["rsi_scan"][0] > 0:
-        sms = all_table["rsi_scan"][0]
-        roofline["scan"] = {"kernel": "rsi_scan", "bound": "lds/alu", "window_evaluations_per_step": int(scan_evals[0]),
-                            "kernel_ms_per_step_in_situ": round(sms, 3),
-                            "evaluations_per_s": round(scan_evals[0] / (sms * 1e-3), 1),
-                            "note": "2 sweeps x Lmax x bins x 2 passes per chromosome over the kernel's HIP-event time (all launches of one untimed pass)"}
-    pool.set_timing(3)
-    pool.times = timed_table
+        pool.times = timed_table
     phase_ms = pool.phase_table()
 
     side = None
-    if rank == 0 and world == 1 and args.config == 4 and args.scale == 1.0 and not args.no_single:
+    if rank == 0 and world == 1 and args.config == 4 and args.scale == 1.0 and args.full and not args.no_single:
         side = side_measurements(lib, pool, dev, args)
 
     # ---- CPU baseline on a bounded sample (rank 0, N = 1 only) ----
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(lib, args, flags)
 
     # ---- who ran where (every rank's device), the collective's backend and library version ----
@@ -479,7 +498,7 @@ def main():
     # tools/make_golden_full.py from the compiled reference's output for the very same generated chromosomes) ----
     rows_ref = None
     rows_match = None
-    if args.check_rows == "auto" and sharded and args.scale == 1.0 and args.config in (4, 5):
+    if args.full and args.check_rows == "auto" and sharded and args.scale == 1.0 and args.config in (4, 5):
         try:
             with open(os.path.join(ROOT, "tests", "golden", "genome_rows.json")) as f:
                 rows_ref = json.load(f).get(f"config{args.config}")
@@ -498,7 +517,7 @@ def main():
             par = f"{world} rank(s), one genome per GPU (another sample each), {args.workers} chromosomes in flight per GPU, all_gather of summaries"
         out = {
             "metric": "bases/sec through RSI pipeline (bin+GC+NB+segment)", "value": round(value, 1), "unit": "bases/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "strong" if sharded else "weak",
             "vs_baseline": None, "dtype": "int32", "data": "synthetic",
             "config": {"workload": workload_name(args), "chromosomes": len(plans), "genome_bases": genome_bases,

@@ -182,7 +182,7 @@ def table():
         e2e = (f"{e['chromosomes_run']} of {e['chromosomes_of_genome']} chromosomes, {e['depth_text_bytes'] / 1e9:.1f} GB of depth text: {e['sequential']['s']:.1f} s one after the other = "
                f"{e['sequential']['bases_per_s'] / 1e6:.0f} Mbases/s; four processes at once {e['4_processes_at_once']['s']:.1f} s = {e['4_processes_at_once']['bases_per_s'] / 1e6:.0f} Mbases/s (north_star: ≥ 50)")
     rows = [
-        ("step", "3 Gb genome (configs[3]) through the pool, `python bench.py`"),
+        ("step", "3 Gb genome (configs[3]) through the pool, `python bench.py --full`"),
         ("one", "the same, one genome at a time (`one_genome_at_a_time`)"),
         ("whole", "whole path, fraction of 23.7 B/base × 8 TB/s"),
         ("k2j", "dominant per-base kernel K2j: `roofline.frac` in situ / `isolated`"),

@@ -287,6 +287,73 @@ int rsi_hot_run_bam(rsi_ctx* ctx, const rsi_params* p, const char* bam_path, con
 int rsi_hot_run_device(rsi_ctx* ctx, const rsi_params* p, const void* d_depth, const void* d_fasta, int64_t n,
                        rsi_result** out);
 
+/* ---- The reference sequence read on the device ------------------------------------------------------------------
+ * An rsi_ref is an indexed FASTA file (FILE with FILE.fai; samtools faidx), plain text or BGZF (bgzip; then with FILE.gzi, or
+ * without: the members are walked once).  A load reads the bytes of one sequence's lines -- for BGZF the compressed bytes of the
+ * members that hold them, inflated on the device with their CRC32 and ISIZE checked -- and a kernel unfolds them by the .fai's
+ * arithmetic (base k lies at OFFSET + k / LINEBASES * LINEWIDTH + k % LINEBASES) into one byte per base, unchanged: no case
+ * folding, no classification.  While unfolding, every line terminator position must hold '\n' or '\r' and no base position
+ * '\n', '\r' or '>': otherwise the .fai does not fit the file and the load fails with RSI_ERR_BAD_ARG naming the sequence.
+ * The format comes from the file's first bytes as for depth files; plain gzip is RSI_ERR_UNSUPPORTED (recompress with bgzip).
+ * rsi_ref_open parses only and makes no GPU call.  fai_path / gzi_path NULL: fasta_path + ".fai" / ".gzi"; gzi_path "none" (or a
+ * default .gzi that is not there): the member table is built at the first load from the members' BSIZE and ISIZE fields.  A
+ * .gzi that does not fit the file -- an offset that is no member header, text offsets that disagree with the members' ISIZE,
+ * offsets that do not increase -- is RSI_ERR_BAD_ARG.  One handle serves one device (the first it loads on) and one load at a time. */
+typedef struct rsi_ref rsi_ref;
+typedef struct rsi_ref_seq {
+  int64_t length, offset;         /* the .fai's LENGTH and OFFSET */
+  int32_t linebases, linewidth;   /* LINEBASES, LINEWIDTH */
+  char name[256];
+} rsi_ref_seq;
+typedef struct rsi_ref_stats {
+  int64_t bytes_read;     /* bytes of the file read (BGZF: compressed bytes) */
+  int64_t text_bytes;     /* bytes of text unfolded from */
+  int64_t members;        /* BGZF members inflated */
+  int32_t format;         /* 0 text, 1 BGZF */
+  int32_t index_used;     /* BGZF: 1 the .gzi, 0 members walked */
+  double t_kernel_ms;     /* summed HIP-event time of the inflate and unfold launches */
+  double t_wall_ms;       /* wall time of the load */
+} rsi_ref_stats;
+int rsi_ref_open(const char* fasta_path, const char* fai_path, const char* gzi_path, rsi_ref** out);
+void rsi_ref_close(rsi_ref* ref);
+const char* rsi_ref_last_error(const rsi_ref* ref);   /* ref may be NULL: why the last rsi_ref_open failed */
+int rsi_ref_count(const rsi_ref* ref);
+int rsi_ref_sequence(const rsi_ref* ref, int i, rsi_ref_seq* out);
+/* read_fasta's rule: the first sequence named rname or "chr" + rname; -1: none */
+int rsi_ref_find(const rsi_ref* ref, const char* rname);
+int rsi_ref_format(const rsi_ref* ref);               /* 0 text, 1 BGZF */
+/* The path of the .gzi in use, "" when the members are (to be) walked */
+const char* rsi_ref_index_path(const rsi_ref* ref);
+/* Sequence i unfolded into d_out[0, length) in HBM of `device`: d_out 16-byte aligned, cap >= length + 64 (what the run entry
+ * points want of d_fasta).  stream: a hipStream_t of that device, NULL for the handle's own; the call returns when the bytes are there.  st may be NULL. */
+int rsi_ref_load_device(rsi_ref* ref, int device, int i, void* d_out, int64_t cap, void* stream, rsi_ref_stats* st);
+/* The same into a device buffer of the handle's own, then copied to out[0, length); cap >= length. */
+int rsi_ref_load_host(rsi_ref* ref, int device, int i, uint8_t* out, int64_t cap);
+/* rsi_hot_run_text / rsi_hot_run_bam with the sequence already in HBM (d_fasta[n], 16-byte aligned, not modified): no copy of it. */
+int rsi_hot_run_text_dfasta(rsi_ctx* ctx, const rsi_params* p, const char* depth_path, const void* d_fasta, int64_t n,
+                            rsi_result** out, rsi_text_stats* stats);
+int rsi_hot_run_bam_dfasta(rsi_ctx* ctx, const rsi_params* p, const char* bam_path, const char* chrom, int minq, int min_baseq,
+                           const void* d_fasta, int64_t n, rsi_result** out, rsi_bam_stats* stats);
+/* `bytes` of device memory on `device` (hipMalloc: 256-byte aligned), for callers without a HIP runtime of their own: the command
+ * line's sequence buffers.  NULL when there is none. */
+void* rsi_ref_device_alloc(int device, int64_t bytes);
+void rsi_ref_device_free(int device, void* p);
+/* Test hooks for the reader's host decisions (ref_host.h), no file and no device.
+ * _fai_line: one .fai line parsed (0, or RSI_ERR_BAD_ARG with the reason in rsi_ref_last_error(NULL)).
+ * _ranges: for the layout `s` (name unused), out[0] = flen (read_fasta's byte count); out[1], out[2] = the text [a, b) the bases
+ *   [k0, k1) need; out[3], out[4] = the bases [k0', k1') the text span [a_in, b_in) holds whole (at_eof: b_in is the file's end).
+ * _gzi: a .gzi image parsed; the table (the first member's (0, 0) in front) as pairs into table[2 * cap]; returns the number of
+ *   members (also when cap is too small), RSI_ERR_BAD_ARG when it cannot be parsed.
+ * _cover: the members [out[0], out[1]) of such a table (n pairs) that cover the text [a, b), out[2] = a - their first text offset. */
+int rsi_ref_debug_fai_line(const char* line, rsi_ref_seq* out);
+/* Test hook: the sizes a load works in -- a text file's bases per transfer and unfold launch (any number from 1 on, also no
+ * multiple of 16) and a BGZF file's text per inflate launch (from 1024 on; a launch takes one member at least) -- so that
+ * sequences of a few kilobases take the many-chunk paths of a chromosome.  0: the default (32 Mi each). */
+int rsi_ref_debug_set_chunks(rsi_ref* ref, int64_t text_chunk_bases, int64_t bgzf_span_bytes);
+int rsi_ref_debug_ranges(const rsi_ref_seq* s, int64_t k0, int64_t k1, int64_t a_in, int64_t b_in, int at_eof, int64_t* out);
+int64_t rsi_ref_debug_gzi(const uint8_t* image, int64_t len, int64_t* table, int64_t cap);
+int rsi_ref_debug_cover(const int64_t* table, int64_t n, int64_t a, int64_t b, int64_t* out);
+
 /* ---- Excluded regions: a mask applied on the device ---------------------------------------------------------------------
  * An excluded base behaves exactly like an N of the reference sequence: it is not GC, its run is padded by max(50, m/4) and
  * merged with its neighbours (get_noseq_regions, loaddata.cpp:243-273), removed before binning and re-inserted when the calls

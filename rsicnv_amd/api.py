@@ -67,7 +67,11 @@ EXPORTS = ["rsi_default_params", "rsi_hot_create", "rsi_hot_destroy", "rsi_hot_l
            "rsi_hot_write_bin_track", "rsi_hot_debug_bin_track",
            "rsi_hot_set_track_format", "rsi_hot_last_deflate_stats", "rsi_bgzf_write_eof", "rsi_hot_debug_deflate",
            "rsi_track_index_create", "rsi_track_index_free", "rsi_hot_set_track_index", "rsi_track_index_append",
-           "rsi_track_index_write_tbi", "rsi_track_index_counts", "rsi_track_index_debug_tbi"]
+           "rsi_track_index_write_tbi", "rsi_track_index_counts", "rsi_track_index_debug_tbi",
+           "rsi_ref_open", "rsi_ref_close", "rsi_ref_last_error", "rsi_ref_count", "rsi_ref_sequence", "rsi_ref_find", "rsi_ref_format",
+           "rsi_ref_index_path", "rsi_ref_load_device", "rsi_ref_load_host", "rsi_ref_device_alloc", "rsi_ref_device_free",
+           "rsi_hot_run_text_dfasta", "rsi_hot_run_bam_dfasta",
+           "rsi_ref_debug_set_chunks", "rsi_ref_debug_fai_line", "rsi_ref_debug_ranges", "rsi_ref_debug_gzi", "rsi_ref_debug_cover"]
 
 
 class RsiParams(C.Structure):
@@ -120,6 +124,15 @@ class RsiDeflateStats(C.Structure):
 
 INFLATE_FORMATS = {0: "text", 1: "bgzf", 2: "gzip"}
 TRACK_FORMATS = {"text": 0, "bgzf": 1}
+
+
+class RsiRefSeq(C.Structure):
+    _fields_ = [("length", C.c_int64), ("offset", C.c_int64), ("linebases", C.c_int32), ("linewidth", C.c_int32), ("name", C.c_char * 256)]
+
+
+class RsiRefStats(C.Structure):
+    _fields_ = [("bytes_read", C.c_int64), ("text_bytes", C.c_int64), ("members", C.c_int64), ("format", C.c_int32),
+                ("index_used", C.c_int32), ("t_kernel_ms", C.c_double), ("t_wall_ms", C.c_double)]
 
 
 def _inflate_dict(st):
@@ -289,6 +302,32 @@ def load_library():
     L.rsi_track_index_debug_tbi.restype = C.c_int64
     L.rsi_hot_debug_deflate.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(RsiDeflateStats)]
     L.rsi_hot_debug_deflate.restype = C.c_int64
+    L.rsi_ref_open.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]
+    L.rsi_ref_close.argtypes = [C.c_void_p]
+    L.rsi_ref_close.restype = None
+    L.rsi_ref_last_error.argtypes = [C.c_void_p]
+    L.rsi_ref_last_error.restype = C.c_char_p
+    L.rsi_ref_count.argtypes = [C.c_void_p]
+    L.rsi_ref_sequence.argtypes = [C.c_void_p, C.c_int, C.POINTER(RsiRefSeq)]
+    L.rsi_ref_find.argtypes = [C.c_void_p, C.c_char_p]
+    L.rsi_ref_format.argtypes = [C.c_void_p]
+    L.rsi_ref_index_path.argtypes = [C.c_void_p]
+    L.rsi_ref_index_path.restype = C.c_char_p
+    L.rsi_ref_load_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(RsiRefStats)]
+    L.rsi_ref_load_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64]
+    L.rsi_ref_device_alloc.argtypes = [C.c_int, C.c_int64]
+    L.rsi_ref_device_alloc.restype = C.c_void_p
+    L.rsi_ref_device_free.argtypes = [C.c_int, C.c_void_p]
+    L.rsi_ref_device_free.restype = None
+    L.rsi_hot_run_text_dfasta.argtypes = [C.c_void_p, C.POINTER(RsiParams), C.c_char_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(RsiTextStats)]
+    L.rsi_hot_run_bam_dfasta.argtypes = [C.c_void_p, C.POINTER(RsiParams), C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_int64,
+                                         C.POINTER(C.c_void_p), C.POINTER(RsiBamStats)]
+    L.rsi_ref_debug_set_chunks.argtypes = [C.c_void_p, C.c_int64, C.c_int64]
+    L.rsi_ref_debug_fai_line.argtypes = [C.c_char_p, C.POINTER(RsiRefSeq)]
+    L.rsi_ref_debug_ranges.argtypes = [C.POINTER(RsiRefSeq), C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_void_p]
+    L.rsi_ref_debug_gzi.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_int64]
+    L.rsi_ref_debug_gzi.restype = C.c_int64
+    L.rsi_ref_debug_cover.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]
     _lib = L
     return L
 
@@ -381,6 +420,70 @@ class TrackIndex:
         k2 = self.lib.rsi_track_index_debug_tbi(self.handle, out.ctypes.data, k)
         self._check(int(k2))
         return out[:k].tobytes()
+
+
+class RsiRef:
+    """An indexed FASTA file, plain text or BGZF, read on the device (rsi_ref).  Opening parses the .fai (and
+    later the .gzi) and touches no GPU.  fai / gzi: their paths (None: PATH.fai, PATH.gzi when it is there); gzi="none": the
+    BGZF members are walked instead."""
+
+    def __init__(self, path, fai=None, gzi=None, device=0):
+        self.lib = load_library()
+        self.device = int(device)
+        h = C.c_void_p()
+        rc = self.lib.rsi_ref_open(os.fsencode(path), None if fai is None else os.fsencode(fai), None if gzi is None else os.fsencode(gzi), C.byref(h))
+        if rc != 0:
+            raise RsiError(rc, self.lib.rsi_ref_last_error(None).decode())
+        self.handle = h
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.rsi_ref_close(self.handle)
+            self.handle = None
+
+    __del__ = close
+
+    def _check(self, rc):
+        if rc < 0:
+            raise RsiError(rc, self.lib.rsi_ref_last_error(self.handle).decode())
+
+    @property
+    def count(self):
+        return self.lib.rsi_ref_count(self.handle)
+
+    @property
+    def format(self):
+        """0 text, 1 BGZF"""
+        return self.lib.rsi_ref_format(self.handle)
+
+    def find(self, rname):
+        """Index of the first sequence named rname or "chr" + rname (read_fasta's rule), -1 when there is none."""
+        return self.lib.rsi_ref_find(self.handle, rname.encode())
+
+    def sequence(self, i):
+        """{"name", "length", "offset", "linebases", "linewidth"} of sequence i."""
+        s = RsiRefSeq()
+        if self.lib.rsi_ref_sequence(self.handle, int(i), C.byref(s)) != 0:
+            raise IndexError(i)
+        return {"name": s.name.decode(), "length": s.length, "offset": s.offset, "linebases": s.linebases, "linewidth": s.linewidth}
+
+    def debug_set_chunks(self, text_chunk_bases=0, bgzf_span_bytes=0):
+        """Test hook (rsi_ref_debug_set_chunks): the bases per transfer of a text load and the text per inflate launch of a BGZF
+        load; 0: the default."""
+        self._check(self.lib.rsi_ref_debug_set_chunks(self.handle, int(text_chunk_bases), int(bgzf_span_bytes)))
+
+    def load_device(self, i, d_out, cap, stream=None):
+        """Sequence i unfolded into device memory at address d_out (16-byte aligned, cap >= length + 64); returns the load's figures."""
+        st = RsiRefStats()
+        self._check(self.lib.rsi_ref_load_device(self.handle, self.device, int(i), d_out, int(cap), stream, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in RsiRefStats._fields_}
+
+    def load_host(self, i):
+        """Sequence i, unfolded on the device, as bytes."""
+        n = self.sequence(i)["length"]
+        out = np.zeros(max(n, 1), dtype=np.uint8)
+        self._check(self.lib.rsi_ref_load_host(self.handle, self.device, int(i), out.ctypes.data, n))
+        return out[:n].tobytes()
 
 
 class Result:

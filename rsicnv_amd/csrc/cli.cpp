@@ -11,6 +11,8 @@
 // written by the device (rsi_hot_write_track) chromosome by chromosome into part files that are joined in row order at the end.
 // -bintrack FILE saves the signal the calls are made from, one value per bin (its median, or with -bintrackvalue ratio its ratio
 // to the chromosome's median), the same way (rsi_hot_write_bin_track).
+// -f REFFILE is read by read_fasta's host loop, or -- a BGZF file always, a plain one with -refread device -- by the device reader
+// (rsi_ref: the sequence unfolded in HBM, handed to the _dfasta entry points and rsi_hot_run_device without a host copy).
 #include <fcntl.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -61,6 +63,94 @@ struct Options {
   std::string dindex;        // -dindex PATH|none: the .tbi / .csi of a BGZF bedGraph -d FILE for -c RNAME (empty: FILE.tbi, else FILE.csi, when there)
   std::string dindex_path;   // what that gives (main sets it); empty: the whole file is read
   bool trackindex = false;   // -trackindex: FILE.tbi beside every track that is BGZF, built from the device's records
+  std::string refread;       // -refread device|host: the reference through the device reader (rsi_ref) or read_fasta (empty: host for text, device for BGZF)
+  std::string refindex;      // -refindex PATH|none: the .gzi of a BGZF reference (empty: REFFILE.gzi when there, else the members are walked)
+  bool ref_device = false;   // what that gives (main sets it)
+};
+
+// The reference through the device reader: one rsi_ref per device, shared by that device's workers (a handle loads
+// one sequence at a time), and what all of a run's loads read, for the log's one "#reference:" line.
+struct RefTotals {
+  std::mutex mu;
+  int64_t loads = 0, bytes = 0, text = 0, members = 0;
+  double kernel_ms = 0, wall_ms = 0;
+};
+struct RefReader {
+  rsi_ref* ref = nullptr;
+  int device = 0;
+  RefTotals* totals = nullptr;
+  // Sequence buffers handed back by release(), kept for the next chromosome: a device allocation or free per chromosome would
+  // synchronise the device under the workers' feet.  At most as many exist as sequences were ever held at once.
+  std::mutex pool_mu;
+  std::vector<std::pair<void*, int64_t>> spare, lent;   // (buffer, its bytes)
+  ~RefReader() {
+    for (auto& b : spare) rsi_ref_device_free(device, b.first);
+    for (auto& b : lent) rsi_ref_device_free(device, b.first);
+    rsi_ref_close(ref);
+  }
+  void* take(int64_t bytes) {
+    std::lock_guard<std::mutex> lk(pool_mu);
+    size_t best = spare.size();   // the smallest spare buffer that is large enough
+    for (size_t k = 0; k < spare.size(); ++k) if (spare[k].second >= bytes && (best == spare.size() || spare[k].second < spare[best].second)) best = k;
+    if (best < spare.size()) { lent.push_back(spare[best]); spare.erase(spare.begin() + (ptrdiff_t)best); return lent.back().first; }
+    if (!spare.empty()) {   // none fits: the largest of them makes room for the new one
+      size_t big = 0;
+      for (size_t k = 1; k < spare.size(); ++k) if (spare[k].second > spare[big].second) big = k;
+      rsi_ref_device_free(device, spare[big].first);
+      spare.erase(spare.begin() + (ptrdiff_t)big);
+    }
+    void* p = rsi_ref_device_alloc(device, bytes);
+    if (p) lent.emplace_back(p, bytes);
+    return p;
+  }
+  bool open(const Options& o, int dev, RefTotals* t, std::string& err) {
+    device = dev; totals = t;
+    const char* gzi = o.refindex.empty() ? nullptr : o.refindex.c_str();
+    if (rsi_ref_open(o.reffile.c_str(), nullptr, gzi, &ref) == RSI_OK) return true;
+    err = rsi_ref_last_error(nullptr);
+    return false;
+  }
+  // The sequence read_fasta would take for `chr`, unfolded into a device buffer of its own (release() frees it); false: err says why
+  // (missing: no such sequence, which read_fasta tells stderr alone)
+  bool load(const std::string& chr, void*& d_fasta, int64_t& n, std::string& err, bool* missing = nullptr) {
+    d_fasta = nullptr;
+    const int i = rsi_ref_find(ref, chr.c_str());
+    if (missing) *missing = i < 0;
+    if (i < 0) { err = chr + " not found in fai index"; return false; }
+    rsi_ref_seq s;
+    rsi_ref_sequence(ref, i, &s);
+    n = s.length;
+    d_fasta = take(n + 64);
+    if (!d_fasta) { err = "out of device memory for the sequence of " + chr; return false; }
+    rsi_ref_stats st;
+    if (rsi_ref_load_device(ref, device, i, d_fasta, n + 64, nullptr, &st) != RSI_OK) {
+      err = rsi_ref_last_error(ref);
+      release(d_fasta);
+      d_fasta = nullptr;
+      return false;
+    }
+    std::lock_guard<std::mutex> lk(totals->mu);
+    ++totals->loads; totals->bytes += st.bytes_read; totals->text += st.text_bytes; totals->members += st.members;
+    totals->kernel_ms += st.t_kernel_ms; totals->wall_ms += st.t_wall_ms;
+    return true;
+  }
+  void release(void* d_fasta) {
+    std::lock_guard<std::mutex> lk(pool_mu);
+    for (size_t k = 0; k < lent.size(); ++k) if (lent[k].first == d_fasta) { spare.push_back(lent[k]); lent.erase(lent.begin() + (ptrdiff_t)k); return; }
+  }
+  // in the style of inflate_line
+  std::string line() const {
+    std::ostringstream o;
+    const bool bgzf = rsi_ref_format(ref) == 1;
+    const std::string gzi = rsi_ref_index_path(ref);
+    std::lock_guard<std::mutex> lk(totals->mu);
+    o << "#reference: " << (bgzf ? "BGZF" : "text");
+    if (bgzf) o << ", " << (gzi.empty() ? std::string("members walked") : "index " + gzi);
+    o << ", " << totals->loads << " sequences, " << totals->bytes << (bgzf ? " compressed bytes read, " : " bytes read, ");
+    if (bgzf) o << totals->text << " text bytes, " << totals->members << " members inflated, ";
+    o << "kernels " << totals->kernel_ms << " ms, loads " << totals->wall_ms << " ms (device)\n";
+    return o.str();
+  }
 };
 
 int usage() {
@@ -92,6 +182,8 @@ int usage() {
             << "   -trackformat text|bgzf  -track and -bintrack as plain text or as BGZF (default: BGZF when FILE ends in .gz or .bgz)\n"
             << "   -trackindex  write the tabix index FILE.tbi beside every BGZF track, see below\n"
             << "   -dindex PATH|none  the tabix / CSI index of a BGZF bedGraph -d FILE, used with -c RNAME (default: FILE.tbi, else FILE.csi)\n"
+            << "   -refread device|host  read REFFILE on the GPU, or with the host loop (default: host for plain text, device for BGZF), see below\n"
+            << "   -refindex PATH|none  the .gzi of a BGZF REFFILE (default: REFFILE.gzi when there; none: the members are walked)\n"
             << "\nNote:\n"
             << "   This build runs the read-depth hot path on an MI355X; input is a read depth file\n"
             << "   (samtools mpileup BAM | cut -f2,4) with -c RNAME, a whole-genome depth file without -c\n"
@@ -134,6 +226,12 @@ int usage() {
             << "   -trackindex writes FILE.tbi beside every BGZF track (with -samples: FILE.k.tbi): the index tabix -p bed would make,\n"
             << "   collected on the GPU while the track is written, so that IGV and tabix FILE chr7:1-2000000 take the file as it\n"
             << "   is.  Chromosomes longer than 2^29 bases are beyond that format; a plain-text track has no index.\n"
+            << "   -f REFFILE may be BGZF (bgzip REFFILE; samtools faidx gives REFFILE.fai, bgzip -i or -r REFFILE.gzi), told from its\n"
+            << "   first bytes, not its name: the members that hold a chromosome's lines are found through the .gzi (without one the\n"
+            << "   members' sizes are walked once), inflated on the GPU, and the lines are unfolded there by the .fai's arithmetic.\n"
+            << "   -refread device reads a plain-text REFFILE the same way; -refread host keeps the host loop (plain text only).\n"
+            << "   Works with every input and option.  An index that does not fit the file is an error, never a wrong sequence; a\n"
+            << "   plain-gzip REFFILE is refused: recompress it with bgzip.\n"
             << std::endl;
   return 0;
 }
@@ -194,6 +292,8 @@ void parse(int argc, char** argv, Options& o) {
     else if (s == "-trackformat") { o.trackformat = need(i); ++i; }
     else if (s == "-trackindex") o.trackindex = true;
     else if (s == "-dindex") { o.dindex = need(i); ++i; }
+    else if (s == "-refread") { o.refread = need(i); ++i; }
+    else if (s == "-refindex") { o.refindex = need(i); ++i; }
     else { std::cerr << "unknown option " << s << std::endl; exit(usage()); }
   }
   if (o.rdfile.empty() && o.bamfile.empty()) { std::cerr << "need input file " << std::endl; exit(usage()); }
@@ -287,15 +387,31 @@ bool arm_exclude(rsi_ctx* ctx, const Options& o, const std::string& chr, int64_t
 }
 
 // One chromosome on one context, first half: FASTA, depth (text or BAM, on the device), the hot path; then report_chromosome.
-void process_chromosome(rsi_ctx* ctx, const Options& o, const std::string& chr, bool many, ChromOutput& co) {
+// rr (the device reader, -refread device or a BGZF reference): the sequence is unfolded into a device buffer of this call's and
+// the _dfasta entry points take it from there; without it read_fasta's host string is uploaded as always.
+void process_chromosome(rsi_ctx* ctx, const Options& o, const std::string& chr, bool many, ChromOutput& co, RefReader* rr = nullptr) {
   const bool from_bam = !o.bamfile.empty();
   std::ostringstream info;
   info << "#processing " << chr << "\n";
   const double t0 = now_s();
   std::string fasta;
-  if (!read_fasta(o.reffile, chr, fasta)) { co.log = info.str(); co.fatal = !many; return; }
+  void* d_fasta = nullptr;
+  int64_t nref = 0;
+  struct Free { RefReader* rr; void*& p; ~Free() { if (rr && p) rr->release(p); } } free_fasta{rr, d_fasta};
+  if (rr) {
+    std::string err;
+    bool missing = false;
+    if (!rr->load(chr, d_fasta, nref, err, &missing)) {
+      std::cerr << err << "\n";
+      if (!missing) info << err << "\n";
+      co.log = info.str(); co.fatal = !many; return;
+    }
+  } else {
+    if (!read_fasta(o.reffile, chr, fasta)) { co.log = info.str(); co.fatal = !many; return; }
+    nref = (int64_t)fasta.size();
+  }
   const double t1 = now_s();
-  if (!arm_exclude(ctx, o, chr, (int64_t)fasta.size(), info)) { co.log = info.str(); co.fatal = true; return; }
+  if (!arm_exclude(ctx, o, chr, nref, info)) { co.log = info.str(); co.fatal = true; return; }
 
   rsi_result* res = nullptr;
   rsi_text_stats ts;
@@ -303,7 +419,10 @@ void process_chromosome(rsi_ctx* ctx, const Options& o, const std::string& chr, 
   memset(&ts, 0, sizeof(ts)); memset(&bs, 0, sizeof(bs));
   // the depth comes from a text file parsed on the device (load_data_from_text's loop, loaddata.cpp:496-517) or from
   // the BAM file's reads, inflated on the host and piled up on the device (load_data_from_bam, loaddata.cpp:277-333)
-  const int rc = from_bam
+  const int rc = rr
+      ? (from_bam ? rsi_hot_run_bam_dfasta(ctx, &o.P, o.bamfile.c_str(), chr.c_str(), o.minq, o.min_baseQ, d_fasta, nref, &res, &bs)
+                  : rsi_hot_run_text_dfasta(ctx, &o.P, o.rdfile.c_str(), d_fasta, nref, &res, &ts))
+      : from_bam
       ? rsi_hot_run_bam(ctx, &o.P, o.bamfile.c_str(), chr.c_str(), o.minq, o.min_baseQ, reinterpret_cast<const uint8_t*>(fasta.data()), (int64_t)fasta.size(), &res, &bs)
       : rsi_hot_run_text(ctx, &o.P, o.rdfile.c_str(), reinterpret_cast<const uint8_t*>(fasta.data()), (int64_t)fasta.size(), &res, &ts);
   if (rc != RSI_OK) {   // the reference prints its message and exits with status 0
@@ -526,7 +645,7 @@ bool read_fai(const std::string& fasta, std::vector<std::string>& names, std::ve
 // bed: a bedGraph file (rsi_genome_bedgraph_open); with `only` (-c RNAME) the reader knows RNAME's .fai sequence alone, and
 // the file's other chromosomes are passed over.
 bool run_genome(const Options& o, const std::vector<int32_t>& cols, std::vector<std::string>& chroms, std::vector<std::vector<ChromOutput>>& outs,
-                std::string& err, std::string& summary, bool bed = false, const std::string* only = nullptr) {
+                std::string& err, std::string& summary, bool bed = false, const std::string* only = nullptr, RefReader* rr = nullptr) {
   std::vector<std::string> names;
   std::vector<int64_t> lens;
   if (!read_fai(o.reffile, names, lens)) { err = "no reference index"; return false; }
@@ -560,7 +679,11 @@ bool run_genome(const Options& o, const std::vector<int32_t>& cols, std::vector<
     if (!o.bintrackfile.empty()) so[j].bintrackfile = o.bintrackfile + "." + std::to_string(cols[j]);
   }
 
-  struct Job { size_t idx; int j; rsi_genome_chrom c; const void* d_depth; std::shared_ptr<const std::string> fasta; double t_fasta; };
+  // fasta: read_fasta's host string, uploaded by every job; with the device reader (rr) d_fasta instead: the chromosome's sequence
+  // in a device buffer that belongs to its slot, loaded once, read by all its samples' jobs, freed when the slot is released
+  struct Job { size_t idx; int j; rsi_genome_chrom c; const void* d_depth; std::shared_ptr<const std::string> fasta; const void* d_fasta; double t_fasta; };
+  std::vector<void*> slot_fasta((size_t)rsi_genome_text_max_resident(g), nullptr);
+  auto free_slot_fasta = [&](int slot) { if (rr && slot_fasta[(size_t)slot]) { rr->release(slot_fasta[(size_t)slot]); slot_fasta[(size_t)slot] = nullptr; } };
   std::deque<Job> jobs;
   std::deque<std::vector<ChromOutput>> done_outs;   // stable references while the main thread appends
   std::vector<int> pending(rsi_genome_text_max_resident(g), 0);   // samples of each held depth buffer not run yet
@@ -589,7 +712,9 @@ bool run_genome(const Options& o, const std::vector<int32_t>& cols, std::vector<
         rsi_result* res = nullptr;
         const double t1 = now_s();
         const bool armed = arm_exclude(ctx, o, chr, j.c.n, info);   // (false: it has logged why)
-        const int rc = !armed ? RSI_ERR_BAD_ARG : rsi_hot_run_depth_device(ctx, &o.P, j.d_depth, reinterpret_cast<const uint8_t*>(j.fasta->data()), j.c.n, &res);
+        const int rc = !armed ? RSI_ERR_BAD_ARG
+            : j.d_fasta ? rsi_hot_run_device(ctx, &o.P, j.d_depth, j.d_fasta, j.c.n, &res)
+                        : rsi_hot_run_depth_device(ctx, &o.P, j.d_depth, reinterpret_cast<const uint8_t*>(j.fasta->data()), j.c.n, &res);
         if (rc != RSI_OK) {   // as the BAM walk: a chromosome that has data and fails stops the run (rsi.cpp exits) -- of its sample
           if (armed) info << rsi_hot_last_error(ctx) << "\n";
           co.log = info.str();
@@ -621,7 +746,7 @@ bool run_genome(const Options& o, const std::vector<int32_t>& cols, std::vector<
     {   // hand the run chromosomes' buffers back; hold at most max_held (nwork when memory allows)
       std::unique_lock<std::mutex> lk(mu);
       for (;;) {
-        for (int slot : returned) { rsi_genome_text_release(g, slot); --held; }
+        for (int slot : returned) { free_slot_fasta(slot); rsi_genome_text_release(g, slot); --held; }
         returned.clear();
         if (held < max_held) break;
         cv_back.wait(lk, [&] { return !returned.empty(); });
@@ -643,7 +768,16 @@ bool run_genome(const Options& o, const std::vector<int32_t>& cols, std::vector<
     }
     const double tf = now_s();
     auto fasta = std::make_shared<std::string>();
-    if (!read_fasta(o.reffile, chr, *fasta)) {   // not fatal for a run over many chromosomes (process_chromosome with `many`)
+    bool have_fasta;
+    if (rr) {
+      std::string why;
+      bool missing = false;
+      int64_t nref = 0;
+      have_fasta = rr->load(chr, slot_fasta[(size_t)c.slot], nref, why, &missing);
+      if (have_fasta && nref != c.n) { have_fasta = false; why = chr + ": the reference has " + std::to_string(nref) + " bases, the depth reader " + std::to_string(c.n); }
+      if (!have_fasta) { std::cerr << why << "\n"; free_slot_fasta(c.slot); }
+    } else have_fasta = read_fasta(o.reffile, chr, *fasta);
+    if (!have_fasta) {   // not fatal for a run over many chromosomes (process_chromosome with `many`)
       rsi_genome_text_release(g, c.slot);
       std::lock_guard<std::mutex> lk(mu);
       for (ChromOutput& co : done_outs[idx]) co.log = "#processing " + chr + "\n";
@@ -653,13 +787,14 @@ bool run_genome(const Options& o, const std::vector<int32_t>& cols, std::vector<
     std::lock_guard<std::mutex> lk(mu);
     pending[(size_t)c.slot] = nsamp;
     for (int j = 0; j < nsamp; ++j)
-      jobs.push_back(Job{idx, j, c, cols.empty() ? c.d_depth : rsi_genome_text_sample_depth(g, c.slot, j), fasta, t_fasta});
+      jobs.push_back(Job{idx, j, c, cols.empty() ? c.d_depth : rsi_genome_text_sample_depth(g, c.slot, j), fasta, rr ? slot_fasta[(size_t)c.slot] : nullptr, t_fasta});
     ++held;
     cv_job.notify_all();
   }
   { std::lock_guard<std::mutex> lk(mu); closing = true; }
   cv_job.notify_all();
   for (auto& t : threads) t.join();
+  for (size_t slot = 0; slot < slot_fasta.size(); ++slot) free_slot_fasta((int)slot);
   double bound_ms = 0, parse_ms = 0;
   rsi_genome_text_kernel_ms(g, &bound_ms, &parse_ms);
   std::ostringstream sm;
@@ -825,6 +960,35 @@ int main(int argc, char** argv) {
     std::cerr << "rsicnv: -dindex: an index serves -d FILE -c RNAME with a bedGraph FILE in BGZF only" << std::endl;
     return 1;
   }
+  // -refread, -refindex: the reference's format comes from its first bytes; BGZF goes through the device reader, plain text
+  // through read_fasta unless -refread device asks otherwise; plain gzip is refused (rsi_ref_open says how to recompress it)
+  if (!o.refread.empty() && o.refread != "device" && o.refread != "host") {
+    std::cerr << "rsicnv: -refread " << o.refread << ": expected device or host" << std::endl;
+    return 1;
+  }
+  RefTotals ref_totals;
+  std::vector<std::unique_ptr<RefReader>> ref_readers;   // one per device in use; [0] serves -gpu
+  {
+    unsigned char head[2] = {0, 0};
+    FILE* f = fopen(o.reffile.c_str(), "rb");
+    const bool compressed = f && fread(head, 1, 2, f) == 2 && head[0] == 0x1f && head[1] == 0x8b;
+    if (f) fclose(f);
+    if (compressed || o.refread == "device") {
+      std::string err;
+      ref_readers.emplace_back(new RefReader);
+      if (!ref_readers[0]->open(o, o.device, &ref_totals, err)) { std::cerr << "rsicnv: -f " << o.reffile << ": " << err << std::endl; return 1; }
+      if (compressed && o.refread == "host") {
+        std::cerr << "rsicnv: -refread host: " << o.reffile << " is BGZF, which the host loop cannot read: leave -refread out, or give -refread device" << std::endl;
+        return 1;
+      }
+      o.ref_device = true;
+    }
+    if (!o.refindex.empty() && !(o.ref_device && rsi_ref_format(ref_readers[0]->ref) == 1)) {
+      std::cerr << "rsicnv: -refindex: a .gzi serves a BGZF reference only (" << o.reffile << " is plain text)" << std::endl;
+      return 1;
+    }
+  }
+  RefReader* rr = o.ref_device ? ref_readers[0].get() : nullptr;
   // -track: refused where it cannot work, before any output or device work
   if (o.trackdepth != "raw" && o.trackdepth != "gc") {
     std::cerr << "rsicnv: -trackdepth " << o.trackdepth << ": expected raw or gc" << std::endl;
@@ -949,7 +1113,7 @@ int main(int argc, char** argv) {
     std::vector<std::string> chroms;
     std::vector<std::vector<ChromOutput>> outs;
     std::string err, summary;
-    const bool ok = run_genome(o, cols, chroms, outs, err, summary);
+    const bool ok = run_genome(o, cols, chroms, outs, err, summary, false, nullptr, rr);
     if (!ok) {   // no sample's output: the rows of a file that cannot be read through are not an answer
       std::cerr << "rsicnv: " << err << std::endl; log << "rsicnv: " << err << std::endl;
       for (size_t j = 0; j < cols.size(); ++j) { remove(out_k(j).c_str()); remove((out_k(j) + ".log").c_str()); }
@@ -987,6 +1151,7 @@ int main(int argc, char** argv) {
       }
       if (!finish_tracks(o, "." + std::to_string(cols[j]), parts, chroms.size(), slog)) tracks_ok = false;
     }
+    if (rr) summary += rr->line();
     std::cerr << summary; log << summary;
     return tracks_ok ? 0 : 1;
   }
@@ -995,7 +1160,7 @@ int main(int argc, char** argv) {
     std::vector<std::string> chroms;
     std::vector<std::vector<ChromOutput>> outs;
     std::string err, summary;
-    const bool ok = run_genome(o, cols, chroms, outs, err, summary, bedgraph, bed_one ? &o.chr : nullptr);
+    const bool ok = run_genome(o, cols, chroms, outs, err, summary, bedgraph, bed_one ? &o.chr : nullptr, rr);
     if (!ok) {   // nothing is written under OUT: the rows of a file that cannot be read through are not an answer
       for (const auto& co : outs) { std::cerr << co[0].log; log << co[0].log; }
       std::cerr << "rsicnv: " << err << std::endl; log << "rsicnv: " << err << std::endl;
@@ -1010,6 +1175,7 @@ int main(int argc, char** argv) {
       parts.add(i, outs[i][0]);
       if (outs[i][0].fatal) break;
     }
+    if (rr) summary += rr->line();
     std::cerr << summary; log << summary;
     return finish_tracks(o, "", parts, chroms.size(), log) ? 0 : 1;
   }
@@ -1023,7 +1189,7 @@ int main(int argc, char** argv) {
       const std::string& chr = todo[i];
       ChromOutput co;
       co.track_index = i;
-      process_chromosome(ctx, o, chr, many, co);
+      process_chromosome(ctx, o, chr, many, co, rr);
       if (co.bad_input) {   // as the genome mode: a depth file that cannot be read through gives no output
         std::cerr << co.log; log << co.log;
         remove(o.outfile.c_str());
@@ -1037,6 +1203,7 @@ int main(int argc, char** argv) {
       if (co.fatal) break;
     }
     rsi_hot_destroy(ctx);
+    if (rr) { std::cerr << rr->line(); log << rr->line(); }
     return finish_tracks(o, "", parts, todo.size(), log) ? 0 : 1;
   }
 
@@ -1065,6 +1232,19 @@ int main(int argc, char** argv) {
     pools.push_back(pl);
   }
   std::cerr << "rsicnv: " << todo.size() << " chromosomes over " << pools.size() << " device(s), " << nwork << " in flight each" << std::endl;
+  // the device reader: a handle of its own per device (a handle belongs to the device it first loads on), shared by that device's workers
+  std::vector<RefReader*> dev_reader(pools.size(), nullptr);
+  for (size_t d = 0; rr && d < pools.size(); ++d) {
+    if (d == 0 && physical(0) == o.device) { dev_reader[0] = rr; continue; }
+    std::string err;
+    ref_readers.emplace_back(new RefReader);
+    if (!ref_readers.back()->open(o, physical((int)d), &ref_totals, err)) {
+      std::cerr << "rsicnv: -f " << o.reffile << ": " << err << std::endl;
+      for (rsi_pool* pl : pools) rsi_pool_destroy(pl);
+      return 1;
+    }
+    dev_reader[d] = ref_readers.back().get();
+  }
   std::vector<std::vector<int>> per_dev(pools.size());
   {
     std::vector<int> order(todo.size());
@@ -1091,7 +1271,7 @@ int main(int argc, char** argv) {
           const int k = next[d].fetch_add(1);
           if (k >= (int)per_dev[d].size()) break;
           const int i = per_dev[d][(size_t)k];
-          process_chromosome(ctx, o, todo[(size_t)i], true, outs[(size_t)i]);
+          process_chromosome(ctx, o, todo[(size_t)i], true, outs[(size_t)i], dev_reader[d]);
         }
       });
   for (auto& t : threads) t.join();
@@ -1101,5 +1281,6 @@ int main(int argc, char** argv) {
     parts.add(i, outs[i]);
   }
   for (rsi_pool* pl : pools) rsi_pool_destroy(pl);
+  if (rr) { std::cerr << rr->line(); log << rr->line(); }
   return finish_tracks(o, "", parts, todo.size(), log) ? 0 : 1;   // (-track, -bintrack: one device only, -gpus 1)
 }

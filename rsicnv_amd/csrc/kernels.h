@@ -526,6 +526,20 @@ void launch_parse_genome(GenomeFormat format, const void* text, long long begin,
 struct InflateBlock { long long coff, out; uint32_t clen, isize, crc, pad; };
 void launch_inflate_bgzf(const void* comp, const InflateBlock* blocks, int nblocks, void* text, int* last_nl,
                          unsigned long long* status, hipStream_t stream);
+// ---- The reference sequence unfolded (kernels_ref.hip) ----
+// span[0, span_len): text of a FASTA file in HBM, its first byte at text offset span_off; span is 16-byte aligned and its buffer
+// readable up to span_len rounded up to 16.  L: one sequence's .fai layout (linebases >= 1, linewidth >= linebases, length <
+// 2^31 - 4096).  The bases [k0, k1), 0 <= k0 < k1 <= length, whose bytes -- and, behind a base that ends a full line, the
+// line's terminator -- lie inside the span (ref_host.h: contained_bases) go to out[k0 .. k1) unchanged, one byte each; out is 16-byte aligned.  flags[0] += the
+// terminator positions that hold something other than '\n' or '\r', flags[1] += the base positions that hold '\n', '\r' or '>'
+// (or lie outside the span): non-zero means the layout does not fit the text.  A terminator that would lie behind the span (the
+// file's last line may lack it) is not looked at.  Launching twice writes the same bytes; no workgroup waits for another.
+constexpr int kRefTileBases = 4096;      // bases per workgroup
+constexpr int kRefStageBytes = 16896;    // LDS for a tile's text: lines of one base with "\r\n" and a byte to spare still fit
+struct RefLayout { long long offset, length; int linebases, linewidth; };
+bool ref_unfold_staged(const RefLayout& L);   // the tile's text goes through LDS (else it is picked from HBM byte by byte)
+void launch_ref_unfold(const void* span, long long span_off, long long span_len, const RefLayout& L, long long k0, long long k1,
+                       void* out, unsigned int* flags, hipStream_t stream);
 // Name bytes of the boundary pass's entries bounds[k0, k1) into out[(i - k0) * 256 ...] (at most 255 bytes each).
 void launch_gather_names(const void* text, const NameBound* bounds, unsigned k0, unsigned k1, char* out, hipStream_t stream);
 

@@ -29,7 +29,11 @@ with -dindex none, alternating after a warm-up pair.  The record holds the media
 figures, and says whether the rows agree.
 
 usage: genome_text_e2e.py [--dir SCRATCH] [--out JSON] [--config 4] [--workers 4] [--max-gb G] [--compress none|bgzf|gzip]
-                          [--samples K] [--format depth|bedgraph] [--index-read K [--index-scale S] [--index-repeat R]]"""
+                          [--samples K] [--format depth|bedgraph] [--index-read K [--index-scale S] [--index-repeat R]]
+                          [--refread host|device]
+
+--refread host|device passes -refread to the timed whole-genome run (the reference through read_fasta or through the device
+reader), so that two calls compare the two end to end."""
 import argparse, json, os, re, shutil, subprocess, sys, tempfile, time, zlib
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import ctypes as C
@@ -51,6 +55,8 @@ ap.add_argument("--format", choices=["depth", "bedgraph"], default="depth",
 ap.add_argument("--index-read", type=int, default=0, help="K > 0: only time -c on the last of K chromosomes of a BGZF bedGraph, with and without its index")
 ap.add_argument("--index-scale", type=float, default=0.05, help="--index-read: shrinks the chromosomes")
 ap.add_argument("--index-repeat", type=int, default=3)
+ap.add_argument("--refread", choices=["host", "device"], default=None,
+                help="the timed whole-genome run with -refread host or device (DESIGN.md 6j); default: the command line's own default")
 args = ap.parse_args()
 if args.format == "bedgraph" and (args.samples > 0 or args.compress == "gzip"):
     raise SystemExit("genome_text_e2e: --format bedgraph takes --compress none or bgzf, without --samples")
@@ -360,8 +366,8 @@ print(f"[genome_text_e2e] {len(chosen)} of 24 chromosomes, {bases / 1e9:.3f} Gb,
 def run_once(tag, depth_file=genome):
     out = os.path.join(args.dir, f"out_{tag}.txt")
     t = time.perf_counter()
-    r = subprocess.run([exe, "rsi", "-f", fa, "-d", depth_file, "-o", out, "-np", "-workers", str(args.workers)] + flag_args,
-                       capture_output=True, text=True, timeout=1800)
+    r = subprocess.run([exe, "rsi", "-f", fa, "-d", depth_file, "-o", out, "-np", "-workers", str(args.workers)] + flag_args +
+                       (["-refread", args.refread] if args.refread else []), capture_output=True, text=True, timeout=1800)
     wall = time.perf_counter() - t
     if r.returncode != 0:
         raise RuntimeError(r.stderr[-2000:])
@@ -389,7 +395,7 @@ rec = {"config": f"configs[{args.config - 1}]: {flags}", "chromosomes_run": len(
        "one_process": {"s": round(wall, 3), "bases_per_s": round(bases / wall, 1), "text_bytes_per_s": round(text_bytes / wall, 1)},
        "reader_s": float(m.group(1)) if m else None, "boundary_kernels_ms": float(m.group(3)) if m else None,
        "parse_kernels_ms": float(m.group(4)) if m else None,
-       "calls": len(rows), "rows_match": rows == own_rows,
+       "calls": len(rows), "rows_match": rows == own_rows, "refread": args.refread or "default",
        "compare": "profiles/r5_e2e_genome.json: one process per chromosome, 1.85e8 bases/s one at a time, 5.75e8 with four at once",
        "note": "rsicnv rsi -f REF -d genome.depth -o OUT -np: process start, FASTA reads, one pass of the depth text through the device, "
                "detection of every chromosome on a pool, one output file; second of two runs (the file in the page cache as far as it holds it)"}

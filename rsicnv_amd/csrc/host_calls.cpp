@@ -655,7 +655,7 @@ void test_block_segments(const CallerInput& in, IntSpan status, std::vector<Cand
   const VecView bins{in.binmedint};
   std::vector<Candidate> T = segs;
   // First round (rsi.cpp:430-436): test i sees which of the segments before it were just rejected (a rejected neighbour is no
-  // longer jumped over).  With a device tester and enough segments to pay for its four launches, all of them are tested in one
+  // longer jumped over).  With a device tester and enough segments to pay for its three launches, all of them are tested in one
   // batch against the list as it stands.  Such a result holds for test i unless a segment rejected since lies where i's LEFT
   // walk went (the segments behind i are untouched when i's turn comes; its own fields do not change): every rejected
   // segment must end before the last position that walk examined.  Comparing the whole plans, as the final tests do, is too

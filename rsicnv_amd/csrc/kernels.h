@@ -421,7 +421,7 @@ struct CandJob {            // one isitcnvwrap test, prepared on the host from t
   int32_t cut;              // bit 0 / 1: the left / right chain was cut short by the host (the kernel reports when it runs out)
   double right_cap;         // 2*chklen*d (the right side appends while used < right_cap)
   int64_t iscratch_off;     // value scratch, in int32 units (a multiple of 4): the pieces of cand_scratch_bytes
-  int64_t lscratch_off;     // int64 scratch: capacity + 1 rounded up to a multiple of 4; offset even
+  int64_t lscratch_off;     // int64 scratch (one-workgroup form only): capacity + 1 rounded up to a multiple of 4; offset even
 };
 struct CandOut {
   int32_t flags;            // 1: empty neighbourhood, 2: body value range beyond the LDS histogram, 4: same for the window means, 8: cut chain used up, 16: the left walk ran short where the host had vouched it would not (split form)
@@ -451,21 +451,20 @@ inline size_t cand_scratch_bytes(int top, int capacity, int budget, int value_by
   return up16((size_t)(top + 1 > 0 ? top + 1 : 0) * vb) + up16((size_t)capacity * 4) +
          up16((size_t)(capacity < budget ? capacity : budget) * vb) + (split ? up16((size_t)capacity * vb) : 0);
 }
-// The same test spread over several workgroups (four launches: the two walks side by side; chunked prefix + the candidate's
-// statistics; chunked window means; chunked histogram with a last-workgroup fold).  mid: njobs CandMid records, `done`
+// The same test spread over several workgroups (three launches: the two walks side by side; chunked window means by sliding
+// sums + the candidate's statistics; chunked histogram with a last-workgroup fold).  No int64 scratch.  mid: njobs CandMid records, `done`
 // zero before the first launch (each launch leaves it zero); ghist: njobs x kCandHistBins counters, zero likewise.
 constexpr int kCandChunks = 16;
 struct CandMid {
   int32_t lcnt, lreach, lused, rcnt_max, rreach, rused;
   uint32_t done, body_flags;
-  long long totals[kCandChunks];
   float flo[kCandChunks], fhi[kCandChunks];
   double m1[kCandChunks], m2[kCandChunks];
   int32_t body_min, body_max;
   double body_q[3], body_s1, body_s2;
 };
 void launch_candidate_test_split(DepthRef rdc, int64_t ncompact, const CandJob* jobs, int njobs, const void* chains,
-                                 int32_t* iscratch, long long* lscratch, double RDmedian, CandMid* mid, uint32_t* ghist,
+                                 int32_t* iscratch, double RDmedian, CandMid* mid, uint32_t* ghist,
                                  CandOut* outs, int value_bytes, hipStream_t stream);
 void launch_candidate_test(DepthRef rdc, int64_t ncompact, const CandJob* jobs, int njobs, const void* chains,
                            int32_t* iscratch, long long* lscratch, double RDmedian, CandOut* outs, int value_bytes, hipStream_t stream);

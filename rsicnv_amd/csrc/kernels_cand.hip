@@ -8,6 +8,11 @@
 // as in the reference; quantiles come from integer histograms on the reference's grids.  The one
 // deviation is the second moment of the window means, summed here as a tree of doubles instead of
 // sequentially (relative difference ~1e-15; it only enters the p-value).
+//
+// Two forms of the neighbourhood test.  k_candidate_test: one workgroup per test, window sums from an exact prefix array.
+// The split form, three launches: k_cand_gather (the two walks side by side), k_cand_sums (sixteen chunks of windows per
+// test, window sums by sliding differences -- no prefix array, no int64 scratch, nothing waits for another workgroup --
+// and the candidate's own statistics in a seventeenth workgroup), k_cand_hist (0.01-grid histogram, last-workgroup fold).
 #include "kernels.h"
 
 namespace rsik {
@@ -475,7 +480,7 @@ __device__ inline CandBufs cand_buffers(const CandJob& J, int32_t* iscratch, lon
   b.ref = reinterpret_cast<int32_t*>(p); p += up16((size_t)J.capacity * 4);
   b.thin = p; p += up16((size_t)(J.capacity < J.budget ? J.capacity : J.budget) * vb);
   b.right = p;
-  b.P = lscratch + J.lscratch_off;
+  b.P = lscratch ? lscratch + J.lscratch_off : nullptr;   // the split form has no prefix array
   return b;
 }
 // four consecutive stored values from a 4-aligned index of a piece
@@ -566,7 +571,7 @@ __global__ __launch_bounds__(kTestThreads) void k_candidate_test(const TD* __res
   // ---- body statistics: integer histogram quantiles (partition_stat_tp with dy = 1), sum, sum of squares ----
   {
     int lo = 0x7fffffff, hi = (int)0x80000000; long long s1 = 0, s2 = 0;
-    for (int q0 = threadIdx.x; q0 < width; q0 += 8 * kTestThreads) {   // eight independent loads per round (see k_cand_prefix)
+    for (int q0 = threadIdx.x; q0 < width; q0 += 8 * kTestThreads) {   // eight independent loads per round (see k_cand_sums)
       int x[8];
 #pragma unroll
       for (int k = 0; k < 8; ++k) { const int q = q0 + k * kTestThreads; x[k] = body_at(q < width ? q : q0); }
@@ -724,8 +729,9 @@ __global__ __launch_bounds__(kTestThreads) void k_candidate_test(const TD* __res
 
 // ------------------------------------------------------------------------------------------
 // The neighbourhood test over several workgroups.  Same arithmetic as k_candidate_test (see there for the reference
-// lines); only the order in which the two float moments of the window means are summed differs (chunks, then a fixed
-// order over the chunks).  The neighbourhood is not materialised: ref(j) = left part ++ right part is read in place.
+// lines); only the order in which the two float moments of the window means are summed differs (a thread's sixteen
+// consecutive windows, the chunk's threads as a tree, then a fixed order over the chunks).  The neighbourhood is not
+// materialised: ref(j) = left part ++ right part is read in place.
 struct CandGeom { int used0, rcnt, nref_raw, nref, nbody, nbody_eff, width, nwin; bool thin; };
 
 __device__ inline CandGeom cand_geometry(const CandJob& J, const CandMid& M) {
@@ -756,8 +762,6 @@ __device__ inline int cand_value(const CandJob& J, const CandGeom& g, const TS* 
   return (int)(j < g.used0 ? left[J.top + 1 - g.used0 + j] : right[j - g.used0]);
 }
 __device__ inline int cand_chunk_len(int n) { return (((n + kCandChunks - 1) / kCandChunks) + 3) & ~3; }
-constexpr int kCandP32MaxChunk = 16000000;   // 255 x this many bytes still fit 32 bits: chunk-local prefixes of byte depth are kept as uint32
-
 // launch 1: grid (2, njobs) -- the left and the right walk of every test side by side
 template <typename TD, typename TS>
 __global__ __launch_bounds__(kTestThreads) void k_cand_gather(const TD* __restrict__ A, int64_t N, const CandJob* __restrict__ jobs,
@@ -793,70 +797,149 @@ __global__ __launch_bounds__(kTestThreads) void k_cand_gather(const TD* __restri
   }
 }
 
-// launch 2: grid (kCandChunks + 1, njobs) -- chunk-local exact prefix of the neighbourhood (+ chunk totals); the last
-// workgroup of a job computes the candidate's own statistics meanwhile
+// Sixteen consecutive values of the neighbourhood as a thread holds them: in the width they are stored in, so that the
+// sixteen bytes of a load stay four registers until a value is used.
+template <typename TS> struct CandRun16;
+template <> struct CandRun16<uint8_t> {
+  uint32_t w[4];
+  __device__ inline void clear() { w[0] = w[1] = w[2] = w[3] = 0u; }
+  __device__ inline void load(const uint8_t* p) { const WalkBytes16 b = *reinterpret_cast<const WalkBytes16*>(p); w[0] = b.w[0]; w[1] = b.w[1]; w[2] = b.w[2]; w[3] = b.w[3]; }
+  __device__ inline void put(int k, int x) { w[k >> 2] |= (uint32_t)x << (8 * (k & 3)); }   // behind clear(), k a constant
+  __device__ inline int get(int k) const { return (int)((w[k >> 2] >> (8 * (k & 3))) & 0xffu); }
+  __device__ inline long long sum() const {   // four bytes a step: sum of absolute differences against zero
+    unsigned s = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) s = __builtin_amdgcn_sad_u8(w[q], 0u, s);
+    return (long long)s;
+  }
+};
+template <> struct CandRun16<int32_t> {
+  int v[16];
+  __device__ inline void clear() {
+#pragma unroll
+    for (int k = 0; k < 16; ++k) v[k] = 0;
+  }
+  __device__ inline void load(const int32_t* p) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { const WalkInts4 b = *reinterpret_cast<const WalkInts4*>(p + 4 * q); v[4 * q] = b.x; v[4 * q + 1] = b.y; v[4 * q + 2] = b.z; v[4 * q + 3] = b.w; }
+  }
+  __device__ inline void put(int k, int x) { v[k] = x; }
+  __device__ inline int get(int k) const { return v[k]; }
+  __device__ inline long long sum() const {
+    long long s = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) s += v[k];
+    return s;
+  }
+};
+// ref(i0 .. i0 + 15); those at `lim` and beyond come back as 0.  Where the sixteen lie on one side of the seam at used0 and
+// nothing is thinned: ONE 16-byte load of stored bytes, four of stored ints (a load per value makes the 64 lanes of every
+// load touch 64 cache lines, sixteen times over); else a value at a time through cand_value.
+template <typename TS>
+__device__ inline void cand_load16(const CandJob& J, const CandGeom& g, const TS* __restrict__ left, const TS* __restrict__ right,
+                                   int i0, int lim, CandRun16<TS>& r) {
+  if (!g.thin && i0 + 16 <= lim && (i0 + 16 <= g.used0 || i0 >= g.used0)) {
+    r.load(i0 < g.used0 ? left + (J.top + 1 - g.used0 + i0) : right + (i0 - g.used0));
+  } else {
+    r.clear();
+#pragma unroll
+    for (int k = 0; k < 16; ++k) if (i0 + k < lim) r.put(k, cand_value(J, g, left, right, i0 + k));
+  }
+}
+
+// How many of the kCandChunks workgroups share a job's windows.  Every chunk sums its first window by itself (`width`
+// values), so that no chunk waits for another; with all sixteen that is 16 x width values, 3.2 x nref at the default
+// -reflen (nref = 5 x width).  Where the candidate is long against its window count the job takes fewer, longer chunks:
+// as many as keep chunks x width <= 4 x nref (at least four, since nref > width where there is a window at all).
+__device__ inline int cand_sum_chunks(const CandGeom& g) {
+  const long long fit = 4ll * g.nref / g.width;
+  return fit < kCandChunks ? (int)fit : kCandChunks;
+}
+__device__ inline int cand_sum_chunk_len(int nwin, int chunks) { return (((nwin + chunks - 1) / chunks) + 3) & ~3; }   // cand_chunk_len for all sixteen
+
+// launch 2: grid (kCandChunks + 1, njobs) -- float window means of a chunk of windows, their extremes and moments, from
+// exact window sums by sliding differences: S(q + 1) = S(q) + ref(q + width) - ref(q).  No prefix array: a chunk sums its
+// first window outright, then takes rounds of 16 x 1024 windows -- sixteen consecutive ones per thread, their differences
+// from two 16-byte loads, ONE exact int64 block scan of the per-thread totals, a carry from round to round.  Every sum is
+// the integer the prefix difference was, so every mean is the same float.  The last workgroup of a job computes the
+// candidate's own statistics meanwhile.
 template <typename TD, typename TS>
-__global__ __launch_bounds__(kTestThreads) void k_cand_prefix(const TD* __restrict__ A, const CandJob* __restrict__ jobs,
-                                                          int32_t* __restrict__ iscratch, long long* __restrict__ lscratch,
-                                                          CandMid* __restrict__ mid) {
+__global__ __launch_bounds__(kTestThreads) void k_cand_sums(const TD* __restrict__ A, const CandJob* __restrict__ jobs,
+                                                        int32_t* __restrict__ iscratch, CandMid* __restrict__ mid) {
   extern __shared__ unsigned int s_hist[];   // kCandHistBins counters (candidate statistics only)
-  __shared__ long long s_l[kMaxWaves];
-  __shared__ int s_i2[kMaxWaves];
+  __shared__ long long s_l[kMaxWaves];       // also the double moments' exchange
+  __shared__ int s_i2[kMaxWaves];            // also the float extremes' exchange
   __shared__ int s_scan[kMaxWaves];
   __shared__ int s_q[3];
   const CandJob J = jobs[blockIdx.y];
   CandMid& M = mid[blockIdx.y];
   const CandGeom g = cand_geometry(J, M);
-  const CandBufs b = cand_buffers(J, iscratch, lscratch, (int)sizeof(TS));
+  const CandBufs b = cand_buffers(J, iscratch, nullptr, (int)sizeof(TS));
   const TS* const left = reinterpret_cast<const TS*>(b.left);
   const TS* const right = reinterpret_cast<const TS*>(b.right);
   if (g.nwin <= 0 || g.width <= 0) return;
+  const int width = g.width;
   if (blockIdx.x < kCandChunks) {
-    const int Lc = cand_chunk_len(g.nref);
-    const int cb = blockIdx.x * Lc;
-    int ce = cb + Lc; if (ce > g.nref) ce = g.nref;
+    constexpr int kPer = 16, kRound = kPer * kTestThreads;
+    const int chunks = cand_sum_chunks(g);
+    const int Wc = cand_sum_chunk_len(g.nwin, chunks);
+    const int wb = (int)blockIdx.x < chunks ? (int)blockIdx.x * Wc : g.nwin;
+    int we = wb + Wc; if (we > g.nwin) we = g.nwin;
+    float flo = 3.0e38f, fhi = -3.0e38f; double m1 = 0, m2 = 0;
+    if (wb >= we) {   // a chunk without windows leaves the neutral elements
+      if (threadIdx.x == 0) { M.flo[blockIdx.x] = flo; M.fhi[blockIdx.x] = fhi; M.m1[blockIdx.x] = m1; M.m2[blockIdx.x] = m2; }
+      return;
+    }
+    // ---- the first window's sum: a plain reduction, four blocks of sixteen values in flight per thread ----
     long long carry = 0;
-    // byte depth: a chunk's local prefix stays below 2^24 (62 500 values of at most 255), so it is kept in 32 bits -- half the bytes
-    // this launch writes and the next one reads (the prefixes were most of the split form's memory traffic)
-    uint32_t* const P32 = reinterpret_cast<uint32_t*>(b.P);
-    const bool p32 = sizeof(TD) == 1 && Lc <= kCandP32MaxChunk;
-    if (blockIdx.x == 0 && threadIdx.x == 0) { if (p32) P32[0] = 0u; else b.P[0] = 0; }
-    // sixteen consecutive values per thread and round (sixteen independent loads, ONE block scan): with four per round the
-    // chunk's 62 000 values took sixteen rounds of barriers
-    constexpr int kPer = 16;
-    for (int t0 = cb; t0 < ce; t0 += kPer * kTestThreads) {
-      const int e = t0 + kPer * (int)threadIdx.x;
-      int v[kPer];
-      if (!g.thin && e + kPer <= ce && (e + kPer <= g.used0 || e >= g.used0)) {
-        // sixteen consecutive values from one side of the neighbourhood: ONE 16-byte load of stored bytes, four of stored ints
-        // (a load per value makes the 64 lanes of every load touch 64 cache lines, sixteen times over)
-        const TS* src = e < g.used0 ? left + (J.top + 1 - g.used0 + e) : right + (e - g.used0);
-        if constexpr (sizeof(TS) == 1) {
-          const WalkBytes16 w16 = *reinterpret_cast<const WalkBytes16*>(src);
+    {
+      const int lim = wb + width;
+      for (int i0 = wb + kPer * (int)threadIdx.x; i0 < lim; i0 += 4 * kRound) {
+        CandRun16<TS> v[4];
 #pragma unroll
-          for (int k = 0; k < kPer; ++k) v[k] = (int)((w16.w[k >> 2] >> (8 * (k & 3))) & 0xffu);
-        } else {
+        for (int r = 0; r < 4; ++r) cand_load16(J, g, left, right, i0 + r * kRound, lim, v[r]);
 #pragma unroll
-          for (int q = 0; q < 4; ++q) { const WalkInts4 w4 = *reinterpret_cast<const WalkInts4*>(src + 4 * q); v[4 * q] = w4.x; v[4 * q + 1] = w4.y; v[4 * q + 2] = w4.z; v[4 * q + 3] = w4.w; }
-        }
-      } else {
-#pragma unroll
-        for (int k = 0; k < kPer; ++k) v[k] = e + k < ce ? cand_value(J, g, left, right, e + k) : 0;
+        for (int r = 0; r < 4; ++r) carry += v[r].sum();
       }
+      carry = block_reduce(carry, [](long long a, long long b2) { return a + b2; }, s_l);
+    }
+    // ---- the other windows by differences (depths are not negative, so a difference of two fits an int) ----
+    float* const Wm = reinterpret_cast<float*>(b.ref);
+    const double dw = (double)width;
+    for (int q0 = wb; q0 < we; q0 += kRound) {
+      const int e = q0 + kPer * (int)threadIdx.x;
+      CandRun16<TS> out, in;   // the values that leave the sixteen windows and those that enter them
+      cand_load16(J, g, left, right, e, we, out);
+      cand_load16(J, g, left, right, e + width, we + width, in);
+      int d[kPer];
       long long run = 0;
 #pragma unroll
-      for (int k = 0; k < kPer; ++k) run += v[k];
+      for (int k = 0; k < kPer; ++k) { d[k] = in.get(k) - out.get(k); run += d[k]; }
       long long total;
-      long long at = carry + block_exscan_i64(run, s_l, &total);
+      long long S = carry + block_exscan_i64(run, s_l, &total);   // the sum of window e
+      float w[kPer];
 #pragma unroll
-      for (int k = 0; k < kPer; ++k) { at += v[k]; if (e + k < ce) { if (p32) P32[e + k + 1] = (uint32_t)at; else b.P[e + k + 1] = at; } }
+      for (int k = 0; k < kPer; ++k) { w[k] = (float)((double)S / dw); S += d[k]; }
+      if (e + kPer <= we) {   // e is a multiple of four (so is every chunk's length): 16-byte stores
+#pragma unroll
+        for (int q = 0; q < 4; ++q) *reinterpret_cast<float4*>(Wm + e + 4 * q) = make_float4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+      } else {
+#pragma unroll
+        for (int k = 0; k < kPer; ++k) if (e + k < we) Wm[e + k] = w[k];
+      }
+#pragma unroll
+      for (int k = 0; k < kPer; ++k)
+        if (e + k < we) { flo = w[k] < flo ? w[k] : flo; fhi = w[k] > fhi ? w[k] : fhi; m1 += (double)w[k]; m2 += (double)w[k] * (double)w[k]; }
       carry += total;
     }
-    if (threadIdx.x == 0) M.totals[blockIdx.x] = carry;
+    flo = block_reduce(flo, [](float a, float b2) { return a < b2 ? a : b2; }, reinterpret_cast<float*>(s_i2));
+    fhi = block_reduce(fhi, [](float a, float b2) { return a > b2 ? a : b2; }, reinterpret_cast<float*>(s_i2));
+    m1 = block_reduce(m1, [](double a, double b2) { return a + b2; }, reinterpret_cast<double*>(s_l));
+    m2 = block_reduce(m2, [](double a, double b2) { return a + b2; }, reinterpret_cast<double*>(s_l));
+    if (threadIdx.x == 0) { M.flo[blockIdx.x] = flo; M.fhi[blockIdx.x] = fhi; M.m1[blockIdx.x] = m1; M.m2[blockIdx.x] = m2; }
     return;
   }
   // ---- candidate statistics: integer histogram quantiles (partition_stat_tp with dy = 1), sum, sum of squares ----
-  const int width = g.width;
   auto body_at = [&](int q) -> int {
     return (int)(g.thin ? A[J.start + (int)((double)q / (double)g.nbody_eff * (double)g.nbody)] : A[J.start + q]);
   };
@@ -866,8 +949,14 @@ __global__ __launch_bounds__(kTestThreads) void k_cand_prefix(const TD* __restri
     // thread -- into a histogram over the byte values themselves; minimum, maximum, sum and sum of squares follow from its 256
     // counters exactly, and the quantile walk starts at the minimum's counter.  The general form below reads the candidate
     // twice, a value per load: 100 us for a candidate of 200 000 bases, the longest workgroup of the launch by far.
-    for (unsigned e = threadIdx.x; e < 260; e += kTestThreads) s_hist[e] = 0;
+    // At 30x nearly every base falls into some twenty values, and the lanes of an LDS atomic that meet on a counter take
+    // turns.  So every value has a counter per bank, [256][32], and a lane adds to the column of its own bank: the 32 lanes
+    // the LDS serves together never meet.  (A set of counters per wave would not help: waves take turns at the LDS anyway,
+    // it is the lanes of ONE instruction that collide.)  Folded into 256 counters behind the pass, 260 for the walk.
+    constexpr unsigned kCols = 32, kFold = 256 * kCols;
+    for (unsigned e = threadIdx.x; e < kFold + 260; e += kTestThreads) s_hist[e] = 0;
     __syncthreads();
+    const unsigned col = threadIdx.x & (kCols - 1);
     const uint8_t* B = reinterpret_cast<const uint8_t*>(A) + J.start;
     for (int q0 = 16 * (int)threadIdx.x; q0 < width; q0 += 4 * 16 * kTestThreads) {
       WalkBytes16 v[4];
@@ -885,12 +974,16 @@ __global__ __launch_bounds__(kTestThreads) void k_cand_prefix(const TD* __restri
       for (int k = 0; k < 4; ++k) {
         const int q = q0 + k * 16 * kTestThreads;
 #pragma unroll
-        for (int j = 0; j < 16; ++j) if (q + j < width) atomicAdd(&s_hist[(v[k].w[j >> 2] >> (8 * (j & 3))) & 0xffu], 1u);
+        for (int j = 0; j < 16; ++j) if (q + j < width) atomicAdd(&s_hist[((v[k].w[j >> 2] >> (8 * (j & 3))) & 0xffu) * kCols + col], 1u);
       }
     }
     __syncthreads();
     if (threadIdx.x < 256) {
-      const long long c = s_hist[threadIdx.x];
+      unsigned n = 0;   // row threadIdx.x, read from the thread's own column on: the lanes of a load stay on different banks
+#pragma unroll 8
+      for (unsigned j = 0; j < kCols; ++j) n += s_hist[threadIdx.x * kCols + ((j + threadIdx.x) & (kCols - 1))];
+      s_hist[kFold + threadIdx.x] = n;
+      const long long c = n;
       if (c) { lo = (int)threadIdx.x; hi = (int)threadIdx.x; s1 = c * (long long)threadIdx.x; s2 = c * (long long)threadIdx.x * (long long)threadIdx.x; }
     }
     lo = block_reduce(lo, [](int a, int b2) { return a < b2 ? a : b2; }, s_i2);
@@ -902,7 +995,7 @@ __global__ __launch_bounds__(kTestThreads) void k_cand_prefix(const TD* __restri
     if ((double)hi - (double)lo >= 1.0) {
       const unsigned nbk = (unsigned)(hi - lo) + 2;
       int qb[3];
-      hist_ranks(s_hist + lo, nbk, (size_t)width, s_scan, s_q, qb);
+      hist_ranks(s_hist + kFold + lo, nbk, (size_t)width, s_scan, s_q, qb);
       if (qb[0] >= 0) q0 = (double)lo + qb[0] * 1.0;
       if (qb[1] >= 0) q1 = (double)lo + qb[1] * 1.0;
       if (qb[2] >= 0) q2 = (double)lo + qb[2] * 1.0;
@@ -955,44 +1048,7 @@ __global__ __launch_bounds__(kTestThreads) void k_cand_prefix(const TD* __restri
   }
 }
 
-// launch 3: grid (kCandChunks, njobs) -- float window means of a chunk of windows, their extremes and moments
-__global__ __launch_bounds__(kTestThreads) void k_cand_means(const CandJob* __restrict__ jobs, int32_t* __restrict__ iscratch,
-                                                         long long* __restrict__ lscratch, CandMid* __restrict__ mid,
-                                                         int p32 /* the chunk-local prefixes are 32-bit (byte depth, k_cand_prefix) */,
-                                                         int vb /* bytes per stored neighbourhood value: where `ref` lies */) {
-  __shared__ long long s_off[kCandChunks];
-  __shared__ double s_d[kMaxWaves];
-  __shared__ float s_f[kMaxWaves];
-  const CandJob J = jobs[blockIdx.y];
-  CandMid& M = mid[blockIdx.y];
-  const CandGeom g = cand_geometry(J, M);
-  const CandBufs b = cand_buffers(J, iscratch, lscratch, vb);
-  if (g.nwin <= 0 || g.width <= 0) return;
-  if (threadIdx.x == 0) { long long o = 0; for (int c = 0; c < kCandChunks; ++c) { s_off[c] = o; o += M.totals[c]; } }
-  __syncthreads();
-  const int Lc = cand_chunk_len(g.nref);
-  const uint32_t* const P32 = reinterpret_cast<const uint32_t*>(b.P);
-  const bool use32 = p32 != 0 && Lc <= kCandP32MaxChunk;
-  auto P_at = [&](int x) -> long long { return x == 0 ? 0ll : s_off[(x - 1) / Lc] + (use32 ? (long long)P32[x] : b.P[x]); };
-  const int Wc = cand_chunk_len(g.nwin);
-  const int wb = blockIdx.x * Wc;
-  int we = wb + Wc; if (we > g.nwin) we = g.nwin;
-  float* Wm = reinterpret_cast<float*>(b.ref);
-  const double dw = (double)g.width;
-  float flo = 3.0e38f, fhi = -3.0e38f; double m1 = 0, m2 = 0;
-  for (int q = wb + (int)threadIdx.x; q < we; q += kTestThreads) {
-    const float w = (float)((double)(P_at(q + g.width) - P_at(q)) / dw);
-    Wm[q] = w;
-    flo = w < flo ? w : flo; fhi = w > fhi ? w : fhi; m1 += (double)w; m2 += (double)w * (double)w;
-  }
-  flo = block_reduce(flo, [](float a, float b2) { return a < b2 ? a : b2; }, s_f);
-  fhi = block_reduce(fhi, [](float a, float b2) { return a > b2 ? a : b2; }, s_f);
-  m1 = block_reduce(m1, [](double a, double b2) { return a + b2; }, s_d);
-  m2 = block_reduce(m2, [](double a, double b2) { return a + b2; }, s_d);
-  if (threadIdx.x == 0) { M.flo[blockIdx.x] = flo; M.fhi[blockIdx.x] = fhi; M.m1[blockIdx.x] = m1; M.m2[blockIdx.x] = m2; }
-}
-
-// launch 4: grid (kCandChunks, njobs) -- 0.01-grid histogram of the means; the last workgroup of a job walks it and
+// launch 3: grid (kCandChunks, njobs) -- 0.01-grid histogram of the means; the last workgroup of a job walks it and
 // writes the result.  ghist and the ticket are left zero.
 __global__ __launch_bounds__(kTestThreads) void k_cand_hist(const CandJob* __restrict__ jobs, int32_t* __restrict__ iscratch,
                                                         long long* __restrict__ lscratch, CandMid* __restrict__ mid,
@@ -1105,16 +1161,16 @@ void launch_sharpen_edges(DepthRef d, int64_t ncompact, EdgeJob* jobs, int njobs
 }
 namespace {
 template <typename TD, typename TS>
-void cand_launch_split(const TD* rdc, int depth_bytes, int64_t ncompact, const CandJob* jobs, int njobs, const int2* ch, int32_t* iscratch,
-                       long long* lscratch, double RDmedian, CandMid* mid, uint32_t* ghist, CandOut* outs, hipStream_t stream) {
+void cand_launch_split(const TD* rdc, int64_t ncompact, const CandJob* jobs, int njobs, const int2* ch, int32_t* iscratch,
+                       double RDmedian, CandMid* mid, uint32_t* ghist, CandOut* outs, hipStream_t stream) {
   const size_t lds = (size_t)kCandHistBins * 4;
   RSI_ALLOW_FULL_LDS((k_cand_gather<TD, TS>));
-  RSI_ALLOW_FULL_LDS((k_cand_prefix<TD, TS>));
+  RSI_ALLOW_FULL_LDS((k_cand_sums<TD, TS>));
   RSI_ALLOW_FULL_LDS(k_cand_hist);
   const int vb = (int)sizeof(TS);
+  long long* const lscratch = nullptr;   // no int64 scratch in this form
   RSI_LAUNCH((k_cand_gather<TD, TS>), dim3(2, njobs), dim3(kTestThreads), lds, stream, rdc, ncompact, jobs, ch, iscratch, lscratch, RDmedian, mid);
-  RSI_LAUNCH((k_cand_prefix<TD, TS>), dim3(kCandChunks + 1, njobs), dim3(kTestThreads), lds, stream, rdc, jobs, iscratch, lscratch, mid);
-  RSI_LAUNCH(k_cand_means, dim3(kCandChunks, njobs), dim3(kTestThreads), 0, stream, jobs, iscratch, lscratch, mid, depth_bytes == 1 ? 1 : 0, vb);
+  RSI_LAUNCH((k_cand_sums<TD, TS>), dim3(kCandChunks + 1, njobs), dim3(kTestThreads), lds, stream, rdc, jobs, iscratch, mid);
   RSI_LAUNCH(k_cand_hist, dim3(kCandChunks, njobs), dim3(kTestThreads), lds, stream, jobs, iscratch, lscratch, mid, ghist, outs, vb);
 }
 template <typename TD, typename TS>
@@ -1127,16 +1183,16 @@ void cand_launch_one_wg(const TD* rdc, int64_t ncompact, const CandJob* jobs, in
 }  // namespace
 // value_bytes: how the gathered values are stored, 1 (byte depth only) or 4; the caller sizes iscratch accordingly
 void launch_candidate_test_split(DepthRef d, int64_t ncompact, const CandJob* jobs, int njobs, const void* chains,
-                                 int32_t* iscratch, long long* lscratch, double RDmedian, CandMid* mid, uint32_t* ghist,
+                                 int32_t* iscratch, double RDmedian, CandMid* mid, uint32_t* ghist,
                                  CandOut* outs, int value_bytes, hipStream_t stream) {
   if (njobs <= 0) return;
   const int2* ch = static_cast<const int2*>(chains);
   if (d.bytes == 1 && value_bytes == 1)
-    cand_launch_split<uint8_t, uint8_t>(static_cast<const uint8_t*>(d.p), d.bytes, ncompact, jobs, njobs, ch, iscratch, lscratch, RDmedian, mid, ghist, outs, stream);
+    cand_launch_split<uint8_t, uint8_t>(static_cast<const uint8_t*>(d.p), ncompact, jobs, njobs, ch, iscratch, RDmedian, mid, ghist, outs, stream);
   else if (d.bytes == 1)
-    cand_launch_split<uint8_t, int32_t>(static_cast<const uint8_t*>(d.p), d.bytes, ncompact, jobs, njobs, ch, iscratch, lscratch, RDmedian, mid, ghist, outs, stream);
+    cand_launch_split<uint8_t, int32_t>(static_cast<const uint8_t*>(d.p), ncompact, jobs, njobs, ch, iscratch, RDmedian, mid, ghist, outs, stream);
   else
-    cand_launch_split<int32_t, int32_t>(static_cast<const int32_t*>(d.p), d.bytes, ncompact, jobs, njobs, ch, iscratch, lscratch, RDmedian, mid, ghist, outs, stream);
+    cand_launch_split<int32_t, int32_t>(static_cast<const int32_t*>(d.p), ncompact, jobs, njobs, ch, iscratch, RDmedian, mid, ghist, outs, stream);
 }
 size_t sharpen_workspace_bytes(int njobs) { return sharpen_zero_bytes(njobs) + (size_t)njobs * 2 * kEdgeChunks * (8 + 8 + 4); }
 size_t sharpen_workspace_zero_bytes(int njobs) { return sharpen_zero_bytes(njobs); }

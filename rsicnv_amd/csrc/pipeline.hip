@@ -252,7 +252,7 @@ class DeviceTester : public rsih::NeighbourTester {
     stats.assign(n, rsih::TestStats{});
     left_reach.assign(n, 0);
     okv.assign(n, 0);
-    // One workgroup per test (k_candidate_test) or the four-launch form that spreads a test over 17 workgroups.  A lone
+    // One workgroup per test (k_candidate_test) or the three-launch form that spreads a test over 17 workgroups.  A lone
     // chromosome gets its tests back 40 % sooner from the second; in a pool the first is better (35.3 against 38.1 ms per
     // genome): a few long-lived workgroups cost the per-base kernels of the other chromosomes next to nothing, hundreds of
     // full ones take their CUs.  RSI_HOT_CAND_SPLIT=0 / 1 overrides.
@@ -272,7 +272,7 @@ class DeviceTester : public rsih::NeighbourTester {
         if (T.capacity <= 0 || T.end < T.start || T.start < 0 || T.end >= N) break;   // left to the host path (ok stays 0)
         auto up4 = [](size_t x) { return (x + 3) & ~(size_t)3; };   // the kernel wants every piece on a 16-byte boundary
         const size_t ib = cand_scratch_bytes(T.top, T.capacity, T.budget, value_bytes, split);
-        const size_t lw = up4((size_t)T.capacity + 1);
+        const size_t lw = split ? 0 : up4((size_t)T.capacity + 1);   // the prefix array of the one-workgroup form
         if (!jobs.empty() && ibytes + ib + (lwords + lw) * 8 > kCandScratchBytes) break;
         CandJob J{};
         J.start = T.start; J.end = T.end; J.kind = T.kind; J.margin = T.margin; J.capacity = T.capacity; J.top = T.top;
@@ -293,7 +293,7 @@ class DeviceTester : public rsih::NeighbourTester {
         Phase ph(ctx, "cand.ensure");
         if (!ok(ctx->cand_jobs.ensure(jobs.size() * sizeof(CandJob))) || !ok(ctx->cand_chains.ensure(chains.size() * 4)) ||
             !ok(ctx->cand_outs.ensure(outs.size() * sizeof(CandOut))) || !ok(ctx->cand_i32.ensure(ibytes)) ||
-            !ok(ctx->cand_i64.ensure(lwords * 8)))
+            (!split && !ok(ctx->cand_i64.ensure(lwords * 8))))
           return false;
         if (split) {   // per-job records and folded histograms of the split form: zero when (re)allocated, left zero by every launch
           // (re)allocated = the capacity changed: the allocator may hand the freed address out again, with whatever lies behind
@@ -327,7 +327,7 @@ class DeviceTester : public rsih::NeighbourTester {
         Timer t(ctx, split ? (wide ? "candidate_test_i32" : "candidate_test") : (wide ? "candidate_test_one_wg_i32" : "candidate_test_one_wg"));
         if (split)
           launch_candidate_test_split(d_rdc, N, d_jobs, (int)jobs.size(), d_chains, ctx->cand_i32.as<int32_t>(),
-                                      ctx->cand_i64.as<long long>(), median, ctx->cand_mid.as<CandMid>(), ctx->cand_hist.as<uint32_t>(),
+                                      median, ctx->cand_mid.as<CandMid>(), ctx->cand_hist.as<uint32_t>(),
                                       d_outs, value_bytes, ctx->stream);
         else
           launch_candidate_test(d_rdc, N, d_jobs, (int)jobs.size(), d_chains, ctx->cand_i32.as<int32_t>(),

@@ -511,6 +511,24 @@ int rsi_hot_debug_level_sums(rsi_ctx* ctx, const float* T, const int32_t* status
  * detection pass listed, trimming walks that left the array, inexact-threshold flags, 0. */
 int rsi_hot_debug_scan(rsi_ctx* ctx, const float* T, const int32_t* medint, int64_t nb, double RDmedian, double tmedian, double tlamda,
                        int Lmax, int32_t* status, int32_t* info);
+/* Test hook: get_rsi_segments (rsi.cpp:1060-1117) over HOST arrays: T[nb], status[nb] and the marked runs as nruns (start, end)
+ * pairs -- sorted, disjoint, inside [0, nb); anything else is RSI_ERR_BAD_ARG -- through the function the scan calls behind its
+ * second pass: the runs' prefixes, the best (L, offset) per work item, the fold over the items, the type by the median of the
+ * status values covered.  pairs_per_item: (L, offset) pairs a work item takes; 0 = what a run chooses for this context.  A segment
+ * whose |score| is below tlamda / 2 is dropped as the scan drops it: with tlamda = 0 every run gives one segment.  seg_*: room for
+ * nruns entries.  info[8] = runs, work items, 1 / 0 for lists in the kernel arguments / behind pointers, 1 / 0 for the runs' status
+ * values through the mailbox / a copy of the array, runs longer than the LDS staging holds, segments kept, pairs per item, 0.
+ * Overwrites the bin arrays the rsi_hot_fetch_* calls read. */
+int rsi_hot_debug_segments(rsi_ctx* ctx, const float* T, const int32_t* status, int64_t nb, const int32_t* runs, int nruns, double tmedian,
+                           double tlamda, int64_t pairs_per_item, int32_t* seg_start, int32_t* seg_end, int32_t* seg_type, double* seg_score,
+                           int32_t* info);
+/* Test hook: optimize_with_derivative (rsi.cpp:889-944), called twice (rsi.cpp:1876-1877), for njobs candidates (start, end, type;
+ * updated in place) over the HOST array depth[n], which becomes the context's compacted depth as bytes (storage 1; a value outside
+ * 0 .. 255 is RSI_ERR_BAD_ARG) or as int32 (storage 4).  The candidate stages' own function with the context's own workspace, grown as
+ * a run grows it.  info[4] (may be NULL) = jobs the workspace was laid out for before, and after, 1 / 0 for the job list in the mailbox /
+ * copied, waits. */
+int rsi_hot_debug_sharpen(rsi_ctx* ctx, const int32_t* depth, int64_t n, int storage, int32_t* start, int32_t* end, const int32_t* type,
+                          int njobs, int32_t* info);
 /* Test hook: the 0.01-grid median and MAD (partition_stat_tp, wufunctions.cpp:364-424) of the HOST array x[nb], restricted to
  * mask[i] == 0 when mask != NULL, through the forms the scan's thresholds take:
  *   mode 0: the device chain of a (median, MAD) pair, the MAD centred on the chain's own median;

@@ -194,6 +194,12 @@ class Ref:
             L.ref_rsistatus.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_int32), C.c_int32, C.c_double, C.c_double, C.c_double,
                                         C.c_int32, C.POINTER(C.c_int32)]
             L.ref_rsistatus.restype = None
+        if hasattr(L, "ref_get_rsi_segments"):   # likewise
+            L.ref_get_rsi_segments.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_int32), C.c_int32, C.c_double, C.POINTER(C.c_int32),
+                                               C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int32]
+            L.ref_optimize_with_derivative.argtypes = [C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32,
+                                                       C.c_int32]
+            L.ref_optimize_with_derivative.restype = None
 
     def load(self, params, depth, fasta, chrom="chrS", log=None):
         d, dp = _i32(depth)
@@ -330,3 +336,28 @@ class Ref:
         self.lib.ref_rsistatus(t.ctypes.data_as(C.POINTER(C.c_float)), mp, t.size, float(RDmedian), float(tmedian), float(tlamda),
                                int(Lmax), out.ctypes.data_as(C.POINTER(C.c_int32)))
         return out
+
+    def get_rsi_segments(self, T, status, tmedian):
+        """The reference's get_rsi_segments (rsi.cpp:1060-1117) over the caller's bins and status: (start, end, type, score), one entry
+        per marked run but the last."""
+        if not hasattr(self.lib, "ref_get_rsi_segments"):
+            raise RuntimeError(f"{REF_SO} predates ref_get_rsi_segments: rebuild it with `make -f oracle/Makefile.ref`")
+        t = np.ascontiguousarray(T, dtype=np.float32)
+        st, sp = _i32(status)
+        cap = t.size
+        s, e, ty = (np.zeros(cap, dtype=np.int32) for _ in range(3))
+        sc = np.zeros(cap, dtype=np.float64)
+        ip = C.POINTER(C.c_int32)
+        k = self.lib.ref_get_rsi_segments(t.ctypes.data_as(C.POINTER(C.c_float)), sp, t.size, float(tmedian), s.ctypes.data_as(ip),
+                                          e.ctypes.data_as(ip), ty.ctypes.data_as(ip), sc.ctypes.data_as(C.POINTER(C.c_double)), cap)
+        return s[:k].copy(), e[:k].copy(), ty[:k].copy(), sc[:k].copy()
+
+    def optimize_with_derivative(self, rd, start, end, type_, calls=2):
+        """The reference's optimize_with_derivative (rsi.cpp:889-937), `calls` times, on one candidate: (start, end).  The caller keeps
+        end >= start through every call: the reference indexes its vector out of range otherwise."""
+        if not hasattr(self.lib, "ref_optimize_with_derivative"):
+            raise RuntimeError(f"{REF_SO} predates ref_optimize_with_derivative: rebuild it with `make -f oracle/Makefile.ref`")
+        d, dp = _i32(rd)
+        s, e = C.c_int32(int(start)), C.c_int32(int(end))
+        self.lib.ref_optimize_with_derivative(dp, d.size, C.byref(s), C.byref(e), int(type_), int(calls))
+        return s.value, e.value

@@ -53,6 +53,7 @@ void areblockscnv(Array<int>& RDmedint, Array<int>& RDtrans_status,
                   vector<cnv_st>& rsiseglist);                                     // rsi.cpp:415
 string cnv_format1(cnv_st& icnv);                                                  // rsi.cpp:581
 int expand_coordinate(int p1);                                                     // rsi.cpp:1524
+void optimize_with_derivative(Array<int>& RD, cnv_st& icnv);                       // rsi.cpp:889
 void plot_icnv(cnv_st icnv, string title, string datfile, string gpfile, string imgfile);   // plotcnv.cpp:246
 
 extern "C" {
@@ -450,6 +451,37 @@ void ref_rsistatus(const float* T, const int32_t* medint, int32_t nb, double RDm
   quiet_end();
   rsi::RDmedian = keep;
   for (int i = 0; i < nb; ++i) status[i] = st[i];
+}
+
+// get_rsi_segments alone (rsi.cpp:1060-1117) on the caller's bins and status: one segment per marked run but the last
+// (get_continuous_segments never emits it), start / end / type and the score as cnv_st stores it.  Returns the number of segments.
+int ref_get_rsi_segments(const float* T, const int32_t* status, int32_t nb, double tmedian, int32_t* start, int32_t* end, int32_t* type,
+                         double* score, int32_t cap) {
+  Array<float> t(nb, T);
+  Array<int> st(nb, 0);
+  for (int i = 0; i < nb; ++i) st[i] = status[i];
+  vector<cnv_st> segs;
+  quiet_begin();
+  get_rsi_segments(t, st, tmedian, segs);
+  quiet_end();
+  for (size_t i = 0; i < segs.size() && (int)i < cap; ++i) { start[i] = segs[i].start; end[i] = segs[i].end; type[i] = segs[i].type; score[i] = segs[i].score; }
+  return (int)segs.size();
+}
+
+// optimize_with_derivative (rsi.cpp:889-937) `calls` times on one candidate over the caller's array (detectcnv calls it twice,
+// rsi.cpp:1876-1877).  A candidate with end < start makes the reference index its vector out of range: the caller sends none
+// (tests/sharpen_cases.py proves it for every case before it comes here).
+void ref_optimize_with_derivative(const int32_t* rd, int32_t n, int32_t* start, int32_t* end, int32_t type, int32_t calls) {
+  static Array<int> RD(1);
+  RD.resize(0);
+  RD.resize(n);
+  for (int k = 0; k < n; ++k) RD[k] = rd[k];
+  cnv_st c;
+  c.start = *start; c.end = *end; c.type = type;
+  quiet_begin();
+  for (int k = 0; k < calls; ++k) optimize_with_derivative(RD, c);
+  quiet_end();
+  *start = c.start; *end = c.end;
 }
 
 // Direct probes of the numeric utilities (used to pin the oracle's restatements).

@@ -55,7 +55,7 @@ EXPORTS = ["rsi_default_params", "rsi_hot_create", "rsi_hot_destroy", "rsi_hot_l
            "rsi_hot_run_device", "rsi_hot_load_depth_text", "rsi_hot_run_text", "rsi_hot_load_depth_bam", "rsi_hot_run_bam", "rsi_bam_references", "rsi_result_annotate_bam", "rsi_result_summary", "rsi_summary_format_row", "rsi_summary_format_rows", "rsi_result_pairs", "rsi_result_ncalls", "rsi_result_calls", "rsi_result_stats", "rsi_result_noncode",
            "rsi_result_format_row", "rsi_result_free", "rsi_hot_fetch_i32", "rsi_hot_fetch_f32", "rsi_hot_fetch_i64",
            "rsi_hot_kernel_times", "rsi_hot_phase_times", "rsi_hot_set_timing", "rsi_hot_process_setup", "rsi_pool_create", "rsi_pool_destroy", "rsi_pool_workers", "rsi_pool_hw_queues", "rsi_pool_worker",
-           "rsi_pool_set_timing", "rsi_pool_set_timing_kernel", "rsi_hot_set_timing_kernel", "rsi_pool_set_schedule", "rsi_pool_last_error", "rsi_pool_run", "rsi_pool_run_host", "rsi_pool_submit", "rsi_pool_wait", "rsi_plot_expand", "rsi_plot_write_files", "rsi_result_log_line", "rsi_hot_debug_level_sums", "rsi_hot_debug_scan", "rsi_hot_debug_grid_median", "rsi_hot_debug_grid_mad_i32", "rsi_synth_generate_host", "rsi_synth_generate_device", "rsi_synth_write_depth_text", "rsi_synth_write_fasta", "rsi_synth_append_genome_text",
+           "rsi_pool_set_timing", "rsi_pool_set_timing_kernel", "rsi_hot_set_timing_kernel", "rsi_pool_set_schedule", "rsi_pool_last_error", "rsi_pool_run", "rsi_pool_run_host", "rsi_pool_submit", "rsi_pool_wait", "rsi_plot_expand", "rsi_plot_write_files", "rsi_result_log_line", "rsi_hot_debug_level_sums", "rsi_hot_debug_scan", "rsi_hot_debug_segments", "rsi_hot_debug_sharpen", "rsi_hot_debug_grid_median", "rsi_hot_debug_grid_mad_i32", "rsi_synth_generate_host", "rsi_synth_generate_device", "rsi_synth_write_depth_text", "rsi_synth_write_fasta", "rsi_synth_append_genome_text",
            "rsi_genome_text_open", "rsi_genome_text_next", "rsi_genome_text_release", "rsi_genome_text_copy_depth",
            "rsi_genome_text_kernel_ms", "rsi_genome_text_close", "rsi_genome_text_last_error", "rsi_hot_run_depth_device",
            "rsi_hot_last_inflate_stats", "rsi_hot_inflate_bgzf", "rsi_genome_text_inflate_stats",
@@ -614,6 +614,38 @@ class RsiHot:
         self._check(self.lib.rsi_hot_debug_scan(self.ctx, t.ctypes.data, mi.ctypes.data, t.size, float(RDmedian), float(tmedian), float(tlamda),
                                                 int(Lmax), st.ctypes.data, info.ctypes.data))
         return st, info
+
+    def debug_segments(self, T, status, runs, tmedian, tlamda=0.0, pairs_per_item=0):
+        """get_rsi_segments over host arrays on the device (test hook): runs = (start, end) pairs.  Returns (start, end, type, score, info);
+        info = runs, work items, lists inline, status through the mailbox, runs beyond the LDS staging, segments, pairs per item, 0."""
+        t = np.ascontiguousarray(T, dtype=np.float32)
+        st = np.ascontiguousarray(status, dtype=np.int32)
+        assert st.size == t.size
+        rl = np.ascontiguousarray(runs, dtype=np.int32).reshape(-1, 2)
+        k = rl.shape[0]
+        s, e, ty = (np.zeros(max(k, 1), dtype=np.int32) for _ in range(3))
+        sc = np.zeros(max(k, 1), dtype=np.float64)
+        info = np.zeros(8, dtype=np.int32)
+        self.lib.rsi_hot_debug_segments.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_double, C.c_double,
+                                                    C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._check(self.lib.rsi_hot_debug_segments(self.ctx, t.ctypes.data, st.ctypes.data, t.size, rl.ctypes.data, k, float(tmedian), float(tlamda),
+                                                    int(pairs_per_item), s.ctypes.data, e.ctypes.data, ty.ctypes.data, sc.ctypes.data, info.ctypes.data))
+        n = int(info[5])
+        return s[:n], e[:n], ty[:n], sc[:n], info
+
+    def debug_sharpen(self, depth, storage, start, end, type_):
+        """optimize_with_derivative, both calls, for a list of candidates over a host array on the device (test hook): storage 1 keeps the
+        array as bytes, 4 as int32.  Returns (start, end, info); info = workspace jobs before, after, job list in the mailbox, waits."""
+        d = np.ascontiguousarray(depth, dtype=np.int32)
+        s = np.array(start, dtype=np.int32).reshape(-1)
+        e = np.array(end, dtype=np.int32).reshape(-1)
+        ty = np.ascontiguousarray(type_, dtype=np.int32).reshape(-1)
+        assert s.size == e.size == ty.size
+        info = np.zeros(4, dtype=np.int32)
+        self.lib.rsi_hot_debug_sharpen.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        self._check(self.lib.rsi_hot_debug_sharpen(self.ctx, d.ctypes.data, d.size, int(storage), s.ctypes.data, e.ctypes.data, ty.ctypes.data, s.size,
+                                                   info.ctypes.data))
+        return s, e, info
 
     GRID_MODES = {"pair": 0, "mad": 1, "host": 2}
 

@@ -353,6 +353,7 @@ struct BestSeg { double score; int32_t start; int32_t len; };
 struct SegItem { int32_t run; int32_t len; int32_t Lbeg; int32_t Lend; };   // lengths [Lbeg, Lend) of one run
 // Short run / item lists ride in the kernel arguments (the pointer forms are for longer ones).
 constexpr int kRunsInline = 200, kItemsInline = 150;
+constexpr int kBestLds = 6144;   // doubles of a run's prefix k_best_subsegment stages in LDS (48 KB); a longer prefix is read from global memory
 struct RunsInline { int32_t se[2 * kRunsInline]; int32_t off[kRunsInline]; };     // (start, end) pairs; prefix offsets
 struct ItemsInline { SegItem it[kItemsInline]; int32_t off[kRunsInline]; };
 // exact double prefix of every run into scratch + poff[run] (len+1 entries), one workgroup per run

@@ -1277,7 +1277,6 @@ __device__ inline bool seg_better(double s, int L, int j, double bs, int bL, int
   return j < bj;
 }
 
-constexpr int kBestLds = 6144;   // doubles of a run's prefix staged in LDS (48 KB)
 __global__ __launch_bounds__(kThreads) void k_best_subsegment(const SegItem* __restrict__ items,
                                                               const int64_t* __restrict__ poff,
                                                               const double* __restrict__ scratch, double tmedian,

@@ -468,6 +468,89 @@ int scan_pass(rsi_ctx* ctx, int pass, const float* d_T, const int32_t* d_medint,
   return RSI_OK;
 }
 
+// get_rsi_segments (rsi.cpp:1060-1117) over the marked runs of d_st2: each run's exact prefix (k_run_prefix), the best (L, offset)
+// of every work item (k_best_subsegment), the fold over a run's items and the type on the host (segments_from_best).  The stream
+// is idle when it is called.  pairs_per_item 0: what a run chooses (segment_pairs_per_item).  form: the road taken, for
+// rsi_hot_debug_segments.
+struct SegForm { int runs = 0, items = 0, inl = 0, mailbox_status = 0, unstaged = 0; int64_t pairs_per_item = 0; };
+int rsi_segments(rsi_ctx* ctx, const float* d_T, const int32_t* d_st2, int64_t nb, const std::vector<Region>& runs, double tmedian,
+                 double tlamda, int64_t pairs_per_item, ScanOut& out, SegForm* form) {
+  int rc;
+  out.status2 = rsih::IntSpan();
+  out.segs.clear();
+  if (runs.empty()) return RSI_OK;
+  std::vector<int64_t> poff;
+  std::vector<SegItem> items;
+  // About 256 (L, offset) pairs per thread of a workgroup in a pool that shares the chip (a long, thin kernel there costs the
+  // other chromosomes next to nothing).  A chromosome that has the chip to itself (a stand-alone context, a pool run over a
+  // few chromosomes) waits for exactly this kernel: as many items as still ride in the kernel arguments (kItemsInline), down
+  // to 32 pairs per thread -- a 60 Mb chromosome's 2 M pairs then spread over ~130 workgroups instead of ~35.
+  if (pairs_per_item <= 0) pairs_per_item = rsih::segment_pairs_per_item(runs, !ctx->gate || ctx->gate->lonely());
+  rsih::segment_items(runs, pairs_per_item, poff, items);
+  HIPCHK(ctx->scratch.ensure((size_t)poff.back() * 8 + (runs.size() + 1) * 8));
+  double* d_scratch = ctx->scratch.as<double>();
+  // short lists ride in the kernel arguments and the per-item results land in the pinned mailbox: two launches, no copy
+  const bool inl = runs.size() <= (size_t)kRunsInline && items.size() <= (size_t)kItemsInline && poff.back() < (int64_t)1 << 31;
+  std::vector<BestSeg> best(items.size());
+  if (inl) {
+    RunArgs ra;
+    if ((rc = prepare_runs(ctx, runs, ra)) != RSI_OK) return rc;
+    ItemsInline ii;
+    memset(&ii, 0, sizeof(ii));
+    for (size_t r = 0; r < runs.size(); ++r) { ra.inl.off[r] = (int32_t)poff[r]; ii.off[r] = (int32_t)poff[r]; }
+    for (size_t i = 0; i < items.size(); ++i) ii.it[i] = items[i];
+    BestSeg* slot = static_cast<BestSeg*>(mb_alloc(ctx, items.size() * sizeof(BestSeg)));
+    if (!slot) return fail(ctx, RSI_ERR_INTERNAL, "out of pinned mailbox memory");
+    // The host reads the status array inside the runs only (a segment's type, the nested levels of the block tests): the
+    // prefix kernel writes those values, run after run, into the mailbox -- 2 % of the array instead of a copy of all of it.
+    const size_t run_bins = (size_t)(poff.back() - (int64_t)runs.size());
+    int32_t* sslot = run_bins * 4 <= kMailboxMaxCopy ? static_cast<int32_t*>(mb_alloc(ctx, std::max<size_t>(run_bins, 1) * 4)) : nullptr;
+    if (!sslot) {
+      HIPCHK(ctx->h_status2.ensure((size_t)nb * 4));
+      HIPCHK(hipMemcpyAsync(ctx->h_status2.p, d_st2, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    { Timer t(ctx, "run_prefix"); launch_run_prefix(d_T, nullptr, nullptr, &ra.inl, (int)runs.size(), nullptr, d_scratch, d_st2, sslot, ctx->stream); }
+    { Timer t(ctx, "best_subsegment"); launch_best_items(nullptr, &ii, (int)items.size(), nullptr, d_scratch, tmedian, slot, ctx->stream); }
+    HIPCHK(CTX_SYNC());
+    memcpy(best.data(), slot, items.size() * sizeof(BestSeg));
+    if (sslot) {
+      out.run_status.assign(sslot, sslot + run_bins);
+      out.run_ranges.clear();
+      for (size_t r = 0; r < runs.size(); ++r) out.run_ranges.push_back({runs[r].start, runs[r].end, poff[r] - (int64_t)r});
+      out.status2 = rsih::IntSpan(out.run_status.data(), nb, &out.run_ranges);
+    } else {
+      out.status2 = rsih::IntSpan(ctx->h_status2.as<int>(), nb);
+    }
+  } else {
+    RunArgs ra;
+    const size_t kr = runs.size();
+    HIPCHK(ctx->run_se.ensure(kr * 8 + 64));
+    std::vector<int32_t> se(2 * kr);
+    for (size_t i = 0; i < kr; ++i) { se[i] = runs[i].start; se[kr + i] = runs[i].end; }
+    HIPCHK(copy_h2d(ctx, ctx->run_se.p, se.data(), kr * 8));
+    int64_t* d_poff = reinterpret_cast<int64_t*>(d_scratch + poff.back());
+    HIPCHK(ctx->items.ensure(items.size() * sizeof(SegItem)));
+    HIPCHK(ctx->best.ensure(items.size() * sizeof(BestSeg)));
+    HIPCHK(copy_h2d(ctx, d_poff, poff.data(), poff.size() * 8));
+    HIPCHK(copy_h2d(ctx, ctx->items.p, items.data(), items.size() * sizeof(SegItem)));
+    HIPCHK(ctx->h_status2.ensure((size_t)nb * 4));
+    HIPCHK(hipMemcpyAsync(ctx->h_status2.p, d_st2, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
+    out.status2 = rsih::IntSpan(ctx->h_status2.as<int>(), nb);   // complete at the sync below
+    { Timer t(ctx, "run_prefix"); launch_run_prefix(d_T, ctx->run_se.as<int32_t>(), ctx->run_se.as<int32_t>() + kr, nullptr, (int)kr, d_poff, d_scratch, nullptr, nullptr, ctx->stream); }
+    { Timer t(ctx, "best_subsegment"); launch_best_items(ctx->items.p, nullptr, (int)items.size(), d_poff, d_scratch, tmedian, ctx->best.as<BestSeg>(), ctx->stream); }
+    HIPCHK(copy_d2h(ctx, best.data(), ctx->best.p, items.size() * sizeof(BestSeg)));
+    HIPCHK(CTX_SYNC());
+  }
+  if (form) {
+    form->runs = (int)runs.size(); form->items = (int)items.size(); form->inl = inl ? 1 : 0;
+    form->mailbox_status = out.status2.ranges ? 1 : 0;
+    form->pairs_per_item = pairs_per_item;
+    for (const Region& r : runs) if (r.end - r.start + 2 > kBestLds) ++form->unstaged;
+  }
+  rsih::segments_from_best(runs, items, best.data(), out.status2, tlamda, out.segs);
+  return RSI_OK;
+}
+
 // rsicnvnbn (rsi.cpp:1262-1360) / rsicnvmed (rsi.cpp:1402-1501) around the device scan.  `first` = the record the quantile
 // chain in front of the first pass leaves in the mailbox (issued by the caller, behind the transform).
 int run_scan(rsi_ctx* ctx, const rsi_params& P, bool use_med, const float* d_T, int64_t nb, double RDmedian,
@@ -620,79 +703,7 @@ int run_scan(rsi_ctx* ctx, const rsi_params& P, bool use_med, const float* d_T, 
   std::vector<Region> runs;
   if ((rc = runs_from_export(ctx, rslot, ctx->runs.as<uint64_t>(), runs)) != RSI_OK) return rc;
   if ((rc = take_record(wslot, 1)) != RSI_OK) return rc;
-  out.status2 = rsih::IntSpan();
-  out.segs.clear();
-  if (runs.empty()) return RSI_OK;
-  std::vector<int64_t> poff;
-  std::vector<SegItem> items;
-  // About 256 (L, offset) pairs per thread of a workgroup in a pool that shares the chip (a long, thin kernel there costs the
-  // other chromosomes next to nothing).  A chromosome that has the chip to itself (a stand-alone context, a pool run over a
-  // few chromosomes) waits for exactly this kernel: as many items as still ride in the kernel arguments (kItemsInline), down
-  // to 32 pairs per thread -- a 60 Mb chromosome's 2 M pairs then spread over ~130 workgroups instead of ~35.
-  int64_t pairs_per_item = 1 << 16;
-  if (!ctx->gate || ctx->gate->lonely()) {
-    int64_t total = 0;
-    for (const Region& r : runs) { const int64_t len = r.end - r.start + 1; total += len * (len + 1) / 2; }
-    const int64_t room = std::max<int64_t>(8, (int64_t)kItemsInline - 2 * (int64_t)runs.size());   // every run's last item is a partial one
-    pairs_per_item = std::min<int64_t>(pairs_per_item, std::max<int64_t>(1 << 13, total / room + 1));
-  }
-  rsih::segment_items(runs, pairs_per_item, poff, items);
-  HIPCHK(ctx->scratch.ensure((size_t)poff.back() * 8 + (runs.size() + 1) * 8));
-  double* d_scratch = ctx->scratch.as<double>();
-  // short lists ride in the kernel arguments and the per-item results land in the pinned mailbox: two launches, no copy
-  const bool inl = runs.size() <= (size_t)kRunsInline && items.size() <= (size_t)kItemsInline && poff.back() < (int64_t)1 << 31;
-  std::vector<BestSeg> best(items.size());
-  if (inl) {
-    RunArgs ra;
-    if ((rc = prepare_runs(ctx, runs, ra)) != RSI_OK) return rc;
-    ItemsInline ii;
-    memset(&ii, 0, sizeof(ii));
-    for (size_t r = 0; r < runs.size(); ++r) { ra.inl.off[r] = (int32_t)poff[r]; ii.off[r] = (int32_t)poff[r]; }
-    for (size_t i = 0; i < items.size(); ++i) ii.it[i] = items[i];
-    BestSeg* slot = static_cast<BestSeg*>(mb_alloc(ctx, items.size() * sizeof(BestSeg)));
-    if (!slot) return fail(ctx, RSI_ERR_INTERNAL, "out of pinned mailbox memory");
-    // The host reads the status array inside the runs only (a segment's type, the nested levels of the block tests): the
-    // prefix kernel writes those values, run after run, into the mailbox -- 2 % of the array instead of a copy of all of it.
-    const size_t run_bins = (size_t)(poff.back() - (int64_t)runs.size());
-    int32_t* sslot = run_bins * 4 <= kMailboxMaxCopy ? static_cast<int32_t*>(mb_alloc(ctx, std::max<size_t>(run_bins, 1) * 4)) : nullptr;
-    if (!sslot) {
-      HIPCHK(ctx->h_status2.ensure((size_t)nb * 4));
-      HIPCHK(hipMemcpyAsync(ctx->h_status2.p, d_st2, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    { Timer t(ctx, "run_prefix"); launch_run_prefix(d_T, nullptr, nullptr, &ra.inl, (int)runs.size(), nullptr, d_scratch, d_st2, sslot, ctx->stream); }
-    { Timer t(ctx, "best_subsegment"); launch_best_items(nullptr, &ii, (int)items.size(), nullptr, d_scratch, tmedian, slot, ctx->stream); }
-    HIPCHK(CTX_SYNC());
-    memcpy(best.data(), slot, items.size() * sizeof(BestSeg));
-    if (sslot) {
-      out.run_status.assign(sslot, sslot + run_bins);
-      out.run_ranges.clear();
-      for (size_t r = 0; r < runs.size(); ++r) out.run_ranges.push_back({runs[r].start, runs[r].end, poff[r] - (int64_t)r});
-      out.status2 = rsih::IntSpan(out.run_status.data(), nb, &out.run_ranges);
-    } else {
-      out.status2 = rsih::IntSpan(ctx->h_status2.as<int>(), nb);
-    }
-  } else {
-    RunArgs ra;
-    const size_t kr = runs.size();
-    HIPCHK(ctx->run_se.ensure(kr * 8 + 64));
-    std::vector<int32_t> se(2 * kr);
-    for (size_t i = 0; i < kr; ++i) { se[i] = runs[i].start; se[kr + i] = runs[i].end; }
-    HIPCHK(copy_h2d(ctx, ctx->run_se.p, se.data(), kr * 8));
-    int64_t* d_poff = reinterpret_cast<int64_t*>(d_scratch + poff.back());
-    HIPCHK(ctx->items.ensure(items.size() * sizeof(SegItem)));
-    HIPCHK(ctx->best.ensure(items.size() * sizeof(BestSeg)));
-    HIPCHK(copy_h2d(ctx, d_poff, poff.data(), poff.size() * 8));
-    HIPCHK(copy_h2d(ctx, ctx->items.p, items.data(), items.size() * sizeof(SegItem)));
-    HIPCHK(ctx->h_status2.ensure((size_t)nb * 4));
-    HIPCHK(hipMemcpyAsync(ctx->h_status2.p, d_st2, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
-    out.status2 = rsih::IntSpan(ctx->h_status2.as<int>(), nb);   // complete at the sync below
-    { Timer t(ctx, "run_prefix"); launch_run_prefix(d_T, ctx->run_se.as<int32_t>(), ctx->run_se.as<int32_t>() + kr, nullptr, (int)kr, d_poff, d_scratch, nullptr, nullptr, ctx->stream); }
-    { Timer t(ctx, "best_subsegment"); launch_best_items(ctx->items.p, nullptr, (int)items.size(), d_poff, d_scratch, tmedian, ctx->best.as<BestSeg>(), ctx->stream); }
-    HIPCHK(copy_d2h(ctx, best.data(), ctx->best.p, items.size() * sizeof(BestSeg)));
-    HIPCHK(CTX_SYNC());
-  }
-  rsih::segments_from_best(runs, items, best.data(), out.status2, tlamda, out.segs);
-  return RSI_OK;
+  return rsi_segments(ctx, d_T, d_st2, nb, runs, tmedian, tlamda, 0, out, nullptr);
 }
 
 void to_call(const Candidate& c, rsi_call* o) {
@@ -1819,6 +1830,91 @@ int rsi_hot_debug_scan(rsi_ctx* ctx, const float* T, const int32_t* medint, int6
   HIPCHK(CTX_SYNC());
   const rsih::ScanRecord rec{wslot, Lmax};
   if (info) { info[0] = (int32_t)rec.tiles_listed(); info[1] = (int32_t)rec.escapes(); info[2] = (int32_t)rec.inexact(); info[3] = 0; }
+  return RSI_OK;
+}
+
+// Test hook: get_rsi_segments over host arrays (include/rsi_hot.h).  The arrays are uploaded into the buffers a run keeps them in and
+// rsi_segments -- what run_scan calls behind its second pass -- does the rest.
+int rsi_hot_debug_segments(rsi_ctx* ctx, const float* T, const int32_t* status, int64_t nb, const int32_t* runs, int nruns, double tmedian,
+                           double tlamda, int64_t pairs_per_item, int32_t* seg_start, int32_t* seg_end, int32_t* seg_type, double* seg_score,
+                           int32_t* info) {
+  if (!ctx || !T || !status || !info || nb <= 0 || nb >= (1ll << 31) - 4096 || nruns < 0 || (nruns > 0 && (!runs || !seg_start || !seg_end || !seg_type || !seg_score)) ||
+      pairs_per_item < 0)
+    return fail(ctx, RSI_ERR_BAD_ARG, "bad argument");
+  std::vector<Region> rl((size_t)nruns);
+  for (int r = 0; r < nruns; ++r) {
+    rl[(size_t)r] = Region{runs[2 * r], runs[2 * r + 1]};
+    const Region& g = rl[(size_t)r];
+    if (g.start < 0 || g.end < g.start || (int64_t)g.end >= nb || (r > 0 && g.start <= rl[(size_t)r - 1].end))
+      return fail(ctx, RSI_ERR_BAD_ARG, "runs must be sorted, disjoint and inside [0, nb)");
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!ctx_enter(ctx)) return RSI_ERR_HIP;
+  mailbox_reset(ctx);
+  ctx->ktimes.clear(); ctx->event_next = 0; ctx->phases.clear();
+  ctx->nb = nb; ctx->run_m = 0;
+  ctx->have_nb = false;   // tnb holds the caller's array now
+  HIPCHK(ctx->tnb.ensure((size_t)nb * 4));
+  HIPCHK(ctx->status2.ensure((size_t)nb * 4));
+  HIPCHK(hipMemcpyAsync(ctx->tnb.p, T, (size_t)nb * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(ctx->status2.p, status, (size_t)nb * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(CTX_SYNC());
+  ScanOut out;
+  SegForm form;
+  int rc;
+  {
+    GateShared gs(ctx);
+    if ((rc = rsi_segments(ctx, ctx->tnb.as<float>(), ctx->status2.as<int32_t>(), nb, rl, tmedian, tlamda, pairs_per_item, out, &form)) != RSI_OK) return rc;
+  }
+  for (size_t i = 0; i < out.segs.size(); ++i) {
+    seg_start[i] = out.segs[i].start; seg_end[i] = out.segs[i].end; seg_type[i] = out.segs[i].type; seg_score[i] = out.segs[i].score;
+  }
+  info[0] = form.runs; info[1] = form.items; info[2] = form.inl; info[3] = form.mailbox_status; info[4] = form.unstaged;
+  info[5] = (int32_t)out.segs.size(); info[6] = (int32_t)std::min<int64_t>(form.pairs_per_item, 0x7fffffff); info[7] = 0;
+  return RSI_OK;
+}
+
+// Test hook: optimize_with_derivative, both calls, over a host array (include/rsi_hot.h): the array becomes the context's
+// compacted depth, as bytes or as int32, and DeviceTester::sharpen -- what the candidate stages call -- does the rest, with the
+// context's own workspace.
+int rsi_hot_debug_sharpen(rsi_ctx* ctx, const int32_t* depth, int64_t n, int storage, int32_t* start, int32_t* end, const int32_t* type,
+                          int njobs, int32_t* info) {
+  if (!ctx || !depth || n <= 0 || n >= (1ll << 31) - 4096 || (storage != 1 && storage != 4) || njobs < 0 || (njobs > 0 && (!start || !end || !type)))
+    return fail(ctx, RSI_ERR_BAD_ARG, "bad argument");
+  std::vector<uint8_t> bytes;
+  if (storage == 1) {
+    bytes.resize((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+      if (depth[i] < 0 || depth[i] > 255) return fail(ctx, RSI_ERR_BAD_ARG, "byte storage holds depths of 0 .. 255");
+      bytes[(size_t)i] = (uint8_t)depth[i];
+    }
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!ctx_enter(ctx)) return RSI_ERR_HIP;
+  mailbox_reset(ctx);
+  ctx->ktimes.clear(); ctx->event_next = 0; ctx->phases.clear();
+  ctx->run_m = 0; ctx->ncompact = n;
+  DepthRef ref;
+  if (storage == 1) {
+    HIPCHK(ctx->rdc8.ensure((size_t)n + 64));
+    HIPCHK(hipMemcpyAsync(ctx->rdc8.p, bytes.data(), (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    ctx->rdc_is_bytes = true; ctx->rdc_valid = false;
+    ref = DepthRef{ctx->rdc8.p, 1};
+  } else {
+    HIPCHK(ctx->rdc.ensure((size_t)(n + 4) * 4));
+    HIPCHK(hipMemcpyAsync(ctx->rdc.p, depth, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    ctx->rdc_is_bytes = false; ctx->rdc_valid = false;
+    ref = DepthRef{ctx->rdc.p, 4};
+  }
+  HIPCHK(CTX_SYNC());
+  std::vector<Candidate> L((size_t)njobs);
+  for (int i = 0; i < njobs; ++i) { L[(size_t)i].start = start[i]; L[(size_t)i].end = end[i]; L[(size_t)i].type = type[i]; }
+  const int ws_before = ctx->sharpen_ws_jobs;
+  const size_t mb_before = ctx->mb_used;
+  DeviceTester tester(ctx, ref, n, 0.0);
+  if (!tester.sharpen(L)) return tester.failed ? RSI_ERR_HIP : fail(ctx, RSI_ERR_INTERNAL, "the edge refinement declined the list");
+  for (int i = 0; i < njobs; ++i) { start[i] = L[(size_t)i].start; end[i] = L[(size_t)i].end; }
+  if (info) { info[0] = ws_before; info[1] = ctx->sharpen_ws_jobs; info[2] = ctx->mb_used > mb_before ? 1 : 0; info[3] = tester.launches; }
   return RSI_OK;
 }
 

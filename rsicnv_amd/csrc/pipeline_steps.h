@@ -270,6 +270,19 @@ inline LevelChoice choose_levels(const std::vector<float>& wsum, const std::vect
 // ---- get_rsi_segments (rsi.cpp:1060-1117) around the device's best-subsegment kernel -------------------------------------------
 // The work items: each run's lengths in chunks with about pairs_per_item (L, offset) pairs; poff[r]: where run r's prefix
 // (len + 1 entries) starts in the scratch.
+// pairs_per_item as a run chooses it.  About 256 pairs per thread of a workgroup (65 536 an item) where a dozen chromosomes share
+// the chip; a chromosome that has it to itself (lonely) waits for exactly this kernel and spreads its pairs over as many items as
+// still ride in the kernel arguments (kItemsInline; every run's last item is a partial one), down to 32 pairs per thread.
+inline int64_t segment_pairs_per_item(const std::vector<Region>& runs, bool lonely) {
+  int64_t pairs_per_item = 1 << 16;
+  if (lonely) {
+    int64_t total = 0;
+    for (const Region& r : runs) { const int64_t len = r.end - r.start + 1; total += len * (len + 1) / 2; }
+    const int64_t room = std::max<int64_t>(8, (int64_t)rsik::kItemsInline - 2 * (int64_t)runs.size());
+    pairs_per_item = std::min<int64_t>(pairs_per_item, std::max<int64_t>(1 << 13, total / room + 1));
+  }
+  return pairs_per_item;
+}
 inline void segment_items(const std::vector<Region>& runs, int64_t pairs_per_item, std::vector<int64_t>& poff, std::vector<rsik::SegItem>& items) {
   poff.assign(runs.size() + 1, 0);
   items.clear();

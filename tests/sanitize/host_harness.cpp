@@ -387,6 +387,17 @@ static void pipeline_step_edges() {
     const rsih::Lamda l = rsih::lamda_from_mad(2.0, 6.6, 30.0 * sqrt(2.0));
     CHECK(s.tlamda == l.tlamda && s.tsigma == l.tsigma && l.tlamda == 30.0 * sqrt(2.0), "the second pass' update is the first pass' rule");
   }
+  {   // pairs per work item of the segment search, by hand: len (len + 1) / 2 pairs a run, 150 - 2 runs items of room (8 at least)
+    auto one = [](int s, int e) { return std::vector<Region>{Region{s, e}}; };
+    CHECK(rsih::segment_pairs_per_item(one(0, 99), false) == 65536 && rsih::segment_pairs_per_item(one(0, 8191), false) == 65536, "a shared chip: 65 536 pairs");
+    CHECK(rsih::segment_pairs_per_item(one(0, 99), true) == 8192, "5050 pairs over 148 items: the floor of 8192");
+    CHECK(rsih::segment_pairs_per_item(one(10, 2009), true) == 13521, "2 001 000 pairs over 148 items: 13 520 and a fraction, + 1");
+    CHECK(rsih::segment_pairs_per_item(one(0, 8191), true) == 65536, "33 558 528 pairs over 148 items: the ceiling of 65 536");
+    std::vector<Region> many;
+    for (int k = 0; k < 80; ++k) many.push_back(Region{100 * k, 100 * k + 39});
+    CHECK(rsih::segment_pairs_per_item(many, true) == 8201, "80 runs of 40 bins: 65 600 pairs over the 8 items of room left, + 1");
+    CHECK(rsih::segment_pairs_per_item(std::vector<Region>(), true) == 8192, "no runs");
+  }
   {   // scan record: 100 bins, the 20 % rule by one bin
     const int Lmax = 4, stride = rsik::scan_level_stride(Lmax);
     std::vector<uint32_t> w((size_t)(rsik::kScanRecLevels + 2 * stride), 0u);

@@ -23,6 +23,8 @@ def test_every_declared_symbol_is_exported(hotlib):
     assert not missing, f"librsi_hot.so lacks: {missing}"
     assert set(api.EXPORTS) <= set(names)
     assert "rsi_hot_debug_per_base" in names and "rsi_hot_debug_per_base" in api.EXPORTS
+    for hook in ("rsi_hot_debug_segments", "rsi_hot_debug_sharpen"):
+        assert hook in names and hook in api.EXPORTS
 
 
 def test_struct_layouts_match_header(hotlib):

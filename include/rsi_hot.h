@@ -529,6 +529,26 @@ int rsi_hot_debug_segments(rsi_ctx* ctx, const float* T, const int32_t* status, 
  * copied, waits. */
 int rsi_hot_debug_sharpen(rsi_ctx* ctx, const int32_t* depth, int64_t n, int storage, int32_t* start, int32_t* end, const int32_t* type,
                           int njobs, int32_t* info);
+/* Test hook: the NB transform (negative_binomial_transfer, rsi.cpp:1145-1185) of the HOST bin sums binsum[nb] through the function a
+ * run calls: the formula and the raw minimum (raw[nb]: the array between the two launches), then the subtraction, the scaling and
+ * the three overwritten bins (T[nb]).  nb >= 3 (the reference writes bins 0..2) and nb == ncompact / m (the reference's bin count),
+ * r > 0; anything else is RSI_ERR_BAD_ARG.  info[8] = the raw minimum as float bits; flags, bucket count and minimum (float bits)
+ * of the plan the scale kernel leaves for the first quantile grid (flags: 2 = a non-finite value, 4 = range below 0.01, 8 = too wide
+ * for the resident buckets; buckets = (max - min) / 0.01 + 2); the min/max record's words or-ed together, as the kernel leaves them
+ * for the next user (0); the scaled levels t0, t2 (float bits) as the scan derives them from the raw minimum; 0.
+ * Overwrites the bin arrays the rsi_hot_fetch_* calls read. */
+int rsi_hot_debug_nb_transform(rsi_ctx* ctx, const int64_t* binsum, int64_t nb, int m, int64_t ncompact, double RDmedian, double r,
+                               float* raw, float* T, int32_t* info);
+/* Test hook: filterstatus (rsi.cpp:948-1047) behind a scan pass, over the HOST arrays T[nb] and status[nb] (values in [-Lmax, Lmax],
+ * 1 <= Lmax <= 4194304; anything else is RSI_ERR_BAD_ARG).  The pass's last launch is reproduced (first lengths taken from status,
+ * both stop levels Lmax), so the status array, its copy, the run boundaries and their export are the production ones; then the
+ * function the scan calls: level sums, level choice, run list, edge trimming.  status_out[nb]: the trimmed copy.  info[10] = runs
+ * after the last is dropped (-1: nothing was trimmed); 1 / 0 for the run list in the kernel arguments / behind pointers (-1); 1 / 0
+ * for boundary entries beyond the eager ones copied / none (-1); level sums by the device (0), by the host loop because the device
+ * declined (1), by the host loop of a long scan (2); an unmarked level exists; trimming applies; leveldel; leveladd; the unmarked
+ * bins' mean as float bits; 0.  Overwrites the bin arrays the rsi_hot_fetch_* calls read. */
+int rsi_hot_debug_filterstatus(rsi_ctx* ctx, const float* T, const int32_t* status, int64_t nb, int Lmax, double dev, int32_t* status_out,
+                               int32_t* info);
 /* Test hook: the 0.01-grid median and MAD (partition_stat_tp, wufunctions.cpp:364-424) of the HOST array x[nb], restricted to
  * mask[i] == 0 when mask != NULL, through the forms the scan's thresholds take:
  *   mode 0: the device chain of a (median, MAD) pair, the MAD centred on the chain's own median;

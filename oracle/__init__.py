@@ -201,6 +201,11 @@ class Ref:
                                                        C.c_int32]
             L.ref_optimize_with_derivative.restype = None
 
+        if hasattr(L, "ref_filterstatus"):   # likewise
+            L.ref_negative_binomial_transfer.argtypes = [C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_int32]
+            L.ref_filterstatus.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_int32), C.c_int32, C.c_double]
+            L.ref_filterstatus.restype = None
+
     def load(self, params, depth, fasta, chrom="chrS", log=None):
         d, dp = _i32(depth)
         f = np.ascontiguousarray(fasta, dtype=np.uint8)
@@ -351,6 +356,27 @@ class Ref:
         k = self.lib.ref_get_rsi_segments(t.ctypes.data_as(C.POINTER(C.c_float)), sp, t.size, float(tmedian), s.ctypes.data_as(ip),
                                           e.ctypes.data_as(ip), ty.ctypes.data_as(ip), sc.ctypes.data_as(C.POINTER(C.c_double)), cap)
         return s[:k].copy(), e[:k].copy(), ty[:k].copy(), sc[:k].copy()
+
+    def negative_binomial_transfer(self, rd, m):
+        """The reference's negative_binomial_transfer (rsi.cpp:1120-1188) over the caller's compacted depth: the rd.size // m bins."""
+        if not hasattr(self.lib, "ref_negative_binomial_transfer"):
+            raise RuntimeError(f"{REF_SO} predates ref_negative_binomial_transfer: rebuild it with `make -f oracle/Makefile.ref`")
+        d, dp = _i32(rd)
+        out = np.zeros(d.size // int(m), dtype=np.float32)
+        k = self.lib.ref_negative_binomial_transfer(dp, d.size, int(m), out.ctypes.data_as(C.POINTER(C.c_float)), out.size)
+        assert k == out.size
+        return out
+
+    def filterstatus(self, T, status, dev):
+        """The reference's filterstatus (rsi.cpp:948-1047) over the caller's bins and status: the filtered status.  The caller sends an
+        array with an unmarked level inside its level range: the reference indexes out of range otherwise."""
+        if not hasattr(self.lib, "ref_filterstatus"):
+            raise RuntimeError(f"{REF_SO} predates ref_filterstatus: rebuild it with `make -f oracle/Makefile.ref`")
+        t = np.ascontiguousarray(T, dtype=np.float32)
+        st = np.array(status, dtype=np.int32)
+        assert st.shape == t.shape and t.ndim == 1
+        self.lib.ref_filterstatus(t.ctypes.data_as(C.POINTER(C.c_float)), st.ctypes.data_as(C.POINTER(C.c_int32)), t.size, float(dev))
+        return st
 
     def optimize_with_derivative(self, rd, start, end, type_, calls=2):
         """The reference's optimize_with_derivative (rsi.cpp:889-937), `calls` times, on one candidate: (start, end).  The caller keeps

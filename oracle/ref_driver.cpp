@@ -484,6 +484,34 @@ void ref_optimize_with_derivative(const int32_t* rd, int32_t n, int32_t* start, 
   *start = c.start; *end = c.end;
 }
 
+// negative_binomial_transfer alone (rsi.cpp:1120-1188) on the caller's compacted depth: n / m transformed bins into out (room for
+// cap of them).  Its median, its 31 subsample MADs and r are its own; it reads no global.  Returns the number of bins.
+int ref_negative_binomial_transfer(const int32_t* rd, int32_t n, int32_t m, float* out, int32_t cap) {
+  static Array<int> RD(1);
+  RD.resize(0);
+  RD.resize(n);
+  for (int k = 0; k < n; ++k) RD[k] = rd[k];
+  Array<float> t(1);
+  quiet_begin();
+  negative_binomial_transfer(RD, m, t);
+  quiet_end();
+  for (int i = 0; i < t.size() && i < cap; ++i) out[i] = t[i];
+  return t.size();
+}
+
+// filterstatus alone (rsi.cpp:948-1047) on the caller's bins and status, which is filtered in place.  Without an unmarked level
+// inside [min status, max status] the reference indexes its level sums out of range: the caller sends no such array
+// (tests/filter_cases.py proves it for every case before it comes here).
+void ref_filterstatus(const float* T, int32_t* status, int32_t nb, double dev) {
+  Array<float> t(nb, T);
+  Array<int> st(nb, 0);
+  for (int i = 0; i < nb; ++i) st[i] = status[i];
+  quiet_begin();
+  filterstatus(t, dev, st);
+  quiet_end();
+  for (int i = 0; i < nb; ++i) status[i] = st[i];
+}
+
 // Direct probes of the numeric utilities (used to pin the oracle's restatements).
 double ref_median_i32(const int32_t* x, int64_t n) { return _median(const_cast<int*>(x), (size_t)n); }
 double ref_median_f32(const float* x, int64_t n) { return _median(const_cast<float*>(x), (size_t)n); }

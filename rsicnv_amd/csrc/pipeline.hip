@@ -98,6 +98,25 @@ GridChain grid_chain(rsi_ctx* ctx) {
   return GridChain{reinterpret_cast<MinMaxF*>(small + kOffMinMax), ctx->hist_f.as<uint32_t>(), kGridCap,
                    reinterpret_cast<unsigned int*>(small + kOffDone) + kDoneBinSlot};
 }
+// A10: the NB transform (K5; negative_binomial_transfer, rsi.cpp:1145-1185) of the bin sums into ctx->tnb, always computed as the
+// reference does (Q10).  The raw minimum stays on the device: the scaling kernel derives the scaled levels from it and from
+// the three raw reference levels computed here (host libm, as the reference), and takes the min/max of the scaled values for
+// the median that follows (its grid lands in the first GridMedian record).  The raw-minimum word and the min/max record are
+// clear when it is called.  raw_out (rsi_hot_debug_nb_transform): the array between the two launches, copied out before the second.
+int nb_transform(rsi_ctx* ctx, const int64_t* d_binsum, int64_t nb, int m, int64_t ncompact, double RDmedian, double r, rsih::NbLevels& lev,
+                 float* raw_out) {
+  uint8_t* small = ctx->small.as<uint8_t>();
+  hipStream_t st = ctx->stream;
+  HIPCHK(ctx->tnb.ensure((size_t)nb * 4));
+  HIPCHK(ctx->hist_f.ensure((size_t)kGridCap * 4));
+  uint32_t* d_rawmin = reinterpret_cast<uint32_t*>(small + kOffRawMin);
+  GridMedian* d_g = reinterpret_cast<GridMedian*>(small + kOffGrid);
+  { Timer t(ctx, "nb_raw"); launch_nb_raw(d_binsum, nb, m, ncompact, r, ctx->tnb.as<float>(), d_rawmin, st); }
+  if (raw_out) HIPCHK(hipMemcpyAsync(raw_out, ctx->tnb.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
+  lev = rsih::nb_reference_levels(RDmedian, m, r);
+  { Timer t(ctx, "nb_scale"); launch_nb_scale_minmax(ctx->tnb.as<float>(), nb, d_rawmin, lev.med_raw, lev.del_raw, lev.dup_raw, RDmedian, grid_chain(ctx), d_g, st); }
+  return RSI_OK;
+}
 // what the scan pass `pass` needs cleared: the first-L arrays, its work block, the run-boundary counter
 void scan_fill_list(rsi_ctx* ctx, int pass, int64_t nb, FillList& fl) {
   uint8_t* small = ctx->small.as<uint8_t>();
@@ -551,6 +570,73 @@ int rsi_segments(rsi_ctx* ctx, const float* d_T, const int32_t* d_st2, int64_t n
   return RSI_OK;
 }
 
+// filterstatus behind the first scan pass (rsi.cpp:948-1047): the per-level sums are float accumulations in index order
+// (App. A Q13) -- computed on the device by an exact parallel form of the sequential loop (kernels_fs.hip), so neither the
+// transformed bins nor the status array travel to the host; the edge trimming runs on the device too, one workgroup per run.
+// d_st1: the pass's status, d_st1f: its copy, which is trimmed; rslot: the pass's run boundaries in the mailbox (scan_pass).
+// synced(): what the caller reads from the mailbox once the stream has drained (run_scan: the pass's record), called behind
+// the wait, a failure ends the stage.  form: the road taken, for rsi_hot_debug_filterstatus.
+struct FsForm { int runs = -1, inl = -1, copied = -1, route = 0, has_level0 = 0, trim = 0, leveldel = 0, leveladd = 0; float m0 = 0.0f; };
+template <class Synced>
+int rsi_filterstatus(rsi_ctx* ctx, const float* d_T, const int32_t* d_st1, int32_t* d_st1f, int64_t nb, int Lmax, double dev,
+                     const uint32_t* rslot, Synced&& synced, std::vector<std::string>* fs_lines, FsForm* form) {
+  int rc;
+  const bool long_scan = Lmax > kMaxL;
+  const int nlev = 2 * Lmax + 1;
+  uint32_t* fs_slot = long_scan ? nullptr : static_cast<uint32_t*>(mb_alloc(ctx, (size_t)nlev * 8));
+  if (!fs_slot && !long_scan) return fail(ctx, RSI_ERR_INTERNAL, "out of pinned mailbox memory");
+  if (!long_scan) {
+    GateShared gs(ctx);
+    Timer t(ctx, "level_sums");
+    launch_level_sums(d_T, d_st1, nb, Lmax, ctx->fs_ws.p, kMaxL, kFsListCap, ctx->fs_out.as<float>(),
+                      reinterpret_cast<unsigned int*>(ctx->small.as<uint8_t>() + kOffDone) + kDoneBinSlot + 4, fs_slot, ctx->stream);
+  }
+  { Phase phc(ctx, "fs.wait"); HIPCHK(CTX_SYNC()); }
+  if ((rc = synced()) != RSI_OK) return rc;
+  {
+    Phase phs(ctx, "fs.sums");
+    // status values lie in [-Lmax, Lmax].  The level range the reference works on is [min status, max status]: taken from
+    // the counts afterwards.
+    std::vector<float> wsum((size_t)nlev, 0.0f);
+    std::vector<int> wcnt((size_t)nlev, 0);
+    if (fs_slot) {
+      memcpy(wsum.data(), fs_slot, (size_t)nlev * 4);
+      memcpy(wcnt.data(), fs_slot + nlev, (size_t)nlev * 4);
+    }
+    if (form) form->route = long_scan ? 2 : (wcnt[(size_t)Lmax] < 0 ? 1 : 0);
+    if (long_scan || wcnt[(size_t)Lmax] < 0) {   // a long scan, or the device declined (negative / non-finite values, too many marked bins): the loop itself
+      Phase phc(ctx, "fs.copy");
+      HIPCHK(ctx->h_T.ensure((size_t)nb * 4));
+      HIPCHK(ctx->h_status.ensure((size_t)nb * 4));
+      HIPCHK(hipMemcpyAsync(ctx->h_T.p, d_T, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHK(hipMemcpyAsync(ctx->h_status.p, d_st1, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHK(CTX_SYNC());
+      rsih::level_sums_host(ctx->h_T.as<float>(), ctx->h_status.as<int>(), nb, Lmax, wsum, wcnt);
+    }
+    rsih::LevelChoice lc = rsih::choose_levels(wsum, wcnt, Lmax, dev);
+    phs.stop();
+    Phase phr(ctx, "fs.runs");
+    if (form) { form->has_level0 = lc.has_level0; form->trim = lc.trim; form->leveldel = lc.leveldel; form->leveladd = lc.leveladd; form->m0 = lc.m0; }
+    if (lc.has_level0) {
+      const float m0 = lc.m0;
+      if (fs_lines) *fs_lines = std::move(lc.lines);   // filterstatus' level table as the reference logs it (rsi.cpp:991-997)
+      if (lc.trim) {
+        std::vector<Region> runs;
+        GateShared gs(ctx);
+        if ((rc = runs_from_export(ctx, rslot, ctx->runs.as<uint64_t>(), runs)) != RSI_OK) return rc;
+        if (form) { form->runs = (int)runs.size(); form->copied = rslot[0] > kEagerBounds ? 1 : 0; form->inl = runs.size() <= (size_t)kRunsInline ? 1 : 0; }
+        if (!runs.empty()) {
+          RunArgs ra;
+          if ((rc = prepare_runs(ctx, runs, ra)) != RSI_OK) return rc;
+          Timer t(ctx, "trim_runs");
+          launch_trim_runs(d_T, d_st1f, ra.d_start, ra.d_end, ra.use_inl ? &ra.inl : nullptr, (int)runs.size(), (double)m0 - dev, (double)m0 + dev, ctx->stream);
+        }
+      }
+    }
+  }
+  return RSI_OK;
+}
+
 // rsicnvnbn (rsi.cpp:1262-1360) / rsicnvmed (rsi.cpp:1402-1501) around the device scan.  `first` = the record the quantile
 // chain in front of the first pass leaves in the mailbox (issued by the caller, behind the transform).
 int run_scan(rsi_ctx* ctx, const rsi_params& P, bool use_med, const float* d_T, int64_t nb, double RDmedian,
@@ -597,7 +683,6 @@ int run_scan(rsi_ctx* ctx, const rsi_params& P, bool use_med, const float* d_T, 
   // 32 000, per-L counts in device memory past 20 000) and filterstatus' level sums run on the host.  kHardMaxL bounds the
   // scratch (a tile of 4 M bins is 440 MB per workgroup); the reference itself would need years for such a sweep.
   if (Lmax > kHardMaxL) return fail(ctx, RSI_ERR_UNSUPPORTED, "scan length Lmax beyond 4194304 bins");
-  const bool long_scan = Lmax > kMaxL;
   std::vector<uint32_t> spill1, spill2;
   // what a pass's record tells the run: the reference's exit (a sweep reached every bin), the counters, the per-L log of sweeps 2 * pass, 2 * pass + 1
   auto take_record = [&](const uint32_t* w, int pass) -> int {
@@ -619,58 +704,7 @@ int run_scan(rsi_ctx* ctx, const rsi_params& P, bool use_med, const float* d_T, 
   { Phase ph(ctx, "scan.pass"); GateShared gs(ctx); if ((rc = scan_pass(ctx, 0, d_T, d_medint, nb, RDmedian, tmedian, tlamda, Lmax, d_st1, d_st1f, &wslot, &rslot, &spill1)) != RSI_OK) return rc; }
 
   Phase ph_filter(ctx, "scan.filterstatus");
-  // ---- filterstatus (rsi.cpp:948-1047): the per-level sums are float accumulations in index order (App. A Q13) -- computed
-  // on the device by an exact parallel form of the sequential loop (kernels_fs.hip), so neither the transformed bins nor
-  // the status array travel to the host; the edge trimming runs on the device too, one thread per run ----
-  const int nlev = 2 * Lmax + 1;
-  uint32_t* fs_slot = long_scan ? nullptr : static_cast<uint32_t*>(mb_alloc(ctx, (size_t)nlev * 8));
-  if (!fs_slot && !long_scan) return fail(ctx, RSI_ERR_INTERNAL, "out of pinned mailbox memory");
-  if (!long_scan) {
-    GateShared gs(ctx);
-    Timer t(ctx, "level_sums");
-    launch_level_sums(d_T, d_st1, nb, Lmax, ctx->fs_ws.p, kMaxL, kFsListCap, ctx->fs_out.as<float>(),
-                      reinterpret_cast<unsigned int*>(ctx->small.as<uint8_t>() + kOffDone) + kDoneBinSlot + 4, fs_slot, ctx->stream);
-  }
-  { Phase phc(ctx, "fs.wait"); HIPCHK(CTX_SYNC()); }
-  if ((rc = take_record(wslot, 0)) != RSI_OK) return rc;
-  {
-    Phase phs(ctx, "fs.sums");
-    // status values lie in [-Lmax, Lmax].  The level range the reference works on is [min status, max status]: taken from
-    // the counts afterwards.
-    std::vector<float> wsum((size_t)nlev, 0.0f);
-    std::vector<int> wcnt((size_t)nlev, 0);
-    if (fs_slot) {
-      memcpy(wsum.data(), fs_slot, (size_t)nlev * 4);
-      memcpy(wcnt.data(), fs_slot + nlev, (size_t)nlev * 4);
-    }
-    if (long_scan || wcnt[(size_t)Lmax] < 0) {   // a long scan, or the device declined (negative / non-finite values, too many marked bins): the loop itself
-      Phase phc(ctx, "fs.copy");
-      HIPCHK(ctx->h_T.ensure((size_t)nb * 4));
-      HIPCHK(ctx->h_status.ensure((size_t)nb * 4));
-      HIPCHK(hipMemcpyAsync(ctx->h_T.p, d_T, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
-      HIPCHK(hipMemcpyAsync(ctx->h_status.p, d_st1, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
-      HIPCHK(CTX_SYNC());
-      rsih::level_sums_host(ctx->h_T.as<float>(), ctx->h_status.as<int>(), nb, Lmax, wsum, wcnt);
-    }
-    rsih::LevelChoice lc = rsih::choose_levels(wsum, wcnt, Lmax, dev);
-    phs.stop();
-    Phase phr(ctx, "fs.runs");
-    if (lc.has_level0) {
-      const float m0 = lc.m0;
-      out.fs_lines = std::move(lc.lines);   // filterstatus' level table as the reference logs it (rsi.cpp:991-997)
-      if (lc.trim) {
-        std::vector<Region> runs;
-        GateShared gs(ctx);
-        if ((rc = runs_from_export(ctx, rslot, ctx->runs.as<uint64_t>(), runs)) != RSI_OK) return rc;
-        if (!runs.empty()) {
-          RunArgs ra;
-          if ((rc = prepare_runs(ctx, runs, ra)) != RSI_OK) return rc;
-          Timer t(ctx, "trim_runs");
-          launch_trim_runs(d_T, d_st1f, ra.d_start, ra.d_end, ra.use_inl ? &ra.inl : nullptr, (int)runs.size(), (double)m0 - dev, (double)m0 + dev, ctx->stream);
-        }
-      }
-    }
-  }
+  if ((rc = rsi_filterstatus(ctx, d_T, d_st1, d_st1f, nb, Lmax, dev, rslot, [&] { return take_record(wslot, 0); }, &out.fs_lines, nullptr)) != RSI_OK) return rc;
   ph_filter.stop();
   // ---- second-pass parameters on the unmarked bins (rsi.cpp:1307-1319 / 1457-1469) ----
   Phase ph_q2(ctx, "scan.quantiles");
@@ -1250,17 +1284,11 @@ int bin_level_stages(rsi_ctx* ctx, const rsi_params& P, int64_t n, rsi_result* r
     HIPCHK(ctx->fs_ws.ensure(level_sums_workspace_bytes(nb, kFsListCap, kMaxL)));
     HIPCHK(ctx->fs_out.ensure((size_t)(2 * kMaxL + 1) * 8 + 64));
 
-    // ---- A10: NB transform (K5), always computed as the reference does (Q10).  The raw minimum stays on the device: the
-    // scaling kernel derives the scaled levels from it and from the three raw reference levels computed here (host libm, as
-    // the reference), and takes the min/max of the scaled values for the median that follows. ----
-    HIPCHK(ctx->tnb.ensure((size_t)nb * 4));
-    HIPCHK(ctx->hist_f.ensure((size_t)kGridCap * 4));
-    uint32_t* d_rawmin = reinterpret_cast<uint32_t*>(small + kOffRawMin);
+    // ---- A10: NB transform (K5): nb_transform ----
     GridMedian* d_g = reinterpret_cast<GridMedian*>(small + kOffGrid);
-    { Timer t(ctx, "nb_raw"); launch_nb_raw(ctx->binsum.as<int64_t>(), nb, P.m, ncompact, r, ctx->tnb.as<float>(), d_rawmin, st); }
-    const rsih::NbLevels lev = rsih::nb_reference_levels(RDmedian, P.m, r);
+    rsih::NbLevels lev;
+    if ((rc = nb_transform(ctx, ctx->binsum.as<int64_t>(), nb, P.m, ncompact, RDmedian, r, lev, nullptr)) != RSI_OK) return rc;
     const double med_raw = lev.med_raw, del_raw = lev.del_raw, dup_raw = lev.dup_raw;
-    { Timer t(ctx, "nb_scale"); launch_nb_scale_minmax(ctx->tnb.as<float>(), nb, d_rawmin, med_raw, del_raw, dup_raw, RDmedian, grid_chain(ctx), d_g, st); }
     bool nb_planned = true;   // d_g[0] holds the grid of the NB values' median, its buckets are clear
     ctx->have_nb = true;
 
@@ -1871,6 +1899,113 @@ int rsi_hot_debug_segments(rsi_ctx* ctx, const float* T, const int32_t* status, 
   }
   info[0] = form.runs; info[1] = form.items; info[2] = form.inl; info[3] = form.mailbox_status; info[4] = form.unstaged;
   info[5] = (int32_t)out.segs.size(); info[6] = (int32_t)std::min<int64_t>(form.pairs_per_item, 0x7fffffff); info[7] = 0;
+  return RSI_OK;
+}
+
+// Test hook: the NB transform over host bin sums (include/rsi_hot.h).  The sums are uploaded into the buffer a run keeps them in
+// and nb_transform -- what bin_level_stages calls -- does the rest.  The scale kernel's last workgroup turns the min/max record
+// into the plan of the first quantile grid and clears the record: what comes back is that plan, and the record as it was left.
+int rsi_hot_debug_nb_transform(rsi_ctx* ctx, const int64_t* binsum, int64_t nb, int m, int64_t ncompact, double RDmedian, double r,
+                               float* raw, float* T, int32_t* info) {
+  if (!ctx || !binsum || !raw || !T || !info || nb < 3 || nb >= (1ll << 31) - 4096 || m < 1 || ncompact / m != nb || !(r > 0.0))
+    return fail(ctx, RSI_ERR_BAD_ARG, "bad argument");
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!ctx_enter(ctx)) return RSI_ERR_HIP;
+  mailbox_reset(ctx);
+  ctx->ktimes.clear(); ctx->event_next = 0; ctx->phases.clear();
+  ctx->nb = nb; ctx->run_m = 0;
+  ctx->have_nb = false;   // tnb and binsum hold the caller's bins now
+  HIPCHK(ctx->small.ensure(kSmallBytes));
+  HIPCHK(ctx->binsum.ensure((size_t)nb * 8));
+  HIPCHK(hipMemsetAsync(ctx->small.p, 0, kHeaderBytes, ctx->stream));   // the raw minimum, the min/max record, the arrival counters
+  HIPCHK(hipMemcpyAsync(ctx->binsum.p, binsum, (size_t)nb * 8, hipMemcpyHostToDevice, ctx->stream));
+  rsih::NbLevels lev;
+  int rc;
+  {
+    GateShared gs(ctx);
+    if ((rc = nb_transform(ctx, ctx->binsum.as<int64_t>(), nb, m, ncompact, RDmedian, r, lev, raw)) != RSI_OK) return rc;
+  }
+  uint8_t* small = ctx->small.as<uint8_t>();
+  uint32_t rawmin_inv = 0;
+  MinMaxF mm;
+  GridMedian g;
+  HIPCHK(hipMemcpyAsync(T, ctx->tnb.p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(&rawmin_inv, small + kOffRawMin, 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(&mm, small + kOffMinMax, sizeof(mm), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(&g, small + kOffGrid, sizeof(g), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(CTX_SYNC());
+  const float tmin = rsih::unkey_f32(~rawmin_inv), ymin = (float)g.ymin;
+  const rsih::NbScaled lv = rsih::nb_scaled_levels(tmin, lev.med_raw, lev.del_raw, RDmedian);
+  memcpy(&info[0], &tmin, 4);
+  info[1] = (int32_t)g.flags; info[2] = (int32_t)g.np;
+  memcpy(&info[3], &ymin, 4);
+  info[4] = (int32_t)(mm.min_inv | mm.max_bits | mm.nonfinite);
+  memcpy(&info[5], &lv.t0, 4);
+  memcpy(&info[6], &lv.t2, 4);
+  info[7] = 0;
+  return RSI_OK;
+}
+
+// Test hook: filterstatus behind a scan pass, over host arrays (include/rsi_hot.h).  What a pass leaves is reproduced with the pass's
+// own last launch: the first-length arrays are built from `status`, both stop levels are Lmax, and launch_resolve_runs -- with
+// the arguments scan_pass gives it -- writes status1, its copy, the boundary list and its mailbox export.  rsi_filterstatus, what
+// run_scan calls behind its first pass, does the rest.
+int rsi_hot_debug_filterstatus(rsi_ctx* ctx, const float* T, const int32_t* status, int64_t nb, int Lmax, double dev, int32_t* status_out,
+                               int32_t* info) {
+  if (!ctx || !T || !status || !status_out || !info || nb <= 0 || nb >= (1ll << 31) - 4096 || Lmax < 1 || Lmax > kHardMaxL)
+    return fail(ctx, RSI_ERR_BAD_ARG, "bad argument");
+  const int64_t nbpad = (nb + 3) & ~int64_t(3);
+  std::vector<uint32_t> first((size_t)(nbpad + nb), 0xffffffffu);   // first_del | first_dup, "no length" where a bin has none
+  for (int64_t i = 0; i < nb; ++i) {
+    const int32_t s = status[i];
+    if (s < -Lmax || s > Lmax) return fail(ctx, RSI_ERR_BAD_ARG, "status values must lie in [-Lmax, Lmax]");
+    if (s < 0) first[(size_t)i] = (uint32_t)(-s);
+    if (s > 0) first[(size_t)(nbpad + i)] = (uint32_t)s;
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!ctx_enter(ctx)) return RSI_ERR_HIP;
+  mailbox_reset(ctx);
+  ctx->ktimes.clear(); ctx->event_next = 0; ctx->phases.clear();
+  ctx->nb = nb; ctx->run_m = 0;
+  ctx->have_nb = false;   // tnb holds the caller's array now
+  HIPCHK(ctx->small.ensure(kSmallBytes));
+  HIPCHK(ctx->tnb.ensure((size_t)nb * 4));
+  HIPCHK(ctx->first_del.ensure((size_t)(2 * nb + 8) * 4));
+  HIPCHK(ctx->status1.ensure((size_t)nb * 4));
+  HIPCHK(ctx->status1f.ensure((size_t)nb * 4));
+  HIPCHK(ctx->runs.ensure((size_t)kMaxRunEntries * 8));
+  HIPCHK(ctx->fs_ws.ensure(level_sums_workspace_bytes(nb, kFsListCap, kMaxL)));
+  HIPCHK(ctx->fs_out.ensure((size_t)(2 * kMaxL + 1) * 8 + 64));
+  uint8_t* small = ctx->small.as<uint8_t>();
+  uint32_t* work = reinterpret_cast<uint32_t*>(small + kOffScanPass);   // the first pass's work block: [2], [3] = the stop levels
+  const uint32_t stops[2] = {(uint32_t)Lmax, (uint32_t)Lmax};
+  HIPCHK(hipMemsetAsync(ctx->small.p, 0, kHeaderBytes, ctx->stream));   // arrival counters, the boundary count
+  HIPCHK(hipMemsetAsync(ctx->fs_ws.p, 0, level_sums_head_bytes(kMaxL), ctx->stream));
+  HIPCHK(hipMemcpyAsync(ctx->tnb.p, T, (size_t)nb * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(ctx->first_del.p, first.data(), first.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(work + 2, stops, 8, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(CTX_SYNC());
+  uint32_t* d_first_del = ctx->first_del.as<uint32_t>();
+  unsigned int* d_done = reinterpret_cast<unsigned int*>(small + kOffDone) + kDoneBinSlot;
+  uint32_t* d_count = reinterpret_cast<uint32_t*>(small + kOffCounters) + 4;
+  uint32_t* rslot = static_cast<uint32_t*>(mb_alloc(ctx, 8 + (size_t)kEagerBounds * 8));
+  if (!rslot) return fail(ctx, RSI_ERR_INTERNAL, "out of pinned mailbox memory");
+  FsForm form;
+  int rc;
+  {
+    GateShared gs(ctx);
+    Timer t(ctx, "resolve_runs");
+    launch_resolve_runs(d_first_del, d_first_del + nbpad, work + 2, nb, ctx->status1.as<int32_t>(), ctx->status1f.as<int32_t>(), ctx->runs.as<uint64_t>(),
+                        d_count, kMaxRunEntries, d_done + 3, rslot, kEagerBounds, ctx->stream);
+  }
+  if ((rc = rsi_filterstatus(ctx, ctx->tnb.as<float>(), ctx->status1.as<int32_t>(), ctx->status1f.as<int32_t>(), nb, Lmax, dev, rslot,
+                             [] { return (int)RSI_OK; }, nullptr, &form)) != RSI_OK) return rc;
+  HIPCHK(hipMemcpyAsync(status_out, ctx->status1f.p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(CTX_SYNC());
+  info[0] = form.runs; info[1] = form.inl; info[2] = form.copied; info[3] = form.route;
+  info[4] = form.has_level0; info[5] = form.trim; info[6] = form.leveldel; info[7] = form.leveladd;
+  memcpy(&info[8], &form.m0, 4);
+  info[9] = 0;
   return RSI_OK;
 }
 

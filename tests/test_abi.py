@@ -23,7 +23,7 @@ def test_every_declared_symbol_is_exported(hotlib):
     assert not missing, f"librsi_hot.so lacks: {missing}"
     assert set(api.EXPORTS) <= set(names)
     assert "rsi_hot_debug_per_base" in names and "rsi_hot_debug_per_base" in api.EXPORTS
-    for hook in ("rsi_hot_debug_segments", "rsi_hot_debug_sharpen"):
+    for hook in ("rsi_hot_debug_segments", "rsi_hot_debug_sharpen", "rsi_hot_debug_nb_transform", "rsi_hot_debug_filterstatus"):
         assert hook in names and hook in api.EXPORTS
 
 

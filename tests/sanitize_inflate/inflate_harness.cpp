@@ -2,6 +2,8 @@
 // ASan + UBSan).  Every member is checked as the kernel checks it: inflate_raw into exactly ISIZE bytes, then the size and
 // the CRC32 (as 64 slices combined with the shift constants, the way the kernel's lanes do it).
 //   inflate FILE OUT      the BGZF file's members, their text concatenated into OUT; exit 1 on a bad member
+//   verdicts FILE OUT     one line per member, "member I: ok" or "member I: <reason>" (rsinf::err_name); the text of the good
+//                         members into OUT; exit 0 whatever the verdicts
 //   fuzz FILE SEED N      N damaged copies of the file's members (bit flips, truncation, random bytes, random payloads):
 //                         each must give an error or exactly the original text; prints counts, exit 1 on a wrong output
 #include "../../rsicnv_amd/csrc/inflate_core.h"
@@ -74,7 +76,7 @@ bool read_blocks(const char* path, std::vector<Block>& blocks) {
 }  // namespace
 
 int main(int argc, char** argv) {
-  if (argc < 4) { fprintf(stderr, "usage: inflate FILE OUT | fuzz FILE SEED N\n"); return 2; }
+  if (argc < 4) { fprintf(stderr, "usage: inflate FILE OUT | verdicts FILE OUT | fuzz FILE SEED N\n"); return 2; }
   std::vector<Block> blocks;
   if (!read_blocks(argv[2], blocks)) return 2;
   const std::string mode = argv[1];
@@ -89,6 +91,18 @@ int main(int argc, char** argv) {
     }
     fclose(out);
     printf("inflate ok: %zu members\n", blocks.size());
+    return 0;
+  }
+  if (mode == "verdicts") {
+    FILE* out = fopen(argv[3], "wb");
+    if (!out) return 2;
+    for (size_t i = 0; i < blocks.size(); ++i) {
+      std::vector<uint8_t> t;
+      const int rc = inflate_member(blocks[i].payload, blocks[i].isize, blocks[i].crc, t);
+      printf("member %zu: %s\n", i, rsinf::err_name(rc));
+      if (rc == rsinf::kOk && !t.empty()) fwrite(t.data(), 1, t.size(), out);
+    }
+    fclose(out);
     return 0;
   }
   if (mode != "fuzz" || argc < 5) return 2;

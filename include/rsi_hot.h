@@ -21,6 +21,7 @@
  */
 #ifndef RSI_HOT_H
 #define RSI_HOT_H
+#include <stddef.h>
 #include <stdint.h>
 #ifdef __cplusplus
 extern "C" {
@@ -251,6 +252,28 @@ typedef struct rsi_bam_stats {
 } rsi_bam_stats;
 /* Depth of `chrom` into the context's device depth buffer (int32[stats->n]); rsi_hot_fetch_i32("depth_in") reads it back. */
 int rsi_hot_load_depth_bam(rsi_ctx* ctx, const char* bam_path, const char* chrom, int minq, int min_baseq, rsi_bam_stats* stats);
+/* Where rsi_hot_load_depth_bam / rsi_hot_run_bam / _run_bam_dfasta of this context read the file's records from now on
+ * (RSI_BAM_READ_HOST when never called; any other mode is RSI_ERR_BAD_ARG).  RSI_BAM_READ_DEVICE: the compressed BGZF members
+ * go to the GPU, are inflated there (CRC32 and ISIZE checked), the records of the chromosome are found there and piled up by the
+ * same kernel; nothing inflated crosses PCIe and the host touches member headers only (the BAM header's few blocks and the .bai
+ * excepted).  The depth and the stats fields n, tid, indexed, records, on_chrom, used, runs and malformed are the host mode's for
+ * the same file; bytes_* and t_* describe this mode's own chunks (t_inflate_ms: the inflate kernels, t_walk_ms: the record
+ * finder's).  chunk_bytes: inflated bytes per chunk, rounded up to whole members, at least 64 KiB and at most 32 MiB; 0: the
+ * default (32 MiB).  Errors of the device mode, the context usable afterwards: a member that fails its CRC32, ISIZE or the decoder
+ * (RSI_ERR_BAD_ARG naming the member's file offset and the reason), a file cut inside a member, a block_size below 32 where a
+ * record must start ("malformed BAM record"), both RSI_ERR_BAD_ARG; a record longer than 8 MB that spans chunks,
+ * RSI_ERR_UNSUPPORTED as in the host mode. */
+enum { RSI_BAM_READ_HOST = 0, RSI_BAM_READ_DEVICE = 1 };
+int rsi_hot_set_bam_read(rsi_ctx* ctx, int mode, size_t chunk_bytes);
+typedef struct rsi_bam_read_stats {
+  int32_t mode, pad;                 /* of the context's last BAM load; the rest is 0 after a host-mode load */
+  int64_t chunks, members, segments; /* chunks read, BGZF members inflated, 16 384-byte segments searched */
+  int64_t guessed, rewalked, passed; /* segments whose guessed record start was the true one / that were walked again from the
+                                        true one / that a long record covers */
+  double t_upload_ms, t_inflate_ms, t_find_ms;   /* HIP events: compressed bytes and member table to the device, inflate kernels,
+                                                    guess + walk + stitch kernels */
+} rsi_bam_read_stats;
+int rsi_hot_last_bam_read_stats(const rsi_ctx* ctx, rsi_bam_read_stats* out);
 /* RP / Q0 annotation of the final calls (cnv_stat, pairrd.cpp:622-748; host only): the insert-size statistics are
  * sampled from the window the reference uses (1 Mb of reads from position 10 Mb of the chromosome on, pairrd.cpp:636),
  * then, per call, the read pairs within max(1000, length) <= 5000 bases are classified.  Needs BAM.bai.  The result's

@@ -71,6 +71,7 @@ EXPORTS = ["rsi_default_params", "rsi_hot_create", "rsi_hot_destroy", "rsi_hot_l
            "rsi_ref_open", "rsi_ref_close", "rsi_ref_last_error", "rsi_ref_count", "rsi_ref_sequence", "rsi_ref_find", "rsi_ref_format",
            "rsi_ref_index_path", "rsi_ref_load_device", "rsi_ref_load_host", "rsi_ref_device_alloc", "rsi_ref_device_free",
            "rsi_hot_run_text_dfasta", "rsi_hot_run_bam_dfasta",
+           "rsi_hot_set_bam_read", "rsi_hot_last_bam_read_stats",
            "rsi_ref_debug_set_chunks", "rsi_ref_debug_fai_line", "rsi_ref_debug_ranges", "rsi_ref_debug_gzi", "rsi_ref_debug_cover"]
 
 
@@ -151,6 +152,16 @@ class RsiBamStats(C.Structure):
                 ("used", C.c_int64), ("runs", C.c_int64), ("tid", C.c_int32), ("indexed", C.c_int32),
                 ("t_total_ms", C.c_double), ("t_inflate_ms", C.c_double), ("t_walk_ms", C.c_double), ("t_wait_ms", C.c_double),
                 ("malformed", C.c_int64)]
+
+
+class RsiBamReadStats(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("pad", C.c_int32), ("chunks", C.c_int64), ("members", C.c_int64), ("segments", C.c_int64),
+                ("guessed", C.c_int64), ("rewalked", C.c_int64), ("passed", C.c_int64),
+                ("t_upload_ms", C.c_double), ("t_inflate_ms", C.c_double), ("t_find_ms", C.c_double)]
+
+
+BAM_READ_MODES = {"host": 0, "device": 1}
+BAM_SEGMENT = 16384          # kernels.h, RSI_BAM_SEGMENT: bytes of inflated BAM per segment of the device record finder
 
 
 class RsiBatchTimes(C.Structure):
@@ -289,6 +300,8 @@ def load_library():
     L.rsi_hot_debug_bin_track.restype = C.c_int64
     L.rsi_hot_set_track_format.argtypes = [C.c_void_p, C.c_int]
     L.rsi_hot_last_deflate_stats.argtypes = [C.c_void_p, C.POINTER(RsiDeflateStats)]
+    L.rsi_hot_set_bam_read.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
+    L.rsi_hot_last_bam_read_stats.argtypes = [C.c_void_p, C.POINTER(RsiBamReadStats)]
     L.rsi_bgzf_write_eof.argtypes = [C.c_char_p]
     L.rsi_track_index_create.argtypes = []
     L.rsi_track_index_create.restype = C.c_void_p
@@ -816,6 +829,24 @@ class RsiHot:
         st = RsiBamStats()
         self._check(self.lib.rsi_hot_load_depth_bam(self.ctx, os.fsencode(bam), chrom.encode(), int(minq), int(min_baseq), C.byref(st)))
         return {f[0]: getattr(st, f[0]) for f in RsiBamStats._fields_}
+
+    def set_bam_read(self, mode, chunk_bytes=0):
+        """Where this context's BAM loads read the records from now on (rsi_hot_set_bam_read): "host" / 0, zlib threads and a
+        host walk, or "device" / 1, BGZF inflated and records found on the GPU.  chunk_bytes: inflated bytes per chunk of the
+        device mode (0: the default)."""
+        m = BAM_READ_MODES.get(mode, mode) if isinstance(mode, str) else mode
+        if isinstance(m, str) or isinstance(m, bool):
+            raise ValueError(f"BAM read mode {mode!r}: expected 'host' or 'device'")
+        self._check(self.lib.rsi_hot_set_bam_read(self.ctx, int(m), int(chunk_bytes)))
+
+    def bam_read_stats(self):
+        """The record reader's side of the last BAM load (rsi_hot_last_bam_read_stats): mode ("host" / "device"), and for the
+        device mode chunks, members, segments, guessed, rewalked, passed, t_upload_ms, t_inflate_ms, t_find_ms."""
+        st = RsiBamReadStats()
+        self._check(self.lib.rsi_hot_last_bam_read_stats(self.ctx, C.byref(st)))
+        d = {f[0]: getattr(st, f[0]) for f in RsiBamReadStats._fields_ if f[0] != "pad"}
+        d["mode"] = {v: k for k, v in BAM_READ_MODES.items()}.get(d["mode"], d["mode"])
+        return d
 
     def run_bam(self, params, bam, chrom, fasta, minq=0, min_baseq=13, exclude=None):
         f = np.ascontiguousarray(fasta, dtype=np.uint8)

@@ -16,6 +16,7 @@ class BamFile {
   ~BamFile();
   bool open(const std::string& path, std::string& err);
   uint64_t size() const { return size_; }
+  const uint8_t* bytes() const { return map_; }   // the mapped file (the device reader copies the members' payloads from it)
   // block starting at file offset `off`; false at the end of the file or on a malformed block (err set)
   bool block_at(uint64_t off, BgzfBlock& b, std::string& err) const;
   // raw-deflate payload of a block into out[b.isize]

@@ -63,6 +63,7 @@ struct Options {
   std::string dindex;        // -dindex PATH|none: the .tbi / .csi of a BGZF bedGraph -d FILE for -c RNAME (empty: FILE.tbi, else FILE.csi, when there)
   std::string dindex_path;   // what that gives (main sets it); empty: the whole file is read
   bool trackindex = false;   // -trackindex: FILE.tbi beside every track that is BGZF, built from the device's records
+  std::string bamread;       // -bamread device|host: the BAM's records inflated and found on the GPU (rsi_hot_set_bam_read), or by the host threads (empty: host)
   std::string refread;       // -refread device|host: the reference through the device reader (rsi_ref) or read_fasta (empty: host for text, device for BGZF)
   std::string refindex;      // -refindex PATH|none: the .gzi of a BGZF reference (empty: REFFILE.gzi when there, else the members are walked)
   bool ref_device = false;   // what that gives (main sets it)
@@ -182,6 +183,7 @@ int usage() {
             << "   -trackformat text|bgzf  -track and -bintrack as plain text or as BGZF (default: BGZF when FILE ends in .gz or .bgz)\n"
             << "   -trackindex  write the tabix index FILE.tbi beside every BGZF track, see below\n"
             << "   -dindex PATH|none  the tabix / CSI index of a BGZF bedGraph -d FILE, used with -c RNAME (default: FILE.tbi, else FILE.csi)\n"
+            << "   -bamread device|host  with -b: inflate the BAM's BGZF blocks and find its records on the GPU, or on host threads (default: host)\n"
             << "   -refread device|host  read REFFILE on the GPU, or with the host loop (default: host for plain text, device for BGZF), see below\n"
             << "   -refindex PATH|none  the .gzi of a BGZF REFFILE (default: REFFILE.gzi when there; none: the members are walked)\n"
             << "\nNote:\n"
@@ -293,6 +295,7 @@ void parse(int argc, char** argv, Options& o) {
     else if (s == "-trackindex") o.trackindex = true;
     else if (s == "-dindex") { o.dindex = need(i); ++i; }
     else if (s == "-refread") { o.refread = need(i); ++i; }
+    else if (s == "-bamread") { o.bamread = need(i); ++i; }
     else if (s == "-refindex") { o.refindex = need(i); ++i; }
     else { std::cerr << "unknown option " << s << std::endl; exit(usage()); }
   }
@@ -413,6 +416,9 @@ void process_chromosome(rsi_ctx* ctx, const Options& o, const std::string& chr, 
   const double t1 = now_s();
   if (!arm_exclude(ctx, o, chr, nref, info)) { co.log = info.str(); co.fatal = true; return; }
 
+  if (from_bam && !o.bamread.empty() && rsi_hot_set_bam_read(ctx, o.bamread == "device" ? RSI_BAM_READ_DEVICE : RSI_BAM_READ_HOST, 0) != RSI_OK) {
+    info << rsi_hot_last_error(ctx) << "\n"; co.log = info.str(); co.fatal = true; return;
+  }
   rsi_result* res = nullptr;
   rsi_text_stats ts;
   rsi_bam_stats bs;
@@ -519,6 +525,11 @@ void report_chromosome(rsi_ctx* ctx, const Options& o, const std::string& chr, r
     info << "depth text " << ts->t_total_ms * 1e-3 << " s (" << ts->bytes << " bytes, " << ts->lines << " lines"
          << (ts->fallback ? ", host parser: positions not increasing" : "") << ")";
   info << ", whole device path " << t_path << " s (" << S->t_device_ms << " ms on resident inputs)\n";
+  rsi_bam_read_stats brs;
+  if (from_bam && o.bamread == "device" && rsi_hot_last_bam_read_stats(ctx, &brs) == RSI_OK)
+    info << "#bam: read on the device, " << brs.chunks << " chunks, " << brs.members << " BGZF blocks, " << brs.segments << " segments (" << brs.guessed
+         << " guessed right, " << brs.rewalked << " walked again, " << brs.passed << " passed over), upload " << brs.t_upload_ms << " ms, inflate "
+         << brs.t_inflate_ms << " ms, record finder " << brs.t_find_ms << " ms\n";
   if (from_bam) {   // if ( fp_in ) cnv_stat(fp_in, bamidx, cnvlist), rsi.cpp:2210
     if (rsi_result_annotate_bam(res, o.bamfile.c_str(), chr.c_str()) != RSI_OK) info << "RP / Q0 annotation failed: " << rsi_hot_last_error(nullptr) << "\n";
   }
@@ -958,6 +969,14 @@ int main(int argc, char** argv) {
   }
   if (!o.dindex.empty() && o.dindex != "none" && !bed_one) {
     std::cerr << "rsicnv: -dindex: an index serves -d FILE -c RNAME with a bedGraph FILE in BGZF only" << std::endl;
+    return 1;
+  }
+  if (!o.bamread.empty() && o.bamread != "device" && o.bamread != "host") {
+    std::cerr << "rsicnv: -bamread " << o.bamread << ": expected device or host" << std::endl;
+    return 1;
+  }
+  if (!o.bamread.empty() && !from_bam) {
+    std::cerr << "rsicnv: -bamread device|host: there is no BAM file to read (-b BAMFILE)" << std::endl;
     return 1;
   }
   // -refread, -refindex: the reference's format comes from its first bytes; BGZF goes through the device reader, plain text

@@ -1,7 +1,8 @@
 // ingest.hip -- the two data formats in front of the path: the depth of one chromosome from a
 // text file (load_data_from_text, loaddata.cpp:496-517) or from a BAM (the pileup loop, samfunctions.cpp), built in HBM.
 // The file bytes go through pinned double buffers; parsing, per-read work and the difference-array scan are kernels
-// (kernels_io.hip); BGZF inflation and the record walk stay on host threads (bam_host.cpp).  At the end of the file: the reference
+// (kernels_io.hip); a BAM's BGZF inflation and record walk run on host threads (bam_host.cpp) or, with rsi_hot_set_bam_read's
+// device mode, on the device too (kernels_inflate.hip, kernels_bam.hip).  At the end of the file: the reference
 // reader (rsi_ref), which brings an indexed FASTA, text or BGZF, into HBM through the same chunk source.
 #include "pipeline_internal.h"
 #include "inflate_core.h"
@@ -687,6 +688,157 @@ int upload_fasta(rsi_ctx* ctx, const uint8_t* fasta, int64_t n) {
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return RSI_OK;
 }
+// rsi_hot_load_depth_bam's chunks in RSI_BAM_READ_DEVICE mode.  Per chunk the host walks member headers, copies
+// the deflate payloads into a pinned buffer and builds the member table; upload and launch_inflate_bgzf run on a stream of
+// their own (istream), so the next chunk is inflated while the current chunk's records are found (guess, walk, stitch) and piled
+// up on ctx->stream.  A chunk's members inflate to text_dev[b] + kBamLead; the unfinished record at the end of the chunk before
+// is moved, device to device, right in front of them, so the chunk's stream is contiguous and begins with a record.
+constexpr size_t kBamLead = (size_t(8) << 20) + 64;          // room for a carried record of up to 8 MB (and the guess kernel's word reads)
+constexpr size_t kBamCarryMax = size_t(8) << 20;
+constexpr size_t kBamChunkDefault = size_t(32) << 20, kBamChunkMin = size_t(64) << 10;
+static_assert(kBamCarryMax + kBamChunkDefault + kMemberMax <= (size_t)kBamMaxSegs * RSI_BAM_SEGMENT, "a chunk's segments fit the record finder's buffers");
+static_assert(kBamLead + kBamChunkDefault + kMemberMax + 64 <= kTextChunk, "a chunk fits text_dev");
+
+int bam_chunks_device(rsi_ctx* ctx, const char* bam_path, const rsih::BamFile& bam, const std::vector<std::pair<std::string, int64_t>>& refs,
+                      uint64_t voff, int tid, int64_t n, int minq, int min_baseq, int32_t* d_diff, BamDepthStats* d_stats, rsi_bam_stats* st) {
+  rsi_ctx::BamDev& D = ctx->bamdev;
+  rsi_bam_read_stats& rs = ctx->last_bam_read;
+  rs.mode = RSI_BAM_READ_DEVICE;
+  const size_t chunk = std::min(kBamChunkDefault, std::max(kBamChunkMin, ctx->bam_chunk ? ctx->bam_chunk : kBamChunkDefault));
+  const size_t ccap = chunk + 4 * kMemberMax;
+  if (!D.istream) HIPCHK(hipStreamCreateWithFlags(&D.istream, hipStreamNonBlocking));
+  for (int b = 0; b < 2; ++b) {
+    for (hipEvent_t& e : D.ev[b]) if (!e) HIPCHK(hipEventCreate(&e));
+    if (!D.find[b]) HIPCHK(hipEventCreate(&D.find[b]));
+    HIPCHK(D.cpin[b].ensure(ccap)); HIPCHK(D.cdev[b].ensure(ccap));
+  }
+  HIPCHK(D.wpin.ensure(128)); HIPCHK(D.wdev.ensure(128));
+  HIPCHK(D.guess.ensure((size_t)kBamMaxSegs * 4)); HIPCHK(D.segout.ensure((size_t)kBamMaxSegs * sizeof(BamSegOut)));
+  HIPCHK(D.lists.ensure((size_t)kBamMaxSegs * kBamListCap * 4)); HIPCHK(D.rec.ensure((size_t)kBamMaxSegs * kBamListCap * 4));
+  std::vector<int32_t> reflen(refs.size());
+  for (size_t r = 0; r < refs.size(); ++r) reflen[r] = (int32_t)std::min<int64_t>(std::max<int64_t>(refs[r].second, 0), INT32_MAX);
+  HIPCHK(D.reflen.ensure(reflen.size() * 4));
+  HIPCHK(hipMemcpy(D.reflen.p, reflen.data(), reflen.size() * 4, hipMemcpyHostToDevice));
+  // whatever way the load ends, nothing of it is left running on the context's buffers
+  struct Drain { rsi_ctx* c; ~Drain() { (void)hipStreamSynchronize(c->bamdev.istream); (void)hipStreamSynchronize(c->stream); } } drain{ctx};
+
+  struct Chunk { size_t added = 0; bool eof = false; std::vector<uint64_t> at; } ch[2];
+  bool used[2] = {false, false};
+  uint64_t coff = voff >> 16;            // next member to take
+  std::string perr;
+  // the members of the next chunk into buffer b: payloads and table uploaded, inflate queued, status read back, on istream
+  auto prepare = [&](int b) -> int {
+    Chunk& c = ch[b];
+    c.added = 0; c.eof = false; c.at.clear();
+    std::vector<InflateBlock> tab;
+    uint8_t* cp = D.cpin[b].as<uint8_t>();
+    size_t comp = 0;
+    while (c.added < chunk) {
+      rsih::BgzfBlock blk;
+      std::string e2;
+      if (!bam.block_at(coff, blk, e2)) {
+        if (e2.empty() && coff < bam.size()) e2 = "truncated BGZF block";
+        if (!e2.empty()) { perr = e2 + " at file offset " + std::to_string((unsigned long long)coff) + " of " + bam_path; return RSI_ERR_BAD_ARG; }
+        c.eof = true;
+        break;
+      }
+      if (blk.isize > kMemberMax) { perr = "BGZF: ISIZE above 65536 in the block at file offset " + std::to_string((unsigned long long)coff) + " of " + bam_path; return RSI_ERR_BAD_ARG; }
+      const uint32_t clen = blk.csize - blk.hdr - 8;
+      if (!tab.empty() && comp + clen > ccap) break;
+      const uint8_t* m = bam.bytes() + blk.coff;
+      memcpy(cp + comp, m + blk.hdr, clen);
+      uint32_t crc;
+      memcpy(&crc, m + blk.csize - 8, 4);
+      tab.push_back(InflateBlock{(long long)comp, (long long)(kBamLead + c.added), clen, blk.isize, crc, 0});
+      c.at.push_back(coff);
+      comp += clen; c.added += blk.isize; coff += blk.csize;
+      st->bytes_compressed += blk.csize;
+    }
+    if (tab.empty()) return RSI_OK;
+    rs.members += (int64_t)tab.size();
+    const size_t tb = tab.size() * sizeof(InflateBlock);
+    if (D.tpin[b].ensure(tb) != hipSuccess || D.tdev[b].ensure(tb) != hipSuccess) { perr = "out of memory for the BGZF member table"; return RSI_ERR_HIP; }
+    memcpy(D.tpin[b].p, tab.data(), tb);
+    char* w = D.wdev.as<char>() + 64 * b;
+    hipStream_t s = D.istream;
+    hipError_t e = used[b] ? hipStreamWaitEvent(s, D.ev[b][3], 0) : hipSuccess;   // text_dev[b]'s chunk before is piled up
+    if (e == hipSuccess) e = hipEventRecord(D.ev[b][0], s);
+    if (e == hipSuccess) e = hipMemcpyAsync(D.cdev[b].p, cp, comp, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(D.tdev[b].p, D.tpin[b].p, tb, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemsetAsync(w, 0xff, 16, s);     // the status word; last_nl (unused here) starts at -1
+    if (e == hipSuccess) e = hipEventRecord(D.ev[b][1], s);
+    if (e != hipSuccess) { perr = std::string("BAM device read: ") + hipGetErrorString(e); return RSI_ERR_HIP; }
+    launch_inflate_bgzf(D.cdev[b].p, D.tdev[b].as<InflateBlock>(), (int)tab.size(), ctx->text_dev[b].p, reinterpret_cast<int*>(w + 8),
+                        reinterpret_cast<unsigned long long*>(w), s);
+    e = hipMemcpyAsync(D.wpin.as<char>() + 64 * b, w, 16, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipEventRecord(D.ev[b][2], s);
+    if (e != hipSuccess) { perr = std::string("BAM device read: ") + hipGetErrorString(e); return RSI_ERR_HIP; }
+    return RSI_OK;
+  };
+
+  size_t skip = (size_t)(voff & 0xffff); // bytes of the first member in front of the first record
+  size_t carry = 0;                      // bytes of the unfinished record in front of the current chunk's members
+  int cur = 0;
+  if (int rc = prepare(0)) return fail(ctx, rc, perr);
+  for (;;) {
+    Chunk& c = ch[cur];
+    const int other = cur ^ 1;
+    const bool more = !c.eof;
+    if (more) if (int rc = prepare(other)) return fail(ctx, rc, perr);
+    if (!c.at.empty()) {
+      const double tq = now_ms();
+      HIPCHK(event_wait(D.ev[cur][2]));
+      st->t_wait_ms += now_ms() - tq;
+      float ms = 0;
+      if (hipEventElapsedTime(&ms, D.ev[cur][0], D.ev[cur][1]) == hipSuccess) rs.t_upload_ms += ms;
+      if (hipEventElapsedTime(&ms, D.ev[cur][1], D.ev[cur][2]) == hipSuccess) { rs.t_inflate_ms += ms; st->t_inflate_ms += ms; }
+      unsigned long long status;
+      memcpy(&status, D.wpin.as<char>() + 64 * cur, 8);
+      if (status != ~0ull) {
+        const size_t k = (size_t)(status >> 8);
+        return fail(ctx, RSI_ERR_BAD_ARG, "BGZF: the block at file offset " + std::to_string(k < c.at.size() ? (unsigned long long)c.at[k] : 0ull) + " of " + bam_path +
+                                              " is bad: " + rsinf::err_name((int)(status & 0xff)));
+      }
+      ++rs.chunks;
+      st->bytes_inflated += (int64_t)c.added;
+    }
+    if (skip > c.added) return fail(ctx, RSI_ERR_BAD_ARG, "the first record's offset lies behind its BGZF block");
+    const size_t base = kBamLead - carry + skip, total = carry + c.added - skip;
+    skip = 0;
+    const uint8_t* data = ctx->text_dev[cur].as<uint8_t>() + base;
+    BamFindReport rep{};
+    if (bam_segments((long long)total) > kBamMaxSegs) return fail(ctx, RSI_ERR_INTERNAL, "BAM device read: a chunk has more segments than the record finder takes");
+    if (total > 0) {
+      char* w = D.wdev.as<char>() + 64 * cur;
+      BamFindReport* d_rep = reinterpret_cast<BamFindReport*>(w + 16);
+      HIPCHK(hipEventRecord(D.find[0], ctx->stream));
+      { Timer t(ctx, "bam_guess"); launch_bam_guess(data, (long long)total, (int)reflen.size(), D.reflen.as<int32_t>(), D.guess.as<uint32_t>(), ctx->stream); }
+      { Timer t(ctx, "bam_walk"); launch_bam_walk(data, (long long)total, tid, D.guess.as<uint32_t>(), D.segout.as<BamSegOut>(), D.lists.as<uint32_t>(), ctx->stream); }
+      { Timer t(ctx, "bam_stitch"); launch_bam_stitch(data, (long long)total, tid, D.guess.as<uint32_t>(), D.segout.as<BamSegOut>(), D.lists.as<uint32_t>(), D.rec.as<uint32_t>(), d_rep, ctx->stream); }
+      HIPCHK(hipEventRecord(D.find[1], ctx->stream));
+      HIPCHK(hipMemcpyAsync(D.wpin.as<char>() + 64 * cur + 16, d_rep, sizeof(BamFindReport), hipMemcpyDeviceToHost, ctx->stream));
+      { const double tq = now_ms(); HIPCHK(CTX_SYNC()); st->t_wait_ms += now_ms() - tq; }
+      memcpy(&rep, D.wpin.as<char>() + 64 * cur + 16, sizeof(rep));
+      float ms = 0;
+      if (hipEventElapsedTime(&ms, D.find[0], D.find[1]) == hipSuccess) { rs.t_find_ms += ms; st->t_walk_ms += ms; }
+      rs.segments += bam_segments((long long)total); rs.guessed += rep.guessed; rs.rewalked += rep.rewalked; rs.passed += rep.passed;
+      st->records += rep.seen; st->on_chrom += rep.listed;
+      if (rep.flags & rsibam::kBad) return fail(ctx, RSI_ERR_BAD_ARG, "malformed BAM record");
+      if (rep.end > total || rep.listed > (uint32_t)kBamMaxSegs * kBamListCap) return fail(ctx, RSI_ERR_INTERNAL, "BAM device read: the record finder's report is out of range");
+      if (rep.listed) { Timer t(ctx, "bam_depth"); launch_bam_depth(data, D.rec.as<uint32_t>(), (int)rep.listed, tid, minq, min_baseq, (long long)n, d_diff, d_stats, ctx->stream); }
+    }
+    const bool finished = (rep.flags & rsibam::kBeyond) || !more;
+    carry = finished ? 0 : total - rep.end;
+    if (carry > kBamCarryMax) return fail(ctx, RSI_ERR_UNSUPPORTED, "a BAM record is longer than 8 MB");
+    if (carry) HIPCHK(hipMemcpyAsync(ctx->text_dev[other].as<uint8_t>() + kBamLead - carry, data + rep.end, carry, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(hipEventRecord(D.ev[cur][3], ctx->stream));
+    used[cur] = true;
+    if (finished) break;
+    cur = other;
+  }
+  return RSI_OK;
+}
+
 // rsi_hot_run_text and rsi_hot_run_text_dfasta: exactly one of fasta (host) and d_fasta (HBM) is set
 int run_text(rsi_ctx* ctx, const rsi_params* p, const char* depth_path, const uint8_t* fasta, const void* d_fasta, int64_t n, rsi_result** out,
              rsi_text_stats* stats) {
@@ -742,6 +894,7 @@ int rsi_hot_load_depth_bam(rsi_ctx* ctx, const char* bam_path, const char* chrom
   rsi_bam_stats* st = stats ? stats : &local;
   memset(st, 0, sizeof(*st));
   if (!ctx || !bam_path || !chrom) return fail(ctx, RSI_ERR_BAD_ARG, "null argument");
+  ctx->last_bam_read = rsi_bam_read_stats{};
   const double t0 = now_ms();
   HIPCHK(hipSetDevice(ctx->device));
   std::string err;
@@ -773,6 +926,21 @@ int rsi_hot_load_depth_bam(rsi_ctx* ctx, const char* bam_path, const char* chrom
   uint8_t* wsb = ctx->text_wg.as<uint8_t>();
   BamDepthStats* d_stats = reinterpret_cast<BamDepthStats*>(wsb + stats_off);
   HIPCHK(hipMemsetAsync(d_stats, 0, sizeof(BamDepthStats), ctx->stream));
+
+  // behind the last chunk, in either mode: the difference array scanned into the depth, the pileup's counts
+  auto finish = [&]() -> int {
+    { Timer t(ctx, "depth_scan"); launch_inclusive_scan_i32(d_diff, (long long)n, reinterpret_cast<int32_t*>(wsb + scan_off), ctx->stream); }
+    BamDepthStats hs;
+    HIPCHK(hipMemcpyAsync(&hs, d_stats, sizeof(hs), hipMemcpyDeviceToHost, ctx->stream));
+    { const double tq = now_ms(); HIPCHK(hipStreamSynchronize(ctx->stream)); st->t_wait_ms += now_ms() - tq; }
+    st->used = (int64_t)hs.used; st->runs = (int64_t)hs.runs; st->malformed = (int64_t)hs.malformed;
+    st->t_total_ms = now_ms() - t0;
+    return RSI_OK;
+  };
+  if (ctx->bam_read == RSI_BAM_READ_DEVICE) {
+    if (int rc = bam_chunks_device(ctx, bam_path, bam, refs, voff, tid, n, minq, min_baseq, d_diff, d_stats, st)) return rc;
+    return finish();
+  }
 
   hipEvent_t done[2] = {nullptr, nullptr};
   for (int b = 0; b < 2; ++b) if (hipEventCreateWithFlags(&done[b], hipEventDisableTiming) != hipSuccess) return fail(ctx, RSI_ERR_HIP, "hipEventCreate failed");
@@ -918,12 +1086,19 @@ int rsi_hot_load_depth_bam(rsi_ctx* ctx, const char* bam_path, const char* chrom
     if (!more) finished = true;
     cur = other;
   }
-  { Timer t(ctx, "depth_scan"); launch_inclusive_scan_i32(d_diff, (long long)n, reinterpret_cast<int32_t*>(wsb + scan_off), ctx->stream); }
-  BamDepthStats hs;
-  HIPCHK(hipMemcpyAsync(&hs, d_stats, sizeof(hs), hipMemcpyDeviceToHost, ctx->stream));
-  { const double tq = now_ms(); HIPCHK(hipStreamSynchronize(ctx->stream)); st->t_wait_ms += now_ms() - tq; }
-  st->used = (int64_t)hs.used; st->runs = (int64_t)hs.runs; st->malformed = (int64_t)hs.malformed;
-  st->t_total_ms = now_ms() - t0;
+  return finish();
+}
+
+int rsi_hot_set_bam_read(rsi_ctx* ctx, int mode, size_t chunk_bytes) {
+  if (!ctx) return fail(ctx, RSI_ERR_BAD_ARG, "null context");
+  if (mode != RSI_BAM_READ_HOST && mode != RSI_BAM_READ_DEVICE) return fail(ctx, RSI_ERR_BAD_ARG, "BAM read mode must be RSI_BAM_READ_HOST or RSI_BAM_READ_DEVICE");
+  ctx->bam_read = mode;
+  ctx->bam_chunk = chunk_bytes;
+  return RSI_OK;
+}
+int rsi_hot_last_bam_read_stats(const rsi_ctx* ctx, rsi_bam_read_stats* out) {
+  if (!ctx || !out) return RSI_ERR_BAD_ARG;
+  *out = ctx->last_bam_read;
   return RSI_OK;
 }
 

@@ -7,6 +7,7 @@
 #include <stdint.h>
 #include <mutex>
 #include "device_util.h"
+#include "bam_walk_core.h"
 
 namespace rsik {
 
@@ -551,6 +552,23 @@ void launch_bam_depth(const void* data, const uint32_t* rec_off, int nrec, int t
                       BamDepthStats* stats, hipStream_t stream);
 int scan_tiles(long long n);
 void launch_inclusive_scan_i32(int32_t* x, long long n, int32_t* tile_scratch, hipStream_t stream);
+
+// ---- BAM records found on the device (kernels_bam.hip, bam_walk_core.h) ----
+// data[0, len): a chunk of inflated BAM bytes whose byte 0 starts a record, cut into segments of RSI_BAM_SEGMENT bytes.  The three launches, in this order on one stream, leave in rec_off[] the ascending offsets of the whole
+// records of `tid` on the chain from 0 -- what launch_bam_depth takes -- and in *report their number and where and why the chain
+// stopped.  guess: bam_segments(len) words; out: as many BamSegOut; lists: bam_segments(len) * kBamListCap words; reflen[nref]:
+// the header's reference lengths.  The buffer behind data must be readable 3 bytes in front of data and 3 bytes behind data + len
+// (the guess stages whole words).
+#define RSI_BAM_SEGMENT 16384
+constexpr int kBamMaxSegs = 3072;                           // 48 MB: what the loader's buffers (guess, out, lists, rec_off) are laid out for
+constexpr int kBamListCap = RSI_BAM_SEGMENT / 36 + 1;       // a record has at least 36 bytes
+using BamSegOut = rsibam::SegOut;
+using BamFindReport = rsibam::Report;
+int bam_segments(long long len);
+void launch_bam_guess(const void* data, long long len, int nref, const int32_t* reflen, uint32_t* guess, hipStream_t stream);
+void launch_bam_walk(const void* data, long long len, int tid, const uint32_t* guess, BamSegOut* out, uint32_t* lists, hipStream_t stream);
+void launch_bam_stitch(const void* data, long long len, int tid, const uint32_t* guess, const BamSegOut* out, uint32_t* lists, uint32_t* rec_off,
+                       BamFindReport* report, hipStream_t stream);
 
 // ---- depth track: an int32 array as bedGraph text, run-length encoded and formatted on the device (kernels_track.hip) ----
 // One line "NAME \t pos0+start \t pos0+end \t value \n" per maximal run of equal values of v[0, n), worked through in slices

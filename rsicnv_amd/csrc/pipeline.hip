@@ -1551,6 +1551,11 @@ void rsi_hot_destroy(rsi_ctx* ctx) {
   if (ctx->mailbox) (void)hipHostFree(ctx->mailbox);
   for (int b = 0; b < 2; ++b) if (ctx->text_pin[b]) (void)hipHostFree(ctx->text_pin[b]);
   track_free(ctx);
+  for (int b = 0; b < 2; ++b) {
+    for (hipEvent_t e : ctx->bamdev.ev[b]) if (e) (void)hipEventDestroy(e);
+    if (ctx->bamdev.find[b]) (void)hipEventDestroy(ctx->bamdev.find[b]);
+  }
+  if (ctx->bamdev.istream) (void)hipStreamDestroy(ctx->bamdev.istream);
   if (ctx->sync_ev) (void)hipEventDestroy(ctx->sync_ev);
   if (ctx->copy_ev) (void)hipEventDestroy(ctx->copy_ev);   // (copy_stream is the device's shared one: never destroyed)
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);

@@ -152,6 +152,18 @@ struct rsi_ctx {
   char* text_pin[2] = {nullptr, nullptr};    // pinned staging for the file bytes
   size_t text_pin_cap = 0;
   rsi_inflate_stats last_inflate{};          // format and inflate figures of the last text load (rsi_hot_last_inflate_stats)
+  // BAM read on the device (rsi_hot_set_bam_read; ingest.hip): the mode, the chunk size (0: default), the
+  // last load's figures, and the mode's own buffers and stream, made by its first load
+  int bam_read = RSI_BAM_READ_HOST;
+  size_t bam_chunk = 0;
+  rsi_bam_read_stats last_bam_read{};
+  struct BamDev {
+    PinBuf cpin[2], tpin[2], wpin;             // compressed payloads, member tables, status words + reports
+    DevBuf cdev[2], tdev[2], wdev, guess, segout, lists, rec, reflen;
+    hipStream_t istream = nullptr;             // uploads and inflates, beside the record kernels on `stream`
+    hipEvent_t ev[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};   // per buffer: upload begins, inflate begins, inflate ends, its depth launch is through
+    hipEvent_t find[2] = {nullptr, nullptr};   // around the record finder
+  } bamdev;
   int64_t n_in = 0;                          // length of the depth currently in in_depth
   DevBuf gcbits, nbits, rd_gc, rdc, binmed, binsum, tnb, tmed, first_del;
   DevBuf depth8, rescaled8;   // byte copies: the raw depth (K2 writes it, K3' streams it), the rescaled depth (K3' -> K4')

@@ -1,28 +1,127 @@
-"""BAM -> depth rate: a synthetic paired-end BAM for an N Mb chromosome at COV x, then the library's
-loader (host inflate threads + device pileup) timed.  Usage: python tools/bam_ingest_bench.py [Mb=10] [cov=30]"""
-import os, sys, time, tempfile
+"""BAM -> depth rate: a synthetic BAM for an N Mb chromosome at COV x, then the library's loader
+timed -- with the records read on the host (zlib threads + host walk) or on the device (BGZF inflated and records found
+there), by one context or by K contexts of one GPU that load the same file at once, each from its own thread.
+
+  python tools/bam_ingest_bench.py [Mb=10] [cov=30] [--read host|device|both] [--loaders 1,4,8] [--reps 3] [--out FILE.json]
+
+Per (mode, K): the wall time of the K concurrent loads (best of --reps, after one untimed round that allocates the buffers),
+GB/s of compressed and of inflated bytes over all loaders, and the loaders' mean upload / inflate / record-finder times (HIP
+events) and segment counts."""
+import argparse, json, os, struct, sys, tempfile, threading, time, zlib
+from concurrent.futures import ThreadPoolExecutor
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 import numpy as np
 import bam_util as bu
 from rsicnv_amd import api
 
-mb = float(sys.argv[1]) if len(sys.argv) > 1 else 10
-cov = float(sys.argv[2]) if len(sys.argv) > 2 else 30
-n = int(mb * 1e6)
-depth = np.full(n, cov, dtype=np.float64)
-t0 = time.time()
-recs = bu.paired_reads_following_depth(depth, n)
-d = tempfile.mkdtemp(dir="/tmp")
-bam = os.path.join(d, "x.bam")
-bu.write_bam(bam, [("chrS", n)], recs)
-print(f"wrote {len(recs)} reads, {os.path.getsize(bam)/1e6:.0f} MB compressed in {time.time()-t0:.0f} s", flush=True)
-h = api.RsiHot(0)
-for rep in range(3):
-    st = h.load_depth_bam(bam, "chrS")
-    print(f"loader: {st['t_total_ms']:.0f} ms total ({st['bytes_compressed']/1e6:.0f} MB compressed -> {st['bytes_inflated']/1e6:.0f} MB, "
-          f"{st['records']} reads, {st['runs']} runs; inflate {st['t_inflate_ms']:.0f} ms, walk {st['t_walk_ms']:.0f} ms, device wait {st['t_wait_ms']:.0f} ms) = {n/st['t_total_ms']/1e3:.1f} Mbases/s of chromosome, "
-          f"{st['records']/st['t_total_ms']/1e3:.2f} M reads/s, {st['bytes_compressed']/st['t_total_ms']/1e6:.2f} GB/s compressed", flush=True)
-rd = h.fetch("depth_in")
-print("mean depth", rd.mean())
-os.remove(bam); os.rmdir(d)
+
+def synth_bam(path, n, cov, read_len=100, seed=7):
+    """Sorted single-end reads, read_len M, random qualities 14..40, written as BGZF blocks of 0xff00 bytes cut wherever
+    that falls (built as one byte array: a per-read Python loop takes minutes at this size)."""
+    rng = np.random.default_rng(seed)
+    nreads = int(n * cov / read_len)
+    pos = np.sort(rng.integers(1, n - read_len, nreads)).astype("<i4")
+    L = read_len
+    size = 4 + 32 + 9 + 4 + (L + 1) // 2 + L
+    a = np.zeros((nreads, size), dtype=np.uint8)
+    def put(col, fmt, values):
+        v = np.asarray(values).astype(fmt)
+        a[:, col:col + v.dtype.itemsize] = v.view(np.uint8).reshape(nreads, v.dtype.itemsize)
+    put(0, "<i4", np.full(nreads, size - 4))
+    put(4, "<i4", np.zeros(nreads))                       # refID
+    put(8, "<i4", pos)
+    a[:, 12] = 9                                          # l_read_name
+    a[:, 13] = rng.integers(20, 61, nreads)               # mapq
+    put(14, "<u2", np.full(nreads, 4681))                 # bin (not read by the loader)
+    put(16, "<u2", np.ones(nreads))                       # n_cigar_op
+    put(20, "<i4", np.full(nreads, L))
+    put(24, "<i4", np.full(nreads, -1)); put(28, "<i4", np.full(nreads, -1))
+    names = np.char.zfill(np.arange(nreads).astype("U8"), 8).astype("S8")
+    a[:, 36:44] = names.view(np.uint8).reshape(nreads, 8)
+    put(45, "<u4", np.full(nreads, L << 4))
+    a[:, 49:49 + (L + 1) // 2] = 0x11
+    a[:, 49 + (L + 1) // 2:] = rng.integers(14, 41, (nreads, L), dtype=np.uint8)
+    data = a.tobytes()
+    text = f"@HD\tVN:1.0\tSO:coordinate\n@SQ\tSN:chrS\tLN:{n}\n"
+    hdr = b"BAM\1" + struct.pack("<i", len(text)) + text.encode() + struct.pack("<i", 1) + struct.pack("<i", 5) + b"chrS\0" + struct.pack("<i", n)
+    step = bu.BGZF_MAX_PAYLOAD
+    with ThreadPoolExecutor(16) as ex, open(path, "wb") as f:
+        f.write(bu._bgzf_block(hdr))
+        for blk in ex.map(lambda o: bu._bgzf_block(data[o:o + step]), range(0, len(data), step)):
+            f.write(blk)
+        f.write(bu._bgzf_block(b""))
+    return nreads, len(data)
+
+
+def measure(ctxs, bam, mode, reps):
+    for h in ctxs:
+        h.set_bam_read(mode)
+    best = None
+    for rep in range(reps + 1):
+        out = [None] * len(ctxs)
+        gate = threading.Barrier(len(ctxs) + 1)
+        def work(i):
+            gate.wait()
+            st = ctxs[i].load_depth_bam(bam, "chrS")
+            out[i] = (st, ctxs[i].bam_read_stats())
+        th = [threading.Thread(target=work, args=(i,)) for i in range(len(ctxs))]
+        for t in th: t.start()
+        gate.wait()
+        t0 = time.perf_counter()
+        for t in th: t.join()
+        wall = (time.perf_counter() - t0) * 1e3
+        if rep and (best is None or wall < best[0]):      # round 0 allocates
+            best = (wall, out)
+    wall, out = best
+    k = len(ctxs)
+    mean = lambda f: float(np.mean([f(o) for o in out]))
+    return {"mode": mode, "loaders": k, "wall_ms": wall,
+            "gbps_compressed": k * out[0][0]["bytes_compressed"] / wall / 1e6, "gbps_inflated": k * out[0][0]["bytes_inflated"] / wall / 1e6,
+            "loader_ms": mean(lambda o: o[0]["t_total_ms"]), "wait_ms": mean(lambda o: o[0]["t_wait_ms"]),
+            "inflate_ms": mean(lambda o: o[0]["t_inflate_ms"]), "walk_ms": mean(lambda o: o[0]["t_walk_ms"]),
+            "upload_ms": mean(lambda o: o[1]["t_upload_ms"]), "find_ms": mean(lambda o: o[1]["t_find_ms"]),
+            "chunks": out[0][1]["chunks"], "members": out[0][1]["members"], "segments": out[0][1]["segments"],
+            "guessed": out[0][1]["guessed"], "rewalked": out[0][1]["rewalked"], "passed": out[0][1]["passed"],
+            "records": out[0][0]["records"], "used": out[0][0]["used"], "runs": out[0][0]["runs"]}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("mb", nargs="?", type=float, default=10)
+    ap.add_argument("cov", nargs="?", type=float, default=30)
+    ap.add_argument("--read", default="host", choices=["host", "device", "both"])
+    ap.add_argument("--loaders", default="1")
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--out")
+    a = ap.parse_args()
+    n = int(a.mb * 1e6)
+    d = tempfile.mkdtemp()
+    bam = os.path.join(d, "x.bam")
+    t0 = time.time()
+    nreads, inflated = synth_bam(bam, n, a.cov)
+    print(f"wrote {nreads} reads, {os.path.getsize(bam) / 1e6:.0f} MB compressed ({inflated / 1e6:.0f} MB inflated) in {time.time() - t0:.0f} s", flush=True)
+    ks = [int(k) for k in a.loaders.split(",")]
+    ctxs = [api.RsiHot(0) for _ in range(max(ks))]
+    rows, depth = [], {}
+    for mode in (["host", "device"] if a.read == "both" else [a.read]):
+        for k in ks:
+            r = measure(ctxs[:k], bam, mode, a.reps)
+            rows.append(r)
+            print(json.dumps(r), flush=True)
+        depth[mode] = ctxs[0].fetch("depth_in").copy()
+    if len(depth) == 2:
+        assert np.array_equal(depth["host"], depth["device"]), "the two modes disagree"
+    print("mean depth", float(next(iter(depth.values())).mean()))
+    result = {"chromosome_mb": a.mb, "coverage": a.cov, "reads": nreads, "bytes_compressed": os.path.getsize(bam), "bytes_inflated": inflated,
+              "cpus": len(os.sched_getaffinity(0)), "omp_num_threads": os.environ.get("OMP_NUM_THREADS"), "rows": rows}
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(result, f, indent=1)
+    for h in ctxs:
+        h.close()
+    os.remove(bam); os.rmdir(d)
+
+
+if __name__ == "__main__":
+    main()

@@ -282,6 +282,40 @@ int rsi_hot_last_bam_read_stats(const rsi_ctx* ctx, rsi_bam_read_stats* out);
  * defaults (-1) there. */
 int rsi_result_annotate_bam(rsi_result* r, const char* bam_path, const char* chrom);
 int rsi_result_pairs(const rsi_result* r, int i, int32_t* rp, double* q0);
+/* ---- The same annotation on the device, with no second pass over the BAM ----
+ * rsi_hot_set_bam_pairs(ctx, 1) arms the context's BAM loads from now on (off when never called; 0 disarms): beside the pileup,
+ * in either read mode, a load then keeps five int32 words per read of the chromosome in HBM -- the pair table, entry k = record
+ * k in file order: pos, rend (bam_calend, or pos + 1 without CIGAR), mpos, isize, and info = mapq | flag << 8 | cigar class (0,
+ * 1, 2 for two or more operations) << 24 | (mtid != tid && mtid > 0) << 26 | (mtid == tid) << 27 -- 20 bytes per read, held
+ * until the context's next BAM load; rsi_hot_fetch_i32 reads the arrays as "pairs_pos", "pairs_rend", "pairs_mpos",
+ * "pairs_isize", "pairs_info".  An unarmed load allocates nothing and launches nothing for it.
+ * rsi_result_annotate_device fills the result's RP / Q0 from that table exactly as rsi_result_annotate_bam does from the file
+ * (same integers, same doubles): it needs an armed load of the result's chromosome still held by ctx, no .bai and no file.
+ * It refuses what the host pass cannot make sense of either: a table whose positions are not ascending (RSI_ERR_UNSUPPORTED,
+ * "BAM not sorted by position") and one with a record whose name and CIGAR overrun its block_size (RSI_ERR_BAD_ARG, the host
+ * reader's message) -- the latter wherever the record lies, where the host fails only if it reads it. */
+int rsi_hot_set_bam_pairs(rsi_ctx* ctx, int on);
+int rsi_result_annotate_device(rsi_ctx* ctx, rsi_result* r);
+typedef struct rsi_pairs_stats {
+  int64_t records, table_bytes;     /* entries of the pair table the context holds and their bytes; 0 / 0: no table */
+  int64_t maxspan;                  /* the largest rend - pos */
+  int64_t sample_count, sample_abs, sample_sq, sample_stop;   /* the insert-size sample: proper pairs, sum |isize|, sum of the
+                                       squares wrapped to int32, and S, the index among the sampled reads at which it stopped */
+  int32_t isize, isize_sd;          /* bam_pair_sample's results from those sums (-1 / -1 with fewer than three pairs) */
+  int64_t calls, examined;          /* calls annotated; table entries their workgroups looked at */
+  double t_table_ms, t_sample_ms, t_annotate_ms;   /* HIP events: the load's k_bam_pairs launches, the sample, the annotation */
+} rsi_pairs_stats;
+/* of the context's last armed load and its last rsi_result_annotate_device (the sample and annotation fields 0 before one) */
+int rsi_hot_last_pairs_stats(const rsi_ctx* ctx, rsi_pairs_stats* out);
+/* Test hooks: a table from the caller in place of a BAM's (n entries, five arrays as above; the context's own table is dropped).
+ * rsi_hot_debug_pair_sample: the insert-size sample over it, out[4] = count, sum |isize|, sum of wrapped squares, S (-1: no
+ * read sampled).  rsi_hot_debug_pair_annotate: the counts of ncalls calls (start, end, type as in rsi_call) with the windows
+ * rsi_result_annotate_device gives them; the table must be ascending in pos. */
+int rsi_hot_debug_pair_sample(rsi_ctx* ctx, int64_t n, const int32_t* pos, const int32_t* rend, const int32_t* mpos, const int32_t* isize,
+                              const int32_t* info, int64_t tid_len, int64_t* out);
+int rsi_hot_debug_pair_annotate(rsi_ctx* ctx, int64_t n, const int32_t* pos, const int32_t* rend, const int32_t* mpos, const int32_t* isize,
+                                const int32_t* info, int ncalls, const int32_t* start, const int32_t* end, const int32_t* type,
+                                int isize_mean, int isize_sd, uint32_t* rp_out, uint32_t* q0all_out, uint32_t* q0q0_out);
 /* Fixed-layout summary of a chromosome's result for the one exchange of a multi-GPU run (the gather of per-chromosome
  * results that replaces the reference's sequential output loop, rsi.cpp:1594-1608):
  *   out[0..7]  = chromosome id (the caller's), chromosome median, SD, number of final calls, number stored here, 0, 0, 0

@@ -72,6 +72,8 @@ EXPORTS = ["rsi_default_params", "rsi_hot_create", "rsi_hot_destroy", "rsi_hot_l
            "rsi_ref_index_path", "rsi_ref_load_device", "rsi_ref_load_host", "rsi_ref_device_alloc", "rsi_ref_device_free",
            "rsi_hot_run_text_dfasta", "rsi_hot_run_bam_dfasta",
            "rsi_hot_set_bam_read", "rsi_hot_last_bam_read_stats",
+           "rsi_hot_set_bam_pairs", "rsi_result_annotate_device", "rsi_hot_last_pairs_stats", "rsi_hot_debug_pair_sample",
+           "rsi_hot_debug_pair_annotate",
            "rsi_ref_debug_set_chunks", "rsi_ref_debug_fai_line", "rsi_ref_debug_ranges", "rsi_ref_debug_gzi", "rsi_ref_debug_cover"]
 
 
@@ -158,6 +160,13 @@ class RsiBamReadStats(C.Structure):
     _fields_ = [("mode", C.c_int32), ("pad", C.c_int32), ("chunks", C.c_int64), ("members", C.c_int64), ("segments", C.c_int64),
                 ("guessed", C.c_int64), ("rewalked", C.c_int64), ("passed", C.c_int64),
                 ("t_upload_ms", C.c_double), ("t_inflate_ms", C.c_double), ("t_find_ms", C.c_double)]
+
+
+class RsiPairsStats(C.Structure):
+    _fields_ = [("records", C.c_int64), ("table_bytes", C.c_int64), ("maxspan", C.c_int64), ("sample_count", C.c_int64),
+                ("sample_abs", C.c_int64), ("sample_sq", C.c_int64), ("sample_stop", C.c_int64), ("isize", C.c_int32),
+                ("isize_sd", C.c_int32), ("calls", C.c_int64), ("examined", C.c_int64),
+                ("t_table_ms", C.c_double), ("t_sample_ms", C.c_double), ("t_annotate_ms", C.c_double)]
 
 
 BAM_READ_MODES = {"host": 0, "device": 1}
@@ -302,6 +311,13 @@ def load_library():
     L.rsi_hot_last_deflate_stats.argtypes = [C.c_void_p, C.POINTER(RsiDeflateStats)]
     L.rsi_hot_set_bam_read.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
     L.rsi_hot_last_bam_read_stats.argtypes = [C.c_void_p, C.POINTER(RsiBamReadStats)]
+    L.rsi_hot_set_bam_pairs.argtypes = [C.c_void_p, C.c_int]
+    L.rsi_result_annotate_device.argtypes = [C.c_void_p, C.c_void_p]
+    L.rsi_result_annotate_bam.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
+    L.rsi_result_pairs.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double)]
+    L.rsi_hot_last_pairs_stats.argtypes = [C.c_void_p, C.POINTER(RsiPairsStats)]
+    L.rsi_hot_debug_pair_sample.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p]
+    L.rsi_hot_debug_pair_annotate.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 3
     L.rsi_bgzf_write_eof.argtypes = [C.c_char_p]
     L.rsi_track_index_create.argtypes = []
     L.rsi_track_index_create.restype = C.c_void_p
@@ -539,6 +555,22 @@ class Result:
         then 8 doubles per stored call) into a float64 numpy row; returns the number of doubles written."""
         assert row.dtype == np.float64 and row.flags["C_CONTIGUOUS"] and row.size >= SUMMARY_HEAD + SUMMARY_CALL * max_calls
         return self._lib.rsi_result_summary(self._h, int(chrom_id), row.ctypes.data, int(max_calls))
+
+    def annotate_bam(self, bam, chrom):
+        """RP / Q0 of the final calls from the BAM file and its .bai, on the host (rsi_result_annotate_bam)."""
+        rc = self._lib.rsi_result_annotate_bam(self._h, os.fsencode(bam), chrom.encode())
+        if rc != RSI_OK:
+            raise RsiError(rc, self._lib.rsi_hot_last_error(None).decode())
+        self._rows = None
+
+    def pairs(self):
+        """(rp, q0) of every final call (rsi_result_pairs): -1 / -1.0 before an annotation."""
+        out = []
+        rp, q0 = C.c_int32(0), C.c_double(0.0)
+        for i in range(self._lib.rsi_result_ncalls(self._h, WHICH["calls"])):
+            self._lib.rsi_result_pairs(self._h, i, C.byref(rp), C.byref(q0))
+            out.append((rp.value, q0.value))
+        return out
 
     def log_lines(self):
         """The per-L "DEL-" / "DUP+" lines of the scan passes (rsi.cpp:1221-1224, 1251-1254)."""
@@ -838,6 +870,47 @@ class RsiHot:
         if isinstance(m, str) or isinstance(m, bool):
             raise ValueError(f"BAM read mode {mode!r}: expected 'host' or 'device'")
         self._check(self.lib.rsi_hot_set_bam_read(self.ctx, int(m), int(chunk_bytes)))
+
+    def set_bam_pairs(self, on=True):
+        """Arm (or disarm) this context's BAM loads to keep the pair table in HBM (rsi_hot_set_bam_pairs): what annotate_device
+        needs.  fetch("pairs_pos" / "pairs_rend" / "pairs_mpos" / "pairs_isize" / "pairs_info") reads an armed load's table."""
+        self._check(self.lib.rsi_hot_set_bam_pairs(self.ctx, int(bool(on))))
+
+    def annotate_device(self, res):
+        """RP / Q0 of the final calls of `res` from the pair table of the context's last armed load (rsi_result_annotate_device)."""
+        self._check(self.lib.rsi_result_annotate_device(self.ctx, res._h))
+        res._rows = None
+
+    def pairs_stats(self):
+        """The pair table of the last armed load and the last annotate_device (rsi_hot_last_pairs_stats); records == 0: no table."""
+        st = RsiPairsStats()
+        self._check(self.lib.rsi_hot_last_pairs_stats(self.ctx, C.byref(st)))
+        return {f[0]: getattr(st, f[0]) for f in RsiPairsStats._fields_}
+
+    @staticmethod
+    def _pair_arrays(table):
+        arrs = [np.ascontiguousarray(np.asarray(a).astype(np.int64) & 0xffffffff, dtype=np.uint32).view(np.int32) for a in table]
+        assert len(arrs) == 5 and all(a.ndim == 1 and a.size == arrs[0].size for a in arrs)
+        return arrs
+
+    def debug_pair_sample(self, table, tid_len):
+        """The insert-size sample over a caller's pair table (test hook, rsi_hot_debug_pair_sample): table = (pos, rend, mpos,
+        isize, info).  Returns [count, sum |isize|, sum of wrapped squares, S]."""
+        arrs = self._pair_arrays(table)
+        out = np.zeros(4, dtype=np.int64)
+        self._check(self.lib.rsi_hot_debug_pair_sample(self.ctx, arrs[0].size, *[a.ctypes.data for a in arrs], int(tid_len), out.ctypes.data))
+        return [int(v) for v in out]
+
+    def debug_pair_annotate(self, table, start, end, type_, isize_mean, isize_sd):
+        """The annotation counts of calls over a caller's pair table, ascending in pos (test hook, rsi_hot_debug_pair_annotate):
+        returns (rp, q0_all, q0_q0), one uint32 array each."""
+        arrs = self._pair_arrays(table)
+        s, e, ty = (np.ascontiguousarray(v, dtype=np.int32).reshape(-1) for v in (start, end, type_))
+        assert s.size == e.size == ty.size
+        rp, qa, qq = (np.zeros(max(s.size, 1), dtype=np.uint32) for _ in range(3))
+        self._check(self.lib.rsi_hot_debug_pair_annotate(self.ctx, arrs[0].size, *[a.ctypes.data for a in arrs], s.size, s.ctypes.data, e.ctypes.data,
+                                                         ty.ctypes.data, int(isize_mean), int(isize_sd), rp.ctypes.data, qa.ctypes.data, qq.ctypes.data))
+        return rp[:s.size], qa[:s.size], qq[:s.size]
 
     def bam_read_stats(self):
         """The record reader's side of the last BAM load (rsi_hot_last_bam_read_stats): mode ("host" / "device"), and for the

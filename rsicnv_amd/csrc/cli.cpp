@@ -63,6 +63,7 @@ struct Options {
   std::string dindex;        // -dindex PATH|none: the .tbi / .csi of a BGZF bedGraph -d FILE for -c RNAME (empty: FILE.tbi, else FILE.csi, when there)
   std::string dindex_path;   // what that gives (main sets it); empty: the whole file is read
   bool trackindex = false;   // -trackindex: FILE.tbi beside every track that is BGZF, built from the device's records
+  std::string pairs;         // -pairs device|host: RP / Q0 from the pair table the BAM load keeps on the GPU (rsi_hot_set_bam_pairs), or from a second pass over the file on the host (empty: host)
   std::string bamread;       // -bamread device|host: the BAM's records inflated and found on the GPU (rsi_hot_set_bam_read), or by the host threads (empty: host)
   std::string refread;       // -refread device|host: the reference through the device reader (rsi_ref) or read_fasta (empty: host for text, device for BGZF)
   std::string refindex;      // -refindex PATH|none: the .gzi of a BGZF reference (empty: REFFILE.gzi when there, else the members are walked)
@@ -184,6 +185,7 @@ int usage() {
             << "   -trackindex  write the tabix index FILE.tbi beside every BGZF track, see below\n"
             << "   -dindex PATH|none  the tabix / CSI index of a BGZF bedGraph -d FILE, used with -c RNAME (default: FILE.tbi, else FILE.csi)\n"
             << "   -bamread device|host  with -b: inflate the BAM's BGZF blocks and find its records on the GPU, or on host threads (default: host)\n"
+            << "   -pairs device|host  with -b: RP / Q0 from the reads the BAM load keeps on the GPU, or from a second pass over the file on the host (default: host)\n"
             << "   -refread device|host  read REFFILE on the GPU, or with the host loop (default: host for plain text, device for BGZF), see below\n"
             << "   -refindex PATH|none  the .gzi of a BGZF REFFILE (default: REFFILE.gzi when there; none: the members are walked)\n"
             << "\nNote:\n"
@@ -296,6 +298,7 @@ void parse(int argc, char** argv, Options& o) {
     else if (s == "-dindex") { o.dindex = need(i); ++i; }
     else if (s == "-refread") { o.refread = need(i); ++i; }
     else if (s == "-bamread") { o.bamread = need(i); ++i; }
+    else if (s == "-pairs") { o.pairs = need(i); ++i; }
     else if (s == "-refindex") { o.refindex = need(i); ++i; }
     else { std::cerr << "unknown option " << s << std::endl; exit(usage()); }
   }
@@ -419,6 +422,9 @@ void process_chromosome(rsi_ctx* ctx, const Options& o, const std::string& chr, 
   if (from_bam && !o.bamread.empty() && rsi_hot_set_bam_read(ctx, o.bamread == "device" ? RSI_BAM_READ_DEVICE : RSI_BAM_READ_HOST, 0) != RSI_OK) {
     info << rsi_hot_last_error(ctx) << "\n"; co.log = info.str(); co.fatal = true; return;
   }
+  if (from_bam && o.pairs == "device" && rsi_hot_set_bam_pairs(ctx, 1) != RSI_OK) {
+    info << rsi_hot_last_error(ctx) << "\n"; co.log = info.str(); co.fatal = true; return;
+  }
   rsi_result* res = nullptr;
   rsi_text_stats ts;
   rsi_bam_stats bs;
@@ -531,7 +537,14 @@ void report_chromosome(rsi_ctx* ctx, const Options& o, const std::string& chr, r
          << " guessed right, " << brs.rewalked << " walked again, " << brs.passed << " passed over), upload " << brs.t_upload_ms << " ms, inflate "
          << brs.t_inflate_ms << " ms, record finder " << brs.t_find_ms << " ms\n";
   if (from_bam) {   // if ( fp_in ) cnv_stat(fp_in, bamidx, cnvlist), rsi.cpp:2210
-    if (rsi_result_annotate_bam(res, o.bamfile.c_str(), chr.c_str()) != RSI_OK) info << "RP / Q0 annotation failed: " << rsi_hot_last_error(nullptr) << "\n";
+    const bool on_device = o.pairs == "device";   // the pair table of the load, still in HBM; else a second pass over the file
+    if ((on_device ? rsi_result_annotate_device(ctx, res) : rsi_result_annotate_bam(res, o.bamfile.c_str(), chr.c_str())) != RSI_OK)
+      info << "RP / Q0 annotation failed: " << rsi_hot_last_error(nullptr) << "\n";
+    rsi_pairs_stats ps;
+    if (on_device && rsi_hot_last_pairs_stats(ctx, &ps) == RSI_OK && ps.records + ps.table_bytes > 0)
+      info << "#pairs: " << ps.records << " records, " << ps.table_bytes * 1e-6 << " MB, sample S " << ps.sample_stop << " isize " << ps.isize << " +- "
+           << ps.isize_sd << ", " << ps.calls << " calls, " << ps.examined << " records examined, table " << ps.t_table_ms << " ms, sample "
+           << ps.t_sample_ms << " ms, annotation " << ps.t_annotate_ms << " ms\n";
   }
   char row[1024];
   for (int i = 0; i < rsi_result_ncalls(res, 0); ++i) {
@@ -973,6 +986,10 @@ int main(int argc, char** argv) {
   }
   if (!o.bamread.empty() && o.bamread != "device" && o.bamread != "host") {
     std::cerr << "rsicnv: -bamread " << o.bamread << ": expected device or host" << std::endl;
+    return 1;
+  }
+  if (!o.pairs.empty() && o.pairs != "device" && o.pairs != "host") {
+    std::cerr << "rsicnv: -pairs " << o.pairs << ": expected device or host" << std::endl;
     return 1;
   }
   if (!o.bamread.empty() && !from_bam) {

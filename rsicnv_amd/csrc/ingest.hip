@@ -2,10 +2,12 @@
 // text file (load_data_from_text, loaddata.cpp:496-517) or from a BAM (the pileup loop, samfunctions.cpp), built in HBM.
 // The file bytes go through pinned double buffers; parsing, per-read work and the difference-array scan are kernels
 // (kernels_io.hip); a BAM's BGZF inflation and record walk run on host threads (bam_host.cpp) or, with rsi_hot_set_bam_read's
-// device mode, on the device too (kernels_inflate.hip, kernels_bam.hip).  At the end of the file: the reference
+// device mode, on the device too (kernels_inflate.hip, kernels_bam.hip).  An armed load (rsi_hot_set_bam_pairs) also keeps the
+// pair table, from which the RP / Q0 annotation is computed with no second pass over the file (kernels_pairs.hip).  At the end of the file: the reference
 // reader (rsi_ref), which brings an indexed FASTA, text or BGZF, into HBM through the same chunk source.
 #include "pipeline_internal.h"
 #include "inflate_core.h"
+#include "bam_pairs_core.h"
 #include "text_rules.h"
 #include "track_index_host.h"
 #include "ref_host.h"
@@ -688,6 +690,142 @@ int upload_fasta(rsi_ctx* ctx, const uint8_t* fasta, int64_t n) {
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return RSI_OK;
 }
+// ---- the pair table of an armed BAM load and what is computed from it ----
+constexpr size_t kPairsFirstCap = size_t(1) << 20;           // entries of the first allocation (20 MB); doubled when it fills up
+
+PairTable pair_table(const rsi_ctx* ctx) {
+  int32_t* b = ctx->pairs.tab.as<int32_t>();
+  const size_t c = ctx->pairs.cap;
+  return PairTable{b, b + c, b + 2 * c, b + 3 * c, reinterpret_cast<uint32_t*>(b + 4 * c)};
+}
+// Room for `need` entries: a larger table takes over the entries written so far, copied on the stream.
+int pairs_reserve(rsi_ctx* ctx, size_t need) {
+  rsi_ctx::Pairs& P = ctx->pairs;
+  if (need <= P.cap) return RSI_OK;
+  const size_t cap = std::max(need, P.cap ? 2 * P.cap : kPairsFirstCap);
+  DevBuf grown;
+  HIPCHK(grown.ensure(cap * 20));
+  for (int k = 0; k < 5 && P.n > 0; ++k)
+    HIPCHK(hipMemcpyAsync(grown.as<int32_t>() + (size_t)k * cap, P.tab.as<int32_t>() + (size_t)k * P.cap, (size_t)P.n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  if (P.tab.p) HIPCHK(hipStreamSynchronize(ctx->stream));    // the old table is freed below: nothing may still read or write it
+  std::swap(P.tab.p, grown.p); std::swap(P.tab.cap, grown.cap);
+  P.cap = cap;
+  return RSI_OK;
+}
+hipEvent_t pairs_event(rsi_ctx* ctx) {
+  rsi_ctx::Pairs& P = ctx->pairs;
+  if (P.ev_next == P.events.size()) { hipEvent_t e = nullptr; (void)hipEventCreate(&e); P.events.push_back(e); }
+  return P.events[P.ev_next++];
+}
+double pairs_elapsed(rsi_ctx* ctx, size_t first, size_t last) {   // summed time of the event pairs [first, last)
+  double sum = 0;
+  for (size_t k = first; k + 1 < last && k + 1 < ctx->pairs.events.size(); k += 2) {
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, ctx->pairs.events[k], ctx->pairs.events[k + 1]) == hipSuccess) sum += ms;
+  }
+  return sum;
+}
+// An armed load begins: an empty table, the words cleared, no predecessor.
+int pairs_begin(rsi_ctx* ctx) {
+  rsi_ctx::Pairs& P = ctx->pairs;
+  P.n = 0; P.parity = 0; P.ev_next = 0; P.maxspan = 0; P.flags = 0;
+  P.stats = rsi_pairs_stats{};
+  if (int rc = pairs_reserve(ctx, 1)) return rc;
+  HIPCHK(P.words.ensure(64));
+  const int32_t init[kPairWords] = {0, 0, INT32_MIN, INT32_MIN};
+  HIPCHK(copy_h2d(ctx, P.words.p, init, sizeof(init)));
+  return RSI_OK;
+}
+// Beside a chunk's launch_bam_depth, same arguments: its records appended to the table.
+int pairs_append(rsi_ctx* ctx, const void* data, const uint32_t* rec_off, int nrec, int tid) {
+  rsi_ctx::Pairs& P = ctx->pairs;
+  if (nrec <= 0) return RSI_OK;
+  if (int rc = pairs_reserve(ctx, (size_t)P.n + (size_t)nrec)) return rc;
+  const hipEvent_t a = pairs_event(ctx), b = pairs_event(ctx);
+  HIPCHK(hipEventRecord(a, ctx->stream));
+  launch_bam_pairs(data, rec_off, nrec, tid, (long long)P.n, pair_table(ctx), P.words.as<int32_t>(), P.parity, ctx->stream);
+  HIPCHK(hipEventRecord(b, ctx->stream));
+  P.n += nrec;
+  P.parity ^= 1;
+  return RSI_OK;
+}
+// Behind the load's last wait: the two reduced words are on the host (w), the table stands.
+void pairs_end(rsi_ctx* ctx, const int32_t* w, int tid, int64_t tid_len) {
+  rsi_ctx::Pairs& P = ctx->pairs;
+  P.maxspan = w[0]; P.flags = (uint32_t)w[1];
+  P.tid = tid; P.tid_len = tid_len;
+  P.valid = true;
+  P.stats.records = P.n; P.stats.table_bytes = P.n * 20; P.stats.maxspan = P.maxspan;
+  P.stats.t_table_ms = pairs_elapsed(ctx, 0, P.ev_next);
+}
+
+// The insert-size sample over table[0, n): out = count, sum |isize|, sum of wrapped squares, S.
+int pairs_sample(rsi_ctx* ctx, PairTable t, int64_t n, int64_t tid_len, int64_t out[4]) {
+  rsi_ctx::Pairs& P = ctx->pairs;
+  HIPCHK(P.ws.ensure(pair_sample_workspace_bytes((long long)n)));
+  unsigned long long* d_out = reinterpret_cast<unsigned long long*>(P.ws.as<char>() + 64);   // inside the workspace's 256-byte head
+  const size_t e0 = P.ev_next;
+  const hipEvent_t a = pairs_event(ctx), b = pairs_event(ctx);
+  HIPCHK(hipEventRecord(a, ctx->stream));
+  launch_pair_sample(t, (long long)n, (long long)tid_len, P.ws.p, d_out, ctx->stream);
+  HIPCHK(hipEventRecord(b, ctx->stream));
+  unsigned long long h[4];
+  HIPCHK(copy_d2h(ctx, h, d_out, sizeof(h)));
+  HIPCHK(CTX_SYNC());
+  out[0] = (int64_t)h[0]; out[1] = (int64_t)h[1]; out[2] = (int64_t)h[2]; out[3] = (int64_t)h[3] - 1;
+  P.stats.sample_count = out[0]; P.stats.sample_abs = out[1]; P.stats.sample_sq = out[2]; P.stats.sample_stop = out[3];
+  P.stats.t_sample_ms = pairs_elapsed(ctx, e0, e0 + 2);
+  P.ev_next = e0;
+  return RSI_OK;
+}
+// isize and isize_sd from the sums, with the very expressions of bam_pair_sample (bam_host.cpp): the integer sums are its
+// double sums wherever those are exact (|sum| < 2^53).
+rsih::PairSample pairs_sample_result(const int64_t sums[4]) {
+  rsih::PairSample out;
+  double isize = (double)sums[1];
+  const double isize2 = (double)sums[2], isize_c = (double)sums[0];
+  if (isize_c > 2) {
+    isize /= isize_c;
+    const double sd = sqrt((isize2 - isize_c * isize * isize) / isize_c);
+    out.isize = (int)isize;
+    out.isize_sd = (int)sd;
+  }
+  return out;
+}
+// The counts of the calls over table[0, n), ascending in pos: counts[4 * i ...] = q0_all, q0_q0, rp, entries examined.
+int pairs_annotate(rsi_ctx* ctx, PairTable t, int64_t n, int maxspan, const std::vector<rsipairs::Call>& calls, int isize_mean, int isize_sd,
+                   std::vector<uint32_t>& counts) {
+  rsi_ctx::Pairs& P = ctx->pairs;
+  counts.assign(calls.size() * 4, 0);
+  P.stats.calls = (int64_t)calls.size(); P.stats.examined = 0; P.stats.t_annotate_ms = 0;
+  if (calls.empty()) return RSI_OK;
+  HIPCHK(P.calls.ensure(calls.size() * sizeof(rsipairs::Call)));
+  HIPCHK(P.out.ensure(counts.size() * 4));
+  HIPCHK(copy_h2d(ctx, P.calls.p, calls.data(), calls.size() * sizeof(rsipairs::Call)));
+  const size_t e0 = P.ev_next;
+  const hipEvent_t a = pairs_event(ctx), b = pairs_event(ctx);
+  HIPCHK(hipEventRecord(a, ctx->stream));
+  launch_pairs_annotate(t, (long long)n, maxspan, P.calls.p, (int)calls.size(), isize_mean, isize_sd, P.out.as<uint32_t>(), ctx->stream);
+  HIPCHK(hipEventRecord(b, ctx->stream));
+  HIPCHK(copy_d2h(ctx, counts.data(), P.out.p, counts.size() * 4));
+  HIPCHK(CTX_SYNC());
+  for (size_t i = 0; i < calls.size(); ++i) P.stats.examined += counts[4 * i + 3];
+  P.stats.t_annotate_ms = pairs_elapsed(ctx, e0, e0 + 2);
+  P.ev_next = e0;
+  return RSI_OK;
+}
+// A caller's table in place of a BAM's (the debug hooks): whatever the context held is dropped.
+int pairs_upload(rsi_ctx* ctx, int64_t n, const int32_t* const arrays[5]) {
+  rsi_ctx::Pairs& P = ctx->pairs;
+  P.valid = false; P.n = 0;
+  P.stats = rsi_pairs_stats{};
+  if (int rc = pairs_reserve(ctx, (size_t)std::max<int64_t>(n, 1))) return rc;
+  for (int k = 0; k < 5 && n > 0; ++k)
+    HIPCHK(hipMemcpyAsync(P.tab.as<int32_t>() + (size_t)k * P.cap, arrays[k], (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return RSI_OK;
+}
+
 // rsi_hot_load_depth_bam's chunks in RSI_BAM_READ_DEVICE mode.  Per chunk the host walks member headers, copies
 // the deflate payloads into a pinned buffer and builds the member table; upload and launch_inflate_bgzf run on a stream of
 // their own (istream), so the next chunk is inflated while the current chunk's records are found (guess, walk, stitch) and piled
@@ -826,6 +964,7 @@ int bam_chunks_device(rsi_ctx* ctx, const char* bam_path, const rsih::BamFile& b
       if (rep.flags & rsibam::kBad) return fail(ctx, RSI_ERR_BAD_ARG, "malformed BAM record");
       if (rep.end > total || rep.listed > (uint32_t)kBamMaxSegs * kBamListCap) return fail(ctx, RSI_ERR_INTERNAL, "BAM device read: the record finder's report is out of range");
       if (rep.listed) { Timer t(ctx, "bam_depth"); launch_bam_depth(data, D.rec.as<uint32_t>(), (int)rep.listed, tid, minq, min_baseq, (long long)n, d_diff, d_stats, ctx->stream); }
+      if (ctx->pairs.armed) if (int rc = pairs_append(ctx, data, D.rec.as<uint32_t>(), (int)rep.listed, tid)) return rc;
     }
     const bool finished = (rep.flags & rsibam::kBeyond) || !more;
     carry = finished ? 0 : total - rep.end;
@@ -926,14 +1065,19 @@ int rsi_hot_load_depth_bam(rsi_ctx* ctx, const char* bam_path, const char* chrom
   uint8_t* wsb = ctx->text_wg.as<uint8_t>();
   BamDepthStats* d_stats = reinterpret_cast<BamDepthStats*>(wsb + stats_off);
   HIPCHK(hipMemsetAsync(d_stats, 0, sizeof(BamDepthStats), ctx->stream));
+  ctx->pairs.valid = false;              // whatever table the context held was the load before's
+  if (ctx->pairs.armed) if (int rc = pairs_begin(ctx)) return rc;
 
   // behind the last chunk, in either mode: the difference array scanned into the depth, the pileup's counts
   auto finish = [&]() -> int {
     { Timer t(ctx, "depth_scan"); launch_inclusive_scan_i32(d_diff, (long long)n, reinterpret_cast<int32_t*>(wsb + scan_off), ctx->stream); }
     BamDepthStats hs;
     HIPCHK(hipMemcpyAsync(&hs, d_stats, sizeof(hs), hipMemcpyDeviceToHost, ctx->stream));
+    int32_t pw[kPairWords] = {0, 0, 0, 0};
+    if (ctx->pairs.armed) HIPCHK(hipMemcpyAsync(pw, ctx->pairs.words.p, sizeof(pw), hipMemcpyDeviceToHost, ctx->stream));
     { const double tq = now_ms(); HIPCHK(hipStreamSynchronize(ctx->stream)); st->t_wait_ms += now_ms() - tq; }
     st->used = (int64_t)hs.used; st->runs = (int64_t)hs.runs; st->malformed = (int64_t)hs.malformed;
+    if (ctx->pairs.armed) pairs_end(ctx, pw, tid, n);
     st->t_total_ms = now_ms() - t0;
     return RSI_OK;
   };
@@ -1077,6 +1221,7 @@ int rsi_hot_load_depth_bam(rsi_ctx* ctx, const char* bam_path, const char* chrom
       HIPCHK(hipMemcpyAsync(ctx->text_dev[cur].p, buf + start, len - start, hipMemcpyHostToDevice, ctx->stream));
       HIPCHK(hipMemcpyAsync(d_off, offs.data(), offs.size() * 4, hipMemcpyHostToDevice, ctx->stream));
       { Timer t(ctx, "bam_depth"); launch_bam_depth(ctx->text_dev[cur].p, d_off, (int)offs.size(), tid, minq, min_baseq, (long long)n, d_diff, d_stats, ctx->stream); }
+      if (ctx->pairs.armed) if (int rc = pairs_append(ctx, ctx->text_dev[cur].p, d_off, (int)offs.size(), tid)) return rc;
       HIPCHK(hipEventRecord(done[cur], ctx->stream));
       used[cur] = true;
     }
@@ -1099,6 +1244,81 @@ int rsi_hot_set_bam_read(rsi_ctx* ctx, int mode, size_t chunk_bytes) {
 int rsi_hot_last_bam_read_stats(const rsi_ctx* ctx, rsi_bam_read_stats* out) {
   if (!ctx || !out) return RSI_ERR_BAD_ARG;
   *out = ctx->last_bam_read;
+  return RSI_OK;
+}
+
+int rsi_hot_set_bam_pairs(rsi_ctx* ctx, int on) {
+  if (!ctx) return fail(ctx, RSI_ERR_BAD_ARG, "null context");
+  ctx->pairs.armed = on != 0;
+  return RSI_OK;
+}
+int rsi_hot_last_pairs_stats(const rsi_ctx* ctx, rsi_pairs_stats* out) {
+  if (!ctx || !out) return RSI_ERR_BAD_ARG;
+  *out = ctx->pairs.valid ? ctx->pairs.stats : rsi_pairs_stats{};
+  return RSI_OK;
+}
+
+int rsi_result_annotate_device(rsi_ctx* ctx, rsi_result* r) {
+  if (!ctx || !r) return fail(ctx, RSI_ERR_BAD_ARG, "null argument");
+  rsi_ctx::Pairs& P = ctx->pairs;
+  if (!P.valid) return fail(ctx, RSI_ERR_BAD_ARG, "no pair table: the context's last BAM load was not armed (rsi_hot_set_bam_pairs)");
+  if (r->stats.n != P.tid_len) return fail(ctx, RSI_ERR_BAD_ARG, "the pair table the context holds is not of the result's chromosome");
+  if (P.flags & rsipairs::kUnsorted) return fail(ctx, RSI_ERR_UNSUPPORTED, "BAM not sorted by position");
+  if (P.flags & rsipairs::kOverrun) return fail(ctx, RSI_ERR_BAD_ARG, "malformed BAM record (name / CIGAR overrun the record)");
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!ctx_enter(ctx)) return RSI_ERR_HIP;
+  mailbox_reset(ctx);
+  int64_t sums[4];
+  if (int rc = pairs_sample(ctx, pair_table(ctx), P.n, P.tid_len, sums)) return rc;
+  const rsih::PairSample ps = pairs_sample_result(sums);
+  P.stats.isize = ps.isize; P.stats.isize_sd = ps.isize_sd;
+  std::vector<rsipairs::Call> calls;
+  rsipairs::Windows win;
+  for (const rsi_call& c : r->lists[0]) calls.push_back(win.next(c.start, c.end, c.type));
+  std::vector<uint32_t> counts;
+  if (int rc = pairs_annotate(ctx, pair_table(ctx), P.n, P.maxspan, calls, ps.isize, ps.isize_sd, counts)) return rc;
+  r->rp.clear(); r->q0.clear();
+  for (size_t i = 0; i < calls.size(); ++i) {
+    const double q0_all = (double)counts[4 * i], q0_q0 = (double)counts[4 * i + 1];
+    r->rp.push_back((int32_t)counts[4 * i + 2]);
+    r->q0.push_back(q0_q0 / (q0_all + 0.00001));
+  }
+  return RSI_OK;
+}
+
+int rsi_hot_debug_pair_sample(rsi_ctx* ctx, int64_t n, const int32_t* pos, const int32_t* rend, const int32_t* mpos, const int32_t* isize,
+                              const int32_t* info, int64_t tid_len, int64_t* out) {
+  if (!ctx || !out || n < 0 || n >= (1ll << 31) || (n > 0 && (!pos || !rend || !mpos || !isize || !info))) return fail(ctx, RSI_ERR_BAD_ARG, "bad argument");
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!ctx_enter(ctx)) return RSI_ERR_HIP;
+  mailbox_reset(ctx);
+  const int32_t* const arrays[5] = {pos, rend, mpos, isize, info};
+  if (int rc = pairs_upload(ctx, n, arrays)) return rc;
+  return pairs_sample(ctx, pair_table(ctx), n, tid_len, out);
+}
+
+int rsi_hot_debug_pair_annotate(rsi_ctx* ctx, int64_t n, const int32_t* pos, const int32_t* rend, const int32_t* mpos, const int32_t* isize,
+                                const int32_t* info, int ncalls, const int32_t* start, const int32_t* end, const int32_t* type,
+                                int isize_mean, int isize_sd, uint32_t* rp_out, uint32_t* q0all_out, uint32_t* q0q0_out) {
+  if (!ctx || n < 0 || n >= (1ll << 31) || (n > 0 && (!pos || !rend || !mpos || !isize || !info)) || ncalls < 0 ||
+      (ncalls > 0 && (!start || !end || !type || !rp_out || !q0all_out || !q0q0_out)))
+    return fail(ctx, RSI_ERR_BAD_ARG, "bad argument");
+  int64_t maxspan = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    if (i > 0 && pos[i] < pos[i - 1]) return fail(ctx, RSI_ERR_UNSUPPORTED, "BAM not sorted by position");
+    maxspan = std::max(maxspan, (int64_t)rend[i] - (int64_t)pos[i]);
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!ctx_enter(ctx)) return RSI_ERR_HIP;
+  mailbox_reset(ctx);
+  const int32_t* const arrays[5] = {pos, rend, mpos, isize, info};
+  if (int rc = pairs_upload(ctx, n, arrays)) return rc;
+  std::vector<rsipairs::Call> calls;
+  rsipairs::Windows win;
+  for (int i = 0; i < ncalls; ++i) calls.push_back(win.next(start[i], end[i], type[i]));
+  std::vector<uint32_t> counts;
+  if (int rc = pairs_annotate(ctx, pair_table(ctx), n, (int)std::min<int64_t>(maxspan, INT32_MAX), calls, isize_mean, isize_sd, counts)) return rc;
+  for (int i = 0; i < ncalls; ++i) { q0all_out[i] = counts[4 * (size_t)i]; q0q0_out[i] = counts[4 * (size_t)i + 1]; rp_out[i] = counts[4 * (size_t)i + 2]; }
   return RSI_OK;
 }
 

@@ -570,6 +570,25 @@ void launch_bam_walk(const void* data, long long len, int tid, const uint32_t* g
 void launch_bam_stitch(const void* data, long long len, int tid, const uint32_t* guess, const BamSegOut* out, uint32_t* lists, uint32_t* rec_off,
                        BamFindReport* report, hipStream_t stream);
 
+// ---- read-pair annotation on the device (kernels_pairs.hip, bam_pairs_core.h) ----
+// The pair table: five int32 arrays, entry k = record k of the chromosome in file order (bam_pairs_core.h, Entry).
+struct PairTable { int32_t *pos, *rend, *mpos, *isize; uint32_t* info; };
+// words[4]: the largest rend - pos, the load flags (rsipairs::LoadFlag), and the last pos of the chunk before, kept in
+// words[2 + parity] and left for the next launch in words[2 + (parity ^ 1)]: the launches of a load alternate parity.
+constexpr int kPairWords = 4;
+// One thread per entry of rec_off[] (what launch_bam_depth takes, same data): entry base + i of the table is written.
+void launch_bam_pairs(const void* data, const uint32_t* rec_off, int nrec, int tid, long long base, PairTable t, int32_t* words, int parity,
+                      hipStream_t stream);
+// The insert-size sample over table[0, n).  ws: pair_sample_workspace_bytes(n) bytes.  out[4] (device, unsigned long long):
+// count, sum |isize|, sum of the wrapped squares (two's complement), records kept up to and including the stopping one.
+constexpr int kPairSampleTile = 1024;
+size_t pair_sample_workspace_bytes(long long n);
+void launch_pair_sample(PairTable t, long long n, long long tid_len, void* ws, unsigned long long* out, hipStream_t stream);
+// One workgroup per call: calls[ncalls] (rsipairs::Call), out[4 * ncalls]: q0_all, q0_q0, rp, records examined.  The table is
+// ascending in pos; maxspan: the largest rend - pos in it.
+void launch_pairs_annotate(PairTable t, long long n, int maxspan, const void* calls, int ncalls, int isize_mean, int isize_sd, uint32_t* out,
+                           hipStream_t stream);
+
 // ---- depth track: an int32 array as bedGraph text, run-length encoded and formatted on the device (kernels_track.hip) ----
 // One line "NAME \t pos0+start \t pos0+end \t value \n" per maximal run of equal values of v[0, n), worked through in slices
 // [b, e) of bases.  A run start is i == 0 or v[i] != v[i - 1] -- read from the whole array, so slicing moves no start.  A line is

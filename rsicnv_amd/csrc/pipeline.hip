@@ -1556,6 +1556,7 @@ void rsi_hot_destroy(rsi_ctx* ctx) {
     if (ctx->bamdev.find[b]) (void)hipEventDestroy(ctx->bamdev.find[b]);
   }
   if (ctx->bamdev.istream) (void)hipStreamDestroy(ctx->bamdev.istream);
+  for (hipEvent_t e : ctx->pairs.events) (void)hipEventDestroy(e);
   if (ctx->sync_ev) (void)hipEventDestroy(ctx->sync_ev);
   if (ctx->copy_ev) (void)hipEventDestroy(ctx->copy_ev);   // (copy_stream is the device's shared one: never destroyed)
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -1748,6 +1749,10 @@ int64_t rsi_hot_fetch_i32(rsi_ctx* ctx, const char* name, int32_t* out, int64_t 
     return k;
   }
   else if (s == "depth_in" && ctx->in_depth.p) { src = ctx->in_depth.p; cnt = ctx->n_in; }
+  else if (s.rfind("pairs_", 0) == 0 && ctx->pairs.valid) {   // the pair table of the last armed BAM load
+    static const char* kArrays[5] = {"pairs_pos", "pairs_rend", "pairs_mpos", "pairs_isize", "pairs_info"};
+    for (int k = 0; k < 5; ++k) if (s == kArrays[k]) { src = ctx->pairs.tab.as<int32_t>() + (size_t)k * ctx->pairs.cap; cnt = ctx->pairs.n; }
+  }
   else if (s == "binmedint") { src = ctx->binmed.p; cnt = ctx->nb; }
   else if (s == "status1") { src = ctx->status1.p; cnt = ctx->nb; }
   else if (s == "status1f") { src = ctx->status1f.p; cnt = ctx->nb; }

@@ -164,7 +164,22 @@ struct rsi_ctx {
     hipEvent_t ev[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};   // per buffer: upload begins, inflate begins, inflate ends, its depth launch is through
     hipEvent_t find[2] = {nullptr, nullptr};   // around the record finder
   } bamdev;
-  int64_t n_in = 0;                          // length of the depth currently in in_depth
+  // Read-pair annotation on the device (rsi_hot_set_bam_pairs; ingest.hip): nothing of it exists until the first
+  // armed load.  tab: the pair table, five arrays of `cap` entries one behind the other; it belongs to the last armed load
+  // (valid) until the next BAM load or debug hook.
+  struct Pairs {
+    bool armed = false, valid = false;
+    DevBuf tab, words, ws, calls, out;
+    size_t cap = 0;                            // entries each of the five arrays has room for
+    int64_t n = 0, tid_len = 0;                // entries written; the chromosome's length
+    int tid = -1, parity = 0;                  // parity: which carry word the next k_bam_pairs launch reads (kernels.h)
+    int32_t maxspan = 0;
+    uint32_t flags = 0;                        // rsipairs::LoadFlag
+    std::vector<hipEvent_t> events;            // pairs around the load's k_bam_pairs launches, then around sample and annotation
+    size_t ev_next = 0;
+    rsi_pairs_stats stats{};
+  } pairs;
+  int64_t n_in = 0;                         // length of the depth currently in in_depth
   DevBuf gcbits, nbits, rd_gc, rdc, binmed, binsum, tnb, tmed, first_del;
   DevBuf depth8, rescaled8;   // byte copies: the raw depth (K2 writes it, K3' streams it), the rescaled depth (K3' -> K4')
   DevBuf slabs;   // per-workgroup partial results of the streaming kernels

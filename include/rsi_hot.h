@@ -586,6 +586,37 @@ int rsi_hot_debug_segments(rsi_ctx* ctx, const float* T, const int32_t* status, 
  * copied, waits. */
 int rsi_hot_debug_sharpen(rsi_ctx* ctx, const int32_t* depth, int64_t n, int storage, int32_t* start, int32_t* end, const int32_t* type,
                           int njobs, int32_t* info);
+/* One record of rsi_hot_debug_candidate_tests: the plan the host made from the list, the record the device wrote for it (flags -1:
+ * the plan was never sent), which road judged the candidate (0: the device's statistics, 1: the host walk because the device
+ * declined), and the candidate as judged. */
+typedef struct rsi_cand_record {
+  int32_t capacity, top, margin, cut, nleft, nright;                                 /* plan_test */
+  int32_t road;
+  int32_t flags, nref, nbody, nwin, left_reach, right_reach, body_min, body_max;     /* the device's record */
+  int32_t type, status, geno;                                                        /* the candidate as judged */
+  double body_q[3], body_s1, body_s2, ref_q[3], ref_s1, ref_s2;                      /* the device's record */
+  double p1, cnvmed, cnvsd, cnviqr, refmed, refsd, refiqr;                           /* the candidate as judged */
+} rsi_cand_record;
+/* Test hook: the neighbourhood test of a candidate (isitcnvwrap + isitcnv, rsi.cpp:101-287) over the HOST array depth[n], which
+ * becomes the context's compacted depth as bytes (storage 1; a value outside 0 .. 255 is RSI_ERR_BAD_ARG) or as int32 (storage 4).
+ * span_all: the compacted length the stage compares n with (n == span_all: the per-base form, n < span_all / 2: the form of the
+ * block tests on bin medians).  The list is ncand candidates (start, end, type, status); for every one of the nindex indices the
+ * road of a run is taken against the list as handed in: the plan, ONE call of the device tester over all plans, the judgement --
+ * by the host walk where the device declined.  form: bit 0 = the split form (three launches) / the one-workgroup form, bit 1 =
+ * gathered values of byte depth kept as int32.  The environment switches of whole runs are not read.  out[nindex].
+ * RSI_ERR_BAD_ARG, with the context left usable: a candidate outside 0 <= start <= end < n, a type other than 0 (DEL) / 1 (DUP)
+ * (the reference exits), an index outside the list, m < 1, maxchkbp < 1, minmlen or chklen not positive, a negative buffer, a
+ * negative depth, a plan without capacity.  info[8] (may be NULL) = waits, job lists that rode in the mailbox, job lists that were copied, the capacity in bytes
+ * of the per-job records before and after, of the folded histograms before and after, 0.  The kernels' names: rsi_hot_kernel_times. */
+int rsi_hot_debug_candidate_tests(rsi_ctx* ctx, const int32_t* depth, int64_t n, int storage, int64_t span_all, double RDmedian, int m,
+                                  double minmlen, double chklen, double buffer, int maxchkbp, const int32_t* start, const int32_t* end,
+                                  const int32_t* type, const int32_t* status, int ncand, const int32_t* index, int nindex, int form,
+                                  rsi_cand_record* out, int32_t* info);
+/* Test hook: exact sums of depth[n] (storage as above) over nranges inclusive ranges (lo[k], hi[k]) through the device tester's
+ * range_sums (mean_tp of mergesegments, rsi.cpp:775-779); sums[nranges].  A range with hi < lo, lo < 0 or hi >= n is
+ * RSI_ERR_BAD_ARG, as the tester refuses the whole list.  info[2] (may be NULL) = waits, 1 / 0 for ranges in the mailbox / copied. */
+int rsi_hot_debug_range_sums(rsi_ctx* ctx, const int32_t* depth, int64_t n, int storage, const int32_t* lo, const int32_t* hi, int nranges,
+                             int64_t* sums, int32_t* info);
 /* Test hook: the NB transform (negative_binomial_transfer, rsi.cpp:1145-1185) of the HOST bin sums binsum[nb] through the function a
  * run calls: the formula and the raw minimum (raw[nb]: the array between the two launches), then the subtraction, the scaling and
  * the three overwritten bins (T[nb]).  nb >= 3 (the reference writes bins 0..2) and nb == ncompact / m (the reference's bin count),

@@ -206,6 +206,27 @@ class Ref:
             L.ref_filterstatus.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_int32), C.c_int32, C.c_double]
             L.ref_filterstatus.restype = None
 
+        if hasattr(L, "ref_isitcnvwrap"):   # likewise
+            ip = C.POINTER(C.c_int32)
+            L.ref_isitcnvwrap.argtypes = [C.POINTER(Params), ip, C.c_int32, C.c_int32, C.c_double, ip, ip, ip, ip, C.c_int32, C.c_int32,
+                                          C.POINTER(Call)]
+
+    def isitcnvwrap(self, params, rd, span_all, RDmedian, cands, idx):
+        """The reference's isitcnvwrap + isitcnv (rsi.cpp:101-287) for entry idx of the list cands (int32 [k, 4]: start, end, type,
+        status) over the caller's array: the candidate as judged, a dict.  The caller keeps the walks inside the reference's arrays
+        (a RuntimeError here says one left them)."""
+        if not hasattr(self.lib, "ref_isitcnvwrap"):
+            raise RuntimeError(f"{REF_SO} predates ref_isitcnvwrap: rebuild it with `make -f oracle/Makefile.ref`")
+        d, dp = _i32(rd)
+        c = np.ascontiguousarray(cands, dtype=np.int32).reshape(-1, 4)
+        cols = [_i32(c[:, j]) for j in range(4)]
+        out = (Call * 1)()
+        rc = self.lib.ref_isitcnvwrap(C.byref(params), dp, d.size, int(span_all), float(RDmedian), cols[0][1], cols[1][1], cols[2][1], cols[3][1],
+                                      c.shape[0], int(idx), out)
+        if rc != 0:
+            raise RuntimeError("the reference's Array threw: a walk or the running mean left its array")
+        return calls_to_dicts(out, 1)[0]
+
     def load(self, params, depth, fasta, chrom="chrS", log=None):
         d, dp = _i32(depth)
         f = np.ascontiguousarray(fasta, dtype=np.uint8)

@@ -54,6 +54,7 @@ void areblockscnv(Array<int>& RDmedint, Array<int>& RDtrans_status,
 string cnv_format1(cnv_st& icnv);                                                  // rsi.cpp:581
 int expand_coordinate(int p1);                                                     // rsi.cpp:1524
 void optimize_with_derivative(Array<int>& RD, cnv_st& icnv);                       // rsi.cpp:889
+void isitcnvwrap(Array<int>& RD, vector<cnv_st>& cnvlist, int cnvidx);             // rsi.cpp:175
 void plot_icnv(cnv_st icnv, string title, string datfile, string gpfile, string imgfile);   // plotcnv.cpp:246
 
 extern "C" {
@@ -510,6 +511,33 @@ void ref_filterstatus(const float* T, int32_t* status, int32_t nb, double dev) {
   filterstatus(t, dev, st);
   quiet_end();
   for (int i = 0; i < nb; ++i) status[i] = st[i];
+}
+
+// isitcnvwrap + isitcnv alone (rsi.cpp:101-287) for cnvlist[idx] over the caller's array and list, with the globals the function
+// reads set for the call and restored: RDmedian, m, minmlen, chklen, buffer, maxchkbp, and rsi::start = 1, rsi::end = span_all
+// (RD.size() is compared with rsi::end - rsi::start + 1).  out: the candidate as judged.  Returns 0, or -1 when the reference's
+// Array threw (an index outside its neighbourhood array or an empty running mean): the caller sends no such case
+// (tests/cand_cases.py proves it for every case before it comes here).  A type other than DEL / DUP makes the reference exit.
+int ref_isitcnvwrap(const ref_params* p, const int32_t* rd, int32_t n, int32_t span_all, double RDmedian, const int32_t* start,
+                    const int32_t* end, const int32_t* type, const int32_t* status, int32_t ncand, int32_t idx, ref_call* out) {
+  static Array<int> RD(1);
+  RD.resize(0);
+  RD.resize(n);
+  for (int k = 0; k < n; ++k) RD[k] = rd[k];
+  vector<cnv_st> list((size_t)ncand);
+  for (int i = 0; i < ncand; ++i) { list[i].start = start[i]; list[i].end = end[i]; list[i].type = type[i]; list[i].status = status[i]; }
+  const double k_med = rsi::RDmedian, k_minmlen = rsi::minmlen, k_chklen = rsi::chklen, k_buffer = rsi::buffer;
+  const int k_m = rsi::m, k_max = rsi::maxchkbp, k_start = rsi::start, k_end = rsi::end;
+  rsi::RDmedian = RDmedian; rsi::m = p->m; rsi::minmlen = p->minmlen; rsi::chklen = p->chklen; rsi::buffer = p->buffer;
+  rsi::maxchkbp = p->maxchkbp; rsi::start = 1; rsi::end = span_all;
+  int rc = 0;
+  quiet_begin();
+  try { isitcnvwrap(RD, list, idx); } catch (const char*) { rc = -1; }
+  quiet_end();
+  rsi::RDmedian = k_med; rsi::m = k_m; rsi::minmlen = k_minmlen; rsi::chklen = k_chklen; rsi::buffer = k_buffer;
+  rsi::maxchkbp = k_max; rsi::start = k_start; rsi::end = k_end;
+  fill_call(list[idx], out);
+  return rc;
 }
 
 // Direct probes of the numeric utilities (used to pin the oracle's restatements).

@@ -50,12 +50,20 @@ RSI_OK = 0
 STATUS_NAMES = {0: "RSI_OK", -1: "RSI_ERR_NO_DEVICE", -2: "RSI_ERR_BAD_ARG", -3: "RSI_ERR_HIP",
                 -4: "RSI_ERR_TOO_SMALL", -5: "RSI_ERR_UNSUPPORTED", -6: "RSI_ERR_INTERNAL"}
 
+# rsi_cand_record (include/rsi_hot.h): one record of rsi_hot_debug_candidate_tests
+CAND_RECORD = np.dtype([(k, np.int32) for k in ("capacity", "top", "margin", "cut", "nleft", "nright", "road", "flags", "nref", "nbody", "nwin",
+                                                "left_reach", "right_reach", "body_min", "body_max", "type", "status", "geno")] +
+                       [("body_q", np.float64, 3), ("body_s1", np.float64), ("body_s2", np.float64), ("ref_q", np.float64, 3),
+                        ("ref_s1", np.float64), ("ref_s2", np.float64)] +
+                       [(k, np.float64) for k in ("p1", "cnvmed", "cnvsd", "cnviqr", "refmed", "refsd", "refiqr")])
+assert CAND_RECORD.itemsize == 18 * 4 + 17 * 8
+
 # every symbol include/rsi_hot.h and include/rsi_synth.h declare
 EXPORTS = ["rsi_default_params", "rsi_hot_create", "rsi_hot_destroy", "rsi_hot_last_error", "rsi_hot_run",
            "rsi_hot_run_device", "rsi_hot_load_depth_text", "rsi_hot_run_text", "rsi_hot_load_depth_bam", "rsi_hot_run_bam", "rsi_bam_references", "rsi_result_annotate_bam", "rsi_result_summary", "rsi_summary_format_row", "rsi_summary_format_rows", "rsi_result_pairs", "rsi_result_ncalls", "rsi_result_calls", "rsi_result_stats", "rsi_result_noncode",
            "rsi_result_format_row", "rsi_result_free", "rsi_hot_fetch_i32", "rsi_hot_fetch_f32", "rsi_hot_fetch_i64",
            "rsi_hot_kernel_times", "rsi_hot_phase_times", "rsi_hot_set_timing", "rsi_hot_process_setup", "rsi_pool_create", "rsi_pool_destroy", "rsi_pool_workers", "rsi_pool_hw_queues", "rsi_pool_worker",
-           "rsi_pool_set_timing", "rsi_pool_set_timing_kernel", "rsi_hot_set_timing_kernel", "rsi_pool_set_schedule", "rsi_pool_last_error", "rsi_pool_run", "rsi_pool_run_host", "rsi_pool_submit", "rsi_pool_wait", "rsi_plot_expand", "rsi_plot_write_files", "rsi_result_log_line", "rsi_hot_debug_level_sums", "rsi_hot_debug_scan", "rsi_hot_debug_segments", "rsi_hot_debug_sharpen", "rsi_hot_debug_nb_transform", "rsi_hot_debug_filterstatus", "rsi_hot_debug_grid_median", "rsi_hot_debug_grid_mad_i32", "rsi_synth_generate_host", "rsi_synth_generate_device", "rsi_synth_write_depth_text", "rsi_synth_write_fasta", "rsi_synth_append_genome_text",
+           "rsi_pool_set_timing", "rsi_pool_set_timing_kernel", "rsi_hot_set_timing_kernel", "rsi_pool_set_schedule", "rsi_pool_last_error", "rsi_pool_run", "rsi_pool_run_host", "rsi_pool_submit", "rsi_pool_wait", "rsi_plot_expand", "rsi_plot_write_files", "rsi_result_log_line", "rsi_hot_debug_level_sums", "rsi_hot_debug_scan", "rsi_hot_debug_segments", "rsi_hot_debug_sharpen", "rsi_hot_debug_candidate_tests", "rsi_hot_debug_range_sums", "rsi_hot_debug_nb_transform", "rsi_hot_debug_filterstatus", "rsi_hot_debug_grid_median", "rsi_hot_debug_grid_mad_i32", "rsi_synth_generate_host", "rsi_synth_generate_device", "rsi_synth_write_depth_text", "rsi_synth_write_fasta", "rsi_synth_append_genome_text",
            "rsi_genome_text_open", "rsi_genome_text_next", "rsi_genome_text_release", "rsi_genome_text_copy_depth",
            "rsi_genome_text_kernel_ms", "rsi_genome_text_close", "rsi_genome_text_last_error", "rsi_hot_run_depth_device",
            "rsi_hot_last_inflate_stats", "rsi_hot_inflate_bgzf", "rsi_genome_text_inflate_stats",
@@ -691,6 +699,41 @@ class RsiHot:
         self._check(self.lib.rsi_hot_debug_sharpen(self.ctx, d.ctypes.data, d.size, int(storage), s.ctypes.data, e.ctypes.data, ty.ctypes.data, s.size,
                                                    info.ctypes.data))
         return s, e, info
+
+    def debug_candidate_tests(self, depth, storage, span_all, RDmedian, cands, index, form, m=101, minmlen=3.01, chklen=2.5, buffer=0.05,
+                              maxchkbp=100000):
+        """The neighbourhood tests of list entries over a host array on the device (test hook).  cands: int32 [k, 4] (start, end, type,
+        status); index: the entries to test, all in one call of the device tester; form: bit 0 split / one workgroup, bit 1 byte depth
+        gathered as int32.  Returns (records, info): records a structured array with the fields of rsi_cand_record; info = waits, job
+        lists in the mailbox, job lists copied, capacity of the per-job records before / after, of the folded histograms before / after, 0."""
+        d = np.ascontiguousarray(depth, dtype=np.int32)
+        c = np.ascontiguousarray(cands, dtype=np.int32).reshape(-1, 4)
+        cols = [np.ascontiguousarray(c[:, j]) for j in range(4)]
+        ix = np.ascontiguousarray(index, dtype=np.int32).reshape(-1)
+        out = np.zeros(max(ix.size, 1), dtype=CAND_RECORD)
+        info = np.zeros(8, dtype=np.int32)
+        self.lib.rsi_hot_debug_candidate_tests.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_double, C.c_int, C.c_double,
+                                                           C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                           C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        self._check(self.lib.rsi_hot_debug_candidate_tests(self.ctx, d.ctypes.data, d.size, int(storage), int(span_all), float(RDmedian), int(m),
+                                                           float(minmlen), float(chklen), float(buffer), int(maxchkbp), cols[0].ctypes.data,
+                                                           cols[1].ctypes.data, cols[2].ctypes.data, cols[3].ctypes.data, c.shape[0],
+                                                           ix.ctypes.data, ix.size, int(form), out.ctypes.data, info.ctypes.data))
+        return out[:ix.size], info
+
+    def debug_range_sums(self, depth, storage, lo, hi):
+        """Exact sums of a host array over inclusive ranges through the device tester (test hook): (int64 sums, info); info = waits,
+        1 / 0 for the ranges in the mailbox / copied."""
+        d = np.ascontiguousarray(depth, dtype=np.int32)
+        a = np.ascontiguousarray(lo, dtype=np.int32).reshape(-1)
+        b = np.ascontiguousarray(hi, dtype=np.int32).reshape(-1)
+        assert a.size == b.size
+        sums = np.zeros(max(a.size, 1), dtype=np.int64)
+        info = np.zeros(2, dtype=np.int32)
+        self.lib.rsi_hot_debug_range_sums.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        self._check(self.lib.rsi_hot_debug_range_sums(self.ctx, d.ctypes.data, d.size, int(storage), a.ctypes.data, b.ctypes.data, a.size,
+                                                      sums.ctypes.data, info.ctypes.data))
+        return sums[:a.size], info
 
     def debug_nb_transform(self, binsum, m, ncompact, RDmedian, r):
         """The NB transform of host bin sums on the device (test hook): (raw, T, info).  raw: the values before the minimum is taken off;

@@ -650,6 +650,30 @@ int to_reference(const std::vector<Region>& noncode, int p) {
 
 }  // namespace
 
+int debug_neighbour_tests(const CallerInput& in, DepthPager& depth, const std::vector<Candidate>& list, const std::vector<int>& idx,
+                          std::vector<DebugTest>& out) {
+  const PagedView A{&depth};
+  std::vector<TestPlan> plans;
+  int cut = 0;
+  for (int ci : idx) {
+    plans.push_back(plan_test(in, A.size(), list, ci, &cut));
+    if (plans.back().capacity <= 0) return 2;   // the reference sizes its array with it
+  }
+  std::vector<TestStats> stats;
+  std::vector<int> reach;
+  std::vector<char> ok;
+  if (!in.tester || !in.tester->test(plans, stats, reach, ok)) return 1;
+  out.clear();
+  std::vector<Candidate> L;
+  for (size_t k = 0; k < idx.size(); ++k) {
+    L = list;
+    if (ok[k]) finish_judgement(in, stats[k], L[(size_t)idx[k]]);
+    else test_candidate(in, A, L, idx[k]);
+    out.push_back(DebugTest{plans[k], L[(size_t)idx[k]], ok[k] ? 0 : 1});
+  }
+  return 0;
+}
+
 // ---- areblockscnv (rsi.cpp:415-546) ----
 void test_block_segments(const CallerInput& in, IntSpan status, std::vector<Candidate>& segs) {
   const VecView bins{in.binmedint};

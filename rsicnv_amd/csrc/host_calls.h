@@ -146,6 +146,14 @@ void test_block_segments(const CallerInput& in, IntSpan status, std::vector<Cand
 void call_from_segments(const CallerInput& in, std::vector<Candidate> segs, DepthPager& depth,
                         std::vector<Candidate>& blocks, std::vector<Candidate>& raw, std::vector<Candidate>& kept);
 
+// Test harness (rsi_hot_debug_candidate_tests): the road test_bases takes, for every list[idx[k]] against the list as it is handed
+// in: plan_test, ONE call of in.tester->test over all the plans, finish_judgement -- or, where the device declined, the host walk
+// test_candidate over `depth`.  road 0: judged from the device's statistics, 1: by the host walk.  Returns 0, 1 when the tester
+// failed, 2 when a plan has no capacity (nothing was run).
+struct DebugTest { TestPlan plan; Candidate judged; int road; };
+int debug_neighbour_tests(const CallerInput& in, DepthPager& depth, const std::vector<Candidate>& list, const std::vector<int>& idx,
+                          std::vector<DebugTest>& out);
+
 // Depth from host memory, narrowed to bytes before it crosses PCIe: dst[i] = src[i] where 0 <= src[i] < 255, else 255 with the value
 // listed in (esc_pos, esc_val) (up to cap entries).  Returns the number of values that did not fit (may exceed cap).
 int64_t narrow_depth_u8(const int32_t* src, int64_t n, uint8_t* dst, int32_t* esc_pos, int32_t* esc_val, int64_t cap);

@@ -228,6 +228,11 @@ class DeviceTester : public rsih::NeighbourTester {
   DeviceTester(rsi_ctx* c, DepthRef rdc, int64_t n, double RDmedian) : ctx(c), d_rdc(rdc), N(n), median(RDmedian) {}
   double kernel_wait_ms = 0;
   int launches = 0;
+  // rsi_hot_debug_candidate_tests: the form of test() as an argument (-1: what the environment says, as every run takes it), the
+  // raw record of every plan (flags -1: never sent to the device), and how the job lists travelled
+  int force_split = -1, force_bytes = -1;
+  std::vector<CandOut>* sink = nullptr;
+  int mailbox_lists = 0, copied_lists = 0;
 
   // Jobs, neighbour lists and results of the candidate kernels live in the pinned mailbox (mapped host memory): the kernels
   // read a few dozen bytes per workgroup from it and write their records into it, so a call is its launches and one wait --
@@ -277,10 +282,11 @@ class DeviceTester : public rsih::NeighbourTester {
     // full ones take their CUs.  RSI_HOT_CAND_SPLIT=0 / 1 overrides.
     // several workgroups per test when the chip has room for them: a stand-alone context, or a pool run over a few
     // chromosomes only (a rank's share of a sharded genome); one workgroup per test when a dozen chromosomes share the chip
-    const bool split = env_int("RSI_HOT_CAND_SPLIT", 1) != 0;
+    const bool split = force_split >= 0 ? force_split != 0 : env_int("RSI_HOT_CAND_SPLIT", 1) != 0;
+    if (sink) { CandOut none{}; none.flags = -1; sink->assign(n, none); }
     // byte depth: the gathered values are stored as bytes and a trip of the walk covers 65 536 positions; RSI_HOT_CAND_BYTES=0
     // keeps them as int32, with trips of 16 384 (the form int32 depth always takes)
-    const int value_bytes = d_rdc.bytes == 1 && env_int("RSI_HOT_CAND_BYTES", 1) != 0 ? 1 : 4;
+    const int value_bytes = d_rdc.bytes == 1 && (force_bytes >= 0 ? force_bytes != 0 : env_int("RSI_HOT_CAND_BYTES", 1) != 0) ? 1 : 4;
     size_t first = 0;
     while (first < n) {
       std::vector<CandJob> jobs;
@@ -332,6 +338,7 @@ class DeviceTester : public rsih::NeighbourTester {
       const CandJob* d_jobs = ctx->cand_jobs.as<CandJob>();
       const void* d_chains = ctx->cand_chains.p;
       CandOut* d_outs = ctx->cand_outs.as<CandOut>();
+      ++(slot ? mailbox_lists : copied_lists);
       if (slot) {
         memcpy(slot, jobs.data(), jobs.size() * sizeof(CandJob));
         memcpy(slot + jb, chains.data(), chains.size() * 4);
@@ -364,6 +371,7 @@ class DeviceTester : public rsih::NeighbourTester {
           fprintf(stderr, "[cand] [%d,%d] kind %d margin %d cap %d top %d chains %d/%d cut %d -> flags %d nref %d nbody %d nwin %d reach %d/%d ref q %.6f %.6f %.6f s1 %.6f s2 %.6f\n",
                   jobs[k].start, jobs[k].end, jobs[k].kind, jobs[k].margin, jobs[k].capacity, jobs[k].top, jobs[k].nleft, jobs[k].nright, jobs[k].cut,
                   O.flags, O.nref, O.nbody, O.nwin, O.left_reach, O.right_reach, O.ref_q[0], O.ref_q[1], O.ref_q[2], O.ref_s1, O.ref_s2);
+        if (sink) (*sink)[first + k] = O;
         if (O.flags != 0) continue;
         rsih::TestStats& S = stats[first + k];
         const double nb = (double)O.nbody, nw = (double)O.nwin;
@@ -2019,13 +2027,10 @@ int rsi_hot_debug_filterstatus(rsi_ctx* ctx, const float* T, const int32_t* stat
   return RSI_OK;
 }
 
-// Test hook: optimize_with_derivative, both calls, over a host array (include/rsi_hot.h): the array becomes the context's
-// compacted depth, as bytes or as int32, and DeviceTester::sharpen -- what the candidate stages call -- does the rest, with the
-// context's own workspace.
-int rsi_hot_debug_sharpen(rsi_ctx* ctx, const int32_t* depth, int64_t n, int storage, int32_t* start, int32_t* end, const int32_t* type,
-                          int njobs, int32_t* info) {
-  if (!ctx || !depth || n <= 0 || n >= (1ll << 31) - 4096 || (storage != 1 && storage != 4) || njobs < 0 || (njobs > 0 && (!start || !end || !type)))
-    return fail(ctx, RSI_ERR_BAD_ARG, "bad argument");
+// The candidate hooks' common entry: depth[n] becomes the context's compacted depth, as bytes (storage 1) or as int32 (storage 4).
+// Its own arguments are checked before the context is touched.
+static int debug_depth_upload(rsi_ctx* ctx, const int32_t* depth, int64_t n, int storage, DepthRef* ref) {
+  if (!ctx || !depth || n <= 0 || n >= (1ll << 31) - 4096 || (storage != 1 && storage != 4)) return fail(ctx, RSI_ERR_BAD_ARG, "bad argument");
   std::vector<uint8_t> bytes;
   if (storage == 1) {
     bytes.resize((size_t)n);
@@ -2039,19 +2044,30 @@ int rsi_hot_debug_sharpen(rsi_ctx* ctx, const int32_t* depth, int64_t n, int sto
   mailbox_reset(ctx);
   ctx->ktimes.clear(); ctx->event_next = 0; ctx->phases.clear();
   ctx->run_m = 0; ctx->ncompact = n;
-  DepthRef ref;
   if (storage == 1) {
     HIPCHK(ctx->rdc8.ensure((size_t)n + 64));
     HIPCHK(hipMemcpyAsync(ctx->rdc8.p, bytes.data(), (size_t)n, hipMemcpyHostToDevice, ctx->stream));
     ctx->rdc_is_bytes = true; ctx->rdc_valid = false;
-    ref = DepthRef{ctx->rdc8.p, 1};
+    *ref = DepthRef{ctx->rdc8.p, 1};
   } else {
     HIPCHK(ctx->rdc.ensure((size_t)(n + 4) * 4));
     HIPCHK(hipMemcpyAsync(ctx->rdc.p, depth, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
     ctx->rdc_is_bytes = false; ctx->rdc_valid = false;
-    ref = DepthRef{ctx->rdc.p, 4};
+    *ref = DepthRef{ctx->rdc.p, 4};
   }
   HIPCHK(CTX_SYNC());
+  return RSI_OK;
+}
+
+// Test hook: optimize_with_derivative, both calls, over a host array (include/rsi_hot.h): the array becomes the context's
+// compacted depth, as bytes or as int32, and DeviceTester::sharpen -- what the candidate stages call -- does the rest, with the
+// context's own workspace.
+int rsi_hot_debug_sharpen(rsi_ctx* ctx, const int32_t* depth, int64_t n, int storage, int32_t* start, int32_t* end, const int32_t* type,
+                          int njobs, int32_t* info) {
+  if (njobs < 0 || (njobs > 0 && (!start || !end || !type))) return fail(ctx, RSI_ERR_BAD_ARG, "bad argument");
+  DepthRef ref;
+  int rc;
+  if ((rc = debug_depth_upload(ctx, depth, n, storage, &ref)) != RSI_OK) return rc;
   std::vector<Candidate> L((size_t)njobs);
   for (int i = 0; i < njobs; ++i) { L[(size_t)i].start = start[i]; L[(size_t)i].end = end[i]; L[(size_t)i].type = type[i]; }
   const int ws_before = ctx->sharpen_ws_jobs;
@@ -2060,6 +2076,89 @@ int rsi_hot_debug_sharpen(rsi_ctx* ctx, const int32_t* depth, int64_t n, int sto
   if (!tester.sharpen(L)) return tester.failed ? RSI_ERR_HIP : fail(ctx, RSI_ERR_INTERNAL, "the edge refinement declined the list");
   for (int i = 0; i < njobs; ++i) { start[i] = L[(size_t)i].start; end[i] = L[(size_t)i].end; }
   if (info) { info[0] = ws_before; info[1] = ctx->sharpen_ws_jobs; info[2] = ctx->mb_used > mb_before ? 1 : 0; info[3] = tester.launches; }
+  return RSI_OK;
+}
+
+// Test hook: the neighbourhood tests of candidates over a host array (include/rsi_hot.h).  The array becomes the context's compacted
+// depth; rsih::debug_neighbour_tests takes the road of test_bases (host_calls.cpp) with a DeviceTester whose form is the caller's.
+int rsi_hot_debug_candidate_tests(rsi_ctx* ctx, const int32_t* depth, int64_t n, int storage, int64_t span_all, double RDmedian, int m,
+                                  double minmlen, double chklen, double buffer, int maxchkbp, const int32_t* start, const int32_t* end,
+                                  const int32_t* type, const int32_t* status, int ncand, const int32_t* index, int nindex, int form,
+                                  rsi_cand_record* out, int32_t* info) {
+  if (!ctx || !depth || !start || !end || !type || !status || !index || !out || ncand < 1 || nindex < 1 || n <= 0 || form < 0 || form > 3 ||
+      span_all < 1 || span_all >= (1ll << 31) || m < 1 || maxchkbp < 1 || maxchkbp > ((1 << 30) / 10) ||
+      !(minmlen > 0 && minmlen < 1e6) || !(chklen > 0 && chklen < 1e6) || !(buffer >= 0 && buffer < 1e6) || !(RDmedian == RDmedian))
+    return fail(ctx, RSI_ERR_BAD_ARG, "bad argument");
+  for (int64_t i = 0; i < n; ++i) if (depth[i] < 0) return fail(ctx, RSI_ERR_BAD_ARG, "a negative depth");   // (n is checked again with the upload)
+  std::vector<Candidate> L((size_t)ncand);
+  for (int i = 0; i < ncand; ++i) {
+    if (start[i] < 0 || end[i] < start[i] || end[i] >= n) return fail(ctx, RSI_ERR_BAD_ARG, "a candidate must lie inside the array, start <= end");
+    if (type[i] != rsih::kDel && type[i] != rsih::kDup) return fail(ctx, RSI_ERR_BAD_ARG, "a candidate's type must be DEL or DUP");   // rsi.cpp:178-182: the reference exits
+    L[(size_t)i].start = start[i]; L[(size_t)i].end = end[i]; L[(size_t)i].type = type[i]; L[(size_t)i].status = status[i];
+  }
+  std::vector<int> idx((size_t)nindex);
+  for (int k = 0; k < nindex; ++k) {
+    if (index[k] < 0 || index[k] >= ncand) return fail(ctx, RSI_ERR_BAD_ARG, "an index outside the list");
+    idx[(size_t)k] = index[k];
+    // the largest capacity any plan can have must fit an int (chklen * d * 2 with d up to the longer of the body and m * minmlen)
+    const double d = std::max({(double)(end[index[k]] - start[index[k]] + 1), (double)m * minmlen, minmlen + 1});
+    if (chklen * d * 2 >= 1073741824.0) return fail(ctx, RSI_ERR_BAD_ARG, "a plan's capacity would not fit");
+  }
+  DepthRef ref;
+  int rc;
+  if ((rc = debug_depth_upload(ctx, depth, n, storage, &ref)) != RSI_OK) return rc;
+  rsih::CallerInput in{};
+  rsi_default_params(&in.P);
+  in.P.m = m; in.P.minmlen = minmlen; in.P.chklen = chklen; in.P.buffer = buffer; in.P.maxchkbp = maxchkbp;
+  in.RDmedian = RDmedian; in.RDsd = 0; in.ncompact = span_all; in.noncode = nullptr;
+  DeviceTester tester(ctx, ref, n, RDmedian);
+  std::vector<CandOut> raw;
+  tester.force_split = form & 1; tester.force_bytes = (form & 2) ? 0 : 1; tester.sink = &raw;
+  in.tester = &tester;
+  const size_t mid0 = ctx->cand_mid.cap, hist0 = ctx->cand_hist.cap;
+  rsih::DepthPager pager(depth, n);
+  std::vector<rsih::DebugTest> res;
+  const int how = rsih::debug_neighbour_tests(in, pager, L, idx, res);
+  if (how == 2) return fail(ctx, RSI_ERR_BAD_ARG, "a plan without capacity");
+  if (how != 0) return tester.failed ? RSI_ERR_HIP : fail(ctx, RSI_ERR_INTERNAL, "the device tester refused the list");
+  for (int k = 0; k < nindex; ++k) {
+    const rsih::DebugTest& T = res[(size_t)k];
+    const CandOut& O = raw[(size_t)k];
+    rsi_cand_record& R = out[k];
+    memset(&R, 0, sizeof(R));
+    R.capacity = T.plan.capacity; R.top = T.plan.top; R.margin = T.plan.margin; R.cut = T.plan.cut;
+    R.nleft = (int32_t)T.plan.left_chain.size(); R.nright = (int32_t)T.plan.right_chain.size();
+    R.road = T.road;
+    R.flags = O.flags; R.nref = O.nref; R.nbody = O.nbody; R.nwin = O.nwin; R.left_reach = O.left_reach; R.right_reach = O.right_reach;
+    R.body_min = O.body_min; R.body_max = O.body_max;
+    for (int q = 0; q < 3; ++q) { R.body_q[q] = O.body_q[q]; R.ref_q[q] = O.ref_q[q]; }
+    R.body_s1 = O.body_s1; R.body_s2 = O.body_s2; R.ref_s1 = O.ref_s1; R.ref_s2 = O.ref_s2;
+    const Candidate& c = T.judged;
+    R.type = c.type; R.status = c.status; R.geno = c.geno;
+    R.p1 = c.p1; R.cnvmed = c.cnvmed; R.cnvsd = c.cnvsd; R.cnviqr = c.cnviqr; R.refmed = c.refmed; R.refsd = c.refsd; R.refiqr = c.refiqr;
+  }
+  if (info) {
+    info[0] = tester.launches; info[1] = tester.mailbox_lists; info[2] = tester.copied_lists;
+    info[3] = (int32_t)mid0; info[4] = (int32_t)ctx->cand_mid.cap; info[5] = (int32_t)hist0; info[6] = (int32_t)ctx->cand_hist.cap; info[7] = 0;
+  }
+  return RSI_OK;
+}
+
+// Test hook: DeviceTester::range_sums over a host array (include/rsi_hot.h).
+int rsi_hot_debug_range_sums(rsi_ctx* ctx, const int32_t* depth, int64_t n, int storage, const int32_t* lo, const int32_t* hi, int nranges,
+                             int64_t* sums, int32_t* info) {
+  if (!lo || !hi || !sums || nranges < 1) return fail(ctx, RSI_ERR_BAD_ARG, "bad argument");
+  DepthRef ref;
+  int rc;
+  if ((rc = debug_depth_upload(ctx, depth, n, storage, &ref)) != RSI_OK) return rc;
+  std::vector<std::pair<int, int>> ranges((size_t)nranges);
+  for (int k = 0; k < nranges; ++k) ranges[(size_t)k] = {lo[k], hi[k]};
+  const size_t mb_before = ctx->mb_used;
+  DeviceTester tester(ctx, ref, n, 0.0);
+  std::vector<int64_t> got;
+  if (!tester.range_sums(ranges, got)) return tester.failed ? RSI_ERR_HIP : fail(ctx, RSI_ERR_BAD_ARG, "a range outside the array, or hi < lo");
+  memcpy(sums, got.data(), (size_t)nranges * 8);
+  if (info) { info[0] = tester.launches; info[1] = ctx->mb_used > mb_before ? 1 : 0; }
   return RSI_OK;
 }
 

@@ -23,7 +23,8 @@ def test_every_declared_symbol_is_exported(hotlib):
     assert not missing, f"librsi_hot.so lacks: {missing}"
     assert set(api.EXPORTS) <= set(names)
     assert "rsi_hot_debug_per_base" in names and "rsi_hot_debug_per_base" in api.EXPORTS
-    for hook in ("rsi_hot_debug_segments", "rsi_hot_debug_sharpen", "rsi_hot_debug_nb_transform", "rsi_hot_debug_filterstatus"):
+    for hook in ("rsi_hot_debug_segments", "rsi_hot_debug_sharpen", "rsi_hot_debug_nb_transform", "rsi_hot_debug_filterstatus",
+                 "rsi_hot_debug_candidate_tests", "rsi_hot_debug_range_sums"):
         assert hook in names and hook in api.EXPORTS
 
 
@@ -31,6 +32,13 @@ def test_struct_layouts_match_header(hotlib):
     from rsicnv_amd import api
     assert C.sizeof(api.RsiParams) == 6 * 4 + 7 * 8
     assert C.sizeof(api.RsiCall) == 8 * 4 + 8 * 8
+    hdr = open(os.path.join(ROOT, "include", "rsi_hot.h")).read()
+    body = re.search(r"typedef struct rsi_cand_record \{(.*?)\} rsi_cand_record;", hdr, flags=re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    fields = [(ty, re.sub(r"\[\d+\]", "", nm.strip())) for ty, names in re.findall(r"(int32_t|double)\s+([^;]+);", body) for nm in names.split(",")]
+    assert [nm for _, nm in fields] == list(api.CAND_RECORD.names)          # the same fields in the same order
+    assert all((ty == "int32_t") == (api.CAND_RECORD[nm].base == "int32") for ty, nm in fields)
+    assert api.CAND_RECORD.itemsize == 18 * 4 + 17 * 8 and api.CAND_RECORD.fields["body_q"][1] == 18 * 4
     p = api.RsiParams()
     hotlib.rsi_default_params(C.byref(p))
     assert (p.m, p.gcadjust, p.trans, p.merge, p.maxchkbp, p.cap, p.epsilon, p.chklen, p.minmlen, p.buffer, p.p) == \

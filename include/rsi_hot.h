@@ -316,6 +316,48 @@ int rsi_hot_debug_pair_sample(rsi_ctx* ctx, int64_t n, const int32_t* pos, const
 int rsi_hot_debug_pair_annotate(rsi_ctx* ctx, int64_t n, const int32_t* pos, const int32_t* rend, const int32_t* mpos, const int32_t* isize,
                                 const int32_t* info, int ncalls, const int32_t* start, const int32_t* end, const int32_t* type,
                                 int isize_mean, int isize_sd, uint32_t* rp_out, uint32_t* q0all_out, uint32_t* q0q0_out);
+/* ---- `stat` and `pin`: a list of CNVs that exists already, annotated and sharpened from the BAM ----
+ * rsi_hot_stat_calls: RP / Q0 of ncalls calls of the chromosome of the context's last armed load (rsi_hot_set_bam_pairs), with
+ * the windows given: start / end / type as in the list (type 2: unknown, RP 0), p1e / p2e the window cnv_stat reads for the
+ * call -- the caller carries DIS through its whole list, across chromosomes.  isize_io / isize_sd_io: on entry what the
+ * chromosome before left (-1 / -1 at first), on return this chromosome's insert size and deviation, or the values unchanged
+ * when it has fewer than three proper pairs in the sample, as cnv_stat's one bamstat_st does.
+ * rsi_hot_set_bam_pin(ctx, 1) arms the context's BAM loads (and with them the pair table) to keep, beside each pair-table
+ * entry, the read's l_qseq and its CIGAR: 8 bytes per read plus 4 + 4 n_cigar bytes in a pool of words, fetchable as "pin_lq",
+ * "pin_coff" (the read's place in the pool: pool[coff] = n_cigar, then the words) and "pin_pool".  Unarmed, nothing is kept.
+ * rsi_hot_pin_sample: the depth sample of bam_rd_pr_stats from 10 Mb on -- read length, rd and drd mean and deviation -- kept
+ * by the context for rsi_hot_pin_calls.  RSI_ERR_UNSUPPORTED with the reason as the error text where the chromosome cannot be
+ * sampled as the reference does: no accepted read from 10 Mb on, or a sampled read more than 1 000 900 bases behind its
+ * stretch's start; an unsorted table and an overrun record are refused as rsi_result_annotate_device refuses them.
+ * rsi_hot_pin_calls: every call with |end - start| >= 800 and type 0 / 1 gets each breakpoint moved to the best-scoring base of
+ * its window of max(m, read length, 50) bases on each side, where at least two clipped reads end; sc1 / sc2: the clip counts
+ * (0 for a call not looked at).  RSI_ERR_UNSUPPORTED when that window's counters do not fit the workgroup's LDS. */
+typedef struct rsi_pin_stats {
+  int64_t records, table_bytes, pool_words;   /* reads kept, bytes of their two arrays plus the pool, words of the pool in use */
+  int64_t sample_reads;                       /* reads of the sample's last stretch */
+  int32_t pos_start, pos_end;                 /* that stretch: its first read's pos, the pos of the last read counted */
+  int32_t l_qseq, r_len;                      /* the sample's read length; the half window rsi_hot_pin_calls last used */
+  double rd, rd_sd, drd, drd_sd;
+  int64_t breakpoints;                        /* workgroups of the last rsi_hot_pin_calls */
+  double t_table_ms, t_sample_ms, t_windows_ms;   /* HIP events: the load's k_bam_pin launches, the sample, the windows */
+} rsi_pin_stats;
+int rsi_hot_set_bam_pin(rsi_ctx* ctx, int on);
+int rsi_hot_stat_calls(rsi_ctx* ctx, int ncalls, const int32_t* start, const int32_t* end, const int32_t* type, const int32_t* p1e, const int32_t* p2e,
+                       int32_t* isize_io, int32_t* isize_sd_io, int32_t* rp, double* q0);
+int rsi_hot_pin_sample(rsi_ctx* ctx, rsi_pin_stats* out);
+int rsi_hot_pin_calls(rsi_ctx* ctx, int m, int ncalls, const int32_t* start, const int32_t* end, const int32_t* type, int32_t* new_start,
+                      int32_t* new_end, int32_t* sc1, int32_t* sc2);
+int rsi_hot_last_pin_stats(const rsi_ctx* ctx, rsi_pin_stats* out);
+/* Test hooks: a pair table plus lq[n], coff[n] and pool[npool] from the caller in place of a BAM's.  _sample: rsi_hot_pin_sample
+ * over it, and rd[rd_cap] / drd[rd_cap] (may be null) get the last stretch's arrays from its start on.  _calls:
+ * rsi_hot_pin_calls over it with the read length and drd deviation given. */
+int rsi_hot_debug_pin_sample(rsi_ctx* ctx, int64_t n, const int32_t* pos, const int32_t* rend, const int32_t* mpos, const int32_t* isize,
+                             const int32_t* info, const int32_t* lq, const uint32_t* coff, const uint32_t* pool, int64_t npool, int64_t tid_len,
+                             rsi_pin_stats* out, int32_t* rd, int32_t* drd, int64_t rd_cap);
+int rsi_hot_debug_pin_calls(rsi_ctx* ctx, int64_t n, const int32_t* pos, const int32_t* rend, const int32_t* mpos, const int32_t* isize,
+                            const int32_t* info, const int32_t* lq, const uint32_t* coff, const uint32_t* pool, int64_t npool, int64_t tid_len,
+                            int m, int l_qseq, double drd_sd, int ncalls, const int32_t* start, const int32_t* end, const int32_t* type,
+                            int32_t* new_start, int32_t* new_end, int32_t* sc1, int32_t* sc2);
 /* Fixed-layout summary of a chromosome's result for the one exchange of a multi-GPU run (the gather of per-chromosome
  * results that replaces the reference's sequential output loop, rsi.cpp:1594-1608):
  *   out[0..7]  = chromosome id (the caller's), chromosome median, SD, number of final calls, number stored here, 0, 0, 0

@@ -82,6 +82,8 @@ EXPORTS = ["rsi_default_params", "rsi_hot_create", "rsi_hot_destroy", "rsi_hot_l
            "rsi_hot_set_bam_read", "rsi_hot_last_bam_read_stats",
            "rsi_hot_set_bam_pairs", "rsi_result_annotate_device", "rsi_hot_last_pairs_stats", "rsi_hot_debug_pair_sample",
            "rsi_hot_debug_pair_annotate",
+           "rsi_hot_set_bam_pin", "rsi_hot_stat_calls", "rsi_hot_pin_sample", "rsi_hot_pin_calls", "rsi_hot_last_pin_stats",
+           "rsi_hot_debug_pin_sample", "rsi_hot_debug_pin_calls",
            "rsi_ref_debug_set_chunks", "rsi_ref_debug_fai_line", "rsi_ref_debug_ranges", "rsi_ref_debug_gzi", "rsi_ref_debug_cover"]
 
 
@@ -175,6 +177,13 @@ class RsiPairsStats(C.Structure):
                 ("sample_abs", C.c_int64), ("sample_sq", C.c_int64), ("sample_stop", C.c_int64), ("isize", C.c_int32),
                 ("isize_sd", C.c_int32), ("calls", C.c_int64), ("examined", C.c_int64),
                 ("t_table_ms", C.c_double), ("t_sample_ms", C.c_double), ("t_annotate_ms", C.c_double)]
+
+
+class RsiPinStats(C.Structure):
+    _fields_ = [("records", C.c_int64), ("table_bytes", C.c_int64), ("pool_words", C.c_int64), ("sample_reads", C.c_int64),
+                ("pos_start", C.c_int32), ("pos_end", C.c_int32), ("l_qseq", C.c_int32), ("r_len", C.c_int32),
+                ("rd", C.c_double), ("rd_sd", C.c_double), ("drd", C.c_double), ("drd_sd", C.c_double), ("breakpoints", C.c_int64),
+                ("t_table_ms", C.c_double), ("t_sample_ms", C.c_double), ("t_windows_ms", C.c_double)]
 
 
 BAM_READ_MODES = {"host": 0, "device": 1}
@@ -326,6 +335,15 @@ def load_library():
     L.rsi_hot_last_pairs_stats.argtypes = [C.c_void_p, C.POINTER(RsiPairsStats)]
     L.rsi_hot_debug_pair_sample.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p]
     L.rsi_hot_debug_pair_annotate.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 3
+    L.rsi_hot_set_bam_pin.argtypes = [C.c_void_p, C.c_int]
+    L.rsi_hot_stat_calls.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]
+    L.rsi_hot_pin_sample.argtypes = [C.c_void_p, C.POINTER(RsiPinStats)]
+    L.rsi_hot_pin_calls.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7
+    L.rsi_hot_last_pin_stats.argtypes = [C.c_void_p, C.POINTER(RsiPinStats)]
+    L.rsi_hot_debug_pin_sample.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 8 + [C.c_int64, C.c_int64, C.POINTER(RsiPinStats), C.c_void_p, C.c_void_p,
+                                           C.c_int64]
+    L.rsi_hot_debug_pin_calls.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 8 + [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int] + \
+                                         [C.c_void_p] * 7
     L.rsi_bgzf_write_eof.argtypes = [C.c_char_p]
     L.rsi_track_index_create.argtypes = []
     L.rsi_track_index_create.restype = C.c_void_p
@@ -954,6 +972,77 @@ class RsiHot:
         self._check(self.lib.rsi_hot_debug_pair_annotate(self.ctx, arrs[0].size, *[a.ctypes.data for a in arrs], s.size, s.ctypes.data, e.ctypes.data,
                                                          ty.ctypes.data, int(isize_mean), int(isize_sd), rp.ctypes.data, qa.ctypes.data, qq.ctypes.data))
         return rp[:s.size], qa[:s.size], qq[:s.size]
+
+    def set_bam_pin(self, on=True):
+        """Arm (or disarm) this context's BAM loads to keep every read's l_qseq and CIGAR beside the pair table
+        (rsi_hot_set_bam_pin; arming arms the pair table too): what pin_sample and pin_calls need.  fetch("pin_lq" / "pin_coff" /
+        "pin_pool") reads an armed load's arrays: pool[coff[k]] is read k's n_cigar, its CIGAR words follow."""
+        self._check(self.lib.rsi_hot_set_bam_pin(self.ctx, int(bool(on))))
+
+    def stat_calls(self, start, end, type_, p1e, p2e, isize=-1, isize_sd=-1):
+        """RP / Q0 of a list's calls on the chromosome of the last armed load, with cnv_stat's windows given (rsi_hot_stat_calls).
+        Returns (rp int32[], q0 float64[], isize, isize_sd): the insert size to carry to the next chromosome."""
+        a = [np.ascontiguousarray(v, dtype=np.int32).reshape(-1) for v in (start, end, type_, p1e, p2e)]
+        assert all(v.size == a[0].size for v in a)
+        k = a[0].size
+        rp, q0 = np.zeros(max(k, 1), dtype=np.int32), np.zeros(max(k, 1), dtype=np.float64)
+        i1, i2 = C.c_int32(int(isize)), C.c_int32(int(isize_sd))
+        self._check(self.lib.rsi_hot_stat_calls(self.ctx, k, *[v.ctypes.data for v in a], C.byref(i1), C.byref(i2), rp.ctypes.data, q0.ctypes.data))
+        return rp[:k], q0[:k], i1.value, i2.value
+
+    @staticmethod
+    def _pin_dict(st):
+        return {f[0]: getattr(st, f[0]) for f in RsiPinStats._fields_}
+
+    def pin_sample(self):
+        """The depth sample of the last load armed for pin (rsi_hot_pin_sample): l_qseq, rd, rd_sd, drd, drd_sd and the rest of
+        pin_stats().  RsiError RSI_ERR_UNSUPPORTED where the chromosome cannot be sampled as the reference does."""
+        st = RsiPinStats()
+        self._check(self.lib.rsi_hot_pin_sample(self.ctx, C.byref(st)))
+        return self._pin_dict(st)
+
+    def pin_calls(self, m, start, end, type_):
+        """The calls' breakpoints moved (rsi_hot_pin_calls, behind pin_sample): (new_start, new_end, sc1, sc2), int32 arrays."""
+        a = [np.ascontiguousarray(v, dtype=np.int32).reshape(-1) for v in (start, end, type_)]
+        k = a[0].size
+        out = [np.zeros(max(k, 1), dtype=np.int32) for _ in range(4)]
+        self._check(self.lib.rsi_hot_pin_calls(self.ctx, int(m), k, *[v.ctypes.data for v in a], *[v.ctypes.data for v in out]))
+        return tuple(v[:k] for v in out)
+
+    def pin_stats(self):
+        """The CIGAR table of the last load armed for pin, its sample and its last pin_calls (rsi_hot_last_pin_stats); records == 0:
+        no table."""
+        st = RsiPinStats()
+        self._check(self.lib.rsi_hot_last_pin_stats(self.ctx, C.byref(st)))
+        return self._pin_dict(st)
+
+    @staticmethod
+    def _pin_arrays(cigars):
+        lq, coff, pool = (np.ascontiguousarray(np.asarray(a).astype(np.int64) & 0xffffffff, dtype=np.uint32) for a in cigars)
+        return lq.view(np.int32), coff, pool
+
+    def debug_pin_sample(self, table, cigars, tid_len, rd_cap=0):
+        """pin_sample over a caller's pair table and cigars = (lq, coff, pool) (test hook, rsi_hot_debug_pin_sample).  Returns
+        (stats, rd, drd): the last stretch's arrays from its start on, rd_cap entries at the most."""
+        arrs = self._pair_arrays(table)
+        lq, coff, pool = self._pin_arrays(cigars)
+        st = RsiPinStats()
+        rd, drd = np.zeros(max(rd_cap, 1), dtype=np.int32), np.zeros(max(rd_cap, 1), dtype=np.int32)
+        self._check(self.lib.rsi_hot_debug_pin_sample(self.ctx, arrs[0].size, *[a.ctypes.data for a in arrs], lq.ctypes.data, coff.ctypes.data, pool.ctypes.data,
+                                                      pool.size, int(tid_len), C.byref(st), rd.ctypes.data, drd.ctypes.data, int(rd_cap)))
+        return self._pin_dict(st), rd[:rd_cap], drd[:rd_cap]
+
+    def debug_pin_calls(self, table, cigars, tid_len, m, l_qseq, drd_sd, start, end, type_):
+        """pin_calls over a caller's tables with the sample's two results given (test hook, rsi_hot_debug_pin_calls)."""
+        arrs = self._pair_arrays(table)
+        lq, coff, pool = self._pin_arrays(cigars)
+        a = [np.ascontiguousarray(v, dtype=np.int32).reshape(-1) for v in (start, end, type_)]
+        k = a[0].size
+        out = [np.zeros(max(k, 1), dtype=np.int32) for _ in range(4)]
+        self._check(self.lib.rsi_hot_debug_pin_calls(self.ctx, arrs[0].size, *[v.ctypes.data for v in arrs], lq.ctypes.data, coff.ctypes.data, pool.ctypes.data,
+                                                     pool.size, int(tid_len), int(m), int(l_qseq), float(drd_sd), k, *[v.ctypes.data for v in a],
+                                                     *[v.ctypes.data for v in out]))
+        return tuple(v[:k] for v in out)
 
     def bam_read_stats(self):
         """The record reader's side of the last BAM load (rsi_hot_last_bam_read_stats): mode ("host" / "device"), and for the

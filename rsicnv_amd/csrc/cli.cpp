@@ -3,8 +3,8 @@
 // number formatting).  Inputs: a depth file (-d RDFILE -c RNAME, parsed on the device), a whole-genome
 // depth file (-d GENOME.depth without -c: "RNAME pos depth" lines, every chromosome in one pass, each run
 // as soon as its lines are parsed) or a BAM file (-b BAMFILE [-c RNAME], piled up on the device, calls
-// annotated with RP / Q0 from its read pairs); plot, stat and pin are outside the accelerated path
-//  and say so.  A whole-genome file with several depth columns (a cohort, RNAME POS D1 ... DK) is
+// annotated with RP / Q0 from its read pairs); `rsicnv stat` and `rsicnv pin` annotate and sharpen a CNV list (-v CNVFILE) from
+// a BAM (run_cnvlist); plot is outside the accelerated path and says so.  A whole-genome file with several depth columns (a cohort, RNAME POS D1 ... DK) is
 // called sample by sample with -samples all|LIST: one OUT.k per selected column k.  A bedGraph depth file (RNAME START END
 // DEPTH: mosdepth, bedtools genomecov -bg / -bga) runs as the per-base file it stands for, whole or one chromosome (-c).
 // -track FILE saves the depth every chromosome was called from (raw, or GC-adjusted with -trackdepth gc) as one bedGraph file,
@@ -40,11 +40,12 @@
 #include "../../include/rsi_hot.h"
 #include "hostmath.h"
 #include "track_host.h"
+#include "pin_host.h"
 
 namespace {
 
 struct Options {
-  std::string function = "rsi", rdfile, bamfile, reffile, outfile = "rsiout.txt", chr = "1-22XY", plotfolder = "cnv_plots";
+  std::string function = "rsi", rdfile, bamfile, reffile, cnvfile, outfile = "rsiout.txt", chr = "1-22XY", plotfolder = "cnv_plots";
   rsi_params P;
   int minq = 0, min_baseQ = 13, device = 0;
   int gpus = 0;      // -gpus N: chromosomes spread over N devices, several in flight per device (0: one context, one at a time)
@@ -159,6 +160,13 @@ int usage() {
   std::cerr << "Usage:\n\n1. detect CNV\n\n"
             << "   rsicnv rsi <options> [-b BAMFILE | -d RDFILE -c RNAME ] -f REFFILE \n"
             << "   rsicnv rsi <options> -d GENOME.depth -f REFFILE      (every chromosome of a whole-genome depth file)\n"
+            << "\n2. annotate or sharpen a list of CNVs (RNAME START END TYPE ... per line; TYPE holds del / loss or dup / gain / add)\n\n"
+            << "   rsicnv stat <options> -b BAMFILE -v CNVFILE -o OUT   every line with RP=#support_read_pairs;Q0=#fraction_of_Q0_reads appended\n"
+            << "   rsicnv pin  <options> -b BAMFILE -v CNVFILE -o OUT   RNAME START END moved to where clipped reads pile up and the depth\n"
+            << "             steps, the line's other fields, SC=#clipped_reads_at_START;#clipped_reads_at_END; calls below 800 bases and\n"
+            << "             of unknown type stay.  Both take -m, -gpu and -bamread, read each chromosome of the list once (no .bai) and\n"
+            << "             count on the GPU; lines of a chromosome the BAM does not name, or pin cannot sample from 10 Mb on, are\n"
+            << "             written unchanged and OUT.log says why\n"
             << "\nOptions:\n"
             << "   -m   INT  bin size, default=101\n"
             << "   -q   INT  minimum mapping quality, default=0\n"
@@ -260,7 +268,7 @@ void parse(int argc, char** argv, Options& o) {
     if (s == "-d") { o.rdfile = need(i); ++i; }
     else if (s == "-b") { o.bamfile = need(i); ++i; }
     else if (s == "-f") { o.reffile = need(i); ++i; }
-    else if (s == "-v") { need(i); ++i; }
+    else if (s == "-v") { o.cnvfile = need(i); ++i; }
     else if (s == "-o") { o.outfile = need(i); ++i; }
     else if (s == "-c") { o.chr = need(i); o.chr_given = true; ++i; }
     else if (s == "-s") o.saverd = true;
@@ -936,6 +944,111 @@ bool finish_tracks(const Options& o, const std::string& suffix, const TrackParts
   return a && b;
 }
 
+// `rsicnv stat` and `rsicnv pin`: the lines of -v CNVFILE grouped by chromosome, each chromosome's BAM records
+// loaded once with the pair table (and for pin the CIGARs) kept in HBM, the results written back in the file's order.  A line
+// this build cannot serve -- a chromosome the BAM header does not name, a chromosome the sample's limits refuse -- is written
+// as it stands, and the log says why.
+int run_cnvlist(const Options& o) {
+  const bool pin = o.function == "pin";
+  if (o.bamfile.empty()) { std::cerr << "rsicnv " << o.function << ": need a BAM file (-b BAMFILE)" << std::endl; return 1; }
+  if (o.cnvfile.empty()) { std::cerr << "rsicnv " << o.function << ": need a CNV list (-v CNVFILE)" << std::endl; return 1; }
+  if (o.gpus > 1) { std::cerr << "rsicnv " << o.function << ": -gpus: a CNV list runs on one device (-gpu INT picks it)" << std::endl; return 1; }
+  if (!o.bamread.empty() && o.bamread != "device" && o.bamread != "host") {
+    std::cerr << "rsicnv: -bamread " << o.bamread << ": expected device or host" << std::endl;
+    return 1;
+  }
+  std::vector<std::string> names;
+  {
+    std::vector<char> buf(1 << 20);
+    std::vector<int64_t> lens(65536);
+    const int nref = rsi_bam_references(o.bamfile.c_str(), buf.data(), (int)buf.size(), lens.data(), (int)lens.size());
+    if (nref < 0) { std::cerr << "rsicnv " << o.function << ": " << rsi_hot_last_error(nullptr) << std::endl; return 1; }
+    std::istringstream iss(buf.data());
+    std::string nm;
+    while (std::getline(iss, nm)) names.push_back(nm);
+  }
+  std::vector<rsipinh::CnvLine> lines;
+  if (!rsipinh::read_cnvlist(o.cnvfile, names, lines, std::cerr)) return 0;      // the reference says so and exits with 0
+  std::ofstream log((o.outfile + ".log").c_str());
+  std::vector<std::string> rows(lines.size());
+  std::vector<size_t> known;                    // the lines whose chromosome the header names, in file order
+  for (size_t i = 0; i < lines.size(); ++i) {
+    rows[i] = lines[i].text;
+    if (lines[i].tid >= 0) known.push_back(i);
+    else log << "#" << o.function << ": " << lines[i].cell[0] << " is not in the BAM header: line written unchanged\n";
+  }
+  // cnv_stat's windows: DIS travels through the whole file, so they are fixed before the lines are grouped
+  std::vector<rsipinh::CnvLine> known_lines;
+  for (size_t i : known) known_lines.push_back(lines[i]);
+  const std::vector<rsipairs::Call> windows = rsipinh::stat_windows(known_lines);
+  std::vector<int> order;                       // chromosomes by first appearance
+  for (size_t i : known) if (std::find(order.begin(), order.end(), lines[i].tid) == order.end()) order.push_back(lines[i].tid);
+
+  int st = 0;
+  rsi_ctx* ctx = order.empty() ? nullptr : rsi_hot_create(o.device, &st);
+  if (!order.empty() && !ctx) { std::cerr << "rsicnv " << o.function << ": no context on device " << o.device << ": " << rsi_hot_last_error(nullptr) << std::endl; return 1; }
+  struct Destroy { rsi_ctx* c; ~Destroy() { if (c) rsi_hot_destroy(c); } } destroy{ctx};
+  if (ctx && ((!o.bamread.empty() && rsi_hot_set_bam_read(ctx, o.bamread == "device" ? RSI_BAM_READ_DEVICE : RSI_BAM_READ_HOST, 0) != RSI_OK) ||
+              (pin ? rsi_hot_set_bam_pin(ctx, 1) : rsi_hot_set_bam_pairs(ctx, 1)) != RSI_OK)) {
+    std::cerr << "rsicnv " << o.function << ": " << rsi_hot_last_error(ctx) << std::endl;
+    return 1;
+  }
+  int32_t isize = -1, isize_sd = -1;
+  for (int tid : order) {
+    const std::string& chrom = names[(size_t)tid];
+    std::vector<size_t> mine, at;               // this chromosome's lines, and where each stands among the known ones
+    for (size_t k = 0; k < known.size(); ++k) if (lines[known[k]].tid == tid) { mine.push_back(known[k]); at.push_back(k); }
+    std::vector<int32_t> start, end, type;
+    bool sampled = !pin;                        // optimize_resolution samples a chromosome at its first line of 800 bases or more
+    for (size_t i : mine) {
+      start.push_back(lines[i].start); end.push_back(lines[i].end); type.push_back(lines[i].type);
+      if (std::abs((long long)lines[i].end - lines[i].start) >= 800) sampled = true;
+    }
+    auto refuse = [&](const std::string& why) { log << "#" << o.function << ": " << chrom << ": " << why << ": its lines are written unchanged\n"; };
+    if (pin && !sampled) {
+      for (size_t i : mine) rows[i] = rsipinh::pin_row(lines[i], lines[i].start, lines[i].end, 0, 0);
+      continue;
+    }
+    rsi_bam_stats bs;
+    memset(&bs, 0, sizeof(bs));
+    const double t0 = now_s();
+    if (rsi_hot_load_depth_bam(ctx, o.bamfile.c_str(), chrom.c_str(), o.minq, o.min_baseQ, &bs) != RSI_OK) { refuse(rsi_hot_last_error(ctx)); continue; }
+    const double t1 = now_s();
+    const size_t nl = mine.size();
+    if (!pin) {
+      std::vector<int32_t> p1e, p2e, rp(nl);
+      std::vector<double> q0(nl);
+      for (size_t k : at) { p1e.push_back(windows[k].p1e); p2e.push_back(windows[k].p2e); }
+      if (rsi_hot_stat_calls(ctx, (int)nl, start.data(), end.data(), type.data(), p1e.data(), p2e.data(), &isize, &isize_sd, rp.data(), q0.data()) != RSI_OK) {
+        refuse(rsi_hot_last_error(ctx));
+        continue;
+      }
+      for (size_t k = 0; k < nl; ++k) rows[mine[k]] = rsipinh::stat_row(lines[mine[k]], rp[k], q0[k]);
+      log << "#stat: " << chrom << ": " << nl << " lines, " << bs.on_chrom << " reads, ISIZE " << isize << " +- " << isize_sd << ", load " << (t1 - t0) * 1e3
+          << " ms, counts " << (now_s() - t1) * 1e3 << " ms\n";
+      continue;
+    }
+    rsi_pin_stats ps;
+    if (rsi_hot_pin_sample(ctx, &ps) != RSI_OK) { refuse(rsi_hot_last_error(ctx)); continue; }
+    rsipinh::SampleStats ss;
+    ss.l_qseq = ps.l_qseq; ss.rd = ps.rd; ss.rd_sd = ps.rd_sd; ss.drd = ps.drd; ss.drd_sd = ps.drd_sd;
+    log << rsipinh::sample_log(chrom, ss);
+    std::vector<int32_t> ns(nl), ne(nl), sc1(nl), sc2(nl);
+    if (rsi_hot_pin_calls(ctx, o.P.m, (int)nl, start.data(), end.data(), type.data(), ns.data(), ne.data(), sc1.data(), sc2.data()) != RSI_OK) {
+      refuse(rsi_hot_last_error(ctx));
+      continue;
+    }
+    for (size_t k = 0; k < nl; ++k) rows[mine[k]] = rsipinh::pin_row(lines[mine[k]], ns[k], ne[k], sc1[k], sc2[k]);
+    rsi_hot_last_pin_stats(ctx, &ps);
+    log << "#pin: " << chrom << ": " << nl << " lines, " << ps.breakpoints << " breakpoints, window +-" << ps.r_len << ", " << ps.records << " reads, "
+        << ps.table_bytes * 1e-6 << " MB of CIGARs, load " << (t1 - t0) * 1e3 << " ms, sample " << ps.t_sample_ms << " ms, windows " << ps.t_windows_ms
+        << " ms (device)\n";
+  }
+  std::ofstream out(o.outfile.c_str());
+  for (const std::string& r : rows) out << r << "\n";
+  return out.good() ? 0 : 1;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -945,6 +1058,7 @@ int main(int argc, char** argv) {
   rsi_hot_process_setup();
   Options o;
   parse(argc, argv, o);
+  if (o.function == "stat" || o.function == "pin") return run_cnvlist(o);
   if (o.function != "rsi") {
     std::cerr << "rsicnv " << o.function << ": not part of the accelerated read-depth path in this build" << std::endl;
     return 0;

@@ -8,6 +8,8 @@
 #include "pipeline_internal.h"
 #include "inflate_core.h"
 #include "bam_pairs_core.h"
+#include "bam_pin_core.h"
+#include "pin_host.h"
 #include "text_rules.h"
 #include "track_index_host.h"
 #include "ref_host.h"
@@ -826,6 +828,188 @@ int pairs_upload(rsi_ctx* ctx, int64_t n, const int32_t* const arrays[5]) {
   return RSI_OK;
 }
 
+// ---- the kept CIGARs of a load armed for `pin`, and what is computed from them ----
+PinTable pin_table(const rsi_ctx* ctx) {
+  int32_t* b = ctx->pin.tab.as<int32_t>();
+  return PinTable{b, reinterpret_cast<uint32_t*>(b + ctx->pin.cap), ctx->pin.pool.as<uint32_t>()};
+}
+// Room for `need` reads and `pool_need` pool words: larger buffers take over what is written so far, copied on the stream.
+int pin_reserve(rsi_ctx* ctx, size_t need, size_t pool_need) {
+  rsi_ctx::Pin& Q = ctx->pin;
+  if (need > Q.cap) {
+    const size_t cap = std::max(need, Q.cap ? 2 * Q.cap : kPairsFirstCap);
+    DevBuf grown;
+    HIPCHK(grown.ensure(cap * 8));
+    for (int k = 0; k < 2 && Q.n > 0; ++k)
+      HIPCHK(hipMemcpyAsync(grown.as<int32_t>() + (size_t)k * cap, Q.tab.as<int32_t>() + (size_t)k * Q.cap, (size_t)Q.n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    if (Q.tab.p) HIPCHK(hipStreamSynchronize(ctx->stream));
+    std::swap(Q.tab.p, grown.p); std::swap(Q.tab.cap, grown.cap);
+    Q.cap = cap;
+  }
+  if (pool_need > Q.pool_cap) {
+    const size_t cap = std::max(pool_need, Q.pool_cap ? 2 * Q.pool_cap : kPairsFirstCap);
+    if (cap >= (size_t(1) << 32)) return fail(ctx, RSI_ERR_UNSUPPORTED, "the CIGARs of this chromosome's reads take more than 2^32 words");
+    DevBuf grown;
+    HIPCHK(grown.ensure(cap * 4));
+    if (Q.pool.p) {
+      HIPCHK(hipMemcpyAsync(grown.p, Q.pool.p, (size_t)Q.cursor_h * 4, hipMemcpyDeviceToDevice, ctx->stream));
+      HIPCHK(hipStreamSynchronize(ctx->stream));
+    }
+    std::swap(Q.pool.p, grown.p); std::swap(Q.pool.cap, grown.cap);
+    Q.pool_cap = cap;
+  }
+  return RSI_OK;
+}
+// the cursor of the launches so far, on the host (waits for them)
+int pin_read_cursor(rsi_ctx* ctx) {
+  rsi_ctx::Pin& Q = ctx->pin;
+  if (!Q.launched) return RSI_OK;
+  uint32_t c = 0;
+  HIPCHK(hipMemcpyAsync(&c, Q.cursor.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  float ms = 0;
+  if (hipEventElapsedTime(&ms, Q.ev[0], Q.ev[1]) == hipSuccess) Q.t_table_ms += ms;
+  if ((size_t)c > Q.pool_cap) return fail(ctx, RSI_ERR_INTERNAL, "the CIGAR pool was sized too small for a chunk");
+  Q.cursor_h = c;
+  Q.launched = false;
+  return RSI_OK;
+}
+// the pool begins with one word 0, the empty CIGAR; the cursor stands behind it
+int pin_reset(rsi_ctx* ctx) {
+  rsi_ctx::Pin& Q = ctx->pin;
+  Q.valid = Q.sampled = Q.launched = false; Q.n = 0; Q.cursor_h = 1; Q.t_table_ms = 0;
+  Q.stats = rsi_pin_stats{};
+  for (hipEvent_t& e : Q.ev) if (!e) HIPCHK(hipEventCreate(&e));
+  if (int rc = pin_reserve(ctx, 1, 1)) return rc;
+  HIPCHK(Q.cursor.ensure(64));
+  const uint32_t one = 1, zero = 0;
+  HIPCHK(copy_h2d(ctx, Q.cursor.p, &one, 4));
+  HIPCHK(copy_h2d(ctx, Q.pool.p, &zero, 4));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return RSI_OK;
+}
+// Beside a chunk's pairs_append: the chunk's `bytes` bound its CIGAR words (4 n_cigar <= block_size of every record read).
+int pin_append(rsi_ctx* ctx, const void* data, const uint32_t* rec_off, int nrec, size_t bytes) {
+  rsi_ctx::Pin& Q = ctx->pin;
+  if (nrec <= 0) return RSI_OK;
+  if (int rc = pin_read_cursor(ctx)) return rc;
+  if (int rc = pin_reserve(ctx, (size_t)Q.n + (size_t)nrec, (size_t)Q.cursor_h + (size_t)nrec + bytes / 4 + 1)) return rc;
+  HIPCHK(hipEventRecord(Q.ev[0], ctx->stream));
+  launch_bam_pin(data, rec_off, nrec, (long long)Q.n, pin_table(ctx), Q.cursor.as<unsigned int>(), (unsigned int)Q.pool_cap, ctx->stream);
+  HIPCHK(hipEventRecord(Q.ev[1], ctx->stream));
+  Q.n += nrec;
+  Q.launched = true;
+  return RSI_OK;
+}
+int pin_end(rsi_ctx* ctx) {
+  rsi_ctx::Pin& Q = ctx->pin;
+  if (int rc = pin_read_cursor(ctx)) return rc;
+  Q.valid = true;
+  Q.stats.records = Q.n; Q.stats.pool_words = Q.cursor_h; Q.stats.table_bytes = Q.n * 8 + (int64_t)Q.cursor_h * 4;
+  Q.stats.t_table_ms = Q.t_table_ms;
+  return RSI_OK;
+}
+// A caller's arrays in place of a BAM's (the debug hooks), behind pairs_upload.
+int pin_upload(rsi_ctx* ctx, int64_t n, const int32_t* lq, const uint32_t* coff, const uint32_t* pool, int64_t npool) {
+  rsi_ctx::Pin& Q = ctx->pin;
+  if (int rc = pin_reset(ctx)) return rc;
+  if (int rc = pin_reserve(ctx, (size_t)std::max<int64_t>(n, 1), (size_t)std::max<int64_t>(npool, 1))) return rc;
+  if (n > 0) {
+    HIPCHK(hipMemcpyAsync(Q.tab.p, lq, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(Q.tab.as<int32_t>() + Q.cap, coff, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+  }
+  if (npool > 0) HIPCHK(hipMemcpyAsync(Q.pool.p, pool, (size_t)npool * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  Q.n = n; Q.cursor_h = (uint32_t)npool;
+  return RSI_OK;
+}
+double pin_elapsed(rsi_ctx* ctx) {
+  float ms = 0;
+  return hipEventElapsedTime(&ms, ctx->pin.ev[0], ctx->pin.ev[1]) == hipSuccess ? ms : 0.0;
+}
+// The depth sample over table[0, n) (behind pairs_sample on the same table, whose workspace it reads).  rd / drd: when given,
+// the last stretch's arrays from its start on, rd_cap entries at the most.
+int pin_sample(rsi_ctx* ctx, PairTable t, PinTable p, int64_t n, int64_t tid_len, int32_t* rd_out, int32_t* drd_out, int64_t rd_cap) {
+  rsi_ctx::Pin& Q = ctx->pin;
+  Q.sampled = false;
+  int64_t sums[4];
+  if (int rc = pairs_sample(ctx, t, n, tid_len, sums)) return rc;
+  HIPCHK(Q.rdc.ensure((size_t)kPinRdcWords * 4));
+  HIPCHK(Q.drd.ensure((size_t)kPinRdcWords * 4));
+  HIPCHK(Q.scan.ensure((size_t)scan_tiles(kPinRdcWords) * 4 + 64));
+  HIPCHK(Q.state.ensure(64));
+  HIPCHK(hipEventRecord(Q.ev[0], ctx->stream));
+  launch_pin_sample(t, p, (long long)n, (long long)tid_len, ctx->pairs.ws.p, Q.rdc.as<int32_t>(), Q.scan.as<int32_t>(), Q.state.p, ctx->stream);
+  HIPCHK(hipEventRecord(Q.ev[1], ctx->stream));
+  rsipin::SampleState st;
+  HIPCHK(copy_d2h(ctx, &st, Q.state.p, sizeof(st)));
+  HIPCHK(CTX_SYNC());
+  Q.stats.t_sample_ms = pin_elapsed(ctx);
+  if (st.count <= 0) return fail(ctx, RSI_ERR_UNSUPPORTED, "no read from position 10000000 on passes the sample's filters");
+  if (st.flags & rsipin::kGrows) return fail(ctx, RSI_ERR_UNSUPPORTED, "a sampled read ends more than 1000900 bases behind its stretch's start");
+  const int l_qseq = rsipinh::l_qseq_of(st.lq_sum, st.count);
+  if (l_qseq < 1) return fail(ctx, RSI_ERR_UNSUPPORTED, "the sampled reads have no sequence (read length " + std::to_string(l_qseq) + ")");
+  const int64_t len = (int64_t)st.pos_end - st.pos_start, q = l_qseq / 4;
+  if (len + q > rsipin::kRdcSize) return fail(ctx, RSI_ERR_UNSUPPORTED, "the sample's read length does not fit its depth array");
+  const int lo = (int)q, hi = (int)std::max<int64_t>(len - q, q);
+  HIPCHK(hipMemsetAsync(Q.drd.p, 0, (size_t)std::max<int64_t>(len, 1) * 4, ctx->stream));
+  HIPCHK(hipEventRecord(Q.ev[0], ctx->stream));
+  launch_pin_sample_drd(Q.rdc.as<int32_t>(), Q.drd.as<int32_t>(), lo, hi, l_qseq, ctx->stream);
+  HIPCHK(hipEventRecord(Q.ev[1], ctx->stream));
+  std::vector<int32_t> rd((size_t)std::max<int64_t>(len, 1)), drd(rd.size());
+  HIPCHK(copy_d2h(ctx, rd.data(), Q.rdc.p, rd.size() * 4));
+  HIPCHK(copy_d2h(ctx, drd.data(), Q.drd.p, drd.size() * 4));
+  HIPCHK(CTX_SYNC());
+  Q.stats.t_sample_ms += pin_elapsed(ctx);
+  const rsipinh::SampleStats s = rsipinh::sample_stats(rd.data(), drd.data(), (int)len, l_qseq);
+  Q.stats.sample_reads = st.count; Q.stats.pos_start = st.pos_start; Q.stats.pos_end = st.pos_end;
+  Q.stats.l_qseq = s.l_qseq; Q.stats.rd = s.rd; Q.stats.rd_sd = s.rd_sd; Q.stats.drd = s.drd; Q.stats.drd_sd = s.drd_sd;
+  for (int64_t k = 0; k < std::min<int64_t>(rd_cap, len); ++k) { if (rd_out) rd_out[k] = rd[(size_t)k]; if (drd_out) drd_out[k] = drd[(size_t)k]; }
+  Q.sampled = true;
+  return RSI_OK;
+}
+// The breakpoints of the calls over table[0, n), ascending in pos.
+int pin_calls(rsi_ctx* ctx, PairTable t, PinTable p, int64_t n, int maxspan, int64_t tid_len, int m, int l_qseq, double drd_sd, int ncalls,
+              const int32_t* start, const int32_t* end, const int32_t* type, int32_t* new_start, int32_t* new_end, int32_t* sc1, int32_t* sc2) {
+  rsi_ctx::Pin& Q = ctx->pin;
+  const int r_len = rsipin::r_len_of(m, l_qseq);
+  Q.stats.r_len = r_len; Q.stats.breakpoints = 0; Q.stats.t_windows_ms = 0;
+  std::vector<rsipin::Bp> bps;
+  std::vector<int> owner;
+  for (int i = 0; i < ncalls; ++i) {
+    new_start[i] = start[i]; new_end[i] = end[i]; sc1[i] = sc2[i] = 0;
+    if (!rsipin::call_pinned(start[i], end[i], type[i])) continue;
+    rsipin::Bp b[2];
+    rsipin::bps_of(start[i], end[i], type[i], b);
+    bps.push_back(b[0]); bps.push_back(b[1]);
+    owner.push_back(i);
+  }
+  if (bps.empty()) return RSI_OK;
+  if (l_qseq < 1) return fail(ctx, RSI_ERR_BAD_ARG, "read length below 1");
+  if (r_len > kPinMaxRlen)
+    return fail(ctx, RSI_ERR_UNSUPPORTED, "a window of " + std::to_string(r_len) + " bases on each side does not fit the workgroup's LDS (at most " +
+                                              std::to_string(kPinMaxRlen) + ")");
+  HIPCHK(Q.bps.ensure(bps.size() * sizeof(rsipin::Bp)));
+  HIPCHK(Q.out.ensure(bps.size() * 8));
+  HIPCHK(copy_h2d(ctx, Q.bps.p, bps.data(), bps.size() * sizeof(rsipin::Bp)));
+  HIPCHK(hipEventRecord(Q.ev[0], ctx->stream));
+  launch_pin_windows(t, p, (long long)n, maxspan, (long long)tid_len, Q.bps.p, (int)bps.size(), r_len, l_qseq, drd_sd, Q.out.as<int32_t>(), ctx->stream);
+  HIPCHK(hipEventRecord(Q.ev[1], ctx->stream));
+  std::vector<int32_t> res(bps.size() * 2);
+  HIPCHK(copy_d2h(ctx, res.data(), Q.out.p, res.size() * 4));
+  HIPCHK(CTX_SYNC());
+  Q.stats.t_windows_ms = pin_elapsed(ctx);
+  Q.stats.breakpoints = (int64_t)bps.size();
+  for (size_t c = 0; c < owner.size(); ++c) {
+    const int i = owner[c];
+    const int32_t* r = res.data() + 4 * c;
+    sc1[i] = r[1]; sc2[i] = r[3];
+    new_start[i] = rsipin::moved(start[i], r_len, r[0], r[1]);
+    new_end[i] = rsipin::moved(end[i], r_len, r[2], r[3]);
+  }
+  return RSI_OK;
+}
+
 // rsi_hot_load_depth_bam's chunks in RSI_BAM_READ_DEVICE mode.  Per chunk the host walks member headers, copies
 // the deflate payloads into a pinned buffer and builds the member table; upload and launch_inflate_bgzf run on a stream of
 // their own (istream), so the next chunk is inflated while the current chunk's records are found (guess, walk, stitch) and piled
@@ -965,6 +1149,7 @@ int bam_chunks_device(rsi_ctx* ctx, const char* bam_path, const rsih::BamFile& b
       if (rep.end > total || rep.listed > (uint32_t)kBamMaxSegs * kBamListCap) return fail(ctx, RSI_ERR_INTERNAL, "BAM device read: the record finder's report is out of range");
       if (rep.listed) { Timer t(ctx, "bam_depth"); launch_bam_depth(data, D.rec.as<uint32_t>(), (int)rep.listed, tid, minq, min_baseq, (long long)n, d_diff, d_stats, ctx->stream); }
       if (ctx->pairs.armed) if (int rc = pairs_append(ctx, data, D.rec.as<uint32_t>(), (int)rep.listed, tid)) return rc;
+      if (ctx->pin.armed) if (int rc = pin_append(ctx, data, D.rec.as<uint32_t>(), (int)rep.listed, (size_t)rep.end)) return rc;
     }
     const bool finished = (rep.flags & rsibam::kBeyond) || !more;
     carry = finished ? 0 : total - rep.end;
@@ -1067,6 +1252,8 @@ int rsi_hot_load_depth_bam(rsi_ctx* ctx, const char* bam_path, const char* chrom
   HIPCHK(hipMemsetAsync(d_stats, 0, sizeof(BamDepthStats), ctx->stream));
   ctx->pairs.valid = false;              // whatever table the context held was the load before's
   if (ctx->pairs.armed) if (int rc = pairs_begin(ctx)) return rc;
+  ctx->pin.valid = ctx->pin.sampled = false;
+  if (ctx->pin.armed) if (int rc = pin_reset(ctx)) return rc;
 
   // behind the last chunk, in either mode: the difference array scanned into the depth, the pileup's counts
   auto finish = [&]() -> int {
@@ -1078,6 +1265,7 @@ int rsi_hot_load_depth_bam(rsi_ctx* ctx, const char* bam_path, const char* chrom
     { const double tq = now_ms(); HIPCHK(hipStreamSynchronize(ctx->stream)); st->t_wait_ms += now_ms() - tq; }
     st->used = (int64_t)hs.used; st->runs = (int64_t)hs.runs; st->malformed = (int64_t)hs.malformed;
     if (ctx->pairs.armed) pairs_end(ctx, pw, tid, n);
+    if (ctx->pin.armed) if (int rc = pin_end(ctx)) return rc;
     st->t_total_ms = now_ms() - t0;
     return RSI_OK;
   };
@@ -1222,6 +1410,7 @@ int rsi_hot_load_depth_bam(rsi_ctx* ctx, const char* bam_path, const char* chrom
       HIPCHK(hipMemcpyAsync(d_off, offs.data(), offs.size() * 4, hipMemcpyHostToDevice, ctx->stream));
       { Timer t(ctx, "bam_depth"); launch_bam_depth(ctx->text_dev[cur].p, d_off, (int)offs.size(), tid, minq, min_baseq, (long long)n, d_diff, d_stats, ctx->stream); }
       if (ctx->pairs.armed) if (int rc = pairs_append(ctx, ctx->text_dev[cur].p, d_off, (int)offs.size(), tid)) return rc;
+      if (ctx->pin.armed) if (int rc = pin_append(ctx, ctx->text_dev[cur].p, d_off, (int)offs.size(), len - start)) return rc;
       HIPCHK(hipEventRecord(done[cur], ctx->stream));
       used[cur] = true;
     }
@@ -1320,6 +1509,127 @@ int rsi_hot_debug_pair_annotate(rsi_ctx* ctx, int64_t n, const int32_t* pos, con
   if (int rc = pairs_annotate(ctx, pair_table(ctx), n, (int)std::min<int64_t>(maxspan, INT32_MAX), calls, isize_mean, isize_sd, counts)) return rc;
   for (int i = 0; i < ncalls; ++i) { q0all_out[i] = counts[4 * (size_t)i]; q0q0_out[i] = counts[4 * (size_t)i + 1]; rp_out[i] = counts[4 * (size_t)i + 2]; }
   return RSI_OK;
+}
+
+// ---- `stat` and `pin` ----
+namespace {
+// the refusals every entry point over a BAM's table shares
+int table_usable(rsi_ctx* ctx) {
+  const rsi_ctx::Pairs& P = ctx->pairs;
+  if (!P.valid) return fail(ctx, RSI_ERR_BAD_ARG, "no pair table: the context's last BAM load was not armed (rsi_hot_set_bam_pairs)");
+  if (P.flags & rsipairs::kUnsorted) return fail(ctx, RSI_ERR_UNSUPPORTED, "BAM not sorted by position");
+  if (P.flags & rsipairs::kOverrun) return fail(ctx, RSI_ERR_BAD_ARG, "malformed BAM record (name / CIGAR overrun the record)");
+  return RSI_OK;
+}
+int pin_usable(rsi_ctx* ctx) {
+  if (int rc = table_usable(ctx)) return rc;
+  if (!ctx->pin.valid || ctx->pin.n != ctx->pairs.n) return fail(ctx, RSI_ERR_BAD_ARG, "no CIGAR table: the context's last BAM load was not armed (rsi_hot_set_bam_pin)");
+  return RSI_OK;
+}
+int debug_tables(rsi_ctx* ctx, int64_t n, const int32_t* const arrays[5], const int32_t* lq, const uint32_t* coff, const uint32_t* pool, int64_t npool,
+                 int64_t* maxspan) {
+  if (n < 0 || n >= (1ll << 31) || npool < 1 || npool >= (1ll << 32) || !pool || (n > 0 && (!arrays[0] || !arrays[1] || !arrays[2] || !arrays[3] || !arrays[4] || !lq || !coff)))
+    return fail(ctx, RSI_ERR_BAD_ARG, "bad argument");
+  *maxspan = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    if (i > 0 && arrays[0][i] < arrays[0][i - 1]) return fail(ctx, RSI_ERR_UNSUPPORTED, "BAM not sorted by position");
+    if ((int64_t)coff[i] >= npool || (int64_t)coff[i] + 1 + (int64_t)pool[coff[i]] > npool) return fail(ctx, RSI_ERR_BAD_ARG, "a CIGAR lies outside the pool");
+    *maxspan = std::max(*maxspan, (int64_t)arrays[1][i] - (int64_t)arrays[0][i]);
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!ctx_enter(ctx)) return RSI_ERR_HIP;
+  mailbox_reset(ctx);
+  if (int rc = pairs_upload(ctx, n, arrays)) return rc;
+  return pin_upload(ctx, n, lq, coff, pool, npool);
+}
+}  // namespace
+
+int rsi_hot_set_bam_pin(rsi_ctx* ctx, int on) {
+  if (!ctx) return fail(ctx, RSI_ERR_BAD_ARG, "null context");
+  ctx->pin.armed = on != 0;
+  if (on) ctx->pairs.armed = true;       // the CIGARs lie beside the pair table's entries
+  return RSI_OK;
+}
+int rsi_hot_last_pin_stats(const rsi_ctx* ctx, rsi_pin_stats* out) {
+  if (!ctx || !out) return RSI_ERR_BAD_ARG;
+  *out = ctx->pin.valid ? ctx->pin.stats : rsi_pin_stats{};
+  return RSI_OK;
+}
+
+int rsi_hot_stat_calls(rsi_ctx* ctx, int ncalls, const int32_t* start, const int32_t* end, const int32_t* type, const int32_t* p1e, const int32_t* p2e,
+                       int32_t* isize_io, int32_t* isize_sd_io, int32_t* rp, double* q0) {
+  if (!ctx || ncalls < 0 || !isize_io || !isize_sd_io || (ncalls > 0 && (!start || !end || !type || !p1e || !p2e || !rp || !q0)))
+    return fail(ctx, RSI_ERR_BAD_ARG, "bad argument");
+  if (int rc = table_usable(ctx)) return rc;
+  rsi_ctx::Pairs& P = ctx->pairs;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!ctx_enter(ctx)) return RSI_ERR_HIP;
+  mailbox_reset(ctx);
+  int64_t sums[4];
+  if (int rc = pairs_sample(ctx, pair_table(ctx), P.n, P.tid_len, sums)) return rc;
+  const rsih::PairSample ps = pairs_sample_result(sums);
+  P.stats.isize = ps.isize; P.stats.isize_sd = ps.isize_sd;
+  if (sums[0] > 2) { *isize_io = ps.isize; *isize_sd_io = ps.isize_sd; }    // (isize_c > 2: else bamstat_st keeps what it had)
+  std::vector<rsipairs::Call> calls((size_t)ncalls);
+  for (int i = 0; i < ncalls; ++i) {
+    const int32_t b = std::min(start[i], end[i]), e = std::max(start[i], end[i]);
+    calls[(size_t)i] = rsipairs::Call{b, e, type[i], e - b + 1, p1e[i], p2e[i]};
+  }
+  std::vector<uint32_t> counts;
+  if (int rc = pairs_annotate(ctx, pair_table(ctx), P.n, P.maxspan, calls, *isize_io, *isize_sd_io, counts)) return rc;
+  for (int i = 0; i < ncalls; ++i) {
+    const double q0_all = (double)counts[4 * (size_t)i], q0_q0 = (double)counts[4 * (size_t)i + 1];
+    rp[i] = (int32_t)counts[4 * (size_t)i + 2];
+    q0[i] = q0_q0 / (q0_all + 0.00001);
+  }
+  return RSI_OK;
+}
+
+int rsi_hot_pin_sample(rsi_ctx* ctx, rsi_pin_stats* out) {
+  if (!ctx) return fail(ctx, RSI_ERR_BAD_ARG, "null context");
+  if (int rc = pin_usable(ctx)) return rc;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!ctx_enter(ctx)) return RSI_ERR_HIP;
+  mailbox_reset(ctx);
+  const int rc = pin_sample(ctx, pair_table(ctx), pin_table(ctx), ctx->pairs.n, ctx->pairs.tid_len, nullptr, nullptr, 0);
+  if (out) *out = ctx->pin.stats;
+  return rc;
+}
+
+int rsi_hot_pin_calls(rsi_ctx* ctx, int m, int ncalls, const int32_t* start, const int32_t* end, const int32_t* type, int32_t* new_start,
+                      int32_t* new_end, int32_t* sc1, int32_t* sc2) {
+  if (!ctx || ncalls < 0 || (ncalls > 0 && (!start || !end || !type || !new_start || !new_end || !sc1 || !sc2))) return fail(ctx, RSI_ERR_BAD_ARG, "bad argument");
+  if (int rc = pin_usable(ctx)) return rc;
+  if (!ctx->pin.sampled) return fail(ctx, RSI_ERR_BAD_ARG, "no sample: rsi_hot_pin_sample comes first");
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!ctx_enter(ctx)) return RSI_ERR_HIP;
+  mailbox_reset(ctx);
+  return pin_calls(ctx, pair_table(ctx), pin_table(ctx), ctx->pairs.n, ctx->pairs.maxspan, ctx->pairs.tid_len, m, ctx->pin.stats.l_qseq,
+                   ctx->pin.stats.drd_sd, ncalls, start, end, type, new_start, new_end, sc1, sc2);
+}
+
+int rsi_hot_debug_pin_sample(rsi_ctx* ctx, int64_t n, const int32_t* pos, const int32_t* rend, const int32_t* mpos, const int32_t* isize,
+                             const int32_t* info, const int32_t* lq, const uint32_t* coff, const uint32_t* pool, int64_t npool, int64_t tid_len,
+                             rsi_pin_stats* out, int32_t* rd, int32_t* drd, int64_t rd_cap) {
+  if (!ctx || !out) return fail(ctx, RSI_ERR_BAD_ARG, "bad argument");
+  const int32_t* const arrays[5] = {pos, rend, mpos, isize, info};
+  int64_t maxspan = 0;
+  if (int rc = debug_tables(ctx, n, arrays, lq, coff, pool, npool, &maxspan)) return rc;
+  const int rc = pin_sample(ctx, pair_table(ctx), pin_table(ctx), n, tid_len, rd, drd, rd_cap);
+  *out = ctx->pin.stats;
+  return rc;
+}
+
+int rsi_hot_debug_pin_calls(rsi_ctx* ctx, int64_t n, const int32_t* pos, const int32_t* rend, const int32_t* mpos, const int32_t* isize,
+                            const int32_t* info, const int32_t* lq, const uint32_t* coff, const uint32_t* pool, int64_t npool, int64_t tid_len,
+                            int m, int l_qseq, double drd_sd, int ncalls, const int32_t* start, const int32_t* end, const int32_t* type,
+                            int32_t* new_start, int32_t* new_end, int32_t* sc1, int32_t* sc2) {
+  if (!ctx || ncalls < 0 || (ncalls > 0 && (!start || !end || !type || !new_start || !new_end || !sc1 || !sc2))) return fail(ctx, RSI_ERR_BAD_ARG, "bad argument");
+  const int32_t* const arrays[5] = {pos, rend, mpos, isize, info};
+  int64_t maxspan = 0;
+  if (int rc = debug_tables(ctx, n, arrays, lq, coff, pool, npool, &maxspan)) return rc;
+  return pin_calls(ctx, pair_table(ctx), pin_table(ctx), n, (int)std::min<int64_t>(maxspan, INT32_MAX), tid_len, m, l_qseq, drd_sd, ncalls, start, end, type,
+                   new_start, new_end, sc1, sc2);
 }
 
 int rsi_bam_references(const char* bam_path, char* names, int names_cap, int64_t* lengths, int max_refs) {

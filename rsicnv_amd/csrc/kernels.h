@@ -588,6 +588,32 @@ void launch_pair_sample(PairTable t, long long n, long long tid_len, void* ws, u
 // ascending in pos; maxspan: the largest rend - pos in it.
 void launch_pairs_annotate(PairTable t, long long n, int maxspan, const void* calls, int ncalls, int isize_mean, int isize_sd, uint32_t* out,
                            hipStream_t stream);
+// What launch_pair_sample leaves in its workspace for the kernels behind it: the stop word (the stopping record's table index,
+// 0xffffffff: none) at its start, and every tile's prefix (rsipairs::Seg per tile).
+const void* pair_sample_tile_pre(const void* ws, long long n);
+
+// ---- `pin`: the kept CIGARs, the depth sample, one workgroup per breakpoint (kernels_pin.hip, bam_pin_core.h) ----
+// Beside the pair table, entry for entry: lq = l_qseq, coff = the read's place in the pool (pool[coff] = n_cigar, then its words).
+struct PinTable { int32_t* lq; uint32_t* coff; uint32_t* pool; };
+// One thread per entry of rec_off[], beside launch_bam_pairs.  *cursor: the pool words taken so far; a wave takes its reads'
+// words with one atomicAdd.  pool_cap: words the pool has room for -- the caller makes it cursor + nrec + (bytes of the chunk) / 4
+// at least, which no chunk's CIGARs exceed; a read that would not fit all the same is not copied and *cursor still grows.
+// A record whose name and CIGAR overrun its block_size gets n_cigar 0 (the pair kernel flags it; its CIGAR is not read).
+void launch_bam_pin(const void* data, const uint32_t* rec_off, int nrec, long long base, PinTable t, unsigned int* cursor, unsigned int pool_cap,
+                    hipStream_t stream);
+// The depth sample behind launch_pair_sample (same table, n, tid_len and workspace ws).  rdc: kPinRdcWords int32, scan_scratch:
+// scan_tiles(kPinRdcWords) ints.  Afterwards rdc[0, 1 001 000) holds the sample's rd, each read counted at its own stretch's
+// offset, and *state (rsipin::SampleState, device) what the loop leaves behind.
+constexpr int kPinRdcWords = 1001000 + 8;
+void launch_pin_sample(PairTable t, PinTable p, long long n, long long tid_len, const void* ws, int32_t* rdc, int32_t* scan_scratch, void* state,
+                       hipStream_t stream);
+// drd[k] for k in [lo, hi) of the sample's last stretch (rsipin::sample_drd)
+void launch_pin_sample_drd(const int32_t* rdc, int32_t* drd, int lo, int hi, int l_qseq, hipStream_t stream);
+// One workgroup per breakpoint: bps[nbp] (rsipin::Bp), out[2 * nbp]: i_max (-1: none) and the clip count there.  3 (2 r_len + 1)
+// counters in LDS: r_len <= kPinMaxRlen.
+constexpr int kPinMaxRlen = 2559;
+void launch_pin_windows(PairTable t, PinTable p, long long n, int maxspan, long long tid_len, const void* bps, int nbp, int r_len, int l_qseq,
+                        double drd_sd, int32_t* out, hipStream_t stream);
 
 // ---- depth track: an int32 array as bedGraph text, run-length encoded and formatted on the device (kernels_track.hip) ----
 // One line "NAME \t pos0+start \t pos0+end \t value \n" per maximal run of equal values of v[0, n), worked through in slices

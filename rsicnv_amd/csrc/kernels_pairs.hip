@@ -5,16 +5,13 @@
 // bam_pairs_core.h's, the host harness's own.
 #include "kernels.h"
 #include "bam_pairs_core.h"
+#include "pairs_scan_device.h"
 
 namespace rsik {
 
 namespace {
 
 using rsipairs::Seg;
-
-constexpr int kPairThreads = 256;
-constexpr int kItems = kPairSampleTile / kPairThreads;     // consecutive records per thread of a sample tile
-static_assert(kItems * kPairThreads == kPairSampleTile, "a tile is whole threads");
 
 __global__ __launch_bounds__(kPairThreads) void k_bam_pairs(const uint8_t* __restrict__ data, const uint32_t* __restrict__ rec_off, int nrec, int tid,
                                                             long long base, PairTable t, int32_t* __restrict__ words, int parity) {
@@ -37,35 +34,10 @@ __global__ __launch_bounds__(kPairThreads) void k_bam_pairs(const uint8_t* __res
   if (i == nrec - 1) words[2 + (parity ^ 1)] = e.pos;
 }
 
-// Inclusive scan of one Seg per thread under rsipairs::compose (not commutative: the left operand is the lower thread).  On
-// return s[t] holds thread t's result too.
-__device__ inline Seg block_scan(Seg v, Seg* s) {
-  const int t = threadIdx.x;
-  s[t] = v;
-  __syncthreads();
-  for (int d = 1; d < kPairThreads; d <<= 1) {
-    const Seg a = t >= d ? s[t - d] : rsipairs::seg_none();
-    __syncthreads();
-    if (t >= d) { v = rsipairs::compose(a, v); s[t] = v; }
-    __syncthreads();
-  }
-  return v;
-}
-
-// the kept records among a thread's kItems, joined
-__device__ inline Seg thread_seg(const PairTable& t, long long i0, long long n) {
-  Seg v = rsipairs::seg_none();
-  for (int k = 0; k < kItems; ++k) {
-    const long long i = i0 + k;
-    if (i < n && rsipairs::sample_kept(t.pos[i], t.rend[i], t.info[i])) v = rsipairs::compose(v, rsipairs::seg_one(t.pos[i]));
-  }
-  return v;
-}
-
 __global__ __launch_bounds__(kPairThreads) void k_pair_sample_tiles(PairTable t, long long n, Seg* __restrict__ tile_sum) {
   __shared__ Seg s[kPairThreads];
-  const long long i0 = (long long)blockIdx.x * kPairSampleTile + (long long)threadIdx.x * kItems;
-  const Seg v = block_scan(thread_seg(t, i0, n), s);
+  const long long i0 = (long long)blockIdx.x * kPairSampleTile + (long long)threadIdx.x * kPairItems;
+  const Seg v = pair_block_scan(pair_thread_seg(t, i0, n), s);
   if (threadIdx.x == kPairThreads - 1) tile_sum[blockIdx.x] = v;
 }
 
@@ -79,7 +51,7 @@ __global__ __launch_bounds__(kPairThreads) void k_pair_sample_scan(const Seg* __
   Seg carry = rsipairs::seg_none();
   for (long long c0 = 0; c0 < ntiles; c0 += kPairThreads) {
     const long long b = c0 + t;
-    block_scan(b < ntiles ? tile_sum[b] : rsipairs::seg_none(), s);
+    pair_block_scan(b < ntiles ? tile_sum[b] : rsipairs::seg_none(), s);
     if (b < ntiles) tile_pre[b] = rsipairs::compose(carry, t ? s[t - 1] : rsipairs::seg_none());
     carry = rsipairs::compose(carry, s[kPairThreads - 1]);
     __syncthreads();
@@ -90,10 +62,10 @@ __global__ __launch_bounds__(kPairThreads) void k_pair_sample_scan(const Seg* __
 __global__ __launch_bounds__(kPairThreads) void k_pair_sample_stop(PairTable t, long long n, long long tid_len, const Seg* __restrict__ tile_pre,
                                                                    unsigned int* __restrict__ stop) {
   __shared__ Seg s[kPairThreads];
-  const long long i0 = (long long)blockIdx.x * kPairSampleTile + (long long)threadIdx.x * kItems;
-  block_scan(thread_seg(t, i0, n), s);
+  const long long i0 = (long long)blockIdx.x * kPairSampleTile + (long long)threadIdx.x * kPairItems;
+  pair_block_scan(pair_thread_seg(t, i0, n), s);
   Seg p = rsipairs::compose(tile_pre[blockIdx.x], threadIdx.x ? s[threadIdx.x - 1] : rsipairs::seg_none());
-  for (int k = 0; k < kItems; ++k) {
+  for (int k = 0; k < kPairItems; ++k) {
     const long long i = i0 + k;
     if (i >= n) break;
     const int32_t pos = t.pos[i], rend = t.rend[i];
@@ -138,15 +110,6 @@ __global__ __launch_bounds__(kPairThreads) void k_pair_sample_sum(PairTable t, l
   }
 }
 
-__device__ inline uint32_t lower_bound_pos(const int32_t* __restrict__ pos, uint32_t n, long long key) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t mid = lo + (hi - lo) / 2;
-    if ((long long)pos[mid] < key) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
 __global__ __launch_bounds__(kPairThreads) void k_pairs_annotate(PairTable t, uint32_t n, int maxspan, const rsipairs::Call* __restrict__ calls,
                                                                  int isize_mean, int isize_sd, uint32_t* __restrict__ out) {
   __shared__ uint32_t s_part[kPairThreads / 64][3];
@@ -184,6 +147,10 @@ void launch_bam_pairs(const void* data, const uint32_t* rec_off, int nrec, int t
 }
 
 size_t pair_sample_workspace_bytes(long long n) { return 256 + 2 * (size_t)(sample_tiles(n) + 1) * sizeof(Seg); }
+
+const void* pair_sample_tile_pre(const void* ws, long long n) {
+  return reinterpret_cast<const Seg*>(static_cast<const char*>(ws) + 256) + sample_tiles(n) + 1;
+}
 
 void launch_pair_sample(PairTable t, long long n, long long tid_len, void* ws, unsigned long long* out, hipStream_t stream) {
   const long long ntiles = sample_tiles(n);

@@ -1565,6 +1565,7 @@ void rsi_hot_destroy(rsi_ctx* ctx) {
   }
   if (ctx->bamdev.istream) (void)hipStreamDestroy(ctx->bamdev.istream);
   for (hipEvent_t e : ctx->pairs.events) (void)hipEventDestroy(e);
+  for (hipEvent_t e : ctx->pin.ev) if (e) (void)hipEventDestroy(e);
   if (ctx->sync_ev) (void)hipEventDestroy(ctx->sync_ev);
   if (ctx->copy_ev) (void)hipEventDestroy(ctx->copy_ev);   // (copy_stream is the device's shared one: never destroyed)
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -1760,6 +1761,11 @@ int64_t rsi_hot_fetch_i32(rsi_ctx* ctx, const char* name, int32_t* out, int64_t 
   else if (s.rfind("pairs_", 0) == 0 && ctx->pairs.valid) {   // the pair table of the last armed BAM load
     static const char* kArrays[5] = {"pairs_pos", "pairs_rend", "pairs_mpos", "pairs_isize", "pairs_info"};
     for (int k = 0; k < 5; ++k) if (s == kArrays[k]) { src = ctx->pairs.tab.as<int32_t>() + (size_t)k * ctx->pairs.cap; cnt = ctx->pairs.n; }
+  }
+  else if (s.rfind("pin_", 0) == 0 && ctx->pin.valid) {       // the kept CIGARs of the last load armed for `pin`
+    if (s == "pin_lq") { src = ctx->pin.tab.p; cnt = ctx->pin.n; }
+    if (s == "pin_coff") { src = ctx->pin.tab.as<int32_t>() + ctx->pin.cap; cnt = ctx->pin.n; }
+    if (s == "pin_pool") { src = ctx->pin.pool.p; cnt = ctx->pin.cursor_h; }
   }
   else if (s == "binmedint") { src = ctx->binmed.p; cnt = ctx->nb; }
   else if (s == "status1") { src = ctx->status1.p; cnt = ctx->nb; }

@@ -179,7 +179,20 @@ struct rsi_ctx {
     size_t ev_next = 0;
     rsi_pairs_stats stats{};
   } pairs;
-  int64_t n_in = 0;                         // length of the depth currently in in_depth
+  // `pin` (rsi_hot_set_bam_pin; ingest.hip): nothing of it exists until the first armed load.  tab: lq and coff,
+  // `cap` entries each, one behind the other, entry for entry beside the pair table; pool: the CIGAR words, pool_cap of them.
+  struct Pin {
+    bool armed = false, valid = false, sampled = false;
+    DevBuf tab, pool, cursor, rdc, drd, scan, state, bps, out;
+    size_t cap = 0, pool_cap = 0;
+    int64_t n = 0;                             // entries written (the pair table's count)
+    uint32_t cursor_h = 1;                     // pool words taken by the launches waited for so far
+    bool launched = false;                     // a k_bam_pin launch whose cursor the host has not read yet
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    double t_table_ms = 0;
+    rsi_pin_stats stats{};
+  } pin;
+  int64_t n_in = 0;                        // length of the depth currently in in_depth
   DevBuf gcbits, nbits, rd_gc, rdc, binmed, binsum, tnb, tmed, first_del;
   DevBuf depth8, rescaled8;   // byte copies: the raw depth (K2 writes it, K3' streams it), the rescaled depth (K3' -> K4')
   DevBuf slabs;   // per-workgroup partial results of the streaming kernels

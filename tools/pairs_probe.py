@@ -42,7 +42,11 @@ def synth_paired_bam(path, n, cov, read_len=100, seed=7):
     put(8, "<i4", pos)
     a[:, 12] = 9
     a[:, 13] = np.where(rng.random(nreads) < 0.05, 0, rng.integers(20, 61, nreads))
-    put(14, "<u2", np.full(nreads, 4681))
+    bins = np.full(nreads, -1, dtype=np.int64)               # reg2bin(pos, pos + L - 5): samtools' own index is built from this field
+    for shift, first in ((14, 4681), (17, 585), (20, 73), (23, 9), (26, 1)):
+        m = (bins < 0) & ((pos >> shift) == ((pos + L - 6) >> shift))
+        bins[m] = first + (pos[m] >> shift)
+    put(14, "<u2", np.maximum(bins, 0))
     put(16, "<u2", np.full(nreads, 2))
     put(18, "<u2", np.full(nreads, 0x1 | 0x2 | 0x20 | 0x40))
     put(20, "<i4", np.full(nreads, L))

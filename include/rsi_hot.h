@@ -358,6 +358,34 @@ int rsi_hot_debug_pin_calls(rsi_ctx* ctx, int64_t n, const int32_t* pos, const i
                             const int32_t* info, const int32_t* lq, const uint32_t* coff, const uint32_t* pool, int64_t npool, int64_t tid_len,
                             int m, int l_qseq, double drd_sd, int ncalls, const int32_t* start, const int32_t* end, const int32_t* type,
                             int32_t* new_start, int32_t* new_end, int32_t* sc1, int32_t* sc2);
+/* ---- `geno`: the copy number of a list of regions, from the depth a run leaves in HBM ----
+ * After a successful run the context holds the GC-adjusted, capped, N-free depth the calls were made from, the removed regions
+ * and the chromosome's median.  rsi_hot_geno_calls reduces ncalls regions of that array, in a number of launches that does not
+ * depend on ncalls: start / end are 1-based inclusive reference coordinates as in the output rows (swapped when start > end,
+ * clipped to [1, n]); the body is their kept bases, N of them; the flank is the max(N, m) kept bases on each side, clipped to the
+ * array, both sides feeding one statistic.  body_q / flank_q: lower quartile, median, upper quartile as the reference's
+ * _lowerquartile / _median / _upperquartile give them on ints (partition_stat_tp, wufunctions.cpp:364-424): of n sorted values
+ * s[], s[max(n/4,1)-1], s[max(n/2,1)-1], s[max(3n/4,1)-1]; all 0 for an empty range.  RSI_ERR_BAD_ARG when the context's last
+ * run failed, there was none, or a debug hook has overwritten its depth since.  ncalls == 0 is RSI_OK and launches nothing. */
+/* rsi_geno_record layout: int32 n_body, n_flank, body_min, body_max; int64 body_sum, flank_sum; double body_q[3], flank_q[3], chrom_median */
+typedef struct rsi_geno_record {
+  int32_t n_body, n_flank, body_min, body_max;
+  int64_t body_sum, flank_sum;
+  double body_q[3], flank_q[3], chrom_median;
+} rsi_geno_record;
+typedef struct rsi_geno_stats {
+  int64_t launches, jobs, tiles, passes;   /* kernel launches of the last call; its jobs (two per line) and tiles; histogram passes (1 for bytes) */
+  int64_t bytes;                           /* device memory the context holds for this step (0 until the first call with lines) */
+  double ms;                               /* wall time of the last call's device part, tables up and records back included */
+} rsi_geno_stats;
+int rsi_hot_geno_calls(rsi_ctx* ctx, int m, int ncalls, const int32_t* start, const int32_t* end, rsi_geno_record* out);
+int rsi_hot_last_geno_stats(const rsi_ctx* ctx, rsi_geno_stats* out);
+/* Test hook: the same kernels through the same function over the HOST array depth[n], which becomes the context's compacted depth
+ * as bytes (storage 1; a value outside 0 .. 255 is RSI_ERR_BAD_ARG) or as int32 (storage 4), with explicit half-open compacted
+ * ranges per job: the body [lo, hi), the flank's pieces [flo0, fhi0) and [flo1, fhi1); any may be empty, a range outside [0, n]
+ * or with hi < lo is RSI_ERR_BAD_ARG.  tile: values per tile (0: the default, 16384).  chrom_median comes back 0. */
+int rsi_hot_debug_geno(rsi_ctx* ctx, const int32_t* depth, int64_t n, int storage, const int32_t* lo, const int32_t* hi, const int32_t* flo0,
+                       const int32_t* fhi0, const int32_t* flo1, const int32_t* fhi1, int njobs, int tile, rsi_geno_record* out);
 /* Fixed-layout summary of a chromosome's result for the one exchange of a multi-GPU run (the gather of per-chromosome
  * results that replaces the reference's sequential output loop, rsi.cpp:1594-1608):
  *   out[0..7]  = chromosome id (the caller's), chromosome median, SD, number of final calls, number stored here, 0, 0, 0

@@ -58,6 +58,12 @@ CAND_RECORD = np.dtype([(k, np.int32) for k in ("capacity", "top", "margin", "cu
                        [(k, np.float64) for k in ("p1", "cnvmed", "cnvsd", "cnviqr", "refmed", "refsd", "refiqr")])
 assert CAND_RECORD.itemsize == 18 * 4 + 17 * 8
 
+# rsi_geno_record (include/rsi_hot.h): one line of rsi_hot_geno_calls / rsi_hot_debug_geno
+GENO_RECORD = np.dtype([(k, np.int32) for k in ("n_body", "n_flank", "body_min", "body_max")] +
+                       [("body_sum", np.int64), ("flank_sum", np.int64), ("body_q", np.float64, 3), ("flank_q", np.float64, 3),
+                        ("chrom_median", np.float64)])
+assert GENO_RECORD.itemsize == 4 * 4 + 2 * 8 + 7 * 8
+
 # every symbol include/rsi_hot.h and include/rsi_synth.h declare
 EXPORTS = ["rsi_default_params", "rsi_hot_create", "rsi_hot_destroy", "rsi_hot_last_error", "rsi_hot_run",
            "rsi_hot_run_device", "rsi_hot_load_depth_text", "rsi_hot_run_text", "rsi_hot_load_depth_bam", "rsi_hot_run_bam", "rsi_bam_references", "rsi_result_annotate_bam", "rsi_result_summary", "rsi_summary_format_row", "rsi_summary_format_rows", "rsi_result_pairs", "rsi_result_ncalls", "rsi_result_calls", "rsi_result_stats", "rsi_result_noncode",
@@ -84,6 +90,7 @@ EXPORTS = ["rsi_default_params", "rsi_hot_create", "rsi_hot_destroy", "rsi_hot_l
            "rsi_hot_debug_pair_annotate",
            "rsi_hot_set_bam_pin", "rsi_hot_stat_calls", "rsi_hot_pin_sample", "rsi_hot_pin_calls", "rsi_hot_last_pin_stats",
            "rsi_hot_debug_pin_sample", "rsi_hot_debug_pin_calls",
+           "rsi_hot_geno_calls", "rsi_hot_last_geno_stats", "rsi_hot_debug_geno",
            "rsi_ref_debug_set_chunks", "rsi_ref_debug_fai_line", "rsi_ref_debug_ranges", "rsi_ref_debug_gzi", "rsi_ref_debug_cover"]
 
 
@@ -184,6 +191,11 @@ class RsiPinStats(C.Structure):
                 ("pos_start", C.c_int32), ("pos_end", C.c_int32), ("l_qseq", C.c_int32), ("r_len", C.c_int32),
                 ("rd", C.c_double), ("rd_sd", C.c_double), ("drd", C.c_double), ("drd_sd", C.c_double), ("breakpoints", C.c_int64),
                 ("t_table_ms", C.c_double), ("t_sample_ms", C.c_double), ("t_windows_ms", C.c_double)]
+
+
+class RsiGenoStats(C.Structure):
+    _fields_ = [("launches", C.c_int64), ("jobs", C.c_int64), ("tiles", C.c_int64), ("passes", C.c_int64), ("bytes", C.c_int64),
+                ("ms", C.c_double)]
 
 
 BAM_READ_MODES = {"host": 0, "device": 1}
@@ -344,6 +356,9 @@ def load_library():
                                            C.c_int64]
     L.rsi_hot_debug_pin_calls.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 8 + [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int] + \
                                          [C.c_void_p] * 7
+    L.rsi_hot_geno_calls.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rsi_hot_last_geno_stats.argtypes = [C.c_void_p, C.POINTER(RsiGenoStats)]
+    L.rsi_hot_debug_geno.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p]
     L.rsi_bgzf_write_eof.argtypes = [C.c_char_p]
     L.rsi_track_index_create.argtypes = []
     L.rsi_track_index_create.restype = C.c_void_p
@@ -1015,6 +1030,35 @@ class RsiHot:
         st = RsiPinStats()
         self._check(self.lib.rsi_hot_last_pin_stats(self.ctx, C.byref(st)))
         return self._pin_dict(st)
+
+    def geno_calls(self, m, start, end):
+        """The copy-number statistics of regions of the last run's chromosome (rsi_hot_geno_calls): start / end are 1-based inclusive
+        reference coordinates; a GENO_RECORD array, one record per region."""
+        a = [np.ascontiguousarray(v, dtype=np.int32).reshape(-1) for v in (start, end)]
+        assert a[0].size == a[1].size
+        k = a[0].size
+        out = np.zeros(max(k, 1), dtype=GENO_RECORD)
+        self._check(self.lib.rsi_hot_geno_calls(self.ctx, int(m), k, a[0].ctypes.data, a[1].ctypes.data, out.ctypes.data))
+        return out[:k]
+
+    def debug_geno(self, depth, storage, lo, hi, flo0, fhi0, flo1, fhi1, tile=0):
+        """The same kernels over a host array and explicit half-open compacted ranges (test hook, rsi_hot_debug_geno): the body
+        [lo, hi), the flank's pieces [flo0, fhi0) and [flo1, fhi1) per job; tile: values per tile (0: the default).  A GENO_RECORD
+        array (chrom_median 0)."""
+        d = np.ascontiguousarray(depth, dtype=np.int32)
+        a = [np.ascontiguousarray(v, dtype=np.int32).reshape(-1) for v in (lo, hi, flo0, fhi0, flo1, fhi1)]
+        k = a[0].size
+        assert all(v.size == k for v in a)
+        out = np.zeros(max(k, 1), dtype=GENO_RECORD)
+        self._check(self.lib.rsi_hot_debug_geno(self.ctx, d.ctypes.data, d.size, int(storage), *[v.ctypes.data for v in a], k, int(tile),
+                                                out.ctypes.data))
+        return out[:k]
+
+    def geno_stats(self):
+        """Launches, jobs, tiles, passes, bytes held and ms of the context's last geno_calls / debug_geno (rsi_hot_last_geno_stats)."""
+        st = RsiGenoStats()
+        self._check(self.lib.rsi_hot_last_geno_stats(self.ctx, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in RsiGenoStats._fields_}
 
     @staticmethod
     def _pin_arrays(cigars):

@@ -4,7 +4,8 @@
 // depth file (-d GENOME.depth without -c: "RNAME pos depth" lines, every chromosome in one pass, each run
 // as soon as its lines are parsed) or a BAM file (-b BAMFILE [-c RNAME], piled up on the device, calls
 // annotated with RP / Q0 from its read pairs); `rsicnv stat` and `rsicnv pin` annotate and sharpen a CNV list (-v CNVFILE) from
-// a BAM (run_cnvlist); plot is outside the accelerated path and says so.  A whole-genome file with several depth columns (a cohort, RNAME POS D1 ... DK) is
+// a BAM (run_cnvlist); `rsicnv geno` runs the chromosomes such a list names as rsi does and appends every region's copy
+// number, reduced on the device from the depth the run leaves there (geno_chromosome); plot is outside the accelerated path and says so.  A whole-genome file with several depth columns (a cohort, RNAME POS D1 ... DK) is
 // called sample by sample with -samples all|LIST: one OUT.k per selected column k.  A bedGraph depth file (RNAME START END
 // DEPTH: mosdepth, bedtools genomecov -bg / -bga) runs as the per-base file it stands for, whole or one chromosome (-c).
 // -track FILE saves the depth every chromosome was called from (raw, or GC-adjusted with -trackdepth gc) as one bedGraph file,
@@ -41,6 +42,7 @@
 #include "hostmath.h"
 #include "track_host.h"
 #include "pin_host.h"
+#include "geno_host.h"
 
 namespace {
 
@@ -69,7 +71,18 @@ struct Options {
   std::string refread;       // -refread device|host: the reference through the device reader (rsi_ref) or read_fasta (empty: host for text, device for BGZF)
   std::string refindex;      // -refindex PATH|none: the .gzi of a BGZF reference (empty: REFFILE.gzi when there, else the members are walked)
   bool ref_device = false;   // what that gives (main sets it)
+  double ploidy = 2.0;       // -ploidy P (geno): CN = P x the body's median over the chromosome's
+  const std::vector<rsipinh::CnvLine>* geno = nullptr;   // `rsicnv geno`: the lines of -v CNVFILE (main sets it); every chromosome's run then
+                                                         // ends in geno_chromosome instead of rows and plots
 };
+
+// `rsicnv geno`: a list names a chromosome as the reference's index does, with or without a leading "chr"
+bool same_chrom(const std::string& a, const std::string& b) { return a == b || "chr" + a == b || a == "chr" + b; }
+bool geno_names(const std::vector<rsipinh::CnvLine>& lines, const std::string& chr) {
+  for (const rsipinh::CnvLine& l : lines) if (same_chrom(l.cell[0], chr)) return true;
+  return false;
+}
+struct GenoRow { size_t line; std::string field, cn; };   // what a line gets: the appended field, and its CN alone for OUT.matrix
 
 // The reference through the device reader: one rsi_ref per device, shared by that device's workers (a handle loads
 // one sequence at a time), and what all of a run's loads read, for the log's one "#reference:" line.
@@ -167,6 +180,15 @@ int usage() {
             << "             of unknown type stay.  Both take -m, -gpu and -bamread, read each chromosome of the list once (no .bai) and\n"
             << "             count on the GPU; lines of a chromosome the BAM does not name, or pin cannot sample from 10 Mb on, are\n"
             << "             written unchanged and OUT.log says why\n"
+            << "\n3. copy number of a list of regions (the same lines), per sample\n\n"
+            << "   rsicnv geno <options> -f REFFILE (-d DEPTH [-c RNAME] | -b BAMFILE [-c RNAME]) -v CNVFILE -o OUT [-ploidy P]\n"
+            << "             runs the chromosomes the list names as rsi does (-m -cap -NOGC -x -q -Q -refread -bamread -dformat -dindex\n"
+            << "             -workers as there), writes no calls and no plots, and appends to every line\n"
+            << "             CN=;RATIO=;MED=;FLANK=;CHR=;N= -- N kept bases between START and END, MED their median depth (GC-adjusted,\n"
+            << "             capped), RATIO = MED over the chromosome's median CHR, CN = RATIO x P (default 2), FLANK the median of\n"
+            << "             max(N, m) kept bases on each side; computed on the GPU from the depth the run leaves there.  With -samples\n"
+            << "             OUT.k per column k and OUT.matrix (one CN per sample and line).  Lines of a chromosome the input lacks or\n"
+            << "             whose run fails are written unchanged and OUT.log says why\n"
             << "\nOptions:\n"
             << "   -m   INT  bin size, default=101\n"
             << "   -q   INT  minimum mapping quality, default=0\n"
@@ -256,7 +278,7 @@ void parse(int argc, char** argv, Options& o) {
   size_t i = 1;
   if (a[1][0] != '-') {
     o.function = a[1];
-    if (o.function != "rsi" && o.function != "plot" && o.function != "stat" && o.function != "pin") {
+    if (o.function != "rsi" && o.function != "plot" && o.function != "stat" && o.function != "pin" && o.function != "geno") {
       std::cerr << "no such function " << o.function << std::endl;
       exit(usage());
     }
@@ -308,10 +330,11 @@ void parse(int argc, char** argv, Options& o) {
     else if (s == "-bamread") { o.bamread = need(i); ++i; }
     else if (s == "-pairs") { o.pairs = need(i); ++i; }
     else if (s == "-refindex") { o.refindex = need(i); ++i; }
+    else if (s == "-ploidy") { o.ploidy = atof(need(i).c_str()); ++i; }
     else { std::cerr << "unknown option " << s << std::endl; exit(usage()); }
   }
   if (o.rdfile.empty() && o.bamfile.empty()) { std::cerr << "need input file " << std::endl; exit(usage()); }
-  if (o.reffile.empty() && o.function == "rsi") { std::cerr << "need reference file " << std::endl; exit(usage()); }
+  if (o.reffile.empty() && (o.function == "rsi" || o.function == "geno")) { std::cerr << "need reference file " << std::endl; exit(usage()); }
   if (o.outfile == o.bamfile || o.outfile == o.rdfile) { std::cerr << "output file is same as input file " << std::endl; exit(usage()); }
   if (!o.rdfile.empty() && o.chr.empty()) { std::cerr << "readdepth file and chromosome must be specified together" << std::endl; exit(usage()); }
   if ((o.P.m % 2) != 1) { o.P.m += 1; std::cerr << "m is changed to " << o.P.m << std::endl; }   // rsi.cpp:2061-2064
@@ -360,6 +383,8 @@ struct ChromOutput {
   bool track_failed = false;       // -track: its part could not be written (the reason is in the log): no track file
   bool bintrack_failed = false;    // -bintrack: likewise
   std::shared_ptr<rsi_track_index> track_ix, bintrack_ix;   // -trackindex: the index of this chromosome's part (offsets from the part's start)
+  std::vector<GenoRow> geno;       // `geno`: what this chromosome's lines get
+  bool geno_done = false;          // ... and that they got it
 };
 
 std::shared_ptr<rsi_track_index> new_track_index() { return std::shared_ptr<rsi_track_index>(rsi_track_index_create(), rsi_track_index_free); }
@@ -382,6 +407,7 @@ std::string inflate_line(const rsi_inflate_stats& s) {
 
 void report_chromosome(rsi_ctx* ctx, const Options& o, const std::string& chr, rsi_result* res, const rsi_text_stats* ts,
                        const rsi_bam_stats* bs, double t_fasta, double t_path, std::ostringstream& info, ChromOutput& co);
+void geno_chromosome(rsi_ctx* ctx, const Options& o, const std::string& chr, rsi_result* res, std::ostringstream& info, ChromOutput& co);
 
 // -x FILE: the BED file's intervals on `chr` (n bases) arm the context for the run that follows (the mask is spent by that run);
 // one log line.  false: the file could not be read (the message is in the log line).
@@ -467,6 +493,32 @@ void process_chromosome(rsi_ctx* ctx, const Options& o, const std::string& chr, 
   report_chromosome(ctx, o, chr, res, from_bam ? nullptr : &ts, from_bam ? &bs : nullptr, t1 - t0, t2 - t1, info, co);
 }
 
+// `geno` behind a chromosome's run, for every input: its lines' regions reduced on the device (rsi_hot_geno_calls), formatted here.
+void geno_chromosome(rsi_ctx* ctx, const Options& o, const std::string& chr, rsi_result* res, std::ostringstream& info, ChromOutput& co) {
+  std::vector<size_t> mine;
+  std::vector<int32_t> start, end;
+  for (size_t i = 0; i < o.geno->size(); ++i)
+    if (same_chrom((*o.geno)[i].cell[0], chr)) { mine.push_back(i); start.push_back((*o.geno)[i].start); end.push_back((*o.geno)[i].end); }
+  const rsi_chrom_stats* S = rsi_result_stats(res);
+  info << "region  : " << chr << ":1-" << S->n_compact << "\nmedian  : " << S->RDmedian << "\nrs::m   : " << o.P.m << "\nrs::cap : " << o.P.cap << "\n";
+  std::vector<rsi_geno_record> rec(std::max<size_t>(mine.size(), 1));
+  if (rsi_hot_geno_calls(ctx, o.P.m, (int)mine.size(), start.data(), end.data(), rec.data()) != RSI_OK) {
+    info << "#geno: " << chr << ": " << rsi_hot_last_error(ctx) << "\n";
+    return;
+  }
+  for (size_t k = 0; k < mine.size(); ++k) {
+    const rsi_geno_record& r = rec[k];
+    co.geno.push_back(GenoRow{mine[k], rsigeno::format_field(r.n_body, r.n_flank, r.body_q[1], r.flank_q[1], r.chrom_median, o.ploidy),
+                              rsigeno::cn_text(r.n_body, r.body_q[1], r.chrom_median, o.ploidy)});
+  }
+  co.geno_done = true;
+  rsi_geno_stats gs;
+  memset(&gs, 0, sizeof(gs));
+  (void)rsi_hot_last_geno_stats(ctx, &gs);
+  info << "#geno: " << chr << ": " << mine.size() << " lines, " << gs.jobs << " jobs, " << gs.tiles << " tiles, " << gs.launches << " launches, " << gs.ms
+       << " ms (device)\n";
+}
+
 // Second half, shared by every input: a chromosome's result (run on ctx, which still holds it) -> its log block, RP / Q0
 // (BAM input), its rows, its plots.  Frees res.
 void report_chromosome(rsi_ctx* ctx, const Options& o, const std::string& chr, rsi_result* res, const rsi_text_stats* ts,
@@ -480,6 +532,12 @@ void report_chromosome(rsi_ctx* ctx, const Options& o, const std::string& chr, r
     FILE* f = fopen(dump.c_str(), "w");
     if (f) { for (int64_t i = 0; i < bs->n; ++i) fprintf(f, "%lld\t%d\n", (long long)i + 1, rd[(size_t)i]); fclose(f); }
     info << "RD of " << chr << " is saved to " << dump << "\n";
+  }
+  if (o.geno) {   // `geno`: the list's lines on this chromosome, from the depth the run has left in HBM; no rows, no plots
+    geno_chromosome(ctx, o, chr, res, info, co);
+    co.log = info.str();
+    rsi_result_free(res);
+    return;
   }
   if (!o.trackfile.empty()) {   // -track: this chromosome's lines into its part file, from the depth the context still holds
     rsi_track_stats tk;
@@ -790,6 +848,10 @@ bool run_genome(const Options& o, const std::vector<int32_t>& cols, std::vector<
     if (rc < 0) { err = rsi_genome_text_last_error(g); ok = false; break; }
     const std::string chr = c.name;
     if (only && c.slot < 0) continue;   // another chromosome of the file
+    if (o.geno && !geno_names(*o.geno, chr)) {   // `geno` runs the chromosomes its list names
+      if (c.slot >= 0) rsi_genome_text_release(g, c.slot);
+      continue;
+    }
     size_t idx;
     { std::lock_guard<std::mutex> lk(mu); idx = done_outs.size(); done_outs.emplace_back((size_t)nsamp); }
     chroms.push_back(chr);
@@ -1049,6 +1111,31 @@ int run_cnvlist(const Options& o) {
   return out.good() ? 0 : 1;
 }
 
+// `geno`: what one output (OUT, or a sample's OUT.k) collects from its chromosomes, and the file it becomes: the list's lines in
+// the list's order, each with its field; a line nobody served is written as it stands and the log says why.
+struct GenoCollect {
+  std::vector<std::string> field, cn;
+  std::vector<std::string> seen;   // the chromosomes this output's run met
+  explicit GenoCollect(size_t n) : field(n), cn(n, "NA") {}
+  void take(const std::string& chr, const ChromOutput& co) {
+    seen.push_back(chr);
+    if (co.geno_done) for (const GenoRow& r : co.geno) { field[r.line] = r.field; cn[r.line] = r.cn; }
+  }
+  bool write(const std::vector<rsipinh::CnvLine>& lines, const std::string& path, std::ostream& log) const {
+    std::ofstream out(path.c_str());
+    for (size_t i = 0; i < lines.size(); ++i) {
+      if (!field[i].empty()) { out << lines[i].text << "\t" << field[i] << "\n"; continue; }
+      out << lines[i].text << "\n";
+      bool met = false;
+      for (const std::string& c : seen) met = met || same_chrom(lines[i].cell[0], c);
+      log << "#geno: " << lines[i].cell[0] << (met ? ": its run failed (see above)" : " is not in the input") << ": line written unchanged\n";
+    }
+    out.close();
+    std::cerr << "output written to " << path << std::endl; log << "output written to " << path << std::endl;
+    return out.good();
+  }
+};
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -1059,6 +1146,17 @@ int main(int argc, char** argv) {
   Options o;
   parse(argc, argv, o);
   if (o.function == "stat" || o.function == "pin") return run_cnvlist(o);
+  std::vector<rsipinh::CnvLine> geno_lines;
+  if (o.function == "geno") {   // refused where it cannot work, before any output
+    if (o.cnvfile.empty()) { std::cerr << "rsicnv geno: need a list of regions (-v CNVFILE)" << std::endl; return 1; }
+    if (o.gpus > 1) { std::cerr << "rsicnv geno: -gpus: a CNV list runs on one device (-gpu INT picks it)" << std::endl; return 1; }
+    if (!o.trackfile.empty() || !o.bintrackfile.empty()) { std::cerr << "rsicnv geno: -track / -bintrack: geno writes no tracks (run rsi for them)" << std::endl; return 1; }
+    if (!(o.ploidy > 0)) { std::cerr << "rsicnv geno: -ploidy: expected a positive number" << std::endl; return 1; }
+    if (!rsipinh::read_cnvlist(o.cnvfile, {}, geno_lines, std::cerr)) return 0;   // as stat / pin: the reference says so and exits with 0
+    o.geno = &geno_lines;
+    o.plot = false;
+    o.function = "rsi";
+  }
   if (o.function != "rsi") {
     std::cerr << "rsicnv " << o.function << ": not part of the accelerated read-depth path in this build" << std::endl;
     return 0;
@@ -1227,6 +1325,7 @@ int main(int argc, char** argv) {
       const int64_t len = k < (int)lens.size() ? lens[(size_t)k] : 0;
       ++k;
       if (nm.find("MT") != std::string::npos || nm.find(".") != std::string::npos) continue;
+      if (o.geno && !geno_names(*o.geno, nm)) continue;   // `geno` runs the chromosomes its list names
       todo.push_back(nm); todo_len.push_back(len);
     }
   } else {
@@ -1237,8 +1336,10 @@ int main(int argc, char** argv) {
   // write_cnv_to_file, rsi.cpp:1592-1616: the first processed chromosome opens the file and writes the header, the others
   // append.  Rows always leave in the order of `todo` (the BAM header's), whatever ran where.
   bool wrote_header = false;
+  GenoCollect geno_out(geno_lines.size());
   auto emit = [&](const std::string& chr, const ChromOutput& co) {
     std::cerr << co.log; log << co.log;
+    if (o.geno) { geno_out.take(chr, co); return; }
     if (!co.populated) return;
     std::ofstream out(o.outfile.c_str(), wrote_header ? std::ios::app : std::ios::trunc);
     if (!wrote_header) {
@@ -1272,6 +1373,7 @@ int main(int argc, char** argv) {
       return 1;
     }
     bool tracks_ok = true;
+    std::vector<std::vector<std::string>> geno_cn;   // `geno`: per sample, the lines' CN
     // each sample as its own genome run would write it: header, then its chromosomes until the first fatal one
     for (size_t j = 0; j < cols.size(); ++j) {
       const std::string path = out_k(j);
@@ -1281,11 +1383,13 @@ int main(int argc, char** argv) {
       slog << h << "#sample " << cols[j] << (sample_names[j].empty() ? "" : ": " + sample_names[j]) << "\n";
       bool header_done = false;
       TrackParts parts;
+      GenoCollect sample_out(geno_lines.size());
       for (size_t i = 0; i < chroms.size(); ++i) {
         const ChromOutput& co = outs[i][j];
         std::cerr << co.log; slog << co.log;
         parts.add(i, co);
-        if (co.populated) {
+        if (o.geno) sample_out.take(chroms[i], co);
+        if (co.populated && !o.geno) {
           std::ofstream out(path.c_str(), header_done ? std::ios::app : std::ios::trunc);
           if (!header_done) {
             out << "#input " << o.rdfile << " sample " << cols[j] << (sample_names[j].empty() ? "" : " " + sample_names[j]) << std::endl;
@@ -1297,9 +1401,28 @@ int main(int argc, char** argv) {
           out.close();
           std::cerr << "output written to " << path << std::endl; slog << "output written to " << path << std::endl;
         }
-        if (co.fatal) break;
+        if (co.fatal && !o.geno) break;   // (geno: a chromosome that fails leaves its lines unchanged, the others go on)
       }
       if (!finish_tracks(o, "." + std::to_string(cols[j]), parts, chroms.size(), slog)) tracks_ok = false;
+      if (o.geno) {
+        if (!sample_out.write(geno_lines, path, slog)) tracks_ok = false;
+        geno_cn.push_back(sample_out.cn);
+      }
+    }
+    if (o.geno) {   // OUT.matrix: one CN (or NA) per line and sample
+      std::ofstream mx((o.outfile + ".matrix").c_str());
+      mx << "#RNAME\tSTART\tEND\tTYPE";
+      for (int32_t k : cols) mx << "\t" << k;
+      mx << "\n";
+      for (size_t i = 0; i < geno_lines.size(); ++i) {
+        const rsipinh::CnvLine& l = geno_lines[i];
+        mx << l.cell[0] << "\t" << l.cell[1] << "\t" << l.cell[2] << "\t" << l.cell[3];
+        for (size_t j = 0; j < cols.size(); ++j) mx << "\t" << geno_cn[j][i];
+        mx << "\n";
+      }
+      mx.close();
+      if (!mx.good()) tracks_ok = false;
+      std::cerr << "matrix written to " << o.outfile << ".matrix" << std::endl; log << "matrix written to " << o.outfile << ".matrix" << std::endl;
     }
     if (rr) summary += rr->line();
     std::cerr << summary; log << summary;
@@ -1323,10 +1446,11 @@ int main(int argc, char** argv) {
     for (size_t i = 0; i < chroms.size(); ++i) {
       emit(chroms[i], outs[i][0]);
       parts.add(i, outs[i][0]);
-      if (outs[i][0].fatal) break;
+      if (outs[i][0].fatal && !o.geno) break;
     }
     if (rr) summary += rr->line();
     std::cerr << summary; log << summary;
+    if (o.geno && !geno_out.write(geno_lines, o.outfile, log)) return 1;
     return finish_tracks(o, "", parts, chroms.size(), log) ? 0 : 1;
   }
 
@@ -1350,10 +1474,11 @@ int main(int argc, char** argv) {
       }
       emit(chr, co);
       parts.add(i, co);
-      if (co.fatal) break;
+      if (co.fatal && !o.geno) break;
     }
     rsi_hot_destroy(ctx);
     if (rr) { std::cerr << rr->line(); log << rr->line(); }
+    if (o.geno && !geno_out.write(geno_lines, o.outfile, log)) return 1;
     return finish_tracks(o, "", parts, todo.size(), log) ? 0 : 1;
   }
 
@@ -1432,5 +1557,6 @@ int main(int argc, char** argv) {
   }
   for (rsi_pool* pl : pools) rsi_pool_destroy(pl);
   if (rr) { std::cerr << rr->line(); log << rr->line(); }
+  if (o.geno && !geno_out.write(geno_lines, o.outfile, log)) return 1;
   return finish_tracks(o, "", parts, todo.size(), log) ? 0 : 1;   // (-track, -bintrack: one device only, -gpus 1)
 }

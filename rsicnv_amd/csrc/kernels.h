@@ -615,6 +615,26 @@ constexpr int kPinMaxRlen = 2559;
 void launch_pin_windows(PairTable t, PinTable p, long long n, int maxspan, long long tid_len, const void* bps, int nbp, int r_len, int l_qseq,
                         double drd_sd, int32_t* out, hipStream_t stream);
 
+// ---- `geno`: quantiles, count, sum, minimum and maximum of ranges of the compacted depth (kernels_geno.hip) ----
+// A job is one statistic over the values of its tiles; a tile (rsigeno::Tile's layout, geno_host.h) is `len` consecutive values
+// from `off` on, inside the array -- the caller checks that.  hist: geno_hist_bytes() bytes, all zero before the first launch.
+// Bytes: launch_geno_hist8 (a workgroup per tile), then launch_geno_scan8 (a workgroup per job) writes out[job].
+// int32: launch_geno_init32, _minmax32, _plan32 -- which finishes empty and all-equal jobs and leaves in *maxbits the widest
+// max - min of the others, in bits -- then ceil(*maxbits / kGenoBits) times launch_geno_hist32 + launch_geno_scan32; the scan of
+// a job's last pass writes out[job] and every scan leaves the job's histogram zero.
+struct GenoTile { int32_t job, off, len, pad; };
+struct GenoOut { int32_t n, vmin, vmax, q[3]; long long sum; };
+struct GenoState { int32_t vmin, vmax; unsigned int n; int32_t shift; unsigned long long sum; uint32_t prefix[3], k[3]; };
+constexpr int kGenoThreads = 256, kGenoBits = 11, kGenoBins = 1 << kGenoBits;
+size_t geno_hist_bytes(int storage, int64_t njobs);
+void launch_geno_hist8(const uint8_t* d, const GenoTile* tiles, int ntiles, unsigned int* hist, hipStream_t stream);
+void launch_geno_scan8(const unsigned int* hist, int njobs, GenoOut* out, hipStream_t stream);
+void launch_geno_init32(GenoState* st, int njobs, unsigned int* maxbits, hipStream_t stream);
+void launch_geno_minmax32(const int32_t* d, const GenoTile* tiles, int ntiles, GenoState* st, hipStream_t stream);
+void launch_geno_plan32(GenoState* st, int njobs, GenoOut* out, unsigned int* maxbits, hipStream_t stream);
+void launch_geno_hist32(const int32_t* d, const GenoTile* tiles, int ntiles, const GenoState* st, unsigned int* hist, hipStream_t stream);
+void launch_geno_scan32(GenoState* st, int njobs, unsigned int* hist, GenoOut* out, hipStream_t stream);
+
 // ---- depth track: an int32 array as bedGraph text, run-length encoded and formatted on the device (kernels_track.hip) ----
 // One line "NAME \t pos0+start \t pos0+end \t value \n" per maximal run of equal values of v[0, n), worked through in slices
 // [b, e) of bases.  A run start is i == 0 or v[i] != v[i - 1] -- read from the whole array, so slicing moves no start.  A line is

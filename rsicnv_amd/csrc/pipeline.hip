@@ -6,6 +6,7 @@
 // device-built histograms and runs the candidate list logic (host_calls.cpp).
 #include <new>
 #include "pipeline_internal.h"
+#include "geno_host.h"        // `geno`: a list line -> compacted ranges -> the kernels' tile table (plain C++, tested on the CPU)
 #include "pipeline_steps.h"   // the host decisions between the kernels, as pure functions (tested on the CPU: tests/sanitize)
 
 using namespace rsik;
@@ -2166,6 +2167,106 @@ int rsi_hot_debug_range_sums(rsi_ctx* ctx, const int32_t* depth, int64_t n, int 
   memcpy(sums, got.data(), (size_t)nranges * 8);
   if (info) { info[0] = tester.launches; info[1] = ctx->mb_used > mb_before ? 1 : 0; }
   return RSI_OK;
+}
+
+// ---- `geno` (include/rsi_hot.h) ----
+// The statistics of `lines` over the compacted depth d_depth[ncompact] (storage 1: bytes, 4: int32) through the kernels of
+// kernels_geno.hip; what rsi_hot_geno_calls and rsi_hot_debug_geno share.  The caller has entered the context and reset the mailbox.
+static int geno_run(rsi_ctx* ctx, const void* d_depth, int storage, int64_t ncompact, const std::vector<rsigeno::Ranges>& lines, int tile,
+                    double chrom_median, rsi_geno_record* out) {
+  rsi_ctx::Geno& G = ctx->geno;
+  const int64_t bytes_held = G.stats.bytes;
+  G.stats = rsi_geno_stats{};
+  G.stats.bytes = bytes_held;
+  if (lines.empty()) return RSI_OK;
+  if (lines.size() > (size_t)(1 << 29)) return fail(ctx, RSI_ERR_UNSUPPORTED, "geno: more than 2^29 lines in one batch");
+  const double t0 = now_ms();
+  std::vector<rsigeno::Tile> tiles;
+  if (!rsigeno::build_tiles(lines, ncompact, tile > 0 ? tile : rsigeno::kDefaultTile, tiles)) return fail(ctx, RSI_ERR_BAD_ARG, "geno: a range outside the array, or hi < lo");
+  if (tiles.size() >= (size_t)0x7fffffff) return fail(ctx, RSI_ERR_UNSUPPORTED, "geno: more than 2^31 tiles in one batch");
+  static_assert(sizeof(rsigeno::Tile) == sizeof(GenoTile), "one tile layout for the host table and the kernels");
+  const int njobs = (int)(2 * lines.size()), ntiles = (int)tiles.size();
+  const size_t hist_bytes = geno_hist_bytes(storage, njobs);
+  HIPCHK(G.tiles.ensure(std::max<size_t>(tiles.size(), 1) * sizeof(GenoTile)));
+  HIPCHK(G.hist.ensure(hist_bytes));
+  HIPCHK(G.out.ensure((size_t)njobs * sizeof(GenoOut)));
+  if (storage != 1) HIPCHK(G.state.ensure((size_t)njobs * sizeof(GenoState) + 256));
+  G.stats.bytes = (int64_t)(G.tiles.cap + G.hist.cap + G.out.cap + G.state.cap);
+  hipStream_t st = ctx->stream;
+  if (ntiles) HIPCHK(copy_h2d(ctx, G.tiles.p, tiles.data(), tiles.size() * sizeof(GenoTile)));
+  HIPCHK(hipMemsetAsync(G.hist.p, 0, hist_bytes, st));
+  const GenoTile* d_tiles = G.tiles.as<GenoTile>();
+  unsigned int* d_hist = G.hist.as<unsigned int>();
+  GenoOut* d_out = G.out.as<GenoOut>();
+  int launches = 0, passes = 0;
+  if (storage == 1) {
+    { Timer t(ctx, "geno_hist"); launch_geno_hist8(static_cast<const uint8_t*>(d_depth), d_tiles, ntiles, d_hist, st); }
+    { Timer t(ctx, "geno_scan"); launch_geno_scan8(d_hist, njobs, d_out, st); }
+    launches = (ntiles ? 1 : 0) + 1; passes = 1;
+  } else {
+    GenoState* d_st = G.state.as<GenoState>();
+    unsigned int* d_bits = reinterpret_cast<unsigned int*>(G.state.as<uint8_t>() + (size_t)njobs * sizeof(GenoState));
+    const int32_t* d32 = static_cast<const int32_t*>(d_depth);
+    { Timer t(ctx, "geno_minmax"); launch_geno_init32(d_st, njobs, d_bits, st); launch_geno_minmax32(d32, d_tiles, ntiles, d_st, st); launch_geno_plan32(d_st, njobs, d_out, d_bits, st); }
+    launches = 2 + (ntiles ? 1 : 0);
+    unsigned int maxbits = 0;   // the widest max - min among the jobs still open decides the number of passes: one small word back
+    HIPCHK(copy_d2h(ctx, &maxbits, d_bits, 4));
+    HIPCHK(CTX_SYNC());
+    passes = (int)((maxbits + kGenoBits - 1) / kGenoBits);
+    for (int p = 0; p < passes; ++p) {
+      { Timer t(ctx, "geno_hist"); launch_geno_hist32(d32, d_tiles, ntiles, d_st, d_hist, st); }
+      { Timer t(ctx, "geno_scan"); launch_geno_scan32(d_st, njobs, d_hist, d_out, st); }
+      launches += 2;
+    }
+  }
+  std::vector<GenoOut> got((size_t)njobs);
+  HIPCHK(copy_d2h(ctx, got.data(), d_out, (size_t)njobs * sizeof(GenoOut)));
+  HIPCHK(CTX_SYNC());
+  for (size_t i = 0; i < lines.size(); ++i) {
+    const GenoOut& b = got[2 * i], & f = got[2 * i + 1];
+    rsi_geno_record& r = out[i];
+    memset(&r, 0, sizeof(r));
+    r.n_body = b.n; r.n_flank = f.n; r.body_min = b.vmin; r.body_max = b.vmax; r.body_sum = b.sum; r.flank_sum = f.sum;
+    for (int q = 0; q < 3; ++q) { r.body_q[q] = b.q[q]; r.flank_q[q] = f.q[q]; }
+    r.chrom_median = chrom_median;
+  }
+  G.stats.launches = launches; G.stats.jobs = njobs; G.stats.tiles = ntiles; G.stats.passes = passes;
+  G.stats.ms = now_ms() - t0;
+  return RSI_OK;
+}
+
+int rsi_hot_geno_calls(rsi_ctx* ctx, int m, int ncalls, const int32_t* start, const int32_t* end, rsi_geno_record* out) {
+  if (!ctx || ncalls < 0 || m < 1 || (ncalls > 0 && (!start || !end || !out))) return fail(ctx, RSI_ERR_BAD_ARG, "bad argument");
+  if (!ctx->run_m || ctx->ncompact <= 0 || !(ctx->rdc_is_bytes ? ctx->rdc8.p : ctx->rdc.p))
+    return fail(ctx, RSI_ERR_BAD_ARG, "geno: the context holds no successful run's compacted depth (none yet, the last one failed, or a debug hook has overwritten it)");
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!ctx_enter(ctx)) return RSI_ERR_HIP;
+  mailbox_reset(ctx);
+  const int npairs = (int)(ctx->noncode_pairs.size() / 2);
+  std::vector<rsigeno::Ranges> lines((size_t)ncalls);
+  for (int i = 0; i < ncalls; ++i)
+    lines[(size_t)i] = rsigeno::line_ranges(rsigeno::map_line(start[i], end[i], ctx->n, ctx->noncode_pairs.data(), npairs), m, ctx->ncompact);
+  return geno_run(ctx, ctx->rdc_is_bytes ? ctx->rdc8.p : ctx->rdc.p, ctx->rdc_is_bytes ? 1 : 4, ctx->ncompact, lines, 0, ctx->run_rdmedian, out);
+}
+
+int rsi_hot_last_geno_stats(const rsi_ctx* ctx, rsi_geno_stats* out) {
+  if (!ctx || !out) return RSI_ERR_BAD_ARG;
+  *out = ctx->geno.stats;
+  return RSI_OK;
+}
+
+int rsi_hot_debug_geno(rsi_ctx* ctx, const int32_t* depth, int64_t n, int storage, const int32_t* lo, const int32_t* hi, const int32_t* flo0,
+                       const int32_t* fhi0, const int32_t* flo1, const int32_t* fhi1, int njobs, int tile, rsi_geno_record* out) {
+  if (njobs < 0 || tile < 0 || (njobs > 0 && (!lo || !hi || !flo0 || !fhi0 || !flo1 || !fhi1 || !out))) return fail(ctx, RSI_ERR_BAD_ARG, "bad argument");
+  DepthRef ref;
+  int rc;
+  if ((rc = debug_depth_upload(ctx, depth, n, storage, &ref)) != RSI_OK) return rc;
+  std::vector<rsigeno::Ranges> lines((size_t)njobs);
+  for (int i = 0; i < njobs; ++i) {
+    rsigeno::Ranges& r = lines[(size_t)i];
+    r.body.a = lo[i]; r.body.b = hi[i]; r.left.a = flo0[i]; r.left.b = fhi0[i]; r.right.a = flo1[i]; r.right.b = fhi1[i];
+  }
+  return geno_run(ctx, ref.p, storage, n, lines, tile, 0.0, out);
 }
 
 int rsi_hot_debug_grid_median(rsi_ctx* ctx, const float* x, const int32_t* mask, int64_t nb, int mode, double center, double* out,

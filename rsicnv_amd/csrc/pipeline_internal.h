@@ -192,6 +192,12 @@ struct rsi_ctx {
     double t_table_ms = 0;
     rsi_pin_stats stats{};
   } pin;
+  // `geno` (rsi_hot_geno_calls; pipeline.hip): nothing of it exists until the first call with lines.  Every
+  // call clears the part of hist it uses, so nothing of an earlier, longer list is ever counted.
+  struct Geno {
+    DevBuf tiles, hist, state, out;
+    rsi_geno_stats stats{};
+  } geno;
   int64_t n_in = 0;                        // length of the depth currently in in_depth
   DevBuf gcbits, nbits, rd_gc, rdc, binmed, binsum, tnb, tmed, first_del;
   DevBuf depth8, rescaled8;   // byte copies: the raw depth (K2 writes it, K3' streams it), the rescaled depth (K3' -> K4')

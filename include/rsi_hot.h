@@ -606,6 +606,65 @@ int rsi_track_index_counts(const rsi_track_index* ix, int64_t* nref, int64_t* nc
 /* Test hook: the .tbi stream before compression into out[cap]; returns its length (also when it does not fit: nothing written). */
 int64_t rsi_track_index_debug_tbi(const rsi_track_index* ix, uint8_t* out, int64_t cap);
 
+/* ---- `depth`: what a chromosome's per-base depth says about itself, without a run ----
+ * Every function below takes d_depth, an int32[n] in HBM that is not modified: the context's own input buffer
+ * (rsi_hot_loaded_depth) or any other, a genome reader's slot for one, as rsi_hot_write_track_device does.  n == 0 and zero
+ * regions are RSI_OK and launch nothing.  Every wait has the library's 60 s deadline.
+ * rsi_hot_loaded_depth: the array the context's last successful rsi_hot_load_depth_text / _load_depth_bam left in its input buffer
+ * (valid until the next load, run from host arrays or debug hook of the context); RSI_ERR_BAD_ARG when the buffer holds nothing. */
+int rsi_hot_loaded_depth(rsi_ctx* ctx, const void** d_depth, int64_t* n);
+/* rsi_depth_summary layout: int64 n, sum, over, negative; int32 min, max */
+typedef struct rsi_depth_summary {
+  int64_t n, sum;      /* bases, and the exact sum of their depth */
+  int64_t over;        /* bases deeper than 65535 (counted in dist[65535]) */
+  int64_t negative;    /* negative depths met: the call then fails and nothing else of the record counts */
+  int32_t min, max;    /* the real ones, whatever the distribution's cap (0, 0 for n == 0) */
+} rsi_depth_summary;
+/* One pass over the array: the record, and dist[d] = bases of depth d for d < min(dist_cap, 65536), depths above 65535 counted at
+ * 65535 (dist may be NULL).  Integer atomics only: the same array gives the same numbers on every call.  A negative depth indexes
+ * nothing: it is counted in out->negative and the call returns RSI_ERR_BAD_ARG ("negative depth"). */
+int rsi_hot_depth_summary(rsi_ctx* ctx, const void* d_depth, int64_t n, rsi_depth_summary* out, int64_t* dist, int dist_cap);
+/* rsi_depth_region layout: int64 n, sum; int32 min, max */
+typedef struct rsi_depth_region { int64_t n, sum; int32_t min, max; } rsi_depth_region;
+/* nreg regions [start, end), 0-based half-open, in any order, overlapping or equal ones too, each clipped to [0, n): the bases
+ * left, their exact sum, minimum and maximum (all 0 for a region with nothing left, end < start included).  Reduced through geno's
+ * tile table and min / max kernels, in a number of launches that does not depend on nreg. */
+int rsi_hot_depth_regions(rsi_ctx* ctx, const void* d_depth, int64_t n, int nreg, const int64_t* start, const int64_t* end, rsi_depth_region* out);
+/* The mean depth of every window [k W, min((k + 1) W, n)) (the last one short; W >= 1) as lines "chrom<TAB>start<TAB>end<TAB>mean",
+ * appended to (append != 0) or replacing `path`: summed slice by slice into a workspace that does not grow with n, formatted on
+ * the device and sent through the track writer's slices, as text or as BGZF members (rsi_hot_set_track_format; a BGZF file is
+ * complete once rsi_bgzf_write_eof has ended it).  The mean has two decimals and is rounded half up in integers: with a = S / L
+ * and r = S mod L the hundredths are (200 r + L) / (2 L), a hundred of them carrying into a.  The depth must not be negative
+ * (rsi_hot_depth_summary says whether it is): a sum that is not positive is written as 0.00.  An index set with
+ * rsi_hot_set_track_index is left alone: these lines are not indexed.  stats->n counts the lines. */
+int rsi_hot_write_window_track(rsi_ctx* ctx, const void* d_depth, int64_t n, const char* chrom, int64_t W, const char* path, int append,
+                               rsi_track_stats* stats);
+/* The same for nreg explicit regions, in the order given: a region is clipped to [0, n) and written with its clipped
+ * coordinates; one with nothing left is written with the coordinates given and 0.00.  The sums are rsi_hot_depth_regions'. */
+int rsi_hot_write_region_track(rsi_ctx* ctx, const void* d_depth, int64_t n, const char* chrom, int nreg, const int64_t* start,
+                               const int64_t* end, const char* path, int append, rsi_track_stats* stats);
+typedef struct rsi_depth_stats {
+  int64_t launches;     /* kernel launches of the last rsi_hot_depth_summary / _depth_regions (or their hooks) */
+  int64_t workgroups;   /* of its summary pass, or tiles of its regions */
+  int64_t bytes;        /* device memory the context holds for these two */
+  double ms;            /* wall time of the call's device part, results back included */
+  double kernel_ms;     /* HIP-event time of the summary pass alone (0 for regions) */
+} rsi_depth_stats;
+int rsi_hot_last_depth_stats(const rsi_ctx* ctx, rsi_depth_stats* out);
+/* Test hooks: host values[n] uploaded into the context's input depth buffer (what rsi_hot_loaded_depth then returns), then the
+ * same functions.  span / tile: values per workgroup of the summary pass, values per tile of the regions (0: the defaults, 131072
+ * and 16384). */
+int rsi_hot_debug_depth_summary(rsi_ctx* ctx, const int32_t* values, int64_t n, int64_t span, rsi_depth_summary* out, int64_t* dist, int dist_cap);
+int rsi_hot_debug_depth_regions(rsi_ctx* ctx, const int32_t* values, int64_t n, int tile, int nreg, const int64_t* start, const int64_t* end,
+                                rsi_depth_region* out);
+/* ... and of the two track writers: W > 0 writes the windows, W == 0 the nreg regions.  span: bases per workgroup of the window
+ * sums (0: the default, 4096, which is also the most); slice_lines > 0 forces that slice length in lines; tile as above; pos0 is
+ * added to every coordinate written (the means are not touched).  The text (or, with the format BGZF, its members) into out[cap];
+ * returns its length as rsi_hot_debug_track does.  stats->slices counts the slices; stats->lines the lines. */
+int64_t rsi_hot_debug_region_track(rsi_ctx* ctx, const int32_t* values, int64_t n, const char* chrom, int64_t W, int nreg, const int64_t* start,
+                                   const int64_t* end, int span, int tile, int64_t slice_lines, int64_t pos0, char* out, int64_t cap,
+                                   rsi_track_stats* stats);
+
 /* Results.  which: 0 = calls after sd_filters (what write_cnv_to_file prints),
  *                  1 = detectcnv output before sd_filters,
  *                  2 = bin-space segments after the scan (rsicnvnbn / rsicnvmed output),

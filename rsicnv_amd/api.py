@@ -64,6 +64,12 @@ GENO_RECORD = np.dtype([(k, np.int32) for k in ("n_body", "n_flank", "body_min",
                         ("chrom_median", np.float64)])
 assert GENO_RECORD.itemsize == 4 * 4 + 2 * 8 + 7 * 8
 
+# rsi_depth_summary, rsi_depth_region (include/rsi_hot.h): rsi_hot_depth_summary's record, one region of rsi_hot_depth_regions
+DEPTH_SUMMARY = np.dtype([(k, np.int64) for k in ("n", "sum", "over", "negative")] + [("min", np.int32), ("max", np.int32)])
+DEPTH_REGION = np.dtype([("n", np.int64), ("sum", np.int64), ("min", np.int32), ("max", np.int32)])
+assert DEPTH_SUMMARY.itemsize == 40 and DEPTH_REGION.itemsize == 24
+DEPTH_BINS = 65536
+
 # every symbol include/rsi_hot.h and include/rsi_synth.h declare
 EXPORTS = ["rsi_default_params", "rsi_hot_create", "rsi_hot_destroy", "rsi_hot_last_error", "rsi_hot_run",
            "rsi_hot_run_device", "rsi_hot_load_depth_text", "rsi_hot_run_text", "rsi_hot_load_depth_bam", "rsi_hot_run_bam", "rsi_bam_references", "rsi_result_annotate_bam", "rsi_result_summary", "rsi_summary_format_row", "rsi_summary_format_rows", "rsi_result_pairs", "rsi_result_ncalls", "rsi_result_calls", "rsi_result_stats", "rsi_result_noncode",
@@ -91,6 +97,8 @@ EXPORTS = ["rsi_default_params", "rsi_hot_create", "rsi_hot_destroy", "rsi_hot_l
            "rsi_hot_set_bam_pin", "rsi_hot_stat_calls", "rsi_hot_pin_sample", "rsi_hot_pin_calls", "rsi_hot_last_pin_stats",
            "rsi_hot_debug_pin_sample", "rsi_hot_debug_pin_calls",
            "rsi_hot_geno_calls", "rsi_hot_last_geno_stats", "rsi_hot_debug_geno",
+           "rsi_hot_loaded_depth", "rsi_hot_depth_summary", "rsi_hot_depth_regions", "rsi_hot_write_window_track", "rsi_hot_write_region_track",
+           "rsi_hot_last_depth_stats", "rsi_hot_debug_depth_summary", "rsi_hot_debug_depth_regions", "rsi_hot_debug_region_track",
            "rsi_ref_debug_set_chunks", "rsi_ref_debug_fai_line", "rsi_ref_debug_ranges", "rsi_ref_debug_gzi", "rsi_ref_debug_cover"]
 
 
@@ -196,6 +204,10 @@ class RsiPinStats(C.Structure):
 class RsiGenoStats(C.Structure):
     _fields_ = [("launches", C.c_int64), ("jobs", C.c_int64), ("tiles", C.c_int64), ("passes", C.c_int64), ("bytes", C.c_int64),
                 ("ms", C.c_double)]
+
+
+class RsiDepthStats(C.Structure):
+    _fields_ = [("launches", C.c_int64), ("workgroups", C.c_int64), ("bytes", C.c_int64), ("ms", C.c_double), ("kernel_ms", C.c_double)]
 
 
 BAM_READ_MODES = {"host": 0, "device": 1}
@@ -359,6 +371,18 @@ def load_library():
     L.rsi_hot_geno_calls.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.rsi_hot_last_geno_stats.argtypes = [C.c_void_p, C.POINTER(RsiGenoStats)]
     L.rsi_hot_debug_geno.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p]
+    L.rsi_hot_loaded_depth.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    L.rsi_hot_depth_summary.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int]
+    L.rsi_hot_depth_regions.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rsi_hot_write_window_track.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_char_p, C.c_int64, C.c_char_p, C.c_int, C.POINTER(RsiTrackStats)]
+    L.rsi_hot_write_region_track.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int,
+                                             C.POINTER(RsiTrackStats)]
+    L.rsi_hot_last_depth_stats.argtypes = [C.c_void_p, C.POINTER(RsiDepthStats)]
+    L.rsi_hot_debug_depth_summary.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int]
+    L.rsi_hot_debug_depth_regions.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rsi_hot_debug_region_track.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_char_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                             C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(RsiTrackStats)]
+    L.rsi_hot_debug_region_track.restype = C.c_int64
     L.rsi_bgzf_write_eof.argtypes = [C.c_char_p]
     L.rsi_track_index_create.argtypes = []
     L.rsi_track_index_create.restype = C.c_void_p
@@ -1059,6 +1083,99 @@ class RsiHot:
         st = RsiGenoStats()
         self._check(self.lib.rsi_hot_last_geno_stats(self.ctx, C.byref(st)))
         return {k: getattr(st, k) for k, _ in RsiGenoStats._fields_}
+
+    # ---- `depth`: a per-base depth array in HBM summed up without a run ----
+    def loaded_depth(self):
+        """(device pointer, n) of the array the last load_depth_text / load_depth_bam (or a depth hook) left in the context's input
+        buffer (rsi_hot_loaded_depth)."""
+        p, n = C.c_void_p(), C.c_int64()
+        self._check(self.lib.rsi_hot_loaded_depth(self.ctx, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    @staticmethod
+    def _regions(start, end):
+        a = [np.ascontiguousarray(v, dtype=np.int64).reshape(-1) for v in (start, end)]
+        assert a[0].size == a[1].size
+        return a[0], a[1], a[0].size
+
+    def depth_summary(self, d_depth_ptr, n, dist=True):
+        """One pass over int32[n] in HBM (rsi_hot_depth_summary): (a DEPTH_SUMMARY record, the 65536-bin distribution as int64 or
+        None).  A negative depth raises RsiError."""
+        out = np.zeros(1, dtype=DEPTH_SUMMARY)
+        bins = np.zeros(DEPTH_BINS, dtype=np.int64) if dist else None
+        self._check(self.lib.rsi_hot_depth_summary(self.ctx, C.c_void_p(d_depth_ptr), int(n), out.ctypes.data,
+                                                   bins.ctypes.data if dist else None, DEPTH_BINS if dist else 0))
+        return out[0], bins
+
+    def depth_regions(self, d_depth_ptr, n, start, end):
+        """n, sum, min, max of regions [start, end) of int32[n] in HBM, each clipped to [0, n) (rsi_hot_depth_regions): a
+        DEPTH_REGION array."""
+        s, e, k = self._regions(start, end)
+        out = np.zeros(max(k, 1), dtype=DEPTH_REGION)
+        self._check(self.lib.rsi_hot_depth_regions(self.ctx, C.c_void_p(d_depth_ptr), int(n), k, s.ctypes.data, e.ctypes.data, out.ctypes.data))
+        return out[:k]
+
+    def write_window_track(self, d_depth_ptr, n, chrom, W, path, append=False, format=None):
+        """The mean depth of every window of W bases of int32[n] in HBM as lines of `chrom` (rsi_hot_write_window_track)."""
+        st = RsiTrackStats()
+        with self._track_format_for(format):
+            self._check(self.lib.rsi_hot_write_window_track(self.ctx, C.c_void_p(d_depth_ptr), int(n), self._name_bytes(chrom), int(W),
+                                                            os.fsencode(path), int(bool(append)), C.byref(st)))
+        return {f[0]: getattr(st, f[0]) for f in RsiTrackStats._fields_}
+
+    def write_region_track(self, d_depth_ptr, n, chrom, start, end, path, append=False, format=None):
+        """The mean depth of explicit regions, in the order given (rsi_hot_write_region_track)."""
+        s, e, k = self._regions(start, end)
+        st = RsiTrackStats()
+        with self._track_format_for(format):
+            self._check(self.lib.rsi_hot_write_region_track(self.ctx, C.c_void_p(d_depth_ptr), int(n), self._name_bytes(chrom), k, s.ctypes.data,
+                                                            e.ctypes.data, os.fsencode(path), int(bool(append)), C.byref(st)))
+        return {f[0]: getattr(st, f[0]) for f in RsiTrackStats._fields_}
+
+    def depth_stats(self):
+        """launches, workgroups (or tiles), bytes held, ms and kernel_ms of the context's last depth call (rsi_hot_last_depth_stats)."""
+        st = RsiDepthStats()
+        self._check(self.lib.rsi_hot_last_depth_stats(self.ctx, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in RsiDepthStats._fields_}
+
+    def debug_depth_summary(self, values, span=0, dist=True):
+        """depth_summary of a host array (test hook, rsi_hot_debug_depth_summary); span: values per workgroup (0: the default)."""
+        v = np.ascontiguousarray(values, dtype=np.int32)
+        out = np.zeros(1, dtype=DEPTH_SUMMARY)
+        bins = np.zeros(DEPTH_BINS, dtype=np.int64) if dist else None
+        rc = self.lib.rsi_hot_debug_depth_summary(self.ctx, v.ctypes.data if v.size else None, v.size, int(span), out.ctypes.data,
+                                                  bins.ctypes.data if dist else None, DEPTH_BINS if dist else 0)
+        self.last_depth_summary = out[0]   # (on a refusal its `negative` says how many)
+        self._check(rc)
+        return out[0], bins
+
+    def debug_depth_regions(self, values, start, end, tile=0):
+        """depth_regions of a host array (test hook, rsi_hot_debug_depth_regions); tile: values per tile (0: the default)."""
+        v = np.ascontiguousarray(values, dtype=np.int32)
+        s, e, k = self._regions(start, end)
+        out = np.zeros(max(k, 1), dtype=DEPTH_REGION)
+        self._check(self.lib.rsi_hot_debug_depth_regions(self.ctx, v.ctypes.data if v.size else None, v.size, int(tile), k, s.ctypes.data,
+                                                         e.ctypes.data, out.ctypes.data))
+        return out[:k]
+
+    def debug_region_track(self, values, chrom, W=0, start=(), end=(), span=0, tile=0, slice_lines=0, pos0=0, format=None):
+        """The window (W > 0) or region (W == 0) lines of a host array through the device's writer (test hook,
+        rsi_hot_debug_region_track): (bytes, stats).  With the format "bgzf" the bytes are the BGZF members of the text."""
+        v = np.ascontiguousarray(values, dtype=np.int32)
+        s, e, k = self._regions(start, end)
+        name = self._name_bytes(chrom)
+        lines = (-(-v.size // min(int(W), max(v.size, 1))) if v.size else 0) if W > 0 else k
+        cap = lines * (len(name) + 4 + 2 * 20 + 23 + 64) + 64   # room for every line at its longest, in a member of its own
+        st = RsiTrackStats()
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        with self._track_format_for(format):
+            n = self.lib.rsi_hot_debug_region_track(self.ctx, v.ctypes.data if v.size else None, v.size, name, int(W), k, s.ctypes.data, e.ctypes.data,
+                                                    int(span), int(tile), int(slice_lines), int(pos0), out.ctypes.data, cap, C.byref(st))
+        if n < 0:
+            self._check(int(n))
+        if n > cap:
+            raise RsiError(-6, "region track: more text than its lines can take")
+        return out[:n].tobytes(), {f[0]: getattr(st, f[0]) for f in RsiTrackStats._fields_}
 
     @staticmethod
     def _pin_arrays(cigars):

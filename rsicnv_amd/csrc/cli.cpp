@@ -5,7 +5,9 @@
 // as soon as its lines are parsed) or a BAM file (-b BAMFILE [-c RNAME], piled up on the device, calls
 // annotated with RP / Q0 from its read pairs); `rsicnv stat` and `rsicnv pin` annotate and sharpen a CNV list (-v CNVFILE) from
 // a BAM (run_cnvlist); `rsicnv geno` runs the chromosomes such a list names as rsi does and appends every region's copy
-// number, reduced on the device from the depth the run leaves there (geno_chromosome); plot is outside the accelerated path and says so.  A whole-genome file with several depth columns (a cohort, RNAME POS D1 ... DK) is
+// number, reduced on the device from the depth the run leaves there (geno_chromosome); `rsicnv depth` loads every
+// chromosome as rsi does and writes its coverage summary, distribution, per-base track and window / region means from HBM, with
+// no run (run_depth); plot is outside the accelerated path and says so.  A whole-genome file with several depth columns (a cohort, RNAME POS D1 ... DK) is
 // called sample by sample with -samples all|LIST: one OUT.k per selected column k.  A bedGraph depth file (RNAME START END
 // DEPTH: mosdepth, bedtools genomecov -bg / -bga) runs as the per-base file it stands for, whole or one chromosome (-c).
 // -track FILE saves the depth every chromosome was called from (raw, or GC-adjusted with -trackdepth gc) as one bedGraph file,
@@ -43,6 +45,7 @@
 #include "track_host.h"
 #include "pin_host.h"
 #include "geno_host.h"
+#include "depth_host.h"
 
 namespace {
 
@@ -71,6 +74,9 @@ struct Options {
   std::string refread;       // -refread device|host: the reference through the device reader (rsi_ref) or read_fasta (empty: host for text, device for BGZF)
   std::string refindex;      // -refindex PATH|none: the .gzi of a BGZF reference (empty: REFFILE.gzi when there, else the members are walked)
   bool ref_device = false;   // what that gives (main sets it)
+  std::string by;            // -by W | REGIONS.bed (depth): mean depth per window of W bases, or per line of a BED file
+  bool nobase = false;       // -nobase (depth): no PREFIX.per-base.bed.gz
+  bool out_given = false;    // -o was given (depth has no default prefix)
   double ploidy = 2.0;       // -ploidy P (geno): CN = P x the body's median over the chromosome's
   const std::vector<rsipinh::CnvLine>* geno = nullptr;   // `rsicnv geno`: the lines of -v CNVFILE (main sets it); every chromosome's run then
                                                          // ends in geno_chromosome instead of rows and plots
@@ -189,6 +195,18 @@ int usage() {
             << "             max(N, m) kept bases on each side; computed on the GPU from the depth the run leaves there.  With -samples\n"
             << "             OUT.k per column k and OUT.matrix (one CN per sample and line).  Lines of a chromosome the input lacks or\n"
             << "             whose run fails are written unchanged and OUT.log says why\n"
+            << "\n4. coverage of a sample before calling: summary, distribution, per-base depth, windows or regions\n\n"
+            << "   rsicnv depth (-b BAMFILE | -f REFFILE -d DEPTH) [-c RNAME] -o PREFIX [-by W | -by REGIONS.bed] [-nobase]\n"
+            << "             the chromosomes rsi would process (-q -Q -bamread -dformat -dindex -gpu as there; of -f only the .fai is read),\n"
+            << "             each loaded once and summed on the GPU, no calling run: PREFIX.mosdepth.summary.txt (length, bases, mean,\n"
+            << "             min, max per chromosome and in total), PREFIX.mosdepth.global.dist.txt (share of bases at least d deep, d\n"
+            << "             from the maximum, at most 65535, down to 0), PREFIX.per-base.bed.gz (one line per run of equal depth,\n"
+            << "             BGZF; -trackindex adds its .tbi, -nobase leaves it out) and with -by PREFIX.regions.bed.gz: the mean depth\n"
+            << "             of every window of W bases, or of every line of a BED file in the file's order (names with or without\n"
+            << "             chr, lines clipped to the chromosome).  -trackformat text writes both tracks as plain text, without .gz.\n"
+            << "             The files are laid out as mosdepth's; the depth is this program's pileup (M and = bases of base quality\n"
+            << "             -Q or more), not mosdepth's read spans.  Means and shares have two decimals, rounded half up.\n"
+            << "             -d PREFIX.per-base.bed.gz reads the per-base file back\n"
             << "\nOptions:\n"
             << "   -m   INT  bin size, default=101\n"
             << "   -q   INT  minimum mapping quality, default=0\n"
@@ -278,7 +296,7 @@ void parse(int argc, char** argv, Options& o) {
   size_t i = 1;
   if (a[1][0] != '-') {
     o.function = a[1];
-    if (o.function != "rsi" && o.function != "plot" && o.function != "stat" && o.function != "pin" && o.function != "geno") {
+    if (o.function != "rsi" && o.function != "plot" && o.function != "stat" && o.function != "pin" && o.function != "geno" && o.function != "depth") {
       std::cerr << "no such function " << o.function << std::endl;
       exit(usage());
     }
@@ -291,7 +309,7 @@ void parse(int argc, char** argv, Options& o) {
     else if (s == "-b") { o.bamfile = need(i); ++i; }
     else if (s == "-f") { o.reffile = need(i); ++i; }
     else if (s == "-v") { o.cnvfile = need(i); ++i; }
-    else if (s == "-o") { o.outfile = need(i); ++i; }
+    else if (s == "-o") { o.outfile = need(i); o.out_given = true; ++i; }
     else if (s == "-c") { o.chr = need(i); o.chr_given = true; ++i; }
     else if (s == "-s") o.saverd = true;
     else if (s == "-m") { o.P.m = atoi(need(i).c_str()); ++i; }
@@ -331,10 +349,12 @@ void parse(int argc, char** argv, Options& o) {
     else if (s == "-pairs") { o.pairs = need(i); ++i; }
     else if (s == "-refindex") { o.refindex = need(i); ++i; }
     else if (s == "-ploidy") { o.ploidy = atof(need(i).c_str()); ++i; }
+    else if (s == "-by") { o.by = need(i); ++i; }
+    else if (s == "-nobase") o.nobase = true;
     else { std::cerr << "unknown option " << s << std::endl; exit(usage()); }
   }
   if (o.rdfile.empty() && o.bamfile.empty()) { std::cerr << "need input file " << std::endl; exit(usage()); }
-  if (o.reffile.empty() && (o.function == "rsi" || o.function == "geno")) { std::cerr << "need reference file " << std::endl; exit(usage()); }
+  if (o.reffile.empty() && (o.function == "rsi" || o.function == "geno" || (o.function == "depth" && o.bamfile.empty()))) { std::cerr << "need reference file " << std::endl; exit(usage()); }
   if (o.outfile == o.bamfile || o.outfile == o.rdfile) { std::cerr << "output file is same as input file " << std::endl; exit(usage()); }
   if (!o.rdfile.empty() && o.chr.empty()) { std::cerr << "readdepth file and chromosome must be specified together" << std::endl; exit(usage()); }
   if ((o.P.m % 2) != 1) { o.P.m += 1; std::cerr << "m is changed to " << o.P.m << std::endl; }   // rsi.cpp:2061-2064
@@ -403,6 +423,42 @@ std::string inflate_line(const rsi_inflate_stats& s) {
     << " text bytes, inflate " << (s.format == 1 ? s.t_inflate_kernel_ms : s.t_host_inflate_ms) << " ms ("
     << (s.format == 1 ? "device" : "host") << ")" << (s.format == 1 && !s.eof_block ? ", no BGZF EOF block at the end" : "") << "\n";
   return o.str();
+}
+
+// The log's line for a BAM load that went through the device reader (-bamread device)
+std::string bam_read_line(rsi_ctx* ctx) {
+  rsi_bam_read_stats brs;
+  if (rsi_hot_last_bam_read_stats(ctx, &brs) != RSI_OK) return "";
+  std::ostringstream info;
+  info << "#bam: read on the device, " << brs.chunks << " chunks, " << brs.members << " BGZF blocks, " << brs.segments << " segments (" << brs.guessed
+       << " guessed right, " << brs.rewalked << " walked again, " << brs.passed << " passed over), upload " << brs.t_upload_ms << " ms, inflate "
+       << brs.t_inflate_ms << " ms, record finder " << brs.t_find_ms << " ms\n";
+  return info.str();
+}
+
+// The chromosomes to process: -c RNAME, or (BAM input, rsi.cpp:2114-2131) every reference of the header that is not a
+// mitochondrial / decoy name (and, for `geno`, that its list names).  false: the BAM's header cannot be read (stderr says why).
+bool select_chromosomes(const Options& o, std::vector<std::string>& todo, std::vector<int64_t>& todo_len, std::ostream& log) {
+  if (!o.bamfile.empty() && (o.chr.empty() || o.chr == "1-22XY")) {
+    std::vector<char> names(1 << 20);
+    std::vector<int64_t> lens(1 << 16);
+    const int nref = rsi_bam_references(o.bamfile.c_str(), names.data(), (int)names.size(), lens.data(), (int)lens.size());
+    if (nref < 0) { std::cerr << rsi_hot_last_error(nullptr) << std::endl; return false; }
+    std::istringstream iss(names.data());
+    std::string nm;
+    std::cerr << "#Check bam header for 1-22XY \n"; log << "#Check bam header for 1-22XY \n";
+    int k = 0;
+    while (std::getline(iss, nm)) {
+      const int64_t len = k < (int)lens.size() ? lens[(size_t)k] : 0;
+      ++k;
+      if (nm.find("MT") != std::string::npos || nm.find(".") != std::string::npos) continue;
+      if (o.geno && !geno_names(*o.geno, nm)) continue;   // `geno` runs the chromosomes its list names
+      todo.push_back(nm); todo_len.push_back(len);
+    }
+  } else {
+    todo.push_back(o.chr); todo_len.push_back(0);
+  }
+  return true;
 }
 
 void report_chromosome(rsi_ctx* ctx, const Options& o, const std::string& chr, rsi_result* res, const rsi_text_stats* ts,
@@ -597,11 +653,7 @@ void report_chromosome(rsi_ctx* ctx, const Options& o, const std::string& chr, r
     info << "depth text " << ts->t_total_ms * 1e-3 << " s (" << ts->bytes << " bytes, " << ts->lines << " lines"
          << (ts->fallback ? ", host parser: positions not increasing" : "") << ")";
   info << ", whole device path " << t_path << " s (" << S->t_device_ms << " ms on resident inputs)\n";
-  rsi_bam_read_stats brs;
-  if (from_bam && o.bamread == "device" && rsi_hot_last_bam_read_stats(ctx, &brs) == RSI_OK)
-    info << "#bam: read on the device, " << brs.chunks << " chunks, " << brs.members << " BGZF blocks, " << brs.segments << " segments (" << brs.guessed
-         << " guessed right, " << brs.rewalked << " walked again, " << brs.passed << " passed over), upload " << brs.t_upload_ms << " ms, inflate "
-         << brs.t_inflate_ms << " ms, record finder " << brs.t_find_ms << " ms\n";
+  if (from_bam && o.bamread == "device") info << bam_read_line(ctx);
   if (from_bam) {   // if ( fp_in ) cnv_stat(fp_in, bamidx, cnvlist), rsi.cpp:2210
     const bool on_device = o.pairs == "device";   // the pair table of the load, still in HBM; else a second pass over the file
     if ((on_device ? rsi_result_annotate_device(ctx, res) : rsi_result_annotate_bam(res, o.bamfile.c_str(), chr.c_str())) != RSI_OK)
@@ -1136,6 +1188,231 @@ struct GenoCollect {
   }
 };
 
+// `rsicnv depth`: every chromosome of the input loaded once as rsi loads it -- the same selection, the same
+// readers -- and summed from HBM, no calling run and no FASTA: PREFIX.mosdepth.summary.txt, PREFIX.mosdepth.global.dist.txt,
+// PREFIX.per-base.bed.gz (unless -nobase), PREFIX.regions.bed.gz (with -by), PREFIX.log.  One context, one chromosome at a time.
+int run_depth(const Options& o, int argc, char** argv) {
+  auto refuse = [](const std::string& why) { std::cerr << "rsicnv depth: " << why << std::endl; return 1; };
+  // refused where it cannot work, before any output
+  if (!o.out_given) return refuse("need an output prefix (-o PREFIX)");
+  if (o.gpus > 1) return refuse("-gpus: the coverage files are written by one device (-gpu INT picks it)");
+  if (o.samples_given) return refuse("-samples: one sample at a time (a cohort file's columns are not summed)");
+  if (!o.trackformat.empty() && o.trackformat != "text" && o.trackformat != "bgzf") return refuse("-trackformat " + o.trackformat + ": expected text or bgzf");
+  if (!o.bamread.empty() && o.bamread != "device" && o.bamread != "host") return refuse("-bamread " + o.bamread + ": expected device or host");
+  if (!o.dformat.empty() && o.dformat != "depth" && o.dformat != "bedgraph") return refuse("-dformat " + o.dformat + ": expected depth or bedgraph");
+  const bool from_bam = !o.bamfile.empty();
+  if (!o.bamread.empty() && !from_bam) return refuse("-bamread device|host: there is no BAM file to read (-b BAMFILE)");
+  const bool bgzf = o.trackformat != "text";
+  if (o.trackindex && (!bgzf || o.nobase)) return refuse("-trackindex: no BGZF per-base track to index (not with -trackformat text or -nobase)");
+  int64_t W = 0;
+  std::vector<rsidepth::BedLine> bed;
+  const bool by_number = !o.by.empty() && o.by.find_first_not_of("0123456789", o.by[0] == '-' ? 1 : 0) == std::string::npos && o.by != "-";
+  if (by_number) {
+    W = o.by.size() > 18 ? 0 : atoll(o.by.c_str());
+    if (W <= 0) return refuse("-by " + o.by + ": a window has at least one base");
+  } else if (!o.by.empty()) {
+    std::ifstream in(o.by.c_str());
+    if (!in) return refuse("-by: cannot open " + o.by);
+    std::string err;
+    if (!rsidepth::read_bed(in, o.by, bed, err)) return refuse("-by: " + err);
+  }
+  const bool bedgraph = !from_bam && (o.dformat.empty() ? is_bedgraph_name(o.rdfile) : o.dformat == "bedgraph");
+  const bool one = o.chr != "1-22XY" && !o.chr.empty();   // -c RNAME
+  const bool genome = !from_bam && (!one || bedgraph);    // the genome reader: RNAME POS DEPTH, or bedGraph (whole, or RNAME's lines)
+  std::vector<std::string> fnames;
+  std::vector<int64_t> flens;
+  if (!from_bam && !read_fai(o.reffile, fnames, flens)) return 1;
+  size_t fai_one = 0;
+  if (!from_bam && one) {   // read_fasta's rule: the first sequence named RNAME or chrRNAME
+    while (fai_one < fnames.size() && fnames[fai_one] != o.chr && fnames[fai_one] != "chr" + o.chr) ++fai_one;
+    if (fai_one == fnames.size()) return refuse(o.chr + " not found in fai index");
+  }
+  std::string dindex_path;   // -dindex: as rsi, for -d FILE.bed.gz -c RNAME
+  if (!o.dindex.empty() && o.dindex != "none" && !(bedgraph && one)) return refuse("-dindex: an index serves -d FILE -c RNAME with a bedGraph FILE in BGZF only");
+  if (bedgraph && one && o.dindex != "none") {
+    unsigned char head[4] = {0, 0, 0, 0};
+    FILE* f = fopen(o.rdfile.c_str(), "rb");
+    const bool is_bgzf = f && fread(head, 1, 4, f) == 4 && head[0] == 0x1f && head[1] == 0x8b && head[2] == 8 && (head[3] & 4);
+    if (f) fclose(f);
+    if (!o.dindex.empty()) dindex_path = o.dindex;
+    else if (is_bgzf) for (const char* ext : {".tbi", ".csi"}) if (dindex_path.empty() && access((o.rdfile + ext).c_str(), R_OK) == 0) dindex_path = o.rdfile + ext;
+  }
+
+  const std::string gz = bgzf ? ".gz" : "";
+  const std::string base_path = o.outfile + ".per-base.bed" + gz, region_path = o.outfile + ".regions.bed" + gz;
+  std::ofstream log((o.outfile + ".log").c_str());
+  std::ostringstream hdr;
+  hdr << "#command:   "; for (int i = 0; i < argc; ++i) hdr << argv[i] << " ";
+  hdr << "\n#bamfile:   " << o.bamfile << "\n#rdfile:    " << o.rdfile << "\n#chrom:     " << o.chr << "\n#min_mapq:  " << o.minq << "\n#min_baseQ: " << o.min_baseQ
+      << "\n#output:    " << o.outfile << "\n";
+  std::cerr << hdr.str(); log << hdr.str();
+  auto say = [&](const std::string& s) { std::cerr << s; log << s; };
+
+  int st = 0;
+  rsi_ctx* ctx = rsi_hot_create(o.device, &st);
+  if (!ctx) { say("rsicnv depth: no context on device " + std::to_string(o.device) + ": " + rsi_hot_last_error(nullptr) + "\n"); return 1; }
+  struct Destroy { rsi_ctx* c; ~Destroy() { rsi_hot_destroy(c); } } destroy{ctx};
+  std::shared_ptr<rsi_track_index> index = o.trackindex ? new_track_index() : nullptr;
+  if ((from_bam && !o.bamread.empty() && rsi_hot_set_bam_read(ctx, o.bamread == "device" ? RSI_BAM_READ_DEVICE : RSI_BAM_READ_HOST, 0) != RSI_OK) ||
+      rsi_hot_set_track_format(ctx, bgzf ? RSI_TRACK_BGZF : RSI_TRACK_TEXT) != RSI_OK) {
+    say(std::string("rsicnv depth: ") + rsi_hot_last_error(ctx) + "\n");
+    return 1;
+  }
+
+  std::vector<rsidepth::ChromSummary> rows;
+  std::vector<int64_t> total(rsidepth::kDistBins, 0), dist(rsidepth::kDistBins);
+  std::ostringstream dist_text;
+  std::vector<std::string> seen;
+  bool wrote_base = false, wrote_regions = false, ok = true, refused = false;
+  // one chromosome, its depth in HBM: the summary, then the tracks
+  auto chromosome = [&](const std::string& chr, const void* d_depth, int64_t n) {
+    const double t0 = now_s();
+    rsi_depth_summary sum;
+    rsi_depth_stats ds;
+    if (rsi_hot_depth_summary(ctx, d_depth, n, &sum, dist.data(), rsidepth::kDistBins) != RSI_OK) {
+      say("#depth: " + chr + ": " + rsi_hot_last_error(ctx) + ": nothing written for it\n");
+      refused = true;
+      return;
+    }
+    // the chromosome is summed: it enters the two tables here, whatever becomes of its tracks (a track that fails is an exit
+    // status of 1, and the log says which file lacks the chromosome or ends in a part of it)
+    seen.push_back(chr);
+    (void)rsi_hot_last_depth_stats(ctx, &ds);
+    int64_t launches = ds.launches;
+    rsidepth::ChromSummary row;
+    row.name = chr; row.length = n; row.bases = sum.sum; row.min = sum.min; row.max = sum.max;
+    rows.push_back(row);
+    rsidepth::write_dist(dist_text, chr, dist.data(), n, sum.max);
+    for (int k = 0; k < rsidepth::kDistBins; ++k) total[(size_t)k] += dist[(size_t)k];
+    rsi_track_stats tk;
+    if (!o.nobase) {
+      (void)rsi_hot_set_track_index(ctx, index.get());
+      const int rc = rsi_hot_write_track_device(ctx, d_depth, n, chr.c_str(), base_path.c_str(), wrote_base ? 1 : 0, &tk);
+      (void)rsi_hot_set_track_index(ctx, nullptr);
+      if (rc != RSI_OK) {
+        say("#depth: " + chr + ": per-base track: " + rsi_hot_last_error(ctx) + ": " + base_path + " is incomplete from " + chr + " on, the tables hold it\n");
+        ok = false;
+        return;
+      }
+      wrote_base = true;
+    }
+    if (W > 0 || !bed.empty() || (!o.by.empty() && !by_number)) {
+      int rc;
+      if (W > 0) rc = rsi_hot_write_window_track(ctx, d_depth, n, chr.c_str(), W, region_path.c_str(), wrote_regions ? 1 : 0, &tk);
+      else {
+        std::vector<int64_t> s, e;
+        for (const rsidepth::BedLine& l : bed) if (rsidepth::same_chrom(l.chrom, chr)) { s.push_back(l.start); e.push_back(l.end); }
+        rc = rsi_hot_write_region_track(ctx, d_depth, n, chr.c_str(), (int)s.size(), s.data(), e.data(), region_path.c_str(), wrote_regions ? 1 : 0, &tk);
+      }
+      if (rc != RSI_OK) {
+        say("#depth: " + chr + ": regions: " + rsi_hot_last_error(ctx) + ": " + region_path + " is incomplete from " + chr + " on, the tables" +
+            (o.nobase ? "" : " and " + base_path) + " hold it\n");
+        ok = false;
+        return;
+      }
+      wrote_regions = true;
+      (void)rsi_hot_last_depth_stats(ctx, &ds);
+      launches += ds.launches;
+    }
+    std::ostringstream line;
+    line << "#depth: " << chr << ": length " << n << ", mean " << rsidepth::fixed2(sum.sum, n) << ", " << launches << " launches, " << (now_s() - t0) * 1e3 << " ms\n";
+    say(line.str());
+  };
+
+  if (from_bam) {
+    std::vector<std::string> todo;
+    std::vector<int64_t> todo_len;
+    if (!select_chromosomes(o, todo, todo_len, log)) return 1;
+    const bool many = todo.size() > 1;
+    for (const std::string& chr : todo) {
+      rsi_bam_stats bs;
+      memset(&bs, 0, sizeof(bs));
+      if (rsi_hot_load_depth_bam(ctx, o.bamfile.c_str(), chr.c_str(), o.minq, o.min_baseQ, &bs) != RSI_OK) {
+        say("#depth: " + chr + ": " + rsi_hot_last_error(ctx) + "\n");
+        ok = false;
+        continue;
+      }
+      if (o.bamread == "device") say(bam_read_line(ctx));
+      if (many && bs.on_chrom == 0) { say("no reads on " + chr + "\n"); continue; }   // not "populated": rsi does not process it (rsi.cpp:2125)
+      const void* d = nullptr;
+      int64_t n = 0;
+      if (rsi_hot_loaded_depth(ctx, &d, &n) != RSI_OK) { say("#depth: " + chr + ": " + rsi_hot_last_error(ctx) + "\n"); ok = false; continue; }
+      chromosome(chr, d, n);
+    }
+  } else if (!genome) {   // POS DEPTH with -c RNAME
+    rsi_text_stats ts;
+    const void* d = nullptr;
+    int64_t n = 0;
+    if (rsi_hot_load_depth_text(ctx, o.rdfile.c_str(), flens[fai_one], &ts) != RSI_OK || rsi_hot_loaded_depth(ctx, &d, &n) != RSI_OK) {
+      say("#depth: " + o.chr + ": " + rsi_hot_last_error(ctx) + "\n");
+      ok = false;
+    } else {
+      rsi_inflate_stats is;
+      if (rsi_hot_last_inflate_stats(ctx, &is) == RSI_OK) say(inflate_line(is));
+      chromosome(o.chr, d, n);
+    }
+  } else {   // the genome reader, in the file's order
+    if (one) { fnames = {fnames[fai_one]}; flens = {flens[fai_one]}; }
+    std::vector<const char*> cnames;
+    for (const std::string& nm : fnames) cnames.push_back(nm.c_str());
+    rsi_genome_text* g = bedgraph && one && !dindex_path.empty()
+        ? rsi_genome_bedgraph_open_indexed(o.device, o.rdfile.c_str(), dindex_path.c_str(), (int)cnames.size(), cnames.data(), flens.data(), 2, 0, &st)
+        : bedgraph ? rsi_genome_bedgraph_open(o.device, o.rdfile.c_str(), (int)cnames.size(), cnames.data(), flens.data(), 2, 0, &st)
+                   : rsi_genome_text_open(o.device, o.rdfile.c_str(), (int)cnames.size(), cnames.data(), flens.data(), 2, 0, &st);
+    if (!g) { say(std::string("rsicnv depth: ") + rsi_hot_last_error(nullptr) + "\n"); return 1; }
+    for (;;) {
+      rsi_genome_chrom c;
+      const int rc = rsi_genome_text_next(g, &c);
+      if (rc == 0) break;
+      if (rc < 0) { say(std::string("rsicnv depth: ") + rsi_genome_text_last_error(g) + "\n"); ok = false; break; }
+      if (c.slot < 0) { if (!one) say(std::string(c.name) + " not found in fai index, skipped\n"); continue; }
+      chromosome(c.name, c.d_depth, c.n);
+      rsi_genome_text_release(g, c.slot);
+    }
+    rsi_inflate_stats is;
+    if (rsi_genome_text_inflate_stats(g, &is) == RSI_OK) say(inflate_line(is));
+    rsi_genome_text_close(g);
+  }
+
+  // the files end: the BGZF end-of-file blocks, the index, the two tables
+  if (bgzf && wrote_base && rsi_bgzf_write_eof(base_path.c_str()) != RSI_OK) { say(std::string("rsicnv depth: ") + rsi_hot_last_error(nullptr) + "\n"); ok = false; }
+  if (bgzf && wrote_regions && rsi_bgzf_write_eof(region_path.c_str()) != RSI_OK) { say(std::string("rsicnv depth: ") + rsi_hot_last_error(nullptr) + "\n"); ok = false; }
+  if (index && wrote_base && ok) {
+    if (rsi_track_index_write_tbi(index.get(), (base_path + ".tbi").c_str()) != RSI_OK) { say(std::string("rsicnv depth: ") + rsi_hot_last_error(nullptr) + "\n"); ok = false; }
+    else say("index written to " + base_path + ".tbi" + index_counts(index.get()) + "\n");
+  }
+  std::vector<std::pair<std::string, int64_t>> unmet;   // -by FILE: names of no chromosome of the input, by first appearance
+  for (const rsidepth::BedLine& l : bed) {
+    bool met = false;
+    for (const std::string& c : seen) met = met || rsidepth::same_chrom(l.chrom, c);
+    if (met) continue;
+    size_t k = 0;
+    while (k < unmet.size() && unmet[k].first != l.chrom) ++k;
+    if (k == unmet.size()) unmet.emplace_back(l.chrom, 0);
+    ++unmet[k].second;
+  }
+  for (const auto& u : unmet) say("#depth: -by: " + u.first + " is not in the input" + (refused ? " (or was refused above)" : "") + ": " + std::to_string(u.second) + " lines passed over\n");
+  {
+    std::ofstream out((o.outfile + ".mosdepth.summary.txt").c_str());
+    rsidepth::write_summary(out, rows);
+    out.close();
+    if (!out.good()) ok = false;
+  }
+  {
+    int64_t n = 0;
+    int32_t top = 0;
+    for (const rsidepth::ChromSummary& r : rows) { n += r.length; top = std::max(top, r.max); }
+    std::ofstream out((o.outfile + ".mosdepth.global.dist.txt").c_str());
+    out << dist_text.str();
+    rsidepth::write_dist(out, "total", total.data(), n, top);
+    out.close();
+    if (!out.good()) ok = false;
+  }
+  say("coverage written to " + o.outfile + ".mosdepth.summary.txt, " + o.outfile + ".mosdepth.global.dist.txt" + (wrote_base ? ", " + base_path : "") +
+      (wrote_regions ? ", " + region_path : "") + "\n");
+  return ok ? 0 : 1;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -1146,6 +1423,7 @@ int main(int argc, char** argv) {
   Options o;
   parse(argc, argv, o);
   if (o.function == "stat" || o.function == "pin") return run_cnvlist(o);
+  if (o.function == "depth") return run_depth(o, argc, argv);
   std::vector<rsipinh::CnvLine> geno_lines;
   if (o.function == "geno") {   // refused where it cannot work, before any output
     if (o.cnvfile.empty()) { std::cerr << "rsicnv geno: need a list of regions (-v CNVFILE)" << std::endl; return 1; }
@@ -1312,25 +1590,7 @@ int main(int argc, char** argv) {
   // a mitochondrial / decoy name and has reads
   std::vector<std::string> todo;
   std::vector<int64_t> todo_len;
-  if (from_bam && (o.chr.empty() || o.chr == "1-22XY")) {
-    std::vector<char> names(1 << 20);
-    std::vector<int64_t> lens(1 << 16);
-    const int nref = rsi_bam_references(o.bamfile.c_str(), names.data(), (int)names.size(), lens.data(), (int)lens.size());
-    if (nref < 0) { std::cerr << rsi_hot_last_error(nullptr) << std::endl; return 0; }
-    std::istringstream iss(names.data());
-    std::string nm;
-    std::cerr << "#Check bam header for 1-22XY \n"; log << "#Check bam header for 1-22XY \n";
-    int k = 0;
-    while (std::getline(iss, nm)) {
-      const int64_t len = k < (int)lens.size() ? lens[(size_t)k] : 0;
-      ++k;
-      if (nm.find("MT") != std::string::npos || nm.find(".") != std::string::npos) continue;
-      if (o.geno && !geno_names(*o.geno, nm)) continue;   // `geno` runs the chromosomes its list names
-      todo.push_back(nm); todo_len.push_back(len);
-    }
-  } else {
-    todo.push_back(o.chr); todo_len.push_back(0);
-  }
+  if (!select_chromosomes(o, todo, todo_len, log)) return 0;
   const bool many = todo.size() > 1;
 
   // write_cnv_to_file, rsi.cpp:1592-1616: the first processed chromosome opens the file and writes the header, the others

@@ -635,6 +635,24 @@ void launch_geno_plan32(GenoState* st, int njobs, GenoOut* out, unsigned int* ma
 void launch_geno_hist32(const int32_t* d, const GenoTile* tiles, int ntiles, const GenoState* st, unsigned int* hist, hipStream_t stream);
 void launch_geno_scan32(GenoState* st, int njobs, unsigned int* hist, GenoOut* out, hipStream_t stream);
 
+// ---- `depth`: a chromosome's per-base depth int32[n] summed up without a run (kernels_depth.hip) ----
+// launch_depth_summary: one pass, a workgroup per `span` values.  acc: vmin = INT32_MAX, vmax = INT32_MIN and zeros before the
+// launch; dist: kDepthBins zeros.  After it acc holds the exact sum, minimum and maximum of the non-negative depths, how many lie
+// above 65535 (counted in bin 65535) and how many are negative (counted nowhere else: they index nothing).
+struct DepthAcc { unsigned long long sum, over, negative; int32_t vmin, vmax; };
+constexpr int kDepthThreads = 256, kDepthBins = 65536;
+constexpr int kDepthSplit = 512, kDepthCopies = 16;   // depths below the split are counted in LDS, in so many counters per value
+constexpr long long kDepthSpan = 1ll << 17;            // values per workgroup
+void launch_depth_summary(const int32_t* d, long long n, long long span, DepthAcc* acc, unsigned int* dist, hipStream_t stream);
+// Windows [k W, min((k + 1) W, n)) for k in [w0, w1), a slice: launch_depth_window_table writes start[k - w0], end[k - w0] and
+// clears sum[k - w0]; launch_depth_windows adds every window's depths into sum[k - w0], exact in 64 bits, a workgroup per `span`
+// bases of the slice (1 <= span <= kWindowSpan; W need not divide it, and may exceed it).  W >= 1, w1 <= ceil(n / W).
+constexpr int kWindowSpan = 4096;
+void launch_depth_window_table(long long w0, long long w1, long long W, long long n, long long* start, long long* end, unsigned long long* sum,
+                               hipStream_t stream);
+void launch_depth_windows(const int32_t* d, long long n, long long W, long long w0, long long w1, int span, unsigned long long* sum,
+                          hipStream_t stream);
+
 // ---- depth track: an int32 array as bedGraph text, run-length encoded and formatted on the device (kernels_track.hip) ----
 // One line "NAME \t pos0+start \t pos0+end \t value \n" per maximal run of equal values of v[0, n), worked through in slices
 // [b, e) of bases.  A run start is i == 0 or v[i] != v[i - 1] -- read from the whole array, so slicing moves no start.  A line is
@@ -688,6 +706,17 @@ void launch_bintrack_line_bytes(const BinTrackSource& src, TrackState* st, int n
                                 hipStream_t stream);
 void launch_bintrack_format(const BinTrackSource& src, const unsigned int* ltiles, long long nlines, const TrackName& name, char* text,
                             long long cap, hipStream_t stream);
+
+// ---- region lines: "NAME \t pos0+start \t pos0+end \t mean \n" from (start, end, sum) triples in HBM (kernels_track.hip) ----
+// One line per triple of a slice, in order; windows (-by W) and BED regions (-by FILE) both come as triples.  The mean is
+// sum / (end - start) with two decimals, rounded half up in integers: a = S / L, r = S mod L, hundredths (200 r + L) / (2 L), a
+// hundred of them carrying into a; 0.00 when end <= start or the sum is not positive.  No state passes from slice to slice.
+struct RegionTrackSource { const long long* start; const long long* end; const long long* sum; };
+// st for a slice of nlines lines, then passes 4 and 5 of the depth track on the triples (ltiles: track_tiles(nlines) + 1 words)
+void launch_regiontrack_line_bytes(const RegionTrackSource& src, TrackState* st, long long nlines, long long pos0, int name_len,
+                                   unsigned int* ltiles, hipStream_t stream);
+void launch_regiontrack_format(const RegionTrackSource& src, const unsigned int* ltiles, long long nlines, long long pos0, const TrackName& name,
+                               char* text, long long cap, hipStream_t stream);
 
 
 // ---- BGZF tracks: a slice's text deflated member by member (kernels_deflate.hip, deflate_core.h) ----

@@ -269,6 +269,44 @@ struct BinLines {
   }
 };
 
+// ---- region lines (`rsicnv depth -by`): a line per (start, end, sum) triple, its value the mean ----
+// The passes hand a line's `val` from the source to the value format; here it is the line's index in the slice, and the format
+// reads the triple behind it: a mean needs 64 bits of sum and a length, which no int holds.
+struct RegionLines {
+  const long long* __restrict__ start;
+  const long long* __restrict__ end;
+  __device__ void get(long long j, long long& s, long long& e, int& val) const { s = start[j]; e = end[j]; val = (int)j; }
+};
+// sum / (end - start), two decimals, rounded half up: q = 100 a + h hundredths with a = S / L, r = S mod L, h = (200 r + L) / (2 L)
+// (h = 100 is the carry into a); 0.00 for an empty line or a sum that is not positive.  200 r stays below 2^63 for L < 2^55, and
+// 100 a in 64 bits because a, a mean of int32 depths, is below 2^31.
+struct MeanValue {
+  const long long* __restrict__ start;
+  const long long* __restrict__ end;
+  const long long* __restrict__ sum;
+  __device__ int len(int j, unsigned long long& q) const {
+    const long long L = end[j] - start[j], S = sum[j];
+    q = 0ull;
+    if (L > 0 && S > 0) {
+      const unsigned long long l = (unsigned long long)L, a = (unsigned long long)S / l, r = (unsigned long long)S % l;
+      q = 100ull * a + (200ull * r + l) / (2ull * l);
+    }
+    return dec_len_u64(q / 100ull) + 3;   // the point and two places
+  }
+  __device__ char* put(char* __restrict__ p, int, unsigned long long q, int lv) const {
+    put_dec(p, lv - 3, q / 100ull);
+    const unsigned int f = (unsigned int)(q % 100ull);
+    p[lv - 3] = '.';
+    p[lv - 2] = (char)('0' + (int)(f / 10u));
+    p[lv - 1] = (char)('0' + (int)(f % 10u));
+    return p + lv;
+  }
+};
+
+__global__ void k_regiontrack_begin(TrackState* __restrict__ st, long long nlines) {
+  st->carry = -1; st->nstarts = 0; st->nlines = nlines; st->nbytes = 0;
+}
+
 // ---- the index pass: one thread per line, as the format pass (kernels.h states the records) ----
 // tabix's reg2bin of [s, e1], e1 the line's last base: the first level at which both fall into one bin
 __device__ inline unsigned int reg2bin(long long s, long long e1) {
@@ -418,6 +456,24 @@ void launch_bintrack_format(const BinTrackSource& src, const unsigned int* ltile
     RSI_LAUNCH((k_track_format<BinLines, RatioValue>), dim3(ntiles), dim3(kTrackTile), 0, stream, lines, RatioValue{src.median2}, ltiles, nlines, 0ll, name, text, cap);
   else
     RSI_LAUNCH((k_track_format<BinLines, DecValue>), dim3(ntiles), dim3(kTrackTile), 0, stream, lines, DecValue{}, ltiles, nlines, 0ll, name, text, cap);
+}
+
+void launch_regiontrack_line_bytes(const RegionTrackSource& src, TrackState* st, long long nlines, long long pos0, int name_len,
+                                   unsigned int* ltiles, hipStream_t stream) {
+  const int ntiles = track_tiles(nlines);
+  if (ntiles <= 0) return;
+  RSI_LAUNCH(k_regiontrack_begin, dim3(1), dim3(1), 0, stream, st, nlines);
+  RSI_LAUNCH((k_track_line_bytes<RegionLines, MeanValue>), dim3(ntiles), dim3(kTrackTile), 0, stream, RegionLines{src.start, src.end},
+             MeanValue{src.start, src.end, src.sum}, st, pos0, name_len, ltiles);
+  RSI_LAUNCH(k_track_scan_lines, dim3(1), dim3(kTrackTile), 0, stream, ltiles, static_cast<const long long*>(nullptr), st);
+}
+
+void launch_regiontrack_format(const RegionTrackSource& src, const unsigned int* ltiles, long long nlines, long long pos0, const TrackName& name,
+                               char* text, long long cap, hipStream_t stream) {
+  const int ntiles = track_tiles(nlines);
+  if (ntiles <= 0) return;
+  RSI_LAUNCH((k_track_format<RegionLines, MeanValue>), dim3(ntiles), dim3(kTrackTile), 0, stream, RegionLines{src.start, src.end},
+             MeanValue{src.start, src.end, src.sum}, ltiles, nlines, pos0, name, text, cap);
 }
 
 }  // namespace rsik

@@ -1560,6 +1560,7 @@ void rsi_hot_destroy(rsi_ctx* ctx) {
   if (ctx->mailbox) (void)hipHostFree(ctx->mailbox);
   for (int b = 0; b < 2; ++b) if (ctx->text_pin[b]) (void)hipHostFree(ctx->text_pin[b]);
   track_free(ctx);
+  depth_free(ctx);
   for (int b = 0; b < 2; ++b) {
     for (hipEvent_t e : ctx->bamdev.ev[b]) if (e) (void)hipEventDestroy(e);
     if (ctx->bamdev.find[b]) (void)hipEventDestroy(ctx->bamdev.find[b]);

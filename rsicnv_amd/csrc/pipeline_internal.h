@@ -198,6 +198,13 @@ struct rsi_ctx {
     DevBuf tiles, hist, state, out;
     rsi_geno_stats stats{};
   } geno;
+  // `depth` (rsi_hot_depth_summary, _depth_regions; depth.hip): nothing of it exists until the first call.  Every
+  // call clears what it uses.
+  struct Depth {
+    DevBuf acc, dist, tiles, state;
+    hipEvent_t ev[2] = {nullptr, nullptr};   // around the summary pass
+    rsi_depth_stats stats{};
+  } depth;
   int64_t n_in = 0;                        // length of the depth currently in in_depth
   DevBuf gcbits, nbits, rd_gc, rdc, binmed, binsum, tnb, tmed, first_del;
   DevBuf depth8, rescaled8;   // byte copies: the raw depth (K2 writes it, K3' streams it), the rescaled depth (K3' -> K4')
@@ -415,6 +422,15 @@ inline void normalize_intervals(std::vector<std::pair<int64_t, int64_t>>& v, int
 // The GC-rescaled depth of the last run in ctx->rd_gc (pipeline.hip: built on demand); RSI_ERR_BAD_ARG after a -NOGC run.
 int ensure_rd_gc(rsi_ctx* ctx);
 void track_free(rsi_ctx* ctx);   // track.hip: the track writer's workspace and events
+void depth_free(rsi_ctx* ctx);   // depth.hip: the events of `depth`
+// depth.hip: host values[n] into the context's input depth buffer (n_in = n), the context entered and its mailbox reset: what the
+// depth hooks begin with.  n == 0 uploads nothing and leaves n_in = 0.
+int depth_upload(rsi_ctx* ctx, const int32_t* values, int64_t n);
+// depth.hip: n, sum, min and max of nreg regions [start, end) of d_depth[n], each clipped to [0, n), through geno's tile table and
+// min / max kernels (tile: values per tile, 0 for the default).  What rsi_hot_depth_regions and the region track share; the
+// caller has entered the context and reset the mailbox.
+int depth_region_records(rsi_ctx* ctx, const int32_t* d_depth, int64_t n, int64_t nreg, const int64_t* start, const int64_t* end, int tile,
+                         rsi_depth_region* out);
 
 struct ExcludeOneShot {   // first statement of a run entry point: the armed mask does not outlive the call
   rsi_ctx* ctx;

@@ -8,6 +8,7 @@
 #include "pipeline_internal.h"
 #include "track_host.h"
 #include "track_index_host.h"
+#include "depth_host.h"
 #include <sys/stat.h>
 #include <new>
 
@@ -446,9 +447,153 @@ int bin_track_run(rsi_ctx* ctx, const int32_t* d_v, int64_t nb, int m, int64_t n
   return RSI_OK;
 }
 
+// Region lines (`rsicnv depth -by`): a line "chrom start end mean" per (start, end, sum) triple into the sink, a
+// slice of lines at a time.  W > 0: the windows of d_v[0, n), whose triples a slice's measuring passes make on the device
+// (kernels_depth.hip; span: bases per workgroup of the sums).  W == 0: the host's triples, a slice's uploaded in front of its
+// passes.  No state passes from slice to slice and nothing is indexed.  extra_launches: what the caller launched for the triples.
+struct RegionTriples { std::vector<int64_t> start, end, sum; };
+int region_track_run(rsi_ctx* ctx, const int32_t* d_v, int64_t n, int64_t W, int span, const RegionTriples* host, const char* chrom, int64_t pos0,
+                     int64_t slice_lines, int64_t extra_launches, TrackSink& sink, rsi_track_stats* stats) {
+  const double t_begin = now_ms();
+  rsi_track_stats S;
+  memset(&S, 0, sizeof(S));
+  if (stats) *stats = S;
+  ctx->last_deflate = rsi_deflate_stats{};
+  ctx->depth.stats.launches = extra_launches;
+  const bool bgzf = ctx->track_format == RSI_TRACK_BGZF;
+  const int name_len = rsitrack::name_length(chrom);
+  if (name_len < 0) return fail(ctx, RSI_ERR_BAD_ARG, "region track: the name must have 1 to 255 bytes and no tab or newline");
+  if (pos0 < -(1ll << 62) || pos0 > (1ll << 62)) return fail(ctx, RSI_ERR_BAD_ARG, "region track: bad coordinate offset");
+  if (W > 0 && n > 0) W = std::min(W, n);   // one window then, as for W = n
+  const int64_t count = W > 0 ? rsidepth::window_count(n, W) : (int64_t)host->start.size();
+  rsidepth::Plan plan;
+  if (!rsidepth::plan(name_len, count, slice_lines, plan)) return fail(ctx, RSI_ERR_BAD_ARG, "region track: bad line count");
+  S.n = count;
+  if (count == 0) { if (stats) *stats = S; return RSI_OK; }
+  if (W > 0 && (!d_v || span < 1 || span > kWindowSpan)) return fail(ctx, RSI_ERR_BAD_ARG, "region track: no values, or a span outside 1 .. 4096");
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!ctx_enter(ctx)) return RSI_ERR_HIP;
+  const TrackLayout L = track_layout(plan.text_cap, 0, 0, plan.slice, (size_t)3 * plan.slice, bgzf);
+  int rc = track_ensure(ctx, L);
+  if (rc != RSI_OK) return rc;
+  rsi_ctx::TrackWs& w = ctx->track;
+  TrackBgzf z;
+  if (bgzf) z.place(w.dev, L);
+  TrackIndexer X;   // off: these lines are not indexed
+  char* d_text = static_cast<char*>(w.dev) + L.text;
+  unsigned int* d_ltiles = reinterpret_cast<unsigned int*>(static_cast<char*>(w.dev) + L.ltiles);
+  TrackState* d_st = reinterpret_cast<TrackState*>(static_cast<char*>(w.dev) + L.state);
+  long long* d_start = reinterpret_cast<long long*>(static_cast<char*>(w.dev) + L.table);
+  long long* d_end = d_start + plan.slice;
+  long long* d_sum = d_end + plan.slice;
+  const RegionTrackSource src{d_start, d_end, d_sum};
+  TrackName name;
+  memset(&name, 0, sizeof(name));
+  memcpy(name.s, chrom, (size_t)name_len);
+  name.len = name_len;
+  hipStream_t st = ctx->stream;
+  hipError_t up = hipSuccess;   // a slice's upload that failed: its line count is then out of range for nobody, so it is told here
+  rc = track_slices(ctx, count, plan.slice, plan.text_cap, plan.max_line, d_st, d_text, sink, S, z, X,
+      [&](int64_t b, int64_t end) {
+        if (W > 0) {
+          launch_depth_window_table(b, end, W, n, d_start, d_end, reinterpret_cast<unsigned long long*>(d_sum), st);
+          launch_depth_windows(d_v, n, W, b, end, span, reinterpret_cast<unsigned long long*>(d_sum), st);
+        } else {
+          const size_t bytes = (size_t)(end - b) * 8;
+          for (auto pr : {std::make_pair(d_start, &host->start), std::make_pair(d_end, &host->end), std::make_pair(d_sum, &host->sum)}) {
+            const hipError_t e = hipMemcpyAsync(pr.first, pr.second->data() + b, bytes, hipMemcpyHostToDevice, st);
+            if (e != hipSuccess && up == hipSuccess) up = e;
+          }
+        }
+        launch_regiontrack_line_bytes(src, d_st, end - b, pos0, name_len, d_ltiles, st);
+      },
+      [](int64_t b, int64_t end) { return end - b; },
+      [&](int64_t, int64_t nlines) { launch_regiontrack_format(src, d_ltiles, nlines, pos0, name, d_text, plan.text_cap, st); },
+      [](int64_t, int64_t) { return (int64_t)0; },
+      [](int64_t, int64_t, int64_t, const TrackIndexOut&) {});
+  if (rc == RSI_OK && up != hipSuccess) rc = fail(ctx, RSI_ERR_HIP, std::string("region track: hipMemcpyAsync: ") + hipGetErrorString(up));
+  if (rc != RSI_OK) return rc;
+  // per slice: (the window table and sums,) the state, the line lengths, their scan, the format pass(, deflate and pack)
+  ctx->depth.stats.launches = extra_launches + S.slices * ((W > 0 ? 2 : 0) + 4 + (bgzf ? 2 : 0));
+  S.t_total_ms = now_ms() - t_begin;
+  if (stats) *stats = S;
+  ctx->last_deflate = z.D;
+  return RSI_OK;
+}
+
+// The triples of explicit regions: summed on the device (depth.hip), written with their clipped coordinates -- or, with nothing
+// left of them, with the ones given and a sum of 0
+int region_triples(rsi_ctx* ctx, const int32_t* d_v, int64_t n, int nreg, const int64_t* start, const int64_t* end, int tile, RegionTriples& T) {
+  for (int i = 0; i < nreg; ++i)
+    if (start[i] < -(1ll << 62) || start[i] > (1ll << 62) || end[i] < -(1ll << 62) || end[i] > (1ll << 62))
+      return fail(ctx, RSI_ERR_BAD_ARG, "region track: a coordinate beyond 2^62");
+  std::vector<rsi_depth_region> rec((size_t)std::max(nreg, 1));
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!ctx_enter(ctx)) return RSI_ERR_HIP;
+  mailbox_reset(ctx);
+  const int rc = depth_region_records(ctx, d_v, n, nreg, start, end, tile, rec.data());
+  if (rc != RSI_OK) return rc;
+  T.start.resize((size_t)nreg); T.end.resize((size_t)nreg); T.sum.resize((size_t)nreg);
+  for (int i = 0; i < nreg; ++i) {
+    rsidepth::written(start[i], end[i], n, T.start[(size_t)i], T.end[(size_t)i]);
+    T.sum[(size_t)i] = rec[(size_t)i].sum;
+  }
+  return RSI_OK;
+}
+
+// windows (W > 0) or regions of d_v[0, n) into `path`
+int region_track_to_file(rsi_ctx* ctx, const int32_t* d_v, int64_t n, const char* chrom, int64_t W, int nreg, const int64_t* start,
+                         const int64_t* end, const char* path, int append, rsi_track_stats* stats) {
+  if (!ctx) return fail(ctx, RSI_ERR_BAD_ARG, "null context");
+  if (n < 0 || n >= (1ll << 31) || (n > 0 && !d_v)) return fail(ctx, RSI_ERR_BAD_ARG, "region track: bad array");
+  if (!path || !path[0]) return fail(ctx, RSI_ERR_BAD_ARG, "region track: no path");
+  if (rsitrack::name_length(chrom) < 0) return fail(ctx, RSI_ERR_BAD_ARG, "region track: the name must have 1 to 255 bytes and no tab or newline");
+  RegionTriples T;
+  if (W <= 0) { const int rc = region_triples(ctx, d_v, n, nreg, start, end, 0, T); if (rc != RSI_OK) return rc; }
+  TrackSink sink;
+  sink.fd = ::open(path, O_WRONLY | O_CREAT | (append ? O_APPEND : O_TRUNC), 0644);
+  if (sink.fd < 0) return fail(ctx, RSI_ERR_INTERNAL, std::string("region track: cannot open ") + path + ": " + strerror(errno));
+  int rc = region_track_run(ctx, d_v, n, W, kWindowSpan, W > 0 ? nullptr : &T, chrom, 0, 0, W > 0 ? 0 : ctx->depth.stats.launches, sink, stats);
+  if (::close(sink.fd) != 0 && rc == RSI_OK) rc = fail(ctx, RSI_ERR_INTERNAL, std::string("region track: write failed: ") + strerror(errno));
+  return rc;
+}
+
 }  // namespace
 
 extern "C" {
+
+int rsi_hot_write_window_track(rsi_ctx* ctx, const void* d_depth, int64_t n, const char* chrom, int64_t W, const char* path, int append,
+                               rsi_track_stats* stats) {
+  if (W < 1) return fail(ctx, RSI_ERR_BAD_ARG, "window track: the window must have at least one base");
+  return region_track_to_file(ctx, static_cast<const int32_t*>(d_depth), n, chrom, W, 0, nullptr, nullptr, path, append, stats);
+}
+
+int rsi_hot_write_region_track(rsi_ctx* ctx, const void* d_depth, int64_t n, const char* chrom, int nreg, const int64_t* start,
+                               const int64_t* end, const char* path, int append, rsi_track_stats* stats) {
+  if (nreg < 0 || (nreg > 0 && (!start || !end))) return fail(ctx, RSI_ERR_BAD_ARG, "region track: bad region list");
+  return region_track_to_file(ctx, static_cast<const int32_t*>(d_depth), n, chrom, 0, nreg, start, end, path, append, stats);
+}
+
+int64_t rsi_hot_debug_region_track(rsi_ctx* ctx, const int32_t* values, int64_t n, const char* chrom, int64_t W, int nreg, const int64_t* start,
+                                   const int64_t* end, int span, int tile, int64_t slice_lines, int64_t pos0, char* out, int64_t cap,
+                                   rsi_track_stats* stats) {
+  if (!ctx) return fail(ctx, RSI_ERR_BAD_ARG, "null context");
+  if (n < 0 || n >= (1ll << 31) - 4096 || (n > 0 && !values) || W < 0 || span < 0 || tile < 0 || slice_lines < 0 || nreg < 0 ||
+      (W == 0 && nreg > 0 && (!start || !end)))
+    return fail(ctx, RSI_ERR_BAD_ARG, "region track: bad argument");
+  if (int rc = depth_upload(ctx, values, n)) return rc;
+  RegionTriples T;
+  if (W == 0) { const int rc = region_triples(ctx, ctx->in_depth.as<int32_t>(), n, nreg, start, end, tile, T); if (rc != RSI_OK) return rc; }
+  std::string text;
+  TrackSink sink;
+  sink.text = &text;
+  const int rc = region_track_run(ctx, ctx->in_depth.as<int32_t>(), n, W, span > 0 ? span : kWindowSpan, W > 0 ? nullptr : &T, chrom, pos0,
+                                  slice_lines, W > 0 ? 0 : ctx->depth.stats.launches, sink, stats);
+  if (rc != RSI_OK) return rc;
+  if (out && (int64_t)text.size() <= cap) memcpy(out, text.data(), text.size());
+  return (int64_t)text.size();
+}
+
 
 int rsi_hot_write_track(rsi_ctx* ctx, int which, const char* chrom, const char* path, int append, rsi_track_stats* stats) {
   if (!ctx) return fail(ctx, RSI_ERR_BAD_ARG, "null context");

@@ -777,7 +777,7 @@ bool read_fai(const std::string& fasta, std::vector<std::string>& names, std::ve
   return true;
 }
 
-// -d GENOME.depth without -c: the main thread drives the genome reader (ingest.hip) and reads each finished chromosome's FASTA;
+// -d GENOME.depth without -c: the main thread drives the genome reader (ingest_genome.hip) and reads each finished chromosome's FASTA;
 // `workers` threads, each on a context of one pool on -gpu, run the chromosomes whose depth is already in HBM and format them
 // (report_chromosome, on the context that ran them: the plots fetch from it).  At most workers + 1 depth buffers exist: before
 // asking for the next chromosome the main thread waits until one of the `workers` it may hold has come back.  cols (-samples):

@@ -91,8 +91,7 @@ int depth_summary_run(rsi_ctx* ctx, const int32_t* d_depth, int64_t n, int64_t s
   HIPCHK(copy_d2h(ctx, &acc, D.acc.p, sizeof(acc)));
   if (nbins) HIPCHK(copy_d2h(ctx, bins.data(), D.dist.p, (size_t)nbins * 4));
   HIPCHK(CTX_SYNC());
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, D.ev[0], D.ev[1]) == hipSuccess) D.stats.kernel_ms = ms;
+  D.stats.kernel_ms = elapsed_ms(D.ev[0], D.ev[1]);
   D.stats.launches = 1;
   D.stats.workgroups = (n + span - 1) / span;
   D.stats.ms = now_ms() - t0;

@@ -1,4 +1,4 @@
-// pin_host.h -- the host side of `rsicnv stat` and `rsicnv pin`, plain C++ for cli.cpp, ingest.hip and
+// pin_host.h -- the host side of `rsicnv stat` and `rsicnv pin`, plain C++ for cli.cpp, ingest_bam.hip and
 // tests/pin_harness.cpp: the CNV list as read_cnvlist reads it (loaddata.cpp:542 and :606), cnv_stat's windows carried through
 // the whole file, the sample's means and deviations by bam_rd_pr_stats' own loops, and the two output rows.
 #pragma once

@@ -1461,7 +1461,7 @@ int run_device_impl(rsi_ctx* ctx, const rsi_params* Pp, const int32_t* d_depth, 
   ctx->phases.push_back({"z.total", S.t_device_ms});
   if (ctx->timing) {
     double tot = 0;
-    for (const KernelTime& k : ctx->ktimes) { float ms = 0; (void)hipEventElapsedTime(&ms, k.a, k.b); tot += ms; }
+    for (const KernelTime& k : ctx->ktimes) tot += elapsed_ms(k.a, k.b);
     S.t_kernels_ms = tot;
   }
   ctx->run_m = P.m; ctx->run_rdmedian = S.RDmedian;   // the run is whole: rsi_hot_write_bin_track may read its bins
@@ -2340,7 +2340,7 @@ int rsi_hot_kernel_times(const rsi_ctx* ctx, const char** names, float* ms, int 
   if (!ctx) return 0;
   int k = 0;
   for (const KernelTime& t : ctx->ktimes) {
-    if (k < cap) { names[k] = t.name; float v = 0; (void)hipEventElapsedTime(&v, t.a, t.b); ms[k] = v; }
+    if (k < cap) { names[k] = t.name; ms[k] = (float)elapsed_ms(t.a, t.b); }
     ++k;
   }
   return k;

@@ -1,6 +1,7 @@
 // pipeline_internal.h -- what the translation units behind include/rsi_hot.h share: the context (device workspace,
 // stream, pinned mailbox), the pool's gate, the small-transfer and timing helpers, the layout of the `small` buffer.
-// pipeline.hip: one chromosome through the path; ingest.hip: depth from text / BAM; pool.hip: several chromosomes at once.
+// pipeline.hip: one chromosome through the path; ingest.hip, ingest_bam.hip, ingest_genome.hip, ref.hip: depth from text / BAM,
+// the whole-genome reader, the reference; pool.hip: several chromosomes at once.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -107,6 +108,11 @@ struct KernelTime { const char* name; hipEvent_t a, b; };
 inline double now_ms() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
+// milliseconds between two recorded events; 0 when the query fails (an event that is null or was never recorded)
+inline double elapsed_ms(hipEvent_t a, hipEvent_t b) {
+  float ms = 0;
+  return hipEventElapsedTime(&ms, a, b) == hipSuccess ? (double)ms : 0.0;
+}
 
 
 }  // namespace rsip
@@ -115,6 +121,8 @@ using rsip::DevBuf;
 using rsip::PinBuf;
 using rsip::KernelTime;
 using rsip::GpuGate;
+
+#include "bgzf_launch.h"   // rsing::BgzfLaunch: a batch of BGZF members inflated on the device (needs DevBuf, PinBuf, elapsed_ms)
 
 struct rsi_result {
   std::vector<rsi_call> lists[4];
@@ -152,19 +160,21 @@ struct rsi_ctx {
   char* text_pin[2] = {nullptr, nullptr};    // pinned staging for the file bytes
   size_t text_pin_cap = 0;
   rsi_inflate_stats last_inflate{};          // format and inflate figures of the last text load (rsi_hot_last_inflate_stats)
-  // BAM read on the device (rsi_hot_set_bam_read; ingest.hip): the mode, the chunk size (0: default), the
+  rsing::BgzfLaunch inflate;                 // rsi_hot_inflate_bgzf's launches
+  // BAM read on the device (rsi_hot_set_bam_read; ingest_bam.hip): the mode, the chunk size (0: default), the
   // last load's figures, and the mode's own buffers and stream, made by its first load
   int bam_read = RSI_BAM_READ_HOST;
   size_t bam_chunk = 0;
   rsi_bam_read_stats last_bam_read{};
   struct BamDev {
-    PinBuf cpin[2], tpin[2], wpin;             // compressed payloads, member tables, status words + reports
-    DevBuf cdev[2], tdev[2], wdev, guess, segout, lists, rec, reflen;
+    PinBuf cpin[2], wpin;                      // compressed payloads, the record finder's reports
+    DevBuf cdev[2], wdev, guess, segout, lists, rec, reflen;
+    rsing::BgzfLaunch inflate[2];              // per buffer: its members' inflate
     hipStream_t istream = nullptr;             // uploads and inflates, beside the record kernels on `stream`
     hipEvent_t ev[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};   // per buffer: upload begins, inflate begins, inflate ends, its depth launch is through
     hipEvent_t find[2] = {nullptr, nullptr};   // around the record finder
   } bamdev;
-  // Read-pair annotation on the device (rsi_hot_set_bam_pairs; ingest.hip): nothing of it exists until the first
+  // Read-pair annotation on the device (rsi_hot_set_bam_pairs; ingest_bam.hip): nothing of it exists until the first
   // armed load.  tab: the pair table, five arrays of `cap` entries one behind the other; it belongs to the last armed load
   // (valid) until the next BAM load or debug hook.
   struct Pairs {
@@ -179,7 +189,7 @@ struct rsi_ctx {
     size_t ev_next = 0;
     rsi_pairs_stats stats{};
   } pairs;
-  // `pin` (rsi_hot_set_bam_pin; ingest.hip): nothing of it exists until the first armed load.  tab: lq and coff,
+  // `pin` (rsi_hot_set_bam_pin; ingest_bam.hip): nothing of it exists until the first armed load.  tab: lq and coff,
   // `cap` entries each, one behind the other, entry for entry beside the pair table; pool: the CIGAR words, pool_cap of them.
   struct Pin {
     bool armed = false, valid = false, sampled = false;

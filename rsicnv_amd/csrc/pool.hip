@@ -85,7 +85,7 @@ struct rsi_pool {
       fprintf(stderr, "\n");
     }
     if (R.times) {   // this worker's own rows: nobody else touches them
-      for (const KernelTime& t : ctx->ktimes) { float ms = 0; (void)hipEventElapsedTime(&ms, t.a, t.b); R.ktimes[w].push_back({t.name, ms}); R.kbases[w].push_back(R.n[(size_t)i]); }
+      for (const KernelTime& t : ctx->ktimes) { R.ktimes[w].push_back({t.name, (float)elapsed_ms(t.a, t.b)}); R.kbases[w].push_back(R.n[(size_t)i]); }
       for (const auto& ph : ctx->phases) R.ptimes[w].push_back(ph);
     }
   }

@@ -1,6 +1,6 @@
 // ref_host.h -- the host decisions of the reference reader as pure functions: the .fai line parse, where a base
 // lies in the file, the text a base range needs, the bases a span of text holds whole, the .gzi parse and the members that cover
-// a text range.  No file, no device: ingest.hip's rsi_ref_* calls them, tests/test_ref_host.py checks them through the
+// a text range.  No file, no device: ref.hip's rsi_ref_* calls them, tests/test_ref_host.py checks them through the
 // rsi_ref_debug_* exports on a machine without a GPU.
 #pragma once
 #include <stdint.h>

@@ -164,7 +164,7 @@ int track_slices(rsi_ctx* ctx, int64_t count, int64_t slice, int64_t text_cap, i
   int rc = RSI_OK;
   auto leave = [&](int code, const std::string& msg) { (void)ctx_sync(ctx); return fail(ctx, code, msg); };
   auto hip_failed = [&](hipError_t e, const char* what) { return leave(RSI_ERR_HIP, std::string("track: ") + what + ": " + hipGetErrorString(e)); };
-  auto elapsed = [&](int a, int b) { float ms = 0.f; return hipEventElapsedTime(&ms, w.ev[a], w.ev[b]) == hipSuccess ? (double)ms : 0.0; };
+  auto elapsed = [&](int a, int b) { return elapsed_ms(w.ev[a], w.ev[b]); };
   hipError_t e = hipSuccess;
   int pending = -1, next_buf = 0;   // the pinned buffer whose slice is formatted and on its way, not yet in the sink
   int64_t pending_bytes = 0;
@@ -785,8 +785,7 @@ int64_t rsi_hot_debug_deflate(rsi_ctx* ctx, const uint8_t* text, int64_t len, ui
     HIPCHK(hipMemcpyAsync(w.pin[0], z.packed, (size_t)bytes, hipMemcpyDeviceToHost, st));
     HIPCHK(CTX_SYNC());
     file.append(w.pin[0], (size_t)bytes);
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, w.ev[kEvF1], w.ev[kEvD1]) == hipSuccess) D.t_kernel_ms += ms;
+    D.t_kernel_ms += elapsed_ms(w.ev[kEvF1], w.ev[kEvD1]);
     D.members += members;
     D.stored_members += stored;
     D.text_bytes += nbytes;

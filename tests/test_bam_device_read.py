@@ -241,6 +241,23 @@ def test_errors_leave_the_context_usable(hot, golden, tmp_path):
     still_good()
 
 
+def test_bad_member_message_names_the_block_and_the_file(hot, tmp_path):
+    """A small BAM of several members, the CRC32 of a middle one flipped: the whole message of the device read."""
+    from rsicnv_amd import api
+    refs = [("chrT", 3000)]
+    p = str(tmp_path / "crc_small.bam")
+    bu.write_bam(p, refs, bu.synth_reads(3000, coverage=2.0, seed=5), block=2000)
+    raw = bytearray(open(p, "rb").read())
+    blocks = bgzf_blocks(bytes(raw))
+    assert len(blocks) >= 5                             # header, three members of reads at least, the end-of-file block
+    off, bsize, _ = blocks[2]
+    raw[off + bsize - 8] ^= 0x10
+    open(p, "wb").write(raw)
+    with pytest.raises(api.RsiError) as e:
+        load(hot, p, "chrT", "device", SMALL)
+    assert str(e.value) == f"RSI_ERR_BAD_ARG: BGZF: the block at file offset {off} of {p} is bad: CRC32 mismatch"
+
+
 def test_set_bam_read_arguments(hot):
     from rsicnv_amd import api
     for bad in (2, -1):

@@ -102,6 +102,28 @@ def test_bad_members_are_errors_and_the_context_stays_usable(hot):
         assert hot.inflate_bgzf(good) == good_text, name
 
 
+@pytest.mark.gpu
+@pytest.mark.timeout(120)
+def test_bad_member_messages_name_the_member_and_the_file(hot, tmp_path):
+    """Three members of a few hundred bytes, the CRC32 of the second one flipped: the whole message of the depth reader (the
+    member's offset in the file, the file) and of inflate_bgzf (the member's offset in the caller's bytes)."""
+    from rsicnv_amd import api
+    text = bz.depth_text(400, 7)
+    cut =[0, len(text) // 3, 2 * len(text) // 3, len(text)]
+    members = [bytearray(bz.member(text[a:b])) for a, b in zip(cut, cut[1:])]
+    assert all(200 < len(m) < 1000 for m in members)
+    members[1][-8] ^= 0x10
+    data = b"".join(bytes(m) for m in members) + bz.EOF_BLOCK
+    path = tmp_path / "bad_second.depth.gz"
+    path.write_bytes(data)
+    with pytest.raises(api.RsiError) as e:
+        hot.load_depth_text(str(path), 1000)
+    assert str(e.value) == f"RSI_ERR_BAD_ARG: BGZF: the member at compressed offset {len(members[0])} of {path} is bad: CRC32 mismatch"
+    with pytest.raises(api.RsiError) as e:
+        hot.inflate_bgzf(data)
+    assert str(e.value) == f"RSI_ERR_BAD_ARG: BGZF: the member at compressed offset {len(members[0])} is bad: CRC32 mismatch"
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # the readers: every form of a file gives what its text gives
 # ---------------------------------------------------------------------------------------------------------------------

@@ -854,7 +854,7 @@ int rsi_pool_run(rsi_pool* pool, const rsi_params* p, int nchrom, const void* co
                  const void* const* d_fasta, const int64_t* n, rsi_result** out, int* status,
                  rsi_batch_times* times);
 
-/* ---- Plot files (plotcnv.cpp:245-610; host only) ---------------------------------------------------------
+/* ---- Plot files (plotcnv.cpp:245-610): from an array in host memory ---------------------------------------------------------
  * The gnuplot data (.dat) and script (.gp) file of one call as plot_icnv writes them.  rd: the capped, GC-adjusted per-base
  * depth with the removed N regions back in as zeros (expand_data, loaddata.cpp:140; rsi_plot_expand builds it from
  * rsi_hot_fetch_i32("rd_concat") and rsi_result_noncode); chrom_median: _median of that array (plot::RDmed).  The reference
@@ -863,6 +863,55 @@ int rsi_plot_expand(const int32_t* rdc, int64_t ncompact, const int32_t* regions
 int rsi_plot_write_files(const rsi_call* c, const char* title, const int32_t* rd, int64_t n, double chrom_median, int m,
                          double minmlen, double chklen, const char* format, double gnuplot_version, const char* datfile,
                          const char* gpfile, const char* imgfile);
+
+/* ---- Plot data from the device -----------------------------------------------------------------------------
+ * rsi_plot_write_files in three steps, so that the array never has to leave HBM.  A rsi_plot_batch is a list of calls planned
+ * against an array of n values with the run's m / minmlen / chklen: per call the body, the two pieces of the neighbourhood, the
+ * running mean's band and one query per printed row (which position, which array value, which running-mean window) -- all of
+ * it from the coordinates alone.  A fill then provides a value per query, the exact integer sum of every queried window, the
+ * quartiles and sums of body and neighbourhood and the array's median: rsi_plot_batch_fill_host from host memory (what
+ * rsi_plot_write_files does), rsi_hot_plot_depth from any int32[n] in HBM (not modified), rsi_hot_plot_run from the last
+ * successful run's compacted depth, expanded on the device by its removed regions into a buffer the context keeps.
+ * rsi_plot_batch_write writes call i's two files from a filled batch, with the bytes rsi_plot_write_files gives.
+ * rsi_plot_batch_add returns 0 or what the writer refuses (1 beyond the array, 2 size error, 3 empty body, 4 no band;
+ * rsi_plot_refusal_text): a refused call keeps its index, costs nothing on the device and cannot be written.  _add_span: a
+ * call with cnv_st's defaults (length 0, p1 1).
+ * On the device 20 bytes per query cross PCIe (two indices up, a value and a sum back) and about 100 bytes per call; a list is
+ * processed in batches of as many calls as fit a workspace of 64 MB (at least one), with a number of launches per batch that
+ * does not depend on the calls in it.  Every wait has the library's 60 s deadline.  A batch without plannable calls is RSI_OK and
+ * launches nothing; a context that never plots allocates nothing for it. */
+typedef struct rsi_plot_batch rsi_plot_batch;
+rsi_plot_batch* rsi_plot_batch_new(int64_t n, int m, double minmlen, double chklen);
+void rsi_plot_batch_free(rsi_plot_batch* b);
+int rsi_plot_batch_add(rsi_plot_batch* b, const rsi_call* c);
+int rsi_plot_batch_add_span(rsi_plot_batch* b, int start, int end, int type);
+int rsi_plot_batch_size(const rsi_plot_batch* b);
+int rsi_plot_batch_refusal(const rsi_plot_batch* b, int i);
+const char* rsi_plot_refusal_text(int refusal);
+int64_t rsi_plot_batch_queries(const rsi_plot_batch* b);
+int rsi_plot_batch_fill_host(rsi_plot_batch* b, const int32_t* rd, int64_t n);
+double rsi_plot_batch_chrom_median(const rsi_plot_batch* b);   /* of the last fill; 0 before one */
+/* Two filled batches of the same calls: 0 when every number of every call is the same (values, window sums, quantiles, sums, the
+ * array's median), else 1 + the index of the first call that differs (1 + the number of calls: only the array's median does). */
+int rsi_plot_batch_compare(const rsi_plot_batch* a, const rsi_plot_batch* b);
+int rsi_plot_batch_write(const rsi_plot_batch* b, int i, const char* title, const char* format, double gnuplot_version, const char* datfile,
+                         const char* gpfile, const char* imgfile);
+typedef struct rsi_plot_stats {
+  int64_t launches, batches, tiles;   /* kernel launches of the last call (geno's and the expansion included), its batches, its window-sum tiles */
+  int64_t calls, queries;             /* planned calls filled, and their queries */
+  int64_t bytes_up, bytes_down;       /* what crossed PCIe */
+  int64_t bytes;                      /* device memory the context holds for this step, the expanded array included (0 until the first call) */
+  double ms, expand_ms;               /* wall time of the last call; of its expansion (rsi_hot_plot_run) */
+} rsi_plot_stats;
+int rsi_hot_plot_depth(rsi_ctx* ctx, const void* d_depth, int64_t n, rsi_plot_batch* b);
+int rsi_hot_plot_run(rsi_ctx* ctx, const rsi_result* res, rsi_plot_batch* b);
+int rsi_hot_last_plot_stats(const rsi_ctx* ctx, rsi_plot_stats* out);
+/* Test hook: the HOST array depth[n] becomes the context's input depth (what rsi_hot_loaded_depth returns) and goes through the
+ * same function, with `tile` values per window-sum tile (0: the default, 2048; at most 4096) and a workspace of
+ * workspace_bytes (0: the default). */
+int rsi_hot_debug_plot(rsi_ctx* ctx, const int32_t* depth, int64_t n, int tile, int64_t workspace_bytes, rsi_plot_batch* b);
+/* Test hook: rsi_plot_expand on the device -- compacted values (storage 1: bytes, 4: int32) and (start, end) pairs up, int32[n] back. */
+int rsi_hot_debug_plot_expand(rsi_ctx* ctx, const int32_t* rdc, int64_t ncompact, int storage, const int32_t* regions, int npairs, int32_t* out, int64_t n);
 
 /* The same from host memory (load_data_from_text / load_data_from_bam leave the reference's RD in host memory, loaddata.cpp:473-539):
  * every worker moves its chromosome over its own stream (pinned buffers: asynchronous DMA; pageable ones work, staged by

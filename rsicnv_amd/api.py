@@ -99,6 +99,10 @@ EXPORTS = ["rsi_default_params", "rsi_hot_create", "rsi_hot_destroy", "rsi_hot_l
            "rsi_hot_geno_calls", "rsi_hot_last_geno_stats", "rsi_hot_debug_geno",
            "rsi_hot_loaded_depth", "rsi_hot_depth_summary", "rsi_hot_depth_regions", "rsi_hot_write_window_track", "rsi_hot_write_region_track",
            "rsi_hot_last_depth_stats", "rsi_hot_debug_depth_summary", "rsi_hot_debug_depth_regions", "rsi_hot_debug_region_track",
+           "rsi_plot_batch_new", "rsi_plot_batch_free", "rsi_plot_batch_add", "rsi_plot_batch_add_span", "rsi_plot_batch_size",
+           "rsi_plot_batch_refusal", "rsi_plot_refusal_text", "rsi_plot_batch_queries", "rsi_plot_batch_fill_host",
+           "rsi_plot_batch_chrom_median", "rsi_plot_batch_compare", "rsi_plot_batch_write", "rsi_hot_plot_depth", "rsi_hot_plot_run", "rsi_hot_last_plot_stats",
+           "rsi_hot_debug_plot", "rsi_hot_debug_plot_expand",
            "rsi_ref_debug_set_chunks", "rsi_ref_debug_fai_line", "rsi_ref_debug_ranges", "rsi_ref_debug_gzi", "rsi_ref_debug_cover"]
 
 
@@ -204,6 +208,11 @@ class RsiPinStats(C.Structure):
 class RsiGenoStats(C.Structure):
     _fields_ = [("launches", C.c_int64), ("jobs", C.c_int64), ("tiles", C.c_int64), ("passes", C.c_int64), ("bytes", C.c_int64),
                 ("ms", C.c_double)]
+
+
+class RsiPlotStats(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("launches", "batches", "tiles", "calls", "queries", "bytes_up", "bytes_down", "bytes")] + \
+               [("ms", C.c_double), ("expand_ms", C.c_double)]
 
 
 class RsiDepthStats(C.Structure):
@@ -371,6 +380,28 @@ def load_library():
     L.rsi_hot_geno_calls.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.rsi_hot_last_geno_stats.argtypes = [C.c_void_p, C.POINTER(RsiGenoStats)]
     L.rsi_hot_debug_geno.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p]
+    L.rsi_plot_batch_new.argtypes = [C.c_int64, C.c_int, C.c_double, C.c_double]
+    L.rsi_plot_batch_new.restype = C.c_void_p
+    L.rsi_plot_batch_free.argtypes = [C.c_void_p]
+    L.rsi_plot_batch_free.restype = None
+    L.rsi_plot_batch_add.argtypes = [C.c_void_p, C.POINTER(RsiCall)]
+    L.rsi_plot_batch_add_span.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+    L.rsi_plot_batch_size.argtypes = [C.c_void_p]
+    L.rsi_plot_batch_refusal.argtypes = [C.c_void_p, C.c_int]
+    L.rsi_plot_refusal_text.argtypes = [C.c_int]
+    L.rsi_plot_refusal_text.restype = C.c_char_p
+    L.rsi_plot_batch_queries.argtypes = [C.c_void_p]
+    L.rsi_plot_batch_queries.restype = C.c_int64
+    L.rsi_plot_batch_fill_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    L.rsi_plot_batch_chrom_median.argtypes = [C.c_void_p]
+    L.rsi_plot_batch_chrom_median.restype = C.c_double
+    L.rsi_plot_batch_compare.argtypes = [C.c_void_p, C.c_void_p]
+    L.rsi_plot_batch_write.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_double, C.c_char_p, C.c_char_p, C.c_char_p]
+    L.rsi_hot_plot_depth.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.rsi_hot_plot_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rsi_hot_last_plot_stats.argtypes = [C.c_void_p, C.POINTER(RsiPlotStats)]
+    L.rsi_hot_debug_plot.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p]
+    L.rsi_hot_debug_plot_expand.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64]
     L.rsi_hot_loaded_depth.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     L.rsi_hot_depth_summary.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int]
     L.rsi_hot_depth_regions.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -1084,6 +1115,37 @@ class RsiHot:
         self._check(self.lib.rsi_hot_last_geno_stats(self.ctx, C.byref(st)))
         return {k: getattr(st, k) for k, _ in RsiGenoStats._fields_}
 
+    # ---- plot data: the numbers of planned figures from an array in HBM ----
+    def plot_depth(self, d_depth_ptr, n, batch):
+        """Fills a PlotBatch from int32[n] in HBM (rsi_hot_plot_depth); the batch can then write its files."""
+        self._check(self.lib.rsi_hot_plot_depth(self.ctx, C.c_void_p(d_depth_ptr), int(n), batch._h))
+
+    def plot_run(self, res, batch):
+        """Fills a PlotBatch from the depth the run of `res` left in this context, expanded on the device (rsi_hot_plot_run)."""
+        self._check(self.lib.rsi_hot_plot_run(self.ctx, res._h, batch._h))
+
+    def debug_plot(self, depth, batch, tile=0, workspace_bytes=0):
+        """plot_depth of a host array (test hook, rsi_hot_debug_plot); tile: values per window-sum tile, workspace_bytes: what a
+        batch of calls may take on the device (0: the defaults)."""
+        d = np.ascontiguousarray(depth, dtype=np.int32)
+        self._check(self.lib.rsi_hot_debug_plot(self.ctx, d.ctypes.data, d.size, int(tile), int(workspace_bytes), batch._h))
+
+    def debug_plot_expand(self, rdc, regions, n, storage=4):
+        """rsi_plot_expand on the device (test hook, rsi_hot_debug_plot_expand): compacted values and (start, end) pairs -> int32[n]."""
+        v = np.ascontiguousarray(rdc, dtype=np.int32)
+        r = np.ascontiguousarray(regions, dtype=np.int32).reshape(-1)
+        out = np.zeros(int(n), dtype=np.int32)
+        self._check(self.lib.rsi_hot_debug_plot_expand(self.ctx, v.ctypes.data if v.size else None, v.size, int(storage),
+                                                       r.ctypes.data if r.size else None, r.size // 2, out.ctypes.data, int(n)))
+        return out
+
+    def plot_stats(self):
+        """launches, batches, tiles, calls, queries, bytes up / down, bytes held, ms and expand_ms of the context's last plot call
+        (rsi_hot_last_plot_stats)."""
+        st = RsiPlotStats()
+        self._check(self.lib.rsi_hot_last_plot_stats(self.ctx, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in RsiPlotStats._fields_}
+
     # ---- `depth` (DESIGN.md 6o): a per-base depth array in HBM summed up without a run ----
     def loaded_depth(self):
         """(device pointer, n) of the array the last load_depth_text / load_depth_bam (or a depth hook) left in the context's input
@@ -1485,6 +1547,63 @@ class RsiPool:
     def phase_table(self):
         t = self.times
         return {t.phase_name[i].decode(): t.phase_ms[i] for i in range(t.nphases)}
+
+
+class PlotBatch:
+    """Calls planned as gnuplot figures against an array of n values (rsi_plot_batch_*): add() plans a call and
+    returns 0 or what the writer refuses; a fill -- fill_host(array), RsiHot.plot_depth / plot_run / debug_plot -- provides the
+    numbers; write(i, ...) then leaves call i's .dat and .gp files, byte for byte those of rsi_plot_write_files."""
+
+    def __init__(self, n, m, minmlen=2.0, chklen=2.0):
+        self.lib = load_library()
+        self._h = self.lib.rsi_plot_batch_new(int(n), int(m), float(minmlen), float(chklen))
+        if not self._h:
+            raise RsiError(-2, "plot batch: bad array length or bin size")
+
+    def close(self):
+        if self._h:
+            self.lib.rsi_plot_batch_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def add(self, start, end, type_=0, call=None):
+        """Plans one call: start / end as in the output rows; call: an RsiCall whose length / type / p1 the data file's first line
+        prints (default: cnv_st's, length 0 and p1 1)."""
+        if call is not None:
+            return self.lib.rsi_plot_batch_add(self._h, C.byref(call))
+        return self.lib.rsi_plot_batch_add_span(self._h, int(start), int(end), int(type_))
+
+    def __len__(self):
+        return self.lib.rsi_plot_batch_size(self._h)
+
+    def refusal(self, i):
+        return self.lib.rsi_plot_batch_refusal(self._h, int(i))
+
+    def refusal_text(self, i):
+        return self.lib.rsi_plot_refusal_text(self.refusal(i)).decode()
+
+    def queries(self):
+        return self.lib.rsi_plot_batch_queries(self._h)
+
+    def fill_host(self, depth):
+        d = np.ascontiguousarray(depth, dtype=np.int32)
+        rc = self.lib.rsi_plot_batch_fill_host(self._h, d.ctypes.data, d.size)
+        if rc != RSI_OK:
+            raise RsiError(rc, "plot batch: the array is not the length the batch was planned for")
+
+    def chrom_median(self):
+        return self.lib.rsi_plot_batch_chrom_median(self._h)
+
+    def compare(self, other):
+        """0 when both filled batches hold the same numbers for every call, else 1 + the first call that differs."""
+        return self.lib.rsi_plot_batch_compare(self._h, other._h)
+
+    def write(self, i, title, datfile, gpfile, imgfile, format="ps", gnuplot_version=5.0):
+        """Call i's files from the last fill; False for a refused call (no file is written)."""
+        return self.lib.rsi_plot_batch_write(self._h, int(i), title.encode(), format.encode(), float(gnuplot_version), os.fsencode(datfile),
+                                             os.fsencode(gpfile), os.fsencode(imgfile)) == RSI_OK
 
 
 class GenomeText:

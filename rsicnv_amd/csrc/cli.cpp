@@ -7,7 +7,9 @@
 // a BAM (run_cnvlist); `rsicnv geno` runs the chromosomes such a list names as rsi does and appends every region's copy
 // number, reduced on the device from the depth the run leaves there (geno_chromosome); `rsicnv depth` loads every
 // chromosome as rsi does and writes its coverage summary, distribution, per-base track and window / region means from HBM, with
-// no run (run_depth); plot is outside the accelerated path and says so.  A whole-genome file with several depth columns (a cohort, RNAME POS D1 ... DK) is
+// no run (run_depth); `rsicnv view` draws the figures of such a list from the raw depth in HBM (run_view), and
+// -plots device takes the numbers of rsi's own figures from there too; `rsicnv plot` is not yet an alias of view and says that it is
+// outside the accelerated path.  A whole-genome file with several depth columns (a cohort, RNAME POS D1 ... DK) is
 // called sample by sample with -samples all|LIST: one OUT.k per selected column k.  A bedGraph depth file (RNAME START END
 // DEPTH: mosdepth, bedtools genomecov -bg / -bga) runs as the per-base file it stands for, whole or one chromosome (-c).
 // -track FILE saves the depth every chromosome was called from (raw, or GC-adjusted with -trackdepth gc) as one bedGraph file,
@@ -56,6 +58,7 @@ struct Options {
   int gpus = 0;      // -gpus N: chromosomes spread over N devices, several in flight per device (0: one context, one at a time)
   int workers = 4;   // -workers W: chromosomes in flight per device with -gpus, and on -gpu for a whole-genome depth file
   bool saverd = false, plot = true, plotfiles = false;
+  std::string plots = "host";   // -plots device|host: the figures' numbers from the depth in HBM (rsi_hot_plot_run), or from a host copy of it
   std::string samples;   // -samples all|k1,k2,...: the depth columns of a cohort file to call (without: the first one, as always)
   bool samples_given = false, chr_given = false;
   std::string dformat;   // -dformat depth|bedgraph: the -d file's format (without: from its name, is_bedgraph_name)
@@ -207,6 +210,16 @@ int usage() {
             << "             The files are laid out as mosdepth's; the depth is this program's pileup (M and = bases of base quality\n"
             << "             -Q or more), not mosdepth's read spans.  Means and shares have two decimals, rounded half up.\n"
             << "             -d PREFIX.per-base.bed.gz reads the per-base file back\n"
+            << "\n5. the figures of a list of CNVs that exists already (this program's rows, pin's output, a published set)\n\n"
+            << "   rsicnv view -f REFFILE (-d RDFILE -c RNAME | -b BAMFILE [-c RNAME]) -v CNVFILE [-p FOLDER] [-m INT] [-plotfiles]\n"
+            << "             what the reference's plot does: raw depth, no GC adjustment, no cap, nothing removed (-q -Q -bamread -gpu as for\n"
+            << "             rsi; -f is needed with -d only, for the .fai).  Every chromosome the list names is loaded once, the numbers of\n"
+            << "             its lines' figures come from the GPU, and FOLDER/rsi_RNAME_START_END_TYPE.ps is drawn by gnuplot (-plotfiles:\n"
+            << "             the .dat and .gp files are written and kept, gnuplot or not).  Names match with or without chr; files and\n"
+            << "             titles carry the input's name.  A line on a chromosome the input lacks, or whose call the writer refuses, gets\n"
+            << "             a line in FOLDER/view.log and no file.  A BAM's figures are those of its depth file (the reference's pile up\n"
+            << "             where windows overlap, and lack the chromosome's median line), and -p names the folder with -b too.\n"
+            << "             rsicnv plot is not this command yet: it still answers that it is not part of the accelerated path\n"
             << "\nOptions:\n"
             << "   -m   INT  bin size, default=101\n"
             << "   -q   INT  minimum mapping quality, default=0\n"
@@ -218,6 +231,10 @@ int usage() {
             << "   -NB       only use negative binomial transformation (default)\n"
             << "   -o   STR  output file, default=rsiout.txt \n"
             << "   -np       do not plot CNV\n"
+            << "   -p   STR  folder of the plots, default=cnv_plots\n"
+            << "   -plotfiles  write and keep every call's gnuplot data and script file, with or without a gnuplot\n"
+            << "   -plots device|host  the numbers of the plots from the depth on the GPU (about 20 bytes per plotted point cross PCIe), or\n"
+            << "             from a host copy of the whole chromosome's depth (default: host); the files are the same\n"
             << "   -gpu INT  HIP device to run on, default=0\n"
             << "   -gpus INT spread the chromosomes of a BAM over INT devices (longest first), several in flight per\n"
             << "             device (-workers INT, default=4); rows are written in BAM header order all the same\n"
@@ -296,7 +313,7 @@ void parse(int argc, char** argv, Options& o) {
   size_t i = 1;
   if (a[1][0] != '-') {
     o.function = a[1];
-    if (o.function != "rsi" && o.function != "plot" && o.function != "stat" && o.function != "pin" && o.function != "geno" && o.function != "depth") {
+    if (o.function != "rsi" && o.function != "plot" && o.function != "stat" && o.function != "pin" && o.function != "geno" && o.function != "depth" && o.function != "view") {
       std::cerr << "no such function " << o.function << std::endl;
       exit(usage());
     }
@@ -319,6 +336,7 @@ void parse(int argc, char** argv, Options& o) {
     else if (s == "-p") { o.plotfolder = need(i); ++i; }
     else if (s == "-np") o.plot = false;
     else if (s == "-plotfiles") o.plotfiles = true;
+    else if (s == "-plots") { o.plots = need(i); ++i; }
     else if (s == "-threshold") { o.P.threshold = atof(need(i).c_str()); ++i; }
     else if (s == "-e") { o.P.epsilon = atof(need(i).c_str()); ++i; }
     else if (s == "-cap") { o.P.cap = atof(need(i).c_str()); ++i; }
@@ -354,7 +372,7 @@ void parse(int argc, char** argv, Options& o) {
     else { std::cerr << "unknown option " << s << std::endl; exit(usage()); }
   }
   if (o.rdfile.empty() && o.bamfile.empty()) { std::cerr << "need input file " << std::endl; exit(usage()); }
-  if (o.reffile.empty() && (o.function == "rsi" || o.function == "geno" || (o.function == "depth" && o.bamfile.empty()))) { std::cerr << "need reference file " << std::endl; exit(usage()); }
+  if (o.reffile.empty() && (o.function == "rsi" || o.function == "geno" || ((o.function == "depth" || o.function == "view") && o.bamfile.empty()))) { std::cerr << "need reference file " << std::endl; exit(usage()); }
   if (o.outfile == o.bamfile || o.outfile == o.rdfile) { std::cerr << "output file is same as input file " << std::endl; exit(usage()); }
   if (!o.rdfile.empty() && o.chr.empty()) { std::cerr << "readdepth file and chromosome must be specified together" << std::endl; exit(usage()); }
   if ((o.P.m % 2) != 1) { o.P.m += 1; std::cerr << "m is changed to " << o.P.m << std::endl; }   // rsi.cpp:2061-2064
@@ -463,6 +481,37 @@ bool select_chromosomes(const Options& o, std::vector<std::string>& todo, std::v
 
 void report_chromosome(rsi_ctx* ctx, const Options& o, const std::string& chr, rsi_result* res, const rsi_text_stats* ts,
                        const rsi_bam_stats* bs, double t_fasta, double t_path, std::ostringstream& info, ChromOutput& co);
+
+// What the plot step of rsi and `view` share around the files.  gnuplot_version() (plotcnv.cpp:51-65), once per process: what
+// `gnuplot -V` reports, -1 without a gnuplot.
+double gnuplot_found() {
+  static const double gv = [] {
+    double v = -1.0;
+    if (FILE* pp = popen("gnuplot -V 2>/dev/null | cut -d' ' -f2", "r")) { char b[64] = {0}; if (fgets(b, sizeof(b), pp) && atof(b) > 0) v = atof(b); pclose(pp); }
+    return v;
+  }();
+  return gv;
+}
+// a call's script through gnuplot, its two files deleted, as the reference does
+void draw_figure(const std::string& dat, const std::string& gp, const std::string& img, std::vector<std::string>& psfiles) {
+  (void)!system(("gnuplot < " + gp).c_str());
+  remove(dat.c_str());
+  remove(gp.c_str());
+  psfiles.push_back(img);
+}
+// plot_cnv's last step (plotcnv.cpp:665-677): with ImageMagick at hand every figure also becomes a .png
+void convert_figures(const std::vector<std::string>& psfiles, std::ostream& info) {
+  static const bool have_convert = [] {
+    bool yes = false;
+    if (FILE* pp = popen("convert -version 2>/dev/null | grep Image", "r")) { char b[256]; while (fgets(b, sizeof(b), pp)) if (strstr(b, "ImageMagick")) yes = true; pclose(pp); }
+    return yes;
+  }();
+  if (have_convert) for (const std::string& ps : psfiles) {
+    info << "converting: " << ps << "\n";
+    (void)!system(("convert -limit thread 1 -limit area 256MB -limit disk 512MB -density 72 -rotate 90 -background white -render -antialias -flatten " +
+                   ps + " " + ps.substr(0, ps.size() - 3) + ".png").c_str());
+  }
+}
 void geno_chromosome(rsi_ctx* ctx, const Options& o, const std::string& chr, rsi_result* res, std::ostringstream& info, ChromOutput& co);
 
 // -x FILE: the BED file's intervals on `chr` (n bases) arm the context for the run that follows (the mask is spent by that run);
@@ -672,23 +721,35 @@ void report_chromosome(rsi_ctx* ctx, const Options& o, const std::string& chr, r
   // ---- plots (rsi.cpp:2213-2216: expand_data, plot_cnv): the data / script files of every written call, piped through gnuplot
   // and deleted, as the reference does -- and like the reference only when there is a gnuplot.  -plotfiles (not a reference
   // flag) writes and keeps the files without one. ----
-  // gnuplot_version() (plotcnv.cpp:51-65) once per process, not once per chromosome
-  static const double gv = [] {
-    double v = -1.0;
-    if (FILE* pp = popen("gnuplot -V 2>/dev/null | cut -d' ' -f2", "r")) { char b[64] = {0}; if (fgets(b, sizeof(b), pp) && atof(b) > 0) v = atof(b); pclose(pp); }
-    return v;
-  }();
+  const double gv = gnuplot_found();
   if (o.plot && rsi_result_ncalls(res, 0) > 0 && gv <= 0 && !o.plotfiles) info << "gnuplot not found\n";
   if (o.plot && rsi_result_ncalls(res, 0) > 0 && (gv > 0 || o.plotfiles)) {
     const int64_t nc = S->n_compact, nfull = S->n;
-    std::vector<int32_t> rdc((size_t)nc), full((size_t)nfull), pairs((size_t)S->n_noncode * 2 + 2);
-    const int np = rsi_result_noncode(res, pairs.data(), S->n_noncode);
-    if (rsi_hot_fetch_i32(ctx, "rd_concat", rdc.data(), nc) == nc && rsi_plot_expand(rdc.data(), nc, pairs.data(), np, full.data(), nfull) == RSI_OK) {
-      (void)!system(("mkdir -p " + o.plotfolder).c_str());
+    const bool on_device = o.plots == "device";   // -plots device: the figures' numbers come from HBM (rsi_hot_plot_run)
+    std::vector<int32_t> full;
+    double med = 0;
+    std::shared_ptr<rsi_plot_batch> batch;
+    const rsi_call* calls = rsi_result_calls(res, 0);
+    bool have = false;
+    if (on_device) {
+      batch.reset(rsi_plot_batch_new(nfull, o.P.m, o.P.minmlen, o.P.chklen), rsi_plot_batch_free);
+      for (int i = 0; batch && i < rsi_result_ncalls(res, 0); ++i) (void)rsi_plot_batch_add(batch.get(), &calls[i]);
+      have = batch && rsi_hot_plot_run(ctx, res, batch.get()) == RSI_OK;
+      rsi_plot_stats ps;
+      if (have && rsi_hot_last_plot_stats(ctx, &ps) == RSI_OK)
+        info << "#plots: " << chr << ": " << ps.calls << " calls, " << ps.queries << " points, " << ps.batches << " batches, " << ps.launches << " launches, "
+             << ps.bytes_up << " bytes up, " << ps.bytes_down << " bytes down, " << ps.ms << " ms (expansion " << ps.expand_ms << " ms)\n";
+    } else {
+      std::vector<int32_t> rdc((size_t)nc), pairs((size_t)S->n_noncode * 2 + 2);
+      full.resize((size_t)nfull);
+      const int np = rsi_result_noncode(res, pairs.data(), S->n_noncode);
+      have = rsi_hot_fetch_i32(ctx, "rd_concat", rdc.data(), nc) == nc && rsi_plot_expand(rdc.data(), nc, pairs.data(), np, full.data(), nfull) == RSI_OK;
       // plot::RDmed = _median over the expanded array (plotcnv.cpp:625): zeros of the N regions included
-      const double med = rsih::grid_quantiles<int>(full.data(), (size_t)nfull).med;   // partition_stat_tp's walk, its degenerate case included
+      if (have) med = rsih::grid_quantiles<int>(full.data(), (size_t)nfull).med;   // partition_stat_tp's walk, its degenerate case included
+    }
+    if (have) {
+      (void)!system(("mkdir -p " + o.plotfolder).c_str());
       if (gv <= 0) info << "plot data and scripts are left in " << o.plotfolder << "\n";
-      const rsi_call* calls = rsi_result_calls(res, 0);
       static const char* kT[3] = {"DEL", "DUP", "UNKNOWN"};
       std::vector<std::string> psfiles;
       for (int i = 0; i < rsi_result_ncalls(res, 0); ++i) {
@@ -698,24 +759,17 @@ void report_chromosome(rsi_ctx* ctx, const Options& o, const std::string& chr, r
         title << chr << ":" << c.start << "-" << c.end << " " << c.end - c.start + 1 << " " << kT[c.type < 0 || c.type > 2 ? 2 : c.type];
         const std::string dat = base.str() + ".dat", gp = base.str() + ".gp", img = base.str() + ".ps";
         info << "plotting: " << title.str() << "\n";
-        if (rsi_plot_write_files(&c, title.str().c_str(), full.data(), nfull, med, o.P.m, o.P.minmlen, o.P.chklen, "ps", gv > 0 ? gv : 5.0, dat.c_str(), gp.c_str(), img.c_str()) != RSI_OK) {
+        const int rc = on_device ? rsi_plot_batch_write(batch.get(), i, title.str().c_str(), "ps", gv > 0 ? gv : 5.0, dat.c_str(), gp.c_str(), img.c_str())
+                                 : rsi_plot_write_files(&c, title.str().c_str(), full.data(), nfull, med, o.P.m, o.P.minmlen, o.P.chklen, "ps", gv > 0 ? gv : 5.0, dat.c_str(), gp.c_str(), img.c_str());
+        if (rc != RSI_OK) {
           info << "CNV exceeds reference length\n";
           continue;
         }
-        if (gv > 0) { (void)!system(("gnuplot < " + gp).c_str()); remove(dat.c_str()); remove(gp.c_str()); psfiles.push_back(img); }
+        if (gv > 0) draw_figure(dat, gp, img, psfiles);
       }
-      // plot_cnv's last step (plotcnv.cpp:665-677): with ImageMagick at hand every figure also becomes a .png
-      static const bool have_convert = [] {
-        bool yes = false;
-        if (FILE* pp = popen("convert -version 2>/dev/null | grep Image", "r")) { char b[256]; while (fgets(b, sizeof(b), pp)) if (strstr(b, "ImageMagick")) yes = true; pclose(pp); }
-        return yes;
-      }();
-      if (have_convert) for (const std::string& ps : psfiles) {
-        info << "converting: " << ps << "\n";
-        (void)!system(("convert -limit thread 1 -limit area 256MB -limit disk 512MB -density 72 -rotate 90 -background white -render -antialias -flatten " +
-                       ps + " " + ps.substr(0, ps.size() - 3) + ".png").c_str());
-      }
-    } else info << "plots skipped: the per-base depth could not be fetched\n";
+      convert_figures(psfiles, info);
+    } else if (on_device) info << "plots skipped: " << rsi_hot_last_error(ctx) << "\n";
+    else info << "plots skipped: the per-base depth could not be fetched\n";
   }
   co.log = info.str();
   rsi_result_free(res);
@@ -1413,6 +1467,129 @@ int run_depth(const Options& o, int argc, char** argv) {
   return ok ? 0 : 1;
 }
 
+// `rsicnv view`: the figures of an existing CNV list, what the reference's `plot` does (rsi.cpp:2151-2185) -- raw depth,
+// no GC adjustment, no cap, nothing removed.  Every chromosome the list names is loaded once (a depth file's, or a BAM's pileup), its
+// lines are planned against its length, filled from HBM (rsi_hot_plot_depth) and written as rsi's plot step writes a call's.
+int run_view(const Options& o_in, int argc, char** argv) {
+  auto refuse = [](const std::string& why) { std::cerr << "rsicnv view: " << why << std::endl; return 1; };
+  // refused where it cannot work, before any output
+  if (o_in.cnvfile.empty()) return refuse("need a list of CNVs (-v CNVFILE)");
+  if (o_in.gpus > 1) return refuse("-gpus: a CNV list runs on one device (-gpu INT picks it)");
+  if (o_in.samples_given) return refuse("-samples: one sample at a time");
+  const bool from_bam = !o_in.bamfile.empty();
+  if (!from_bam && !o_in.chr_given) return refuse("-d RDFILE needs -c RNAME (a whole-genome depth file is not read)");
+  if (!o_in.bamread.empty() && o_in.bamread != "device" && o_in.bamread != "host") return refuse("-bamread " + o_in.bamread + ": expected device or host");
+  if (!o_in.bamread.empty() && !from_bam) return refuse("-bamread device|host: there is no BAM file to read (-b BAMFILE)");
+  std::vector<rsipinh::CnvLine> lines;
+  if (!rsipinh::read_cnvlist(o_in.cnvfile, {}, lines, std::cerr)) return 0;   // as stat / pin: the reference says so and exits with 0
+  Options o = o_in;
+  o.geno = &lines;   // select_chromosomes: of a BAM's header, the chromosomes the list names
+  std::vector<std::string> fnames;
+  std::vector<int64_t> flens;
+  size_t fai_one = 0;
+  if (!from_bam) {   // read_fasta's rule: the first sequence named RNAME or chrRNAME
+    if (!read_fai(o.reffile, fnames, flens)) return 1;
+    while (fai_one < fnames.size() && fnames[fai_one] != o.chr && fnames[fai_one] != "chr" + o.chr) ++fai_one;
+    if (fai_one == fnames.size()) return refuse(o.chr + " not found in fai index");
+  }
+  const double gv = gnuplot_found();
+  if (gv <= 0 && !o.plotfiles) { std::cerr << "gnuplot not found" << std::endl; return 0; }   // plot_cnv returns there, and the reference exits with 0
+
+  (void)!system(("mkdir -p " + o.plotfolder).c_str());
+  std::ofstream log((o.plotfolder + "/view.log").c_str());
+  if (!log) return refuse("cannot write into " + o.plotfolder);
+  log << "#command:   "; for (int i = 0; i < argc; ++i) log << argv[i] << " ";
+  log << "\n";
+  auto say = [&](const std::string& s) { std::cerr << s; log << s; };
+  int st = 0;
+  rsi_ctx* ctx = rsi_hot_create(o.device, &st);
+  if (!ctx) { say("rsicnv view: no context on device " + std::to_string(o.device) + ": " + rsi_hot_last_error(nullptr) + "\n"); return 1; }
+  struct Destroy { rsi_ctx* c; ~Destroy() { rsi_hot_destroy(c); } } destroy{ctx};
+  if (from_bam && !o.bamread.empty() && rsi_hot_set_bam_read(ctx, o.bamread == "device" ? RSI_BAM_READ_DEVICE : RSI_BAM_READ_HOST, 0) != RSI_OK) {
+    say(std::string("rsicnv view: ") + rsi_hot_last_error(ctx) + "\n");
+    return 1;
+  }
+  if (gv <= 0) say("plot data and scripts are left in " + o.plotfolder + "\n");
+
+  bool ok = true;
+  std::vector<std::string> seen, psfiles;
+  // one chromosome, its depth in HBM: its lines planned, filled and written
+  auto chromosome = [&](const std::string& chr, const void* d_depth, int64_t n) {
+    seen.push_back(chr);
+    std::shared_ptr<rsi_plot_batch> batch(rsi_plot_batch_new(n, o.P.m, o.P.minmlen, o.P.chklen), rsi_plot_batch_free);
+    if (!batch) { say("#view: " + chr + ": an array of " + std::to_string(n) + " values cannot be planned\n"); ok = false; return; }
+    std::vector<size_t> mine;
+    for (size_t i = 0; i < lines.size(); ++i) {
+      if (!same_chrom(lines[i].cell[0], chr)) continue;
+      mine.push_back(i);
+      (void)rsi_plot_batch_add_span(batch.get(), lines[i].start, lines[i].end, lines[i].type);
+    }
+    if (rsi_hot_plot_depth(ctx, d_depth, n, batch.get()) != RSI_OK) { say("#view: " + chr + ": " + rsi_hot_last_error(ctx) + ": no figures for it\n"); ok = false; return; }
+    rsi_plot_stats ps;
+    (void)rsi_hot_last_plot_stats(ctx, &ps);
+    int written = 0;
+    for (size_t k = 0; k < mine.size(); ++k) {
+      const rsipinh::CnvLine& l = lines[mine[k]];
+      const std::string what = chr + ":" + l.cell[1] + "-" + l.cell[2] + " " + l.cell[3];
+      if (const int r = rsi_plot_batch_refusal(batch.get(), (int)k)) { say("#view: " + what + ": " + rsi_plot_refusal_text(r) + ": no figure\n"); continue; }
+      const std::string base = o.plotfolder + "/rsi_" + chr + "_" + l.cell[1] + "_" + l.cell[2] + "_" + l.cell[3];
+      const std::string title = chr + ":" + l.cell[1] + "-" + l.cell[2] + " " + std::to_string(abs(l.end - l.start) + 1) + " " + l.cell[3];
+      const std::string dat = base + ".dat", gp = base + ".gp", img = base + ".ps";
+      say("plotting: " + title + "\n");
+      if (rsi_plot_batch_write(batch.get(), (int)k, title.c_str(), "ps", gv > 0 ? gv : 5.0, dat.c_str(), gp.c_str(), img.c_str()) != RSI_OK) {
+        say("#view: " + what + ": cannot write " + dat + "\n");
+        ok = false;
+        continue;
+      }
+      ++written;
+      if (gv > 0) draw_figure(dat, gp, img, psfiles);
+    }
+    std::ostringstream line;
+    line << "#plots: " << chr << ": " << mine.size() << " lines, " << written << " figures, " << ps.queries << " points, " << ps.batches << " batches, "
+         << ps.launches << " launches, " << ps.bytes_up << " bytes up, " << ps.bytes_down << " bytes down, " << ps.ms << " ms\n";
+    say(line.str());
+  };
+
+  if (from_bam) {
+    std::vector<std::string> todo;
+    std::vector<int64_t> todo_len;
+    if (!select_chromosomes(o, todo, todo_len, log)) return 1;
+    for (const std::string& chr : todo) {
+      if (!geno_names(lines, chr)) continue;   // -c RNAME that the list does not name
+      rsi_bam_stats bs;
+      memset(&bs, 0, sizeof(bs));
+      const void* d = nullptr;
+      int64_t n = 0;
+      if (rsi_hot_load_depth_bam(ctx, o.bamfile.c_str(), chr.c_str(), o.minq, o.min_baseQ, &bs) != RSI_OK || rsi_hot_loaded_depth(ctx, &d, &n) != RSI_OK) {
+        say("#view: " + chr + ": " + rsi_hot_last_error(ctx) + "\n");
+        ok = false;
+        continue;
+      }
+      if (o.bamread == "device") say(bam_read_line(ctx));
+      chromosome(chr, d, n);
+    }
+  } else if (geno_names(lines, fnames[fai_one])) {
+    rsi_text_stats ts;
+    const void* d = nullptr;
+    int64_t n = 0;
+    if (rsi_hot_load_depth_text(ctx, o.rdfile.c_str(), flens[fai_one], &ts) != RSI_OK || rsi_hot_loaded_depth(ctx, &d, &n) != RSI_OK) {
+      say("#view: " + o.chr + ": " + rsi_hot_last_error(ctx) + "\n");
+      ok = false;
+    } else {
+      rsi_inflate_stats is;
+      if (rsi_hot_last_inflate_stats(ctx, &is) == RSI_OK) say(inflate_line(is));
+      chromosome(fnames[fai_one], d, n);
+    }
+  }
+  convert_figures(psfiles, log);
+  for (const rsipinh::CnvLine& l : lines) {
+    bool met = false;
+    for (const std::string& c : seen) met = met || same_chrom(l.cell[0], c);
+    if (!met) say("#view: " + l.cell[0] + " is not in the input: no figure for " + l.cell[0] + ":" + l.cell[1] + "-" + l.cell[2] + "\n");
+  }
+  return ok ? 0 : 1;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -1424,6 +1601,8 @@ int main(int argc, char** argv) {
   parse(argc, argv, o);
   if (o.function == "stat" || o.function == "pin") return run_cnvlist(o);
   if (o.function == "depth") return run_depth(o, argc, argv);
+  if (o.function == "view") return run_view(o, argc, argv);
+  if (o.plots != "host" && o.plots != "device") { std::cerr << "rsicnv: -plots " << o.plots << ": expected device or host" << std::endl; return 1; }
   std::vector<rsipinh::CnvLine> geno_lines;
   if (o.function == "geno") {   // refused where it cannot work, before any output
     if (o.cnvfile.empty()) { std::cerr << "rsicnv geno: need a list of regions (-v CNVFILE)" << std::endl; return 1; }

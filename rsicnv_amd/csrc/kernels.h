@@ -635,6 +635,31 @@ void launch_geno_plan32(GenoState* st, int njobs, GenoOut* out, unsigned int* ma
 void launch_geno_hist32(const int32_t* d, const GenoTile* tiles, int ntiles, const GenoState* st, unsigned int* hist, hipStream_t stream);
 void launch_geno_scan32(GenoState* st, int njobs, unsigned int* hist, GenoOut* out, hipStream_t stream);
 
+// ---- plot data: the running mean's window sums and the queried values of planned figures (kernels_plot.hip) ----
+// A job is one figure's neighbourhood: la values from a0 on, then lb values from b0 on, all inside the array (the caller checks
+// that), cut into tiles of `tile` values (1 <= tile <= kPlotMaxTile) of that concatenation; tile0 is the job's first tile in the
+// batch's numbering (ascending over the jobs, every job has at least one value).  Its queries start at q0: nq0 rows of block 0, nq1
+// of block 1, nq2 of block 2, the two of block 3.  qref[q]: neighbourhood index of the window's centre before the clamp, in
+// [0, la + lb), or -1 for no window; inside blocks 0 and 2 it is never -1 and never descends.  Per batch: launch_plot_tile_sums
+// (a workgroup per tile: tsum[tile]), launch_plot_tile_scan (a workgroup per job: tsum becomes the sum in front of each tile),
+// launch_plot_window_ends (a workgroup per tile scans its values in LDS and writes the prefix sum at every window end that falls
+// into the tile: ends[2 q] at the window's last value, ends[2 q + 1] at the value in front of its first; `ends` all zero before),
+// launch_plot_gather (a thread per query: value[q] = d[qdepth[q]] or 0 for -1, wsum[q] = ends[2 q] - ends[2 q + 1]).  The kernel
+// boundary is the only synchronisation between workgroups; all sums are exact in 64 bits.
+struct PlotJob { int32_t a0, la, b0, lb, band, nq0, nq1, nq2; long long q0; int32_t tile0, pad; };
+constexpr int kPlotThreads = 256, kPlotMaxTile = 4096, kPlotDefaultTile = 2048;
+void launch_plot_tile_sums(const int32_t* d, const PlotJob* jobs, int njobs, int ntiles, int tile, long long* tsum, hipStream_t stream);
+void launch_plot_tile_scan(const PlotJob* jobs, int njobs, int tile, long long* tsum, hipStream_t stream);
+void launch_plot_window_ends(const int32_t* d, const PlotJob* jobs, int njobs, int ntiles, int tile, const long long* tsum, const int32_t* qref,
+                             long long* ends, hipStream_t stream);
+void launch_plot_gather(const int32_t* d, const int32_t* qdepth, const int32_t* qref, const long long* ends, long long nq, int32_t* value,
+                        long long* wsum, hipStream_t stream);
+// expand_data (loaddata.cpp:140-183) on the device: out[n] = the compacted array src (storage 1: bytes, 4: int32) with the removed
+// regions back in as zeros.  starts / ends: npairs inclusive pairs, ascending and disjoint; before[k]: removed values in front of
+// pair k.  The caller has checked that the pairs lie inside [0, n) and that n minus their lengths is the compacted length.
+void launch_plot_expand(const void* src, int storage, const int32_t* starts, const int32_t* ends, const long long* before, int npairs, int32_t* out,
+                        long long n, hipStream_t stream);
+
 // ---- `depth`: a chromosome's per-base depth int32[n] summed up without a run (kernels_depth.hip) ----
 // launch_depth_summary: one pass, a workgroup per `span` values.  acc: vmin = INT32_MAX, vmax = INT32_MIN and zeros before the
 // launch; dist: kDepthBins zeros.  After it acc holds the exact sum, minimum and maximum of the non-negative depths, how many lie

@@ -1561,6 +1561,7 @@ void rsi_hot_destroy(rsi_ctx* ctx) {
   for (int b = 0; b < 2; ++b) if (ctx->text_pin[b]) (void)hipHostFree(ctx->text_pin[b]);
   track_free(ctx);
   depth_free(ctx);
+  plot_free(ctx);
   for (int b = 0; b < 2; ++b) {
     for (hipEvent_t e : ctx->bamdev.ev[b]) if (e) (void)hipEventDestroy(e);
     if (ctx->bamdev.find[b]) (void)hipEventDestroy(ctx->bamdev.find[b]);
@@ -2172,8 +2173,10 @@ int rsi_hot_debug_range_sums(rsi_ctx* ctx, const int32_t* depth, int64_t n, int 
 
 // ---- `geno` (include/rsi_hot.h) ----
 // The statistics of `lines` over the compacted depth d_depth[ncompact] (storage 1: bytes, 4: int32) through the kernels of
-// kernels_geno.hip; what rsi_hot_geno_calls and rsi_hot_debug_geno share.  The caller has entered the context and reset the mailbox.
-static int geno_run(rsi_ctx* ctx, const void* d_depth, int storage, int64_t ncompact, const std::vector<rsigeno::Ranges>& lines, int tile,
+// kernels_geno.hip; what rsi_hot_geno_calls, rsi_hot_debug_geno and the plot data (plot.hip) share.  The caller has entered the
+// context and reset the mailbox.
+}  // extern "C"
+int rsip::geno_run(rsi_ctx* ctx, const void* d_depth, int storage, int64_t ncompact, const std::vector<rsigeno::Ranges>& lines, int tile,
                     double chrom_median, rsi_geno_record* out) {
   rsi_ctx::Geno& G = ctx->geno;
   const int64_t bytes_held = G.stats.bytes;
@@ -2235,6 +2238,7 @@ static int geno_run(rsi_ctx* ctx, const void* d_depth, int storage, int64_t ncom
   G.stats.ms = now_ms() - t0;
   return RSI_OK;
 }
+extern "C" {
 
 int rsi_hot_geno_calls(rsi_ctx* ctx, int m, int ncalls, const int32_t* start, const int32_t* end, rsi_geno_record* out) {
   if (!ctx || ncalls < 0 || m < 1 || (ncalls > 0 && (!start || !end || !out))) return fail(ctx, RSI_ERR_BAD_ARG, "bad argument");

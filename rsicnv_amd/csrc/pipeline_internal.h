@@ -124,6 +124,8 @@ using rsip::GpuGate;
 
 #include "bgzf_launch.h"   // rsing::BgzfLaunch: a batch of BGZF members inflated on the device (needs DevBuf, PinBuf, elapsed_ms)
 
+namespace rsigeno { struct Ranges; }
+
 struct rsi_result {
   std::vector<rsi_call> lists[4];
   std::vector<int32_t> noncode;   // pairs
@@ -215,6 +217,13 @@ struct rsi_ctx {
     hipEvent_t ev[2] = {nullptr, nullptr};   // around the summary pass
     rsi_depth_stats stats{};
   } depth;
+  // plot data (rsi_hot_plot_depth, _plot_run; plot.hip): nothing of it exists until the first call with a plannable
+  // figure.  ws: one batch's tables and results; full: the last run's depth with its removed regions back in (rsi_hot_plot_run).
+  struct Plot {
+    DevBuf ws, full, pairs;
+    hipEvent_t ev[2] = {nullptr, nullptr};   // around the expansion
+    rsi_plot_stats stats{};
+  } plot;
   int64_t n_in = 0;                        // length of the depth currently in in_depth
   DevBuf gcbits, nbits, rd_gc, rdc, binmed, binsum, tnb, tmed, first_del;
   DevBuf depth8, rescaled8;   // byte copies: the raw depth (K2 writes it, K3' streams it), the rescaled depth (K3' -> K4')
@@ -441,6 +450,12 @@ int depth_upload(rsi_ctx* ctx, const int32_t* values, int64_t n);
 // caller has entered the context and reset the mailbox.
 int depth_region_records(rsi_ctx* ctx, const int32_t* d_depth, int64_t n, int64_t nreg, const int64_t* start, const int64_t* end, int tile,
                          rsi_depth_region* out);
+
+// pipeline.hip: the statistics of `lines` (geno_host.h) over d_depth[ncompact] (storage 1: bytes, 4: int32) through the kernels of
+// kernels_geno.hip, `tile` values per tile (0: the default); the caller has entered the context and reset the mailbox.
+int geno_run(rsi_ctx* ctx, const void* d_depth, int storage, int64_t ncompact, const std::vector<rsigeno::Ranges>& lines, int tile,
+             double chrom_median, rsi_geno_record* out);
+void plot_free(rsi_ctx* ctx);    // plot.hip: the events of the plot data
 
 struct ExcludeOneShot {   // first statement of a run entry point: the armed mask does not outlive the call
   rsi_ctx* ctx;

@@ -1,8 +1,10 @@
 // plot_host.cpp -- the data (.dat) and script (.gp) files of a call's gnuplot figure, as plot_icnv writes them
-// (plotcnv.cpp:245-610), behind the command line's -p.  SURVEY.md section 8f row 4: presentation, no GPU work -- the
-// per-base array it reads is the capped, GC-adjusted depth the device path leaves (rsi_hot_fetch "rd_concat"), expanded by
-// the removed N regions (expand_data, loaddata.cpp:140-183).  The reference runs gnuplot on the pair and deletes both
-// files; this writer only produces them (the command line runs gnuplot when there is one, and keeps the files when not).
+// (plotcnv.cpp:245-610), behind the command line's -p and behind `rsicnv view`.  The text rules live here once: a figure is planned
+// (plot_plan.h: which rows, which values), filled -- from an array in host memory here (fill_host), or on the device from one in
+// HBM (plot.hip) -- and written (write_planned).  rsi_plot_write_files is plan + fill_host + write_planned over the
+// capped, GC-adjusted depth a run leaves (rsi_hot_fetch "rd_concat"), expanded by the removed N regions (expand_data,
+// loaddata.cpp:140-183).  The reference runs gnuplot on the pair and deletes both files; this writer only produces them (the
+// command line runs gnuplot when there is one, and keeps the files when not).
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -15,141 +17,93 @@
 
 #include "../../include/rsi_hot.h"
 #include "hostmath.h"
+#include "plot_plan.h"
 
 namespace {
 
-constexpr int kPlotPoints = 30000;   // plot::pts, plotcnv.cpp:29
-
-// runmeantp with end_rule = 1 (wufunctions.cpp:573-647): centred window of `band` values, double sliding sum, the ends filled
-// with the first / last mean; the float overload rounds every mean to float (wufunctions.cpp:640-646)
-void running_mean(const std::vector<int>& y, std::vector<float>& smo, int band) {
-  const int n = (int)y.size();
-  std::vector<double> s((size_t)n, 0.0);
-  double sum = 0;
-  for (int i = 0; i < band; ++i) sum += (double)y[(size_t)i];
-  double mean = sum / double(band);
-  int band2 = band / 2;
-  for (int i = 0; i < band2; ++i) s[(size_t)i] = mean;
-  s[(size_t)band2] = mean;
-  ++band2;
-  int ismo = band2;
-  for (int first = 1, last = band; last < n; ++first, ++last, ++ismo) {
-    sum = sum - (double)y[(size_t)first - 1] + (double)y[(size_t)last];
-    mean = sum / double(band);
-    s[(size_t)ismo] = mean;
-  }
-  for (int i = ismo; i < n; ++i) s[(size_t)i] = mean;
-  smo.resize((size_t)n);
-  for (int i = 0; i < n; ++i) smo[(size_t)i] = (float)s[(size_t)i];
-}
-
 const char* kType[3] = {"DEL", "DUP", "UNKNOWN"};
+
+// _lowerquartile / _median / _upperquartile on ints (partition_stat_tp with dy = 1, wufunctions.cpp:364-424) in closed form: of n >= 1
+// sorted values s[], s[max(n/4,1)-1], s[max(n/2,1)-1], s[max(3n/4,1)-1] -- what rsih::grid_quantiles<int> walks a counter per unit
+// of max - min for, all-equal values included (their mean is their value).  v is reordered.
+void rank_quantiles(std::vector<int>& v, double q[3]) {
+  const size_t n = v.size();
+  const size_t r[3] = {n / 4, n / 2, n * 3 / 4};
+  for (int k = 0; k < 3; ++k) {
+    const size_t at = std::max<size_t>(r[k], 1) - 1;
+    std::nth_element(v.begin(), v.begin() + (ptrdiff_t)at, v.end());
+    q[k] = (double)v[at];
+  }
+}
 
 }  // namespace
 
-extern "C" {
+namespace rsiplot {
 
-// Writes <base>.dat and <base>.gp for call `c` (coordinates in the expanded array, as printed in the output table).
-// rd: the expanded per-base depth (n values); chrom_median: _median of that array (plot::RDmed, plotcnv.cpp:625);
-// m / minmlen / chklen: the run's parameters (rsi.cpp:34-98); format: "ps", "eps" or "png" (plot::format);
-// gnuplot_version: what `gnuplot -V` reports, -1 = none found (gnuplot_version(), plotcnv.cpp:51-65).  The script has two
-// dialects and the reference picks the newer one only above 4.19 (plotcnv.cpp:512) -- "none found" gets the older one.
-// Returns RSI_OK, or RSI_ERR_BAD_ARG when the call lies outside the array (the reference draws an empty frame there).
-int rsi_plot_write_files(const rsi_call* c, const char* title_in, const int32_t* rd, int64_t n, double chrom_median, int m,
-                         double minmlen, double chklen, const char* format, double gnuplot_version, const char* datfile,
-                         const char* gpfile, const char* imgfile) {
-  if (!c || !title_in || !rd || n <= 0 || !format || !datfile || !gpfile || !imgfile) return RSI_ERR_BAD_ARG;
-  int cs = c->start, ce = c->end;
-  if (cs > ce) std::swap(cs, ce);
-  const int size = (int)n;
-  if (cs > size || ce > size) return RSI_ERR_BAD_ARG;
+// The host's fill: the neighbourhood gathered, its prefix sums, a window sum per running-mean query -- runmeantp with end_rule = 1
+// (wufunctions.cpp:573-647) is the mean of the window around the clamped centre, and a sum of ints is the same in any order.
+void fill_host(const Plan& P, const int32_t* rd, Filled& F) {
+  F = Filled{};
+  if (P.refusal != kOk) return;
+  std::vector<int> ref;
+  ref.reserve((size_t)P.nref);
+  for (int i = P.a0; i < P.a1; ++i) ref.push_back(rd[i]);
+  for (int i = P.b0; i < P.b1; ++i) ref.push_back(rd[i]);
+  std::vector<int64_t> pre((size_t)P.nref + 1, 0);
+  for (int i = 0; i < P.nref; ++i) pre[(size_t)i + 1] = pre[(size_t)i] + ref[(size_t)i];
+  F.ref_sum = pre[(size_t)P.nref];
+  std::vector<int> body(rd + P.c1, rd + P.c2 + 1);
+  rank_quantiles(body, F.body_q);
+  rank_quantiles(ref, F.ref_q);   // (the prefix sums are taken: ref may be reordered)
+  F.value.assign(P.q.size(), 0);
+  F.wsum.assign(P.q.size(), 0);
+  const int h = P.band / 2;
+  for (size_t k = 0; k < P.q.size(); ++k) {
+    const Query& q = P.q[k];
+    if (q.depth >= 0) F.value[k] = rd[q.depth];
+    if (q.ref >= 0) { const int c = window_centre(q.ref, P.band, P.nref); F.wsum[k] = pre[(size_t)(c + h + 1)] - pre[(size_t)(c - h)]; }
+  }
+}
+
+int write_planned(const Plan& P, const Filled& F, int length, int type, double p1, const char* title_in, double chrom_median, const char* format,
+                  double gnuplot_version, const char* datfile, const char* gpfile, const char* imgfile) {
+  if (P.refusal != kOk || !title_in || !format || !datfile || !gpfile || !imgfile) return RSI_ERR_BAD_ARG;
+  if (F.value.size() != P.q.size() || F.wsum.size() != P.q.size()) return RSI_ERR_BAD_ARG;
+  const int cs = P.cs, ce = P.ce;
+  int i1 = P.i1, i2 = P.i2;
   std::string term = "png xffffff x222222";
   const std::string fmt = format;
   if (fmt == "ps") term = "postscript color enhanced solid";
   if (fmt == "eps") term = "postscript eps enhanced solid";
-  int d = ce - cs + 1;
-  if (d < m * minmlen) d = (int)(m * minmlen);
-  int i1 = (int)(cs - chklen * d), i2 = (int)(ce + chklen * d);
-  if (i1 < 1) i1 = 1;
-  if (i1 > size - 1) i1 = size - 1;
-  if (i2 > size - 1) i2 = size - 1;
-  int c1 = cs - 1, c2 = ce - 1;
-  if (c1 < 0) c1 = 0;
-  if (c1 >= size) c1 = size - 1;
-  if (c2 >= size) c2 = size - 1;
-  // the neighbourhood: bases i1 .. start-1 and end+1 .. i2 (1-based positions: value at index position - 1)
-  std::vector<int> ref((size_t)abs(cs - i1 + i2 - ce));
-  int k = 0;
-  double sum = 0;
-  for (int i = i1; i < cs; ++i, ++k) {
-    const int ic = i - 1;
-    if (ic >= size) break;
-    ref[(size_t)k] = ic < 0 ? 0 : rd[ic];
-    sum += ref[(size_t)k];
-  }
-  for (int i = ce + 1; i <= i2; ++i, ++k) {
-    const int ic = i - 1;
-    if (ic >= size) break;
-    ref[(size_t)k] = ic < 0 ? 0 : rd[ic];
-    sum += ref[(size_t)k];
-  }
-  if (k != (int)ref.size() || ref.empty()) return RSI_ERR_BAD_ARG;   // "size error": the reference returns without a figure
-  const double refmean = sum / double(k);
-  const int nbody = c2 - c1 + 1;
-  if (nbody <= 0) return RSI_ERR_BAD_ARG;
-  const rsih::Quantiles qc = rsih::grid_quantiles(rd + c1, (size_t)nbody);   // _median / _lowerquartile / _upperquartile
-  std::vector<float> runmean;
-  d = abs(ce - cs) + 1;
-  int band = d + ((d + 1) % 2) * 1;
-  if (band > (int)ref.size()) band = (int)ref.size() / 2 + (((int)ref.size() / 2 + 1) % 2) * 1;
-  while (band > (int)ref.size()) band -= 2;
-  if (band <= 0) return RSI_ERR_BAD_ARG;
-  running_mean(ref, runmean, band);
-  const rsih::Quantiles qr = rsih::grid_quantiles(ref.data(), ref.size());
+  const double refmean = (double)F.ref_sum / double(P.nref);
+  struct Q3 { double lqt, med, uqt; };
+  const Q3 qc{F.body_q[0], F.body_q[1], F.body_q[2]}, qr{F.ref_q[0], F.ref_q[1], F.ref_q[2]};
   int ymax = (int)(qr.med * 2.25);
   const double y2max = (double)ymax / refmean / 2.0;
   if (qc.med < qr.med) ymax = (int)(qr.med * 2);
   else ymax = (int)(qc.uqt + 1.5 * (qr.uqt - qr.lqt));
+  // the float overload of runmeantp rounds every mean to float (wufunctions.cpp:640-646)
+  auto runmean = [&](size_t k) { return (float)((double)F.wsum[k] / double(P.band)); };
 
   std::ofstream D(datfile);
   if (!D) return RSI_ERR_BAD_ARG;
-  D << "#" << cs << " ~ " << ce << "  " << c->length << "  " << kType[c->type < 0 || c->type > 2 ? 2 : c->type] << "  " << c->p1 << std::endl;
+  D << "#" << cs << " ~ " << ce << "  " << length << "  " << kType[type < 0 || type > 2 ? 2 : type] << "  " << p1 << std::endl;
   int RDmax = 0;
-  double step = (double)(i2 - i1 + 1) / (double)kPlotPoints;
-  if (step < 1.0) step = 1.0;
-  int i = 0;
-  // block 0: before the call: position, depth, running mean of the neighbourhood
-  for (double ir = (double)i1 + 0.00001; ir < (double)cs + 0.000011; ir += step) {
-    i = (int)ir;
-    const int ic = i - 1;
-    if (ic < 0 || ic >= size) { D << i << "\t0\tNaN" << std::endl; continue; }
-    D << i << "\t" << rd[ic] << "\t" << runmean[(size_t)(i - i1)] << std::endl;
-    if (ic > 0 && rd[ic] > RDmax) RDmax = rd[ic];
+  size_t k = 0;
+  // blocks 0 - 2: in front of the call, the call, behind it: position, depth, running mean of the neighbourhood (none in the call)
+  for (int b = 0; b < 3; ++b) {
+    for (int r = 0; r < P.rows[b]; ++r, ++k) {
+      const Query& q = P.q[k];
+      if (q.depth < 0) { D << q.pos << "\t0\tNaN" << std::endl; continue; }
+      D << q.pos << "\t" << F.value[k] << "\t";
+      if (q.ref >= 0) D << runmean(k); else D << "NaN";
+      D << std::endl;
+      if (q.depth > 0 && F.value[k] > RDmax) RDmax = F.value[k];
+    }
+    D << std::endl << std::endl;
   }
-  D << std::endl << std::endl;
-  // block 1: the call: position, depth
-  for (double ir = (double)cs + 0.00001; ir <= (double)ce + 0.000011; ir += step) {
-    const int ic = (int)(ir - 1);
-    if (ic < 0 || ic >= size) { D << i << "\t0\tNaN" << std::endl; continue; }
-    D << (int)ir << "\t" << rd[ic] << "\t" << "NaN" << std::endl;
-    if (ic > 0 && rd[ic] > RDmax) RDmax = rd[ic];
-  }
-  D << std::endl << std::endl;
-  // block 2: behind the call
-  for (double ir = (double)ce + 1.00001; ir <= (double)i2 + 0.000011; ir += step) {
-    const int ic = (int)(ir - 1);
-    if (ic < 0 || ic >= size) { D << i << "\t0\tNaN" << std::endl; continue; }
-    const int ri = (int)(ir - i1 - d);
-    D << (int)ir << "\t" << rd[ic] << "\t" << runmean[(size_t)std::min(std::max(ri, 0), (int)runmean.size() - 1)] << std::endl;
-    if (ic > 0 && rd[ic] > RDmax) RDmax = rd[ic];
-  }
-  D << std::endl << std::endl;
   // block 3: the line that joins the two running means
-  int imid1 = cs - 3 - i1, imid2 = ce + 1 - i1 - d;
-  if (imid1 < 0) imid1 = 0;
-  if (imid2 >= (int)runmean.size()) imid2 = (int)runmean.size() - 1;
-  if (imid2 < 0) imid2 = 0;
-  D << cs << "\t" << runmean[(size_t)imid1] << std::endl << ce << "\t" << runmean[(size_t)imid2] << std::endl;
+  D << cs << "\t" << runmean(k) << std::endl << ce << "\t" << runmean(k + 1) << std::endl;
   D << std::endl << std::endl;
   // blocks 4-6: median and quartiles of the call; 7-9: of the neighbourhood; 10: nothing
   const double cq[3] = {qc.med, qc.lqt, qc.uqt}, rq[3] = {qr.med, qr.lqt, qr.uqt};
@@ -161,7 +115,7 @@ int rsi_plot_write_files(const rsi_call* c, const char* title_in, const int32_t*
   std::string title = title_in;
   std::replace(title.begin(), title.end(), '~', '-');
   if (ymax > RDmax) ymax = RDmax + RDmax / 10;
-  d = (i2 - i1 + 1) / 6;
+  int d = (i2 - i1 + 1) / 6;
   i1 = i1 + d / 2;
   i2 = i2 - d / 2;
   std::ofstream G(gpfile);
@@ -223,6 +177,91 @@ int rsi_plot_write_files(const rsi_call* c, const char* title_in, const int32_t*
   }
   G << "set output" << std::endl << "quit" << std::endl;
   return RSI_OK;
+}
+
+}  // namespace rsiplot
+
+extern "C" {
+
+// Writes <base>.dat and <base>.gp for call `c` (coordinates in the expanded array, as printed in the output table).
+// rd: the expanded per-base depth (n values); chrom_median: _median of that array (plot::RDmed, plotcnv.cpp:625);
+// m / minmlen / chklen: the run's parameters (rsi.cpp:34-98); format: "ps", "eps" or "png" (plot::format);
+// gnuplot_version: what `gnuplot -V` reports, -1 = none found (gnuplot_version(), plotcnv.cpp:51-65).  The script has two
+// dialects and the reference picks the newer one only above 4.19 (plotcnv.cpp:512) -- "none found" gets the older one.
+// Returns RSI_OK, or RSI_ERR_BAD_ARG when the call lies outside the array (the reference draws an empty frame there).
+int rsi_plot_write_files(const rsi_call* c, const char* title_in, const int32_t* rd, int64_t n, double chrom_median, int m,
+                         double minmlen, double chklen, const char* format, double gnuplot_version, const char* datfile,
+                         const char* gpfile, const char* imgfile) {
+  if (!c || !title_in || !rd || n <= 0 || !format || !datfile || !gpfile || !imgfile) return RSI_ERR_BAD_ARG;
+  const rsiplot::Plan P = rsiplot::plan_call(c->start, c->end, n, m, minmlen, chklen);
+  if (P.refusal != rsiplot::kOk) return RSI_ERR_BAD_ARG;
+  rsiplot::Filled F;
+  rsiplot::fill_host(P, rd, F);
+  return rsiplot::write_planned(P, F, c->length, c->type, c->p1, title_in, chrom_median, format, gnuplot_version, datfile, gpfile, imgfile);
+}
+
+rsi_plot_batch* rsi_plot_batch_new(int64_t n, int m, double minmlen, double chklen) {
+  if (n <= 0 || n >= (1ll << 31) - 4096 || m < 1) return nullptr;
+  rsi_plot_batch* b = new rsi_plot_batch;
+  b->n = n; b->m = m; b->minmlen = minmlen; b->chklen = chklen;
+  return b;
+}
+void rsi_plot_batch_free(rsi_plot_batch* b) { delete b; }
+int rsi_plot_batch_add(rsi_plot_batch* b, const rsi_call* c) {
+  if (!b || !c) return RSI_ERR_BAD_ARG;
+  b->calls.push_back(*c);
+  b->plans.push_back(rsiplot::plan_call(c->start, c->end, b->n, b->m, b->minmlen, b->chklen));
+  b->is_filled = false;
+  return b->plans.back().refusal;
+}
+int rsi_plot_batch_add_span(rsi_plot_batch* b, int start, int end, int type) {
+  rsi_call c;
+  memset(&c, 0, sizeof(c));
+  c.start = start; c.end = end; c.type = type; c.p1 = 1.0;   // cnv_st's defaults: length 0, p1 1
+  return rsi_plot_batch_add(b, &c);
+}
+int rsi_plot_batch_size(const rsi_plot_batch* b) { return b ? (int)b->plans.size() : 0; }
+int rsi_plot_batch_refusal(const rsi_plot_batch* b, int i) { return (!b || i < 0 || i >= (int)b->plans.size()) ? RSI_ERR_BAD_ARG : b->plans[(size_t)i].refusal; }
+const char* rsi_plot_refusal_text(int refusal) { return rsiplot::refusal_text(refusal); }
+int64_t rsi_plot_batch_queries(const rsi_plot_batch* b) {
+  int64_t k = 0;
+  if (b) for (const rsiplot::Plan& P : b->plans) k += (int64_t)P.q.size();
+  return k;
+}
+int rsi_plot_batch_fill_host(rsi_plot_batch* b, const int32_t* rd, int64_t n) {
+  if (!b || !rd || n != b->n) return RSI_ERR_BAD_ARG;
+  b->filled.assign(b->plans.size(), rsiplot::Filled{});
+  for (size_t i = 0; i < b->plans.size(); ++i) rsiplot::fill_host(b->plans[i], rd, b->filled[i]);
+  bool any = false;
+  for (const rsiplot::Plan& P : b->plans) any = any || P.refusal == rsiplot::kOk;
+  b->chrom_median = 0;
+  if (any) {   // plot::RDmed, plotcnv.cpp:625 (nothing to write: no median either, as on the device)
+    std::vector<int> all(rd, rd + n);
+    double q[3];
+    rank_quantiles(all, q);
+    b->chrom_median = q[1];
+  }
+  b->is_filled = true;
+  return RSI_OK;
+}
+int rsi_plot_batch_compare(const rsi_plot_batch* a, const rsi_plot_batch* b) {
+  if (!a || !b || !a->is_filled || !b->is_filled || a->plans.size() != b->plans.size()) return RSI_ERR_BAD_ARG;
+  for (size_t i = 0; i < a->plans.size(); ++i) {
+    const rsiplot::Filled& x = a->filled[i], & y = b->filled[i];
+    if (a->plans[i].refusal != b->plans[i].refusal || x.value != y.value || x.wsum != y.wsum || x.ref_sum != y.ref_sum ||
+        memcmp(x.body_q, y.body_q, sizeof x.body_q) != 0 || memcmp(x.ref_q, y.ref_q, sizeof x.ref_q) != 0)
+      return (int)i + 1;
+  }
+  if (memcmp(&a->chrom_median, &b->chrom_median, sizeof(double)) != 0) return (int)a->plans.size() + 1;
+  return 0;
+}
+double rsi_plot_batch_chrom_median(const rsi_plot_batch* b) { return b && b->is_filled ? b->chrom_median : 0.0; }
+int rsi_plot_batch_write(const rsi_plot_batch* b, int i, const char* title, const char* format, double gnuplot_version, const char* datfile,
+                         const char* gpfile, const char* imgfile) {
+  if (!b || !b->is_filled || i < 0 || i >= (int)b->plans.size()) return RSI_ERR_BAD_ARG;
+  const rsi_call& c = b->calls[(size_t)i];
+  return rsiplot::write_planned(b->plans[(size_t)i], b->filled[(size_t)i], c.length, c.type, c.p1, title, b->chrom_median, format, gnuplot_version,
+                                datfile, gpfile, imgfile);
 }
 
 // expand_data (loaddata.cpp:140-183): the compacted array with the removed regions back in, as zeros.  regions: npairs

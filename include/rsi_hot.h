@@ -746,6 +746,35 @@ int rsi_hot_debug_candidate_tests(rsi_ctx* ctx, const int32_t* depth, int64_t n,
  * RSI_ERR_BAD_ARG, as the tester refuses the whole list.  info[2] (may be NULL) = waits, 1 / 0 for ranges in the mailbox / copied. */
 int rsi_hot_debug_range_sums(rsi_ctx* ctx, const int32_t* depth, int64_t n, int storage, const int32_t* lo, const int32_t* hi, int nranges,
                              int64_t* sums, int32_t* info);
+/* Test hooks: the three list stages behind the scan, each alone over HOST arrays, with the context's own workspace and the device
+ * tester a run attaches (use_tester 1) or none (0: the host walks).  Lists travel as rsi_call records (qscore and pad unused); P: the
+ * fields the stage reads (m, minmlen, chklen, buffer, maxchkbp, p, merge).  The environment switches of whole runs are not read.
+ * RSI_ERR_BAD_ARG, with the context left usable: an entry outside the array or with end < start, a type other than 0 (DEL) / 1 (DUP),
+ * m < 1, maxchkbp < 1, minmlen or chklen not positive, a negative buffer, a negative value in the array.  RSI_ERR_UNSUPPORTED: a test
+ * whose neighbourhood is no longer than its candidate (the reference aborts).  info[10] (may be NULL) = tests judged from a result
+ * launched ahead (spec_hits), tests launched alone (single_tests), tests the device declined (host_fallbacks), first-round block tests
+ * judged from the batch (block_batch_hits), the tester's waits, calls of its range sums, merge means answered from the batch of sums,
+ * merge means taken by a call of their own, tests with a tester attached, 0.
+ *
+ * rsi_hot_debug_block_stage: areblockscnv (rsi.cpp:415-546) on nsegs segments in bin space (start, end, type, score, status; judged in
+ * place) over binmedint[nb] and status[nb]; ncompact: the compacted length the tests compare nb with.  The bin medians become the
+ * context's compacted depth as int32.  sparse 1: the status array is read through the sparse form a scan leaves -- the values inside
+ * the maximal runs of non-zero status, run after run -- and needs one such run.  road[nsegs] (may be NULL): the road of every
+ * first-round test: 0 the batch's result, 1 the host walk because no batch was run, 2 because a segment rejected since reaches into
+ * the left walk, 3 because the left chain was cut, 4 because the device declined. */
+int rsi_hot_debug_block_stage(rsi_ctx* ctx, const int32_t* binmedint, const int32_t* status, int64_t nb, int64_t ncompact, double RDmedian,
+                              const rsi_params* P, rsi_call* segs, int nsegs, int use_tester, int sparse, int32_t* road, int32_t* info);
+/* rsi_hot_debug_merge: mergesegments (rsi.cpp:694-885) on a list in base coordinates whose geno, status, p1 and refsd are the caller's,
+ * over depth[n] as bytes (storage 1; a value outside 0 .. 255 is RSI_ERR_BAD_ARG) or as int32 (storage 4).  out[nlist], *nout: the list
+ * after both passes. */
+int rsi_hot_debug_merge(rsi_ctx* ctx, const int32_t* depth, int64_t n, int storage, double RDmedian, const rsi_params* P, const rsi_call* list,
+                        int nlist, int use_tester, rsi_call* out, int32_t* nout, int32_t* info);
+/* rsi_hot_debug_calls: everything detectcnv does behind the block tests (rsi.cpp:1860-1931) and sd_filters (rsi.cpp:1753-1792) on nsegs
+ * tested segments in bin space over depth[n] (storage as above), with nnoncode regions (sorted, disjoint, end > start, reference coordinates).
+ * blocks, raw, kept: room for nsegs records each; counts[3]: how many of each. */
+int rsi_hot_debug_calls(rsi_ctx* ctx, const int32_t* depth, int64_t n, int storage, double RDmedian, double RDsd, const rsi_params* P,
+                        const rsi_call* segs, int nsegs, const int32_t* noncode_start, const int32_t* noncode_end, int nnoncode, int use_tester,
+                        rsi_call* blocks, rsi_call* raw, rsi_call* kept, int32_t* counts, int32_t* info);
 /* Test hook: the NB transform (negative_binomial_transfer, rsi.cpp:1145-1185) of the HOST bin sums binsum[nb] through the function a
  * run calls: the formula and the raw minimum (raw[nb]: the array between the two launches), then the subtraction, the scaling and
  * the three overwritten bins (T[nb]).  nb >= 3 (the reference writes bins 0..2) and nb == ncompact / m (the reference's bin count),

@@ -211,6 +211,78 @@ class Ref:
             L.ref_isitcnvwrap.argtypes = [C.POINTER(Params), ip, C.c_int32, C.c_int32, C.c_double, ip, ip, ip, ip, C.c_int32, C.c_int32,
                                           C.POINTER(Call)]
 
+        if hasattr(L, "ref_areblockscnv"):   # likewise
+            ip, cp = C.POINTER(C.c_int32), C.POINTER(Call)
+            L.ref_areblockscnv.argtypes = [C.POINTER(Params), ip, ip, C.c_int32, C.c_int32, C.c_double, cp, C.c_int32]
+            L.ref_mergesegments.argtypes = [C.POINTER(Params), ip, C.c_int32, C.c_double, cp, C.c_int32, cp, C.c_int32]
+            L.ref_isitcnvwrap_in_order.argtypes = [C.POINTER(Params), ip, C.c_int32, C.c_int32, C.c_double, cp, C.c_int32, C.c_int32]
+            L.ref_expand_coordinate.argtypes = [ip, ip, C.c_int32, ip, C.c_int32, ip]
+            L.ref_expand_coordinate.restype = None
+            L.ref_sd_filters.argtypes = [C.c_int32, C.c_double, C.c_double, cp, C.c_int32, cp, C.c_int32]
+
+    # ---- the list stages alone: lists travel as sequences of dicts with (some of) CALL_FIELDS, missing fields as cnv_st() leaves them ----
+    @staticmethod
+    def _list(dicts):
+        arr = (Call * max(len(dicts), 1))()
+        for i, d in enumerate(dicts):
+            arr[i].type, arr[i].p1 = 2, 1.0          # cnv_st(): TYPE_UNKNOWN, p1 = 1
+            for k, v in d.items():
+                if k in CALL_FIELDS:
+                    setattr(arr[i], k, v)
+        return arr
+
+    def _need(self, name):
+        if not hasattr(self.lib, name):
+            raise RuntimeError(f"{REF_SO} predates {name}: rebuild it with `make -f oracle/Makefile.ref`")
+
+    def areblockscnv(self, params, medint, status, span_all, RDmedian, segs):
+        """The reference's areblockscnv (rsi.cpp:415-546) on the caller's bin medians, status array and segments: the segments as judged."""
+        self._need("ref_areblockscnv")
+        m, mp = _i32(medint)
+        s, sp = _i32(status)
+        arr = self._list(segs)
+        if self.lib.ref_areblockscnv(C.byref(params), mp, sp, m.size, int(span_all), float(RDmedian), arr, len(segs)) != 0:
+            raise RuntimeError("the reference's Array threw")
+        return calls_to_dicts(arr, len(segs))
+
+    def mergesegments(self, params, rd, RDmedian, cands):
+        """The reference's mergesegments (rsi.cpp:694-885): the list after both passes."""
+        self._need("ref_mergesegments")
+        d, dp = _i32(rd)
+        arr, out = self._list(cands), (Call * max(len(cands), 1))()
+        n = self.lib.ref_mergesegments(C.byref(params), dp, d.size, float(RDmedian), arr, len(cands), out, len(cands))
+        if n < 0:
+            raise RuntimeError("the reference's Array threw")
+        return calls_to_dicts(out, n)
+
+    def isitcnvwrap_in_order(self, params, rd, span_all, RDmedian, cands, k=None):
+        """isitcnvwrap for the indices 0 .. k - 1 in order on one list (the final-test loop's stateful part): the list afterwards."""
+        self._need("ref_isitcnvwrap_in_order")
+        d, dp = _i32(rd)
+        arr = self._list(cands)
+        k = len(cands) if k is None else k
+        if self.lib.ref_isitcnvwrap_in_order(C.byref(params), dp, d.size, int(span_all), float(RDmedian), arr, len(cands), int(k)) != 0:
+            raise RuntimeError("the reference's Array threw")
+        return calls_to_dicts(arr, len(cands))
+
+    def expand_coordinate(self, noncode, positions):
+        """expand_coordinate (rsi.cpp:1524-1551) of every position with the caller's regions as rsi::noncodelist."""
+        self._need("ref_expand_coordinate")
+        nc = np.asarray(noncode, dtype=np.int32).reshape(-1, 2)
+        a, ap = _i32(nc[:, 0])
+        b, bp = _i32(nc[:, 1])
+        p, pp = _i32(positions)
+        out = np.zeros(p.size, dtype=np.int32)
+        self.lib.ref_expand_coordinate(ap, bp, a.size, pp, p.size, out.ctypes.data_as(C.POINTER(C.c_int32)))
+        return out
+
+    def sd_filters(self, m, RDmedian, RDsd, cands):
+        """sd_filters (rsi.cpp:1753-1792): the entries that stay."""
+        self._need("ref_sd_filters")
+        arr, out = self._list(cands), (Call * max(len(cands), 1))()
+        n = self.lib.ref_sd_filters(int(m), float(RDmedian), float(RDsd), arr, len(cands), out, len(cands))
+        return calls_to_dicts(out, n)
+
     def isitcnvwrap(self, params, rd, span_all, RDmedian, cands, idx):
         """The reference's isitcnvwrap + isitcnv (rsi.cpp:101-287) for entry idx of the list cands (int32 [k, 4]: start, end, type,
         status) over the caller's array: the candidate as judged, a dict.  The caller keeps the walks inside the reference's arrays

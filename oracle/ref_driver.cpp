@@ -55,6 +55,7 @@ string cnv_format1(cnv_st& icnv);                                               
 int expand_coordinate(int p1);                                                     // rsi.cpp:1524
 void optimize_with_derivative(Array<int>& RD, cnv_st& icnv);                       // rsi.cpp:889
 void isitcnvwrap(Array<int>& RD, vector<cnv_st>& cnvlist, int cnvidx);             // rsi.cpp:175
+void mergesegments(Array<int>& RD, vector<cnv_st>& cnvlist);                       // rsi.cpp:694
 void plot_icnv(cnv_st icnv, string title, string datfile, string gpfile, string imgfile);   // plotcnv.cpp:246
 
 extern "C" {
@@ -538,6 +539,123 @@ int ref_isitcnvwrap(const ref_params* p, const int32_t* rd, int32_t n, int32_t s
   rsi::maxchkbp = k_max; rsi::start = k_start; rsi::end = k_end;
   fill_call(list[idx], out);
   return rc;
+}
+
+// ---- the list stages alone (tests/calls_cases.py, tools/make_golden_calls.py) ----
+// Each entry calls ONE reference function on the caller's arrays and list, with the globals that function reads set for the call
+// and restored afterwards.  The caller keeps every walk inside the reference's arrays (tests/calls_cases.py proves it per case
+// before it comes here); -1 says the reference's Array threw all the same.
+}  // extern "C"
+namespace {
+struct ListGlobals {   // what isitcnvwrap, mergesegments and sd_filters read
+  double med, sd, minmlen, chklen, buffer, p;
+  int m, maxchkbp, start, end;
+  bool merge, debug;
+  ListGlobals() : med(rsi::RDmedian), sd(rsi::RDsd), minmlen(rsi::minmlen), chklen(rsi::chklen), buffer(rsi::buffer), p(rsi::p), m(rsi::m),
+                  maxchkbp(rsi::maxchkbp), start(rsi::start), end(rsi::end), merge(rsi::merge), debug(rsi::debug) {}
+  void set(const ref_params* q, double RDmedian, int span_all) {
+    rsi::RDmedian = RDmedian; rsi::m = q->m; rsi::minmlen = q->minmlen; rsi::chklen = q->chklen; rsi::buffer = q->buffer; rsi::p = q->p;
+    rsi::maxchkbp = q->maxchkbp; rsi::start = 1; rsi::end = span_all; rsi::merge = q->merge != 0; rsi::debug = false;
+  }
+  ~ListGlobals() {
+    rsi::RDmedian = med; rsi::RDsd = sd; rsi::minmlen = minmlen; rsi::chklen = chklen; rsi::buffer = buffer; rsi::p = p; rsi::m = m;
+    rsi::maxchkbp = maxchkbp; rsi::start = start; rsi::end = end; rsi::merge = merge; rsi::debug = debug;
+  }
+};
+void list_in(const ref_call* in, int n, vector<cnv_st>& L) {
+  L.assign((size_t)n, cnv_st());
+  for (int i = 0; i < n; ++i) {
+    cnv_st& c = L[i];
+    c.start = in[i].start; c.end = in[i].end; c.type = in[i].type; c.geno = in[i].geno; c.status = in[i].status; c.length = in[i].length;
+    c.score = in[i].score; c.p1 = in[i].p1; c.cnvmed = in[i].cnvmed; c.cnvsd = in[i].cnvsd; c.cnviqr = in[i].cnviqr;
+    c.refmed = in[i].refmed; c.refsd = in[i].refsd; c.refiqr = in[i].refiqr;
+  }
+}
+int list_out(const vector<cnv_st>& L, ref_call* out, int cap) {
+  for (size_t i = 0; i < L.size() && (int)i < cap; ++i) fill_call(L[i], &out[i]);
+  return (int)L.size();
+}
+void fill_array(Array<int>& A, const int32_t* v, int n) {
+  A.resize(0);
+  A.resize(n);
+  for (int k = 0; k < n; ++k) A[k] = v[k];
+}
+}  // namespace
+extern "C" {
+
+// areblockscnv (rsi.cpp:415-546) on the caller's bin medians, status array and segments (judged in place).
+int ref_areblockscnv(const ref_params* p, const int32_t* medint, const int32_t* status, int32_t nb, int32_t span_all, double RDmedian,
+                     ref_call* segs, int32_t nsegs) {
+  static Array<int> MI(1), ST(1);
+  fill_array(MI, medint, nb);
+  fill_array(ST, status, nb);
+  vector<cnv_st> L;
+  list_in(segs, nsegs, L);
+  ListGlobals keep;
+  keep.set(p, RDmedian, span_all);
+  int rc = 0;
+  quiet_begin();
+  try { areblockscnv(MI, ST, L); } catch (const char*) { rc = -1; }
+  quiet_end();
+  if (rc == 0) list_out(L, segs, nsegs);
+  return rc;
+}
+
+// mergesegments (rsi.cpp:694-885) on the caller's depth and list; out: the list after both passes.  Returns its length.
+int ref_mergesegments(const ref_params* p, const int32_t* rd, int32_t n, double RDmedian, const ref_call* list, int32_t nlist, ref_call* out,
+                      int32_t cap) {
+  static Array<int> RD(1);
+  fill_array(RD, rd, n);
+  vector<cnv_st> L;
+  list_in(list, nlist, L);
+  ListGlobals keep;
+  keep.set(p, RDmedian, n);
+  int rc = 0;
+  quiet_begin();
+  try { mergesegments(RD, L); } catch (const char*) { rc = -1; }
+  quiet_end();
+  return rc == 0 ? list_out(L, out, cap) : -1;
+}
+
+// isitcnvwrap for the indices 0 .. k - 1 in order on ONE list (judged in place): the stateful part of the final-test loop
+// (rsi.cpp:1910-1912) -- a rejection persists from one index to the next.
+int ref_isitcnvwrap_in_order(const ref_params* p, const int32_t* rd, int32_t n, int32_t span_all, double RDmedian, ref_call* list,
+                             int32_t nlist, int32_t k) {
+  static Array<int> RD(1);
+  fill_array(RD, rd, n);
+  vector<cnv_st> L;
+  list_in(list, nlist, L);
+  ListGlobals keep;
+  keep.set(p, RDmedian, span_all);
+  int rc = 0;
+  quiet_begin();
+  try { for (int i = 0; i < k && i < nlist; ++i) isitcnvwrap(RD, L, i); } catch (const char*) { rc = -1; }
+  quiet_end();
+  if (rc == 0) list_out(L, list, nlist);
+  return rc;
+}
+
+// expand_coordinate (rsi.cpp:1524-1551) for np positions with rsi::noncodelist set to the caller's regions for the call.
+void ref_expand_coordinate(const int32_t* nc_start, const int32_t* nc_end, int32_t nnc, const int32_t* pos, int32_t np, int32_t* out) {
+  const vector<cnv_st> keep = rsi::noncodelist;
+  rsi::noncodelist.assign((size_t)nnc, cnv_st());
+  for (int i = 0; i < nnc; ++i) { rsi::noncodelist[i].start = nc_start[i]; rsi::noncodelist[i].end = nc_end[i]; }
+  quiet_begin();
+  for (int i = 0; i < np; ++i) out[i] = expand_coordinate(pos[i]);
+  quiet_end();
+  rsi::noncodelist = keep;
+}
+
+// sd_filters (rsi.cpp:1753-1792) on the caller's list; out: the entries that stay, in order.  Returns how many.
+int ref_sd_filters(int32_t m, double RDmedian, double RDsd, const ref_call* list, int32_t nlist, ref_call* out, int32_t cap) {
+  vector<cnv_st> L;
+  list_in(list, nlist, L);
+  ListGlobals keep;
+  rsi::m = m; rsi::RDmedian = RDmedian; rsi::RDsd = RDsd;
+  quiet_begin();
+  sd_filters(L);
+  quiet_end();
+  return list_out(L, out, cap);
 }
 
 // Direct probes of the numeric utilities (used to pin the oracle's restatements).

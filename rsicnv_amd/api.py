@@ -58,6 +58,12 @@ CAND_RECORD = np.dtype([(k, np.int32) for k in ("capacity", "top", "margin", "cu
                        [(k, np.float64) for k in ("p1", "cnvmed", "cnvsd", "cnviqr", "refmed", "refsd", "refiqr")])
 assert CAND_RECORD.itemsize == 18 * 4 + 17 * 8
 
+# rsi_call (include/rsi_hot.h) as a numpy record: the lists of rsi_hot_debug_block_stage / _merge / _calls
+CALL_RECORD = np.dtype([(k, np.int32) for k in ("start", "end", "type", "geno", "status", "length", "qscore", "pad")] +
+                       [(k, np.float64) for k in ("score", "p1", "cnvmed", "cnvsd", "cnviqr", "refmed", "refsd", "refiqr")])
+assert CALL_RECORD.itemsize == 8 * 4 + 8 * 8
+LIST_INFO = ("spec_hits", "single_tests", "host_fallbacks", "block_batch_hits", "waits", "sum_launches", "sum_reused", "sum_redone", "tests")
+
 # rsi_geno_record (include/rsi_hot.h): one line of rsi_hot_geno_calls / rsi_hot_debug_geno
 GENO_RECORD = np.dtype([(k, np.int32) for k in ("n_body", "n_flank", "body_min", "body_max")] +
                        [("body_sum", np.int64), ("flank_sum", np.int64), ("body_q", np.float64, 3), ("flank_q", np.float64, 3),
@@ -75,7 +81,7 @@ EXPORTS = ["rsi_default_params", "rsi_hot_create", "rsi_hot_destroy", "rsi_hot_l
            "rsi_hot_run_device", "rsi_hot_load_depth_text", "rsi_hot_run_text", "rsi_hot_load_depth_bam", "rsi_hot_run_bam", "rsi_bam_references", "rsi_result_annotate_bam", "rsi_result_summary", "rsi_summary_format_row", "rsi_summary_format_rows", "rsi_result_pairs", "rsi_result_ncalls", "rsi_result_calls", "rsi_result_stats", "rsi_result_noncode",
            "rsi_result_format_row", "rsi_result_free", "rsi_hot_fetch_i32", "rsi_hot_fetch_f32", "rsi_hot_fetch_i64",
            "rsi_hot_kernel_times", "rsi_hot_phase_times", "rsi_hot_set_timing", "rsi_hot_process_setup", "rsi_pool_create", "rsi_pool_destroy", "rsi_pool_workers", "rsi_pool_hw_queues", "rsi_pool_worker",
-           "rsi_pool_set_timing", "rsi_pool_set_timing_kernel", "rsi_hot_set_timing_kernel", "rsi_pool_set_schedule", "rsi_pool_last_error", "rsi_pool_run", "rsi_pool_run_host", "rsi_pool_submit", "rsi_pool_wait", "rsi_plot_expand", "rsi_plot_write_files", "rsi_result_log_line", "rsi_hot_debug_level_sums", "rsi_hot_debug_scan", "rsi_hot_debug_segments", "rsi_hot_debug_sharpen", "rsi_hot_debug_candidate_tests", "rsi_hot_debug_range_sums", "rsi_hot_debug_nb_transform", "rsi_hot_debug_filterstatus", "rsi_hot_debug_grid_median", "rsi_hot_debug_grid_mad_i32", "rsi_synth_generate_host", "rsi_synth_generate_device", "rsi_synth_write_depth_text", "rsi_synth_write_fasta", "rsi_synth_append_genome_text",
+           "rsi_pool_set_timing", "rsi_pool_set_timing_kernel", "rsi_hot_set_timing_kernel", "rsi_pool_set_schedule", "rsi_pool_last_error", "rsi_pool_run", "rsi_pool_run_host", "rsi_pool_submit", "rsi_pool_wait", "rsi_plot_expand", "rsi_plot_write_files", "rsi_result_log_line", "rsi_hot_debug_level_sums", "rsi_hot_debug_scan", "rsi_hot_debug_segments", "rsi_hot_debug_sharpen", "rsi_hot_debug_candidate_tests", "rsi_hot_debug_range_sums", "rsi_hot_debug_block_stage", "rsi_hot_debug_merge", "rsi_hot_debug_calls", "rsi_hot_debug_nb_transform", "rsi_hot_debug_filterstatus", "rsi_hot_debug_grid_median", "rsi_hot_debug_grid_mad_i32", "rsi_synth_generate_host", "rsi_synth_generate_device", "rsi_synth_write_depth_text", "rsi_synth_write_fasta", "rsi_synth_append_genome_text",
            "rsi_genome_text_open", "rsi_genome_text_next", "rsi_genome_text_release", "rsi_genome_text_copy_depth",
            "rsi_genome_text_kernel_ms", "rsi_genome_text_close", "rsi_genome_text_last_error", "rsi_hot_run_depth_device",
            "rsi_hot_last_inflate_stats", "rsi_hot_inflate_bgzf", "rsi_genome_text_inflate_stats",
@@ -822,6 +828,56 @@ class RsiHot:
         self._check(self.lib.rsi_hot_debug_range_sums(self.ctx, d.ctypes.data, d.size, int(storage), a.ctypes.data, b.ctypes.data, a.size,
                                                       sums.ctypes.data, info.ctypes.data))
         return sums[:a.size], info
+
+    def debug_block_stage(self, binmedint, status, segs, ncompact, RDmedian, tester=True, sparse=False, **params):
+        """areblockscnv on a segment list in bin space over host arrays (test hook).  segs: a CALL_RECORD array (start, end, type, score,
+        status); params: make_params' keywords.  Returns (segments as judged, road per first-round test, info as a dict of LIST_INFO)."""
+        b = np.ascontiguousarray(binmedint, dtype=np.int32)
+        st = np.ascontiguousarray(status, dtype=np.int32)
+        assert b.size == st.size
+        L = np.array(segs, dtype=CALL_RECORD).reshape(-1)
+        road = np.full(max(L.size, 1), -1, dtype=np.int32)
+        info = np.zeros(10, dtype=np.int32)
+        P = make_params(**params)
+        self.lib.rsi_hot_debug_block_stage.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_void_p,
+                                                       C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        self._check(self.lib.rsi_hot_debug_block_stage(self.ctx, b.ctypes.data, st.ctypes.data, b.size, int(ncompact), float(RDmedian), C.addressof(P),
+                                                       L.ctypes.data, L.size, int(bool(tester)), int(bool(sparse)), road.ctypes.data, info.ctypes.data))
+        return L, road[:L.size], dict(zip(LIST_INFO, (int(v) for v in info)))
+
+    def debug_merge(self, depth, storage, cands, RDmedian, tester=True, **params):
+        """mergesegments on a list in base coordinates over a host array (test hook).  cands: a CALL_RECORD array whose geno, status, p1 and
+        refsd are the caller's.  Returns (the list after both passes, info as a dict of LIST_INFO)."""
+        d = np.ascontiguousarray(depth, dtype=np.int32)
+        L = np.ascontiguousarray(np.array(cands, dtype=CALL_RECORD).reshape(-1))
+        out = np.zeros(max(L.size, 1), dtype=CALL_RECORD)
+        nout = np.zeros(1, dtype=np.int32)
+        info = np.zeros(10, dtype=np.int32)
+        P = make_params(**params)
+        self.lib.rsi_hot_debug_merge.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]
+        self._check(self.lib.rsi_hot_debug_merge(self.ctx, d.ctypes.data, d.size, int(storage), float(RDmedian), C.addressof(P), L.ctypes.data, L.size,
+                                                 int(bool(tester)), out.ctypes.data, nout.ctypes.data, info.ctypes.data))
+        return out[:int(nout[0])], dict(zip(LIST_INFO, (int(v) for v in info)))
+
+    def debug_calls(self, depth, storage, segs, noncode, RDmedian, RDsd, tester=True, **params):
+        """Everything behind the block tests on tested segments in bin space over a host array (test hook).  noncode: (k, 2) regions.
+        Returns (blocks, raw, kept, info as a dict of LIST_INFO)."""
+        d = np.ascontiguousarray(depth, dtype=np.int32)
+        L = np.ascontiguousarray(np.array(segs, dtype=CALL_RECORD).reshape(-1))
+        nc = np.asarray(noncode, dtype=np.int32).reshape(-1, 2)
+        a, b = np.ascontiguousarray(nc[:, 0]), np.ascontiguousarray(nc[:, 1])
+        outs = [np.zeros(max(L.size, 1), dtype=CALL_RECORD) for _ in range(3)]
+        counts = np.zeros(3, dtype=np.int32)
+        info = np.zeros(10, dtype=np.int32)
+        P = make_params(**params)
+        self.lib.rsi_hot_debug_calls.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_int,
+                                                 C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._check(self.lib.rsi_hot_debug_calls(self.ctx, d.ctypes.data, d.size, int(storage), float(RDmedian), float(RDsd), C.addressof(P),
+                                                 L.ctypes.data, L.size, a.ctypes.data if a.size else None, b.ctypes.data if b.size else None, a.size,
+                                                 int(bool(tester)), outs[0].ctypes.data, outs[1].ctypes.data, outs[2].ctypes.data, counts.ctypes.data,
+                                                 info.ctypes.data))
+        return outs[0][:counts[0]], outs[1][:counts[1]], outs[2][:counts[2]], dict(zip(LIST_INFO, (int(v) for v in info)))
 
     def debug_nb_transform(self, binsum, m, ncompact, RDmedian, r):
         """The NB transform of host bin sums on the device (test hook): (raw, T, info).  raw: the values before the minimum is taken off;

@@ -589,13 +589,18 @@ void merge_neighbours(const CallerInput& in, const PagedView& A, std::vector<Can
       ranges.push_back({L[i + 1].start, L[i + 1].end});
       ranges.push_back({L[i].start, L[i + 1].end});
     }
+    if (!ranges.empty() && in.prof) in.prof->sum_launches++;
     if (!ranges.empty() && !in.tester->range_sums(ranges, sums)) { sums.clear(); std::fill(sum_slot.begin(), sum_slot.end(), -1); }
   }
   auto mean_of = [&](int slot, int lo, int hi) -> double {   // mean_tp, wufunctions.cpp:666-690 (integer sums are exact in double)
-    if (slot >= 0 && ranges[slot].first == lo && ranges[slot].second == hi) return (double)sums[slot] / double(hi - lo + 1);
+    if (slot >= 0 && ranges[slot].first == lo && ranges[slot].second == hi) {
+      if (in.prof) in.prof->sum_reused++;
+      return (double)sums[slot] / double(hi - lo + 1);
+    }
     if (in.tester) {
       std::vector<std::pair<int, int>> one(1, {lo, hi});
       std::vector<int64_t> s1;
+      if (in.prof) { in.prof->sum_launches++; in.prof->sum_redone++; }
       if (in.tester->range_sums(one, s1)) return (double)s1[0] / double(hi - lo + 1);
     }
     return range_mean(A, lo, hi);
@@ -650,6 +655,10 @@ int to_reference(const std::vector<Region>& noncode, int p) {
 
 }  // namespace
 
+void debug_merge_neighbours(const CallerInput& in, DepthPager& depth, std::vector<Candidate>& list) {
+  merge_neighbours(in, PagedView{&depth}, list);
+}
+
 int debug_neighbour_tests(const CallerInput& in, DepthPager& depth, const std::vector<Candidate>& list, const std::vector<int>& idx,
                           std::vector<DebugTest>& out) {
   const PagedView A{&depth};
@@ -701,11 +710,14 @@ void test_block_segments(const CallerInput& in, IntSpan status, std::vector<Cand
     if (!in.block_tester->test(plans, stats, reach, ok)) plans.clear();
   }
   int rejected_end = -1;   // the largest end among the segments rejected so far
+  if (in.block_roads) in.block_roads->clear();
   for (int i = 0; i < (int)T.size(); ++i) {
     if (!plans.empty() && ok[(size_t)i] && !(plans[(size_t)i].cut & 1) && rejected_end < reach[(size_t)i]) {
       finish_judgement(in, stats[(size_t)i], T[i]);
       if (in.prof) in.prof->block_batch_hits++;
+      if (in.block_roads) in.block_roads->push_back(0);
     } else {
+      if (in.block_roads) in.block_roads->push_back(plans.empty() ? 1 : !ok[(size_t)i] ? 4 : (plans[(size_t)i].cut & 1) ? 3 : 2);
       test_candidate(in, bins, T, i);
     }
     if (T[i].status == -9 && T[i].end > rejected_end) rejected_end = T[i].end;

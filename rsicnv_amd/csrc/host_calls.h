@@ -71,6 +71,8 @@ class DepthPager {
 struct CallProfile {
   double fetch = 0, gather = 0, winmean = 0, quantiles = 0, variance = 0, sharpen = 0, merge = 0, final_tests = 0, device_ms = 0;
   int tests = 0, spec_hits = 0, single_tests = 0, host_fallbacks = 0, block_batch_hits = 0;
+  // mergesegments' means with a tester attached: calls of range_sums, means answered from the batch's slots, means taken by a call of their own
+  int sum_launches = 0, sum_reused = 0, sum_redone = 0;
 };
 
 // Statistics of one neighbourhood test (what isitcnv derives from its two arrays, rsi.cpp:113-147).
@@ -135,6 +137,10 @@ struct CallerInput {
   // spans most of what is left): the reference sizes its running-mean array ref - body (rsi.cpp:107) and indexes it -- its
   // Array throws and the program aborts.  Counted here; the caller fails the chromosome with RSI_ERR_UNSUPPORTED.
   int* short_neighbourhoods = nullptr;
+  // Test harness (rsi_hot_debug_block_stage): the road of every first-round block test.  0: the batch's result; 1: the host walk, no
+  // batch was run; 2: the host walk, a segment rejected since reaches into the left walk; 3: the host walk, the left chain was cut;
+  // 4: the host walk, the device declined the test.
+  std::vector<int>* block_roads = nullptr;
 };
 
 // areblockscnv on one scan's segments (rsi.cpp:415-546); segs are updated in place.
@@ -153,6 +159,9 @@ void call_from_segments(const CallerInput& in, std::vector<Candidate> segs, Dept
 struct DebugTest { TestPlan plan; Candidate judged; int road; };
 int debug_neighbour_tests(const CallerInput& in, DepthPager& depth, const std::vector<Candidate>& list, const std::vector<int>& idx,
                           std::vector<DebugTest>& out);
+
+// Test harness (rsi_hot_debug_merge): mergesegments (rsi.cpp:694-885) alone on a list whose fields are the caller's.
+void debug_merge_neighbours(const CallerInput& in, DepthPager& depth, std::vector<Candidate>& list);
 
 // Depth from host memory, narrowed to bytes before it crosses PCIe: dst[i] = src[i] where 0 <= src[i] < 255, else 255 with the value
 // listed in (esc_pos, esc_val) (up to cap entries).  Returns the number of values that did not fit (may exceed cap).

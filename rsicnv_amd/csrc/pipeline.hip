@@ -2171,6 +2171,174 @@ int rsi_hot_debug_range_sums(rsi_ctx* ctx, const int32_t* depth, int64_t n, int 
   return RSI_OK;
 }
 
+// ---- the list stages alone (include/rsi_hot.h): test_block_segments, merge_neighbours, call_from_segments over host arrays ----
+static Candidate list_in(const rsi_call& c) {
+  Candidate k;
+  k.type = c.type; k.geno = c.geno; k.status = c.status; k.start = c.start; k.end = c.end; k.length = c.length;
+  k.score = c.score; k.p1 = c.p1; k.cnvmed = c.cnvmed; k.cnvsd = c.cnvsd; k.cnviqr = c.cnviqr; k.refmed = c.refmed; k.refsd = c.refsd;
+  k.refiqr = c.refiqr;
+  return k;
+}
+static void list_out(const std::vector<Candidate>& L, rsi_call* out, int32_t* count) {
+  for (size_t i = 0; i < L.size(); ++i) {
+    const Candidate& k = L[i];
+    rsi_call& c = out[i];
+    memset(&c, 0, sizeof(c));
+    c.type = k.type; c.geno = k.geno; c.status = k.status; c.start = k.start; c.end = k.end; c.length = k.length;
+    c.score = k.score; c.p1 = k.p1; c.cnvmed = k.cnvmed; c.cnvsd = k.cnvsd; c.cnviqr = k.cnviqr; c.refmed = k.refmed; c.refsd = k.refsd;
+    c.refiqr = k.refiqr;
+  }
+  *count = (int32_t)L.size();
+}
+// What the three hooks check alike.  longest: the longest body a test of the stage can have.
+static bool list_params_ok(const rsi_params* P, double RDmedian, int64_t longest) {
+  if (!P || P->m < 1 || P->maxchkbp < 1 || P->maxchkbp > ((1 << 30) / 10) || !(P->minmlen > 0 && P->minmlen < 1e6) ||
+      !(P->chklen > 0 && P->chklen < 1e6) || !(P->buffer >= 0 && P->buffer < 1e6) || !(P->p == P->p) || !(RDmedian == RDmedian))
+    return false;
+  const double d = std::max({(double)longest, (double)P->m * P->minmlen, P->minmlen + 1});
+  return P->chklen * d * 2 < 1073741824.0;   // every plan's capacity fits an int
+}
+static void list_info(const rsih::CallProfile& prof, int launches, int32_t* info) {
+  if (!info) return;
+  info[0] = prof.spec_hits; info[1] = prof.single_tests; info[2] = prof.host_fallbacks; info[3] = prof.block_batch_hits;
+  info[4] = launches; info[5] = prof.sum_launches; info[6] = prof.sum_reused; info[7] = prof.sum_redone; info[8] = prof.tests; info[9] = 0;
+}
+// Test hook: areblockscnv over host arrays (include/rsi_hot.h).  The bin medians become the context's compacted depth as int32 -- the
+// array the block tester of a run reads -- and rsih::test_block_segments does the rest.
+int rsi_hot_debug_block_stage(rsi_ctx* ctx, const int32_t* binmedint, const int32_t* status, int64_t nb, int64_t ncompact, double RDmedian,
+                              const rsi_params* P, rsi_call* segs, int nsegs, int use_tester, int sparse, int32_t* road, int32_t* info) {
+  if (!ctx || !binmedint || !status || !segs || nsegs < 1 || nb < 1 || ncompact < 1 || ncompact >= (1ll << 31) || !list_params_ok(P, RDmedian, nb))
+    return fail(ctx, RSI_ERR_BAD_ARG, "bad argument");
+  for (int64_t i = 0; i < nb; ++i) if (binmedint[i] < 0) return fail(ctx, RSI_ERR_BAD_ARG, "a negative bin median");
+  std::vector<Candidate> L((size_t)nsegs);
+  for (int i = 0; i < nsegs; ++i) {
+    if (segs[i].start < 0 || segs[i].end < segs[i].start || segs[i].end >= nb) return fail(ctx, RSI_ERR_BAD_ARG, "a segment must lie inside the bins, start <= end");
+    if (segs[i].type != rsih::kDel && segs[i].type != rsih::kDup) return fail(ctx, RSI_ERR_BAD_ARG, "a segment's type must be DEL or DUP");
+    L[(size_t)i] = list_in(segs[i]);
+  }
+  // the sparse form as the scan leaves it (rsi_segments): the values inside the marked runs, run after run, and where each run starts
+  std::vector<int> run_status;
+  std::vector<rsih::IntSpan::Range> run_ranges;
+  if (sparse) {
+    for (int64_t i = 0; i < nb;) {
+      if (status[i] == 0) { ++i; continue; }
+      int64_t j = i;
+      while (j + 1 < nb && status[j + 1] != 0) ++j;
+      run_ranges.push_back({i, j, (int64_t)run_status.size()});
+      run_status.insert(run_status.end(), status + i, status + j + 1);
+      i = j + 1;
+    }
+    if (run_ranges.empty()) return fail(ctx, RSI_ERR_BAD_ARG, "the sparse form needs a marked run");
+  }
+  DepthRef ref;
+  int rc;
+  if ((rc = debug_depth_upload(ctx, binmedint, nb, 4, &ref)) != RSI_OK) return rc;
+  rsih::CallerInput in{};
+  in.P = *P;
+  in.RDmedian = RDmedian; in.RDsd = 0; in.ncompact = ncompact; in.noncode = nullptr;
+  in.binmedint = rsih::IntSpan(binmedint, nb);
+  rsih::CallProfile prof;
+  int short_neighbourhoods = 0;
+  std::vector<int> roads;
+  in.prof = &prof; in.short_neighbourhoods = &short_neighbourhoods; in.block_roads = &roads;
+  DeviceTester tester(ctx, ref, nb, RDmedian);
+  tester.force_split = 1; tester.force_bytes = 1;   // what a run takes by default, whatever the environment says
+  in.block_tester = use_tester ? &tester : nullptr;
+  const rsih::IntSpan st = sparse ? rsih::IntSpan(run_status.data(), nb, &run_ranges) : rsih::IntSpan(status, nb);
+  rsih::test_block_segments(in, st, L);
+  if (tester.failed) return RSI_ERR_HIP;
+  if (short_neighbourhoods) return fail(ctx, RSI_ERR_UNSUPPORTED, "a segment longer than the neighbourhood left around it");
+  int32_t count = 0;
+  list_out(L, segs, &count);
+  if (road) for (int i = 0; i < nsegs; ++i) road[i] = roads[(size_t)i];
+  list_info(prof, tester.launches, info);
+  return RSI_OK;
+}
+
+// The per-base list of the merge and the calls hook: inside the array, DEL or DUP.
+static int base_list(rsi_ctx* ctx, const rsi_call* list, int nlist, int64_t n, std::vector<Candidate>& L) {
+  L.resize((size_t)nlist);
+  for (int i = 0; i < nlist; ++i) {
+    if (list[i].start < 0 || list[i].end < list[i].start || list[i].end >= n) return fail(ctx, RSI_ERR_BAD_ARG, "a candidate must lie inside the array, start <= end");
+    if (list[i].type != rsih::kDel && list[i].type != rsih::kDup) return fail(ctx, RSI_ERR_BAD_ARG, "a candidate's type must be DEL or DUP");
+    L[(size_t)i] = list_in(list[i]);
+  }
+  return RSI_OK;
+}
+
+// Test hook: mergesegments over a host array (include/rsi_hot.h): rsih::debug_merge_neighbours with the production DeviceTester.
+int rsi_hot_debug_merge(rsi_ctx* ctx, const int32_t* depth, int64_t n, int storage, double RDmedian, const rsi_params* P, const rsi_call* list,
+                        int nlist, int use_tester, rsi_call* out, int32_t* nout, int32_t* info) {
+  if (!ctx || !depth || !list || !out || !nout || nlist < 1 || n < 1 || !list_params_ok(P, RDmedian, n)) return fail(ctx, RSI_ERR_BAD_ARG, "bad argument");
+  for (int64_t i = 0; i < n; ++i) if (depth[i] < 0) return fail(ctx, RSI_ERR_BAD_ARG, "a negative depth");
+  std::vector<Candidate> L;
+  int rc;
+  if ((rc = base_list(ctx, list, nlist, n, L)) != RSI_OK) return rc;
+  DepthRef ref;
+  if ((rc = debug_depth_upload(ctx, depth, n, storage, &ref)) != RSI_OK) return rc;
+  rsih::CallerInput in{};
+  in.P = *P;
+  in.RDmedian = RDmedian; in.RDsd = 0; in.ncompact = n; in.noncode = nullptr;
+  rsih::CallProfile prof;
+  int short_neighbourhoods = 0;
+  in.prof = &prof; in.short_neighbourhoods = &short_neighbourhoods;
+  DeviceTester tester(ctx, ref, n, RDmedian);
+  tester.force_split = 1; tester.force_bytes = 1;   // what a run takes by default, whatever the environment says
+  in.tester = use_tester ? &tester : nullptr;
+  rsih::DepthPager pager(depth, n);
+  rsih::debug_merge_neighbours(in, pager, L);
+  if (tester.failed) return RSI_ERR_HIP;
+  if (short_neighbourhoods) return fail(ctx, RSI_ERR_UNSUPPORTED, "a candidate longer than the neighbourhood left around it");
+  list_out(L, out, nout);
+  list_info(prof, tester.launches, info);
+  return RSI_OK;
+}
+
+// Test hook: detectcnv behind the block tests and sd_filters over a host array (include/rsi_hot.h): rsih::call_from_segments.
+int rsi_hot_debug_calls(rsi_ctx* ctx, const int32_t* depth, int64_t n, int storage, double RDmedian, double RDsd, const rsi_params* P,
+                        const rsi_call* segs, int nsegs, const int32_t* noncode_start, const int32_t* noncode_end, int nnoncode, int use_tester,
+                        rsi_call* blocks, rsi_call* raw, rsi_call* kept, int32_t* counts, int32_t* info) {
+  if (!ctx || !depth || !segs || !blocks || !raw || !kept || !counts || nsegs < 1 || n < 1 || nnoncode < 0 || (nnoncode > 0 && (!noncode_start || !noncode_end)) ||
+      !(RDsd == RDsd) || !list_params_ok(P, RDmedian, n))
+    return fail(ctx, RSI_ERR_BAD_ARG, "bad argument");
+  for (int64_t i = 0; i < n; ++i) if (depth[i] < 0) return fail(ctx, RSI_ERR_BAD_ARG, "a negative depth");
+  std::vector<Candidate> S((size_t)nsegs);
+  for (int i = 0; i < nsegs; ++i) {   // bin space: a segment's first base must exist
+    if (segs[i].start < 0 || segs[i].end < segs[i].start || (int64_t)segs[i].start * P->m + P->m / 2 > n - 1 || (int64_t)segs[i].end * P->m + P->m / 2 >= (1ll << 31))
+      return fail(ctx, RSI_ERR_BAD_ARG, "a segment must start inside the array, start <= end");
+    if (segs[i].type != rsih::kDel && segs[i].type != rsih::kDup) return fail(ctx, RSI_ERR_BAD_ARG, "a segment's type must be DEL or DUP");
+    S[(size_t)i] = list_in(segs[i]);
+  }
+  std::vector<Region> noncode((size_t)nnoncode);
+  for (int i = 0; i < nnoncode; ++i) {
+    if (noncode_start[i] < 0 || noncode_end[i] <= noncode_start[i] || (i > 0 && noncode_start[i] <= noncode_end[i - 1]))   // (rsi.cpp:1532: the reference exits on end <= start)
+      return fail(ctx, RSI_ERR_BAD_ARG, "the regions must be sorted, disjoint and longer than one base");
+    noncode[(size_t)i] = Region{noncode_start[i], noncode_end[i]};
+  }
+  DepthRef ref;
+  int rc;
+  if ((rc = debug_depth_upload(ctx, depth, n, storage, &ref)) != RSI_OK) return rc;
+  rsih::CallerInput in{};
+  in.P = *P;
+  in.RDmedian = RDmedian; in.RDsd = RDsd; in.ncompact = n; in.noncode = &noncode;
+  rsih::CallProfile prof;
+  int short_neighbourhoods = 0;
+  in.prof = &prof; in.short_neighbourhoods = &short_neighbourhoods;
+  DeviceTester tester(ctx, ref, n, RDmedian);
+  tester.force_split = 1; tester.force_bytes = 1;   // what a run takes by default, whatever the environment says
+  in.tester = use_tester ? &tester : nullptr;
+  rsih::DepthPager pager(depth, n);
+  std::vector<Candidate> B, R, K;
+  rsih::call_from_segments(in, S, pager, B, R, K);
+  if (tester.failed) return RSI_ERR_HIP;
+  if (short_neighbourhoods) return fail(ctx, RSI_ERR_UNSUPPORTED, "a candidate longer than the neighbourhood left around it");
+  list_out(B, blocks, &counts[0]);
+  list_out(R, raw, &counts[1]);
+  list_out(K, kept, &counts[2]);
+  list_info(prof, tester.launches, info);
+  return RSI_OK;
+}
+
 // ---- `geno` (include/rsi_hot.h) ----
 // The statistics of `lines` over the compacted depth d_depth[ncompact] (storage 1: bytes, 4: int32) through the kernels of
 // kernels_geno.hip; what rsi_hot_geno_calls, rsi_hot_debug_geno and the plot data (plot.hip) share.  The caller has entered the

@@ -24,7 +24,8 @@ def test_every_declared_symbol_is_exported(hotlib):
     assert set(api.EXPORTS) <= set(names)
     assert "rsi_hot_debug_per_base" in names and "rsi_hot_debug_per_base" in api.EXPORTS
     for hook in ("rsi_hot_debug_segments", "rsi_hot_debug_sharpen", "rsi_hot_debug_nb_transform", "rsi_hot_debug_filterstatus",
-                 "rsi_hot_debug_candidate_tests", "rsi_hot_debug_range_sums"):
+                 "rsi_hot_debug_candidate_tests", "rsi_hot_debug_range_sums", "rsi_hot_debug_block_stage", "rsi_hot_debug_merge",
+                 "rsi_hot_debug_calls"):
         assert hook in names and hook in api.EXPORTS
 
 

@@ -810,6 +810,17 @@ int rsi_hot_debug_grid_median(rsi_ctx* ctx, const float* x, const int32_t* mask,
 /* Mode 3 of the same hook, -MED's form: the int32 bin medians x[nb] become floats in the kernel that also plans the MAD's grid
  * around `center`, then the MAD's chain. */
 int rsi_hot_debug_grid_mad_i32(rsi_ctx* ctx, const int32_t* x, int64_t nb, double center, double* out, int32_t* info);
+/* Test hook: the keyed form of the NB transform and of its two quantile chains, over the HOST bin sums binsum[nb]: every statistic
+ * comes from the histogram of the sums (K possible sums, 0 .. K - 1; bins 0..2 apart), T from the table of their values -- through the
+ * functions a run calls.  mask == NULL: the transform and the (median, MAD) pair of all bins, as in front of the first scan pass;
+ * mask != NULL: after them the pair of the bins with mask[b] == 0, as in front of the second.  nb >= 3, r > 0.
+ * T[nb]: the transformed bins.  out[4] = median, its count, MAD, its count (of the masked selection where a mask is given).
+ * info[8] = the flags and bucket count of the median record, the same of the MAD record (-1 and 0: no record), the raw minimum as
+ * float bits, the form taken (1: keyed; 0: a bin sum lay outside [0, K), the keyed launch declined and the chain of launches ran; -1:
+ * the route does not apply -- K above 2^15 or nb < 8 -- and nothing ran), the number of host-driven medians, 0.
+ * A non-finite value fails with RSI_ERR_UNSUPPORTED.  Overwrites the bin arrays the rsi_hot_fetch_* calls read. */
+int rsi_hot_debug_nb_keyed(rsi_ctx* ctx, const int64_t* binsum, const int32_t* mask, int64_t nb, int m, int64_t K, double RDmedian, double r,
+                           float* T, double* out, int32_t* info);
 
 /* Test hook: the classification alone, at any length: fasta[n] is uploaded and classified (K1), the intervals -- taken as
  * rsi_hot_set_exclude takes them -- are applied by the mask kernel when count > 0, and the two planes come back: n/64 + 1 words

@@ -81,7 +81,7 @@ EXPORTS = ["rsi_default_params", "rsi_hot_create", "rsi_hot_destroy", "rsi_hot_l
            "rsi_hot_run_device", "rsi_hot_load_depth_text", "rsi_hot_run_text", "rsi_hot_load_depth_bam", "rsi_hot_run_bam", "rsi_bam_references", "rsi_result_annotate_bam", "rsi_result_summary", "rsi_summary_format_row", "rsi_summary_format_rows", "rsi_result_pairs", "rsi_result_ncalls", "rsi_result_calls", "rsi_result_stats", "rsi_result_noncode",
            "rsi_result_format_row", "rsi_result_free", "rsi_hot_fetch_i32", "rsi_hot_fetch_f32", "rsi_hot_fetch_i64",
            "rsi_hot_kernel_times", "rsi_hot_phase_times", "rsi_hot_set_timing", "rsi_hot_process_setup", "rsi_pool_create", "rsi_pool_destroy", "rsi_pool_workers", "rsi_pool_hw_queues", "rsi_pool_worker",
-           "rsi_pool_set_timing", "rsi_pool_set_timing_kernel", "rsi_hot_set_timing_kernel", "rsi_pool_set_schedule", "rsi_pool_last_error", "rsi_pool_run", "rsi_pool_run_host", "rsi_pool_submit", "rsi_pool_wait", "rsi_plot_expand", "rsi_plot_write_files", "rsi_result_log_line", "rsi_hot_debug_level_sums", "rsi_hot_debug_scan", "rsi_hot_debug_segments", "rsi_hot_debug_sharpen", "rsi_hot_debug_candidate_tests", "rsi_hot_debug_range_sums", "rsi_hot_debug_block_stage", "rsi_hot_debug_merge", "rsi_hot_debug_calls", "rsi_hot_debug_nb_transform", "rsi_hot_debug_filterstatus", "rsi_hot_debug_grid_median", "rsi_hot_debug_grid_mad_i32", "rsi_synth_generate_host", "rsi_synth_generate_device", "rsi_synth_write_depth_text", "rsi_synth_write_fasta", "rsi_synth_append_genome_text",
+           "rsi_pool_set_timing", "rsi_pool_set_timing_kernel", "rsi_hot_set_timing_kernel", "rsi_pool_set_schedule", "rsi_pool_last_error", "rsi_pool_run", "rsi_pool_run_host", "rsi_pool_submit", "rsi_pool_wait", "rsi_plot_expand", "rsi_plot_write_files", "rsi_result_log_line", "rsi_hot_debug_level_sums", "rsi_hot_debug_scan", "rsi_hot_debug_segments", "rsi_hot_debug_sharpen", "rsi_hot_debug_candidate_tests", "rsi_hot_debug_range_sums", "rsi_hot_debug_block_stage", "rsi_hot_debug_merge", "rsi_hot_debug_calls", "rsi_hot_debug_nb_transform", "rsi_hot_debug_nb_keyed", "rsi_hot_debug_filterstatus", "rsi_hot_debug_grid_median", "rsi_hot_debug_grid_mad_i32", "rsi_synth_generate_host", "rsi_synth_generate_device", "rsi_synth_write_depth_text", "rsi_synth_write_fasta", "rsi_synth_append_genome_text",
            "rsi_genome_text_open", "rsi_genome_text_next", "rsi_genome_text_release", "rsi_genome_text_copy_depth",
            "rsi_genome_text_kernel_ms", "rsi_genome_text_close", "rsi_genome_text_last_error", "rsi_hot_run_depth_device",
            "rsi_hot_last_inflate_stats", "rsi_hot_inflate_bgzf", "rsi_genome_text_inflate_stats",
@@ -892,6 +892,23 @@ class RsiHot:
         self._check(self.lib.rsi_hot_debug_nb_transform(self.ctx, b.ctypes.data, b.size, int(m), int(ncompact), float(RDmedian), float(r),
                                                         raw.ctypes.data, T.ctypes.data, info.ctypes.data))
         return raw, T, info
+
+    def debug_nb_keyed(self, binsum, m, K, RDmedian, r, mask=None):
+        """The keyed form of the NB transform and its quantile chains over host bin sums (test hook, include/rsi_hot.h): (T, out, info).
+        out = (median, count, MAD, count), of the bins with mask == 0 where a mask is given; info = flags and buckets of the median
+        record, the same of the MAD record, the raw minimum (float bits), the form (1 keyed, 0 declined to the chain, -1 the route
+        does not apply), host-driven medians, 0."""
+        b = np.ascontiguousarray(binsum, dtype=np.int64)
+        mk = None if mask is None else np.ascontiguousarray(mask, dtype=np.int32)
+        assert mk is None or mk.size == b.size
+        T = np.zeros(b.size, dtype=np.float32)
+        out = np.zeros(4, dtype=np.float64)
+        info = np.zeros(8, dtype=np.int32)
+        self.lib.rsi_hot_debug_nb_keyed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_double, C.c_double,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p]
+        self._check(self.lib.rsi_hot_debug_nb_keyed(self.ctx, b.ctypes.data, None if mk is None else mk.ctypes.data, b.size, int(m), int(K),
+                                                    float(RDmedian), float(r), T.ctypes.data, out.ctypes.data, info.ctypes.data))
+        return T, out, info
 
     def debug_filterstatus(self, T, status, Lmax, dev):
         """filterstatus behind a scan pass over host arrays on the device (test hook): (status_out, info).  info = runs after the last

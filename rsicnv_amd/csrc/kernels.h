@@ -264,7 +264,8 @@ struct MinMaxF { uint32_t min_inv, max_bits; unsigned int nonfinite; unsigned in
 // The whole median as a chain of two launches (min/max + grid plan by the last workgroup -> histogram + walk by the last
 // workgroup); `out` receives the result, or the flag of the first test that failed.
 struct GridMedian { double med, ymin; unsigned long long count; uint32_t np, flags; };
-enum { kGridEmpty = 1, kGridNonFinite = 2, kGridDegenerate = 4, kGridTooWide = 8 };
+enum { kGridEmpty = 1, kGridNonFinite = 2, kGridDegenerate = 4, kGridTooWide = 8,
+       kGridDeclined = 16 /* the keyed form met a bin sum outside its table: the chain of launches follows (launch_nb_keys) */ };
 // Shared state of a context's chains: mm holds "nothing seen" (all zero) before a chain and again after it; hist has cap
 // entries; counters: two arrival counters (plan, walk), zero before and after.
 struct GridChain { MinMaxF* mm; uint32_t* hist; uint32_t cap; unsigned int* counters; };
@@ -296,6 +297,22 @@ void launch_hist_walk(const float* x, const int32_t* mask, int64_t nb, int use_a
                       const GridChain& c, GridMedian* out, const GridExport* ex, const FillList* fill, hipStream_t stream);
 // whether launch_hist_walk counts nb values with 16-bit LDS counters (else 32-bit)
 bool hist_walk_pack16(int64_t nb);
+
+// ---- K5 + K6 from the histogram of the bin sums (the "keyed" form) ----
+// The NB value of a whole bin is a function of its integer sum, so the transformed array's minimum, both 0.01 grids, their bucket
+// counts and the walks to the median and the MAD follow from H[sum] alone.  launch_nb_keys counts the sums in [0, K) of the bins
+// with mask[b] == 0 (mask NULL: all), bins 0..2 apart (they hold the three levels, not their sums' values); its last workgroup
+// evaluates the chain's expressions once per occupied sum and leaves the two GridMedian records at g[0], g[1] and the export exactly
+// as launch_nb_scale_minmax + launch_hist_walk + launch_minmax_plan + launch_hist_walk would.  Without a mask it also finds the raw
+// minimum (*rawmin_bits) and writes the table tval[sum] (tval[K + b]: the level of bin b < 3); with one it reads that table.
+// launch_nb_apply then writes T[b] = tval[binsum[b]].  A sum outside [0, K): g[0].flags = kGridDeclined and nothing else is valid.
+// ws: nb_keys_workspace_bytes() bytes, zero before the first launch (the kernels leave its counters zero again).
+constexpr int64_t kNbKeyMax = 1 << 15;   // the widest table (pipeline_steps.h: nb_keyed_applies)
+size_t nb_keys_workspace_bytes();
+void launch_nb_keys(const int64_t* binsum, const int32_t* mask, int64_t nb, int m, int64_t K, double r, double med_raw, double del_raw,
+                    double dup_raw, double RDmedian, void* ws, uint32_t* rawmin_bits, const GridChain& c, GridMedian* g,
+                    const GridExport* ex, const FillList* fill, hipStream_t stream);
+void launch_nb_apply(const int64_t* binsum, int64_t nb, int64_t K, const void* ws, float* T, const FillList* fill, hipStream_t stream);
 
 // ---- K7: RSI scan (rsistatus, rsi.cpp:1191-1259; runmeantp wufunctions.cpp:573-647) ----
 struct ScanParams {

@@ -32,6 +32,35 @@ __device__ inline uint32_t f32_key(float f) {
 
 // ------------------------------------------------------------------------------------------
 // K5  NB transform (rsi.cpp:1155-1162): the formula, then the running minimum.
+// The per-bin expressions, shared by the array kernels (k_nb_raw, k_nb_scale_mm, the quantile kernels) and by the keyed form
+// (k_nb_keys), which evaluates them once per distinct bin sum: the same functions, so the same floats.
+__device__ __forceinline__ float nb_raw_value(double sum, double m2, double r) {
+  const double q = (sum + 0.25) / (m2 * r - 0.5);
+  const double t = 2.0 * sqrt(r) * log(sqrt(q) + sqrt(1.0 + q));
+  return (float)t;
+}
+// rsi.cpp:1176-1185: the scalars of the scaling from the raw minimum (complemented order key) and the host's three raw levels
+struct NbLevels { double med_raw, del_raw, dup_raw, RDmedian; };
+struct NbScale { double tmin, med_nbt, RDmedian; float lev[3]; };
+__device__ __forceinline__ NbScale nb_scale_constants(uint32_t rawmin_inv, const NbLevels& lv) {
+  const uint32_t key = ~rawmin_inv;
+  NbScale s;
+  s.tmin = (double)__uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key);
+  s.med_nbt = lv.med_raw - s.tmin;
+  s.RDmedian = lv.RDmedian;
+  const double del_s = (lv.del_raw - s.tmin) / s.med_nbt * lv.RDmedian, dup_s = (lv.dup_raw - s.tmin) / s.med_nbt * lv.RDmedian;
+  const double med_s = s.med_nbt / s.med_nbt * lv.RDmedian;
+  s.lev[0] = (float)del_s; s.lev[1] = (float)dup_s; s.lev[2] = (float)med_s;
+  return s;
+}
+__device__ __forceinline__ float nb_scaled_value(float raw, const NbScale& s) {
+  const float v = (float)((double)raw - s.tmin);
+  return (float)((double)v / s.med_nbt * s.RDmedian);
+}
+// RDtmp[i] = abs(RDtrans[i]-tmedian), rsi.cpp:1276
+__device__ __forceinline__ float abs_dev_value(float v, double center) { return (float)fabs((double)v - center); }
+__device__ __forceinline__ bool f32_out_of_range(float v) { return !(fabsf(v) <= 3.0e38f); }
+
 __global__ __launch_bounds__(kThreads) void k_nb_raw(const int64_t* __restrict__ binsum, int64_t nb, int m,
                                                      int64_t ncompact, double r, float* __restrict__ raw,
                                                      uint32_t* __restrict__ rawmin_key) {
@@ -41,10 +70,7 @@ __global__ __launch_bounds__(kThreads) void k_nb_raw(const int64_t* __restrict__
     int64_t i2 = b * m + m - 1;
     if (i2 > ncompact - 1) i2 = ncompact - 1;
     const double m2 = (double)(i2 - i1 + 1);
-    const double sum = (double)binsum[b];
-    const double q = (sum + 0.25) / (m2 * r - 0.5);
-    const double t = 2.0 * sqrt(r) * log(sqrt(q) + sqrt(1.0 + q));
-    const float f = (float)t;
+    const float f = nb_raw_value((double)binsum[b], m2, r);
     raw[b] = f;
     const uint32_t k = f32_key(f);
     kmin = k < kmin ? k : kmin;
@@ -65,7 +91,7 @@ __global__ __launch_bounds__(kThreads) void k_nb_raw(const int64_t* __restrict__
 // K6  quantile histograms of float arrays on the 0.01 grid (partition_stat_tp, wufunctions.cpp:364-424)
 __device__ inline float sel_value(const float* __restrict__ x, int64_t i, int use_abs, double center) {
   const float v = x[i];
-  return use_abs ? (float)fabs((double)v - center) : v;   // RDtmp[i] = abs(RDtrans[i]-tmedian), rsi.cpp:1276
+  return use_abs ? abs_dev_value(v, center) : v;
 }
 
 __device__ __forceinline__ void minmax_body(const float* __restrict__ x, const int32_t* __restrict__ mask, int64_t nb,
@@ -108,6 +134,12 @@ constexpr uint32_t kLdsBins = 12288;   // 48 KB of LDS counters: covers a value 
 // one-atomic-per-element histogram serialises on it (271 ms per 3 Gb step with global atomics).
 constexpr int kHistRun = 8;
 
+__device__ __forceinline__ uint32_t grid_bucket(float v, double ymin, uint32_t np) {
+  const double idx = ((double)v - ymin) / 0.01 + 0.5;        // wufunctions.cpp:396
+  const uint32_t k = (uint32_t)(unsigned long long)idx;
+  return k >= np ? np - 1 : k;                               // cannot happen (np = range/dy + 2)
+}
+
 // PACK16: two 16-bit LDS counters to a word (half the LDS: the kernel then fits beside four resident per-base workgroups
 // instead of waiting for one to leave); the caller guarantees that a workgroup counts fewer than 65536 values in all.
 template <bool PACK16 = false>
@@ -116,11 +148,7 @@ __device__ __forceinline__ void hist_body(const float* __restrict__ x, const int
                                           unsigned int* s_h) {
   const uint32_t nl = use_lds ? (np < (uint32_t)use_lds ? np : (uint32_t)use_lds) : 0;   // buckets counted in LDS (use_lds = how many fit)
   auto lds_add = [&](uint32_t k, uint32_t c) { if (PACK16) atomicAdd(&s_h[k >> 1], c << ((k & 1u) << 4)); else atomicAdd(&s_h[k], c); };
-  auto bucket = [&](float v) {
-    const double idx = ((double)v - ymin) / 0.01 + 0.5;        // wufunctions.cpp:396
-    uint32_t k = (uint32_t)(unsigned long long)idx;
-    return k >= np ? np - 1 : k;                               // cannot happen (np = range/dy + 2)
-  };
+  auto bucket = [&](float v) { return grid_bucket(v, ymin, np); };
   // Which nl buckets live in LDS: [wb, wb + nl).  A grid longer than that (values spread over more than 122: deep coverage --
   // at 300x every bin's value lay beyond the first 12 288 buckets and took a global atomic, 280 us per launch instead of 40)
   // gets its window around the median of 64 values sampled across the array; every workgroup samples the same positions.
@@ -148,7 +176,7 @@ __device__ __forceinline__ void hist_body(const float* __restrict__ x, const int
     uint32_t pend_k = 0xffffffffu, pend_c = 0;
     const int64_t i0 = c * kHistRun, i1 = i0 + kHistRun < nb ? i0 + kHistRun : nb;
     auto one = [&](float xv) {
-      const float v = use_abs ? (float)fabs((double)xv - center) : xv;   // sel_value
+      const float v = use_abs ? abs_dev_value(xv, center) : xv;   // sel_value
       const uint32_t k = bucket(v);
       if (k != pend_k) {
         if (pend_c) count(pend_k, pend_c);
@@ -199,8 +227,8 @@ __device__ inline float f32_unkey(uint32_t k) { return __uint_as_float((k & 0x80
 
 // one workgroup, after every min/max atomic of the launch has landed: anchor and bucket count -> *g, buckets cleared,
 // the min/max record back to "nothing seen"
-__device__ inline void grid_plan_block(MinMaxF* __restrict__ mm, uint32_t cap, uint32_t* __restrict__ hist, GridMedian* __restrict__ g) {
-  const uint32_t kmin = ~ld_cg(&mm->min_inv), kmax = ld_cg(&mm->max_bits), bad = ld_cg(&mm->nonfinite);
+struct GridPlan { uint32_t flags, np; double ymin; };
+__device__ __forceinline__ GridPlan grid_plan_values(uint32_t kmin, uint32_t kmax, uint32_t bad, uint32_t cap) {
   uint32_t flags = 0, np = 0;
   double ymin = 0.0;
   if (kmin == 0xffffffffu) flags = kGridEmpty;
@@ -214,6 +242,13 @@ __device__ inline void grid_plan_block(MinMaxF* __restrict__ mm, uint32_t cap, u
       if (n > cap) flags = kGridTooWide; else np = (uint32_t)n;
     }
   }
+  return GridPlan{flags, np, ymin};
+}
+__device__ inline void grid_plan_block(MinMaxF* __restrict__ mm, uint32_t cap, uint32_t* __restrict__ hist, GridMedian* __restrict__ g) {
+  const uint32_t kmin = ~ld_cg(&mm->min_inv), kmax = ld_cg(&mm->max_bits), bad = ld_cg(&mm->nonfinite);
+  const GridPlan pl = grid_plan_values(kmin, kmax, bad, cap);
+  const uint32_t flags = pl.flags, np = pl.np;
+  const double ymin = pl.ymin;
   for (uint32_t e = threadIdx.x; e < np; e += kThreads) hist[e] = 0;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -247,7 +282,7 @@ __global__ __launch_bounds__(kThreads) void k_minmax_plan(const float* __restric
   uint32_t kmin = 0xffffffffu, kmax = 0;
   unsigned int bad = 0;
   auto one = [&](float xv) {
-    const float v = use_abs ? (float)fabs((double)xv - c) : xv;   // sel_value
+    const float v = use_abs ? abs_dev_value(xv, c) : xv;   // sel_value
     if (!(fabsf(v) <= 3.0e38f)) bad = 1;
     const uint32_t k = f32_key(v);
     kmin = k < kmin ? k : kmin;
@@ -285,11 +320,10 @@ struct ExportPair { const void* src[2]; void* dst[2]; unsigned int bytes[2]; };
 // 16-byte loads, eight in flight; the stretch in which the count crosses total/2 is then read once more by the whole workgroup,
 // a few buckets per thread.  (One load and one wait per bucket was 30 of this kernel's 37 us on a 30x chromosome -- 12 000
 // buckets of 0.01 -- and 300 us at 300x, where the values span ten times the range.)
-__device__ inline void grid_walk_block(const uint32_t* __restrict__ hist, GridMedian* __restrict__ g) {
+__device__ inline void grid_walk_block(const uint32_t* __restrict__ hist, GridMedian* __restrict__ g, const uint32_t np, const double ymin) {
   __shared__ unsigned long long s_sum[kThreads];
   __shared__ unsigned long long s_seen;
   __shared__ unsigned int s_cross;
-  const uint32_t np = g->np;
   const uint32_t chunk = (((np + kThreads - 1) / kThreads) + 3u) & ~3u;   // whole quads
   const uint32_t b0 = threadIdx.x * chunk < np ? threadIdx.x * chunk : np;
   const uint32_t b1 = b0 + chunk < np ? b0 + chunk : np;
@@ -315,7 +349,7 @@ __device__ inline void grid_walk_block(const uint32_t* __restrict__ hist, GridMe
   const unsigned long long r2 = total / 2;
   // agent-scope stores: the same workgroup reads the record back through ld_cg for the export
   unsigned long long* med_bits = reinterpret_cast<unsigned long long*>(&g->med);
-  if (threadIdx.x == 0) { st_cg(&g->count, total); if (r2 == 0) st_cg(med_bits, (unsigned long long)__double_as_longlong(g->ymin)); }
+  if (threadIdx.x == 0) { st_cg(&g->count, total); if (r2 == 0) st_cg(med_bits, (unsigned long long)__double_as_longlong(ymin)); }
   if (r2 != 0 && mine != 0 && seen < r2 && seen + mine >= r2) { s_cross = b0; s_seen = seen; }   // exactly one thread
   __syncthreads();
   const uint32_t cb = s_cross;
@@ -335,7 +369,7 @@ __device__ inline void grid_walk_block(const uint32_t* __restrict__ hist, GridMe
   if (part != 0 && run < r2 && run + part >= r2) {
     for (uint32_t bb = m0; bb < m1; ++bb) {
       const unsigned long long upto = run + ld_cg(hist + bb);
-      if (run < r2 && upto >= r2) st_cg(med_bits, (unsigned long long)__double_as_longlong(g->ymin + (double)bb * 0.01));
+      if (run < r2 && upto >= r2) st_cg(med_bits, (unsigned long long)__double_as_longlong(ymin + (double)bb * 0.01));
       run = upto;
     }
   }
@@ -354,7 +388,7 @@ __global__ __launch_bounds__(kThreads) void k_hist_walk(const float* __restrict_
     hist_body<PACK16>(x, mask, nb, use_abs, center_ptr ? *center_ptr : center, g->ymin, hist, np, (int)lds_bins, s_h);   // the first lds_bins buckets in LDS
   }
   if (!last_block_done(counter)) return;
-  if (!g->flags) grid_walk_block(hist, g);
+  if (!g->flags) grid_walk_block(hist, g, g->np, g->ymin);
   sync_drained();
   for (int k = 0; k < 2; ++k) export_words(ex.dst[k], ex.src[k], ex.bytes[k]);
 }
@@ -363,22 +397,15 @@ __global__ __launch_bounds__(kThreads) void k_hist_walk(const float* __restrict_
 // pass through, their min/max for the median that follows (the last workgroup derives that median's grid).
 // The scalars come from the raw minimum found by k_nb_raw and the three reference levels the host computed with its
 // own libm (no device log in them); the host repeats the same IEEE operations on the minimum it gets back.
-struct NbLevels { double med_raw, del_raw, dup_raw, RDmedian; };
 __global__ __launch_bounds__(kThreads) void k_nb_scale_mm(float* __restrict__ x, int64_t nb, const uint32_t* __restrict__ rawmin_inv,
                                                           NbLevels lv, MinMaxF* __restrict__ mm, unsigned int* __restrict__ counter,
                                                           uint32_t cap, uint32_t* __restrict__ hist, GridMedian* __restrict__ g) {
-  const uint32_t key = ~(*rawmin_inv);
-  const double tmin = (double)__uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key);
-  const double med_nbt = lv.med_raw - tmin;
-  const double del_s = (lv.del_raw - tmin) / med_nbt * lv.RDmedian, dup_s = (lv.dup_raw - tmin) / med_nbt * lv.RDmedian;
-  const double med_s = med_nbt / med_nbt * lv.RDmedian;
-  const float lev0 = (float)del_s, lev1 = (float)dup_s, lev2 = (float)med_s;
+  const NbScale sc = nb_scale_constants(*rawmin_inv, lv);
+  const float lev0 = sc.lev[0], lev1 = sc.lev[1], lev2 = sc.lev[2];
   uint32_t kmin = 0xffffffffu, kmax = 0;
   unsigned int bad = 0;
   for (int64_t b = (int64_t)blockIdx.x * kThreads + threadIdx.x; b < nb; b += (int64_t)gridDim.x * kThreads) {
-    float v = x[b];
-    v = (float)((double)v - tmin);
-    v = (float)((double)v / med_nbt * lv.RDmedian);
+    float v = nb_scaled_value(x[b], sc);
     if (b == 0) v = lev0;
     if (b == 1) v = lev1;
     if (b == 2) v = lev2;
@@ -409,6 +436,192 @@ __global__ __launch_bounds__(kThreads) void k_i32_to_f32_mm(const int32_t* __res
   }
   minmax_commit(kmin, kmax, bad, mm);
   if (last_block_done(counter)) grid_plan_block(mm, cap, hist, g);
+}
+
+// ------------------------------------------------------------------------------------------
+// K5 + K6 from the histogram of the bin sums.  Every workgroup counts the sums of a slice of bins: the first kKeyLds keys in LDS
+// (16-bit counters, two to a word: a slice has fewer than 65 536 bins), the keys behind and bins 0..2 (slots K, K + 1, K + 2)
+// through global atomics; the LDS counters are then added to the global ones.  The last workgroup gathers the occupied slots into a
+// list (a thousand or two at 30x) and runs the whole median -> MAD chain over it: each link is the array kernels' expressions per
+// occupied key, weighted with its count.  What it hands on inside the launch goes through st_cg / atomics and comes back through
+// ld_cg after sync_drained() (device_util.h); nothing is fenced.
+constexpr uint32_t kKeyLds = 16384;
+constexpr uint32_t kKeyPad = (uint32_t)kNbKeyMax + 8;   // slots per table: the keys, the three special bins, whole quads
+constexpr int64_t kKeySliceMax = 61440;
+struct NbKeyArgs {
+  const int64_t* binsum; const int32_t* mask; int64_t nb, slice;
+  int m; uint32_t K; double r; NbLevels lv;
+  uint32_t* keyhist; float* tval; uint32_t* occ_key; uint32_t* occ_cnt; uint32_t* occ_val; uint32_t* flag;
+  uint32_t* rawmin_inv; unsigned int* counter; uint32_t cap; uint32_t* hist; GridMedian* g;
+};
+
+// min / max / non-finite over the workgroup, the same in every thread
+__device__ inline void block_minmax(uint32_t& kmin, uint32_t& kmax, unsigned int& bad) {
+  __shared__ uint32_t s_bmin[kThreads / 64], s_bmax[kThreads / 64], s_bbad[kThreads / 64];
+  for (int d = 32; d >= 1; d >>= 1) {
+    const uint32_t a = __shfl_xor(kmin, d), b = __shfl_xor(kmax, d);
+    kmin = a < kmin ? a : kmin; kmax = b > kmax ? b : kmax; bad |= __shfl_xor(bad, d);
+  }
+  __syncthreads();   // the arrays' last readers are done
+  if (lane_id() == 0) { s_bmin[threadIdx.x >> 6] = kmin; s_bmax[threadIdx.x >> 6] = kmax; s_bbad[threadIdx.x >> 6] = bad; }
+  __syncthreads();
+  kmin = s_bmin[0]; kmax = s_bmax[0]; bad = s_bbad[0];
+  for (int w = 1; w < kThreads / 64; ++w) { kmin = s_bmin[w] < kmin ? s_bmin[w] : kmin; kmax = s_bmax[w] > kmax ? s_bmax[w] : kmax; bad |= s_bbad[w]; }
+}
+__device__ inline void grid_record_store(GridMedian* g, double med, double ymin, unsigned long long count, uint32_t np, uint32_t flags) {
+  unsigned long long* w = reinterpret_cast<unsigned long long*>(g);
+  static_assert(sizeof(GridMedian) == 32, "four 64-bit words");
+  st_cg(w + 0, (unsigned long long)__double_as_longlong(med));
+  st_cg(w + 1, (unsigned long long)__double_as_longlong(ymin));
+  st_cg(w + 2, count);
+  st_cg(w + 3, (unsigned long long)np | ((unsigned long long)flags << 32));
+}
+// One link of the chain over the list of n (value, count) pairs, by one workgroup: k_minmax_plan's tests, grid_plan_block's
+// record, hist_body's buckets, grid_walk_block's walk.
+__device__ inline void keyed_link(const uint32_t* occ_cnt, const uint32_t* occ_val, uint32_t n, int use_abs, double c, uint32_t cap,
+                                  uint32_t* hist, GridMedian* g) {
+  uint32_t kmin = 0xffffffffu, kmax = 0;
+  unsigned int bad = 0;
+  for (uint32_t i = threadIdx.x; i < n; i += kThreads) {
+    const float xv = __uint_as_float(ld_cg(occ_val + i));
+    const float v = use_abs ? abs_dev_value(xv, c) : xv;
+    if (f32_out_of_range(v)) bad = 1;
+    const uint32_t k = f32_key(v);
+    kmin = k < kmin ? k : kmin;
+    kmax = k > kmax ? k : kmax;
+  }
+  block_minmax(kmin, kmax, bad);
+  const GridPlan pl = grid_plan_values(kmin, kmax, bad, cap);
+  for (uint32_t e = threadIdx.x; e < pl.np; e += kThreads) st_cg(hist + e, 0u);
+  if (threadIdx.x == 0) grid_record_store(g, 0.0, pl.ymin, 0ull, pl.np, pl.flags);
+  sync_drained();
+  if (pl.flags) return;
+  for (uint32_t i = threadIdx.x; i < n; i += kThreads) {
+    const float xv = __uint_as_float(ld_cg(occ_val + i));
+    const float v = use_abs ? abs_dev_value(xv, c) : xv;
+    atomicAdd(&hist[grid_bucket(v, pl.ymin, pl.np)], ld_cg(occ_cnt + i));
+  }
+  sync_drained();
+  grid_walk_block(hist, g, pl.np, pl.ymin);
+  sync_drained();
+}
+
+template <bool MASKED>
+__global__ __launch_bounds__(kThreads) void k_nb_keys(NbKeyArgs a, ExportPair ex, FillList fill) {
+  __shared__ unsigned int s_k[kKeyLds / 2];
+  __shared__ unsigned int s_n;
+  fill_ranges(fill);   // for the kernels behind this one
+  const uint32_t K = a.K;
+  const uint32_t nl = K < kKeyLds ? K : kKeyLds;
+  for (uint32_t e = threadIdx.x; e < (nl + 1) / 2; e += kThreads) s_k[e] = 0;
+  __syncthreads();
+  {
+    const int64_t b0 = (int64_t)blockIdx.x * a.slice, b1 = b0 + a.slice < a.nb ? b0 + a.slice : a.nb;
+    unsigned int outside = 0;
+    auto one = [&](int64_t b, int64_t s) {
+      if (b < 3) { atomicAdd(&a.keyhist[K + (uint32_t)b], 1u); return; }
+      if (s < 0 || s >= (int64_t)K) { outside = 1; return; }
+      const uint32_t k = (uint32_t)s;
+      if (k < nl) atomicAdd(&s_k[k >> 1], 1u << ((k & 1u) << 4)); else atomicAdd(&a.keyhist[k], 1u);
+    };
+    int64_t b = b0 + threadIdx.x;
+    for (; b + 3 * kThreads < b1; b += 4 * kThreads) {   // four loads in flight
+      int64_t sv[4]; int mv[4] = {0, 0, 0, 0};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) sv[e] = a.binsum[b + e * kThreads];
+      if (MASKED) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) mv[e] = a.mask[b + e * kThreads];
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) if (mv[e] == 0) one(b + e * kThreads, sv[e]);
+    }
+    for (; b < b1; b += kThreads) {
+      if (MASKED && a.mask[b] != 0) continue;
+      one(b, a.binsum[b]);
+    }
+    if (outside) atomicOr(a.flag, 1u);
+  }
+  __syncthreads();
+  for (uint32_t e = threadIdx.x; e < nl; e += kThreads) {
+    const unsigned int c = (s_k[e >> 1] >> ((e & 1u) << 4)) & 0xffffu;
+    if (c) atomicAdd(&a.keyhist[e], c);
+  }
+  if (!last_block_done(a.counter)) return;
+
+  // ---- the last workgroup: occupied slots -> list, the counters back to zero ----
+  if (threadIdx.x == 0) s_n = 0;
+  __syncthreads();
+  const uint32_t declined = ld_cg(a.flag);
+  {
+    const uint32_t nq = (K + 3 + 3) / 4;   // whole quads: the slots behind K + 2 stay zero
+    const __amdgpu_buffer_rsrc_t rs = coherent_buffer(a.keyhist);
+    for (uint32_t q0 = threadIdx.x; q0 < nq; q0 += 4 * kThreads) {
+      u32x4 v[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { const uint32_t q = q0 + j * kThreads; v[j] = ld_cg_buf_x4(rs, (q < nq ? q : q0) * 16u, 0u); }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const uint32_t q = q0 + j * kThreads;
+        if (q >= nq) continue;
+        const unsigned int c[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          if (!c[e]) continue;
+          const uint32_t slot = atomicAdd(&s_n, 1u);
+          st_cg(a.occ_key + slot, q * 4u + e);
+          st_cg(a.occ_cnt + slot, c[e]);
+          st_cg(a.keyhist + q * 4u + e, 0u);
+        }
+      }
+    }
+  }
+  sync_drained();
+  const uint32_t n = s_n;
+  if (declined) {
+    if (threadIdx.x == 0) { grid_record_store(a.g, 0.0, 0.0, 0ull, 0u, kGridDeclined); grid_record_store(a.g + 1, 0.0, 0.0, 0ull, 0u, 0u); st_cg(a.flag, 0u); }
+  } else {
+    const double m2 = (double)a.m;
+    auto slot_sum = [&](uint32_t key) { return key < K ? (double)key : (double)a.binsum[key - K]; };
+    if (!MASKED) {
+      // the raw minimum over the occupied sums (bins 0..2 count with their sums' values), the scalars of the scaling, the table
+      uint32_t kmin = 0xffffffffu, kmax = 0;
+      unsigned int bad = 0;
+      for (uint32_t i = threadIdx.x; i < n; i += kThreads) {
+        const uint32_t k = f32_key(nb_raw_value(slot_sum(ld_cg(a.occ_key + i)), m2, a.r));
+        kmin = k < kmin ? k : kmin;
+      }
+      block_minmax(kmin, kmax, bad);
+      if (threadIdx.x == 0) st_cg(a.rawmin_inv, ~kmin);
+      const NbScale sc = nb_scale_constants(~kmin, a.lv);
+      for (uint32_t i = threadIdx.x; i < n; i += kThreads) {
+        const uint32_t key = ld_cg(a.occ_key + i);
+        const float v = key < K ? nb_scaled_value(nb_raw_value((double)key, m2, a.r), sc) : key == K ? sc.lev[0] : key == K + 1 ? sc.lev[1] : sc.lev[2];
+        a.tval[key] = v;   // for the kernels behind this one
+        st_cg(a.occ_val + i, __float_as_uint(v));
+      }
+    } else {
+      for (uint32_t i = threadIdx.x; i < n; i += kThreads) st_cg(a.occ_val + i, __float_as_uint(a.tval[ld_cg(a.occ_key + i)]));
+    }
+    sync_drained();
+    keyed_link(a.occ_cnt, a.occ_val, n, 0, 0.0, a.cap, a.hist, a.g);
+    const double med = __longlong_as_double((long long)ld_cg(reinterpret_cast<const unsigned long long*>(&a.g->med)));   // 0 where the record carries a flag
+    keyed_link(a.occ_cnt, a.occ_val, n, 1, med, a.cap, a.hist, a.g + 1);
+  }
+  sync_drained();
+  for (int k = 0; k < 2; ++k) export_words(ex.dst[k], ex.src[k], ex.bytes[k]);
+}
+
+__global__ __launch_bounds__(kThreads) void k_nb_apply(const int64_t* __restrict__ binsum, int64_t nb, uint32_t K, const float* __restrict__ tval,
+                                                       float* __restrict__ T, FillList fill) {
+  fill_ranges(fill);   // the scan's first-L arrays, its counters
+  for (int64_t b = (int64_t)blockIdx.x * kThreads + threadIdx.x; b < nb; b += (int64_t)gridDim.x * kThreads) {
+    const int64_t s = binsum[b];
+    float v = 0.0f;   // (a sum outside the table: the launch in front has declined, the chain rewrites T)
+    if (b < 3) v = tval[K + (uint32_t)b];
+    else if (s >= 0 && s < (int64_t)K) v = tval[s];
+    T[b] = v;
+  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1390,6 +1603,43 @@ void launch_hist_walk(const float* x, const int32_t* mask, int64_t nb, int use_a
   if (fill) f = *fill;
   if (pack16) RSI_LAUNCH(k_hist_walk<true>, dim3(grid), dim3(kThreads), lds, stream, x, mask, nb, use_abs, center, d_center, out, c.hist, c.counters + 1, e, f, bins);
   else { RSI_ALLOW_FULL_LDS(k_hist_walk<false>); RSI_LAUNCH(k_hist_walk<false>, dim3(grid), dim3(kThreads), lds, stream, x, mask, nb, use_abs, center, d_center, out, c.hist, c.counters + 1, e, f, bins); }
+}
+// the keyed form's workspace: counters | table | the occupied slots' keys, counts, values | the "sum outside the table" word
+size_t nb_keys_workspace_bytes() { return (size_t)(5 * kKeyPad + 4) * 4; }
+static NbKeyArgs nb_key_args(const int64_t* binsum, const int32_t* mask, int64_t nb, int m, int64_t K, double r, const NbLevels& lv, void* ws,
+                             uint32_t* rawmin_bits, const GridChain& c, GridMedian* g) {
+  uint32_t* w = static_cast<uint32_t*>(ws);
+  NbKeyArgs a{};
+  a.binsum = binsum; a.mask = mask; a.nb = nb;
+  // about 128 long-lived workgroups (each adds its occupied LDS counters to the global ones), never fewer than 1024 bins nor as many
+  // as 65 536 in one (the 16-bit counters)
+  a.slice = (((nb + 127) / 128) + 255) & ~int64_t(255);
+  if (a.slice < 1024) a.slice = 1024;
+  if (a.slice > kKeySliceMax) a.slice = kKeySliceMax;
+  a.m = m; a.K = (uint32_t)K; a.r = r; a.lv = lv;
+  a.keyhist = w; a.tval = reinterpret_cast<float*>(w + kKeyPad); a.occ_key = w + 2 * kKeyPad; a.occ_cnt = w + 3 * kKeyPad;
+  a.occ_val = w + 4 * kKeyPad; a.flag = w + 5 * kKeyPad;
+  a.rawmin_inv = rawmin_bits; a.counter = c.counters; a.cap = c.cap; a.hist = c.hist; a.g = g;
+  return a;
+}
+void launch_nb_keys(const int64_t* binsum, const int32_t* mask, int64_t nb, int m, int64_t K, double r, double med_raw, double del_raw,
+                    double dup_raw, double RDmedian, void* ws, uint32_t* rawmin_bits, const GridChain& c, GridMedian* g,
+                    const GridExport* ex, const FillList* fill, hipStream_t stream) {
+  if (K < 1 || K > kNbKeyMax || nb < 3) { if (tl_launch_error == hipSuccess) tl_launch_error = hipErrorInvalidValue; return; }
+  const NbKeyArgs a = nb_key_args(binsum, mask, nb, m, K, r, NbLevels{med_raw, del_raw, dup_raw, RDmedian}, ws, rawmin_bits, c, g);
+  const int grid = (int)((nb + a.slice - 1) / a.slice);
+  ExportPair e{};
+  if (ex) for (int k = 0; k < 2; ++k) { e.src[k] = ex->src[k]; e.dst[k] = ex->dst[k]; e.bytes[k] = (unsigned int)ex->bytes[k]; }
+  FillList f{};
+  if (fill) f = *fill;
+  if (mask) RSI_LAUNCH(k_nb_keys<true>, dim3(grid), dim3(kThreads), 0, stream, a, e, f);
+  else RSI_LAUNCH(k_nb_keys<false>, dim3(grid), dim3(kThreads), 0, stream, a, e, f);
+}
+void launch_nb_apply(const int64_t* binsum, int64_t nb, int64_t K, const void* ws, float* T, const FillList* fill, hipStream_t stream) {
+  FillList f{};
+  if (fill) f = *fill;
+  RSI_LAUNCH(k_nb_apply, dim3(bounded_grid(nb, kThreads * 4, 512)), dim3(kThreads), 0, stream, binsum, nb, (uint32_t)K,
+             reinterpret_cast<const float*>(static_cast<const uint32_t*>(ws) + kKeyPad), T, f);
 }
 constexpr int kGTileGrid = 256;   // workgroups of the device-memory-tile form (one workspace slice each) ...
 constexpr size_t kGTileBudget = size_t(8) << 30;   // ... fewer where 256 slices would take more than this (Lmax beyond 300 000)

@@ -156,6 +156,42 @@ int grid_pair_issue(rsi_ctx* ctx, const float* d_x, const int32_t* d_mask, int64
   *out = slot;
   return RSI_OK;
 }
+// The keyed form of the transform and a (median, MAD) pair (kernels.h: launch_nb_keys): what nb_transform + grid_pair_issue leave --
+// T in ctx->tnb, the two records, the raw minimum, the mailbox record, the cleared ranges of scan pass `fill_pass` -- from the
+// histogram of the bin sums.  Without a mask: two launches (the histogram and its chain, then T from the table); with one (the
+// second pass' parameters over the unmarked bins): one launch.  K = 0: the route does not apply (pipeline_steps.h).
+static_assert(rsih::kNbKeyLimit == kNbKeyMax, "the route's limit is the kernels' table size");
+struct NbKeyed { int64_t K = 0; const int64_t* d_binsum = nullptr; int m = 0; int64_t ncompact = 0; double r = 0, RDmedian = 0; rsih::NbLevels lev{0, 0, 0}; };
+int nb_keyed_issue(rsi_ctx* ctx, const NbKeyed& kd, const int32_t* d_mask, int64_t nb, int fill_pass, ChainOut** out) {
+  uint8_t* small = ctx->small.as<uint8_t>();
+  GridMedian* d_g = reinterpret_cast<GridMedian*>(small + kOffGrid);
+  hipStream_t st = ctx->stream;
+  HIPCHK(ctx->tnb.ensure((size_t)nb * 4));
+  HIPCHK(ctx->hist_f.ensure((size_t)kGridCap * 4));
+  const bool fresh = ctx->nb_keys.p == nullptr;
+  HIPCHK(ctx->nb_keys.ensure(nb_keys_workspace_bytes()));
+  if (fresh) HIPCHK(hipMemsetAsync(ctx->nb_keys.p, 0, nb_keys_workspace_bytes(), st));
+  ChainOut* slot = static_cast<ChainOut*>(mb_alloc(ctx, sizeof(ChainOut)));
+  if (!slot) return fail(ctx, RSI_ERR_INTERNAL, "out of pinned mailbox memory");
+  memset(slot, 0, sizeof(*slot));
+  GridExport ex{};
+  ex.src[0] = d_g; ex.dst[0] = slot->g; ex.bytes[0] = 2 * sizeof(GridMedian);
+  ex.src[1] = small + kOffRawMin; ex.dst[1] = &slot->rawmin_inv; ex.bytes[1] = 4;
+  FillList fl{};
+  if (fill_pass >= 0) scan_fill_list(ctx, fill_pass, nb, fl);
+  uint32_t* d_rawmin = reinterpret_cast<uint32_t*>(small + kOffRawMin);
+  GateShared gs(ctx);
+  if (!d_mask) {
+    { Timer t(ctx, "nb_keys"); launch_nb_keys(kd.d_binsum, nullptr, nb, kd.m, kd.K, kd.r, kd.lev.med_raw, kd.lev.del_raw, kd.lev.dup_raw, kd.RDmedian, ctx->nb_keys.p, d_rawmin, grid_chain(ctx), d_g, &ex, nullptr, st); }
+    { Timer t(ctx, "nb_apply"); launch_nb_apply(kd.d_binsum, nb, kd.K, ctx->nb_keys.p, ctx->tnb.as<float>(), &fl, st); }
+  } else {
+    Timer t(ctx, "nb_keys_masked");
+    launch_nb_keys(kd.d_binsum, d_mask, nb, kd.m, kd.K, kd.r, kd.lev.med_raw, kd.lev.del_raw, kd.lev.dup_raw, kd.RDmedian, ctx->nb_keys.p, d_rawmin, grid_chain(ctx), d_g, &ex, &fl, st);
+  }
+  *out = slot;
+  return RSI_OK;
+}
+
 // what grid_median() would have returned for this record (same tests, same order, same messages); the selection's own
 // description is needed for the degenerate case (its mean, on the host)
 struct Selection { const float* d_x; const int32_t* d_mask; int64_t nb; int use_abs; double center; };
@@ -649,7 +685,7 @@ int rsi_filterstatus(rsi_ctx* ctx, const float* d_T, const int32_t* d_st1, int32
 // rsicnvnbn (rsi.cpp:1262-1360) / rsicnvmed (rsi.cpp:1402-1501) around the device scan.  `first` = the record the quantile
 // chain in front of the first pass leaves in the mailbox (issued by the caller, behind the transform).
 int run_scan(rsi_ctx* ctx, const rsi_params& P, bool use_med, const float* d_T, int64_t nb, double RDmedian,
-             double factor, int LmaxBase, ChainOut* first, double nb_med_raw, double nb_del_raw, double nb_dup_raw, ScanOut& out) {
+             double factor, int LmaxBase, ChainOut*& first, double nb_med_raw, double nb_del_raw, double nb_dup_raw, NbKeyed* keyed, ScanOut& out) {
   const int32_t* d_medint = ctx->binmed.as<int32_t>();
   double tmedian, absmed;
   uint64_t cnt;
@@ -658,6 +694,14 @@ int run_scan(rsi_ctx* ctx, const rsi_params& P, bool use_med, const float* d_T, 
   {
     Phase ph(ctx, "scan.quantiles");
     HIPCHK(CTX_SYNC());
+    if (keyed && keyed->K && (first->g[0].flags & kGridDeclined)) {   // a bin sum outside the table (cannot happen under a cap): the chain of launches
+      ctx->phases.push_back({"nb.keyed declined", 1.0});
+      rsih::NbLevels lev;
+      if ((rc = nb_transform(ctx, keyed->d_binsum, nb, keyed->m, keyed->ncompact, RDmedian, keyed->r, lev, nullptr)) != RSI_OK) return rc;
+      if ((rc = grid_pair_issue(ctx, d_T, nullptr, nb, true, 0.0, true, 0, &first)) != RSI_OK) return rc;
+      keyed->K = 0;
+      HIPCHK(CTX_SYNC());
+    }
     const GridMedian* g = first->g;
     if ((!use_med && (g[0].flags & kGridTooWide)) || (g[1].flags & kGridTooWide)) {   // host-driven path, any range
       GateShared gs(ctx);
@@ -720,8 +764,14 @@ int run_scan(rsi_ctx* ctx, const rsi_params& P, bool use_med, const float* d_T, 
   double tmed2;
   uint64_t k = 0;
   ChainOut* second = nullptr;
-  if ((rc = grid_pair_issue(ctx, d_T, d_st1f, nb, true, 0.0, false, 1, &second)) != RSI_OK) return rc;
+  const bool keyed2 = keyed && keyed->K && Lmax <= kMaxL;
+  if ((rc = keyed2 ? nb_keyed_issue(ctx, *keyed, d_st1f, nb, 1, &second) : grid_pair_issue(ctx, d_T, d_st1f, nb, true, 0.0, false, 1, &second)) != RSI_OK) return rc;
   HIPCHK(CTX_SYNC());
+  if (keyed2 && (second->g[0].flags & kGridDeclined)) {
+    ctx->phases.push_back({"nb.keyed declined", 1.0});
+    if ((rc = grid_pair_issue(ctx, d_T, d_st1f, nb, true, 0.0, false, 1, &second)) != RSI_OK) return rc;
+    HIPCHK(CTX_SYNC());
+  }
   const GridMedian* g2 = second->g;
   {
     GateShared gs_q2(ctx);
@@ -765,6 +815,7 @@ struct PerBase {
   size_t res_vals = 0;               // values covered by the residue-class histogram
   std::vector<uint32_t> hres_all;    // BinAccum header + [value][MAD residue class] counts of the compacted depth
   double RDmedian = 0;
+  int32_t capval = 0; bool capped = false;   // the cap of the compacted depth, where one exists: a bin's sum is at most m * capval
   bool host_stats = false;           // depths of 65 536 and more in the compacted array: the statistics came from the array itself
   double mads[31] = {};              // ... and so did the 31 subsamples' MADs (bin_level_stages)
 };
@@ -1242,6 +1293,7 @@ int per_base_phase(rsi_ctx* ctx, const rsi_params& P, const int32_t* d_depth, co
     S.RDsd = cs.sd;
     S.RDmedian = RDmed;
     pb.host_stats = true;
+    pb.capval = capval; pb.capped = want_cap;
     pb.ncompact = ncompact; pb.nb = nb; pb.res_vals = 0; pb.RDmedian = RDmed;
     return RSI_OK;
   }
@@ -1250,6 +1302,7 @@ int per_base_phase(rsi_ctx* ctx, const rsi_params& P, const int32_t* d_depth, co
   const double RDmedian = cs.median;
   S.RDsd = cs.sd;
   S.RDmedian = RDmedian;
+  pb.capval = capval; pb.capped = want_cap;
   pb.ncompact = ncompact; pb.nb = nb; pb.res_vals = res_vals; pb.RDmedian = RDmedian;
   pb.hres_all = std::move(hres_all);
   return RSI_OK;
@@ -1296,10 +1349,19 @@ int bin_level_stages(rsi_ctx* ctx, const rsi_params& P, int64_t n, rsi_result* r
     // ---- A10: NB transform (K5): nb_transform ----
     GridMedian* d_g = reinterpret_cast<GridMedian*>(small + kOffGrid);
     rsih::NbLevels lev;
-    if ((rc = nb_transform(ctx, ctx->binsum.as<int64_t>(), nb, P.m, ncompact, RDmedian, r, lev, nullptr)) != RSI_OK) return rc;
+    // the keyed form where a cap bounds the bin sums (pipeline_steps.h); RSI_HOT_NB_KEYED=0: the chain of launches (A/B runs; same results)
+    NbKeyed keyed;
+    const int64_t nkeys = pb.capped ? rsih::nb_key_count(P.m, pb.capval) : 0;
+    if (!env_off("RSI_HOT_NB_KEYED") && rsih::nb_keyed_applies(P.trans == 0, pb.capped && pb.capval >= 0, nkeys, nb, LmaxBase > kMaxL)) {
+      keyed.K = nkeys; keyed.d_binsum = ctx->binsum.as<int64_t>(); keyed.m = P.m; keyed.ncompact = ncompact; keyed.r = r; keyed.RDmedian = RDmedian;
+      keyed.lev = lev = rsih::nb_reference_levels(RDmedian, P.m, r);
+      ctx->phases.push_back({"nb.keyed", 1.0});
+    } else {
+      if ((rc = nb_transform(ctx, ctx->binsum.as<int64_t>(), nb, P.m, ncompact, RDmedian, r, lev, nullptr)) != RSI_OK) return rc;
+      ctx->have_nb = true;
+    }
     const double med_raw = lev.med_raw, del_raw = lev.del_raw, dup_raw = lev.dup_raw;
     bool nb_planned = true;   // d_g[0] holds the grid of the NB values' median, its buckets are clear
-    ctx->have_nb = true;
 
     ph_nb.stop();
     gs_nb.release();
@@ -1334,11 +1396,15 @@ int bin_level_stages(rsi_ctx* ctx, const rsi_params& P, int64_t n, rsi_result* r
         nb_planned = false;   // the chains share the bucket array
         if ((rc2 = grid_pair_issue(ctx, d_T, nullptr, nb, false, RDmedian, true, 0, &first)) != RSI_OK) return rc2;
       } else {
-        d_T = ctx->tnb.as<float>();
-        if ((rc2 = grid_pair_issue(ctx, d_T, nullptr, nb, true, 0.0, nb_planned, 0, &first)) != RSI_OK) return rc2;
+        if (keyed.K) {
+          if ((rc2 = nb_keyed_issue(ctx, keyed, nullptr, nb, 0, &first)) != RSI_OK) return rc2;
+          ctx->have_nb = true;
+        }
+        d_T = ctx->tnb.as<float>();   // (taken behind the keyed form's issue: on a fresh context that is what allocates it)
+        if (!keyed.K && (rc2 = grid_pair_issue(ctx, d_T, nullptr, nb, true, 0.0, nb_planned, 0, &first)) != RSI_OK) return rc2;
         nb_planned = false;
       }
-      rc2 = run_scan(ctx, P, use_med, d_T, nb, RDmedian, factor, LmaxBase, first, med_raw, del_raw, dup_raw, so);
+      rc2 = run_scan(ctx, P, use_med, d_T, nb, RDmedian, factor, LmaxBase, first, med_raw, del_raw, dup_raw, use_med ? nullptr : &keyed, so);
       if (rc2 != RSI_OK) return rc2;
       S.nb_tmin = rsih::unkey_f32(~first->rawmin_inv);
       ctx->last_scan_med = use_med;
@@ -2482,6 +2548,72 @@ int rsi_hot_debug_grid_median(rsi_ctx* ctx, const float* x, const int32_t* mask,
       else rc = grid_result(ctx, g1, Selection{d_x, d_mask, nb, 1, med}, &mad, &c1);
       if (rc != RSI_OK) return rc;
     }
+  }
+  out[0] = med; out[1] = (double)c0; out[2] = mad; out[3] = (double)c1;
+  return RSI_OK;
+}
+
+// Test hook: the keyed form of the NB transform and its quantile chains (include/rsi_hot.h), through nb_keyed_issue -- what a run
+// calls -- and, where its record declines, through nb_transform + grid_pair_issue as run_scan falls back to them.  The records are
+// resolved as run_scan resolves them (host-driven medians for a range too wide, the MAD again around a degenerate median's mean).
+int rsi_hot_debug_nb_keyed(rsi_ctx* ctx, const int64_t* binsum, const int32_t* mask, int64_t nb, int m, int64_t K, double RDmedian, double r,
+                           float* T, double* out, int32_t* info) {
+  int rc;
+  if (!ctx || !binsum || !T || m < 1 || !(r > 0.0) || nb < 3) return fail(ctx, RSI_ERR_BAD_ARG, "bad argument");
+  if ((rc = grid_debug_enter(ctx, nb, out, info)) != RSI_OK) return rc;
+  info[0] = info[2] = -1; info[4] = 0;
+  ctx->ktimes.clear(); ctx->event_next = 0; ctx->phases.clear();
+  ctx->nb = nb; ctx->run_m = 0;
+  ctx->have_nb = false;   // tnb and binsum hold the caller's bins now
+  if (!rsih::nb_keyed_applies(true, true, K, nb, false)) { info[5] = -1; return RSI_OK; }
+  uint8_t* small = ctx->small.as<uint8_t>();
+  HIPCHK(ctx->binsum.ensure((size_t)nb * 8));
+  HIPCHK(hipMemcpyAsync(ctx->binsum.p, binsum, (size_t)nb * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemsetAsync(small + kOffRawMin, 0, 4, ctx->stream));   // "nothing seen", as the first kernel of a run leaves it
+  const int32_t* d_mask = nullptr;
+  if (mask) {
+    HIPCHK(ctx->status1f.ensure((size_t)nb * 4));
+    HIPCHK(hipMemcpyAsync(ctx->status1f.p, mask, (size_t)nb * 4, hipMemcpyHostToDevice, ctx->stream));
+    d_mask = ctx->status1f.as<int32_t>();
+  }
+  NbKeyed kd;
+  kd.K = K; kd.d_binsum = ctx->binsum.as<int64_t>(); kd.m = m; kd.ncompact = nb * m; kd.r = r; kd.RDmedian = RDmedian;
+  kd.lev = rsih::nb_reference_levels(RDmedian, m, r);
+  ChainOut* co = nullptr;
+  if ((rc = nb_keyed_issue(ctx, kd, nullptr, nb, -1, &co)) != RSI_OK) return rc;
+  HIPCHK(CTX_SYNC());
+  info[5] = 1;
+  const float* d_x = ctx->tnb.as<float>();
+  if (co->g[0].flags & kGridDeclined) {
+    info[5] = 0;
+    rsih::NbLevels lev;
+    if ((rc = nb_transform(ctx, kd.d_binsum, nb, m, kd.ncompact, RDmedian, r, lev, nullptr)) != RSI_OK) return rc;
+    if ((rc = grid_pair_issue(ctx, d_x, nullptr, nb, true, 0.0, true, -1, &co)) != RSI_OK) return rc;
+    if (d_mask && (rc = grid_pair_issue(ctx, d_x, d_mask, nb, true, 0.0, false, -1, &co)) != RSI_OK) return rc;
+    HIPCHK(CTX_SYNC());
+  } else if (d_mask) {
+    if ((rc = nb_keyed_issue(ctx, kd, d_mask, nb, -1, &co)) != RSI_OK) return rc;
+    HIPCHK(CTX_SYNC());
+    if (co->g[0].flags & kGridDeclined) return fail(ctx, RSI_ERR_INTERNAL, "the masked keyed form declined sums the unmasked one took");
+  }
+  const GridMedian g0 = co->g[0], g1 = co->g[1];
+  const float tmin = rsih::unkey_f32(~co->rawmin_inv);
+  HIPCHK(hipMemcpyAsync(T, ctx->tnb.p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(CTX_SYNC());
+  grid_debug_record(g0, info);
+  grid_debug_record(g1, info + 2);
+  memcpy(&info[4], &tmin, 4);
+  double med = 0, mad = 0;
+  uint64_t c0 = 0, c1 = 0;
+  if ((g0.flags | g1.flags) & kGridTooWide) {
+    info[6] = 2;
+    if ((rc = grid_median(ctx, d_x, d_mask, nb, 0, 0.0, &med, &c0)) != RSI_OK) return rc;
+    if ((rc = grid_median(ctx, d_x, d_mask, nb, 1, med, &mad, &c1)) != RSI_OK) return rc;
+  } else {
+    if ((rc = grid_result(ctx, g0, Selection{d_x, d_mask, nb, 0, 0.0}, &med, &c0)) != RSI_OK) return rc;
+    if (g0.flags & kGridDegenerate) { info[6] = 1; rc = grid_median(ctx, d_x, d_mask, nb, 1, med, &mad, &c1); }
+    else rc = grid_result(ctx, g1, Selection{d_x, d_mask, nb, 1, med}, &mad, &c1);
+    if (rc != RSI_OK) return rc;
   }
   out[0] = med; out[1] = (double)c0; out[2] = mad; out[3] = (double)c1;
   return RSI_OK;

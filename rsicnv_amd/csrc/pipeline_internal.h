@@ -233,6 +233,7 @@ struct rsi_ctx {
   DevBuf cand_jobs, cand_chains, cand_outs, cand_i32, cand_i64, cand_mid, cand_hist;   // candidate tests on the device (kernels_cand.hip)
   DevBuf sharpen_ws;          // workspace of k_sharpen_edges, cleared when (re)allocated
   DevBuf fs_ws, fs_out;       // filterstatus' level sums on the device (kernels_fs.hip)
+  DevBuf nb_keys;             // the keyed NB form's counters, table and slot list (kernels.h: nb_keys_workspace_bytes), cleared when allocated
   DevBuf scan_tiles;          // tiles the scan's detection pass lists for the exact sweep
   DevBuf scan_ws;             // the exact sweep's tiles in device memory, for scans too long for LDS (scan_tile_workspace_bytes)
   DevBuf joint_tot;           // K2j's folded joint histogram [GC count][depth byte] + escapes

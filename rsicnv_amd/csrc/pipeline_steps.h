@@ -153,6 +153,19 @@ inline NbScaled nb_scaled_levels(double tmin, double nb_med_raw, double nb_del_r
   return NbScaled{(float)((nb_del_raw - tmin) / med_nbt * RDmedian), (float)(med_nbt / med_nbt * RDmedian)};
 }
 
+// ---- the keyed form of the NB transform and its quantile chains (kernels.h: launch_nb_keys) ------------------------------------
+// A capped depth makes a bin's sum an integer in [0, m * capval]: K = m * capval + 1 possible sums.  The keyed form keeps a counter
+// and a table entry per possible sum and its last workgroup reads them all, 128 a thread at the limit of 2^15; the first 2^14 are
+// counted in 32 KB of LDS.  -m 101 -cap 4 at 30x gives 12 100 - 12 600 sums and is inside both; 2^15 leaves the same chromosome
+// room up to 80x, and beyond it (deep coverage, wide bins) a bin sum spreads over so many values that the array passes are no
+// longer the smaller part of the work: the chain of launches stays.
+constexpr int64_t kNbKeyLimit = 1 << 15;
+inline int64_t nb_key_count(int m, int32_t capval) { return (int64_t)m * (int64_t)capval + 1; }
+// nb_route: the NB scan alone (no -MED scan shares the bucket array); capped: a cap exists; long_scan: the scan's long form
+inline bool nb_keyed_applies(bool nb_route, bool capped, int64_t K, int64_t nb, bool long_scan) {
+  return nb_route && capped && K >= 1 && K <= kNbKeyLimit && nb >= 8 && !long_scan;
+}
+
 // ---- scan parameters (rsicnvnbn, rsi.cpp:1262-1360 / rsicnvmed, rsi.cpp:1402-1501) ------------------------------------------------
 struct Lamda { double tsigma, tlamda; };
 inline Lamda lamda_from_mad(double absmed, double factor, double target) {

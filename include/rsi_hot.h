@@ -691,7 +691,8 @@ int64_t rsi_hot_fetch_i64(rsi_ctx* ctx, const char* name, int64_t* out, int64_t 
 
 /* Test hook: filterstatus' per-level sums (rsi.cpp:967-976: float accumulation in index order per status level) of HOST arrays
  * T[nb], status[nb] (values in [-Lmax, Lmax]) through the device's exact parallel form; sums / counts: 2 Lmax + 1 entries, index
- * = level + Lmax.  counts[Lmax] == -1: the device declined the input (the pipeline then runs the sequential loop itself). */
+ * = level + Lmax.  counts[Lmax] == -1: the device declined the input (the pipeline then runs the sequential loop itself).  A status
+ * value outside [-Lmax, Lmax]: RSI_ERR_BAD_ARG, checked on the host before anything is launched. */
 int rsi_hot_debug_level_sums(rsi_ctx* ctx, const float* T, const int32_t* status, int64_t nb, int Lmax, float* sums, int32_t* counts);
 /* Test hook: one scan pass (rsistatus) over host arrays with the caller's thresholds; status[nb] out, info[4] = tiles the
  * detection pass listed, trimming walks that left the array, inexact-threshold flags, 0. */

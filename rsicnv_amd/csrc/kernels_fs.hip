@@ -6,11 +6,14 @@
 // x = X u + r (0 <= r < u), fl(s + x) = (S + X + c) u where c = 0 / 1 for r below / above u/2 and, on a tie, whatever
 // makes the result even.  So every element is a function S -> S + a[S & 1] with two small constants, such functions
 // compose into functions of the same form, and the composition over a chunk of bins is an ordered reduction.  The binade
-// the sum is in when it reaches a chunk is not known in advance, but it is known to within one: the float sum of at
-// most 2^22 non-negative terms stays within 15 % of their exact sum, so two candidate binades per chunk cover it.  A
-// last, sequential pass over the CHUNKS applies each chunk's function in one step when the sum stays inside the
-// candidate binade (values are >= 0: if it is inside at the end it never left), and walks the chunk's bins one by one
-// when it does not -- the ~25 binade crossings of a chromosome, and whatever precedes the first unmarked bin.
+// the sum is in when it reaches a chunk is not known in advance, but it is guessed to within one from the exact sum of
+// the bins in front of it: while the float sum stays within 15 % of that (a few million terms of one magnitude do), two
+// candidate binades per chunk cover it.  A last, sequential pass over the CHUNKS applies each chunk's function in one
+// step when the sum is in a candidate binade and stays inside it (values are >= 0: if it is inside at the end it never
+// left), and stages the chunk's bins when it does not -- the ~25 binade crossings of a chromosome, whatever precedes
+// the first unmarked bin, and every chunk whose candidates miss the sum's binade: nothing limits the terms of a level,
+// and a float sum that has stopped growing (2^24 + 1 + 1 + ...) falls behind its exact sum without bound.  A miss is
+// not an error: a saturated increment stands in for the chunk's function, so the chunk is staged -- correct, and slower.
 //
 // The unmarked level (almost every bin) goes that way.  The marked levels hold few bins each: the marked bins are
 // compacted in order, and one thread per level walks the compact list.
@@ -153,8 +156,10 @@ __global__ __launch_bounds__(kThreads) void k_fs_chunk_fns(const float* __restri
   extern __shared__ unsigned int s_lev[];   // [2 Lmax + 1]: this chunk's marked bins per level
   for (int e = threadIdx.x; e < 2 * Lmax + 1; e += kThreads) s_lev[e] = 0;
   __syncthreads();
-  // candidate binades: the float sum that reaches the chunk lies within 15 % of the exact prefix P (at most 2^22 terms, each
-  // addition off by at most 2^-24 of the sum); the binade of 0.85 P and the one above it cover [0.85 P, 1.15 P]
+  // candidate binades: while the float sum that reaches the chunk lies within 15 % of the exact prefix P (each addition is off by
+  // at most 2^-24 of the sum), the binade of 0.85 P and the one above it cover it.  Nothing guarantees that -- a level may hold any
+  // number of terms -- and nothing needs to: the last workgroup takes a saturated increment for a chunk whose candidates miss the
+  // sum's binade and stages it
   const double P = cpre[blockIdx.x];
   int ue0 = -200;
   if (P > 0.0) { int ex; (void)frexp(P * 0.85, &ex); ue0 = (ex - 1) - 23; }   // 0.85 P in [2^(ex-1), 2^ex)
@@ -205,16 +210,6 @@ __global__ __launch_bounds__(kThreads) void k_fs_chunk_fns(const float* __restri
 // out: [2 Lmax + 1] float sums then [2 Lmax + 1] int counts (index = level + Lmax); the workgroup that finishes last copies
 // them to mapped host memory.  A count of -1 at the unmarked level tells the host to do the sums itself (more marked bins
 // than the compact list holds, or a negative / non-finite value: the integer-step argument needs x >= 0).
-__device__ inline bool fs_apply(float& s, int ue, StepFn f) {   // one step of a function valid for unit exponent ue; false: not applicable
-  const uint32_t bits = __float_as_uint(s);
-  const int ex = (int)((bits >> 23) & 0xff);
-  if (ex == 0 || ex == 255 || ex - 150 != ue) return false;
-  const long long S = (long long)((bits & 0x7fffffu) | 0x800000u);
-  const long long S2 = S + ((S & 1) ? f.a1 : f.a0);
-  if (S2 >= (1ll << 24)) return false;                          // the sum would leave the binade
-  s = __uint_as_float(((uint32_t)ex << 23) | ((uint32_t)S2 & 0x7fffffu));
-  return true;
-}
 __global__ __launch_bounds__(kThreads) void k_fs_level_sums(const float* __restrict__ T, const int32_t* __restrict__ status, int64_t nb,
                                                             int nchunks, const ChunkFn* __restrict__ fns, const int32_t* __restrict__ clist_s,
                                                             const float* __restrict__ clist_t, const int32_t* __restrict__ total_marked,

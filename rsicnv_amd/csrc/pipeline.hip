@@ -1889,6 +1889,9 @@ int64_t rsi_hot_fetch_i64(rsi_ctx* ctx, const char* name, int64_t* out, int64_t 
 // Test hook: filterstatus' per-level sums of host arrays through the device kernels (include/rsi_hot.h).
 int rsi_hot_debug_level_sums(rsi_ctx* ctx, const float* T, const int32_t* status, int64_t nb, int Lmax, float* sums, int32_t* counts) {
   if (!ctx || !T || !status || !sums || !counts || nb <= 0 || Lmax < 1 || Lmax > kMaxL) return fail(ctx, RSI_ERR_BAD_ARG, "bad argument");
+  // a level outside the range is skipped by the level counters and still enters the compact list: the counts would not add up
+  for (int64_t i = 0; i < nb; ++i)
+    if (status[i] < -Lmax || status[i] > Lmax) return fail(ctx, RSI_ERR_BAD_ARG, "status values must lie in [-Lmax, Lmax]");
   HIPCHK(hipSetDevice(ctx->device));
   if (!ctx_enter(ctx)) return RSI_ERR_HIP;
   mailbox_reset(ctx);
